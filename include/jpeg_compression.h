@@ -1,5 +1,6 @@
 /*
- * jpeg_compression.h -- C-ABI of the MI355X-native BMP -> grayscale baseline-JPEG encoder.
+ * jpeg_compression.h -- C-ABI of the MI355X-native BMP -> baseline-JPEG encoder: grayscale (the reference's output) and
+ * colour (YCbCr 4:4:4 / 4:2:0 in three non-interleaved scans, jpegamd_encode_color_async).
  *
  * This is the drop-in boundary for the reference's encode path
  * (strbac-damjan/jpeg-image-compression).  Every entry point cites the reference interface
@@ -63,14 +64,17 @@ extern "C" {
  */
 #define JPEGAMD_ORDER_BGR 0
 #define JPEGAMD_ORDER_RGB 1
+/* One byte per pixel: `pixels` holds the luma itself (row_stride >= width); the output is a grayscale file.  Accepted by
+ * jpegamd_encode_async, jpegamd_encode_batch_async and jpegamd_debug_stages (not by the colour entry points). */
+#define JPEGAMD_ORDER_GRAY 2
 
 typedef struct JpegAmdImage {
     const void *pixels;    /* DEVICE pointer to the first stored row */
     int32_t width;         /* original (unpadded) width,  1..65535 */
     int32_t height;        /* original (unpadded) height, 1..65535 */
-    int32_t row_stride;    /* bytes between stored rows (>= 3*width) */
+    int32_t row_stride;    /* bytes between stored rows (>= 3*width; GRAY: >= width) */
     int32_t bottom_up;     /* 1: stored row 0 is the LAST image row (BMP default) */
-    int32_t channel_order; /* JPEGAMD_ORDER_BGR or JPEGAMD_ORDER_RGB */
+    int32_t channel_order; /* JPEGAMD_ORDER_BGR, JPEGAMD_ORDER_RGB or JPEGAMD_ORDER_GRAY */
     int32_t quality;       /* 0 or 50: the reference's only table
                               (natural_c/src/core/jpeg_tables.c:3-12); 1..100 otherwise =
                               libjpeg scaling of that table (extension) */
@@ -131,6 +135,27 @@ int32_t jpegamd_encode_batch_async(JpegAmdEncoder *enc, const JpegAmdImage *imgs
                                    uint64_t out_capacity, uint64_t *const *out_sizes_dev, int32_t with_container,
                                    void *stream);
 
+/* ---- Colour (no reference counterpart: the reference writes grayscale only) ------------------------------------------
+ * A baseline JFIF file with three components in three NON-interleaved scans, Y, Cb, Cr (colour scans):
+ *   Y  = (77 R + 150 G + 29 B) >> 8              (the grayscale path's luma; its scan is byte for byte the grayscale file's)
+ *   Cb = (32768 - 43 R - 85 G + 128 B) >> 8      Cr = (32768 + 128 R - 107 G - 21 B) >> 8
+ *   4:2:0: chroma planes of ceil(W/2) x ceil(H/2), sample = (a + b + c + d + 2) >> 2 over 2 x 2 pixels (last column / row
+ *   replicated); 4:4:4: W x H.  Chroma: T.81 Annex K tables K.2 (quantisation, scaled for `quality` like the luma table),
+ *   K.4 / K.6 (Huffman).  No restart markers.
+ * jpegamd_encode_color_async always writes the whole file (prefix, three scans, EOI) into out_dev, stream-ordered, with no host
+ * synchronisation inside the call.  A GRAY image or another subsampling value: JPEGAMD_ERR_ARG.  If the file does not fit
+ * out_capacity, jpegamd_encoder_finish returns JPEGAMD_ERR_HUFF_CAPACITY, *out_size_dev is 0 and nothing is written past
+ * out_capacity.  Its statistics are sums over the three scans; ns_total spans the whole call.
+ * The context allocates its colour scratch (chroma constants, the two planes, the chroma scans) on its first colour call, sized
+ * for that picture at 4:4:4 and grown when a later colour call needs more; a context that never encodes colour allocates
+ * nothing for it. */
+#define JPEGAMD_SUBSAMPLE_444 1
+#define JPEGAMD_SUBSAMPLE_420 2
+/* Upper bound on the colour file's bytes (every block at the 1723-bit chroma worst case, every byte stuffed); 0 for bad args. */
+uint64_t jpegamd_max_jfif_bytes_color(int32_t width, int32_t height, int32_t subsampling);
+int32_t jpegamd_encode_color_async(JpegAmdEncoder *enc, const JpegAmdImage *img, int32_t subsampling, void *out_dev,
+                                   uint64_t out_capacity, uint64_t *out_size_dev, void *stream);
+
 /* Which kernels follow k_tile_encode for whole pictures (no reference counterpart: a tuning knob, results are byte-identical).
  *   PAIR    k_segment_merge + k_finalize: the tiles' bit strings joined per segment, then stitched behind a kernel boundary;
  *   STITCH  k_stitch: one pass, the offsets handed from workgroup to workgroup inside the launch (decoupled look-back);
@@ -182,6 +207,14 @@ int32_t jpegamd_debug_quant_table(int32_t quality, uint8_t *table);
 
 /* Constants of the fast quantiser: qmul, qthr, bias float[64] by ZIGZAG position; the rigorous guard band delta, double[64], by raster k. */
 int32_t jpegamd_debug_mfma_consts(int32_t quality, float *qmul, float *qthr, float *bias, double *delta);
+/* The same for the colour files' chroma table: the table (raster order) and its constants (every output pointer may be NULL;
+ * zoff / qadd as in jpegamd_debug_mfma_offsets). */
+int32_t jpegamd_debug_chroma_quant_table(int32_t quality, uint8_t *table);
+int32_t jpegamd_debug_chroma_mfma_consts(int32_t quality, float *qmul, float *qthr, float *bias, double *delta, float *zoff,
+                                         float *qadd);
+/* Per-kernel durations of a PROFILED colour encode in ring slot `slot` (jpegamd_encoder_set_profiling), ns[11]: k_chroma_planes,
+ * then for Y, Cb, Cr the transform / merge / finalize kernels (k_stitch: in the finalize entry, merge 0), then k_append_scans. */
+int32_t jpegamd_debug_color_profile(JpegAmdEncoder *enc, int32_t slot, uint64_t *ns);
 /* Zero thresholds of the coefficient groups ([group 0..3][lane half 0..1], group G of half h = zigzag 16G+8h .. +7): a tile
  * whose hi-chain LUT sums all stay below grp_thr skips that group's quantiser entirely; lo_bound (may be NULL) is the largest
  * magnitude the lo chain can add to a site of the group -- grp_thr has it taken off. */
@@ -282,6 +315,9 @@ bool saveJPEGGrayscale(const char *filename, const BMPImage *img);
  * Returns the JFIF size, or a negative JPEGAMD_ERR_* code. */
 int64_t jpegamd_encode_bmp_memory(const uint8_t *bmp, uint64_t bmp_len, int32_t quality,
                                   uint8_t *out, uint64_t out_cap);
+/* ... the colour file (jpegamd_encode_color_async) of the same BMP; subsampling JPEGAMD_SUBSAMPLE_444 or _420. */
+int64_t jpegamd_encode_bmp_memory_color(const uint8_t *bmp, uint64_t bmp_len, int32_t quality, int32_t subsampling,
+                                        uint8_t *out, uint64_t out_cap);
 
 /* ---- One image sharded over several GPUs by block rows (no reference counterpart) --------
  * Blocks are independent up to the entropy stage, which couples them only through the previous

@@ -57,7 +57,11 @@ struct JpegAmdEncoder {
     int prefix_w = -1, prefix_h = -1, prefix_q = -1;
     // profiling: a ring of event quadruples so callers can time many async encodes and read
     // the per-kernel durations after ONE synchronisation
-    struct EventSet { hipEvent_t ev[6]; bool merged; };   // begin / end of k_tile_encode, [k_segment_merge,] k_stitch or k_finalize (the kernels' own timestamps)
+    struct EventSet {
+        hipEvent_t ev[6]; bool merged;   // begin / end of k_tile_encode, [k_segment_merge,] k_stitch or k_finalize (the kernels' own timestamps)
+        // a colour encode (made on the slot's first one): k_chroma_planes, 3 x the six above, k_append_scans
+        std::vector<hipEvent_t> cev; bool color = false; bool cmerged[3] = {false, false, false};
+    };
     std::vector<EventSet> ring;
     uint64_t calls = 0;          // encodes enqueued since profiling was (re)enabled
     int last_slot = -1;
@@ -66,6 +70,21 @@ struct JpegAmdEncoder {
     hipStream_t last_stream = nullptr;
     bool pending = false;
     bool timed = false;
+    bool last_color = false;            // the last call was a colour encode: its statistics are summed already (k_append_scans)
+    // Colour (jpegamd_encode_color_async): nothing of this is allocated before the context's first colour call.
+    struct Color {
+        MfmaTables *tables_dev = nullptr;   // the chroma table's constants (a second set: no re-upload between the scans)
+        uint32_t *code_tab = nullptr, *huff = nullptr;
+        uint8_t *hdr = nullptr;             // [0, kColorPrefixMax) the prefix up to the Y scan; then the SOS of Cb and of Cr
+        uint64_t *scan_size = nullptr;      // [3]
+        ScanStats *scan_stats = nullptr;    // [3]
+        uint8_t *planes = nullptr;          // Cb, then Cr
+        uint8_t *scans = nullptr;           // the Cb part, then the Cr part (each scan_cap bytes)
+        size_t planes_cap = 0, scan_cap = 0;
+        int cur_quality = -1;
+        int hdr_w = -1, hdr_h = -1, hdr_q = -1, hdr_sub = -1;
+        int hdr_len = 0;
+    } color;
 };
 
 static int segs_for(int w, int h, int *bw, int *bh, int *spr, int seg_tiles = kSegTiles) {
@@ -136,6 +155,46 @@ extern "C" int32_t jpegamd_debug_cos_lut(float *lut /*[8][8]: COS_LUT[x][u]*/) {
     if (!lut) return JPEGAMD_ERR_ARG;
     cos_lut_copy(lut);
     return JPEGAMD_OK;
+}
+
+extern "C" int32_t jpegamd_debug_chroma_quant_table(int32_t quality, uint8_t *table) {
+    if (!table) return JPEGAMD_ERR_ARG;
+    chroma_quant_table_for_quality(quality, table);
+    return JPEGAMD_OK;
+}
+
+extern "C" int32_t jpegamd_debug_chroma_mfma_consts(int32_t quality, float *qmul, float *qthr, float *bias, double *delta, float *zoff,
+                                                    float *qadd) {
+    uint8_t t[64];
+    MfmaTables *mt = new (std::nothrow) MfmaTables;
+    if (!mt) return JPEGAMD_ERR_HIP;
+    double d[64];
+    chroma_quant_table_for_quality(quality, t);
+    derive_mfma_tables(t, mt, d);
+    if (qmul) std::memcpy(qmul, mt->qmul, sizeof(mt->qmul));
+    if (qthr) std::memcpy(qthr, mt->qthr, sizeof(mt->qthr));
+    if (bias) std::memcpy(bias, mt->bias, sizeof(mt->bias));
+    if (delta) std::memcpy(delta, d, sizeof(d));
+    if (zoff) std::memcpy(zoff, mt->zoff, sizeof(mt->zoff));
+    if (qadd) std::memcpy(qadd, mt->qadd, sizeof(mt->qadd));
+    delete mt;
+    return JPEGAMD_OK;
+}
+
+static void chroma_dims(int w, int h, int sub, int *cw, int *ch) {
+    *cw = sub == JPEGAMD_SUBSAMPLE_420 ? (w + 1) / 2 : w;
+    *ch = sub == JPEGAMD_SUBSAMPLE_420 ? (h + 1) / 2 : h;
+}
+
+// One scan of nb blocks at the chroma worst case, every byte stuffed, its flush byte.
+static uint64_t scan_bound(uint64_t nb) { return 2 * ((nb * kMaxBlockBitsColor + 7) / 8 + 1); }
+static uint64_t blocks_of(int w, int h) { return (uint64_t)((w + 7) / 8) * (uint64_t)((h + 7) / 8); }
+
+extern "C" uint64_t jpegamd_max_jfif_bytes_color(int32_t width, int32_t height, int32_t subsampling) {
+    if (width <= 0 || height <= 0 || (subsampling != JPEGAMD_SUBSAMPLE_444 && subsampling != JPEGAMD_SUBSAMPLE_420)) return 0;
+    int cw, ch;
+    chroma_dims(width, height, subsampling, &cw, &ch);
+    return kColorPrefixMax + 2 * kSosBytes + 2 + scan_bound(blocks_of(width, height)) + 2 * scan_bound(blocks_of(cw, ch)) + 16;
 }
 
 extern "C" uint64_t jpegamd_max_jfif_bytes(int32_t width, int32_t height) {
@@ -227,7 +286,9 @@ extern "C" int32_t jpegamd_encoder_destroy(JpegAmdEncoder *e) {
     hipFree(e->seg.words); hipFree(e->seg.bits); hipFree(e->seg.syms); hipFree(e->seg.exact); hipFree(e->seg.edge); hipFree(e->seg.ffin); hipFree(e->seg.grp_bits); hipFree(e->seg.grp_ff);
     hipFree(e->huff); hipFree(e->prefix); hipFree(e->stats_dev); hipFree(e->tables_dev);
     hipFree(e->tile_head); hipFree(e->tile_over); hipFree(e->code_tab); hipFree(e->tile_ctr); hipFree(e->desc); hipFree(e->stamps_dev);
-    for (auto &set : e->ring) for (auto &ev : set.ev) if (ev) hipEventDestroy(ev);
+    hipFree(e->color.tables_dev); hipFree(e->color.code_tab); hipFree(e->color.huff); hipFree(e->color.hdr); hipFree(e->color.scan_size);
+    hipFree(e->color.scan_stats); hipFree(e->color.planes); hipFree(e->color.scans);
+    for (auto &set : e->ring) { for (auto &ev : set.ev) if (ev) hipEventDestroy(ev); for (auto &ev : set.cev) if (ev) hipEventDestroy(ev); }
     delete e->tables_host;
     delete e;
     return JPEGAMD_OK;
@@ -242,7 +303,7 @@ extern "C" int32_t jpegamd_encoder_set_pipeline(JpegAmdEncoder *e, int32_t pipel
 extern "C" int32_t jpegamd_encoder_set_profiling(JpegAmdEncoder *e, int32_t slots) {
     if (!e || slots < 0 || slots > 65536) return JPEGAMD_ERR_ARG;
     if (e->pending) HIP_TRY(hipStreamSynchronize(e->last_stream));
-    for (auto &set : e->ring) for (auto &ev : set.ev) if (ev) hipEventDestroy(ev);
+    for (auto &set : e->ring) { for (auto &ev : set.ev) if (ev) hipEventDestroy(ev); for (auto &ev : set.cev) if (ev) hipEventDestroy(ev); }
     e->ring.clear();
     e->ring.resize((size_t)slots);
     for (auto &set : e->ring) { set.merged = false; for (auto &ev : set.ev) HIP_TRY(hipEventCreate(&ev)); }
@@ -251,8 +312,39 @@ extern "C" int32_t jpegamd_encoder_set_profiling(JpegAmdEncoder *e, int32_t slot
     return JPEGAMD_OK;
 }
 
+static int32_t read_color_slot(JpegAmdEncoder *e, int slot, uint64_t ns[11]) {
+    const auto &set = e->ring[(size_t)slot];
+    const hipEvent_t *cev = set.cev.data();
+    float ms = 0;
+    const auto span = [&](int i0, int i1, uint64_t &out) -> int32_t {
+        HIP_TRY(hipEventElapsedTime(&ms, cev[i0], cev[i1]));
+        out = (uint64_t)((double)ms * 1e6);
+        return JPEGAMD_OK;
+    };
+    for (int i = 0; i < 11; ++i) ns[i] = 0;
+    if (int32_t rc = span(0, 1, ns[0])) return rc;
+    for (int c = 0; c < 3; ++c) {
+        const int b = 2 + 6 * c;
+        if (int32_t rc = span(b, b + 1, ns[1 + 3 * c])) return rc;
+        if (set.cmerged[c]) if (int32_t rc = span(b + 2, b + 3, ns[2 + 3 * c])) return rc;
+        if (int32_t rc = span(b + 4, b + 5, ns[3 + 3 * c])) return rc;
+    }
+    return span(20, 21, ns[10]);
+}
+
 static int32_t read_slot(JpegAmdEncoder *e, int slot, JpegAmdStats *stats) {
     if (slot < 0 || (size_t)slot >= e->ring.size()) return JPEGAMD_ERR_ARG;
+    if (e->ring[(size_t)slot].color) {            // sums over the three scans; the planes count as transform, the append as pack
+        uint64_t ns[11];
+        if (int32_t rc = read_color_slot(e, slot, ns)) return rc;
+        stats->ns_transform = ns[0] + ns[1] + ns[4] + ns[7];
+        stats->ns_entropy = ns[2] + ns[5] + ns[8];
+        stats->ns_pack = ns[3] + ns[6] + ns[9] + ns[10];
+        float ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, e->ring[(size_t)slot].cev[0], e->ring[(size_t)slot].cev[21]));
+        stats->ns_total = (uint64_t)((double)ms * 1e6);
+        return JPEGAMD_OK;
+    }
     hipEvent_t *ev = e->ring[(size_t)slot].ev;
     float ms = 0;
     HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1])); stats->ns_transform = (uint64_t)((double)ms * 1e6);
@@ -261,6 +353,11 @@ static int32_t read_slot(JpegAmdEncoder *e, int slot, JpegAmdStats *stats) {
     HIP_TRY(hipEventElapsedTime(&ms, ev[4], ev[5])); stats->ns_pack = (uint64_t)((double)ms * 1e6);
     HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[5])); stats->ns_total = (uint64_t)((double)ms * 1e6);     // first begin .. last end: includes the launch gaps
     return JPEGAMD_OK;
+}
+
+extern "C" int32_t jpegamd_debug_color_profile(JpegAmdEncoder *e, int32_t slot, uint64_t *ns) {
+    if (!e || !ns || slot < 0 || (size_t)slot >= e->ring.size() || !e->ring[(size_t)slot].color) return JPEGAMD_ERR_ARG;
+    return read_color_slot(e, slot, ns);
 }
 
 extern "C" int32_t jpegamd_encoder_profile(JpegAmdEncoder *e, int32_t slot, JpegAmdStats *stats) {
@@ -300,8 +397,9 @@ static bool context_fits(const JpegAmdEncoder *e, int w, int h) {
 static int32_t describe(const JpegAmdEncoder *e, const JpegAmdImage *img, ImageDesc *d, int seg_tiles = kSegTiles) {
     if (!img || !img->pixels || img->width <= 0 || img->height <= 0 || img->width > 65535 || img->height > 65535)
         return JPEGAMD_ERR_ARG;
-    if (img->row_stride < 3 * img->width) return JPEGAMD_ERR_ARG;
-    if (img->channel_order != JPEGAMD_ORDER_BGR && img->channel_order != JPEGAMD_ORDER_RGB) return JPEGAMD_ERR_ARG;
+    if (img->channel_order != JPEGAMD_ORDER_BGR && img->channel_order != JPEGAMD_ORDER_RGB && img->channel_order != JPEGAMD_ORDER_GRAY)
+        return JPEGAMD_ERR_ARG;
+    if (img->row_stride < (img->channel_order == JPEGAMD_ORDER_GRAY ? 1 : 3) * img->width) return JPEGAMD_ERR_ARG;
     d->pixels = (const uint8_t *)img->pixels;
     d->width = img->width; d->height = img->height; d->row_stride = img->row_stride;
     d->bottom_up = img->bottom_up ? 1 : 0;
@@ -325,22 +423,26 @@ static int32_t describe(const JpegAmdEncoder *e, const JpegAmdImage *img, ImageD
     return JPEGAMD_OK;
 }
 
+// What k_tile_encode reads for this image (kTileSrcChroma: set by the colour path alone).
+static int src_of(const JpegAmdImage *img) { return img->channel_order == JPEGAMD_ORDER_GRAY ? kTileSrcGray : kTileSrcRgb; }
+
 // k_tile_encode (+ the fault injection of the tests).
 static int launch_transform(JpegAmdEncoder *e, const ImageDesc &im, bool taps, int8_t *ty, int16_t *tzz, uint64_t *tmask,
-                            void *stream, hipEvent_t *ev = nullptr /*2: begin/end*/) {
+                            void *stream, hipEvent_t *ev = nullptr /*2: begin/end*/, int src = kTileSrcRgb) {
     TransformOutM to;
     std::memset(&to, 0, sizeof(to));
-    to.tables = e->tables_dev; to.stamps = e->stamps_dev;
+    const bool chroma = src == kTileSrcChroma;
+    to.tables = chroma ? e->color.tables_dev : e->tables_dev; to.stamps = e->stamps_dev;
     to.tap_y = ty; to.tap_zz = tzz; to.tap_mask = tmask;
-    to.tile_head = e->tile_head; to.tile_over = e->tile_over; to.code_tab = e->code_tab;
+    to.tile_head = e->tile_head; to.tile_over = e->tile_over; to.code_tab = chroma ? e->color.code_tab : e->code_tab;
     // Launches on one context are stream-ordered by contract (they share the scratch): launch i draws tickets from set
     // i % 2 and zeroes the other one for launch i + 1.
     to.tile_ctr = e->tile_ctr + (e->ctr_set ? 64 * 32 : 0);
     to.tile_ctr_next = e->tile_ctr + (e->ctr_set ? 0 : 64 * 32);
     const bool stamped = e->stamp_next && e->stamps_dev && !taps;
     e->stamp_next = false;
-    if (int err = stamped ? launch_tile_transform_stamped(im, to, taps, stream, ev ? (void *const *)ev : nullptr)
-                          : launch_tile_transform(im, to, taps, stream, (ev && !taps) ? (void *const *)ev : nullptr)) return err;
+    if (int err = stamped ? launch_tile_transform_stamped(im, to, taps, stream, ev ? (void *const *)ev : nullptr, src)
+                          : launch_tile_transform(im, to, taps, stream, (ev && !taps) ? (void *const *)ev : nullptr, src)) return err;
     if (im.tile_end > im.tile_begin) e->ctr_set ^= 1;      // (an empty range launches nothing)
     if (e->poison_tile >= 0) {                             // fault injection for the tests: a corrupt record must end in a status code
         if (e->poison_tile < e->max_tiles &&
@@ -353,12 +455,12 @@ static int launch_transform(JpegAmdEncoder *e, const ImageDesc &im, bool taps, i
 
 // k_tile_encode, then k_segment_merge (block-row shards, stage taps).
 static int launch_transform_and_entropy(JpegAmdEncoder *e, const ImageDesc &im, bool taps, int8_t *ty, int16_t *tzz, uint64_t *tmask,
-                                        void *stream, hipEvent_t *ev = nullptr /*4: begin/end of the two kernels*/) {
-    if (int err = launch_transform(e, im, taps, ty, tzz, tmask, stream, ev)) return err;
+                                        void *stream, hipEvent_t *ev = nullptr /*4: begin/end of the two kernels*/, int src = kTileSrcRgb) {
+    if (int err = launch_transform(e, im, taps, ty, tzz, tmask, stream, ev, src)) return err;
     MergeArgs ea;
     std::memset(&ea, 0, sizeof(ea));
     ea.tile_head = e->tile_head; ea.tile_over = e->tile_over;
-    ea.huff = e->huff; ea.num_segs = im.num_segs; ea.segs_per_row = im.segs_per_row; ea.tiles_per_row = im.tiles_per_row;
+    ea.huff = src == kTileSrcChroma ? e->color.huff : e->huff; ea.num_segs = im.num_segs; ea.segs_per_row = im.segs_per_row; ea.tiles_per_row = im.tiles_per_row;
     ea.seg_tiles = im.seg_tiles;
     ea.seg_begin = im.seg_begin; ea.seg_end = im.seg_end;
     ea.tiles_per_image = im.batch > 1 ? im.num_tiles : 0;
@@ -394,12 +496,21 @@ static bool use_stitch(const JpegAmdEncoder *e, int w, int h) {
     return segs_for(w, h, nullptr, nullptr, nullptr) >= kStitchAutoSegs;
 }
 
+// Where a scan of a colour file goes: its own header bytes in front, EOI or not, its own statistics record.
+struct ScanTarget {
+    const uint8_t *prefix;
+    int32_t prefix_len, write_eoi;
+    ScanStats *stats;
+    bool chroma;
+};
+
 // k_stitch over the tiles k_tile_encode left: whole images, one or a batch.
 static int run_stitch(JpegAmdEncoder *e, const ImageDesc &im, void *const *outs_dev, uint64_t out_capacity,
-                      uint64_t *const *out_sizes_dev, int32_t with_container, hipStream_t stream, hipEvent_t *ev = nullptr) {
+                      uint64_t *const *out_sizes_dev, int32_t with_container, hipStream_t stream, hipEvent_t *ev = nullptr,
+                      const ScanTarget *tgt = nullptr) {
     StitchArgs sa;
     std::memset(&sa, 0, sizeof(sa));
-    sa.tile_head = e->tile_head; sa.tile_over = e->tile_over; sa.huff = e->huff;
+    sa.tile_head = e->tile_head; sa.tile_over = e->tile_over; sa.huff = (tgt && tgt->chroma) ? e->color.huff : e->huff;
     sa.num_segs = im.num_segs; sa.segs_per_row = im.segs_per_row; sa.tiles_per_row = im.tiles_per_row;
     sa.seg_tiles = im.seg_tiles; sa.tiles_per_image = im.num_tiles;
     sa.batch = im.batch; sa.wgs_per_image = stitch_workgroups(im.num_segs);
@@ -417,11 +528,16 @@ static int run_stitch(JpegAmdEncoder *e, const ImageDesc &im, void *const *outs_
     sa.out_capacity = out_capacity; sa.stats = e->stats_dev; sa.status = &e->stats_dev->status;
     sa.prefix = e->prefix; sa.prefix_len = with_container ? JPEGAMD_JFIF_PREFIX_BYTES : 0;
     sa.write_eoi = with_container ? 1 : 0;
+    if (tgt) {
+        sa.prefix = tgt->prefix; sa.prefix_len = tgt->prefix_len; sa.write_eoi = tgt->write_eoi;
+        sa.stats = tgt->stats; sa.status = &tgt->stats->status;
+    }
     return launch_stitch(sa, stream, (void *const *)ev);
 }
 
 static int run_finalize(JpegAmdEncoder *e, const ImageDesc &im, void *out_dev, uint64_t out_capacity, uint64_t *out_size_dev,
-                        int32_t with_container, hipStream_t stream, hipEvent_t *ev = nullptr, bool groups_valid = false) {
+                        int32_t with_container, hipStream_t stream, hipEvent_t *ev = nullptr, bool groups_valid = false,
+                        const ScanTarget *tgt = nullptr) {
     FinalizeArgs fa;
     std::memset(&fa, 0, sizeof(fa));
     fa.seg = e->seg;
@@ -432,6 +548,7 @@ static int run_finalize(JpegAmdEncoder *e, const ImageDesc &im, void *out_dev, u
     fa.out[0] = (uint8_t *)out_dev; fa.out_capacity = out_capacity; fa.out_size[0] = out_size_dev; fa.stats = e->stats_dev;
     fa.prefix = e->prefix; fa.prefix_len = with_container ? JPEGAMD_JFIF_PREFIX_BYTES : 0;
     fa.write_eoi = with_container ? 1 : 0;
+    if (tgt) { fa.prefix = tgt->prefix; fa.prefix_len = tgt->prefix_len; fa.write_eoi = tgt->write_eoi; fa.stats = tgt->stats; }
     return launch_finalize(fa, stream, (void *const *)ev);
 }
 
@@ -464,10 +581,10 @@ extern "C" int32_t jpegamd_encode_rows_async(JpegAmdEncoder *e, const JpegAmdIma
     im.seg_begin = block_row_begin * im.segs_per_row;
     im.seg_end = block_row_end * im.segs_per_row;
     hipStream_t stream = (hipStream_t)stream_;
-    if (launch_transform_and_entropy(e, im, false, nullptr, nullptr, nullptr, stream, nullptr)) return JPEGAMD_ERR_HIP;
+    if (launch_transform_and_entropy(e, im, false, nullptr, nullptr, nullptr, stream, nullptr, src_of(img))) return JPEGAMD_ERR_HIP;
     e->last_segs = im.num_segs;
     e->last_stream = stream;
-    e->pending = true;
+    e->pending = true; e->last_color = false;
     e->timed = false;
     return JPEGAMD_OK;
 }
@@ -495,7 +612,7 @@ extern "C" int32_t jpegamd_export_segments(JpegAmdEncoder *e, const JpegAmdImage
     int32_t rc = exchange_args(e, img, block_row_begin, block_row_end, dense_words_dev, dense_capacity_words, meta_dev, total_words_dev, &x);
     if (rc) return rc;
     if (launch_seg_export(x, stream)) return JPEGAMD_ERR_HIP;
-    e->last_stream = (hipStream_t)stream; e->pending = true; e->timed = false;
+    e->last_stream = (hipStream_t)stream; e->pending = true; e->last_color = false; e->timed = false;
     return JPEGAMD_OK;
 }
 
@@ -506,7 +623,7 @@ extern "C" int32_t jpegamd_import_segments(JpegAmdEncoder *e, const JpegAmdImage
                                const_cast<uint32_t *>(meta_dev), nullptr, &x);
     if (rc) return rc;
     if (launch_seg_import(x, stream)) return JPEGAMD_ERR_HIP;
-    e->last_stream = (hipStream_t)stream; e->pending = true; e->timed = false;
+    e->last_stream = (hipStream_t)stream; e->pending = true; e->last_color = false; e->timed = false;
     return JPEGAMD_OK;
 }
 
@@ -522,7 +639,7 @@ extern "C" int32_t jpegamd_finalize_async(JpegAmdEncoder *e, const JpegAmdImage 
     if (run_finalize(e, im, out_dev, out_capacity, out_size_dev, with_container, stream)) return JPEGAMD_ERR_HIP;
     e->last_segs = im.num_segs;
     e->last_stream = stream;
-    e->pending = true;
+    e->pending = true; e->last_color = false;
     e->timed = false;
     return JPEGAMD_OK;
 }
@@ -546,20 +663,20 @@ extern "C" int32_t jpegamd_encode_async(JpegAmdEncoder *e, const JpegAmdImage *i
         ev = e->ring[(size_t)e->last_slot].ev;
         ++e->calls;
     }
-    if (timed) e->ring[(size_t)e->last_slot].merged = !stitch;
+    if (timed) { e->ring[(size_t)e->last_slot].merged = !stitch; e->ring[(size_t)e->last_slot].color = false; }
     if (stitch) {
-        if (launch_transform(e, im, false, nullptr, nullptr, nullptr, stream, ev)) return JPEGAMD_ERR_HIP;
+        if (launch_transform(e, im, false, nullptr, nullptr, nullptr, stream, ev, src_of(img))) return JPEGAMD_ERR_HIP;
         void *const outs[1] = {out_dev};
         uint64_t *const sizes[1] = {out_size_dev};
         if (run_stitch(e, im, outs, out_capacity, sizes, with_container, stream, ev ? ev + 4 : nullptr)) return JPEGAMD_ERR_HIP;
     } else {
-        if (launch_transform_and_entropy(e, im, false, nullptr, nullptr, nullptr, stream, ev)) return JPEGAMD_ERR_HIP;
+        if (launch_transform_and_entropy(e, im, false, nullptr, nullptr, nullptr, stream, ev, src_of(img))) return JPEGAMD_ERR_HIP;
         if (run_finalize(e, im, out_dev, out_capacity, out_size_dev, with_container, stream, ev ? ev + 4 : nullptr,
                          im.num_segs % kSegGroup == 0)) return JPEGAMD_ERR_HIP;
     }
     e->last_segs = im.num_segs;
     e->last_stream = stream;
-    e->pending = true;
+    e->pending = true; e->last_color = false;
     e->timed = timed;
     return JPEGAMD_OK;
 }
@@ -605,18 +722,178 @@ extern "C" int32_t jpegamd_encode_batch_async(JpegAmdEncoder *e, const JpegAmdIm
         ev = e->ring[(size_t)e->last_slot].ev;
         ++e->calls;
     }
-    if (timed) e->ring[(size_t)e->last_slot].merged = !stitch;
+    if (timed) { e->ring[(size_t)e->last_slot].merged = !stitch; e->ring[(size_t)e->last_slot].color = false; }
     if (stitch) {
-        if (launch_transform(e, im, false, nullptr, nullptr, nullptr, stream, ev)) return JPEGAMD_ERR_HIP;
+        if (launch_transform(e, im, false, nullptr, nullptr, nullptr, stream, ev, src_of(imgs))) return JPEGAMD_ERR_HIP;
         if (run_stitch(e, im, outs_dev, out_capacity, out_sizes_dev, with_container, stream, ev ? ev + 4 : nullptr)) return JPEGAMD_ERR_HIP;
     } else {
-        if (launch_transform_and_entropy(e, im, false, nullptr, nullptr, nullptr, stream, ev)) return JPEGAMD_ERR_HIP;
+        if (launch_transform_and_entropy(e, im, false, nullptr, nullptr, nullptr, stream, ev, src_of(imgs))) return JPEGAMD_ERR_HIP;
         if (run_finalize_batch(e, im, outs_dev, out_capacity, out_sizes_dev, with_container, stream, ev ? ev + 4 : nullptr)) return JPEGAMD_ERR_HIP;
     }
     e->last_segs = count * im.num_segs;
     e->last_stream = stream;
+    e->pending = true; e->last_color = false;
+    e->timed = timed;
+    return JPEGAMD_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Colour: three non-interleaved scans (colour scans).  k_chroma_planes writes the Cb / Cr planes; Y runs through the
+// unchanged RGB path straight into `out` behind the colour prefix; Cb and Cr run through k_tile_encode's one-byte mode with the
+// chroma constants into context scratch, each behind its SOS (Cr with EOI); k_append_scans copies them behind the Y scan at
+// offsets the device knows.  Everything is stream-ordered: the host never waits between the scans.
+// ---------------------------------------------------------------------------------------------------------
+static int32_t color_alloc(JpegAmdEncoder *e, int w, int h) {
+    auto &c = e->color;
+    if (!c.tables_dev) {
+        HIP_TRY(hipMalloc((void **)&c.tables_dev, sizeof(MfmaTables)));
+        HIP_TRY(hipMalloc((void **)&c.code_tab, kCodeWords * sizeof(uint32_t)));
+        HIP_TRY(hipMalloc((void **)&c.huff, 272 * sizeof(uint32_t)));
+        HIP_TRY(hipMalloc((void **)&c.hdr, 1024));
+        HIP_TRY(hipMalloc((void **)&c.scan_size, 4 * sizeof(uint64_t)));
+        HIP_TRY(hipMalloc((void **)&c.scan_stats, 3 * sizeof(ScanStats)));
+        uint32_t words[272];
+        build_huffman_words_chroma(words);
+        HIP_TRY(hipMemcpy(c.huff, words, sizeof(words), hipMemcpyHostToDevice));
+        std::vector<uint32_t> ct(kCodeWords);
+        build_code_table_chroma(ct.data());
+        HIP_TRY(hipMemcpy(c.code_tab, ct.data(), kCodeWords * sizeof(uint32_t), hipMemcpyHostToDevice));
+        uint8_t sos[2 * 16] = {};
+        color_sos(2, sos);
+        color_sos(3, sos + 16);
+        HIP_TRY(hipMemcpy(c.hdr + kColorPrefixMax, sos, sizeof(sos), hipMemcpyHostToDevice));
+    }
+    // planes and scans sized for this picture at 4:4:4 (the larger case), grown when a later picture needs more
+    const size_t planes = 2 * (size_t)((w + 3) / 4 * 4) * (size_t)h + 64;
+    const size_t scan = (kSosBytes + 2 + scan_bound(blocks_of(w, h)) + 64 + 255) & ~(size_t)255;     // (k_append_scans reads 16 bytes at a time)
+    if (planes > c.planes_cap || scan > c.scan_cap) {
+        if (e->pending) HIP_TRY(hipStreamSynchronize(e->last_stream));
+        hipFree(c.planes); hipFree(c.scans);
+        c.planes = nullptr; c.scans = nullptr; c.planes_cap = c.scan_cap = 0;
+        HIP_TRY(hipMalloc((void **)&c.planes, planes));
+        HIP_TRY(hipMalloc((void **)&c.scans, 2 * scan));
+        c.planes_cap = planes; c.scan_cap = scan;
+    }
+    return JPEGAMD_OK;
+}
+
+static int32_t prepare_color_constants(JpegAmdEncoder *e, const JpegAmdImage *img, int sub) {
+    auto &c = e->color;
+    const int q = (img->quality <= 0) ? 50 : (img->quality > 100 ? 100 : img->quality);
+    if (q != c.cur_quality) {
+        uint8_t t[64];
+        chroma_quant_table_for_quality(q, t);
+        MfmaTables *mt = new (std::nothrow) MfmaTables;
+        if (!mt) return JPEGAMD_ERR_HIP;
+        derive_mfma_tables(t, mt, nullptr);
+        if (e->pending) { hipError_t err = hipStreamSynchronize(e->last_stream); if (err != hipSuccess) { delete mt; return JPEGAMD_ERR_HIP; } }
+        const hipError_t err = hipMemcpy(c.tables_dev, mt, sizeof(MfmaTables), hipMemcpyHostToDevice);
+        delete mt;
+        if (err != hipSuccess) return JPEGAMD_ERR_HIP;
+        c.cur_quality = q;
+    }
+    if (c.hdr_w != img->width || c.hdr_h != img->height || c.hdr_q != q || c.hdr_sub != sub) {
+        uint8_t luma[64], chroma[64], hdr[kColorPrefixMax];
+        quant_table_for_quality(q, luma);
+        chroma_quant_table_for_quality(q, chroma);
+        c.hdr_len = (int)build_jfif_prefix_color(img->width, img->height, luma, chroma, sub == JPEGAMD_SUBSAMPLE_420, hdr);
+        if (e->pending) HIP_TRY(hipStreamSynchronize(e->last_stream));
+        HIP_TRY(hipMemcpy(c.hdr, hdr, (size_t)c.hdr_len, hipMemcpyHostToDevice));
+        c.hdr_w = img->width; c.hdr_h = img->height; c.hdr_q = q; c.hdr_sub = sub;
+    }
+    return JPEGAMD_OK;
+}
+
+// One scan of the colour file: k_tile_encode, then k_segment_merge + k_finalize or k_stitch, then the scan's symbol sums.
+static int run_scan(JpegAmdEncoder *e, const ImageDesc &im, int src, void *out, uint64_t cap, uint64_t *size_dev, const ScanTarget &tgt,
+                    bool stitch, hipStream_t stream, hipEvent_t *ev) {
+    if (stitch) {
+        if (int err = launch_transform(e, im, false, nullptr, nullptr, nullptr, stream, ev, src)) return err;
+        void *const outs[1] = {out};
+        uint64_t *const sizes[1] = {size_dev};
+        if (int err = run_stitch(e, im, outs, cap, sizes, 1, stream, ev ? ev + 4 : nullptr, &tgt)) return err;
+    } else {
+        if (int err = launch_transform_and_entropy(e, im, false, nullptr, nullptr, nullptr, stream, ev, src)) return err;
+        if (int err = run_finalize(e, im, out, cap, size_dev, 1, stream, ev ? ev + 4 : nullptr, im.num_segs % kSegGroup == 0, &tgt)) return err;
+    }
+    return launch_sum_stats(e->seg.syms, e->seg.exact, im.num_segs, tgt.stats, stream);
+}
+
+extern "C" int32_t jpegamd_encode_color_async(JpegAmdEncoder *e, const JpegAmdImage *img, int32_t subsampling, void *out_dev,
+                                              uint64_t out_capacity, uint64_t *out_size_dev, void *stream_) {
+    if (!e || !img || !out_dev || !out_size_dev) return JPEGAMD_ERR_ARG;
+    if (subsampling != JPEGAMD_SUBSAMPLE_444 && subsampling != JPEGAMD_SUBSAMPLE_420) return JPEGAMD_ERR_ARG;
+    if (img->channel_order != JPEGAMD_ORDER_BGR && img->channel_order != JPEGAMD_ORDER_RGB) return JPEGAMD_ERR_ARG;
+    ImageDesc iy;
+    const bool stitch_y = use_stitch(e, img->width, img->height);
+    int32_t rc = describe(e, img, &iy, stitch_y ? kSegTilesBatch : kSegTiles);
+    if (rc) return rc;
+    int cw, ch;
+    chroma_dims(img->width, img->height, subsampling, &cw, &ch);
+    const int pitch = (cw + 3) / 4 * 4;
+    rc = color_alloc(e, img->width, img->height);
+    if (rc) return rc;
+    rc = prepare_constants(e, img, false);
+    if (rc) return rc;
+    rc = prepare_color_constants(e, img, subsampling);
+    if (rc) return rc;
+    auto &c = e->color;
+    hipStream_t stream = (hipStream_t)stream_;
+
+    const bool timed = !e->ring.empty();
+    hipEvent_t *cev = nullptr;
+    if (timed) {
+        e->last_slot = (int)(e->calls % e->ring.size());
+        auto &set = e->ring[(size_t)e->last_slot];
+        if (set.cev.empty()) {
+            set.cev.assign(22, nullptr);
+            for (auto &ev : set.cev) HIP_TRY(hipEventCreate(&ev));
+        }
+        set.color = true;
+        cev = set.cev.data();
+        ++e->calls;
+    }
+    HIP_TRY(hipMemsetAsync(c.scan_stats, 0, 3 * sizeof(ScanStats), stream));
+
+    ChromaPlanesArgs pa;
+    pa.pixels = (const uint8_t *)img->pixels;
+    pa.width = img->width; pa.height = img->height; pa.row_stride = img->row_stride; pa.bottom_up = img->bottom_up ? 1 : 0;
+    pa.rgb = img->channel_order == JPEGAMD_ORDER_RGB ? 1 : 0;
+    pa.sub420 = subsampling == JPEGAMD_SUBSAMPLE_420 ? 1 : 0;
+    pa.cw = cw; pa.ch = ch; pa.pitch = pitch;
+    pa.cb = c.planes; pa.cr = c.planes + (size_t)pitch * (size_t)ch;
+    if (launch_chroma_planes(pa, stream, cev ? (void *const *)cev : nullptr)) return JPEGAMD_ERR_HIP;
+
+    // Y: the grayscale scan of the same picture, behind the colour prefix, no EOI
+    const ScanTarget ty = {c.hdr, c.hdr_len, 0, &c.scan_stats[0], false};
+    if (timed) e->ring[(size_t)e->last_slot].cmerged[0] = !stitch_y;
+    if (run_scan(e, iy, kTileSrcRgb, out_dev, out_capacity, &c.scan_size[0], ty, stitch_y, stream, cev ? cev + 2 : nullptr))
+        return JPEGAMD_ERR_HIP;
+    // Cb, Cr: one-byte planes, chroma tables, into scratch
+    JpegAmdImage pimg = *img;
+    pimg.width = cw; pimg.height = ch; pimg.row_stride = pitch; pimg.bottom_up = 0; pimg.channel_order = JPEGAMD_ORDER_GRAY;
+    const bool stitch_c = use_stitch(e, cw, ch);
+    for (int k = 0; k < 2; ++k) {
+        pimg.pixels = k ? pa.cr : pa.cb;
+        ImageDesc ic;
+        rc = describe(e, &pimg, &ic, stitch_c ? kSegTilesBatch : kSegTiles);
+        if (rc) return rc;
+        const ScanTarget tc = {c.hdr + kColorPrefixMax + 16 * k, kSosBytes, k, &c.scan_stats[1 + k], true};
+        if (timed) e->ring[(size_t)e->last_slot].cmerged[1 + k] = !stitch_c;
+        if (run_scan(e, ic, kTileSrcChroma, c.scans + (size_t)k * c.scan_cap, c.scan_cap, &c.scan_size[1 + k], tc, stitch_c, stream,
+                     cev ? cev + 8 + 6 * k : nullptr))
+            return JPEGAMD_ERR_HIP;
+    }
+    AppendArgs aa;
+    aa.out = (uint8_t *)out_dev; aa.out_capacity = out_capacity; aa.out_size = out_size_dev;
+    aa.scan_size = c.scan_size; aa.src[0] = c.scans; aa.src[1] = c.scans + c.scan_cap;
+    aa.scan_stats = c.scan_stats; aa.stats = e->stats_dev;
+    if (launch_append_scans(aa, stream, cev ? (void *const *)(cev + 20) : nullptr)) return JPEGAMD_ERR_HIP;
+    e->last_segs = iy.num_segs;
+    e->last_stream = stream;
     e->pending = true;
     e->timed = timed;
+    e->last_color = true;
     return JPEGAMD_OK;
 }
 
@@ -627,7 +904,7 @@ extern "C" int32_t jpegamd_encode_batch_async(JpegAmdEncoder *e, const JpegAmdIm
 extern "C" int32_t jpegamd_encoder_finish(JpegAmdEncoder *e, JpegAmdStats *stats) {
     if (!e) return JPEGAMD_ERR_ARG;
     if (!e->pending) return JPEGAMD_ERR_ARG;
-    if (stats)                          // symbol / exact-path totals are only summed when somebody asks
+    if (stats && !e->last_color)        // symbol / exact-path totals are only summed when somebody asks (a colour call summed its own)
         if (launch_sum_stats(e->seg.syms, e->seg.exact, e->last_segs, e->stats_dev, e->last_stream)) return JPEGAMD_ERR_HIP;
     HIP_TRY(hipStreamSynchronize(e->last_stream));
     e->pending = false;
@@ -660,7 +937,7 @@ extern "C" int32_t jpegamd_debug_stages(JpegAmdEncoder *e, const JpegAmdImage *i
     if (rc) return rc;
     rc = prepare_constants(e, img, false);
     if (rc) return rc;
-    if (launch_transform_and_entropy(e, im, true, y_centered, quant_zigzag, exact_mask, nullptr)) return JPEGAMD_ERR_HIP;
+    if (launch_transform_and_entropy(e, im, true, y_centered, quant_zigzag, exact_mask, nullptr, nullptr, src_of(img))) return JPEGAMD_ERR_HIP;
     HIP_TRY(hipStreamSynchronize(nullptr));
     return JPEGAMD_OK;
 }
@@ -759,7 +1036,7 @@ int32_t first_block_taps(JpegAmdEncoder *e, const JpegAmdImage *img, int8_t y[64
     int err = (int)hipMalloc((void **)&y_dev, 64);              // (every exit path below frees what was allocated)
     if (!err) err = (int)hipMalloc((void **)&zz_dev, 128);
     if (!err) err = (int)hipMalloc((void **)&dct_dev, 256);
-    if (!err) err = launch_transform_and_entropy(e, im, true, y_dev, zz_dev, nullptr, nullptr);
+    if (!err) err = launch_transform_and_entropy(e, im, true, y_dev, zz_dev, nullptr, nullptr, nullptr, src_of(img));
     if (!err) err = launch_dct_exact(y_dev, dct_dev, 1, nullptr);
     if (!err) err = (int)hipMemcpy(y, y_dev, 64, hipMemcpyDeviceToHost);
     if (!err) err = (int)hipMemcpy(zz, zz_dev, 128, hipMemcpyDeviceToHost);

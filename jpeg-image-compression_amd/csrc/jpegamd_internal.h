@@ -29,6 +29,14 @@ constexpr int kSegTilesMax = kSegTilesBatch;
 constexpr int kMaxBlockBits = 20 + 63 * 27;                          // 1721
 constexpr int seg_cap_words(int seg_tiles) { return ((kTileBlocks * seg_tiles * kMaxBlockBits + 31) / 32 + 1 + 63) / 64 * 64; }   // words reserved per segment
 constexpr int kSegCapWords = seg_cap_words(kSegTiles);
+// Colour scans (jpegamd_encode_color_async): a chroma DC code is up to 11 bits (T.81 K.4), so a chroma block's bound is
+// 22 + 63 x 27 bits.  The reservations sized with kMaxBlockBits hold it as well (they round to the same word counts); the
+// attainable worst case is lower still -- neither AC table has a code for size 11, so an AC symbol is at most 16 + 10 bits.
+constexpr int kMaxBlockBitsColor = 22 + 63 * 27;                     // 1723
+constexpr int seg_cap_words_at(int seg_tiles, int block_bits) { return ((kTileBlocks * seg_tiles * block_bits + 31) / 32 + 1 + 63) / 64 * 64; }
+static_assert(seg_cap_words_at(kSegTiles, kMaxBlockBitsColor) == seg_cap_words(kSegTiles) &&
+              seg_cap_words_at(kSegTilesBatch, kMaxBlockBitsColor) == seg_cap_words(kSegTilesBatch),
+              "a segment of chroma blocks fits the luma reservation");
 constexpr int kAFragWords = 2 * 2 * 4 * 64 * 4;                      // [term][chain][kstep][lane] x 8 binary16 = 16 KiB
 constexpr float kMfmaScale = 1.0f / 8192.0f;                         // the accumulator chains hold kMfmaScale * LUT sum (hi chain + lo chain): the A terms are 2048 K, the B operand is y 2^-24
 
@@ -58,6 +66,7 @@ constexpr int kCodeRows = 64;
 constexpr int kCodeRowStride = 33;
 constexpr int kCodeWords = kCodeLead + kCodeRows * kCodeRowStride;   // 2144
 constexpr uint32_t kZrlBits = 11, kZrlCode = 0x7F9u;                  // symbol 0xF0: '11111111001' (jpeg_tables.c:36-48)
+constexpr uint32_t kZrlBitsChroma = 10, kZrlCodeChroma = 0x3FAu;      // ... in the chroma AC table (T.81 K.6): '1111111010'
 
 // Per-tile output of k_tile_encode in HBM: an 8-word record and the tile's bit string (MSB-first): every symbol of the tile
 // except the DC of its first block.
@@ -71,6 +80,7 @@ constexpr int kTileRecWords = 8;
 constexpr int kTileHeadWords = 128;             // record + first string words: ONE 8-byte-per-lane store
 constexpr int kTileHeadStr = kTileHeadWords - kTileRecWords;   // 120
 constexpr int kTileOverCap = ((kTileBlocks * kMaxBlockBits + 31) / 32 + 2 + 63) / 64 * 64;   // words reserved per tile behind the head (1728)
+static_assert(((kTileBlocks * kMaxBlockBitsColor + 31) / 32 + 2 + 63) / 64 * 64 == kTileOverCap, "a tile of chroma blocks fits the luma reservation");
 // (A dense array for the segments' strings as well was measured: k_finalize 38 -> 51 us per launch of eight pictures.)
 
 struct MfmaTables {
@@ -147,9 +157,12 @@ struct TransformOutM {
 };
 // `ev` (optional): two hipEvent_t that receive the kernel's OWN begin / end timestamps (hipExtLaunchKernelGGL), i.e. what a
 // kernel trace reports as its duration -- an event recorded in front of a launch also sees the dispatch latency.
-int launch_tile_transform(const ImageDesc &im, const TransformOutM &out, bool taps, void *stream, void *const *ev = nullptr);
+// `src`: what a pixel is -- kTileSrcRgb (3 bytes, ImageDesc::weights), kTileSrcGray (1 byte: the luma itself), kTileSrcChroma (1 byte of
+// a chroma plane, coded with the chroma tables: TransformOutM must then point at the chroma constants).
+constexpr int kTileSrcRgb = 0, kTileSrcGray = 1, kTileSrcChroma = 2;
+int launch_tile_transform(const ImageDesc &im, const TransformOutM &out, bool taps, void *stream, void *const *ev = nullptr, int src = kTileSrcRgb);
 // the same kernel with its phases stamped (out.stamps must point at 16 words per wave): jpegamd_tile_pipeline.hip, -DJPEGAMD_STAMPED_TU
-int launch_tile_transform_stamped(const ImageDesc &im, const TransformOutM &out, bool taps, void *stream, void *const *ev = nullptr);
+int launch_tile_transform_stamped(const ImageDesc &im, const TransformOutM &out, bool taps, void *stream, void *const *ev = nullptr, int src = kTileSrcRgb);
 
 struct MergeArgs {              // k_segment_merge: the tile strings of a segment -> ONE bit string per segment + its numbers
     const uint32_t *tile_head, *tile_over;
@@ -224,8 +237,42 @@ int launch_seg_import(const SegExchange &x, void *stream);
 int launch_sum_stats(const uint32_t *seg_syms, const uint32_t *seg_exact, int n, ScanStats *stats, void *stream);
 int launch_dct_exact(const int8_t *blocks, float *coeffs, int64_t nblocks, void *stream);
 
+// Colour (jpegamd_color.hip).  k_chroma_planes: the picture -> Cb and Cr planes (u8, `pitch` bytes per row, a multiple of 4), full
+// resolution (4:4:4) or 2 x 2 averaged (4:2:0).  k_append_scans: the chroma scans, coded into context scratch, copied behind the
+// Y scan in the caller's buffer at the offsets the device computed; the per-scan statistics summed into one record.
+struct ChromaPlanesArgs {
+    const uint8_t *pixels;
+    int32_t width, height, row_stride, bottom_up;
+    int32_t rgb;                        // 1: stored bytes R, G, B; 0: B, G, R
+    int32_t sub420;                     // 1: 4:2:0, 0: 4:4:4
+    int32_t cw, ch, pitch;              // plane geometry
+    uint8_t *cb, *cr;
+};
+int launch_chroma_planes(const ChromaPlanesArgs &a, void *stream, void *const *ev = nullptr);
+struct AppendArgs {
+    uint8_t *out;
+    uint64_t out_capacity;
+    uint64_t *out_size;                 // the caller's: the file's size, or 0 when it did not fit
+    const uint64_t *scan_size;          // [3] bytes of the Y part (prefix + Y scan) and of the two chroma parts (SOS + scan [+ EOI])
+    const uint8_t *src[2];              // the chroma parts (context scratch)
+    ScanStats *scan_stats;              // [3] per-scan records (status, bits, 0xFF bytes, symbols, exact-path count)
+    ScanStats *stats;                   // the context's record: the sums
+};
+int launch_append_scans(const AppendArgs &a, void *stream, void *const *ev = nullptr);
+
 // ---- host-side constant derivation (quant_consts.cpp) ----------------------------------
 void quant_table_for_quality(int quality, uint8_t table[64]);
+// T.81 Annex K K.2 (the chroma table), scaled for `quality` with the rule of quant_table_for_quality
+void chroma_quant_table_for_quality(int quality, uint8_t table[64]);
+void build_huffman_words_chroma(uint32_t words[272]);
+void build_code_table_chroma(uint32_t words[kCodeWords]);
+// The colour file's headers up to the Y scan: SOI, APP0, DQT (tables 0 and 1), SOF0 (3 components), DHT x 4, SOS (Y).  Returns
+// the byte count (<= kColorPrefixMax).  color_sos: the SOS segment in front of the scan of component 2 or 3 (10 bytes).
+constexpr int kColorPrefixMax = 640;
+constexpr int kSosBytes = 10;
+size_t build_jfif_prefix_color(int width, int height, const uint8_t luma[64], const uint8_t chroma[64], int sub420,
+                               uint8_t out[kColorPrefixMax]);
+void color_sos(int component, uint8_t out[kSosBytes]);
 // A-row order of the pipeline: lane half h, site s <-> zigzag 16(s>>3) + 8h + (s&7)
 void derive_mfma_tables(const uint8_t table[64], MfmaTables *mt, double delta_out[64] /*by raster k, may be null*/);
 void build_huffman_words(uint32_t words[272]);

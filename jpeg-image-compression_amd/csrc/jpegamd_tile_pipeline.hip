@@ -139,6 +139,29 @@ constexpr int kPassItems = 128;                                  // items coded 
 constexpr int kQuadMinItems = 384;                               // lists at least this long try four items per lane first
 static_assert(8 * 65 <= kStageItemCap, "a quarter of a tile's items (8 blocks) always fits the staging region");
 static_assert(kPassItems * (27 + 3 * (int)kZrlBits) / 32 + 6 <= kWinStr && 2 * kPassItems * 27 / 32 + 6 <= kWinStr, "the window takes a whole pass, ZRLs included, and a four-item pass without");
+static_assert(kPassItems * (27 + 3 * (int)kZrlBitsChroma) / 32 + 6 <= kWinStr && 27 + 3 * (int)kZrlBitsChroma <= 64,
+              "... with the chroma table's ZRL as well (and a string with three of them in front still fits hi:lo)");
+
+// What k_tile_encode reads (template parameter kSrc: no runtime branch, the RGB instantiations are unchanged):
+//   kSrcRgb    3 bytes per pixel, luma by the weights of ImageDesc (BGR / RGB, either row order)
+//   kSrcPlane  1 byte per pixel: the sample itself (a GRAY picture, or a chroma plane of k_chroma_planes)
+constexpr int kSrcRgb = 0, kSrcPlane = 1;
+
+// 8 plane samples (2 dwords) -> the B fragment of one k-step half: each byte zero-extended into a 16-bit half (= the binary16
+// subnormal y 2^-24, as luma_row8_f16 makes it).
+__device__ __forceinline__ f16x8 plane_row8_f16(uint32_t d0, uint32_t d1) {
+    typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
+    const u32x4 packed = {__builtin_amdgcn_perm(0u, d0, 0x0C010C00u), __builtin_amdgcn_perm(0u, d0, 0x0C030C02u),
+                          __builtin_amdgcn_perm(0u, d1, 0x0C010C00u), __builtin_amdgcn_perm(0u, d1, 0x0C030C02u)};
+    return __builtin_bit_cast(f16x8, packed);
+}
+
+// Sample of plane pixel (x, y) with the edge clamp (the padding of converter.c:31,36 by replication).
+__device__ __forceinline__ int plane_clamped(const ImageDesc &im, const uint8_t *pixels, int x, int y) {
+    x = min(x, im.width - 1);
+    y = min(y, im.height - 1);
+    return (int)row_ptr(im, pixels, y)[x];
+}
 
 struct TileSched {            // division-free launch geometry, filled by launch_tile_transform
     int32_t grp_shift;        // workgroups form 1 << grp_shift ticket groups (blockIdx & mask)
@@ -220,15 +243,25 @@ __device__ __forceinline__ void code_item(uint32_t it, uint32_t prev, const uint
 
 // z ZRL codes (huffman.c:158-188 codes them as ordinary symbols: 0xF0 is 11111111001, 11 bits) in front of a left-aligned
 // string of <= 27 bits: (bits : 0) >> 11 z under the constant prefix.  z = 3 shifts by 33: the string lands in the low word.
+// The chroma table's ZRL is 10 bits, 0x3FA (T.81 K.6): z of them take at most 30 bits, so z = 3 needs no low-word case.
+template <uint32_t kZBits, uint32_t kZCode>
 __device__ __forceinline__ void zrl_prefix(uint32_t bits, uint32_t z /*0..3*/, uint32_t &hi, uint32_t &lo) {
-    static_assert(kZrlBits == 11 && kZrlCode == 0x7F9, "the prefix constants below are three copies of this code");
-    const uint32_t sh = z * 11u;
-    const uint32_t hs = __builtin_amdgcn_alignbit(0u, bits, sh), ls = __builtin_amdgcn_alignbit(bits, 0u, sh);     // (the funnel shifts use sh mod 32)
-    // three copies of the code are 0xFF3FE7FC : 0x80000000; z of them = its top 11 z bits (branch-free: the compiler makes a switch of a constant table)
-    const bool three = z == 3u;
-    const uint32_t chi = 0xFF3FE7FCu & ~(three ? 0u : 0xFFFFFFFFu >> sh);
-    hi = chi | (three ? 0u : hs);
-    lo = three ? (0x80000000u | hs) : ls;
+    if constexpr (kZBits == 10) {
+        static_assert(kZCode == kZrlCodeChroma, "the prefix constant below is three copies of this code");
+        const uint32_t sh = z * 10u;                                   // 0, 10, 20, 30
+        constexpr uint32_t c3 = (kZCode << 22) | (kZCode << 12) | (kZCode << 2);
+        hi = (c3 & ~(0xFFFFFFFFu >> sh)) | (bits >> sh);                 // (sh = 0: no ZRL, the string unchanged)
+        lo = __builtin_amdgcn_alignbit(bits, 0u, sh);                   // the bits shifted out of hi (sh = 0: none)
+    } else {
+        static_assert(kZBits == 11 && kZCode == 0x7F9, "the prefix constants below are three copies of this code");
+        const uint32_t sh = z * 11u;
+        const uint32_t hs = __builtin_amdgcn_alignbit(0u, bits, sh), ls = __builtin_amdgcn_alignbit(bits, 0u, sh);     // (the funnel shifts use sh mod 32)
+        // three copies of the code are 0xFF3FE7FC : 0x80000000; z of them = its top 11 z bits (branch-free: the compiler makes a switch of a constant table)
+        const bool three = z == 3u;
+        const uint32_t chi = 0xFF3FE7FCu & ~(three ? 0u : 0xFFFFFFFFu >> sh);
+        hi = chi | (three ? 0u : hs);
+        lo = three ? (0x80000000u | hs) : ls;
+    }
 }
 // sum over the wave of a small per-lane count (0..7): three ballots and scalar population counts instead of a DPP prefix sum
 __device__ __forceinline__ uint32_t wave_sum_3bit(uint32_t v) {
@@ -243,7 +276,9 @@ __device__ __forceinline__ void window_or(uint32_t *win, uint32_t rel, uint32_t 
     if (third) atomicOr(&win[w + 2], __builtin_amdgcn_alignbit(lo, 0u, sh));
 }
 
-template <bool kTaps>
+// kSrc: what a pixel is (kSrcRgb / kSrcPlane); kZBits / kZCode: the ZRL code of the Huffman table in TransformOutM::code_tab
+// (luma: 11 bits 0x7F9; chroma: 10 bits 0x3FA).  A GRAY picture is <kTaps, kSrcPlane>, a chroma plane <false, kSrcPlane, 10, 0x3FA>.
+template <bool kTaps, int kSrc = kSrcRgb, uint32_t kZBits = kZrlBits, uint32_t kZCode = kZrlCode>
 __global__ __launch_bounds__(64 * kWavesT) __attribute__((amdgpu_waves_per_eu(JPEGAMD_TILE_WAVES, JPEGAMD_TILE_WAVES)))
 void k_tile_encode(const ImageDesc im, const TransformOutM out, const TileSched sch) {
     __shared__ __attribute__((aligned(16))) uint32_t s_afrag[kAFragWords];
@@ -379,6 +414,18 @@ void k_tile_encode(const ImageDesc im, const TransformOutM out, const TileSched 
         const uint8_t *tb = im.batch_pixels[g.img] + (size_t)row_low * (size_t)im.row_stride + 24 * (size_t)g.tbx0;
         uint32_t hh = (uint32_t)h;
         asm volatile("" : "+v"(hh));
+        if constexpr (kSrc == kSrcPlane) {                      // 8 bytes per lane-row: a block row of one-byte samples
+            const uint8_t *pb = im.batch_pixels[g.img] + (size_t)row_low * (size_t)im.row_stride + 8 * (size_t)g.tbx0;
+            uint32_t poff = __umul24((uint32_t)min(b, g.nblk - 1), 8u) + __umul24(im.bottom_up ? 7u - hh : hh, (uint32_t)im.row_stride);
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {
+                const uint32_t *src = reinterpret_cast<const uint32_t *>(pb + poff);
+                raw[s].d[0] = src[0];
+                raw[s].d[1] = src[1];
+                poff += (uint32_t)row_step;
+            }
+            return;
+        }
         uint32_t off = __umul24((uint32_t)min(b, g.nblk - 1), 24u) + __umul24(im.bottom_up ? 7u - hh : hh, (uint32_t)im.row_stride);   // row_stride < 2^24
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
@@ -413,7 +460,10 @@ void k_tile_encode(const ImageDesc im, const TransformOutM out, const TileSched 
         f16x8 bfrag[4];
         if (interior) {                        // rows requested one iteration ago, behind the ticket (below)
 #pragma unroll
-            for (int s = 0; s < 4; ++s) bfrag[s] = luma_row8_f16(raw[s], lw, luma_sel);
+            for (int s = 0; s < 4; ++s) {
+                if constexpr (kSrc == kSrcPlane) bfrag[s] = plane_row8_f16(raw[s].d[0], raw[s].d[1]);
+                else bfrag[s] = luma_row8_f16(raw[s], lw, luma_sel);
+            }
         } else {
             // edge tile (right/bottom replication, converter.c:31,36) or unaligned source: clamped byte gather
             typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
@@ -421,9 +471,14 @@ void k_tile_encode(const ImageDesc im, const TransformOutM out, const TileSched 
             for (int s = 0; s < 4; ++s) {
                 u32x4 pk;
 #pragma unroll
-                for (int j = 0; j < 8; j += 2)                  // two values per register: Y in each 16-bit half (= Y 2^-24 as binary16, as above)
-                    pk[j >> 1] = (uint32_t)luma_clamped(im, im.batch_pixels[tg.img], px0 + j, py0 + 2 * s + h) |
-                                 ((uint32_t)luma_clamped(im, im.batch_pixels[tg.img], px0 + j + 1, py0 + 2 * s + h) << 16);
+                for (int j = 0; j < 8; j += 2) {                // two values per register: Y in each 16-bit half (= Y 2^-24 as binary16, as above)
+                    if constexpr (kSrc == kSrcPlane)
+                        pk[j >> 1] = (uint32_t)plane_clamped(im, im.batch_pixels[tg.img], px0 + j, py0 + 2 * s + h) |
+                                     ((uint32_t)plane_clamped(im, im.batch_pixels[tg.img], px0 + j + 1, py0 + 2 * s + h) << 16);
+                    else
+                        pk[j >> 1] = (uint32_t)luma_clamped(im, im.batch_pixels[tg.img], px0 + j, py0 + 2 * s + h) |
+                                     ((uint32_t)luma_clamped(im, im.batch_pixels[tg.img], px0 + j + 1, py0 + 2 * s + h) << 16);
+                }
                 bfrag[s] = __builtin_bit_cast(f16x8, pk);
             }
         }
@@ -839,9 +894,9 @@ void k_tile_encode(const ImageDesc im, const TransformOutM out, const TileSched 
                     const bool zrl1 = __ballot((e1 & 0x60u) != 0u) != 0ull;
                     if (__builtin_expect(zrl1, 0)) {              // runs >= 16 (rle.c:99-103): ZRL symbols in front
                         const uint32_t z1 = (e1 >> 5) & 3u;
-                        l1 += z1 * kZrlBits;
+                        l1 += z1 * kZBits;
                         nzrl += wave_sum_3bit(z1);
-                        zrl_prefix(s1, z1, h1, lo1);
+                        zrl_prefix<kZBits, kZCode>(s1, z1, h1, lo1);
                     }
                     const uint32_t incl1 = wave_incl_scan_u32(l1);
                     const uint32_t bits1 = (uint32_t)__builtin_amdgcn_readlane((int)incl1, 63);
@@ -904,8 +959,8 @@ void k_tile_encode(const ImageDesc im, const TransformOutM out, const TileSched 
                 const bool any_zrl = __ballot(((ea | eb) & 0x60u) != 0u) != 0ull;
                 if (__builtin_expect(any_zrl, 0)) {               // runs >= 16 (rle.c:99-103): ZRL symbols in front, coded below
                     const uint32_t za = (ea >> 5) & 3u, zb = (eb >> 5) & 3u;
-                    la += za * kZrlBits;
-                    lb += zb * kZrlBits;
+                    la += za * kZBits;
+                    lb += zb * kZBits;
                     nzrl += wave_sum_3bit(za + zb);
                 }
                 const uint32_t lab = la + lb;
@@ -921,9 +976,9 @@ void k_tile_encode(const ImageDesc im, const TransformOutM out, const TileSched 
                 } else {
                     // symbol by symbol, each with its ZRLs in front (huffman.c:158-188 codes them as ordinary symbols)
                     uint32_t hi, lo;
-                    zrl_prefix(sa, (ea >> 5) & 3u, hi, lo);
+                    zrl_prefix<kZBits, kZCode>(sa, (ea >> 5) & 3u, hi, lo);
                     window_or(win, rel, hi, lo, true);
-                    zrl_prefix(sb, (eb >> 5) & 3u, hi, lo);
+                    zrl_prefix<kZBits, kZCode>(sb, (eb >> 5) & 3u, hi, lo);
                     window_or(win, rel + la, hi, lo, true);
                 }
                 cur_bits += pass_bits;
@@ -980,7 +1035,7 @@ void k_tile_encode(const ImageDesc im, const TransformOutM out, const TileSched 
 #endif
 }
 
-int launch_tile_transform(const ImageDesc &im, const TransformOutM &out, bool taps, void *stream, void *const *ev) {
+int launch_tile_transform(const ImageDesc &im, const TransformOutM &out, bool taps, void *stream, void *const *ev, int src) {
     // persistent: at most 2 workgroups per CU (16 waves/CU at 4 waves/SIMD), fewer for small images
     const int ntiles = im.tile_end - im.tile_begin;
     if (ntiles <= 0) return 0;
@@ -994,6 +1049,16 @@ int launch_tile_transform(const ImageDesc &im, const TransformOutM &out, bool ta
     const uint64_t magic = 0x100000000ull / (uint64_t)im.tiles_per_row + 1ull;
     sch.tpr_magic = magic > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)magic;   // tiles_per_row == 1: the correction step makes up for it
     const dim3 grid(wgs), block(64 * kWavesT);
+    if (src != kTileSrcRgb) {
+        const bool chroma = src == kTileSrcChroma;
+        const auto gray = k_tile_encode<false, kSrcPlane>;
+        const auto plane = k_tile_encode<false, kSrcPlane, kZrlBitsChroma, kZrlCodeChroma>;
+        if (taps && !chroma) hipLaunchKernelGGL((k_tile_encode<true, kSrcPlane>), grid, block, 0, (hipStream_t)stream, im, out, sch);
+        else if (taps) return (int)hipErrorInvalidValue;                    // (no stage taps of a chroma scan)
+        else if (ev) hipExtLaunchKernelGGL(chroma ? plane : gray, grid, block, 0, (hipStream_t)stream, (hipEvent_t)ev[0], (hipEvent_t)ev[1], 0, im, out, sch);
+        else hipLaunchKernelGGL(chroma ? plane : gray, grid, block, 0, (hipStream_t)stream, im, out, sch);
+        return (int)hipGetLastError();
+    }
     if (taps) hipLaunchKernelGGL(k_tile_encode<true>, grid, block, 0, (hipStream_t)stream, im, out, sch);
     else if (ev) hipExtLaunchKernelGGL(k_tile_encode<false>, grid, block, 0, (hipStream_t)stream, (hipEvent_t)ev[0], (hipEvent_t)ev[1], 0, im, out, sch);
     else hipLaunchKernelGGL(k_tile_encode<false>, grid, block, 0, (hipStream_t)stream, im, out, sch);

@@ -53,6 +53,29 @@ static const uint8_t kAcSymbols[162] = {
     0xD9, 0xDA, 0xE1, 0xE2, 0xE3, 0xE4, 0xE5, 0xE6, 0xE7, 0xE8, 0xE9, 0xEA, 0xF1, 0xF2,
     0xF3, 0xF4, 0xF5, 0xF6, 0xF7, 0xF8, 0xF9, 0xFA};
 
+// Colour (jpegamd_encode_color_async): ITU-T T.81 Annex K, Table K.2 (chroma quantisation, raster order), Tables K.4 / K.6 as
+// BITS / HUFFVAL lists (chroma DC and AC Huffman tables).
+static const uint8_t kBaseQuantChroma[64] = {
+    17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99,
+    24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99,
+    99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99,
+    99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99};
+static const uint8_t kDcCountsChroma[16] = {0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0};
+static const uint8_t kAcCountsChroma[16] = {0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 0x77};
+static const uint8_t kAcSymbolsChroma[162] = {
+    0x00, 0x01, 0x02, 0x03, 0x11, 0x04, 0x05, 0x21, 0x31, 0x06, 0x12, 0x41, 0x51, 0x07,
+    0x61, 0x71, 0x13, 0x22, 0x32, 0x81, 0x08, 0x14, 0x42, 0x91, 0xA1, 0xB1, 0xC1, 0x09,
+    0x23, 0x33, 0x52, 0xF0, 0x15, 0x62, 0x72, 0xD1, 0x0A, 0x16, 0x24, 0x34, 0xE1, 0x25,
+    0xF1, 0x17, 0x18, 0x19, 0x1A, 0x26, 0x27, 0x28, 0x29, 0x2A, 0x35, 0x36, 0x37, 0x38,
+    0x39, 0x3A, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48, 0x49, 0x4A, 0x53, 0x54, 0x55, 0x56,
+    0x57, 0x58, 0x59, 0x5A, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6A, 0x73, 0x74,
+    0x75, 0x76, 0x77, 0x78, 0x79, 0x7A, 0x82, 0x83, 0x84, 0x85, 0x86, 0x87, 0x88, 0x89,
+    0x8A, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9A, 0xA2, 0xA3, 0xA4, 0xA5,
+    0xA6, 0xA7, 0xA8, 0xA9, 0xAA, 0xB2, 0xB3, 0xB4, 0xB5, 0xB6, 0xB7, 0xB8, 0xB9, 0xBA,
+    0xC2, 0xC3, 0xC4, 0xC5, 0xC6, 0xC7, 0xC8, 0xC9, 0xCA, 0xD2, 0xD3, 0xD4, 0xD5, 0xD6,
+    0xD7, 0xD8, 0xD9, 0xDA, 0xE2, 0xE3, 0xE4, 0xE5, 0xE6, 0xE7, 0xE8, 0xE9, 0xEA, 0xF2,
+    0xF3, 0xF4, 0xF5, 0xF6, 0xF7, 0xF8, 0xF9, 0xFA};
+
 // COS_LUT[x][u] as the float32 literals of natural_c/src/core/dct.c:9-18.
 static const float kCosLut[8][8] = {
     {1.000000f, 0.980785f, 0.923880f, 0.831470f, 0.707107f, 0.555570f, 0.382683f, 0.195090f},
@@ -64,20 +87,26 @@ static const float kCosLut[8][8] = {
     {1.000000f, -0.831470f, 0.382684f, 0.195091f, -0.707107f, 0.980785f, -0.923879f, 0.555570f},
     {1.000000f, -0.980785f, 0.923880f, -0.831470f, 0.707107f, -0.555570f, 0.382684f, -0.195090f}};
 
-void quant_table_for_quality(int quality, uint8_t table[64]) {
-    // quality 0/50 -> the reference's table; otherwise libjpeg scaling (extension, SURVEY.md D4).
+static void scale_table(const uint8_t base[64], int quality, uint8_t table[64]) {
     if (quality <= 0) quality = 50;
     if (quality > 100) quality = 100;
     const int s = quality < 50 ? 5000 / quality : 200 - 2 * quality;
     for (int i = 0; i < 64; ++i) {
-        int q = (kBaseQuant[i] * s + 50) / 100;
+        int q = (base[i] * s + 50) / 100;
         if (q < 1) q = 1;
         if (q > 255) q = 255;
         table[i] = (uint8_t)q;
     }
 }
 
-void build_huffman_words(uint32_t words[272]) {
+void quant_table_for_quality(int quality, uint8_t table[64]) {
+    // quality 0/50 -> the reference's table; otherwise libjpeg scaling (extension, SURVEY.md D4).
+    scale_table(kBaseQuant, quality, table);
+}
+
+void chroma_quant_table_for_quality(int quality, uint8_t table[64]) { scale_table(kBaseQuantChroma, quality, table); }
+
+static void fill_huffman_words(const uint8_t dc_counts[16], const uint8_t ac_counts[16], const uint8_t *ac_symbols, uint32_t words[272]) {
     // Canonical codes (natural_c/src/core/huffman.c:89-104) packed as len<<16 | code.
     // Symbols the spec does not list stay 0 (length 0: the reference emits no code bits
     // for them, huffman.c:36).
@@ -90,15 +119,17 @@ void build_huffman_words(uint32_t words[272]) {
             code <<= 1;
         }
     };
-    fill(kAcCounts, kAcSymbols, words);
-    fill(kDcCounts, kDcSymbols, words + 256);
+    fill(ac_counts, ac_symbols, words);
+    fill(dc_counts, kDcSymbols, words + 256);
 }
 
-void build_code_table(uint32_t words[kCodeWords]) {
+void build_huffman_words(uint32_t words[272]) { fill_huffman_words(kDcCounts, kAcCounts, kAcSymbols, words); }
+void build_huffman_words_chroma(uint32_t words[272]) { fill_huffman_words(kDcCountsChroma, kAcCountsChroma, kAcSymbolsChroma, words); }
+
+static void fill_code_table(const uint32_t hw[272], uint32_t words[kCodeWords]) {
     // The coder's view of the same codes (jpegamd_internal.h: entry (row, fb)).  rle.c:9-35 (size, amplitude), rle.c:99-123
-    // (ZRL, run/size symbol, EOB), huffman.c:145-188 (code, then amplitude bits).
-    uint32_t hw[272];
-    build_huffman_words(hw);
+    // (ZRL, run/size symbol, EOB), huffman.c:145-188 (code, then amplitude bits).  The ZRL codes themselves are the kernel's
+    // (zrl_prefix): the entry only counts them.
     std::memset(words, 0, kCodeWords * sizeof(uint32_t));
     auto entry = [](uint32_t w, uint32_t size, uint32_t zrl) -> uint32_t {
         const uint32_t clen = w >> 16, code = w & 0xFFFFu;
@@ -121,6 +152,18 @@ void build_code_table(uint32_t words[kCodeWords]) {
         }
 }
 
+void build_code_table(uint32_t words[kCodeWords]) {
+    uint32_t hw[272];
+    build_huffman_words(hw);
+    fill_code_table(hw, words);
+}
+
+void build_code_table_chroma(uint32_t words[kCodeWords]) {
+    uint32_t hw[272];
+    build_huffman_words_chroma(hw);
+    fill_code_table(hw, words);
+}
+
 size_t build_jfif_prefix(int width, int height, const uint8_t table[64], uint8_t out[328]) {
     // natural_c/src/io/jpeg_handler.c:7-110 (byte layout of the six marker segments).
     uint8_t *p = out;
@@ -138,6 +181,43 @@ size_t build_jfif_prefix(int width, int height, const uint8_t table[64], uint8_t
     std::memcpy(p, kAcCounts, 16); p += 16; std::memcpy(p, kAcSymbols, 162); p += 162;
     be16(0xFFDA); be16(8); *p++ = 1; *p++ = 1; *p++ = 0; *p++ = 0; *p++ = 63; *p++ = 0;
     return (size_t)(p - out);
+}
+
+size_t build_jfif_prefix_color(int width, int height, const uint8_t luma[64], const uint8_t chroma[64], int sub420,
+                               uint8_t out[kColorPrefixMax]) {
+    // The grayscale prefix's SOI + APP0, then the colour headers (colour scans).
+    uint8_t *p = out;
+    auto be16 = [&](unsigned v) { *p++ = (uint8_t)(v >> 8); *p++ = (uint8_t)v; };
+    be16(0xFFD8); be16(0xFFE0); be16(16);
+    std::memcpy(p, "JFIF", 5); p += 5;
+    be16(0x0101); *p++ = 1; be16(96); be16(96); *p++ = 0; *p++ = 0;
+    be16(0xFFDB); be16(2 + 2 * 65);
+    *p++ = 0;
+    for (int i = 0; i < 64; ++i) *p++ = luma[kZigzagHost[i]];
+    *p++ = 1;
+    for (int i = 0; i < 64; ++i) *p++ = chroma[kZigzagHost[i]];
+    be16(0xFFC0); be16(8 + 3 * 3); *p++ = 8; be16((uint16_t)height); be16((uint16_t)width); *p++ = 3;
+    *p++ = 1; *p++ = sub420 ? 0x22 : 0x11; *p++ = 0;
+    *p++ = 2; *p++ = 0x11; *p++ = 1;
+    *p++ = 3; *p++ = 0x11; *p++ = 1;
+    auto dht = [&](int tc_th, const uint8_t counts[16], const uint8_t *symbols) {
+        int n = 0;
+        for (int i = 0; i < 16; ++i) n += counts[i];
+        be16(0xFFC4); be16((unsigned)(3 + 16 + n)); *p++ = (uint8_t)tc_th;
+        std::memcpy(p, counts, 16); p += 16; std::memcpy(p, symbols, (size_t)n); p += n;
+    };
+    dht(0x00, kDcCounts, kDcSymbols);
+    dht(0x10, kAcCounts, kAcSymbols);
+    dht(0x01, kDcCountsChroma, kDcSymbols);
+    dht(0x11, kAcCountsChroma, kAcSymbolsChroma);
+    color_sos(1, p); p += kSosBytes;
+    return (size_t)(p - out);
+}
+
+void color_sos(int component, uint8_t out[kSosBytes]) {
+    // SOS, Ns = 1: component `component`, tables 0/0 (Y) or 1/1 (Cb, Cr), Ss = 0, Se = 63, Ah/Al = 0
+    const uint8_t s[kSosBytes] = {0xFF, 0xDA, 0x00, 0x08, 0x01, (uint8_t)component, (uint8_t)(component == 1 ? 0x00 : 0x11), 0, 63, 0};
+    std::memcpy(out, s, kSosBytes);
 }
 
 namespace {

@@ -43,7 +43,8 @@ struct DeviceBuf {
 };
 
 // Encode device-resident pixels into a host vector (JFIF file bytes).
-int64_t encode_to_host(const JpegAmdImage &img, std::vector<uint8_t> &out, JpegAmdStats *st) {
+// subsampling 0: the grayscale file; JPEGAMD_SUBSAMPLE_444 / _420: the colour file (jpegamd_encode_color_async).
+int64_t encode_to_host(const JpegAmdImage &img, std::vector<uint8_t> &out, JpegAmdStats *st, int32_t subsampling = 0) {
     uint64_t *size_dev = nullptr;
     JpegAmdEncoder *enc = jpegamd::shared_context(img.width, img.height, &size_dev);
     if (!enc) return JPEGAMD_ERR_NO_DEVICE;
@@ -52,11 +53,15 @@ int64_t encode_to_host(const JpegAmdImage &img, std::vector<uint8_t> &out, JpegA
     for (int attempt = 0; attempt < 2; ++attempt) {
         DeviceBuf d;
         if (!d.alloc(cap)) return JPEGAMD_ERR_HIP;
-        int32_t rc = jpegamd_encode_async(enc, &img, d.p, cap, size_dev, 1, nullptr);
+        int32_t rc = subsampling ? jpegamd_encode_color_async(enc, &img, subsampling, d.p, cap, size_dev, nullptr)
+                                 : jpegamd_encode_async(enc, &img, d.p, cap, size_dev, 1, nullptr);
         if (rc) return rc;
         JpegAmdStats local;
         rc = jpegamd_encoder_finish(enc, &local);
-        if (rc == JPEGAMD_ERR_HUFF_CAPACITY && attempt == 0) { cap = jpegamd_max_jfif_bytes(img.width, img.height); continue; }
+        if (rc == JPEGAMD_ERR_HUFF_CAPACITY && attempt == 0) {
+            cap = subsampling ? jpegamd_max_jfif_bytes_color(img.width, img.height, subsampling) : jpegamd_max_jfif_bytes(img.width, img.height);
+            continue;
+        }
         if (rc) return rc;
         out.resize(local.jfif_bytes);
         if (hipMemcpy(out.data(), d.p, local.jfif_bytes, hipMemcpyDeviceToHost) != hipSuccess) return JPEGAMD_ERR_HIP;
@@ -84,8 +89,17 @@ extern "C" int32_t jpegamd_parse_bmp(const uint8_t *bmp, uint64_t bmp_len, JpegA
     return JPEGAMD_OK;
 }
 
+// subsampling 0: the grayscale file (jpegamd_encode_bmp_memory); 444 / 420: the colour file (jpegamd_encode_bmp_memory_color)
+static int64_t encode_bmp_memory(const uint8_t *bmp, uint64_t bmp_len, int32_t quality, int32_t subsampling, uint8_t *out,
+                                 uint64_t out_cap);
+
 extern "C" int64_t jpegamd_encode_bmp_memory(const uint8_t *bmp, uint64_t bmp_len, int32_t quality, uint8_t *out,
                                              uint64_t out_cap) {
+    return encode_bmp_memory(bmp, bmp_len, quality, 0, out, out_cap);
+}
+
+static int64_t encode_bmp_memory(const uint8_t *bmp, uint64_t bmp_len, int32_t quality, int32_t subsampling, uint8_t *out,
+                                 uint64_t out_cap) {
     JpegAmdImage img;
     uint64_t off = 0;
     int32_t rc = jpegamd_parse_bmp(bmp, bmp_len, &img, &off);
@@ -98,11 +112,17 @@ extern "C" int64_t jpegamd_encode_bmp_memory(const uint8_t *bmp, uint64_t bmp_le
     img.pixels = d.p;
     img.quality = quality;
     std::vector<uint8_t> jf;
-    const int64_t n = encode_to_host(img, jf, nullptr);
+    const int64_t n = encode_to_host(img, jf, nullptr, subsampling);
     if (n < 0) return n;
     if ((uint64_t)n > out_cap || !out) return JPEGAMD_ERR_HUFF_CAPACITY;
     std::memcpy(out, jf.data(), (size_t)n);
     return n;
+}
+
+extern "C" int64_t jpegamd_encode_bmp_memory_color(const uint8_t *bmp, uint64_t bmp_len, int32_t quality, int32_t subsampling,
+                                                   uint8_t *out, uint64_t out_cap) {
+    if (subsampling != JPEGAMD_SUBSAMPLE_444 && subsampling != JPEGAMD_SUBSAMPLE_420) return JPEGAMD_ERR_ARG;
+    return encode_bmp_memory(bmp, bmp_len, quality, subsampling, out, out_cap);
 }
 
 // ---------------------------------------------------------------------------------------

@@ -15,7 +15,8 @@ _PKG_ROOT = Path(__file__).resolve().parents[2]          # .../jpeg-image-compre
 LIB_PATH = Path(os.environ.get("JPEGAMD_LIB") or (_PKG_ROOT / "libjpegamd.so"))
 HEADER_PATH = _PKG_ROOT.parent / "include" / "jpeg_compression.h"
 
-ORDER_BGR, ORDER_RGB = 0, 1
+ORDER_BGR, ORDER_RGB, ORDER_GRAY = 0, 1, 2                  # JPEGAMD_ORDER_* (GRAY: one byte per pixel, the luma itself)
+SUBSAMPLE_444, SUBSAMPLE_420 = 1, 2                          # JPEGAMD_SUBSAMPLE_* (colour files)
 JFIF_PREFIX_BYTES = 328
 
 ERR_NAMES = {0: "OK", -1: "ERR_ARG", -2: "ERR_NO_DEVICE", -3: "ERR_HIP", -4: "ERR_NOT_INIT", -5: "ERR_TOO_LARGE",
@@ -91,6 +92,12 @@ def _load() -> C.CDLL:
         "freeBMPImage": (None, [C.POINTER(BMPImage)]),
         "saveJPEGGrayscale": (C.c_bool, [C.c_char_p, C.POINTER(BMPImage)]),
         "jpegamd_encode_bmp_memory": (i64, [vp, u64, i32, vp, u64]),
+        "jpegamd_encode_bmp_memory_color": (i64, [vp, u64, i32, i32, vp, u64]),
+        "jpegamd_max_jfif_bytes_color": (u64, [i32, i32, i32]),
+        "jpegamd_encode_color_async": (i32, [vp, C.POINTER(Image), i32, vp, u64, vp, vp]),
+        "jpegamd_debug_chroma_quant_table": (i32, [i32, vp]),
+        "jpegamd_debug_chroma_mfma_consts": (i32, [i32, vp, vp, vp, vp, vp, vp]),
+        "jpegamd_debug_color_profile": (i32, [vp, i32, vp]),
         "jpegamd_parse_bmp": (i32, [vp, u64, C.POINTER(Image), C.POINTER(u64)]),
         "jpegamd_gather_streams": (i32, [vp, i32, i32, i32, vp, u64, i32, vp, vp, u64, vp]),
         "jpegamd_encode_rows_async": (i32, [vp, C.POINTER(Image), i32, i32, vp]),
@@ -112,7 +119,9 @@ EXPORTED = ("jpegamd_encoder_create jpegamd_encoder_destroy jpegamd_max_jfif_byt
             "jpegamd_synth_bmp jpegamd_version jpegamd_debug_quant_table jpegamd_segment_meta_words jpegamd_debug_mfma_consts jpegamd_debug_group_thresholds jpegamd_debug_mfma_offsets jpegamd_debug_cos_lut JpegCompression_Init JpegCompression_DeInit JpegCompression_Reserve "
             "convertToJpeg JpegCompression_RemoteServiceHandler loadBMPImage freeBMPImage saveJPEGGrayscale "
             "jpegamd_encode_bmp_memory jpegamd_parse_bmp jpegamd_encode_files jpegamd_gather_streams "
-            "jpegamd_encode_rows_async jpegamd_export_segments jpegamd_import_segments jpegamd_finalize_async").split()
+            "jpegamd_encode_rows_async jpegamd_export_segments jpegamd_import_segments jpegamd_finalize_async "
+            "jpegamd_max_jfif_bytes_color jpegamd_encode_color_async jpegamd_encode_bmp_memory_color jpegamd_debug_chroma_quant_table "
+            "jpegamd_debug_chroma_mfma_consts jpegamd_debug_color_profile").split()
 
 
 def quant_table(quality: int = 50):
@@ -121,6 +130,26 @@ def quant_table(quality: int = 50):
     table = np.zeros(64, np.uint8)
     lib.jpegamd_debug_quant_table(quality, table.ctypes.data)
     return table
+
+
+def chroma_quant_table(quality: int = 50):
+    """uint8[64], raster order: the colour files' chroma table (T.81 Annex K, K.2), scaled for `quality` like quant_table."""
+    import numpy as np
+    table = np.zeros(64, np.uint8)
+    lib.jpegamd_debug_chroma_quant_table(quality, table.ctypes.data)
+    return table
+
+
+def chroma_mfma_consts(quality: int = 50):
+    """mfma_consts() for the chroma table: qmul/qthr/bias/zoff/qadd float32[64] by zigzag position, delta float64[64] by raster k,
+    dc_off and scale (table-independent: the luma set's)."""
+    import numpy as np
+    out = {k: np.zeros(64, np.float32) for k in ("qmul", "qthr", "bias", "zoff", "qadd")}
+    delta = np.zeros(64, np.float64)
+    lib.jpegamd_debug_chroma_mfma_consts(quality, out["qmul"].ctypes.data, out["qthr"].ctypes.data, out["bias"].ctypes.data,
+                                         delta.ctypes.data, out["zoff"].ctypes.data, out["qadd"].ctypes.data)
+    luma = mfma_consts(quality)
+    return dict(out, delta=delta, dc_off=luma["dc_off"], scale=luma["scale"])
 
 
 PIPELINE_AUTO, PIPELINE_PAIR, PIPELINE_STITCH = 0, 1, 2                    # JPEGAMD_PIPELINE_*
@@ -206,6 +235,66 @@ def encode_bmp_bytes(bmp: bytes, quality: int = 0) -> bytes:
     raise JpegAmdError(-8, "jpegamd_encode_bmp_memory")
 
 
+def max_jfif_bytes_color(width: int, height: int, subsampling: int = SUBSAMPLE_420) -> int:
+    return int(lib.jpegamd_max_jfif_bytes_color(width, height, subsampling))
+
+
+def encode_bmp_bytes_color(bmp: bytes, quality: int = 0, subsampling: int = SUBSAMPLE_420) -> bytes:
+    """BMP file bytes -> colour JFIF file bytes (YCbCr, three scans) through the device."""
+    img, _ = parse_bmp(bmp)
+    cap = max_jfif_bytes_color(img.width, img.height, subsampling) or 1
+    out = (C.c_uint8 * cap)()
+    n = lib.jpegamd_encode_bmp_memory_color(bmp, len(bmp), quality, subsampling, out, cap)
+    if n < 0:
+        raise JpegAmdError(int(n), "jpegamd_encode_bmp_memory_color")
+    return bytes(out[:n])
+
+
+_tensor_encoders = {}
+
+
+def encode_tensor(t, quality: int = 0, subsampling: int = SUBSAMPLE_420) -> bytes:
+    """A uint8 DEVICE tensor -> JFIF file bytes: [H, W] a grayscale file (the tensor is the luma), [H, W, 3] (R, G, B) a colour file.
+    Rows may be strided (t.stride(0) bytes apart); pixels within a row must be packed.  Runs on the tensor's device and the
+    current stream; one encoder context per device is kept and grown as needed."""
+    import torch
+    if t.dtype != torch.uint8 or not t.is_cuda:
+        raise ValueError("encode_tensor needs a uint8 device tensor")
+    if t.dim() == 2:
+        h, w = t.shape
+        if t.stride(1) != 1:
+            raise ValueError("pixels of a row must be packed (stride(1) == 1)")
+        order = ORDER_GRAY
+    elif t.dim() == 3 and t.shape[2] == 3:
+        h, w = t.shape[0], t.shape[1]
+        if t.stride(2) != 1 or t.stride(1) != 3:
+            raise ValueError("pixels of a row must be packed RGB (stride(1) == 3, stride(2) == 1)")
+        order = ORDER_RGB
+    else:
+        raise ValueError("encode_tensor takes [H, W] or [H, W, 3]")
+    dev = t.device.index if t.device.index is not None else torch.cuda.current_device()
+    with torch.cuda.device(dev):
+        enc, mw, mh = _tensor_encoders.get(dev, (None, 0, 0))
+        if enc is None or w > mw or h > mh:
+            mw, mh = max(w, mw), max(h, mh)
+            if enc is not None:
+                enc.close()
+            enc = Encoder(mw, mh)
+            _tensor_encoders[dev] = (enc, mw, mh)
+        cap = max_jfif_bytes(w, h) if order == ORDER_GRAY else max_jfif_bytes_color(w, h, subsampling)
+        out = torch.empty(cap, dtype=torch.uint8, device=t.device)
+        size = torch.zeros(1, dtype=torch.int64, device=t.device)
+        stream = torch.cuda.current_stream(t.device).cuda_stream
+        img = Encoder.image(t.data_ptr(), w, h, t.stride(0), bottom_up=False, channel_order=order, quality=quality)
+        if order == ORDER_GRAY:
+            enc.encode_async(img, out.data_ptr(), cap, size.data_ptr(), True, stream)
+        else:
+            enc.encode_color_async(img, subsampling, out.data_ptr(), cap, size.data_ptr(), stream)
+        enc.finish()
+        n = int(size.item())
+        return bytes(out[:n].cpu().numpy().tobytes())
+
+
 class BatchStats(C.Structure):
     _fields_ = [("files_ok", C.c_int32), ("files_failed", C.c_int32), ("bytes_in", C.c_uint64), ("bytes_out", C.c_uint64),
                 ("seconds_total", C.c_double), ("seconds_read", C.c_double), ("seconds_write", C.c_double)]
@@ -276,6 +365,21 @@ class Encoder:
                                       1 if with_container else 0, C.c_void_p(stream))
         if rc:
             raise JpegAmdError(rc, "jpegamd_encode_async")
+
+    def encode_color_async(self, img: Image, subsampling: int, out_ptr: int, out_cap: int, size_ptr: int, stream: int = 0):
+        """The colour file of an RGB / BGR image (jpegamd_encode_color_async): SUBSAMPLE_444 or SUBSAMPLE_420."""
+        rc = lib.jpegamd_encode_color_async(self._h, C.byref(img), int(subsampling), C.c_void_p(out_ptr), out_cap, C.c_void_p(size_ptr),
+                                            C.c_void_p(stream))
+        if rc:
+            raise JpegAmdError(rc, "jpegamd_encode_color_async")
+
+    def color_profile(self, slot: int):
+        """Per-kernel ns of a profiled colour encode: planes, (tile, merge, finalize) x Y / Cb / Cr, append."""
+        ns = (C.c_uint64 * 11)()
+        rc = lib.jpegamd_debug_color_profile(self._h, slot, ns)
+        if rc:
+            raise JpegAmdError(rc, "jpegamd_debug_color_profile")
+        return list(ns)
 
     def encode_batch_async(self, imgs, out_ptrs, out_cap: int, size_ptrs, with_container: bool = True, stream: int = 0):
         """`len(imgs)` images of one geometry (<= MAX_BATCH) through ONE launch of each kernel; the context must hold

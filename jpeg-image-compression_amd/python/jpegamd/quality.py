@@ -74,6 +74,37 @@ def analyze(bmp: bytes, jpeg: bytes) -> dict:
             "mse": m, "psnr": psnr(m), "ssim": ssim(go, gc)}
 
 
+def decode_jpeg_rgb(jpeg: bytes) -> np.ndarray:
+    """Decode a colour file (jpegamd_encode_color_async) with Pillow -> uint8 [H, W, 3] (R, G, B)."""
+    from PIL import Image
+
+    img = Image.open(io.BytesIO(jpeg))
+    img.load()
+    if img.format != "JPEG" or img.mode != "RGB":
+        raise ValueError(f"not a colour baseline JPEG: format={img.format} mode={img.mode}")
+    return np.asarray(img, dtype=np.uint8)
+
+
+def analyze_color(bmp: bytes, jpeg: bytes) -> dict:
+    """PSNR of a colour file against its original: over R, G, B together, and per channel of Pillow's YCbCr of both pictures."""
+    from PIL import Image
+
+    orig = Image.open(io.BytesIO(bmp)).convert("RGB")
+    comp = Image.open(io.BytesIO(jpeg))
+    comp.load()
+    if orig.size != comp.size:
+        raise ValueError(f"dimensions differ: original {orig.size}, compressed {comp.size}")
+    if comp.mode != "RGB":
+        raise ValueError(f"not a colour file: mode {comp.mode}")
+    r = {"width": orig.size[0], "height": orig.size[1], "size_original": len(bmp), "size_compressed": len(jpeg),
+         "bpp": 8.0 * len(jpeg) / (orig.size[0] * orig.size[1]),
+         "psnr_rgb": psnr(mse(np.asarray(orig, np.float64), np.asarray(comp, np.float64)))}
+    yo, yc = np.asarray(orig.convert("YCbCr"), np.float64), np.asarray(comp.convert("YCbCr"), np.float64)
+    for i, name in enumerate(("y", "cb", "cr")):
+        r["psnr_" + name] = psnr(mse(yo[:, :, i], yc[:, :, i]))
+    return r
+
+
 def format_report(r: dict) -> str:
     lines = ["-" * 50, "ANALYSIS RESULTS", "-" * 50,
              f"File Size Orig : {r['size_original']} bytes", f"File Size Comp : {r['size_compressed']} bytes",

@@ -1,12 +1,12 @@
 #!/usr/bin/env python3
-"""Static instruction census of k_tile_encode<false> between the TSTAMP markers.
+"""Static instruction census of k_tile_encode<false> (the RGB instantiation) between the TSTAMP markers.
   hipcc ... -DJPEGAMD_MARKS --save-temps=obj -c csrc/jpegamd_tile_pipeline.hip ; isa_census.py file.s"""
 import re
 import sys
 from collections import Counter
 
 src = open(sys.argv[1]).read()
-m = re.search(r"^_ZN7jpegamd13k_tile_encodeILb0EEE.*?:\n(.*?)\n\s*s_endpgm", src, re.S | re.M)
+m = re.search(r"^_ZN7jpegamd13k_tile_encodeILb0ELi0ELj11ELj2041EEE.*?:\n(.*?)\n\s*s_endpgm", src, re.S | re.M)
 body = m.group(1).splitlines()
 phase = "pre"
 cnt = {}
