@@ -129,3 +129,63 @@ def test_gray_order_and_colour_entries_are_declared(jpegamd):
     assert jpegamd.ORDER_GRAY == 2 and (jpegamd.SUBSAMPLE_444, jpegamd.SUBSAMPLE_420) == (1, 2)
     for name in ("jpegamd_encode_color_async", "jpegamd_encode_bmp_memory_color", "jpegamd_max_jfif_bytes_color"):
         assert name in jpegamd.EXPORTED and hasattr(jpegamd.lib, name)
+
+
+# ---- the fixture builders of tests/test_gpu_color_edges.py (tests/color_fixtures.py) ---------------------------------------
+def test_rgb_for_plane_meets_the_target_plane_exactly():
+    import color_fixtures as cf
+    rng = np.random.default_rng(12)
+    every = np.arange(256, dtype=np.uint8).reshape(16, 16)
+    for target in (every, rng.integers(0, 256, (9, 13), np.uint8), np.zeros((3, 5), np.uint8), np.full((2, 7), 255, np.uint8)):
+        base = rng.integers(0, 256, target.shape, np.uint8)
+        for which, idx in (("cb", 0), ("cr", 1)):
+            for sub in (cm.SUB_444, cm.SUB_420):
+                for b in (None, base):
+                    rgb = cf.rgb_for_plane(target, which, sub, base=b)
+                    assert np.array_equal(cm.chroma_planes(rgb, sub)[idx], target), (which, sub, target.shape)
+            # odd picture sizes at 4:2:0: the last column / row replicated, the plane unchanged
+            h, w = 2 * target.shape[0] - 1, 2 * target.shape[1] - 1
+            rgb = cf.rgb_for_plane(target, which, cm.SUB_420, shape=(h, w))
+            assert rgb.shape == (h, w, 3) and np.array_equal(cm.chroma_planes(rgb, cm.SUB_420)[idx], target)
+
+
+def test_chroma_symbol_fixture_covers_every_symbol_class(oracle):
+    """The chroma scan of the symbol fixture holds every DC size 0..11, every AC size 1..10, every run 0..15, ZRLs, EOBs and a block
+    whose zigzag 63 is non-zero -- counted from the model's own symbol list, so the fixture cannot quietly lose any of them."""
+    import color_fixtures as cf
+    plane = cf.symbol_plane(oracle)
+    cov = cf.chroma_symbol_coverage(oracle, plane)
+    assert cov["dc_sizes"] == set(range(12))
+    assert cov["sizes"] == set(range(1, 11))
+    assert cov["runs"] == set(range(16))
+    assert cov["zrl"] > 0 and cov["eob"] > 0 and cov["no_eob"] > 0
+    # of the 162 K.6 codes (EOB, ZRL, 16 runs x 10 sizes) a baseline block cannot make every one (at most 63 - run
+    # positions, and high frequencies cap the amplitude); measured 132 when the fixture was written
+    reached = len(cov["codes"]) + 2
+    print(f"chroma symbol fixture: {reached} of 162 K.6 codes, {plane.shape[1] // 8} x {plane.shape[0] // 8} blocks")
+    assert reached >= 130
+    # the fixture's blocks through the RGB pictures the GPU test sends
+    for which, idx in (("cb", 0), ("cr", 1)):
+        for sub in (cm.SUB_444, cm.SUB_420):
+            assert np.array_equal(cm.chroma_planes(cf.rgb_for_plane(plane, which, sub), sub)[idx], plane)
+
+
+def test_chroma_tie_fixture_sits_on_rounding_ties(jpegamd, oracle):
+    """At the tie quality, many coefficients of the tie plane, exact-order value over the chroma step, lie within the guard band
+    (the chroma constants' delta) of a half: the kernel cannot settle them on the fast path and must take the exact-order fallback."""
+    import color_fixtures as cf
+    plane = cf.tie_plane()
+    h, w = plane.shape
+    blocks = plane.reshape(h // 8, 8, w // 8, 8).transpose(0, 2, 1, 3).reshape(-1, 8, 8)
+    f = oracle.dct_blocks((blocks.astype(np.int16) - 128).astype(np.int8)).reshape(-1, 64).astype(np.float64)
+    z = f / cm.scaled_table(cm.CHROMA_Q, cf.TIE_QUALITY).astype(np.float64)[None, :]
+    near = np.abs(np.abs(z) % 1 - 0.5) <= jpegamd.chroma_mfma_consts(cf.TIE_QUALITY)["delta"][None, :]
+    assert near.sum() >= 100
+
+
+def test_extreme_plane_is_the_grayscale_block_set(jpegamd):
+    import color_fixtures as cf
+    blocks = cf.extreme_blocks(jpegamd.cos_lut())
+    assert len(blocks) == 64 * 4 + 4 + 6 + 58
+    p = cf.extreme_plane(jpegamd.cos_lut())
+    assert p.shape == (8 * ((len(blocks) + 39) // 40), 320) and set(np.unique(p)) <= {0, 1, 127, 128, 255}
