@@ -155,6 +155,21 @@ int32_t jpegamd_encode_batch_async(JpegAmdEncoder *enc, const JpegAmdImage *imgs
 uint64_t jpegamd_max_jfif_bytes_color(int32_t width, int32_t height, int32_t subsampling);
 int32_t jpegamd_encode_color_async(JpegAmdEncoder *enc, const JpegAmdImage *img, int32_t subsampling, void *out_dev,
                                    uint64_t out_capacity, uint64_t *out_size_dev, void *stream);
+/* The colour files of `count` pictures (1 .. JPEGAMD_MAX_BATCH) of ONE geometry -- the rules of jpegamd_encode_batch_async, BGR or
+ * RGB only -- with one launch of each kernel: the chroma planes of all pictures, the Y scans as one batch, and the Cb and Cr planes
+ * of all pictures as batches of planes (one launch for count <= 16 at 4:2:0 on a context created for count x H with H a multiple
+ * of 16; more where the context's scratch holds fewer planes).  outs_dev[i] / *out_sizes_dev[i] receive exactly what
+ * jpegamd_encode_color_async writes for imgs[i]; a picture whose file does not fit out_capacity gets size 0 and nothing past
+ * out_capacity, the others are unaffected, and jpegamd_encoder_finish returns JPEGAMD_ERR_HUFF_CAPACITY.  The context must hold
+ * count x the tiles and segments of one picture, i.e. count x its block rows: jpegamd_encoder_create(W, count * H8) with H8 = H
+ * rounded up to a multiple of 8 (count * H is too small when H is not a multiple of 8); JPEGAMD_ERR_TOO_LARGE otherwise.  No host
+ * synchronisation inside the call.  jpegamd_encoder_finish then reports the last picture's size; entropy_bits, stuffed_bytes and
+ * exact_fallbacks are sums over every picture and scan.  With profiling on, a batch records ns_total only (the whole call).  The
+ * colour batch scratch (2 x count planes and chroma scans) is sized for the call's real plane geometry and grown when a later
+ * batch needs more. */
+int32_t jpegamd_encode_color_batch_async(JpegAmdEncoder *enc, const JpegAmdImage *imgs, int32_t count, int32_t subsampling,
+                                         void *const *outs_dev, uint64_t out_capacity, uint64_t *const *out_sizes_dev,
+                                         void *stream);
 
 /* Which kernels follow k_tile_encode for whole pictures (no reference counterpart: a tuning knob, results are byte-identical).
  *   PAIR    k_segment_merge + k_finalize: the tiles' bit strings joined per segment, then stitched behind a kernel boundary;

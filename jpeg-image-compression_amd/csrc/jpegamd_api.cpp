@@ -9,6 +9,7 @@
 
 #include <cstdio>
 #include <cstdlib>
+#include <algorithm>
 #include <cstring>
 #include <mutex>
 #include <new>
@@ -61,6 +62,7 @@ struct JpegAmdEncoder {
         hipEvent_t ev[6]; bool merged;   // begin / end of k_tile_encode, [k_segment_merge,] k_stitch or k_finalize (the kernels' own timestamps)
         // a colour encode (made on the slot's first one): k_chroma_planes, 3 x the six above, k_append_scans
         std::vector<hipEvent_t> cev; bool color = false; bool cmerged[3] = {false, false, false};
+        bool cbatch = false;             // a colour batch: only cev[0] (k_chroma_planes_batch begin) and cev[21] (k_append_scans_batch end)
     };
     std::vector<EventSet> ring;
     uint64_t calls = 0;          // encodes enqueued since profiling was (re)enabled
@@ -84,6 +86,10 @@ struct JpegAmdEncoder {
         int cur_quality = -1;
         int hdr_w = -1, hdr_h = -1, hdr_q = -1, hdr_sub = -1;
         int hdr_len = 0;
+        // colour batches (jpegamd_encode_color_batch_async), sized for the planes and scans of the largest batch so far
+        uint8_t *bmeta = nullptr;           // ScanStats [kBatchLaunches], u64 pic [kMaxBatch][kPicStatWords], y_size [kMaxBatch], c_size [2 kMaxBatch]
+        uint8_t *bplanes = nullptr, *bscans = nullptr;
+        size_t bplanes_cap = 0, bscans_cap = 0;
     } color;
 };
 
@@ -216,6 +222,23 @@ extern "C" uint64_t jpegamd_max_jfif_bytes(int32_t width, int32_t height) {
         }                                                                                       \
     } while (0)
 
+// What a context created for max_w x max_h holds: the bounds every launch on it is checked against.
+struct CtxLimits {
+    int max_segs, max_tiles, max_wgs;
+    size_t words_cap;
+};
+static CtxLimits context_limits(int max_w, int max_h) {
+    CtxLimits l;
+    l.max_segs = segs_for(max_w, max_h, nullptr, nullptr, nullptr);
+    l.max_tiles = ((max_h + 7) / 8) * (((max_w + 7) / 8 + kTileBlocks - 1) / kTileBlocks);
+    // (room for either segment length: the same blocks as fewer, longer segments need a little more than as many short ones)
+    const size_t w8 = (size_t)l.max_segs * kSegCapWords;
+    const size_t w16 = (size_t)segs_for(max_w, max_h, nullptr, nullptr, nullptr, kSegTilesBatch) * seg_cap_words(kSegTilesBatch);
+    l.words_cap = (w8 > w16 ? w8 : w16) + seg_cap_words(kSegTilesBatch);
+    l.max_wgs = l.max_segs + 2;                                    // (a picture never has more workgroups than segments)
+    return l;
+}
+
 extern "C" int32_t jpegamd_encoder_create(JpegAmdEncoder **out, int32_t max_width, int32_t max_height) {
     // (an image is at most 65535 rows -- describe() checks that; a context may reserve room for a batch of them)
     if (!out || max_width <= 0 || max_height <= 0 || max_width > 65535 || max_height > 65535 * kMaxBatch) return JPEGAMD_ERR_ARG;
@@ -232,15 +255,11 @@ extern "C" int32_t jpegamd_encoder_create(JpegAmdEncoder **out, int32_t max_widt
     if (!e->tables_host) { delete e; return JPEGAMD_ERR_HIP; }
     HIP_TRY_CREATE(hipGetDevice(&e->device));
     e->max_w = max_width; e->max_h = max_height;
-    e->max_segs = segs_for(max_width, max_height, nullptr, nullptr, nullptr);
-    e->max_tiles = ((max_height + 7) / 8) * (((max_width + 7) / 8 + kTileBlocks - 1) / kTileBlocks);
+    const CtxLimits lim = context_limits(max_width, max_height);
+    e->max_segs = lim.max_segs;
+    e->max_tiles = lim.max_tiles;
     const size_t segs = (size_t)e->max_segs + 16;                 // k_finalize reads the per-segment arrays four at a time
-    // (room for either segment length: the same blocks as fewer, longer segments need a little more than as many short ones)
-    {
-        const size_t w8 = (size_t)e->max_segs * kSegCapWords;
-        const size_t w16 = (size_t)segs_for(max_width, max_height, nullptr, nullptr, nullptr, kSegTilesBatch) * seg_cap_words(kSegTilesBatch);
-        e->words_cap = (w8 > w16 ? w8 : w16) + seg_cap_words(kSegTilesBatch);
-    }
+    e->words_cap = lim.words_cap;
     HIP_TRY_CREATE(hipMalloc((void **)&e->seg.words, e->words_cap * sizeof(uint32_t)));
     e->seg.words_stride = kSegCapWords;
     HIP_TRY_CREATE(hipMalloc((void **)&e->seg.bits, segs * sizeof(uint32_t)));
@@ -260,7 +279,7 @@ extern "C" int32_t jpegamd_encoder_create(JpegAmdEncoder **out, int32_t max_widt
     HIP_TRY_CREATE(hipMalloc((void **)&e->code_tab, kCodeWords * sizeof(uint32_t)));
     HIP_TRY_CREATE(hipMalloc((void **)&e->tile_ctr, 2 * 64 * 128));      // two sets of ticket-group cache lines, used alternately
     HIP_TRY_CREATE(hipMemset(e->tile_ctr, 0, 2 * 64 * 128));
-    e->max_wgs = e->max_segs + 2;                                          // (a picture never has more workgroups than segments)
+    e->max_wgs = lim.max_wgs;
     HIP_TRY_CREATE(hipMalloc((void **)&e->desc, 12 * (size_t)e->max_wgs * sizeof(uint32_t)));
     HIP_TRY_CREATE(hipMemset(e->desc, 0, 12 * (size_t)e->max_wgs * sizeof(uint32_t)));
     if (std::getenv("JPEGAMD_STAMPS")) {
@@ -288,6 +307,7 @@ extern "C" int32_t jpegamd_encoder_destroy(JpegAmdEncoder *e) {
     hipFree(e->tile_head); hipFree(e->tile_over); hipFree(e->code_tab); hipFree(e->tile_ctr); hipFree(e->desc); hipFree(e->stamps_dev);
     hipFree(e->color.tables_dev); hipFree(e->color.code_tab); hipFree(e->color.huff); hipFree(e->color.hdr); hipFree(e->color.scan_size);
     hipFree(e->color.scan_stats); hipFree(e->color.planes); hipFree(e->color.scans);
+    hipFree(e->color.bmeta); hipFree(e->color.bplanes); hipFree(e->color.bscans);
     for (auto &set : e->ring) { for (auto &ev : set.ev) if (ev) hipEventDestroy(ev); for (auto &ev : set.cev) if (ev) hipEventDestroy(ev); }
     delete e->tables_host;
     delete e;
@@ -334,6 +354,12 @@ static int32_t read_color_slot(JpegAmdEncoder *e, int slot, uint64_t ns[11]) {
 
 static int32_t read_slot(JpegAmdEncoder *e, int slot, JpegAmdStats *stats) {
     if (slot < 0 || (size_t)slot >= e->ring.size()) return JPEGAMD_ERR_ARG;
+    if (e->ring[(size_t)slot].color && e->ring[(size_t)slot].cbatch) {   // a colour batch: the whole call only
+        float ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, e->ring[(size_t)slot].cev[0], e->ring[(size_t)slot].cev[21]));
+        stats->ns_total = (uint64_t)((double)ms * 1e6);
+        return JPEGAMD_OK;
+    }
     if (e->ring[(size_t)slot].color) {            // sums over the three scans; the planes count as transform, the append as pack
         uint64_t ns[11];
         if (int32_t rc = read_color_slot(e, slot, ns)) return rc;
@@ -356,7 +382,8 @@ static int32_t read_slot(JpegAmdEncoder *e, int slot, JpegAmdStats *stats) {
 }
 
 extern "C" int32_t jpegamd_debug_color_profile(JpegAmdEncoder *e, int32_t slot, uint64_t *ns) {
-    if (!e || !ns || slot < 0 || (size_t)slot >= e->ring.size() || !e->ring[(size_t)slot].color) return JPEGAMD_ERR_ARG;
+    if (!e || !ns || slot < 0 || (size_t)slot >= e->ring.size() || !e->ring[(size_t)slot].color || e->ring[(size_t)slot].cbatch)
+        return JPEGAMD_ERR_ARG;
     return read_color_slot(e, slot, ns);
 }
 
@@ -470,8 +497,17 @@ static int launch_transform_and_entropy(JpegAmdEncoder *e, const ImageDesc &im, 
     return launch_segment_merge(ea, stream, ev ? (void *const *)(ev + 2) : nullptr);
 }
 
+// Where a scan of a colour file goes: its own header bytes in front, EOI or not, its own statistics record.
+struct ScanTarget {
+    const uint8_t *prefix;
+    int32_t prefix_len, write_eoi;
+    ScanStats *stats;
+    bool chroma;
+};
+
 static int run_finalize_batch(JpegAmdEncoder *e, const ImageDesc &im, void *const *outs_dev, uint64_t out_capacity,
-                              uint64_t *const *out_sizes_dev, int32_t with_container, hipStream_t stream, hipEvent_t *ev = nullptr) {
+                              uint64_t *const *out_sizes_dev, int32_t with_container, hipStream_t stream, hipEvent_t *ev = nullptr,
+                              const ScanTarget *tgt = nullptr) {
     FinalizeArgs fa;
     std::memset(&fa, 0, sizeof(fa));
     fa.seg = e->seg;
@@ -483,6 +519,7 @@ static int run_finalize_batch(JpegAmdEncoder *e, const ImageDesc &im, void *cons
     fa.out_capacity = out_capacity; fa.stats = e->stats_dev;
     fa.prefix = e->prefix; fa.prefix_len = with_container ? JPEGAMD_JFIF_PREFIX_BYTES : 0;
     fa.write_eoi = with_container ? 1 : 0;
+    if (tgt) { fa.prefix = tgt->prefix; fa.prefix_len = tgt->prefix_len; fa.write_eoi = tgt->write_eoi; fa.stats = tgt->stats; }
     return launch_finalize(fa, stream, (void *const *)ev);
 }
 
@@ -490,19 +527,12 @@ static int run_finalize_batch(JpegAmdEncoder *e, const ImageDesc &im, void *cons
 // up to 8192^2-class pictures and on dense content (profiles/r04_notes_experiments.txt) -- or the single-pass k_stitch, whose
 // look-back reads at most 256 predecessors per round where k_finalize's scan reads every predecessor of every workgroup.
 constexpr int kStitchAutoSegs = 16384;      // 8-tile segments of ONE picture from which AUTO takes k_stitch (a 16384^2 picture)
-static bool use_stitch(const JpegAmdEncoder *e, int w, int h) {
-    if (e->pipeline == JPEGAMD_PIPELINE_PAIR) return false;
-    if (e->pipeline == JPEGAMD_PIPELINE_STITCH) return true;
+static bool use_stitch_for(int pipeline, int w, int h) {
+    if (pipeline == JPEGAMD_PIPELINE_PAIR) return false;
+    if (pipeline == JPEGAMD_PIPELINE_STITCH) return true;
     return segs_for(w, h, nullptr, nullptr, nullptr) >= kStitchAutoSegs;
 }
-
-// Where a scan of a colour file goes: its own header bytes in front, EOI or not, its own statistics record.
-struct ScanTarget {
-    const uint8_t *prefix;
-    int32_t prefix_len, write_eoi;
-    ScanStats *stats;
-    bool chroma;
-};
+static bool use_stitch(const JpegAmdEncoder *e, int w, int h) { return use_stitch_for(e->pipeline, w, h); }
 
 // k_stitch over the tiles k_tile_encode left: whole images, one or a batch.
 static int run_stitch(JpegAmdEncoder *e, const ImageDesc &im, void *const *outs_dev, uint64_t out_capacity,
@@ -743,7 +773,7 @@ extern "C" int32_t jpegamd_encode_batch_async(JpegAmdEncoder *e, const JpegAmdIm
 // chroma constants into context scratch, each behind its SOS (Cr with EOI); k_append_scans copies them behind the Y scan at
 // offsets the device knows.  Everything is stream-ordered: the host never waits between the scans.
 // ---------------------------------------------------------------------------------------------------------
-static int32_t color_alloc(JpegAmdEncoder *e, int w, int h) {
+static int32_t color_alloc_consts(JpegAmdEncoder *e) {
     auto &c = e->color;
     if (!c.tables_dev) {
         HIP_TRY(hipMalloc((void **)&c.tables_dev, sizeof(MfmaTables)));
@@ -763,6 +793,12 @@ static int32_t color_alloc(JpegAmdEncoder *e, int w, int h) {
         color_sos(3, sos + 16);
         HIP_TRY(hipMemcpy(c.hdr + kColorPrefixMax, sos, sizeof(sos), hipMemcpyHostToDevice));
     }
+    return JPEGAMD_OK;
+}
+
+static int32_t color_alloc(JpegAmdEncoder *e, int w, int h) {
+    auto &c = e->color;
+    if (int32_t rc = color_alloc_consts(e)) return rc;
     // planes and scans sized for this picture at 4:4:4 (the larger case), grown when a later picture needs more
     const size_t planes = 2 * (size_t)((w + 3) / 4 * 4) * (size_t)h + 64;
     const size_t scan = (kSosBytes + 2 + scan_bound(blocks_of(w, h)) + 64 + 255) & ~(size_t)255;     // (k_append_scans reads 16 bytes at a time)
@@ -849,7 +885,7 @@ extern "C" int32_t jpegamd_encode_color_async(JpegAmdEncoder *e, const JpegAmdIm
             set.cev.assign(22, nullptr);
             for (auto &ev : set.cev) HIP_TRY(hipEventCreate(&ev));
         }
-        set.color = true;
+        set.color = true; set.cbatch = false;
         cev = set.cev.data();
         ++e->calls;
     }
@@ -890,6 +926,248 @@ extern "C" int32_t jpegamd_encode_color_async(JpegAmdEncoder *e, const JpegAmdIm
     aa.scan_stats = c.scan_stats; aa.stats = e->stats_dev;
     if (launch_append_scans(aa, stream, cev ? (void *const *)(cev + 20) : nullptr)) return JPEGAMD_ERR_HIP;
     e->last_segs = iy.num_segs;
+    e->last_stream = stream;
+    e->pending = true;
+    e->timed = timed;
+    e->last_color = true;
+    return JPEGAMD_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Colour batches: `count` pictures of one geometry.  k_chroma_planes_batch writes all 2 x count chroma planes; Y runs as ONE batch of
+// the RGB path straight into the callers' buffers behind the colour prefix; every Cb and Cr plane shares one geometry and one set of
+// tables, so all of them run through the chroma pipeline as batches of planes -- as few launches as the context's scratch allows --
+// bare (no SOS, no EOI) into per-plane scratch slots; k_picture_stats adds up each launch's tile records per picture and scan; and
+// k_append_scans_batch finishes every picture.  Nothing waits on the host.
+// ---------------------------------------------------------------------------------------------------------
+constexpr int kBatchLaunches = 1 + 2 * kMaxBatch;     // the Y launch, and at most one chroma launch per plane
+
+// How the chroma planes of a batch are grouped into launches: the most planes per launch that kMaxBatch and the context's tiles,
+// segments, segment words (k_segment_merge + k_finalize) or k_stitch workgroups allow -- a group never holds more than fits, whatever
+// the per-row rounding of the plane's geometry -- then spread evenly over the launches that takes.  Returns false only when not
+// even one plane fits.
+struct ChromaPlan { int group, launches, seg_tiles; bool stitch; };
+static int chroma_group_limit(const CtxLimits &l, int cw, int ch, int seg_tiles, bool stitch) {
+    const int64_t bw = (cw + 7) / 8, bh = (ch + 7) / 8;
+    const int64_t tiles = bh * ((bw + kTileBlocks - 1) / kTileBlocks);
+    const int64_t segs = segs_for(cw, ch, nullptr, nullptr, nullptr, seg_tiles);
+    int64_t g = kMaxBatch;
+    g = std::min(g, (int64_t)l.max_tiles / tiles);
+    g = std::min(g, (int64_t)l.max_segs / segs);
+    if (stitch) g = std::min(g, (int64_t)l.max_wgs / stitch_workgroups((int)segs));
+    else g = std::min(g, (int64_t)(l.words_cap / ((size_t)segs * (size_t)seg_cap_words(seg_tiles))));
+    return (int)g;
+}
+static bool chroma_plan(const CtxLimits &l, int pipeline, int cw, int ch, int planes, ChromaPlan *p) {
+    p->stitch = use_stitch_for(pipeline, cw, ch);
+    int g;
+    if (p->stitch) {
+        p->seg_tiles = kSegTilesBatch;                                 // (k_stitch works on segments of 16 tiles)
+        g = chroma_group_limit(l, cw, ch, kSegTilesBatch, true);
+    } else {                                                           // segments of 16 tiles for four planes or more, as a grayscale batch --
+        p->seg_tiles = kSegTiles;                                      // unless that takes more launches
+        g = chroma_group_limit(l, cw, ch, kSegTiles, false);
+        const int g16 = chroma_group_limit(l, cw, ch, kSegTilesBatch, false);
+        if (std::min(g16, planes) >= 4 && g16 >= 1 && (planes + g16 - 1) / g16 <= (planes + g - 1) / std::max(g, 1)) {
+            p->seg_tiles = kSegTilesBatch;
+            g = g16;
+        }
+    }
+    if (g < 1 || planes < 1) return false;
+    p->launches = (planes + g - 1) / g;
+    p->group = (planes + p->launches - 1) / p->launches;
+    return true;
+}
+
+// Host-only (tests): the chroma launches of a colour batch of `count` width x height pictures on a context created for
+// max_width x max_height under `pipeline`: out = {planes per launch, launches, tiles per segment, k_stitch}.  Not part of the
+// public header.
+extern "C" int32_t jpegamd_debug_chroma_groups(int32_t max_width, int32_t max_height, int32_t pipeline, int32_t width, int32_t height,
+                                               int32_t count, int32_t subsampling, int32_t *out) {
+    if (!out || max_width <= 0 || max_height <= 0 || width <= 0 || height <= 0 || count < 1 || count > kMaxBatch) return JPEGAMD_ERR_ARG;
+    if (subsampling != JPEGAMD_SUBSAMPLE_444 && subsampling != JPEGAMD_SUBSAMPLE_420) return JPEGAMD_ERR_ARG;
+    int cw, ch;
+    chroma_dims(width, height, subsampling, &cw, &ch);
+    ChromaPlan p;
+    if (!chroma_plan(context_limits(max_width, max_height), pipeline, cw, ch, 2 * count, &p)) return JPEGAMD_ERR_TOO_LARGE;
+    out[0] = p.group; out[1] = p.launches; out[2] = p.seg_tiles; out[3] = p.stitch ? 1 : 0;
+    return JPEGAMD_OK;
+}
+
+static size_t round_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+constexpr size_t kBatchMetaStats = kBatchLaunches * sizeof(ScanStats);
+constexpr size_t kBatchMetaPic = (size_t)kMaxBatch * kPicStatWords * sizeof(uint64_t);
+constexpr size_t kBatchMetaBytes = kBatchMetaStats + kBatchMetaPic + 3 * kMaxBatch * sizeof(uint64_t);
+
+// The batch's scratch: fixed-size records once, planes and scan slots grown when a call needs more than the context holds.
+static int32_t color_batch_alloc(JpegAmdEncoder *e, size_t planes, size_t scans) {
+    auto &c = e->color;
+    if (!c.bmeta) HIP_TRY(hipMalloc((void **)&c.bmeta, kBatchMetaBytes));
+    if (planes > c.bplanes_cap || scans > c.bscans_cap) {
+        if (e->pending) HIP_TRY(hipStreamSynchronize(e->last_stream));
+        if (planes > c.bplanes_cap) {
+            hipFree(c.bplanes); c.bplanes = nullptr; c.bplanes_cap = 0;
+            HIP_TRY(hipMalloc((void **)&c.bplanes, planes));
+            c.bplanes_cap = planes;
+        }
+        if (scans > c.bscans_cap) {
+            hipFree(c.bscans); c.bscans = nullptr; c.bscans_cap = 0;
+            HIP_TRY(hipMalloc((void **)&c.bscans, scans));
+            c.bscans_cap = scans;
+        }
+    }
+    return JPEGAMD_OK;
+}
+
+extern "C" int32_t jpegamd_encode_color_batch_async(JpegAmdEncoder *e, const JpegAmdImage *imgs, int32_t count, int32_t subsampling,
+                                                    void *const *outs_dev, uint64_t out_capacity, uint64_t *const *out_sizes_dev,
+                                                    void *stream_) {
+    // the arguments first: nothing of the context is read before they are known to be good
+    if (!e || !imgs || !outs_dev || !out_sizes_dev || count < 1 || count > kMaxBatch) return JPEGAMD_ERR_ARG;
+    if (subsampling != JPEGAMD_SUBSAMPLE_444 && subsampling != JPEGAMD_SUBSAMPLE_420) return JPEGAMD_ERR_ARG;
+    const JpegAmdImage &g0 = imgs[0];
+    if (g0.channel_order != JPEGAMD_ORDER_BGR && g0.channel_order != JPEGAMD_ORDER_RGB) return JPEGAMD_ERR_ARG;
+    for (int i = 0; i < count; ++i) {
+        const JpegAmdImage &g = imgs[i];
+        if (!outs_dev[i] || !out_sizes_dev[i] || !g.pixels) return JPEGAMD_ERR_ARG;
+        if (g.width != g0.width || g.height != g0.height || g.row_stride != g0.row_stride || (g.bottom_up != 0) != (g0.bottom_up != 0) ||
+            g.channel_order != g0.channel_order || g.quality != g0.quality)
+            return JPEGAMD_ERR_ARG;
+    }
+    // Y: the grayscale batch's launch plan
+    ImageDesc iy;
+    const bool stitch_y = use_stitch(e, g0.width, g0.height);
+    int seg_tiles = (stitch_y || count >= 4) ? kSegTilesBatch : kSegTiles;
+    int32_t rc = describe(e, &g0, &iy, seg_tiles);
+    if (rc) return rc;
+    if (!stitch_y && seg_tiles != kSegTiles && (size_t)count * iy.num_segs * seg_cap_words(seg_tiles) > e->words_cap) {
+        seg_tiles = kSegTiles;
+        rc = describe(e, &g0, &iy, seg_tiles);
+        if (rc) return rc;
+    }
+    if ((int64_t)count * iy.num_tiles > e->max_tiles || (int64_t)count * iy.num_segs > e->max_segs ||
+        (!stitch_y && (size_t)count * iy.num_segs * seg_cap_words(seg_tiles) > e->words_cap)) return JPEGAMD_ERR_TOO_LARGE;
+    for (int i = 0; i < count; ++i) {
+        iy.batch_pixels[i] = (const uint8_t *)imgs[i].pixels;
+        if ((((uintptr_t)imgs[i].pixels) & 3u) != 0) iy.fast_ok = 0;
+    }
+    iy.batch = count;
+    iy.tile_end = count * iy.num_tiles;
+    iy.seg_end = count * iy.num_segs;
+    // Cb, Cr: 2 count planes at one pitch, in as few launches as the context allows
+    int cw, ch;
+    chroma_dims(g0.width, g0.height, subsampling, &cw, &ch);
+    const int pitch = (cw + 3) / 4 * 4;
+    const int planes = 2 * count;
+    ChromaPlan plan;
+    const CtxLimits lim = {e->max_segs, e->max_tiles, e->max_wgs, e->words_cap};
+    if (!chroma_plan(lim, e->pipeline, cw, ch, planes, &plan)) return JPEGAMD_ERR_TOO_LARGE;
+    const size_t plane_bytes = round_up((size_t)pitch * (size_t)ch, 256);
+    const size_t slot_bytes = round_up(scan_bound(blocks_of(cw, ch)) + 64, 256);      // (k_append_scans_batch reads 16 bytes at a time)
+    rc = color_alloc_consts(e);
+    if (rc) return rc;
+    rc = color_batch_alloc(e, planes * plane_bytes + 256, planes * slot_bytes);
+    if (rc) return rc;
+    rc = prepare_constants(e, &g0, false);
+    if (rc) return rc;
+    rc = prepare_color_constants(e, &g0, subsampling);
+    if (rc) return rc;
+    auto &c = e->color;
+    ScanStats *lstats = reinterpret_cast<ScanStats *>(c.bmeta);
+    unsigned long long *pic = reinterpret_cast<unsigned long long *>(c.bmeta + kBatchMetaStats);
+    uint64_t *y_size = reinterpret_cast<uint64_t *>(c.bmeta + kBatchMetaStats + kBatchMetaPic);
+    uint64_t *c_size = y_size + kMaxBatch;
+    hipStream_t stream = (hipStream_t)stream_;
+
+    const bool timed = !e->ring.empty();
+    hipEvent_t *cev = nullptr;
+    if (timed) {
+        e->last_slot = (int)(e->calls % e->ring.size());
+        auto &set = e->ring[(size_t)e->last_slot];
+        if (set.cev.empty()) {
+            set.cev.assign(22, nullptr);
+            for (auto &ev : set.cev) HIP_TRY(hipEventCreate(&ev));
+        }
+        set.color = true; set.cbatch = true;
+        cev = set.cev.data();
+        ++e->calls;
+    }
+    HIP_TRY(hipMemsetAsync(c.bmeta, 0, kBatchMetaStats + kBatchMetaPic, stream));
+
+    ChromaPlanesBatchArgs pa;
+    std::memset(&pa, 0, sizeof(pa));
+    for (int i = 0; i < count; ++i) pa.pixels[i] = (const uint8_t *)imgs[i].pixels;
+    pa.batch = count;
+    pa.width = g0.width; pa.height = g0.height; pa.row_stride = g0.row_stride; pa.bottom_up = g0.bottom_up ? 1 : 0;
+    pa.rgb = g0.channel_order == JPEGAMD_ORDER_RGB ? 1 : 0;
+    pa.sub420 = subsampling == JPEGAMD_SUBSAMPLE_420 ? 1 : 0;
+    pa.cw = cw; pa.ch = ch; pa.pitch = pitch;
+    pa.plane_bytes = plane_bytes; pa.planes = c.bplanes;
+    hipEvent_t ev_planes[2] = {cev ? cev[0] : nullptr, nullptr};
+    if (launch_chroma_planes_batch(pa, stream, cev ? (void *const *)ev_planes : nullptr)) return JPEGAMD_ERR_HIP;
+
+    // Y: every picture's scan behind the colour prefix, no EOI; its size into y_size
+    {
+        uint64_t *sizes[kMaxBatch];
+        for (int i = 0; i < count; ++i) sizes[i] = y_size + i;
+        const ScanTarget ty = {c.hdr, c.hdr_len, 0, &lstats[0], false};
+        PictureStatsArgs ps = {e->tile_head, e->huff, iy.num_tiles, count, 0, 0, pic};
+        if (stitch_y) {
+            if (launch_transform(e, iy, false, nullptr, nullptr, nullptr, stream, nullptr, kTileSrcRgb)) return JPEGAMD_ERR_HIP;
+            if (launch_picture_stats(ps, stream)) return JPEGAMD_ERR_HIP;
+            if (run_stitch(e, iy, outs_dev, out_capacity, sizes, 1, stream, nullptr, &ty)) return JPEGAMD_ERR_HIP;
+        } else {
+            if (launch_transform_and_entropy(e, iy, false, nullptr, nullptr, nullptr, stream, nullptr, kTileSrcRgb)) return JPEGAMD_ERR_HIP;
+            if (launch_picture_stats(ps, stream)) return JPEGAMD_ERR_HIP;
+            if (run_finalize_batch(e, iy, outs_dev, out_capacity, sizes, 1, stream, nullptr, &ty)) return JPEGAMD_ERR_HIP;
+        }
+    }
+    // Cb, Cr: plane j (picture j / 2) bare into slot j; its size into c_size[j]
+    JpegAmdImage pimg = g0;
+    pimg.width = cw; pimg.height = ch; pimg.row_stride = pitch; pimg.bottom_up = 0; pimg.channel_order = JPEGAMD_ORDER_GRAY;
+    pimg.pixels = c.bplanes;
+    for (int l = 0; l < plan.launches; ++l) {
+        const int first = l * plan.group, n = std::min(plan.group, planes - first);
+        ImageDesc ic;
+        rc = describe(e, &pimg, &ic, plan.seg_tiles);
+        if (rc) return rc;
+        void *outs[kMaxBatch];
+        uint64_t *sizes[kMaxBatch];
+        for (int i = 0; i < n; ++i) {
+            ic.batch_pixels[i] = c.bplanes + (size_t)(first + i) * plane_bytes;
+            outs[i] = c.bscans + (size_t)(first + i) * slot_bytes;
+            sizes[i] = c_size + first + i;
+        }
+        ic.pixels = ic.batch_pixels[0];
+        ic.batch = n;
+        ic.tile_end = n * ic.num_tiles;
+        ic.seg_end = n * ic.num_segs;
+        const ScanTarget tc = {c.hdr, 0, 0, &lstats[1 + l], true};
+        PictureStatsArgs ps = {e->tile_head, c.huff, ic.num_tiles, n, 1, first, pic};
+        if (plan.stitch) {
+            if (launch_transform(e, ic, false, nullptr, nullptr, nullptr, stream, nullptr, kTileSrcChroma)) return JPEGAMD_ERR_HIP;
+            if (launch_picture_stats(ps, stream)) return JPEGAMD_ERR_HIP;
+            if (run_stitch(e, ic, outs, slot_bytes, sizes, 1, stream, nullptr, &tc)) return JPEGAMD_ERR_HIP;
+        } else {
+            if (launch_transform_and_entropy(e, ic, false, nullptr, nullptr, nullptr, stream, nullptr, kTileSrcChroma)) return JPEGAMD_ERR_HIP;
+            if (launch_picture_stats(ps, stream)) return JPEGAMD_ERR_HIP;
+            if (run_finalize_batch(e, ic, outs, slot_bytes, sizes, 1, stream, nullptr, &tc)) return JPEGAMD_ERR_HIP;
+        }
+    }
+    AppendBatchArgs aa;
+    std::memset(&aa, 0, sizeof(aa));
+    for (int i = 0; i < count; ++i) { aa.out[i] = (uint8_t *)outs_dev[i]; aa.out_size[i] = out_sizes_dev[i]; }
+    aa.out_capacity = out_capacity;
+    aa.batch = count; aa.hdr_len = c.hdr_len;
+    aa.y_size = y_size; aa.c_size = c_size;
+    aa.scans = c.bscans; aa.slot_bytes = slot_bytes;
+    aa.sos = c.hdr + kColorPrefixMax;
+    aa.pic = pic;
+    aa.launch_stats = lstats; aa.n_launch = 1 + plan.launches;
+    aa.stats = e->stats_dev;
+    hipEvent_t ev_append[2] = {nullptr, cev ? cev[21] : nullptr};
+    if (launch_append_scans_batch(aa, stream, cev ? (void *const *)ev_append : nullptr)) return JPEGAMD_ERR_HIP;
+    e->last_segs = count * iy.num_segs;
     e->last_stream = stream;
     e->pending = true;
     e->timed = timed;

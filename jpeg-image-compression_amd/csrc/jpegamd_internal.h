@@ -260,6 +260,49 @@ struct AppendArgs {
 };
 int launch_append_scans(const AppendArgs &a, void *stream, void *const *ev = nullptr);
 
+// Colour batches (jpegamd_encode_color_batch_async): `batch` pictures of one geometry, ONE launch of each kernel where the context
+// allows.  k_chroma_planes_batch writes 2 x batch planes, plane j = picture j / 2, Cb (j even) or Cr (j odd), `plane_bytes` apart.
+struct ChromaPlanesBatchArgs {
+    const uint8_t *pixels[kMaxBatch];
+    int32_t batch;
+    int32_t width, height, row_stride, bottom_up;
+    int32_t rgb, sub420;
+    int32_t cw, ch, pitch;
+    uint64_t plane_bytes;               // a multiple of 16
+    uint8_t *planes;
+};
+int launch_chroma_planes_batch(const ChromaPlanesBatchArgs &a, void *stream, void *const *ev = nullptr);
+// k_picture_stats: what the tile records of one k_tile_encode launch add up to per picture and scan -- bits (with the first DC
+// symbol of every tile, which the record leaves out), run/size symbols, exact-order fallbacks -- summed into
+// pic[picture][scan][3].  Launch image i is picture i, scan 0 (luma), or plane first_plane + i (chroma).
+constexpr int kPicStatWords = 9;        // [scan 0..2][bits, symbols, exact]
+struct PictureStatsArgs {
+    const uint32_t *tile_head;
+    const uint32_t *huff;               // the scan's table: DC size s at 256 + s
+    int32_t tiles_per_image, batch;
+    int32_t chroma, first_plane;
+    unsigned long long *pic;            // [picture][kPicStatWords]
+};
+int launch_picture_stats(const PictureStatsArgs &a, void *stream);
+// k_append_scans_batch: per picture, behind its Y scan: SOS(2), the Cb scan, SOS(3), the Cr scan, EOI -- only when the whole file
+// fits; the picture's size (0 when it did not fit); the context's record (last picture's size, sums over every picture and scan).
+struct AppendBatchArgs {
+    uint8_t *out[kMaxBatch];
+    uint64_t *out_size[kMaxBatch];
+    uint64_t out_capacity;
+    int32_t batch, hdr_len;
+    const uint64_t *y_size;             // [batch] prefix + Y scan
+    const uint64_t *c_size;             // [2 batch] bare chroma scans, by plane
+    const uint8_t *scans;               // plane j's scan at scans + j * slot_bytes (slot_bytes a multiple of 16)
+    uint64_t slot_bytes;
+    const uint8_t *sos;                 // SOS(2) at 0, SOS(3) at 16
+    const unsigned long long *pic;      // [batch][kPicStatWords]
+    const ScanStats *launch_stats;      // [n_launch] the records of the Y launch and of every chroma launch
+    int32_t n_launch;
+    ScanStats *stats;                   // the context's record
+};
+int launch_append_scans_batch(const AppendBatchArgs &a, void *stream, void *const *ev = nullptr);
+
 // ---- host-side constant derivation (quant_consts.cpp) ----------------------------------
 void quant_table_for_quality(int quality, uint8_t table[64]);
 // T.81 Annex K K.2 (the chroma table), scaled for `quality` with the rule of quant_table_for_quality

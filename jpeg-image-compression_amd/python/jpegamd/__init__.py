@@ -95,6 +95,8 @@ def _load() -> C.CDLL:
         "jpegamd_encode_bmp_memory_color": (i64, [vp, u64, i32, i32, vp, u64]),
         "jpegamd_max_jfif_bytes_color": (u64, [i32, i32, i32]),
         "jpegamd_encode_color_async": (i32, [vp, C.POINTER(Image), i32, vp, u64, vp, vp]),
+        "jpegamd_encode_color_batch_async": (i32, [vp, C.POINTER(Image), i32, i32, C.POINTER(C.c_void_p), u64, C.POINTER(C.c_void_p), vp]),
+        "jpegamd_debug_chroma_groups": (i32, [i32, i32, i32, i32, i32, i32, i32, vp]),
         "jpegamd_debug_chroma_quant_table": (i32, [i32, vp]),
         "jpegamd_debug_chroma_mfma_consts": (i32, [i32, vp, vp, vp, vp, vp, vp]),
         "jpegamd_debug_color_profile": (i32, [vp, i32, vp]),
@@ -106,7 +108,8 @@ def _load() -> C.CDLL:
         "jpegamd_finalize_async": (i32, [vp, C.POINTER(Image), vp, u64, vp, i32, vp]),
     }
     for name, (res, args) in sig.items():
-        if name in ("jpegamd_encoder_set_pipeline", "jpegamd_gather_streams", "jpegamd_debug_mfma_offsets") and os.environ.get("JPEGAMD_LIB") and not hasattr(lib, name):
+        if name in ("jpegamd_encoder_set_pipeline", "jpegamd_gather_streams", "jpegamd_debug_mfma_offsets", "jpegamd_encode_color_batch_async",
+                    "jpegamd_debug_chroma_groups") and os.environ.get("JPEGAMD_LIB") and not hasattr(lib, name):
             continue                                              # (A/B tooling: a variant build of an older round)
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = res, args
@@ -121,7 +124,7 @@ EXPORTED = ("jpegamd_encoder_create jpegamd_encoder_destroy jpegamd_max_jfif_byt
             "jpegamd_encode_bmp_memory jpegamd_parse_bmp jpegamd_encode_files jpegamd_gather_streams "
             "jpegamd_encode_rows_async jpegamd_export_segments jpegamd_import_segments jpegamd_finalize_async "
             "jpegamd_max_jfif_bytes_color jpegamd_encode_color_async jpegamd_encode_bmp_memory_color jpegamd_debug_chroma_quant_table "
-            "jpegamd_debug_chroma_mfma_consts jpegamd_debug_color_profile").split()
+            "jpegamd_debug_chroma_mfma_consts jpegamd_debug_color_profile jpegamd_encode_color_batch_async").split()
 
 
 def quant_table(quality: int = 50):
@@ -295,6 +298,86 @@ def encode_tensor(t, quality: int = 0, subsampling: int = SUBSAMPLE_420) -> byte
         return bytes(out[:n].cpu().numpy().tobytes())
 
 
+def _chroma_groups(max_width: int, max_height: int, width: int, height: int, count: int, subsampling: int = SUBSAMPLE_420,
+                   pipeline: int = 0):
+    """Test hook, not part of the API (jpegamd_debug_chroma_groups is not in the public header).  Host-only: how a colour batch of `count` width x height pictures on a context created for max_width x max_height groups its
+    2 x count chroma planes into launches -> (planes per launch, launches, tiles per segment, k_stitch)."""
+    out = (C.c_int32 * 4)()
+    rc = lib.jpegamd_debug_chroma_groups(max_width, max_height, pipeline, width, height, count, subsampling, out)
+    if rc:
+        raise JpegAmdError(rc, "jpegamd_debug_chroma_groups")
+    return out[0], out[1], out[2], bool(out[3])
+
+
+def _batch_tensor_layout(t):
+    """-> (count, height, width, row stride, channel order) of a [N, H, W, 3] (R, G, B) or [N, H, W] uint8 tensor whose pixels
+    are packed within each row; pictures and rows may be strided."""
+    import torch
+    if t.dtype != torch.uint8:
+        raise ValueError("encode_tensor_batch needs a uint8 tensor")
+    if t.dim() == 3:
+        n, h, w = t.shape
+        if t.stride(2) != 1:
+            raise ValueError("pixels of a row must be packed (stride(2) == 1)")
+        order = ORDER_GRAY
+        row_bytes = w
+    elif t.dim() == 4 and t.shape[3] == 3:
+        n, h, w = t.shape[0], t.shape[1], t.shape[2]
+        if t.stride(3) != 1 or t.stride(2) != 3:
+            raise ValueError("pixels of a row must be packed RGB (stride(2) == 3, stride(3) == 1)")
+        order = ORDER_RGB
+        row_bytes = 3 * w
+    else:
+        raise ValueError("encode_tensor_batch takes [N, H, W] or [N, H, W, 3]")
+    if n < 1 or h < 1 or w < 1:
+        raise ValueError("encode_tensor_batch needs at least one picture of at least one pixel")
+    if h > 1 and t.stride(1) < row_bytes:
+        raise ValueError("rows overlap (stride(1) is less than a row)")
+    return n, h, w, (t.stride(1) if h > 1 else row_bytes), order
+
+
+def encode_tensor_batch(t, quality: int = 0, subsampling: int = SUBSAMPLE_420) -> list:
+    """A uint8 DEVICE tensor of N pictures -> N JFIF files: [N, H, W, 3] (R, G, B) colour files through
+    jpegamd_encode_color_batch_async, [N, H, W] grayscale files through jpegamd_encode_batch_async.  Pictures may be strided
+    (t[::2]), pixels within a row must be packed.  Batches of more than MAX_BATCH pictures go as several calls of at most
+    MAX_BATCH.  Runs on the tensor's device and the current stream, with the per-device context of encode_tensor (grown to
+    hold a batch)."""
+    import torch
+    n, h, w, stride, order = _batch_tensor_layout(t)
+    if not t.is_cuda:
+        raise ValueError("encode_tensor_batch needs a device tensor")
+    dev = t.device.index if t.device.index is not None else torch.cuda.current_device()
+    files = []
+    with torch.cuda.device(dev):
+        per = min(n, MAX_BATCH)
+        rows = per * ((h + 7) // 8 * 8)              # a batch needs `per` x the block rows of one picture
+        enc, mw, mh = _tensor_encoders.get(dev, (None, 0, 0))
+        if enc is None or w > mw or rows > mh:
+            mw, mh = max(w, mw), max(rows, mh)
+            if enc is not None:
+                enc.close()
+            enc = Encoder(mw, mh)
+            _tensor_encoders[dev] = (enc, mw, mh)
+        cap = max_jfif_bytes(w, h) if order == ORDER_GRAY else max_jfif_bytes_color(w, h, subsampling)
+        out = torch.empty((per, cap), dtype=torch.uint8, device=t.device)
+        sizes = torch.zeros(per, dtype=torch.int64, device=t.device)
+        stream = torch.cuda.current_stream(t.device).cuda_stream
+        for b0 in range(0, n, MAX_BATCH):
+            k = min(MAX_BATCH, n - b0)
+            imgs = [Encoder.image(t[b0 + i].data_ptr(), w, h, stride, bottom_up=False, channel_order=order, quality=quality)
+                    for i in range(k)]
+            outs = [out[i].data_ptr() for i in range(k)]
+            size_ptrs = [sizes.data_ptr() + 8 * i for i in range(k)]
+            if order == ORDER_GRAY:
+                enc.encode_batch_async(imgs, outs, cap, size_ptrs, True, stream)
+            else:
+                enc.encode_color_batch_async(imgs, subsampling, outs, cap, size_ptrs, stream)
+            enc.finish()
+            got = sizes[:k].cpu().tolist()
+            files += [bytes(out[i, :got[i]].cpu().numpy().tobytes()) for i in range(k)]
+    return files
+
+
 class BatchStats(C.Structure):
     _fields_ = [("files_ok", C.c_int32), ("files_failed", C.c_int32), ("bytes_in", C.c_uint64), ("bytes_out", C.c_uint64),
                 ("seconds_total", C.c_double), ("seconds_read", C.c_double), ("seconds_write", C.c_double)]
@@ -372,6 +455,17 @@ class Encoder:
                                             C.c_void_p(stream))
         if rc:
             raise JpegAmdError(rc, "jpegamd_encode_color_async")
+
+    def encode_color_batch_async(self, imgs, subsampling: int, out_ptrs, out_cap: int, size_ptrs, stream: int = 0):
+        """The colour files of `len(imgs)` RGB / BGR pictures of one geometry (<= MAX_BATCH) with one launch of each kernel
+        (jpegamd_encode_color_batch_async); the context must hold len(imgs) x the tiles and segments of one picture."""
+        n = len(imgs)
+        arr = (Image * n)(*imgs)
+        outs = (C.c_void_p * n)(*[C.c_void_p(p) for p in out_ptrs])
+        sizes = (C.c_void_p * n)(*[C.c_void_p(p) for p in size_ptrs])
+        rc = lib.jpegamd_encode_color_batch_async(self._h, arr, n, int(subsampling), outs, out_cap, sizes, C.c_void_p(stream))
+        if rc:
+            raise JpegAmdError(rc, "jpegamd_encode_color_batch_async")
 
     def color_profile(self, slot: int):
         """Per-kernel ns of a profiled colour encode: planes, (tile, merge, finalize) x Y / Cb / Cr, append."""
