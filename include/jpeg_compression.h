@@ -67,14 +67,21 @@ extern "C" {
 /* One byte per pixel: `pixels` holds the luma itself (row_stride >= width); the output is a grayscale file.  Accepted by
  * jpegamd_encode_async, jpegamd_encode_batch_async and jpegamd_debug_stages (not by the colour entry points). */
 #define JPEGAMD_ORDER_GRAY 2
+/* Four bytes per pixel (row_stride >= 4 * width): R, G, B, x or B, G, R, x.  The fourth byte is ignored: the output is byte for
+ * byte that of the same R, G, B values stored as JPEGAMD_ORDER_RGB.  Accepted by jpegamd_encode_async, jpegamd_encode_batch_async
+ * (the grayscale file), jpegamd_encode_color_async and jpegamd_encode_color_batch_async (the colour file); every other entry that
+ * takes an image or a DTO -- the row-sharded entries, convertToJpeg, jpegamd_debug_stages, the BMP and file entries -- answers
+ * JPEGAMD_ERR_ARG. */
+#define JPEGAMD_ORDER_RGBA 3
+#define JPEGAMD_ORDER_BGRA 4
 
 typedef struct JpegAmdImage {
     const void *pixels;    /* DEVICE pointer to the first stored row */
     int32_t width;         /* original (unpadded) width,  1..65535 */
     int32_t height;        /* original (unpadded) height, 1..65535 */
-    int32_t row_stride;    /* bytes between stored rows (>= 3*width; GRAY: >= width) */
+    int32_t row_stride;    /* bytes between stored rows (>= 3*width; GRAY: >= width; RGBA / BGRA: >= 4*width) */
     int32_t bottom_up;     /* 1: stored row 0 is the LAST image row (BMP default) */
-    int32_t channel_order; /* JPEGAMD_ORDER_BGR, JPEGAMD_ORDER_RGB or JPEGAMD_ORDER_GRAY */
+    int32_t channel_order; /* JPEGAMD_ORDER_BGR, _RGB, _GRAY, _RGBA or _BGRA */
     int32_t quality;       /* 0 or 50: the reference's only table
                               (natural_c/src/core/jpeg_tables.c:3-12); 1..100 otherwise =
                               libjpeg scaling of that table (extension) */
@@ -143,7 +150,8 @@ int32_t jpegamd_encode_batch_async(JpegAmdEncoder *enc, const JpegAmdImage *imgs
  *   replicated); 4:4:4: W x H.  Chroma: T.81 Annex K tables K.2 (quantisation, scaled for `quality` like the luma table),
  *   K.4 / K.6 (Huffman).  No restart markers.
  * jpegamd_encode_color_async always writes the whole file (prefix, three scans, EOI) into out_dev, stream-ordered, with no host
- * synchronisation inside the call.  A GRAY image or another subsampling value: JPEGAMD_ERR_ARG.  If the file does not fit
+ * synchronisation inside the call.  A GRAY image or another subsampling value: JPEGAMD_ERR_ARG.  An RGBA / BGRA image runs as a
+ * colour batch of one (jpegamd_encode_color_batch_async: with profiling on it records ns_total only).  If the file does not fit
  * out_capacity, jpegamd_encoder_finish returns JPEGAMD_ERR_HUFF_CAPACITY, *out_size_dev is 0 and nothing is written past
  * out_capacity.  Its statistics are sums over the three scans; ns_total spans the whole call.
  * The context allocates its colour scratch (chroma constants, the two planes, the chroma scans) on its first colour call, sized
@@ -156,7 +164,7 @@ uint64_t jpegamd_max_jfif_bytes_color(int32_t width, int32_t height, int32_t sub
 int32_t jpegamd_encode_color_async(JpegAmdEncoder *enc, const JpegAmdImage *img, int32_t subsampling, void *out_dev,
                                    uint64_t out_capacity, uint64_t *out_size_dev, void *stream);
 /* The colour files of `count` pictures (1 .. JPEGAMD_MAX_BATCH) of ONE geometry -- the rules of jpegamd_encode_batch_async, BGR or
- * RGB only -- with one launch of each kernel: the chroma planes of all pictures, the Y scans as one batch, and the Cb and Cr planes
+ * RGB (or RGBA / BGRA) only -- with one launch of each kernel: the chroma planes of all pictures, the Y scans as one batch, and the Cb and Cr planes
  * of all pictures as batches of planes (one launch for count <= 16 at 4:2:0 on a context created for count x H with H a multiple
  * of 16; more where the context's scratch holds fewer planes).  outs_dev[i] / *out_sizes_dev[i] receive exactly what
  * jpegamd_encode_color_async writes for imgs[i]; a picture whose file does not fit out_capacity gets size 0 and nothing past
@@ -170,6 +178,25 @@ int32_t jpegamd_encode_color_async(JpegAmdEncoder *enc, const JpegAmdImage *img,
 int32_t jpegamd_encode_color_batch_async(JpegAmdEncoder *enc, const JpegAmdImage *imgs, int32_t count, int32_t subsampling,
                                          void *const *outs_dev, uint64_t out_capacity, uint64_t *const *out_sizes_dev,
                                          void *stream);
+
+/* ---- Planar (channels-first) pictures: the R, G and B planes of one byte per sample, as a [3, H, W] tensor stores them ------------
+ * Three pointers, not a base and a plane stride: a crop of a [3, H, W] tensor and three separate allocations both fit. */
+typedef struct JpegAmdPlanarImage {
+    const void *plane[3];   /* DEVICE pointers: the R, G and B planes, one byte per sample */
+    int32_t width, height;  /* 1..65535 */
+    int32_t row_stride;     /* bytes between stored rows, the same for the three planes, >= width */
+    int32_t bottom_up;
+    int32_t quality;
+} JpegAmdPlanarImage;
+/* The files of `count` (1 .. JPEGAMD_MAX_BATCH) planar pictures of ONE geometry (width, height, row_stride, bottom_up, quality), read
+ * where they lie -- no repacking pass.  subsampling 0: grayscale files with container, as jpegamd_encode_batch_async writes them;
+ * JPEGAMD_SUBSAMPLE_444 / _420: colour files, as jpegamd_encode_color_batch_async writes them.  Each file is byte for byte the one
+ * those entries produce for the same R, G, B values stored as packed JPEGAMD_ORDER_RGB.  Context sizing, capacity, status and
+ * statistics are those of the entry it stands for.  out_sizes_dev[i] is a DEVICE uint64_t.  Bad arguments -- a null array or element,
+ * a null plane, count out of range, row_stride < width, another subsampling value, pictures of different geometry -- are refused
+ * with JPEGAMD_ERR_ARG before the context is read. */
+int32_t jpegamd_encode_planar_batch_async(JpegAmdEncoder *enc, const JpegAmdPlanarImage *imgs, int32_t count, int32_t subsampling,
+                                          void *const *outs_dev, uint64_t out_capacity, void *const *out_sizes_dev, void *stream);
 
 /* Which kernels follow k_tile_encode for whole pictures (no reference counterpart: a tuning knob, results are byte-identical).
  *   PAIR    k_segment_merge + k_finalize: the tiles' bit strings joined per segment, then stitched behind a kernel boundary;

@@ -421,18 +421,28 @@ static bool context_fits(const JpegAmdEncoder *e, int w, int h) {
     return segs_for(w, h, nullptr, nullptr, nullptr) <= e->max_segs && tiles <= e->max_tiles;
 }
 
-static int32_t describe(const JpegAmdEncoder *e, const JpegAmdImage *img, ImageDesc *d, int seg_tiles = kSegTiles) {
+// Layouts beyond the three every entry takes: the 4-byte orders (the four whole-picture encode entries), and the internal order of
+// a planar picture (jpegamd_encode_planar_batch_async: `pixels` is its R plane, G and B travel in a PlaneSet).
+constexpr int kOrderPlanar = 0x100;
+enum Accept { kAcceptBasic = 0, kAcceptPx4 = 1, kAcceptPlanar = 2 };
+static bool is_px4(int order) { return order == JPEGAMD_ORDER_RGBA || order == JPEGAMD_ORDER_BGRA; }
+static int bytes_per_pixel(int order) {
+    return (order == JPEGAMD_ORDER_GRAY || order == kOrderPlanar) ? 1 : (is_px4(order) ? 4 : 3);
+}
+
+static int32_t describe(const JpegAmdEncoder *e, const JpegAmdImage *img, ImageDesc *d, int seg_tiles = kSegTiles, int accept = kAcceptBasic) {
     if (!img || !img->pixels || img->width <= 0 || img->height <= 0 || img->width > 65535 || img->height > 65535)
         return JPEGAMD_ERR_ARG;
-    if (img->channel_order != JPEGAMD_ORDER_BGR && img->channel_order != JPEGAMD_ORDER_RGB && img->channel_order != JPEGAMD_ORDER_GRAY)
+    const bool basic = img->channel_order == JPEGAMD_ORDER_BGR || img->channel_order == JPEGAMD_ORDER_RGB || img->channel_order == JPEGAMD_ORDER_GRAY;
+    if (!basic && !(accept == kAcceptPx4 && is_px4(img->channel_order)) && !(accept == kAcceptPlanar && img->channel_order == kOrderPlanar))
         return JPEGAMD_ERR_ARG;
-    if (img->row_stride < (img->channel_order == JPEGAMD_ORDER_GRAY ? 1 : 3) * img->width) return JPEGAMD_ERR_ARG;
+    if (img->row_stride < bytes_per_pixel(img->channel_order) * img->width) return JPEGAMD_ERR_ARG;
     d->pixels = (const uint8_t *)img->pixels;
     d->width = img->width; d->height = img->height; d->row_stride = img->row_stride;
     d->bottom_up = img->bottom_up ? 1 : 0;
     // Y = (77 R + 150 G + 29 B) >> 8 (natural_c/src/core/converter.c:51); weights follow the STORED byte order.
-    d->weights = img->channel_order == JPEGAMD_ORDER_BGR ? (29u | (150u << 8) | (77u << 16))
-                                                         : (77u | (150u << 8) | (29u << 16));
+    d->weights = (img->channel_order == JPEGAMD_ORDER_BGR || img->channel_order == JPEGAMD_ORDER_BGRA) ? (29u | (150u << 8) | (77u << 16))
+                                                                                                       : (77u | (150u << 8) | (29u << 16));
     d->seg_tiles = seg_tiles;
     d->num_segs = segs_for(img->width, img->height, &d->blocks_w, &d->blocks_h, &d->segs_per_row, seg_tiles);
     d->tiles_per_row = (d->blocks_w + kTileBlocks - 1) / kTileBlocks;
@@ -451,11 +461,20 @@ static int32_t describe(const JpegAmdEncoder *e, const JpegAmdImage *img, ImageD
 }
 
 // What k_tile_encode reads for this image (kTileSrcChroma: set by the colour path alone).
-static int src_of(const JpegAmdImage *img) { return img->channel_order == JPEGAMD_ORDER_GRAY ? kTileSrcGray : kTileSrcRgb; }
+static int src_of(const JpegAmdImage *img) {
+    if (img->channel_order == JPEGAMD_ORDER_GRAY) return kTileSrcGray;
+    if (img->channel_order == kOrderPlanar) return kTileSrcPlanar;
+    return is_px4(img->channel_order) ? kTileSrcPx4 : kTileSrcRgb;
+}
+
+// The pictures of a batch as the kernels take them: p[0] the pixels (planar: the R planes), p[1] / p[2] the G / B planes.
+struct PlaneSet {
+    const uint8_t *p[3][kMaxBatch];
+};
 
 // k_tile_encode (+ the fault injection of the tests).
 static int launch_transform(JpegAmdEncoder *e, const ImageDesc &im, bool taps, int8_t *ty, int16_t *tzz, uint64_t *tmask,
-                            void *stream, hipEvent_t *ev = nullptr /*2: begin/end*/, int src = kTileSrcRgb) {
+                            void *stream, hipEvent_t *ev = nullptr /*2: begin/end*/, int src = kTileSrcRgb, const PlaneSet *ps = nullptr) {
     TransformOutM to;
     std::memset(&to, 0, sizeof(to));
     const bool chroma = src == kTileSrcChroma;
@@ -468,8 +487,15 @@ static int launch_transform(JpegAmdEncoder *e, const ImageDesc &im, bool taps, i
     to.tile_ctr_next = e->tile_ctr + (e->ctr_set ? 0 : 64 * 32);
     const bool stamped = e->stamp_next && e->stamps_dev && !taps;
     e->stamp_next = false;
-    if (int err = stamped ? launch_tile_transform_stamped(im, to, taps, stream, ev ? (void *const *)ev : nullptr, src)
-                          : launch_tile_transform(im, to, taps, stream, (ev && !taps) ? (void *const *)ev : nullptr, src)) return err;
+    TilePlanes tp;
+    if (src == kTileSrcPlanar) {
+        if (!ps) return (int)hipErrorInvalidValue;
+        std::memcpy(tp.g, ps->p[1], sizeof(tp.g));
+        std::memcpy(tp.b, ps->p[2], sizeof(tp.b));
+    }
+    const TilePlanes *planes = src == kTileSrcPlanar ? &tp : nullptr;
+    if (int err = stamped ? launch_tile_transform_stamped(im, to, taps, stream, ev ? (void *const *)ev : nullptr, src, planes)
+                          : launch_tile_transform(im, to, taps, stream, (ev && !taps) ? (void *const *)ev : nullptr, src, planes)) return err;
     if (im.tile_end > im.tile_begin) e->ctr_set ^= 1;      // (an empty range launches nothing)
     if (e->poison_tile >= 0) {                             // fault injection for the tests: a corrupt record must end in a status code
         if (e->poison_tile < e->max_tiles &&
@@ -482,8 +508,9 @@ static int launch_transform(JpegAmdEncoder *e, const ImageDesc &im, bool taps, i
 
 // k_tile_encode, then k_segment_merge (block-row shards, stage taps).
 static int launch_transform_and_entropy(JpegAmdEncoder *e, const ImageDesc &im, bool taps, int8_t *ty, int16_t *tzz, uint64_t *tmask,
-                                        void *stream, hipEvent_t *ev = nullptr /*4: begin/end of the two kernels*/, int src = kTileSrcRgb) {
-    if (int err = launch_transform(e, im, taps, ty, tzz, tmask, stream, ev, src)) return err;
+                                        void *stream, hipEvent_t *ev = nullptr /*4: begin/end of the two kernels*/, int src = kTileSrcRgb,
+                                        const PlaneSet *ps = nullptr) {
+    if (int err = launch_transform(e, im, taps, ty, tzz, tmask, stream, ev, src, ps)) return err;
     MergeArgs ea;
     std::memset(&ea, 0, sizeof(ea));
     ea.tile_head = e->tile_head; ea.tile_over = e->tile_over;
@@ -680,7 +707,7 @@ extern "C" int32_t jpegamd_encode_async(JpegAmdEncoder *e, const JpegAmdImage *i
     if (!e || !out_dev || !out_size_dev) return JPEGAMD_ERR_ARG;
     ImageDesc im;
     const bool stitch = use_stitch(e, img ? img->width : 0, img ? img->height : 0);
-    int32_t rc = describe(e, img, &im, stitch ? kSegTilesBatch : kSegTiles);   // (k_stitch works on segments of 16 tiles)
+    int32_t rc = describe(e, img, &im, stitch ? kSegTilesBatch : kSegTiles, kAcceptPx4);   // (k_stitch works on segments of 16 tiles)
     if (rc) return rc;
     rc = prepare_constants(e, img, with_container != 0);
     if (rc) return rc;
@@ -713,29 +740,31 @@ extern "C" int32_t jpegamd_encode_async(JpegAmdEncoder *e, const JpegAmdImage *i
 
 // `count` images of one geometry through ONE launch of each kernel (see the header): image i's tiles are
 // [i * num_tiles, (i + 1) * num_tiles), its segments [i * num_segs, ..); DC prediction, bit offsets and stuffing restart per image.
-extern "C" int32_t jpegamd_encode_batch_async(JpegAmdEncoder *e, const JpegAmdImage *imgs, int32_t count, void *const *outs_dev,
-                                              uint64_t out_capacity, uint64_t *const *out_sizes_dev, int32_t with_container,
-                                              void *stream_) {
-    if (!e || !imgs || !outs_dev || !out_sizes_dev || count < 1 || count > kMaxBatch) return JPEGAMD_ERR_ARG;
+// Every pointer of every picture on a dword boundary?  (what ImageDesc::fast_ok asks besides the stride)
+static bool planes_aligned(const PlaneSet &ps, int count, int order) {
+    uintptr_t bits = 0;
+    for (int k = 0; k < (order == kOrderPlanar ? 3 : 1); ++k)
+        for (int i = 0; i < count; ++i) bits |= (uintptr_t)ps.p[k][i];
+    return (bits & 3u) == 0;
+}
+
+// The grayscale files of a batch whose arguments are known to be good: g0 describes every picture, ps holds their pixels.
+static int32_t gray_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, const PlaneSet &ps, int32_t count, void *const *outs_dev,
+                          uint64_t out_capacity, uint64_t *const *out_sizes_dev, int32_t with_container, void *stream_) {
     ImageDesc im;
+    const JpegAmdImage *imgs = &g0;
+    const int accept = g0.channel_order == kOrderPlanar ? kAcceptPlanar : kAcceptPx4;
     const bool stitch = use_stitch(e, imgs[0].width, imgs[0].height);
     int seg_tiles = (stitch || count >= 4) ? kSegTilesBatch : kSegTiles;  // many pictures: longer segments (jpegamd_internal.h); k_stitch: always
-    int32_t rc = describe(e, &imgs[0], &im, seg_tiles);
+    int32_t rc = describe(e, &imgs[0], &im, seg_tiles, accept);
     if (rc) return rc;
     if (!stitch && seg_tiles != kSegTiles && (size_t)count * im.num_segs * seg_cap_words(seg_tiles) > e->words_cap) {   // (a geometry other than the context's own)
         seg_tiles = kSegTiles;
-        rc = describe(e, &imgs[0], &im, seg_tiles);
+        rc = describe(e, &imgs[0], &im, seg_tiles, accept);
         if (rc) return rc;
     }
-    for (int i = 0; i < count; ++i) {
-        const JpegAmdImage &g = imgs[i];
-        if (!outs_dev[i] || !out_sizes_dev[i] || !g.pixels) return JPEGAMD_ERR_ARG;
-        if (g.width != imgs[0].width || g.height != imgs[0].height || g.row_stride != imgs[0].row_stride ||
-            (g.bottom_up != 0) != (imgs[0].bottom_up != 0) || g.channel_order != imgs[0].channel_order || g.quality != imgs[0].quality)
-            return JPEGAMD_ERR_ARG;
-        im.batch_pixels[i] = (const uint8_t *)g.pixels;
-        if ((((uintptr_t)g.pixels) & 3u) != 0) im.fast_ok = 0;
-    }
+    for (int i = 0; i < count; ++i) im.batch_pixels[i] = ps.p[0][i];
+    if (!planes_aligned(ps, count, g0.channel_order)) im.fast_ok = 0;
     if ((int64_t)count * im.num_tiles > e->max_tiles || (int64_t)count * im.num_segs > e->max_segs ||
         (!stitch && (size_t)count * im.num_segs * seg_cap_words(seg_tiles) > e->words_cap)) return JPEGAMD_ERR_TOO_LARGE;
     im.batch = count;
@@ -754,10 +783,10 @@ extern "C" int32_t jpegamd_encode_batch_async(JpegAmdEncoder *e, const JpegAmdIm
     }
     if (timed) { e->ring[(size_t)e->last_slot].merged = !stitch; e->ring[(size_t)e->last_slot].color = false; }
     if (stitch) {
-        if (launch_transform(e, im, false, nullptr, nullptr, nullptr, stream, ev, src_of(imgs))) return JPEGAMD_ERR_HIP;
+        if (launch_transform(e, im, false, nullptr, nullptr, nullptr, stream, ev, src_of(imgs), &ps)) return JPEGAMD_ERR_HIP;
         if (run_stitch(e, im, outs_dev, out_capacity, out_sizes_dev, with_container, stream, ev ? ev + 4 : nullptr)) return JPEGAMD_ERR_HIP;
     } else {
-        if (launch_transform_and_entropy(e, im, false, nullptr, nullptr, nullptr, stream, ev, src_of(imgs))) return JPEGAMD_ERR_HIP;
+        if (launch_transform_and_entropy(e, im, false, nullptr, nullptr, nullptr, stream, ev, src_of(imgs), &ps)) return JPEGAMD_ERR_HIP;
         if (run_finalize_batch(e, im, outs_dev, out_capacity, out_sizes_dev, with_container, stream, ev ? ev + 4 : nullptr)) return JPEGAMD_ERR_HIP;
     }
     e->last_segs = count * im.num_segs;
@@ -765,6 +794,25 @@ extern "C" int32_t jpegamd_encode_batch_async(JpegAmdEncoder *e, const JpegAmdIm
     e->pending = true; e->last_color = false;
     e->timed = timed;
     return JPEGAMD_OK;
+}
+
+extern "C" int32_t jpegamd_encode_batch_async(JpegAmdEncoder *e, const JpegAmdImage *imgs, int32_t count, void *const *outs_dev,
+                                              uint64_t out_capacity, uint64_t *const *out_sizes_dev, int32_t with_container,
+                                              void *stream_) {
+    if (!e || !imgs || !outs_dev || !out_sizes_dev || count < 1 || count > kMaxBatch) return JPEGAMD_ERR_ARG;
+    ImageDesc im;
+    int32_t rc = describe(nullptr, &imgs[0], &im, kSegTiles, kAcceptPx4);      // (the arguments alone: the context is looked at by gray_batch)
+    if (rc) return rc;
+    PlaneSet ps = {};
+    for (int i = 0; i < count; ++i) {
+        const JpegAmdImage &g = imgs[i];
+        if (!outs_dev[i] || !out_sizes_dev[i] || !g.pixels) return JPEGAMD_ERR_ARG;
+        if (g.width != imgs[0].width || g.height != imgs[0].height || g.row_stride != imgs[0].row_stride ||
+            (g.bottom_up != 0) != (imgs[0].bottom_up != 0) || g.channel_order != imgs[0].channel_order || g.quality != imgs[0].quality)
+            return JPEGAMD_ERR_ARG;
+        ps.p[0][i] = (const uint8_t *)g.pixels;
+    }
+    return gray_batch(e, imgs[0], ps, count, outs_dev, out_capacity, out_sizes_dev, with_container, stream_);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -859,6 +907,11 @@ extern "C" int32_t jpegamd_encode_color_async(JpegAmdEncoder *e, const JpegAmdIm
                                               uint64_t out_capacity, uint64_t *out_size_dev, void *stream_) {
     if (!e || !img || !out_dev || !out_size_dev) return JPEGAMD_ERR_ARG;
     if (subsampling != JPEGAMD_SUBSAMPLE_444 && subsampling != JPEGAMD_SUBSAMPLE_420) return JPEGAMD_ERR_ARG;
+    if (is_px4(img->channel_order)) {             // a batch of one through the batch kernels (k_chroma_planes reads 3-byte pixels only)
+        void *const outs[1] = {out_dev};
+        uint64_t *const sizes[1] = {out_size_dev};
+        return jpegamd_encode_color_batch_async(e, img, 1, subsampling, outs, out_capacity, sizes, stream_);
+    }
     if (img->channel_order != JPEGAMD_ORDER_BGR && img->channel_order != JPEGAMD_ORDER_RGB) return JPEGAMD_ERR_ARG;
     ImageDesc iy;
     const bool stitch_y = use_stitch(e, img->width, img->height);
@@ -1019,38 +1072,25 @@ static int32_t color_batch_alloc(JpegAmdEncoder *e, size_t planes, size_t scans)
     return JPEGAMD_OK;
 }
 
-extern "C" int32_t jpegamd_encode_color_batch_async(JpegAmdEncoder *e, const JpegAmdImage *imgs, int32_t count, int32_t subsampling,
-                                                    void *const *outs_dev, uint64_t out_capacity, uint64_t *const *out_sizes_dev,
-                                                    void *stream_) {
-    // the arguments first: nothing of the context is read before they are known to be good
-    if (!e || !imgs || !outs_dev || !out_sizes_dev || count < 1 || count > kMaxBatch) return JPEGAMD_ERR_ARG;
-    if (subsampling != JPEGAMD_SUBSAMPLE_444 && subsampling != JPEGAMD_SUBSAMPLE_420) return JPEGAMD_ERR_ARG;
-    const JpegAmdImage &g0 = imgs[0];
-    if (g0.channel_order != JPEGAMD_ORDER_BGR && g0.channel_order != JPEGAMD_ORDER_RGB) return JPEGAMD_ERR_ARG;
-    for (int i = 0; i < count; ++i) {
-        const JpegAmdImage &g = imgs[i];
-        if (!outs_dev[i] || !out_sizes_dev[i] || !g.pixels) return JPEGAMD_ERR_ARG;
-        if (g.width != g0.width || g.height != g0.height || g.row_stride != g0.row_stride || (g.bottom_up != 0) != (g0.bottom_up != 0) ||
-            g.channel_order != g0.channel_order || g.quality != g0.quality)
-            return JPEGAMD_ERR_ARG;
-    }
+// The colour files of a batch whose arguments are known to be good: g0 describes every picture, ps holds their pixels.
+static int32_t color_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, const PlaneSet &px, int32_t count, int32_t subsampling,
+                           void *const *outs_dev, uint64_t out_capacity, uint64_t *const *out_sizes_dev, void *stream_) {
     // Y: the grayscale batch's launch plan
     ImageDesc iy;
     const bool stitch_y = use_stitch(e, g0.width, g0.height);
     int seg_tiles = (stitch_y || count >= 4) ? kSegTilesBatch : kSegTiles;
-    int32_t rc = describe(e, &g0, &iy, seg_tiles);
+    const int accept = g0.channel_order == kOrderPlanar ? kAcceptPlanar : kAcceptPx4;
+    int32_t rc = describe(e, &g0, &iy, seg_tiles, accept);
     if (rc) return rc;
     if (!stitch_y && seg_tiles != kSegTiles && (size_t)count * iy.num_segs * seg_cap_words(seg_tiles) > e->words_cap) {
         seg_tiles = kSegTiles;
-        rc = describe(e, &g0, &iy, seg_tiles);
+        rc = describe(e, &g0, &iy, seg_tiles, accept);
         if (rc) return rc;
     }
     if ((int64_t)count * iy.num_tiles > e->max_tiles || (int64_t)count * iy.num_segs > e->max_segs ||
         (!stitch_y && (size_t)count * iy.num_segs * seg_cap_words(seg_tiles) > e->words_cap)) return JPEGAMD_ERR_TOO_LARGE;
-    for (int i = 0; i < count; ++i) {
-        iy.batch_pixels[i] = (const uint8_t *)imgs[i].pixels;
-        if ((((uintptr_t)imgs[i].pixels) & 3u) != 0) iy.fast_ok = 0;
-    }
+    for (int i = 0; i < count; ++i) iy.batch_pixels[i] = px.p[0][i];
+    if (!planes_aligned(px, count, g0.channel_order)) iy.fast_ok = 0;
     iy.batch = count;
     iy.tile_end = count * iy.num_tiles;
     iy.seg_end = count * iy.num_segs;
@@ -1096,10 +1136,11 @@ extern "C" int32_t jpegamd_encode_color_batch_async(JpegAmdEncoder *e, const Jpe
 
     ChromaPlanesBatchArgs pa;
     std::memset(&pa, 0, sizeof(pa));
-    for (int i = 0; i < count; ++i) pa.pixels[i] = (const uint8_t *)imgs[i].pixels;
+    for (int i = 0; i < count; ++i) { pa.pixels[i] = px.p[0][i]; pa.pixels_g[i] = px.p[1][i]; pa.pixels_b[i] = px.p[2][i]; }
+    pa.layout = g0.channel_order == kOrderPlanar ? kChromaSrcPlanar : (is_px4(g0.channel_order) ? kChromaSrcPx4 : kChromaSrcPx3);
     pa.batch = count;
     pa.width = g0.width; pa.height = g0.height; pa.row_stride = g0.row_stride; pa.bottom_up = g0.bottom_up ? 1 : 0;
-    pa.rgb = g0.channel_order == JPEGAMD_ORDER_RGB ? 1 : 0;
+    pa.rgb = (g0.channel_order == JPEGAMD_ORDER_BGR || g0.channel_order == JPEGAMD_ORDER_BGRA) ? 0 : 1;
     pa.sub420 = subsampling == JPEGAMD_SUBSAMPLE_420 ? 1 : 0;
     pa.cw = cw; pa.ch = ch; pa.pitch = pitch;
     pa.plane_bytes = plane_bytes; pa.planes = c.bplanes;
@@ -1113,11 +1154,11 @@ extern "C" int32_t jpegamd_encode_color_batch_async(JpegAmdEncoder *e, const Jpe
         const ScanTarget ty = {c.hdr, c.hdr_len, 0, &lstats[0], false};
         PictureStatsArgs ps = {e->tile_head, e->huff, iy.num_tiles, count, 0, 0, pic};
         if (stitch_y) {
-            if (launch_transform(e, iy, false, nullptr, nullptr, nullptr, stream, nullptr, kTileSrcRgb)) return JPEGAMD_ERR_HIP;
+            if (launch_transform(e, iy, false, nullptr, nullptr, nullptr, stream, nullptr, src_of(&g0), &px)) return JPEGAMD_ERR_HIP;
             if (launch_picture_stats(ps, stream)) return JPEGAMD_ERR_HIP;
             if (run_stitch(e, iy, outs_dev, out_capacity, sizes, 1, stream, nullptr, &ty)) return JPEGAMD_ERR_HIP;
         } else {
-            if (launch_transform_and_entropy(e, iy, false, nullptr, nullptr, nullptr, stream, nullptr, kTileSrcRgb)) return JPEGAMD_ERR_HIP;
+            if (launch_transform_and_entropy(e, iy, false, nullptr, nullptr, nullptr, stream, nullptr, src_of(&g0), &px)) return JPEGAMD_ERR_HIP;
             if (launch_picture_stats(ps, stream)) return JPEGAMD_ERR_HIP;
             if (run_finalize_batch(e, iy, outs_dev, out_capacity, sizes, 1, stream, nullptr, &ty)) return JPEGAMD_ERR_HIP;
         }
@@ -1173,6 +1214,55 @@ extern "C" int32_t jpegamd_encode_color_batch_async(JpegAmdEncoder *e, const Jpe
     e->timed = timed;
     e->last_color = true;
     return JPEGAMD_OK;
+}
+
+extern "C" int32_t jpegamd_encode_color_batch_async(JpegAmdEncoder *e, const JpegAmdImage *imgs, int32_t count, int32_t subsampling,
+                                                    void *const *outs_dev, uint64_t out_capacity, uint64_t *const *out_sizes_dev,
+                                                    void *stream_) {
+    // the arguments first: nothing of the context is read before they are known to be good
+    if (!e || !imgs || !outs_dev || !out_sizes_dev || count < 1 || count > kMaxBatch) return JPEGAMD_ERR_ARG;
+    if (subsampling != JPEGAMD_SUBSAMPLE_444 && subsampling != JPEGAMD_SUBSAMPLE_420) return JPEGAMD_ERR_ARG;
+    const JpegAmdImage &g0 = imgs[0];
+    if (g0.channel_order != JPEGAMD_ORDER_BGR && g0.channel_order != JPEGAMD_ORDER_RGB && !is_px4(g0.channel_order)) return JPEGAMD_ERR_ARG;
+    if (g0.width <= 0 || g0.row_stride < bytes_per_pixel(g0.channel_order) * (int64_t)g0.width) return JPEGAMD_ERR_ARG;
+    PlaneSet ps = {};
+    for (int i = 0; i < count; ++i) {
+        const JpegAmdImage &g = imgs[i];
+        if (!outs_dev[i] || !out_sizes_dev[i] || !g.pixels) return JPEGAMD_ERR_ARG;
+        if (g.width != g0.width || g.height != g0.height || g.row_stride != g0.row_stride || (g.bottom_up != 0) != (g0.bottom_up != 0) ||
+            g.channel_order != g0.channel_order || g.quality != g0.quality)
+            return JPEGAMD_ERR_ARG;
+        ps.p[0][i] = (const uint8_t *)g.pixels;
+    }
+    return color_batch(e, g0, ps, count, subsampling, outs_dev, out_capacity, out_sizes_dev, stream_);
+}
+
+// `count` planar pictures: the argument checks, then the grayscale or the colour batch with the planes as the pixel source.
+extern "C" int32_t jpegamd_encode_planar_batch_async(JpegAmdEncoder *e, const JpegAmdPlanarImage *imgs, int32_t count, int32_t subsampling,
+                                                     void *const *outs_dev, uint64_t out_capacity, void *const *out_sizes_dev,
+                                                     void *stream_) {
+    // the arguments first: nothing of the context is read before they are known to be good
+    if (!e || !imgs || !outs_dev || !out_sizes_dev || count < 1 || count > kMaxBatch) return JPEGAMD_ERR_ARG;
+    if (subsampling != 0 && subsampling != JPEGAMD_SUBSAMPLE_444 && subsampling != JPEGAMD_SUBSAMPLE_420) return JPEGAMD_ERR_ARG;
+    const JpegAmdPlanarImage &p0 = imgs[0];
+    if (p0.width <= 0 || p0.height <= 0 || p0.width > 65535 || p0.height > 65535 || p0.row_stride < p0.width) return JPEGAMD_ERR_ARG;
+    PlaneSet ps = {};
+    uint64_t *sizes[kMaxBatch];
+    for (int i = 0; i < count; ++i) {
+        const JpegAmdPlanarImage &g = imgs[i];
+        if (!outs_dev[i] || !out_sizes_dev[i] || !g.plane[0] || !g.plane[1] || !g.plane[2]) return JPEGAMD_ERR_ARG;
+        if (g.width != p0.width || g.height != p0.height || g.row_stride != p0.row_stride || (g.bottom_up != 0) != (p0.bottom_up != 0) ||
+            g.quality != p0.quality)
+            return JPEGAMD_ERR_ARG;
+        for (int k = 0; k < 3; ++k) ps.p[k][i] = (const uint8_t *)g.plane[k];
+        sizes[i] = (uint64_t *)out_sizes_dev[i];
+    }
+    JpegAmdImage g0;
+    g0.pixels = p0.plane[0];
+    g0.width = p0.width; g0.height = p0.height; g0.row_stride = p0.row_stride; g0.bottom_up = p0.bottom_up;
+    g0.channel_order = kOrderPlanar; g0.quality = p0.quality;
+    if (subsampling == 0) return gray_batch(e, g0, ps, count, outs_dev, out_capacity, sizes, 1, stream_);
+    return color_batch(e, g0, ps, count, subsampling, outs_dev, out_capacity, sizes, stream_);
 }
 
 // The capacity status is STICKY on the device: every kernel only ORs into it, and it is cleared here, after it was read.
@@ -1325,7 +1415,7 @@ int32_t first_block_taps(JpegAmdEncoder *e, const JpegAmdImage *img, int8_t y[64
 }  // namespace jpegamd
 
 extern "C" int32_t convertToJpeg(JPEG_COMPRESSION_DTO *dto) {
-    if (!dto) return JPEGAMD_ERR_ARG;
+    if (!dto || is_px4(dto->channel_order)) return JPEGAMD_ERR_ARG;     // (the DTO boundary takes the reference's 3-byte and 1-byte layouts)
     {
         std::lock_guard<std::mutex> lk(g_mu);
         if (!g_ctx) return JPEGAMD_ERR_NOT_INIT;

@@ -138,46 +138,56 @@ int launch_append_scans(const AppendArgs &a, void *stream, void *const *ev) {
 // k_chroma_planes_batch: workgroup (bx, cy, p) makes samples [1024 bx, 1024 bx + 1024) of plane row cy of picture p, both planes.
 // The source rows it needs (3 x 2048 bytes twice at 4:2:0, 3 x 1024 bytes at 4:4:4) are staged in LDS by aligned 16-byte loads --
 // one instruction covers 1 KiB of a row -- and every thread then reads its pixels from LDS as dwords, funnel-shifted by the row's
-// misalignment.  Only chunks that lie wholly inside the row's 3 x width bytes are loaded as vectors; the partial chunks at both
+// misalignment.  Only chunks that lie wholly inside the row's bytes are loaded as vectors; the partial chunks at both
 // ends are gathered byte by byte.  The arithmetic is k_chroma_planes's: the planes are the same, bit for bit.
+// kLay is how the picture is stored: 3 or 4 bytes per pixel in one stream of bytes (the fourth byte is never looked at), or
+// three streams -- the R, G and B planes -- of one byte per pixel, each staged like a row a third as long.
 constexpr int kPbThreads = 256;
 constexpr int kPbSpan = kPbThreads * kPlaneOut;            // plane samples per workgroup and row
 
-template <int kSub>
+template <int kSub, int kLay>
 __global__ __launch_bounds__(kPbThreads) void k_chroma_planes_batch(const ChromaPlanesBatchArgs a) {
+    constexpr bool kPlanar = kLay == kChromaSrcPlanar;
+    constexpr int kStreams = kPlanar ? 3 : 1;
+    constexpr int kBpp = kPlanar ? 1 : (kLay == kChromaSrcPx4 ? 4 : 3);  // bytes per pixel of one stream
     constexpr int kPix = kPlaneOut * kSub;                               // source pixels per row and thread
-    constexpr int kRowBytes = 3 * kSub * kPbSpan;                        // source bytes per row and workgroup
+    constexpr int kRowBytes = kBpp * kSub * kPbSpan;                     // source bytes per row, stream and workgroup
     constexpr int kLdsBytes = kRowBytes + 32;                            // + the misalignment (< 16) and the funnel's extra dword
-    __shared__ __attribute__((aligned(16))) uint8_t s_row[kSub][kLdsBytes];
+    constexpr int kDw = kBpp * kPix / 4;                                 // dwords of a thread's pixels in one stream
+    __shared__ __attribute__((aligned(16))) uint8_t s_row[kSub][kStreams][kLdsBytes];
     const int p = (int)blockIdx.z, cy = (int)blockIdx.y, t = (int)threadIdx.x;
     const int s0 = (int)blockIdx.x * kPbSpan;                            // < cw
     const int x0 = s0 * kSub;                                            // < width
     const int x_end = min(x0 + kSub * kPbSpan, a.width);
-    int mis[kSub];
+    int mis[kSub][kStreams];
 #pragma unroll
     for (int r = 0; r < kSub; ++r) {
         const int y = min(cy * kSub + r, a.height - 1);                  // the last row replicated (odd heights)
         const int stored = a.bottom_up ? a.height - 1 - y : y;
-        const uintptr_t row = (uintptr_t)a.pixels[p] + (size_t)stored * (size_t)a.row_stride;
-        const uintptr_t row_end = row + 3 * (size_t)a.width;
-        const uintptr_t base = row + 3 * (size_t)x0;
-        const int m = (int)(base & 15u);
-        mis[r] = m;
-        const uintptr_t abase = base - (uintptr_t)m;
-        const int nch = (m + 3 * (x_end - x0) + 15) >> 4;               // <= kRowBytes / 16 + 1
-        for (int c = t; c < nch; c += kPbThreads) {
-            const uintptr_t g = abase + 16u * (uintptr_t)c;
-            uint4 v;
-            if (g >= row && g + 16u <= row_end) {
-                v = *reinterpret_cast<const uint4 *>(g);
-            } else {                                                     // a partial chunk at either end of the row
-                uint32_t w[4] = {0u, 0u, 0u, 0u};
 #pragma unroll
-                for (int k = 0; k < 16; ++k)
-                    if (g + k >= row && g + k < row_end) w[k >> 2] |= (uint32_t)(*reinterpret_cast<const uint8_t *>(g + k)) << (8 * (k & 3));
-                v = make_uint4(w[0], w[1], w[2], w[3]);
+        for (int st = 0; st < kStreams; ++st) {
+            const uint8_t *pic = st == 0 ? a.pixels[p] : (st == 1 ? a.pixels_g[p] : a.pixels_b[p]);
+            const uintptr_t row = (uintptr_t)pic + (size_t)stored * (size_t)a.row_stride;
+            const uintptr_t row_end = row + kBpp * (size_t)a.width;
+            const uintptr_t base = row + kBpp * (size_t)x0;
+            const int m = (int)(base & 15u);
+            mis[r][st] = m;
+            const uintptr_t abase = base - (uintptr_t)m;
+            const int nch = (m + kBpp * (x_end - x0) + 15) >> 4;        // <= kRowBytes / 16 + 1
+            for (int c = t; c < nch; c += kPbThreads) {
+                const uintptr_t g = abase + 16u * (uintptr_t)c;
+                uint4 v;
+                if (g >= row && g + 16u <= row_end) {
+                    v = *reinterpret_cast<const uint4 *>(g);
+                } else {                                                 // a partial chunk at either end of the row
+                    uint32_t w[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+                    for (int k = 0; k < 16; ++k)
+                        if (g + k >= row && g + k < row_end) w[k >> 2] |= (uint32_t)(*reinterpret_cast<const uint8_t *>(g + k)) << (8 * (k & 3));
+                    v = make_uint4(w[0], w[1], w[2], w[3]);
+                }
+                *reinterpret_cast<uint4 *>(&s_row[r][st][16 * c]) = v;
             }
-            *reinterpret_cast<uint4 *>(&s_row[r][16 * c]) = v;
         }
     }
     __syncthreads();
@@ -187,31 +197,39 @@ __global__ __launch_bounds__(kPbThreads) void k_chroma_planes_batch(const Chroma
     int cb[kSub][kPix], cr[kSub][kPix];
 #pragma unroll
     for (int r = 0; r < kSub; ++r) {
-        uint8_t px[3 * kPix];
-        if (xs + kPix <= a.width) {                                      // whole pixels: 3 kPix / 4 dwords behind the misalignment
-            const int off = mis[r] + 3 * (xs - x0);
-            const uint32_t *w32 = reinterpret_cast<const uint32_t *>(&s_row[r][off & ~3]);
-            const uint32_t sh = (uint32_t)(off & 3);
-            uint32_t d[3 * kPix / 4 + 1];
+        uint8_t px[kStreams][kBpp * kPix];
 #pragma unroll
-            for (int i = 0; i < 3 * kPix / 4 + 1; ++i) d[i] = w32[i];
+        for (int st = 0; st < kStreams; ++st) {
+            if (xs + kPix <= a.width) {                                  // whole pixels: kDw dwords behind the misalignment
+                const int off = mis[r][st] + kBpp * (xs - x0);
+                const uint32_t *w32 = reinterpret_cast<const uint32_t *>(&s_row[r][st][off & ~3]);
+                const uint32_t sh = (uint32_t)(off & 3);
+                uint32_t d[kDw + 1];
 #pragma unroll
-            for (int i = 0; i < 3 * kPix / 4; ++i) {
-                const uint32_t v = __builtin_amdgcn_alignbyte(d[i + 1], d[i], sh);
+                for (int i = 0; i < kDw + 1; ++i) d[i] = w32[i];
 #pragma unroll
-                for (int k = 0; k < 4; ++k) px[4 * i + k] = (uint8_t)(v >> (8 * k));
-            }
-        } else {                                                         // the right edge: the last column replicated
+                for (int i = 0; i < kDw; ++i) {
+                    const uint32_t v = __builtin_amdgcn_alignbyte(d[i + 1], d[i], sh);
 #pragma unroll
-            for (int j = 0; j < kPix; ++j) {
-                const int off = mis[r] + 3 * (min(xs + j, a.width - 1) - x0);
-                px[3 * j] = s_row[r][off]; px[3 * j + 1] = s_row[r][off + 1]; px[3 * j + 2] = s_row[r][off + 2];
+                    for (int k = 0; k < 4; ++k) px[st][4 * i + k] = (uint8_t)(v >> (8 * k));
+                }
+            } else {                                                     // the right edge: the last column replicated
+#pragma unroll
+                for (int j = 0; j < kPix; ++j) {
+                    const int off = mis[r][st] + kBpp * (min(xs + j, a.width - 1) - x0);
+#pragma unroll
+                    for (int k = 0; k < (kBpp < 3 ? kBpp : 3); ++k) px[st][kBpp * j + k] = s_row[r][st][off + k];
+                }
             }
         }
 #pragma unroll
         for (int j = 0; j < kPix; ++j) {
-            const int c0 = px[3 * j], c1 = px[3 * j + 1], c2 = px[3 * j + 2];
-            cbcr(a.rgb ? c0 : c2, c1, a.rgb ? c2 : c0, cb[r][j], cr[r][j]);
+            if constexpr (kPlanar) {
+                cbcr(px[0][j], px[1][j], px[2][j], cb[r][j], cr[r][j]);
+            } else {
+                const int c0 = px[0][kBpp * j], c1 = px[0][kBpp * j + 1], c2 = px[0][kBpp * j + 2];
+                cbcr(a.rgb ? c0 : c2, c1, a.rgb ? c2 : c0, cb[r][j], cr[r][j]);
+            }
         }
     }
     uint32_t wcb = 0, wcr = 0;
@@ -234,14 +252,22 @@ __global__ __launch_bounds__(kPbThreads) void k_chroma_planes_batch(const Chroma
     *reinterpret_cast<uint32_t *>(cbp + a.plane_bytes + o) = wcr;
 }
 
+template <int kLay>
+static void launch_planes_batch_as(const ChromaPlanesBatchArgs &a, dim3 grid, dim3 block, hipStream_t stream, hipEvent_t e0, hipEvent_t e1) {
+    if (a.sub420) hipExtLaunchKernelGGL((k_chroma_planes_batch<2, kLay>), grid, block, 0, stream, e0, e1, 0, a);
+    else hipExtLaunchKernelGGL((k_chroma_planes_batch<1, kLay>), grid, block, 0, stream, e0, e1, 0, a);
+}
+
 int launch_chroma_planes_batch(const ChromaPlanesBatchArgs &a, void *stream, void *const *ev) {
     if (a.cw <= 0 || a.ch <= 0 || a.batch < 1 || a.batch > kMaxBatch || a.pitch % 4 != 0 || a.pitch < (a.cw + 3) / 4 * 4 ||
         a.plane_bytes % 16 != 0 || a.plane_bytes < (uint64_t)a.pitch * (uint64_t)a.ch)
         return (int)hipErrorInvalidValue;
     const dim3 grid((unsigned)((a.cw + kPbSpan - 1) / kPbSpan), (unsigned)a.ch, (unsigned)a.batch), block(kPbThreads);
     hipEvent_t e0 = ev ? (hipEvent_t)ev[0] : nullptr, e1 = ev ? (hipEvent_t)ev[1] : nullptr;
-    if (a.sub420) hipExtLaunchKernelGGL(k_chroma_planes_batch<2>, grid, block, 0, (hipStream_t)stream, e0, e1, 0, a);
-    else hipExtLaunchKernelGGL(k_chroma_planes_batch<1>, grid, block, 0, (hipStream_t)stream, e0, e1, 0, a);
+    if (a.layout == kChromaSrcPx3) launch_planes_batch_as<kChromaSrcPx3>(a, grid, block, (hipStream_t)stream, e0, e1);
+    else if (a.layout == kChromaSrcPx4) launch_planes_batch_as<kChromaSrcPx4>(a, grid, block, (hipStream_t)stream, e0, e1);
+    else if (a.layout == kChromaSrcPlanar) launch_planes_batch_as<kChromaSrcPlanar>(a, grid, block, (hipStream_t)stream, e0, e1);
+    else return (int)hipErrorInvalidValue;
     return (int)hipGetLastError();
 }
 

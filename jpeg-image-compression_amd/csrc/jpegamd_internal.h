@@ -123,7 +123,7 @@ struct ImageDesc {
     int32_t tiles_per_row, num_tiles;
     int32_t tile_begin, tile_end;       // tiles this launch transforms (whole images: 0, batch * num_tiles; a block-row shard otherwise)
     int32_t seg_begin, seg_end;         // segments this launch codes (whole images: 0, batch * num_segs)
-    int32_t fast_ok;           // pixels % 4 == 0 && row_stride % 4 == 0
+    int32_t fast_ok;           // pixels % 4 == 0 && row_stride % 4 == 0 (planar: every plane)
 };
 
 // What k_segment_merge leaves per segment (and what one image sharded over GPUs exchanges, besides the bit strings).
@@ -159,10 +159,18 @@ struct TransformOutM {
 // kernel trace reports as its duration -- an event recorded in front of a launch also sees the dispatch latency.
 // `src`: what a pixel is -- kTileSrcRgb (3 bytes, ImageDesc::weights), kTileSrcGray (1 byte: the luma itself), kTileSrcChroma (1 byte of
 // a chroma plane, coded with the chroma tables: TransformOutM must then point at the chroma constants).
-constexpr int kTileSrcRgb = 0, kTileSrcGray = 1, kTileSrcChroma = 2;
-int launch_tile_transform(const ImageDesc &im, const TransformOutM &out, bool taps, void *stream, void *const *ev = nullptr, int src = kTileSrcRgb);
+// kTileSrcPx4: 4 bytes per pixel (RGBA / BGRA; ImageDesc::weights, the fourth byte ignored); kTileSrcPlanar: the R, G and B planes
+// of one byte per sample -- R in ImageDesc::batch_pixels, G and B in `planes`.  Neither has a stage-tap or a stamped variant.
+constexpr int kTileSrcRgb = 0, kTileSrcGray = 1, kTileSrcChroma = 2, kTileSrcPx4 = 3, kTileSrcPlanar = 4;
+struct TilePlanes {                     // the second and third plane of every picture of a planar launch (its own kernel argument)
+    const uint8_t *g[kMaxBatch];
+    const uint8_t *b[kMaxBatch];
+};
+int launch_tile_transform(const ImageDesc &im, const TransformOutM &out, bool taps, void *stream, void *const *ev = nullptr, int src = kTileSrcRgb,
+                          const TilePlanes *planes = nullptr);
 // the same kernel with its phases stamped (out.stamps must point at 16 words per wave): jpegamd_tile_pipeline.hip, -DJPEGAMD_STAMPED_TU
-int launch_tile_transform_stamped(const ImageDesc &im, const TransformOutM &out, bool taps, void *stream, void *const *ev = nullptr, int src = kTileSrcRgb);
+int launch_tile_transform_stamped(const ImageDesc &im, const TransformOutM &out, bool taps, void *stream, void *const *ev = nullptr, int src = kTileSrcRgb,
+                                  const TilePlanes *planes = nullptr);
 
 struct MergeArgs {              // k_segment_merge: the tile strings of a segment -> ONE bit string per segment + its numbers
     const uint32_t *tile_head, *tile_over;
@@ -262,14 +270,17 @@ int launch_append_scans(const AppendArgs &a, void *stream, void *const *ev = nul
 
 // Colour batches (jpegamd_encode_color_batch_async): `batch` pictures of one geometry, ONE launch of each kernel where the context
 // allows.  k_chroma_planes_batch writes 2 x batch planes, plane j = picture j / 2, Cb (j even) or Cr (j odd), `plane_bytes` apart.
+constexpr int kChromaSrcPx3 = 0, kChromaSrcPx4 = 1, kChromaSrcPlanar = 2;   // 3 / 4 bytes per pixel, or the R, G and B planes
 struct ChromaPlanesBatchArgs {
-    const uint8_t *pixels[kMaxBatch];
+    const uint8_t *pixels[kMaxBatch];   // (planar: the R planes)
     int32_t batch;
     int32_t width, height, row_stride, bottom_up;
     int32_t rgb, sub420;
     int32_t cw, ch, pitch;
     uint64_t plane_bytes;               // a multiple of 16
     uint8_t *planes;
+    int32_t layout;                     // kChromaSrc*
+    const uint8_t *pixels_g[kMaxBatch], *pixels_b[kMaxBatch];   // kChromaSrcPlanar alone
 };
 int launch_chroma_planes_batch(const ChromaPlanesBatchArgs &a, void *stream, void *const *ev = nullptr);
 // k_picture_stats: what the tile records of one k_tile_encode launch add up to per picture and scan -- bits (with the first DC

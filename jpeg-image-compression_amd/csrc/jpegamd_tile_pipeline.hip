@@ -145,7 +145,14 @@ static_assert(kPassItems * (27 + 3 * (int)kZrlBitsChroma) / 32 + 6 <= kWinStr &&
 // What k_tile_encode reads (template parameter kSrc: no runtime branch, the RGB instantiations are unchanged):
 //   kSrcRgb    3 bytes per pixel, luma by the weights of ImageDesc (BGR / RGB, either row order)
 //   kSrcPlane  1 byte per pixel: the sample itself (a GRAY picture, or a chroma plane of k_chroma_planes)
-constexpr int kSrcRgb = 0, kSrcPlane = 1;
+//   kSrcPx4    4 bytes per pixel (RGBA / BGRA): luma by the weights of ImageDesc, whose fourth weight is 0
+//   kSrcPlanar three planes of one byte per sample, R (ImageDesc::batch_pixels), G and B (TilePlanes)
+constexpr int kSrcRgb = 0, kSrcPlane = 1, kSrcPx4 = 2, kSrcPlanar = 3;
+// The kernel's last argument: the G and B planes for kSrcPlanar, an empty struct -- no kernel-argument bytes, so the offsets of
+// the hidden arguments behind it stay where they were -- for every other source.
+struct NoPlanes {};
+template <int kSrc> struct PlanesArg { typedef NoPlanes type; };
+template <> struct PlanesArg<kSrcPlanar> { typedef TilePlanes type; };
 
 // 8 plane samples (2 dwords) -> the B fragment of one k-step half: each byte zero-extended into a 16-bit half (= the binary16
 // subnormal y 2^-24, as luma_row8_f16 makes it).
@@ -154,6 +161,55 @@ __device__ __forceinline__ f16x8 plane_row8_f16(uint32_t d0, uint32_t d1) {
     const u32x4 packed = {__builtin_amdgcn_perm(0u, d0, 0x0C010C00u), __builtin_amdgcn_perm(0u, d0, 0x0C030C02u),
                           __builtin_amdgcn_perm(0u, d1, 0x0C010C00u), __builtin_amdgcn_perm(0u, d1, 0x0C030C02u)};
     return __builtin_bit_cast(f16x8, packed);
+}
+
+// 8 four-byte pixels (8 dwords) -> 8 luma values: ONE dot product per pixel (the ignored byte meets a zero weight), paired by the
+// v_perm of luma_row8_f16 -- 8 v_dot4 + 4 v_perm per 8 pixels.
+__device__ __forceinline__ f16x8 px4_row8_f16(const uint32_t *d, uint32_t w, uint32_t sel) {
+    typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
+    u32x4 packed;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+        packed[i] = __builtin_amdgcn_perm(__builtin_amdgcn_udot4(d[2 * i + 1], w, 0u, false), __builtin_amdgcn_udot4(d[2 * i], w, 0u, false), sel);
+    return __builtin_bit_cast(f16x8, packed);
+}
+
+// 8 samples of each of the R, G and B planes (raw.d[0..1], [2..3], [4..5]) -> 8 luma values.  Per 4 pixels: two v_perm interleave
+// the R and G dwords into (R0 G0 R1 G1) and (R2 G2 R3 G3), a pixel is two chained dot products -- 29 B through a weight that
+// selects its byte of the B dword, then 77 R + 150 G through the weights of its half of the interleaved dword -- and two v_perm
+// pair the results: 8 v_dot4 + 4 v_perm, 24 instructions per 8 pixels.  (Packed 16-bit multiply-adds on byte pairs -- the sum is
+// <= 65280 -- need 6 v_perm to widen the bytes, 6 multiply-adds and 2 shifts per 4 pixels: 28.)
+__device__ __forceinline__ f16x8 planar_row8_f16(const RawRow &raw, uint32_t sel) {
+    typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
+    constexpr uint32_t wrg = 77u | (150u << 8), wb = 29u;
+    u32x4 packed;
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const uint32_t r = raw.d[k], g = raw.d[2 + k], b = raw.d[4 + k];
+        const uint32_t rg01 = __builtin_amdgcn_perm(g, r, 0x05010400u), rg23 = __builtin_amdgcn_perm(g, r, 0x07030602u);
+        const uint32_t t0 = __builtin_amdgcn_udot4(rg01, wrg, __builtin_amdgcn_udot4(b, wb, 0u, false), false);
+        const uint32_t t1 = __builtin_amdgcn_udot4(rg01, wrg << 16, __builtin_amdgcn_udot4(b, wb << 8, 0u, false), false);
+        const uint32_t t2 = __builtin_amdgcn_udot4(rg23, wrg, __builtin_amdgcn_udot4(b, wb << 16, 0u, false), false);
+        const uint32_t t3 = __builtin_amdgcn_udot4(rg23, wrg << 16, __builtin_amdgcn_udot4(b, wb << 24, 0u, false), false);
+        packed[2 * k] = __builtin_amdgcn_perm(t1, t0, sel);
+        packed[2 * k + 1] = __builtin_amdgcn_perm(t3, t2, sel);
+    }
+    return __builtin_bit_cast(f16x8, packed);
+}
+
+// Luma of pixel (x, y) of a four-byte-pixel picture / of three planes, with the edge clamp (as luma_clamped).
+__device__ __forceinline__ int luma_clamped_px4(const ImageDesc &im, const uint8_t *pixels, int x, int y) {
+    x = min(x, im.width - 1);
+    y = min(y, im.height - 1);
+    const uint8_t *p = row_ptr(im, pixels, y) + 4 * (size_t)x;
+    const uint32_t w = im.weights;
+    return (int)(((w & 0xFF) * p[0] + ((w >> 8) & 0xFF) * p[1] + ((w >> 16) & 0xFF) * p[2]) >> 8);
+}
+__device__ __forceinline__ int luma_clamped_planar(const ImageDesc &im, const uint8_t *r, const uint8_t *g, const uint8_t *b, int x, int y) {
+    x = min(x, im.width - 1);
+    y = min(y, im.height - 1);
+    const size_t o = (size_t)(row_ptr(im, r, y) - r) + (size_t)x;
+    return (int)((77u * r[o] + 150u * g[o] + 29u * b[o]) >> 8);
 }
 
 // Sample of plane pixel (x, y) with the edge clamp (the padding of converter.c:31,36 by replication).
@@ -276,11 +332,11 @@ __device__ __forceinline__ void window_or(uint32_t *win, uint32_t rel, uint32_t 
     if (third) atomicOr(&win[w + 2], __builtin_amdgcn_alignbit(lo, 0u, sh));
 }
 
-// kSrc: what a pixel is (kSrcRgb / kSrcPlane); kZBits / kZCode: the ZRL code of the Huffman table in TransformOutM::code_tab
+// kSrc: what a pixel is (kSrcRgb / kSrcPlane / kSrcPx4 / kSrcPlanar; `pl` is read by kSrcPlanar alone); kZBits / kZCode: the ZRL code of the Huffman table in TransformOutM::code_tab
 // (luma: 11 bits 0x7F9; chroma: 10 bits 0x3FA).  A GRAY picture is <kTaps, kSrcPlane>, a chroma plane <false, kSrcPlane, 10, 0x3FA>.
 template <bool kTaps, int kSrc = kSrcRgb, uint32_t kZBits = kZrlBits, uint32_t kZCode = kZrlCode>
 __global__ __launch_bounds__(64 * kWavesT) __attribute__((amdgpu_waves_per_eu(JPEGAMD_TILE_WAVES, JPEGAMD_TILE_WAVES)))
-void k_tile_encode(const ImageDesc im, const TransformOutM out, const TileSched sch) {
+void k_tile_encode(const ImageDesc im, const TransformOutM out, const TileSched sch, const typename PlanesArg<kSrc>::type pl) {
     __shared__ __attribute__((aligned(16))) uint32_t s_afrag[kAFragWords];
     // s_qt[0..127]: (multiplier, additive constant: bias + zoff) by zigzag position; [136 + 16 h]: the DC row's surplus (h == 0; 0 for h == 1); [160 + 16 h + 32 G + j]: flag threshold (2 bias - 1) of zigzag 16 G + 8 h + j; [128 + 16 h + G]: zero threshold of group G for lane half h
     // (|acc| below it => every site of the group quantises to an unflagged 0), [132 + 16 h + G]: the largest tie threshold of the
@@ -414,6 +470,35 @@ void k_tile_encode(const ImageDesc im, const TransformOutM out, const TileSched 
         const uint8_t *tb = im.batch_pixels[g.img] + (size_t)row_low * (size_t)im.row_stride + 24 * (size_t)g.tbx0;
         uint32_t hh = (uint32_t)h;
         asm volatile("" : "+v"(hh));
+        if constexpr (kSrc == kSrcPx4) {                        // 32 bytes per lane-row.  Four rows of eight dwords are 8 registers more than
+            // raw[] holds (the kernel sits at its register limit): rows 0 .. 2 are requested here, row 3 at the top of the tile's iteration
+            const uint8_t *qb = im.batch_pixels[g.img] + (size_t)row_low * (size_t)im.row_stride + 32 * (size_t)g.tbx0;
+            uint32_t qoff = __umul24((uint32_t)min(b, g.nblk - 1), 32u) + __umul24(im.bottom_up ? 7u - hh : hh, (uint32_t)im.row_stride);
+            uint32_t *const flat = &raw[0].d[0];
+#pragma unroll
+            for (int s = 0; s < 3; ++s) {
+                const uint32_t *src = reinterpret_cast<const uint32_t *>(qb + qoff);
+#pragma unroll
+                for (int i = 0; i < 8; ++i) flat[8 * s + i] = src[i];
+                qoff += (uint32_t)row_step;
+            }
+            return;
+        }
+        if constexpr (kSrc == kSrcPlanar) {                     // 8 bytes per lane-row from each plane: the six dwords of a RawRow
+            const size_t pbase = (size_t)row_low * (size_t)im.row_stride + 8 * (size_t)g.tbx0;
+            const uint8_t *p0 = im.batch_pixels[g.img] + pbase, *p1 = pl.g[g.img] + pbase, *p2 = pl.b[g.img] + pbase;
+            uint32_t poff = __umul24((uint32_t)min(b, g.nblk - 1), 8u) + __umul24(im.bottom_up ? 7u - hh : hh, (uint32_t)im.row_stride);
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {
+                const uint32_t *s0 = reinterpret_cast<const uint32_t *>(p0 + poff), *s1 = reinterpret_cast<const uint32_t *>(p1 + poff),
+                               *s2 = reinterpret_cast<const uint32_t *>(p2 + poff);
+                raw[s].d[0] = s0[0]; raw[s].d[1] = s0[1];
+                raw[s].d[2] = s1[0]; raw[s].d[3] = s1[1];
+                raw[s].d[4] = s2[0]; raw[s].d[5] = s2[1];
+                poff += (uint32_t)row_step;
+            }
+            return;
+        }
         if constexpr (kSrc == kSrcPlane) {                      // 8 bytes per lane-row: a block row of one-byte samples
             const uint8_t *pb = im.batch_pixels[g.img] + (size_t)row_low * (size_t)im.row_stride + 8 * (size_t)g.tbx0;
             uint32_t poff = __umul24((uint32_t)min(b, g.nblk - 1), 8u) + __umul24(im.bottom_up ? 7u - hh : hh, (uint32_t)im.row_stride);
@@ -459,10 +544,28 @@ void k_tile_encode(const ImageDesc im, const TransformOutM out, const TileSched 
         // ---- 1. pixels -> B fragments ----------------------------------------------------------
         f16x8 bfrag[4];
         if (interior) {                        // rows requested one iteration ago, behind the ticket (below)
+            if constexpr (kSrc == kSrcPx4) {   // ... but for the fourth row pair (request_rows): on its way while the other three are converted
+                uint32_t hh = (uint32_t)h;
+                asm volatile("" : "+v"(hh));
+                const int row_low = im.bottom_up ? im.height - 8 - by * 8 : by * 8;
+                const uint8_t *qb = im.batch_pixels[tg.img] + (size_t)row_low * (size_t)im.row_stride + 32 * (size_t)tg.tbx0;
+                const uint32_t qoff = __umul24((uint32_t)min(b, nblk - 1), 32u) + __umul24(im.bottom_up ? 7u - hh : hh, (uint32_t)im.row_stride) +
+                                      3u * (uint32_t)row_step;
+                const uint32_t *src = reinterpret_cast<const uint32_t *>(qb + qoff);
+                uint32_t last[8];
+#pragma unroll
+                for (int i = 0; i < 8; ++i) last[i] = src[i];
+                const uint32_t *const flat = &raw[0].d[0];
+#pragma unroll
+                for (int s = 0; s < 3; ++s) bfrag[s] = px4_row8_f16(flat + 8 * s, im.weights, luma_sel);
+                bfrag[3] = px4_row8_f16(last, im.weights, luma_sel);
+            } else {
 #pragma unroll
             for (int s = 0; s < 4; ++s) {
                 if constexpr (kSrc == kSrcPlane) bfrag[s] = plane_row8_f16(raw[s].d[0], raw[s].d[1]);
+                else if constexpr (kSrc == kSrcPlanar) bfrag[s] = planar_row8_f16(raw[s], luma_sel);
                 else bfrag[s] = luma_row8_f16(raw[s], lw, luma_sel);
+            }
             }
         } else {
             // edge tile (right/bottom replication, converter.c:31,36) or unaligned source: clamped byte gather
@@ -475,6 +578,12 @@ void k_tile_encode(const ImageDesc im, const TransformOutM out, const TileSched 
                     if constexpr (kSrc == kSrcPlane)
                         pk[j >> 1] = (uint32_t)plane_clamped(im, im.batch_pixels[tg.img], px0 + j, py0 + 2 * s + h) |
                                      ((uint32_t)plane_clamped(im, im.batch_pixels[tg.img], px0 + j + 1, py0 + 2 * s + h) << 16);
+                    else if constexpr (kSrc == kSrcPx4)
+                        pk[j >> 1] = (uint32_t)luma_clamped_px4(im, im.batch_pixels[tg.img], px0 + j, py0 + 2 * s + h) |
+                                     ((uint32_t)luma_clamped_px4(im, im.batch_pixels[tg.img], px0 + j + 1, py0 + 2 * s + h) << 16);
+                    else if constexpr (kSrc == kSrcPlanar)
+                        pk[j >> 1] = (uint32_t)luma_clamped_planar(im, im.batch_pixels[tg.img], pl.g[tg.img], pl.b[tg.img], px0 + j, py0 + 2 * s + h) |
+                                     ((uint32_t)luma_clamped_planar(im, im.batch_pixels[tg.img], pl.g[tg.img], pl.b[tg.img], px0 + j + 1, py0 + 2 * s + h) << 16);
                     else
                         pk[j >> 1] = (uint32_t)luma_clamped(im, im.batch_pixels[tg.img], px0 + j, py0 + 2 * s + h) |
                                      ((uint32_t)luma_clamped(im, im.batch_pixels[tg.img], px0 + j + 1, py0 + 2 * s + h) << 16);
@@ -1035,7 +1144,7 @@ void k_tile_encode(const ImageDesc im, const TransformOutM out, const TileSched 
 #endif
 }
 
-int launch_tile_transform(const ImageDesc &im, const TransformOutM &out, bool taps, void *stream, void *const *ev, int src) {
+int launch_tile_transform(const ImageDesc &im, const TransformOutM &out, bool taps, void *stream, void *const *ev, int src, const TilePlanes *planes) {
     // persistent: at most 2 workgroups per CU (16 waves/CU at 4 waves/SIMD), fewer for small images
     const int ntiles = im.tile_end - im.tile_begin;
     if (ntiles <= 0) return 0;
@@ -1049,19 +1158,33 @@ int launch_tile_transform(const ImageDesc &im, const TransformOutM &out, bool ta
     const uint64_t magic = 0x100000000ull / (uint64_t)im.tiles_per_row + 1ull;
     sch.tpr_magic = magic > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)magic;   // tiles_per_row == 1: the correction step makes up for it
     const dim3 grid(wgs), block(64 * kWavesT);
+    const NoPlanes pl;
+    if (src == kTileSrcPx4 || src == kTileSrcPlanar) {
+#ifdef JPEGAMD_STAMPED_TU
+        return (int)hipErrorInvalidValue;                                   // (these sources exist in the plain build alone)
+#else
+        if (taps || (src == kTileSrcPlanar && !planes)) return (int)hipErrorInvalidValue;
+        const auto px4 = k_tile_encode<false, kSrcPx4>;
+        const auto planar = k_tile_encode<false, kSrcPlanar>;
+        hipEvent_t e0 = ev ? (hipEvent_t)ev[0] : nullptr, e1 = ev ? (hipEvent_t)ev[1] : nullptr;
+        if (src == kTileSrcPx4) hipExtLaunchKernelGGL(px4, grid, block, 0, (hipStream_t)stream, e0, e1, 0, im, out, sch, pl);
+        else hipExtLaunchKernelGGL(planar, grid, block, 0, (hipStream_t)stream, e0, e1, 0, im, out, sch, *planes);
+        return (int)hipGetLastError();
+#endif
+    }
     if (src != kTileSrcRgb) {
         const bool chroma = src == kTileSrcChroma;
         const auto gray = k_tile_encode<false, kSrcPlane>;
         const auto plane = k_tile_encode<false, kSrcPlane, kZrlBitsChroma, kZrlCodeChroma>;
-        if (taps && !chroma) hipLaunchKernelGGL((k_tile_encode<true, kSrcPlane>), grid, block, 0, (hipStream_t)stream, im, out, sch);
+        if (taps && !chroma) hipLaunchKernelGGL((k_tile_encode<true, kSrcPlane>), grid, block, 0, (hipStream_t)stream, im, out, sch, pl);
         else if (taps) return (int)hipErrorInvalidValue;                    // (no stage taps of a chroma scan)
-        else if (ev) hipExtLaunchKernelGGL(chroma ? plane : gray, grid, block, 0, (hipStream_t)stream, (hipEvent_t)ev[0], (hipEvent_t)ev[1], 0, im, out, sch);
-        else hipLaunchKernelGGL(chroma ? plane : gray, grid, block, 0, (hipStream_t)stream, im, out, sch);
+        else if (ev) hipExtLaunchKernelGGL(chroma ? plane : gray, grid, block, 0, (hipStream_t)stream, (hipEvent_t)ev[0], (hipEvent_t)ev[1], 0, im, out, sch, pl);
+        else hipLaunchKernelGGL(chroma ? plane : gray, grid, block, 0, (hipStream_t)stream, im, out, sch, pl);
         return (int)hipGetLastError();
     }
-    if (taps) hipLaunchKernelGGL(k_tile_encode<true>, grid, block, 0, (hipStream_t)stream, im, out, sch);
-    else if (ev) hipExtLaunchKernelGGL(k_tile_encode<false>, grid, block, 0, (hipStream_t)stream, (hipEvent_t)ev[0], (hipEvent_t)ev[1], 0, im, out, sch);
-    else hipLaunchKernelGGL(k_tile_encode<false>, grid, block, 0, (hipStream_t)stream, im, out, sch);
+    if (taps) hipLaunchKernelGGL(k_tile_encode<true>, grid, block, 0, (hipStream_t)stream, im, out, sch, pl);
+    else if (ev) hipExtLaunchKernelGGL(k_tile_encode<false>, grid, block, 0, (hipStream_t)stream, (hipEvent_t)ev[0], (hipEvent_t)ev[1], 0, im, out, sch, pl);
+    else hipLaunchKernelGGL(k_tile_encode<false>, grid, block, 0, (hipStream_t)stream, im, out, sch, pl);
     return (int)hipGetLastError();
 }
 

@@ -16,6 +16,7 @@ LIB_PATH = Path(os.environ.get("JPEGAMD_LIB") or (_PKG_ROOT / "libjpegamd.so"))
 HEADER_PATH = _PKG_ROOT.parent / "include" / "jpeg_compression.h"
 
 ORDER_BGR, ORDER_RGB, ORDER_GRAY = 0, 1, 2                  # JPEGAMD_ORDER_* (GRAY: one byte per pixel, the luma itself)
+ORDER_RGBA, ORDER_BGRA = 3, 4                                # four bytes per pixel, the fourth ignored
 SUBSAMPLE_444, SUBSAMPLE_420 = 1, 2                          # JPEGAMD_SUBSAMPLE_* (colour files)
 JFIF_PREFIX_BYTES = 328
 
@@ -32,6 +33,12 @@ class JpegAmdError(RuntimeError):
 class Image(C.Structure):
     _fields_ = [("pixels", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32), ("row_stride", C.c_int32),
                 ("bottom_up", C.c_int32), ("channel_order", C.c_int32), ("quality", C.c_int32)]
+
+
+class PlanarImage(C.Structure):
+    """JpegAmdPlanarImage: the R, G and B planes of one picture (device pointers), one byte per sample."""
+    _fields_ = [("plane", C.c_void_p * 3), ("width", C.c_int32), ("height", C.c_int32), ("row_stride", C.c_int32),
+                ("bottom_up", C.c_int32), ("quality", C.c_int32)]
 
 
 class Stats(C.Structure):
@@ -96,6 +103,7 @@ def _load() -> C.CDLL:
         "jpegamd_max_jfif_bytes_color": (u64, [i32, i32, i32]),
         "jpegamd_encode_color_async": (i32, [vp, C.POINTER(Image), i32, vp, u64, vp, vp]),
         "jpegamd_encode_color_batch_async": (i32, [vp, C.POINTER(Image), i32, i32, C.POINTER(C.c_void_p), u64, C.POINTER(C.c_void_p), vp]),
+        "jpegamd_encode_planar_batch_async": (i32, [vp, C.POINTER(PlanarImage), i32, i32, C.POINTER(C.c_void_p), u64, C.POINTER(C.c_void_p), vp]),
         "jpegamd_debug_chroma_groups": (i32, [i32, i32, i32, i32, i32, i32, i32, vp]),
         "jpegamd_debug_chroma_quant_table": (i32, [i32, vp]),
         "jpegamd_debug_chroma_mfma_consts": (i32, [i32, vp, vp, vp, vp, vp, vp]),
@@ -109,7 +117,7 @@ def _load() -> C.CDLL:
     }
     for name, (res, args) in sig.items():
         if name in ("jpegamd_encoder_set_pipeline", "jpegamd_gather_streams", "jpegamd_debug_mfma_offsets", "jpegamd_encode_color_batch_async",
-                    "jpegamd_debug_chroma_groups") and os.environ.get("JPEGAMD_LIB") and not hasattr(lib, name):
+                    "jpegamd_debug_chroma_groups", "jpegamd_encode_planar_batch_async") and os.environ.get("JPEGAMD_LIB") and not hasattr(lib, name):
             continue                                              # (A/B tooling: a variant build of an older round)
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = res, args
@@ -124,7 +132,8 @@ EXPORTED = ("jpegamd_encoder_create jpegamd_encoder_destroy jpegamd_max_jfif_byt
             "jpegamd_encode_bmp_memory jpegamd_parse_bmp jpegamd_encode_files jpegamd_gather_streams "
             "jpegamd_encode_rows_async jpegamd_export_segments jpegamd_import_segments jpegamd_finalize_async "
             "jpegamd_max_jfif_bytes_color jpegamd_encode_color_async jpegamd_encode_bmp_memory_color jpegamd_debug_chroma_quant_table "
-            "jpegamd_debug_chroma_mfma_consts jpegamd_debug_color_profile jpegamd_encode_color_batch_async").split()
+            "jpegamd_debug_chroma_mfma_consts jpegamd_debug_color_profile jpegamd_encode_color_batch_async "
+            "jpegamd_encode_planar_batch_async").split()
 
 
 def quant_table(quality: int = 50):
@@ -256,11 +265,14 @@ def encode_bmp_bytes_color(bmp: bytes, quality: int = 0, subsampling: int = SUBS
 _tensor_encoders = {}
 
 
-def encode_tensor(t, quality: int = 0, subsampling: int = SUBSAMPLE_420) -> bytes:
+def encode_tensor(t, quality: int = 0, subsampling: int = SUBSAMPLE_420, layout=None) -> bytes:
     """A uint8 DEVICE tensor -> JFIF file bytes: [H, W] a grayscale file (the tensor is the luma), [H, W, 3] (R, G, B) a colour file.
     Rows may be strided (t.stride(0) bytes apart); pixels within a row must be packed.  Runs on the tensor's device and the
-    current stream; one encoder context per device is kept and grown as needed."""
+    current stream; one encoder context per device is kept and grown as needed.
+    `layout` names how the picture is stored, as for encode_tensor_batch: "chw" [3, H, W], "rgba" / "bgra" [H, W, 4], "hwc" [H, W, 3]."""
     import torch
+    if layout is not None:
+        return encode_tensor_batch(t, quality, subsampling, layout, _single=True)[0]
     if t.dtype != torch.uint8 or not t.is_cuda:
         raise ValueError("encode_tensor needs a uint8 device tensor")
     if t.dim() == 2:
@@ -336,17 +348,80 @@ def _batch_tensor_layout(t):
     return n, h, w, (t.stride(1) if h > 1 else row_bytes), order
 
 
-def encode_tensor_batch(t, quality: int = 0, subsampling: int = SUBSAMPLE_420) -> list:
+LAYOUTS = ("hwc", "chw", "rgba", "bgra")
+
+
+def _named_layout(t, layout, single: bool):
+    """The pictures of `t` stored as `layout` says -> (count, height, width, row stride, channel order -- None for planes --,
+    picture index -> device pointer or (R, G, B) plane pointers, the tensors).  Shapes and strides only: host tensors pass."""
+    import torch
+    if layout not in LAYOUTS:
+        raise ValueError(f"layout must be one of {LAYOUTS} or None, not {layout!r}")
+    planes = list(t) if isinstance(t, (tuple, list)) else None
+    if planes is not None and (layout != "chw" or len(planes) != 3):
+        raise ValueError('a sequence of tensors is the R, G and B planes of layout="chw"')
+    tensors = planes if planes is not None else [t]
+    if any(not isinstance(x, torch.Tensor) or x.dtype != torch.uint8 for x in tensors):
+        raise ValueError("the encoder needs uint8 tensors")
+    lead = 0 if single else 1                                  # dimensions in front of a picture
+    if layout == "chw":
+        if planes is None:
+            if t.dim() != lead + 3 or t.shape[lead] != 3:
+                raise ValueError('layout="chw" takes [3, H, W] or [N, 3, H, W]')
+            planes = [t.select(lead, k) for k in range(3)]
+        if any(p.dim() != lead + 2 or p.shape != planes[0].shape for p in planes):
+            raise ValueError("the three planes must be [H, W] or [N, H, W] tensors of one shape")
+        if single:
+            planes = [p.unsqueeze(0) for p in planes]
+        n, h, w = planes[0].shape
+        if n < 1 or h < 1 or w < 1:
+            raise ValueError("the encoder needs at least one picture of at least one pixel")
+        if any(p.stride(2) != 1 for p in planes):
+            raise ValueError("samples of a row must be packed (last stride 1)")
+        strides = {(p.stride(1) if h > 1 else w) for p in planes}
+        if len(strides) != 1:
+            raise ValueError("the three planes of a picture must share one row stride")
+        stride = strides.pop()
+        if stride < w:
+            raise ValueError("rows overlap (the row stride is less than a row)")
+        return n, h, w, stride, None, (lambda i: tuple(p[i].data_ptr() for p in planes)), planes
+    c = 3 if layout == "hwc" else 4
+    if t.dim() != lead + 3 or t.shape[-1] != c:
+        raise ValueError(f'layout="{layout}" takes [H, W, {c}] or [N, H, W, {c}]')
+    if single:
+        t = t.unsqueeze(0)
+    n, h, w = t.shape[0], t.shape[1], t.shape[2]
+    if n < 1 or h < 1 or w < 1:
+        raise ValueError("the encoder needs at least one picture of at least one pixel")
+    if t.stride(3) != 1 or t.stride(2) != c:
+        raise ValueError(f"pixels of a row must be packed (pixel stride {c}, last stride 1)")
+    if h > 1 and t.stride(1) < c * w:
+        raise ValueError("rows overlap (the row stride is less than a row)")
+    order = {"hwc": ORDER_RGB, "rgba": ORDER_RGBA, "bgra": ORDER_BGRA}[layout]
+    return n, h, w, (t.stride(1) if h > 1 else c * w), order, (lambda i: t[i].data_ptr()), [t]
+
+
+def encode_tensor_batch(t, quality: int = 0, subsampling: int = SUBSAMPLE_420, layout=None, _single: bool = False) -> list:
     """A uint8 DEVICE tensor of N pictures -> N JFIF files: [N, H, W, 3] (R, G, B) colour files through
     jpegamd_encode_color_batch_async, [N, H, W] grayscale files through jpegamd_encode_batch_async.  Pictures may be strided
     (t[::2]), pixels within a row must be packed.  Batches of more than MAX_BATCH pictures go as several calls of at most
     MAX_BATCH.  Runs on the tensor's device and the current stream, with the per-device context of encode_tensor (grown to
-    hold a batch)."""
+    hold a batch).
+    `layout` names another storage, read where it lies (no repacking): "chw" [N, 3, H, W] -- or a sequence of three [N, H, W]
+    tensors, the R, G and B planes -- through jpegamd_encode_planar_batch_async (rows may be strided, the planes of a picture
+    share one row stride, any plane stride; subsampling 0 gives grayscale files); "rgba" / "bgra" [N, H, W, 4], the fourth byte
+    ignored; "hwc" the explicit name of [N, H, W, 3].  The files are those of the same R, G, B values as [N, H, W, 3]."""
     import torch
-    n, h, w, stride, order = _batch_tensor_layout(t)
-    if not t.is_cuda:
+    if layout is None:
+        n, h, w, stride, order = _batch_tensor_layout(t)
+        ptr, tensors = (lambda i: t[i].data_ptr()), [t]
+    else:
+        n, h, w, stride, order, ptr, tensors = _named_layout(t, layout, _single)
+    if any(not x.is_cuda or x.device != tensors[0].device for x in tensors):
         raise ValueError("encode_tensor_batch needs a device tensor")
-    dev = t.device.index if t.device.index is not None else torch.cuda.current_device()
+    device = tensors[0].device
+    dev = device.index if device.index is not None else torch.cuda.current_device()
+    gray = order == ORDER_GRAY or (order is None and subsampling == 0)
     files = []
     with torch.cuda.device(dev):
         per = min(n, MAX_BATCH)
@@ -358,20 +433,24 @@ def encode_tensor_batch(t, quality: int = 0, subsampling: int = SUBSAMPLE_420) -
                 enc.close()
             enc = Encoder(mw, mh)
             _tensor_encoders[dev] = (enc, mw, mh)
-        cap = max_jfif_bytes(w, h) if order == ORDER_GRAY else max_jfif_bytes_color(w, h, subsampling)
-        out = torch.empty((per, cap), dtype=torch.uint8, device=t.device)
-        sizes = torch.zeros(per, dtype=torch.int64, device=t.device)
-        stream = torch.cuda.current_stream(t.device).cuda_stream
+        cap = max_jfif_bytes(w, h) if gray else max_jfif_bytes_color(w, h, subsampling)
+        out = torch.empty((per, cap), dtype=torch.uint8, device=device)
+        sizes = torch.zeros(per, dtype=torch.int64, device=device)
+        stream = torch.cuda.current_stream(device).cuda_stream
         for b0 in range(0, n, MAX_BATCH):
             k = min(MAX_BATCH, n - b0)
-            imgs = [Encoder.image(t[b0 + i].data_ptr(), w, h, stride, bottom_up=False, channel_order=order, quality=quality)
-                    for i in range(k)]
             outs = [out[i].data_ptr() for i in range(k)]
             size_ptrs = [sizes.data_ptr() + 8 * i for i in range(k)]
-            if order == ORDER_GRAY:
-                enc.encode_batch_async(imgs, outs, cap, size_ptrs, True, stream)
+            if order is None:
+                imgs = [Encoder.planar_image(ptr(b0 + i), w, h, stride, bottom_up=False, quality=quality) for i in range(k)]
+                enc.encode_planar_batch_async(imgs, subsampling, outs, cap, size_ptrs, stream)
             else:
-                enc.encode_color_batch_async(imgs, subsampling, outs, cap, size_ptrs, stream)
+                imgs = [Encoder.image(ptr(b0 + i), w, h, stride, bottom_up=False, channel_order=order, quality=quality)
+                        for i in range(k)]
+                if order == ORDER_GRAY:
+                    enc.encode_batch_async(imgs, outs, cap, size_ptrs, True, stream)
+                else:
+                    enc.encode_color_batch_async(imgs, subsampling, outs, cap, size_ptrs, stream)
             enc.finish()
             got = sizes[:k].cpu().tolist()
             files += [bytes(out[i, :got[i]].cpu().numpy().tobytes()) for i in range(k)]
@@ -441,6 +520,23 @@ class Encoder:
     def image(pixels_ptr: int, width: int, height: int, row_stride: int, bottom_up: bool = True,
               channel_order: int = ORDER_BGR, quality: int = 0) -> Image:
         return Image(pixels_ptr, width, height, row_stride, 1 if bottom_up else 0, channel_order, quality)
+
+    @staticmethod
+    def planar_image(planes, width: int, height: int, row_stride: int, bottom_up: bool = False, quality: int = 0) -> PlanarImage:
+        """`planes`: the device pointers of the R, G and B planes, each `row_stride` bytes per stored row."""
+        r, g, b = planes
+        return PlanarImage((C.c_void_p * 3)(r, g, b), width, height, row_stride, 1 if bottom_up else 0, quality)
+
+    def encode_planar_batch_async(self, imgs, subsampling: int, out_ptrs, out_cap: int, size_ptrs, stream: int = 0):
+        """The files of `len(imgs)` planar pictures of one geometry (jpegamd_encode_planar_batch_async): subsampling 0 grayscale
+        files, SUBSAMPLE_444 / SUBSAMPLE_420 colour files; the context as for the packed batch entries."""
+        n = len(imgs)
+        arr = (PlanarImage * n)(*imgs)
+        outs = (C.c_void_p * n)(*[C.c_void_p(p) for p in out_ptrs])
+        sizes = (C.c_void_p * n)(*[C.c_void_p(p) for p in size_ptrs])
+        rc = lib.jpegamd_encode_planar_batch_async(self._h, arr, n, int(subsampling), outs, out_cap, sizes, C.c_void_p(stream))
+        if rc:
+            raise JpegAmdError(rc, "jpegamd_encode_planar_batch_async")
 
     def encode_async(self, img: Image, out_ptr: int, out_cap: int, size_ptr: int, with_container: bool = True,
                      stream: int = 0):

@@ -6,6 +6,12 @@ ring (every kernel's own begin / end events), with the per-kernel durations.  Pr
 
 With --batch N the same timed loop goes through jpegamd_encode_color_batch_async: N distinct pictures (seeds 1 .. N) per call,
 reported as the whole call's time (ns_total) per picture, and Gpixels/s.
+
+With --layout {hwc,chw,rgba} (and --batch N, default 8) the pictures are device tensors stored that way -- [N, H, W, 3], [N, 3, H, W],
+[N, H, W, 4] -- and go through the entry that reads them where they lie, 4:2:0 only.  Every call is timed as a whole between two
+events on the stream; --rounds R medians of --steps calls each are reported, with their spread (max - min).  --repack (chw only)
+also times the route without the planar entry, in the same run and alternating with the direct one: permute(0, 2, 3, 1) into a
+preallocated [N, H, W, 3] tensor, then the packed batch entry.
 """
 from __future__ import annotations
 
@@ -30,6 +36,9 @@ def main() -> None:
     ap.add_argument("--quality", type=int, default=50)
     ap.add_argument("--kind", type=int, default=0)
     ap.add_argument("--batch", type=int, default=None, help="pictures per call through the colour batch entry (1 .. 32)")
+    ap.add_argument("--layout", choices=("hwc", "chw", "rgba"), default=None, help="device tensors stored this way, read where they lie")
+    ap.add_argument("--rounds", type=int, default=5, help="--layout: medians taken (each of --steps calls)")
+    ap.add_argument("--repack", action="store_true", help="--layout chw: also time permute + packed encode")
     a = ap.parse_args()
     import torch                          # (the device runtime comes up through torch first, as in bench.py)
     if not torch.cuda.is_available():
@@ -39,6 +48,9 @@ def main() -> None:
 
     dev = torch.device("cuda:0")
     w = h = a.size
+    if a.layout is not None:
+        run_layout(a, jpegamd, torch, dev)
+        return
     if a.batch is not None:
         run_batch(a, jpegamd, torch, dev)
         return
@@ -103,6 +115,80 @@ def run_batch(a, jpegamd, torch, dev) -> None:
                           "ns_total_median": int(t), "us_per_picture": round(t / n / 1000, 1),
                           "gpixels_per_s": round(n * w * h / t, 2)}))
         del outs
+
+
+def run_layout(a, jpegamd, torch, dev) -> None:
+    w = h = a.size
+    n = a.batch or 8
+    sub = jpegamd.SUBSAMPLE_420
+    pics = []
+    for i in range(n):
+        bmp = jpegamd.synth_bmp(w, h, 1 + i, a.kind, 0)
+        img, off = jpegamd.parse_bmp(bmp)
+        rows = torch.frombuffer(bytearray(bmp[off:off + img.row_stride * h]), dtype=torch.uint8).to(dev).view(h, img.row_stride)
+        pics.append(rows[:, :3 * w].reshape(h, w, 3).flip(0).flip(2))       # bottom-up B, G, R -> top-down R, G, B
+        del bmp, rows
+    hwc = torch.stack(pics)
+    del pics
+    if a.layout == "chw":
+        src = hwc.permute(0, 3, 1, 2).contiguous()
+    elif a.layout == "rgba":
+        src = torch.cat([hwc, torch.full_like(hwc[..., :1], 255)], dim=3)
+    else:
+        src = hwc
+    if a.layout != "hwc" and not a.repack:
+        del hwc
+    enc = jpegamd.Encoder(w, n * h)
+    stream = torch.cuda.current_stream().cuda_stream
+    cap = jpegamd.max_jfif_bytes_color(w, h, sub)
+    outs = [torch.empty(cap, dtype=torch.uint8, device=dev) for _ in range(n)]
+    sizes = torch.zeros(n, dtype=torch.int64, device=dev)
+    out_ptrs = [o.data_ptr() for o in outs]
+    size_ptrs = [sizes.data_ptr() + 8 * i for i in range(n)]
+
+    def packed_descs(t, order, bpp):
+        return [jpegamd.Encoder.image(t[i].data_ptr(), w, h, bpp * w, False, order, a.quality) for i in range(n)]
+
+    if a.layout == "chw":
+        planar = [jpegamd.Encoder.planar_image(tuple(src[i, k].data_ptr() for k in range(3)), w, h, w, False, a.quality) for i in range(n)]
+        direct = lambda: enc.encode_planar_batch_async(planar, sub, out_ptrs, cap, size_ptrs, stream)
+    else:
+        descs = packed_descs(src, jpegamd.ORDER_RGBA if a.layout == "rgba" else jpegamd.ORDER_RGB, 4 if a.layout == "rgba" else 3)
+        direct = lambda: enc.encode_color_batch_async(descs, sub, out_ptrs, cap, size_ptrs, stream)
+    routes = {"direct": direct}
+    if a.repack:
+        if a.layout != "chw":
+            sys.exit("--repack needs --layout chw")
+        tmp = torch.empty_like(hwc)
+        del hwc
+        tmp_descs = packed_descs(tmp, jpegamd.ORDER_RGB, 3)
+
+        def repack():
+            tmp.copy_(src.permute(0, 2, 3, 1))
+            enc.encode_color_batch_async(tmp_descs, sub, out_ptrs, cap, size_ptrs, stream)
+        routes["repack"] = repack
+    medians = {k: [] for k in routes}
+    got = {}
+    for k, call in routes.items():
+        for _ in range(a.warmup):
+            call()
+        enc.finish()
+        got[k] = sizes.cpu().tolist()
+    for _ in range(a.rounds):
+        for k, call in routes.items():                                      # the routes alternate: one thermal history
+            evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(a.steps)]
+            for e0, e1 in evs:
+                e0.record()
+                call()
+                e1.record()
+            enc.finish()
+            medians[k].append(statistics.median(e0.elapsed_time(e1) for e0, e1 in evs) * 1000.0 / n)
+    for k in routes:
+        m = medians[k]
+        print(json.dumps({"layout": a.layout, "route": k, "width": w, "height": h, "batch": n, "quality": a.quality, "kind": a.kind,
+                          "steps": a.steps, "rounds": a.rounds, "bytes": got[k], "us_per_picture_medians": [round(v, 1) for v in m],
+                          "us_per_picture": round(statistics.median(m), 1), "spread_us": round(max(m) - min(m), 1),
+                          "gpixels_per_s": round(w * h / statistics.median(m) / 1000, 2)}))
 
 
 if __name__ == "__main__":
