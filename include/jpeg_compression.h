@@ -198,6 +198,35 @@ typedef struct JpegAmdPlanarImage {
 int32_t jpegamd_encode_planar_batch_async(JpegAmdEncoder *enc, const JpegAmdPlanarImage *imgs, int32_t count, int32_t subsampling,
                                           void *const *outs_dev, uint64_t out_capacity, void *const *out_sizes_dev, void *stream);
 
+/* ---- YCbCr pictures: samples that already ARE Y, Cb and Cr (a video decoder's NV12 / I420 frame, a resizer's output) ----------------
+ * The planes are coded as they are given: the samples are taken as JFIF full-range values (Y 0..255, Cb / Cr centred on 128), and
+ * NO range or matrix conversion, no subsampling and no filtering is done -- limited-range (16..235) or BT.709 material must be
+ * converted by the caller.  The Y plane is width x height; the chroma planes are cw x ch: width x height at JPEGAMD_SUBSAMPLE_444,
+ * ceil(width / 2) x ceil(height / 2) at JPEGAMD_SUBSAMPLE_420 (odd sizes are allowed). */
+#define JPEGAMD_CHROMA_PLANES 0   /* cb and cr: two planes of one byte per sample (I420; YV12 by swapping the pointers; planar 4:4:4) */
+#define JPEGAMD_CHROMA_CBCR   1   /* cb: ONE plane of byte pairs Cb0 Cr0 Cb1 Cr1 ... (NV12; NV24 at 4:4:4); cr is ignored and may be null */
+#define JPEGAMD_CHROMA_CRCB   2   /* the same with Cr first (NV21 / NV42) */
+typedef struct JpegAmdYCbCrImage {
+    const void *y, *cb, *cr;      /* DEVICE pointers, top row first */
+    int32_t width, height;        /* of the Y plane, 1..65535 */
+    int32_t y_stride, c_stride;   /* bytes between rows; y_stride >= width; c_stride >= cw (PLANES) or >= 2*cw (CBCR / CRCB) */
+    int32_t chroma_layout;        /* JPEGAMD_CHROMA_* */
+    int32_t quality;
+} JpegAmdYCbCrImage;
+/* The colour files of `count` (1 .. JPEGAMD_MAX_BATCH) YCbCr pictures of ONE geometry (width, height, both strides, layout, quality),
+ * read where they lie.  The file is the colour file of jpegamd_encode_color_batch_async for (width, height, quality, subsampling)
+ * with these samples in its three scans: the Y scan is the entropy-coded segment of the grayscale file of the Y plane, the Cb and
+ * Cr scans are the chroma pipeline (tables K.2, K.4 / K.6) over the chroma planes.  Fed the Y, Cb and Cr that the colour entry derives
+ * from an RGB picture it writes that entry's file byte for byte, and every chroma layout of the same samples gives the same file.
+ * No chroma-plane pass runs and no plane scratch is allocated.  Any pointer alignment and stride is taken (planes on dword
+ * boundaries with strides that are multiples of 4 below 2^24 take the fast loader).  Context sizing, capacity behaviour (size 0 and
+ * JPEGAMD_ERR_HUFF_CAPACITY at jpegamd_encoder_finish), status, statistics and profiling are those of
+ * jpegamd_encode_color_batch_async.  out_sizes_dev[i] is a DEVICE uint64_t.  Bad arguments -- a null array or element, a null y or
+ * cb, a null cr with JPEGAMD_CHROMA_PLANES, an unknown layout or subsampling, count out of range, a stride too short, pictures of
+ * different geometry -- are refused with JPEGAMD_ERR_ARG before the context is read. */
+int32_t jpegamd_encode_ycbcr_batch_async(JpegAmdEncoder *enc, const JpegAmdYCbCrImage *imgs, int32_t count, int32_t subsampling,
+                                         void *const *outs_dev, uint64_t out_capacity, void *const *out_sizes_dev, void *stream);
+
 /* Which kernels follow k_tile_encode for whole pictures (no reference counterpart: a tuning knob, results are byte-identical).
  *   PAIR    k_segment_merge + k_finalize: the tiles' bit strings joined per segment, then stitched behind a kernel boundary;
  *   STITCH  k_stitch: one pass, the offsets handed from workgroup to workgroup inside the launch (decoupled look-back);

@@ -477,7 +477,7 @@ static int launch_transform(JpegAmdEncoder *e, const ImageDesc &im, bool taps, i
                             void *stream, hipEvent_t *ev = nullptr /*2: begin/end*/, int src = kTileSrcRgb, const PlaneSet *ps = nullptr) {
     TransformOutM to;
     std::memset(&to, 0, sizeof(to));
-    const bool chroma = src == kTileSrcChroma;
+    const bool chroma = src == kTileSrcChroma || src == kTileSrcChromaPair;
     to.tables = chroma ? e->color.tables_dev : e->tables_dev; to.stamps = e->stamps_dev;
     to.tap_y = ty; to.tap_zz = tzz; to.tap_mask = tmask;
     to.tile_head = e->tile_head; to.tile_over = e->tile_over; to.code_tab = chroma ? e->color.code_tab : e->code_tab;
@@ -514,7 +514,7 @@ static int launch_transform_and_entropy(JpegAmdEncoder *e, const ImageDesc &im, 
     MergeArgs ea;
     std::memset(&ea, 0, sizeof(ea));
     ea.tile_head = e->tile_head; ea.tile_over = e->tile_over;
-    ea.huff = src == kTileSrcChroma ? e->color.huff : e->huff; ea.num_segs = im.num_segs; ea.segs_per_row = im.segs_per_row; ea.tiles_per_row = im.tiles_per_row;
+    ea.huff = (src == kTileSrcChroma || src == kTileSrcChromaPair) ? e->color.huff : e->huff; ea.num_segs = im.num_segs; ea.segs_per_row = im.segs_per_row; ea.tiles_per_row = im.tiles_per_row;
     ea.seg_tiles = im.seg_tiles;
     ea.seg_begin = im.seg_begin; ea.seg_end = im.seg_end;
     ea.tiles_per_image = im.batch > 1 ? im.num_tiles : 0;
@@ -1072,9 +1072,18 @@ static int32_t color_batch_alloc(JpegAmdEncoder *e, size_t planes, size_t scans)
     return JPEGAMD_OK;
 }
 
+// The caller's own chroma (jpegamd_encode_ycbcr_batch_async): cb[i] / cr[i] the planes of picture i (a pair layout: cb[i] alone).
+struct YccSource {
+    int32_t layout, c_stride;
+    const uint8_t *cb[kMaxBatch], *cr[kMaxBatch];
+};
+
 // The colour files of a batch whose arguments are known to be good: g0 describes every picture, ps holds their pixels.
+// `ycc` (a YCbCr batch): g0 / px are the Y planes as a GRAY picture, the chroma scans read the caller's planes -- no
+// k_chroma_planes_batch launch, no plane scratch.
 static int32_t color_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, const PlaneSet &px, int32_t count, int32_t subsampling,
-                           void *const *outs_dev, uint64_t out_capacity, uint64_t *const *out_sizes_dev, void *stream_) {
+                           void *const *outs_dev, uint64_t out_capacity, uint64_t *const *out_sizes_dev, void *stream_,
+                           const YccSource *ycc = nullptr) {
     // Y: the grayscale batch's launch plan
     ImageDesc iy;
     const bool stitch_y = use_stitch(e, g0.width, g0.height);
@@ -1106,7 +1115,7 @@ static int32_t color_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, const Plan
     const size_t slot_bytes = round_up(scan_bound(blocks_of(cw, ch)) + 64, 256);      // (k_append_scans_batch reads 16 bytes at a time)
     rc = color_alloc_consts(e);
     if (rc) return rc;
-    rc = color_batch_alloc(e, planes * plane_bytes + 256, planes * slot_bytes);
+    rc = color_batch_alloc(e, ycc ? 0 : planes * plane_bytes + 256, planes * slot_bytes);
     if (rc) return rc;
     rc = prepare_constants(e, &g0, false);
     if (rc) return rc;
@@ -1134,18 +1143,21 @@ static int32_t color_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, const Plan
     }
     HIP_TRY(hipMemsetAsync(c.bmeta, 0, kBatchMetaStats + kBatchMetaPic, stream));
 
-    ChromaPlanesBatchArgs pa;
-    std::memset(&pa, 0, sizeof(pa));
-    for (int i = 0; i < count; ++i) { pa.pixels[i] = px.p[0][i]; pa.pixels_g[i] = px.p[1][i]; pa.pixels_b[i] = px.p[2][i]; }
-    pa.layout = g0.channel_order == kOrderPlanar ? kChromaSrcPlanar : (is_px4(g0.channel_order) ? kChromaSrcPx4 : kChromaSrcPx3);
-    pa.batch = count;
-    pa.width = g0.width; pa.height = g0.height; pa.row_stride = g0.row_stride; pa.bottom_up = g0.bottom_up ? 1 : 0;
-    pa.rgb = (g0.channel_order == JPEGAMD_ORDER_BGR || g0.channel_order == JPEGAMD_ORDER_BGRA) ? 0 : 1;
-    pa.sub420 = subsampling == JPEGAMD_SUBSAMPLE_420 ? 1 : 0;
-    pa.cw = cw; pa.ch = ch; pa.pitch = pitch;
-    pa.plane_bytes = plane_bytes; pa.planes = c.bplanes;
-    hipEvent_t ev_planes[2] = {cev ? cev[0] : nullptr, nullptr};
-    if (launch_chroma_planes_batch(pa, stream, cev ? (void *const *)ev_planes : nullptr)) return JPEGAMD_ERR_HIP;
+    hipEvent_t *const ev_y = ycc ? cev : nullptr;     // a YCbCr batch begins with its Y launch: that kernel's begin stamp opens ns_total
+    if (!ycc) {
+        ChromaPlanesBatchArgs pa;
+        std::memset(&pa, 0, sizeof(pa));
+        for (int i = 0; i < count; ++i) { pa.pixels[i] = px.p[0][i]; pa.pixels_g[i] = px.p[1][i]; pa.pixels_b[i] = px.p[2][i]; }
+        pa.layout = g0.channel_order == kOrderPlanar ? kChromaSrcPlanar : (is_px4(g0.channel_order) ? kChromaSrcPx4 : kChromaSrcPx3);
+        pa.batch = count;
+        pa.width = g0.width; pa.height = g0.height; pa.row_stride = g0.row_stride; pa.bottom_up = g0.bottom_up ? 1 : 0;
+        pa.rgb = (g0.channel_order == JPEGAMD_ORDER_BGR || g0.channel_order == JPEGAMD_ORDER_BGRA) ? 0 : 1;
+        pa.sub420 = subsampling == JPEGAMD_SUBSAMPLE_420 ? 1 : 0;
+        pa.cw = cw; pa.ch = ch; pa.pitch = pitch;
+        pa.plane_bytes = plane_bytes; pa.planes = c.bplanes;
+        hipEvent_t ev_planes[2] = {cev ? cev[0] : nullptr, nullptr};
+        if (launch_chroma_planes_batch(pa, stream, cev ? (void *const *)ev_planes : nullptr)) return JPEGAMD_ERR_HIP;
+    }
 
     // Y: every picture's scan behind the colour prefix, no EOI; its size into y_size
     {
@@ -1154,11 +1166,11 @@ static int32_t color_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, const Plan
         const ScanTarget ty = {c.hdr, c.hdr_len, 0, &lstats[0], false};
         PictureStatsArgs ps = {e->tile_head, e->huff, iy.num_tiles, count, 0, 0, pic};
         if (stitch_y) {
-            if (launch_transform(e, iy, false, nullptr, nullptr, nullptr, stream, nullptr, src_of(&g0), &px)) return JPEGAMD_ERR_HIP;
+            if (launch_transform(e, iy, false, nullptr, nullptr, nullptr, stream, ev_y, src_of(&g0), &px)) return JPEGAMD_ERR_HIP;
             if (launch_picture_stats(ps, stream)) return JPEGAMD_ERR_HIP;
             if (run_stitch(e, iy, outs_dev, out_capacity, sizes, 1, stream, nullptr, &ty)) return JPEGAMD_ERR_HIP;
         } else {
-            if (launch_transform_and_entropy(e, iy, false, nullptr, nullptr, nullptr, stream, nullptr, src_of(&g0), &px)) return JPEGAMD_ERR_HIP;
+            if (launch_transform_and_entropy(e, iy, false, nullptr, nullptr, nullptr, stream, ev_y, src_of(&g0), &px)) return JPEGAMD_ERR_HIP;
             if (launch_picture_stats(ps, stream)) return JPEGAMD_ERR_HIP;
             if (run_finalize_batch(e, iy, outs_dev, out_capacity, sizes, 1, stream, nullptr, &ty)) return JPEGAMD_ERR_HIP;
         }
@@ -1167,6 +1179,16 @@ static int32_t color_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, const Plan
     JpegAmdImage pimg = g0;
     pimg.width = cw; pimg.height = ch; pimg.row_stride = pitch; pimg.bottom_up = 0; pimg.channel_order = JPEGAMD_ORDER_GRAY;
     pimg.pixels = c.bplanes;
+    int csrc = kTileSrcChroma;
+    bool ycc_aligned = true;
+    if (ycc) {
+        pimg.pixels = ycc->cb[0]; pimg.row_stride = ycc->c_stride;
+        const bool pair = ycc->layout != JPEGAMD_CHROMA_PLANES;
+        if (pair) csrc = kTileSrcChromaPair;
+        uintptr_t bits = 0;
+        for (int i = 0; i < count; ++i) bits |= (uintptr_t)ycc->cb[i] | (pair ? 0 : (uintptr_t)ycc->cr[i]);
+        ycc_aligned = (bits & 3u) == 0;
+    }
     for (int l = 0; l < plan.launches; ++l) {
         const int first = l * plan.group, n = std::min(plan.group, planes - first);
         ImageDesc ic;
@@ -1175,7 +1197,10 @@ static int32_t color_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, const Plan
         void *outs[kMaxBatch];
         uint64_t *sizes[kMaxBatch];
         for (int i = 0; i < n; ++i) {
-            ic.batch_pixels[i] = c.bplanes + (size_t)(first + i) * plane_bytes;
+            const int j = first + i;                                   // the plane's index in the whole call: picture j / 2, Cb (even) or Cr (odd)
+            if (!ycc) ic.batch_pixels[i] = c.bplanes + (size_t)j * plane_bytes;
+            else if (csrc == kTileSrcChromaPair) ic.batch_pixels[i] = ycc->cb[j / 2];
+            else ic.batch_pixels[i] = (j & 1) ? ycc->cr[j / 2] : ycc->cb[j / 2];
             outs[i] = c.bscans + (size_t)(first + i) * slot_bytes;
             sizes[i] = c_size + first + i;
         }
@@ -1183,14 +1208,18 @@ static int32_t color_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, const Plan
         ic.batch = n;
         ic.tile_end = n * ic.num_tiles;
         ic.seg_end = n * ic.num_segs;
+        if (!ycc_aligned) ic.fast_ok = 0;
+        // a pair plane: launch image i reads byte (weights + i) & 1 of each pair -- the parity of its plane in the WHOLE call (a group
+        // may be odd: a launch then starts on a Cr plane), flipped when Cr is stored first
+        if (csrc == kTileSrcChromaPair) ic.weights = (uint32_t)((first & 1) ^ (ycc->layout == JPEGAMD_CHROMA_CRCB ? 1 : 0));
         const ScanTarget tc = {c.hdr, 0, 0, &lstats[1 + l], true};
         PictureStatsArgs ps = {e->tile_head, c.huff, ic.num_tiles, n, 1, first, pic};
         if (plan.stitch) {
-            if (launch_transform(e, ic, false, nullptr, nullptr, nullptr, stream, nullptr, kTileSrcChroma)) return JPEGAMD_ERR_HIP;
+            if (launch_transform(e, ic, false, nullptr, nullptr, nullptr, stream, nullptr, csrc)) return JPEGAMD_ERR_HIP;
             if (launch_picture_stats(ps, stream)) return JPEGAMD_ERR_HIP;
             if (run_stitch(e, ic, outs, slot_bytes, sizes, 1, stream, nullptr, &tc)) return JPEGAMD_ERR_HIP;
         } else {
-            if (launch_transform_and_entropy(e, ic, false, nullptr, nullptr, nullptr, stream, nullptr, kTileSrcChroma)) return JPEGAMD_ERR_HIP;
+            if (launch_transform_and_entropy(e, ic, false, nullptr, nullptr, nullptr, stream, nullptr, csrc)) return JPEGAMD_ERR_HIP;
             if (launch_picture_stats(ps, stream)) return JPEGAMD_ERR_HIP;
             if (run_finalize_batch(e, ic, outs, slot_bytes, sizes, 1, stream, nullptr, &tc)) return JPEGAMD_ERR_HIP;
         }
@@ -1263,6 +1292,43 @@ extern "C" int32_t jpegamd_encode_planar_batch_async(JpegAmdEncoder *e, const Jp
     g0.channel_order = kOrderPlanar; g0.quality = p0.quality;
     if (subsampling == 0) return gray_batch(e, g0, ps, count, outs_dev, out_capacity, sizes, 1, stream_);
     return color_batch(e, g0, ps, count, subsampling, outs_dev, out_capacity, sizes, stream_);
+}
+
+// `count` YCbCr pictures: the argument checks, then the colour batch with the Y planes as its one-byte source and the caller's chroma.
+extern "C" int32_t jpegamd_encode_ycbcr_batch_async(JpegAmdEncoder *e, const JpegAmdYCbCrImage *imgs, int32_t count, int32_t subsampling,
+                                                    void *const *outs_dev, uint64_t out_capacity, void *const *out_sizes_dev,
+                                                    void *stream_) {
+    // the arguments first: nothing of the context is read before they are known to be good
+    if (!e || !imgs || !outs_dev || !out_sizes_dev || count < 1 || count > kMaxBatch) return JPEGAMD_ERR_ARG;
+    if (subsampling != JPEGAMD_SUBSAMPLE_444 && subsampling != JPEGAMD_SUBSAMPLE_420) return JPEGAMD_ERR_ARG;
+    const JpegAmdYCbCrImage &p0 = imgs[0];
+    if (p0.chroma_layout != JPEGAMD_CHROMA_PLANES && p0.chroma_layout != JPEGAMD_CHROMA_CBCR && p0.chroma_layout != JPEGAMD_CHROMA_CRCB)
+        return JPEGAMD_ERR_ARG;
+    if (p0.width <= 0 || p0.height <= 0 || p0.width > 65535 || p0.height > 65535) return JPEGAMD_ERR_ARG;
+    const bool pair = p0.chroma_layout != JPEGAMD_CHROMA_PLANES;
+    int cw, ch;
+    chroma_dims(p0.width, p0.height, subsampling, &cw, &ch);
+    if (p0.y_stride < p0.width || p0.c_stride < (pair ? 2 * cw : cw)) return JPEGAMD_ERR_ARG;
+    PlaneSet ps = {};
+    YccSource ycc = {};
+    ycc.layout = p0.chroma_layout; ycc.c_stride = p0.c_stride;
+    uint64_t *sizes[kMaxBatch];
+    for (int i = 0; i < count; ++i) {
+        const JpegAmdYCbCrImage &g = imgs[i];
+        if (!outs_dev[i] || !out_sizes_dev[i] || !g.y || !g.cb || (!pair && !g.cr)) return JPEGAMD_ERR_ARG;
+        if (g.width != p0.width || g.height != p0.height || g.y_stride != p0.y_stride || g.c_stride != p0.c_stride ||
+            g.chroma_layout != p0.chroma_layout || g.quality != p0.quality)
+            return JPEGAMD_ERR_ARG;
+        ps.p[0][i] = (const uint8_t *)g.y;
+        ycc.cb[i] = (const uint8_t *)g.cb;
+        ycc.cr[i] = pair ? nullptr : (const uint8_t *)g.cr;
+        sizes[i] = (uint64_t *)out_sizes_dev[i];
+    }
+    JpegAmdImage g0;
+    g0.pixels = p0.y;
+    g0.width = p0.width; g0.height = p0.height; g0.row_stride = p0.y_stride; g0.bottom_up = 0;
+    g0.channel_order = JPEGAMD_ORDER_GRAY; g0.quality = p0.quality;
+    return color_batch(e, g0, ps, count, subsampling, outs_dev, out_capacity, sizes, stream_, &ycc);
 }
 
 // The capacity status is STICKY on the device: every kernel only ORs into it, and it is cleared here, after it was read.

@@ -161,7 +161,10 @@ struct TransformOutM {
 // a chroma plane, coded with the chroma tables: TransformOutM must then point at the chroma constants).
 // kTileSrcPx4: 4 bytes per pixel (RGBA / BGRA; ImageDesc::weights, the fourth byte ignored); kTileSrcPlanar: the R, G and B planes
 // of one byte per sample -- R in ImageDesc::batch_pixels, G and B in `planes`.  Neither has a stage-tap or a stamped variant.
-constexpr int kTileSrcRgb = 0, kTileSrcGray = 1, kTileSrcChroma = 2, kTileSrcPx4 = 3, kTileSrcPlanar = 4;
+// kTileSrcChromaPair: a chroma scan (chroma tables, as kTileSrcChroma) whose samples are one component of a plane of byte pairs
+// (Cb Cr Cb Cr ...): launch image i reads component (ImageDesc::weights + i) & 1 of the pair plane batch_pixels[i]; width, height and
+// row_stride describe the component (width pairs per row, row_stride bytes between rows).  Plain build only, like the two above.
+constexpr int kTileSrcRgb = 0, kTileSrcGray = 1, kTileSrcChroma = 2, kTileSrcPx4 = 3, kTileSrcPlanar = 4, kTileSrcChromaPair = 5;
 struct TilePlanes {                     // the second and third plane of every picture of a planar launch (its own kernel argument)
     const uint8_t *g[kMaxBatch];
     const uint8_t *b[kMaxBatch];

@@ -147,7 +147,9 @@ static_assert(kPassItems * (27 + 3 * (int)kZrlBitsChroma) / 32 + 6 <= kWinStr &&
 //   kSrcPlane  1 byte per pixel: the sample itself (a GRAY picture, or a chroma plane of k_chroma_planes)
 //   kSrcPx4    4 bytes per pixel (RGBA / BGRA): luma by the weights of ImageDesc, whose fourth weight is 0
 //   kSrcPlanar three planes of one byte per sample, R (ImageDesc::batch_pixels), G and B (TilePlanes)
-constexpr int kSrcRgb = 0, kSrcPlane = 1, kSrcPx4 = 2, kSrcPlanar = 3;
+//   kSrcPair   one plane of byte pairs (Cb Cr Cb Cr ...: NV12 chroma), of which a launch image takes ONE component: launch image i
+//              reads component (ImageDesc::weights + i) & 1 of the pair plane ImageDesc::batch_pixels[i]
+constexpr int kSrcRgb = 0, kSrcPlane = 1, kSrcPx4 = 2, kSrcPlanar = 3, kSrcPair = 4;
 // The kernel's last argument: the G and B planes for kSrcPlanar, an empty struct -- no kernel-argument bytes, so the offsets of
 // the hidden arguments behind it stay where they were -- for every other source.
 struct NoPlanes {};
@@ -160,6 +162,15 @@ __device__ __forceinline__ f16x8 plane_row8_f16(uint32_t d0, uint32_t d1) {
     typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
     const u32x4 packed = {__builtin_amdgcn_perm(0u, d0, 0x0C010C00u), __builtin_amdgcn_perm(0u, d0, 0x0C030C02u),
                           __builtin_amdgcn_perm(0u, d1, 0x0C010C00u), __builtin_amdgcn_perm(0u, d1, 0x0C030C02u)};
+    return __builtin_bit_cast(f16x8, packed);
+}
+
+// 8 byte pairs (4 dwords) -> the B fragment of one k-step half, from ONE component of the pairs: the selector takes bytes 0 / 2
+// (0x0C020C00) or bytes 1 / 3 (0x0C030C01) of a dword into the two halves -- the four v_perm of plane_row8_f16 over twice the bytes.
+__device__ __forceinline__ f16x8 pair_row8_f16(const uint32_t *d, uint32_t sel) {
+    typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
+    const u32x4 packed = {__builtin_amdgcn_perm(0u, d[0], sel), __builtin_amdgcn_perm(0u, d[1], sel),
+                          __builtin_amdgcn_perm(0u, d[2], sel), __builtin_amdgcn_perm(0u, d[3], sel)};
     return __builtin_bit_cast(f16x8, packed);
 }
 
@@ -217,6 +228,13 @@ __device__ __forceinline__ int plane_clamped(const ImageDesc &im, const uint8_t 
     x = min(x, im.width - 1);
     y = min(y, im.height - 1);
     return (int)row_ptr(im, pixels, y)[x];
+}
+
+// Component `comp` (0 / 1) of byte pair (x, y) of a pair plane, with the edge clamp.
+__device__ __forceinline__ int pair_clamped(const ImageDesc &im, const uint8_t *pixels, int comp, int x, int y) {
+    x = min(x, im.width - 1);
+    y = min(y, im.height - 1);
+    return (int)row_ptr(im, pixels, y)[2 * (size_t)x + (size_t)comp];
 }
 
 struct TileSched {            // division-free launch geometry, filled by launch_tile_transform
@@ -332,8 +350,9 @@ __device__ __forceinline__ void window_or(uint32_t *win, uint32_t rel, uint32_t 
     if (third) atomicOr(&win[w + 2], __builtin_amdgcn_alignbit(lo, 0u, sh));
 }
 
-// kSrc: what a pixel is (kSrcRgb / kSrcPlane / kSrcPx4 / kSrcPlanar; `pl` is read by kSrcPlanar alone); kZBits / kZCode: the ZRL code of the Huffman table in TransformOutM::code_tab
-// (luma: 11 bits 0x7F9; chroma: 10 bits 0x3FA).  A GRAY picture is <kTaps, kSrcPlane>, a chroma plane <false, kSrcPlane, 10, 0x3FA>.
+// kSrc: what a pixel is (kSrcRgb / kSrcPlane / kSrcPx4 / kSrcPlanar / kSrcPair; `pl` is read by kSrcPlanar alone); kZBits / kZCode: the ZRL code of the Huffman table in TransformOutM::code_tab
+// (luma: 11 bits 0x7F9; chroma: 10 bits 0x3FA).  A GRAY picture is <kTaps, kSrcPlane>, a chroma plane <false, kSrcPlane, 10, 0x3FA>,
+// one component of an interleaved chroma plane <false, kSrcPair, 10, 0x3FA>.
 template <bool kTaps, int kSrc = kSrcRgb, uint32_t kZBits = kZrlBits, uint32_t kZCode = kZrlCode>
 __global__ __launch_bounds__(64 * kWavesT) __attribute__((amdgpu_waves_per_eu(JPEGAMD_TILE_WAVES, JPEGAMD_TILE_WAVES)))
 void k_tile_encode(const ImageDesc im, const TransformOutM out, const TileSched sch, const typename PlanesArg<kSrc>::type pl) {
@@ -499,6 +518,18 @@ void k_tile_encode(const ImageDesc im, const TransformOutM out, const TileSched 
             }
             return;
         }
+        if constexpr (kSrc == kSrcPair) {                       // 16 bytes per lane-row: a block row of byte pairs, both components
+            const uint8_t *pb = im.batch_pixels[g.img] + (size_t)row_low * (size_t)im.row_stride + 16 * (size_t)g.tbx0;
+            uint32_t poff = __umul24((uint32_t)min(b, g.nblk - 1), 16u) + __umul24(im.bottom_up ? 7u - hh : hh, (uint32_t)im.row_stride);
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {
+                const uint32_t *src = reinterpret_cast<const uint32_t *>(pb + poff);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) raw[s].d[i] = src[i];
+                poff += (uint32_t)row_step;
+            }
+            return;
+        }
         if constexpr (kSrc == kSrcPlane) {                      // 8 bytes per lane-row: a block row of one-byte samples
             const uint8_t *pb = im.batch_pixels[g.img] + (size_t)row_low * (size_t)im.row_stride + 8 * (size_t)g.tbx0;
             uint32_t poff = __umul24((uint32_t)min(b, g.nblk - 1), 8u) + __umul24(im.bottom_up ? 7u - hh : hh, (uint32_t)im.row_stride);
@@ -562,7 +593,9 @@ void k_tile_encode(const ImageDesc im, const TransformOutM out, const TileSched 
             } else {
 #pragma unroll
             for (int s = 0; s < 4; ++s) {
-                if constexpr (kSrc == kSrcPlane) bfrag[s] = plane_row8_f16(raw[s].d[0], raw[s].d[1]);
+                // (kSrcPair: the component is the launch image's parity, wave-uniform: the selector stays on the scalar unit)
+                if constexpr (kSrc == kSrcPair) bfrag[s] = pair_row8_f16(raw[s].d, 0x0C020C00u + 0x00010001u * ((im.weights + (uint32_t)tg.img) & 1u));
+                else if constexpr (kSrc == kSrcPlane) bfrag[s] = plane_row8_f16(raw[s].d[0], raw[s].d[1]);
                 else if constexpr (kSrc == kSrcPlanar) bfrag[s] = planar_row8_f16(raw[s], luma_sel);
                 else bfrag[s] = luma_row8_f16(raw[s], lw, luma_sel);
             }
@@ -575,7 +608,10 @@ void k_tile_encode(const ImageDesc im, const TransformOutM out, const TileSched 
                 u32x4 pk;
 #pragma unroll
                 for (int j = 0; j < 8; j += 2) {                // two values per register: Y in each 16-bit half (= Y 2^-24 as binary16, as above)
-                    if constexpr (kSrc == kSrcPlane)
+                    if constexpr (kSrc == kSrcPair)
+                        pk[j >> 1] = (uint32_t)pair_clamped(im, im.batch_pixels[tg.img], (int)((im.weights + (uint32_t)tg.img) & 1u), px0 + j, py0 + 2 * s + h) |
+                                     ((uint32_t)pair_clamped(im, im.batch_pixels[tg.img], (int)((im.weights + (uint32_t)tg.img) & 1u), px0 + j + 1, py0 + 2 * s + h) << 16);
+                    else if constexpr (kSrc == kSrcPlane)
                         pk[j >> 1] = (uint32_t)plane_clamped(im, im.batch_pixels[tg.img], px0 + j, py0 + 2 * s + h) |
                                      ((uint32_t)plane_clamped(im, im.batch_pixels[tg.img], px0 + j + 1, py0 + 2 * s + h) << 16);
                     else if constexpr (kSrc == kSrcPx4)
@@ -1159,7 +1195,7 @@ int launch_tile_transform(const ImageDesc &im, const TransformOutM &out, bool ta
     sch.tpr_magic = magic > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)magic;   // tiles_per_row == 1: the correction step makes up for it
     const dim3 grid(wgs), block(64 * kWavesT);
     const NoPlanes pl;
-    if (src == kTileSrcPx4 || src == kTileSrcPlanar) {
+    if (src == kTileSrcPx4 || src == kTileSrcPlanar || src == kTileSrcChromaPair) {
 #ifdef JPEGAMD_STAMPED_TU
         return (int)hipErrorInvalidValue;                                   // (these sources exist in the plain build alone)
 #else
@@ -1167,7 +1203,9 @@ int launch_tile_transform(const ImageDesc &im, const TransformOutM &out, bool ta
         const auto px4 = k_tile_encode<false, kSrcPx4>;
         const auto planar = k_tile_encode<false, kSrcPlanar>;
         hipEvent_t e0 = ev ? (hipEvent_t)ev[0] : nullptr, e1 = ev ? (hipEvent_t)ev[1] : nullptr;
-        if (src == kTileSrcPx4) hipExtLaunchKernelGGL(px4, grid, block, 0, (hipStream_t)stream, e0, e1, 0, im, out, sch, pl);
+        const auto pair = k_tile_encode<false, kSrcPair, kZrlBitsChroma, kZrlCodeChroma>;
+        if (src == kTileSrcChromaPair) hipExtLaunchKernelGGL(pair, grid, block, 0, (hipStream_t)stream, e0, e1, 0, im, out, sch, pl);
+        else if (src == kTileSrcPx4) hipExtLaunchKernelGGL(px4, grid, block, 0, (hipStream_t)stream, e0, e1, 0, im, out, sch, pl);
         else hipExtLaunchKernelGGL(planar, grid, block, 0, (hipStream_t)stream, e0, e1, 0, im, out, sch, *planes);
         return (int)hipGetLastError();
 #endif

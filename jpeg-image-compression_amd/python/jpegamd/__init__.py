@@ -41,6 +41,15 @@ class PlanarImage(C.Structure):
                 ("bottom_up", C.c_int32), ("quality", C.c_int32)]
 
 
+CHROMA_PLANES, CHROMA_CBCR, CHROMA_CRCB = 0, 1, 2           # JPEGAMD_CHROMA_*
+
+
+class YCbCrImage(C.Structure):
+    """JpegAmdYCbCrImage: the Y plane and the chroma of one picture (device pointers), JFIF full-range samples."""
+    _fields_ = [("y", C.c_void_p), ("cb", C.c_void_p), ("cr", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32),
+                ("y_stride", C.c_int32), ("c_stride", C.c_int32), ("chroma_layout", C.c_int32), ("quality", C.c_int32)]
+
+
 class Stats(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("jfif_bytes", "entropy_bits", "stuffed_bytes", "exact_fallbacks",
                                           "ns_transform", "ns_entropy", "ns_pack", "ns_total")]
@@ -104,6 +113,7 @@ def _load() -> C.CDLL:
         "jpegamd_encode_color_async": (i32, [vp, C.POINTER(Image), i32, vp, u64, vp, vp]),
         "jpegamd_encode_color_batch_async": (i32, [vp, C.POINTER(Image), i32, i32, C.POINTER(C.c_void_p), u64, C.POINTER(C.c_void_p), vp]),
         "jpegamd_encode_planar_batch_async": (i32, [vp, C.POINTER(PlanarImage), i32, i32, C.POINTER(C.c_void_p), u64, C.POINTER(C.c_void_p), vp]),
+        "jpegamd_encode_ycbcr_batch_async": (i32, [vp, C.POINTER(YCbCrImage), i32, i32, C.POINTER(C.c_void_p), u64, C.POINTER(C.c_void_p), vp]),
         "jpegamd_debug_chroma_groups": (i32, [i32, i32, i32, i32, i32, i32, i32, vp]),
         "jpegamd_debug_chroma_quant_table": (i32, [i32, vp]),
         "jpegamd_debug_chroma_mfma_consts": (i32, [i32, vp, vp, vp, vp, vp, vp]),
@@ -117,7 +127,7 @@ def _load() -> C.CDLL:
     }
     for name, (res, args) in sig.items():
         if name in ("jpegamd_encoder_set_pipeline", "jpegamd_gather_streams", "jpegamd_debug_mfma_offsets", "jpegamd_encode_color_batch_async",
-                    "jpegamd_debug_chroma_groups", "jpegamd_encode_planar_batch_async") and os.environ.get("JPEGAMD_LIB") and not hasattr(lib, name):
+                    "jpegamd_debug_chroma_groups", "jpegamd_encode_planar_batch_async", "jpegamd_encode_ycbcr_batch_async") and os.environ.get("JPEGAMD_LIB") and not hasattr(lib, name):
             continue                                              # (A/B tooling: a variant build of an older round)
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = res, args
@@ -133,7 +143,7 @@ EXPORTED = ("jpegamd_encoder_create jpegamd_encoder_destroy jpegamd_max_jfif_byt
             "jpegamd_encode_rows_async jpegamd_export_segments jpegamd_import_segments jpegamd_finalize_async "
             "jpegamd_max_jfif_bytes_color jpegamd_encode_color_async jpegamd_encode_bmp_memory_color jpegamd_debug_chroma_quant_table "
             "jpegamd_debug_chroma_mfma_consts jpegamd_debug_color_profile jpegamd_encode_color_batch_async "
-            "jpegamd_encode_planar_batch_async").split()
+            "jpegamd_encode_planar_batch_async jpegamd_encode_ycbcr_batch_async").split()
 
 
 def quant_table(quality: int = 50):
@@ -457,6 +467,98 @@ def encode_tensor_batch(t, quality: int = 0, subsampling: int = SUBSAMPLE_420, l
     return files
 
 
+def _ycbcr_layout(y, cb, cr, subsampling, order):
+    """The pictures of encode_ycbcr_batch -> (count, height, width, y stride, chroma stride, JPEGAMD_CHROMA_* layout).  Shapes,
+    dtypes and strides only: host tensors pass."""
+    import torch
+    if subsampling not in (SUBSAMPLE_444, SUBSAMPLE_420):
+        raise ValueError("subsampling must be SUBSAMPLE_444 or SUBSAMPLE_420")
+    if order not in ("cbcr", "crcb"):
+        raise ValueError(f'order must be "cbcr" or "crcb", not {order!r}')
+    tensors = [y, cb] + ([cr] if cr is not None else [])
+    if any(not isinstance(x, torch.Tensor) or x.dtype != torch.uint8 for x in tensors):
+        raise ValueError("the encoder needs uint8 tensors")
+    if y.dim() != 3:
+        raise ValueError("y must be [N, H, W]")
+    n, h, w = y.shape
+    if n < 1 or h < 1 or w < 1 or h > 65535 or w > 65535:
+        raise ValueError("the encoder needs at least one picture of 1..65535 pixels each way")
+    cw, ch = ((w + 1) // 2, (h + 1) // 2) if subsampling == SUBSAMPLE_420 else (w, h)
+    if cr is None:
+        if cb.dim() != 4 or tuple(cb.shape) != (n, ch, cw, 2):
+            raise ValueError(f"with cr=None, cb holds the byte pairs: [N, {ch}, {cw}, 2] for this y and subsampling, not {tuple(cb.shape)}")
+        if cb.stride(3) != 1 or cb.stride(2) != 2:
+            raise ValueError("the pairs of a row must be packed (pair stride 2, last stride 1)")
+        layout, c_row = (CHROMA_CBCR if order == "cbcr" else CHROMA_CRCB), 2 * cw
+    else:
+        if order != "cbcr":
+            raise ValueError('order="crcb" names the interleaved layout (cr=None); swap the tensors for planes')
+        for name, p in (("cb", cb), ("cr", cr)):
+            if p.dim() != 3 or tuple(p.shape) != (n, ch, cw):
+                raise ValueError(f"{name} must be [N, {ch}, {cw}] for this y and subsampling, not {tuple(p.shape)}")
+            if p.stride(2) != 1:
+                raise ValueError("samples of a row must be packed (last stride 1)")
+        if ch > 1 and cb.stride(1) != cr.stride(1):
+            raise ValueError("cb and cr must share one row stride")
+        layout, c_row = CHROMA_PLANES, cw
+    if y.stride(2) != 1:
+        raise ValueError("samples of a row must be packed (last stride 1)")
+    y_stride = y.stride(1) if h > 1 else w
+    c_stride = cb.stride(1) if ch > 1 else c_row
+    if y_stride < w or c_stride < c_row:
+        raise ValueError("rows overlap (a row stride is less than a row)")
+    return n, h, w, y_stride, c_stride, layout
+
+
+def encode_ycbcr_batch(y, cb, cr=None, quality: int = 0, subsampling: int = SUBSAMPLE_420, order: str = "cbcr") -> list:
+    """N pictures whose samples already ARE Y, Cb and Cr (JFIF full range; no range or matrix conversion is done) -> N colour JFIF
+    files through jpegamd_encode_ycbcr_batch_async, read where they lie: no RGB detour, no chroma-plane pass.
+    `y` is a uint8 DEVICE tensor [N, H, W]; `cb` and `cr` are [N, ch, cw] with (ch, cw) = (H, W) at SUBSAMPLE_444 and
+    (ceil(H / 2), ceil(W / 2)) at SUBSAMPLE_420 (I420; YV12 by swapping them).  With cr=None, `cb` is [N, ch, cw, 2]: byte pairs
+    Cb Cr (NV12; NV24 at 4:4:4), or Cr Cb with order="crcb" (NV21 / NV42).  Rows and pictures may be strided, samples within a row
+    are packed.  Batches of more than MAX_BATCH pictures go as several calls; the per-device context of encode_tensor is used.
+    An NV12 frame tensor `f` of shape [3 * H // 2, W] (H and W even: H rows of Y, then H / 2 rows of Cb Cr pairs) is
+
+        y    = f[:H].unsqueeze(0)                                   # [1, H, W]
+        cbcr = f[H:].view(H // 2, W // 2, 2).unsqueeze(0)           # [1, H / 2, W / 2, 2]
+        jpegamd.encode_ycbcr_batch(y, cbcr)
+
+    and a stack of frames [N, 3 * H // 2, W] slices the same way: f[:, :H] and f[:, H:].unflatten(2, (W // 2, 2))."""
+    import torch
+    n, h, w, y_stride, c_stride, layout = _ycbcr_layout(y, cb, cr, subsampling, order)
+    tensors = [y, cb] + ([cr] if cr is not None else [])
+    if any(not x.is_cuda or x.device != y.device for x in tensors):
+        raise ValueError("encode_ycbcr_batch needs device tensors on one device")
+    device = y.device
+    dev = device.index if device.index is not None else torch.cuda.current_device()
+    files = []
+    with torch.cuda.device(dev):
+        per = min(n, MAX_BATCH)
+        rows = per * ((h + 7) // 8 * 8)              # a batch needs `per` x the block rows of one picture
+        enc, mw, mh = _tensor_encoders.get(dev, (None, 0, 0))
+        if enc is None or w > mw or rows > mh:
+            mw, mh = max(w, mw), max(rows, mh)
+            if enc is not None:
+                enc.close()
+            enc = Encoder(mw, mh)
+            _tensor_encoders[dev] = (enc, mw, mh)
+        cap = max_jfif_bytes_color(w, h, subsampling)
+        out = torch.empty((per, cap), dtype=torch.uint8, device=device)
+        sizes = torch.zeros(per, dtype=torch.int64, device=device)
+        stream = torch.cuda.current_stream(device).cuda_stream
+        for b0 in range(0, n, MAX_BATCH):
+            k = min(MAX_BATCH, n - b0)
+            outs = [out[i].data_ptr() for i in range(k)]
+            size_ptrs = [sizes.data_ptr() + 8 * i for i in range(k)]
+            imgs = [Encoder.ycbcr_image(y[b0 + i].data_ptr(), cb[b0 + i].data_ptr(), cr[b0 + i].data_ptr() if cr is not None else 0,
+                                        w, h, y_stride, c_stride, layout, quality) for i in range(k)]
+            enc.encode_ycbcr_batch_async(imgs, subsampling, outs, cap, size_ptrs, stream)
+            enc.finish()
+            got = sizes[:k].cpu().tolist()
+            files += [bytes(out[i, :got[i]].cpu().numpy().tobytes()) for i in range(k)]
+    return files
+
+
 class BatchStats(C.Structure):
     _fields_ = [("files_ok", C.c_int32), ("files_failed", C.c_int32), ("bytes_in", C.c_uint64), ("bytes_out", C.c_uint64),
                 ("seconds_total", C.c_double), ("seconds_read", C.c_double), ("seconds_write", C.c_double)]
@@ -537,6 +639,24 @@ class Encoder:
         rc = lib.jpegamd_encode_planar_batch_async(self._h, arr, n, int(subsampling), outs, out_cap, sizes, C.c_void_p(stream))
         if rc:
             raise JpegAmdError(rc, "jpegamd_encode_planar_batch_async")
+
+    @staticmethod
+    def ycbcr_image(y_ptr: int, cb_ptr: int, cr_ptr: int, width: int, height: int, y_stride: int, c_stride: int,
+                    chroma_layout: int = CHROMA_PLANES, quality: int = 0) -> YCbCrImage:
+        """Device pointers of the Y plane and the chroma: two planes (CHROMA_PLANES), or one plane of byte pairs in `cb_ptr`
+        (CHROMA_CBCR / CHROMA_CRCB; `cr_ptr` is then ignored and may be 0)."""
+        return YCbCrImage(y_ptr or None, cb_ptr or None, cr_ptr or None, width, height, y_stride, c_stride, chroma_layout, quality)
+
+    def encode_ycbcr_batch_async(self, imgs, subsampling: int, out_ptrs, out_cap: int, size_ptrs, stream: int = 0):
+        """The colour files of `len(imgs)` YCbCr pictures of one geometry (jpegamd_encode_ycbcr_batch_async); the context as for
+        encode_color_batch_async."""
+        n = len(imgs)
+        arr = (YCbCrImage * n)(*imgs)
+        outs = (C.c_void_p * n)(*[C.c_void_p(p) for p in out_ptrs])
+        sizes = (C.c_void_p * n)(*[C.c_void_p(p) for p in size_ptrs])
+        rc = lib.jpegamd_encode_ycbcr_batch_async(self._h, arr, n, int(subsampling), outs, out_cap, sizes, C.c_void_p(stream))
+        if rc:
+            raise JpegAmdError(rc, "jpegamd_encode_ycbcr_batch_async")
 
     def encode_async(self, img: Image, out_ptr: int, out_cap: int, size_ptr: int, with_container: bool = True,
                      stream: int = 0):

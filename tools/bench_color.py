@@ -7,6 +7,11 @@ ring (every kernel's own begin / end events), with the per-kernel durations.  Pr
 With --batch N the same timed loop goes through jpegamd_encode_color_batch_async: N distinct pictures (seeds 1 .. N) per call,
 reported as the whole call's time (ns_total) per picture, and Gpixels/s.
 
+With --source (and --batch N, default 8) the batch loop reads another source, 4:2:0 only: `i420` the Y, Cb and Cr planes and `nv12` the
+Y plane and one plane of Cb Cr pairs that the colour path itself derives from the same pictures (computed once, outside the timed
+loop), through jpegamd_encode_ycbcr_batch_async -- the files are those of `rgb`, so "bytes" must agree.  Several sources separated
+by commas (--source rgb,i420,nv12) run one after the other in ONE process: one session, one set of pictures.
+
 With --layout {hwc,chw,rgba} (and --batch N, default 8) the pictures are device tensors stored that way -- [N, H, W, 3], [N, 3, H, W],
 [N, H, W, 4] -- and go through the entry that reads them where they lie, 4:2:0 only.  Every call is timed as a whole between two
 events on the stream; --rounds R medians of --steps calls each are reported, with their spread (max - min).  --repack (chw only)
@@ -36,6 +41,7 @@ def main() -> None:
     ap.add_argument("--quality", type=int, default=50)
     ap.add_argument("--kind", type=int, default=0)
     ap.add_argument("--batch", type=int, default=None, help="pictures per call through the colour batch entry (1 .. 32)")
+    ap.add_argument("--source", default="rgb", help="rgb (default), i420, nv12, or several separated by commas: what the batch loop reads")
     ap.add_argument("--layout", choices=("hwc", "chw", "rgba"), default=None, help="device tensors stored this way, read where they lie")
     ap.add_argument("--rounds", type=int, default=5, help="--layout: medians taken (each of --steps calls)")
     ap.add_argument("--repack", action="store_true", help="--layout chw: also time permute + packed encode")
@@ -51,8 +57,11 @@ def main() -> None:
     if a.layout is not None:
         run_layout(a, jpegamd, torch, dev)
         return
-    if a.batch is not None:
-        run_batch(a, jpegamd, torch, dev)
+    sources = a.source.split(",")
+    if any(s not in ("rgb", "i420", "nv12") for s in sources):
+        sys.exit("--source takes rgb, i420, nv12 or a comma-separated list of them")
+    if a.batch is not None or sources != ["rgb"]:
+        run_batch(a, jpegamd, torch, dev, sources)
         return
     bmp = jpegamd.synth_bmp(w, h, 1, a.kind, 0)
     img, off = jpegamd.parse_bmp(bmp)
@@ -82,9 +91,24 @@ def main() -> None:
                           "kernel_ns_sum": sum(med.values())}))
 
 
-def run_batch(a, jpegamd, torch, dev) -> None:
+def ycbcr_420(torch, px, w, h, stride):
+    """The planes the colour path derives from one stored picture (bottom-up B, G, R rows): Y [H, W], Cb and Cr [H / 2, W / 2]."""
+    bgr = px.view(h, stride)[:, :3 * w].reshape(h, w, 3).flip(0)
+    b, g, r = (bgr[:, :, k].to(torch.int32) for k in range(3))
+    y = ((77 * r + 150 * g + 29 * b) >> 8).to(torch.uint8)
+
+    def box(p):
+        return ((p[0::2, 0::2] + p[0::2, 1::2] + p[1::2, 0::2] + p[1::2, 1::2] + 2) >> 2).to(torch.uint8)
+    cb = box((32768 - 43 * r - 85 * g + 128 * b) >> 8)
+    cr = box((32768 + 128 * r - 107 * g - 21 * b) >> 8)
+    return y, cb, cr
+
+
+def run_batch(a, jpegamd, torch, dev, sources=("rgb",)) -> None:
     w = h = a.size
-    n = a.batch
+    n = a.batch or 8
+    if any(s != "rgb" for s in sources) and (w % 2 or h % 2):
+        sys.exit("--source i420 / nv12 needs an even --size")
     pxs, descs = [], []
     for i in range(n):
         bmp = jpegamd.synth_bmp(w, h, 1 + i, a.kind, 0)
@@ -94,23 +118,49 @@ def run_batch(a, jpegamd, torch, dev) -> None:
         del bmp
     enc = jpegamd.Encoder(w, n * h)
     stream = torch.cuda.current_stream().cuda_stream
-    for sub, name in ((jpegamd.SUBSAMPLE_420, "420"), (jpegamd.SUBSAMPLE_444, "444")):
+    frames = None
+    if any(s != "rgb" for s in sources):                         # NV12 frames [N, 3 H / 2, W], and the chroma as two planes
+        frames = torch.empty((n, 3 * h // 2, w), dtype=torch.uint8, device=dev)
+        cbs, crs = (torch.empty((n, h // 2, w // 2), dtype=torch.uint8, device=dev) for _ in range(2))
+        for i in range(n):
+            y, cbs[i], crs[i] = ycbcr_420(torch, pxs[i], w, h, img.row_stride)
+            frames[i, :h] = y
+            frames[i, h:].view(h // 2, w // 2, 2)[:, :, 0] = cbs[i]
+            frames[i, h:].view(h // 2, w // 2, 2)[:, :, 1] = crs[i]
+            del y
+    runs = []
+    for source in sources:
+        if source == "rgb":
+            runs += [(source, sub, name, None) for sub, name in ((jpegamd.SUBSAMPLE_420, "420"), (jpegamd.SUBSAMPLE_444, "444"))]
+        elif source == "i420":
+            runs.append((source, jpegamd.SUBSAMPLE_420, "420",
+                         [jpegamd.Encoder.ycbcr_image(frames[i].data_ptr(), cbs[i].data_ptr(), crs[i].data_ptr(), w, h, w, w // 2,
+                                                      jpegamd.CHROMA_PLANES, a.quality) for i in range(n)]))
+        else:
+            runs.append((source, jpegamd.SUBSAMPLE_420, "420",
+                         [jpegamd.Encoder.ycbcr_image(frames[i].data_ptr(), frames[i, h:].data_ptr(), 0, w, h, w, w,
+                                                      jpegamd.CHROMA_CBCR, a.quality) for i in range(n)]))
+    for source, sub, name, ycc in runs:
         cap = jpegamd.max_jfif_bytes_color(w, h, sub)
         outs = [torch.empty(cap, dtype=torch.uint8, device=dev) for _ in range(n)]
         sizes = torch.zeros(n, dtype=torch.int64, device=dev)
         out_ptrs = [o.data_ptr() for o in outs]
         size_ptrs = [sizes.data_ptr() + 8 * i for i in range(n)]
+        if ycc is None:
+            call = lambda: enc.encode_color_batch_async(descs, sub, out_ptrs, cap, size_ptrs, stream)
+        else:
+            call = lambda: enc.encode_ycbcr_batch_async(ycc, sub, out_ptrs, cap, size_ptrs, stream)
         for _ in range(a.warmup):
-            enc.encode_color_batch_async(descs, sub, out_ptrs, cap, size_ptrs, stream)
+            call()
         enc.finish()
         enc.set_profiling(a.steps)
         for _ in range(a.steps):
-            enc.encode_color_batch_async(descs, sub, out_ptrs, cap, size_ptrs, stream)
+            call()
         st = enc.finish()
         totals = [enc.profile(i).ns_total for i in range(a.steps)]
         enc.set_profiling(0)
         t = statistics.median(totals)
-        print(json.dumps({"subsampling": name, "width": w, "height": h, "batch": n, "quality": a.quality, "kind": a.kind,
+        print(json.dumps({"source": source, "subsampling": name, "width": w, "height": h, "batch": n, "quality": a.quality, "kind": a.kind,
                           "steps": a.steps, "bytes": sizes.cpu().tolist(), "entropy_bits": st.entropy_bits,
                           "ns_total_median": int(t), "us_per_picture": round(t / n / 1000, 1),
                           "gpixels_per_s": round(n * w * h / t, 2)}))
