@@ -147,7 +147,8 @@ int32_t jpegamd_encode_batch_async(JpegAmdEncoder *enc, const JpegAmdImage *imgs
  *   Y  = (77 R + 150 G + 29 B) >> 8              (the grayscale path's luma; its scan is byte for byte the grayscale file's)
  *   Cb = (32768 - 43 R - 85 G + 128 B) >> 8      Cr = (32768 + 128 R - 107 G - 21 B) >> 8
  *   4:2:0: chroma planes of ceil(W/2) x ceil(H/2), sample = (a + b + c + d + 2) >> 2 over 2 x 2 pixels (last column / row
- *   replicated); 4:4:4: W x H.  Chroma: T.81 Annex K tables K.2 (quantisation, scaled for `quality` like the luma table),
+ *   replicated); 4:2:2: ceil(W/2) x H, sample = (a + b + 1) >> 1 over the two pixels 2x, 2x + 1 of one row (last column replicated,
+ *   no vertical filter; SOF0 gives component 1 the sampling factors 2 x 1); 4:4:4: W x H.  Chroma: T.81 Annex K tables K.2 (quantisation, scaled for `quality` like the luma table),
  *   K.4 / K.6 (Huffman).  No restart markers.
  * jpegamd_encode_color_async always writes the whole file (prefix, three scans, EOI) into out_dev, stream-ordered, with no host
  * synchronisation inside the call.  A GRAY image or another subsampling value: JPEGAMD_ERR_ARG.  An RGBA / BGRA image runs as a
@@ -159,6 +160,9 @@ int32_t jpegamd_encode_batch_async(JpegAmdEncoder *enc, const JpegAmdImage *imgs
  * nothing for it. */
 #define JPEGAMD_SUBSAMPLE_444 1
 #define JPEGAMD_SUBSAMPLE_420 2
+/* (3 is skipped, here and among the chroma layouts below: every entry has always answered 3 with JPEGAMD_ERR_ARG, callers and the
+ *  test suite rely on it as a known-bad value, and a new meaning for it would change what existing code gets.) */
+#define JPEGAMD_SUBSAMPLE_422 4
 /* Upper bound on the colour file's bytes (every block at the 1723-bit chroma worst case, every byte stuffed); 0 for bad args. */
 uint64_t jpegamd_max_jfif_bytes_color(int32_t width, int32_t height, int32_t subsampling);
 int32_t jpegamd_encode_color_async(JpegAmdEncoder *enc, const JpegAmdImage *img, int32_t subsampling, void *out_dev,
@@ -190,7 +194,7 @@ typedef struct JpegAmdPlanarImage {
 } JpegAmdPlanarImage;
 /* The files of `count` (1 .. JPEGAMD_MAX_BATCH) planar pictures of ONE geometry (width, height, row_stride, bottom_up, quality), read
  * where they lie -- no repacking pass.  subsampling 0: grayscale files with container, as jpegamd_encode_batch_async writes them;
- * JPEGAMD_SUBSAMPLE_444 / _420: colour files, as jpegamd_encode_color_batch_async writes them.  Each file is byte for byte the one
+ * JPEGAMD_SUBSAMPLE_444 / _420 / _422: colour files, as jpegamd_encode_color_batch_async writes them.  Each file is byte for byte the one
  * those entries produce for the same R, G, B values stored as packed JPEGAMD_ORDER_RGB.  Context sizing, capacity, status and
  * statistics are those of the entry it stands for.  out_sizes_dev[i] is a DEVICE uint64_t.  Bad arguments -- a null array or element,
  * a null plane, count out of range, row_stride < width, another subsampling value, pictures of different geometry -- are refused
@@ -202,14 +206,21 @@ int32_t jpegamd_encode_planar_batch_async(JpegAmdEncoder *enc, const JpegAmdPlan
  * The planes are coded as they are given: the samples are taken as JFIF full-range values (Y 0..255, Cb / Cr centred on 128), and
  * NO range or matrix conversion, no subsampling and no filtering is done -- limited-range (16..235) or BT.709 material must be
  * converted by the caller.  The Y plane is width x height; the chroma planes are cw x ch: width x height at JPEGAMD_SUBSAMPLE_444,
- * ceil(width / 2) x ceil(height / 2) at JPEGAMD_SUBSAMPLE_420 (odd sizes are allowed). */
+ * ceil(width / 2) x ceil(height / 2) at JPEGAMD_SUBSAMPLE_420, ceil(width / 2) x height at JPEGAMD_SUBSAMPLE_422 (I422; NV16 / NV61
+ * as byte pairs).  Odd sizes are allowed.
+ * 4:2:2 also comes packed, as capture hardware delivers it: ONE plane of 4-byte groups, two pixels each, that holds all three
+ * components (YUY2 / UYVY).  Then y points at the packed plane, y_stride is its row stride (>= 4 * ceil(width / 2)), cb, cr and
+ * c_stride are not looked at (cb and cr may be null), and JPEGAMD_SUBSAMPLE_422 is the only subsampling accepted.  Odd widths are
+ * allowed: the second Y byte of a row's last group is never read. */
 #define JPEGAMD_CHROMA_PLANES 0   /* cb and cr: two planes of one byte per sample (I420; YV12 by swapping the pointers; planar 4:4:4) */
 #define JPEGAMD_CHROMA_CBCR   1   /* cb: ONE plane of byte pairs Cb0 Cr0 Cb1 Cr1 ... (NV12; NV24 at 4:4:4); cr is ignored and may be null */
 #define JPEGAMD_CHROMA_CRCB   2   /* the same with Cr first (NV21 / NV42) */
+#define JPEGAMD_CHROMA_YUYV   4   /* y: ONE plane of 4-byte groups Y0 Cb Y1 Cr (YUY2); cb, cr, c_stride ignored (3: see JPEGAMD_SUBSAMPLE_422) */
+#define JPEGAMD_CHROMA_UYVY   5   /* the same as Cb Y0 Cr Y1 */
 typedef struct JpegAmdYCbCrImage {
     const void *y, *cb, *cr;      /* DEVICE pointers, top row first */
     int32_t width, height;        /* of the Y plane, 1..65535 */
-    int32_t y_stride, c_stride;   /* bytes between rows; y_stride >= width; c_stride >= cw (PLANES) or >= 2*cw (CBCR / CRCB) */
+    int32_t y_stride, c_stride;   /* bytes between rows; y_stride >= width; c_stride >= cw (PLANES) or >= 2*cw (CBCR / CRCB); YUYV / UYVY: y_stride >= 4*cw */
     int32_t chroma_layout;        /* JPEGAMD_CHROMA_* */
     int32_t quality;
 } JpegAmdYCbCrImage;
@@ -222,8 +233,8 @@ typedef struct JpegAmdYCbCrImage {
  * boundaries with strides that are multiples of 4 below 2^24 take the fast loader).  Context sizing, capacity behaviour (size 0 and
  * JPEGAMD_ERR_HUFF_CAPACITY at jpegamd_encoder_finish), status, statistics and profiling are those of
  * jpegamd_encode_color_batch_async.  out_sizes_dev[i] is a DEVICE uint64_t.  Bad arguments -- a null array or element, a null y or
- * cb, a null cr with JPEGAMD_CHROMA_PLANES, an unknown layout or subsampling, count out of range, a stride too short, pictures of
- * different geometry -- are refused with JPEGAMD_ERR_ARG before the context is read. */
+ * cb, a null cr with JPEGAMD_CHROMA_PLANES, an unknown layout or subsampling, a packed layout with another subsampling than 4:2:2,
+ * count out of range, a stride too short, pictures of different geometry or layout -- are refused with JPEGAMD_ERR_ARG before the context is read. */
 int32_t jpegamd_encode_ycbcr_batch_async(JpegAmdEncoder *enc, const JpegAmdYCbCrImage *imgs, int32_t count, int32_t subsampling,
                                          void *const *outs_dev, uint64_t out_capacity, void *const *out_sizes_dev, void *stream);
 
@@ -386,7 +397,7 @@ bool saveJPEGGrayscale(const char *filename, const BMPImage *img);
  * Returns the JFIF size, or a negative JPEGAMD_ERR_* code. */
 int64_t jpegamd_encode_bmp_memory(const uint8_t *bmp, uint64_t bmp_len, int32_t quality,
                                   uint8_t *out, uint64_t out_cap);
-/* ... the colour file (jpegamd_encode_color_async) of the same BMP; subsampling JPEGAMD_SUBSAMPLE_444 or _420. */
+/* ... the colour file (jpegamd_encode_color_async) of the same BMP; subsampling JPEGAMD_SUBSAMPLE_444, _420 or _422. */
 int64_t jpegamd_encode_bmp_memory_color(const uint8_t *bmp, uint64_t bmp_len, int32_t quality, int32_t subsampling,
                                         uint8_t *out, uint64_t out_cap);
 

@@ -187,17 +187,21 @@ extern "C" int32_t jpegamd_debug_chroma_mfma_consts(int32_t quality, float *qmul
     return JPEGAMD_OK;
 }
 
+// The colour subsamplings: 4:4:4, 4:2:0 (chroma halved both ways) and 4:2:2 (halved along the row alone).
+static bool sub_valid(int sub) { return sub == JPEGAMD_SUBSAMPLE_444 || sub == JPEGAMD_SUBSAMPLE_420 || sub == JPEGAMD_SUBSAMPLE_422; }
+static int chroma_mode(int sub) { return sub == JPEGAMD_SUBSAMPLE_420 ? kChromaMode420 : (sub == JPEGAMD_SUBSAMPLE_422 ? kChromaMode422 : kChromaMode444); }
 static void chroma_dims(int w, int h, int sub, int *cw, int *ch) {
-    *cw = sub == JPEGAMD_SUBSAMPLE_420 ? (w + 1) / 2 : w;
+    *cw = sub == JPEGAMD_SUBSAMPLE_444 ? w : (w + 1) / 2;
     *ch = sub == JPEGAMD_SUBSAMPLE_420 ? (h + 1) / 2 : h;
 }
+static bool is_packed422(int layout) { return layout == JPEGAMD_CHROMA_YUYV || layout == JPEGAMD_CHROMA_UYVY; }
 
 // One scan of nb blocks at the chroma worst case, every byte stuffed, its flush byte.
 static uint64_t scan_bound(uint64_t nb) { return 2 * ((nb * kMaxBlockBitsColor + 7) / 8 + 1); }
 static uint64_t blocks_of(int w, int h) { return (uint64_t)((w + 7) / 8) * (uint64_t)((h + 7) / 8); }
 
 extern "C" uint64_t jpegamd_max_jfif_bytes_color(int32_t width, int32_t height, int32_t subsampling) {
-    if (width <= 0 || height <= 0 || (subsampling != JPEGAMD_SUBSAMPLE_444 && subsampling != JPEGAMD_SUBSAMPLE_420)) return 0;
+    if (width <= 0 || height <= 0 || !sub_valid(subsampling)) return 0;
     int cw, ch;
     chroma_dims(width, height, subsampling, &cw, &ch);
     return kColorPrefixMax + 2 * kSosBytes + 2 + scan_bound(blocks_of(width, height)) + 2 * scan_bound(blocks_of(cw, ch)) + 16;
@@ -477,7 +481,7 @@ static int launch_transform(JpegAmdEncoder *e, const ImageDesc &im, bool taps, i
                             void *stream, hipEvent_t *ev = nullptr /*2: begin/end*/, int src = kTileSrcRgb, const PlaneSet *ps = nullptr) {
     TransformOutM to;
     std::memset(&to, 0, sizeof(to));
-    const bool chroma = src == kTileSrcChroma || src == kTileSrcChromaPair;
+    const bool chroma = src == kTileSrcChroma || src == kTileSrcChromaPair || src == kTileSrcChromaQuad;
     to.tables = chroma ? e->color.tables_dev : e->tables_dev; to.stamps = e->stamps_dev;
     to.tap_y = ty; to.tap_zz = tzz; to.tap_mask = tmask;
     to.tile_head = e->tile_head; to.tile_over = e->tile_over; to.code_tab = chroma ? e->color.code_tab : e->code_tab;
@@ -514,7 +518,7 @@ static int launch_transform_and_entropy(JpegAmdEncoder *e, const ImageDesc &im, 
     MergeArgs ea;
     std::memset(&ea, 0, sizeof(ea));
     ea.tile_head = e->tile_head; ea.tile_over = e->tile_over;
-    ea.huff = (src == kTileSrcChroma || src == kTileSrcChromaPair) ? e->color.huff : e->huff; ea.num_segs = im.num_segs; ea.segs_per_row = im.segs_per_row; ea.tiles_per_row = im.tiles_per_row;
+    ea.huff = (src == kTileSrcChroma || src == kTileSrcChromaPair || src == kTileSrcChromaQuad) ? e->color.huff : e->huff; ea.num_segs = im.num_segs; ea.segs_per_row = im.segs_per_row; ea.tiles_per_row = im.tiles_per_row;
     ea.seg_tiles = im.seg_tiles;
     ea.seg_begin = im.seg_begin; ea.seg_end = im.seg_end;
     ea.tiles_per_image = im.batch > 1 ? im.num_tiles : 0;
@@ -880,7 +884,7 @@ static int32_t prepare_color_constants(JpegAmdEncoder *e, const JpegAmdImage *im
         uint8_t luma[64], chroma[64], hdr[kColorPrefixMax];
         quant_table_for_quality(q, luma);
         chroma_quant_table_for_quality(q, chroma);
-        c.hdr_len = (int)build_jfif_prefix_color(img->width, img->height, luma, chroma, sub == JPEGAMD_SUBSAMPLE_420, hdr);
+        c.hdr_len = (int)build_jfif_prefix_color(img->width, img->height, luma, chroma, chroma_mode(sub), hdr);
         if (e->pending) HIP_TRY(hipStreamSynchronize(e->last_stream));
         HIP_TRY(hipMemcpy(c.hdr, hdr, (size_t)c.hdr_len, hipMemcpyHostToDevice));
         c.hdr_w = img->width; c.hdr_h = img->height; c.hdr_q = q; c.hdr_sub = sub;
@@ -906,7 +910,7 @@ static int run_scan(JpegAmdEncoder *e, const ImageDesc &im, int src, void *out, 
 extern "C" int32_t jpegamd_encode_color_async(JpegAmdEncoder *e, const JpegAmdImage *img, int32_t subsampling, void *out_dev,
                                               uint64_t out_capacity, uint64_t *out_size_dev, void *stream_) {
     if (!e || !img || !out_dev || !out_size_dev) return JPEGAMD_ERR_ARG;
-    if (subsampling != JPEGAMD_SUBSAMPLE_444 && subsampling != JPEGAMD_SUBSAMPLE_420) return JPEGAMD_ERR_ARG;
+    if (!sub_valid(subsampling)) return JPEGAMD_ERR_ARG;
     if (is_px4(img->channel_order)) {             // a batch of one through the batch kernels (k_chroma_planes reads 3-byte pixels only)
         void *const outs[1] = {out_dev};
         uint64_t *const sizes[1] = {out_size_dev};
@@ -948,7 +952,7 @@ extern "C" int32_t jpegamd_encode_color_async(JpegAmdEncoder *e, const JpegAmdIm
     pa.pixels = (const uint8_t *)img->pixels;
     pa.width = img->width; pa.height = img->height; pa.row_stride = img->row_stride; pa.bottom_up = img->bottom_up ? 1 : 0;
     pa.rgb = img->channel_order == JPEGAMD_ORDER_RGB ? 1 : 0;
-    pa.sub420 = subsampling == JPEGAMD_SUBSAMPLE_420 ? 1 : 0;
+    pa.mode = chroma_mode(subsampling);
     pa.cw = cw; pa.ch = ch; pa.pitch = pitch;
     pa.cb = c.planes; pa.cr = c.planes + (size_t)pitch * (size_t)ch;
     if (launch_chroma_planes(pa, stream, cev ? (void *const *)cev : nullptr)) return JPEGAMD_ERR_HIP;
@@ -1038,7 +1042,7 @@ static bool chroma_plan(const CtxLimits &l, int pipeline, int cw, int ch, int pl
 extern "C" int32_t jpegamd_debug_chroma_groups(int32_t max_width, int32_t max_height, int32_t pipeline, int32_t width, int32_t height,
                                                int32_t count, int32_t subsampling, int32_t *out) {
     if (!out || max_width <= 0 || max_height <= 0 || width <= 0 || height <= 0 || count < 1 || count > kMaxBatch) return JPEGAMD_ERR_ARG;
-    if (subsampling != JPEGAMD_SUBSAMPLE_444 && subsampling != JPEGAMD_SUBSAMPLE_420) return JPEGAMD_ERR_ARG;
+    if (!sub_valid(subsampling)) return JPEGAMD_ERR_ARG;
     int cw, ch;
     chroma_dims(width, height, subsampling, &cw, &ch);
     ChromaPlan p;
@@ -1072,7 +1076,8 @@ static int32_t color_batch_alloc(JpegAmdEncoder *e, size_t planes, size_t scans)
     return JPEGAMD_OK;
 }
 
-// The caller's own chroma (jpegamd_encode_ycbcr_batch_async): cb[i] / cr[i] the planes of picture i (a pair layout: cb[i] alone).
+// The caller's own chroma (jpegamd_encode_ycbcr_batch_async): cb[i] / cr[i] the planes of picture i (a pair layout: cb[i] alone; a
+// packed 4:2:2 layout: cb[i] is the packed plane -- the picture's y -- and c_stride its row stride).
 struct YccSource {
     int32_t layout, c_stride;
     const uint8_t *cb[kMaxBatch], *cr[kMaxBatch];
@@ -1152,7 +1157,7 @@ static int32_t color_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, const Plan
         pa.batch = count;
         pa.width = g0.width; pa.height = g0.height; pa.row_stride = g0.row_stride; pa.bottom_up = g0.bottom_up ? 1 : 0;
         pa.rgb = (g0.channel_order == JPEGAMD_ORDER_BGR || g0.channel_order == JPEGAMD_ORDER_BGRA) ? 0 : 1;
-        pa.sub420 = subsampling == JPEGAMD_SUBSAMPLE_420 ? 1 : 0;
+        pa.mode = chroma_mode(subsampling);
         pa.cw = cw; pa.ch = ch; pa.pitch = pitch;
         pa.plane_bytes = plane_bytes; pa.planes = c.bplanes;
         hipEvent_t ev_planes[2] = {cev ? cev[0] : nullptr, nullptr};
@@ -1165,12 +1170,16 @@ static int32_t color_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, const Plan
         for (int i = 0; i < count; ++i) sizes[i] = y_size + i;
         const ScanTarget ty = {c.hdr, c.hdr_len, 0, &lstats[0], false};
         PictureStatsArgs ps = {e->tile_head, e->huff, iy.num_tiles, count, 0, 0, pic};
+        // a packed 4:2:2 plane: Y is one byte of every pair of the row -- byte 0 (Y Cb Y Cr) or byte 1 (Cb Y Cr Y) -- for EVERY picture
+        const bool packed = ycc && is_packed422(ycc->layout);
+        const int ysrc = packed ? kTileSrcLumaPair : src_of(&g0);
+        if (packed) iy.weights = ycc->layout == JPEGAMD_CHROMA_UYVY ? 1u : 0u;
         if (stitch_y) {
-            if (launch_transform(e, iy, false, nullptr, nullptr, nullptr, stream, ev_y, src_of(&g0), &px)) return JPEGAMD_ERR_HIP;
+            if (launch_transform(e, iy, false, nullptr, nullptr, nullptr, stream, ev_y, ysrc, &px)) return JPEGAMD_ERR_HIP;
             if (launch_picture_stats(ps, stream)) return JPEGAMD_ERR_HIP;
             if (run_stitch(e, iy, outs_dev, out_capacity, sizes, 1, stream, nullptr, &ty)) return JPEGAMD_ERR_HIP;
         } else {
-            if (launch_transform_and_entropy(e, iy, false, nullptr, nullptr, nullptr, stream, ev_y, src_of(&g0), &px)) return JPEGAMD_ERR_HIP;
+            if (launch_transform_and_entropy(e, iy, false, nullptr, nullptr, nullptr, stream, ev_y, ysrc, &px)) return JPEGAMD_ERR_HIP;
             if (launch_picture_stats(ps, stream)) return JPEGAMD_ERR_HIP;
             if (run_finalize_batch(e, iy, outs_dev, out_capacity, sizes, 1, stream, nullptr, &ty)) return JPEGAMD_ERR_HIP;
         }
@@ -1183,8 +1192,8 @@ static int32_t color_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, const Plan
     bool ycc_aligned = true;
     if (ycc) {
         pimg.pixels = ycc->cb[0]; pimg.row_stride = ycc->c_stride;
-        const bool pair = ycc->layout != JPEGAMD_CHROMA_PLANES;
-        if (pair) csrc = kTileSrcChromaPair;
+        const bool pair = ycc->layout != JPEGAMD_CHROMA_PLANES;      // (or a packed plane: one pointer per picture as well)
+        if (pair) csrc = is_packed422(ycc->layout) ? kTileSrcChromaQuad : kTileSrcChromaPair;
         uintptr_t bits = 0;
         for (int i = 0; i < count; ++i) bits |= (uintptr_t)ycc->cb[i] | (pair ? 0 : (uintptr_t)ycc->cr[i]);
         ycc_aligned = (bits & 3u) == 0;
@@ -1199,7 +1208,7 @@ static int32_t color_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, const Plan
         for (int i = 0; i < n; ++i) {
             const int j = first + i;                                   // the plane's index in the whole call: picture j / 2, Cb (even) or Cr (odd)
             if (!ycc) ic.batch_pixels[i] = c.bplanes + (size_t)j * plane_bytes;
-            else if (csrc == kTileSrcChromaPair) ic.batch_pixels[i] = ycc->cb[j / 2];
+            else if (csrc != kTileSrcChroma) ic.batch_pixels[i] = ycc->cb[j / 2];
             else ic.batch_pixels[i] = (j & 1) ? ycc->cr[j / 2] : ycc->cb[j / 2];
             outs[i] = c.bscans + (size_t)(first + i) * slot_bytes;
             sizes[i] = c_size + first + i;
@@ -1212,6 +1221,9 @@ static int32_t color_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, const Plan
         // a pair plane: launch image i reads byte (weights + i) & 1 of each pair -- the parity of its plane in the WHOLE call (a group
         // may be odd: a launch then starts on a Cr plane), flipped when Cr is stored first
         if (csrc == kTileSrcChromaPair) ic.weights = (uint32_t)((first & 1) ^ (ycc->layout == JPEGAMD_CHROMA_CRCB ? 1 : 0));
+        // a packed plane: launch image i reads byte ((weights >> 8) & 1) + 2 ((weights + i) & 1) of each 4-byte group -- Cb in front of Cr,
+        // at bytes 1 and 3 (Y Cb Y Cr) or 0 and 2 (Cb Y Cr Y); bit 0 is the same parity rule
+        if (csrc == kTileSrcChromaQuad) ic.weights = (uint32_t)(first & 1) | (ycc->layout == JPEGAMD_CHROMA_YUYV ? 0x100u : 0u);
         const ScanTarget tc = {c.hdr, 0, 0, &lstats[1 + l], true};
         PictureStatsArgs ps = {e->tile_head, c.huff, ic.num_tiles, n, 1, first, pic};
         if (plan.stitch) {
@@ -1250,7 +1262,7 @@ extern "C" int32_t jpegamd_encode_color_batch_async(JpegAmdEncoder *e, const Jpe
                                                     void *stream_) {
     // the arguments first: nothing of the context is read before they are known to be good
     if (!e || !imgs || !outs_dev || !out_sizes_dev || count < 1 || count > kMaxBatch) return JPEGAMD_ERR_ARG;
-    if (subsampling != JPEGAMD_SUBSAMPLE_444 && subsampling != JPEGAMD_SUBSAMPLE_420) return JPEGAMD_ERR_ARG;
+    if (!sub_valid(subsampling)) return JPEGAMD_ERR_ARG;
     const JpegAmdImage &g0 = imgs[0];
     if (g0.channel_order != JPEGAMD_ORDER_BGR && g0.channel_order != JPEGAMD_ORDER_RGB && !is_px4(g0.channel_order)) return JPEGAMD_ERR_ARG;
     if (g0.width <= 0 || g0.row_stride < bytes_per_pixel(g0.channel_order) * (int64_t)g0.width) return JPEGAMD_ERR_ARG;
@@ -1272,7 +1284,7 @@ extern "C" int32_t jpegamd_encode_planar_batch_async(JpegAmdEncoder *e, const Jp
                                                      void *stream_) {
     // the arguments first: nothing of the context is read before they are known to be good
     if (!e || !imgs || !outs_dev || !out_sizes_dev || count < 1 || count > kMaxBatch) return JPEGAMD_ERR_ARG;
-    if (subsampling != 0 && subsampling != JPEGAMD_SUBSAMPLE_444 && subsampling != JPEGAMD_SUBSAMPLE_420) return JPEGAMD_ERR_ARG;
+    if (subsampling != 0 && !sub_valid(subsampling)) return JPEGAMD_ERR_ARG;
     const JpegAmdPlanarImage &p0 = imgs[0];
     if (p0.width <= 0 || p0.height <= 0 || p0.width > 65535 || p0.height > 65535 || p0.row_stride < p0.width) return JPEGAMD_ERR_ARG;
     PlaneSet ps = {};
@@ -1300,28 +1312,30 @@ extern "C" int32_t jpegamd_encode_ycbcr_batch_async(JpegAmdEncoder *e, const Jpe
                                                     void *stream_) {
     // the arguments first: nothing of the context is read before they are known to be good
     if (!e || !imgs || !outs_dev || !out_sizes_dev || count < 1 || count > kMaxBatch) return JPEGAMD_ERR_ARG;
-    if (subsampling != JPEGAMD_SUBSAMPLE_444 && subsampling != JPEGAMD_SUBSAMPLE_420) return JPEGAMD_ERR_ARG;
+    if (!sub_valid(subsampling)) return JPEGAMD_ERR_ARG;
     const JpegAmdYCbCrImage &p0 = imgs[0];
-    if (p0.chroma_layout != JPEGAMD_CHROMA_PLANES && p0.chroma_layout != JPEGAMD_CHROMA_CBCR && p0.chroma_layout != JPEGAMD_CHROMA_CRCB)
+    const bool packed = is_packed422(p0.chroma_layout);               // y is the packed plane; cb, cr and c_stride are not looked at
+    if (p0.chroma_layout != JPEGAMD_CHROMA_PLANES && p0.chroma_layout != JPEGAMD_CHROMA_CBCR && p0.chroma_layout != JPEGAMD_CHROMA_CRCB && !packed)
         return JPEGAMD_ERR_ARG;
+    if (packed && subsampling != JPEGAMD_SUBSAMPLE_422) return JPEGAMD_ERR_ARG;
     if (p0.width <= 0 || p0.height <= 0 || p0.width > 65535 || p0.height > 65535) return JPEGAMD_ERR_ARG;
-    const bool pair = p0.chroma_layout != JPEGAMD_CHROMA_PLANES;
+    const bool pair = p0.chroma_layout != JPEGAMD_CHROMA_PLANES && !packed;
     int cw, ch;
     chroma_dims(p0.width, p0.height, subsampling, &cw, &ch);
-    if (p0.y_stride < p0.width || p0.c_stride < (pair ? 2 * cw : cw)) return JPEGAMD_ERR_ARG;
+    if (packed ? p0.y_stride < 4 * cw : (p0.y_stride < p0.width || p0.c_stride < (pair ? 2 * cw : cw))) return JPEGAMD_ERR_ARG;
     PlaneSet ps = {};
     YccSource ycc = {};
-    ycc.layout = p0.chroma_layout; ycc.c_stride = p0.c_stride;
+    ycc.layout = p0.chroma_layout; ycc.c_stride = packed ? p0.y_stride : p0.c_stride;
     uint64_t *sizes[kMaxBatch];
     for (int i = 0; i < count; ++i) {
         const JpegAmdYCbCrImage &g = imgs[i];
-        if (!outs_dev[i] || !out_sizes_dev[i] || !g.y || !g.cb || (!pair && !g.cr)) return JPEGAMD_ERR_ARG;
-        if (g.width != p0.width || g.height != p0.height || g.y_stride != p0.y_stride || g.c_stride != p0.c_stride ||
+        if (!outs_dev[i] || !out_sizes_dev[i] || !g.y || (!packed && (!g.cb || (!pair && !g.cr)))) return JPEGAMD_ERR_ARG;
+        if (g.width != p0.width || g.height != p0.height || g.y_stride != p0.y_stride || (!packed && g.c_stride != p0.c_stride) ||
             g.chroma_layout != p0.chroma_layout || g.quality != p0.quality)
             return JPEGAMD_ERR_ARG;
         ps.p[0][i] = (const uint8_t *)g.y;
-        ycc.cb[i] = (const uint8_t *)g.cb;
-        ycc.cr[i] = pair ? nullptr : (const uint8_t *)g.cr;
+        ycc.cb[i] = (const uint8_t *)(packed ? g.y : g.cb);
+        ycc.cr[i] = (pair || packed) ? nullptr : (const uint8_t *)g.cr;
         sizes[i] = (uint64_t *)out_sizes_dev[i];
     }
     JpegAmdImage g0;

@@ -22,17 +22,19 @@ __device__ __forceinline__ void cbcr(int r, int g, int b, int &cb, int &cr) {
 
 constexpr int kPlaneOut = 4;              // chroma samples per thread: one 4-byte store per plane (the pitch is a multiple of 4)
 
-// kSub: 2 (4:2:0, 2 x 2 pixels per sample) or 1 (4:4:4).  Thread (gx, cy) makes samples 4 gx .. 4 gx + 3 of plane row cy.
-template <int kSub>
+// kSx x kSy pixels per sample: 2 x 2 (4:2:0), 2 x 1 (4:2:2: one source row per plane row) or 1 x 1 (4:4:4).  Thread (gx, cy) makes
+// samples 4 gx .. 4 gx + 3 of plane row cy.
+template <int kSx, int kSy>
 __global__ __launch_bounds__(256) void k_chroma_planes(const ChromaPlanesArgs a) {
-    constexpr int kPix = kPlaneOut * kSub;                                   // source pixels per row and thread
+    static_assert((kSx == 1 || kSx == 2) && (kSy == 1 || kSy == 2) && kSy <= kSx, "4:4:4, 4:2:2 or 4:2:0");
+    constexpr int kPix = kPlaneOut * kSx;                                    // source pixels per row and thread
     const int gx = (int)(blockIdx.x * blockDim.x + threadIdx.x), cy = (int)blockIdx.y;
     const int x0 = gx * kPix;
     if (kPlaneOut * gx >= a.cw) return;                                      // (then x0 < width as well)
-    int cb[kSub][kPix], cr[kSub][kPix];
+    int cb[kSy][kPix], cr[kSy][kPix];
 #pragma unroll
-    for (int r = 0; r < kSub; ++r) {
-        const int y = min(cy * kSub + r, a.height - 1);                      // the last row replicated (odd heights)
+    for (int r = 0; r < kSy; ++r) {
+        const int y = min(cy * kSy + r, a.height - 1);                      // the last row replicated (odd heights)
         const int stored = a.bottom_up ? a.height - 1 - y : y;
         const uint8_t *row = a.pixels + (size_t)stored * (size_t)a.row_stride;
         uint8_t px[3 * kPix];
@@ -61,11 +63,16 @@ __global__ __launch_bounds__(256) void k_chroma_planes(const ChromaPlanesArgs a)
 #pragma unroll
     for (int k = 0; k < kPlaneOut; ++k) {
         int vb, vr;
-        if (kSub == 2) {
-            // the pair's right pixel is the replicated last column when 2 x + 1 == width; (a + b + c + d + 2) >> 2
+        if (kSx == 2) {
+            // the pair's right pixel is the replicated last column when 2 x + 1 == width; (a + b + c + d + 2) >> 2, or (a + b + 1) >> 1
             const int j0 = 2 * k, j1 = x0 + 2 * k + 1 < a.width ? 2 * k + 1 : 2 * k;
-            vb = (cb[0][j0] + cb[0][j1] + cb[kSub - 1][j0] + cb[kSub - 1][j1] + 2) >> 2;
-            vr = (cr[0][j0] + cr[0][j1] + cr[kSub - 1][j0] + cr[kSub - 1][j1] + 2) >> 2;
+            if (kSy == 2) {
+                vb = (cb[0][j0] + cb[0][j1] + cb[kSy - 1][j0] + cb[kSy - 1][j1] + 2) >> 2;
+                vr = (cr[0][j0] + cr[0][j1] + cr[kSy - 1][j0] + cr[kSy - 1][j1] + 2) >> 2;
+            } else {
+                vb = (cb[0][j0] + cb[0][j1] + 1) >> 1;
+                vr = (cr[0][j0] + cr[0][j1] + 1) >> 1;
+            }
         } else {
             vb = cb[0][k]; vr = cr[0][k];
         }
@@ -81,13 +88,10 @@ int launch_chroma_planes(const ChromaPlanesArgs &a, void *stream, void *const *e
     if (a.cw <= 0 || a.ch <= 0 || a.pitch % 4 != 0 || a.pitch < (a.cw + 3) / 4 * 4) return (int)hipErrorInvalidValue;
     const int threads_x = (a.cw + kPlaneOut - 1) / kPlaneOut;
     const dim3 grid((unsigned)((threads_x + 255) / 256), (unsigned)a.ch), block(256);
-    if (a.sub420) {
-        if (ev) hipExtLaunchKernelGGL(k_chroma_planes<2>, grid, block, 0, (hipStream_t)stream, (hipEvent_t)ev[0], (hipEvent_t)ev[1], 0, a);
-        else hipLaunchKernelGGL(k_chroma_planes<2>, grid, block, 0, (hipStream_t)stream, a);
-    } else {
-        if (ev) hipExtLaunchKernelGGL(k_chroma_planes<1>, grid, block, 0, (hipStream_t)stream, (hipEvent_t)ev[0], (hipEvent_t)ev[1], 0, a);
-        else hipLaunchKernelGGL(k_chroma_planes<1>, grid, block, 0, (hipStream_t)stream, a);
-    }
+    if (a.mode != kChromaMode444 && a.mode != kChromaMode420 && a.mode != kChromaMode422) return (int)hipErrorInvalidValue;
+    const auto kernel = a.mode == kChromaMode420 ? k_chroma_planes<2, 2> : (a.mode == kChromaMode422 ? k_chroma_planes<2, 1> : k_chroma_planes<1, 1>);
+    if (ev) hipExtLaunchKernelGGL(kernel, grid, block, 0, (hipStream_t)stream, (hipEvent_t)ev[0], (hipEvent_t)ev[1], 0, a);
+    else hipLaunchKernelGGL(kernel, grid, block, 0, (hipStream_t)stream, a);
     return (int)hipGetLastError();
 }
 
@@ -136,7 +140,7 @@ int launch_append_scans(const AppendArgs &a, void *stream, void *const *ev) {
 
 // ---- colour batches (jpegamd_encode_color_batch_async) --------------------------------------------------------------------
 // k_chroma_planes_batch: workgroup (bx, cy, p) makes samples [1024 bx, 1024 bx + 1024) of plane row cy of picture p, both planes.
-// The source rows it needs (3 x 2048 bytes twice at 4:2:0, 3 x 1024 bytes at 4:4:4) are staged in LDS by aligned 16-byte loads --
+// The source rows it needs (3 x 2048 bytes twice at 4:2:0, once at 4:2:2, 3 x 1024 bytes at 4:4:4) are staged in LDS by aligned 16-byte loads --
 // one instruction covers 1 KiB of a row -- and every thread then reads its pixels from LDS as dwords, funnel-shifted by the row's
 // misalignment.  Only chunks that lie wholly inside the row's bytes are loaded as vectors; the partial chunks at both
 // ends are gathered byte by byte.  The arithmetic is k_chroma_planes's: the planes are the same, bit for bit.
@@ -145,24 +149,25 @@ int launch_append_scans(const AppendArgs &a, void *stream, void *const *ev) {
 constexpr int kPbThreads = 256;
 constexpr int kPbSpan = kPbThreads * kPlaneOut;            // plane samples per workgroup and row
 
-template <int kSub, int kLay>
+template <int kSx, int kSy, int kLay>
 __global__ __launch_bounds__(kPbThreads) void k_chroma_planes_batch(const ChromaPlanesBatchArgs a) {
     constexpr bool kPlanar = kLay == kChromaSrcPlanar;
     constexpr int kStreams = kPlanar ? 3 : 1;
     constexpr int kBpp = kPlanar ? 1 : (kLay == kChromaSrcPx4 ? 4 : 3);  // bytes per pixel of one stream
-    constexpr int kPix = kPlaneOut * kSub;                               // source pixels per row and thread
-    constexpr int kRowBytes = kBpp * kSub * kPbSpan;                     // source bytes per row, stream and workgroup
+    static_assert((kSx == 1 || kSx == 2) && (kSy == 1 || kSy == 2) && kSy <= kSx, "4:4:4, 4:2:2 or 4:2:0");
+    constexpr int kPix = kPlaneOut * kSx;                                // source pixels per row and thread
+    constexpr int kRowBytes = kBpp * kSx * kPbSpan;                     // source bytes per row, stream and workgroup
     constexpr int kLdsBytes = kRowBytes + 32;                            // + the misalignment (< 16) and the funnel's extra dword
     constexpr int kDw = kBpp * kPix / 4;                                 // dwords of a thread's pixels in one stream
-    __shared__ __attribute__((aligned(16))) uint8_t s_row[kSub][kStreams][kLdsBytes];
+    __shared__ __attribute__((aligned(16))) uint8_t s_row[kSy][kStreams][kLdsBytes];
     const int p = (int)blockIdx.z, cy = (int)blockIdx.y, t = (int)threadIdx.x;
     const int s0 = (int)blockIdx.x * kPbSpan;                            // < cw
-    const int x0 = s0 * kSub;                                            // < width
-    const int x_end = min(x0 + kSub * kPbSpan, a.width);
-    int mis[kSub][kStreams];
+    const int x0 = s0 * kSx;                                             // < width
+    const int x_end = min(x0 + kSx * kPbSpan, a.width);
+    int mis[kSy][kStreams];
 #pragma unroll
-    for (int r = 0; r < kSub; ++r) {
-        const int y = min(cy * kSub + r, a.height - 1);                  // the last row replicated (odd heights)
+    for (int r = 0; r < kSy; ++r) {
+        const int y = min(cy * kSy + r, a.height - 1);                  // the last row replicated (odd heights)
         const int stored = a.bottom_up ? a.height - 1 - y : y;
 #pragma unroll
         for (int st = 0; st < kStreams; ++st) {
@@ -193,10 +198,10 @@ __global__ __launch_bounds__(kPbThreads) void k_chroma_planes_batch(const Chroma
     __syncthreads();
     const int s = s0 + kPlaneOut * t;
     if (s >= a.cw) return;
-    const int xs = s * kSub;                                             // the thread's first pixel
-    int cb[kSub][kPix], cr[kSub][kPix];
+    const int xs = s * kSx;                                              // the thread's first pixel
+    int cb[kSy][kPix], cr[kSy][kPix];
 #pragma unroll
-    for (int r = 0; r < kSub; ++r) {
+    for (int r = 0; r < kSy; ++r) {
         uint8_t px[kStreams][kBpp * kPix];
 #pragma unroll
         for (int st = 0; st < kStreams; ++st) {
@@ -236,10 +241,15 @@ __global__ __launch_bounds__(kPbThreads) void k_chroma_planes_batch(const Chroma
 #pragma unroll
     for (int k = 0; k < kPlaneOut; ++k) {
         int vb, vr;
-        if (kSub == 2) {
+        if (kSx == 2) {
             const int j0 = 2 * k, j1 = xs + 2 * k + 1 < a.width ? 2 * k + 1 : 2 * k;
-            vb = (cb[0][j0] + cb[0][j1] + cb[kSub - 1][j0] + cb[kSub - 1][j1] + 2) >> 2;
-            vr = (cr[0][j0] + cr[0][j1] + cr[kSub - 1][j0] + cr[kSub - 1][j1] + 2) >> 2;
+            if (kSy == 2) {
+                vb = (cb[0][j0] + cb[0][j1] + cb[kSy - 1][j0] + cb[kSy - 1][j1] + 2) >> 2;
+                vr = (cr[0][j0] + cr[0][j1] + cr[kSy - 1][j0] + cr[kSy - 1][j1] + 2) >> 2;
+            } else {
+                vb = (cb[0][j0] + cb[0][j1] + 1) >> 1;
+                vr = (cr[0][j0] + cr[0][j1] + 1) >> 1;
+            }
         } else {
             vb = cb[0][k]; vr = cr[0][k];
         }
@@ -254,13 +264,15 @@ __global__ __launch_bounds__(kPbThreads) void k_chroma_planes_batch(const Chroma
 
 template <int kLay>
 static void launch_planes_batch_as(const ChromaPlanesBatchArgs &a, dim3 grid, dim3 block, hipStream_t stream, hipEvent_t e0, hipEvent_t e1) {
-    if (a.sub420) hipExtLaunchKernelGGL((k_chroma_planes_batch<2, kLay>), grid, block, 0, stream, e0, e1, 0, a);
-    else hipExtLaunchKernelGGL((k_chroma_planes_batch<1, kLay>), grid, block, 0, stream, e0, e1, 0, a);
+    if (a.mode == kChromaMode420) hipExtLaunchKernelGGL((k_chroma_planes_batch<2, 2, kLay>), grid, block, 0, stream, e0, e1, 0, a);
+    else if (a.mode == kChromaMode422) hipExtLaunchKernelGGL((k_chroma_planes_batch<2, 1, kLay>), grid, block, 0, stream, e0, e1, 0, a);
+    else hipExtLaunchKernelGGL((k_chroma_planes_batch<1, 1, kLay>), grid, block, 0, stream, e0, e1, 0, a);
 }
 
 int launch_chroma_planes_batch(const ChromaPlanesBatchArgs &a, void *stream, void *const *ev) {
     if (a.cw <= 0 || a.ch <= 0 || a.batch < 1 || a.batch > kMaxBatch || a.pitch % 4 != 0 || a.pitch < (a.cw + 3) / 4 * 4 ||
-        a.plane_bytes % 16 != 0 || a.plane_bytes < (uint64_t)a.pitch * (uint64_t)a.ch)
+        a.plane_bytes % 16 != 0 || a.plane_bytes < (uint64_t)a.pitch * (uint64_t)a.ch ||
+        (a.mode != kChromaMode444 && a.mode != kChromaMode420 && a.mode != kChromaMode422))
         return (int)hipErrorInvalidValue;
     const dim3 grid((unsigned)((a.cw + kPbSpan - 1) / kPbSpan), (unsigned)a.ch, (unsigned)a.batch), block(kPbThreads);
     hipEvent_t e0 = ev ? (hipEvent_t)ev[0] : nullptr, e1 = ev ? (hipEvent_t)ev[1] : nullptr;

@@ -164,7 +164,13 @@ struct TransformOutM {
 // kTileSrcChromaPair: a chroma scan (chroma tables, as kTileSrcChroma) whose samples are one component of a plane of byte pairs
 // (Cb Cr Cb Cr ...): launch image i reads component (ImageDesc::weights + i) & 1 of the pair plane batch_pixels[i]; width, height and
 // row_stride describe the component (width pairs per row, row_stride bytes between rows).  Plain build only, like the two above.
-constexpr int kTileSrcRgb = 0, kTileSrcGray = 1, kTileSrcChroma = 2, kTileSrcPx4 = 3, kTileSrcPlanar = 4, kTileSrcChromaPair = 5;
+// A packed 4:2:2 plane (Y Cb Y Cr / Cb Y Cr Y groups of 4 bytes for 2 pixels), plain build only as well:
+// kTileSrcLumaPair: the Y scan (luma tables) -- the rows are byte pairs of which EVERY launch image takes byte ImageDesc::weights & 1;
+// width (pixels), height and row_stride describe the Y component.  kTileSrcChromaQuad: a chroma scan (chroma tables) whose samples are
+// one byte of every 4-byte group: launch image i reads byte ((weights >> 8) & 1) + 2 ((weights + i) & 1) of the groups of
+// batch_pixels[i]; width is in groups.
+constexpr int kTileSrcRgb = 0, kTileSrcGray = 1, kTileSrcChroma = 2, kTileSrcPx4 = 3, kTileSrcPlanar = 4, kTileSrcChromaPair = 5,
+              kTileSrcLumaPair = 6, kTileSrcChromaQuad = 7;
 struct TilePlanes {                     // the second and third plane of every picture of a planar launch (its own kernel argument)
     const uint8_t *g[kMaxBatch];
     const uint8_t *b[kMaxBatch];
@@ -249,13 +255,14 @@ int launch_sum_stats(const uint32_t *seg_syms, const uint32_t *seg_exact, int n,
 int launch_dct_exact(const int8_t *blocks, float *coeffs, int64_t nblocks, void *stream);
 
 // Colour (jpegamd_color.hip).  k_chroma_planes: the picture -> Cb and Cr planes (u8, `pitch` bytes per row, a multiple of 4), full
-// resolution (4:4:4) or 2 x 2 averaged (4:2:0).  k_append_scans: the chroma scans, coded into context scratch, copied behind the
+// resolution (4:4:4), 2 x 2 averaged (4:2:0) or 2 x 1 averaged (4:2:2: cw x ch = ceil(w / 2) x h).  k_append_scans: the chroma scans, coded into context scratch, copied behind the
 // Y scan in the caller's buffer at the offsets the device computed; the per-scan statistics summed into one record.
+constexpr int kChromaMode444 = 0, kChromaMode420 = 1, kChromaMode422 = 2;
 struct ChromaPlanesArgs {
     const uint8_t *pixels;
     int32_t width, height, row_stride, bottom_up;
     int32_t rgb;                        // 1: stored bytes R, G, B; 0: B, G, R
-    int32_t sub420;                     // 1: 4:2:0, 0: 4:4:4
+    int32_t mode;                       // kChromaMode*
     int32_t cw, ch, pitch;              // plane geometry
     uint8_t *cb, *cr;
 };
@@ -278,7 +285,7 @@ struct ChromaPlanesBatchArgs {
     const uint8_t *pixels[kMaxBatch];   // (planar: the R planes)
     int32_t batch;
     int32_t width, height, row_stride, bottom_up;
-    int32_t rgb, sub420;
+    int32_t rgb, mode;                  // mode: kChromaMode*
     int32_t cw, ch, pitch;
     uint64_t plane_bytes;               // a multiple of 16
     uint8_t *planes;
@@ -327,7 +334,8 @@ void build_code_table_chroma(uint32_t words[kCodeWords]);
 // the byte count (<= kColorPrefixMax).  color_sos: the SOS segment in front of the scan of component 2 or 3 (10 bytes).
 constexpr int kColorPrefixMax = 640;
 constexpr int kSosBytes = 10;
-size_t build_jfif_prefix_color(int width, int height, const uint8_t luma[64], const uint8_t chroma[64], int sub420,
+// mode (kChromaMode*): the sampling factors of component 1 in SOF0 -- 0x11, 0x22 or 0x21.
+size_t build_jfif_prefix_color(int width, int height, const uint8_t luma[64], const uint8_t chroma[64], int mode,
                                uint8_t out[kColorPrefixMax]);
 void color_sos(int component, uint8_t out[kSosBytes]);
 // A-row order of the pipeline: lane half h, site s <-> zigzag 16(s>>3) + 8h + (s&7)

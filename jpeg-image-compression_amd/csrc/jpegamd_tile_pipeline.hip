@@ -148,8 +148,12 @@ static_assert(kPassItems * (27 + 3 * (int)kZrlBitsChroma) / 32 + 6 <= kWinStr &&
 //   kSrcPx4    4 bytes per pixel (RGBA / BGRA): luma by the weights of ImageDesc, whose fourth weight is 0
 //   kSrcPlanar three planes of one byte per sample, R (ImageDesc::batch_pixels), G and B (TilePlanes)
 //   kSrcPair   one plane of byte pairs (Cb Cr Cb Cr ...: NV12 chroma), of which a launch image takes ONE component: launch image i
-//              reads component (ImageDesc::weights + i) & 1 of the pair plane ImageDesc::batch_pixels[i]
-constexpr int kSrcRgb = 0, kSrcPlane = 1, kSrcPx4 = 2, kSrcPlanar = 3, kSrcPair = 4;
+//              reads component (ImageDesc::weights + i) & 1 of the pair plane ImageDesc::batch_pixels[i].  With the LUMA tables it is
+//              the Y scan of a packed 4:2:2 plane (Y Cb Y Cr / Cb Y Cr Y): EVERY launch image then reads component weights & 1
+//   kSrcQuad   one plane of 4-byte groups (the same packed 4:2:2 plane, as its chroma scans see it), of which a launch image takes
+//              ONE byte per group: launch image i reads byte ((weights >> 8) & 1) + 2 ((weights + i) & 1) -- Cb or Cr by the parity
+//              rule of kSrcPair, at bytes 1 / 3 (Y Cb Y Cr) or 0 / 2 (Cb Y Cr Y)
+constexpr int kSrcRgb = 0, kSrcPlane = 1, kSrcPx4 = 2, kSrcPlanar = 3, kSrcPair = 4, kSrcQuad = 5;
 // The kernel's last argument: the G and B planes for kSrcPlanar, an empty struct -- no kernel-argument bytes, so the offsets of
 // the hidden arguments behind it stay where they were -- for every other source.
 struct NoPlanes {};
@@ -171,6 +175,15 @@ __device__ __forceinline__ f16x8 pair_row8_f16(const uint32_t *d, uint32_t sel) 
     typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
     const u32x4 packed = {__builtin_amdgcn_perm(0u, d[0], sel), __builtin_amdgcn_perm(0u, d[1], sel),
                           __builtin_amdgcn_perm(0u, d[2], sel), __builtin_amdgcn_perm(0u, d[3], sel)};
+    return __builtin_bit_cast(f16x8, packed);
+}
+
+// 8 four-byte groups (8 dwords) -> the B fragment of one k-step half, from ONE byte k of every group: the selector
+// 0x0C040C00 + 0x00010001 k takes byte k of two dwords into the two halves -- four v_perm over four times the bytes of plane_row8_f16.
+__device__ __forceinline__ f16x8 quad_row8_f16(const uint32_t *d, uint32_t sel) {
+    typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
+    const u32x4 packed = {__builtin_amdgcn_perm(d[1], d[0], sel), __builtin_amdgcn_perm(d[3], d[2], sel),
+                          __builtin_amdgcn_perm(d[5], d[4], sel), __builtin_amdgcn_perm(d[7], d[6], sel)};
     return __builtin_bit_cast(f16x8, packed);
 }
 
@@ -235,6 +248,13 @@ __device__ __forceinline__ int pair_clamped(const ImageDesc &im, const uint8_t *
     x = min(x, im.width - 1);
     y = min(y, im.height - 1);
     return (int)row_ptr(im, pixels, y)[2 * (size_t)x + (size_t)comp];
+}
+
+// Byte `byte` (0 .. 3) of 4-byte group (x, y) of a packed plane, with the edge clamp (im.width counts groups).
+__device__ __forceinline__ int quad_clamped(const ImageDesc &im, const uint8_t *pixels, int byte, int x, int y) {
+    x = min(x, im.width - 1);
+    y = min(y, im.height - 1);
+    return (int)row_ptr(im, pixels, y)[4 * (size_t)x + (size_t)byte];
 }
 
 struct TileSched {            // division-free launch geometry, filled by launch_tile_transform
@@ -350,9 +370,10 @@ __device__ __forceinline__ void window_or(uint32_t *win, uint32_t rel, uint32_t 
     if (third) atomicOr(&win[w + 2], __builtin_amdgcn_alignbit(lo, 0u, sh));
 }
 
-// kSrc: what a pixel is (kSrcRgb / kSrcPlane / kSrcPx4 / kSrcPlanar / kSrcPair; `pl` is read by kSrcPlanar alone); kZBits / kZCode: the ZRL code of the Huffman table in TransformOutM::code_tab
+// kSrc: what a pixel is (kSrcRgb / kSrcPlane / kSrcPx4 / kSrcPlanar / kSrcPair / kSrcQuad; `pl` is read by kSrcPlanar alone); kZBits / kZCode: the ZRL code of the Huffman table in TransformOutM::code_tab
 // (luma: 11 bits 0x7F9; chroma: 10 bits 0x3FA).  A GRAY picture is <kTaps, kSrcPlane>, a chroma plane <false, kSrcPlane, 10, 0x3FA>,
-// one component of an interleaved chroma plane <false, kSrcPair, 10, 0x3FA>.
+// one component of an interleaved chroma plane <false, kSrcPair, 10, 0x3FA>, the Y of a packed 4:2:2 plane <false, kSrcPair> and its
+// Cb or Cr <false, kSrcQuad, 10, 0x3FA>.
 template <bool kTaps, int kSrc = kSrcRgb, uint32_t kZBits = kZrlBits, uint32_t kZCode = kZrlCode>
 __global__ __launch_bounds__(64 * kWavesT) __attribute__((amdgpu_waves_per_eu(JPEGAMD_TILE_WAVES, JPEGAMD_TILE_WAVES)))
 void k_tile_encode(const ImageDesc im, const TransformOutM out, const TileSched sch, const typename PlanesArg<kSrc>::type pl) {
@@ -401,6 +422,9 @@ void k_tile_encode(const ImageDesc im, const TransformOutM out, const TileSched 
         } \
         __syncthreads(); \
 
+    // kSrcPair with the luma tables is a packed plane's Y scan: one component for every launch image (the chroma instantiation adds the
+    // launch image's index as before: a compile-time zero or the index, no new instruction in either)
+    constexpr bool kPairFixed = kSrc == kSrcPair && kZBits == kZrlBits;
     const int lane = lane_id();
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));   // provably uniform: tile indices, list pointers and the buffer descriptor stay on the scalar unit
     const int h = lane >> 5, b = lane & 31;
@@ -489,7 +513,7 @@ void k_tile_encode(const ImageDesc im, const TransformOutM out, const TileSched 
         const uint8_t *tb = im.batch_pixels[g.img] + (size_t)row_low * (size_t)im.row_stride + 24 * (size_t)g.tbx0;
         uint32_t hh = (uint32_t)h;
         asm volatile("" : "+v"(hh));
-        if constexpr (kSrc == kSrcPx4) {                        // 32 bytes per lane-row.  Four rows of eight dwords are 8 registers more than
+        if constexpr (kSrc == kSrcPx4 || kSrc == kSrcQuad) {    // 32 bytes per lane-row (kSrcQuad: 8 groups).  Four rows of eight dwords are 8 registers more than
             // raw[] holds (the kernel sits at its register limit): rows 0 .. 2 are requested here, row 3 at the top of the tile's iteration
             const uint8_t *qb = im.batch_pixels[g.img] + (size_t)row_low * (size_t)im.row_stride + 32 * (size_t)g.tbx0;
             uint32_t qoff = __umul24((uint32_t)min(b, g.nblk - 1), 32u) + __umul24(im.bottom_up ? 7u - hh : hh, (uint32_t)im.row_stride);
@@ -575,7 +599,7 @@ void k_tile_encode(const ImageDesc im, const TransformOutM out, const TileSched 
         // ---- 1. pixels -> B fragments ----------------------------------------------------------
         f16x8 bfrag[4];
         if (interior) {                        // rows requested one iteration ago, behind the ticket (below)
-            if constexpr (kSrc == kSrcPx4) {   // ... but for the fourth row pair (request_rows): on its way while the other three are converted
+            if constexpr (kSrc == kSrcPx4 || kSrc == kSrcQuad) {   // ... but for the fourth row pair (request_rows): on its way while the other three are converted
                 uint32_t hh = (uint32_t)h;
                 asm volatile("" : "+v"(hh));
                 const int row_low = im.bottom_up ? im.height - 8 - by * 8 : by * 8;
@@ -587,14 +611,21 @@ void k_tile_encode(const ImageDesc im, const TransformOutM out, const TileSched 
 #pragma unroll
                 for (int i = 0; i < 8; ++i) last[i] = src[i];
                 const uint32_t *const flat = &raw[0].d[0];
+                if constexpr (kSrc == kSrcQuad) {   // (the byte is wave-uniform: the selector stays on the scalar unit, as kSrcPair's)
+                    const uint32_t qsel = 0x0C040C00u + 0x00010001u * (((im.weights >> 8) & 1u) + 2u * ((im.weights + (uint32_t)tg.img) & 1u));
+#pragma unroll
+                    for (int s = 0; s < 3; ++s) bfrag[s] = quad_row8_f16(flat + 8 * s, qsel);
+                    bfrag[3] = quad_row8_f16(last, qsel);
+                } else {
 #pragma unroll
                 for (int s = 0; s < 3; ++s) bfrag[s] = px4_row8_f16(flat + 8 * s, im.weights, luma_sel);
                 bfrag[3] = px4_row8_f16(last, im.weights, luma_sel);
+                }
             } else {
 #pragma unroll
             for (int s = 0; s < 4; ++s) {
                 // (kSrcPair: the component is the launch image's parity, wave-uniform: the selector stays on the scalar unit)
-                if constexpr (kSrc == kSrcPair) bfrag[s] = pair_row8_f16(raw[s].d, 0x0C020C00u + 0x00010001u * ((im.weights + (uint32_t)tg.img) & 1u));
+                if constexpr (kSrc == kSrcPair) bfrag[s] = pair_row8_f16(raw[s].d, 0x0C020C00u + 0x00010001u * ((im.weights + (kPairFixed ? 0u : (uint32_t)tg.img)) & 1u));
                 else if constexpr (kSrc == kSrcPlane) bfrag[s] = plane_row8_f16(raw[s].d[0], raw[s].d[1]);
                 else if constexpr (kSrc == kSrcPlanar) bfrag[s] = planar_row8_f16(raw[s], luma_sel);
                 else bfrag[s] = luma_row8_f16(raw[s], lw, luma_sel);
@@ -609,8 +640,11 @@ void k_tile_encode(const ImageDesc im, const TransformOutM out, const TileSched 
 #pragma unroll
                 for (int j = 0; j < 8; j += 2) {                // two values per register: Y in each 16-bit half (= Y 2^-24 as binary16, as above)
                     if constexpr (kSrc == kSrcPair)
-                        pk[j >> 1] = (uint32_t)pair_clamped(im, im.batch_pixels[tg.img], (int)((im.weights + (uint32_t)tg.img) & 1u), px0 + j, py0 + 2 * s + h) |
-                                     ((uint32_t)pair_clamped(im, im.batch_pixels[tg.img], (int)((im.weights + (uint32_t)tg.img) & 1u), px0 + j + 1, py0 + 2 * s + h) << 16);
+                        pk[j >> 1] = (uint32_t)pair_clamped(im, im.batch_pixels[tg.img], (int)((im.weights + (kPairFixed ? 0u : (uint32_t)tg.img)) & 1u), px0 + j, py0 + 2 * s + h) |
+                                     ((uint32_t)pair_clamped(im, im.batch_pixels[tg.img], (int)((im.weights + (kPairFixed ? 0u : (uint32_t)tg.img)) & 1u), px0 + j + 1, py0 + 2 * s + h) << 16);
+                    else if constexpr (kSrc == kSrcQuad)
+                        pk[j >> 1] = (uint32_t)quad_clamped(im, im.batch_pixels[tg.img], (int)(((im.weights >> 8) & 1u) + 2u * ((im.weights + (uint32_t)tg.img) & 1u)), px0 + j, py0 + 2 * s + h) |
+                                     ((uint32_t)quad_clamped(im, im.batch_pixels[tg.img], (int)(((im.weights >> 8) & 1u) + 2u * ((im.weights + (uint32_t)tg.img) & 1u)), px0 + j + 1, py0 + 2 * s + h) << 16);
                     else if constexpr (kSrc == kSrcPlane)
                         pk[j >> 1] = (uint32_t)plane_clamped(im, im.batch_pixels[tg.img], px0 + j, py0 + 2 * s + h) |
                                      ((uint32_t)plane_clamped(im, im.batch_pixels[tg.img], px0 + j + 1, py0 + 2 * s + h) << 16);
@@ -1195,7 +1229,7 @@ int launch_tile_transform(const ImageDesc &im, const TransformOutM &out, bool ta
     sch.tpr_magic = magic > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)magic;   // tiles_per_row == 1: the correction step makes up for it
     const dim3 grid(wgs), block(64 * kWavesT);
     const NoPlanes pl;
-    if (src == kTileSrcPx4 || src == kTileSrcPlanar || src == kTileSrcChromaPair) {
+    if (src == kTileSrcPx4 || src == kTileSrcPlanar || src == kTileSrcChromaPair || src == kTileSrcLumaPair || src == kTileSrcChromaQuad) {
 #ifdef JPEGAMD_STAMPED_TU
         return (int)hipErrorInvalidValue;                                   // (these sources exist in the plain build alone)
 #else
@@ -1204,7 +1238,11 @@ int launch_tile_transform(const ImageDesc &im, const TransformOutM &out, bool ta
         const auto planar = k_tile_encode<false, kSrcPlanar>;
         hipEvent_t e0 = ev ? (hipEvent_t)ev[0] : nullptr, e1 = ev ? (hipEvent_t)ev[1] : nullptr;
         const auto pair = k_tile_encode<false, kSrcPair, kZrlBitsChroma, kZrlCodeChroma>;
+        const auto ypair = k_tile_encode<false, kSrcPair>;
+        const auto quad = k_tile_encode<false, kSrcQuad, kZrlBitsChroma, kZrlCodeChroma>;
         if (src == kTileSrcChromaPair) hipExtLaunchKernelGGL(pair, grid, block, 0, (hipStream_t)stream, e0, e1, 0, im, out, sch, pl);
+        else if (src == kTileSrcLumaPair) hipExtLaunchKernelGGL(ypair, grid, block, 0, (hipStream_t)stream, e0, e1, 0, im, out, sch, pl);
+        else if (src == kTileSrcChromaQuad) hipExtLaunchKernelGGL(quad, grid, block, 0, (hipStream_t)stream, e0, e1, 0, im, out, sch, pl);
         else if (src == kTileSrcPx4) hipExtLaunchKernelGGL(px4, grid, block, 0, (hipStream_t)stream, e0, e1, 0, im, out, sch, pl);
         else hipExtLaunchKernelGGL(planar, grid, block, 0, (hipStream_t)stream, e0, e1, 0, im, out, sch, *planes);
         return (int)hipGetLastError();

@@ -183,7 +183,7 @@ size_t build_jfif_prefix(int width, int height, const uint8_t table[64], uint8_t
     return (size_t)(p - out);
 }
 
-size_t build_jfif_prefix_color(int width, int height, const uint8_t luma[64], const uint8_t chroma[64], int sub420,
+size_t build_jfif_prefix_color(int width, int height, const uint8_t luma[64], const uint8_t chroma[64], int mode,
                                uint8_t out[kColorPrefixMax]) {
     // The grayscale prefix's SOI + APP0, then the colour headers (colour scans).
     uint8_t *p = out;
@@ -197,7 +197,7 @@ size_t build_jfif_prefix_color(int width, int height, const uint8_t luma[64], co
     *p++ = 1;
     for (int i = 0; i < 64; ++i) *p++ = chroma[kZigzagHost[i]];
     be16(0xFFC0); be16(8 + 3 * 3); *p++ = 8; be16((uint16_t)height); be16((uint16_t)width); *p++ = 3;
-    *p++ = 1; *p++ = sub420 ? 0x22 : 0x11; *p++ = 0;
+    *p++ = 1; *p++ = mode == kChromaMode420 ? 0x22 : (mode == kChromaMode422 ? 0x21 : 0x11); *p++ = 0;
     *p++ = 2; *p++ = 0x11; *p++ = 1;
     *p++ = 3; *p++ = 0x11; *p++ = 1;
     auto dht = [&](int tc_th, const uint8_t counts[16], const uint8_t *symbols) {

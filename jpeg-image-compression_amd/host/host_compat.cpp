@@ -43,7 +43,7 @@ struct DeviceBuf {
 };
 
 // Encode device-resident pixels into a host vector (JFIF file bytes).
-// subsampling 0: the grayscale file; JPEGAMD_SUBSAMPLE_444 / _420: the colour file (jpegamd_encode_color_async).
+// subsampling 0: the grayscale file; JPEGAMD_SUBSAMPLE_444 / _420 / _422: the colour file (jpegamd_encode_color_async).
 int64_t encode_to_host(const JpegAmdImage &img, std::vector<uint8_t> &out, JpegAmdStats *st, int32_t subsampling = 0) {
     uint64_t *size_dev = nullptr;
     JpegAmdEncoder *enc = jpegamd::shared_context(img.width, img.height, &size_dev);
@@ -89,7 +89,7 @@ extern "C" int32_t jpegamd_parse_bmp(const uint8_t *bmp, uint64_t bmp_len, JpegA
     return JPEGAMD_OK;
 }
 
-// subsampling 0: the grayscale file (jpegamd_encode_bmp_memory); 444 / 420: the colour file (jpegamd_encode_bmp_memory_color)
+// subsampling 0: the grayscale file (jpegamd_encode_bmp_memory); 444 / 420 / 422: the colour file (jpegamd_encode_bmp_memory_color)
 static int64_t encode_bmp_memory(const uint8_t *bmp, uint64_t bmp_len, int32_t quality, int32_t subsampling, uint8_t *out,
                                  uint64_t out_cap);
 
@@ -121,7 +121,7 @@ static int64_t encode_bmp_memory(const uint8_t *bmp, uint64_t bmp_len, int32_t q
 
 extern "C" int64_t jpegamd_encode_bmp_memory_color(const uint8_t *bmp, uint64_t bmp_len, int32_t quality, int32_t subsampling,
                                                    uint8_t *out, uint64_t out_cap) {
-    if (subsampling != JPEGAMD_SUBSAMPLE_444 && subsampling != JPEGAMD_SUBSAMPLE_420) return JPEGAMD_ERR_ARG;
+    if (subsampling != JPEGAMD_SUBSAMPLE_444 && subsampling != JPEGAMD_SUBSAMPLE_420 && subsampling != JPEGAMD_SUBSAMPLE_422) return JPEGAMD_ERR_ARG;
     return encode_bmp_memory(bmp, bmp_len, quality, subsampling, out, out_cap);
 }
 

@@ -17,7 +17,7 @@ HEADER_PATH = _PKG_ROOT.parent / "include" / "jpeg_compression.h"
 
 ORDER_BGR, ORDER_RGB, ORDER_GRAY = 0, 1, 2                  # JPEGAMD_ORDER_* (GRAY: one byte per pixel, the luma itself)
 ORDER_RGBA, ORDER_BGRA = 3, 4                                # four bytes per pixel, the fourth ignored
-SUBSAMPLE_444, SUBSAMPLE_420 = 1, 2                          # JPEGAMD_SUBSAMPLE_* (colour files)
+SUBSAMPLE_444, SUBSAMPLE_420, SUBSAMPLE_422 = 1, 2, 4        # JPEGAMD_SUBSAMPLE_* (colour files; 3 stays an invalid value)
 JFIF_PREFIX_BYTES = 328
 
 ERR_NAMES = {0: "OK", -1: "ERR_ARG", -2: "ERR_NO_DEVICE", -3: "ERR_HIP", -4: "ERR_NOT_INIT", -5: "ERR_TOO_LARGE",
@@ -42,6 +42,7 @@ class PlanarImage(C.Structure):
 
 
 CHROMA_PLANES, CHROMA_CBCR, CHROMA_CRCB = 0, 1, 2           # JPEGAMD_CHROMA_*
+CHROMA_YUYV, CHROMA_UYVY = 4, 5                             # packed 4:2:2: the picture's y is the packed plane (3 stays invalid)
 
 
 class YCbCrImage(C.Structure):
@@ -471,8 +472,8 @@ def _ycbcr_layout(y, cb, cr, subsampling, order):
     """The pictures of encode_ycbcr_batch -> (count, height, width, y stride, chroma stride, JPEGAMD_CHROMA_* layout).  Shapes,
     dtypes and strides only: host tensors pass."""
     import torch
-    if subsampling not in (SUBSAMPLE_444, SUBSAMPLE_420):
-        raise ValueError("subsampling must be SUBSAMPLE_444 or SUBSAMPLE_420")
+    if subsampling not in (SUBSAMPLE_444, SUBSAMPLE_420, SUBSAMPLE_422):
+        raise ValueError("subsampling must be SUBSAMPLE_444, SUBSAMPLE_420 or SUBSAMPLE_422")
     if order not in ("cbcr", "crcb"):
         raise ValueError(f'order must be "cbcr" or "crcb", not {order!r}')
     tensors = [y, cb] + ([cr] if cr is not None else [])
@@ -483,7 +484,8 @@ def _ycbcr_layout(y, cb, cr, subsampling, order):
     n, h, w = y.shape
     if n < 1 or h < 1 or w < 1 or h > 65535 or w > 65535:
         raise ValueError("the encoder needs at least one picture of 1..65535 pixels each way")
-    cw, ch = ((w + 1) // 2, (h + 1) // 2) if subsampling == SUBSAMPLE_420 else (w, h)
+    cw = w if subsampling == SUBSAMPLE_444 else (w + 1) // 2
+    ch = (h + 1) // 2 if subsampling == SUBSAMPLE_420 else h
     if cr is None:
         if cb.dim() != 4 or tuple(cb.shape) != (n, ch, cw, 2):
             raise ValueError(f"with cr=None, cb holds the byte pairs: [N, {ch}, {cw}, 2] for this y and subsampling, not {tuple(cb.shape)}")
@@ -513,9 +515,10 @@ def _ycbcr_layout(y, cb, cr, subsampling, order):
 def encode_ycbcr_batch(y, cb, cr=None, quality: int = 0, subsampling: int = SUBSAMPLE_420, order: str = "cbcr") -> list:
     """N pictures whose samples already ARE Y, Cb and Cr (JFIF full range; no range or matrix conversion is done) -> N colour JFIF
     files through jpegamd_encode_ycbcr_batch_async, read where they lie: no RGB detour, no chroma-plane pass.
-    `y` is a uint8 DEVICE tensor [N, H, W]; `cb` and `cr` are [N, ch, cw] with (ch, cw) = (H, W) at SUBSAMPLE_444 and
-    (ceil(H / 2), ceil(W / 2)) at SUBSAMPLE_420 (I420; YV12 by swapping them).  With cr=None, `cb` is [N, ch, cw, 2]: byte pairs
-    Cb Cr (NV12; NV24 at 4:4:4), or Cr Cb with order="crcb" (NV21 / NV42).  Rows and pictures may be strided, samples within a row
+    `y` is a uint8 DEVICE tensor [N, H, W]; `cb` and `cr` are [N, ch, cw] with (ch, cw) = (H, W) at SUBSAMPLE_444,
+    (ceil(H / 2), ceil(W / 2)) at SUBSAMPLE_420 (I420; YV12 by swapping them) and (H, ceil(W / 2)) at SUBSAMPLE_422 (I422).  With
+    cr=None, `cb` is [N, ch, cw, 2]: byte pairs Cb Cr (NV12; NV16 at 4:2:2; NV24 at 4:4:4), or Cr Cb with order="crcb" (NV21 / NV61 /
+    NV42).  Packed 4:2:2 frames (YUY2 / UYVY) go through encode_yuyv_batch.  Rows and pictures may be strided, samples within a row
     are packed.  Batches of more than MAX_BATCH pictures go as several calls; the per-device context of encode_tensor is used.
     An NV12 frame tensor `f` of shape [3 * H // 2, W] (H and W even: H rows of Y, then H / 2 rows of Cb Cr pairs) is
 
@@ -524,12 +527,18 @@ def encode_ycbcr_batch(y, cb, cr=None, quality: int = 0, subsampling: int = SUBS
         jpegamd.encode_ycbcr_batch(y, cbcr)
 
     and a stack of frames [N, 3 * H // 2, W] slices the same way: f[:, :H] and f[:, H:].unflatten(2, (W // 2, 2))."""
-    import torch
     n, h, w, y_stride, c_stride, layout = _ycbcr_layout(y, cb, cr, subsampling, order)
     tensors = [y, cb] + ([cr] if cr is not None else [])
     if any(not x.is_cuda or x.device != y.device for x in tensors):
         raise ValueError("encode_ycbcr_batch needs device tensors on one device")
-    device = y.device
+    return _encode_ycbcr_images(y.device, n, h, w, subsampling, lambda i: Encoder.ycbcr_image(
+        y[i].data_ptr(), cb[i].data_ptr(), cr[i].data_ptr() if cr is not None else 0, w, h, y_stride, c_stride, layout, quality))
+
+
+def _encode_ycbcr_images(device, n, h, w, subsampling, image):
+    """`n` YCbCr pictures of one geometry, picture i described by image(i), through the per-device context in calls of at most
+    MAX_BATCH -> their files."""
+    import torch
     dev = device.index if device.index is not None else torch.cuda.current_device()
     files = []
     with torch.cuda.device(dev):
@@ -550,13 +559,48 @@ def encode_ycbcr_batch(y, cb, cr=None, quality: int = 0, subsampling: int = SUBS
             k = min(MAX_BATCH, n - b0)
             outs = [out[i].data_ptr() for i in range(k)]
             size_ptrs = [sizes.data_ptr() + 8 * i for i in range(k)]
-            imgs = [Encoder.ycbcr_image(y[b0 + i].data_ptr(), cb[b0 + i].data_ptr(), cr[b0 + i].data_ptr() if cr is not None else 0,
-                                        w, h, y_stride, c_stride, layout, quality) for i in range(k)]
+            imgs = [image(b0 + i) for i in range(k)]
             enc.encode_ycbcr_batch_async(imgs, subsampling, outs, cap, size_ptrs, stream)
             enc.finish()
             got = sizes[:k].cpu().tolist()
             files += [bytes(out[i, :got[i]].cpu().numpy().tobytes()) for i in range(k)]
     return files
+
+
+def _yuyv_layout(frames, order):
+    """The pictures of encode_yuyv_batch -> (count, height, width, row stride, JPEGAMD_CHROMA_* layout).  Shapes, dtypes and strides
+    only: host tensors pass."""
+    import torch
+    if order not in ("yuyv", "uyvy"):
+        raise ValueError(f'order must be "yuyv" or "uyvy", not {order!r}')
+    if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8:
+        raise ValueError("the encoder needs a uint8 tensor")
+    if frames.dim() != 4 or frames.shape[3] != 2:
+        raise ValueError("frames must be [N, H, W, 2]: two bytes per pixel")
+    n, h, w = frames.shape[0], frames.shape[1], frames.shape[2]
+    if n < 1 or h < 1 or w < 1 or h > 65535 or w > 65535:
+        raise ValueError("the encoder needs at least one picture of 1..65535 pixels each way")
+    if w % 2:
+        raise ValueError("a [N, H, W, 2] frame holds whole 4-byte groups of two pixels: W must be even")
+    if frames.stride(3) != 1 or frames.stride(2) != 2:
+        raise ValueError("the pixels of a row must be packed (pixel stride 2, last stride 1)")
+    stride = frames.stride(1) if h > 1 else 2 * w
+    if stride < 2 * w:
+        raise ValueError("rows overlap (the row stride is less than a row)")
+    return n, h, w, stride, (CHROMA_YUYV if order == "yuyv" else CHROMA_UYVY)
+
+
+def encode_yuyv_batch(frames, quality: int = 0, order: str = "yuyv") -> list:
+    """N packed 4:2:2 frames -> N colour JFIF files at SUBSAMPLE_422 through jpegamd_encode_ycbcr_batch_async, read where they
+    lie: the samples are coded as given (JFIF full range; no range or matrix conversion, no filter).
+    `frames` is a uint8 DEVICE tensor [N, H, W, 2], W even: groups of four bytes Y0 Cb Y1 Cr for two pixels (YUY2), or Cb Y0 Cr Y1
+    with order="uyvy".  Rows and pictures may be strided; the two bytes of a pixel and the pixels of a row are packed.  Batches of
+    more than MAX_BATCH frames go as several calls; the per-device context of encode_tensor is used."""
+    n, h, w, stride, layout = _yuyv_layout(frames, order)
+    if not frames.is_cuda:
+        raise ValueError("encode_yuyv_batch needs a device tensor")
+    return _encode_ycbcr_images(frames.device, n, h, w, SUBSAMPLE_422, lambda i: Encoder.ycbcr_image(
+        frames[i].data_ptr(), 0, 0, w, h, stride, 0, layout, quality))
 
 
 class BatchStats(C.Structure):
@@ -631,7 +675,7 @@ class Encoder:
 
     def encode_planar_batch_async(self, imgs, subsampling: int, out_ptrs, out_cap: int, size_ptrs, stream: int = 0):
         """The files of `len(imgs)` planar pictures of one geometry (jpegamd_encode_planar_batch_async): subsampling 0 grayscale
-        files, SUBSAMPLE_444 / SUBSAMPLE_420 colour files; the context as for the packed batch entries."""
+        files, SUBSAMPLE_444 / SUBSAMPLE_420 / SUBSAMPLE_422 colour files; the context as for the packed batch entries."""
         n = len(imgs)
         arr = (PlanarImage * n)(*imgs)
         outs = (C.c_void_p * n)(*[C.c_void_p(p) for p in out_ptrs])
@@ -644,7 +688,8 @@ class Encoder:
     def ycbcr_image(y_ptr: int, cb_ptr: int, cr_ptr: int, width: int, height: int, y_stride: int, c_stride: int,
                     chroma_layout: int = CHROMA_PLANES, quality: int = 0) -> YCbCrImage:
         """Device pointers of the Y plane and the chroma: two planes (CHROMA_PLANES), or one plane of byte pairs in `cb_ptr`
-        (CHROMA_CBCR / CHROMA_CRCB; `cr_ptr` is then ignored and may be 0)."""
+        (CHROMA_CBCR / CHROMA_CRCB; `cr_ptr` is then ignored and may be 0), or one packed 4:2:2 plane in `y_ptr` (CHROMA_YUYV /
+        CHROMA_UYVY: `y_stride` is its row stride, the chroma arguments are ignored)."""
         return YCbCrImage(y_ptr or None, cb_ptr or None, cr_ptr or None, width, height, y_stride, c_stride, chroma_layout, quality)
 
     def encode_ycbcr_batch_async(self, imgs, subsampling: int, out_ptrs, out_cap: int, size_ptrs, stream: int = 0):
@@ -666,7 +711,7 @@ class Encoder:
             raise JpegAmdError(rc, "jpegamd_encode_async")
 
     def encode_color_async(self, img: Image, subsampling: int, out_ptr: int, out_cap: int, size_ptr: int, stream: int = 0):
-        """The colour file of an RGB / BGR image (jpegamd_encode_color_async): SUBSAMPLE_444 or SUBSAMPLE_420."""
+        """The colour file of an RGB / BGR image (jpegamd_encode_color_async): SUBSAMPLE_444, SUBSAMPLE_420 or SUBSAMPLE_422."""
         rc = lib.jpegamd_encode_color_async(self._h, C.byref(img), int(subsampling), C.c_void_p(out_ptr), out_cap, C.c_void_p(size_ptr),
                                             C.c_void_p(stream))
         if rc:

@@ -11,6 +11,8 @@ With --source (and --batch N, default 8) the batch loop reads another source, 4:
 Y plane and one plane of Cb Cr pairs that the colour path itself derives from the same pictures (computed once, outside the timed
 loop), through jpegamd_encode_ycbcr_batch_async -- the files are those of `rgb`, so "bytes" must agree.  Several sources separated
 by commas (--source rgb,i420,nv12) run one after the other in ONE process: one session, one set of pictures.
+`i422` (three planes) and `yuyv` (one packed YUY2 plane per picture) are the 4:2:2 sources, derived the same way.
+--subsampling {420,444,422} picks ONE subsampling for the rgb loops (default: 4:2:0 and 4:4:4 in turn, as before).
 
 With --layout {hwc,chw,rgba} (and --batch N, default 8) the pictures are device tensors stored that way -- [N, H, W, 3], [N, 3, H, W],
 [N, H, W, 4] -- and go through the entry that reads them where they lie, 4:2:0 only.  Every call is timed as a whole between two
@@ -41,7 +43,8 @@ def main() -> None:
     ap.add_argument("--quality", type=int, default=50)
     ap.add_argument("--kind", type=int, default=0)
     ap.add_argument("--batch", type=int, default=None, help="pictures per call through the colour batch entry (1 .. 32)")
-    ap.add_argument("--source", default="rgb", help="rgb (default), i420, nv12, or several separated by commas: what the batch loop reads")
+    ap.add_argument("--source", default="rgb", help="rgb (default), i420, nv12, i422, yuyv, or several separated by commas: what the batch loop reads")
+    ap.add_argument("--subsampling", choices=("420", "444", "422"), default=None, help="rgb: this subsampling alone (default: 420, then 444)")
     ap.add_argument("--layout", choices=("hwc", "chw", "rgba"), default=None, help="device tensors stored this way, read where they lie")
     ap.add_argument("--rounds", type=int, default=5, help="--layout: medians taken (each of --steps calls)")
     ap.add_argument("--repack", action="store_true", help="--layout chw: also time permute + packed encode")
@@ -58,8 +61,8 @@ def main() -> None:
         run_layout(a, jpegamd, torch, dev)
         return
     sources = a.source.split(",")
-    if any(s not in ("rgb", "i420", "nv12") for s in sources):
-        sys.exit("--source takes rgb, i420, nv12 or a comma-separated list of them")
+    if any(s not in ("rgb", "i420", "nv12", "i422", "yuyv") for s in sources):
+        sys.exit("--source takes rgb, i420, nv12, i422, yuyv or a comma-separated list of them")
     if a.batch is not None or sources != ["rgb"]:
         run_batch(a, jpegamd, torch, dev, sources)
         return
@@ -69,7 +72,7 @@ def main() -> None:
     desc = jpegamd.Encoder.image(px.data_ptr(), w, h, img.row_stride, True, jpegamd.ORDER_BGR, a.quality)
     enc = jpegamd.Encoder(w, h)
     stream = torch.cuda.current_stream().cuda_stream
-    for sub, name in ((jpegamd.SUBSAMPLE_420, "420"), (jpegamd.SUBSAMPLE_444, "444")):
+    for sub, name in rgb_subsamplings(a, jpegamd):
         cap = jpegamd.max_jfif_bytes_color(w, h, sub)
         out = torch.empty(cap, dtype=torch.uint8, device=dev)
         size = torch.zeros(1, dtype=torch.int64, device=dev)
@@ -91,6 +94,22 @@ def main() -> None:
                           "kernel_ns_sum": sum(med.values())}))
 
 
+def rgb_subsamplings(a, jpegamd):
+    subs = {"420": jpegamd.SUBSAMPLE_420, "444": jpegamd.SUBSAMPLE_444, "422": jpegamd.SUBSAMPLE_422}
+    return [(subs[a.subsampling], a.subsampling)] if a.subsampling else [(subs["420"], "420"), (subs["444"], "444")]
+
+
+def ycbcr_422(torch, px, w, h, stride):
+    """... at 4:2:2: Y [H, W], Cb and Cr [H, W / 2], (a + b + 1) >> 1 over the pixel pairs of a row."""
+    bgr = px.view(h, stride)[:, :3 * w].reshape(h, w, 3).flip(0)
+    b, g, r = (bgr[:, :, k].to(torch.int32) for k in range(3))
+    y = ((77 * r + 150 * g + 29 * b) >> 8).to(torch.uint8)
+
+    def pair(p):
+        return ((p[:, 0::2] + p[:, 1::2] + 1) >> 1).to(torch.uint8)
+    return y, pair((32768 - 43 * r - 85 * g + 128 * b) >> 8), pair((32768 + 128 * r - 107 * g - 21 * b) >> 8)
+
+
 def ycbcr_420(torch, px, w, h, stride):
     """The planes the colour path derives from one stored picture (bottom-up B, G, R rows): Y [H, W], Cb and Cr [H / 2, W / 2]."""
     bgr = px.view(h, stride)[:, :3 * w].reshape(h, w, 3).flip(0)
@@ -108,7 +127,7 @@ def run_batch(a, jpegamd, torch, dev, sources=("rgb",)) -> None:
     w = h = a.size
     n = a.batch or 8
     if any(s != "rgb" for s in sources) and (w % 2 or h % 2):
-        sys.exit("--source i420 / nv12 needs an even --size")
+        sys.exit("--source i420 / nv12 / i422 / yuyv needs an even --size")
     pxs, descs = [], []
     for i in range(n):
         bmp = jpegamd.synth_bmp(w, h, 1 + i, a.kind, 0)
@@ -119,7 +138,7 @@ def run_batch(a, jpegamd, torch, dev, sources=("rgb",)) -> None:
     enc = jpegamd.Encoder(w, n * h)
     stream = torch.cuda.current_stream().cuda_stream
     frames = None
-    if any(s != "rgb" for s in sources):                         # NV12 frames [N, 3 H / 2, W], and the chroma as two planes
+    if any(s in ("i420", "nv12") for s in sources):              # NV12 frames [N, 3 H / 2, W], and the chroma as two planes
         frames = torch.empty((n, 3 * h // 2, w), dtype=torch.uint8, device=dev)
         cbs, crs = (torch.empty((n, h // 2, w // 2), dtype=torch.uint8, device=dev) for _ in range(2))
         for i in range(n):
@@ -129,9 +148,28 @@ def run_batch(a, jpegamd, torch, dev, sources=("rgb",)) -> None:
             frames[i, h:].view(h // 2, w // 2, 2)[:, :, 1] = crs[i]
             del y
     runs = []
+    packed = None
+    if any(s in ("i422", "yuyv") for s in sources):              # YUY2 frames [N, H, W, 2], and the same samples as three planes
+        packed = torch.empty((n, h, w, 2), dtype=torch.uint8, device=dev)
+        cbs2, crs2 = (torch.empty((n, h, w // 2), dtype=torch.uint8, device=dev) for _ in range(2))
+        for i in range(n):
+            y, cbs2[i], crs2[i] = ycbcr_422(torch, pxs[i], w, h, img.row_stride)
+            packed[i, :, :, 0] = y
+            packed[i, :, 0::2, 1] = cbs2[i]
+            packed[i, :, 1::2, 1] = crs2[i]
+            del y
+        ys2 = packed[:, :, :, 0].contiguous()
     for source in sources:
         if source == "rgb":
-            runs += [(source, sub, name, None) for sub, name in ((jpegamd.SUBSAMPLE_420, "420"), (jpegamd.SUBSAMPLE_444, "444"))]
+            runs += [(source, sub, name, None) for sub, name in rgb_subsamplings(a, jpegamd)]
+        elif source == "i422":
+            runs.append((source, jpegamd.SUBSAMPLE_422, "422",
+                         [jpegamd.Encoder.ycbcr_image(ys2[i].data_ptr(), cbs2[i].data_ptr(), crs2[i].data_ptr(), w, h, w, w // 2,
+                                                      jpegamd.CHROMA_PLANES, a.quality) for i in range(n)]))
+        elif source == "yuyv":
+            runs.append((source, jpegamd.SUBSAMPLE_422, "422",
+                         [jpegamd.Encoder.ycbcr_image(packed[i].data_ptr(), 0, 0, w, h, 2 * w, 0, jpegamd.CHROMA_YUYV, a.quality)
+                          for i in range(n)]))
         elif source == "i420":
             runs.append((source, jpegamd.SUBSAMPLE_420, "420",
                          [jpegamd.Encoder.ycbcr_image(frames[i].data_ptr(), cbs[i].data_ptr(), crs[i].data_ptr(), w, h, w, w // 2,
