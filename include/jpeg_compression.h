@@ -204,8 +204,8 @@ int32_t jpegamd_encode_planar_batch_async(JpegAmdEncoder *enc, const JpegAmdPlan
 
 /* ---- YCbCr pictures: samples that already ARE Y, Cb and Cr (a video decoder's NV12 / I420 frame, a resizer's output) ----------------
  * The planes are coded as they are given: the samples are taken as JFIF full-range values (Y 0..255, Cb / Cr centred on 128), and
- * NO range or matrix conversion, no subsampling and no filtering is done -- limited-range (16..235) or BT.709 material must be
- * converted by the caller.  The Y plane is width x height; the chroma planes are cw x ch: width x height at JPEGAMD_SUBSAMPLE_444,
+ * NO range or matrix conversion, no subsampling and no filtering is done -- limited-range (16..235) material goes through
+ * jpegamd_encode_ycbcr_range_batch_async below, BT.709 material must be converted by the caller.  The Y plane is width x height; the chroma planes are cw x ch: width x height at JPEGAMD_SUBSAMPLE_444,
  * ceil(width / 2) x ceil(height / 2) at JPEGAMD_SUBSAMPLE_420, ceil(width / 2) x height at JPEGAMD_SUBSAMPLE_422 (I422; NV16 / NV61
  * as byte pairs).  Odd sizes are allowed.
  * 4:2:2 also comes packed, as capture hardware delivers it: ONE plane of 4-byte groups, two pixels each, that holds all three
@@ -237,6 +237,24 @@ typedef struct JpegAmdYCbCrImage {
  * count out of range, a stride too short, pictures of different geometry or layout -- are refused with JPEGAMD_ERR_ARG before the context is read. */
 int32_t jpegamd_encode_ycbcr_batch_async(JpegAmdEncoder *enc, const JpegAmdYCbCrImage *imgs, int32_t count, int32_t subsampling,
                                          void *const *outs_dev, uint64_t out_capacity, void *const *out_sizes_dev, void *stream);
+
+/* The same entry for samples of either range.  Video decoders and capture hardware deliver LIMITED ("video", "studio") range: Y in
+ * 16..235, Cb / Cr in 16..240.  With JPEGAMD_RANGE_LIMITED every sample is expanded to JFIF full range as the tile kernel reads it --
+ * no pass over the planes, no scratch, no extra launch -- by this map (integers, `/` is floor division: clamp, then rescale with
+ * round-half-up):
+ *     Y' = (255 * (clamp(Y, 16, 235) - 16) + 109) / 219        0..255
+ *     C' = (255 * (clamp(C, 16, 240) - 16) + 112) / 224        0..255   (Cb and Cr alike)
+ * so Y 16 -> 0 and 235 -> 255, Cb / Cr 16 -> 0, 128 -> 128 (neutral chroma stays neutral) and 240 -> 255; both maps are monotone and
+ * everything outside the nominal range clamps.  The file is byte for byte the file jpegamd_encode_ycbcr_batch_async writes for the
+ * mapped samples.  Only the RANGE is expanded: the matrix stays BT.601 as JFIF defines it, and BT.709 -> BT.601 matrix conversion is
+ * still the caller's.  With JPEGAMD_RANGE_FULL this IS jpegamd_encode_ycbcr_batch_async: same code path, same files.  Layouts,
+ * subsamplings, context sizing, capacity behaviour, status, statistics and profiling are those of that entry, and so are its argument
+ * checks; any other sample_range is refused with JPEGAMD_ERR_ARG, like them before the context is read. */
+#define JPEGAMD_RANGE_FULL    0   /* samples are JFIF full range: coded as given */
+#define JPEGAMD_RANGE_LIMITED 1   /* Y 16..235, Cb / Cr 16..240: expanded on read by the map above */
+int32_t jpegamd_encode_ycbcr_range_batch_async(JpegAmdEncoder *enc, const JpegAmdYCbCrImage *imgs, int32_t count, int32_t subsampling,
+                                               int32_t sample_range, void *const *outs_dev, uint64_t out_capacity, void *const *out_sizes_dev,
+                                               void *stream);
 
 /* Which kernels follow k_tile_encode for whole pictures (no reference counterpart: a tuning knob, results are byte-identical).
  *   PAIR    k_segment_merge + k_finalize: the tiles' bit strings joined per segment, then stitched behind a kernel boundary;

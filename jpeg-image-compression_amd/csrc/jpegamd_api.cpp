@@ -481,7 +481,7 @@ static int launch_transform(JpegAmdEncoder *e, const ImageDesc &im, bool taps, i
                             void *stream, hipEvent_t *ev = nullptr /*2: begin/end*/, int src = kTileSrcRgb, const PlaneSet *ps = nullptr) {
     TransformOutM to;
     std::memset(&to, 0, sizeof(to));
-    const bool chroma = src == kTileSrcChroma || src == kTileSrcChromaPair || src == kTileSrcChromaQuad;
+    const bool chroma = tile_src_is_chroma(src);
     to.tables = chroma ? e->color.tables_dev : e->tables_dev; to.stamps = e->stamps_dev;
     to.tap_y = ty; to.tap_zz = tzz; to.tap_mask = tmask;
     to.tile_head = e->tile_head; to.tile_over = e->tile_over; to.code_tab = chroma ? e->color.code_tab : e->code_tab;
@@ -518,7 +518,7 @@ static int launch_transform_and_entropy(JpegAmdEncoder *e, const ImageDesc &im, 
     MergeArgs ea;
     std::memset(&ea, 0, sizeof(ea));
     ea.tile_head = e->tile_head; ea.tile_over = e->tile_over;
-    ea.huff = (src == kTileSrcChroma || src == kTileSrcChromaPair || src == kTileSrcChromaQuad) ? e->color.huff : e->huff; ea.num_segs = im.num_segs; ea.segs_per_row = im.segs_per_row; ea.tiles_per_row = im.tiles_per_row;
+    ea.huff = tile_src_is_chroma(src) ? e->color.huff : e->huff; ea.num_segs = im.num_segs; ea.segs_per_row = im.segs_per_row; ea.tiles_per_row = im.tiles_per_row;
     ea.seg_tiles = im.seg_tiles;
     ea.seg_begin = im.seg_begin; ea.seg_end = im.seg_end;
     ea.tiles_per_image = im.batch > 1 ? im.num_tiles : 0;
@@ -1078,8 +1078,10 @@ static int32_t color_batch_alloc(JpegAmdEncoder *e, size_t planes, size_t scans)
 
 // The caller's own chroma (jpegamd_encode_ycbcr_batch_async): cb[i] / cr[i] the planes of picture i (a pair layout: cb[i] alone; a
 // packed 4:2:2 layout: cb[i] is the packed plane -- the picture's y -- and c_stride its row stride).
+// `expand`: the samples are limited range (JPEGAMD_RANGE_LIMITED) -- the Y and the chroma launches take the kTileSrc*Expand twin of their source.
 struct YccSource {
     int32_t layout, c_stride;
+    bool expand;
     const uint8_t *cb[kMaxBatch], *cr[kMaxBatch];
 };
 
@@ -1172,7 +1174,7 @@ static int32_t color_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, const Plan
         PictureStatsArgs ps = {e->tile_head, e->huff, iy.num_tiles, count, 0, 0, pic};
         // a packed 4:2:2 plane: Y is one byte of every pair of the row -- byte 0 (Y Cb Y Cr) or byte 1 (Cb Y Cr Y) -- for EVERY picture
         const bool packed = ycc && is_packed422(ycc->layout);
-        const int ysrc = packed ? kTileSrcLumaPair : src_of(&g0);
+        const int ysrc = packed ? (ycc->expand ? kTileSrcLumaPairExpand : kTileSrcLumaPair) : ((ycc && ycc->expand) ? kTileSrcGrayExpand : src_of(&g0));
         if (packed) iy.weights = ycc->layout == JPEGAMD_CHROMA_UYVY ? 1u : 0u;
         if (stitch_y) {
             if (launch_transform(e, iy, false, nullptr, nullptr, nullptr, stream, ev_y, ysrc, &px)) return JPEGAMD_ERR_HIP;
@@ -1224,14 +1226,17 @@ static int32_t color_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, const Plan
         // a packed plane: launch image i reads byte ((weights >> 8) & 1) + 2 ((weights + i) & 1) of each 4-byte group -- Cb in front of Cr,
         // at bytes 1 and 3 (Y Cb Y Cr) or 0 and 2 (Cb Y Cr Y); bit 0 is the same parity rule
         if (csrc == kTileSrcChromaQuad) ic.weights = (uint32_t)(first & 1) | (ycc->layout == JPEGAMD_CHROMA_YUYV ? 0x100u : 0u);
+        // limited range: the same launch through the twin that expands on read
+        const int lsrc = !(ycc && ycc->expand) ? csrc : csrc == kTileSrcChromaPair ? kTileSrcChromaPairExpand
+                       : csrc == kTileSrcChromaQuad ? kTileSrcChromaQuadExpand : kTileSrcChromaExpand;
         const ScanTarget tc = {c.hdr, 0, 0, &lstats[1 + l], true};
         PictureStatsArgs ps = {e->tile_head, c.huff, ic.num_tiles, n, 1, first, pic};
         if (plan.stitch) {
-            if (launch_transform(e, ic, false, nullptr, nullptr, nullptr, stream, nullptr, csrc)) return JPEGAMD_ERR_HIP;
+            if (launch_transform(e, ic, false, nullptr, nullptr, nullptr, stream, nullptr, lsrc)) return JPEGAMD_ERR_HIP;
             if (launch_picture_stats(ps, stream)) return JPEGAMD_ERR_HIP;
             if (run_stitch(e, ic, outs, slot_bytes, sizes, 1, stream, nullptr, &tc)) return JPEGAMD_ERR_HIP;
         } else {
-            if (launch_transform_and_entropy(e, ic, false, nullptr, nullptr, nullptr, stream, nullptr, csrc)) return JPEGAMD_ERR_HIP;
+            if (launch_transform_and_entropy(e, ic, false, nullptr, nullptr, nullptr, stream, nullptr, lsrc)) return JPEGAMD_ERR_HIP;
             if (launch_picture_stats(ps, stream)) return JPEGAMD_ERR_HIP;
             if (run_finalize_batch(e, ic, outs, slot_bytes, sizes, 1, stream, nullptr, &tc)) return JPEGAMD_ERR_HIP;
         }
@@ -1307,12 +1312,14 @@ extern "C" int32_t jpegamd_encode_planar_batch_async(JpegAmdEncoder *e, const Jp
 }
 
 // `count` YCbCr pictures: the argument checks, then the colour batch with the Y planes as its one-byte source and the caller's chroma.
-extern "C" int32_t jpegamd_encode_ycbcr_batch_async(JpegAmdEncoder *e, const JpegAmdYCbCrImage *imgs, int32_t count, int32_t subsampling,
-                                                    void *const *outs_dev, uint64_t out_capacity, void *const *out_sizes_dev,
-                                                    void *stream_) {
+// sample_range: JPEGAMD_RANGE_FULL -- the samples are coded as given -- or JPEGAMD_RANGE_LIMITED: every launch expands them on read.
+extern "C" int32_t jpegamd_encode_ycbcr_range_batch_async(JpegAmdEncoder *e, const JpegAmdYCbCrImage *imgs, int32_t count, int32_t subsampling,
+                                                          int32_t sample_range, void *const *outs_dev, uint64_t out_capacity,
+                                                          void *const *out_sizes_dev, void *stream_) {
     // the arguments first: nothing of the context is read before they are known to be good
     if (!e || !imgs || !outs_dev || !out_sizes_dev || count < 1 || count > kMaxBatch) return JPEGAMD_ERR_ARG;
     if (!sub_valid(subsampling)) return JPEGAMD_ERR_ARG;
+    if (sample_range != JPEGAMD_RANGE_FULL && sample_range != JPEGAMD_RANGE_LIMITED) return JPEGAMD_ERR_ARG;
     const JpegAmdYCbCrImage &p0 = imgs[0];
     const bool packed = is_packed422(p0.chroma_layout);               // y is the packed plane; cb, cr and c_stride are not looked at
     if (p0.chroma_layout != JPEGAMD_CHROMA_PLANES && p0.chroma_layout != JPEGAMD_CHROMA_CBCR && p0.chroma_layout != JPEGAMD_CHROMA_CRCB && !packed)
@@ -1326,6 +1333,7 @@ extern "C" int32_t jpegamd_encode_ycbcr_batch_async(JpegAmdEncoder *e, const Jpe
     PlaneSet ps = {};
     YccSource ycc = {};
     ycc.layout = p0.chroma_layout; ycc.c_stride = packed ? p0.y_stride : p0.c_stride;
+    ycc.expand = sample_range == JPEGAMD_RANGE_LIMITED;
     uint64_t *sizes[kMaxBatch];
     for (int i = 0; i < count; ++i) {
         const JpegAmdYCbCrImage &g = imgs[i];
@@ -1343,6 +1351,13 @@ extern "C" int32_t jpegamd_encode_ycbcr_batch_async(JpegAmdEncoder *e, const Jpe
     g0.width = p0.width; g0.height = p0.height; g0.row_stride = p0.y_stride; g0.bottom_up = 0;
     g0.channel_order = JPEGAMD_ORDER_GRAY; g0.quality = p0.quality;
     return color_batch(e, g0, ps, count, subsampling, outs_dev, out_capacity, sizes, stream_, &ycc);
+}
+
+// Full-range samples: the entry above with JPEGAMD_RANGE_FULL.
+extern "C" int32_t jpegamd_encode_ycbcr_batch_async(JpegAmdEncoder *e, const JpegAmdYCbCrImage *imgs, int32_t count, int32_t subsampling,
+                                                    void *const *outs_dev, uint64_t out_capacity, void *const *out_sizes_dev,
+                                                    void *stream_) {
+    return jpegamd_encode_ycbcr_range_batch_async(e, imgs, count, subsampling, JPEGAMD_RANGE_FULL, outs_dev, out_capacity, out_sizes_dev, stream_);
 }
 
 // The capacity status is STICKY on the device: every kernel only ORs into it, and it is cleared here, after it was read.

@@ -169,8 +169,17 @@ struct TransformOutM {
 // width (pixels), height and row_stride describe the Y component.  kTileSrcChromaQuad: a chroma scan (chroma tables) whose samples are
 // one byte of every 4-byte group: launch image i reads byte ((weights >> 8) & 1) + 2 ((weights + i) & 1) of the groups of
 // batch_pixels[i]; width is in groups.
+// Limited-range YCbCr (JPEGAMD_RANGE_LIMITED), plain build only: kTileSrcGrayExpand, kTileSrcChromaExpand, kTileSrcChromaPairExpand,
+// kTileSrcLumaPairExpand and kTileSrcChromaQuadExpand read what the source of the same name without "Expand" reads and expand every
+// sample to full range behind the loader -- the Y map with the luma tables, the Cb / Cr map with the chroma tables.
 constexpr int kTileSrcRgb = 0, kTileSrcGray = 1, kTileSrcChroma = 2, kTileSrcPx4 = 3, kTileSrcPlanar = 4, kTileSrcChromaPair = 5,
-              kTileSrcLumaPair = 6, kTileSrcChromaQuad = 7;
+              kTileSrcLumaPair = 6, kTileSrcChromaQuad = 7, kTileSrcGrayExpand = 8, kTileSrcChromaExpand = 9, kTileSrcChromaPairExpand = 10,
+              kTileSrcLumaPairExpand = 11, kTileSrcChromaQuadExpand = 12;
+// (a chroma scan: the chroma constants, code table and Huffman table)
+constexpr bool tile_src_is_chroma(int src) {
+    return src == kTileSrcChroma || src == kTileSrcChromaPair || src == kTileSrcChromaQuad || src == kTileSrcChromaExpand ||
+           src == kTileSrcChromaPairExpand || src == kTileSrcChromaQuadExpand;
+}
 struct TilePlanes {                     // the second and third plane of every picture of a planar launch (its own kernel argument)
     const uint8_t *g[kMaxBatch];
     const uint8_t *b[kMaxBatch];

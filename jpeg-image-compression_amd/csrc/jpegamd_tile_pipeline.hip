@@ -187,6 +187,26 @@ __device__ __forceinline__ f16x8 quad_row8_f16(const uint32_t *d, uint32_t sel) 
     return __builtin_bit_cast(f16x8, packed);
 }
 
+// Limited ("video") range -> JFIF full range, on the two samples a B-fragment dword holds in its 16-bit halves (kExpand; the map of
+// include/jpeg_compression.h, JPEGAMD_RANGE_LIMITED):
+//   Y' = (255 (clamp(Y, 16, 235) - 16) + 109) / 219        C' = (255 (clamp(C, 16, 240) - 16) + 112) / 224
+// With t the clamped sample minus 16 these are (2385 t + 986) >> 11 and (4663 t + 2032) >> 12 for every t (products below 2^20).  No
+// single 16-bit product reproduces them, but the multiplier splits at bit 8 -- 2385 = 9 * 256 + 81, 4663 = 18 * 256 + 55 -- and
+// floor((256 a + b) / 2^s) = floor((a + floor(b / 256)) / 2^(s - 8)):
+//   Y' = (9 t + ((81 t + 986) >> 8)) >> 3                  C' = (18 t + ((55 t + 2032) >> 8)) >> 4
+// Every term stays below 2^15, so both halves go through PACKED 16-bit instructions: a saturating subtract and a minimum (the
+// clamp), two multiply-adds and two shifts -- 6 per dword, 96 per tile and lane.  (tests/range_model.py checks all three forms.)
+template <bool kChroma>
+__device__ __forceinline__ uint32_t expand_range_pk(uint32_t d) {
+    typedef __attribute__((ext_vector_type(2))) uint16_t u16x2;
+    constexpr uint16_t top = kChroma ? 224 : 219, m0 = kChroma ? 55 : 81, a0 = kChroma ? 2032 : 986, m1 = kChroma ? 18 : 9, s1 = kChroma ? 4 : 3;
+    const u16x2 c = __builtin_bit_cast(u16x2, d);
+    const u16x2 t = __builtin_elementwise_min(__builtin_elementwise_sub_sat(c, (u16x2){16, 16}), (u16x2){top, top});
+    const u16x2 u = (t * (u16x2){m0, m0} + (u16x2){a0, a0}) >> (u16x2){8, 8};
+    const u16x2 v = (t * (u16x2){m1, m1} + u) >> (u16x2){s1, s1};
+    return __builtin_bit_cast(uint32_t, v);
+}
+
 // 8 four-byte pixels (8 dwords) -> 8 luma values: ONE dot product per pixel (the ignored byte meets a zero weight), paired by the
 // v_perm of luma_row8_f16 -- 8 v_dot4 + 4 v_perm per 8 pixels.
 __device__ __forceinline__ f16x8 px4_row8_f16(const uint32_t *d, uint32_t w, uint32_t sel) {
@@ -373,8 +393,10 @@ __device__ __forceinline__ void window_or(uint32_t *win, uint32_t rel, uint32_t 
 // kSrc: what a pixel is (kSrcRgb / kSrcPlane / kSrcPx4 / kSrcPlanar / kSrcPair / kSrcQuad; `pl` is read by kSrcPlanar alone); kZBits / kZCode: the ZRL code of the Huffman table in TransformOutM::code_tab
 // (luma: 11 bits 0x7F9; chroma: 10 bits 0x3FA).  A GRAY picture is <kTaps, kSrcPlane>, a chroma plane <false, kSrcPlane, 10, 0x3FA>,
 // one component of an interleaved chroma plane <false, kSrcPair, 10, 0x3FA>, the Y of a packed 4:2:2 plane <false, kSrcPair> and its
-// Cb or Cr <false, kSrcQuad, 10, 0x3FA>.
-template <bool kTaps, int kSrc = kSrcRgb, uint32_t kZBits = kZrlBits, uint32_t kZCode = kZrlCode>
+// Cb or Cr <false, kSrcQuad, 10, 0x3FA>.  kExpand: the samples are limited-range YCbCr and are expanded to full range as they are read
+// (expand_range_pk: the Y map with the luma tables, the Cb / Cr map with the chroma tables); for the five one-byte sources of a YCbCr
+// batch alone, and off in every other instantiation, whose code it does not touch.
+template <bool kTaps, int kSrc = kSrcRgb, uint32_t kZBits = kZrlBits, uint32_t kZCode = kZrlCode, bool kExpand = false>
 __global__ __launch_bounds__(64 * kWavesT) __attribute__((amdgpu_waves_per_eu(JPEGAMD_TILE_WAVES, JPEGAMD_TILE_WAVES)))
 void k_tile_encode(const ImageDesc im, const TransformOutM out, const TileSched sch, const typename PlanesArg<kSrc>::type pl) {
     __shared__ __attribute__((aligned(16))) uint32_t s_afrag[kAFragWords];
@@ -658,6 +680,17 @@ void k_tile_encode(const ImageDesc im, const TransformOutM out, const TileSched 
                         pk[j >> 1] = (uint32_t)luma_clamped(im, im.batch_pixels[tg.img], px0 + j, py0 + 2 * s + h) |
                                      ((uint32_t)luma_clamped(im, im.batch_pixels[tg.img], px0 + j + 1, py0 + 2 * s + h) << 16);
                 }
+                bfrag[s] = __builtin_bit_cast(f16x8, pk);
+            }
+        }
+        if constexpr (kExpand) {               // limited range -> full range: ONE place behind both loaders, so the stash below holds the mapped samples
+            static_assert(!kTaps && (kSrc == kSrcPlane || kSrc == kSrcPair || kSrc == kSrcQuad), "range expansion is for the sources of a YCbCr batch");
+            typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {
+                u32x4 pk = __builtin_bit_cast(u32x4, bfrag[s]);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) pk[j] = expand_range_pk<kZBits != kZrlBits>(pk[j]);
                 bfrag[s] = __builtin_bit_cast(f16x8, pk);
             }
         }
@@ -1229,7 +1262,8 @@ int launch_tile_transform(const ImageDesc &im, const TransformOutM &out, bool ta
     sch.tpr_magic = magic > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)magic;   // tiles_per_row == 1: the correction step makes up for it
     const dim3 grid(wgs), block(64 * kWavesT);
     const NoPlanes pl;
-    if (src == kTileSrcPx4 || src == kTileSrcPlanar || src == kTileSrcChromaPair || src == kTileSrcLumaPair || src == kTileSrcChromaQuad) {
+    if (src == kTileSrcPx4 || src == kTileSrcPlanar || src == kTileSrcChromaPair || src == kTileSrcLumaPair || src == kTileSrcChromaQuad ||
+        (src >= kTileSrcGrayExpand && src <= kTileSrcChromaQuadExpand)) {
 #ifdef JPEGAMD_STAMPED_TU
         return (int)hipErrorInvalidValue;                                   // (these sources exist in the plain build alone)
 #else
@@ -1240,7 +1274,18 @@ int launch_tile_transform(const ImageDesc &im, const TransformOutM &out, bool ta
         const auto pair = k_tile_encode<false, kSrcPair, kZrlBitsChroma, kZrlCodeChroma>;
         const auto ypair = k_tile_encode<false, kSrcPair>;
         const auto quad = k_tile_encode<false, kSrcQuad, kZrlBitsChroma, kZrlCodeChroma>;
-        if (src == kTileSrcChromaPair) hipExtLaunchKernelGGL(pair, grid, block, 0, (hipStream_t)stream, e0, e1, 0, im, out, sch, pl);
+        // limited-range YCbCr: the same five sources with the range map behind the loader
+        const auto xgray = k_tile_encode<false, kSrcPlane, kZrlBits, kZrlCode, true>;
+        const auto xplane = k_tile_encode<false, kSrcPlane, kZrlBitsChroma, kZrlCodeChroma, true>;
+        const auto xpair = k_tile_encode<false, kSrcPair, kZrlBitsChroma, kZrlCodeChroma, true>;
+        const auto xypair = k_tile_encode<false, kSrcPair, kZrlBits, kZrlCode, true>;
+        const auto xquad = k_tile_encode<false, kSrcQuad, kZrlBitsChroma, kZrlCodeChroma, true>;
+        if (src == kTileSrcGrayExpand) hipExtLaunchKernelGGL(xgray, grid, block, 0, (hipStream_t)stream, e0, e1, 0, im, out, sch, pl);
+        else if (src == kTileSrcChromaExpand) hipExtLaunchKernelGGL(xplane, grid, block, 0, (hipStream_t)stream, e0, e1, 0, im, out, sch, pl);
+        else if (src == kTileSrcChromaPairExpand) hipExtLaunchKernelGGL(xpair, grid, block, 0, (hipStream_t)stream, e0, e1, 0, im, out, sch, pl);
+        else if (src == kTileSrcLumaPairExpand) hipExtLaunchKernelGGL(xypair, grid, block, 0, (hipStream_t)stream, e0, e1, 0, im, out, sch, pl);
+        else if (src == kTileSrcChromaQuadExpand) hipExtLaunchKernelGGL(xquad, grid, block, 0, (hipStream_t)stream, e0, e1, 0, im, out, sch, pl);
+        else if (src == kTileSrcChromaPair) hipExtLaunchKernelGGL(pair, grid, block, 0, (hipStream_t)stream, e0, e1, 0, im, out, sch, pl);
         else if (src == kTileSrcLumaPair) hipExtLaunchKernelGGL(ypair, grid, block, 0, (hipStream_t)stream, e0, e1, 0, im, out, sch, pl);
         else if (src == kTileSrcChromaQuad) hipExtLaunchKernelGGL(quad, grid, block, 0, (hipStream_t)stream, e0, e1, 0, im, out, sch, pl);
         else if (src == kTileSrcPx4) hipExtLaunchKernelGGL(px4, grid, block, 0, (hipStream_t)stream, e0, e1, 0, im, out, sch, pl);

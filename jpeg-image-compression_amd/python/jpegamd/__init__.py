@@ -43,6 +43,7 @@ class PlanarImage(C.Structure):
 
 CHROMA_PLANES, CHROMA_CBCR, CHROMA_CRCB = 0, 1, 2           # JPEGAMD_CHROMA_*
 CHROMA_YUYV, CHROMA_UYVY = 4, 5                             # packed 4:2:2: the picture's y is the packed plane (3 stays invalid)
+RANGE_FULL, RANGE_LIMITED = 0, 1                            # JPEGAMD_RANGE_*: JFIF full range / video range (Y 16..235, Cb Cr 16..240), expanded on read
 
 
 class YCbCrImage(C.Structure):
@@ -115,6 +116,7 @@ def _load() -> C.CDLL:
         "jpegamd_encode_color_batch_async": (i32, [vp, C.POINTER(Image), i32, i32, C.POINTER(C.c_void_p), u64, C.POINTER(C.c_void_p), vp]),
         "jpegamd_encode_planar_batch_async": (i32, [vp, C.POINTER(PlanarImage), i32, i32, C.POINTER(C.c_void_p), u64, C.POINTER(C.c_void_p), vp]),
         "jpegamd_encode_ycbcr_batch_async": (i32, [vp, C.POINTER(YCbCrImage), i32, i32, C.POINTER(C.c_void_p), u64, C.POINTER(C.c_void_p), vp]),
+        "jpegamd_encode_ycbcr_range_batch_async": (i32, [vp, C.POINTER(YCbCrImage), i32, i32, i32, C.POINTER(C.c_void_p), u64, C.POINTER(C.c_void_p), vp]),
         "jpegamd_debug_chroma_groups": (i32, [i32, i32, i32, i32, i32, i32, i32, vp]),
         "jpegamd_debug_chroma_quant_table": (i32, [i32, vp]),
         "jpegamd_debug_chroma_mfma_consts": (i32, [i32, vp, vp, vp, vp, vp, vp]),
@@ -128,7 +130,8 @@ def _load() -> C.CDLL:
     }
     for name, (res, args) in sig.items():
         if name in ("jpegamd_encoder_set_pipeline", "jpegamd_gather_streams", "jpegamd_debug_mfma_offsets", "jpegamd_encode_color_batch_async",
-                    "jpegamd_debug_chroma_groups", "jpegamd_encode_planar_batch_async", "jpegamd_encode_ycbcr_batch_async") and os.environ.get("JPEGAMD_LIB") and not hasattr(lib, name):
+                    "jpegamd_debug_chroma_groups", "jpegamd_encode_planar_batch_async", "jpegamd_encode_ycbcr_batch_async",
+                    "jpegamd_encode_ycbcr_range_batch_async") and os.environ.get("JPEGAMD_LIB") and not hasattr(lib, name):
             continue                                              # (A/B tooling: a variant build of an older round)
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = res, args
@@ -144,7 +147,7 @@ EXPORTED = ("jpegamd_encoder_create jpegamd_encoder_destroy jpegamd_max_jfif_byt
             "jpegamd_encode_rows_async jpegamd_export_segments jpegamd_import_segments jpegamd_finalize_async "
             "jpegamd_max_jfif_bytes_color jpegamd_encode_color_async jpegamd_encode_bmp_memory_color jpegamd_debug_chroma_quant_table "
             "jpegamd_debug_chroma_mfma_consts jpegamd_debug_color_profile jpegamd_encode_color_batch_async "
-            "jpegamd_encode_planar_batch_async jpegamd_encode_ycbcr_batch_async").split()
+            "jpegamd_encode_planar_batch_async jpegamd_encode_ycbcr_batch_async jpegamd_encode_ycbcr_range_batch_async").split()
 
 
 def quant_table(quality: int = 50):
@@ -512,9 +515,19 @@ def _ycbcr_layout(y, cb, cr, subsampling, order):
     return n, h, w, y_stride, c_stride, layout
 
 
-def encode_ycbcr_batch(y, cb, cr=None, quality: int = 0, subsampling: int = SUBSAMPLE_420, order: str = "cbcr") -> list:
+def _sample_range(sample_range) -> int:
+    """"full" / "limited" -> JPEGAMD_RANGE_*; anything else is a ValueError."""
+    if not isinstance(sample_range, str) or sample_range not in ("full", "limited"):
+        raise ValueError(f'sample_range must be "full" or "limited", not {sample_range!r}')
+    return RANGE_LIMITED if sample_range == "limited" else RANGE_FULL
+
+
+def encode_ycbcr_batch(y, cb, cr=None, quality: int = 0, subsampling: int = SUBSAMPLE_420, order: str = "cbcr",
+                       sample_range: str = "full") -> list:
     """N pictures whose samples already ARE Y, Cb and Cr (JFIF full range; no range or matrix conversion is done) -> N colour JFIF
     files through jpegamd_encode_ycbcr_batch_async, read where they lie: no RGB detour, no chroma-plane pass.
+    sample_range="limited": the samples are video range (Y 16..235, Cb / Cr 16..240, as decoders deliver them) and are expanded to
+    full range as the kernel reads them (jpegamd_encode_ycbcr_range_batch_async: no pass over the planes); the matrix stays BT.601.
     `y` is a uint8 DEVICE tensor [N, H, W]; `cb` and `cr` are [N, ch, cw] with (ch, cw) = (H, W) at SUBSAMPLE_444,
     (ceil(H / 2), ceil(W / 2)) at SUBSAMPLE_420 (I420; YV12 by swapping them) and (H, ceil(W / 2)) at SUBSAMPLE_422 (I422).  With
     cr=None, `cb` is [N, ch, cw, 2]: byte pairs Cb Cr (NV12; NV16 at 4:2:2; NV24 at 4:4:4), or Cr Cb with order="crcb" (NV21 / NV61 /
@@ -527,15 +540,16 @@ def encode_ycbcr_batch(y, cb, cr=None, quality: int = 0, subsampling: int = SUBS
         jpegamd.encode_ycbcr_batch(y, cbcr)
 
     and a stack of frames [N, 3 * H // 2, W] slices the same way: f[:, :H] and f[:, H:].unflatten(2, (W // 2, 2))."""
+    rng = _sample_range(sample_range)
     n, h, w, y_stride, c_stride, layout = _ycbcr_layout(y, cb, cr, subsampling, order)
     tensors = [y, cb] + ([cr] if cr is not None else [])
     if any(not x.is_cuda or x.device != y.device for x in tensors):
         raise ValueError("encode_ycbcr_batch needs device tensors on one device")
     return _encode_ycbcr_images(y.device, n, h, w, subsampling, lambda i: Encoder.ycbcr_image(
-        y[i].data_ptr(), cb[i].data_ptr(), cr[i].data_ptr() if cr is not None else 0, w, h, y_stride, c_stride, layout, quality))
+        y[i].data_ptr(), cb[i].data_ptr(), cr[i].data_ptr() if cr is not None else 0, w, h, y_stride, c_stride, layout, quality), rng)
 
 
-def _encode_ycbcr_images(device, n, h, w, subsampling, image):
+def _encode_ycbcr_images(device, n, h, w, subsampling, image, sample_range: int = RANGE_FULL):
     """`n` YCbCr pictures of one geometry, picture i described by image(i), through the per-device context in calls of at most
     MAX_BATCH -> their files."""
     import torch
@@ -560,7 +574,7 @@ def _encode_ycbcr_images(device, n, h, w, subsampling, image):
             outs = [out[i].data_ptr() for i in range(k)]
             size_ptrs = [sizes.data_ptr() + 8 * i for i in range(k)]
             imgs = [image(b0 + i) for i in range(k)]
-            enc.encode_ycbcr_batch_async(imgs, subsampling, outs, cap, size_ptrs, stream)
+            enc.encode_ycbcr_batch_async(imgs, subsampling, outs, cap, size_ptrs, stream, sample_range)
             enc.finish()
             got = sizes[:k].cpu().tolist()
             files += [bytes(out[i, :got[i]].cpu().numpy().tobytes()) for i in range(k)]
@@ -590,17 +604,19 @@ def _yuyv_layout(frames, order):
     return n, h, w, stride, (CHROMA_YUYV if order == "yuyv" else CHROMA_UYVY)
 
 
-def encode_yuyv_batch(frames, quality: int = 0, order: str = "yuyv") -> list:
+def encode_yuyv_batch(frames, quality: int = 0, order: str = "yuyv", sample_range: str = "full") -> list:
     """N packed 4:2:2 frames -> N colour JFIF files at SUBSAMPLE_422 through jpegamd_encode_ycbcr_batch_async, read where they
     lie: the samples are coded as given (JFIF full range; no range or matrix conversion, no filter).
     `frames` is a uint8 DEVICE tensor [N, H, W, 2], W even: groups of four bytes Y0 Cb Y1 Cr for two pixels (YUY2), or Cb Y0 Cr Y1
     with order="uyvy".  Rows and pictures may be strided; the two bytes of a pixel and the pixels of a row are packed.  Batches of
-    more than MAX_BATCH frames go as several calls; the per-device context of encode_tensor is used."""
+    more than MAX_BATCH frames go as several calls; the per-device context of encode_tensor is used.  sample_range="limited": video-range
+    samples, expanded to full range on read as in encode_ycbcr_batch."""
+    rng = _sample_range(sample_range)
     n, h, w, stride, layout = _yuyv_layout(frames, order)
     if not frames.is_cuda:
         raise ValueError("encode_yuyv_batch needs a device tensor")
     return _encode_ycbcr_images(frames.device, n, h, w, SUBSAMPLE_422, lambda i: Encoder.ycbcr_image(
-        frames[i].data_ptr(), 0, 0, w, h, stride, 0, layout, quality))
+        frames[i].data_ptr(), 0, 0, w, h, stride, 0, layout, quality), rng)
 
 
 class BatchStats(C.Structure):
@@ -692,13 +708,21 @@ class Encoder:
         CHROMA_UYVY: `y_stride` is its row stride, the chroma arguments are ignored)."""
         return YCbCrImage(y_ptr or None, cb_ptr or None, cr_ptr or None, width, height, y_stride, c_stride, chroma_layout, quality)
 
-    def encode_ycbcr_batch_async(self, imgs, subsampling: int, out_ptrs, out_cap: int, size_ptrs, stream: int = 0):
+    def encode_ycbcr_batch_async(self, imgs, subsampling: int, out_ptrs, out_cap: int, size_ptrs, stream: int = 0,
+                                 sample_range: int = RANGE_FULL):
         """The colour files of `len(imgs)` YCbCr pictures of one geometry (jpegamd_encode_ycbcr_batch_async); the context as for
-        encode_color_batch_async."""
+        encode_color_batch_async.  sample_range: RANGE_FULL, or RANGE_LIMITED for video-range samples, which go through
+        jpegamd_encode_ycbcr_range_batch_async and are expanded on read."""
         n = len(imgs)
         arr = (YCbCrImage * n)(*imgs)
         outs = (C.c_void_p * n)(*[C.c_void_p(p) for p in out_ptrs])
         sizes = (C.c_void_p * n)(*[C.c_void_p(p) for p in size_ptrs])
+        if int(sample_range) != RANGE_FULL:          # (the full-range call keeps to the older entry: a variant library without the new one still serves it)
+            rc = lib.jpegamd_encode_ycbcr_range_batch_async(self._h, arr, n, int(subsampling), int(sample_range), outs, out_cap, sizes,
+                                                            C.c_void_p(stream))
+            if rc:
+                raise JpegAmdError(rc, "jpegamd_encode_ycbcr_range_batch_async")
+            return
         rc = lib.jpegamd_encode_ycbcr_batch_async(self._h, arr, n, int(subsampling), outs, out_cap, sizes, C.c_void_p(stream))
         if rc:
             raise JpegAmdError(rc, "jpegamd_encode_ycbcr_batch_async")

@@ -13,6 +13,11 @@ loop), through jpegamd_encode_ycbcr_batch_async -- the files are those of `rgb`,
 by commas (--source rgb,i420,nv12) run one after the other in ONE process: one session, one set of pictures.
 `i422` (three planes) and `yuyv` (one packed YUY2 plane per picture) are the 4:2:2 sources, derived the same way.
 --subsampling {420,444,422} picks ONE subsampling for the rgb loops (default: 4:2:0 and 4:4:4 in turn, as before).
+--range limited (i420, nv12, i422, yuyv) takes the same samples as limited ("video") range: the calls go through
+jpegamd_encode_ycbcr_range_batch_async with JPEGAMD_RANGE_LIMITED, which expands them on read; the line then carries "range".  With
+--convert it also times what that replaces, in the same run: the range map as a pass of its own over the planes (a torch table
+lookup, lut[plane.long()], into preallocated planes: "convert_us_per_picture") and the full-range encode of the planes it wrote
+("mapped_full_us_per_picture", whose files must be the limited ones: "mapped_bytes_equal").
 
 With --layout {hwc,chw,rgba} (and --batch N, default 8) the pictures are device tensors stored that way -- [N, H, W, 3], [N, 3, H, W],
 [N, H, W, 4] -- and go through the entry that reads them where they lie, 4:2:0 only.  Every call is timed as a whole between two
@@ -45,6 +50,9 @@ def main() -> None:
     ap.add_argument("--batch", type=int, default=None, help="pictures per call through the colour batch entry (1 .. 32)")
     ap.add_argument("--source", default="rgb", help="rgb (default), i420, nv12, i422, yuyv, or several separated by commas: what the batch loop reads")
     ap.add_argument("--subsampling", choices=("420", "444", "422"), default=None, help="rgb: this subsampling alone (default: 420, then 444)")
+    ap.add_argument("--range", choices=("full", "limited"), default="full", dest="sample_range",
+                    help="i420 / nv12 / i422 / yuyv: the samples are full range (default) or limited range, expanded on read")
+    ap.add_argument("--convert", action="store_true", help="--range limited: also time the map as a separate pass + the full-range encode")
     ap.add_argument("--layout", choices=("hwc", "chw", "rgba"), default=None, help="device tensors stored this way, read where they lie")
     ap.add_argument("--rounds", type=int, default=5, help="--layout: medians taken (each of --steps calls)")
     ap.add_argument("--repack", action="store_true", help="--layout chw: also time permute + packed encode")
@@ -63,6 +71,10 @@ def main() -> None:
     sources = a.source.split(",")
     if any(s not in ("rgb", "i420", "nv12", "i422", "yuyv") for s in sources):
         sys.exit("--source takes rgb, i420, nv12, i422, yuyv or a comma-separated list of them")
+    if a.sample_range != "full" and "rgb" in sources:
+        sys.exit("--range limited is for the YCbCr sources (i420, nv12, i422, yuyv)")
+    if a.convert and a.sample_range != "limited":
+        sys.exit("--convert needs --range limited")
     if a.batch is not None or sources != ["rgb"]:
         run_batch(a, jpegamd, torch, dev, sources)
         return
@@ -160,25 +172,30 @@ def run_batch(a, jpegamd, torch, dev, sources=("rgb",)) -> None:
             del y
         ys2 = packed[:, :, :, 0].contiguous()
     for source in sources:
+        # a YCbCr source: its tensors, and the descriptors of pictures stored in tensors of those shapes (--convert writes a second set)
         if source == "rgb":
-            runs += [(source, sub, name, None) for sub, name in rgb_subsamplings(a, jpegamd)]
+            runs += [(source, sub, name, None, None) for sub, name in rgb_subsamplings(a, jpegamd)]
         elif source == "i422":
-            runs.append((source, jpegamd.SUBSAMPLE_422, "422",
-                         [jpegamd.Encoder.ycbcr_image(ys2[i].data_ptr(), cbs2[i].data_ptr(), crs2[i].data_ptr(), w, h, w, w // 2,
-                                                      jpegamd.CHROMA_PLANES, a.quality) for i in range(n)]))
+            runs.append((source, jpegamd.SUBSAMPLE_422, "422", (ys2, cbs2, crs2), lambda t: [
+                jpegamd.Encoder.ycbcr_image(t[0][i].data_ptr(), t[1][i].data_ptr(), t[2][i].data_ptr(), w, h, w, w // 2,
+                                            jpegamd.CHROMA_PLANES, a.quality) for i in range(n)]))
         elif source == "yuyv":
-            runs.append((source, jpegamd.SUBSAMPLE_422, "422",
-                         [jpegamd.Encoder.ycbcr_image(packed[i].data_ptr(), 0, 0, w, h, 2 * w, 0, jpegamd.CHROMA_YUYV, a.quality)
-                          for i in range(n)]))
+            runs.append((source, jpegamd.SUBSAMPLE_422, "422", (packed,), lambda t: [
+                jpegamd.Encoder.ycbcr_image(t[0][i].data_ptr(), 0, 0, w, h, 2 * w, 0, jpegamd.CHROMA_YUYV, a.quality) for i in range(n)]))
         elif source == "i420":
-            runs.append((source, jpegamd.SUBSAMPLE_420, "420",
-                         [jpegamd.Encoder.ycbcr_image(frames[i].data_ptr(), cbs[i].data_ptr(), crs[i].data_ptr(), w, h, w, w // 2,
-                                                      jpegamd.CHROMA_PLANES, a.quality) for i in range(n)]))
+            runs.append((source, jpegamd.SUBSAMPLE_420, "420", (frames, cbs, crs), lambda t: [
+                jpegamd.Encoder.ycbcr_image(t[0][i].data_ptr(), t[1][i].data_ptr(), t[2][i].data_ptr(), w, h, w, w // 2,
+                                            jpegamd.CHROMA_PLANES, a.quality) for i in range(n)]))
         else:
-            runs.append((source, jpegamd.SUBSAMPLE_420, "420",
-                         [jpegamd.Encoder.ycbcr_image(frames[i].data_ptr(), frames[i, h:].data_ptr(), 0, w, h, w, w,
-                                                      jpegamd.CHROMA_CBCR, a.quality) for i in range(n)]))
-    for source, sub, name, ycc in runs:
+            runs.append((source, jpegamd.SUBSAMPLE_420, "420", (frames,), lambda t: [
+                jpegamd.Encoder.ycbcr_image(t[0][i].data_ptr(), t[0][i, h:].data_ptr(), 0, w, h, w, w,
+                                            jpegamd.CHROMA_CBCR, a.quality) for i in range(n)]))
+    limited = a.sample_range == "limited"
+    if a.convert:
+        lut_y = torch.tensor([(255 * (min(max(v, 16), 235) - 16) + 109) // 219 for v in range(256)], dtype=torch.uint8, device=dev)
+        lut_c = torch.tensor([(255 * (min(max(v, 16), 240) - 16) + 112) // 224 for v in range(256)], dtype=torch.uint8, device=dev)
+    for source, sub, name, tensors, describe in runs:
+        ycc = describe(tensors) if describe else None
         cap = jpegamd.max_jfif_bytes_color(w, h, sub)
         outs = [torch.empty(cap, dtype=torch.uint8, device=dev) for _ in range(n)]
         sizes = torch.zeros(n, dtype=torch.int64, device=dev)
@@ -187,7 +204,8 @@ def run_batch(a, jpegamd, torch, dev, sources=("rgb",)) -> None:
         if ycc is None:
             call = lambda: enc.encode_color_batch_async(descs, sub, out_ptrs, cap, size_ptrs, stream)
         else:
-            call = lambda: enc.encode_ycbcr_batch_async(ycc, sub, out_ptrs, cap, size_ptrs, stream)
+            call = lambda: enc.encode_ycbcr_batch_async(ycc, sub, out_ptrs, cap, size_ptrs, stream,
+                                                        **({"sample_range": jpegamd.RANGE_LIMITED} if limited else {}))
         for _ in range(a.warmup):
             call()
         enc.finish()
@@ -198,11 +216,63 @@ def run_batch(a, jpegamd, torch, dev, sources=("rgb",)) -> None:
         totals = [enc.profile(i).ns_total for i in range(a.steps)]
         enc.set_profiling(0)
         t = statistics.median(totals)
-        print(json.dumps({"source": source, "subsampling": name, "width": w, "height": h, "batch": n, "quality": a.quality, "kind": a.kind,
-                          "steps": a.steps, "bytes": sizes.cpu().tolist(), "entropy_bits": st.entropy_bits,
-                          "ns_total_median": int(t), "us_per_picture": round(t / n / 1000, 1),
-                          "gpixels_per_s": round(n * w * h / t, 2)}))
+        line = {"source": source, "subsampling": name, "width": w, "height": h, "batch": n, "quality": a.quality, "kind": a.kind,
+                "steps": a.steps, "bytes": sizes.cpu().tolist(), "entropy_bits": st.entropy_bits,
+                "ns_total_median": int(t), "us_per_picture": round(t / n / 1000, 1),
+                "gpixels_per_s": round(n * w * h / t, 2)}
+        if limited:
+            line["range"] = "limited"
+        if a.convert:
+            line.update(time_convert(a, jpegamd, torch, enc, source, tensors, describe, (lut_y, lut_c), h, sub, out_ptrs, cap, size_ptrs,
+                                     sizes, stream, n))
+        print(json.dumps(line))
         del outs
+
+
+def time_convert(a, jpegamd, torch, enc, source, tensors, describe, luts, h, sub, out_ptrs, cap, size_ptrs, sizes, stream, n):
+    """What expanding on read replaces: the range map as a pass over the source's planes into planes of the same shape (one call's
+    worth, between two events on the stream), then the full-range encode of those."""
+    lut_y, lut_c = luts
+    limited_bytes = sizes.cpu().tolist()
+    mapped = tuple(torch.empty_like(t) for t in tensors)
+
+    def convert():
+        if source == "yuyv":                                     # [N, H, W, 2]: Y in byte 0 of a pixel, Cb / Cr in byte 1
+            mapped[0][..., 0] = lut_y[tensors[0][..., 0].long()]
+            mapped[0][..., 1] = lut_c[tensors[0][..., 1].long()]
+        elif source == "nv12":                                   # [N, 3 H / 2, W]: H rows of Y, then the Cb Cr pairs
+            mapped[0][:, :h] = lut_y[tensors[0][:, :h].long()]
+            mapped[0][:, h:] = lut_c[tensors[0][:, h:].long()]
+        else:                                                    # three planes (i420: the Y rows of the frames)
+            rows = h if source == "i420" else tensors[0].shape[1]
+            mapped[0][:, :rows] = lut_y[tensors[0][:, :rows].long()]
+            mapped[1][:] = lut_c[tensors[1].long()]
+            mapped[2][:] = lut_c[tensors[2].long()]
+
+    for _ in range(2):
+        convert()
+    torch.cuda.synchronize()
+    times = []
+    for _ in range(max(3, a.steps // 5)):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        convert()
+        e1.record()
+        torch.cuda.synchronize()
+        times.append(e0.elapsed_time(e1) * 1000.0 / n)
+    ycc = describe(mapped)
+    call = lambda: enc.encode_ycbcr_batch_async(ycc, sub, out_ptrs, cap, size_ptrs, stream)
+    for _ in range(a.warmup):
+        call()
+    enc.finish()
+    enc.set_profiling(a.steps)
+    for _ in range(a.steps):
+        call()
+    enc.finish()
+    t = statistics.median(enc.profile(i).ns_total for i in range(a.steps))
+    enc.set_profiling(0)
+    return {"convert_us_per_picture": round(statistics.median(times), 1), "mapped_full_us_per_picture": round(t / n / 1000, 1),
+            "mapped_bytes_equal": sizes.cpu().tolist() == limited_bytes}
 
 
 def run_layout(a, jpegamd, torch, dev) -> None:
