@@ -319,6 +319,8 @@ int32_t jpegamd_debug_color_profile(JpegAmdEncoder *enc, int32_t slot, uint64_t 
  * whose hi-chain LUT sums all stay below grp_thr skips that group's quantiser entirely; lo_bound (may be NULL) is the largest
  * magnitude the lo chain can add to a site of the group -- grp_thr has it taken off. */
 int32_t jpegamd_debug_group_thresholds(int32_t quality, float *grp_thr, float *lo_bound);
+/* The same for the colour files' chroma table (as jpegamd_debug_chroma_mfma_consts is to jpegamd_debug_mfma_consts). */
+int32_t jpegamd_debug_chroma_group_thresholds(int32_t quality, float *grp_thr, float *lo_bound);
 /* ... and what the uncentred matrix operand (luma 0 .. 255 as binary16 subnormals) adds: zoff[64] / qadd[64] = bias + zoff by zigzag
  * position, the DC row's surplus in accumulator units, the accumulator scale.  Any pointer may be NULL. */
 int32_t jpegamd_debug_mfma_offsets(int32_t quality, float *zoff, float *qadd, float *dc_off, float *scale);

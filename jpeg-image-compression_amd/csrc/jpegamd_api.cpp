@@ -187,6 +187,20 @@ extern "C" int32_t jpegamd_debug_chroma_mfma_consts(int32_t quality, float *qmul
     return JPEGAMD_OK;
 }
 
+// jpegamd_debug_group_thresholds for the chroma table (the sibling of jpegamd_debug_chroma_mfma_consts).  Host-only.
+extern "C" int32_t jpegamd_debug_chroma_group_thresholds(int32_t quality, float *grp_thr /*[4 groups][2 lane halves]*/, float *lo_bound /*same shape, may be NULL*/) {
+    uint8_t t[64];
+    if (!grp_thr) return JPEGAMD_ERR_ARG;
+    MfmaTables *mt = new (std::nothrow) MfmaTables;
+    if (!mt) return JPEGAMD_ERR_HIP;
+    chroma_quant_table_for_quality(quality, t);
+    derive_mfma_tables(t, mt, nullptr);
+    std::memcpy(grp_thr, mt->grp_thr, sizeof(mt->grp_thr));
+    if (lo_bound) std::memcpy(lo_bound, mt->lo_bound, sizeof(mt->lo_bound));
+    delete mt;
+    return JPEGAMD_OK;
+}
+
 // The colour subsamplings: 4:4:4, 4:2:0 (chroma halved both ways) and 4:2:2 (halved along the row alone).
 static bool sub_valid(int sub) { return sub == JPEGAMD_SUBSAMPLE_444 || sub == JPEGAMD_SUBSAMPLE_420 || sub == JPEGAMD_SUBSAMPLE_422; }
 static int chroma_mode(int sub) { return sub == JPEGAMD_SUBSAMPLE_420 ? kChromaMode420 : (sub == JPEGAMD_SUBSAMPLE_422 ? kChromaMode422 : kChromaMode444); }

@@ -120,6 +120,7 @@ def _load() -> C.CDLL:
         "jpegamd_debug_chroma_groups": (i32, [i32, i32, i32, i32, i32, i32, i32, vp]),
         "jpegamd_debug_chroma_quant_table": (i32, [i32, vp]),
         "jpegamd_debug_chroma_mfma_consts": (i32, [i32, vp, vp, vp, vp, vp, vp]),
+        "jpegamd_debug_chroma_group_thresholds": (i32, [i32, vp, vp]),
         "jpegamd_debug_color_profile": (i32, [vp, i32, vp]),
         "jpegamd_parse_bmp": (i32, [vp, u64, C.POINTER(Image), C.POINTER(u64)]),
         "jpegamd_gather_streams": (i32, [vp, i32, i32, i32, vp, u64, i32, vp, vp, u64, vp]),
@@ -146,7 +147,7 @@ EXPORTED = ("jpegamd_encoder_create jpegamd_encoder_destroy jpegamd_max_jfif_byt
             "jpegamd_encode_bmp_memory jpegamd_parse_bmp jpegamd_encode_files jpegamd_gather_streams "
             "jpegamd_encode_rows_async jpegamd_export_segments jpegamd_import_segments jpegamd_finalize_async "
             "jpegamd_max_jfif_bytes_color jpegamd_encode_color_async jpegamd_encode_bmp_memory_color jpegamd_debug_chroma_quant_table "
-            "jpegamd_debug_chroma_mfma_consts jpegamd_debug_color_profile jpegamd_encode_color_batch_async "
+            "jpegamd_debug_chroma_mfma_consts jpegamd_debug_chroma_group_thresholds jpegamd_debug_color_profile jpegamd_encode_color_batch_async "
             "jpegamd_encode_planar_batch_async jpegamd_encode_ycbcr_batch_async jpegamd_encode_ycbcr_range_batch_async").split()
 
 
@@ -196,11 +197,12 @@ def mfma_consts(quality: int = 50):
     return dict(qmul=qmul, qthr=qthr, bias=bias, delta=delta, zoff=zoff, qadd=qadd, dc_off=float(dc_off[0]), scale=float(scale[0]))
 
 
-def group_thresholds(quality: int = 50, with_lo_bound: bool = False):
-    """float32 [4][2]: zero threshold of coefficient group G for lane half h, on the hi chain (with_lo_bound: and the lo chain's bound)."""
+def group_thresholds(quality: int = 50, with_lo_bound: bool = False, chroma: bool = False):
+    """float32 [4][2]: zero threshold of coefficient group G for lane half h, on the hi chain (with_lo_bound: and the lo chain's bound);
+    chroma: for the colour files' chroma table."""
     import numpy as np
     t, lo = np.zeros(8, np.float32), np.zeros(8, np.float32)
-    lib.jpegamd_debug_group_thresholds(quality, t.ctypes.data, lo.ctypes.data)
+    (lib.jpegamd_debug_chroma_group_thresholds if chroma else lib.jpegamd_debug_group_thresholds)(quality, t.ctypes.data, lo.ctypes.data)
     return (t.reshape(4, 2), lo.reshape(4, 2)) if with_lo_bound else t.reshape(4, 2)
 
 

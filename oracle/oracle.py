@@ -125,6 +125,20 @@ def dct_blocks(blocks: np.ndarray) -> np.ndarray:
     return out.reshape(n, 8, 8)
 
 
+def quantise_blocks(coeffs: np.ndarray, table: np.ndarray) -> np.ndarray:
+    """float32 DCT coefficients [N,8,8] (as dct_blocks gives them) -> int16 [N,64] in zigzag order: the reference's quantiser
+    (quantization.c:34-36) with `table` (uint8[64], raster order), then its zigzag scan."""
+    d = np.ascontiguousarray(coeffs, np.float32)
+    n = d.shape[0]
+    d = np.ascontiguousarray(d.reshape(n * 8, 8))                 # a PW=8, PH=8n image
+    qt = np.ascontiguousarray(table, np.uint8)
+    q = np.zeros((n * 8, 8), np.int16)
+    _lib.oracle_quant_image(d.ctypes.data, 8, n * 8, qt.ctypes.data, q.ctypes.data)
+    zz = np.zeros((n, 64), np.int16)
+    _lib.oracle_zigzag_image(q.ctypes.data, 8, n * 8, zz.ctypes.data)
+    return zz
+
+
 def rle_symbols(zigzag: np.ndarray):
     zz = np.ascontiguousarray(zigzag, np.int16)
     nb = zz.shape[0]

@@ -167,7 +167,8 @@ def test_group_zero_thresholds_are_safe(jpegamd):
     hi accumulator chain alone, |hi| < thr in every site; the lo chain adds at most lo_bound, and the add that joins them rounds
     once: |a| <= (thr + lo_bound)(1 + 2^-24).  For each site of the group, in float32 exactly as the kernel evaluates it,
     fl(a * qmul + bias) must stay inside (qthr, 1) for a = +-that (monotone in a), so floor() is 0 and fract() is above the flag
-    threshold.  lo_bound itself is checked against the split of the LUT products."""
+    threshold.  lo_bound itself is checked against the split of the LUT products.  For the luma table and for the colour files' chroma
+    table (jpegamd_debug_chroma_group_thresholds)."""
     f32 = np.float32
     zz = [0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
           35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63]
@@ -179,9 +180,9 @@ def test_group_zero_thresholds_are_safe(jpegamd):
         K = np.outer(lut[:, u], lut[:, v]).reshape(64)
         lo = np.rint((K - np.rint(K * 2048.0) / 2048.0) * 4194304.0)            # in units of 2^-22
         lo_true[z >> 4, (z >> 3) & 1] = max(lo_true[z >> 4, (z >> 3) & 1], scale * 128.0 * (np.abs(lo).sum() + abs(lo.sum())) / 4194304.0)
-    for q in (50, 10, 90, 1, 100):
-        c = jpegamd.mfma_consts(q)
-        thr, lob = jpegamd.group_thresholds(q, with_lo_bound=True)
+    for chroma, q in [(t, q) for t in (False, True) for q in (50, 10, 90, 1, 100)]:       # the luma table, then the colour files' chroma table
+        c = jpegamd.chroma_mfma_consts(q) if chroma else jpegamd.mfma_consts(q)
+        thr, lob = jpegamd.group_thresholds(q, with_lo_bound=True, chroma=chroma)
         assert (lob.astype(np.float64) >= lo_true).all()
         assert (thr > 0).all() and (lob > 0).all() and (lob <= scale * 2.0 * 1.001).all()    # 64 terms x |p| <= 128 x |lo| <= 1024 units of 2^-22
         for g in range(4):
@@ -191,7 +192,7 @@ def test_group_zero_thresholds_are_safe(jpegamd):
                     z = 16 * g + 8 * h + j
                     for a in (t, -t, np.nextafter(t, f32(0)), -np.nextafter(t, f32(0))):
                         zc = f32(np.float64(a) * np.float64(c["qmul"][z]) + np.float64(f32(c["qadd"][z])))      # one rounding, like v_fma_f32
-                        assert f32(c["qthr"][z]) < zc < f32(1.0), (q, g, h, j, float(a), float(zc))
+                        assert f32(c["qthr"][z]) < zc < f32(1.0), (chroma, q, g, h, j, float(a), float(zc))
         if 10 <= q <= 90:
             assert thr[0].min() <= thr[3].max()                     # coarser quantisation higher up: larger zero zone (Q=1 / 100: every step is 255 / 1)
 
