@@ -407,11 +407,14 @@ void k_tile_encode(const ImageDesc im, const TransformOutM out, const TileSched 
     __shared__ float s_qstep[64];
     __shared__ float s_cos[64];
     __shared__ uint32_t s_zz[64];               // zigzag position -> raster index (exact-order path)
-    // The tile's centred luma (binary16, exact), kept for the exact-order path: row r of block b at word r * 132 + b * 4
+    // The tile's luma (the B fragments: Y in 16-bit halves), stashed for the exact-order path by a tile that HAS an event, at the head
+    // of that path: row r of block b at word r * 132 + b * 4
     // (528-byte rows: the four 1 KiB stores of a wave and the 64 two-byte reads of one block are conflict-free).
     // Reloading the pixels from HBM instead made every exact-order event wait for vmcnt(0), i.e. for the
     // prefetched rows of the NEXT tile as well: ~40 % of a tile's time per event (tools/stamp_profile_tile.py).
-    // After the exact-order phase the same words hold the tile's item list.
+    // After the exact-order phase the same words hold the tile's item list -- and go on holding it through the wave's next tile when
+    // that tile has no event (the stash written for every tile was 3.2 % of a wave's time, for one reader in six tiles at Q=50:
+    // profiles/stash_on_demand.txt).
     __shared__ __attribute__((aligned(16))) uint32_t s_pix[kWavesT][kStageWords];
     __shared__ __attribute__((aligned(16))) uint32_t s_win[kWavesT][kWinWords];      // per wave: the tile's record + bit window; all zero between tiles
     static_assert(kWinWords == 4 * 64, "the exact-order path parks the 64 terms of four coefficients in the (idle, zero) bit window and zeroes it again");
@@ -695,15 +698,7 @@ void k_tile_encode(const ImageDesc im, const TransformOutM out, const TileSched 
             }
         }
         TSTAMP(1);   // wait for the prefetched rows + luma
-        {
-        uint32_t sl;                           // (an opaque lane id: the stash addresses are not worth four registers across the whole loop)
-        asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(sl));
-        // word (sl >> 5) * 132 + (sl & 31) * 4, as bytes: 16 sl + 16 (sl >> 5) -- two shifts, an and, an add (the product with 132 compiled to a v_mul_lo_u32)
-        uint32_t *const sp0 = reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(&s_pix[wave][0]) + ((sl << 4) + ((sl >> 1) & 16u)));
-#pragma unroll
-        for (int s = 0; s < 4; ++s) *reinterpret_cast<f16x8 *>(&sp0[2 * s * 132]) = bfrag[s];     // (one address, four immediate offsets)
-        }
-        TSTAMP(2);   // luma -> LDS
+        TSTAMP(2);   // luma -> LDS: nothing since the stash is made on demand (4. below); the stamp keeps the slot numbering
         if (kTaps && active && out.tap_y) {
             int8_t *ty = out.tap_y + ((size_t)by * im.blocks_w + bx) * 64;
             typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
@@ -858,6 +853,14 @@ void k_tile_encode(const ImageDesc im, const TransformOutM out, const TileSched 
             // every event (and the zigzag table was a global load): three memory round trips per event behind a vmcnt(0).
             int el;
             asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(el));
+            {   // The luma stash, made HERE: only a tile with an event reads it (at Q=50 one tile in six), and the B fragments are still in
+                // their registers.  Until now s_pix[wave] held the item list of the wave's previous tile; the stores are ordinary LDS
+                // stores, ordered by the compiler (and by the in-order LDS queue of a wave) ahead of the reads through pix_lane.
+                // word (el >> 5) * 132 + (el & 31) * 4, as bytes: 16 el + 16 (el >> 5) -- two shifts, an and, an add (the product with 132 compiled to a v_mul_lo_u32)
+                uint32_t *const sp0 = reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(&s_pix[wave][0]) + (((uint32_t)el << 4) + (((uint32_t)el >> 1) & 16u)));
+#pragma unroll
+                for (int s = 0; s < 4; ++s) *reinterpret_cast<f16x8 *>(&sp0[2 * s * 132]) = bfrag[s];     // (one address, four immediate offsets)
+            }
             const uint32_t *pix_lane = &s_pix[wave][(el >> 3) * 132 + ((el & 7) >> 1)];
             float *const terms = reinterpret_cast<float *>(&s_win[wave][0]);      // (the window is idle -- and all zero -- until the coder: zeroed again below)
             const float *const my_terms = terms + (el >> 4) * 64;       // lanes 16 e .. 16 e + 15 add up event e of a batch
