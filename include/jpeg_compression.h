@@ -220,7 +220,8 @@ int32_t jpegamd_encode_planar_batch_async(JpegAmdEncoder *enc, const JpegAmdPlan
 typedef struct JpegAmdYCbCrImage {
     const void *y, *cb, *cr;      /* DEVICE pointers, top row first */
     int32_t width, height;        /* of the Y plane, 1..65535 */
-    int32_t y_stride, c_stride;   /* bytes between rows; y_stride >= width; c_stride >= cw (PLANES) or >= 2*cw (CBCR / CRCB); YUYV / UYVY: y_stride >= 4*cw */
+    int32_t y_stride, c_stride;   /* bytes between rows; y_stride >= width; c_stride >= cw (PLANES) or >= 2*cw (CBCR / CRCB); YUYV / UYVY: y_stride >= 4*cw
+                                   * (16-bit samples, jpegamd_encode_ycbcr_samples_batch_async: twice these) */
     int32_t chroma_layout;        /* JPEGAMD_CHROMA_* */
     int32_t quality;
 } JpegAmdYCbCrImage;
@@ -255,6 +256,33 @@ int32_t jpegamd_encode_ycbcr_batch_async(JpegAmdEncoder *enc, const JpegAmdYCbCr
 int32_t jpegamd_encode_ycbcr_range_batch_async(JpegAmdEncoder *enc, const JpegAmdYCbCrImage *imgs, int32_t count, int32_t subsampling,
                                                int32_t sample_range, void *const *outs_dev, uint64_t out_capacity, void *const *out_sizes_dev,
                                                void *stream);
+
+/* The same entry for 10-bit samples in 16-bit words: what a Main10 / AV1 10-bit / VP9 profile 2 decoder delivers -- P010 from hardware
+ * decoders, yuv420p10le (I010) from software ones.  Every sample is a little-endian 16-bit word w, narrowed to the 8-bit sample that is
+ * coded as the tile kernel reads it -- no pass over the planes, no scratch, no extra launch.  Its 10-bit value v follows from
+ * sample_format:
+ *     JPEGAMD_SAMPLES_8       one byte per sample: this entry IS jpegamd_encode_ycbcr_range_batch_async, same code path, same files
+ *     JPEGAMD_SAMPLES_10_MSB  v = w >> 6, the low six bits ignored   (P010 / P210 / P410 and their planar twins; P012 / P016 read at 10 bits)
+ *     JPEGAMD_SAMPLES_10_LSB  v = min(w, 1023)                       (I010 / I210 / I410, yuv4xxp10le)
+ * and the coded sample from v (integers, `/` is floor division):
+ *     JPEGAMD_RANGE_FULL      s  = min(255, (v + 2) >> 2)                             Y, Cb, Cr alike; 512 -> 128
+ *     JPEGAMD_RANGE_LIMITED   Y' = (255 * (clamp(v, 64, 940) - 64) + 438) / 876       64 -> 0, 940 -> 255
+ *                             C' = (255 * (clamp(v, 64, 960) - 64) + 448) / 896       64 -> 0, 512 -> 128, 960 -> 255
+ * One rounding from ten bits, not two through an 8-bit limited-range sample: every one of the 256 output levels is reached.  The
+ * file is byte for byte the file jpegamd_encode_ycbcr_batch_async writes for the mapped 8-bit planes.
+ * The JpegAmdYCbCrImage is the same and strides stay in BYTES: with a 16-bit format y_stride >= 2 * width, c_stride >= 2 * cw
+ * (JPEGAMD_CHROMA_PLANES: I010 / I210 / I410) or >= 4 * cw (JPEGAMD_CHROMA_CBCR / _CRCB: P010 / P210 / P410 and their Cr-first twins:
+ * one plane of 16-bit pairs).  All three subsamplings and both ranges are taken.  The packed layouts (JPEGAMD_CHROMA_YUYV / _UYVY)
+ * with a 16-bit format -- Y210 -- are NOT taken: JPEGAMD_ERR_ARG.  Any pointer alignment and any stride is taken, odd addresses
+ * included (planes on dword boundaries with strides that are multiples of 4 below 2^24 take the fast loader; everything else is read
+ * byte by byte).  An unknown sample_format is refused with JPEGAMD_ERR_ARG like every other bad argument of that entry, before the
+ * context is read; context sizing, capacity behaviour, status, statistics and profiling are those of jpegamd_encode_color_batch_async. */
+#define JPEGAMD_SAMPLES_8      0   /* one byte per sample */
+#define JPEGAMD_SAMPLES_10_MSB 1   /* 16-bit words, the 10-bit value in the HIGH bits (P010): v = w >> 6 */
+#define JPEGAMD_SAMPLES_10_LSB 2   /* 16-bit words, the 10-bit value in the LOW bits (I010): v = min(w, 1023) */
+int32_t jpegamd_encode_ycbcr_samples_batch_async(JpegAmdEncoder *enc, const JpegAmdYCbCrImage *imgs, int32_t count, int32_t subsampling,
+                                                 int32_t sample_range, int32_t sample_format, void *const *outs_dev, uint64_t out_capacity,
+                                                 void *const *out_sizes_dev, void *stream);
 
 /* Which kernels follow k_tile_encode for whole pictures (no reference counterpart: a tuning knob, results are byte-identical).
  *   PAIR    k_segment_merge + k_finalize: the tiles' bit strings joined per segment, then stitched behind a kernel boundary;

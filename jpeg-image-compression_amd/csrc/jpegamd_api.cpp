@@ -1093,11 +1093,17 @@ static int32_t color_batch_alloc(JpegAmdEncoder *e, size_t planes, size_t scans)
 // The caller's own chroma (jpegamd_encode_ycbcr_batch_async): cb[i] / cr[i] the planes of picture i (a pair layout: cb[i] alone; a
 // packed 4:2:2 layout: cb[i] is the packed plane -- the picture's y -- and c_stride its row stride).
 // `expand`: the samples are limited range (JPEGAMD_RANGE_LIMITED) -- the Y and the chroma launches take the kTileSrc*Expand twin of their source.
+// `format`: JPEGAMD_SAMPLES_* -- with a 16-bit format the Y and the chroma launches read 16-bit words through the kTileSrc*16 sources, which
+// narrow every sample on read (either range), and ImageDesc::weights carries the alignment shift.
 struct YccSource {
     int32_t layout, c_stride;
     bool expand;
+    int32_t format;
     const uint8_t *cb[kMaxBatch], *cr[kMaxBatch];
 };
+
+// The right shift that leaves the 10-bit value of a 16-bit sample word (JPEGAMD_SAMPLES_10_MSB: 6; _LSB: 0, then clamped to 1023).
+static uint32_t depth_shift(int32_t format) { return format == JPEGAMD_SAMPLES_10_MSB ? 6u : 0u; }
 
 // The colour files of a batch whose arguments are known to be good: g0 describes every picture, ps holds their pixels.
 // `ycc` (a YCbCr batch): g0 / px are the Y planes as a GRAY picture, the chroma scans read the caller's planes -- no
@@ -1188,8 +1194,11 @@ static int32_t color_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, const Plan
         PictureStatsArgs ps = {e->tile_head, e->huff, iy.num_tiles, count, 0, 0, pic};
         // a packed 4:2:2 plane: Y is one byte of every pair of the row -- byte 0 (Y Cb Y Cr) or byte 1 (Cb Y Cr Y) -- for EVERY picture
         const bool packed = ycc && is_packed422(ycc->layout);
-        const int ysrc = packed ? (ycc->expand ? kTileSrcLumaPairExpand : kTileSrcLumaPair) : ((ycc && ycc->expand) ? kTileSrcGrayExpand : src_of(&g0));
+        const bool wide = ycc && ycc->format != JPEGAMD_SAMPLES_8;    // 16-bit words: the shift that leaves the 10-bit value rides in weights bits 16..20
+        const int ysrc = wide ? (ycc->expand ? kTileSrcGray16Expand : kTileSrcGray16)
+                       : packed ? (ycc->expand ? kTileSrcLumaPairExpand : kTileSrcLumaPair) : ((ycc && ycc->expand) ? kTileSrcGrayExpand : src_of(&g0));
         if (packed) iy.weights = ycc->layout == JPEGAMD_CHROMA_UYVY ? 1u : 0u;
+        if (wide) iy.weights = depth_shift(ycc->format) << 16;
         if (stitch_y) {
             if (launch_transform(e, iy, false, nullptr, nullptr, nullptr, stream, ev_y, ysrc, &px)) return JPEGAMD_ERR_HIP;
             if (launch_picture_stats(ps, stream)) return JPEGAMD_ERR_HIP;
@@ -1206,10 +1215,12 @@ static int32_t color_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, const Plan
     pimg.pixels = c.bplanes;
     int csrc = kTileSrcChroma;
     bool ycc_aligned = true;
+    const bool wide = ycc && ycc->format != JPEGAMD_SAMPLES_8;
     if (ycc) {
         pimg.pixels = ycc->cb[0]; pimg.row_stride = ycc->c_stride;
         const bool pair = ycc->layout != JPEGAMD_CHROMA_PLANES;      // (or a packed plane: one pointer per picture as well)
         if (pair) csrc = is_packed422(ycc->layout) ? kTileSrcChromaQuad : kTileSrcChromaPair;
+        if (wide) csrc = pair ? kTileSrcChromaPair16 : kTileSrcChroma16;
         uintptr_t bits = 0;
         for (int i = 0; i < count; ++i) bits |= (uintptr_t)ycc->cb[i] | (pair ? 0 : (uintptr_t)ycc->cr[i]);
         ycc_aligned = (bits & 3u) == 0;
@@ -1224,7 +1235,7 @@ static int32_t color_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, const Plan
         for (int i = 0; i < n; ++i) {
             const int j = first + i;                                   // the plane's index in the whole call: picture j / 2, Cb (even) or Cr (odd)
             if (!ycc) ic.batch_pixels[i] = c.bplanes + (size_t)j * plane_bytes;
-            else if (csrc != kTileSrcChroma) ic.batch_pixels[i] = ycc->cb[j / 2];
+            else if (csrc != kTileSrcChroma && csrc != kTileSrcChroma16) ic.batch_pixels[i] = ycc->cb[j / 2];
             else ic.batch_pixels[i] = (j & 1) ? ycc->cr[j / 2] : ycc->cb[j / 2];
             outs[i] = c.bscans + (size_t)(first + i) * slot_bytes;
             sizes[i] = c_size + first + i;
@@ -1240,9 +1251,13 @@ static int32_t color_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, const Plan
         // a packed plane: launch image i reads byte ((weights >> 8) & 1) + 2 ((weights + i) & 1) of each 4-byte group -- Cb in front of Cr,
         // at bytes 1 and 3 (Y Cb Y Cr) or 0 and 2 (Cb Y Cr Y); bit 0 is the same parity rule
         if (csrc == kTileSrcChromaQuad) ic.weights = (uint32_t)(first & 1) | (ycc->layout == JPEGAMD_CHROMA_YUYV ? 0x100u : 0u);
+        // 16-bit words: a pair plane keeps the parity rule in bit 0, the alignment shift rides in bits 16..20
+        if (csrc == kTileSrcChroma16) ic.weights = depth_shift(ycc->format) << 16;
+        if (csrc == kTileSrcChromaPair16) ic.weights = (uint32_t)((first & 1) ^ (ycc->layout == JPEGAMD_CHROMA_CRCB ? 1 : 0)) | (depth_shift(ycc->format) << 16);
         // limited range: the same launch through the twin that expands on read
         const int lsrc = !(ycc && ycc->expand) ? csrc : csrc == kTileSrcChromaPair ? kTileSrcChromaPairExpand
-                       : csrc == kTileSrcChromaQuad ? kTileSrcChromaQuadExpand : kTileSrcChromaExpand;
+                       : csrc == kTileSrcChromaQuad ? kTileSrcChromaQuadExpand : csrc == kTileSrcChroma16 ? kTileSrcChroma16Expand
+                       : csrc == kTileSrcChromaPair16 ? kTileSrcChromaPair16Expand : kTileSrcChromaExpand;
         const ScanTarget tc = {c.hdr, 0, 0, &lstats[1 + l], true};
         PictureStatsArgs ps = {e->tile_head, c.huff, ic.num_tiles, n, 1, first, pic};
         if (plan.stitch) {
@@ -1325,29 +1340,34 @@ extern "C" int32_t jpegamd_encode_planar_batch_async(JpegAmdEncoder *e, const Jp
     return color_batch(e, g0, ps, count, subsampling, outs_dev, out_capacity, sizes, stream_);
 }
 
-// `count` YCbCr pictures: the argument checks, then the colour batch with the Y planes as its one-byte source and the caller's chroma.
+// `count` YCbCr pictures: the argument checks, then the colour batch with the Y planes as its one-sample source and the caller's chroma.
 // sample_range: JPEGAMD_RANGE_FULL -- the samples are coded as given -- or JPEGAMD_RANGE_LIMITED: every launch expands them on read.
-extern "C" int32_t jpegamd_encode_ycbcr_range_batch_async(JpegAmdEncoder *e, const JpegAmdYCbCrImage *imgs, int32_t count, int32_t subsampling,
-                                                          int32_t sample_range, void *const *outs_dev, uint64_t out_capacity,
-                                                          void *const *out_sizes_dev, void *stream_) {
+// sample_format: JPEGAMD_SAMPLES_8, or 10-bit samples in 16-bit words (MSB- or LSB-aligned), which every launch narrows on read.
+extern "C" int32_t jpegamd_encode_ycbcr_samples_batch_async(JpegAmdEncoder *e, const JpegAmdYCbCrImage *imgs, int32_t count, int32_t subsampling,
+                                                            int32_t sample_range, int32_t sample_format, void *const *outs_dev,
+                                                            uint64_t out_capacity, void *const *out_sizes_dev, void *stream_) {
     // the arguments first: nothing of the context is read before they are known to be good
     if (!e || !imgs || !outs_dev || !out_sizes_dev || count < 1 || count > kMaxBatch) return JPEGAMD_ERR_ARG;
     if (!sub_valid(subsampling)) return JPEGAMD_ERR_ARG;
     if (sample_range != JPEGAMD_RANGE_FULL && sample_range != JPEGAMD_RANGE_LIMITED) return JPEGAMD_ERR_ARG;
+    if (sample_format != JPEGAMD_SAMPLES_8 && sample_format != JPEGAMD_SAMPLES_10_MSB && sample_format != JPEGAMD_SAMPLES_10_LSB) return JPEGAMD_ERR_ARG;
+    const int64_t bps = sample_format == JPEGAMD_SAMPLES_8 ? 1 : 2;   // bytes per sample
     const JpegAmdYCbCrImage &p0 = imgs[0];
     const bool packed = is_packed422(p0.chroma_layout);               // y is the packed plane; cb, cr and c_stride are not looked at
     if (p0.chroma_layout != JPEGAMD_CHROMA_PLANES && p0.chroma_layout != JPEGAMD_CHROMA_CBCR && p0.chroma_layout != JPEGAMD_CHROMA_CRCB && !packed)
         return JPEGAMD_ERR_ARG;
     if (packed && subsampling != JPEGAMD_SUBSAMPLE_422) return JPEGAMD_ERR_ARG;
+    if (packed && bps != 1) return JPEGAMD_ERR_ARG;                   // (Y210: not taken)
     if (p0.width <= 0 || p0.height <= 0 || p0.width > 65535 || p0.height > 65535) return JPEGAMD_ERR_ARG;
     const bool pair = p0.chroma_layout != JPEGAMD_CHROMA_PLANES && !packed;
     int cw, ch;
     chroma_dims(p0.width, p0.height, subsampling, &cw, &ch);
-    if (packed ? p0.y_stride < 4 * cw : (p0.y_stride < p0.width || p0.c_stride < (pair ? 2 * cw : cw))) return JPEGAMD_ERR_ARG;
+    if (packed ? p0.y_stride < 4 * cw : (p0.y_stride < bps * p0.width || p0.c_stride < bps * (pair ? 2 * cw : cw))) return JPEGAMD_ERR_ARG;
     PlaneSet ps = {};
     YccSource ycc = {};
     ycc.layout = p0.chroma_layout; ycc.c_stride = packed ? p0.y_stride : p0.c_stride;
     ycc.expand = sample_range == JPEGAMD_RANGE_LIMITED;
+    ycc.format = sample_format;
     uint64_t *sizes[kMaxBatch];
     for (int i = 0; i < count; ++i) {
         const JpegAmdYCbCrImage &g = imgs[i];
@@ -1365,6 +1385,14 @@ extern "C" int32_t jpegamd_encode_ycbcr_range_batch_async(JpegAmdEncoder *e, con
     g0.width = p0.width; g0.height = p0.height; g0.row_stride = p0.y_stride; g0.bottom_up = 0;
     g0.channel_order = JPEGAMD_ORDER_GRAY; g0.quality = p0.quality;
     return color_batch(e, g0, ps, count, subsampling, outs_dev, out_capacity, sizes, stream_, &ycc);
+}
+
+// One byte per sample: the entry above with JPEGAMD_SAMPLES_8.
+extern "C" int32_t jpegamd_encode_ycbcr_range_batch_async(JpegAmdEncoder *e, const JpegAmdYCbCrImage *imgs, int32_t count, int32_t subsampling,
+                                                          int32_t sample_range, void *const *outs_dev, uint64_t out_capacity,
+                                                          void *const *out_sizes_dev, void *stream_) {
+    return jpegamd_encode_ycbcr_samples_batch_async(e, imgs, count, subsampling, sample_range, JPEGAMD_SAMPLES_8, outs_dev, out_capacity,
+                                                    out_sizes_dev, stream_);
 }
 
 // Full-range samples: the entry above with JPEGAMD_RANGE_FULL.

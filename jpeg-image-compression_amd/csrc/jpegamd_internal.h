@@ -172,13 +172,20 @@ struct TransformOutM {
 // Limited-range YCbCr (JPEGAMD_RANGE_LIMITED), plain build only: kTileSrcGrayExpand, kTileSrcChromaExpand, kTileSrcChromaPairExpand,
 // kTileSrcLumaPairExpand and kTileSrcChromaQuadExpand read what the source of the same name without "Expand" reads and expand every
 // sample to full range behind the loader -- the Y map with the luma tables, the Cb / Cr map with the chroma tables.
+// 10-bit YCbCr in 16-bit little-endian words (JPEGAMD_SAMPLES_10_MSB / _LSB), plain build only: kTileSrcGray16 (luma tables) and
+// kTileSrcChroma16 (chroma tables) read a plane of 16-bit samples, kTileSrcChromaPair16 one component of a plane of 16-bit pairs by the
+// parity rule of kTileSrcChromaPair (ImageDesc::weights bit 0); width counts samples / pairs, row_stride bytes.  Every sample is
+// narrowed to 8 bits behind the loader -- the full-range map, or with the "Expand" twin the limited-range map, Y by the luma tables
+// and Cb / Cr by the chroma tables.  ImageDesc::weights bits 16..20 carry the right shift that leaves the 10-bit value (6 or 0).
 constexpr int kTileSrcRgb = 0, kTileSrcGray = 1, kTileSrcChroma = 2, kTileSrcPx4 = 3, kTileSrcPlanar = 4, kTileSrcChromaPair = 5,
               kTileSrcLumaPair = 6, kTileSrcChromaQuad = 7, kTileSrcGrayExpand = 8, kTileSrcChromaExpand = 9, kTileSrcChromaPairExpand = 10,
-              kTileSrcLumaPairExpand = 11, kTileSrcChromaQuadExpand = 12;
+              kTileSrcLumaPairExpand = 11, kTileSrcChromaQuadExpand = 12, kTileSrcGray16 = 13, kTileSrcChroma16 = 14, kTileSrcChromaPair16 = 15,
+              kTileSrcGray16Expand = 16, kTileSrcChroma16Expand = 17, kTileSrcChromaPair16Expand = 18;
 // (a chroma scan: the chroma constants, code table and Huffman table)
 constexpr bool tile_src_is_chroma(int src) {
     return src == kTileSrcChroma || src == kTileSrcChromaPair || src == kTileSrcChromaQuad || src == kTileSrcChromaExpand ||
-           src == kTileSrcChromaPairExpand || src == kTileSrcChromaQuadExpand;
+           src == kTileSrcChromaPairExpand || src == kTileSrcChromaQuadExpand || src == kTileSrcChroma16 || src == kTileSrcChromaPair16 ||
+           src == kTileSrcChroma16Expand || src == kTileSrcChromaPair16Expand;
 }
 struct TilePlanes {                     // the second and third plane of every picture of a planar launch (its own kernel argument)
     const uint8_t *g[kMaxBatch];

@@ -153,7 +153,13 @@ static_assert(kPassItems * (27 + 3 * (int)kZrlBitsChroma) / 32 + 6 <= kWinStr &&
 //   kSrcQuad   one plane of 4-byte groups (the same packed 4:2:2 plane, as its chroma scans see it), of which a launch image takes
 //              ONE byte per group: launch image i reads byte ((weights >> 8) & 1) + 2 ((weights + i) & 1) -- Cb or Cr by the parity
 //              rule of kSrcPair, at bytes 1 / 3 (Y Cb Y Cr) or 0 / 2 (Cb Y Cr Y)
-constexpr int kSrcRgb = 0, kSrcPlane = 1, kSrcPx4 = 2, kSrcPlanar = 3, kSrcPair = 4, kSrcQuad = 5;
+//   kSrcPlane16 one plane of 16-bit little-endian samples (the Y or a chroma plane of a 10-bit YCbCr batch): kSrcPair's loader -- 16
+//              bytes per lane-row, whose four dwords ARE the B fragment -- then the depth map (narrow_depth_pk) behind it
+//   kSrcPair16 one plane of 16-bit pairs (Cb Cr Cb Cr ...: P010 chroma), of which a launch image takes ONE component by kSrcPair's
+//              parity rule: 32 bytes per lane-row on kSrcQuad's schedule, one v_perm per B-fragment dword, then the depth map
+//              Both read the samples' alignment from ImageDesc::weights bits 16..20 (the right shift that leaves the 10-bit value: 6 for
+//              MSB-aligned words, 0 for LSB-aligned ones); kSrcPair16 keeps the parity in bit 0.
+constexpr int kSrcRgb = 0, kSrcPlane = 1, kSrcPx4 = 2, kSrcPlanar = 3, kSrcPair = 4, kSrcQuad = 5, kSrcPlane16 = 6, kSrcPair16 = 7;
 // The kernel's last argument: the G and B planes for kSrcPlanar, an empty struct -- no kernel-argument bytes, so the offsets of
 // the hidden arguments behind it stay where they were -- for every other source.
 struct NoPlanes {};
@@ -205,6 +211,34 @@ __device__ __forceinline__ uint32_t expand_range_pk(uint32_t d) {
     const u16x2 u = (t * (u16x2){m0, m0} + (u16x2){a0, a0}) >> (u16x2){8, 8};
     const u16x2 v = (t * (u16x2){m1, m1} + u) >> (u16x2){s1, s1};
     return __builtin_bit_cast(uint32_t, v);
+}
+
+// 10-bit samples in 16-bit words -> the 8-bit samples that are coded, on the two words a B-fragment dword holds (the maps of
+// include/jpeg_compression.h, JPEGAMD_SAMPLES_10_*).  `sh2` is the alignment shift in BOTH halves (6 : 6 or 0 : 0), wave-uniform.
+//   full range       s  = min(255, (min(w >> sh, 1023) + 2) >> 2)                         5 packed instructions per dword
+//   limited, chroma  t = min(max(w >> sh, 64) - 64, 896);  C' = (255 t + 448) / 896 = (18 t + ((55 t + 8136) >> 8)) >> 6
+//                    -- the 8-bit map's multiplier 4663 = 18 * 256 + 55 again, two bits further down; every term below 2^16: 7 packed
+//   limited, luma    t = min(max(w >> sh, 64) - 64, 876);  Y' = (255 t + 438) / 876 = (19077 t + 33000) >> 16
+//                    -- no split of the multiplier into two 16-bit terms reproduces it, so each sample takes one 24-bit multiply-add
+//                    (product below 2^24) and ONE v_perm pairs byte 2 of the two products: 3 packed + 2 + 2 + 1
+// (the clamp to 1023 of an LSB-aligned word is implied by the limited maps' upper clamp.  tests/depth_model.py checks every form
+// against the definition for every input.)
+template <bool kLimited, bool kChroma>
+__device__ __forceinline__ uint32_t narrow_depth_pk(uint32_t d, uint32_t sh2) {
+    typedef __attribute__((ext_vector_type(2))) uint16_t u16x2;
+    const u16x2 v = __builtin_bit_cast(u16x2, d) >> __builtin_bit_cast(u16x2, sh2);
+    if constexpr (!kLimited) {
+        const u16x2 s = (__builtin_elementwise_min(v, (u16x2){1023, 1023}) + (u16x2){2, 2}) >> (u16x2){2, 2};
+        return __builtin_bit_cast(uint32_t, __builtin_elementwise_min(s, (u16x2){255, 255}));
+    } else if constexpr (kChroma) {
+        const u16x2 t = __builtin_elementwise_min(__builtin_elementwise_sub_sat(v, (u16x2){64, 64}), (u16x2){896, 896});
+        const u16x2 u = (t * (u16x2){55, 55} + (u16x2){8136, 8136}) >> (u16x2){8, 8};
+        return __builtin_bit_cast(uint32_t, (t * (u16x2){18, 18} + u) >> (u16x2){6, 6});
+    } else {
+        const uint32_t t = __builtin_bit_cast(uint32_t, __builtin_elementwise_min(__builtin_elementwise_sub_sat(v, (u16x2){64, 64}), (u16x2){876, 876}));
+        const uint32_t p0 = __umul24(t & 0xFFFFu, 19077u) + 33000u, p1 = __umul24(t >> 16, 19077u) + 33000u;
+        return __builtin_amdgcn_perm(p1, p0, 0x0C060C02u);
+    }
 }
 
 // 8 four-byte pixels (8 dwords) -> 8 luma values: ONE dot product per pixel (the ignored byte meets a zero weight), paired by the
@@ -275,6 +309,21 @@ __device__ __forceinline__ int quad_clamped(const ImageDesc &im, const uint8_t *
     x = min(x, im.width - 1);
     y = min(y, im.height - 1);
     return (int)row_ptr(im, pixels, y)[4 * (size_t)x + (size_t)byte];
+}
+
+// The 16-bit word of sample (x, y) of a plane of 16-bit samples / of component `comp` of a plane of 16-bit pairs, with the edge
+// clamp: plane_clamped and pair_clamped at twice the bytes.  The two bytes are read separately: any address is taken.
+__device__ __forceinline__ uint32_t plane16_clamped(const ImageDesc &im, const uint8_t *pixels, int x, int y) {
+    x = min(x, im.width - 1);
+    y = min(y, im.height - 1);
+    const uint8_t *p = row_ptr(im, pixels, y) + 2 * (size_t)x;
+    return (uint32_t)p[0] | ((uint32_t)p[1] << 8);
+}
+__device__ __forceinline__ uint32_t pair16_clamped(const ImageDesc &im, const uint8_t *pixels, int comp, int x, int y) {
+    x = min(x, im.width - 1);
+    y = min(y, im.height - 1);
+    const uint8_t *p = row_ptr(im, pixels, y) + 4 * (size_t)x + 2 * (size_t)comp;
+    return (uint32_t)p[0] | ((uint32_t)p[1] << 8);
 }
 
 struct TileSched {            // division-free launch geometry, filled by launch_tile_transform
@@ -390,12 +439,13 @@ __device__ __forceinline__ void window_or(uint32_t *win, uint32_t rel, uint32_t 
     if (third) atomicOr(&win[w + 2], __builtin_amdgcn_alignbit(lo, 0u, sh));
 }
 
-// kSrc: what a pixel is (kSrcRgb / kSrcPlane / kSrcPx4 / kSrcPlanar / kSrcPair / kSrcQuad; `pl` is read by kSrcPlanar alone); kZBits / kZCode: the ZRL code of the Huffman table in TransformOutM::code_tab
+// kSrc: what a pixel is (kSrcRgb / kSrcPlane / kSrcPx4 / kSrcPlanar / kSrcPair / kSrcQuad / kSrcPlane16 / kSrcPair16; `pl` is read by kSrcPlanar alone); kZBits / kZCode: the ZRL code of the Huffman table in TransformOutM::code_tab
 // (luma: 11 bits 0x7F9; chroma: 10 bits 0x3FA).  A GRAY picture is <kTaps, kSrcPlane>, a chroma plane <false, kSrcPlane, 10, 0x3FA>,
 // one component of an interleaved chroma plane <false, kSrcPair, 10, 0x3FA>, the Y of a packed 4:2:2 plane <false, kSrcPair> and its
 // Cb or Cr <false, kSrcQuad, 10, 0x3FA>.  kExpand: the samples are limited-range YCbCr and are expanded to full range as they are read
 // (expand_range_pk: the Y map with the luma tables, the Cb / Cr map with the chroma tables); for the five one-byte sources of a YCbCr
-// batch alone, and off in every other instantiation, whose code it does not touch.
+// batch alone, and off in every other instantiation, whose code it does not touch.  With the two 16-bit sources kExpand selects the
+// limited-range or the full-range depth map (narrow_depth_pk): one of the two always runs.
 template <bool kTaps, int kSrc = kSrcRgb, uint32_t kZBits = kZrlBits, uint32_t kZCode = kZrlCode, bool kExpand = false>
 __global__ __launch_bounds__(64 * kWavesT) __attribute__((amdgpu_waves_per_eu(JPEGAMD_TILE_WAVES, JPEGAMD_TILE_WAVES)))
 void k_tile_encode(const ImageDesc im, const TransformOutM out, const TileSched sch, const typename PlanesArg<kSrc>::type pl) {
@@ -538,7 +588,7 @@ void k_tile_encode(const ImageDesc im, const TransformOutM out, const TileSched 
         const uint8_t *tb = im.batch_pixels[g.img] + (size_t)row_low * (size_t)im.row_stride + 24 * (size_t)g.tbx0;
         uint32_t hh = (uint32_t)h;
         asm volatile("" : "+v"(hh));
-        if constexpr (kSrc == kSrcPx4 || kSrc == kSrcQuad) {    // 32 bytes per lane-row (kSrcQuad: 8 groups).  Four rows of eight dwords are 8 registers more than
+        if constexpr (kSrc == kSrcPx4 || kSrc == kSrcQuad || kSrc == kSrcPair16) {    // 32 bytes per lane-row (kSrcQuad: 8 groups; kSrcPair16: 8 pairs of words).  Four rows of eight dwords are 8 registers more than
             // raw[] holds (the kernel sits at its register limit): rows 0 .. 2 are requested here, row 3 at the top of the tile's iteration
             const uint8_t *qb = im.batch_pixels[g.img] + (size_t)row_low * (size_t)im.row_stride + 32 * (size_t)g.tbx0;
             uint32_t qoff = __umul24((uint32_t)min(b, g.nblk - 1), 32u) + __umul24(im.bottom_up ? 7u - hh : hh, (uint32_t)im.row_stride);
@@ -567,7 +617,7 @@ void k_tile_encode(const ImageDesc im, const TransformOutM out, const TileSched 
             }
             return;
         }
-        if constexpr (kSrc == kSrcPair) {                       // 16 bytes per lane-row: a block row of byte pairs, both components
+        if constexpr (kSrc == kSrcPair || kSrc == kSrcPlane16) { // 16 bytes per lane-row: a block row of byte pairs, both components, or of 16-bit samples
             const uint8_t *pb = im.batch_pixels[g.img] + (size_t)row_low * (size_t)im.row_stride + 16 * (size_t)g.tbx0;
             uint32_t poff = __umul24((uint32_t)min(b, g.nblk - 1), 16u) + __umul24(im.bottom_up ? 7u - hh : hh, (uint32_t)im.row_stride);
 #pragma unroll
@@ -624,7 +674,7 @@ void k_tile_encode(const ImageDesc im, const TransformOutM out, const TileSched 
         // ---- 1. pixels -> B fragments ----------------------------------------------------------
         f16x8 bfrag[4];
         if (interior) {                        // rows requested one iteration ago, behind the ticket (below)
-            if constexpr (kSrc == kSrcPx4 || kSrc == kSrcQuad) {   // ... but for the fourth row pair (request_rows): on its way while the other three are converted
+            if constexpr (kSrc == kSrcPx4 || kSrc == kSrcQuad || kSrc == kSrcPair16) {   // ... but for the fourth row pair (request_rows): on its way while the other three are converted
                 uint32_t hh = (uint32_t)h;
                 asm volatile("" : "+v"(hh));
                 const int row_low = im.bottom_up ? im.height - 8 - by * 8 : by * 8;
@@ -641,6 +691,11 @@ void k_tile_encode(const ImageDesc im, const TransformOutM out, const TileSched 
 #pragma unroll
                     for (int s = 0; s < 3; ++s) bfrag[s] = quad_row8_f16(flat + 8 * s, qsel);
                     bfrag[3] = quad_row8_f16(last, qsel);
+                } else if constexpr (kSrc == kSrcPair16) {   // the wanted word of two dwords into the two halves: 0x05040100 (component 0) / 0x07060302
+                    const uint32_t wsel = 0x05040100u + 0x02020202u * ((im.weights + (uint32_t)tg.img) & 1u);
+#pragma unroll
+                    for (int s = 0; s < 3; ++s) bfrag[s] = quad_row8_f16(flat + 8 * s, wsel);
+                    bfrag[3] = quad_row8_f16(last, wsel);
                 } else {
 #pragma unroll
                 for (int s = 0; s < 3; ++s) bfrag[s] = px4_row8_f16(flat + 8 * s, im.weights, luma_sel);
@@ -652,6 +707,10 @@ void k_tile_encode(const ImageDesc im, const TransformOutM out, const TileSched 
                 // (kSrcPair: the component is the launch image's parity, wave-uniform: the selector stays on the scalar unit)
                 if constexpr (kSrc == kSrcPair) bfrag[s] = pair_row8_f16(raw[s].d, 0x0C020C00u + 0x00010001u * ((im.weights + (kPairFixed ? 0u : (uint32_t)tg.img)) & 1u));
                 else if constexpr (kSrc == kSrcPlane) bfrag[s] = plane_row8_f16(raw[s].d[0], raw[s].d[1]);
+                else if constexpr (kSrc == kSrcPlane16) {          // the four dwords ARE the fragment: two words each
+                    typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
+                    bfrag[s] = __builtin_bit_cast(f16x8, (u32x4){raw[s].d[0], raw[s].d[1], raw[s].d[2], raw[s].d[3]});
+                }
                 else if constexpr (kSrc == kSrcPlanar) bfrag[s] = planar_row8_f16(raw[s], luma_sel);
                 else bfrag[s] = luma_row8_f16(raw[s], lw, luma_sel);
             }
@@ -670,6 +729,12 @@ void k_tile_encode(const ImageDesc im, const TransformOutM out, const TileSched 
                     else if constexpr (kSrc == kSrcQuad)
                         pk[j >> 1] = (uint32_t)quad_clamped(im, im.batch_pixels[tg.img], (int)(((im.weights >> 8) & 1u) + 2u * ((im.weights + (uint32_t)tg.img) & 1u)), px0 + j, py0 + 2 * s + h) |
                                      ((uint32_t)quad_clamped(im, im.batch_pixels[tg.img], (int)(((im.weights >> 8) & 1u) + 2u * ((im.weights + (uint32_t)tg.img) & 1u)), px0 + j + 1, py0 + 2 * s + h) << 16);
+                    else if constexpr (kSrc == kSrcPlane16)
+                        pk[j >> 1] = plane16_clamped(im, im.batch_pixels[tg.img], px0 + j, py0 + 2 * s + h) |
+                                     (plane16_clamped(im, im.batch_pixels[tg.img], px0 + j + 1, py0 + 2 * s + h) << 16);
+                    else if constexpr (kSrc == kSrcPair16)
+                        pk[j >> 1] = pair16_clamped(im, im.batch_pixels[tg.img], (int)((im.weights + (uint32_t)tg.img) & 1u), px0 + j, py0 + 2 * s + h) |
+                                     (pair16_clamped(im, im.batch_pixels[tg.img], (int)((im.weights + (uint32_t)tg.img) & 1u), px0 + j + 1, py0 + 2 * s + h) << 16);
                     else if constexpr (kSrc == kSrcPlane)
                         pk[j >> 1] = (uint32_t)plane_clamped(im, im.batch_pixels[tg.img], px0 + j, py0 + 2 * s + h) |
                                      ((uint32_t)plane_clamped(im, im.batch_pixels[tg.img], px0 + j + 1, py0 + 2 * s + h) << 16);
@@ -686,7 +751,18 @@ void k_tile_encode(const ImageDesc im, const TransformOutM out, const TileSched 
                 bfrag[s] = __builtin_bit_cast(f16x8, pk);
             }
         }
-        if constexpr (kExpand) {               // limited range -> full range: ONE place behind both loaders, so the stash below holds the mapped samples
+        if constexpr (kSrc == kSrcPlane16 || kSrc == kSrcPair16) {   // 16-bit words -> the 8-bit samples, either range (kExpand: limited): ONE place behind both
+            static_assert(!kTaps, "the 16-bit sources have no stage taps");   // loaders, so replicated edges copy mapped samples and the stash holds them
+            typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
+            const uint32_t sh2 = ((im.weights >> 16) & 31u) * 0x00010001u;
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {
+                u32x4 pk = __builtin_bit_cast(u32x4, bfrag[s]);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) pk[j] = narrow_depth_pk<kExpand, kZBits != kZrlBits>(pk[j], sh2);
+                bfrag[s] = __builtin_bit_cast(f16x8, pk);
+            }
+        } else if constexpr (kExpand) {        // limited range -> full range: ONE place behind both loaders, so the stash below holds the mapped samples
             static_assert(!kTaps && (kSrc == kSrcPlane || kSrc == kSrcPair || kSrc == kSrcQuad), "range expansion is for the sources of a YCbCr batch");
             typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
 #pragma unroll
@@ -1266,7 +1342,7 @@ int launch_tile_transform(const ImageDesc &im, const TransformOutM &out, bool ta
     const dim3 grid(wgs), block(64 * kWavesT);
     const NoPlanes pl;
     if (src == kTileSrcPx4 || src == kTileSrcPlanar || src == kTileSrcChromaPair || src == kTileSrcLumaPair || src == kTileSrcChromaQuad ||
-        (src >= kTileSrcGrayExpand && src <= kTileSrcChromaQuadExpand)) {
+        (src >= kTileSrcGrayExpand && src <= kTileSrcChromaPair16Expand)) {
 #ifdef JPEGAMD_STAMPED_TU
         return (int)hipErrorInvalidValue;                                   // (these sources exist in the plain build alone)
 #else
@@ -1283,7 +1359,20 @@ int launch_tile_transform(const ImageDesc &im, const TransformOutM &out, bool ta
         const auto xpair = k_tile_encode<false, kSrcPair, kZrlBitsChroma, kZrlCodeChroma, true>;
         const auto xypair = k_tile_encode<false, kSrcPair, kZrlBits, kZrlCode, true>;
         const auto xquad = k_tile_encode<false, kSrcQuad, kZrlBitsChroma, kZrlCodeChroma, true>;
-        if (src == kTileSrcGrayExpand) hipExtLaunchKernelGGL(xgray, grid, block, 0, (hipStream_t)stream, e0, e1, 0, im, out, sch, pl);
+        // 10-bit samples in 16-bit words: a plane with either table set, a pair plane with the chroma tables, each with either depth map
+        const auto gray16 = k_tile_encode<false, kSrcPlane16>;
+        const auto plane16 = k_tile_encode<false, kSrcPlane16, kZrlBitsChroma, kZrlCodeChroma>;
+        const auto pair16 = k_tile_encode<false, kSrcPair16, kZrlBitsChroma, kZrlCodeChroma>;
+        const auto xgray16 = k_tile_encode<false, kSrcPlane16, kZrlBits, kZrlCode, true>;
+        const auto xplane16 = k_tile_encode<false, kSrcPlane16, kZrlBitsChroma, kZrlCodeChroma, true>;
+        const auto xpair16 = k_tile_encode<false, kSrcPair16, kZrlBitsChroma, kZrlCodeChroma, true>;
+        if (src == kTileSrcGray16) hipExtLaunchKernelGGL(gray16, grid, block, 0, (hipStream_t)stream, e0, e1, 0, im, out, sch, pl);
+        else if (src == kTileSrcChroma16) hipExtLaunchKernelGGL(plane16, grid, block, 0, (hipStream_t)stream, e0, e1, 0, im, out, sch, pl);
+        else if (src == kTileSrcChromaPair16) hipExtLaunchKernelGGL(pair16, grid, block, 0, (hipStream_t)stream, e0, e1, 0, im, out, sch, pl);
+        else if (src == kTileSrcGray16Expand) hipExtLaunchKernelGGL(xgray16, grid, block, 0, (hipStream_t)stream, e0, e1, 0, im, out, sch, pl);
+        else if (src == kTileSrcChroma16Expand) hipExtLaunchKernelGGL(xplane16, grid, block, 0, (hipStream_t)stream, e0, e1, 0, im, out, sch, pl);
+        else if (src == kTileSrcChromaPair16Expand) hipExtLaunchKernelGGL(xpair16, grid, block, 0, (hipStream_t)stream, e0, e1, 0, im, out, sch, pl);
+        else if (src == kTileSrcGrayExpand) hipExtLaunchKernelGGL(xgray, grid, block, 0, (hipStream_t)stream, e0, e1, 0, im, out, sch, pl);
         else if (src == kTileSrcChromaExpand) hipExtLaunchKernelGGL(xplane, grid, block, 0, (hipStream_t)stream, e0, e1, 0, im, out, sch, pl);
         else if (src == kTileSrcChromaPairExpand) hipExtLaunchKernelGGL(xpair, grid, block, 0, (hipStream_t)stream, e0, e1, 0, im, out, sch, pl);
         else if (src == kTileSrcLumaPairExpand) hipExtLaunchKernelGGL(xypair, grid, block, 0, (hipStream_t)stream, e0, e1, 0, im, out, sch, pl);

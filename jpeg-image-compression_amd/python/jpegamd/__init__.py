@@ -44,6 +44,7 @@ class PlanarImage(C.Structure):
 CHROMA_PLANES, CHROMA_CBCR, CHROMA_CRCB = 0, 1, 2           # JPEGAMD_CHROMA_*
 CHROMA_YUYV, CHROMA_UYVY = 4, 5                             # packed 4:2:2: the picture's y is the packed plane (3 stays invalid)
 RANGE_FULL, RANGE_LIMITED = 0, 1                            # JPEGAMD_RANGE_*: JFIF full range / video range (Y 16..235, Cb Cr 16..240), expanded on read
+SAMPLES_8, SAMPLES_10_MSB, SAMPLES_10_LSB = 0, 1, 2         # JPEGAMD_SAMPLES_*: one byte per sample / 10 bits in 16-bit words, high bits (P010) or low bits (I010), narrowed on read
 
 
 class YCbCrImage(C.Structure):
@@ -117,6 +118,7 @@ def _load() -> C.CDLL:
         "jpegamd_encode_planar_batch_async": (i32, [vp, C.POINTER(PlanarImage), i32, i32, C.POINTER(C.c_void_p), u64, C.POINTER(C.c_void_p), vp]),
         "jpegamd_encode_ycbcr_batch_async": (i32, [vp, C.POINTER(YCbCrImage), i32, i32, C.POINTER(C.c_void_p), u64, C.POINTER(C.c_void_p), vp]),
         "jpegamd_encode_ycbcr_range_batch_async": (i32, [vp, C.POINTER(YCbCrImage), i32, i32, i32, C.POINTER(C.c_void_p), u64, C.POINTER(C.c_void_p), vp]),
+        "jpegamd_encode_ycbcr_samples_batch_async": (i32, [vp, C.POINTER(YCbCrImage), i32, i32, i32, i32, C.POINTER(C.c_void_p), u64, C.POINTER(C.c_void_p), vp]),
         "jpegamd_debug_chroma_groups": (i32, [i32, i32, i32, i32, i32, i32, i32, vp]),
         "jpegamd_debug_chroma_quant_table": (i32, [i32, vp]),
         "jpegamd_debug_chroma_mfma_consts": (i32, [i32, vp, vp, vp, vp, vp, vp]),
@@ -132,7 +134,7 @@ def _load() -> C.CDLL:
     for name, (res, args) in sig.items():
         if name in ("jpegamd_encoder_set_pipeline", "jpegamd_gather_streams", "jpegamd_debug_mfma_offsets", "jpegamd_encode_color_batch_async",
                     "jpegamd_debug_chroma_groups", "jpegamd_encode_planar_batch_async", "jpegamd_encode_ycbcr_batch_async",
-                    "jpegamd_encode_ycbcr_range_batch_async") and os.environ.get("JPEGAMD_LIB") and not hasattr(lib, name):
+                    "jpegamd_encode_ycbcr_range_batch_async", "jpegamd_encode_ycbcr_samples_batch_async") and os.environ.get("JPEGAMD_LIB") and not hasattr(lib, name):
             continue                                              # (A/B tooling: a variant build of an older round)
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = res, args
@@ -148,7 +150,8 @@ EXPORTED = ("jpegamd_encoder_create jpegamd_encoder_destroy jpegamd_max_jfif_byt
             "jpegamd_encode_rows_async jpegamd_export_segments jpegamd_import_segments jpegamd_finalize_async "
             "jpegamd_max_jfif_bytes_color jpegamd_encode_color_async jpegamd_encode_bmp_memory_color jpegamd_debug_chroma_quant_table "
             "jpegamd_debug_chroma_mfma_consts jpegamd_debug_chroma_group_thresholds jpegamd_debug_color_profile jpegamd_encode_color_batch_async "
-            "jpegamd_encode_planar_batch_async jpegamd_encode_ycbcr_batch_async jpegamd_encode_ycbcr_range_batch_async").split()
+            "jpegamd_encode_planar_batch_async jpegamd_encode_ycbcr_batch_async jpegamd_encode_ycbcr_range_batch_async "
+            "jpegamd_encode_ycbcr_samples_batch_async").split()
 
 
 def quant_table(quality: int = 50):
@@ -551,7 +554,7 @@ def encode_ycbcr_batch(y, cb, cr=None, quality: int = 0, subsampling: int = SUBS
         y[i].data_ptr(), cb[i].data_ptr(), cr[i].data_ptr() if cr is not None else 0, w, h, y_stride, c_stride, layout, quality), rng)
 
 
-def _encode_ycbcr_images(device, n, h, w, subsampling, image, sample_range: int = RANGE_FULL):
+def _encode_ycbcr_images(device, n, h, w, subsampling, image, sample_range: int = RANGE_FULL, sample_format: int = SAMPLES_8):
     """`n` YCbCr pictures of one geometry, picture i described by image(i), through the per-device context in calls of at most
     MAX_BATCH -> their files."""
     import torch
@@ -576,11 +579,79 @@ def _encode_ycbcr_images(device, n, h, w, subsampling, image, sample_range: int 
             outs = [out[i].data_ptr() for i in range(k)]
             size_ptrs = [sizes.data_ptr() + 8 * i for i in range(k)]
             imgs = [image(b0 + i) for i in range(k)]
-            enc.encode_ycbcr_batch_async(imgs, subsampling, outs, cap, size_ptrs, stream, sample_range)
+            enc.encode_ycbcr_batch_async(imgs, subsampling, outs, cap, size_ptrs, stream, sample_range, sample_format=sample_format)
             enc.finish()
             got = sizes[:k].cpu().tolist()
             files += [bytes(out[i, :got[i]].cpu().numpy().tobytes()) for i in range(k)]
     return files
+
+
+def _ycbcr16_layout(y, cb, cr, subsampling, order):
+    """The pictures of encode_ycbcr16_batch -> (count, height, width, y stride, chroma stride, JPEGAMD_CHROMA_* layout), strides in
+    BYTES.  Shapes, dtypes and strides only: host tensors pass."""
+    import torch
+    if subsampling not in (SUBSAMPLE_444, SUBSAMPLE_420, SUBSAMPLE_422):
+        raise ValueError("subsampling must be SUBSAMPLE_444, SUBSAMPLE_420 or SUBSAMPLE_422")
+    if order not in ("cbcr", "crcb"):
+        raise ValueError(f'order must be "cbcr" or "crcb", not {order!r}')
+    tensors = [y, cb] + ([cr] if cr is not None else [])
+    if any(not isinstance(x, torch.Tensor) or x.dtype not in (torch.int16, torch.uint16) for x in tensors):
+        raise ValueError("the encoder needs int16 or uint16 tensors (16-bit sample words)")
+    if y.dim() != 3:
+        raise ValueError("y must be [N, H, W]")
+    n, h, w = y.shape
+    if n < 1 or h < 1 or w < 1 or h > 65535 or w > 65535:
+        raise ValueError("the encoder needs at least one picture of 1..65535 pixels each way")
+    cw = w if subsampling == SUBSAMPLE_444 else (w + 1) // 2
+    ch = (h + 1) // 2 if subsampling == SUBSAMPLE_420 else h
+    if cr is None:
+        if cb.dim() != 4 or tuple(cb.shape) != (n, ch, cw, 2):
+            raise ValueError(f"with cr=None, cb holds the pairs of words: [N, {ch}, {cw}, 2] for this y and subsampling, not {tuple(cb.shape)}")
+        if cb.stride(3) != 1 or cb.stride(2) != 2:
+            raise ValueError("the pairs of a row must be packed (pair stride 2, last stride 1)")
+        layout, c_row = (CHROMA_CBCR if order == "cbcr" else CHROMA_CRCB), 2 * cw
+    else:
+        if order != "cbcr":
+            raise ValueError('order="crcb" names the interleaved layout (cr=None); swap the tensors for planes')
+        for name, p in (("cb", cb), ("cr", cr)):
+            if p.dim() != 3 or tuple(p.shape) != (n, ch, cw):
+                raise ValueError(f"{name} must be [N, {ch}, {cw}] for this y and subsampling, not {tuple(p.shape)}")
+            if p.stride(2) != 1:
+                raise ValueError("samples of a row must be packed (last stride 1)")
+        if ch > 1 and cb.stride(1) != cr.stride(1):
+            raise ValueError("cb and cr must share one row stride")
+        layout, c_row = CHROMA_PLANES, cw
+    if y.stride(2) != 1:
+        raise ValueError("samples of a row must be packed (last stride 1)")
+    y_stride = y.stride(1) if h > 1 else w            # (in words up to here)
+    c_stride = cb.stride(1) if ch > 1 else c_row
+    if y_stride < w or c_stride < c_row:
+        raise ValueError("rows overlap (a row stride is less than a row)")
+    if 2 * y_stride >= 1 << 31 or 2 * c_stride >= 1 << 31:
+        raise ValueError("a row stride must stay below 2^31 bytes")
+    return n, h, w, 2 * y_stride, 2 * c_stride, layout
+
+
+def encode_ycbcr16_batch(y, cb, cr=None, quality: int = 0, subsampling: int = SUBSAMPLE_420, order: str = "cbcr",
+                         sample_range: str = "full", align: str = "msb") -> list:
+    """N pictures of 10-bit Y, Cb and Cr samples in 16-bit words (a Main10 / AV1 10-bit decoder's frames) -> N colour JFIF files through
+    jpegamd_encode_ycbcr_samples_batch_async, read where they lie: every sample is narrowed to 8 bits as the kernel reads it (no pass
+    over the planes), with ONE rounding from ten bits for either sample_range ("full" / "limited": Y 64..940, Cb / Cr 64..960).
+    align="msb": the value sits in the high ten bits of the word and the low six are ignored (P010 / P210 / P410); align="lsb": in the
+    low ten bits, larger words clamp to 1023 (I010 / yuv420p10le).  The tensors are torch.int16 or torch.uint16 DEVICE tensors -- the
+    bit pattern is what counts -- shaped as encode_ycbcr_batch's: `y` [N, H, W], `cb` and `cr` [N, ch, cw], or with cr=None `cb` as
+    [N, ch, cw, 2] pairs of words Cb Cr (Cr Cb with order="crcb").  Rows and pictures may be strided, samples within a row are packed.
+    Batches of more than MAX_BATCH pictures go as several calls; the per-device context of encode_tensor is used."""
+    rng = _sample_range(sample_range)
+    if not isinstance(align, str) or align not in ("msb", "lsb"):
+        raise ValueError(f'align must be "msb" or "lsb", not {align!r}')
+    n, h, w, y_stride, c_stride, layout = _ycbcr16_layout(y, cb, cr, subsampling, order)
+    tensors = [y, cb] + ([cr] if cr is not None else [])
+    if any(not x.is_cuda or x.device != y.device for x in tensors):
+        raise ValueError("encode_ycbcr16_batch needs device tensors on one device")
+    return _encode_ycbcr_images(y.device, n, h, w, subsampling, lambda i: Encoder.ycbcr_image(
+        y[i].data_ptr(), cb[i].data_ptr(), cr[i].data_ptr() if cr is not None else 0, w, h, y_stride, c_stride, layout, quality), rng,
+        SAMPLES_10_MSB if align == "msb" else SAMPLES_10_LSB)
 
 
 def _yuyv_layout(frames, order):
@@ -711,14 +782,22 @@ class Encoder:
         return YCbCrImage(y_ptr or None, cb_ptr or None, cr_ptr or None, width, height, y_stride, c_stride, chroma_layout, quality)
 
     def encode_ycbcr_batch_async(self, imgs, subsampling: int, out_ptrs, out_cap: int, size_ptrs, stream: int = 0,
-                                 sample_range: int = RANGE_FULL):
+                                 sample_range: int = RANGE_FULL, sample_format: int = SAMPLES_8):
         """The colour files of `len(imgs)` YCbCr pictures of one geometry (jpegamd_encode_ycbcr_batch_async); the context as for
         encode_color_batch_async.  sample_range: RANGE_FULL, or RANGE_LIMITED for video-range samples, which go through
-        jpegamd_encode_ycbcr_range_batch_async and are expanded on read."""
+        jpegamd_encode_ycbcr_range_batch_async and are expanded on read.  sample_format: SAMPLES_8, or SAMPLES_10_MSB / SAMPLES_10_LSB
+        for 10-bit samples in 16-bit words (strides in bytes), which go through jpegamd_encode_ycbcr_samples_batch_async and are
+        narrowed on read."""
         n = len(imgs)
         arr = (YCbCrImage * n)(*imgs)
         outs = (C.c_void_p * n)(*[C.c_void_p(p) for p in out_ptrs])
         sizes = (C.c_void_p * n)(*[C.c_void_p(p) for p in size_ptrs])
+        if int(sample_format) != SAMPLES_8:          # (one byte per sample keeps to the older entries, as below)
+            rc = lib.jpegamd_encode_ycbcr_samples_batch_async(self._h, arr, n, int(subsampling), int(sample_range), int(sample_format), outs,
+                                                              out_cap, sizes, C.c_void_p(stream))
+            if rc:
+                raise JpegAmdError(rc, "jpegamd_encode_ycbcr_samples_batch_async")
+            return
         if int(sample_range) != RANGE_FULL:          # (the full-range call keeps to the older entry: a variant library without the new one still serves it)
             rc = lib.jpegamd_encode_ycbcr_range_batch_async(self._h, arr, n, int(subsampling), int(sample_range), outs, out_cap, sizes,
                                                             C.c_void_p(stream))

@@ -18,6 +18,11 @@ jpegamd_encode_ycbcr_range_batch_async with JPEGAMD_RANGE_LIMITED, which expands
 --convert it also times what that replaces, in the same run: the range map as a pass of its own over the planes (a torch table
 lookup, lut[plane.long()], into preallocated planes: "convert_us_per_picture") and the full-range encode of the planes it wrote
 ("mapped_full_us_per_picture", whose files must be the limited ones: "mapped_bytes_equal").
+`p010` and `i010` are the 10-bit 4:2:0 sources: the samples of `nv12` / `i420` as 16-bit words -- s << 8 (MSB-aligned: one plane of Y words
+and one of Cb Cr pairs of words per picture) and s << 2 (LSB-aligned: three planes) -- through jpegamd_encode_ycbcr_samples_batch_async,
+which narrows them on read: at full range the files are those of `nv12`, so "bytes" must agree.  With --narrow they also time what
+that replaces, in the same run: the narrowing as a pass of its own over the planes (16-bit words in, bytes out, into preallocated
+planes: "narrow_us_per_picture") and the 8-bit encode of the planes it wrote at the same --range ("narrowed_8bit_us_per_picture").
 
 With --layout {hwc,chw,rgba} (and --batch N, default 8) the pictures are device tensors stored that way -- [N, H, W, 3], [N, 3, H, W],
 [N, H, W, 4] -- and go through the entry that reads them where they lie, 4:2:0 only.  Every call is timed as a whole between two
@@ -48,11 +53,12 @@ def main() -> None:
     ap.add_argument("--quality", type=int, default=50)
     ap.add_argument("--kind", type=int, default=0)
     ap.add_argument("--batch", type=int, default=None, help="pictures per call through the colour batch entry (1 .. 32)")
-    ap.add_argument("--source", default="rgb", help="rgb (default), i420, nv12, i422, yuyv, or several separated by commas: what the batch loop reads")
+    ap.add_argument("--source", default="rgb", help="rgb (default), i420, nv12, i422, yuyv, p010, i010, or several separated by commas: what the batch loop reads")
     ap.add_argument("--subsampling", choices=("420", "444", "422"), default=None, help="rgb: this subsampling alone (default: 420, then 444)")
     ap.add_argument("--range", choices=("full", "limited"), default="full", dest="sample_range",
                     help="i420 / nv12 / i422 / yuyv: the samples are full range (default) or limited range, expanded on read")
     ap.add_argument("--convert", action="store_true", help="--range limited: also time the map as a separate pass + the full-range encode")
+    ap.add_argument("--narrow", action="store_true", help="p010 / i010: also time the narrowing as a separate pass + the 8-bit encode")
     ap.add_argument("--layout", choices=("hwc", "chw", "rgba"), default=None, help="device tensors stored this way, read where they lie")
     ap.add_argument("--rounds", type=int, default=5, help="--layout: medians taken (each of --steps calls)")
     ap.add_argument("--repack", action="store_true", help="--layout chw: also time permute + packed encode")
@@ -69,12 +75,14 @@ def main() -> None:
         run_layout(a, jpegamd, torch, dev)
         return
     sources = a.source.split(",")
-    if any(s not in ("rgb", "i420", "nv12", "i422", "yuyv") for s in sources):
-        sys.exit("--source takes rgb, i420, nv12, i422, yuyv or a comma-separated list of them")
+    if any(s not in ("rgb", "i420", "nv12", "i422", "yuyv", "p010", "i010") for s in sources):
+        sys.exit("--source takes rgb, i420, nv12, i422, yuyv, p010, i010 or a comma-separated list of them")
     if a.sample_range != "full" and "rgb" in sources:
-        sys.exit("--range limited is for the YCbCr sources (i420, nv12, i422, yuyv)")
+        sys.exit("--range limited is for the YCbCr sources (i420, nv12, i422, yuyv, p010, i010)")
     if a.convert and a.sample_range != "limited":
         sys.exit("--convert needs --range limited")
+    if a.narrow and not any(s in ("p010", "i010") for s in sources):
+        sys.exit("--narrow needs --source p010 or i010")
     if a.batch is not None or sources != ["rgb"]:
         run_batch(a, jpegamd, torch, dev, sources)
         return
@@ -139,7 +147,7 @@ def run_batch(a, jpegamd, torch, dev, sources=("rgb",)) -> None:
     w = h = a.size
     n = a.batch or 8
     if any(s != "rgb" for s in sources) and (w % 2 or h % 2):
-        sys.exit("--source i420 / nv12 / i422 / yuyv needs an even --size")
+        sys.exit("--source i420 / nv12 / i422 / yuyv / p010 / i010 needs an even --size")
     pxs, descs = [], []
     for i in range(n):
         bmp = jpegamd.synth_bmp(w, h, 1 + i, a.kind, 0)
@@ -150,7 +158,7 @@ def run_batch(a, jpegamd, torch, dev, sources=("rgb",)) -> None:
     enc = jpegamd.Encoder(w, n * h)
     stream = torch.cuda.current_stream().cuda_stream
     frames = None
-    if any(s in ("i420", "nv12") for s in sources):              # NV12 frames [N, 3 H / 2, W], and the chroma as two planes
+    if any(s in ("i420", "nv12", "p010", "i010") for s in sources):   # NV12 frames [N, 3 H / 2, W], and the chroma as two planes
         frames = torch.empty((n, 3 * h // 2, w), dtype=torch.uint8, device=dev)
         cbs, crs = (torch.empty((n, h // 2, w // 2), dtype=torch.uint8, device=dev) for _ in range(2))
         for i in range(n):
@@ -161,6 +169,10 @@ def run_batch(a, jpegamd, torch, dev, sources=("rgb",)) -> None:
             del y
     runs = []
     packed = None
+    if "p010" in sources:                                        # the same frames as 16-bit words, the sample in the high byte
+        frames16 = frames.to(torch.int16) << 8
+    if "i010" in sources:                                        # ... and as three planes of words with the value in the low ten bits
+        ys16, cbs16, crs16 = (t.to(torch.int16) << 2 for t in (frames[:, :h], cbs, crs))
     if any(s in ("i422", "yuyv") for s in sources):              # YUY2 frames [N, H, W, 2], and the same samples as three planes
         packed = torch.empty((n, h, w, 2), dtype=torch.uint8, device=dev)
         cbs2, crs2 = (torch.empty((n, h, w // 2), dtype=torch.uint8, device=dev) for _ in range(2))
@@ -175,6 +187,14 @@ def run_batch(a, jpegamd, torch, dev, sources=("rgb",)) -> None:
         # a YCbCr source: its tensors, and the descriptors of pictures stored in tensors of those shapes (--convert writes a second set)
         if source == "rgb":
             runs += [(source, sub, name, None, None) for sub, name in rgb_subsamplings(a, jpegamd)]
+        elif source == "p010":                                   # strides in bytes: 2 W for the Y words and for the W / 2 pairs of words
+            runs.append((source, jpegamd.SUBSAMPLE_420, "420", (frames16,), lambda t: [
+                jpegamd.Encoder.ycbcr_image(t[0][i].data_ptr(), t[0][i, h:].data_ptr(), 0, w, h, 2 * w, 2 * w,
+                                            jpegamd.CHROMA_CBCR, a.quality) for i in range(n)]))
+        elif source == "i010":
+            runs.append((source, jpegamd.SUBSAMPLE_420, "420", (ys16, cbs16, crs16), lambda t: [
+                jpegamd.Encoder.ycbcr_image(t[0][i].data_ptr(), t[1][i].data_ptr(), t[2][i].data_ptr(), w, h, 2 * w, w,
+                                            jpegamd.CHROMA_PLANES, a.quality) for i in range(n)]))
         elif source == "i422":
             runs.append((source, jpegamd.SUBSAMPLE_422, "422", (ys2, cbs2, crs2), lambda t: [
                 jpegamd.Encoder.ycbcr_image(t[0][i].data_ptr(), t[1][i].data_ptr(), t[2][i].data_ptr(), w, h, w, w // 2,
@@ -204,8 +224,10 @@ def run_batch(a, jpegamd, torch, dev, sources=("rgb",)) -> None:
         if ycc is None:
             call = lambda: enc.encode_color_batch_async(descs, sub, out_ptrs, cap, size_ptrs, stream)
         else:
-            call = lambda: enc.encode_ycbcr_batch_async(ycc, sub, out_ptrs, cap, size_ptrs, stream,
-                                                        **({"sample_range": jpegamd.RANGE_LIMITED} if limited else {}))
+            kw = {"sample_range": jpegamd.RANGE_LIMITED} if limited else {}
+            if source in ("p010", "i010"):
+                kw["sample_format"] = jpegamd.SAMPLES_10_MSB if source == "p010" else jpegamd.SAMPLES_10_LSB
+            call = lambda: enc.encode_ycbcr_batch_async(ycc, sub, out_ptrs, cap, size_ptrs, stream, **kw)
         for _ in range(a.warmup):
             call()
         enc.finish()
@@ -222,7 +244,9 @@ def run_batch(a, jpegamd, torch, dev, sources=("rgb",)) -> None:
                 "gpixels_per_s": round(n * w * h / t, 2)}
         if limited:
             line["range"] = "limited"
-        if a.convert:
+        if a.narrow and source in ("p010", "i010"):
+            line.update(time_narrow(a, jpegamd, torch, enc, source, tensors, h, sub, out_ptrs, cap, size_ptrs, sizes, stream, n))
+        if a.convert and source not in ("p010", "i010"):
             line.update(time_convert(a, jpegamd, torch, enc, source, tensors, describe, (lut_y, lut_c), h, sub, out_ptrs, cap, size_ptrs,
                                      sizes, stream, n))
         print(json.dumps(line))
@@ -273,6 +297,52 @@ def time_convert(a, jpegamd, torch, enc, source, tensors, describe, luts, h, sub
     enc.set_profiling(0)
     return {"convert_us_per_picture": round(statistics.median(times), 1), "mapped_full_us_per_picture": round(t / n / 1000, 1),
             "mapped_bytes_equal": sizes.cpu().tolist() == limited_bytes}
+
+
+def time_narrow(a, jpegamd, torch, enc, source, tensors, h, sub, out_ptrs, cap, size_ptrs, sizes, stream, n):
+    """What narrowing on read replaces: a pass over the source's planes that reads the 16-bit words and writes bytes into planes of
+    the same shape (one call's worth, between two events on the stream), then the 8-bit encode of those at the same range."""
+    w = a.size
+    direct_bytes = sizes.cpu().tolist()
+    narrowed = tuple(torch.empty(t.shape, dtype=torch.uint8, device=t.device) for t in tensors)
+
+    def narrow():
+        if source == "p010":                                     # the high byte of every word: ONE strided copy
+            narrowed[0].copy_(tensors[0].view(torch.uint8).view(*tensors[0].shape, 2)[..., 1])
+        else:                                                    # the value in the low ten bits: v >> 2
+            for dst, src in zip(narrowed, tensors):
+                dst.copy_(src >> 2)
+
+    for _ in range(2):
+        narrow()
+    torch.cuda.synchronize()
+    times = []
+    for _ in range(max(3, a.steps // 5)):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        narrow()
+        e1.record()
+        torch.cuda.synchronize()
+        times.append(e0.elapsed_time(e1) * 1000.0 / n)
+    if source == "p010":
+        ycc = [jpegamd.Encoder.ycbcr_image(narrowed[0][i].data_ptr(), narrowed[0][i, h:].data_ptr(), 0, w, h, w, w, jpegamd.CHROMA_CBCR,
+                                           a.quality) for i in range(n)]
+    else:
+        ycc = [jpegamd.Encoder.ycbcr_image(narrowed[0][i].data_ptr(), narrowed[1][i].data_ptr(), narrowed[2][i].data_ptr(), w, h, w, w // 2,
+                                           jpegamd.CHROMA_PLANES, a.quality) for i in range(n)]
+    kw = {"sample_range": jpegamd.RANGE_LIMITED} if a.sample_range == "limited" else {}
+    call = lambda: enc.encode_ycbcr_batch_async(ycc, sub, out_ptrs, cap, size_ptrs, stream, **kw)
+    for _ in range(a.warmup):
+        call()
+    enc.finish()
+    enc.set_profiling(a.steps)
+    for _ in range(a.steps):
+        call()
+    enc.finish()
+    t = statistics.median(enc.profile(i).ns_total for i in range(a.steps))
+    enc.set_profiling(0)
+    return {"narrow_us_per_picture": round(statistics.median(times), 1), "narrowed_8bit_us_per_picture": round(t / n / 1000, 1),
+            "narrowed_bytes_equal": sizes.cpu().tolist() == direct_bytes}
 
 
 def run_layout(a, jpegamd, torch, dev) -> None:
