@@ -106,60 +106,14 @@ extern "C" const char *jpegamd_version(void) { return "jpegamd 0.4 (gfx950)"; }
 
 extern "C" int32_t jpegamd_segment_meta_words(void) { return kSegMetaWords; }
 
+// Small formulas every entry shares: the tiles of a w x h picture, the quality that is coded, the words of the stamp buffer.
+static int tiles_for(int w, int h) { return ((h + 7) / 8) * (((w + 7) / 8 + kTileBlocks - 1) / kTileBlocks); }
+static int clamp_quality(int q) { return q <= 0 ? 50 : (q > 100 ? 100 : q); }
+static size_t stamp_words(int max_segs) { return (size_t)(max_segs > 4096 ? max_segs : 4096) * 16; }   // 16 per wave
+
 extern "C" int32_t jpegamd_debug_quant_table(int32_t quality, uint8_t *table) {
     if (!table) return JPEGAMD_ERR_ARG;
     quant_table_for_quality(quality, table);
-    return JPEGAMD_OK;
-}
-
-// Host-only: the constants of the fast path for `quality` (tests pin them against the oracle's arithmetic).  Reentrant.
-extern "C" int32_t jpegamd_debug_mfma_consts(int32_t quality, float *qmul, float *qthr, float *bias, double *delta) {
-    uint8_t t[64];
-    MfmaTables *mt = new (std::nothrow) MfmaTables;
-    if (!mt) return JPEGAMD_ERR_HIP;
-    double d[64];
-    quant_table_for_quality(quality, t);
-    derive_mfma_tables(t, mt, d);
-    if (qmul) std::memcpy(qmul, mt->qmul, sizeof(mt->qmul));
-    if (qthr) std::memcpy(qthr, mt->qthr, sizeof(mt->qthr));
-    if (bias) std::memcpy(bias, mt->bias, sizeof(mt->bias));
-    if (delta) std::memcpy(delta, d, sizeof(d));
-    delete mt;
-    return JPEGAMD_OK;
-}
-
-// Host-only: what the UNCENTRED matrix operand adds to the quantiser's constants: qadd = bias + zoff by zigzag position, the DC row's
-// surplus in accumulator units, the accumulator scale (kMfmaScale).
-extern "C" int32_t jpegamd_debug_mfma_offsets(int32_t quality, float *zoff, float *qadd, float *dc_off, float *scale) {
-    uint8_t t[64];
-    MfmaTables *mt = new (std::nothrow) MfmaTables;
-    if (!mt) return JPEGAMD_ERR_HIP;
-    quant_table_for_quality(quality, t);
-    derive_mfma_tables(t, mt, nullptr);
-    if (zoff) std::memcpy(zoff, mt->zoff, sizeof(mt->zoff));
-    if (qadd) std::memcpy(qadd, mt->qadd, sizeof(mt->qadd));
-    if (dc_off) *dc_off = mt->dc_off;
-    if (scale) *scale = kMfmaScale;
-    delete mt;
-    return JPEGAMD_OK;
-}
-
-extern "C" int32_t jpegamd_debug_group_thresholds(int32_t quality, float *grp_thr /*[4 groups][2 lane halves]*/, float *lo_bound /*same shape, may be NULL*/) {
-    uint8_t t[64];
-    if (!grp_thr) return JPEGAMD_ERR_ARG;
-    MfmaTables *mt = new (std::nothrow) MfmaTables;
-    if (!mt) return JPEGAMD_ERR_HIP;
-    quant_table_for_quality(quality, t);
-    derive_mfma_tables(t, mt, nullptr);
-    std::memcpy(grp_thr, mt->grp_thr, sizeof(mt->grp_thr));
-    if (lo_bound) std::memcpy(lo_bound, mt->lo_bound, sizeof(mt->lo_bound));
-    delete mt;
-    return JPEGAMD_OK;
-}
-
-extern "C" int32_t jpegamd_debug_cos_lut(float *lut /*[8][8]: COS_LUT[x][u]*/) {
-    if (!lut) return JPEGAMD_ERR_ARG;
-    cos_lut_copy(lut);
     return JPEGAMD_OK;
 }
 
@@ -169,37 +123,60 @@ extern "C" int32_t jpegamd_debug_chroma_quant_table(int32_t quality, uint8_t *ta
     return JPEGAMD_OK;
 }
 
-extern "C" int32_t jpegamd_debug_chroma_mfma_consts(int32_t quality, float *qmul, float *qthr, float *bias, double *delta, float *zoff,
-                                                    float *qadd) {
-    uint8_t t[64];
-    MfmaTables *mt = new (std::nothrow) MfmaTables;
-    if (!mt) return JPEGAMD_ERR_HIP;
-    double d[64];
-    chroma_quant_table_for_quality(quality, t);
-    derive_mfma_tables(t, mt, d);
-    if (qmul) std::memcpy(qmul, mt->qmul, sizeof(mt->qmul));
-    if (qthr) std::memcpy(qthr, mt->qthr, sizeof(mt->qthr));
-    if (bias) std::memcpy(bias, mt->bias, sizeof(mt->bias));
-    if (delta) std::memcpy(delta, d, sizeof(d));
-    if (zoff) std::memcpy(zoff, mt->zoff, sizeof(mt->zoff));
-    if (qadd) std::memcpy(qadd, mt->qadd, sizeof(mt->qadd));
-    delete mt;
+extern "C" int32_t jpegamd_debug_cos_lut(float *lut /*[8][8]: COS_LUT[x][u]*/) {
+    if (!lut) return JPEGAMD_ERR_ARG;
+    cos_lut_copy(lut);
     return JPEGAMD_OK;
 }
 
-// jpegamd_debug_group_thresholds for the chroma table (the sibling of jpegamd_debug_chroma_mfma_consts).  Host-only.
-extern "C" int32_t jpegamd_debug_chroma_group_thresholds(int32_t quality, float *grp_thr /*[4 groups][2 lane halves]*/, float *lo_bound /*same shape, may be NULL*/) {
+// Behind the constant getters below (host-only, reentrant; tests pin the values against the oracle's arithmetic): the constants of
+// the fast path for `quality` with the luma or the chroma table, and the guard bands by raster index, handed to `take`.
+template <class Take>
+static int32_t with_mfma_consts(int32_t quality, bool chroma, Take take) {
     uint8_t t[64];
-    if (!grp_thr) return JPEGAMD_ERR_ARG;
+    double delta[64];
     MfmaTables *mt = new (std::nothrow) MfmaTables;
     if (!mt) return JPEGAMD_ERR_HIP;
-    chroma_quant_table_for_quality(quality, t);
-    derive_mfma_tables(t, mt, nullptr);
-    std::memcpy(grp_thr, mt->grp_thr, sizeof(mt->grp_thr));
-    if (lo_bound) std::memcpy(lo_bound, mt->lo_bound, sizeof(mt->lo_bound));
+    (chroma ? chroma_quant_table_for_quality : quant_table_for_quality)(quality, t);
+    derive_mfma_tables(t, mt, delta);
+    take(*mt, delta);
     delete mt;
     return JPEGAMD_OK;
 }
+template <class T, size_t N>
+static void copy_out(void *dst /*may be null*/, const T (&src)[N]) { if (dst) std::memcpy(dst, src, sizeof(src)); }
+
+// qmul, qthr, bias by zigzag position, delta by raster index; the chroma entry adds what jpegamd_debug_mfma_offsets gives.
+static int32_t mfma_consts(int32_t quality, bool chroma, float *qmul, float *qthr, float *bias, double *delta, float *zoff, float *qadd) {
+    return with_mfma_consts(quality, chroma, [&](const MfmaTables &mt, const double (&d)[64]) {
+        copy_out(qmul, mt.qmul); copy_out(qthr, mt.qthr); copy_out(bias, mt.bias); copy_out(delta, d);
+        copy_out(zoff, mt.zoff); copy_out(qadd, mt.qadd);
+    });
+}
+extern "C" int32_t jpegamd_debug_mfma_consts(int32_t quality, float *qmul, float *qthr, float *bias, double *delta) {
+    return mfma_consts(quality, false, qmul, qthr, bias, delta, nullptr, nullptr);
+}
+extern "C" int32_t jpegamd_debug_chroma_mfma_consts(int32_t quality, float *qmul, float *qthr, float *bias, double *delta, float *zoff,
+                                                    float *qadd) {
+    return mfma_consts(quality, true, qmul, qthr, bias, delta, zoff, qadd);
+}
+
+// What the UNCENTRED matrix operand adds to the quantiser's constants: qadd = bias + zoff by zigzag position, the DC row's
+// surplus in accumulator units, the accumulator scale (kMfmaScale).
+extern "C" int32_t jpegamd_debug_mfma_offsets(int32_t quality, float *zoff, float *qadd, float *dc_off, float *scale) {
+    return with_mfma_consts(quality, false, [&](const MfmaTables &mt, const double (&)[64]) {
+        copy_out(zoff, mt.zoff); copy_out(qadd, mt.qadd);
+        if (dc_off) *dc_off = mt.dc_off;
+        if (scale) *scale = kMfmaScale;
+    });
+}
+
+static int32_t group_thresholds(int32_t quality, bool chroma, float *grp_thr /*[4 groups][2 lane halves]*/, float *lo_bound /*same shape, may be NULL*/) {
+    if (!grp_thr) return JPEGAMD_ERR_ARG;
+    return with_mfma_consts(quality, chroma, [&](const MfmaTables &mt, const double (&)[64]) { copy_out(grp_thr, mt.grp_thr); copy_out(lo_bound, mt.lo_bound); });
+}
+extern "C" int32_t jpegamd_debug_group_thresholds(int32_t quality, float *grp_thr, float *lo_bound) { return group_thresholds(quality, false, grp_thr, lo_bound); }
+extern "C" int32_t jpegamd_debug_chroma_group_thresholds(int32_t quality, float *grp_thr, float *lo_bound) { return group_thresholds(quality, true, grp_thr, lo_bound); }
 
 // The colour subsamplings: 4:4:4, 4:2:0 (chroma halved both ways) and 4:2:2 (halved along the row alone).
 static bool sub_valid(int sub) { return sub == JPEGAMD_SUBSAMPLE_444 || sub == JPEGAMD_SUBSAMPLE_420 || sub == JPEGAMD_SUBSAMPLE_422; }
@@ -248,7 +225,7 @@ struct CtxLimits {
 static CtxLimits context_limits(int max_w, int max_h) {
     CtxLimits l;
     l.max_segs = segs_for(max_w, max_h, nullptr, nullptr, nullptr);
-    l.max_tiles = ((max_h + 7) / 8) * (((max_w + 7) / 8 + kTileBlocks - 1) / kTileBlocks);
+    l.max_tiles = tiles_for(max_w, max_h);
     // (room for either segment length: the same blocks as fewer, longer segments need a little more than as many short ones)
     const size_t w8 = (size_t)l.max_segs * kSegCapWords;
     const size_t w16 = (size_t)segs_for(max_w, max_h, nullptr, nullptr, nullptr, kSegTilesBatch) * seg_cap_words(kSegTilesBatch);
@@ -301,7 +278,7 @@ extern "C" int32_t jpegamd_encoder_create(JpegAmdEncoder **out, int32_t max_widt
     HIP_TRY_CREATE(hipMalloc((void **)&e->desc, 12 * (size_t)e->max_wgs * sizeof(uint32_t)));
     HIP_TRY_CREATE(hipMemset(e->desc, 0, 12 * (size_t)e->max_wgs * sizeof(uint32_t)));
     if (std::getenv("JPEGAMD_STAMPS")) {
-        const size_t n = (size_t)(e->max_segs > 4096 ? e->max_segs : 4096) * 16 * sizeof(unsigned long long);
+        const size_t n = stamp_words(e->max_segs) * sizeof(unsigned long long);
         HIP_TRY_CREATE(hipMalloc((void **)&e->stamps_dev, n));
         HIP_TRY_CREATE(hipMemset(e->stamps_dev, 0, n));
     }
@@ -412,7 +389,7 @@ extern "C" int32_t jpegamd_encoder_profile(JpegAmdEncoder *e, int32_t slot, Jpeg
 }
 
 static int32_t prepare_constants(JpegAmdEncoder *e, const JpegAmdImage *img, bool need_prefix) {
-    const int q = (img->quality <= 0) ? 50 : (img->quality > 100 ? 100 : img->quality);
+    const int q = clamp_quality(img->quality);
     if (q != e->cur_quality) {
         quant_table_for_quality(q, e->qtable);
         derive_mfma_tables(e->qtable, e->tables_host, nullptr);
@@ -434,9 +411,7 @@ static int32_t prepare_constants(JpegAmdEncoder *e, const JpegAmdImage *img, boo
 // fewer rows can need MORE segments or tiles than max_w x max_h (per-row rounding).
 static bool context_fits(const JpegAmdEncoder *e, int w, int h) {
     if (!e || w <= 0 || h <= 0) return false;
-    const int bw = (w + 7) / 8, bh = (h + 7) / 8;
-    const int tiles = bh * ((bw + kTileBlocks - 1) / kTileBlocks);
-    return segs_for(w, h, nullptr, nullptr, nullptr) <= e->max_segs && tiles <= e->max_tiles;
+    return segs_for(w, h, nullptr, nullptr, nullptr) <= e->max_segs && tiles_for(w, h) <= e->max_tiles;
 }
 
 // Layouts beyond the three every entry takes: the 4-byte orders (the four whole-picture encode entries), and the internal order of
@@ -458,9 +433,7 @@ static int32_t describe(const JpegAmdEncoder *e, const JpegAmdImage *img, ImageD
     d->pixels = (const uint8_t *)img->pixels;
     d->width = img->width; d->height = img->height; d->row_stride = img->row_stride;
     d->bottom_up = img->bottom_up ? 1 : 0;
-    // Y = (77 R + 150 G + 29 B) >> 8 (natural_c/src/core/converter.c:51); weights follow the STORED byte order.
-    d->weights = (img->channel_order == JPEGAMD_ORDER_BGR || img->channel_order == JPEGAMD_ORDER_BGRA) ? (29u | (150u << 8) | (77u << 16))
-                                                                                                       : (77u | (150u << 8) | (29u << 16));
+    d->select = select_luma(img->channel_order == JPEGAMD_ORDER_BGR || img->channel_order == JPEGAMD_ORDER_BGRA);   // the weights follow the STORED byte order
     d->seg_tiles = seg_tiles;
     d->num_segs = segs_for(img->width, img->height, &d->blocks_w, &d->blocks_h, &d->segs_per_row, seg_tiles);
     d->tiles_per_row = (d->blocks_w + kTileBlocks - 1) / kTileBlocks;
@@ -478,11 +451,11 @@ static int32_t describe(const JpegAmdEncoder *e, const JpegAmdImage *img, ImageD
     return JPEGAMD_OK;
 }
 
-// What k_tile_encode reads for this image (kTileSrcChroma: set by the colour path alone).
-static int src_of(const JpegAmdImage *img) {
-    if (img->channel_order == JPEGAMD_ORDER_GRAY) return kTileSrcGray;
-    if (img->channel_order == kOrderPlanar) return kTileSrcPlanar;
-    return is_px4(img->channel_order) ? kTileSrcPx4 : kTileSrcRgb;
+// What k_tile_encode reads for this image (a chroma source is set by the colour paths alone).
+static TileSource src_of(const JpegAmdImage *img) {
+    if (img->channel_order == JPEGAMD_ORDER_GRAY) return {kSrcPlane};
+    if (img->channel_order == kOrderPlanar) return {kSrcPlanar};
+    return {is_px4(img->channel_order) ? kSrcPx4 : kSrcRgb};
 }
 
 // The pictures of a batch as the kernels take them: p[0] the pixels (planar: the R planes), p[1] / p[2] the G / B planes.
@@ -492,13 +465,12 @@ struct PlaneSet {
 
 // k_tile_encode (+ the fault injection of the tests).
 static int launch_transform(JpegAmdEncoder *e, const ImageDesc &im, bool taps, int8_t *ty, int16_t *tzz, uint64_t *tmask,
-                            void *stream, hipEvent_t *ev = nullptr /*2: begin/end*/, int src = kTileSrcRgb, const PlaneSet *ps = nullptr) {
+                            void *stream, hipEvent_t *ev = nullptr /*2: begin/end*/, TileSource src = {}, const PlaneSet *ps = nullptr) {
     TransformOutM to;
     std::memset(&to, 0, sizeof(to));
-    const bool chroma = tile_src_is_chroma(src);
-    to.tables = chroma ? e->color.tables_dev : e->tables_dev; to.stamps = e->stamps_dev;
+    to.tables = src.chroma ? e->color.tables_dev : e->tables_dev; to.stamps = e->stamps_dev;
     to.tap_y = ty; to.tap_zz = tzz; to.tap_mask = tmask;
-    to.tile_head = e->tile_head; to.tile_over = e->tile_over; to.code_tab = chroma ? e->color.code_tab : e->code_tab;
+    to.tile_head = e->tile_head; to.tile_over = e->tile_over; to.code_tab = src.chroma ? e->color.code_tab : e->code_tab;
     // Launches on one context are stream-ordered by contract (they share the scratch): launch i draws tickets from set
     // i % 2 and zeroes the other one for launch i + 1.
     to.tile_ctr = e->tile_ctr + (e->ctr_set ? 64 * 32 : 0);
@@ -506,12 +478,12 @@ static int launch_transform(JpegAmdEncoder *e, const ImageDesc &im, bool taps, i
     const bool stamped = e->stamp_next && e->stamps_dev && !taps;
     e->stamp_next = false;
     TilePlanes tp;
-    if (src == kTileSrcPlanar) {
+    if (src.layout == kSrcPlanar) {
         if (!ps) return (int)hipErrorInvalidValue;
         std::memcpy(tp.g, ps->p[1], sizeof(tp.g));
         std::memcpy(tp.b, ps->p[2], sizeof(tp.b));
     }
-    const TilePlanes *planes = src == kTileSrcPlanar ? &tp : nullptr;
+    const TilePlanes *planes = src.layout == kSrcPlanar ? &tp : nullptr;
     if (int err = stamped ? launch_tile_transform_stamped(im, to, taps, stream, ev ? (void *const *)ev : nullptr, src, planes)
                           : launch_tile_transform(im, to, taps, stream, (ev && !taps) ? (void *const *)ev : nullptr, src, planes)) return err;
     if (im.tile_end > im.tile_begin) e->ctr_set ^= 1;      // (an empty range launches nothing)
@@ -526,13 +498,13 @@ static int launch_transform(JpegAmdEncoder *e, const ImageDesc &im, bool taps, i
 
 // k_tile_encode, then k_segment_merge (block-row shards, stage taps).
 static int launch_transform_and_entropy(JpegAmdEncoder *e, const ImageDesc &im, bool taps, int8_t *ty, int16_t *tzz, uint64_t *tmask,
-                                        void *stream, hipEvent_t *ev = nullptr /*4: begin/end of the two kernels*/, int src = kTileSrcRgb,
+                                        void *stream, hipEvent_t *ev = nullptr /*4: begin/end of the two kernels*/, TileSource src = {},
                                         const PlaneSet *ps = nullptr) {
     if (int err = launch_transform(e, im, taps, ty, tzz, tmask, stream, ev, src, ps)) return err;
     MergeArgs ea;
     std::memset(&ea, 0, sizeof(ea));
     ea.tile_head = e->tile_head; ea.tile_over = e->tile_over;
-    ea.huff = tile_src_is_chroma(src) ? e->color.huff : e->huff; ea.num_segs = im.num_segs; ea.segs_per_row = im.segs_per_row; ea.tiles_per_row = im.tiles_per_row;
+    ea.huff = src.chroma ? e->color.huff : e->huff; ea.num_segs = im.num_segs; ea.segs_per_row = im.segs_per_row; ea.tiles_per_row = im.tiles_per_row;
     ea.seg_tiles = im.seg_tiles;
     ea.seg_begin = im.seg_begin; ea.seg_end = im.seg_end;
     ea.tiles_per_image = im.batch > 1 ? im.num_tiles : 0;
@@ -550,17 +522,19 @@ struct ScanTarget {
     bool chroma;
 };
 
-static int run_finalize_batch(JpegAmdEncoder *e, const ImageDesc &im, void *const *outs_dev, uint64_t out_capacity,
-                              uint64_t *const *out_sizes_dev, int32_t with_container, hipStream_t stream, hipEvent_t *ev = nullptr,
-                              const ScanTarget *tgt = nullptr) {
+// k_finalize over the segments k_segment_merge (or an import) left: `batch` pictures.  `use_groups`: the group aggregates are valid
+// -- whole pictures merged on this context whose segments fill whole groups, so that every picture starts on a group boundary;
+// segments imported from other ranks have none.
+static int run_finalize(JpegAmdEncoder *e, const ImageDesc &im, void *const *outs_dev, uint64_t out_capacity, uint64_t *const *out_sizes_dev,
+                        int32_t with_container, hipStream_t stream, hipEvent_t *ev, int batch, bool use_groups, const ScanTarget *tgt = nullptr) {
     FinalizeArgs fa;
     std::memset(&fa, 0, sizeof(fa));
     fa.seg = e->seg;
     fa.seg.words_stride = (uint32_t)seg_cap_words(im.seg_tiles);
     fa.num_segs = im.num_segs; fa.num_chunks = finalize_chunks(im.num_segs);
-    fa.batch = im.batch;
-    fa.use_groups = (im.num_segs % kSegGroup == 0) ? 1 : 0;      // every image then starts on a group boundary
-    for (int i = 0; i < im.batch; ++i) { fa.out[i] = (uint8_t *)outs_dev[i]; fa.out_size[i] = out_sizes_dev[i]; }
+    fa.batch = batch;
+    fa.use_groups = use_groups ? 1 : 0;
+    for (int i = 0; i < batch; ++i) { fa.out[i] = (uint8_t *)outs_dev[i]; fa.out_size[i] = out_sizes_dev[i]; }
     fa.out_capacity = out_capacity; fa.stats = e->stats_dev;
     fa.prefix = e->prefix; fa.prefix_len = with_container ? JPEGAMD_JFIF_PREFIX_BYTES : 0;
     fa.write_eoi = with_container ? 1 : 0;
@@ -610,21 +584,45 @@ static int run_stitch(JpegAmdEncoder *e, const ImageDesc &im, void *const *outs_
     return launch_stitch(sa, stream, (void *const *)ev);
 }
 
-static int run_finalize(JpegAmdEncoder *e, const ImageDesc &im, void *out_dev, uint64_t out_capacity, uint64_t *out_size_dev,
-                        int32_t with_container, hipStream_t stream, hipEvent_t *ev = nullptr, bool groups_valid = false,
-                        const ScanTarget *tgt = nullptr) {
-    FinalizeArgs fa;
-    std::memset(&fa, 0, sizeof(fa));
-    fa.seg = e->seg;
-    fa.seg.words_stride = (uint32_t)seg_cap_words(im.seg_tiles);
-    fa.num_segs = im.num_segs; fa.num_chunks = finalize_chunks(im.num_segs);
-    fa.batch = 1;
-    fa.use_groups = groups_valid ? 1 : 0;       // (segments imported from other ranks have no group aggregates)
-    fa.out[0] = (uint8_t *)out_dev; fa.out_capacity = out_capacity; fa.out_size[0] = out_size_dev; fa.stats = e->stats_dev;
-    fa.prefix = e->prefix; fa.prefix_len = with_container ? JPEGAMD_JFIF_PREFIX_BYTES : 0;
-    fa.write_eoi = with_container ? 1 : 0;
-    if (tgt) { fa.prefix = tgt->prefix; fa.prefix_len = tgt->prefix_len; fa.write_eoi = tgt->write_eoi; fa.stats = tgt->stats; }
-    return launch_finalize(fa, stream, (void *const *)ev);
+// "Code the tiles of this ImageDesc": k_tile_encode, [k_picture_stats over its records,] then k_stitch, or k_segment_merge +
+// k_finalize.  `ev`: begin / end of the first two kernels (4, or null), `ev_out`: of k_stitch or k_finalize (2, or null).
+// `tgt` (a scan of a colour file): its own header bytes, EOI and statistics record instead of the grayscale container.
+static int code_tiles(JpegAmdEncoder *e, const ImageDesc &im, TileSource src, const PlaneSet *ps, const PictureStatsArgs *pstats,
+                      void *const *outs_dev, uint64_t out_capacity, uint64_t *const *out_sizes_dev, int32_t with_container,
+                      const ScanTarget *tgt, bool stitch, hipStream_t stream, hipEvent_t *ev, hipEvent_t *ev_out) {
+    if (int err = stitch ? launch_transform(e, im, false, nullptr, nullptr, nullptr, stream, ev, src, ps)
+                         : launch_transform_and_entropy(e, im, false, nullptr, nullptr, nullptr, stream, ev, src, ps)) return err;
+    if (pstats) if (int err = launch_picture_stats(*pstats, stream)) return err;
+    return stitch ? run_stitch(e, im, outs_dev, out_capacity, out_sizes_dev, with_container, stream, ev_out, tgt)
+                  : run_finalize(e, im, outs_dev, out_capacity, out_sizes_dev, with_container, stream, ev_out, im.batch, im.num_segs % kSegGroup == 0, tgt);
+}
+
+// The next slot of the profiling ring for this call: *ev its events -- a gray call's six, or a colour call's 22 (made on the slot's
+// first colour call) -- or null when profiling is off.  `flag`: a gray call has a k_segment_merge; a colour call is a batch.
+static int32_t claim_slot(JpegAmdEncoder *e, bool color, bool flag, hipEvent_t **ev) {
+    *ev = nullptr;
+    if (e->ring.empty()) return JPEGAMD_OK;
+    e->last_slot = (int)(e->calls % e->ring.size());
+    auto &set = e->ring[(size_t)e->last_slot];
+    if (color && set.cev.empty()) {
+        set.cev.assign(22, nullptr);
+        for (auto &v : set.cev) HIP_TRY(hipEventCreate(&v));
+    }
+    set.color = color;
+    (color ? set.cbatch : set.merged) = flag;
+    *ev = color ? set.cev.data() : set.ev;
+    ++e->calls;
+    return JPEGAMD_OK;
+}
+
+// The bookkeeping behind every enqueued call: what jpegamd_encoder_finish waits for and reads.  segs < 0: the count stays.
+static int32_t enqueued(JpegAmdEncoder *e, hipStream_t stream, int segs, bool timed = false, bool color = false) {
+    if (segs >= 0) e->last_segs = segs;
+    e->last_stream = stream;
+    e->pending = true;
+    e->timed = timed;
+    e->last_color = color;      // a colour call summed its statistics already (k_append_scans)
+    return JPEGAMD_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -657,11 +655,7 @@ extern "C" int32_t jpegamd_encode_rows_async(JpegAmdEncoder *e, const JpegAmdIma
     im.seg_end = block_row_end * im.segs_per_row;
     hipStream_t stream = (hipStream_t)stream_;
     if (launch_transform_and_entropy(e, im, false, nullptr, nullptr, nullptr, stream, nullptr, src_of(img))) return JPEGAMD_ERR_HIP;
-    e->last_segs = im.num_segs;
-    e->last_stream = stream;
-    e->pending = true; e->last_color = false;
-    e->timed = false;
-    return JPEGAMD_OK;
+    return enqueued(e, stream, im.num_segs);
 }
 
 static int32_t exchange_args(JpegAmdEncoder *e, const JpegAmdImage *img, int32_t by0, int32_t by1, uint32_t *dense, uint64_t cap,
@@ -687,8 +681,7 @@ extern "C" int32_t jpegamd_export_segments(JpegAmdEncoder *e, const JpegAmdImage
     int32_t rc = exchange_args(e, img, block_row_begin, block_row_end, dense_words_dev, dense_capacity_words, meta_dev, total_words_dev, &x);
     if (rc) return rc;
     if (launch_seg_export(x, stream)) return JPEGAMD_ERR_HIP;
-    e->last_stream = (hipStream_t)stream; e->pending = true; e->last_color = false; e->timed = false;
-    return JPEGAMD_OK;
+    return enqueued(e, (hipStream_t)stream, -1);
 }
 
 extern "C" int32_t jpegamd_import_segments(JpegAmdEncoder *e, const JpegAmdImage *img, int32_t block_row_begin, int32_t block_row_end,
@@ -698,8 +691,7 @@ extern "C" int32_t jpegamd_import_segments(JpegAmdEncoder *e, const JpegAmdImage
                                const_cast<uint32_t *>(meta_dev), nullptr, &x);
     if (rc) return rc;
     if (launch_seg_import(x, stream)) return JPEGAMD_ERR_HIP;
-    e->last_stream = (hipStream_t)stream; e->pending = true; e->last_color = false; e->timed = false;
-    return JPEGAMD_OK;
+    return enqueued(e, (hipStream_t)stream, -1);
 }
 
 extern "C" int32_t jpegamd_finalize_async(JpegAmdEncoder *e, const JpegAmdImage *img, void *out_dev, uint64_t out_capacity,
@@ -711,49 +703,10 @@ extern "C" int32_t jpegamd_finalize_async(JpegAmdEncoder *e, const JpegAmdImage 
     rc = prepare_constants(e, img, with_container != 0);
     if (rc) return rc;
     hipStream_t stream = (hipStream_t)stream_;
-    if (run_finalize(e, im, out_dev, out_capacity, out_size_dev, with_container, stream)) return JPEGAMD_ERR_HIP;
-    e->last_segs = im.num_segs;
-    e->last_stream = stream;
-    e->pending = true; e->last_color = false;
-    e->timed = false;
-    return JPEGAMD_OK;
-}
-
-extern "C" int32_t jpegamd_encode_async(JpegAmdEncoder *e, const JpegAmdImage *img, void *out_dev,
-                                        uint64_t out_capacity, uint64_t *out_size_dev, int32_t with_container,
-                                        void *stream_) {
-    if (!e || !out_dev || !out_size_dev) return JPEGAMD_ERR_ARG;
-    ImageDesc im;
-    const bool stitch = use_stitch(e, img ? img->width : 0, img ? img->height : 0);
-    int32_t rc = describe(e, img, &im, stitch ? kSegTilesBatch : kSegTiles, kAcceptPx4);   // (k_stitch works on segments of 16 tiles)
-    if (rc) return rc;
-    rc = prepare_constants(e, img, with_container != 0);
-    if (rc) return rc;
-    hipStream_t stream = (hipStream_t)stream_;
-
-    const bool timed = !e->ring.empty();
-    hipEvent_t *ev = nullptr;
-    if (timed) {
-        e->last_slot = (int)(e->calls % e->ring.size());
-        ev = e->ring[(size_t)e->last_slot].ev;
-        ++e->calls;
-    }
-    if (timed) { e->ring[(size_t)e->last_slot].merged = !stitch; e->ring[(size_t)e->last_slot].color = false; }
-    if (stitch) {
-        if (launch_transform(e, im, false, nullptr, nullptr, nullptr, stream, ev, src_of(img))) return JPEGAMD_ERR_HIP;
-        void *const outs[1] = {out_dev};
-        uint64_t *const sizes[1] = {out_size_dev};
-        if (run_stitch(e, im, outs, out_capacity, sizes, with_container, stream, ev ? ev + 4 : nullptr)) return JPEGAMD_ERR_HIP;
-    } else {
-        if (launch_transform_and_entropy(e, im, false, nullptr, nullptr, nullptr, stream, ev, src_of(img))) return JPEGAMD_ERR_HIP;
-        if (run_finalize(e, im, out_dev, out_capacity, out_size_dev, with_container, stream, ev ? ev + 4 : nullptr,
-                         im.num_segs % kSegGroup == 0)) return JPEGAMD_ERR_HIP;
-    }
-    e->last_segs = im.num_segs;
-    e->last_stream = stream;
-    e->pending = true; e->last_color = false;
-    e->timed = timed;
-    return JPEGAMD_OK;
+    void *const outs[1] = {out_dev};
+    uint64_t *const sizes[1] = {out_size_dev};
+    if (run_finalize(e, im, outs, out_capacity, sizes, with_container, stream, nullptr, 1, false)) return JPEGAMD_ERR_HIP;
+    return enqueued(e, stream, im.num_segs);
 }
 
 // `count` images of one geometry through ONE launch of each kernel (see the header): image i's tiles are
@@ -766,52 +719,60 @@ static bool planes_aligned(const PlaneSet &ps, int count, int order) {
     return (bits & 3u) == 0;
 }
 
+// The launch plan of `count` pictures like g0, pixels in ps, coded as ONE batch (a grayscale batch, the Y scans of a colour batch):
+// segments of 16 tiles for k_stitch and from four pictures on (jpegamd_internal.h) -- of 8 after all when the context's words do
+// not hold the longer ones (a geometry other than its own) -- then whether the whole batch fits the context.
+static int32_t plan_batch(const JpegAmdEncoder *e, const JpegAmdImage &g0, const PlaneSet &ps, int32_t count, ImageDesc *im, bool *stitch) {
+    const int accept = g0.channel_order == kOrderPlanar ? kAcceptPlanar : kAcceptPx4;
+    *stitch = use_stitch(e, g0.width, g0.height);
+    int seg_tiles = (*stitch || count >= 4) ? kSegTilesBatch : kSegTiles;
+    const auto words = [&]() { return (size_t)count * im->num_segs * seg_cap_words(seg_tiles); };
+    if (int32_t rc = describe(e, &g0, im, seg_tiles, accept)) return rc;
+    if (!*stitch && seg_tiles != kSegTiles && words() > e->words_cap) {
+        seg_tiles = kSegTiles;
+        if (int32_t rc = describe(e, &g0, im, seg_tiles, accept)) return rc;
+    }
+    if ((int64_t)count * im->num_tiles > e->max_tiles || (int64_t)count * im->num_segs > e->max_segs || (!*stitch && words() > e->words_cap))
+        return JPEGAMD_ERR_TOO_LARGE;
+    for (int i = 0; i < count; ++i) im->batch_pixels[i] = ps.p[0][i];
+    if (!planes_aligned(ps, count, g0.channel_order)) im->fast_ok = 0;
+    im->batch = count;
+    im->tile_end = count * im->num_tiles;
+    im->seg_end = count * im->num_segs;
+    return JPEGAMD_OK;
+}
+
 // The grayscale files of a batch whose arguments are known to be good: g0 describes every picture, ps holds their pixels.
 static int32_t gray_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, const PlaneSet &ps, int32_t count, void *const *outs_dev,
                           uint64_t out_capacity, uint64_t *const *out_sizes_dev, int32_t with_container, void *stream_) {
     ImageDesc im;
-    const JpegAmdImage *imgs = &g0;
-    const int accept = g0.channel_order == kOrderPlanar ? kAcceptPlanar : kAcceptPx4;
-    const bool stitch = use_stitch(e, imgs[0].width, imgs[0].height);
-    int seg_tiles = (stitch || count >= 4) ? kSegTilesBatch : kSegTiles;  // many pictures: longer segments (jpegamd_internal.h); k_stitch: always
-    int32_t rc = describe(e, &imgs[0], &im, seg_tiles, accept);
+    bool stitch;
+    int32_t rc = plan_batch(e, g0, ps, count, &im, &stitch);
     if (rc) return rc;
-    if (!stitch && seg_tiles != kSegTiles && (size_t)count * im.num_segs * seg_cap_words(seg_tiles) > e->words_cap) {   // (a geometry other than the context's own)
-        seg_tiles = kSegTiles;
-        rc = describe(e, &imgs[0], &im, seg_tiles, accept);
-        if (rc) return rc;
-    }
-    for (int i = 0; i < count; ++i) im.batch_pixels[i] = ps.p[0][i];
-    if (!planes_aligned(ps, count, g0.channel_order)) im.fast_ok = 0;
-    if ((int64_t)count * im.num_tiles > e->max_tiles || (int64_t)count * im.num_segs > e->max_segs ||
-        (!stitch && (size_t)count * im.num_segs * seg_cap_words(seg_tiles) > e->words_cap)) return JPEGAMD_ERR_TOO_LARGE;
-    im.batch = count;
-    im.tile_end = count * im.num_tiles;
-    im.seg_end = count * im.num_segs;
-    rc = prepare_constants(e, &imgs[0], with_container != 0);
+    rc = prepare_constants(e, &g0, with_container != 0);
     if (rc) return rc;
     hipStream_t stream = (hipStream_t)stream_;
+    hipEvent_t *ev;
+    rc = claim_slot(e, false, !stitch, &ev);
+    if (rc) return rc;
+    if (code_tiles(e, im, src_of(&g0), &ps, nullptr, outs_dev, out_capacity, out_sizes_dev, with_container, nullptr, stitch, stream, ev,
+                   ev ? ev + 4 : nullptr)) return JPEGAMD_ERR_HIP;
+    return enqueued(e, stream, count * im.num_segs, ev != nullptr);
+}
 
-    const bool timed = !e->ring.empty();
-    hipEvent_t *ev = nullptr;
-    if (timed) {
-        e->last_slot = (int)(e->calls % e->ring.size());
-        ev = e->ring[(size_t)e->last_slot].ev;
-        ++e->calls;
-    }
-    if (timed) { e->ring[(size_t)e->last_slot].merged = !stitch; e->ring[(size_t)e->last_slot].color = false; }
-    if (stitch) {
-        if (launch_transform(e, im, false, nullptr, nullptr, nullptr, stream, ev, src_of(imgs), &ps)) return JPEGAMD_ERR_HIP;
-        if (run_stitch(e, im, outs_dev, out_capacity, out_sizes_dev, with_container, stream, ev ? ev + 4 : nullptr)) return JPEGAMD_ERR_HIP;
-    } else {
-        if (launch_transform_and_entropy(e, im, false, nullptr, nullptr, nullptr, stream, ev, src_of(imgs), &ps)) return JPEGAMD_ERR_HIP;
-        if (run_finalize_batch(e, im, outs_dev, out_capacity, out_sizes_dev, with_container, stream, ev ? ev + 4 : nullptr)) return JPEGAMD_ERR_HIP;
-    }
-    e->last_segs = count * im.num_segs;
-    e->last_stream = stream;
-    e->pending = true; e->last_color = false;
-    e->timed = timed;
-    return JPEGAMD_OK;
+// One picture: the argument checks, then a batch of one.
+extern "C" int32_t jpegamd_encode_async(JpegAmdEncoder *e, const JpegAmdImage *img, void *out_dev,
+                                        uint64_t out_capacity, uint64_t *out_size_dev, int32_t with_container,
+                                        void *stream_) {
+    if (!e || !out_dev || !out_size_dev) return JPEGAMD_ERR_ARG;
+    ImageDesc im;
+    int32_t rc = describe(nullptr, img, &im, kSegTiles, kAcceptPx4);      // (the arguments alone: the context is looked at by gray_batch)
+    if (rc) return rc;
+    PlaneSet ps = {};
+    ps.p[0][0] = (const uint8_t *)img->pixels;
+    void *const outs[1] = {out_dev};
+    uint64_t *const sizes[1] = {out_size_dev};
+    return gray_batch(e, *img, ps, 1, outs, out_capacity, sizes, with_container, stream_);
 }
 
 extern "C" int32_t jpegamd_encode_batch_async(JpegAmdEncoder *e, const JpegAmdImage *imgs, int32_t count, void *const *outs_dev,
@@ -881,7 +842,7 @@ static int32_t color_alloc(JpegAmdEncoder *e, int w, int h) {
 
 static int32_t prepare_color_constants(JpegAmdEncoder *e, const JpegAmdImage *img, int sub) {
     auto &c = e->color;
-    const int q = (img->quality <= 0) ? 50 : (img->quality > 100 ? 100 : img->quality);
+    const int q = clamp_quality(img->quality);
     if (q != c.cur_quality) {
         uint8_t t[64];
         chroma_quant_table_for_quality(q, t);
@@ -907,17 +868,11 @@ static int32_t prepare_color_constants(JpegAmdEncoder *e, const JpegAmdImage *im
 }
 
 // One scan of the colour file: k_tile_encode, then k_segment_merge + k_finalize or k_stitch, then the scan's symbol sums.
-static int run_scan(JpegAmdEncoder *e, const ImageDesc &im, int src, void *out, uint64_t cap, uint64_t *size_dev, const ScanTarget &tgt,
+static int run_scan(JpegAmdEncoder *e, const ImageDesc &im, TileSource src, void *out, uint64_t cap, uint64_t *size_dev, const ScanTarget &tgt,
                     bool stitch, hipStream_t stream, hipEvent_t *ev) {
-    if (stitch) {
-        if (int err = launch_transform(e, im, false, nullptr, nullptr, nullptr, stream, ev, src)) return err;
-        void *const outs[1] = {out};
-        uint64_t *const sizes[1] = {size_dev};
-        if (int err = run_stitch(e, im, outs, cap, sizes, 1, stream, ev ? ev + 4 : nullptr, &tgt)) return err;
-    } else {
-        if (int err = launch_transform_and_entropy(e, im, false, nullptr, nullptr, nullptr, stream, ev, src)) return err;
-        if (int err = run_finalize(e, im, out, cap, size_dev, 1, stream, ev ? ev + 4 : nullptr, im.num_segs % kSegGroup == 0, &tgt)) return err;
-    }
+    void *const outs[1] = {out};
+    uint64_t *const sizes[1] = {size_dev};
+    if (int err = code_tiles(e, im, src, nullptr, nullptr, outs, cap, sizes, 1, &tgt, stitch, stream, ev, ev ? ev + 4 : nullptr)) return err;
     return launch_sum_stats(e->seg.syms, e->seg.exact, im.num_segs, tgt.stats, stream);
 }
 
@@ -947,19 +902,10 @@ extern "C" int32_t jpegamd_encode_color_async(JpegAmdEncoder *e, const JpegAmdIm
     auto &c = e->color;
     hipStream_t stream = (hipStream_t)stream_;
 
-    const bool timed = !e->ring.empty();
-    hipEvent_t *cev = nullptr;
-    if (timed) {
-        e->last_slot = (int)(e->calls % e->ring.size());
-        auto &set = e->ring[(size_t)e->last_slot];
-        if (set.cev.empty()) {
-            set.cev.assign(22, nullptr);
-            for (auto &ev : set.cev) HIP_TRY(hipEventCreate(&ev));
-        }
-        set.color = true; set.cbatch = false;
-        cev = set.cev.data();
-        ++e->calls;
-    }
+    hipEvent_t *cev;
+    rc = claim_slot(e, true, false, &cev);
+    if (rc) return rc;
+    const bool timed = cev != nullptr;
     HIP_TRY(hipMemsetAsync(c.scan_stats, 0, 3 * sizeof(ScanStats), stream));
 
     ChromaPlanesArgs pa;
@@ -974,7 +920,7 @@ extern "C" int32_t jpegamd_encode_color_async(JpegAmdEncoder *e, const JpegAmdIm
     // Y: the grayscale scan of the same picture, behind the colour prefix, no EOI
     const ScanTarget ty = {c.hdr, c.hdr_len, 0, &c.scan_stats[0], false};
     if (timed) e->ring[(size_t)e->last_slot].cmerged[0] = !stitch_y;
-    if (run_scan(e, iy, kTileSrcRgb, out_dev, out_capacity, &c.scan_size[0], ty, stitch_y, stream, cev ? cev + 2 : nullptr))
+    if (run_scan(e, iy, TileSource{kSrcRgb}, out_dev, out_capacity, &c.scan_size[0], ty, stitch_y, stream, cev ? cev + 2 : nullptr))
         return JPEGAMD_ERR_HIP;
     // Cb, Cr: one-byte planes, chroma tables, into scratch
     JpegAmdImage pimg = *img;
@@ -987,7 +933,7 @@ extern "C" int32_t jpegamd_encode_color_async(JpegAmdEncoder *e, const JpegAmdIm
         if (rc) return rc;
         const ScanTarget tc = {c.hdr + kColorPrefixMax + 16 * k, kSosBytes, k, &c.scan_stats[1 + k], true};
         if (timed) e->ring[(size_t)e->last_slot].cmerged[1 + k] = !stitch_c;
-        if (run_scan(e, ic, kTileSrcChroma, c.scans + (size_t)k * c.scan_cap, c.scan_cap, &c.scan_size[1 + k], tc, stitch_c, stream,
+        if (run_scan(e, ic, TileSource{kSrcPlane, true}, c.scans + (size_t)k * c.scan_cap, c.scan_cap, &c.scan_size[1 + k], tc, stitch_c, stream,
                      cev ? cev + 8 + 6 * k : nullptr))
             return JPEGAMD_ERR_HIP;
     }
@@ -996,12 +942,7 @@ extern "C" int32_t jpegamd_encode_color_async(JpegAmdEncoder *e, const JpegAmdIm
     aa.scan_size = c.scan_size; aa.src[0] = c.scans; aa.src[1] = c.scans + c.scan_cap;
     aa.scan_stats = c.scan_stats; aa.stats = e->stats_dev;
     if (launch_append_scans(aa, stream, cev ? (void *const *)(cev + 20) : nullptr)) return JPEGAMD_ERR_HIP;
-    e->last_segs = iy.num_segs;
-    e->last_stream = stream;
-    e->pending = true;
-    e->timed = timed;
-    e->last_color = true;
-    return JPEGAMD_OK;
+    return enqueued(e, stream, iy.num_segs, timed, true);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -1019,8 +960,7 @@ constexpr int kBatchLaunches = 1 + 2 * kMaxBatch;     // the Y launch, and at mo
 // even one plane fits.
 struct ChromaPlan { int group, launches, seg_tiles; bool stitch; };
 static int chroma_group_limit(const CtxLimits &l, int cw, int ch, int seg_tiles, bool stitch) {
-    const int64_t bw = (cw + 7) / 8, bh = (ch + 7) / 8;
-    const int64_t tiles = bh * ((bw + kTileBlocks - 1) / kTileBlocks);
+    const int64_t tiles = tiles_for(cw, ch);
     const int64_t segs = segs_for(cw, ch, nullptr, nullptr, nullptr, seg_tiles);
     int64_t g = kMaxBatch;
     g = std::min(g, (int64_t)l.max_tiles / tiles);
@@ -1091,19 +1031,56 @@ static int32_t color_batch_alloc(JpegAmdEncoder *e, size_t planes, size_t scans)
 }
 
 // The caller's own chroma (jpegamd_encode_ycbcr_batch_async): cb[i] / cr[i] the planes of picture i (a pair layout: cb[i] alone; a
-// packed 4:2:2 layout: cb[i] is the packed plane -- the picture's y -- and c_stride its row stride).
-// `expand`: the samples are limited range (JPEGAMD_RANGE_LIMITED) -- the Y and the chroma launches take the kTileSrc*Expand twin of their source.
-// `format`: JPEGAMD_SAMPLES_* -- with a 16-bit format the Y and the chroma launches read 16-bit words through the kTileSrc*16 sources, which
-// narrow every sample on read (either range), and ImageDesc::weights carries the alignment shift.
+// packed 4:2:2 layout: cb[i] is the packed plane -- the picture's y -- and c_stride its row stride).  layout, format and range
+// (JPEGAMD_CHROMA_*, _SAMPLES_*, _RANGE_*) choose the sources of the launches: ycbcr_y_source, ycbcr_chroma_source.
 struct YccSource {
-    int32_t layout, c_stride;
-    bool expand;
-    int32_t format;
+    int32_t layout, c_stride, format, range;
     const uint8_t *cb[kMaxBatch], *cr[kMaxBatch];
 };
 
-// The right shift that leaves the 10-bit value of a 16-bit sample word (JPEGAMD_SAMPLES_10_MSB: 6; _LSB: 0, then clamped to 1023).
+// The kinds of YCbCr input that are taken: a known layout, format and range; a packed layout in one byte per sample (Y210: not taken).
+static bool ycbcr_kind_valid(int32_t layout, int32_t format, int32_t range) {
+    if (range != JPEGAMD_RANGE_FULL && range != JPEGAMD_RANGE_LIMITED) return false;
+    if (format != JPEGAMD_SAMPLES_8 && format != JPEGAMD_SAMPLES_10_MSB && format != JPEGAMD_SAMPLES_10_LSB) return false;
+    if (layout != JPEGAMD_CHROMA_PLANES && layout != JPEGAMD_CHROMA_CBCR && layout != JPEGAMD_CHROMA_CRCB && !is_packed422(layout)) return false;
+    return !(is_packed422(layout) && format != JPEGAMD_SAMPLES_8);
+}
+
+// What the launches of a YCbCr batch read: the source, and ImageDesc::select (a source that does not read it keeps describe()'s).
+// 16-bit words are narrowed on read whichever the range; the shift that leaves the 10-bit value is 6 (MSB-aligned) or 0.
+struct SourceChoice { TileSource src; uint32_t select; };
 static uint32_t depth_shift(int32_t format) { return format == JPEGAMD_SAMPLES_10_MSB ? 6u : 0u; }
+// The Y launch: a plane of samples; of a packed plane byte 0 (Y Cb Y Cr) or 1 (Cb Y Cr Y) of every pair, for EVERY picture.
+static SourceChoice ycbcr_y_source(int32_t layout, int32_t format, int32_t range) {
+    const bool expand = range == JPEGAMD_RANGE_LIMITED;
+    if (format != JPEGAMD_SAMPLES_8) return {{kSrcPlane16, false, expand}, select_depth(0, depth_shift(format))};
+    if (is_packed422(layout)) return {{kSrcPair, false, expand}, select_byte(layout == JPEGAMD_CHROMA_UYVY ? 1 : 0, 0)};
+    return {{kSrcPlane, false, expand}, select_luma(false)};
+}
+// A chroma launch whose first plane has index `first` in the WHOLE call (picture first / 2; Cb even, Cr odd): a group may be odd, a
+// launch then starts on a Cr plane.  The parity is flipped when Cr is stored first; a packed plane has Cb in front of Cr, at bytes
+// 1 and 3 (Y Cb Y Cr) or 0 and 2 (Cb Y Cr Y).
+static SourceChoice ycbcr_chroma_source(int32_t layout, int32_t format, int32_t range, int first) {
+    const bool expand = range == JPEGAMD_RANGE_LIMITED, wide = format != JPEGAMD_SAMPLES_8;
+    const uint32_t parity = (uint32_t)((first & 1) ^ (layout == JPEGAMD_CHROMA_CRCB ? 1 : 0));
+    if (is_packed422(layout)) return {{kSrcQuad, true, expand}, select_byte(parity, layout == JPEGAMD_CHROMA_YUYV ? 1 : 0)};
+    if (layout == JPEGAMD_CHROMA_PLANES)
+        return wide ? SourceChoice{{kSrcPlane16, true, expand}, select_depth(0, depth_shift(format))} : SourceChoice{{kSrcPlane, true, expand}, select_luma(false)};
+    return wide ? SourceChoice{{kSrcPair16, true, expand}, select_depth(parity, depth_shift(format))} : SourceChoice{{kSrcPair, true, expand}, select_byte(parity, 0)};
+}
+
+// Host-only (tests): the two functions above for one kind of input: out = {layout, chroma, expand, select} of the Y launch, then of
+// a chroma launch that starts on plane `first`.  JPEGAMD_ERR_ARG for a kind the encode entry refuses.  Not part of the public header.
+extern "C" int32_t jpegamd_debug_ycbcr_sources(int32_t chroma_layout, int32_t sample_format, int32_t sample_range, int32_t first, uint32_t *out) {
+    if (!out || first < 0 || !ycbcr_kind_valid(chroma_layout, sample_format, sample_range)) return JPEGAMD_ERR_ARG;
+    const SourceChoice both[2] = {ycbcr_y_source(chroma_layout, sample_format, sample_range),
+                                  ycbcr_chroma_source(chroma_layout, sample_format, sample_range, first)};
+    for (int k = 0; k < 2; ++k) {
+        out[4 * k] = (uint32_t)both[k].src.layout; out[4 * k + 1] = both[k].src.chroma; out[4 * k + 2] = both[k].src.expand;
+        out[4 * k + 3] = both[k].select;
+    }
+    return JPEGAMD_OK;
+}
 
 // The colour files of a batch whose arguments are known to be good: g0 describes every picture, ps holds their pixels.
 // `ycc` (a YCbCr batch): g0 / px are the Y planes as a GRAY picture, the chroma scans read the caller's planes -- no
@@ -1113,23 +1090,9 @@ static int32_t color_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, const Plan
                            const YccSource *ycc = nullptr) {
     // Y: the grayscale batch's launch plan
     ImageDesc iy;
-    const bool stitch_y = use_stitch(e, g0.width, g0.height);
-    int seg_tiles = (stitch_y || count >= 4) ? kSegTilesBatch : kSegTiles;
-    const int accept = g0.channel_order == kOrderPlanar ? kAcceptPlanar : kAcceptPx4;
-    int32_t rc = describe(e, &g0, &iy, seg_tiles, accept);
+    bool stitch_y;
+    int32_t rc = plan_batch(e, g0, px, count, &iy, &stitch_y);
     if (rc) return rc;
-    if (!stitch_y && seg_tiles != kSegTiles && (size_t)count * iy.num_segs * seg_cap_words(seg_tiles) > e->words_cap) {
-        seg_tiles = kSegTiles;
-        rc = describe(e, &g0, &iy, seg_tiles, accept);
-        if (rc) return rc;
-    }
-    if ((int64_t)count * iy.num_tiles > e->max_tiles || (int64_t)count * iy.num_segs > e->max_segs ||
-        (!stitch_y && (size_t)count * iy.num_segs * seg_cap_words(seg_tiles) > e->words_cap)) return JPEGAMD_ERR_TOO_LARGE;
-    for (int i = 0; i < count; ++i) iy.batch_pixels[i] = px.p[0][i];
-    if (!planes_aligned(px, count, g0.channel_order)) iy.fast_ok = 0;
-    iy.batch = count;
-    iy.tile_end = count * iy.num_tiles;
-    iy.seg_end = count * iy.num_segs;
     // Cb, Cr: 2 count planes at one pitch, in as few launches as the context allows
     int cw, ch;
     chroma_dims(g0.width, g0.height, subsampling, &cw, &ch);
@@ -1155,19 +1118,9 @@ static int32_t color_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, const Plan
     uint64_t *c_size = y_size + kMaxBatch;
     hipStream_t stream = (hipStream_t)stream_;
 
-    const bool timed = !e->ring.empty();
-    hipEvent_t *cev = nullptr;
-    if (timed) {
-        e->last_slot = (int)(e->calls % e->ring.size());
-        auto &set = e->ring[(size_t)e->last_slot];
-        if (set.cev.empty()) {
-            set.cev.assign(22, nullptr);
-            for (auto &ev : set.cev) HIP_TRY(hipEventCreate(&ev));
-        }
-        set.color = true; set.cbatch = true;
-        cev = set.cev.data();
-        ++e->calls;
-    }
+    hipEvent_t *cev;
+    rc = claim_slot(e, true, true, &cev);
+    if (rc) return rc;
     HIP_TRY(hipMemsetAsync(c.bmeta, 0, kBatchMetaStats + kBatchMetaPic, stream));
 
     hipEvent_t *const ev_y = ycc ? cev : nullptr;     // a YCbCr batch begins with its Y launch: that kernel's begin stamp opens ns_total
@@ -1192,37 +1145,23 @@ static int32_t color_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, const Plan
         for (int i = 0; i < count; ++i) sizes[i] = y_size + i;
         const ScanTarget ty = {c.hdr, c.hdr_len, 0, &lstats[0], false};
         PictureStatsArgs ps = {e->tile_head, e->huff, iy.num_tiles, count, 0, 0, pic};
-        // a packed 4:2:2 plane: Y is one byte of every pair of the row -- byte 0 (Y Cb Y Cr) or byte 1 (Cb Y Cr Y) -- for EVERY picture
-        const bool packed = ycc && is_packed422(ycc->layout);
-        const bool wide = ycc && ycc->format != JPEGAMD_SAMPLES_8;    // 16-bit words: the shift that leaves the 10-bit value rides in weights bits 16..20
-        const int ysrc = wide ? (ycc->expand ? kTileSrcGray16Expand : kTileSrcGray16)
-                       : packed ? (ycc->expand ? kTileSrcLumaPairExpand : kTileSrcLumaPair) : ((ycc && ycc->expand) ? kTileSrcGrayExpand : src_of(&g0));
-        if (packed) iy.weights = ycc->layout == JPEGAMD_CHROMA_UYVY ? 1u : 0u;
-        if (wide) iy.weights = depth_shift(ycc->format) << 16;
-        if (stitch_y) {
-            if (launch_transform(e, iy, false, nullptr, nullptr, nullptr, stream, ev_y, ysrc, &px)) return JPEGAMD_ERR_HIP;
-            if (launch_picture_stats(ps, stream)) return JPEGAMD_ERR_HIP;
-            if (run_stitch(e, iy, outs_dev, out_capacity, sizes, 1, stream, nullptr, &ty)) return JPEGAMD_ERR_HIP;
-        } else {
-            if (launch_transform_and_entropy(e, iy, false, nullptr, nullptr, nullptr, stream, ev_y, ysrc, &px)) return JPEGAMD_ERR_HIP;
-            if (launch_picture_stats(ps, stream)) return JPEGAMD_ERR_HIP;
-            if (run_finalize_batch(e, iy, outs_dev, out_capacity, sizes, 1, stream, nullptr, &ty)) return JPEGAMD_ERR_HIP;
+        TileSource ysrc = src_of(&g0);
+        if (ycc) {
+            const SourceChoice y = ycbcr_y_source(ycc->layout, ycc->format, ycc->range);
+            ysrc = y.src; iy.select = y.select;
         }
+        if (code_tiles(e, iy, ysrc, &px, &ps, outs_dev, out_capacity, sizes, 1, &ty, stitch_y, stream, ev_y, nullptr)) return JPEGAMD_ERR_HIP;
     }
     // Cb, Cr: plane j (picture j / 2) bare into slot j; its size into c_size[j]
     JpegAmdImage pimg = g0;
     pimg.width = cw; pimg.height = ch; pimg.row_stride = pitch; pimg.bottom_up = 0; pimg.channel_order = JPEGAMD_ORDER_GRAY;
     pimg.pixels = c.bplanes;
-    int csrc = kTileSrcChroma;
     bool ycc_aligned = true;
-    const bool wide = ycc && ycc->format != JPEGAMD_SAMPLES_8;
+    const bool one_plane = ycc && ycc->layout != JPEGAMD_CHROMA_PLANES;      // Cb and Cr of a picture in ONE plane: pairs, or a packed plane
     if (ycc) {
         pimg.pixels = ycc->cb[0]; pimg.row_stride = ycc->c_stride;
-        const bool pair = ycc->layout != JPEGAMD_CHROMA_PLANES;      // (or a packed plane: one pointer per picture as well)
-        if (pair) csrc = is_packed422(ycc->layout) ? kTileSrcChromaQuad : kTileSrcChromaPair;
-        if (wide) csrc = pair ? kTileSrcChromaPair16 : kTileSrcChroma16;
         uintptr_t bits = 0;
-        for (int i = 0; i < count; ++i) bits |= (uintptr_t)ycc->cb[i] | (pair ? 0 : (uintptr_t)ycc->cr[i]);
+        for (int i = 0; i < count; ++i) bits |= (uintptr_t)ycc->cb[i] | (one_plane ? 0 : (uintptr_t)ycc->cr[i]);
         ycc_aligned = (bits & 3u) == 0;
     }
     for (int l = 0; l < plan.launches; ++l) {
@@ -1235,7 +1174,7 @@ static int32_t color_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, const Plan
         for (int i = 0; i < n; ++i) {
             const int j = first + i;                                   // the plane's index in the whole call: picture j / 2, Cb (even) or Cr (odd)
             if (!ycc) ic.batch_pixels[i] = c.bplanes + (size_t)j * plane_bytes;
-            else if (csrc != kTileSrcChroma && csrc != kTileSrcChroma16) ic.batch_pixels[i] = ycc->cb[j / 2];
+            else if (one_plane) ic.batch_pixels[i] = ycc->cb[j / 2];
             else ic.batch_pixels[i] = (j & 1) ? ycc->cr[j / 2] : ycc->cb[j / 2];
             outs[i] = c.bscans + (size_t)(first + i) * slot_bytes;
             sizes[i] = c_size + first + i;
@@ -1245,30 +1184,14 @@ static int32_t color_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, const Plan
         ic.tile_end = n * ic.num_tiles;
         ic.seg_end = n * ic.num_segs;
         if (!ycc_aligned) ic.fast_ok = 0;
-        // a pair plane: launch image i reads byte (weights + i) & 1 of each pair -- the parity of its plane in the WHOLE call (a group
-        // may be odd: a launch then starts on a Cr plane), flipped when Cr is stored first
-        if (csrc == kTileSrcChromaPair) ic.weights = (uint32_t)((first & 1) ^ (ycc->layout == JPEGAMD_CHROMA_CRCB ? 1 : 0));
-        // a packed plane: launch image i reads byte ((weights >> 8) & 1) + 2 ((weights + i) & 1) of each 4-byte group -- Cb in front of Cr,
-        // at bytes 1 and 3 (Y Cb Y Cr) or 0 and 2 (Cb Y Cr Y); bit 0 is the same parity rule
-        if (csrc == kTileSrcChromaQuad) ic.weights = (uint32_t)(first & 1) | (ycc->layout == JPEGAMD_CHROMA_YUYV ? 0x100u : 0u);
-        // 16-bit words: a pair plane keeps the parity rule in bit 0, the alignment shift rides in bits 16..20
-        if (csrc == kTileSrcChroma16) ic.weights = depth_shift(ycc->format) << 16;
-        if (csrc == kTileSrcChromaPair16) ic.weights = (uint32_t)((first & 1) ^ (ycc->layout == JPEGAMD_CHROMA_CRCB ? 1 : 0)) | (depth_shift(ycc->format) << 16);
-        // limited range: the same launch through the twin that expands on read
-        const int lsrc = !(ycc && ycc->expand) ? csrc : csrc == kTileSrcChromaPair ? kTileSrcChromaPairExpand
-                       : csrc == kTileSrcChromaQuad ? kTileSrcChromaQuadExpand : csrc == kTileSrcChroma16 ? kTileSrcChroma16Expand
-                       : csrc == kTileSrcChromaPair16 ? kTileSrcChromaPair16Expand : kTileSrcChromaExpand;
+        TileSource csrc = {kSrcPlane, true};
+        if (ycc) {
+            const SourceChoice cs = ycbcr_chroma_source(ycc->layout, ycc->format, ycc->range, first);
+            csrc = cs.src; ic.select = cs.select;
+        }
         const ScanTarget tc = {c.hdr, 0, 0, &lstats[1 + l], true};
         PictureStatsArgs ps = {e->tile_head, c.huff, ic.num_tiles, n, 1, first, pic};
-        if (plan.stitch) {
-            if (launch_transform(e, ic, false, nullptr, nullptr, nullptr, stream, nullptr, lsrc)) return JPEGAMD_ERR_HIP;
-            if (launch_picture_stats(ps, stream)) return JPEGAMD_ERR_HIP;
-            if (run_stitch(e, ic, outs, slot_bytes, sizes, 1, stream, nullptr, &tc)) return JPEGAMD_ERR_HIP;
-        } else {
-            if (launch_transform_and_entropy(e, ic, false, nullptr, nullptr, nullptr, stream, nullptr, lsrc)) return JPEGAMD_ERR_HIP;
-            if (launch_picture_stats(ps, stream)) return JPEGAMD_ERR_HIP;
-            if (run_finalize_batch(e, ic, outs, slot_bytes, sizes, 1, stream, nullptr, &tc)) return JPEGAMD_ERR_HIP;
-        }
+        if (code_tiles(e, ic, csrc, nullptr, &ps, outs, slot_bytes, sizes, 1, &tc, plan.stitch, stream, nullptr, nullptr)) return JPEGAMD_ERR_HIP;
     }
     AppendBatchArgs aa;
     std::memset(&aa, 0, sizeof(aa));
@@ -1283,12 +1206,7 @@ static int32_t color_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, const Plan
     aa.stats = e->stats_dev;
     hipEvent_t ev_append[2] = {nullptr, cev ? cev[21] : nullptr};
     if (launch_append_scans_batch(aa, stream, cev ? (void *const *)ev_append : nullptr)) return JPEGAMD_ERR_HIP;
-    e->last_segs = count * iy.num_segs;
-    e->last_stream = stream;
-    e->pending = true;
-    e->timed = timed;
-    e->last_color = true;
-    return JPEGAMD_OK;
+    return enqueued(e, stream, count * iy.num_segs, cev != nullptr, true);
 }
 
 extern "C" int32_t jpegamd_encode_color_batch_async(JpegAmdEncoder *e, const JpegAmdImage *imgs, int32_t count, int32_t subsampling,
@@ -1349,15 +1267,11 @@ extern "C" int32_t jpegamd_encode_ycbcr_samples_batch_async(JpegAmdEncoder *e, c
     // the arguments first: nothing of the context is read before they are known to be good
     if (!e || !imgs || !outs_dev || !out_sizes_dev || count < 1 || count > kMaxBatch) return JPEGAMD_ERR_ARG;
     if (!sub_valid(subsampling)) return JPEGAMD_ERR_ARG;
-    if (sample_range != JPEGAMD_RANGE_FULL && sample_range != JPEGAMD_RANGE_LIMITED) return JPEGAMD_ERR_ARG;
-    if (sample_format != JPEGAMD_SAMPLES_8 && sample_format != JPEGAMD_SAMPLES_10_MSB && sample_format != JPEGAMD_SAMPLES_10_LSB) return JPEGAMD_ERR_ARG;
     const int64_t bps = sample_format == JPEGAMD_SAMPLES_8 ? 1 : 2;   // bytes per sample
     const JpegAmdYCbCrImage &p0 = imgs[0];
     const bool packed = is_packed422(p0.chroma_layout);               // y is the packed plane; cb, cr and c_stride are not looked at
-    if (p0.chroma_layout != JPEGAMD_CHROMA_PLANES && p0.chroma_layout != JPEGAMD_CHROMA_CBCR && p0.chroma_layout != JPEGAMD_CHROMA_CRCB && !packed)
-        return JPEGAMD_ERR_ARG;
+    if (!ycbcr_kind_valid(p0.chroma_layout, sample_format, sample_range)) return JPEGAMD_ERR_ARG;
     if (packed && subsampling != JPEGAMD_SUBSAMPLE_422) return JPEGAMD_ERR_ARG;
-    if (packed && bps != 1) return JPEGAMD_ERR_ARG;                   // (Y210: not taken)
     if (p0.width <= 0 || p0.height <= 0 || p0.width > 65535 || p0.height > 65535) return JPEGAMD_ERR_ARG;
     const bool pair = p0.chroma_layout != JPEGAMD_CHROMA_PLANES && !packed;
     int cw, ch;
@@ -1366,8 +1280,7 @@ extern "C" int32_t jpegamd_encode_ycbcr_samples_batch_async(JpegAmdEncoder *e, c
     PlaneSet ps = {};
     YccSource ycc = {};
     ycc.layout = p0.chroma_layout; ycc.c_stride = packed ? p0.y_stride : p0.c_stride;
-    ycc.expand = sample_range == JPEGAMD_RANGE_LIMITED;
-    ycc.format = sample_format;
+    ycc.format = sample_format; ycc.range = sample_range;
     uint64_t *sizes[kMaxBatch];
     for (int i = 0; i < count; ++i) {
         const JpegAmdYCbCrImage &g = imgs[i];
@@ -1459,7 +1372,7 @@ extern "C" int32_t jpegamd_debug_poison_tile_record(JpegAmdEncoder *e, int32_t t
 // Diagnostic: copy the per-wave phase cycle sums of the last launch (null unless JPEGAMD_STAMPS is set
 // in the environment AND the library was built with -DJPEGAMD_STAMPS).  Not part of the public header.
 extern "C" int32_t jpegamd_debug_read_stamps(JpegAmdEncoder *e, unsigned long long *host, int64_t nwaves) {
-    if (!e || !e->stamps_dev || !host || nwaves > (e->max_segs > 4096 ? e->max_segs : 4096)) return JPEGAMD_ERR_ARG;
+    if (!e || !e->stamps_dev || !host || nwaves > (int64_t)(stamp_words(e->max_segs) / 16)) return JPEGAMD_ERR_ARG;
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(host, e->stamps_dev, (size_t)nwaves * 16 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     return JPEGAMD_OK;
@@ -1573,11 +1486,9 @@ extern "C" int32_t convertToJpeg(JPEG_COMPRESSION_DTO *dto) {
     }
     // the six stage counters (jpeg_compression.c:188-210) come from the STAMPED variant of the fused kernel: the same code with its
     // phases bracketed by cycle-counter reads (~10 % slower; the asynchronous entry points never run it)
-    const size_t stamp_words = (size_t)(e->max_segs > 4096 ? e->max_segs : 4096) * 16;
-    if (!e->stamps_dev) {
-        HIP_TRY(hipMalloc((void **)&e->stamps_dev, stamp_words * sizeof(unsigned long long)));
-    }
-    HIP_TRY(hipMemsetAsync(e->stamps_dev, 0, stamp_words * sizeof(unsigned long long), nullptr));
+    const size_t stamp_bytes = stamp_words(e->max_segs) * sizeof(unsigned long long);
+    if (!e->stamps_dev) HIP_TRY(hipMalloc((void **)&e->stamps_dev, stamp_bytes));
+    HIP_TRY(hipMemsetAsync(e->stamps_dev, 0, stamp_bytes, nullptr));
     e->stamp_next = true;
     int32_t rc = jpegamd_encode_async(e, &img, (void *)(uintptr_t)dto->huff_phy_ptr, dto->huff_size, size_dev, 0, nullptr);
     JpegAmdStats st;
@@ -1598,7 +1509,7 @@ extern "C" int32_t convertToJpeg(JPEG_COMPRESSION_DTO *dto) {
     dto->cycles_huffman = st.ns_pack;
     dto->cycles_total = st.ns_total;
     if (e->stamps_dev) {
-        const int tiles = ((dto->height + 7) / 8) * (((dto->width + 7) / 8 + kTileBlocks - 1) / kTileBlocks);
+        const int tiles = tiles_for(dto->width, dto->height);
         const int wgs = (tiles + 7) / 8 < 512 ? (tiles + 7) / 8 : 512;
         std::vector<unsigned long long> stamps((size_t)wgs * 8 * 16);
         if (hipMemcpy(stamps.data(), e->stamps_dev, stamps.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost) == hipSuccess) {

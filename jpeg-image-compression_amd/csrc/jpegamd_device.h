@@ -49,13 +49,22 @@ __device__ __forceinline__ const uint8_t *row_ptr(const ImageDesc &im, const uin
     return pixels + (size_t)stored * (size_t)im.row_stride;
 }
 
+// The readers of ImageDesc::select (jpegamd_internal.h has its three shapes and their packers).
+// Luma of the pixel whose stored bytes are p[0..2] (converter.c:51).
+__device__ __forceinline__ int luma_of(const ImageDesc &im, const uint8_t *p) {
+    const uint32_t w = im.select;
+    return (int)(((w & 0xFF) * p[0] + ((w >> 8) & 0xFF) * p[1] + ((w >> 16) & 0xFF) * p[2]) >> 8);
+}
+// The component (0 / 1) launch image i takes of a pair, the byte (0 .. 3) it takes of a 4-byte group, the alignment shift of 16-bit words.
+__device__ __forceinline__ uint32_t select_component(const ImageDesc &im, int i) { return (im.select + (uint32_t)i) & 1u; }
+__device__ __forceinline__ uint32_t select_quad_byte(const ImageDesc &im, int i) { return ((im.select >> 8) & 1u) + 2u * select_component(im, i); }
+__device__ __forceinline__ uint32_t select_shift(const ImageDesc &im) { return (im.select >> 16) & 31u; }
+
 // Luma of image pixel (x, y) with the converter's edge clamp (converter.c:31,36,51).
 __device__ __forceinline__ int luma_clamped(const ImageDesc &im, const uint8_t *pixels, int x, int y) {
     x = min(x, im.width - 1);
     y = min(y, im.height - 1);
-    const uint8_t *p = row_ptr(im, pixels, y) + 3 * (size_t)x;
-    const uint32_t w = im.weights;
-    return (int)(((w & 0xFF) * p[0] + ((w >> 8) & 0xFF) * p[1] + ((w >> 16) & 0xFF) * p[2]) >> 8);
+    return luma_of(im, row_ptr(im, pixels, y) + 3 * (size_t)x);
 }
 
 // ------------------------------------------------------------------------------------

@@ -111,13 +111,50 @@ struct ScanStats {                   // device-side per-call record
 
 constexpr int kMaxBatch = 32;           // images of one geometry coded by ONE launch of each kernel (jpegamd_encode_batch_async)
 
+// ---- what a launch of k_tile_encode reads -----------------------------------------------------------------------------------
+// TileSource says it in three independent facts.  `layout` is the memory walk of the loader, the kernel's template parameter kSrc:
+//   kSrcRgb     3 bytes per pixel, luma by the weights in ImageDesc::select (BGR / RGB, either row order)
+//   kSrcPlane   1 byte per pixel: the sample itself (a GRAY picture, a Y plane, a chroma plane)
+//   kSrcPx4     4 bytes per pixel (RGBA / BGRA): luma by the same weights, the fourth byte meets a zero weight
+//   kSrcPlanar  the R, G and B planes of one byte per sample: R in ImageDesc::batch_pixels, G and B in TilePlanes
+//   kSrcPair    a plane of byte pairs of which a launch image takes ONE component: a chroma scan of Cb Cr pairs (NV12), or -- with
+//               the luma tables -- the Y scan of a packed 4:2:2 plane (Y Cb Y Cr / Cb Y Cr Y)
+//   kSrcQuad    a plane of 4-byte groups of which a launch image takes ONE byte: the chroma scans of that packed plane
+//   kSrcPlane16 a plane of 16-bit little-endian words holding 10-bit samples; kSrcPair16: a plane of pairs of such words, one
+//               component per launch image.  Every sample is narrowed to 8 bits behind the loader.
+// width, height and row_stride of the ImageDesc describe the component that is coded (width in samples, pairs or groups; row_stride
+// in bytes).  `chroma`: the scan is coded with the chroma MfmaTables, the chroma code and Huffman tables and the chroma ZRL code.
+// `expand`: the samples are limited range (JPEGAMD_RANGE_LIMITED) and are mapped to full range behind the loader, Y by the luma map
+// and Cb / Cr by the chroma map; with a 16-bit layout it selects the limited-range narrowing.  launch_tile_transform has the list of
+// combinations that exist as kernels (stage taps and the stamped build: luma kSrcRgb / kSrcPlane and chroma kSrcPlane alone); any
+// other is hipErrorInvalidValue.
+constexpr int kSrcRgb = 0, kSrcPlane = 1, kSrcPx4 = 2, kSrcPlanar = 3, kSrcPair = 4, kSrcQuad = 5, kSrcPlane16 = 6, kSrcPair16 = 7;
+struct TileSource {
+    int layout = kSrcRgb;
+    bool chroma = false, expand = false;
+};
+
+// ImageDesc::select is ONE word that tells the loader which of the stored bytes it wants.  Its three shapes, each with its packer
+// here and its readers in jpegamd_device.h:
+//   kSrcRgb, kSrcPx4        the luma weights of stored bytes 0, 1, 2 in bytes 0, 1, 2 (byte 3 = 0)       select_luma / luma_of
+//   kSrcPair, kSrcQuad      bit 0: the parity p -- launch image i takes component (p + i) & 1 of a pair, so a chroma launch that
+//                           starts on plane `first` of the call (Cb even, Cr odd) passes first & 1, flipped when Cr is stored first;
+//                           the Y scan of a packed plane takes component p for EVERY image.  Bit 8: kSrcQuad's first byte f -- the
+//                           byte taken is f + 2 ((p + i) & 1): 1 / 3 of Y Cb Y Cr, 0 / 2 of Cb Y Cr Y    select_byte / select_component, select_quad_byte
+//   kSrcPlane16, kSrcPair16 bit 0: kSrcPair16's parity, as above; bits 16..20: the right shift that leaves the 10-bit value of a
+//                           word (6: MSB-aligned, 0: LSB-aligned)                                          select_depth / select_component, select_shift
+// kSrcPlane and kSrcPlanar do not read it.
+constexpr uint32_t select_luma(bool blue_first) { return blue_first ? (29u | (150u << 8) | (77u << 16)) : (77u | (150u << 8) | (29u << 16)); }   // Y = (77 R + 150 G + 29 B) >> 8 (converter.c:51)
+constexpr uint32_t select_byte(uint32_t parity, uint32_t first_byte) { return (parity & 1u) | ((first_byte & 1u) << 8); }
+constexpr uint32_t select_depth(uint32_t parity, uint32_t shift) { return (parity & 1u) | ((shift & 31u) << 16); }
+
 struct ImageDesc {
     const uint8_t *pixels;              // image 0 (== batch_pixels[0])
     const uint8_t *batch_pixels[kMaxBatch];
     int32_t batch;                      // images in this launch; tiles / segments of image i are [i * num_tiles, ..) / [i * num_segs, ..)
     uint32_t tpi_magic;                 // min(floor(2^32 / num_tiles), 2^32 - 1): global tile / num_tiles by multiply-high, at most one too small
     int32_t width, height, row_stride, bottom_up;
-    uint32_t weights;          // luma weights for stored bytes 0,1,2 (byte 3 = 0)
+    uint32_t select;                    // which stored bytes the loader takes (above)
     int32_t blocks_w, blocks_h, segs_per_row, num_segs;
     int32_t seg_tiles;                  // tiles per segment of this launch: kSegTiles, or kSegTilesBatch
     int32_t tiles_per_row, num_tiles;
@@ -125,6 +162,9 @@ struct ImageDesc {
     int32_t seg_begin, seg_end;         // segments this launch codes (whole images: 0, batch * num_segs)
     int32_t fast_ok;           // pixels % 4 == 0 && row_stride % 4 == 0 (planar: every plane)
 };
+// (a kernel argument: the committed profiles and tools know its layout)
+static_assert(sizeof(ImageDesc) == 8 * (1 + kMaxBatch) + 4 * 20 && offsetof(ImageDesc, select) == 8 * (1 + kMaxBatch) + 24 &&
+              offsetof(ImageDesc, fast_ok) == 8 * (1 + kMaxBatch) + 72, "ImageDesc keeps its size and member offsets");
 
 // What k_segment_merge leaves per segment (and what one image sharded over GPUs exchanges, besides the bit strings).
 struct SegArrays {
@@ -157,44 +197,15 @@ struct TransformOutM {
 };
 // `ev` (optional): two hipEvent_t that receive the kernel's OWN begin / end timestamps (hipExtLaunchKernelGGL), i.e. what a
 // kernel trace reports as its duration -- an event recorded in front of a launch also sees the dispatch latency.
-// `src`: what a pixel is -- kTileSrcRgb (3 bytes, ImageDesc::weights), kTileSrcGray (1 byte: the luma itself), kTileSrcChroma (1 byte of
-// a chroma plane, coded with the chroma tables: TransformOutM must then point at the chroma constants).
-// kTileSrcPx4: 4 bytes per pixel (RGBA / BGRA; ImageDesc::weights, the fourth byte ignored); kTileSrcPlanar: the R, G and B planes
-// of one byte per sample -- R in ImageDesc::batch_pixels, G and B in `planes`.  Neither has a stage-tap or a stamped variant.
-// kTileSrcChromaPair: a chroma scan (chroma tables, as kTileSrcChroma) whose samples are one component of a plane of byte pairs
-// (Cb Cr Cb Cr ...): launch image i reads component (ImageDesc::weights + i) & 1 of the pair plane batch_pixels[i]; width, height and
-// row_stride describe the component (width pairs per row, row_stride bytes between rows).  Plain build only, like the two above.
-// A packed 4:2:2 plane (Y Cb Y Cr / Cb Y Cr Y groups of 4 bytes for 2 pixels), plain build only as well:
-// kTileSrcLumaPair: the Y scan (luma tables) -- the rows are byte pairs of which EVERY launch image takes byte ImageDesc::weights & 1;
-// width (pixels), height and row_stride describe the Y component.  kTileSrcChromaQuad: a chroma scan (chroma tables) whose samples are
-// one byte of every 4-byte group: launch image i reads byte ((weights >> 8) & 1) + 2 ((weights + i) & 1) of the groups of
-// batch_pixels[i]; width is in groups.
-// Limited-range YCbCr (JPEGAMD_RANGE_LIMITED), plain build only: kTileSrcGrayExpand, kTileSrcChromaExpand, kTileSrcChromaPairExpand,
-// kTileSrcLumaPairExpand and kTileSrcChromaQuadExpand read what the source of the same name without "Expand" reads and expand every
-// sample to full range behind the loader -- the Y map with the luma tables, the Cb / Cr map with the chroma tables.
-// 10-bit YCbCr in 16-bit little-endian words (JPEGAMD_SAMPLES_10_MSB / _LSB), plain build only: kTileSrcGray16 (luma tables) and
-// kTileSrcChroma16 (chroma tables) read a plane of 16-bit samples, kTileSrcChromaPair16 one component of a plane of 16-bit pairs by the
-// parity rule of kTileSrcChromaPair (ImageDesc::weights bit 0); width counts samples / pairs, row_stride bytes.  Every sample is
-// narrowed to 8 bits behind the loader -- the full-range map, or with the "Expand" twin the limited-range map, Y by the luma tables
-// and Cb / Cr by the chroma tables.  ImageDesc::weights bits 16..20 carry the right shift that leaves the 10-bit value (6 or 0).
-constexpr int kTileSrcRgb = 0, kTileSrcGray = 1, kTileSrcChroma = 2, kTileSrcPx4 = 3, kTileSrcPlanar = 4, kTileSrcChromaPair = 5,
-              kTileSrcLumaPair = 6, kTileSrcChromaQuad = 7, kTileSrcGrayExpand = 8, kTileSrcChromaExpand = 9, kTileSrcChromaPairExpand = 10,
-              kTileSrcLumaPairExpand = 11, kTileSrcChromaQuadExpand = 12, kTileSrcGray16 = 13, kTileSrcChroma16 = 14, kTileSrcChromaPair16 = 15,
-              kTileSrcGray16Expand = 16, kTileSrcChroma16Expand = 17, kTileSrcChromaPair16Expand = 18;
-// (a chroma scan: the chroma constants, code table and Huffman table)
-constexpr bool tile_src_is_chroma(int src) {
-    return src == kTileSrcChroma || src == kTileSrcChromaPair || src == kTileSrcChromaQuad || src == kTileSrcChromaExpand ||
-           src == kTileSrcChromaPairExpand || src == kTileSrcChromaQuadExpand || src == kTileSrcChroma16 || src == kTileSrcChromaPair16 ||
-           src == kTileSrcChroma16Expand || src == kTileSrcChromaPair16Expand;
-}
+// `src`: what the launch reads (TileSource, above); a chroma source wants the chroma constants in TransformOutM.
 struct TilePlanes {                     // the second and third plane of every picture of a planar launch (its own kernel argument)
     const uint8_t *g[kMaxBatch];
     const uint8_t *b[kMaxBatch];
 };
-int launch_tile_transform(const ImageDesc &im, const TransformOutM &out, bool taps, void *stream, void *const *ev = nullptr, int src = kTileSrcRgb,
+int launch_tile_transform(const ImageDesc &im, const TransformOutM &out, bool taps, void *stream, void *const *ev = nullptr, TileSource src = {},
                           const TilePlanes *planes = nullptr);
 // the same kernel with its phases stamped (out.stamps must point at 16 words per wave): jpegamd_tile_pipeline.hip, -DJPEGAMD_STAMPED_TU
-int launch_tile_transform_stamped(const ImageDesc &im, const TransformOutM &out, bool taps, void *stream, void *const *ev = nullptr, int src = kTileSrcRgb,
+int launch_tile_transform_stamped(const ImageDesc &im, const TransformOutM &out, bool taps, void *stream, void *const *ev = nullptr, TileSource src = {},
                                   const TilePlanes *planes = nullptr);
 
 struct MergeArgs {              // k_segment_merge: the tile strings of a segment -> ONE bit string per segment + its numbers

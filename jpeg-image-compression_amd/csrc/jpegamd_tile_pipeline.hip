@@ -142,24 +142,10 @@ static_assert(kPassItems * (27 + 3 * (int)kZrlBits) / 32 + 6 <= kWinStr && 2 * k
 static_assert(kPassItems * (27 + 3 * (int)kZrlBitsChroma) / 32 + 6 <= kWinStr && 27 + 3 * (int)kZrlBitsChroma <= 64,
               "... with the chroma table's ZRL as well (and a string with three of them in front still fits hi:lo)");
 
-// What k_tile_encode reads (template parameter kSrc: no runtime branch, the RGB instantiations are unchanged):
-//   kSrcRgb    3 bytes per pixel, luma by the weights of ImageDesc (BGR / RGB, either row order)
-//   kSrcPlane  1 byte per pixel: the sample itself (a GRAY picture, or a chroma plane of k_chroma_planes)
-//   kSrcPx4    4 bytes per pixel (RGBA / BGRA): luma by the weights of ImageDesc, whose fourth weight is 0
-//   kSrcPlanar three planes of one byte per sample, R (ImageDesc::batch_pixels), G and B (TilePlanes)
-//   kSrcPair   one plane of byte pairs (Cb Cr Cb Cr ...: NV12 chroma), of which a launch image takes ONE component: launch image i
-//              reads component (ImageDesc::weights + i) & 1 of the pair plane ImageDesc::batch_pixels[i].  With the LUMA tables it is
-//              the Y scan of a packed 4:2:2 plane (Y Cb Y Cr / Cb Y Cr Y): EVERY launch image then reads component weights & 1
-//   kSrcQuad   one plane of 4-byte groups (the same packed 4:2:2 plane, as its chroma scans see it), of which a launch image takes
-//              ONE byte per group: launch image i reads byte ((weights >> 8) & 1) + 2 ((weights + i) & 1) -- Cb or Cr by the parity
-//              rule of kSrcPair, at bytes 1 / 3 (Y Cb Y Cr) or 0 / 2 (Cb Y Cr Y)
-//   kSrcPlane16 one plane of 16-bit little-endian samples (the Y or a chroma plane of a 10-bit YCbCr batch): kSrcPair's loader -- 16
-//              bytes per lane-row, whose four dwords ARE the B fragment -- then the depth map (narrow_depth_pk) behind it
-//   kSrcPair16 one plane of 16-bit pairs (Cb Cr Cb Cr ...: P010 chroma), of which a launch image takes ONE component by kSrcPair's
-//              parity rule: 32 bytes per lane-row on kSrcQuad's schedule, one v_perm per B-fragment dword, then the depth map
-//              Both read the samples' alignment from ImageDesc::weights bits 16..20 (the right shift that leaves the 10-bit value: 6 for
-//              MSB-aligned words, 0 for LSB-aligned ones); kSrcPair16 keeps the parity in bit 0.
-constexpr int kSrcRgb = 0, kSrcPlane = 1, kSrcPx4 = 2, kSrcPlanar = 3, kSrcPair = 4, kSrcQuad = 5, kSrcPlane16 = 6, kSrcPair16 = 7;
+// What k_tile_encode reads: template parameter kSrc is TileSource::layout (jpegamd_internal.h: the layouts, and the shapes of
+// ImageDesc::select) -- no runtime branch.  The loaders: kSrcPlane16 takes kSrcPair's -- 16 bytes per lane-row, whose four dwords ARE
+// the B fragment -- and kSrcPair16 runs on kSrcQuad's schedule -- 32 bytes per lane-row, one v_perm per B-fragment dword; the depth
+// map (narrow_depth_pk) follows behind either.
 // The kernel's last argument: the G and B planes for kSrcPlanar, an empty struct -- no kernel-argument bytes, so the offsets of
 // the hidden arguments behind it stay where they were -- for every other source.
 struct NoPlanes {};
@@ -279,9 +265,7 @@ __device__ __forceinline__ f16x8 planar_row8_f16(const RawRow &raw, uint32_t sel
 __device__ __forceinline__ int luma_clamped_px4(const ImageDesc &im, const uint8_t *pixels, int x, int y) {
     x = min(x, im.width - 1);
     y = min(y, im.height - 1);
-    const uint8_t *p = row_ptr(im, pixels, y) + 4 * (size_t)x;
-    const uint32_t w = im.weights;
-    return (int)(((w & 0xFF) * p[0] + ((w >> 8) & 0xFF) * p[1] + ((w >> 16) & 0xFF) * p[2]) >> 8);
+    return luma_of(im, row_ptr(im, pixels, y) + 4 * (size_t)x);
 }
 __device__ __forceinline__ int luma_clamped_planar(const ImageDesc &im, const uint8_t *r, const uint8_t *g, const uint8_t *b, int x, int y) {
     x = min(x, im.width - 1);
@@ -503,7 +487,7 @@ void k_tile_encode(const ImageDesc im, const TransformOutM out, const TileSched 
     const int lane = lane_id();
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));   // provably uniform: tile indices, list pointers and the buffer descriptor stay on the scalar unit
     const int h = lane >> 5, b = lane & 31;
-    const LumaWeights lw = luma_weights(im.weights);
+    const LumaWeights lw = luma_weights(im.select);
     const uint32_t luma_sel = 0x0C050C01u;
     const float *q_lane = &s_qt[16 * h];
 
@@ -687,25 +671,25 @@ void k_tile_encode(const ImageDesc im, const TransformOutM out, const TileSched 
                 for (int i = 0; i < 8; ++i) last[i] = src[i];
                 const uint32_t *const flat = &raw[0].d[0];
                 if constexpr (kSrc == kSrcQuad) {   // (the byte is wave-uniform: the selector stays on the scalar unit, as kSrcPair's)
-                    const uint32_t qsel = 0x0C040C00u + 0x00010001u * (((im.weights >> 8) & 1u) + 2u * ((im.weights + (uint32_t)tg.img) & 1u));
+                    const uint32_t qsel = 0x0C040C00u + 0x00010001u * select_quad_byte(im, tg.img);
 #pragma unroll
                     for (int s = 0; s < 3; ++s) bfrag[s] = quad_row8_f16(flat + 8 * s, qsel);
                     bfrag[3] = quad_row8_f16(last, qsel);
                 } else if constexpr (kSrc == kSrcPair16) {   // the wanted word of two dwords into the two halves: 0x05040100 (component 0) / 0x07060302
-                    const uint32_t wsel = 0x05040100u + 0x02020202u * ((im.weights + (uint32_t)tg.img) & 1u);
+                    const uint32_t wsel = 0x05040100u + 0x02020202u * select_component(im, tg.img);
 #pragma unroll
                     for (int s = 0; s < 3; ++s) bfrag[s] = quad_row8_f16(flat + 8 * s, wsel);
                     bfrag[3] = quad_row8_f16(last, wsel);
                 } else {
 #pragma unroll
-                for (int s = 0; s < 3; ++s) bfrag[s] = px4_row8_f16(flat + 8 * s, im.weights, luma_sel);
-                bfrag[3] = px4_row8_f16(last, im.weights, luma_sel);
+                for (int s = 0; s < 3; ++s) bfrag[s] = px4_row8_f16(flat + 8 * s, im.select, luma_sel);
+                bfrag[3] = px4_row8_f16(last, im.select, luma_sel);
                 }
             } else {
 #pragma unroll
             for (int s = 0; s < 4; ++s) {
                 // (kSrcPair: the component is the launch image's parity, wave-uniform: the selector stays on the scalar unit)
-                if constexpr (kSrc == kSrcPair) bfrag[s] = pair_row8_f16(raw[s].d, 0x0C020C00u + 0x00010001u * ((im.weights + (kPairFixed ? 0u : (uint32_t)tg.img)) & 1u));
+                if constexpr (kSrc == kSrcPair) bfrag[s] = pair_row8_f16(raw[s].d, 0x0C020C00u + 0x00010001u * select_component(im, kPairFixed ? 0 : tg.img));
                 else if constexpr (kSrc == kSrcPlane) bfrag[s] = plane_row8_f16(raw[s].d[0], raw[s].d[1]);
                 else if constexpr (kSrc == kSrcPlane16) {          // the four dwords ARE the fragment: two words each
                     typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
@@ -724,17 +708,17 @@ void k_tile_encode(const ImageDesc im, const TransformOutM out, const TileSched 
 #pragma unroll
                 for (int j = 0; j < 8; j += 2) {                // two values per register: Y in each 16-bit half (= Y 2^-24 as binary16, as above)
                     if constexpr (kSrc == kSrcPair)
-                        pk[j >> 1] = (uint32_t)pair_clamped(im, im.batch_pixels[tg.img], (int)((im.weights + (kPairFixed ? 0u : (uint32_t)tg.img)) & 1u), px0 + j, py0 + 2 * s + h) |
-                                     ((uint32_t)pair_clamped(im, im.batch_pixels[tg.img], (int)((im.weights + (kPairFixed ? 0u : (uint32_t)tg.img)) & 1u), px0 + j + 1, py0 + 2 * s + h) << 16);
+                        pk[j >> 1] = (uint32_t)pair_clamped(im, im.batch_pixels[tg.img], (int)select_component(im, kPairFixed ? 0 : tg.img), px0 + j, py0 + 2 * s + h) |
+                                     ((uint32_t)pair_clamped(im, im.batch_pixels[tg.img], (int)select_component(im, kPairFixed ? 0 : tg.img), px0 + j + 1, py0 + 2 * s + h) << 16);
                     else if constexpr (kSrc == kSrcQuad)
-                        pk[j >> 1] = (uint32_t)quad_clamped(im, im.batch_pixels[tg.img], (int)(((im.weights >> 8) & 1u) + 2u * ((im.weights + (uint32_t)tg.img) & 1u)), px0 + j, py0 + 2 * s + h) |
-                                     ((uint32_t)quad_clamped(im, im.batch_pixels[tg.img], (int)(((im.weights >> 8) & 1u) + 2u * ((im.weights + (uint32_t)tg.img) & 1u)), px0 + j + 1, py0 + 2 * s + h) << 16);
+                        pk[j >> 1] = (uint32_t)quad_clamped(im, im.batch_pixels[tg.img], (int)select_quad_byte(im, tg.img), px0 + j, py0 + 2 * s + h) |
+                                     ((uint32_t)quad_clamped(im, im.batch_pixels[tg.img], (int)select_quad_byte(im, tg.img), px0 + j + 1, py0 + 2 * s + h) << 16);
                     else if constexpr (kSrc == kSrcPlane16)
                         pk[j >> 1] = plane16_clamped(im, im.batch_pixels[tg.img], px0 + j, py0 + 2 * s + h) |
                                      (plane16_clamped(im, im.batch_pixels[tg.img], px0 + j + 1, py0 + 2 * s + h) << 16);
                     else if constexpr (kSrc == kSrcPair16)
-                        pk[j >> 1] = pair16_clamped(im, im.batch_pixels[tg.img], (int)((im.weights + (uint32_t)tg.img) & 1u), px0 + j, py0 + 2 * s + h) |
-                                     (pair16_clamped(im, im.batch_pixels[tg.img], (int)((im.weights + (uint32_t)tg.img) & 1u), px0 + j + 1, py0 + 2 * s + h) << 16);
+                        pk[j >> 1] = pair16_clamped(im, im.batch_pixels[tg.img], (int)select_component(im, tg.img), px0 + j, py0 + 2 * s + h) |
+                                     (pair16_clamped(im, im.batch_pixels[tg.img], (int)select_component(im, tg.img), px0 + j + 1, py0 + 2 * s + h) << 16);
                     else if constexpr (kSrc == kSrcPlane)
                         pk[j >> 1] = (uint32_t)plane_clamped(im, im.batch_pixels[tg.img], px0 + j, py0 + 2 * s + h) |
                                      ((uint32_t)plane_clamped(im, im.batch_pixels[tg.img], px0 + j + 1, py0 + 2 * s + h) << 16);
@@ -754,7 +738,7 @@ void k_tile_encode(const ImageDesc im, const TransformOutM out, const TileSched 
         if constexpr (kSrc == kSrcPlane16 || kSrc == kSrcPair16) {   // 16-bit words -> the 8-bit samples, either range (kExpand: limited): ONE place behind both
             static_assert(!kTaps, "the 16-bit sources have no stage taps");   // loaders, so replicated edges copy mapped samples and the stash holds them
             typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
-            const uint32_t sh2 = ((im.weights >> 16) & 31u) * 0x00010001u;
+            const uint32_t sh2 = select_shift(im) * 0x00010001u;
 #pragma unroll
             for (int s = 0; s < 4; ++s) {
                 u32x4 pk = __builtin_bit_cast(u32x4, bfrag[s]);
@@ -1326,7 +1310,46 @@ void k_tile_encode(const ImageDesc im, const TransformOutM out, const TileSched 
 #endif
 }
 
-int launch_tile_transform(const ImageDesc &im, const TransformOutM &out, bool taps, void *stream, void *const *ev, int src, const TilePlanes *planes) {
+struct TileLaunch {            // what one launch is made of, whichever instantiation runs it
+    dim3 grid;
+    hipStream_t stream;
+    void *const *ev;
+    const ImageDesc &im;
+    const TransformOutM &out;
+    const TileSched &sch;
+    const TilePlanes *planes;
+};
+namespace {                    // (internal linkage: the plain and the stamped build of this file each have their own)
+// The launch of ONE instantiation.  Without events the sources that have stage-tap and stamped variants -- RGB and plane, as they
+// are -- go through hipLaunchKernelGGL, as a tap launch always does; every other source, and every launch with events, through
+// hipExtLaunchKernelGGL.
+template <bool kTaps, int kSrc, bool kChroma, bool kExpand>
+void launch_variant(const TileLaunch &l) {
+    const auto kernel = k_tile_encode<kTaps, kSrc, kChroma ? kZrlBitsChroma : kZrlBits, kChroma ? kZrlCodeChroma : kZrlCode, kExpand>;
+    typename PlanesArg<kSrc>::type pl;
+    if constexpr (kSrc == kSrcPlanar) pl = *l.planes;
+    constexpr bool kDirect = (kSrc == kSrcRgb || kSrc == kSrcPlane) && !kExpand;
+    if (kDirect && (kTaps || !l.ev)) hipLaunchKernelGGL(kernel, l.grid, dim3(64 * kWavesT), 0, l.stream, l.im, l.out, l.sch, pl);
+    else hipExtLaunchKernelGGL(kernel, l.grid, dim3(64 * kWavesT), 0, l.stream, l.ev ? (hipEvent_t)l.ev[0] : nullptr, l.ev ? (hipEvent_t)l.ev[1] : nullptr, 0, l.im, l.out, l.sch, pl);
+}
+// Every instantiation of the kernel there is: (taps, layout, chroma tables, expand) -> its launch.
+struct Variant { bool taps; TileSource src; void (*launch)(const TileLaunch &); };
+template <bool kTaps, int kSrc, bool kChroma = false, bool kExpand = false>
+constexpr Variant kVariant = {kTaps, {kSrc, kChroma, kExpand}, &launch_variant<kTaps, kSrc, kChroma, kExpand>};
+constexpr Variant kVariants[] = {
+#ifndef JPEGAMD_STAMPED_TU     // the plain build alone: no stage taps, no stamps
+    kVariant<false, kSrcPx4>, kVariant<false, kSrcPlanar>,
+    kVariant<false, kSrcPair, true>, kVariant<false, kSrcPair>, kVariant<false, kSrcQuad, true>,                   // NV12-style chroma; a packed 4:2:2 plane's Y and chroma
+    kVariant<false, kSrcPlane, false, true>, kVariant<false, kSrcPlane, true, true>, kVariant<false, kSrcPair, true, true>,   // limited range: the five of a YCbCr batch, expanded on read
+    kVariant<false, kSrcPair, false, true>, kVariant<false, kSrcQuad, true, true>,
+    kVariant<false, kSrcPlane16>, kVariant<false, kSrcPlane16, true>, kVariant<false, kSrcPair16, true>,           // 10-bit samples in 16-bit words, either depth map
+    kVariant<false, kSrcPlane16, false, true>, kVariant<false, kSrcPlane16, true, true>, kVariant<false, kSrcPair16, true, true>,
+#endif
+    kVariant<false, kSrcPlane>, kVariant<false, kSrcPlane, true>, kVariant<true, kSrcPlane>, kVariant<true, kSrcRgb>, kVariant<false, kSrcRgb>,
+};
+}  // namespace
+
+int launch_tile_transform(const ImageDesc &im, const TransformOutM &out, bool taps, void *stream, void *const *ev, TileSource src, const TilePlanes *planes) {
     // persistent: at most 2 workgroups per CU (16 waves/CU at 4 waves/SIMD), fewer for small images
     const int ntiles = im.tile_end - im.tile_begin;
     if (ntiles <= 0) return 0;
@@ -1339,65 +1362,11 @@ int launch_tile_transform(const ImageDesc &im, const TransformOutM &out, bool ta
     sch.tiles_per_group = (ntiles + groups - 1) / groups;
     const uint64_t magic = 0x100000000ull / (uint64_t)im.tiles_per_row + 1ull;
     sch.tpr_magic = magic > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)magic;   // tiles_per_row == 1: the correction step makes up for it
-    const dim3 grid(wgs), block(64 * kWavesT);
-    const NoPlanes pl;
-    if (src == kTileSrcPx4 || src == kTileSrcPlanar || src == kTileSrcChromaPair || src == kTileSrcLumaPair || src == kTileSrcChromaQuad ||
-        (src >= kTileSrcGrayExpand && src <= kTileSrcChromaPair16Expand)) {
-#ifdef JPEGAMD_STAMPED_TU
-        return (int)hipErrorInvalidValue;                                   // (these sources exist in the plain build alone)
-#else
-        if (taps || (src == kTileSrcPlanar && !planes)) return (int)hipErrorInvalidValue;
-        const auto px4 = k_tile_encode<false, kSrcPx4>;
-        const auto planar = k_tile_encode<false, kSrcPlanar>;
-        hipEvent_t e0 = ev ? (hipEvent_t)ev[0] : nullptr, e1 = ev ? (hipEvent_t)ev[1] : nullptr;
-        const auto pair = k_tile_encode<false, kSrcPair, kZrlBitsChroma, kZrlCodeChroma>;
-        const auto ypair = k_tile_encode<false, kSrcPair>;
-        const auto quad = k_tile_encode<false, kSrcQuad, kZrlBitsChroma, kZrlCodeChroma>;
-        // limited-range YCbCr: the same five sources with the range map behind the loader
-        const auto xgray = k_tile_encode<false, kSrcPlane, kZrlBits, kZrlCode, true>;
-        const auto xplane = k_tile_encode<false, kSrcPlane, kZrlBitsChroma, kZrlCodeChroma, true>;
-        const auto xpair = k_tile_encode<false, kSrcPair, kZrlBitsChroma, kZrlCodeChroma, true>;
-        const auto xypair = k_tile_encode<false, kSrcPair, kZrlBits, kZrlCode, true>;
-        const auto xquad = k_tile_encode<false, kSrcQuad, kZrlBitsChroma, kZrlCodeChroma, true>;
-        // 10-bit samples in 16-bit words: a plane with either table set, a pair plane with the chroma tables, each with either depth map
-        const auto gray16 = k_tile_encode<false, kSrcPlane16>;
-        const auto plane16 = k_tile_encode<false, kSrcPlane16, kZrlBitsChroma, kZrlCodeChroma>;
-        const auto pair16 = k_tile_encode<false, kSrcPair16, kZrlBitsChroma, kZrlCodeChroma>;
-        const auto xgray16 = k_tile_encode<false, kSrcPlane16, kZrlBits, kZrlCode, true>;
-        const auto xplane16 = k_tile_encode<false, kSrcPlane16, kZrlBitsChroma, kZrlCodeChroma, true>;
-        const auto xpair16 = k_tile_encode<false, kSrcPair16, kZrlBitsChroma, kZrlCodeChroma, true>;
-        if (src == kTileSrcGray16) hipExtLaunchKernelGGL(gray16, grid, block, 0, (hipStream_t)stream, e0, e1, 0, im, out, sch, pl);
-        else if (src == kTileSrcChroma16) hipExtLaunchKernelGGL(plane16, grid, block, 0, (hipStream_t)stream, e0, e1, 0, im, out, sch, pl);
-        else if (src == kTileSrcChromaPair16) hipExtLaunchKernelGGL(pair16, grid, block, 0, (hipStream_t)stream, e0, e1, 0, im, out, sch, pl);
-        else if (src == kTileSrcGray16Expand) hipExtLaunchKernelGGL(xgray16, grid, block, 0, (hipStream_t)stream, e0, e1, 0, im, out, sch, pl);
-        else if (src == kTileSrcChroma16Expand) hipExtLaunchKernelGGL(xplane16, grid, block, 0, (hipStream_t)stream, e0, e1, 0, im, out, sch, pl);
-        else if (src == kTileSrcChromaPair16Expand) hipExtLaunchKernelGGL(xpair16, grid, block, 0, (hipStream_t)stream, e0, e1, 0, im, out, sch, pl);
-        else if (src == kTileSrcGrayExpand) hipExtLaunchKernelGGL(xgray, grid, block, 0, (hipStream_t)stream, e0, e1, 0, im, out, sch, pl);
-        else if (src == kTileSrcChromaExpand) hipExtLaunchKernelGGL(xplane, grid, block, 0, (hipStream_t)stream, e0, e1, 0, im, out, sch, pl);
-        else if (src == kTileSrcChromaPairExpand) hipExtLaunchKernelGGL(xpair, grid, block, 0, (hipStream_t)stream, e0, e1, 0, im, out, sch, pl);
-        else if (src == kTileSrcLumaPairExpand) hipExtLaunchKernelGGL(xypair, grid, block, 0, (hipStream_t)stream, e0, e1, 0, im, out, sch, pl);
-        else if (src == kTileSrcChromaQuadExpand) hipExtLaunchKernelGGL(xquad, grid, block, 0, (hipStream_t)stream, e0, e1, 0, im, out, sch, pl);
-        else if (src == kTileSrcChromaPair) hipExtLaunchKernelGGL(pair, grid, block, 0, (hipStream_t)stream, e0, e1, 0, im, out, sch, pl);
-        else if (src == kTileSrcLumaPair) hipExtLaunchKernelGGL(ypair, grid, block, 0, (hipStream_t)stream, e0, e1, 0, im, out, sch, pl);
-        else if (src == kTileSrcChromaQuad) hipExtLaunchKernelGGL(quad, grid, block, 0, (hipStream_t)stream, e0, e1, 0, im, out, sch, pl);
-        else if (src == kTileSrcPx4) hipExtLaunchKernelGGL(px4, grid, block, 0, (hipStream_t)stream, e0, e1, 0, im, out, sch, pl);
-        else hipExtLaunchKernelGGL(planar, grid, block, 0, (hipStream_t)stream, e0, e1, 0, im, out, sch, *planes);
-        return (int)hipGetLastError();
-#endif
-    }
-    if (src != kTileSrcRgb) {
-        const bool chroma = src == kTileSrcChroma;
-        const auto gray = k_tile_encode<false, kSrcPlane>;
-        const auto plane = k_tile_encode<false, kSrcPlane, kZrlBitsChroma, kZrlCodeChroma>;
-        if (taps && !chroma) hipLaunchKernelGGL((k_tile_encode<true, kSrcPlane>), grid, block, 0, (hipStream_t)stream, im, out, sch, pl);
-        else if (taps) return (int)hipErrorInvalidValue;                    // (no stage taps of a chroma scan)
-        else if (ev) hipExtLaunchKernelGGL(chroma ? plane : gray, grid, block, 0, (hipStream_t)stream, (hipEvent_t)ev[0], (hipEvent_t)ev[1], 0, im, out, sch, pl);
-        else hipLaunchKernelGGL(chroma ? plane : gray, grid, block, 0, (hipStream_t)stream, im, out, sch, pl);
-        return (int)hipGetLastError();
-    }
-    if (taps) hipLaunchKernelGGL(k_tile_encode<true>, grid, block, 0, (hipStream_t)stream, im, out, sch, pl);
-    else if (ev) hipExtLaunchKernelGGL(k_tile_encode<false>, grid, block, 0, (hipStream_t)stream, (hipEvent_t)ev[0], (hipEvent_t)ev[1], 0, im, out, sch, pl);
-    else hipLaunchKernelGGL(k_tile_encode<false>, grid, block, 0, (hipStream_t)stream, im, out, sch, pl);
+    const Variant *v = nullptr;
+    for (const Variant &k : kVariants)
+        if (k.taps == taps && k.src.layout == src.layout && k.src.chroma == src.chroma && k.src.expand == src.expand) v = &k;
+    if (!v || (src.layout == kSrcPlanar && !planes)) return (int)hipErrorInvalidValue;
+    v->launch(TileLaunch{dim3(wgs), (hipStream_t)stream, ev, im, out, sch, planes});
     return (int)hipGetLastError();
 }
 

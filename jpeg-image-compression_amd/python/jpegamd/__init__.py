@@ -120,6 +120,7 @@ def _load() -> C.CDLL:
         "jpegamd_encode_ycbcr_range_batch_async": (i32, [vp, C.POINTER(YCbCrImage), i32, i32, i32, C.POINTER(C.c_void_p), u64, C.POINTER(C.c_void_p), vp]),
         "jpegamd_encode_ycbcr_samples_batch_async": (i32, [vp, C.POINTER(YCbCrImage), i32, i32, i32, i32, C.POINTER(C.c_void_p), u64, C.POINTER(C.c_void_p), vp]),
         "jpegamd_debug_chroma_groups": (i32, [i32, i32, i32, i32, i32, i32, i32, vp]),
+        "jpegamd_debug_ycbcr_sources": (i32, [i32, i32, i32, i32, vp]),
         "jpegamd_debug_chroma_quant_table": (i32, [i32, vp]),
         "jpegamd_debug_chroma_mfma_consts": (i32, [i32, vp, vp, vp, vp, vp, vp]),
         "jpegamd_debug_chroma_group_thresholds": (i32, [i32, vp, vp]),
@@ -133,7 +134,7 @@ def _load() -> C.CDLL:
     }
     for name, (res, args) in sig.items():
         if name in ("jpegamd_encoder_set_pipeline", "jpegamd_gather_streams", "jpegamd_debug_mfma_offsets", "jpegamd_encode_color_batch_async",
-                    "jpegamd_debug_chroma_groups", "jpegamd_encode_planar_batch_async", "jpegamd_encode_ycbcr_batch_async",
+                    "jpegamd_debug_chroma_groups", "jpegamd_debug_ycbcr_sources", "jpegamd_encode_planar_batch_async", "jpegamd_encode_ycbcr_batch_async",
                     "jpegamd_encode_ycbcr_range_batch_async", "jpegamd_encode_ycbcr_samples_batch_async") and os.environ.get("JPEGAMD_LIB") and not hasattr(lib, name):
             continue                                              # (A/B tooling: a variant build of an older round)
         fn = getattr(lib, name)
@@ -476,17 +477,18 @@ def encode_tensor_batch(t, quality: int = 0, subsampling: int = SUBSAMPLE_420, l
     return files
 
 
-def _ycbcr_layout(y, cb, cr, subsampling, order):
-    """The pictures of encode_ycbcr_batch -> (count, height, width, y stride, chroma stride, JPEGAMD_CHROMA_* layout).  Shapes,
-    dtypes and strides only: host tensors pass."""
+def _ycbcr_layout_of(y, cb, cr, subsampling, order, dtypes, sample_bytes, pairs):
+    """The pictures of a YCbCr batch -> (count, height, width, y stride, chroma stride, JPEGAMD_CHROMA_* layout), strides in BYTES.
+    Shapes, dtypes and strides only: host tensors pass.  `dtypes`: the names of the torch dtypes taken; `sample_bytes`: 1 or 2;
+    `pairs`: what the messages call the interleaved samples."""
     import torch
     if subsampling not in (SUBSAMPLE_444, SUBSAMPLE_420, SUBSAMPLE_422):
         raise ValueError("subsampling must be SUBSAMPLE_444, SUBSAMPLE_420 or SUBSAMPLE_422")
     if order not in ("cbcr", "crcb"):
         raise ValueError(f'order must be "cbcr" or "crcb", not {order!r}')
     tensors = [y, cb] + ([cr] if cr is not None else [])
-    if any(not isinstance(x, torch.Tensor) or x.dtype != torch.uint8 for x in tensors):
-        raise ValueError("the encoder needs uint8 tensors")
+    if any(not isinstance(x, torch.Tensor) or x.dtype not in [getattr(torch, d) for d in dtypes] for x in tensors):
+        raise ValueError(f"the encoder needs {' or '.join(dtypes)} tensors" + (f" ({8 * sample_bytes}-bit sample words)" if sample_bytes > 1 else ""))
     if y.dim() != 3:
         raise ValueError("y must be [N, H, W]")
     n, h, w = y.shape
@@ -496,7 +498,7 @@ def _ycbcr_layout(y, cb, cr, subsampling, order):
     ch = (h + 1) // 2 if subsampling == SUBSAMPLE_420 else h
     if cr is None:
         if cb.dim() != 4 or tuple(cb.shape) != (n, ch, cw, 2):
-            raise ValueError(f"with cr=None, cb holds the byte pairs: [N, {ch}, {cw}, 2] for this y and subsampling, not {tuple(cb.shape)}")
+            raise ValueError(f"with cr=None, cb holds the {pairs}: [N, {ch}, {cw}, 2] for this y and subsampling, not {tuple(cb.shape)}")
         if cb.stride(3) != 1 or cb.stride(2) != 2:
             raise ValueError("the pairs of a row must be packed (pair stride 2, last stride 1)")
         layout, c_row = (CHROMA_CBCR if order == "cbcr" else CHROMA_CRCB), 2 * cw
@@ -513,11 +515,23 @@ def _ycbcr_layout(y, cb, cr, subsampling, order):
         layout, c_row = CHROMA_PLANES, cw
     if y.stride(2) != 1:
         raise ValueError("samples of a row must be packed (last stride 1)")
-    y_stride = y.stride(1) if h > 1 else w
+    y_stride = y.stride(1) if h > 1 else w            # (in samples up to here)
     c_stride = cb.stride(1) if ch > 1 else c_row
     if y_stride < w or c_stride < c_row:
         raise ValueError("rows overlap (a row stride is less than a row)")
-    return n, h, w, y_stride, c_stride, layout
+    if sample_bytes > 1 and (sample_bytes * y_stride >= 1 << 31 or sample_bytes * c_stride >= 1 << 31):
+        raise ValueError("a row stride must stay below 2^31 bytes")
+    return n, h, w, sample_bytes * y_stride, sample_bytes * c_stride, layout
+
+
+def _ycbcr_layout(y, cb, cr, subsampling, order):
+    """_ycbcr_layout_of for encode_ycbcr_batch: one byte per sample."""
+    return _ycbcr_layout_of(y, cb, cr, subsampling, order, ("uint8",), 1, "byte pairs")
+
+
+def _ycbcr16_layout(y, cb, cr, subsampling, order):
+    """_ycbcr_layout_of for encode_ycbcr16_batch: 16-bit sample words."""
+    return _ycbcr_layout_of(y, cb, cr, subsampling, order, ("int16", "uint16"), 2, "pairs of words")
 
 
 def _sample_range(sample_range) -> int:
@@ -584,52 +598,6 @@ def _encode_ycbcr_images(device, n, h, w, subsampling, image, sample_range: int 
             got = sizes[:k].cpu().tolist()
             files += [bytes(out[i, :got[i]].cpu().numpy().tobytes()) for i in range(k)]
     return files
-
-
-def _ycbcr16_layout(y, cb, cr, subsampling, order):
-    """The pictures of encode_ycbcr16_batch -> (count, height, width, y stride, chroma stride, JPEGAMD_CHROMA_* layout), strides in
-    BYTES.  Shapes, dtypes and strides only: host tensors pass."""
-    import torch
-    if subsampling not in (SUBSAMPLE_444, SUBSAMPLE_420, SUBSAMPLE_422):
-        raise ValueError("subsampling must be SUBSAMPLE_444, SUBSAMPLE_420 or SUBSAMPLE_422")
-    if order not in ("cbcr", "crcb"):
-        raise ValueError(f'order must be "cbcr" or "crcb", not {order!r}')
-    tensors = [y, cb] + ([cr] if cr is not None else [])
-    if any(not isinstance(x, torch.Tensor) or x.dtype not in (torch.int16, torch.uint16) for x in tensors):
-        raise ValueError("the encoder needs int16 or uint16 tensors (16-bit sample words)")
-    if y.dim() != 3:
-        raise ValueError("y must be [N, H, W]")
-    n, h, w = y.shape
-    if n < 1 or h < 1 or w < 1 or h > 65535 or w > 65535:
-        raise ValueError("the encoder needs at least one picture of 1..65535 pixels each way")
-    cw = w if subsampling == SUBSAMPLE_444 else (w + 1) // 2
-    ch = (h + 1) // 2 if subsampling == SUBSAMPLE_420 else h
-    if cr is None:
-        if cb.dim() != 4 or tuple(cb.shape) != (n, ch, cw, 2):
-            raise ValueError(f"with cr=None, cb holds the pairs of words: [N, {ch}, {cw}, 2] for this y and subsampling, not {tuple(cb.shape)}")
-        if cb.stride(3) != 1 or cb.stride(2) != 2:
-            raise ValueError("the pairs of a row must be packed (pair stride 2, last stride 1)")
-        layout, c_row = (CHROMA_CBCR if order == "cbcr" else CHROMA_CRCB), 2 * cw
-    else:
-        if order != "cbcr":
-            raise ValueError('order="crcb" names the interleaved layout (cr=None); swap the tensors for planes')
-        for name, p in (("cb", cb), ("cr", cr)):
-            if p.dim() != 3 or tuple(p.shape) != (n, ch, cw):
-                raise ValueError(f"{name} must be [N, {ch}, {cw}] for this y and subsampling, not {tuple(p.shape)}")
-            if p.stride(2) != 1:
-                raise ValueError("samples of a row must be packed (last stride 1)")
-        if ch > 1 and cb.stride(1) != cr.stride(1):
-            raise ValueError("cb and cr must share one row stride")
-        layout, c_row = CHROMA_PLANES, cw
-    if y.stride(2) != 1:
-        raise ValueError("samples of a row must be packed (last stride 1)")
-    y_stride = y.stride(1) if h > 1 else w            # (in words up to here)
-    c_stride = cb.stride(1) if ch > 1 else c_row
-    if y_stride < w or c_stride < c_row:
-        raise ValueError("rows overlap (a row stride is less than a row)")
-    if 2 * y_stride >= 1 << 31 or 2 * c_stride >= 1 << 31:
-        raise ValueError("a row stride must stay below 2^31 bytes")
-    return n, h, w, 2 * y_stride, 2 * c_stride, layout
 
 
 def encode_ycbcr16_batch(y, cb, cr=None, quality: int = 0, subsampling: int = SUBSAMPLE_420, order: str = "cbcr",
