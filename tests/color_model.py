@@ -9,6 +9,7 @@ The file is three non-interleaved baseline scans.  The model builds each of them
 from __future__ import annotations
 
 import ctypes as C
+import hashlib
 import struct
 
 import numpy as np
@@ -35,6 +36,18 @@ AC_CHROMA_VALS = bytes.fromhex(
 ZIGZAG = [0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
           35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63]
 SUB_444, SUB_420 = 1, 2
+PLANES, CBCR, CRCB = 0, 1, 2                                    # JPEGAMD_CHROMA_PLANES / _CBCR / _CRCB
+
+_memo = {}
+
+
+def memo(fn, oracle, *args):
+    """fn(oracle, *args), computed once per distinct arguments (arrays by shape and content): the one cache every suite shares, so that
+    the oracle never encodes the same planes twice in a session."""
+    key = (fn,) + tuple((a.shape, a.dtype.str, hashlib.sha1(np.ascontiguousarray(a)).digest()) if isinstance(a, np.ndarray) else a for a in args)
+    if key not in _memo:
+        _memo[key] = fn(oracle, *args)
+    return _memo[key]
 
 
 def scaled_table(base, quality: int) -> np.ndarray:
@@ -195,6 +208,46 @@ def color_file(oracle, bmp: bytes, quality: int = 0, sub: int = SUB_420) -> byte
     cq = scaled_table(CHROMA_Q, quality)
     cb, cr = chroma_planes(rgb, sub)
     parts = [color_prefix(w, h, quality, sub), gray_scan(oracle, bmp, quality)]
+    for comp, plane in ((2, cb), (3, cr)):
+        parts += [sos(comp), pack_scan(oracle, plane_zigzag(oracle, plane, cq), True)]
+    return b"".join(parts) + b"\xff\xd9"
+
+
+def rgb_file(oracle, rgb: np.ndarray, quality: int, sub: int) -> bytes:
+    """The file the packed path defines for these pixels: the colour file at `sub`, or (sub 0) the oracle's grayscale file."""
+    bmp = write_bmp(rgb)
+    if sub == 0:
+        return oracle.encode_bmp(bmp, quality=quality) if quality else oracle.encode_bmp(bmp)
+    return color_file(oracle, bmp, quality, sub)
+
+
+def gray_file(oracle, plane: np.ndarray, quality: int) -> bytes:
+    """The oracle's file of the picture whose pixels are (p, p, p): its luma is the plane itself."""
+    return oracle.encode_bmp(write_bmp(np.repeat(plane[:, :, None], 3, axis=2)), quality)
+
+
+def model_planes(rgb: np.ndarray, sub: int):
+    """What the colour path derives from an RGB picture: the luma formula and chroma_planes."""
+    r, g, b = (rgb[:, :, i].astype(np.int64) for i in range(3))
+    y = ((77 * r + 150 * g + 29 * b) >> 8).astype(np.uint8)
+    cb, cr = chroma_planes(rgb, sub)
+    return y, cb, cr
+
+
+def chroma_rows(cb: np.ndarray, cr: np.ndarray, layout: int):
+    """The stored chroma of one picture: [cb rows, cr rows] for PLANES, [pair rows] otherwise."""
+    if layout == PLANES:
+        return [cb, cr]
+    first, second = (cb, cr) if layout == CBCR else (cr, cb)
+    return [np.ascontiguousarray(np.stack([first, second], axis=2).reshape(cb.shape[0], -1))]
+
+
+def ycbcr_file(oracle, y: np.ndarray, cb: np.ndarray, cr: np.ndarray, quality: int = 0, sub: int = SUB_420) -> bytes:
+    """The file of samples that already are Y, Cb and Cr: the colour prefix, the oracle's grayscale scan of the Y plane, and the chroma
+    pipeline over the Cb and Cr planes exactly as given."""
+    h, w = y.shape
+    cq = scaled_table(CHROMA_Q, quality)
+    parts = [color_prefix(w, h, quality, sub), gray_scan(oracle, write_bmp(np.stack([y, y, y], axis=2)), quality)]
     for comp, plane in ((2, cb), (3, cr)):
         parts += [sos(comp), pack_scan(oracle, plane_zigzag(oracle, plane, cq), True)]
     return b"".join(parts) + b"\xff\xd9"

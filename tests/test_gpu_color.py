@@ -8,77 +8,21 @@ import numpy as np
 import pytest
 
 import color_model as cm
+from gpu_support import ColorCall, dev, encode_gray, stream, synth_rgb, upload     # noqa: F401
+from gpu_support import gray_bmp_sized as gray_bmp
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
 
-@pytest.fixture(scope="module")
-def dev():
-    if not torch.cuda.is_available():
-        pytest.fail("gpu-marked test started without a GPU: the product path has no CPU fallback")
-    return torch.device("cuda:0")
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def gray_bmp(p: np.ndarray) -> bytes:
-    """The BMP whose pixels are (p, p, p): its luma is p itself ((77 + 150 + 29) p >> 8)."""
-    return cm.write_bmp(np.repeat(p[:, :, None], 3, axis=2))
-
-
-def upload_rows(arr: np.ndarray, dev, stride: int, shift: int = 0):
-    """uint8 [H, W] or [H, W, 3] -> device rows `stride` bytes apart, the first at byte `shift` of the allocation."""
-    h = arr.shape[0]
-    row = arr.reshape(h, -1)
-    buf = np.zeros(shift + stride * h + 16, np.uint8)
-    for y in range(h):
-        buf[shift + y * stride: shift + y * stride + row.shape[1]] = row[y]
-    t = torch.from_numpy(buf).to(dev)
-    return t, t.data_ptr() + shift
-
-
-def encode_gray(jpegamd, enc, p: np.ndarray, dev, stride=None, shift=0, quality=0):
-    h, w = p.shape
-    stride = stride or w
-    t, ptr = upload_rows(p, dev, stride, shift)
-    cap = jpegamd.max_jfif_bytes(w, h)
-    out = torch.empty(cap, dtype=torch.uint8, device=dev)
-    size = torch.zeros(1, dtype=torch.int64, device=dev)
-    img = jpegamd.Encoder.image(ptr, w, h, stride, False, jpegamd.ORDER_GRAY, quality)
-    enc.encode_async(img, out.data_ptr(), cap, size.data_ptr(), True, _stream())
+def encode_color(jpegamd, enc, rgb, dev, sub, quality=0, bgr_bottom_up=False, cap=None, stride=None, shift=0):
+    call = ColorCall(jpegamd, enc, rgb, dev, sub, quality=quality, bgr=bgr_bottom_up, bottom_up=bgr_bottom_up, stride=stride, shift=shift, cap=cap)
     st = enc.finish()
-    n = int(size.item())
-    assert n == st.jfif_bytes
-    return bytes(out[:n].cpu().numpy())
-
-
-def encode_color(jpegamd, enc, rgb: np.ndarray, dev, sub, quality=0, bgr_bottom_up=False, cap=None, stride=None, shift=0,
-                 canary=False):
-    h, w, _ = rgb.shape
-    stored = rgb[::-1, :, ::-1] if bgr_bottom_up else rgb
-    stride = stride or 3 * w
-    t, ptr = upload_rows(np.ascontiguousarray(stored), dev, stride, shift)
-    full = jpegamd.max_jfif_bytes_color(w, h, sub)
-    cap = cap if cap is not None else full
-    out = torch.full((cap + 64,), 0xA5, dtype=torch.uint8, device=dev)          # 64 canary bytes behind the capacity
-    size = torch.full((1,), -1, dtype=torch.int64, device=dev)
-    img = jpegamd.Encoder.image(ptr, w, h, stride, bgr_bottom_up, jpegamd.ORDER_BGR if bgr_bottom_up else jpegamd.ORDER_RGB, quality)
-    enc.encode_color_async(img, sub, out.data_ptr(), cap, size.data_ptr(), _stream())
-    host = out.cpu().numpy()
-    if canary:
-        return enc, int(size.item()), host
-    st = enc.finish()
-    n = int(size.item())
-    assert n == st.jfif_bytes and n <= cap
-    assert np.all(host[cap:] == 0xA5)
-    return bytes(host[:n]), st
-
-
-def synth_rgb(jpegamd, w, h, seed, kind):
-    return cm.read_bmp_rgb(jpegamd.synth_bmp(w, h, seed, kind, 0))
+    got, intact = call.result()
+    n = int(call.size.item())
+    assert n == st.jfif_bytes and n <= call.cap
+    assert intact
+    return got, st
 
 
 def decode_rgb(jf: bytes):
@@ -115,12 +59,12 @@ def test_gray_batch_of_eight(jpegamd, oracle, dev):
     w, h, n = 300, 72, 8
     enc = jpegamd.Encoder(w, n * h)
     planes = [synth_rgb(jpegamd, w, h, 11 + i, i % 4)[:, :, i % 3].copy() for i in range(n)]
-    ts = [upload_rows(p, dev, w)[0] for p in planes]
+    ts = [upload(p, dev, w)[0] for p in planes]
     cap = jpegamd.max_jfif_bytes(w, h)
     outs = [torch.empty(cap, dtype=torch.uint8, device=dev) for _ in range(n)]
     sizes = [torch.zeros(1, dtype=torch.int64, device=dev) for _ in range(n)]
     imgs = [jpegamd.Encoder.image(t.data_ptr(), w, h, w, False, jpegamd.ORDER_GRAY, 0) for t in ts]
-    enc.encode_batch_async(imgs, [o.data_ptr() for o in outs], cap, [s.data_ptr() for s in sizes], True, _stream())
+    enc.encode_batch_async(imgs, [o.data_ptr() for o in outs], cap, [s.data_ptr() for s in sizes], True, stream())
     enc.finish()
     for i in range(n):
         got = bytes(outs[i][:int(sizes[i].item())].cpu().numpy())
@@ -131,7 +75,7 @@ def test_gray_stage_taps(jpegamd, oracle, dev):
     w, h = 70, 20
     p = synth_rgb(jpegamd, w, h, 5, 0)[:, :, 0].copy()
     enc = jpegamd.Encoder(w, h)
-    t, ptr = upload_rows(p, dev, w)
+    t, ptr = upload(p, dev, w)
     nb = ((w + 7) // 8) * ((h + 7) // 8)
     zz = torch.zeros(nb * 64, dtype=torch.int16, device=dev)
     enc.debug_stages(jpegamd.Encoder.image(ptr, w, h, w, False, jpegamd.ORDER_GRAY, 0), 0, zz.data_ptr(), 0)
@@ -198,12 +142,12 @@ def test_color_capacity_one_byte_short(jpegamd, dev):
     enc = jpegamd.Encoder(333, 250)
     full, _ = encode_color(jpegamd, enc, rgb, dev, 2)
     for cap in (len(full) - 1, len(full) // 2, 100):
-        enc2, size, host = encode_color(jpegamd, enc, rgb, dev, 2, cap=cap, canary=True)
+        call = ColorCall(jpegamd, enc, rgb, dev, 2, cap=cap)
         with pytest.raises(jpegamd.JpegAmdError) as ei:
-            enc2.finish()
+            enc.finish()
         assert ei.value.code == -8
-        assert size == 0
-        assert np.all(host[cap:] == 0xA5), cap
+        assert int(call.size.item()) == 0
+        assert call.result()[1], cap
     again, _ = encode_color(jpegamd, enc, rgb, dev, 2)                   # the context is fine afterwards
     assert again == full
 
@@ -237,7 +181,7 @@ def encode_gray_stats(jpegamd, dev, rgb):
     out = torch.empty(cap, dtype=torch.uint8, device=dev)
     size = torch.zeros(1, dtype=torch.int64, device=dev)
     enc.encode_async(jpegamd.Encoder.image(t.data_ptr(), img.width, img.height, img.row_stride, True, jpegamd.ORDER_BGR, 0),
-                     out.data_ptr(), cap, size.data_ptr(), True, _stream())
+                     out.data_ptr(), cap, size.data_ptr(), True, stream())
     return enc.finish().entropy_bits
 
 
@@ -262,7 +206,7 @@ def test_colour_rejects_gray_and_bad_subsampling(jpegamd, dev):
     for order, sub in ((jpegamd.ORDER_GRAY, 2), (jpegamd.ORDER_RGB, 0), (jpegamd.ORDER_RGB, 3)):
         with pytest.raises(jpegamd.JpegAmdError) as ei:
             enc.encode_color_async(jpegamd.Encoder.image(t.data_ptr(), 64, 64, 192, False, order, 0), sub, out.data_ptr(), 1 << 16,
-                                   size.data_ptr(), _stream())
+                                   size.data_ptr(), stream())
         assert ei.value.code == -1
 
 

@@ -7,83 +7,11 @@ import numpy as np
 import pytest
 
 import color_model as cm
+from gpu_support import (S420, S444, WIDE_STRIDE, ColorBatch, dev, finish_files, model, pictures, rows_for, stored_rows, stream,     # noqa: F401
+                         synth_rgb, upload)
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
-
-WIDE_STRIDE = (1 << 24) + 64
-S420, S444 = cm.SUB_420, cm.SUB_444
-
-
-@pytest.fixture(scope="module")
-def dev():
-    if not torch.cuda.is_available():
-        pytest.fail("gpu-marked test started without a GPU: the product path has no CPU fallback")
-    return torch.device("cuda:0")
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def stored_rows(rgb: np.ndarray, bottom_up: bool, bgr: bool) -> np.ndarray:
-    s = rgb[::-1] if bottom_up else rgb
-    if bgr:
-        s = s[:, :, ::-1]
-    return np.ascontiguousarray(s).reshape(s.shape[0], -1)
-
-
-def upload(rows: np.ndarray, dev, stride: int, shift: int = 0):
-    h, n = rows.shape
-    t = torch.zeros(shift + stride * h + 16, dtype=torch.uint8, device=dev)
-    t[shift:shift + stride * h].view(h, stride)[:, :n] = torch.from_numpy(rows).to(dev)
-    return t, t.data_ptr() + shift
-
-
-def rows_for(count, h):
-    """The context height a batch of `count` pictures of h rows needs: count x the block rows of one picture."""
-    return count * ((h + 7) // 8 * 8)
-
-
-def synth_rgb(jpegamd, w, h, seed, kind, flags=0):
-    return cm.read_bmp_rgb(jpegamd.synth_bmp(w, h, seed, kind, flags))
-
-
-def pictures(jpegamd, w, h, n, seed=0):
-    """n distinct pictures: photo-like, noise and flat content in turn, different seeds."""
-    kinds = (0, 1, 0, 3, 2)
-    return [synth_rgb(jpegamd, w, h, 100 + 37 * i + seed, kinds[i % len(kinds)], i % 4) for i in range(n)]
-
-
-def model(oracle, rgb, quality, sub):
-    return cm.color_file(oracle, cm.write_bmp(rgb), quality, sub)
-
-
-class ColorBatch:
-    """One colour batch queued on `enc` (not finished): every picture stored as asked, each output with 64 canary bytes
-    behind `cap`."""
-
-    def __init__(self, jpegamd, enc, rgbs, dev, sub, quality=0, bgr=False, bottom_up=False, stride=None, shifts=None, cap=None):
-        h, w, _ = rgbs[0].shape
-        self.stride = stride or 3 * w
-        shifts = shifts or [0] * len(rgbs)
-        self.px = [upload(stored_rows(r, bottom_up, bgr), dev, self.stride, s) for r, s in zip(rgbs, shifts)]
-        self.cap = cap if cap is not None else jpegamd.max_jfif_bytes_color(w, h, sub)
-        self.outs = [torch.full((self.cap + 64,), 0xA5, dtype=torch.uint8, device=dev) for _ in rgbs]
-        self.sizes = torch.full((len(rgbs),), -1, dtype=torch.int64, device=dev)
-        order = jpegamd.ORDER_BGR if bgr else jpegamd.ORDER_RGB
-        imgs = [jpegamd.Encoder.image(ptr, w, h, self.stride, bottom_up, order, quality) for _, ptr in self.px]
-        enc.encode_color_batch_async(imgs, sub, [o.data_ptr() for o in self.outs], self.cap,
-                                     [self.sizes.data_ptr() + 8 * i for i in range(len(rgbs))], _stream())
-
-    def results(self):
-        """-> [(file bytes, canary intact)] picture by picture."""
-        sizes = self.sizes.cpu().tolist()
-        res = []
-        for o, n in zip(self.outs, sizes):
-            host = o.cpu().numpy()
-            res.append((bytes(host[:n]), bool(np.all(host[self.cap:] == 0xA5))))
-        return res
 
 
 def single(jpegamd, enc, rgb, dev, sub, quality=0):
@@ -94,18 +22,13 @@ def single(jpegamd, enc, rgb, dev, sub, quality=0):
     out = torch.empty(cap, dtype=torch.uint8, device=dev)
     size = torch.zeros(1, dtype=torch.int64, device=dev)
     enc.encode_color_async(jpegamd.Encoder.image(ptr, w, h, 3 * w, False, jpegamd.ORDER_RGB, quality), sub, out.data_ptr(), cap,
-                           size.data_ptr(), _stream())
+                           size.data_ptr(), stream())
     st = enc.finish()
     return bytes(out[:int(size.item())].cpu().numpy()), st
 
 
 def run_batch(jpegamd, enc, rgbs, dev, sub, **kw):
-    b = ColorBatch(jpegamd, enc, rgbs, dev, sub, **kw)
-    st = enc.finish()
-    res = b.results()
-    assert all(ok for _, ok in res)
-    assert st.jfif_bytes == len(res[-1][0])
-    return [f for f, _ in res], st
+    return finish_files(enc, ColorBatch(jpegamd, enc, rgbs, dev, sub, **kw))
 
 
 # ---- batch sizes, content, quality, subsampling ---------------------------------------------------------------------------
@@ -256,7 +179,7 @@ def test_one_context_mixed_calls_without_finish(jpegamd, oracle, dev):
         out = torch.empty(cap, dtype=torch.uint8, device=dev)
         size = torch.zeros(1, dtype=torch.int64, device=dev)
         enc.encode_async(jpegamd.Encoder.image(ptr, w, h, 3 * w, True, jpegamd.ORDER_BGR, q), out.data_ptr(), cap, size.data_ptr(),
-                         True, _stream())
+                         True, stream())
         keep.append((t, out, size))
         checks.append((lambda: bytes(out[:int(size.item())].cpu().numpy()), gray_file(rgb, q)))
 
@@ -266,7 +189,7 @@ def test_one_context_mixed_calls_without_finish(jpegamd, oracle, dev):
         outs = [torch.empty(cap, dtype=torch.uint8, device=dev) for _ in rgbs]
         sizes = [torch.zeros(1, dtype=torch.int64, device=dev) for _ in rgbs]
         imgs = [jpegamd.Encoder.image(p, w, h, 3 * w, True, jpegamd.ORDER_BGR, q) for _, p in ups]
-        enc.encode_batch_async(imgs, [o.data_ptr() for o in outs], cap, [s.data_ptr() for s in sizes], True, _stream())
+        enc.encode_batch_async(imgs, [o.data_ptr() for o in outs], cap, [s.data_ptr() for s in sizes], True, stream())
         keep.append((ups, outs, sizes))
         for r, o, s in zip(rgbs, outs, sizes):
             checks.append(((lambda o=o, s=s: bytes(o[:int(s.item())].cpu().numpy())), gray_file(r, q)))
@@ -278,7 +201,7 @@ def test_one_context_mixed_calls_without_finish(jpegamd, oracle, dev):
         out = torch.empty(cap, dtype=torch.uint8, device=dev)
         size = torch.zeros(1, dtype=torch.int64, device=dev)
         enc.encode_color_async(jpegamd.Encoder.image(ptr, ww, hh, 3 * ww, False, jpegamd.ORDER_RGB, q), sub, out.data_ptr(), cap,
-                               size.data_ptr(), _stream())
+                               size.data_ptr(), stream())
         keep.append((t, out, size))
         checks.append((lambda: bytes(out[:int(size.item())].cpu().numpy()), model(oracle, rgb, q, sub)))
 
@@ -329,7 +252,7 @@ def test_stitch_epoch_wrap_between_y_and_chroma(jpegamd, oracle, dev):
     ssize = torch.zeros(1, dtype=torch.int64, device=dev)
     simg = jpegamd.Encoder.image(sptr, 16, 16, 16, False, jpegamd.ORDER_GRAY, 0)
     for n in range(3, 16383):
-        enc.encode_async(simg, sout.data_ptr(), scap, ssize.data_ptr(), True, _stream())
+        enc.encode_async(simg, sout.data_ptr(), scap, ssize.data_ptr(), True, stream())
         if n % 1000 == 0:
             enc.finish()
     enc.finish()
@@ -376,7 +299,7 @@ def test_encode_tensor_batch_heights_off_the_block_grid(jpegamd, dev, n, w, h):
 def test_eight_8192_pictures_420(jpegamd, dev):
     w = h = 8192
     rgbs = [synth_rgb(jpegamd, w, h, 71 + i, i % 2) for i in range(8)]
-    enc = jpegamd.Encoder(w, 8 * h)
+    enc = jpegamd.Encoder(w, rows_for(8, h))
     got, _ = run_batch(jpegamd, enc, rgbs, dev, S420, quality=50, cap=2 * w * h + (1 << 20))
     del enc
     one = jpegamd.Encoder(w, h)
@@ -387,7 +310,7 @@ def test_eight_8192_pictures_420(jpegamd, dev):
 def test_thirty_two_1024_pictures_444(jpegamd, dev):
     w = h = 1024
     rgbs = [synth_rgb(jpegamd, w, h, 81 + i, (0, 1, 3)[i % 3]) for i in range(32)]
-    enc = jpegamd.Encoder(w, 32 * h)
+    enc = jpegamd.Encoder(w, rows_for(32, h))
     got, _ = run_batch(jpegamd, enc, rgbs, dev, S444)
     one = jpegamd.Encoder(w, h)
     for k, rgb in enumerate(rgbs):

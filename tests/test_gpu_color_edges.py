@@ -12,56 +12,11 @@ import pytest
 
 import color_fixtures as cf
 import color_model as cm
+from gpu_support import WIDE_STRIDE, ColorCall, dev, encode_gray, model, rows_for, stored_rows, stream, synth_rgb, upload     # noqa: F401
+from gpu_support import gray_bmp_sized as gray_bmp
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
-
-WIDE_STRIDE = (1 << 24) + 64
-
-
-@pytest.fixture(scope="module")
-def dev():
-    if not torch.cuda.is_available():
-        pytest.fail("gpu-marked test started without a GPU: the product path has no CPU fallback")
-    return torch.device("cuda:0")
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def gray_bmp(p: np.ndarray) -> bytes:
-    return cm.write_bmp(np.repeat(p[:, :, None], 3, axis=2))
-
-
-def stored_rows(arr: np.ndarray, bottom_up: bool, bgr: bool = False) -> np.ndarray:
-    """uint8 [H, W] (GRAY) or [H, W, 3] (R, G, B) -> the rows as the API reads them: [H, row bytes], first stored row first."""
-    s = arr[::-1] if bottom_up else arr
-    if bgr:
-        s = s[:, :, ::-1]
-    return np.ascontiguousarray(s).reshape(s.shape[0], -1)
-
-
-def upload(rows: np.ndarray, dev, stride: int, shift: int = 0):
-    """Rows `stride` bytes apart on the device, the first at byte `shift` of the allocation (256-aligned) -> (tensor, pointer)."""
-    h, n = rows.shape
-    t = torch.zeros(shift + stride * h + 16, dtype=torch.uint8, device=dev)
-    t[shift:shift + stride * h].view(h, stride)[:, :n] = torch.from_numpy(rows).to(dev)
-    return t, t.data_ptr() + shift
-
-
-def encode_gray(jpegamd, enc, p, dev, bottom_up=False, stride=None, shift=0, quality=0):
-    h, w = p.shape
-    t, ptr = upload(stored_rows(p, bottom_up), dev, stride or w, shift)
-    cap = jpegamd.max_jfif_bytes(w, h)
-    out = torch.empty(cap, dtype=torch.uint8, device=dev)
-    size = torch.zeros(1, dtype=torch.int64, device=dev)
-    enc.encode_async(jpegamd.Encoder.image(ptr, w, h, stride or w, bottom_up, jpegamd.ORDER_GRAY, quality), out.data_ptr(), cap,
-                     size.data_ptr(), True, _stream())
-    st = enc.finish()
-    n = int(size.item())
-    assert n == st.jfif_bytes
-    return bytes(out[:n].cpu().numpy())
 
 
 def encode_gray_batch(jpegamd, enc, planes, dev, quality=0):
@@ -71,32 +26,9 @@ def encode_gray_batch(jpegamd, enc, planes, dev, quality=0):
     outs = [torch.empty(cap, dtype=torch.uint8, device=dev) for _ in planes]
     sizes = [torch.zeros(1, dtype=torch.int64, device=dev) for _ in planes]
     imgs = [jpegamd.Encoder.image(ptr, w, h, w, False, jpegamd.ORDER_GRAY, quality) for _, ptr in keep]
-    enc.encode_batch_async(imgs, [o.data_ptr() for o in outs], cap, [s.data_ptr() for s in sizes], True, _stream())
+    enc.encode_batch_async(imgs, [o.data_ptr() for o in outs], cap, [s.data_ptr() for s in sizes], True, stream())
     enc.finish()
     return [bytes(o[:int(s.item())].cpu().numpy()) for o, s in zip(outs, sizes)]
-
-
-class ColorCall:
-    """One colour call queued on `enc` (not finished): the pixels stored as asked, an output at `out_off` bytes past a 256-byte
-    boundary with 64 canary bytes behind `cap`."""
-
-    def __init__(self, jpegamd, enc, rgb, dev, sub, quality=0, bgr=False, bottom_up=False, stride=None, shift=0, cap=None, out_off=0):
-        h, w, _ = rgb.shape
-        self.stride = stride or 3 * w
-        self.px, ptr = upload(stored_rows(rgb, bottom_up, bgr), dev, self.stride, shift)
-        self.cap = cap if cap is not None else jpegamd.max_jfif_bytes_color(w, h, sub)
-        self.off = out_off
-        self.out = torch.full((out_off + self.cap + 64,), 0xA5, dtype=torch.uint8, device=dev)
-        self.size = torch.full((1,), -1, dtype=torch.int64, device=dev)
-        img = jpegamd.Encoder.image(ptr, w, h, self.stride, bottom_up, jpegamd.ORDER_BGR if bgr else jpegamd.ORDER_RGB, quality)
-        enc.encode_color_async(img, sub, self.out.data_ptr() + out_off, self.cap, self.size.data_ptr(), _stream())
-
-    def result(self):
-        """-> (file bytes, whether the canary behind the capacity and the bytes in front of the output are intact)."""
-        host = self.out.cpu().numpy()
-        n = int(self.size.item())
-        intact = bool(np.all(host[self.off + self.cap:] == 0xA5) and np.all(host[:self.off] == 0xA5))
-        return bytes(host[self.off:self.off + n]), intact
 
 
 def encode_color(jpegamd, enc, rgb, dev, sub, **kw):
@@ -107,19 +39,11 @@ def encode_color(jpegamd, enc, rgb, dev, sub, **kw):
     return got, st
 
 
-def synth_rgb(jpegamd, w, h, seed, kind, flags=0):
-    return cm.read_bmp_rgb(jpegamd.synth_bmp(w, h, seed, kind, flags))
-
-
-def model(oracle, rgb, quality, sub):
-    return cm.color_file(oracle, cm.write_bmp(rgb), quality, sub)
-
-
 # ---- GRAY input -----------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("w,h", [(65535, 8), (8, 65535), (65528, 24), (4104, 8), (4096, 8), (65535, 1), (1, 65535)])
 def test_gray_dimension_limits(jpegamd, oracle, dev, w, h):
     """test_dimension_limits for one-byte input: each shape alone and as a batch of two, through both pipelines."""
-    enc = jpegamd.Encoder(w, 2 * ((h + 7) // 8 * 8))
+    enc = jpegamd.Encoder(w, rows_for(2, h))
     for kind, q in ((0, 0), (1, 90)):
         planes = [synth_rgb(jpegamd, w, h, 80 + i + kind, kind)[:, :, 1 + i].copy() for i in range(2)]
         want = [oracle.encode_bmp(gray_bmp(p), q or 50) for p in planes]
@@ -219,7 +143,7 @@ def test_chroma_ties_take_the_exact_order_fallback(jpegamd, oracle, dev):
             out = torch.empty(cap, dtype=torch.uint8, device=dev)
             size = torch.zeros(1, dtype=torch.int64, device=dev)
             enc.encode_async(jpegamd.Encoder.image(ptr, w, h, 3 * w, False, jpegamd.ORDER_RGB, q), out.data_ptr(), cap, size.data_ptr(),
-                             True, _stream())
+                             True, stream())
             gray = enc.finish().exact_fallbacks
             assert st.exact_fallbacks - gray > 0, (which, sub, st.exact_fallbacks, gray)
 
@@ -394,7 +318,7 @@ def test_stitch_epoch_wrap(jpegamd, oracle, dev):
     def fill_to(last):
         nonlocal n
         while n < last:
-            enc.encode_async(simg, sout.data_ptr(), scap, ssize.data_ptr(), True, _stream())
+            enc.encode_async(simg, sout.data_ptr(), scap, ssize.data_ptr(), True, stream())
             n += 1
             if n % 1000 == 0 or n == last:
                 enc.finish()

@@ -12,25 +12,17 @@ import numpy as np
 
 import pytest
 
+from gpu_support import dev, gray_bmp, rows_for, stream, upload_pixels     # noqa: F401
+
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 
-@pytest.fixture(scope="module")
-def dev():
-    if not torch.cuda.is_available():
-        pytest.fail("gpu-marked test started without a GPU: the product path has no CPU fallback")
-    return torch.device("cuda:0")
-
-
 def _encode_batch(jpegamd, bmps, quality, dev, pipeline=None):
     """bmps: BMP files of ONE geometry -> their JFIF files through ONE launch of each kernel (one image: the plain entry)."""
-    ups = []
-    for b in bmps:
-        img, off = jpegamd.parse_bmp(b)
-        ups.append((img, torch.frombuffer(bytearray(b[off:off + img.row_stride * img.height]), dtype=torch.uint8).to(dev)))
+    ups = [upload_pixels(b, jpegamd, dev) for b in bmps]
     w, h = ups[0][0].width, ups[0][0].height
-    enc = jpegamd.Encoder(w, len(bmps) * ((h + 7) // 8 * 8))
+    enc = jpegamd.Encoder(w, rows_for(len(bmps), h))
     if pipeline is not None:
         enc.set_pipeline(pipeline)
     cap = 4096 + 2 * w * h
@@ -38,11 +30,10 @@ def _encode_batch(jpegamd, bmps, quality, dev, pipeline=None):
     sizes = [torch.zeros(1, dtype=torch.int64, device=dev) for _ in bmps]
     imgs = [jpegamd.Encoder.image(px.data_ptr(), im.width, im.height, im.row_stride, bool(im.bottom_up), jpegamd.ORDER_BGR, quality)
             for im, px in ups]
-    stream = torch.cuda.current_stream().cuda_stream
     if len(bmps) == 1:
-        enc.encode_async(imgs[0], outs[0].data_ptr(), cap, sizes[0].data_ptr(), True, stream)
+        enc.encode_async(imgs[0], outs[0].data_ptr(), cap, sizes[0].data_ptr(), True, stream())
     else:
-        enc.encode_batch_async(imgs, [o.data_ptr() for o in outs], cap, [s.data_ptr() for s in sizes], True, stream)
+        enc.encode_batch_async(imgs, [o.data_ptr() for o in outs], cap, [s.data_ptr() for s in sizes], True, stream())
     enc.finish()
     return [bytes(o[:int(n.item())].cpu().numpy()) for o, n in zip(outs, sizes)]
 
@@ -113,15 +104,14 @@ def test_single_pass_stitch_on_every_kind_of_content(jpegamd, oracle, dev):
     # the segment without container, and an output buffer that is too small: the would-be size and status -8
     bmp = jpegamd.synth_bmp(1500, 700, 5, 1, 0)
     want = oracle.encode_bmp(bmp)
-    img, off = jpegamd.parse_bmp(bmp)
-    px = torch.frombuffer(bytearray(bmp[off:off + img.row_stride * img.height]), dtype=torch.uint8).to(dev)
+    img, px = upload_pixels(bmp, jpegamd, dev)
     enc = jpegamd.Encoder(1500, 700)
     enc.set_pipeline(jpegamd.PIPELINE_STITCH)
     d = jpegamd.Encoder.image(px.data_ptr(), 1500, 700, img.row_stride, True, jpegamd.ORDER_BGR, 0)
     for cap, container in ((len(want), False), (len(want), True), (len(want) // 2, True)):
         out = torch.zeros(len(want) + 64, dtype=torch.uint8, device=dev)
         size = torch.zeros(1, dtype=torch.int64, device=dev)
-        enc.encode_async(d, out.data_ptr(), cap, size.data_ptr(), container, torch.cuda.current_stream().cuda_stream)
+        enc.encode_async(d, out.data_ptr(), cap, size.data_ptr(), container, stream())
         if cap < len(want):
             with pytest.raises(jpegamd.JpegAmdError) as err:
                 enc.finish()
@@ -172,12 +162,11 @@ def test_c_level_gather_of_streams_over_rccl(jpegamd, oracle, dev):
         enc = jpegamd.Encoder(w, h)
         keep = []
         for k, b in enumerate(bmps):
-            img, off = jpegamd.parse_bmp(b)
-            px = torch.frombuffer(bytearray(b[off:off + img.row_stride * img.height]), dtype=torch.uint8).to(dev)
+            img, px = upload_pixels(b, jpegamd, dev)
             keep.append(px)
             d = jpegamd.Encoder.image(px.data_ptr(), w, h, img.row_stride, True, jpegamd.ORDER_BGR, 0)
             base = records.data_ptr() + k * slot_bytes
-            enc.encode_async(d, base, slot_bytes - 8, base + slot_bytes - 8, True, torch.cuda.current_stream().cuda_stream)
+            enc.encode_async(d, base, slot_bytes - 8, base + slot_bytes - 8, True, stream())
         with pytest.raises(jpegamd.JpegAmdError) as err:
             enc.finish()
         assert err.value.code == -8                                        # record 3 did not fit
@@ -185,7 +174,7 @@ def test_c_level_gather_of_streams_over_rccl(jpegamd, oracle, dev):
         stride = slots * slot_bytes
         recv = torch.zeros(stride, dtype=torch.uint8, device=dev)
         rc = jpegamd.lib.jpegamd_gather_streams(comm, 0, 1, 0, records.data_ptr(), slot_bytes, slots, C.addressof(sizes), recv.data_ptr(), stride,
-                                                torch.cuda.current_stream().cuda_stream)
+                                                stream())
         assert rc == 0
         assert list(sizes) == [len(x) for x in want]
         got, off = recv.cpu().numpy().tobytes(), 0
@@ -195,21 +184,10 @@ def test_c_level_gather_of_streams_over_rccl(jpegamd, oracle, dev):
             assert got[off:off + len(want[k])] == want[k], k
             off += (len(want[k]) + 7) // 8 * 8
         assert jpegamd.lib.jpegamd_gather_streams(comm, 0, 1, 0, records.data_ptr(), slot_bytes, slots, C.addressof(sizes), recv.data_ptr(), 64,
-                                                  torch.cuda.current_stream().cuda_stream) == -8      # a receive area that is too small
+                                                  stream()) == -8      # a receive area that is too small
         assert jpegamd.lib.jpegamd_gather_streams(None, 0, 1, 0, records.data_ptr(), slot_bytes, slots, C.addressof(sizes), recv.data_ptr(), stride, None) == -1
     finally:
         rccl.ncclCommDestroy(comm)
-
-
-def _gray_bmp(y: np.ndarray) -> bytes:
-    """24-bit bottom-up BMP whose three channels all equal `y` (uint8 [H, W]): the luma weights sum to 256, so Y == y exactly."""
-    h, w = y.shape
-    stride = (3 * w + 3) & ~3
-    rows = np.zeros((h, stride), np.uint8)
-    rows[:, :3 * w] = np.repeat(y[::-1], 3, axis=1)
-    head = b"BM" + (54 + stride * h).to_bytes(4, "little") + bytes(4) + (54).to_bytes(4, "little")
-    info = (40).to_bytes(4, "little") + w.to_bytes(4, "little") + h.to_bytes(4, "little") + (1).to_bytes(2, "little") + (24).to_bytes(2, "little") + bytes(24)
-    return head + info + rows.tobytes()
 
 
 @pytest.mark.gpu
@@ -238,14 +216,13 @@ def test_extreme_blocks_through_the_subnormal_matrix_operand(jpegamd, oracle, de
     y = np.zeros((rows * 8, per_row * 8), np.uint8)
     for i, b in enumerate(blocks):
         y[(i // per_row) * 8:(i // per_row) * 8 + 8, (i % per_row) * 8:(i % per_row) * 8 + 8] = b
-    bmp = _gray_bmp(y)
+    bmp = gray_bmp(y)
     enc = jpegamd.Encoder(y.shape[1], y.shape[0])
     for q in (100, 50, 10):
         got = _encode_batch(jpegamd, [bmp], q, dev)[0]
         assert got == oracle.encode_bmp(bmp, q), q
     st = oracle.stages(bmp)
-    img, off = jpegamd.parse_bmp(bmp)
-    px = torch.frombuffer(bytearray(bmp[off:off + img.row_stride * img.height]), dtype=torch.uint8).to(dev)
+    img, px = upload_pixels(bmp, jpegamd, dev)
     n = st["zigzag"].shape[0]
     yt = torch.zeros(n * 64, dtype=torch.int8, device=dev)
     zz = torch.zeros(n * 64, dtype=torch.int16, device=dev)

@@ -4,69 +4,22 @@ oracle.encode_bmp of the same picture as a BMP; the largest case is compared wit
 pin at that size.  Every test needs an MI355X."""
 from __future__ import annotations
 
+import functools
 import hashlib
 
 import numpy as np
 import pytest
 
 import color_fixtures as cf
-import color_model as cm
+import gpu_support
+from gpu_support import GRAY, S420, S444, WIDE_STRIDE, Outputs, dev, intact_files, rows_for, stream, synth_rgb, upload     # noqa: F401
+from gpu_support import model as want                           # (memoised: many layouts share one picture)
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
-WIDE_STRIDE = (1 << 24) + 64
-S420, S444, GRAY = cm.SUB_420, cm.SUB_444, 0
 SIZES = [(1, 1), (7, 9), (203, 117), (333, 250), (520, 16), (1024, 64), (2056, 40)]
-GUARD = 64
-
-
-@pytest.fixture(scope="module")
-def dev():
-    if not torch.cuda.is_available():
-        pytest.fail("gpu-marked test started without a GPU: the product path has no CPU fallback")
-    return torch.device("cuda:0")
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def rows_for(count, h):
-    return count * ((h + 7) // 8 * 8)
-
-
-def synth_rgb(jpegamd, w, h, seed, kind, flags=0):
-    return cm.read_bmp_rgb(jpegamd.synth_bmp(w, h, seed, kind, flags))
-
-
-def pictures(jpegamd, w, h, n, seed=0):
-    """n distinct pictures: photo-like, noise, photo-like, gradient and flat content in turn, different seeds."""
-    kinds = (0, 1, 0, 3, 2)
-    return [synth_rgb(jpegamd, w, h, 300 + 41 * i + seed, kinds[i % len(kinds)], i % 4) for i in range(n)]
-
-
-_want = {}
-
-
-def want(oracle, rgb, quality, sub):
-    """The file the packed path defines for these pixels (memoised: many layouts share one picture)."""
-    key = (rgb.shape, hashlib.sha1(rgb.tobytes()).digest(), quality, sub)
-    if key not in _want:
-        bmp = cm.write_bmp(rgb)
-        if sub == GRAY:
-            _want[key] = oracle.encode_bmp(bmp, quality=quality) if quality else oracle.encode_bmp(bmp)
-        else:
-            _want[key] = cm.color_file(oracle, bmp, quality, sub)
-    return _want[key]
-
-
-def upload(rows: np.ndarray, dev, stride: int, shift: int = 0):
-    """[H, n] bytes as H stored rows `stride` apart, `shift` bytes into an allocation -> (tensor, device pointer)."""
-    h, n = rows.shape
-    t = torch.zeros(shift + stride * (h - 1) + n + 16, dtype=torch.uint8, device=dev)
-    t[shift:shift + stride * (h - 1) + n].as_strided((h, n), (stride, 1)).copy_(torch.from_numpy(rows.copy()).to(dev))
-    return t, t.data_ptr() + shift
+pictures = functools.partial(gpu_support.pictures, base=300, step=41)
 
 
 _rng = np.random.default_rng(2024)
@@ -79,25 +32,6 @@ def px4_rows(rgb: np.ndarray, bottom_up: bool, bgra: bool) -> np.ndarray:
         s = s[:, :, ::-1]
     x = _rng.integers(0, 256, s.shape[:2] + (1,), np.uint8)
     return np.concatenate([s, x], axis=2).reshape(s.shape[0], -1)
-
-
-class Outputs:
-    """n output buffers of `cap` bytes with GUARD canary bytes behind each, and their device sizes."""
-
-    def __init__(self, dev, n, cap):
-        self.cap = cap
-        self.outs = [torch.full((cap + GUARD,), 0xA5, dtype=torch.uint8, device=dev) for _ in range(n)]
-        self.sizes = torch.full((n,), -1, dtype=torch.int64, device=dev)
-        self.out_ptrs = [o.data_ptr() for o in self.outs]
-        self.size_ptrs = [self.sizes.data_ptr() + 8 * i for i in range(n)]
-
-    def files(self):
-        res = []
-        for o, n in zip(self.outs, self.sizes.cpu().tolist()):
-            host = o.cpu().numpy()
-            assert np.all(host[self.cap:] == 0xA5), "guard bytes behind an output were overwritten"
-            res.append(bytes(host[:min(n, self.cap)]))
-        return res
 
 
 def cap_for(jpegamd, w, h, sub):
@@ -115,13 +49,13 @@ def queue_px4(jpegamd, enc, rgbs, dev, sub, order, quality=0, bottom_up=False, s
     if single:
         assert len(rgbs) == 1
         if sub == GRAY:
-            enc.encode_async(imgs[0], o.out_ptrs[0], o.cap, o.size_ptrs[0], True, _stream())
+            enc.encode_async(imgs[0], o.out_ptrs[0], o.cap, o.size_ptrs[0], True, stream())
         else:
-            enc.encode_color_async(imgs[0], sub, o.out_ptrs[0], o.cap, o.size_ptrs[0], _stream())
+            enc.encode_color_async(imgs[0], sub, o.out_ptrs[0], o.cap, o.size_ptrs[0], stream())
     elif sub == GRAY:
-        enc.encode_batch_async(imgs, o.out_ptrs, o.cap, o.size_ptrs, True, _stream())
+        enc.encode_batch_async(imgs, o.out_ptrs, o.cap, o.size_ptrs, True, stream())
     else:
-        enc.encode_color_batch_async(imgs, sub, o.out_ptrs, o.cap, o.size_ptrs, _stream())
+        enc.encode_color_batch_async(imgs, sub, o.out_ptrs, o.cap, o.size_ptrs, stream())
     return o, px
 
 
@@ -163,14 +97,14 @@ def queue_planar(jpegamd, enc, rgbs, dev, sub, how="one", quality=0, bottom_up=F
     ptrs, st, keep = planar_sources(rgbs, dev, how, bottom_up, stride, shifts)
     o = Outputs(dev, len(rgbs), cap if cap is not None else cap_for(jpegamd, w, h, sub))
     imgs = [jpegamd.Encoder.planar_image(p, w, h, st, bottom_up, quality) for p in ptrs]
-    enc.encode_planar_batch_async(imgs, sub, o.out_ptrs, o.cap, o.size_ptrs, _stream())
+    enc.encode_planar_batch_async(imgs, sub, o.out_ptrs, o.cap, o.size_ptrs, stream())
     return o, keep
 
 
-def finish_files(enc, job):
+def finished(enc, job):
     o, keep = job
     enc.finish()
-    return o.files()
+    return intact_files(o)
 
 
 # ---- sizes x outputs x qualities x row orders x layouts ----------------------------------------------------------------------
@@ -184,14 +118,14 @@ def test_every_layout_matches_the_packed_path(jpegamd, oracle, dev, w, h):
             exp = [want(oracle, r, q, sub) for r in rgbs]
             for bottom_up in (False, True):
                 for order in (jpegamd.ORDER_RGBA, jpegamd.ORDER_BGRA):
-                    got = finish_files(enc, queue_px4(jpegamd, enc, rgbs, dev, sub, order, q, bottom_up))
+                    got = finished(enc, queue_px4(jpegamd, enc, rgbs, dev, sub, order, q, bottom_up))
                     assert got == exp, (w, h, sub, q, bottom_up, order)
                 for how in ("one", "three", "crop"):
-                    got = finish_files(enc, queue_planar(jpegamd, enc, rgbs, dev, sub, how, q, bottom_up))
+                    got = finished(enc, queue_planar(jpegamd, enc, rgbs, dev, sub, how, q, bottom_up))
                     assert got == exp, (w, h, sub, q, bottom_up, how)
             # the one-picture entries
             for k, order in ((0, jpegamd.ORDER_RGBA), (1, jpegamd.ORDER_BGRA)):
-                got = finish_files(enc, queue_px4(jpegamd, enc, [rgbs[k]], dev, sub, order, q, single=True))
+                got = finished(enc, queue_px4(jpegamd, enc, [rgbs[k]], dev, sub, order, q, single=True))
                 assert got == [exp[k]], (w, h, sub, q, order, "single")
 
 
@@ -203,9 +137,9 @@ def test_extreme_blocks_in_every_layout(jpegamd, oracle, dev):
     enc = jpegamd.Encoder(w, rows_for(1, h))
     for sub, q in ((GRAY, 0), (S444, 90), (S420, 10)):
         exp = [want(oracle, rgb, q, sub)]
-        assert finish_files(enc, queue_px4(jpegamd, enc, [rgb], dev, sub, jpegamd.ORDER_BGRA, q)) == exp, (sub, q)
-        assert finish_files(enc, queue_planar(jpegamd, enc, [rgb], dev, sub, "one", q)) == exp, (sub, q)
-        assert finish_files(enc, queue_planar(jpegamd, enc, [rgb], dev, sub, "three", q, stride=w + 3)) == exp, (sub, q)
+        assert finished(enc, queue_px4(jpegamd, enc, [rgb], dev, sub, jpegamd.ORDER_BGRA, q)) == exp, (sub, q)
+        assert finished(enc, queue_planar(jpegamd, enc, [rgb], dev, sub, "one", q)) == exp, (sub, q)
+        assert finished(enc, queue_planar(jpegamd, enc, [rgb], dev, sub, "three", q, stride=w + 3)) == exp, (sub, q)
 
 
 # ---- strides and alignment -----------------------------------------------------------------------------------------------
@@ -217,10 +151,10 @@ def test_row_strides(jpegamd, oracle, dev, w, h):
         exp = [want(oracle, r, 0, sub) for r in rgbs]
         for extra in (4, 64, 1, 7):                              # multiples of 4 (the dword loader), and not (the gather)
             for order, bottom_up in ((jpegamd.ORDER_RGBA, False), (jpegamd.ORDER_BGRA, True)):
-                got = finish_files(enc, queue_px4(jpegamd, enc, rgbs, dev, sub, order, 0, bottom_up, stride=4 * w + extra))
+                got = finished(enc, queue_px4(jpegamd, enc, rgbs, dev, sub, order, 0, bottom_up, stride=4 * w + extra))
                 assert got == exp, (w, h, sub, extra, order)
             for bottom_up in (False, True):
-                got = finish_files(enc, queue_planar(jpegamd, enc, rgbs, dev, sub, "three", 0, bottom_up, stride=w + extra))
+                got = finished(enc, queue_planar(jpegamd, enc, rgbs, dev, sub, "three", 0, bottom_up, stride=w + extra))
                 assert got == exp, (w, h, sub, extra, bottom_up)
 
 
@@ -232,16 +166,16 @@ def test_base_pointers_off_alignment(jpegamd, oracle, dev, shift):
     for sub in (S420, S444, GRAY):
         exp = [want(oracle, r, 0, sub) for r in rgbs]
         for stride_extra in (0, 1):
-            got = finish_files(enc, queue_px4(jpegamd, enc, rgbs, dev, sub, jpegamd.ORDER_RGBA, stride=4 * w + 4 * stride_extra,
+            got = finished(enc, queue_px4(jpegamd, enc, rgbs, dev, sub, jpegamd.ORDER_RGBA, stride=4 * w + 4 * stride_extra,
                                               shifts=[0, shift, 0]))
             assert got == exp, (shift, sub, stride_extra)
             for plane in range(3):                               # one plane of every picture off the dword grid
                 shifts = [0, 0, 0]
                 shifts[plane] = shift
-                got = finish_files(enc, queue_planar(jpegamd, enc, rgbs, dev, sub, "three", stride=w + 1 + 3 * stride_extra,
+                got = finished(enc, queue_planar(jpegamd, enc, rgbs, dev, sub, "three", stride=w + 1 + 3 * stride_extra,
                                                      shifts=tuple(shifts)))
                 assert got == exp, (shift, sub, stride_extra, plane)
-        got = finish_files(enc, queue_planar(jpegamd, enc, rgbs, dev, sub, "three", stride=w + 1, shifts=(shift, shift, shift)))
+        got = finished(enc, queue_planar(jpegamd, enc, rgbs, dev, sub, "three", stride=w + 1, shifts=(shift, shift, shift)))
         assert got == exp, (shift, sub, "all planes")
 
 
@@ -251,8 +185,8 @@ def test_row_stride_above_2_pow_24(jpegamd, oracle, dev):
     enc = jpegamd.Encoder(w, rows_for(1, h))
     for sub in (S420, GRAY):
         exp = [want(oracle, rgbs[0], 0, sub)]
-        assert finish_files(enc, queue_px4(jpegamd, enc, rgbs, dev, sub, jpegamd.ORDER_RGBA, stride=WIDE_STRIDE)) == exp, sub
-        assert finish_files(enc, queue_planar(jpegamd, enc, rgbs, dev, sub, "three", stride=WIDE_STRIDE)) == exp, sub
+        assert finished(enc, queue_px4(jpegamd, enc, rgbs, dev, sub, jpegamd.ORDER_RGBA, stride=WIDE_STRIDE)) == exp, sub
+        assert finished(enc, queue_planar(jpegamd, enc, rgbs, dev, sub, "three", stride=WIDE_STRIDE)) == exp, sub
 
 
 # ---- batch counts ------------------------------------------------------------------------------------------------------------
@@ -263,10 +197,10 @@ def test_batch_counts(jpegamd, oracle, dev, count):
     enc = jpegamd.Encoder(w, rows_for(count, h))
     for sub, q in ((S420, 0), (S444, 90), (GRAY, 10)):
         exp = [want(oracle, r, q, sub) for r in rgbs]
-        assert finish_files(enc, queue_px4(jpegamd, enc, rgbs, dev, sub, jpegamd.ORDER_RGBA, q)) == exp, (count, sub)
-        assert finish_files(enc, queue_px4(jpegamd, enc, rgbs, dev, sub, jpegamd.ORDER_BGRA, q, bottom_up=True)) == exp, (count, sub)
-        assert finish_files(enc, queue_planar(jpegamd, enc, rgbs, dev, sub, "one", q)) == exp, (count, sub)
-        assert finish_files(enc, queue_planar(jpegamd, enc, rgbs, dev, sub, "crop", q, bottom_up=True)) == exp, (count, sub)
+        assert finished(enc, queue_px4(jpegamd, enc, rgbs, dev, sub, jpegamd.ORDER_RGBA, q)) == exp, (count, sub)
+        assert finished(enc, queue_px4(jpegamd, enc, rgbs, dev, sub, jpegamd.ORDER_BGRA, q, bottom_up=True)) == exp, (count, sub)
+        assert finished(enc, queue_planar(jpegamd, enc, rgbs, dev, sub, "one", q)) == exp, (count, sub)
+        assert finished(enc, queue_planar(jpegamd, enc, rgbs, dev, sub, "crop", q, bottom_up=True)) == exp, (count, sub)
 
 
 def test_forty_pictures_through_encode_tensor_batch(jpegamd, oracle, dev):
@@ -327,10 +261,10 @@ def test_one_picture_of_a_batch_one_byte_short(jpegamd, oracle, dev):
             with pytest.raises(jpegamd.JpegAmdError) as err:
                 enc.finish()
             assert err.value.code == -8
-            got = o.files()                                      # (checks the guard bytes; a file is cut at the capacity)
+            got = intact_files(o)                                      # (checks the guard bytes; a file is cut at the capacity)
             assert int(o.sizes[1].item()) == (len(exp[1]) if sub == GRAY else 0), sub
             assert [got[k] for k in (0, 2, 3)] == [exp[k] for k in (0, 2, 3)], sub
-            assert finish_files(enc, queue(cap + 1)) == exp, sub    # the exact capacity fits; the context is clean again
+            assert finished(enc, queue(cap + 1)) == exp, sub    # the exact capacity fits; the context is clean again
 
 
 # ---- one context, interleaved ---------------------------------------------------------------------------------------------
@@ -346,7 +280,7 @@ def test_one_context_interleaved_sources(jpegamd, oracle, dev):
         px = [upload(np.ascontiguousarray(r).reshape(h, -1), dev, 3 * w) for r in rgbs]
         o = Outputs(dev, 3, cap_for(jpegamd, w, h, sub))
         imgs = [jpegamd.Encoder.image(ptr, w, h, 3 * w, False, jpegamd.ORDER_RGB, q) for _, ptr in px]
-        enc.encode_color_batch_async(imgs, sub, o.out_ptrs, o.cap, o.size_ptrs, _stream())
+        enc.encode_color_batch_async(imgs, sub, o.out_ptrs, o.cap, o.size_ptrs, stream())
         jobs.append((o, px, [want(oracle, r, q, sub) for r in rgbs]))
 
     def gray(q):
@@ -354,7 +288,7 @@ def test_one_context_interleaved_sources(jpegamd, oracle, dev):
         px = [upload(y, dev, w) for y in lum]
         o = Outputs(dev, 3, cap_for(jpegamd, w, h, GRAY))
         imgs = [jpegamd.Encoder.image(ptr, w, h, w, False, jpegamd.ORDER_GRAY, q) for _, ptr in px]
-        enc.encode_batch_async(imgs, o.out_ptrs, o.cap, o.size_ptrs, True, _stream())
+        enc.encode_batch_async(imgs, o.out_ptrs, o.cap, o.size_ptrs, True, stream())
         jobs.append((o, px, [want(oracle, r, q, GRAY) for r in rgbs]))
 
     packed(S420, 0)
@@ -367,7 +301,7 @@ def test_one_context_interleaved_sources(jpegamd, oracle, dev):
     packed(S420, 90)
     enc.finish()
     for i, (o, keep, exp) in enumerate(jobs):
-        assert o.files() == exp, i
+        assert intact_files(o) == exp, i
 
 
 # ---- full size --------------------------------------------------------------------------------------------------------------
@@ -376,7 +310,7 @@ def test_four_4096_pictures_per_layout(jpegamd, dev, pipeline):
     """4096 x 4096, Q = 50, 4:2:0, a batch of 4: every layout against the packed batch entry on the same pixels, by hash."""
     w = h = 4096
     rgbs = [synth_rgb(jpegamd, w, h, 91 + i, i % 2) for i in range(4)]
-    enc = jpegamd.Encoder(w, 4 * h)
+    enc = jpegamd.Encoder(w, rows_for(4, h))
     enc.set_pipeline(getattr(jpegamd, pipeline))
     cap = 2 * w * h + (1 << 20)
 
@@ -387,10 +321,10 @@ def test_four_4096_pictures_per_layout(jpegamd, dev, pipeline):
     px = [upload(np.ascontiguousarray(r).reshape(h, -1), dev, 3 * w) for r in rgbs]
     o = Outputs(dev, 4, cap)
     imgs = [jpegamd.Encoder.image(ptr, w, h, 3 * w, False, jpegamd.ORDER_RGB, 50) for _, ptr in px]
-    enc.encode_color_batch_async(imgs, S420, o.out_ptrs, o.cap, o.size_ptrs, _stream())
+    enc.encode_color_batch_async(imgs, S420, o.out_ptrs, o.cap, o.size_ptrs, stream())
     enc.finish()
-    exp = digests(o.files())
+    exp = digests(intact_files(o))
     del px, o
-    assert digests(finish_files(enc, queue_px4(jpegamd, enc, rgbs, dev, S420, jpegamd.ORDER_RGBA, 50, cap=cap))) == exp
-    assert digests(finish_files(enc, queue_px4(jpegamd, enc, rgbs, dev, S420, jpegamd.ORDER_BGRA, 50, cap=cap))) == exp
-    assert digests(finish_files(enc, queue_planar(jpegamd, enc, rgbs, dev, S420, "one", 50, cap=cap))) == exp
+    assert digests(finished(enc, queue_px4(jpegamd, enc, rgbs, dev, S420, jpegamd.ORDER_RGBA, 50, cap=cap))) == exp
+    assert digests(finished(enc, queue_px4(jpegamd, enc, rgbs, dev, S420, jpegamd.ORDER_BGRA, 50, cap=cap))) == exp
+    assert digests(finished(enc, queue_planar(jpegamd, enc, rgbs, dev, S420, "one", 50, cap=cap))) == exp

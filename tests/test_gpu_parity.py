@@ -14,36 +14,10 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, PKG, ROOT, fixture_bmp, golden_jpg
+from gpu_support import dev, device_encode, upload_pixels     # noqa: F401
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
-
-
-@pytest.fixture(scope="module")
-def dev():
-    if not torch.cuda.is_available():
-        pytest.fail("gpu-marked test started without a GPU: the product path has no CPU fallback")
-    return torch.device("cuda:0")
-
-
-def upload_pixels(bmp: bytes, jpegamd, dev):
-    img, off = jpegamd.parse_bmp(bmp)
-    n = img.row_stride * img.height
-    t = torch.frombuffer(bytearray(bmp[off:off + n]), dtype=torch.uint8).to(dev)
-    return img, t
-
-
-def device_encode(jpegamd, enc, bmp, dev, quality=0, container=True, cap=None):
-    img, px = upload_pixels(bmp, jpegamd, dev)
-    cap = cap or (4096 + 2 * img.width * img.height)
-    out = torch.empty(cap, dtype=torch.uint8, device=dev)
-    size = torch.zeros(1, dtype=torch.int64, device=dev)
-    d = jpegamd.Encoder.image(px.data_ptr(), img.width, img.height, img.row_stride, bool(img.bottom_up), jpegamd.ORDER_BGR, quality)
-    enc.encode_async(d, out.data_ptr(), cap, size.data_ptr(), container, torch.cuda.current_stream().cuda_stream)
-    st = enc.finish()
-    n = int(size.item())
-    assert n == st.jfif_bytes
-    return bytes(out[:n].cpu().numpy()), st
 
 
 def test_goldens_through_c_abi(jpegamd, manifest, dev):

@@ -7,14 +7,14 @@ from __future__ import annotations
 import numpy as np
 import pytest
 
+import color_model as cm
 import quant_fixtures as qf
 import quant_model as qm
 import range_model as rm
-from test_gpu_color_batch import rows_for, upload
-from test_gpu_color_edges import gray_bmp
-from test_gpu_subsample422 import PLANES as I422, YUYV, Ycc422Batch, want_ycc
-from test_gpu_ycbcr import CBCR, PLANES, S444, YccBatch, expected
-from test_gpu_ycbcr_range import limited
+from gpu_support import CBCR, PLANES, S422, S444, YUYV, YccBatch, block_rows_reversed, dev, finish_files, rows_for, upload     # noqa: F401
+from gpu_support import encode_gray_planes as encode_gray
+from gpu_support import gray_bmp_sized as gray_bmp
+from gpu_support import ycc_file as expected
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
@@ -23,29 +23,12 @@ WIDTHS = (256, 264)                                              # whole tiles; 
 
 
 @pytest.fixture(scope="module")
-def dev():
-    if not torch.cuda.is_available():
-        pytest.fail("gpu-marked test started without a GPU: the product path has no CPU fallback")
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
 def full(jpegamd, oracle):
     return qf.fixture_set(jpegamd, oracle, "full")
 
 
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-_files = {}
-
-
 def gray_file(oracle, plane, q):
-    key = (plane.tobytes(), plane.shape, q)
-    if key not in _files:
-        _files[key] = oracle.encode_bmp(gray_bmp(plane), q)
-    return _files[key]
+    return cm.memo(cm.gray_file, oracle, plane, q)
 
 
 def flags_of(jpegamd, oracle, plane, table, q) -> int:
@@ -63,35 +46,9 @@ def flat_like(plane, value=128):
     return np.full_like(plane, value)
 
 
-def encode_gray(jpegamd, enc, planes, dev, q):
-    """GRAY planes of one geometry: one call of jpegamd_encode_async, or one batch -> (files, Stats)."""
-    h, w = planes[0].shape
-    keep = [upload(p, dev, w) for p in planes]
-    cap = jpegamd.max_jfif_bytes(w, h)
-    outs = [torch.empty(cap, dtype=torch.uint8, device=dev) for _ in planes]
-    sizes = [torch.zeros(1, dtype=torch.int64, device=dev) for _ in planes]
-    imgs = [jpegamd.Encoder.image(ptr, w, h, w, False, jpegamd.ORDER_GRAY, q) for _, ptr in keep]
-    if len(planes) == 1:
-        enc.encode_async(imgs[0], outs[0].data_ptr(), cap, sizes[0].data_ptr(), True, _stream())
-    else:
-        enc.encode_batch_async(imgs, [o.data_ptr() for o in outs], cap, [s.data_ptr() for s in sizes], True, _stream())
-    st = enc.finish()
-    return [bytes(o[:int(s.item())].cpu().numpy()) for o, s in zip(outs, sizes)], st
-
-
-def encode_ycc(jpegamd, enc, planes, dev, layout, q):
-    """4:4:4 YCbCr pictures through jpegamd_encode_ycbcr_batch_async (enc: a context, or one wrapped by limited()) -> (files, Stats)."""
-    b = YccBatch(jpegamd, enc, planes, dev, S444, layout, quality=q)
-    st = enc.finish()
-    res = b.results()
-    assert all(ok for _, ok in res)
-    return [f for f, _ in res], st
-
-
-def block_rows_reversed(plane):
-    """The same tiles in the opposite order (another picture of the same geometry for a batch)."""
-    h, w = plane.shape
-    return np.ascontiguousarray(plane.reshape(h // 8, 8, w)[::-1].reshape(h, w))
+def encode_ycc(jpegamd, enc, planes, dev, layout, q, **kw):
+    """4:4:4 YCbCr pictures through jpegamd_encode_ycbcr_batch_async (kw: YccBatch's, such as a sample range) -> (files, Stats)."""
+    return finish_files(enc, YccBatch(jpegamd, enc, planes, dev, S444, layout, quality=q, **kw))
 
 
 # ---- 1. the taps build: coefficients and the flagged set, block for block -----------------------------------------------------------
@@ -174,8 +131,7 @@ def test_expanding_instantiations_chroma_planes(jpegamd, oracle, dev, layout):
     those of the mapped planes."""
     ys, cs, ypre, cpre = limited_sets(jpegamd, oracle)
     for width in WIDTHS:
-        real = jpegamd.Encoder(width, rows_for(2, max(cs.plane(q).shape[0] for q in cs.qualities())))
-        enc = limited(jpegamd, real)
+        enc = jpegamd.Encoder(width, rows_for(2, max(cs.plane(q).shape[0] for q in cs.qualities())))
         for q in cs.qualities():
             p = cs.plane(q, width)
             flat = flat_like(p)
@@ -183,7 +139,7 @@ def test_expanding_instantiations_chroma_planes(jpegamd, oracle, dev, layout):
             mapped = [rm.expand(x) for x in stored]
             assert all(np.array_equal(a, b) for m, x in zip(mapped, [(flat, p, flat), (flat, flat, p)]) for a, b in zip(m, x))
             flags = flags_of(jpegamd, oracle, p, "chroma", q)
-            files, st = encode_ycc(jpegamd, enc, stored, dev, layout, q)
+            files, st = encode_ycc(jpegamd, enc, stored, dev, layout, q, sample_range=jpegamd.RANGE_LIMITED)
             assert st.exact_fallbacks == 2 * flags, (q, width, st.exact_fallbacks, flags)
             assert files == [expected(oracle, x, q, S444) for x in mapped], (q, width)
         assert sum(differ_of(jpegamd, oracle, cs.plane(q, width), "chroma", q) for q in cs.qualities()) >= 16
@@ -193,7 +149,7 @@ def _pad_rows(plane, rows, value=128):
     return np.ascontiguousarray(np.pad(plane, ((0, rows - plane.shape[0]), (0, 0)), constant_values=value))
 
 
-@pytest.mark.parametrize("layout", [I422, YUYV])
+@pytest.mark.parametrize("layout", [PLANES, YUYV])               # I422, and the packed plane
 def test_expanding_instantiations_y_and_422(jpegamd, oracle, dev, layout):
     """4:2:2, limited range: the Y plane is two copies of the luma-map fixture plane side by side (through the plane loader for I422, the
     pair loader for YUYV), Cb and Cr the chroma-map fixture planes (the plane loader, the quad loader)."""
@@ -208,14 +164,13 @@ def test_expanding_instantiations_y_and_422(jpegamd, oracle, dev, layout):
         mapped = rm.expand(stored)
         assert all(np.array_equal(a, b) for a, b in zip(mapped, (y, cb, cr)))
         flags = flags_of(jpegamd, oracle, y, "luma", q) + flags_of(jpegamd, oracle, cb, "chroma", q) + flags_of(jpegamd, oracle, cr, "chroma", q)
-        real = jpegamd.Encoder(2 * width, rows_for(1, rows))
-        enc = limited(jpegamd, real)
-        b = Ycc422Batch(jpegamd, enc, [stored], dev, layout, quality=q)
-        st = real.finish()
+        enc = jpegamd.Encoder(2 * width, rows_for(1, rows))
+        b = YccBatch(jpegamd, enc, [stored], dev, S422, layout, quality=q, sample_range=jpegamd.RANGE_LIMITED)
+        st = enc.finish()
         res = b.results()
         assert all(ok for _, ok in res)
         assert st.exact_fallbacks == flags and flags > 0, (width, st.exact_fallbacks, flags)
-        assert [f for f, _ in res] == [want_ycc(oracle, mapped, q)], width
+        assert [f for f, _ in res] == [expected(oracle, mapped, q, S422)], width
 
 
 # ---- 5. every quality, both tables ----------------------------------------------------------------------------------------------------

@@ -10,19 +10,12 @@ import numpy as np
 import pytest
 
 import stash_sequence as ss
-from test_gpu_color_edges import gray_bmp
-from test_gpu_parity import device_encode, upload_pixels
-from test_gpu_quantiser import block_rows_reversed, encode_gray
+from gpu_support import block_rows_reversed, dev, device_encode, upload_pixels     # noqa: F401
+from gpu_support import encode_gray_planes as encode_gray
+from gpu_support import gray_bmp_sized as gray_bmp
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def dev():
-    if not torch.cuda.is_available():
-        pytest.fail("gpu-marked test started without a GPU: the product path has no CPU fallback")
-    return torch.device("cuda:0")
 
 
 @pytest.fixture(scope="module")

@@ -7,14 +7,14 @@ import pytest
 
 import color_model as cm
 import color_model_422 as m422
-from test_gpu_color_batch import ColorBatch, rows_for, stored_rows, synth_rgb, upload
+from gpu_support import (PLANES, CBCR, CRCB, S422, UYVY, YUYV, ColorBatch, ColorCall, YccBatch, dev, finish_files, random_planes,     # noqa: F401
+                         rows_for, run_ycc, stream, synth_rgb, upload, ycc_file)
+from gpu_support import LAYOUTS_422 as YCC_LAYOUTS
+from gpu_support import model
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
-S422 = m422.SUB_422
-PLANES, CBCR, CRCB, YUYV, UYVY = 0, 1, 2, m422.YUYV, m422.UYVY
-YCC_LAYOUTS = (PLANES, CBCR, CRCB, YUYV, UYVY)
 
 # W x H                  why
 RGB_SIZES = [(1, 1),     # the smallest picture
@@ -31,33 +31,12 @@ YCC_SIZES = [(1, 1), (2, 2),
              (640, 16)]  # cw = 320, every row a multiple of 4 bytes: interior tiles on the fast loaders
 
 
-@pytest.fixture(scope="module")
-def dev():
-    if not torch.cuda.is_available():
-        pytest.fail("gpu-marked test started without a GPU: the product path has no CPU fallback")
-    return torch.device("cuda:0")
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-_want = {}
-
-
 def want_rgb(oracle, rgb, q):
-    key = (rgb.tobytes(), rgb.shape, q)
-    if key not in _want:
-        _want[key] = m422.color_file_422(oracle, cm.write_bmp(rgb), q)
-    return _want[key]
+    return model(oracle, rgb, q, S422)
 
 
 def want_ycc(oracle, planes, q):
-    y, cb, cr = planes
-    key = (y.tobytes(), cb.tobytes(), cr.tobytes(), y.shape, q)
-    if key not in _want:
-        _want[key] = m422.ycbcr_file_422(oracle, y, cb, cr, q)
-    return _want[key]
+    return ycc_file(oracle, planes, q, S422)
 
 
 def two_pictures(jpegamd, w, h, seed=0):
@@ -66,26 +45,16 @@ def two_pictures(jpegamd, w, h, seed=0):
 
 
 def finish_batch(enc, b):
-    st = enc.finish()
-    res = b.results()
-    assert all(ok for _, ok in res)                              # the canaries behind every output
-    assert st.jfif_bytes == len(res[-1][0])
-    return [f for f, _ in res]
+    return finish_files(enc, b)[0]                               # (the canaries behind every output, and Stats.jfif_bytes)
 
 
 def single(jpegamd, enc, rgb, dev, q=0, bgr=False, bottom_up=False):
     """jpegamd_encode_color_async of one picture at 4:2:2."""
-    h, w, _ = rgb.shape
-    t, ptr = upload(stored_rows(rgb, bottom_up, bgr), dev, 3 * w)
-    cap = jpegamd.max_jfif_bytes_color(w, h, S422)
-    out = torch.full((cap + 64,), 0xA5, dtype=torch.uint8, device=dev)
-    size = torch.zeros(1, dtype=torch.int64, device=dev)
-    order = jpegamd.ORDER_BGR if bgr else jpegamd.ORDER_RGB
-    enc.encode_color_async(jpegamd.Encoder.image(ptr, w, h, 3 * w, bottom_up, order, q), S422, out.data_ptr(), cap, size.data_ptr(), _stream())
+    call = ColorCall(jpegamd, enc, rgb, dev, S422, quality=q, bgr=bgr, bottom_up=bottom_up)
     enc.finish()
-    host = out.cpu().numpy()
-    assert np.all(host[cap:] == 0xA5)
-    return bytes(host[:int(size.item())])
+    got, intact = call.result()
+    assert intact
+    return got
 
 
 # ---- 1. RGB -> 4:2:2 ------------------------------------------------------------------------------------------------------------------
@@ -171,58 +140,6 @@ def test_every_layout_gives_the_packed_rgb_file_at_422(jpegamd, oracle, dev, w, 
 
 
 # ---- 3. the YCbCr entry -----------------------------------------------------------------------------------------------------------------
-def random_planes(w, h, seed):
-    rng = np.random.default_rng(seed)
-    cw = (w + 1) // 2
-    return rng.integers(0, 256, (h, w), np.uint8), rng.integers(0, 256, (h, cw), np.uint8), rng.integers(0, 256, (h, cw), np.uint8)
-
-
-class Ycc422Batch:
-    """One 4:2:2 YCbCr batch queued on `enc` (not finished), the samples stored as `layout` says.  Every stored plane lies `shift` bytes
-    into its allocation with rows `stride` apart (y_* : the Y plane, or the packed plane; c_* : the chroma planes or the pair plane);
-    each output has 64 canary bytes behind `cap`."""
-
-    def __init__(self, jpegamd, enc, planes, dev, layout, quality=0, y_stride=None, c_stride=None, y_shifts=None, c_shifts=None, cap=None):
-        h, w = planes[0][0].shape
-        cw = (w + 1) // 2
-        n = len(planes)
-        packed = layout in (YUYV, UYVY)
-        y_stride = y_stride or (4 * cw if packed else w)
-        c_stride = c_stride or (cw if layout == PLANES else 2 * cw)
-        y_shifts, c_shifts = y_shifts or [0] * n, c_shifts or [0] * n
-        self.keep, imgs = [], []
-        for (y, cb, cr), ys, cs in zip(planes, y_shifts, c_shifts):
-            if packed:
-                t, p = upload(m422.pack_yuyv(y, cb, cr, "yuyv" if layout == YUYV else "uyvy"), dev, y_stride, ys)
-                self.keep.append(t)
-                imgs.append(jpegamd.Encoder.ycbcr_image(p, 0, 0, w, h, y_stride, 0, layout, quality))
-                continue
-            ty, py = upload(y, dev, y_stride, ys)
-            if layout == PLANES:
-                ups = [upload(cb, dev, c_stride, cs), upload(cr, dev, c_stride, cs)]
-            else:
-                first, second = (cb, cr) if layout == CBCR else (cr, cb)
-                ups = [upload(np.ascontiguousarray(np.stack([first, second], axis=2).reshape(h, -1)), dev, c_stride, cs)]
-            self.keep.append((ty, ups))
-            imgs.append(jpegamd.Encoder.ycbcr_image(py, ups[0][1], ups[1][1] if layout == PLANES else 0, w, h, y_stride, c_stride, layout, quality))
-        self.cap = cap if cap is not None else jpegamd.max_jfif_bytes_color(w, h, S422)
-        self.outs = [torch.full((self.cap + 64,), 0xA5, dtype=torch.uint8, device=dev) for _ in planes]
-        self.sizes = torch.full((n,), -1, dtype=torch.int64, device=dev)
-        enc.encode_ycbcr_batch_async(imgs, S422, [o.data_ptr() for o in self.outs], self.cap,
-                                     [self.sizes.data_ptr() + 8 * i for i in range(n)], _stream())
-
-    def results(self):
-        res = []
-        for o, n in zip(self.outs, self.sizes.cpu().tolist()):
-            host = o.cpu().numpy()
-            res.append((bytes(host[:n]), bool(np.all(host[self.cap:] == 0xA5))))
-        return res
-
-
-def run_ycc(jpegamd, enc, planes, dev, layout, **kw):
-    return finish_batch(enc, Ycc422Batch(jpegamd, enc, planes, dev, layout, **kw))
-
-
 def test_the_rgb_paths_own_planes_give_the_rgb_paths_file_at_422(jpegamd, oracle, dev):
     w, h = 513, 17
     rgbs = two_pictures(jpegamd, w, h) + [synth_rgb(jpegamd, w, h, 13, 0, 1)]
@@ -231,17 +148,17 @@ def test_the_rgb_paths_own_planes_give_the_rgb_paths_file_at_422(jpegamd, oracle
     assert finish_batch(enc, ColorBatch(jpegamd, enc, rgbs, dev, S422)) == want      # what the colour path writes
     planes = [(m422.luma_plane(r),) + m422.chroma_planes_422(r) for r in rgbs]
     for layout in YCC_LAYOUTS:
-        assert run_ycc(jpegamd, enc, planes, dev, layout) == want, layout
+        assert run_ycc(jpegamd, enc, planes, dev, S422, layout) == want, layout
 
 
 @pytest.mark.parametrize("w,h", YCC_SIZES)
 def test_every_ycbcr_layout_gives_the_file_by_definition(jpegamd, oracle, dev, w, h):
-    planes = [random_planes(w, h, 1000 * w + h + k) for k in range(2)]
+    planes = [random_planes(w, h, S422, 1000 * w + h + k) for k in range(2)]
     enc = jpegamd.Encoder(w, rows_for(2, h))
     for q in ((0, 10, 100) if (w, h) in ((7, 9), (513, 17)) else (0,)):
         want = [want_ycc(oracle, p, q) for p in planes]
         for layout in YCC_LAYOUTS:
-            assert run_ycc(jpegamd, enc, planes, dev, layout, quality=q) == want, (w, h, q, layout)
+            assert run_ycc(jpegamd, enc, planes, dev, S422, layout, quality=q) == want, (w, h, q, layout)
     if w % 2:                                                     # another poison value in the byte that is never read: the same files
         want = [want_ycc(oracle, p, 0) for p in planes]
         cw = (w + 1) // 2
@@ -252,7 +169,7 @@ def test_every_ycbcr_layout_gives_the_file_by_definition(jpegamd, oracle, dev, w
             outs = torch.zeros((2, cap), dtype=torch.uint8, device=dev)
             sizes = torch.zeros(2, dtype=torch.int64, device=dev)
             enc.encode_ycbcr_batch_async(imgs, S422, [outs[i].data_ptr() for i in range(2)], cap, [sizes.data_ptr() + 8 * i for i in range(2)],
-                                         _stream())
+                                         stream())
             enc.finish()
             assert [bytes(outs[i, :int(sizes[i])].cpu().numpy()) for i in range(2)] == want, layout
 
@@ -269,18 +186,18 @@ def test_an_odd_chroma_group_starts_a_launch_on_a_cr_plane(jpegamd, oracle, dev,
     assert group % 2 == 1 and launches == 2 and group == count, (group, launches)
     enc = jpegamd.Encoder(w, rows_for(count, h))
     enc.set_pipeline(pipe)
-    planes = [random_planes(w, h, 90 + k) for k in range(count)]
+    planes = [random_planes(w, h, S422, 90 + k) for k in range(count)]
     want = [want_ycc(oracle, p, 0) for p in planes]
     assert len(set(want)) == count                               # every picture distinct
     for layout in YCC_LAYOUTS:
-        assert run_ycc(jpegamd, enc, planes, dev, layout) == want, (count, layout)
+        assert run_ycc(jpegamd, enc, planes, dev, S422, layout) == want, (count, layout)
 
 
 @pytest.mark.parametrize("layout", [YUYV, UYVY])
 def test_packed_planes_off_the_dword_grid(jpegamd, oracle, dev, layout):
     w, h = 513, 17
     row = 4 * ((w + 1) // 2)
-    planes = [random_planes(w, h, 70 + k) for k in range(3)]
+    planes = [random_planes(w, h, S422, 70 + k) for k in range(3)]
     want = [want_ycc(oracle, p, 0) for p in planes]
     enc = jpegamd.Encoder(w, rows_for(3, h))
     cases = [dict(y_stride=row + 8),                              # aligned, rows apart: the fast loaders
@@ -290,20 +207,20 @@ def test_packed_planes_off_the_dword_grid(jpegamd, oracle, dev, layout):
              dict(y_stride=row + 1), dict(y_stride=row + 2), dict(y_stride=row + 3),     # a stride off the grid
              dict(y_shifts=[1, 1, 1], y_stride=row + 3)]
     for kw in cases:
-        assert run_ycc(jpegamd, enc, planes, dev, layout, **kw) == want, (layout, kw)
+        assert run_ycc(jpegamd, enc, planes, dev, S422, layout, **kw) == want, (layout, kw)
 
 
 def test_i422_and_nv16_off_the_dword_grid(jpegamd, oracle, dev):
     w, h = 513, 17
     cw = (w + 1) // 2
-    planes = [random_planes(w, h, 70 + k) for k in range(3)]
+    planes = [random_planes(w, h, S422, 70 + k) for k in range(3)]
     want = [want_ycc(oracle, p, 0) for p in planes]
     enc = jpegamd.Encoder(w, rows_for(3, h))
     for layout, row in ((PLANES, cw), (CBCR, 2 * cw), (CRCB, 2 * cw)):
         aligned = (row + 3) // 4 * 4
         for kw in (dict(y_stride=w + 3, c_stride=aligned), dict(y_stride=w + 3, c_stride=aligned, c_shifts=[0, 0, 1]),
                    dict(y_stride=w + 3, c_stride=aligned + 1), dict(y_stride=w + 2, c_stride=aligned, y_shifts=[0, 3, 0])):
-            assert run_ycc(jpegamd, enc, planes, dev, layout, **kw) == want, (layout, kw)
+            assert run_ycc(jpegamd, enc, planes, dev, S422, layout, **kw) == want, (layout, kw)
 
 
 def test_encode_yuyv_batch(jpegamd, oracle, dev):
@@ -349,8 +266,8 @@ def test_one_picture_of_a_422_batch_one_byte_short(jpegamd, oracle, dev):
     assert cap > max(len(exp[0]), len(exp[2]))
     enc = jpegamd.Encoder(w, rows_for(3, h))
     planes = [(m422.luma_plane(r),) + m422.chroma_planes_422(r) for r in rgbs]
-    jobs = [lambda c: ColorBatch(jpegamd, enc, rgbs, dev, S422, cap=c), lambda c: Ycc422Batch(jpegamd, enc, planes, dev, YUYV, cap=c),
-            lambda c: Ycc422Batch(jpegamd, enc, planes, dev, PLANES, cap=c)]
+    jobs = [lambda c: ColorBatch(jpegamd, enc, rgbs, dev, S422, cap=c), lambda c: YccBatch(jpegamd, enc, planes, dev, S422, YUYV, cap=c),
+            lambda c: YccBatch(jpegamd, enc, planes, dev, S422, PLANES, cap=c)]
     for k, job in enumerate(jobs):
         b = job(cap)
         with pytest.raises(jpegamd.JpegAmdError) as err:

@@ -17,16 +17,10 @@ import color_fixtures as cf
 import color_model as cm
 import path_model as pm
 import threshold_fixtures as tf
+from gpu_support import dev     # noqa: F401
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
-
-
-@pytest.fixture(scope="module")
-def dev():
-    if not torch.cuda.is_available():
-        pytest.fail("gpu-marked test started without a GPU: the product path has no CPU fallback")
-    return torch.device("cuda:0")
 
 
 @pytest.fixture(scope="module")

@@ -7,15 +7,13 @@ import numpy as np
 import pytest
 
 import color_model as cm
-from test_gpu_color_batch import ColorBatch, pictures, rows_for, stored_rows, synth_rgb, upload
+from gpu_support import (CBCR, CRCB, LAYOUTS, PLANES, S420, S444, WIDE_STRIDE, ColorBatch, YccBatch, chroma_dims, dev, model, pictures,     # noqa: F401
+                         random_planes, rows_for, run_ycc, smooth_planes, stream, upload)
+from gpu_support import ycc_file as expected
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
-S420, S444 = cm.SUB_420, cm.SUB_444
-PLANES, CBCR, CRCB = 0, 1, 2
-LAYOUTS = (PLANES, CBCR, CRCB)
-WIDE_STRIDE = (1 << 24) + 64
 
 # W x H                 why
 SIZES = [(1, 1),        # the smallest picture
@@ -24,111 +22,6 @@ SIZES = [(1, 1),        # the smallest picture
          (48, 32),      # an interior partial tile
          (522, 38),     # 4:2:0 chroma is 261 wide: a full 32-block interior tile plus an edge tile, with a bottom edge
          (1030, 24)]    # three chroma tiles per row
-
-
-@pytest.fixture(scope="module")
-def dev():
-    if not torch.cuda.is_available():
-        pytest.fail("gpu-marked test started without a GPU: the product path has no CPU fallback")
-    return torch.device("cuda:0")
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def chroma_dims(w, h, sub):
-    return ((w + 1) // 2, (h + 1) // 2) if sub == S420 else (w, h)
-
-
-def random_planes(w, h, sub, seed):
-    """(y, cb, cr) of uniform noise: uint8 [H, W], [ch, cw], [ch, cw]."""
-    rng = np.random.default_rng(seed)
-    cw, ch = chroma_dims(w, h, sub)
-    return rng.integers(0, 256, (h, w), np.uint8), rng.integers(0, 256, (ch, cw), np.uint8), rng.integers(0, 256, (ch, cw), np.uint8)
-
-
-def smooth_planes(w, h, sub, seed):
-    """(y, cb, cr) of photo-like content: the model's planes of a synthetic picture (small files)."""
-    import jpegamd
-    return model_planes(synth_rgb(jpegamd, w, h, seed, 0), sub)
-
-
-def model_planes(rgb, sub):
-    """What the colour path derives from an RGB picture: the luma formula and color_model.chroma_planes."""
-    r, g, b = (rgb[:, :, i].astype(np.int64) for i in range(3))
-    y = ((77 * r + 150 * g + 29 * b) >> 8).astype(np.uint8)
-    cb, cr = cm.chroma_planes(rgb, sub)
-    return y, cb, cr
-
-
-_expected = {}
-
-
-def expected(oracle, planes, q, sub):
-    """The file by definition (computed once per distinct input)."""
-    y, cb, cr = planes
-    key = (y.tobytes(), cb.tobytes(), cr.tobytes(), y.shape, q, sub)
-    if key not in _expected:
-        h, w = y.shape
-        cq = cm.scaled_table(cm.CHROMA_Q, q)
-        parts = [cm.color_prefix(w, h, q, sub), cm.gray_scan(oracle, cm.write_bmp(np.stack([y, y, y], axis=2)), q)]
-        for comp, plane in ((2, cb), (3, cr)):
-            parts += [cm.sos(comp), cm.pack_scan(oracle, cm.plane_zigzag(oracle, plane, cq), True)]
-        _expected[key] = b"".join(parts) + b"\xff\xd9"
-    return _expected[key]
-
-
-def chroma_rows(cb, cr, layout):
-    """The stored chroma of one picture: [cb rows, cr rows] for PLANES, [pair rows] otherwise."""
-    if layout == PLANES:
-        return [cb, cr]
-    first, second = (cb, cr) if layout == CBCR else (cr, cb)
-    return [np.ascontiguousarray(np.stack([first, second], axis=2).reshape(cb.shape[0], -1))]
-
-
-class YccBatch:
-    """One YCbCr batch queued on `enc` (not finished).  Every plane is stored at the given stride behind `shift` bytes (y_shifts /
-    c_shifts: per picture); each output has 64 canary bytes behind `cap`."""
-
-    def __init__(self, jpegamd, enc, planes, dev, sub, layout, quality=0, y_stride=None, c_stride=None, y_shifts=None, c_shifts=None,
-                 cap=None):
-        h, w = planes[0][0].shape
-        cw, ch = chroma_dims(w, h, sub)
-        n = len(planes)
-        self.y_stride = y_stride or w
-        self.c_stride = c_stride or (cw if layout == PLANES else 2 * cw)
-        y_shifts, c_shifts = y_shifts or [0] * n, c_shifts or [0] * n
-        self.keep, imgs = [], []
-        for (y, cb, cr), ys, cs in zip(planes, y_shifts, c_shifts):
-            assert cb.shape == (ch, cw) and cr.shape == (ch, cw)
-            ty, py = upload(y, dev, self.y_stride, ys)
-            ups = [upload(rows, dev, self.c_stride, cs) for rows in chroma_rows(cb, cr, layout)]
-            self.keep.append((ty, ups))
-            imgs.append(jpegamd.Encoder.ycbcr_image(py, ups[0][1], ups[1][1] if layout == PLANES else 0, w, h, self.y_stride,
-                                                    self.c_stride, layout, quality))
-        self.cap = cap if cap is not None else jpegamd.max_jfif_bytes_color(w, h, sub)
-        self.outs = [torch.full((self.cap + 64,), 0xA5, dtype=torch.uint8, device=dev) for _ in planes]
-        self.sizes = torch.full((n,), -1, dtype=torch.int64, device=dev)
-        enc.encode_ycbcr_batch_async(imgs, sub, [o.data_ptr() for o in self.outs], self.cap,
-                                     [self.sizes.data_ptr() + 8 * i for i in range(n)], _stream())
-
-    def results(self):
-        """-> [(file bytes, canary intact)] picture by picture."""
-        res = []
-        for o, n in zip(self.outs, self.sizes.cpu().tolist()):
-            host = o.cpu().numpy()
-            res.append((bytes(host[:n]), bool(np.all(host[self.cap:] == 0xA5))))
-        return res
-
-
-def run(jpegamd, enc, planes, dev, sub, layout, **kw):
-    b = YccBatch(jpegamd, enc, planes, dev, sub, layout, **kw)
-    st = enc.finish()
-    res = b.results()
-    assert all(ok for _, ok in res)
-    assert st.jfif_bytes == len(res[-1][0])
-    return [f for f, _ in res]
 
 
 # ---- 1. sizes, subsamplings, layouts, qualities -----------------------------------------------------------------------------------
@@ -140,7 +33,7 @@ def test_every_layout_gives_the_file_by_definition(jpegamd, oracle, dev, w, h, s
     for q in (0, 10, 90):
         want = [expected(oracle, p, q, sub) for p in planes]
         for layout in LAYOUTS:
-            assert run(jpegamd, enc, planes, dev, sub, layout, quality=q) == want, (w, h, sub, q, layout)
+            assert run_ycc(jpegamd, enc, planes, dev, sub, layout, quality=q) == want, (w, h, sub, q, layout)
 
 
 # ---- 2. the identity with the RGB path ---------------------------------------------------------------------------------------------
@@ -153,9 +46,9 @@ def test_the_rgb_paths_own_planes_give_the_rgb_paths_file(jpegamd, dev, sub):
     enc.finish()
     want = [f for f, _ in b.results()]
     assert all(len(f) > 700 for f in want)
-    planes = [model_planes(rgb, sub) for rgb in rgbs]
+    planes = [cm.model_planes(rgb, sub) for rgb in rgbs]
     for layout in LAYOUTS:
-        assert run(jpegamd, enc, planes, dev, sub, layout) == want, (sub, layout)
+        assert run_ycc(jpegamd, enc, planes, dev, sub, layout) == want, (sub, layout)
 
 
 # ---- 3. extreme planes -------------------------------------------------------------------------------------------------------------
@@ -169,13 +62,13 @@ def test_extreme_planes_at_quality_100(jpegamd, oracle, dev):
     enc = jpegamd.Encoder(w, rows_for(len(planes), h))
     want = [expected(oracle, p, 100, sub) for p in planes]
     for layout in LAYOUTS:
-        assert run(jpegamd, enc, planes, dev, sub, layout, quality=100) == want, layout
+        assert run_ycc(jpegamd, enc, planes, dev, sub, layout, quality=100) == want, layout
     # the same at 4:2:0: the chroma planes cut to 132 x 12
     sub = S420
     planes = [(y, cb[:12, :132].copy(), cr[:12, :132].copy()) for y, cb, cr in planes]
     want = [expected(oracle, p, 100, sub) for p in planes]
     for layout in (PLANES, CRCB):
-        assert run(jpegamd, enc, planes, dev, sub, layout, quality=100) == want, layout
+        assert run_ycc(jpegamd, enc, planes, dev, sub, layout, quality=100) == want, layout
 
 
 # ---- 4. alignment and strides ------------------------------------------------------------------------------------------------------
@@ -190,7 +83,7 @@ def test_shifted_pointers_and_odd_strides(jpegamd, oracle, dev, shift):
         for layout in LAYOUTS:
             row = cw if layout == PLANES else 2 * cw
             aligned = -row % 4 + row                              # the next multiple of 4
-            assert run(jpegamd, enc, planes, dev, sub, layout, y_stride=w + 2, c_stride=aligned) == want     # the packed, aligned case
+            assert run_ycc(jpegamd, enc, planes, dev, sub, layout, y_stride=w + 2, c_stride=aligned) == want     # the packed, aligned case
             cases = [dict(y_shifts=[0, shift, 0], y_stride=w + 2, c_stride=aligned),                 # one y off a dword boundary
                      dict(c_shifts=[0, 0, shift], y_stride=w + 2, c_stride=aligned),                 # one cb / cr / pair plane
                      dict(y_shifts=[shift] * 3, c_shifts=[shift] * 3, y_stride=w + 2, c_stride=aligned),
@@ -198,7 +91,7 @@ def test_shifted_pointers_and_odd_strides(jpegamd, oracle, dev, shift):
                      dict(y_stride=w + 2, c_stride=aligned + shift),
                      dict(y_stride=w + 2, c_stride=aligned + 4096)]                                  # rows far apart
             for kw in cases:
-                assert run(jpegamd, enc, planes, dev, sub, layout, **kw) == want, (shift, sub, layout, kw)
+                assert run_ycc(jpegamd, enc, planes, dev, sub, layout, **kw) == want, (shift, sub, layout, kw)
 
 
 def test_strides_of_16_mib_take_the_gather(jpegamd, oracle, dev):
@@ -207,8 +100,8 @@ def test_strides_of_16_mib_take_the_gather(jpegamd, oracle, dev):
     for sub, layout in ((S420, CBCR), (S444, PLANES)):
         planes = [random_planes(w, h, sub, 77)]
         want = [expected(oracle, planes[0], 0, sub)]
-        assert run(jpegamd, enc, planes, dev, sub, layout, c_stride=WIDE_STRIDE) == want, (sub, layout)
-    assert run(jpegamd, enc, planes, dev, S444, PLANES, y_stride=WIDE_STRIDE) == want
+        assert run_ycc(jpegamd, enc, planes, dev, sub, layout, c_stride=WIDE_STRIDE) == want, (sub, layout)
+    assert run_ycc(jpegamd, enc, planes, dev, S444, PLANES, y_stride=WIDE_STRIDE) == want
 
 
 def test_strided_views(jpegamd, oracle, dev):
@@ -241,7 +134,7 @@ def test_counts(jpegamd, oracle, dev, count):
         planes = [random_planes(w, h, sub, 31 * count + k) for k in range(count)]
         want = [expected(oracle, p, 0, sub) for p in planes]
         assert len(set(want)) == count
-        assert run(jpegamd, enc, planes, dev, sub, layout) == want, (count, sub, layout)
+        assert run_ycc(jpegamd, enc, planes, dev, sub, layout) == want, (count, sub, layout)
 
 
 @pytest.mark.parametrize("pipeline", ["PIPELINE_PAIR", "PIPELINE_STITCH"])
@@ -258,7 +151,7 @@ def test_an_odd_chroma_group_starts_a_launch_on_a_cr_plane(jpegamd, oracle, dev,
     want = [expected(oracle, p, 0, S444) for p in planes]
     assert len(set(want)) == count                               # every picture distinct
     for layout in LAYOUTS:
-        assert run(jpegamd, enc, planes, dev, S444, layout) == want, layout
+        assert run_ycc(jpegamd, enc, planes, dev, S444, layout) == want, layout
 
 
 # ---- 6. pipelines ------------------------------------------------------------------------------------------------------------------
@@ -296,7 +189,7 @@ def test_one_picture_of_a_ycbcr_batch_one_byte_short(jpegamd, oracle, dev):
             assert all(ok for _, ok in res)                      # nothing behind any capacity
             assert int(b.sizes[1].item()) == 0
             assert [res[k][0] for k in (0, 2, 3)] == [exp[k] for k in (0, 2, 3)], (sub, layout)
-            assert run(jpegamd, enc, planes, dev, sub, layout, cap=cap + 1) == exp, (sub, layout)     # the exact capacity fits
+            assert run_ycc(jpegamd, enc, planes, dev, sub, layout, cap=cap + 1) == exp, (sub, layout)     # the exact capacity fits
 
 
 # ---- 8. one context, calls queued back to back ---------------------------------------------------------------------------------------
@@ -315,7 +208,7 @@ def test_one_context_interleaves_rgb_gray_and_ycbcr(jpegamd, oracle, dev):
         b = ColorBatch(jpegamd, enc, rgbs, dev, sub, quality=q)
         keep.append(b)
         for k, r in enumerate(rgbs):
-            checks.append(((lambda b=b, k=k: b.results()[k][0]), cm.color_file(oracle, cm.write_bmp(r), q, sub)))
+            checks.append(((lambda b=b, k=k: b.results()[k][0]), model(oracle, r, q, sub)))
 
     def gray(plane, q=0):
         hh, ww = plane.shape
@@ -324,7 +217,7 @@ def test_one_context_interleaves_rgb_gray_and_ycbcr(jpegamd, oracle, dev):
         out = torch.empty(cap, dtype=torch.uint8, device=dev)
         size = torch.zeros(1, dtype=torch.int64, device=dev)
         enc.encode_async(jpegamd.Encoder.image(ptr, ww, hh, ww, False, jpegamd.ORDER_GRAY, q), out.data_ptr(), cap, size.data_ptr(),
-                         True, _stream())
+                         True, stream())
         keep.append((t, out, size))
         bmp = cm.write_bmp(np.stack([plane] * 3, axis=2))
         checks.append(((lambda: bytes(out[:int(size.item())].cpu().numpy())), oracle.encode_bmp(bmp, quality=q) if q else oracle.encode_bmp(bmp)))

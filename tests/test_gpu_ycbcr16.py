@@ -1,40 +1,22 @@
 """10-bit YCbCr input (jpegamd_encode_ycbcr_samples_batch_async, encode_ycbcr16_batch) through the C-ABI into the HIP kernels, byte for
-byte against the file the header defines: the 8-bit full-range file -- the CPU models of tests/test_gpu_ycbcr.py and
+byte against the file the header defines: the 8-bit full-range file -- the CPU models of tests/color_model.py and
 tests/color_model_422.py -- of the planes narrowed with numpy by the tables of tests/depth_model.py.  Every test needs an MI355X."""
 from __future__ import annotations
-
-import ctypes as C
 
 import numpy as np
 import pytest
 
 import depth_model as dm
 import range_model as rm
-from test_gpu_color_batch import rows_for, upload
-from test_gpu_subsample422 import S422, want_ycc
-from test_gpu_ycbcr import CBCR, CRCB, LAYOUTS, PLANES, S420, S444, WIDE_STRIDE, YccBatch, chroma_rows, expected, smooth_planes
-from test_gpu_ycbcr_range import Ranged
+from gpu_support import (CBCR, CRCB, LAYOUTS, PLANES, S420, S422, S444, WIDE_STRIDE, YccBatch, chroma_dims, dev, intact_files,     # noqa: F401
+                         rows_for, run_ycc, smooth_planes)
+from gpu_support import ycc_file as expected
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
 RANGES = (dm.FULL, dm.LIMITED)
 ALIGNS = (dm.MSB, dm.LSB)
-
-
-@pytest.fixture(scope="module")
-def dev():
-    if not torch.cuda.is_available():
-        pytest.fail("gpu-marked test started without a GPU: the product path has no CPU fallback")
-    return torch.device("cuda:0")
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def chroma_dims(w, h, sub):
-    return (w if sub == S444 else (w + 1) // 2), ((h + 1) // 2 if sub == S420 else h)
 
 
 def noise_planes(w, h, sub, seed):
@@ -54,8 +36,7 @@ def words_of(values, align, seed):
 
 def want(oracle, planes16, q, sub, sample_range, align):
     """The file by definition: the 8-bit full-range file of the numpy-narrowed planes (computed once per distinct input)."""
-    planes8 = dm.narrow(planes16, sample_range, align)
-    return want_ycc(oracle, planes8, q) if sub == S422 else expected(oracle, planes8, q, sub)
+    return expected(oracle, dm.narrow(planes16, sample_range, align), q, sub)
 
 
 def fmt_of(jpegamd, align):
@@ -66,50 +47,13 @@ def rng_of(jpegamd, sample_range):
     return jpegamd.RANGE_LIMITED if sample_range == dm.LIMITED else jpegamd.RANGE_FULL
 
 
-def as_bytes(plane16):
-    """[H, W] 16-bit words -> [H, 2 W] bytes, little-endian, as they lie in memory."""
-    p = np.ascontiguousarray(plane16).astype("<u2")
-    return p.view(np.uint8).reshape(p.shape[0], -1)
-
-
-class Ycc16Batch:
-    """One batch of 16-bit planes queued on `enc` (not finished), after YccBatch: every plane is stored at the given stride (BYTES)
-    behind `shift` bytes (y_shifts / c_shifts: per picture); each output has 64 canary bytes behind `cap`."""
-
-    def __init__(self, jpegamd, enc, planes, dev, sub, layout, sample_range, align, quality=0, y_stride=None, c_stride=None, y_shifts=None,
-                 c_shifts=None, cap=None):
-        h, w = planes[0][0].shape
-        cw, ch = chroma_dims(w, h, sub)
-        n = len(planes)
-        self.y_stride = y_stride or 2 * w
-        self.c_stride = c_stride or (2 * cw if layout == PLANES else 4 * cw)
-        y_shifts, c_shifts = y_shifts or [0] * n, c_shifts or [0] * n
-        self.keep, imgs = [], []
-        for (y, cb, cr), ys, cs in zip(planes, y_shifts, c_shifts):
-            assert y.dtype == cb.dtype == cr.dtype == np.uint16 and cb.shape == (ch, cw) and cr.shape == (ch, cw)
-            ty, py = upload(as_bytes(y), dev, self.y_stride, ys)
-            # (chroma_rows interleaves sample by sample: words stay whole)
-            ups = [upload(as_bytes(rows), dev, self.c_stride, cs) for rows in chroma_rows(cb, cr, layout)]
-            self.keep.append((ty, ups))
-            imgs.append(jpegamd.Encoder.ycbcr_image(py, ups[0][1], ups[1][1] if layout == PLANES else 0, w, h, self.y_stride,
-                                                    self.c_stride, layout, quality))
-        self.cap = cap if cap is not None else jpegamd.max_jfif_bytes_color(w, h, sub)
-        self.outs = [torch.full((self.cap + 64,), 0xA5, dtype=torch.uint8, device=dev) for _ in planes]
-        self.sizes = torch.full((n,), -1, dtype=torch.int64, device=dev)
-        enc.encode_ycbcr_batch_async(imgs, sub, [o.data_ptr() for o in self.outs], self.cap,
-                                     [self.sizes.data_ptr() + 8 * i for i in range(n)], _stream(),
-                                     sample_range=rng_of(jpegamd, sample_range), sample_format=fmt_of(jpegamd, align))
-
-    results = YccBatch.results
+def samples16(jpegamd, sample_range, align):
+    """YccBatch's arguments for 16-bit planes of that range and alignment."""
+    return dict(sample_range=rng_of(jpegamd, sample_range), sample_format=fmt_of(jpegamd, align))
 
 
 def run(jpegamd, enc, planes, dev, sub, layout, sample_range, align, **kw):
-    b = Ycc16Batch(jpegamd, enc, planes, dev, sub, layout, sample_range, align, **kw)
-    st = enc.finish()
-    res = b.results()
-    assert all(ok for _, ok in res)
-    assert st.jfif_bytes == len(res[-1][0])
-    return [f for f, _ in res]
+    return run_ycc(jpegamd, enc, planes, dev, sub, layout, **samples16(jpegamd, sample_range, align), **kw)
 
 
 # ---- 1. every value, both loaders ---------------------------------------------------------------------------------------------------
@@ -209,34 +153,21 @@ def test_8_bit_and_16_bit_calls_queued_on_one_context(jpegamd, oracle, dev):
     """No finish between the calls: each gives its own file, and the 8-bit files -- through the old entries and through the new one
     with JPEGAMD_SAMPLES_8 -- are what they were."""
 
-    class Samples8(Ranged):
-        """8-bit planes through jpegamd_encode_ycbcr_samples_batch_async itself (Encoder never takes it for SAMPLES_8)."""
-
-        def encode_ycbcr_batch_async(self, imgs, subsampling, out_ptrs, out_cap, size_ptrs, stream=0):
-            n = len(imgs)
-            arr = (self.jpegamd.YCbCrImage * n)(*imgs)
-            outs = (C.c_void_p * n)(*[C.c_void_p(p) for p in out_ptrs])
-            sizes = (C.c_void_p * n)(*[C.c_void_p(p) for p in size_ptrs])
-            rc = self.jpegamd.lib.jpegamd_encode_ycbcr_samples_batch_async(self.enc._h, arr, n, int(subsampling), int(self.sample_range),
-                                                                           self.jpegamd.SAMPLES_8, outs, out_cap, sizes, C.c_void_p(stream))
-            assert rc == 0, rc
-
     w, h = 522, 38
     enc = jpegamd.Encoder(w, rows_for(2, h))
     for sub, layout in ((S420, CBCR), (S444, PLANES)):
         p16 = [noise_planes(w, h, sub, 400 + sub + k) for k in range(2)]
         p8 = [tuple((p >> 8).astype(np.uint8) for p in pic) for pic in p16]
-        a = Ycc16Batch(jpegamd, enc, p16, dev, sub, layout, dm.LIMITED, dm.MSB)
+        a = YccBatch(jpegamd, enc, p16, dev, sub, layout, **samples16(jpegamd, dm.LIMITED, dm.MSB))
         b = YccBatch(jpegamd, enc, p8, dev, sub, layout)
-        c = Ycc16Batch(jpegamd, enc, p16, dev, sub, layout, dm.FULL, dm.LSB)
-        d = YccBatch(jpegamd, Ranged(jpegamd, enc, jpegamd.RANGE_LIMITED), p8, dev, sub, layout)
-        e = Ycc16Batch(jpegamd, enc, p16, dev, sub, layout, dm.FULL, dm.MSB)
-        f = YccBatch(jpegamd, Samples8(jpegamd, enc, jpegamd.RANGE_FULL), p8, dev, sub, layout)
-        g = YccBatch(jpegamd, Samples8(jpegamd, enc, jpegamd.RANGE_LIMITED), p8, dev, sub, layout)
+        c = YccBatch(jpegamd, enc, p16, dev, sub, layout, **samples16(jpegamd, dm.FULL, dm.LSB))
+        d = YccBatch(jpegamd, enc, p8, dev, sub, layout, sample_range=jpegamd.RANGE_LIMITED)
+        e = YccBatch(jpegamd, enc, p16, dev, sub, layout, **samples16(jpegamd, dm.FULL, dm.MSB))
+        # 8-bit planes through jpegamd_encode_ycbcr_samples_batch_async itself (Encoder never takes it for SAMPLES_8)
+        f = YccBatch(jpegamd, enc, p8, dev, sub, layout, sample_range=jpegamd.RANGE_FULL, entry="samples")
+        g = YccBatch(jpegamd, enc, p8, dev, sub, layout, sample_range=jpegamd.RANGE_LIMITED, entry="samples")
         enc.finish()
-        res = [x.results() for x in (a, b, c, d, e, f, g)]
-        assert all(ok for r in res for _, ok in r)
-        fa, fb, fc, fd, fe, ff, fg = ([x for x, _ in r] for r in res)
+        fa, fb, fc, fd, fe, ff, fg = (intact_files(x) for x in (a, b, c, d, e, f, g))
         full8 = [expected(oracle, p, 0, sub) for p in p8]
         limited8 = [expected(oracle, rm.expand(p), 0, sub) for p in p8]
         assert fb == full8 and ff == full8 and fd == limited8 and fg == limited8, (sub, layout)
@@ -296,7 +227,7 @@ def test_one_picture_of_a_16_bit_batch_one_byte_short(jpegamd, oracle, dev):
         exp = [want(oracle, p, 0, sub, sample_range, align) for p in planes]
         cap = len(exp[1]) - 1                                    # one byte short for the noise picture alone
         assert cap > max(len(exp[k]) for k in (0, 2, 3))
-        b = Ycc16Batch(jpegamd, enc, planes, dev, sub, layout, sample_range, align, cap=cap)
+        b = YccBatch(jpegamd, enc, planes, dev, sub, layout, cap=cap, **samples16(jpegamd, sample_range, align))
         with pytest.raises(jpegamd.JpegAmdError) as err:
             enc.finish()
         assert err.value.code == -8

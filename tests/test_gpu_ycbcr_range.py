@@ -1,54 +1,24 @@
 """Limited-range YCbCr input (jpegamd_encode_ycbcr_range_batch_async, sample_range="limited") through the C-ABI into the HIP kernels,
-byte for byte against the file the header defines: the full-range file -- the CPU models of tests/test_gpu_ycbcr.py and
+byte for byte against the file the header defines: the full-range file -- the CPU models of tests/color_model.py and
 tests/color_model_422.py -- of the planes mapped with numpy by the tables of tests/range_model.py.  Every test needs an MI355X."""
 from __future__ import annotations
-
-import ctypes as C
 
 import numpy as np
 import pytest
 
 import range_model as rm
-from test_gpu_color_batch import rows_for
-from test_gpu_subsample422 import YCC_LAYOUTS, S422, Ycc422Batch, finish_batch, want_ycc
-from test_gpu_subsample422 import random_planes as random_planes_422
-from test_gpu_ycbcr import CBCR, LAYOUTS, PLANES, S420, S444, WIDE_STRIDE, YccBatch, chroma_dims, expected, random_planes, run, smooth_planes
+from gpu_support import (CBCR, LAYOUTS, PLANES, S420, S422, S444, WIDE_STRIDE, YUYV, YccBatch, chroma_dims, dev, intact_files,     # noqa: F401
+                         random_planes, rows_for, run_ycc, smooth_planes)
+from gpu_support import LAYOUTS_422 as YCC_LAYOUTS
+from gpu_support import ycc_file as expected
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
 
-@pytest.fixture(scope="module")
-def dev():
-    if not torch.cuda.is_available():
-        pytest.fail("gpu-marked test started without a GPU: the product path has no CPU fallback")
-    return torch.device("cuda:0")
-
-
-class Ranged:
-    """A context as YccBatch and Ycc422Batch use one, whose YCbCr calls go out with a sample range: through Encoder (which takes the
-    new entry for RANGE_LIMITED alone), or -- direct -- through jpegamd_encode_ycbcr_range_batch_async whatever the range."""
-
-    def __init__(self, jpegamd, enc, sample_range, direct=False):
-        self.jpegamd, self.enc, self.sample_range, self.direct = jpegamd, enc, sample_range, direct
-
-    def encode_ycbcr_batch_async(self, imgs, subsampling, out_ptrs, out_cap, size_ptrs, stream=0):
-        if not self.direct:
-            return self.enc.encode_ycbcr_batch_async(imgs, subsampling, out_ptrs, out_cap, size_ptrs, stream, sample_range=self.sample_range)
-        n = len(imgs)
-        arr = (self.jpegamd.YCbCrImage * n)(*imgs)
-        outs = (C.c_void_p * n)(*[C.c_void_p(p) for p in out_ptrs])
-        sizes = (C.c_void_p * n)(*[C.c_void_p(p) for p in size_ptrs])
-        rc = self.jpegamd.lib.jpegamd_encode_ycbcr_range_batch_async(self.enc._h, arr, n, int(subsampling), int(self.sample_range), outs,
-                                                                     out_cap, sizes, C.c_void_p(stream))
-        assert rc == 0, rc
-
-    def finish(self):
-        return self.enc.finish()
-
-
-def limited(jpegamd, enc):
-    return Ranged(jpegamd, enc, jpegamd.RANGE_LIMITED)
+def run(jpegamd, enc, planes, dev, sub, layout, **kw):
+    """A limited-range batch through Encoder, which takes jpegamd_encode_ycbcr_range_batch_async for RANGE_LIMITED alone."""
+    return run_ycc(jpegamd, enc, planes, dev, sub, layout, sample_range=jpegamd.RANGE_LIMITED, **kw)
 
 
 def want(oracle, planes, q, sub):
@@ -62,7 +32,7 @@ def test_every_input_value(jpegamd, oracle, dev):
     v = np.arange(256, dtype=np.uint8).reshape(16, 16)
     t = np.ascontiguousarray(v.T)
     planes = [(v, v, v), (t, t, t)]
-    enc = limited(jpegamd, jpegamd.Encoder(16, rows_for(2, 16)))
+    enc = jpegamd.Encoder(16, rows_for(2, 16))
     for q in (0, 100):
         files = [want(oracle, p, q, S444) for p in planes]
         assert files[0] != files[1] and files[0] != expected(oracle, planes[0], q, S444)      # (the map changes the file)
@@ -77,7 +47,7 @@ def test_sizes(jpegamd, oracle, dev, w, h, sub):
     """Uniform noise over 0 .. 255: about a quarter of the samples clamp.  (522, 38): a full 32-block interior chroma tile plus an
     edge tile at 4:2:0."""
     planes = [random_planes(w, h, sub, 2000 * w + 10 * h + sub + k) for k in range(2)]
-    enc = limited(jpegamd, jpegamd.Encoder(w, rows_for(2, h)))
+    enc = jpegamd.Encoder(w, rows_for(2, h))
     for q in (0, 90):
         files = [want(oracle, p, q, sub) for p in planes]
         for layout in LAYOUTS:
@@ -87,11 +57,11 @@ def test_sizes(jpegamd, oracle, dev, w, h, sub):
 # ---- 3. 4:2:2 and packed frames: the pair loader with the luma tables, and the quad loader ------------------------------------------
 @pytest.mark.parametrize("w,h", [(522, 38), (18, 9)])
 def test_422_and_packed(jpegamd, oracle, dev, w, h):
-    planes = [random_planes_422(w, h, 3000 * w + h + k) for k in range(2)]
-    files = [want_ycc(oracle, rm.expand(p), 0) for p in planes]
-    enc = limited(jpegamd, jpegamd.Encoder(w, rows_for(2, h)))
+    planes = [random_planes(w, h, S422, 3000 * w + h + k) for k in range(2)]
+    files = [expected(oracle, rm.expand(p), 0, S422) for p in planes]
+    enc = jpegamd.Encoder(w, rows_for(2, h))
     for layout in YCC_LAYOUTS:                                    # I422, NV16, NV61, YUYV, UYVY
-        assert finish_batch(enc, Ycc422Batch(jpegamd, enc, planes, dev, layout)) == files, (w, h, layout)
+        assert run(jpegamd, enc, planes, dev, S422, layout) == files, (w, h, layout)
 
 
 # ---- 4. loader paths ---------------------------------------------------------------------------------------------------------------
@@ -99,7 +69,7 @@ def test_loader_paths_give_one_file(jpegamd, oracle, dev):
     """Dword loaders, the clamped byte gather (a shifted plane, a stride off the grid) and 64-bit addresses (a stride of 2^24 and
     more) end in the same fragment registers: one map behind them, one file."""
     w, h = 522, 38
-    enc = limited(jpegamd, jpegamd.Encoder(w, rows_for(3, h)))
+    enc = jpegamd.Encoder(w, rows_for(3, h))
     for sub in (S420, S444):
         cw, _ = chroma_dims(w, h, sub)
         planes = [random_planes(w, h, sub, 17 + k) for k in range(3)]
@@ -114,7 +84,7 @@ def test_loader_paths_give_one_file(jpegamd, oracle, dev):
                        dict(y_stride=w + 2, c_stride=aligned + 3)):
                 assert run(jpegamd, enc, planes, dev, sub, layout, **kw) == files, (sub, layout, kw)
     w, h = 17, 9
-    enc = limited(jpegamd, jpegamd.Encoder(w, rows_for(1, h)))
+    enc = jpegamd.Encoder(w, rows_for(1, h))
     planes = [random_planes(w, h, S420, 78)]
     assert run(jpegamd, enc, planes, dev, S420, CBCR, c_stride=WIDE_STRIDE) == [want(oracle, planes[0], 0, S420)]
 
@@ -126,9 +96,8 @@ def test_pipelines_with_a_launch_that_starts_on_a_cr_plane(jpegamd, oracle, dev,
     pipe = getattr(jpegamd, pipeline)
     group, launches, _, _ = jpegamd._chroma_groups(w, rows_for(count, h), w, h, count, S444, pipe)
     assert group % 2 == 1 and launches > 1, (group, launches)
-    real = jpegamd.Encoder(w, rows_for(count, h))
-    real.set_pipeline(pipe)
-    enc = limited(jpegamd, real)
+    enc = jpegamd.Encoder(w, rows_for(count, h))
+    enc.set_pipeline(pipe)
     planes = [random_planes(w, h, S444, 190 + k) for k in range(count)]
     files = [want(oracle, p, 0, S444) for p in planes]
     assert len(set(files)) == count
@@ -143,25 +112,24 @@ def test_full_range_stays_full_range_between_limited_calls(jpegamd, oracle, dev)
     enc = jpegamd.Encoder(w, rows_for(2, h))
     for sub, layout in ((S420, CBCR), (S444, PLANES)):
         planes = [random_planes(w, h, sub, 300 + sub + k) for k in range(2)]
-        a = YccBatch(jpegamd, limited(jpegamd, enc), planes, dev, sub, layout)
-        b = YccBatch(jpegamd, Ranged(jpegamd, enc, jpegamd.RANGE_FULL, direct=True), planes, dev, sub, layout)
+        a = YccBatch(jpegamd, enc, planes, dev, sub, layout, sample_range=jpegamd.RANGE_LIMITED)
+        b = YccBatch(jpegamd, enc, planes, dev, sub, layout, sample_range=jpegamd.RANGE_FULL, entry="range")
         c = YccBatch(jpegamd, enc, planes, dev, sub, layout)
         enc.finish()
-        ra, rb, rc = a.results(), b.results(), c.results()
-        assert all(ok for _, ok in ra + rb + rc)
+        fa, fb, fc = intact_files(a), intact_files(b), intact_files(c)
         full = [expected(oracle, p, 0, sub) for p in planes]
-        assert [f for f, _ in rb] == full and [f for f, _ in rc] == full, (sub, layout)
-        assert [f for f, _ in ra] == [want(oracle, p, 0, sub) for p in planes], (sub, layout)
-        assert [f for f, _ in ra] != full
+        assert fb == full and fc == full, (sub, layout)
+        assert fa == [want(oracle, p, 0, sub) for p in planes], (sub, layout)
+        assert fa != full
     # the 4:2:2 entry the same way, from a packed plane
-    planes = [random_planes_422(w, h, 310 + k) for k in range(2)]
-    a = Ycc422Batch(jpegamd, limited(jpegamd, enc), planes, dev, YCC_LAYOUTS[3])
-    b = Ycc422Batch(jpegamd, Ranged(jpegamd, enc, jpegamd.RANGE_FULL, direct=True), planes, dev, YCC_LAYOUTS[3])
-    c = Ycc422Batch(jpegamd, enc, planes, dev, YCC_LAYOUTS[3])
+    planes = [random_planes(w, h, S422, 310 + k) for k in range(2)]
+    a = YccBatch(jpegamd, enc, planes, dev, S422, YUYV, sample_range=jpegamd.RANGE_LIMITED)
+    b = YccBatch(jpegamd, enc, planes, dev, S422, YUYV, sample_range=jpegamd.RANGE_FULL, entry="range")
+    c = YccBatch(jpegamd, enc, planes, dev, S422, YUYV)
     enc.finish()
-    full = [want_ycc(oracle, p, 0) for p in planes]
+    full = [expected(oracle, p, 0, S422) for p in planes]
     assert [f for f, _ in b.results()] == full and [f for f, _ in c.results()] == full
-    assert [f for f, _ in a.results()] == [want_ycc(oracle, rm.expand(p), 0) for p in planes]
+    assert [f for f, _ in a.results()] == [expected(oracle, rm.expand(p), 0, S422) for p in planes]
 
 
 # ---- 7. planes that are limited range already: the tensor entries ---------------------------------------------------------------------
@@ -190,23 +158,22 @@ def test_tensor_entries_on_nominal_range_planes(jpegamd, oracle, dev):
     assert jpegamd.encode_yuyv_batch(swapped, order="uyvy", sample_range="limited") == got
     assert jpegamd.encode_yuyv_batch(swapped_mapped, order="uyvy") == got
     fh = frames[0].cpu().numpy().reshape(h, w // 2, 4)
-    assert got[0] == want_ycc(oracle, rm.expand((np.ascontiguousarray(frames[0, :, :, 0].cpu().numpy()), np.ascontiguousarray(fh[:, :, 1]),
-                                                 np.ascontiguousarray(fh[:, :, 3]))), 0)
+    assert got[0] == expected(oracle, rm.expand((np.ascontiguousarray(frames[0, :, :, 0].cpu().numpy()), np.ascontiguousarray(fh[:, :, 1]),
+                                                 np.ascontiguousarray(fh[:, :, 3]))), 0, S422)
 
 
 # ---- 8. capacity -------------------------------------------------------------------------------------------------------------------
 def test_one_picture_of_a_limited_batch_one_byte_short(jpegamd, oracle, dev):
     w, h = 160, 96
-    real = jpegamd.Encoder(w, rows_for(4, h))
-    enc = limited(jpegamd, real)
+    enc = jpegamd.Encoder(w, rows_for(4, h))
     for sub, layout in ((S420, CBCR), (S444, PLANES)):
         planes = [smooth_planes(w, h, sub, 7), random_planes(w, h, sub, 9), smooth_planes(w, h, sub, 8), smooth_planes(w, h, sub, 6)]
         exp = [want(oracle, p, 0, sub) for p in planes]
         cap = len(exp[1]) - 1                                    # one byte short for the noise picture alone
         assert cap > max(len(exp[k]) for k in (0, 2, 3))
-        b = YccBatch(jpegamd, enc, planes, dev, sub, layout, cap=cap)
+        b = YccBatch(jpegamd, enc, planes, dev, sub, layout, cap=cap, sample_range=jpegamd.RANGE_LIMITED)
         with pytest.raises(jpegamd.JpegAmdError) as err:
-            real.finish()
+            enc.finish()
         assert err.value.code == -8
         res = b.results()
         assert all(ok for _, ok in res)                          # the canaries: nothing behind any capacity
