@@ -205,7 +205,7 @@ int32_t jpegamd_encode_planar_batch_async(JpegAmdEncoder *enc, const JpegAmdPlan
 /* ---- YCbCr pictures: samples that already ARE Y, Cb and Cr (a video decoder's NV12 / I420 frame, a resizer's output) ----------------
  * The planes are coded as they are given: the samples are taken as JFIF full-range values (Y 0..255, Cb / Cr centred on 128), and
  * NO range or matrix conversion, no subsampling and no filtering is done -- limited-range (16..235) material goes through
- * jpegamd_encode_ycbcr_range_batch_async below, BT.709 material must be converted by the caller.  The Y plane is width x height; the chroma planes are cw x ch: width x height at JPEGAMD_SUBSAMPLE_444,
+ * jpegamd_encode_ycbcr_range_batch_async below, BT.709 material through jpegamd_encode_ycbcr_matrix_batch_async.  The Y plane is width x height; the chroma planes are cw x ch: width x height at JPEGAMD_SUBSAMPLE_444,
  * ceil(width / 2) x ceil(height / 2) at JPEGAMD_SUBSAMPLE_420, ceil(width / 2) x height at JPEGAMD_SUBSAMPLE_422 (I422; NV16 / NV61
  * as byte pairs).  Odd sizes are allowed.
  * 4:2:2 also comes packed, as capture hardware delivers it: ONE plane of 4-byte groups, two pixels each, that holds all three
@@ -247,8 +247,8 @@ int32_t jpegamd_encode_ycbcr_batch_async(JpegAmdEncoder *enc, const JpegAmdYCbCr
  *     C' = (255 * (clamp(C, 16, 240) - 16) + 112) / 224        0..255   (Cb and Cr alike)
  * so Y 16 -> 0 and 235 -> 255, Cb / Cr 16 -> 0, 128 -> 128 (neutral chroma stays neutral) and 240 -> 255; both maps are monotone and
  * everything outside the nominal range clamps.  The file is byte for byte the file jpegamd_encode_ycbcr_batch_async writes for the
- * mapped samples.  Only the RANGE is expanded: the matrix stays BT.601 as JFIF defines it, and BT.709 -> BT.601 matrix conversion is
- * still the caller's.  With JPEGAMD_RANGE_FULL this IS jpegamd_encode_ycbcr_batch_async: same code path, same files.  Layouts,
+ * mapped samples.  Only the RANGE is expanded: the matrix stays BT.601 as JFIF defines it (BT.709 -> BT.601 matrix conversion is
+ * jpegamd_encode_ycbcr_matrix_batch_async's).  With JPEGAMD_RANGE_FULL this IS jpegamd_encode_ycbcr_batch_async: same code path, same files.  Layouts,
  * subsamplings, context sizing, capacity behaviour, status, statistics and profiling are those of that entry, and so are its argument
  * checks; any other sample_range is refused with JPEGAMD_ERR_ARG, like them before the context is read. */
 #define JPEGAMD_RANGE_FULL    0   /* samples are JFIF full range: coded as given */
@@ -283,6 +283,35 @@ int32_t jpegamd_encode_ycbcr_range_batch_async(JpegAmdEncoder *enc, const JpegAm
 int32_t jpegamd_encode_ycbcr_samples_batch_async(JpegAmdEncoder *enc, const JpegAmdYCbCrImage *imgs, int32_t count, int32_t subsampling,
                                                  int32_t sample_range, int32_t sample_format, void *const *outs_dev, uint64_t out_capacity,
                                                  void *const *out_sizes_dev, void *stream);
+
+/* The same entry for samples of either matrix.  JFIF fixes the matrix at BT.601; every HD and UHD stream a decoder delivers is BT.709,
+ * and coded as given its colours come out shifted.  With JPEGAMD_MATRIX_BT709 ONE pass over the batch (k_ycbcr_matrix_batch, one launch
+ * for every picture) reads each picture once, in whatever layout, depth and range it has, and writes 8-bit full-range BT.601 Y, Cb and
+ * Cr planes into context scratch (the plane scratch of jpegamd_encode_color_batch_async, and one Y plane more per picture); the
+ * full-range plane launches then code those.  Let Y, Cb, Cr be the 8-bit full-range samples the entries above would code: the stored
+ * bytes, or the bytes after the JPEGAMD_RANGE_LIMITED map, or after the JPEGAMD_SAMPLES_10_* maps for either alignment and range.
+ * Those maps come first and stay as they are; the matrix works on their 8-bit results (so 10-bit BT.709 input is rounded twice, once
+ * by its map and once here).  With cb = Cb - 128, cr = Cr - 128 and >> an arithmetic (floor) shift of a signed 32-bit value:
+ *     Y'  = clamp(Y   + ((  1664 * cb +  3213 * cr + 8192) >> 14), 0, 255)
+ *     Cb' = clamp(128 + (( 16218 * cb -  1813 * cr + 8192) >> 14), 0, 255)
+ *     Cr' = clamp(128 + (( -1187 * cb + 16112 * cr + 8192) >> 14), 0, 255)
+ * Luma sample (x, y) takes the chroma sample at the same indices as the file's subsampling -- (x, y) at 4:4:4, (x >> 1, y) at 4:2:2,
+ * (x >> 1, y >> 1) at 4:2:0 -- without interpolation.  The six integers are round(c * 2^14) of the real matrix that composes BT.709
+ * YCbCr -> R'G'B' (Kr = 0.2126, Kb = 0.0722) with R'G'B' -> BT.601 YCbCr (Kr = 0.299, Kb = 0.114):
+ *      0.101579   0.196076
+ *      0.989854  -0.110653
+ *     -0.072453   0.983398
+ * Each of the three terms is within 0.51 of the real-valued one over all 65 536 (cb, cr); Cb = Cr = 128 is the identity, so grey stays
+ * grey.  The file is byte for byte the file jpegamd_encode_ycbcr_batch_async writes for the planes (Y', Cb', Cr').
+ * With JPEGAMD_MATRIX_BT601 this IS jpegamd_encode_ycbcr_samples_batch_async: no pass, no scratch, the same launches, the same files.
+ * Layouts, subsamplings, formats, ranges, context sizing, capacity behaviour, status, statistics and profiling are those of that entry
+ * (in a profiled call the pass opens ns_total), and so are its argument checks; any other matrix is refused with JPEGAMD_ERR_ARG, like
+ * them before the context is read. */
+#define JPEGAMD_MATRIX_BT601 0   /* the samples are BT.601 YCbCr, as JFIF defines it: coded as given */
+#define JPEGAMD_MATRIX_BT709 1   /* the samples are BT.709 YCbCr: converted to BT.601 by the map above, in one pass in front of the tile kernel */
+int32_t jpegamd_encode_ycbcr_matrix_batch_async(JpegAmdEncoder *enc, const JpegAmdYCbCrImage *imgs, int32_t count, int32_t subsampling,
+                                                int32_t sample_range, int32_t sample_format, int32_t matrix, void *const *outs_dev,
+                                                uint64_t out_capacity, void *const *out_sizes_dev, void *stream);
 
 /* Which kernels follow k_tile_encode for whole pictures (no reference counterpart: a tuning knob, results are byte-identical).
  *   PAIR    k_segment_merge + k_finalize: the tiles' bit strings joined per segment, then stitched behind a kernel boundary;

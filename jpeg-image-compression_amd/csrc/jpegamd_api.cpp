@@ -1036,6 +1036,7 @@ static int32_t color_batch_alloc(JpegAmdEncoder *e, size_t planes, size_t scans)
 struct YccSource {
     int32_t layout, c_stride, format, range;
     const uint8_t *cb[kMaxBatch], *cr[kMaxBatch];
+    int32_t matrix;                     // JPEGAMD_MATRIX_*: BT709 goes through k_ycbcr_matrix_batch, and the launches read ITS planes
 };
 
 // The kinds of YCbCr input that are taken: a known layout, format and range; a packed layout in one byte per sample (Y210: not taken).
@@ -1082,12 +1083,50 @@ extern "C" int32_t jpegamd_debug_ycbcr_sources(int32_t chroma_layout, int32_t sa
     return JPEGAMD_OK;
 }
 
+// What a BT.709 batch keeps in color.bplanes: the 2 x count chroma planes where the RGB route has them, then count Y planes.
+struct MatrixScratch {
+    int ypitch;
+    size_t yplane_bytes, y_off, total;
+};
+static MatrixScratch matrix_scratch(int w, int h, int count, size_t plane_bytes) {
+    MatrixScratch m;
+    m.ypitch = (w + 3) / 4 * 4;
+    m.yplane_bytes = round_up((size_t)m.ypitch * (size_t)h, 256);
+    m.y_off = 2 * (size_t)count * plane_bytes;
+    m.total = m.y_off + (size_t)count * m.yplane_bytes + 256;
+    return m;
+}
+
+// k_ycbcr_matrix_batch over the caller's planes (g0 / px: the Y planes, ycc: the chroma) into color.bplanes, which holds m.total bytes.
+static int launch_matrix_pass(JpegAmdEncoder *e, const JpegAmdImage &g0, const PlaneSet &px, const YccSource &ycc, int32_t count,
+                              int32_t subsampling, int cw, int ch, int pitch, size_t plane_bytes, const MatrixScratch &m, hipStream_t stream,
+                              void *const *ev) {
+    YccMatrixBatchArgs ma;
+    std::memset(&ma, 0, sizeof(ma));
+    for (int i = 0; i < count; ++i) { ma.y[i] = px.p[0][i]; ma.cb[i] = ycc.cb[i]; ma.cr[i] = ycc.cr[i]; }
+    ma.batch = count;
+    ma.width = g0.width; ma.height = g0.height; ma.y_stride = g0.row_stride; ma.c_stride = ycc.c_stride;
+    ma.mode = chroma_mode(subsampling);
+    ma.walk = is_packed422(ycc.layout) ? kMatrixWalkPacked : (ycc.layout == JPEGAMD_CHROMA_PLANES ? kMatrixWalkPlanes : kMatrixWalkPairs);
+    ma.sample_bytes = ycc.format == JPEGAMD_SAMPLES_8 ? 1 : 2;
+    ma.first = (ycc.layout == JPEGAMD_CHROMA_CRCB || ycc.layout == JPEGAMD_CHROMA_UYVY) ? 1 : 0;
+    ma.shift = (int32_t)depth_shift(ycc.format);
+    ma.limited = ycc.range == JPEGAMD_RANGE_LIMITED ? 1 : 0;
+    ma.cw = cw; ma.ch = ch; ma.pitch = pitch; ma.ypitch = m.ypitch;
+    ma.plane_bytes = plane_bytes; ma.yplane_bytes = m.yplane_bytes;
+    ma.planes = e->color.bplanes; ma.yplanes = e->color.bplanes + m.y_off;
+    return launch_ycbcr_matrix_batch(ma, stream, ev);
+}
+
 // The colour files of a batch whose arguments are known to be good: g0 describes every picture, ps holds their pixels.
 // `ycc` (a YCbCr batch): g0 / px are the Y planes as a GRAY picture, the chroma scans read the caller's planes -- no
-// k_chroma_planes_batch launch, no plane scratch.
+// k_chroma_planes_batch launch, no plane scratch.  A BT.709 YCbCr batch (ycc->matrix) is the RGB route with another kernel in front:
+// k_ycbcr_matrix_batch writes BT.601 Y, Cb and Cr planes into the plane scratch, and every launch reads those as full-range planes.
 static int32_t color_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, const PlaneSet &px, int32_t count, int32_t subsampling,
                            void *const *outs_dev, uint64_t out_capacity, uint64_t *const *out_sizes_dev, void *stream_,
-                           const YccSource *ycc = nullptr) {
+                           const YccSource *ycc_in = nullptr) {
+    const bool mx = ycc_in && ycc_in->matrix == JPEGAMD_MATRIX_BT709;
+    const YccSource *const ycc = mx ? nullptr : ycc_in;               // what the launches read: the caller's planes, or the scratch
     // Y: the grayscale batch's launch plan
     ImageDesc iy;
     bool stitch_y;
@@ -1103,10 +1142,20 @@ static int32_t color_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, const Plan
     if (!chroma_plan(lim, e->pipeline, cw, ch, planes, &plan)) return JPEGAMD_ERR_TOO_LARGE;
     const size_t plane_bytes = round_up((size_t)pitch * (size_t)ch, 256);
     const size_t slot_bytes = round_up(scan_bound(blocks_of(cw, ch)) + 64, 256);      // (k_append_scans_batch reads 16 bytes at a time)
+    const MatrixScratch ms = matrix_scratch(g0.width, g0.height, count, plane_bytes);
     rc = color_alloc_consts(e);
     if (rc) return rc;
-    rc = color_batch_alloc(e, ycc ? 0 : planes * plane_bytes + 256, planes * slot_bytes);
+    rc = color_batch_alloc(e, mx ? ms.total : (ycc ? 0 : planes * plane_bytes + 256), planes * slot_bytes);
     if (rc) return rc;
+    // a BT.709 batch: the Y launch is a GRAY batch over the scratch Y planes
+    JpegAmdImage gy = g0;
+    PlaneSet py = px;
+    if (mx) {
+        gy.pixels = e->color.bplanes + ms.y_off; gy.row_stride = ms.ypitch;
+        for (int i = 0; i < count; ++i) py.p[0][i] = e->color.bplanes + ms.y_off + (size_t)i * ms.yplane_bytes;
+        rc = plan_batch(e, gy, py, count, &iy, &stitch_y);
+        if (rc) return rc;
+    }
     rc = prepare_constants(e, &g0, false);
     if (rc) return rc;
     rc = prepare_color_constants(e, &g0, subsampling);
@@ -1124,7 +1173,11 @@ static int32_t color_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, const Plan
     HIP_TRY(hipMemsetAsync(c.bmeta, 0, kBatchMetaStats + kBatchMetaPic, stream));
 
     hipEvent_t *const ev_y = ycc ? cev : nullptr;     // a YCbCr batch begins with its Y launch: that kernel's begin stamp opens ns_total
-    if (!ycc) {
+    hipEvent_t ev_planes[2] = {cev ? cev[0] : nullptr, nullptr};      // (a plane pass comes first: ITS begin stamp opens ns_total)
+    if (mx) {
+        if (launch_matrix_pass(e, g0, px, *ycc_in, count, subsampling, cw, ch, pitch, plane_bytes, ms, stream,
+                               cev ? (void *const *)ev_planes : nullptr)) return JPEGAMD_ERR_HIP;
+    } else if (!ycc) {
         ChromaPlanesBatchArgs pa;
         std::memset(&pa, 0, sizeof(pa));
         for (int i = 0; i < count; ++i) { pa.pixels[i] = px.p[0][i]; pa.pixels_g[i] = px.p[1][i]; pa.pixels_b[i] = px.p[2][i]; }
@@ -1135,7 +1188,6 @@ static int32_t color_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, const Plan
         pa.mode = chroma_mode(subsampling);
         pa.cw = cw; pa.ch = ch; pa.pitch = pitch;
         pa.plane_bytes = plane_bytes; pa.planes = c.bplanes;
-        hipEvent_t ev_planes[2] = {cev ? cev[0] : nullptr, nullptr};
         if (launch_chroma_planes_batch(pa, stream, cev ? (void *const *)ev_planes : nullptr)) return JPEGAMD_ERR_HIP;
     }
 
@@ -1145,12 +1197,12 @@ static int32_t color_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, const Plan
         for (int i = 0; i < count; ++i) sizes[i] = y_size + i;
         const ScanTarget ty = {c.hdr, c.hdr_len, 0, &lstats[0], false};
         PictureStatsArgs ps = {e->tile_head, e->huff, iy.num_tiles, count, 0, 0, pic};
-        TileSource ysrc = src_of(&g0);
+        TileSource ysrc = src_of(&gy);
         if (ycc) {
             const SourceChoice y = ycbcr_y_source(ycc->layout, ycc->format, ycc->range);
             ysrc = y.src; iy.select = y.select;
         }
-        if (code_tiles(e, iy, ysrc, &px, &ps, outs_dev, out_capacity, sizes, 1, &ty, stitch_y, stream, ev_y, nullptr)) return JPEGAMD_ERR_HIP;
+        if (code_tiles(e, iy, ysrc, &py, &ps, outs_dev, out_capacity, sizes, 1, &ty, stitch_y, stream, ev_y, nullptr)) return JPEGAMD_ERR_HIP;
     }
     // Cb, Cr: plane j (picture j / 2) bare into slot j; its size into c_size[j]
     JpegAmdImage pimg = g0;
@@ -1258,15 +1310,14 @@ extern "C" int32_t jpegamd_encode_planar_batch_async(JpegAmdEncoder *e, const Jp
     return color_batch(e, g0, ps, count, subsampling, outs_dev, out_capacity, sizes, stream_);
 }
 
-// `count` YCbCr pictures: the argument checks, then the colour batch with the Y planes as its one-sample source and the caller's chroma.
-// sample_range: JPEGAMD_RANGE_FULL -- the samples are coded as given -- or JPEGAMD_RANGE_LIMITED: every launch expands them on read.
-// sample_format: JPEGAMD_SAMPLES_8, or 10-bit samples in 16-bit words (MSB- or LSB-aligned), which every launch narrows on read.
-extern "C" int32_t jpegamd_encode_ycbcr_samples_batch_async(JpegAmdEncoder *e, const JpegAmdYCbCrImage *imgs, int32_t count, int32_t subsampling,
-                                                            int32_t sample_range, int32_t sample_format, void *const *outs_dev,
-                                                            uint64_t out_capacity, void *const *out_sizes_dev, void *stream_) {
-    // the arguments first: nothing of the context is read before they are known to be good
-    if (!e || !imgs || !outs_dev || !out_sizes_dev || count < 1 || count > kMaxBatch) return JPEGAMD_ERR_ARG;
+// The arguments of a YCbCr batch, checked before anything of the context is read (outs_dev / out_sizes_dev: null for an entry that
+// writes no files) -> the Y planes as a GRAY picture and the caller's chroma.
+static int32_t ycbcr_args(const JpegAmdEncoder *e, const JpegAmdYCbCrImage *imgs, int32_t count, int32_t subsampling, int32_t sample_range,
+                          int32_t sample_format, int32_t matrix, void *const *outs_dev, void *const *out_sizes_dev, bool files,
+                          JpegAmdImage *g0, PlaneSet *ps, YccSource *ycc, uint64_t **sizes) {
+    if (!e || !imgs || (files && (!outs_dev || !out_sizes_dev)) || count < 1 || count > kMaxBatch) return JPEGAMD_ERR_ARG;
     if (!sub_valid(subsampling)) return JPEGAMD_ERR_ARG;
+    if (matrix != JPEGAMD_MATRIX_BT601 && matrix != JPEGAMD_MATRIX_BT709) return JPEGAMD_ERR_ARG;
     const int64_t bps = sample_format == JPEGAMD_SAMPLES_8 ? 1 : 2;   // bytes per sample
     const JpegAmdYCbCrImage &p0 = imgs[0];
     const bool packed = is_packed422(p0.chroma_layout);               // y is the packed plane; cb, cr and c_stride are not looked at
@@ -1277,27 +1328,93 @@ extern "C" int32_t jpegamd_encode_ycbcr_samples_batch_async(JpegAmdEncoder *e, c
     int cw, ch;
     chroma_dims(p0.width, p0.height, subsampling, &cw, &ch);
     if (packed ? p0.y_stride < 4 * cw : (p0.y_stride < bps * p0.width || p0.c_stride < bps * (pair ? 2 * cw : cw))) return JPEGAMD_ERR_ARG;
-    PlaneSet ps = {};
-    YccSource ycc = {};
-    ycc.layout = p0.chroma_layout; ycc.c_stride = packed ? p0.y_stride : p0.c_stride;
-    ycc.format = sample_format; ycc.range = sample_range;
-    uint64_t *sizes[kMaxBatch];
+    *ps = PlaneSet{};
+    *ycc = YccSource{};
+    ycc->layout = p0.chroma_layout; ycc->c_stride = packed ? p0.y_stride : p0.c_stride;
+    ycc->format = sample_format; ycc->range = sample_range; ycc->matrix = matrix;
     for (int i = 0; i < count; ++i) {
         const JpegAmdYCbCrImage &g = imgs[i];
-        if (!outs_dev[i] || !out_sizes_dev[i] || !g.y || (!packed && (!g.cb || (!pair && !g.cr)))) return JPEGAMD_ERR_ARG;
+        if ((files && (!outs_dev[i] || !out_sizes_dev[i])) || !g.y || (!packed && (!g.cb || (!pair && !g.cr)))) return JPEGAMD_ERR_ARG;
         if (g.width != p0.width || g.height != p0.height || g.y_stride != p0.y_stride || (!packed && g.c_stride != p0.c_stride) ||
             g.chroma_layout != p0.chroma_layout || g.quality != p0.quality)
             return JPEGAMD_ERR_ARG;
-        ps.p[0][i] = (const uint8_t *)g.y;
-        ycc.cb[i] = (const uint8_t *)(packed ? g.y : g.cb);
-        ycc.cr[i] = (pair || packed) ? nullptr : (const uint8_t *)g.cr;
-        sizes[i] = (uint64_t *)out_sizes_dev[i];
+        ps->p[0][i] = (const uint8_t *)g.y;
+        ycc->cb[i] = (const uint8_t *)(packed ? g.y : g.cb);
+        ycc->cr[i] = (pair || packed) ? nullptr : (const uint8_t *)g.cr;
+        if (files) sizes[i] = (uint64_t *)out_sizes_dev[i];
     }
+    g0->pixels = p0.y;
+    g0->width = p0.width; g0->height = p0.height; g0->row_stride = p0.y_stride; g0->bottom_up = 0;
+    g0->channel_order = JPEGAMD_ORDER_GRAY; g0->quality = p0.quality;
+    return JPEGAMD_OK;
+}
+
+// `count` YCbCr pictures: the argument checks, then the colour batch with the Y planes as its one-sample source and the caller's chroma.
+// sample_range: JPEGAMD_RANGE_FULL -- the samples are coded as given -- or JPEGAMD_RANGE_LIMITED: every launch expands them on read.
+// sample_format: JPEGAMD_SAMPLES_8, or 10-bit samples in 16-bit words (MSB- or LSB-aligned), which every launch narrows on read.
+// matrix: JPEGAMD_MATRIX_BT601 -- exactly that -- or JPEGAMD_MATRIX_BT709: one pass (k_ycbcr_matrix_batch) applies the same maps and
+// the matrix and leaves full-range BT.601 planes in context scratch, which the launches then read.
+extern "C" int32_t jpegamd_encode_ycbcr_matrix_batch_async(JpegAmdEncoder *e, const JpegAmdYCbCrImage *imgs, int32_t count, int32_t subsampling,
+                                                           int32_t sample_range, int32_t sample_format, int32_t matrix, void *const *outs_dev,
+                                                           uint64_t out_capacity, void *const *out_sizes_dev, void *stream_) {
+    // the arguments first: nothing of the context is read before they are known to be good
     JpegAmdImage g0;
-    g0.pixels = p0.y;
-    g0.width = p0.width; g0.height = p0.height; g0.row_stride = p0.y_stride; g0.bottom_up = 0;
-    g0.channel_order = JPEGAMD_ORDER_GRAY; g0.quality = p0.quality;
+    PlaneSet ps;
+    YccSource ycc;
+    uint64_t *sizes[kMaxBatch];
+    if (int32_t rc = ycbcr_args(e, imgs, count, subsampling, sample_range, sample_format, matrix, outs_dev, out_sizes_dev, true, &g0, &ps, &ycc, sizes))
+        return rc;
     return color_batch(e, g0, ps, count, subsampling, outs_dev, out_capacity, sizes, stream_, &ycc);
+}
+
+// Host-only (tests): the six integers of a matrix and the shift, as k_ycbcr_matrix_batch applies them (BT601: the identity, which no
+// kernel applies).  Not part of the public header.
+extern "C" int32_t jpegamd_debug_matrix_coeffs(int32_t matrix, int32_t *out /*[7]*/) {
+    if (!out || (matrix != JPEGAMD_MATRIX_BT601 && matrix != JPEGAMD_MATRIX_BT709)) return JPEGAMD_ERR_ARG;
+    for (int k = 0; k < 6; ++k) out[k] = matrix == JPEGAMD_MATRIX_BT709 ? kMatrix709[k] : kMatrix601[k];
+    out[6] = kMatrixShift;
+    return JPEGAMD_OK;
+}
+
+// Tests: the pass of a BT.709 batch alone, into the same scratch, and its planes copied tightly packed into the caller's DEVICE buffers
+// (y_out: count x height x width bytes; cb_out, cr_out: count x ch x cw).  Returns when the copies are done.  Only JPEGAMD_MATRIX_BT709
+// has a pass.  Not part of the public header.
+extern "C" int32_t jpegamd_debug_ycbcr_matrix_planes(JpegAmdEncoder *e, const JpegAmdYCbCrImage *imgs, int32_t count, int32_t subsampling,
+                                                     int32_t sample_range, int32_t sample_format, int32_t matrix, void *y_out, void *cb_out,
+                                                     void *cr_out, void *stream_) {
+    JpegAmdImage g0;
+    PlaneSet ps;
+    YccSource ycc;
+    if (!y_out || !cb_out || !cr_out) return JPEGAMD_ERR_ARG;
+    if (int32_t rc = ycbcr_args(e, imgs, count, subsampling, sample_range, sample_format, matrix, nullptr, nullptr, false, &g0, &ps, &ycc, nullptr))
+        return rc;
+    if (matrix != JPEGAMD_MATRIX_BT709) return JPEGAMD_ERR_ARG;
+    int cw, ch;
+    chroma_dims(g0.width, g0.height, subsampling, &cw, &ch);
+    const int pitch = (cw + 3) / 4 * 4;
+    const size_t plane_bytes = round_up((size_t)pitch * (size_t)ch, 256);
+    const MatrixScratch ms = matrix_scratch(g0.width, g0.height, count, plane_bytes);
+    if (int32_t rc = color_batch_alloc(e, ms.total, 0)) return rc;
+    hipStream_t stream = (hipStream_t)stream_;
+    if (launch_matrix_pass(e, g0, ps, ycc, count, subsampling, cw, ch, pitch, plane_bytes, ms, stream, nullptr)) return JPEGAMD_ERR_HIP;
+    const uint8_t *base = e->color.bplanes;
+    for (int i = 0; i < count; ++i) {
+        HIP_TRY(hipMemcpy2DAsync((uint8_t *)y_out + (size_t)i * g0.width * g0.height, (size_t)g0.width, base + ms.y_off + (size_t)i * ms.yplane_bytes,
+                                 (size_t)ms.ypitch, (size_t)g0.width, (size_t)g0.height, hipMemcpyDeviceToDevice, stream));
+        for (int k = 0; k < 2; ++k)
+            HIP_TRY(hipMemcpy2DAsync((uint8_t *)(k ? cr_out : cb_out) + (size_t)i * cw * ch, (size_t)cw, base + (size_t)(2 * i + k) * plane_bytes,
+                                     (size_t)pitch, (size_t)cw, (size_t)ch, hipMemcpyDeviceToDevice, stream));
+    }
+    HIP_TRY(hipStreamSynchronize(stream));
+    return JPEGAMD_OK;
+}
+
+// The BT.601 matrix: the entry above with JPEGAMD_MATRIX_BT601 -- no pass, no scratch, the launches read the caller's planes.
+extern "C" int32_t jpegamd_encode_ycbcr_samples_batch_async(JpegAmdEncoder *e, const JpegAmdYCbCrImage *imgs, int32_t count, int32_t subsampling,
+                                                            int32_t sample_range, int32_t sample_format, void *const *outs_dev,
+                                                            uint64_t out_capacity, void *const *out_sizes_dev, void *stream_) {
+    return jpegamd_encode_ycbcr_matrix_batch_async(e, imgs, count, subsampling, sample_range, sample_format, JPEGAMD_MATRIX_BT601, outs_dev,
+                                                   out_capacity, out_sizes_dev, stream_);
 }
 
 // One byte per sample: the entry above with JPEGAMD_SAMPLES_8.

@@ -320,6 +320,34 @@ struct ChromaPlanesBatchArgs {
     const uint8_t *pixels_g[kMaxBatch], *pixels_b[kMaxBatch];   // kChromaSrcPlanar alone
 };
 int launch_chroma_planes_batch(const ChromaPlanesBatchArgs &a, void *stream, void *const *ev = nullptr);
+
+// BT.709 YCbCr pictures (jpegamd_encode_ycbcr_matrix_batch_async, jpegamd_matrix.hip).  k_ycbcr_matrix_batch reads every picture of
+// the batch once, in whatever layout, depth and range it has, and writes 8-bit full-range BT.601 planes into context scratch: the
+// chroma planes where k_chroma_planes_batch puts them (plane j = picture j / 2, Cb or Cr, `plane_bytes` apart, `pitch` bytes per row),
+// the Y planes `yplane_bytes` apart at `ypitch` bytes per row (the width rounded up to 4).  With cb = Cb - 128, cr = Cr - 128 of the
+// 8-bit full-range samples (after the range and depth maps) and >> an arithmetic shift:
+//     Y'  = clamp(Y   + ((c[0] cb + c[1] cr + 8192) >> 14), 0, 255)
+//     Cb' = clamp(128 + ((c[2] cb + c[3] cr + 8192) >> 14), 0, 255)
+//     Cr' = clamp(128 + ((c[4] cb + c[5] cr + 8192) >> 14), 0, 255)
+// c = round(2^14 x) of BT.709 YCbCr -> R'G'B' (Kr 0.2126, Kb 0.0722) followed by R'G'B' -> BT.601 YCbCr (Kr 0.299, Kb 0.114).
+constexpr int kMatrixShift = 14;
+constexpr int32_t kMatrix709[6] = {1664, 3213, 16218, -1813, -1187, 16112};
+constexpr int32_t kMatrix601[6] = {0, 0, 1 << kMatrixShift, 0, 0, 1 << kMatrixShift};     // the identity: what BT.601 input asks for
+constexpr int kMatrixWalkPlanes = 0, kMatrixWalkPairs = 1, kMatrixWalkPacked = 2;        // Y, Cb, Cr planes / Y and a pair plane / one packed 4:2:2 plane
+struct YccMatrixBatchArgs {
+    const uint8_t *y[kMaxBatch];        // the Y planes (packed: the packed planes)
+    const uint8_t *cb[kMaxBatch];       // the Cb planes, or the pair planes (packed: not read)
+    const uint8_t *cr[kMaxBatch];       // kMatrixWalkPlanes alone
+    int32_t batch;
+    int32_t width, height, y_stride, c_stride;     // strides in bytes
+    int32_t mode, walk, sample_bytes;   // kChromaMode*, kMatrixWalk*, 1 or 2
+    int32_t first;                      // pairs: the index of Cb in a pair (0 / 1); packed: of Y in a pixel's two bytes (0 YUYV, 1 UYVY)
+    int32_t shift, limited;             // 16-bit words: 6 (MSB-aligned) or 0; limited range: 1
+    int32_t cw, ch, pitch, ypitch;
+    uint64_t plane_bytes, yplane_bytes; // multiples of 16
+    uint8_t *planes, *yplanes;
+};
+int launch_ycbcr_matrix_batch(const YccMatrixBatchArgs &a, void *stream, void *const *ev = nullptr);
 // k_picture_stats: what the tile records of one k_tile_encode launch add up to per picture and scan -- bits (with the first DC
 // symbol of every tile, which the record leaves out), run/size symbols, exact-order fallbacks -- summed into
 // pic[picture][scan][3].  Launch image i is picture i, scan 0 (luma), or plane first_plane + i (chroma).

@@ -44,6 +44,7 @@ class PlanarImage(C.Structure):
 CHROMA_PLANES, CHROMA_CBCR, CHROMA_CRCB = 0, 1, 2           # JPEGAMD_CHROMA_*
 CHROMA_YUYV, CHROMA_UYVY = 4, 5                             # packed 4:2:2: the picture's y is the packed plane (3 stays invalid)
 RANGE_FULL, RANGE_LIMITED = 0, 1                            # JPEGAMD_RANGE_*: JFIF full range / video range (Y 16..235, Cb Cr 16..240), expanded on read
+MATRIX_BT601, MATRIX_BT709 = 0, 1                           # JPEGAMD_MATRIX_*: the samples' YCbCr matrix: JFIF's own / BT.709 (HD, UHD video), converted by one pass
 SAMPLES_8, SAMPLES_10_MSB, SAMPLES_10_LSB = 0, 1, 2         # JPEGAMD_SAMPLES_*: one byte per sample / 10 bits in 16-bit words, high bits (P010) or low bits (I010), narrowed on read
 
 
@@ -119,6 +120,9 @@ def _load() -> C.CDLL:
         "jpegamd_encode_ycbcr_batch_async": (i32, [vp, C.POINTER(YCbCrImage), i32, i32, C.POINTER(C.c_void_p), u64, C.POINTER(C.c_void_p), vp]),
         "jpegamd_encode_ycbcr_range_batch_async": (i32, [vp, C.POINTER(YCbCrImage), i32, i32, i32, C.POINTER(C.c_void_p), u64, C.POINTER(C.c_void_p), vp]),
         "jpegamd_encode_ycbcr_samples_batch_async": (i32, [vp, C.POINTER(YCbCrImage), i32, i32, i32, i32, C.POINTER(C.c_void_p), u64, C.POINTER(C.c_void_p), vp]),
+        "jpegamd_encode_ycbcr_matrix_batch_async": (i32, [vp, C.POINTER(YCbCrImage), i32, i32, i32, i32, i32, C.POINTER(C.c_void_p), u64, C.POINTER(C.c_void_p), vp]),
+        "jpegamd_debug_matrix_coeffs": (i32, [i32, vp]),
+        "jpegamd_debug_ycbcr_matrix_planes": (i32, [vp, C.POINTER(YCbCrImage), i32, i32, i32, i32, i32, vp, vp, vp, vp]),
         "jpegamd_debug_chroma_groups": (i32, [i32, i32, i32, i32, i32, i32, i32, vp]),
         "jpegamd_debug_ycbcr_sources": (i32, [i32, i32, i32, i32, vp]),
         "jpegamd_debug_chroma_quant_table": (i32, [i32, vp]),
@@ -135,7 +139,8 @@ def _load() -> C.CDLL:
     for name, (res, args) in sig.items():
         if name in ("jpegamd_encoder_set_pipeline", "jpegamd_gather_streams", "jpegamd_debug_mfma_offsets", "jpegamd_encode_color_batch_async",
                     "jpegamd_debug_chroma_groups", "jpegamd_debug_ycbcr_sources", "jpegamd_encode_planar_batch_async", "jpegamd_encode_ycbcr_batch_async",
-                    "jpegamd_encode_ycbcr_range_batch_async", "jpegamd_encode_ycbcr_samples_batch_async") and os.environ.get("JPEGAMD_LIB") and not hasattr(lib, name):
+                    "jpegamd_encode_ycbcr_range_batch_async", "jpegamd_encode_ycbcr_samples_batch_async", "jpegamd_encode_ycbcr_matrix_batch_async",
+                    "jpegamd_debug_matrix_coeffs", "jpegamd_debug_ycbcr_matrix_planes") and os.environ.get("JPEGAMD_LIB") and not hasattr(lib, name):
             continue                                              # (A/B tooling: a variant build of an older round)
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = res, args
@@ -152,7 +157,7 @@ EXPORTED = ("jpegamd_encoder_create jpegamd_encoder_destroy jpegamd_max_jfif_byt
             "jpegamd_max_jfif_bytes_color jpegamd_encode_color_async jpegamd_encode_bmp_memory_color jpegamd_debug_chroma_quant_table "
             "jpegamd_debug_chroma_mfma_consts jpegamd_debug_chroma_group_thresholds jpegamd_debug_color_profile jpegamd_encode_color_batch_async "
             "jpegamd_encode_planar_batch_async jpegamd_encode_ycbcr_batch_async jpegamd_encode_ycbcr_range_batch_async "
-            "jpegamd_encode_ycbcr_samples_batch_async").split()
+            "jpegamd_encode_ycbcr_samples_batch_async jpegamd_encode_ycbcr_matrix_batch_async").split()
 
 
 def quant_table(quality: int = 50):
@@ -541,12 +546,21 @@ def _sample_range(sample_range) -> int:
     return RANGE_LIMITED if sample_range == "limited" else RANGE_FULL
 
 
+def _matrix(matrix) -> int:
+    """"bt601" / "bt709" -> JPEGAMD_MATRIX_*; anything else is a ValueError."""
+    if not isinstance(matrix, str) or matrix not in ("bt601", "bt709"):
+        raise ValueError(f'matrix must be "bt601" or "bt709", not {matrix!r}')
+    return MATRIX_BT709 if matrix == "bt709" else MATRIX_BT601
+
+
 def encode_ycbcr_batch(y, cb, cr=None, quality: int = 0, subsampling: int = SUBSAMPLE_420, order: str = "cbcr",
-                       sample_range: str = "full") -> list:
+                       sample_range: str = "full", matrix: str = "bt601") -> list:
     """N pictures whose samples already ARE Y, Cb and Cr (JFIF full range; no range or matrix conversion is done) -> N colour JFIF
     files through jpegamd_encode_ycbcr_batch_async, read where they lie: no RGB detour, no chroma-plane pass.
     sample_range="limited": the samples are video range (Y 16..235, Cb / Cr 16..240, as decoders deliver them) and are expanded to
     full range as the kernel reads them (jpegamd_encode_ycbcr_range_batch_async: no pass over the planes); the matrix stays BT.601.
+    matrix="bt709": the samples are BT.709 YCbCr (HD and UHD video) and are converted to JFIF's BT.601 by one pass in front of the tile
+    kernel (jpegamd_encode_ycbcr_matrix_batch_async: the integer map of include/jpeg_compression.h, after the range map).
     `y` is a uint8 DEVICE tensor [N, H, W]; `cb` and `cr` are [N, ch, cw] with (ch, cw) = (H, W) at SUBSAMPLE_444,
     (ceil(H / 2), ceil(W / 2)) at SUBSAMPLE_420 (I420; YV12 by swapping them) and (H, ceil(W / 2)) at SUBSAMPLE_422 (I422).  With
     cr=None, `cb` is [N, ch, cw, 2]: byte pairs Cb Cr (NV12; NV16 at 4:2:2; NV24 at 4:4:4), or Cr Cb with order="crcb" (NV21 / NV61 /
@@ -559,16 +573,17 @@ def encode_ycbcr_batch(y, cb, cr=None, quality: int = 0, subsampling: int = SUBS
         jpegamd.encode_ycbcr_batch(y, cbcr)
 
     and a stack of frames [N, 3 * H // 2, W] slices the same way: f[:, :H] and f[:, H:].unflatten(2, (W // 2, 2))."""
-    rng = _sample_range(sample_range)
+    rng, mat = _sample_range(sample_range), _matrix(matrix)
     n, h, w, y_stride, c_stride, layout = _ycbcr_layout(y, cb, cr, subsampling, order)
     tensors = [y, cb] + ([cr] if cr is not None else [])
     if any(not x.is_cuda or x.device != y.device for x in tensors):
         raise ValueError("encode_ycbcr_batch needs device tensors on one device")
     return _encode_ycbcr_images(y.device, n, h, w, subsampling, lambda i: Encoder.ycbcr_image(
-        y[i].data_ptr(), cb[i].data_ptr(), cr[i].data_ptr() if cr is not None else 0, w, h, y_stride, c_stride, layout, quality), rng)
+        y[i].data_ptr(), cb[i].data_ptr(), cr[i].data_ptr() if cr is not None else 0, w, h, y_stride, c_stride, layout, quality), rng, matrix=mat)
 
 
-def _encode_ycbcr_images(device, n, h, w, subsampling, image, sample_range: int = RANGE_FULL, sample_format: int = SAMPLES_8):
+def _encode_ycbcr_images(device, n, h, w, subsampling, image, sample_range: int = RANGE_FULL, sample_format: int = SAMPLES_8,
+                         matrix: int = MATRIX_BT601):
     """`n` YCbCr pictures of one geometry, picture i described by image(i), through the per-device context in calls of at most
     MAX_BATCH -> their files."""
     import torch
@@ -593,7 +608,8 @@ def _encode_ycbcr_images(device, n, h, w, subsampling, image, sample_range: int 
             outs = [out[i].data_ptr() for i in range(k)]
             size_ptrs = [sizes.data_ptr() + 8 * i for i in range(k)]
             imgs = [image(b0 + i) for i in range(k)]
-            enc.encode_ycbcr_batch_async(imgs, subsampling, outs, cap, size_ptrs, stream, sample_range, sample_format=sample_format)
+            enc.encode_ycbcr_batch_async(imgs, subsampling, outs, cap, size_ptrs, stream, sample_range, sample_format=sample_format,
+                                         matrix=matrix)
             enc.finish()
             got = sizes[:k].cpu().tolist()
             files += [bytes(out[i, :got[i]].cpu().numpy().tobytes()) for i in range(k)]
@@ -601,7 +617,7 @@ def _encode_ycbcr_images(device, n, h, w, subsampling, image, sample_range: int 
 
 
 def encode_ycbcr16_batch(y, cb, cr=None, quality: int = 0, subsampling: int = SUBSAMPLE_420, order: str = "cbcr",
-                         sample_range: str = "full", align: str = "msb") -> list:
+                         sample_range: str = "full", align: str = "msb", matrix: str = "bt601") -> list:
     """N pictures of 10-bit Y, Cb and Cr samples in 16-bit words (a Main10 / AV1 10-bit decoder's frames) -> N colour JFIF files through
     jpegamd_encode_ycbcr_samples_batch_async, read where they lie: every sample is narrowed to 8 bits as the kernel reads it (no pass
     over the planes), with ONE rounding from ten bits for either sample_range ("full" / "limited": Y 64..940, Cb / Cr 64..960).
@@ -609,8 +625,10 @@ def encode_ycbcr16_batch(y, cb, cr=None, quality: int = 0, subsampling: int = SU
     low ten bits, larger words clamp to 1023 (I010 / yuv420p10le).  The tensors are torch.int16 or torch.uint16 DEVICE tensors -- the
     bit pattern is what counts -- shaped as encode_ycbcr_batch's: `y` [N, H, W], `cb` and `cr` [N, ch, cw], or with cr=None `cb` as
     [N, ch, cw, 2] pairs of words Cb Cr (Cr Cb with order="crcb").  Rows and pictures may be strided, samples within a row are packed.
-    Batches of more than MAX_BATCH pictures go as several calls; the per-device context of encode_tensor is used."""
-    rng = _sample_range(sample_range)
+    Batches of more than MAX_BATCH pictures go as several calls; the per-device context of encode_tensor is used.
+    matrix="bt709": BT.709 samples, converted to BT.601 by one pass as in encode_ycbcr_batch; the pass narrows each sample by the same
+    map first and applies the matrix to the 8-bit results."""
+    rng, mat = _sample_range(sample_range), _matrix(matrix)
     if not isinstance(align, str) or align not in ("msb", "lsb"):
         raise ValueError(f'align must be "msb" or "lsb", not {align!r}')
     n, h, w, y_stride, c_stride, layout = _ycbcr16_layout(y, cb, cr, subsampling, order)
@@ -619,7 +637,7 @@ def encode_ycbcr16_batch(y, cb, cr=None, quality: int = 0, subsampling: int = SU
         raise ValueError("encode_ycbcr16_batch needs device tensors on one device")
     return _encode_ycbcr_images(y.device, n, h, w, subsampling, lambda i: Encoder.ycbcr_image(
         y[i].data_ptr(), cb[i].data_ptr(), cr[i].data_ptr() if cr is not None else 0, w, h, y_stride, c_stride, layout, quality), rng,
-        SAMPLES_10_MSB if align == "msb" else SAMPLES_10_LSB)
+        SAMPLES_10_MSB if align == "msb" else SAMPLES_10_LSB, mat)
 
 
 def _yuyv_layout(frames, order):
@@ -645,19 +663,20 @@ def _yuyv_layout(frames, order):
     return n, h, w, stride, (CHROMA_YUYV if order == "yuyv" else CHROMA_UYVY)
 
 
-def encode_yuyv_batch(frames, quality: int = 0, order: str = "yuyv", sample_range: str = "full") -> list:
+def encode_yuyv_batch(frames, quality: int = 0, order: str = "yuyv", sample_range: str = "full", matrix: str = "bt601") -> list:
     """N packed 4:2:2 frames -> N colour JFIF files at SUBSAMPLE_422 through jpegamd_encode_ycbcr_batch_async, read where they
     lie: the samples are coded as given (JFIF full range; no range or matrix conversion, no filter).
     `frames` is a uint8 DEVICE tensor [N, H, W, 2], W even: groups of four bytes Y0 Cb Y1 Cr for two pixels (YUY2), or Cb Y0 Cr Y1
     with order="uyvy".  Rows and pictures may be strided; the two bytes of a pixel and the pixels of a row are packed.  Batches of
     more than MAX_BATCH frames go as several calls; the per-device context of encode_tensor is used.  sample_range="limited": video-range
-    samples, expanded to full range on read as in encode_ycbcr_batch."""
-    rng = _sample_range(sample_range)
+    samples, expanded to full range on read as in encode_ycbcr_batch.  matrix="bt709": BT.709 samples, converted to BT.601 by one pass as
+    in encode_ycbcr_batch."""
+    rng, mat = _sample_range(sample_range), _matrix(matrix)
     n, h, w, stride, layout = _yuyv_layout(frames, order)
     if not frames.is_cuda:
         raise ValueError("encode_yuyv_batch needs a device tensor")
     return _encode_ycbcr_images(frames.device, n, h, w, SUBSAMPLE_422, lambda i: Encoder.ycbcr_image(
-        frames[i].data_ptr(), 0, 0, w, h, stride, 0, layout, quality), rng)
+        frames[i].data_ptr(), 0, 0, w, h, stride, 0, layout, quality), rng, matrix=mat)
 
 
 class BatchStats(C.Structure):
@@ -750,16 +769,23 @@ class Encoder:
         return YCbCrImage(y_ptr or None, cb_ptr or None, cr_ptr or None, width, height, y_stride, c_stride, chroma_layout, quality)
 
     def encode_ycbcr_batch_async(self, imgs, subsampling: int, out_ptrs, out_cap: int, size_ptrs, stream: int = 0,
-                                 sample_range: int = RANGE_FULL, sample_format: int = SAMPLES_8):
+                                 sample_range: int = RANGE_FULL, sample_format: int = SAMPLES_8, matrix: int = MATRIX_BT601):
         """The colour files of `len(imgs)` YCbCr pictures of one geometry (jpegamd_encode_ycbcr_batch_async); the context as for
         encode_color_batch_async.  sample_range: RANGE_FULL, or RANGE_LIMITED for video-range samples, which go through
         jpegamd_encode_ycbcr_range_batch_async and are expanded on read.  sample_format: SAMPLES_8, or SAMPLES_10_MSB / SAMPLES_10_LSB
         for 10-bit samples in 16-bit words (strides in bytes), which go through jpegamd_encode_ycbcr_samples_batch_async and are
-        narrowed on read."""
+        narrowed on read.  matrix: MATRIX_BT601, or MATRIX_BT709 for BT.709 samples, which go through
+        jpegamd_encode_ycbcr_matrix_batch_async: one pass converts them to BT.601 planes in context scratch."""
         n = len(imgs)
         arr = (YCbCrImage * n)(*imgs)
         outs = (C.c_void_p * n)(*[C.c_void_p(p) for p in out_ptrs])
         sizes = (C.c_void_p * n)(*[C.c_void_p(p) for p in size_ptrs])
+        if int(matrix) != MATRIX_BT601:              # (the BT.601 call keeps to the older entries, as below)
+            rc = lib.jpegamd_encode_ycbcr_matrix_batch_async(self._h, arr, n, int(subsampling), int(sample_range), int(sample_format),
+                                                             int(matrix), outs, out_cap, sizes, C.c_void_p(stream))
+            if rc:
+                raise JpegAmdError(rc, "jpegamd_encode_ycbcr_matrix_batch_async")
+            return
         if int(sample_format) != SAMPLES_8:          # (one byte per sample keeps to the older entries, as below)
             rc = lib.jpegamd_encode_ycbcr_samples_batch_async(self._h, arr, n, int(subsampling), int(sample_range), int(sample_format), outs,
                                                               out_cap, sizes, C.c_void_p(stream))

@@ -24,6 +24,13 @@ which narrows them on read: at full range the files are those of `nv12`, so "byt
 that replaces, in the same run: the narrowing as a pass of its own over the planes (16-bit words in, bytes out, into preallocated
 planes: "narrow_us_per_picture") and the 8-bit encode of the planes it wrote at the same --range ("narrowed_8bit_us_per_picture").
 
+--matrix bt709 (the YCbCr sources) takes the same samples as BT.709 YCbCr: the calls go through jpegamd_encode_ycbcr_matrix_batch_async
+with JPEGAMD_MATRIX_BT709, whose one pass (k_ycbcr_matrix_batch) converts them to BT.601 planes in context scratch; the line then carries
+"matrix", and "pass_bytes_per_picture": what that pass reads and writes, from the shapes.  With --convert (i420, nv12, p010, i010) it also
+times the route a caller has without the entry, in the same run: the same conversion written with torch ops into preallocated 8-bit
+planes ("convert_us_per_picture"; the range / depth map first where the source has one), then the plain encode of the planes it wrote
+("converted_plain_us_per_picture", whose files must be the BT.709 call's: "converted_bytes_equal").
+
 With --layout {hwc,chw,rgba} (and --batch N, default 8) the pictures are device tensors stored that way -- [N, H, W, 3], [N, 3, H, W],
 [N, H, W, 4] -- and go through the entry that reads them where they lie, 4:2:0 only.  Every call is timed as a whole between two
 events on the stream; --rounds R medians of --steps calls each are reported, with their spread (max - min).  --repack (chw only)
@@ -57,7 +64,10 @@ def main() -> None:
     ap.add_argument("--subsampling", choices=("420", "444", "422"), default=None, help="rgb: this subsampling alone (default: 420, then 444)")
     ap.add_argument("--range", choices=("full", "limited"), default="full", dest="sample_range",
                     help="i420 / nv12 / i422 / yuyv: the samples are full range (default) or limited range, expanded on read")
-    ap.add_argument("--convert", action="store_true", help="--range limited: also time the map as a separate pass + the full-range encode")
+    ap.add_argument("--matrix", choices=("bt601", "bt709"), default="bt601",
+                    help="the YCbCr sources: the samples are BT.601 (default) or BT.709 YCbCr, converted by one pass in front of the tile kernel")
+    ap.add_argument("--convert", action="store_true", help="--range limited: also time the map as a separate pass + the full-range encode; "
+                    "--matrix bt709: the conversion with torch ops + the plain encode")
     ap.add_argument("--narrow", action="store_true", help="p010 / i010: also time the narrowing as a separate pass + the 8-bit encode")
     ap.add_argument("--layout", choices=("hwc", "chw", "rgba"), default=None, help="device tensors stored this way, read where they lie")
     ap.add_argument("--rounds", type=int, default=5, help="--layout: medians taken (each of --steps calls)")
@@ -79,8 +89,14 @@ def main() -> None:
         sys.exit("--source takes rgb, i420, nv12, i422, yuyv, p010, i010 or a comma-separated list of them")
     if a.sample_range != "full" and "rgb" in sources:
         sys.exit("--range limited is for the YCbCr sources (i420, nv12, i422, yuyv, p010, i010)")
-    if a.convert and a.sample_range != "limited":
-        sys.exit("--convert needs --range limited")
+    if a.matrix != "bt601" and "rgb" in sources:
+        sys.exit("--matrix bt709 is for the YCbCr sources (i420, nv12, i422, yuyv, p010, i010)")
+    if a.convert and a.sample_range != "limited" and a.matrix != "bt709":
+        sys.exit("--convert needs --range limited or --matrix bt709")
+    if a.convert and a.matrix == "bt709" and any(s in ("i422", "yuyv") for s in sources):
+        sys.exit("--matrix bt709 --convert takes the 4:2:0 sources (i420, nv12, p010, i010)")
+    if a.convert and a.matrix == "bt709" and a.sample_range == "limited" and any(s in ("p010", "i010") for s in sources):
+        sys.exit("--matrix bt709 --convert with p010 / i010 is written for --range full (the torch route narrows by a shift)")
     if a.narrow and not any(s in ("p010", "i010") for s in sources):
         sys.exit("--narrow needs --source p010 or i010")
     if a.batch is not None or sources != ["rgb"]:
@@ -211,7 +227,9 @@ def run_batch(a, jpegamd, torch, dev, sources=("rgb",)) -> None:
                 jpegamd.Encoder.ycbcr_image(t[0][i].data_ptr(), t[0][i, h:].data_ptr(), 0, w, h, w, w,
                                             jpegamd.CHROMA_CBCR, a.quality) for i in range(n)]))
     limited = a.sample_range == "limited"
-    if a.convert:
+    bt709 = a.matrix == "bt709"
+    lut_y = lut_c = None
+    if a.convert and limited:
         lut_y = torch.tensor([(255 * (min(max(v, 16), 235) - 16) + 109) // 219 for v in range(256)], dtype=torch.uint8, device=dev)
         lut_c = torch.tensor([(255 * (min(max(v, 16), 240) - 16) + 112) // 224 for v in range(256)], dtype=torch.uint8, device=dev)
     for source, sub, name, tensors, describe in runs:
@@ -227,6 +245,8 @@ def run_batch(a, jpegamd, torch, dev, sources=("rgb",)) -> None:
             kw = {"sample_range": jpegamd.RANGE_LIMITED} if limited else {}
             if source in ("p010", "i010"):
                 kw["sample_format"] = jpegamd.SAMPLES_10_MSB if source == "p010" else jpegamd.SAMPLES_10_LSB
+            if bt709:
+                kw["matrix"] = jpegamd.MATRIX_BT709
             call = lambda: enc.encode_ycbcr_batch_async(ycc, sub, out_ptrs, cap, size_ptrs, stream, **kw)
         for _ in range(a.warmup):
             call()
@@ -244,6 +264,15 @@ def run_batch(a, jpegamd, torch, dev, sources=("rgb",)) -> None:
                 "gpixels_per_s": round(n * w * h / t, 2)}
         if limited:
             line["range"] = "limited"
+        if bt709 and ycc is not None:
+            line["matrix"] = "bt709"
+            line["pass_bytes_per_picture"] = pass_bytes(w, h, sub, jpegamd, 2 if source in ("p010", "i010") else 1)
+            if a.convert:
+                line.update(time_matrix_convert(a, jpegamd, torch, enc, source, tensors, (lut_y, lut_c), h, sub, out_ptrs, cap, size_ptrs,
+                                                sizes, stream, n))
+            print(json.dumps(line))
+            del outs
+            continue
         if a.narrow and source in ("p010", "i010"):
             line.update(time_narrow(a, jpegamd, torch, enc, source, tensors, h, sub, out_ptrs, cap, size_ptrs, sizes, stream, n))
         if a.convert and source not in ("p010", "i010"):
@@ -297,6 +326,72 @@ def time_convert(a, jpegamd, torch, enc, source, tensors, describe, luts, h, sub
     enc.set_profiling(0)
     return {"convert_us_per_picture": round(statistics.median(times), 1), "mapped_full_us_per_picture": round(t / n / 1000, 1),
             "mapped_bytes_equal": sizes.cpu().tolist() == limited_bytes}
+
+
+def pass_bytes(w, h, sub, jpegamd, sample_bytes):
+    """What k_ycbcr_matrix_batch moves for one picture: every stored sample read once, every 8-bit sample of the three planes written once."""
+    cw = w if sub == jpegamd.SUBSAMPLE_444 else (w + 1) // 2
+    ch = (h + 1) // 2 if sub == jpegamd.SUBSAMPLE_420 else h
+    samples = w * h + 2 * cw * ch
+    return samples * sample_bytes + samples
+
+
+def time_matrix_convert(a, jpegamd, torch, enc, source, tensors, luts, h, sub, out_ptrs, cap, size_ptrs, sizes, stream, n):
+    """What the BT.709 entry replaces at 4:2:0: the definition of include/jpeg_compression.h in torch integer ops over the source's planes
+    (the depth / range map first) into preallocated 8-bit planes, one call's worth between two events on the stream, then the plain
+    encode of those planes."""
+    w = a.size
+    lut_y, lut_c = luts if a.sample_range == "limited" else (None, None)
+    direct_bytes = sizes.cpu().tolist()
+    out_y = torch.empty((n, h, w), dtype=torch.uint8, device=tensors[0].device)
+    out_cb, out_cr = (torch.empty((n, h // 2, w // 2), dtype=torch.uint8, device=tensors[0].device) for _ in range(2))
+    c = (1664, 3213, 16218, -1813, -1187, 16112)
+
+    def to8(t, lut, shift):
+        """Stored samples -> int32 full-range 8-bit values (the bench's words hold s << 8 or s << 2: at full range the shift is exact)."""
+        v = (t.to(torch.int32) >> shift) & 0xFF if shift else t.to(torch.int32)
+        return lut[v.long()].to(torch.int32) if lut is not None else v
+
+    def convert():
+        if source in ("nv12", "p010"):                           # [N, 3 H / 2, W]: H rows of Y, then the Cb Cr pairs
+            shift = 8 if source == "p010" else 0
+            y = to8(tensors[0][:, :h], lut_y, shift)
+            pairs = to8(tensors[0][:, h:], lut_c, shift).view(n, h // 2, w // 2, 2)
+            b, r = pairs[..., 0] - 128, pairs[..., 1] - 128
+        else:                                                    # three planes (i420: the Y rows of the frames)
+            shift = 2 if source == "i010" else 0
+            y = to8(tensors[0][:, :h], lut_y, shift)
+            b, r = to8(tensors[1], lut_c, shift) - 128, to8(tensors[2], lut_c, shift) - 128
+        ty = (c[0] * b + c[1] * r + 8192) >> 14
+        out_y.copy_((y + ty.repeat_interleave(2, dim=1).repeat_interleave(2, dim=2)).clamp_(0, 255))
+        out_cb.copy_((128 + ((c[2] * b + c[3] * r + 8192) >> 14)).clamp_(0, 255))
+        out_cr.copy_((128 + ((c[4] * b + c[5] * r + 8192) >> 14)).clamp_(0, 255))
+
+    for _ in range(2):
+        convert()
+    torch.cuda.synchronize()
+    times = []
+    for _ in range(max(3, a.steps // 5)):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        convert()
+        e1.record()
+        torch.cuda.synchronize()
+        times.append(e0.elapsed_time(e1) * 1000.0 / n)
+    ycc = [jpegamd.Encoder.ycbcr_image(out_y[i].data_ptr(), out_cb[i].data_ptr(), out_cr[i].data_ptr(), w, h, w, w // 2,
+                                       jpegamd.CHROMA_PLANES, a.quality) for i in range(n)]
+    call = lambda: enc.encode_ycbcr_batch_async(ycc, sub, out_ptrs, cap, size_ptrs, stream)
+    for _ in range(a.warmup):
+        call()
+    enc.finish()
+    enc.set_profiling(a.steps)
+    for _ in range(a.steps):
+        call()
+    enc.finish()
+    t = statistics.median(enc.profile(i).ns_total for i in range(a.steps))
+    enc.set_profiling(0)
+    return {"convert_us_per_picture": round(statistics.median(times), 1), "converted_plain_us_per_picture": round(t / n / 1000, 1),
+            "converted_bytes_equal": sizes.cpu().tolist() == direct_bytes}
 
 
 def time_narrow(a, jpegamd, torch, enc, source, tensors, h, sub, out_ptrs, cap, size_ptrs, sizes, stream, n):
