@@ -313,6 +313,40 @@ int32_t jpegamd_encode_ycbcr_matrix_batch_async(JpegAmdEncoder *enc, const JpegA
                                                 int32_t sample_range, int32_t sample_format, int32_t matrix, void *const *outs_dev,
                                                 uint64_t out_capacity, void *const *out_sizes_dev, void *stream);
 
+/* Colour files with ONE scan of interleaved MCUs -- what Motion-JPEG containers, RTP/JPEG, hardware and most embedded decoders
+ * need, and what a decoder can take in a streaming fashion.  The file: the colour prefix of the entries above unchanged up to and
+ * including its four DHT segments, then ONE SOS (FF DA 00 0C 03 01 00 02 11 03 11 00 3F 00), one entropy-coded segment, EOI; no
+ * restart markers.  With (hs, vs) = (1,1) at 4:4:4, (2,2) at 4:2:0, (2,1) at 4:2:2 the MCU grid is ceil(W / 8hs) x ceil(H / 8vs),
+ * coded in raster order; inside an MCU the Y blocks (v outer, u inner), then the Cb block, then the Cr block.  A real block's 64
+ * quantised coefficients are exactly those the three-scan entries code for the same picture.  A Y block beyond the picture's last
+ * block column or row (the MCU grid overhangs it) is a pad block: its 63 AC coefficients are zero and its DC is that of the nearest
+ * real block (clamped block coordinates) -- libjpeg's choice; a decoder discards it.  Coding is T.81 F.1.2 with the Annex K tables of
+ * the prefix, one DC predictor per component running through that component's blocks in scan order, pad blocks included.  The file
+ * decodes to the same pixels as the three-scan file of the same picture.
+ * jpegamd_encode_color_interleaved_batch_async follows jpegamd_encode_color_batch_async (JPEGAMD_ORDER_BGR / _RGB, either row order,
+ * all three subsamplings; GRAY, RGBA and BGRA: JPEGAMD_ERR_ARG), jpegamd_encode_ycbcr_interleaved_batch_async follows
+ * jpegamd_encode_ycbcr_batch_async (8-bit, full-range, BT.601 samples in JPEGAMD_CHROMA_PLANES, _CBCR, _CRCB; out_sizes_dev[i] a
+ * DEVICE uint64_t; _YUYV / _UYVY: JPEGAMD_ERR_ARG): count 1 .. JPEGAMD_MAX_BATCH of one geometry, the context created as for those
+ * entries, no host synchronisation inside the call, bad arguments refused with JPEGAMD_ERR_ARG before the context is read.  A picture
+ * that does not fit out_capacity gets size 0, nothing is written past out_capacity, the other pictures are unaffected and
+ * jpegamd_encoder_finish returns JPEGAMD_ERR_HUFF_CAPACITY.  finish reports the last picture's size; entropy_bits, stuffed_bytes and
+ * exact_fallbacks are sums over the batch (exact_fallbacks equals the three-scan entry's figure: pad blocks add none).  With
+ * profiling on, a call records ns_total only.  jpegamd_encoder_set_pipeline has no effect on these entries.
+ * This is a first version: the coefficients make a round trip through device memory (the stage-tap build of the tile kernel stores
+ * them, one launch per picture and component; k_mcu_segments codes them in MCU order; the unchanged k_finalize writes the file), so
+ * it is slower per picture than the three-scan entries.  Its scratch -- the coefficient planes and the path's own segment arrays
+ * -- is allocated on the context's first interleaved call, sized for that call and grown when a later one needs more; a large batch
+ * goes through in groups of pictures that bound it.  Limited range, 16-bit samples, BT.709, packed 4:2:2, planar RGB and 4-byte
+ * pixels in one scan are follow-ups. */
+int32_t jpegamd_encode_color_interleaved_batch_async(JpegAmdEncoder *enc, const JpegAmdImage *imgs, int32_t count, int32_t subsampling,
+                                                     void *const *outs_dev, uint64_t out_capacity, uint64_t *const *out_sizes_dev,
+                                                     void *stream);
+int32_t jpegamd_encode_ycbcr_interleaved_batch_async(JpegAmdEncoder *enc, const JpegAmdYCbCrImage *imgs, int32_t count, int32_t subsampling,
+                                                     void *const *outs_dev, uint64_t out_capacity, void *const *out_sizes_dev, void *stream);
+/* Upper bound on the interleaved file's bytes: 640 (the prefix) + 2 * (ceil(nb * 1723 / 8) + 1) + 2 + 16 with
+ * nb = mx * my * (hs * vs + 2) blocks, pad blocks included (jpegamd_max_jfif_bytes_color does not count those); 0 for bad args. */
+uint64_t jpegamd_max_jfif_bytes_interleaved(int32_t width, int32_t height, int32_t subsampling);
+
 /* Which kernels follow k_tile_encode for whole pictures (no reference counterpart: a tuning knob, results are byte-identical).
  *   PAIR    k_segment_merge + k_finalize: the tiles' bit strings joined per segment, then stitched behind a kernel boundary;
  *   STITCH  k_stitch: one pass, the offsets handed from workgroup to workgroup inside the launch (decoupled look-back);

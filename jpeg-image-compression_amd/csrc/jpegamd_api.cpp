@@ -91,6 +91,18 @@ struct JpegAmdEncoder {
         uint8_t *bplanes = nullptr, *bscans = nullptr;
         size_t bplanes_cap = 0, bscans_cap = 0;
     } color;
+    // Interleaved-MCU colour files (jpegamd_encode_color_interleaved_batch_async): nothing of this is allocated before the context's
+    // first such call; sized for that call, grown when a later one needs more.
+    struct Mcu {
+        int16_t *coef = nullptr;            // the coefficient planes of one group of pictures
+        size_t coef_cap = 0;                // int16 elements
+        SegArrays seg = {};                 // the path's own segments (an MCU scan has 1.5 x to 3 x the blocks of the Y scan)
+        size_t segs_cap = 0;
+        uint8_t *hdr = nullptr;             // the prefix with the three-component SOS
+        ScanStats *scan_stats = nullptr;    // k_finalize's record of the call
+        int hdr_w = -1, hdr_h = -1, hdr_q = -1, hdr_sub = -1;
+        int hdr_len = 0;
+    } mcu;
 };
 
 static int segs_for(int w, int h, int *bw, int *bh, int *spr, int seg_tiles = kSegTiles) {
@@ -303,6 +315,8 @@ extern "C" int32_t jpegamd_encoder_destroy(JpegAmdEncoder *e) {
     hipFree(e->color.tables_dev); hipFree(e->color.code_tab); hipFree(e->color.huff); hipFree(e->color.hdr); hipFree(e->color.scan_size);
     hipFree(e->color.scan_stats); hipFree(e->color.planes); hipFree(e->color.scans);
     hipFree(e->color.bmeta); hipFree(e->color.bplanes); hipFree(e->color.bscans);
+    hipFree(e->mcu.coef); hipFree(e->mcu.seg.words); hipFree(e->mcu.seg.bits); hipFree(e->mcu.seg.syms); hipFree(e->mcu.seg.exact);
+    hipFree(e->mcu.seg.edge); hipFree(e->mcu.seg.ffin); hipFree(e->mcu.hdr); hipFree(e->mcu.scan_stats);
     for (auto &set : e->ring) { for (auto &ev : set.ev) if (ev) hipEventDestroy(ev); for (auto &ev : set.cev) if (ev) hipEventDestroy(ev); }
     delete e->tables_host;
     delete e;
@@ -520,6 +534,7 @@ struct ScanTarget {
     int32_t prefix_len, write_eoi;
     ScanStats *stats;
     bool chroma;
+    const SegArrays *seg = nullptr;     // the segments k_finalize reads when they are not the context's own (an interleaved-MCU scan)
 };
 
 // k_finalize over the segments k_segment_merge (or an import) left: `batch` pictures.  `use_groups`: the group aggregates are valid
@@ -529,7 +544,7 @@ static int run_finalize(JpegAmdEncoder *e, const ImageDesc &im, void *const *out
                         int32_t with_container, hipStream_t stream, hipEvent_t *ev, int batch, bool use_groups, const ScanTarget *tgt = nullptr) {
     FinalizeArgs fa;
     std::memset(&fa, 0, sizeof(fa));
-    fa.seg = e->seg;
+    fa.seg = (tgt && tgt->seg) ? *tgt->seg : e->seg;
     fa.seg.words_stride = (uint32_t)seg_cap_words(im.seg_tiles);
     fa.num_segs = im.num_segs; fa.num_chunks = finalize_chunks(im.num_segs);
     fa.batch = batch;
@@ -1430,6 +1445,256 @@ extern "C" int32_t jpegamd_encode_ycbcr_batch_async(JpegAmdEncoder *e, const Jpe
                                                     void *const *outs_dev, uint64_t out_capacity, void *const *out_sizes_dev,
                                                     void *stream_) {
     return jpegamd_encode_ycbcr_range_batch_async(e, imgs, count, subsampling, JPEGAMD_RANGE_FULL, outs_dev, out_capacity, out_sizes_dev, stream_);
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Colour in ONE scan of interleaved MCUs.  Per picture and component the stage-tap build of k_tile_encode stores
+// the quantised zigzag coefficients (tap_zz) into context scratch -- one launch per picture and component: the tap's block index has
+// no picture term -- and k_picture_stats takes the exact-order fallback counts from the records those launches leave.  k_mcu_segments
+// codes the planes in MCU order into the path's OWN segment arrays, the unchanged k_finalize writes prefix, scan and EOI straight
+// into the caller's buffers, k_mcu_totals sums the call's record.  A large batch goes through in groups of pictures that bound the
+// scratch.  jpegamd_encoder_set_pipeline has no effect here: k_stitch reads tile records.
+// ---------------------------------------------------------------------------------------------------------
+struct McuGeometry {
+    int hs, vs, bw, bh, mx, my, cw, ch, seg_mcus, num_segs, num_segs_pad;
+    size_t coef_per_pic;                // int16 elements
+};
+static McuGeometry mcu_geometry(int w, int h, int sub) {
+    McuGeometry g;
+    g.hs = sub == JPEGAMD_SUBSAMPLE_444 ? 1 : 2;
+    g.vs = sub == JPEGAMD_SUBSAMPLE_420 ? 2 : 1;
+    g.bw = (w + 7) / 8; g.bh = (h + 7) / 8;
+    g.mx = (g.bw + g.hs - 1) / g.hs; g.my = (g.bh + g.vs - 1) / g.vs;
+    chroma_dims(w, h, sub, &g.cw, &g.ch);
+    g.seg_mcus = mcu_seg_mcus(g.hs, g.vs);
+    g.num_segs = (int)(((int64_t)g.mx * g.my + g.seg_mcus - 1) / g.seg_mcus);
+    g.num_segs_pad = (g.num_segs + kSegGroup - 1) / kSegGroup * kSegGroup;
+    g.coef_per_pic = ((size_t)g.bw * g.bh + 2 * (size_t)g.mx * g.my) * 64;
+    return g;
+}
+
+extern "C" uint64_t jpegamd_max_jfif_bytes_interleaved(int32_t width, int32_t height, int32_t subsampling) {
+    if (width <= 0 || height <= 0 || width > 65535 || height > 65535 || !sub_valid(subsampling)) return 0;
+    const McuGeometry g = mcu_geometry(width, height, subsampling);
+    // the prefix, every block of every MCU (pad blocks too) at the worst case with every byte stuffed, the flush byte, EOI
+    return kColorPrefixMax + scan_bound((uint64_t)g.mx * (uint64_t)g.my * (uint64_t)(g.hs * g.vs + 2)) + 2 + 16;
+}
+
+constexpr int kMcuSosBytes = 14;
+constexpr size_t kMcuScratchBudget = (size_t)4 << 30;       // coefficient planes + segment strings of one group of pictures
+
+// The path's scratch for `group` pictures of geometry g: allocated on the first call, grown when a call needs more.
+static int32_t mcu_alloc(JpegAmdEncoder *e, const McuGeometry &g, int group) {
+    auto &m = e->mcu;
+    if (!m.hdr) {
+        HIP_TRY(hipMalloc((void **)&m.hdr, 1024));
+        HIP_TRY(hipMalloc((void **)&m.scan_stats, sizeof(ScanStats)));
+    }
+    const size_t coef = (size_t)group * g.coef_per_pic, segs = (size_t)group * (size_t)g.num_segs_pad;
+    if (coef > m.coef_cap || segs > m.segs_cap) {
+        if (e->pending) HIP_TRY(hipStreamSynchronize(e->last_stream));
+        if (coef > m.coef_cap) {
+            hipFree(m.coef); m.coef = nullptr; m.coef_cap = 0;
+            HIP_TRY(hipMalloc((void **)&m.coef, coef * sizeof(int16_t)));
+            m.coef_cap = coef;
+        }
+        if (segs > m.segs_cap) {
+            hipFree(m.seg.words); hipFree(m.seg.bits); hipFree(m.seg.syms); hipFree(m.seg.exact); hipFree(m.seg.edge); hipFree(m.seg.ffin);
+            m.seg = SegArrays{}; m.segs_cap = 0;
+            const size_t n = segs + 16;                               // k_finalize reads the per-segment arrays four at a time
+            HIP_TRY(hipMalloc((void **)&m.seg.words, (segs + 1) * (size_t)kSegCapWords * sizeof(uint32_t)));
+            HIP_TRY(hipMalloc((void **)&m.seg.bits, n * sizeof(uint32_t)));
+            HIP_TRY(hipMalloc((void **)&m.seg.syms, n * sizeof(uint32_t)));
+            HIP_TRY(hipMalloc((void **)&m.seg.exact, n * sizeof(uint32_t)));
+            HIP_TRY(hipMalloc((void **)&m.seg.edge, n * sizeof(uint32_t)));
+            HIP_TRY(hipMalloc((void **)&m.seg.ffin, n * 8 * sizeof(uint16_t)));
+            m.seg.words_stride = kSegCapWords;
+            m.segs_cap = segs;
+        }
+    }
+    return JPEGAMD_OK;
+}
+
+// The colour prefix up to its DHTs, then the SOS of all three components (Y: tables 0 / 0, Cb and Cr: 1 / 1).
+static int32_t prepare_mcu_prefix(JpegAmdEncoder *e, const JpegAmdImage *img, int sub) {
+    auto &m = e->mcu;
+    const int q = clamp_quality(img->quality);
+    if (m.hdr_w == img->width && m.hdr_h == img->height && m.hdr_q == q && m.hdr_sub == sub) return JPEGAMD_OK;
+    uint8_t luma[64], chroma[64], hdr[kColorPrefixMax + kMcuSosBytes];
+    quant_table_for_quality(q, luma);
+    chroma_quant_table_for_quality(q, chroma);
+    const size_t n = build_jfif_prefix_color(img->width, img->height, luma, chroma, chroma_mode(sub), hdr) - kSosBytes;
+    const uint8_t sos[kMcuSosBytes] = {0xFF, 0xDA, 0x00, 0x0C, 0x03, 0x01, 0x00, 0x02, 0x11, 0x03, 0x11, 0x00, 0x3F, 0x00};
+    std::memcpy(hdr + n, sos, sizeof(sos));
+    if (e->pending) HIP_TRY(hipStreamSynchronize(e->last_stream));
+    HIP_TRY(hipMemcpy(m.hdr, hdr, n + sizeof(sos), hipMemcpyHostToDevice));
+    m.hdr_len = (int)(n + sizeof(sos));
+    m.hdr_w = img->width; m.hdr_h = img->height; m.hdr_q = q; m.hdr_sub = sub;
+    return JPEGAMD_OK;
+}
+
+// The interleaved files of a batch whose arguments are known to be good: g0 describes every picture, px holds their pixels.
+// `ycc` (a YCbCr batch, 8-bit full-range BT.601): g0 / px are the Y planes as a GRAY picture, the chroma comes from the caller.
+static int32_t interleaved_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, const PlaneSet &px, int32_t count, int32_t subsampling,
+                                 void *const *outs_dev, uint64_t out_capacity, uint64_t *const *out_sizes_dev, void *stream_,
+                                 const YccSource *ycc = nullptr) {
+    const McuGeometry g = mcu_geometry(g0.width, g0.height, subsampling);
+    // every launch codes ONE picture's component: the Y plane and a chroma plane must fit the context
+    ImageDesc iy;
+    int32_t rc = describe(e, &g0, &iy);
+    if (rc) return rc;
+    const int pitch = (g.cw + 3) / 4 * 4;
+    JpegAmdImage pimg = g0;
+    pimg.width = g.cw; pimg.height = g.ch; pimg.row_stride = ycc ? ycc->c_stride : pitch; pimg.bottom_up = 0; pimg.channel_order = JPEGAMD_ORDER_GRAY;
+    pimg.pixels = ycc ? ycc->cb[0] : g0.pixels;                      // (a non-null placeholder: every launch sets its own plane)
+    ImageDesc ic;
+    rc = describe(e, &pimg, &ic);
+    if (rc) return rc;
+    if (iy.blocks_w != g.bw || iy.blocks_h != g.bh || ic.blocks_w != g.mx || ic.blocks_h != g.my) return JPEGAMD_ERR_ARG;
+
+    const size_t per_pic = g.coef_per_pic * sizeof(int16_t) + (size_t)g.num_segs_pad * kSegCapWords * sizeof(uint32_t);
+    const int group = (int)std::max<size_t>(1, std::min<size_t>((size_t)count, kMcuScratchBudget / per_pic));
+    const size_t plane_bytes = round_up((size_t)pitch * (size_t)g.ch, 256);
+    rc = color_alloc_consts(e);
+    if (rc) return rc;
+    rc = color_batch_alloc(e, ycc ? 0 : 2 * (size_t)count * plane_bytes + 256, 0);
+    if (rc) return rc;
+    rc = mcu_alloc(e, g, group);
+    if (rc) return rc;
+    rc = prepare_constants(e, &g0, false);
+    if (rc) return rc;
+    rc = prepare_color_constants(e, &g0, subsampling);
+    if (rc) return rc;
+    rc = prepare_mcu_prefix(e, &g0, subsampling);
+    if (rc) return rc;
+    auto &c = e->color;
+    auto &m = e->mcu;
+    unsigned long long *pic = reinterpret_cast<unsigned long long *>(c.bmeta + kBatchMetaStats);
+    hipStream_t stream = (hipStream_t)stream_;
+
+    hipEvent_t *cev;
+    rc = claim_slot(e, true, true, &cev);
+    if (rc) return rc;
+    if (cev) HIP_TRY(hipEventRecord(cev[0], stream));                // ns_total: from here to behind the last kernel
+    HIP_TRY(hipMemsetAsync(c.bmeta + kBatchMetaStats, 0, kBatchMetaPic, stream));
+    HIP_TRY(hipMemsetAsync(m.scan_stats, 0, sizeof(ScanStats), stream));
+    HIP_TRY(hipMemsetAsync(e->stats_dev, 0, offsetof(ScanStats, status), stream));      // the sums and the size; the status stays sticky
+
+    if (!ycc) {
+        ChromaPlanesBatchArgs pa;
+        std::memset(&pa, 0, sizeof(pa));
+        for (int i = 0; i < count; ++i) pa.pixels[i] = px.p[0][i];
+        pa.layout = kChromaSrcPx3;
+        pa.batch = count;
+        pa.width = g0.width; pa.height = g0.height; pa.row_stride = g0.row_stride; pa.bottom_up = g0.bottom_up ? 1 : 0;
+        pa.rgb = g0.channel_order == JPEGAMD_ORDER_BGR ? 0 : 1;
+        pa.mode = chroma_mode(subsampling);
+        pa.cw = g.cw; pa.ch = g.ch; pa.pitch = pitch;
+        pa.plane_bytes = plane_bytes; pa.planes = c.bplanes;
+        if (launch_chroma_planes_batch(pa, stream, nullptr)) return JPEGAMD_ERR_HIP;
+    }
+    const size_t cb_off = (size_t)g.bw * g.bh * 64, cr_off = cb_off + (size_t)g.mx * g.my * 64;
+    for (int first = 0; first < count; first += group) {
+        const int n = std::min(group, count - first);
+        for (int i = 0; i < n; ++i) {
+            const int p = first + i;
+            int16_t *coef = m.coef + (size_t)i * g.coef_per_pic;
+            {   // Y
+                ImageDesc im = iy;
+                im.pixels = px.p[0][p];
+                for (int k = 0; k < kMaxBatch; ++k) im.batch_pixels[k] = im.pixels;
+                im.fast_ok = ((((uintptr_t)im.pixels) & 3u) == 0 && (g0.row_stride & 3) == 0 && g0.row_stride < (1 << 24)) ? 1 : 0;
+                TileSource src = src_of(&g0);
+                if (ycc) {
+                    const SourceChoice y = ycbcr_y_source(ycc->layout, ycc->format, ycc->range);
+                    src = y.src; im.select = y.select;
+                }
+                if (launch_transform(e, im, true, nullptr, coef, nullptr, stream, nullptr, src)) return JPEGAMD_ERR_HIP;
+                const PictureStatsArgs ps = {e->tile_head, e->huff, im.num_tiles, 1, 0, 0, pic + (size_t)p * kPicStatWords};
+                if (launch_picture_stats(ps, stream)) return JPEGAMD_ERR_HIP;
+            }
+            const bool one_plane = ycc && ycc->layout != JPEGAMD_CHROMA_PLANES;
+            for (int k = 0; k < 2; ++k) {   // Cb, Cr
+                ImageDesc im = ic;
+                if (!ycc) im.pixels = c.bplanes + (size_t)(2 * p + k) * plane_bytes;
+                else im.pixels = (one_plane || k == 0) ? ycc->cb[p] : ycc->cr[p];
+                for (int j = 0; j < kMaxBatch; ++j) im.batch_pixels[j] = im.pixels;
+                im.fast_ok = ((((uintptr_t)im.pixels) & 3u) == 0 && (pimg.row_stride & 3) == 0 && pimg.row_stride < (1 << 24)) ? 1 : 0;
+                TileSource src = {kSrcPlane, true};
+                if (ycc) {
+                    const SourceChoice cs = ycbcr_chroma_source(ycc->layout, ycc->format, ycc->range, k);
+                    src = cs.src; im.select = cs.select;
+                }
+                if (launch_transform(e, im, true, nullptr, coef + (k ? cr_off : cb_off), nullptr, stream, nullptr, src)) return JPEGAMD_ERR_HIP;
+                const PictureStatsArgs ps = {e->tile_head, c.huff, im.num_tiles, 1, 1, 2 * p + k, pic};
+                if (launch_picture_stats(ps, stream)) return JPEGAMD_ERR_HIP;
+            }
+        }
+        McuSegArgs sa;
+        std::memset(&sa, 0, sizeof(sa));
+        sa.coef = m.coef; sa.pic_stride = g.coef_per_pic; sa.cb_off = cb_off; sa.cr_off = cr_off;
+        sa.bw = g.bw; sa.bh = g.bh; sa.mx = g.mx; sa.my = g.my; sa.hs = g.hs; sa.vs = g.vs;
+        sa.seg_mcus = g.seg_mcus; sa.num_segs = g.num_segs; sa.num_segs_pad = g.num_segs_pad; sa.batch = n;
+        sa.huff_y = e->huff; sa.huff_c = c.huff;
+        sa.seg = m.seg;
+        sa.status = &m.scan_stats->status;
+        if (launch_mcu_segments(sa, stream)) return JPEGAMD_ERR_HIP;
+
+        ImageDesc is = iy;                                           // what run_finalize reads of it: the segments per picture and their length
+        is.num_segs = g.num_segs_pad; is.seg_tiles = kSegTiles;
+        const ScanTarget tgt = {m.hdr, m.hdr_len, 1, m.scan_stats, false, &m.seg};
+        if (run_finalize(e, is, outs_dev + first, out_capacity, out_sizes_dev + first, 1, stream, nullptr, n, false, &tgt)) return JPEGAMD_ERR_HIP;
+
+        McuTotalsArgs ta;
+        std::memset(&ta, 0, sizeof(ta));
+        ta.seg = m.seg;
+        ta.num_segs_pad = g.num_segs_pad; ta.prefix_len = m.hdr_len;
+        ta.last_of_call = first + n == count ? 1 : 0;
+        for (int i = 0; i < n; ++i) ta.out_size[i] = out_sizes_dev[first + i];
+        ta.out_capacity = out_capacity;
+        ta.pic = pic + (size_t)first * kPicStatWords;
+        ta.scan_stats = m.scan_stats; ta.stats = e->stats_dev;
+        if (launch_mcu_totals(ta, n, stream)) return JPEGAMD_ERR_HIP;
+    }
+    if (cev) HIP_TRY(hipEventRecord(cev[21], stream));
+    return enqueued(e, stream, count * g.num_segs_pad, cev != nullptr, true);
+}
+
+extern "C" int32_t jpegamd_encode_color_interleaved_batch_async(JpegAmdEncoder *e, const JpegAmdImage *imgs, int32_t count, int32_t subsampling,
+                                                                void *const *outs_dev, uint64_t out_capacity, uint64_t *const *out_sizes_dev,
+                                                                void *stream_) {
+    // the arguments first: nothing of the context is read before they are known to be good
+    if (!e || !imgs || !outs_dev || !out_sizes_dev || count < 1 || count > kMaxBatch) return JPEGAMD_ERR_ARG;
+    if (!sub_valid(subsampling)) return JPEGAMD_ERR_ARG;
+    const JpegAmdImage &g0 = imgs[0];
+    if (g0.channel_order != JPEGAMD_ORDER_BGR && g0.channel_order != JPEGAMD_ORDER_RGB) return JPEGAMD_ERR_ARG;
+    if (g0.width <= 0 || g0.height <= 0 || g0.width > 65535 || g0.height > 65535 || g0.row_stride < 3 * (int64_t)g0.width) return JPEGAMD_ERR_ARG;
+    PlaneSet ps = {};
+    for (int i = 0; i < count; ++i) {
+        const JpegAmdImage &g = imgs[i];
+        if (!outs_dev[i] || !out_sizes_dev[i] || !g.pixels) return JPEGAMD_ERR_ARG;
+        if (g.width != g0.width || g.height != g0.height || g.row_stride != g0.row_stride || (g.bottom_up != 0) != (g0.bottom_up != 0) ||
+            g.channel_order != g0.channel_order || g.quality != g0.quality)
+            return JPEGAMD_ERR_ARG;
+        ps.p[0][i] = (const uint8_t *)g.pixels;
+    }
+    return interleaved_batch(e, g0, ps, count, subsampling, outs_dev, out_capacity, out_sizes_dev, stream_);
+}
+
+extern "C" int32_t jpegamd_encode_ycbcr_interleaved_batch_async(JpegAmdEncoder *e, const JpegAmdYCbCrImage *imgs, int32_t count, int32_t subsampling,
+                                                                void *const *outs_dev, uint64_t out_capacity, void *const *out_sizes_dev,
+                                                                void *stream_) {
+    // the arguments first: nothing of the context is read before they are known to be good
+    if (imgs && count >= 1 && count <= kMaxBatch)
+        for (int i = 0; i < count; ++i) if (is_packed422(imgs[i].chroma_layout)) return JPEGAMD_ERR_ARG;      // packed 4:2:2 in one scan: a follow-up
+    JpegAmdImage g0;
+    PlaneSet ps;
+    YccSource ycc;
+    uint64_t *sizes[kMaxBatch];
+    if (int32_t rc = ycbcr_args(e, imgs, count, subsampling, JPEGAMD_RANGE_FULL, JPEGAMD_SAMPLES_8, JPEGAMD_MATRIX_BT601, outs_dev, out_sizes_dev,
+                                true, &g0, &ps, &ycc, sizes))
+        return rc;
+    return interleaved_batch(e, g0, ps, count, subsampling, outs_dev, out_capacity, sizes, stream_, &ycc);
 }
 
 // The capacity status is STICKY on the device: every kernel only ORs into it, and it is cleared here, after it was read.

@@ -126,8 +126,9 @@ constexpr int kMaxBatch = 32;           // images of one geometry coded by ONE l
 // in bytes).  `chroma`: the scan is coded with the chroma MfmaTables, the chroma code and Huffman tables and the chroma ZRL code.
 // `expand`: the samples are limited range (JPEGAMD_RANGE_LIMITED) and are mapped to full range behind the loader, Y by the luma map
 // and Cb / Cr by the chroma map; with a 16-bit layout it selects the limited-range narrowing.  launch_tile_transform has the list of
-// combinations that exist as kernels (stage taps and the stamped build: luma kSrcRgb / kSrcPlane and chroma kSrcPlane alone); any
-// other is hipErrorInvalidValue.
+// combinations that exist as kernels (the stamped build: luma kSrcRgb / kSrcPlane and chroma kSrcPlane alone; stage taps: luma
+// kSrcRgb / kSrcPlane, and -- the coefficient planes of an interleaved-MCU file -- chroma kSrcPlane / kSrcPair); any other is
+// hipErrorInvalidValue.
 constexpr int kSrcRgb = 0, kSrcPlane = 1, kSrcPx4 = 2, kSrcPlanar = 3, kSrcPair = 4, kSrcQuad = 5, kSrcPlane16 = 6, kSrcPair16 = 7;
 struct TileSource {
     int layout = kSrcRgb;
@@ -378,6 +379,41 @@ struct AppendBatchArgs {
     ScanStats *stats;                   // the context's record
 };
 int launch_append_scans_batch(const AppendBatchArgs &a, void *stream, void *const *ev = nullptr);
+
+// Interleaved-MCU colour files (jpegamd_encode_color_interleaved_batch_async, jpegamd_mcu.hip): ONE scan coded from coefficient
+// planes.  A picture's planes lie at coef + picture * pic_stride (int16 elements): Y [bh][bw][64] at 0, Cb and Cr [my][mx][64] at
+// cb_off / cr_off -- what the stage-tap build of k_tile_encode stores through tap_zz, zigzag order inside a block.  The MCU grid
+// is mx x my MCUs of hs x vs Y blocks, one Cb and one Cr block; Y blocks with bx >= bw or by >= bh are pad blocks.  Segment s of a
+// picture is the MCUs [s seg_mcus, (s + 1) seg_mcus) of the raster MCU order; every picture has num_segs_pad entries in the segment
+// arrays -- num_segs rounded up to kSegGroup with EMPTY segments (no bits), so that k_finalize's four-at-a-time reads of the
+// per-segment arrays stay aligned for every picture of a batch.
+constexpr int mcu_seg_mcus(int hs, int vs) { return kSegBlocks / (hs * vs + 2); }     // 85 / 42 / 64: at most 256 blocks per segment
+static_assert(mcu_seg_mcus(1, 1) * 3 <= kSegBlocks && mcu_seg_mcus(2, 2) * 6 <= kSegBlocks && mcu_seg_mcus(2, 1) * 4 <= kSegBlocks &&
+              kSegBlocks == kTileBlocks * kSegTiles, "a segment of MCUs fits seg_cap_words(kSegTiles)");
+struct McuSegArgs {
+    const int16_t *coef;
+    uint64_t pic_stride, cb_off, cr_off;
+    int32_t bw, bh, mx, my, hs, vs;
+    int32_t seg_mcus, num_segs, num_segs_pad, batch;
+    const uint32_t *huff_y, *huff_c;    // [272] (len << 16) | code: AC by run/size symbol, then 16 DC sizes
+    SegArrays seg;                      // the interleaved path's own (words_stride = seg_cap_words(kSegTiles)); no group aggregates
+    uint32_t *status;                   // ScanStats::status: bit 1 = a count that did not fit its 16 bits
+};
+int launch_mcu_segments(const McuSegArgs &a, void *stream);
+// k_mcu_totals, behind k_finalize: per picture of the launch the sums of its segments, its stuffed bytes (from its size) and its
+// exact-order fallbacks (pic: k_picture_stats' words of THESE pictures) ADDED to the context's record, whose sums the caller zeroed;
+// the picture's size word set to 0 when the file did not fit; scan_stats->status (k_finalize's) ORed into the context's.
+struct McuTotalsArgs {
+    SegArrays seg;
+    int32_t num_segs_pad, prefix_len;
+    int32_t last_of_call;               // the launch's last picture is the call's last: its size is what finish reports
+    uint64_t *out_size[kMaxBatch];
+    uint64_t out_capacity;
+    const unsigned long long *pic;
+    const ScanStats *scan_stats;
+    ScanStats *stats;
+};
+int launch_mcu_totals(const McuTotalsArgs &a, int batch, void *stream, void *const *ev = nullptr);
 
 // ---- host-side constant derivation (quant_consts.cpp) ----------------------------------
 void quant_table_for_quality(int quality, uint8_t table[64]);

@@ -1344,6 +1344,7 @@ constexpr Variant kVariants[] = {
     kVariant<false, kSrcPair, false, true>, kVariant<false, kSrcQuad, true, true>,
     kVariant<false, kSrcPlane16>, kVariant<false, kSrcPlane16, true>, kVariant<false, kSrcPair16, true>,           // 10-bit samples in 16-bit words, either depth map
     kVariant<false, kSrcPlane16, false, true>, kVariant<false, kSrcPlane16, true, true>, kVariant<false, kSrcPair16, true, true>,
+    kVariant<true, kSrcPlane, true>, kVariant<true, kSrcPair, true>,                                               // chroma coefficient planes of an interleaved-MCU file (tap_zz)
 #endif
     kVariant<false, kSrcPlane>, kVariant<false, kSrcPlane, true>, kVariant<true, kSrcPlane>, kVariant<true, kSrcRgb>, kVariant<false, kSrcRgb>,
 };

@@ -121,6 +121,9 @@ def _load() -> C.CDLL:
         "jpegamd_encode_ycbcr_range_batch_async": (i32, [vp, C.POINTER(YCbCrImage), i32, i32, i32, C.POINTER(C.c_void_p), u64, C.POINTER(C.c_void_p), vp]),
         "jpegamd_encode_ycbcr_samples_batch_async": (i32, [vp, C.POINTER(YCbCrImage), i32, i32, i32, i32, C.POINTER(C.c_void_p), u64, C.POINTER(C.c_void_p), vp]),
         "jpegamd_encode_ycbcr_matrix_batch_async": (i32, [vp, C.POINTER(YCbCrImage), i32, i32, i32, i32, i32, C.POINTER(C.c_void_p), u64, C.POINTER(C.c_void_p), vp]),
+        "jpegamd_encode_color_interleaved_batch_async": (i32, [vp, C.POINTER(Image), i32, i32, C.POINTER(C.c_void_p), u64, C.POINTER(C.c_void_p), vp]),
+        "jpegamd_encode_ycbcr_interleaved_batch_async": (i32, [vp, C.POINTER(YCbCrImage), i32, i32, C.POINTER(C.c_void_p), u64, C.POINTER(C.c_void_p), vp]),
+        "jpegamd_max_jfif_bytes_interleaved": (u64, [i32, i32, i32]),
         "jpegamd_debug_matrix_coeffs": (i32, [i32, vp]),
         "jpegamd_debug_ycbcr_matrix_planes": (i32, [vp, C.POINTER(YCbCrImage), i32, i32, i32, i32, i32, vp, vp, vp, vp]),
         "jpegamd_debug_chroma_groups": (i32, [i32, i32, i32, i32, i32, i32, i32, vp]),
@@ -140,7 +143,8 @@ def _load() -> C.CDLL:
         if name in ("jpegamd_encoder_set_pipeline", "jpegamd_gather_streams", "jpegamd_debug_mfma_offsets", "jpegamd_encode_color_batch_async",
                     "jpegamd_debug_chroma_groups", "jpegamd_debug_ycbcr_sources", "jpegamd_encode_planar_batch_async", "jpegamd_encode_ycbcr_batch_async",
                     "jpegamd_encode_ycbcr_range_batch_async", "jpegamd_encode_ycbcr_samples_batch_async", "jpegamd_encode_ycbcr_matrix_batch_async",
-                    "jpegamd_debug_matrix_coeffs", "jpegamd_debug_ycbcr_matrix_planes") and os.environ.get("JPEGAMD_LIB") and not hasattr(lib, name):
+                    "jpegamd_debug_matrix_coeffs", "jpegamd_debug_ycbcr_matrix_planes", "jpegamd_encode_color_interleaved_batch_async",
+                    "jpegamd_encode_ycbcr_interleaved_batch_async", "jpegamd_max_jfif_bytes_interleaved") and os.environ.get("JPEGAMD_LIB") and not hasattr(lib, name):
             continue                                              # (A/B tooling: a variant build of an older round)
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = res, args
@@ -157,7 +161,8 @@ EXPORTED = ("jpegamd_encoder_create jpegamd_encoder_destroy jpegamd_max_jfif_byt
             "jpegamd_max_jfif_bytes_color jpegamd_encode_color_async jpegamd_encode_bmp_memory_color jpegamd_debug_chroma_quant_table "
             "jpegamd_debug_chroma_mfma_consts jpegamd_debug_chroma_group_thresholds jpegamd_debug_color_profile jpegamd_encode_color_batch_async "
             "jpegamd_encode_planar_batch_async jpegamd_encode_ycbcr_batch_async jpegamd_encode_ycbcr_range_batch_async "
-            "jpegamd_encode_ycbcr_samples_batch_async jpegamd_encode_ycbcr_matrix_batch_async").split()
+            "jpegamd_encode_ycbcr_samples_batch_async jpegamd_encode_ycbcr_matrix_batch_async "
+            "jpegamd_encode_color_interleaved_batch_async jpegamd_encode_ycbcr_interleaved_batch_async jpegamd_max_jfif_bytes_interleaved").split()
 
 
 def quant_table(quality: int = 50):
@@ -276,6 +281,21 @@ def max_jfif_bytes_color(width: int, height: int, subsampling: int = SUBSAMPLE_4
     return int(lib.jpegamd_max_jfif_bytes_color(width, height, subsampling))
 
 
+def max_jfif_bytes_interleaved(width: int, height: int, subsampling: int = SUBSAMPLE_420) -> int:
+    """Upper bound on the bytes of a colour file with ONE scan of interleaved MCUs (pad blocks counted); 0 for bad arguments."""
+    return int(lib.jpegamd_max_jfif_bytes_interleaved(width, height, subsampling))
+
+
+SCANS = ("separate", "interleaved")
+
+
+def _scan(scan) -> bool:
+    """"separate" / "interleaved" -> is it the interleaved file; anything else is a ValueError."""
+    if not isinstance(scan, str) or scan not in SCANS:
+        raise ValueError(f"scan must be one of {SCANS}, not {scan!r}")
+    return scan == "interleaved"
+
+
 def encode_bmp_bytes_color(bmp: bytes, quality: int = 0, subsampling: int = SUBSAMPLE_420) -> bytes:
     """BMP file bytes -> colour JFIF file bytes (YCbCr, three scans) through the device."""
     img, _ = parse_bmp(bmp)
@@ -290,12 +310,15 @@ def encode_bmp_bytes_color(bmp: bytes, quality: int = 0, subsampling: int = SUBS
 _tensor_encoders = {}
 
 
-def encode_tensor(t, quality: int = 0, subsampling: int = SUBSAMPLE_420, layout=None) -> bytes:
+def encode_tensor(t, quality: int = 0, subsampling: int = SUBSAMPLE_420, layout=None, scan: str = "separate") -> bytes:
     """A uint8 DEVICE tensor -> JFIF file bytes: [H, W] a grayscale file (the tensor is the luma), [H, W, 3] (R, G, B) a colour file.
     Rows may be strided (t.stride(0) bytes apart); pixels within a row must be packed.  Runs on the tensor's device and the
     current stream; one encoder context per device is kept and grown as needed.
-    `layout` names how the picture is stored, as for encode_tensor_batch: "chw" [3, H, W], "rgba" / "bgra" [H, W, 4], "hwc" [H, W, 3]."""
+    `layout` names how the picture is stored, as for encode_tensor_batch: "chw" [3, H, W], "rgba" / "bgra" [H, W, 4], "hwc" [H, W, 3].
+    scan="interleaved": the colour file with ONE scan of interleaved MCUs, as for encode_tensor_batch ([H, W, 3] alone)."""
     import torch
+    if _scan(scan):
+        return encode_tensor_batch(t, quality, subsampling, "hwc" if layout is None else layout, _single=True, scan=scan)[0]
     if layout is not None:
         return encode_tensor_batch(t, quality, subsampling, layout, _single=True)[0]
     if t.dtype != torch.uint8 or not t.is_cuda:
@@ -426,7 +449,8 @@ def _named_layout(t, layout, single: bool):
     return n, h, w, (t.stride(1) if h > 1 else c * w), order, (lambda i: t[i].data_ptr()), [t]
 
 
-def encode_tensor_batch(t, quality: int = 0, subsampling: int = SUBSAMPLE_420, layout=None, _single: bool = False) -> list:
+def encode_tensor_batch(t, quality: int = 0, subsampling: int = SUBSAMPLE_420, layout=None, _single: bool = False,
+                        scan: str = "separate") -> list:
     """A uint8 DEVICE tensor of N pictures -> N JFIF files: [N, H, W, 3] (R, G, B) colour files through
     jpegamd_encode_color_batch_async, [N, H, W] grayscale files through jpegamd_encode_batch_async.  Pictures may be strided
     (t[::2]), pixels within a row must be packed.  Batches of more than MAX_BATCH pictures go as several calls of at most
@@ -435,13 +459,23 @@ def encode_tensor_batch(t, quality: int = 0, subsampling: int = SUBSAMPLE_420, l
     `layout` names another storage, read where it lies (no repacking): "chw" [N, 3, H, W] -- or a sequence of three [N, H, W]
     tensors, the R, G and B planes -- through jpegamd_encode_planar_batch_async (rows may be strided, the planes of a picture
     share one row stride, any plane stride; subsampling 0 gives grayscale files); "rgba" / "bgra" [N, H, W, 4], the fourth byte
-    ignored; "hwc" the explicit name of [N, H, W, 3].  The files are those of the same R, G, B values as [N, H, W, 3]."""
+    ignored; "hwc" the explicit name of [N, H, W, 3].  The files are those of the same R, G, B values as [N, H, W, 3].
+    scan="interleaved": colour files with ONE scan of interleaved MCUs (jpegamd_encode_color_interleaved_batch_async) -- what
+    Motion-JPEG containers and hardware decoders take -- for [N, H, W, 3] (layout None or "hwc") and the three colour subsamplings;
+    every other combination is a ValueError.  They decode to the same pixels as the scan="separate" files."""
     import torch
+    interleaved = _scan(scan)
+    if interleaved and layout not in (None, "hwc"):
+        raise ValueError(f'scan="interleaved" takes layout="hwc" (or None) alone, not {layout!r}')
+    if interleaved and subsampling not in (SUBSAMPLE_444, SUBSAMPLE_420, SUBSAMPLE_422):
+        raise ValueError('scan="interleaved" needs SUBSAMPLE_444, SUBSAMPLE_420 or SUBSAMPLE_422')
     if layout is None:
         n, h, w, stride, order = _batch_tensor_layout(t)
         ptr, tensors = (lambda i: t[i].data_ptr()), [t]
     else:
         n, h, w, stride, order, ptr, tensors = _named_layout(t, layout, _single)
+    if interleaved and order != ORDER_RGB:
+        raise ValueError('scan="interleaved" takes colour pictures [N, H, W, 3] alone')
     if any(not x.is_cuda or x.device != tensors[0].device for x in tensors):
         raise ValueError("encode_tensor_batch needs a device tensor")
     device = tensors[0].device
@@ -459,6 +493,8 @@ def encode_tensor_batch(t, quality: int = 0, subsampling: int = SUBSAMPLE_420, l
             enc = Encoder(mw, mh)
             _tensor_encoders[dev] = (enc, mw, mh)
         cap = max_jfif_bytes(w, h) if gray else max_jfif_bytes_color(w, h, subsampling)
+        if interleaved:
+            cap = max_jfif_bytes_interleaved(w, h, subsampling)
         out = torch.empty((per, cap), dtype=torch.uint8, device=device)
         sizes = torch.zeros(per, dtype=torch.int64, device=device)
         stream = torch.cuda.current_stream(device).cuda_stream
@@ -466,7 +502,10 @@ def encode_tensor_batch(t, quality: int = 0, subsampling: int = SUBSAMPLE_420, l
             k = min(MAX_BATCH, n - b0)
             outs = [out[i].data_ptr() for i in range(k)]
             size_ptrs = [sizes.data_ptr() + 8 * i for i in range(k)]
-            if order is None:
+            if interleaved:
+                imgs = [Encoder.image(ptr(b0 + i), w, h, stride, bottom_up=False, channel_order=order, quality=quality) for i in range(k)]
+                enc.encode_color_interleaved_batch_async(imgs, subsampling, outs, cap, size_ptrs, stream)
+            elif order is None:
                 imgs = [Encoder.planar_image(ptr(b0 + i), w, h, stride, bottom_up=False, quality=quality) for i in range(k)]
                 enc.encode_planar_batch_async(imgs, subsampling, outs, cap, size_ptrs, stream)
             else:
@@ -554,7 +593,7 @@ def _matrix(matrix) -> int:
 
 
 def encode_ycbcr_batch(y, cb, cr=None, quality: int = 0, subsampling: int = SUBSAMPLE_420, order: str = "cbcr",
-                       sample_range: str = "full", matrix: str = "bt601") -> list:
+                       sample_range: str = "full", matrix: str = "bt601", scan: str = "separate") -> list:
     """N pictures whose samples already ARE Y, Cb and Cr (JFIF full range; no range or matrix conversion is done) -> N colour JFIF
     files through jpegamd_encode_ycbcr_batch_async, read where they lie: no RGB detour, no chroma-plane pass.
     sample_range="limited": the samples are video range (Y 16..235, Cb / Cr 16..240, as decoders deliver them) and are expanded to
@@ -572,18 +611,23 @@ def encode_ycbcr_batch(y, cb, cr=None, quality: int = 0, subsampling: int = SUBS
         cbcr = f[H:].view(H // 2, W // 2, 2).unsqueeze(0)           # [1, H / 2, W / 2, 2]
         jpegamd.encode_ycbcr_batch(y, cbcr)
 
-    and a stack of frames [N, 3 * H // 2, W] slices the same way: f[:, :H] and f[:, H:].unflatten(2, (W // 2, 2))."""
+    and a stack of frames [N, 3 * H // 2, W] slices the same way: f[:, :H] and f[:, H:].unflatten(2, (W // 2, 2)).
+    scan="interleaved": the files with ONE scan of interleaved MCUs (jpegamd_encode_ycbcr_interleaved_batch_async), for
+    sample_range="full" and matrix="bt601" alone; anything else is a ValueError."""
     rng, mat = _sample_range(sample_range), _matrix(matrix)
+    interleaved = _scan(scan)
+    if interleaved and (rng != RANGE_FULL or mat != MATRIX_BT601):
+        raise ValueError('scan="interleaved" takes sample_range="full" and matrix="bt601" alone')
     n, h, w, y_stride, c_stride, layout = _ycbcr_layout(y, cb, cr, subsampling, order)
     tensors = [y, cb] + ([cr] if cr is not None else [])
     if any(not x.is_cuda or x.device != y.device for x in tensors):
         raise ValueError("encode_ycbcr_batch needs device tensors on one device")
     return _encode_ycbcr_images(y.device, n, h, w, subsampling, lambda i: Encoder.ycbcr_image(
-        y[i].data_ptr(), cb[i].data_ptr(), cr[i].data_ptr() if cr is not None else 0, w, h, y_stride, c_stride, layout, quality), rng, matrix=mat)
+        y[i].data_ptr(), cb[i].data_ptr(), cr[i].data_ptr() if cr is not None else 0, w, h, y_stride, c_stride, layout, quality), rng, matrix=mat, interleaved=interleaved)
 
 
 def _encode_ycbcr_images(device, n, h, w, subsampling, image, sample_range: int = RANGE_FULL, sample_format: int = SAMPLES_8,
-                         matrix: int = MATRIX_BT601):
+                         matrix: int = MATRIX_BT601, interleaved: bool = False):
     """`n` YCbCr pictures of one geometry, picture i described by image(i), through the per-device context in calls of at most
     MAX_BATCH -> their files."""
     import torch
@@ -599,7 +643,7 @@ def _encode_ycbcr_images(device, n, h, w, subsampling, image, sample_range: int 
                 enc.close()
             enc = Encoder(mw, mh)
             _tensor_encoders[dev] = (enc, mw, mh)
-        cap = max_jfif_bytes_color(w, h, subsampling)
+        cap = max_jfif_bytes_interleaved(w, h, subsampling) if interleaved else max_jfif_bytes_color(w, h, subsampling)
         out = torch.empty((per, cap), dtype=torch.uint8, device=device)
         sizes = torch.zeros(per, dtype=torch.int64, device=device)
         stream = torch.cuda.current_stream(device).cuda_stream
@@ -608,8 +652,11 @@ def _encode_ycbcr_images(device, n, h, w, subsampling, image, sample_range: int 
             outs = [out[i].data_ptr() for i in range(k)]
             size_ptrs = [sizes.data_ptr() + 8 * i for i in range(k)]
             imgs = [image(b0 + i) for i in range(k)]
-            enc.encode_ycbcr_batch_async(imgs, subsampling, outs, cap, size_ptrs, stream, sample_range, sample_format=sample_format,
-                                         matrix=matrix)
+            if interleaved:
+                enc.encode_ycbcr_interleaved_batch_async(imgs, subsampling, outs, cap, size_ptrs, stream)
+            else:
+                enc.encode_ycbcr_batch_async(imgs, subsampling, outs, cap, size_ptrs, stream, sample_range, sample_format=sample_format,
+                                             matrix=matrix)
             enc.finish()
             got = sizes[:k].cpu().tolist()
             files += [bytes(out[i, :got[i]].cpu().numpy().tobytes()) for i in range(k)]
@@ -826,6 +873,28 @@ class Encoder:
         rc = lib.jpegamd_encode_color_batch_async(self._h, arr, n, int(subsampling), outs, out_cap, sizes, C.c_void_p(stream))
         if rc:
             raise JpegAmdError(rc, "jpegamd_encode_color_batch_async")
+
+    def encode_color_interleaved_batch_async(self, imgs, subsampling: int, out_ptrs, out_cap: int, size_ptrs, stream: int = 0):
+        """The colour files of `len(imgs)` RGB / BGR pictures of one geometry (<= MAX_BATCH) with ONE scan of interleaved MCUs each
+        (jpegamd_encode_color_interleaved_batch_async); the context as for encode_color_batch_async."""
+        n = len(imgs)
+        arr = (Image * n)(*imgs)
+        outs = (C.c_void_p * n)(*[C.c_void_p(p) for p in out_ptrs])
+        sizes = (C.c_void_p * n)(*[C.c_void_p(p) for p in size_ptrs])
+        rc = lib.jpegamd_encode_color_interleaved_batch_async(self._h, arr, n, int(subsampling), outs, out_cap, sizes, C.c_void_p(stream))
+        if rc:
+            raise JpegAmdError(rc, "jpegamd_encode_color_interleaved_batch_async")
+
+    def encode_ycbcr_interleaved_batch_async(self, imgs, subsampling: int, out_ptrs, out_cap: int, size_ptrs, stream: int = 0):
+        """The same files from 8-bit full-range BT.601 YCbCr pictures in planes or byte pairs
+        (jpegamd_encode_ycbcr_interleaved_batch_async)."""
+        n = len(imgs)
+        arr = (YCbCrImage * n)(*imgs)
+        outs = (C.c_void_p * n)(*[C.c_void_p(p) for p in out_ptrs])
+        sizes = (C.c_void_p * n)(*[C.c_void_p(p) for p in size_ptrs])
+        rc = lib.jpegamd_encode_ycbcr_interleaved_batch_async(self._h, arr, n, int(subsampling), outs, out_cap, sizes, C.c_void_p(stream))
+        if rc:
+            raise JpegAmdError(rc, "jpegamd_encode_ycbcr_interleaved_batch_async")
 
     def color_profile(self, slot: int):
         """Per-kernel ns of a profiled colour encode: planes, (tile, merge, finalize) x Y / Cb / Cr, append."""

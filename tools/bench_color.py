@@ -36,6 +36,10 @@ With --layout {hwc,chw,rgba} (and --batch N, default 8) the pictures are device 
 events on the stream; --rounds R medians of --steps calls each are reported, with their spread (max - min).  --repack (chw only)
 also times the route without the planar entry, in the same run and alternating with the direct one: permute(0, 2, 3, 1) into a
 preallocated [N, H, W, 3] tensor, then the packed batch entry.
+
+--scan interleaved (with --batch N, default 8; sources rgb, i420, nv12, i422 at full range, BT.601) sends the batch loop through the
+one-scan entries (jpegamd_encode_color_interleaved_batch_async / jpegamd_encode_ycbcr_interleaved_batch_async); the line then carries
+"scan".  The whole call is timed (ns_total); the per-kernel split comes from a kernel trace of the same command.
 """
 from __future__ import annotations
 
@@ -72,6 +76,8 @@ def main() -> None:
     ap.add_argument("--layout", choices=("hwc", "chw", "rgba"), default=None, help="device tensors stored this way, read where they lie")
     ap.add_argument("--rounds", type=int, default=5, help="--layout: medians taken (each of --steps calls)")
     ap.add_argument("--repack", action="store_true", help="--layout chw: also time permute + packed encode")
+    ap.add_argument("--scan", choices=("separate", "interleaved"), default="separate",
+                    help="interleaved: the batch loop goes through the one-scan entries (rgb, i420, nv12, i422; full range, bt601)")
     a = ap.parse_args()
     import torch                          # (the device runtime comes up through torch first, as in bench.py)
     if not torch.cuda.is_available():
@@ -99,7 +105,10 @@ def main() -> None:
         sys.exit("--matrix bt709 --convert with p010 / i010 is written for --range full (the torch route narrows by a shift)")
     if a.narrow and not any(s in ("p010", "i010") for s in sources):
         sys.exit("--narrow needs --source p010 or i010")
-    if a.batch is not None or sources != ["rgb"]:
+    if a.scan == "interleaved" and (a.layout is not None or a.sample_range != "full" or a.matrix != "bt601" or
+                                    any(s in ("yuyv", "p010", "i010") for s in sources)):
+        sys.exit("--scan interleaved takes --source rgb, i420, nv12, i422 at --range full --matrix bt601")
+    if a.batch is not None or sources != ["rgb"] or a.scan == "interleaved":
         run_batch(a, jpegamd, torch, dev, sources)
         return
     bmp = jpegamd.synth_bmp(w, h, 1, a.kind, 0)
@@ -234,12 +243,17 @@ def run_batch(a, jpegamd, torch, dev, sources=("rgb",)) -> None:
         lut_c = torch.tensor([(255 * (min(max(v, 16), 240) - 16) + 112) // 224 for v in range(256)], dtype=torch.uint8, device=dev)
     for source, sub, name, tensors, describe in runs:
         ycc = describe(tensors) if describe else None
-        cap = jpegamd.max_jfif_bytes_color(w, h, sub)
+        one_scan = a.scan == "interleaved"
+        cap = jpegamd.max_jfif_bytes_interleaved(w, h, sub) if one_scan else jpegamd.max_jfif_bytes_color(w, h, sub)
         outs = [torch.empty(cap, dtype=torch.uint8, device=dev) for _ in range(n)]
         sizes = torch.zeros(n, dtype=torch.int64, device=dev)
         out_ptrs = [o.data_ptr() for o in outs]
         size_ptrs = [sizes.data_ptr() + 8 * i for i in range(n)]
-        if ycc is None:
+        if one_scan and ycc is None:
+            call = lambda: enc.encode_color_interleaved_batch_async(descs, sub, out_ptrs, cap, size_ptrs, stream)
+        elif one_scan:
+            call = lambda: enc.encode_ycbcr_interleaved_batch_async(ycc, sub, out_ptrs, cap, size_ptrs, stream)
+        elif ycc is None:
             call = lambda: enc.encode_color_batch_async(descs, sub, out_ptrs, cap, size_ptrs, stream)
         else:
             kw = {"sample_range": jpegamd.RANGE_LIMITED} if limited else {}
@@ -262,6 +276,8 @@ def run_batch(a, jpegamd, torch, dev, sources=("rgb",)) -> None:
                 "steps": a.steps, "bytes": sizes.cpu().tolist(), "entropy_bits": st.entropy_bits,
                 "ns_total_median": int(t), "us_per_picture": round(t / n / 1000, 1),
                 "gpixels_per_s": round(n * w * h / t, 2)}
+        if one_scan:
+            line["scan"] = "interleaved"
         if limited:
             line["range"] = "limited"
         if bt709 and ycc is not None:
