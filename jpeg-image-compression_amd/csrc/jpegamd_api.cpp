@@ -30,10 +30,23 @@ using namespace jpegamd;
         }                                                                                       \
     } while (0)
 
+// What a context created for max_w x max_h holds: the bounds every launch on it is checked against.
+struct CtxLimits {
+    int max_segs, max_tiles, max_wgs;
+    size_t words_cap;                   // words of seg.words
+};
+
+// What a header kept on the device was built for, and its length.  Plain data: all zero means "nothing cached" (no picture is 0 wide).
+struct HeaderCache {
+    int w, h, q, sub, len;
+    bool matches(int w_, int h_, int q_, int sub_) const { return w == w_ && h == h_ && q == q_ && sub == sub_; }
+    void set(int w_, int h_, int q_, int sub_, int len_) { w = w_; h = h_; q = q_; sub = sub_; len = len_; }
+};
+
 struct JpegAmdEncoder {
     int device = -1;
-    int max_w = 0, max_h = 0, max_segs = 0, max_tiles = 0;
-    size_t words_cap = 0;               // words of seg.words
+    int max_w = 0, max_h = 0;
+    CtxLimits lim = {};
     // device scratch, sized once for max_w x max_h
     SegArrays seg = {};
     uint32_t *huff = nullptr;
@@ -45,7 +58,6 @@ struct JpegAmdEncoder {
     uint32_t *tile_head = nullptr, *tile_over = nullptr, *tile_ctr = nullptr, *code_tab = nullptr;
     int ctr_set = 0;                    // which half of tile_ctr the next k_tile_encode launch uses
     uint32_t *desc = nullptr;           // k_stitch's hand-off granules: max_wgs x 16 bytes, then max_wgs x 8 counts in full
-    int max_wgs = 0;
     uint32_t epoch = 0;                 // 1 .. 16383: tag of the last k_stitch launch's granules
     int pipeline = JPEGAMD_PIPELINE_AUTO;
     int poison_tile = -1;               // jpegamd_debug_poison_tile_record: the next encode overwrites this tile's record word 0 ...
@@ -55,7 +67,7 @@ struct JpegAmdEncoder {
     // cached constants
     int cur_quality = -1;
     uint8_t qtable[64];
-    int prefix_w = -1, prefix_h = -1, prefix_q = -1;
+    HeaderCache prefix_for = {};        // what `prefix` holds (no subsampling: 0)
     // profiling: a ring of event quadruples so callers can time many async encodes and read
     // the per-kernel durations after ONE synchronisation
     struct EventSet {
@@ -84,8 +96,7 @@ struct JpegAmdEncoder {
         uint8_t *scans = nullptr;           // the Cb part, then the Cr part (each scan_cap bytes)
         size_t planes_cap = 0, scan_cap = 0;
         int cur_quality = -1;
-        int hdr_w = -1, hdr_h = -1, hdr_q = -1, hdr_sub = -1;
-        int hdr_len = 0;
+        HeaderCache hdr_for = {};           // what the prefix in `hdr` holds
         // colour batches (jpegamd_encode_color_batch_async), sized for the planes and scans of the largest batch so far
         uint8_t *bmeta = nullptr;           // ScanStats [kBatchLaunches], u64 pic [kMaxBatch][kPicStatWords], y_size [kMaxBatch], c_size [2 kMaxBatch]
         uint8_t *bplanes = nullptr, *bscans = nullptr;
@@ -100,8 +111,7 @@ struct JpegAmdEncoder {
         size_t segs_cap = 0;
         uint8_t *hdr = nullptr;             // the prefix with the three-component SOS
         ScanStats *scan_stats = nullptr;    // k_finalize's record of the call
-        int hdr_w = -1, hdr_h = -1, hdr_q = -1, hdr_sub = -1;
-        int hdr_len = 0;
+        HeaderCache hdr_for = {};           // what `hdr` holds
     } mcu;
 };
 
@@ -193,28 +203,37 @@ extern "C" int32_t jpegamd_debug_chroma_group_thresholds(int32_t quality, float 
 // The colour subsamplings: 4:4:4, 4:2:0 (chroma halved both ways) and 4:2:2 (halved along the row alone).
 static bool sub_valid(int sub) { return sub == JPEGAMD_SUBSAMPLE_444 || sub == JPEGAMD_SUBSAMPLE_420 || sub == JPEGAMD_SUBSAMPLE_422; }
 static int chroma_mode(int sub) { return sub == JPEGAMD_SUBSAMPLE_420 ? kChromaMode420 : (sub == JPEGAMD_SUBSAMPLE_422 ? kChromaMode422 : kChromaMode444); }
-static void chroma_dims(int w, int h, int sub, int *cw, int *ch) {
-    *cw = sub == JPEGAMD_SUBSAMPLE_444 ? w : (w + 1) / 2;
-    *ch = sub == JPEGAMD_SUBSAMPLE_420 ? (h + 1) / 2 : h;
+static size_t round_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+// A chroma plane of a w x h picture: cw x ch samples; in scratch its rows lie `pitch` bytes apart, its planes `plane_bytes`.
+struct ChromaGeom {
+    int cw, ch, pitch;
+    size_t plane_bytes;
+};
+static ChromaGeom chroma_geom(int w, int h, int sub) {
+    ChromaGeom c;
+    c.cw = sub == JPEGAMD_SUBSAMPLE_444 ? w : (w + 1) / 2;
+    c.ch = sub == JPEGAMD_SUBSAMPLE_420 ? (h + 1) / 2 : h;
+    c.pitch = (int)(((int64_t)c.cw + 3) / 4 * 4);      // (64-bit: the size bounds take any positive width)
+    c.plane_bytes = round_up((size_t)c.pitch * (size_t)c.ch, 256);
+    return c;
 }
 static bool is_packed422(int layout) { return layout == JPEGAMD_CHROMA_YUYV || layout == JPEGAMD_CHROMA_UYVY; }
 
-// One scan of nb blocks at the chroma worst case, every byte stuffed, its flush byte.
-static uint64_t scan_bound(uint64_t nb) { return 2 * ((nb * kMaxBlockBitsColor + 7) / 8 + 1); }
+// One scan of nb blocks at the worst-case bit count (kMaxBlockBits, or kMaxBlockBitsColor), every byte stuffed, its flush byte.
+static uint64_t scan_bound(uint64_t nb, uint64_t block_bits) { return 2 * ((nb * block_bits + 7) / 8 + 1); }
 static uint64_t blocks_of(int w, int h) { return (uint64_t)((w + 7) / 8) * (uint64_t)((h + 7) / 8); }
 
 extern "C" uint64_t jpegamd_max_jfif_bytes_color(int32_t width, int32_t height, int32_t subsampling) {
     if (width <= 0 || height <= 0 || !sub_valid(subsampling)) return 0;
-    int cw, ch;
-    chroma_dims(width, height, subsampling, &cw, &ch);
-    return kColorPrefixMax + 2 * kSosBytes + 2 + scan_bound(blocks_of(width, height)) + 2 * scan_bound(blocks_of(cw, ch)) + 16;
+    const ChromaGeom cg = chroma_geom(width, height, subsampling);
+    return kColorPrefixMax + 2 * kSosBytes + 2 + scan_bound(blocks_of(width, height), kMaxBlockBitsColor) +
+           2 * scan_bound(blocks_of(cg.cw, cg.ch), kMaxBlockBitsColor) + 16;
 }
 
 extern "C" uint64_t jpegamd_max_jfif_bytes(int32_t width, int32_t height) {
     if (width <= 0 || height <= 0) return 0;
-    const uint64_t nb = (uint64_t)((width + 7) / 8) * (uint64_t)((height + 7) / 8);
     // every block at the worst-case bit count, every byte stuffed, + container
-    return JPEGAMD_JFIF_PREFIX_BYTES + 2 + 2 * ((nb * kMaxBlockBits + 7) / 8 + 1) + 16;
+    return JPEGAMD_JFIF_PREFIX_BYTES + 2 + scan_bound(blocks_of(width, height), kMaxBlockBits) + 16;
 }
 
 // Allocation failures free everything allocated so far (jpegamd_encoder_destroy tolerates a half-built context).
@@ -229,11 +248,6 @@ extern "C" uint64_t jpegamd_max_jfif_bytes(int32_t width, int32_t height) {
         }                                                                                       \
     } while (0)
 
-// What a context created for max_w x max_h holds: the bounds every launch on it is checked against.
-struct CtxLimits {
-    int max_segs, max_tiles, max_wgs;
-    size_t words_cap;
-};
 static CtxLimits context_limits(int max_w, int max_h) {
     CtxLimits l;
     l.max_segs = segs_for(max_w, max_h, nullptr, nullptr, nullptr);
@@ -244,6 +258,33 @@ static CtxLimits context_limits(int max_w, int max_h) {
     l.words_cap = (w8 > w16 ? w8 : w16) + seg_cap_words(kSegTilesBatch);
     l.max_wgs = l.max_segs + 2;                                    // (a picture never has more workgroups than segments)
     return l;
+}
+
+// The per-segment arrays of `segs` segments whose strings take `words` words in all; `groups`: with the group aggregates
+// (k_segment_merge writes them; a path that fills its segments itself has none).
+static int32_t alloc_seg_arrays(SegArrays *s, size_t segs, size_t words, bool groups) {
+    const size_t n = segs + 16;                                   // k_finalize reads the per-segment arrays four at a time
+    HIP_TRY(hipMalloc((void **)&s->words, words * sizeof(uint32_t)));
+    s->words_stride = kSegCapWords;
+    HIP_TRY(hipMalloc((void **)&s->bits, n * sizeof(uint32_t)));
+    HIP_TRY(hipMalloc((void **)&s->syms, n * sizeof(uint32_t)));
+    HIP_TRY(hipMalloc((void **)&s->exact, n * sizeof(uint32_t)));
+    HIP_TRY(hipMalloc((void **)&s->edge, n * sizeof(uint32_t)));
+    HIP_TRY(hipMalloc((void **)&s->ffin, n * 8 * sizeof(uint16_t)));
+    if (groups) {
+        HIP_TRY(hipMalloc((void **)&s->grp_bits, (n / kSegGroup + 2) * sizeof(uint32_t)));
+        HIP_TRY(hipMalloc((void **)&s->grp_ff, (n / kSegGroup + 2) * 8 * sizeof(uint32_t)));
+    }
+    return JPEGAMD_OK;
+}
+static void free_seg_arrays(SegArrays *s) {
+    hipFree(s->words); hipFree(s->bits); hipFree(s->syms); hipFree(s->exact); hipFree(s->edge); hipFree(s->ffin); hipFree(s->grp_bits); hipFree(s->grp_ff);
+    *s = SegArrays{};
+}
+
+// Every event of the profiling ring.
+static void destroy_ring_events(JpegAmdEncoder *e) {
+    for (auto &set : e->ring) { for (auto &ev : set.ev) if (ev) hipEventDestroy(ev); for (auto &ev : set.cev) if (ev) hipEventDestroy(ev); }
 }
 
 extern "C" int32_t jpegamd_encoder_create(JpegAmdEncoder **out, int32_t max_width, int32_t max_height) {
@@ -262,35 +303,22 @@ extern "C" int32_t jpegamd_encoder_create(JpegAmdEncoder **out, int32_t max_widt
     if (!e->tables_host) { delete e; return JPEGAMD_ERR_HIP; }
     HIP_TRY_CREATE(hipGetDevice(&e->device));
     e->max_w = max_width; e->max_h = max_height;
-    const CtxLimits lim = context_limits(max_width, max_height);
-    e->max_segs = lim.max_segs;
-    e->max_tiles = lim.max_tiles;
-    const size_t segs = (size_t)e->max_segs + 16;                 // k_finalize reads the per-segment arrays four at a time
-    e->words_cap = lim.words_cap;
-    HIP_TRY_CREATE(hipMalloc((void **)&e->seg.words, e->words_cap * sizeof(uint32_t)));
-    e->seg.words_stride = kSegCapWords;
-    HIP_TRY_CREATE(hipMalloc((void **)&e->seg.bits, segs * sizeof(uint32_t)));
-    HIP_TRY_CREATE(hipMalloc((void **)&e->seg.syms, segs * sizeof(uint32_t)));
-    HIP_TRY_CREATE(hipMalloc((void **)&e->seg.exact, segs * sizeof(uint32_t)));
-    HIP_TRY_CREATE(hipMalloc((void **)&e->seg.edge, segs * sizeof(uint32_t)));
-    HIP_TRY_CREATE(hipMalloc((void **)&e->seg.ffin, segs * 8 * sizeof(uint16_t)));
-    HIP_TRY_CREATE(hipMalloc((void **)&e->seg.grp_bits, (segs / kSegGroup + 2) * sizeof(uint32_t)));
-    HIP_TRY_CREATE(hipMalloc((void **)&e->seg.grp_ff, (segs / kSegGroup + 2) * 8 * sizeof(uint32_t)));
+    e->lim = context_limits(max_width, max_height);
+    if (alloc_seg_arrays(&e->seg, (size_t)e->lim.max_segs, e->lim.words_cap, true)) { jpegamd_encoder_destroy(e); return JPEGAMD_ERR_HIP; }
     HIP_TRY_CREATE(hipMalloc((void **)&e->huff, 272 * sizeof(uint32_t)));
     HIP_TRY_CREATE(hipMalloc((void **)&e->prefix, 512));
     HIP_TRY_CREATE(hipMalloc((void **)&e->stats_dev, sizeof(ScanStats)));
     HIP_TRY_CREATE(hipMemset(e->stats_dev, 0, sizeof(ScanStats)));
     HIP_TRY_CREATE(hipMalloc((void **)&e->tables_dev, sizeof(MfmaTables)));
-    HIP_TRY_CREATE(hipMalloc((void **)&e->tile_head, ((size_t)e->max_tiles + 1) * kTileHeadWords * sizeof(uint32_t)));
-    HIP_TRY_CREATE(hipMalloc((void **)&e->tile_over, (size_t)e->max_tiles * kTileOverCap * sizeof(uint32_t)));
+    HIP_TRY_CREATE(hipMalloc((void **)&e->tile_head, ((size_t)e->lim.max_tiles + 1) * kTileHeadWords * sizeof(uint32_t)));
+    HIP_TRY_CREATE(hipMalloc((void **)&e->tile_over, (size_t)e->lim.max_tiles * kTileOverCap * sizeof(uint32_t)));
     HIP_TRY_CREATE(hipMalloc((void **)&e->code_tab, kCodeWords * sizeof(uint32_t)));
     HIP_TRY_CREATE(hipMalloc((void **)&e->tile_ctr, 2 * 64 * 128));      // two sets of ticket-group cache lines, used alternately
     HIP_TRY_CREATE(hipMemset(e->tile_ctr, 0, 2 * 64 * 128));
-    e->max_wgs = lim.max_wgs;
-    HIP_TRY_CREATE(hipMalloc((void **)&e->desc, 12 * (size_t)e->max_wgs * sizeof(uint32_t)));
-    HIP_TRY_CREATE(hipMemset(e->desc, 0, 12 * (size_t)e->max_wgs * sizeof(uint32_t)));
+    HIP_TRY_CREATE(hipMalloc((void **)&e->desc, 12 * (size_t)e->lim.max_wgs * sizeof(uint32_t)));
+    HIP_TRY_CREATE(hipMemset(e->desc, 0, 12 * (size_t)e->lim.max_wgs * sizeof(uint32_t)));
     if (std::getenv("JPEGAMD_STAMPS")) {
-        const size_t n = stamp_words(e->max_segs) * sizeof(unsigned long long);
+        const size_t n = stamp_words(e->lim.max_segs) * sizeof(unsigned long long);
         HIP_TRY_CREATE(hipMalloc((void **)&e->stamps_dev, n));
         HIP_TRY_CREATE(hipMemset(e->stamps_dev, 0, n));
     }
@@ -309,15 +337,15 @@ extern "C" int32_t jpegamd_encoder_create(JpegAmdEncoder **out, int32_t max_widt
 extern "C" int32_t jpegamd_encoder_destroy(JpegAmdEncoder *e) {
     if (!e) return JPEGAMD_OK;
     if (e->pending) hipStreamSynchronize(e->last_stream);
-    hipFree(e->seg.words); hipFree(e->seg.bits); hipFree(e->seg.syms); hipFree(e->seg.exact); hipFree(e->seg.edge); hipFree(e->seg.ffin); hipFree(e->seg.grp_bits); hipFree(e->seg.grp_ff);
+    free_seg_arrays(&e->seg);
     hipFree(e->huff); hipFree(e->prefix); hipFree(e->stats_dev); hipFree(e->tables_dev);
     hipFree(e->tile_head); hipFree(e->tile_over); hipFree(e->code_tab); hipFree(e->tile_ctr); hipFree(e->desc); hipFree(e->stamps_dev);
     hipFree(e->color.tables_dev); hipFree(e->color.code_tab); hipFree(e->color.huff); hipFree(e->color.hdr); hipFree(e->color.scan_size);
     hipFree(e->color.scan_stats); hipFree(e->color.planes); hipFree(e->color.scans);
     hipFree(e->color.bmeta); hipFree(e->color.bplanes); hipFree(e->color.bscans);
-    hipFree(e->mcu.coef); hipFree(e->mcu.seg.words); hipFree(e->mcu.seg.bits); hipFree(e->mcu.seg.syms); hipFree(e->mcu.seg.exact);
-    hipFree(e->mcu.seg.edge); hipFree(e->mcu.seg.ffin); hipFree(e->mcu.hdr); hipFree(e->mcu.scan_stats);
-    for (auto &set : e->ring) { for (auto &ev : set.ev) if (ev) hipEventDestroy(ev); for (auto &ev : set.cev) if (ev) hipEventDestroy(ev); }
+    hipFree(e->mcu.coef); hipFree(e->mcu.hdr); hipFree(e->mcu.scan_stats);
+    free_seg_arrays(&e->mcu.seg);
+    destroy_ring_events(e);
     delete e->tables_host;
     delete e;
     return JPEGAMD_OK;
@@ -332,7 +360,7 @@ extern "C" int32_t jpegamd_encoder_set_pipeline(JpegAmdEncoder *e, int32_t pipel
 extern "C" int32_t jpegamd_encoder_set_profiling(JpegAmdEncoder *e, int32_t slots) {
     if (!e || slots < 0 || slots > 65536) return JPEGAMD_ERR_ARG;
     if (e->pending) HIP_TRY(hipStreamSynchronize(e->last_stream));
-    for (auto &set : e->ring) { for (auto &ev : set.ev) if (ev) hipEventDestroy(ev); for (auto &ev : set.cev) if (ev) hipEventDestroy(ev); }
+    destroy_ring_events(e);
     e->ring.clear();
     e->ring.resize((size_t)slots);
     for (auto &set : e->ring) { set.merged = false; for (auto &ev : set.ev) HIP_TRY(hipEventCreate(&ev)); }
@@ -341,53 +369,51 @@ extern "C" int32_t jpegamd_encoder_set_profiling(JpegAmdEncoder *e, int32_t slot
     return JPEGAMD_OK;
 }
 
+// The time between two recorded events, in nanoseconds.
+static int32_t elapsed_ns(hipEvent_t begin, hipEvent_t end, uint64_t *ns) {
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, begin, end));
+    *ns = (uint64_t)((double)ms * 1e6);
+    return JPEGAMD_OK;
+}
+
 static int32_t read_color_slot(JpegAmdEncoder *e, int slot, uint64_t ns[11]) {
     const auto &set = e->ring[(size_t)slot];
     const hipEvent_t *cev = set.cev.data();
-    float ms = 0;
-    const auto span = [&](int i0, int i1, uint64_t &out) -> int32_t {
-        HIP_TRY(hipEventElapsedTime(&ms, cev[i0], cev[i1]));
-        out = (uint64_t)((double)ms * 1e6);
-        return JPEGAMD_OK;
-    };
     for (int i = 0; i < 11; ++i) ns[i] = 0;
-    if (int32_t rc = span(0, 1, ns[0])) return rc;
+    if (int32_t rc = elapsed_ns(cev[0], cev[1], &ns[0])) return rc;
     for (int c = 0; c < 3; ++c) {
         const int b = 2 + 6 * c;
-        if (int32_t rc = span(b, b + 1, ns[1 + 3 * c])) return rc;
-        if (set.cmerged[c]) if (int32_t rc = span(b + 2, b + 3, ns[2 + 3 * c])) return rc;
-        if (int32_t rc = span(b + 4, b + 5, ns[3 + 3 * c])) return rc;
+        if (int32_t rc = elapsed_ns(cev[b], cev[b + 1], &ns[1 + 3 * c])) return rc;
+        if (set.cmerged[c]) {
+            if (int32_t rc = elapsed_ns(cev[b + 2], cev[b + 3], &ns[2 + 3 * c])) return rc;
+        }
+        if (int32_t rc = elapsed_ns(cev[b + 4], cev[b + 5], &ns[3 + 3 * c])) return rc;
     }
-    return span(20, 21, ns[10]);
+    return elapsed_ns(cev[20], cev[21], &ns[10]);
 }
 
 static int32_t read_slot(JpegAmdEncoder *e, int slot, JpegAmdStats *stats) {
     if (slot < 0 || (size_t)slot >= e->ring.size()) return JPEGAMD_ERR_ARG;
-    if (e->ring[(size_t)slot].color && e->ring[(size_t)slot].cbatch) {   // a colour batch: the whole call only
-        float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, e->ring[(size_t)slot].cev[0], e->ring[(size_t)slot].cev[21]));
-        stats->ns_total = (uint64_t)((double)ms * 1e6);
-        return JPEGAMD_OK;
-    }
-    if (e->ring[(size_t)slot].color) {            // sums over the three scans; the planes count as transform, the append as pack
+    const auto &set = e->ring[(size_t)slot];
+    if (set.color && set.cbatch)                  // a colour batch: the whole call only
+        return elapsed_ns(set.cev[0], set.cev[21], &stats->ns_total);
+    if (set.color) {                              // sums over the three scans; the planes count as transform, the append as pack
         uint64_t ns[11];
         if (int32_t rc = read_color_slot(e, slot, ns)) return rc;
         stats->ns_transform = ns[0] + ns[1] + ns[4] + ns[7];
         stats->ns_entropy = ns[2] + ns[5] + ns[8];
         stats->ns_pack = ns[3] + ns[6] + ns[9] + ns[10];
-        float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, e->ring[(size_t)slot].cev[0], e->ring[(size_t)slot].cev[21]));
-        stats->ns_total = (uint64_t)((double)ms * 1e6);
-        return JPEGAMD_OK;
+        return elapsed_ns(set.cev[0], set.cev[21], &stats->ns_total);
     }
-    hipEvent_t *ev = e->ring[(size_t)slot].ev;
-    float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1])); stats->ns_transform = (uint64_t)((double)ms * 1e6);
+    const hipEvent_t *ev = set.ev;
+    if (int32_t rc = elapsed_ns(ev[0], ev[1], &stats->ns_transform)) return rc;
     stats->ns_entropy = 0;                                     // (whole images: there is no separate merge kernel)
-    if (e->ring[(size_t)slot].merged) { HIP_TRY(hipEventElapsedTime(&ms, ev[2], ev[3])); stats->ns_entropy = (uint64_t)((double)ms * 1e6); }
-    HIP_TRY(hipEventElapsedTime(&ms, ev[4], ev[5])); stats->ns_pack = (uint64_t)((double)ms * 1e6);
-    HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[5])); stats->ns_total = (uint64_t)((double)ms * 1e6);     // first begin .. last end: includes the launch gaps
-    return JPEGAMD_OK;
+    if (set.merged) {
+        if (int32_t rc = elapsed_ns(ev[2], ev[3], &stats->ns_entropy)) return rc;
+    }
+    if (int32_t rc = elapsed_ns(ev[4], ev[5], &stats->ns_pack)) return rc;
+    return elapsed_ns(ev[0], ev[5], &stats->ns_total);         // first begin .. last end: includes the launch gaps
 }
 
 extern "C" int32_t jpegamd_debug_color_profile(JpegAmdEncoder *e, int32_t slot, uint64_t *ns) {
@@ -402,21 +428,33 @@ extern "C" int32_t jpegamd_encoder_profile(JpegAmdEncoder *e, int32_t slot, Jpeg
     return read_slot(e, slot, stats);
 }
 
+// Context memory that queued work may still read is rewritten from the host only behind that work.
+static int32_t wait_pending(JpegAmdEncoder *e) {
+    if (e->pending) HIP_TRY(hipStreamSynchronize(e->last_stream));
+    return JPEGAMD_OK;
+}
+
+// The fast path's constants for quantisation table `t` into `dst` (the context's luma or chroma set), staged in tables_host.
+static int32_t upload_tables(JpegAmdEncoder *e, const uint8_t t[64], MfmaTables *dst) {
+    derive_mfma_tables(t, e->tables_host, nullptr);
+    if (int32_t rc = wait_pending(e)) return rc;
+    HIP_TRY(hipMemcpy(dst, e->tables_host, sizeof(MfmaTables), hipMemcpyHostToDevice));
+    return JPEGAMD_OK;
+}
+
 static int32_t prepare_constants(JpegAmdEncoder *e, const JpegAmdImage *img, bool need_prefix) {
     const int q = clamp_quality(img->quality);
     if (q != e->cur_quality) {
         quant_table_for_quality(q, e->qtable);
-        derive_mfma_tables(e->qtable, e->tables_host, nullptr);
-        if (e->pending) HIP_TRY(hipStreamSynchronize(e->last_stream));
-        HIP_TRY(hipMemcpy(e->tables_dev, e->tables_host, sizeof(MfmaTables), hipMemcpyHostToDevice));
+        if (int32_t rc = upload_tables(e, e->qtable, e->tables_dev)) return rc;
         e->cur_quality = q;
     }
-    if (need_prefix && (e->prefix_w != img->width || e->prefix_h != img->height || e->prefix_q != q)) {
+    if (need_prefix && !e->prefix_for.matches(img->width, img->height, q, 0)) {
         uint8_t hdr[JPEGAMD_JFIF_PREFIX_BYTES];
         build_jfif_prefix(img->width, img->height, e->qtable, hdr);
-        if (e->pending) HIP_TRY(hipStreamSynchronize(e->last_stream));
+        if (int32_t rc = wait_pending(e)) return rc;
         HIP_TRY(hipMemcpy(e->prefix, hdr, sizeof(hdr), hipMemcpyHostToDevice));
-        e->prefix_w = img->width; e->prefix_h = img->height; e->prefix_q = q;
+        e->prefix_for.set(img->width, img->height, q, 0, JPEGAMD_JFIF_PREFIX_BYTES);
     }
     return JPEGAMD_OK;
 }
@@ -425,7 +463,7 @@ static int32_t prepare_constants(JpegAmdEncoder *e, const JpegAmdImage *img, boo
 // fewer rows can need MORE segments or tiles than max_w x max_h (per-row rounding).
 static bool context_fits(const JpegAmdEncoder *e, int w, int h) {
     if (!e || w <= 0 || h <= 0) return false;
-    return segs_for(w, h, nullptr, nullptr, nullptr) <= e->max_segs && tiles_for(w, h) <= e->max_tiles;
+    return segs_for(w, h, nullptr, nullptr, nullptr) <= e->lim.max_segs && tiles_for(w, h) <= e->lim.max_tiles;
 }
 
 // Layouts beyond the three every entry takes: the 4-byte orders (the four whole-picture encode entries), and the internal order of
@@ -437,6 +475,21 @@ static int bytes_per_pixel(int order) {
     return (order == JPEGAMD_ORDER_GRAY || order == kOrderPlanar) ? 1 : (is_px4(order) ? 4 : 3);
 }
 
+// ImageDesc::fast_ok, from the OR of every pointer the launch reads and their row stride.  The dword loader wants both on dword
+// boundaries; it multiplies the row stride by a 24-bit multiply (and keeps a tile's eight row offsets in 32 bits): wider strides --
+// a region of interest inside a huge buffer -- take the clamped byte loader, whose addresses are 64-bit.
+static int32_t dword_loader_ok(uintptr_t pointer_bits, int stride) {
+    return ((pointer_bits & 3u) == 0 && (stride & 3) == 0 && stride < (1 << 24)) ? 1 : 0;
+}
+
+// A launch of ONE picture with d's geometry and stride: its pixels, and whether the dword loader may read them.
+static void set_single_picture(ImageDesc *d, const uint8_t *pixels) {
+    d->pixels = pixels;
+    d->batch = 1;
+    for (int i = 0; i < kMaxBatch; ++i) d->batch_pixels[i] = pixels;
+    d->fast_ok = dword_loader_ok((uintptr_t)pixels, d->row_stride);
+}
+
 static int32_t describe(const JpegAmdEncoder *e, const JpegAmdImage *img, ImageDesc *d, int seg_tiles = kSegTiles, int accept = kAcceptBasic) {
     if (!img || !img->pixels || img->width <= 0 || img->height <= 0 || img->width > 65535 || img->height > 65535)
         return JPEGAMD_ERR_ARG;
@@ -444,8 +497,8 @@ static int32_t describe(const JpegAmdEncoder *e, const JpegAmdImage *img, ImageD
     if (!basic && !(accept == kAcceptPx4 && is_px4(img->channel_order)) && !(accept == kAcceptPlanar && img->channel_order == kOrderPlanar))
         return JPEGAMD_ERR_ARG;
     if (img->row_stride < bytes_per_pixel(img->channel_order) * img->width) return JPEGAMD_ERR_ARG;
-    d->pixels = (const uint8_t *)img->pixels;
     d->width = img->width; d->height = img->height; d->row_stride = img->row_stride;
+    set_single_picture(d, (const uint8_t *)img->pixels);
     d->bottom_up = img->bottom_up ? 1 : 0;
     d->select = select_luma(img->channel_order == JPEGAMD_ORDER_BGR || img->channel_order == JPEGAMD_ORDER_BGRA);   // the weights follow the STORED byte order
     d->seg_tiles = seg_tiles;
@@ -454,13 +507,8 @@ static int32_t describe(const JpegAmdEncoder *e, const JpegAmdImage *img, ImageD
     d->num_tiles = d->tiles_per_row * d->blocks_h;
     d->tile_begin = 0; d->tile_end = d->num_tiles;
     d->seg_begin = 0; d->seg_end = d->num_segs;
-    d->batch = 1;
-    for (int i = 0; i < kMaxBatch; ++i) d->batch_pixels[i] = d->pixels;
     const uint64_t tpi = 0x100000000ull / (uint64_t)d->num_tiles;
     d->tpi_magic = tpi > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)tpi;
-    // the dword loader multiplies the row stride by a 24-bit multiply (and keeps a tile's eight row offsets in 32 bits): wider
-    // strides -- a region of interest inside a huge buffer -- take the clamped byte loader, whose addresses are 64-bit
-    d->fast_ok = ((((uintptr_t)img->pixels) & 3u) == 0 && (img->row_stride & 3) == 0 && img->row_stride < (1 << 24)) ? 1 : 0;
     if (e && !context_fits(e, img->width, img->height)) return JPEGAMD_ERR_TOO_LARGE;
     return JPEGAMD_OK;
 }
@@ -475,6 +523,11 @@ static TileSource src_of(const JpegAmdImage *img) {
 // The pictures of a batch as the kernels take them: p[0] the pixels (planar: the R planes), p[1] / p[2] the G / B planes.
 struct PlaneSet {
     const uint8_t *p[3][kMaxBatch];
+};
+// One picture's output buffer and size word, as the arrays the batch functions take.
+struct SingleOut {
+    void *outs[1];
+    uint64_t *sizes[1];
 };
 
 // k_tile_encode (+ the fault injection of the tests).
@@ -502,7 +555,7 @@ static int launch_transform(JpegAmdEncoder *e, const ImageDesc &im, bool taps, i
                           : launch_tile_transform(im, to, taps, stream, (ev && !taps) ? (void *const *)ev : nullptr, src, planes)) return err;
     if (im.tile_end > im.tile_begin) e->ctr_set ^= 1;      // (an empty range launches nothing)
     if (e->poison_tile >= 0) {                             // fault injection for the tests: a corrupt record must end in a status code
-        if (e->poison_tile < e->max_tiles &&
+        if (e->poison_tile < e->lim.max_tiles &&
             hipMemsetD32Async((hipDeviceptr_t)(e->tile_head + (size_t)e->poison_tile * kTileHeadWords), (int)e->poison_value, 1, (hipStream_t)stream) != hipSuccess)
             return (int)hipErrorUnknown;
         e->poison_tile = -1;
@@ -578,15 +631,15 @@ static int run_stitch(JpegAmdEncoder *e, const ImageDesc &im, void *const *outs_
     sa.num_segs = im.num_segs; sa.segs_per_row = im.segs_per_row; sa.tiles_per_row = im.tiles_per_row;
     sa.seg_tiles = im.seg_tiles; sa.tiles_per_image = im.num_tiles;
     sa.batch = im.batch; sa.wgs_per_image = stitch_workgroups(im.num_segs);
-    if ((int64_t)sa.batch * sa.wgs_per_image > e->max_wgs) return (int)hipErrorInvalidValue;
+    if ((int64_t)sa.batch * sa.wgs_per_image > e->lim.max_wgs) return (int)hipErrorInvalidValue;
     // a fresh epoch per launch: granules of older launches never match (no zeroing between launches); the arrays are cleared
     // when the 14-bit tag wraps
     if (e->epoch >= 16383u) {
-        if (hipMemsetAsync(e->desc, 0, 12 * (size_t)e->max_wgs * sizeof(uint32_t), stream) != hipSuccess) return (int)hipErrorUnknown;
+        if (hipMemsetAsync(e->desc, 0, 12 * (size_t)e->lim.max_wgs * sizeof(uint32_t), stream) != hipSuccess) return (int)hipErrorUnknown;
         e->epoch = 0;
     }
     sa.epoch = ++e->epoch;
-    sa.desc = e->desc; sa.desc_ffx = e->desc + 4 * (size_t)e->max_wgs;
+    sa.desc = e->desc; sa.desc_ffx = e->desc + 4 * (size_t)e->lim.max_wgs;
     sa.seg_syms = e->seg.syms; sa.seg_exact = e->seg.exact;
     for (int i = 0; i < im.batch; ++i) { sa.out[i] = (uint8_t *)outs_dev[i]; sa.out_size[i] = out_sizes_dev[i]; }
     sa.out_capacity = out_capacity; sa.stats = e->stats_dev; sa.status = &e->stats_dev->status;
@@ -718,22 +771,29 @@ extern "C" int32_t jpegamd_finalize_async(JpegAmdEncoder *e, const JpegAmdImage 
     rc = prepare_constants(e, img, with_container != 0);
     if (rc) return rc;
     hipStream_t stream = (hipStream_t)stream_;
-    void *const outs[1] = {out_dev};
-    uint64_t *const sizes[1] = {out_size_dev};
-    if (run_finalize(e, im, outs, out_capacity, sizes, with_container, stream, nullptr, 1, false)) return JPEGAMD_ERR_HIP;
+    const SingleOut one = {{out_dev}, {out_size_dev}};
+    if (run_finalize(e, im, one.outs, out_capacity, one.sizes, with_container, stream, nullptr, 1, false)) return JPEGAMD_ERR_HIP;
     return enqueued(e, stream, im.num_segs);
+}
+
+// The pictures of a batch of JpegAmdImage: every output, size word and pixel pointer set, every picture like the first (which the
+// entry has checked: each takes its own layouts) -> their pixels in ps->p[0].  Reads nothing of a context.
+static int32_t uniform_batch_args(const JpegAmdImage *imgs, int32_t count, void *const *outs_dev, uint64_t *const *out_sizes_dev, PlaneSet *ps) {
+    const JpegAmdImage &g0 = imgs[0];
+    *ps = PlaneSet{};
+    for (int i = 0; i < count; ++i) {
+        const JpegAmdImage &g = imgs[i];
+        if (!outs_dev[i] || !out_sizes_dev[i] || !g.pixels) return JPEGAMD_ERR_ARG;
+        if (g.width != g0.width || g.height != g0.height || g.row_stride != g0.row_stride || (g.bottom_up != 0) != (g0.bottom_up != 0) ||
+            g.channel_order != g0.channel_order || g.quality != g0.quality)
+            return JPEGAMD_ERR_ARG;
+        ps->p[0][i] = (const uint8_t *)g.pixels;
+    }
+    return JPEGAMD_OK;
 }
 
 // `count` images of one geometry through ONE launch of each kernel (see the header): image i's tiles are
 // [i * num_tiles, (i + 1) * num_tiles), its segments [i * num_segs, ..); DC prediction, bit offsets and stuffing restart per image.
-// Every pointer of every picture on a dword boundary?  (what ImageDesc::fast_ok asks besides the stride)
-static bool planes_aligned(const PlaneSet &ps, int count, int order) {
-    uintptr_t bits = 0;
-    for (int k = 0; k < (order == kOrderPlanar ? 3 : 1); ++k)
-        for (int i = 0; i < count; ++i) bits |= (uintptr_t)ps.p[k][i];
-    return (bits & 3u) == 0;
-}
-
 // The launch plan of `count` pictures like g0, pixels in ps, coded as ONE batch (a grayscale batch, the Y scans of a colour batch):
 // segments of 16 tiles for k_stitch and from four pictures on (jpegamd_internal.h) -- of 8 after all when the context's words do
 // not hold the longer ones (a geometry other than its own) -- then whether the whole batch fits the context.
@@ -743,14 +803,17 @@ static int32_t plan_batch(const JpegAmdEncoder *e, const JpegAmdImage &g0, const
     int seg_tiles = (*stitch || count >= 4) ? kSegTilesBatch : kSegTiles;
     const auto words = [&]() { return (size_t)count * im->num_segs * seg_cap_words(seg_tiles); };
     if (int32_t rc = describe(e, &g0, im, seg_tiles, accept)) return rc;
-    if (!*stitch && seg_tiles != kSegTiles && words() > e->words_cap) {
+    if (!*stitch && seg_tiles != kSegTiles && words() > e->lim.words_cap) {
         seg_tiles = kSegTiles;
         if (int32_t rc = describe(e, &g0, im, seg_tiles, accept)) return rc;
     }
-    if ((int64_t)count * im->num_tiles > e->max_tiles || (int64_t)count * im->num_segs > e->max_segs || (!*stitch && words() > e->words_cap))
+    if ((int64_t)count * im->num_tiles > e->lim.max_tiles || (int64_t)count * im->num_segs > e->lim.max_segs || (!*stitch && words() > e->lim.words_cap))
         return JPEGAMD_ERR_TOO_LARGE;
     for (int i = 0; i < count; ++i) im->batch_pixels[i] = ps.p[0][i];
-    if (!planes_aligned(ps, count, g0.channel_order)) im->fast_ok = 0;
+    uintptr_t pointer_bits = 0;                                        // every pointer of every picture (planar: of all three planes)
+    for (int k = 0; k < (g0.channel_order == kOrderPlanar ? 3 : 1); ++k)
+        for (int i = 0; i < count; ++i) pointer_bits |= (uintptr_t)ps.p[k][i];
+    im->fast_ok = dword_loader_ok(pointer_bits, g0.row_stride);
     im->batch = count;
     im->tile_end = count * im->num_tiles;
     im->seg_end = count * im->num_segs;
@@ -785,9 +848,8 @@ extern "C" int32_t jpegamd_encode_async(JpegAmdEncoder *e, const JpegAmdImage *i
     if (rc) return rc;
     PlaneSet ps = {};
     ps.p[0][0] = (const uint8_t *)img->pixels;
-    void *const outs[1] = {out_dev};
-    uint64_t *const sizes[1] = {out_size_dev};
-    return gray_batch(e, *img, ps, 1, outs, out_capacity, sizes, with_container, stream_);
+    const SingleOut one = {{out_dev}, {out_size_dev}};
+    return gray_batch(e, *img, ps, 1, one.outs, out_capacity, one.sizes, with_container, stream_);
 }
 
 extern "C" int32_t jpegamd_encode_batch_async(JpegAmdEncoder *e, const JpegAmdImage *imgs, int32_t count, void *const *outs_dev,
@@ -797,15 +859,9 @@ extern "C" int32_t jpegamd_encode_batch_async(JpegAmdEncoder *e, const JpegAmdIm
     ImageDesc im;
     int32_t rc = describe(nullptr, &imgs[0], &im, kSegTiles, kAcceptPx4);      // (the arguments alone: the context is looked at by gray_batch)
     if (rc) return rc;
-    PlaneSet ps = {};
-    for (int i = 0; i < count; ++i) {
-        const JpegAmdImage &g = imgs[i];
-        if (!outs_dev[i] || !out_sizes_dev[i] || !g.pixels) return JPEGAMD_ERR_ARG;
-        if (g.width != imgs[0].width || g.height != imgs[0].height || g.row_stride != imgs[0].row_stride ||
-            (g.bottom_up != 0) != (imgs[0].bottom_up != 0) || g.channel_order != imgs[0].channel_order || g.quality != imgs[0].quality)
-            return JPEGAMD_ERR_ARG;
-        ps.p[0][i] = (const uint8_t *)g.pixels;
-    }
+    PlaneSet ps;
+    rc = uniform_batch_args(imgs, count, outs_dev, out_sizes_dev, &ps);
+    if (rc) return rc;
     return gray_batch(e, imgs[0], ps, count, outs_dev, out_capacity, out_sizes_dev, with_container, stream_);
 }
 
@@ -838,21 +894,26 @@ static int32_t color_alloc_consts(JpegAmdEncoder *e) {
     return JPEGAMD_OK;
 }
 
+// Grow-only scratch: *p holds *cap units of `unit` bytes; a call that needs more gets a new buffer of exactly `need` units, behind
+// whatever queued work may still use the old one.  The contents are not kept.
+template <class T>
+static int32_t grow_scratch(JpegAmdEncoder *e, T **p, size_t *cap, size_t need, size_t unit = sizeof(T)) {
+    if (need <= *cap) return JPEGAMD_OK;
+    if (int32_t rc = wait_pending(e)) return rc;
+    hipFree(*p); *p = nullptr; *cap = 0;
+    HIP_TRY(hipMalloc((void **)p, need * unit));
+    *cap = need;
+    return JPEGAMD_OK;
+}
+
 static int32_t color_alloc(JpegAmdEncoder *e, int w, int h) {
     auto &c = e->color;
     if (int32_t rc = color_alloc_consts(e)) return rc;
     // planes and scans sized for this picture at 4:4:4 (the larger case), grown when a later picture needs more
     const size_t planes = 2 * (size_t)((w + 3) / 4 * 4) * (size_t)h + 64;
-    const size_t scan = (kSosBytes + 2 + scan_bound(blocks_of(w, h)) + 64 + 255) & ~(size_t)255;     // (k_append_scans reads 16 bytes at a time)
-    if (planes > c.planes_cap || scan > c.scan_cap) {
-        if (e->pending) HIP_TRY(hipStreamSynchronize(e->last_stream));
-        hipFree(c.planes); hipFree(c.scans);
-        c.planes = nullptr; c.scans = nullptr; c.planes_cap = c.scan_cap = 0;
-        HIP_TRY(hipMalloc((void **)&c.planes, planes));
-        HIP_TRY(hipMalloc((void **)&c.scans, 2 * scan));
-        c.planes_cap = planes; c.scan_cap = scan;
-    }
-    return JPEGAMD_OK;
+    const size_t scan = (kSosBytes + 2 + scan_bound(blocks_of(w, h), kMaxBlockBitsColor) + 64 + 255) & ~(size_t)255;     // (k_append_scans reads 16 bytes at a time)
+    if (int32_t rc = grow_scratch(e, &c.planes, &c.planes_cap, planes)) return rc;
+    return grow_scratch(e, &c.scans, &c.scan_cap, scan, 2);          // (the Cb part, then the Cr part)
 }
 
 static int32_t prepare_color_constants(JpegAmdEncoder *e, const JpegAmdImage *img, int sub) {
@@ -861,23 +922,17 @@ static int32_t prepare_color_constants(JpegAmdEncoder *e, const JpegAmdImage *im
     if (q != c.cur_quality) {
         uint8_t t[64];
         chroma_quant_table_for_quality(q, t);
-        MfmaTables *mt = new (std::nothrow) MfmaTables;
-        if (!mt) return JPEGAMD_ERR_HIP;
-        derive_mfma_tables(t, mt, nullptr);
-        if (e->pending) { hipError_t err = hipStreamSynchronize(e->last_stream); if (err != hipSuccess) { delete mt; return JPEGAMD_ERR_HIP; } }
-        const hipError_t err = hipMemcpy(c.tables_dev, mt, sizeof(MfmaTables), hipMemcpyHostToDevice);
-        delete mt;
-        if (err != hipSuccess) return JPEGAMD_ERR_HIP;
+        if (int32_t rc = upload_tables(e, t, c.tables_dev)) return rc;
         c.cur_quality = q;
     }
-    if (c.hdr_w != img->width || c.hdr_h != img->height || c.hdr_q != q || c.hdr_sub != sub) {
+    if (!c.hdr_for.matches(img->width, img->height, q, sub)) {
         uint8_t luma[64], chroma[64], hdr[kColorPrefixMax];
         quant_table_for_quality(q, luma);
         chroma_quant_table_for_quality(q, chroma);
-        c.hdr_len = (int)build_jfif_prefix_color(img->width, img->height, luma, chroma, chroma_mode(sub), hdr);
-        if (e->pending) HIP_TRY(hipStreamSynchronize(e->last_stream));
-        HIP_TRY(hipMemcpy(c.hdr, hdr, (size_t)c.hdr_len, hipMemcpyHostToDevice));
-        c.hdr_w = img->width; c.hdr_h = img->height; c.hdr_q = q; c.hdr_sub = sub;
+        const int len = (int)build_jfif_prefix_color(img->width, img->height, luma, chroma, chroma_mode(sub), hdr);
+        if (int32_t rc = wait_pending(e)) return rc;
+        HIP_TRY(hipMemcpy(c.hdr, hdr, (size_t)len, hipMemcpyHostToDevice));
+        c.hdr_for.set(img->width, img->height, q, sub, len);
     }
     return JPEGAMD_OK;
 }
@@ -885,9 +940,8 @@ static int32_t prepare_color_constants(JpegAmdEncoder *e, const JpegAmdImage *im
 // One scan of the colour file: k_tile_encode, then k_segment_merge + k_finalize or k_stitch, then the scan's symbol sums.
 static int run_scan(JpegAmdEncoder *e, const ImageDesc &im, TileSource src, void *out, uint64_t cap, uint64_t *size_dev, const ScanTarget &tgt,
                     bool stitch, hipStream_t stream, hipEvent_t *ev) {
-    void *const outs[1] = {out};
-    uint64_t *const sizes[1] = {size_dev};
-    if (int err = code_tiles(e, im, src, nullptr, nullptr, outs, cap, sizes, 1, &tgt, stitch, stream, ev, ev ? ev + 4 : nullptr)) return err;
+    const SingleOut one = {{out}, {size_dev}};
+    if (int err = code_tiles(e, im, src, nullptr, nullptr, one.outs, cap, one.sizes, 1, &tgt, stitch, stream, ev, ev ? ev + 4 : nullptr)) return err;
     return launch_sum_stats(e->seg.syms, e->seg.exact, im.num_segs, tgt.stats, stream);
 }
 
@@ -896,18 +950,15 @@ extern "C" int32_t jpegamd_encode_color_async(JpegAmdEncoder *e, const JpegAmdIm
     if (!e || !img || !out_dev || !out_size_dev) return JPEGAMD_ERR_ARG;
     if (!sub_valid(subsampling)) return JPEGAMD_ERR_ARG;
     if (is_px4(img->channel_order)) {             // a batch of one through the batch kernels (k_chroma_planes reads 3-byte pixels only)
-        void *const outs[1] = {out_dev};
-        uint64_t *const sizes[1] = {out_size_dev};
-        return jpegamd_encode_color_batch_async(e, img, 1, subsampling, outs, out_capacity, sizes, stream_);
+        const SingleOut one = {{out_dev}, {out_size_dev}};
+        return jpegamd_encode_color_batch_async(e, img, 1, subsampling, one.outs, out_capacity, one.sizes, stream_);
     }
     if (img->channel_order != JPEGAMD_ORDER_BGR && img->channel_order != JPEGAMD_ORDER_RGB) return JPEGAMD_ERR_ARG;
     ImageDesc iy;
     const bool stitch_y = use_stitch(e, img->width, img->height);
     int32_t rc = describe(e, img, &iy, stitch_y ? kSegTilesBatch : kSegTiles);
     if (rc) return rc;
-    int cw, ch;
-    chroma_dims(img->width, img->height, subsampling, &cw, &ch);
-    const int pitch = (cw + 3) / 4 * 4;
+    const ChromaGeom cg = chroma_geom(img->width, img->height, subsampling);
     rc = color_alloc(e, img->width, img->height);
     if (rc) return rc;
     rc = prepare_constants(e, img, false);
@@ -928,19 +979,19 @@ extern "C" int32_t jpegamd_encode_color_async(JpegAmdEncoder *e, const JpegAmdIm
     pa.width = img->width; pa.height = img->height; pa.row_stride = img->row_stride; pa.bottom_up = img->bottom_up ? 1 : 0;
     pa.rgb = img->channel_order == JPEGAMD_ORDER_RGB ? 1 : 0;
     pa.mode = chroma_mode(subsampling);
-    pa.cw = cw; pa.ch = ch; pa.pitch = pitch;
-    pa.cb = c.planes; pa.cr = c.planes + (size_t)pitch * (size_t)ch;
+    pa.cw = cg.cw; pa.ch = cg.ch; pa.pitch = cg.pitch;
+    pa.cb = c.planes; pa.cr = c.planes + (size_t)cg.pitch * (size_t)cg.ch;
     if (launch_chroma_planes(pa, stream, cev ? (void *const *)cev : nullptr)) return JPEGAMD_ERR_HIP;
 
     // Y: the grayscale scan of the same picture, behind the colour prefix, no EOI
-    const ScanTarget ty = {c.hdr, c.hdr_len, 0, &c.scan_stats[0], false};
+    const ScanTarget ty = {c.hdr, c.hdr_for.len, 0, &c.scan_stats[0], false};
     if (timed) e->ring[(size_t)e->last_slot].cmerged[0] = !stitch_y;
     if (run_scan(e, iy, TileSource{kSrcRgb}, out_dev, out_capacity, &c.scan_size[0], ty, stitch_y, stream, cev ? cev + 2 : nullptr))
         return JPEGAMD_ERR_HIP;
     // Cb, Cr: one-byte planes, chroma tables, into scratch
     JpegAmdImage pimg = *img;
-    pimg.width = cw; pimg.height = ch; pimg.row_stride = pitch; pimg.bottom_up = 0; pimg.channel_order = JPEGAMD_ORDER_GRAY;
-    const bool stitch_c = use_stitch(e, cw, ch);
+    pimg.width = cg.cw; pimg.height = cg.ch; pimg.row_stride = cg.pitch; pimg.bottom_up = 0; pimg.channel_order = JPEGAMD_ORDER_GRAY;
+    const bool stitch_c = use_stitch(e, cg.cw, cg.ch);
     for (int k = 0; k < 2; ++k) {
         pimg.pixels = k ? pa.cr : pa.cb;
         ImageDesc ic;
@@ -1012,15 +1063,13 @@ extern "C" int32_t jpegamd_debug_chroma_groups(int32_t max_width, int32_t max_he
                                                int32_t count, int32_t subsampling, int32_t *out) {
     if (!out || max_width <= 0 || max_height <= 0 || width <= 0 || height <= 0 || count < 1 || count > kMaxBatch) return JPEGAMD_ERR_ARG;
     if (!sub_valid(subsampling)) return JPEGAMD_ERR_ARG;
-    int cw, ch;
-    chroma_dims(width, height, subsampling, &cw, &ch);
+    const ChromaGeom cg = chroma_geom(width, height, subsampling);
     ChromaPlan p;
-    if (!chroma_plan(context_limits(max_width, max_height), pipeline, cw, ch, 2 * count, &p)) return JPEGAMD_ERR_TOO_LARGE;
+    if (!chroma_plan(context_limits(max_width, max_height), pipeline, cg.cw, cg.ch, 2 * count, &p)) return JPEGAMD_ERR_TOO_LARGE;
     out[0] = p.group; out[1] = p.launches; out[2] = p.seg_tiles; out[3] = p.stitch ? 1 : 0;
     return JPEGAMD_OK;
 }
 
-static size_t round_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 constexpr size_t kBatchMetaStats = kBatchLaunches * sizeof(ScanStats);
 constexpr size_t kBatchMetaPic = (size_t)kMaxBatch * kPicStatWords * sizeof(uint64_t);
 constexpr size_t kBatchMetaBytes = kBatchMetaStats + kBatchMetaPic + 3 * kMaxBatch * sizeof(uint64_t);
@@ -1029,20 +1078,8 @@ constexpr size_t kBatchMetaBytes = kBatchMetaStats + kBatchMetaPic + 3 * kMaxBat
 static int32_t color_batch_alloc(JpegAmdEncoder *e, size_t planes, size_t scans) {
     auto &c = e->color;
     if (!c.bmeta) HIP_TRY(hipMalloc((void **)&c.bmeta, kBatchMetaBytes));
-    if (planes > c.bplanes_cap || scans > c.bscans_cap) {
-        if (e->pending) HIP_TRY(hipStreamSynchronize(e->last_stream));
-        if (planes > c.bplanes_cap) {
-            hipFree(c.bplanes); c.bplanes = nullptr; c.bplanes_cap = 0;
-            HIP_TRY(hipMalloc((void **)&c.bplanes, planes));
-            c.bplanes_cap = planes;
-        }
-        if (scans > c.bscans_cap) {
-            hipFree(c.bscans); c.bscans = nullptr; c.bscans_cap = 0;
-            HIP_TRY(hipMalloc((void **)&c.bscans, scans));
-            c.bscans_cap = scans;
-        }
-    }
-    return JPEGAMD_OK;
+    if (int32_t rc = grow_scratch(e, &c.bplanes, &c.bplanes_cap, planes)) return rc;
+    return grow_scratch(e, &c.bscans, &c.bscans_cap, scans);
 }
 
 // The caller's own chroma (jpegamd_encode_ycbcr_batch_async): cb[i] / cr[i] the planes of picture i (a pair layout: cb[i] alone; a
@@ -1114,8 +1151,7 @@ static MatrixScratch matrix_scratch(int w, int h, int count, size_t plane_bytes)
 
 // k_ycbcr_matrix_batch over the caller's planes (g0 / px: the Y planes, ycc: the chroma) into color.bplanes, which holds m.total bytes.
 static int launch_matrix_pass(JpegAmdEncoder *e, const JpegAmdImage &g0, const PlaneSet &px, const YccSource &ycc, int32_t count,
-                              int32_t subsampling, int cw, int ch, int pitch, size_t plane_bytes, const MatrixScratch &m, hipStream_t stream,
-                              void *const *ev) {
+                              int32_t subsampling, const ChromaGeom &cg, const MatrixScratch &m, hipStream_t stream, void *const *ev) {
     YccMatrixBatchArgs ma;
     std::memset(&ma, 0, sizeof(ma));
     for (int i = 0; i < count; ++i) { ma.y[i] = px.p[0][i]; ma.cb[i] = ycc.cb[i]; ma.cr[i] = ycc.cr[i]; }
@@ -1127,10 +1163,50 @@ static int launch_matrix_pass(JpegAmdEncoder *e, const JpegAmdImage &g0, const P
     ma.first = (ycc.layout == JPEGAMD_CHROMA_CRCB || ycc.layout == JPEGAMD_CHROMA_UYVY) ? 1 : 0;
     ma.shift = (int32_t)depth_shift(ycc.format);
     ma.limited = ycc.range == JPEGAMD_RANGE_LIMITED ? 1 : 0;
-    ma.cw = cw; ma.ch = ch; ma.pitch = pitch; ma.ypitch = m.ypitch;
-    ma.plane_bytes = plane_bytes; ma.yplane_bytes = m.yplane_bytes;
+    ma.cw = cg.cw; ma.ch = cg.ch; ma.pitch = cg.pitch; ma.ypitch = m.ypitch;
+    ma.plane_bytes = cg.plane_bytes; ma.yplane_bytes = m.yplane_bytes;
     ma.planes = e->color.bplanes; ma.yplanes = e->color.bplanes + m.y_off;
     return launch_ycbcr_matrix_batch(ma, stream, ev);
+}
+
+// k_chroma_planes_batch over the pixels of an RGB batch (g0 / px, any layout the colour entries take): the 2 x count chroma planes of
+// geometry cg into color.bplanes, plane j (picture j / 2, Cb even, Cr odd) at j x cg.plane_bytes.
+static int launch_plane_pass(JpegAmdEncoder *e, const JpegAmdImage &g0, const PlaneSet &px, int32_t count, int32_t subsampling,
+                             const ChromaGeom &cg, hipStream_t stream, void *const *ev) {
+    ChromaPlanesBatchArgs pa;
+    std::memset(&pa, 0, sizeof(pa));
+    for (int i = 0; i < count; ++i) { pa.pixels[i] = px.p[0][i]; pa.pixels_g[i] = px.p[1][i]; pa.pixels_b[i] = px.p[2][i]; }
+    pa.layout = g0.channel_order == kOrderPlanar ? kChromaSrcPlanar : (is_px4(g0.channel_order) ? kChromaSrcPx4 : kChromaSrcPx3);
+    pa.batch = count;
+    pa.width = g0.width; pa.height = g0.height; pa.row_stride = g0.row_stride; pa.bottom_up = g0.bottom_up ? 1 : 0;
+    pa.rgb = (g0.channel_order == JPEGAMD_ORDER_BGR || g0.channel_order == JPEGAMD_ORDER_BGRA) ? 0 : 1;
+    pa.mode = chroma_mode(subsampling);
+    pa.cw = cg.cw; pa.ch = cg.ch; pa.pitch = cg.pitch;
+    pa.plane_bytes = cg.plane_bytes; pa.planes = e->color.bplanes;
+    return launch_chroma_planes_batch(pa, stream, ev);
+}
+
+// What the launches of a colour batch read.  `ycc` null: the call's own pixels for Y, the plane scratch for Cb and Cr (an RGB batch, or
+// a BT.709 one behind its pass); otherwise the caller's planes, and the launch's ImageDesc::select with them.
+// The Y launch (g: the pictures as the launch sees them).
+static TileSource y_source_of(const JpegAmdImage &g, const YccSource *ycc, ImageDesc *im) {
+    if (!ycc) return src_of(&g);
+    const SourceChoice y = ycbcr_y_source(ycc->layout, ycc->format, ycc->range);
+    im->select = y.select;
+    return y.src;
+}
+// A chroma launch whose first plane has index `first` in the whole call.
+static TileSource chroma_source_of(const YccSource *ycc, int first, ImageDesc *im) {
+    if (!ycc) return {kSrcPlane, true};
+    const SourceChoice cs = ycbcr_chroma_source(ycc->layout, ycc->format, ycc->range, first);
+    im->select = cs.select;
+    return cs.src;
+}
+// Plane j of the call (picture j / 2, Cb even, Cr odd).  Cb and Cr of a caller's picture may lie in ONE plane: pairs, or a packed plane.
+static const uint8_t *chroma_plane_of(const JpegAmdEncoder *e, const YccSource *ycc, const ChromaGeom &cg, int j) {
+    if (!ycc) return e->color.bplanes + (size_t)j * cg.plane_bytes;
+    if (ycc->layout != JPEGAMD_CHROMA_PLANES) return ycc->cb[j / 2];
+    return (j & 1) ? ycc->cr[j / 2] : ycc->cb[j / 2];
 }
 
 // The colour files of a batch whose arguments are known to be good: g0 describes every picture, ps holds their pixels.
@@ -1148,19 +1224,15 @@ static int32_t color_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, const Plan
     int32_t rc = plan_batch(e, g0, px, count, &iy, &stitch_y);
     if (rc) return rc;
     // Cb, Cr: 2 count planes at one pitch, in as few launches as the context allows
-    int cw, ch;
-    chroma_dims(g0.width, g0.height, subsampling, &cw, &ch);
-    const int pitch = (cw + 3) / 4 * 4;
+    const ChromaGeom cg = chroma_geom(g0.width, g0.height, subsampling);
     const int planes = 2 * count;
     ChromaPlan plan;
-    const CtxLimits lim = {e->max_segs, e->max_tiles, e->max_wgs, e->words_cap};
-    if (!chroma_plan(lim, e->pipeline, cw, ch, planes, &plan)) return JPEGAMD_ERR_TOO_LARGE;
-    const size_t plane_bytes = round_up((size_t)pitch * (size_t)ch, 256);
-    const size_t slot_bytes = round_up(scan_bound(blocks_of(cw, ch)) + 64, 256);      // (k_append_scans_batch reads 16 bytes at a time)
-    const MatrixScratch ms = matrix_scratch(g0.width, g0.height, count, plane_bytes);
+    if (!chroma_plan(e->lim, e->pipeline, cg.cw, cg.ch, planes, &plan)) return JPEGAMD_ERR_TOO_LARGE;
+    const size_t slot_bytes = round_up(scan_bound(blocks_of(cg.cw, cg.ch), kMaxBlockBitsColor) + 64, 256);      // (k_append_scans_batch reads 16 bytes at a time)
+    const MatrixScratch ms = matrix_scratch(g0.width, g0.height, count, cg.plane_bytes);
     rc = color_alloc_consts(e);
     if (rc) return rc;
-    rc = color_batch_alloc(e, mx ? ms.total : (ycc ? 0 : planes * plane_bytes + 256), planes * slot_bytes);
+    rc = color_batch_alloc(e, mx ? ms.total : (ycc ? 0 : planes * cg.plane_bytes + 256), planes * slot_bytes);
     if (rc) return rc;
     // a BT.709 batch: the Y launch is a GRAY batch over the scratch Y planes
     JpegAmdImage gy = g0;
@@ -1190,47 +1262,27 @@ static int32_t color_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, const Plan
     hipEvent_t *const ev_y = ycc ? cev : nullptr;     // a YCbCr batch begins with its Y launch: that kernel's begin stamp opens ns_total
     hipEvent_t ev_planes[2] = {cev ? cev[0] : nullptr, nullptr};      // (a plane pass comes first: ITS begin stamp opens ns_total)
     if (mx) {
-        if (launch_matrix_pass(e, g0, px, *ycc_in, count, subsampling, cw, ch, pitch, plane_bytes, ms, stream,
-                               cev ? (void *const *)ev_planes : nullptr)) return JPEGAMD_ERR_HIP;
+        if (launch_matrix_pass(e, g0, px, *ycc_in, count, subsampling, cg, ms, stream, cev ? (void *const *)ev_planes : nullptr))
+            return JPEGAMD_ERR_HIP;
     } else if (!ycc) {
-        ChromaPlanesBatchArgs pa;
-        std::memset(&pa, 0, sizeof(pa));
-        for (int i = 0; i < count; ++i) { pa.pixels[i] = px.p[0][i]; pa.pixels_g[i] = px.p[1][i]; pa.pixels_b[i] = px.p[2][i]; }
-        pa.layout = g0.channel_order == kOrderPlanar ? kChromaSrcPlanar : (is_px4(g0.channel_order) ? kChromaSrcPx4 : kChromaSrcPx3);
-        pa.batch = count;
-        pa.width = g0.width; pa.height = g0.height; pa.row_stride = g0.row_stride; pa.bottom_up = g0.bottom_up ? 1 : 0;
-        pa.rgb = (g0.channel_order == JPEGAMD_ORDER_BGR || g0.channel_order == JPEGAMD_ORDER_BGRA) ? 0 : 1;
-        pa.mode = chroma_mode(subsampling);
-        pa.cw = cw; pa.ch = ch; pa.pitch = pitch;
-        pa.plane_bytes = plane_bytes; pa.planes = c.bplanes;
-        if (launch_chroma_planes_batch(pa, stream, cev ? (void *const *)ev_planes : nullptr)) return JPEGAMD_ERR_HIP;
+        if (launch_plane_pass(e, g0, px, count, subsampling, cg, stream, cev ? (void *const *)ev_planes : nullptr)) return JPEGAMD_ERR_HIP;
     }
 
     // Y: every picture's scan behind the colour prefix, no EOI; its size into y_size
     {
         uint64_t *sizes[kMaxBatch];
         for (int i = 0; i < count; ++i) sizes[i] = y_size + i;
-        const ScanTarget ty = {c.hdr, c.hdr_len, 0, &lstats[0], false};
+        const ScanTarget ty = {c.hdr, c.hdr_for.len, 0, &lstats[0], false};
         PictureStatsArgs ps = {e->tile_head, e->huff, iy.num_tiles, count, 0, 0, pic};
-        TileSource ysrc = src_of(&gy);
-        if (ycc) {
-            const SourceChoice y = ycbcr_y_source(ycc->layout, ycc->format, ycc->range);
-            ysrc = y.src; iy.select = y.select;
-        }
+        const TileSource ysrc = y_source_of(gy, ycc, &iy);
         if (code_tiles(e, iy, ysrc, &py, &ps, outs_dev, out_capacity, sizes, 1, &ty, stitch_y, stream, ev_y, nullptr)) return JPEGAMD_ERR_HIP;
     }
     // Cb, Cr: plane j (picture j / 2) bare into slot j; its size into c_size[j]
     JpegAmdImage pimg = g0;
-    pimg.width = cw; pimg.height = ch; pimg.row_stride = pitch; pimg.bottom_up = 0; pimg.channel_order = JPEGAMD_ORDER_GRAY;
-    pimg.pixels = c.bplanes;
-    bool ycc_aligned = true;
-    const bool one_plane = ycc && ycc->layout != JPEGAMD_CHROMA_PLANES;      // Cb and Cr of a picture in ONE plane: pairs, or a packed plane
-    if (ycc) {
-        pimg.pixels = ycc->cb[0]; pimg.row_stride = ycc->c_stride;
-        uintptr_t bits = 0;
-        for (int i = 0; i < count; ++i) bits |= (uintptr_t)ycc->cb[i] | (one_plane ? 0 : (uintptr_t)ycc->cr[i]);
-        ycc_aligned = (bits & 3u) == 0;
-    }
+    pimg.width = cg.cw; pimg.height = cg.ch; pimg.row_stride = ycc ? ycc->c_stride : cg.pitch; pimg.bottom_up = 0; pimg.channel_order = JPEGAMD_ORDER_GRAY;
+    pimg.pixels = chroma_plane_of(e, ycc, cg, 0);
+    uintptr_t chroma_bits = 0;                                         // every plane of the call: one answer for all its launches
+    for (int j = 0; j < planes; ++j) chroma_bits |= (uintptr_t)chroma_plane_of(e, ycc, cg, j);
     for (int l = 0; l < plan.launches; ++l) {
         const int first = l * plan.group, n = std::min(plan.group, planes - first);
         ImageDesc ic;
@@ -1240,22 +1292,16 @@ static int32_t color_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, const Plan
         uint64_t *sizes[kMaxBatch];
         for (int i = 0; i < n; ++i) {
             const int j = first + i;                                   // the plane's index in the whole call: picture j / 2, Cb (even) or Cr (odd)
-            if (!ycc) ic.batch_pixels[i] = c.bplanes + (size_t)j * plane_bytes;
-            else if (one_plane) ic.batch_pixels[i] = ycc->cb[j / 2];
-            else ic.batch_pixels[i] = (j & 1) ? ycc->cr[j / 2] : ycc->cb[j / 2];
-            outs[i] = c.bscans + (size_t)(first + i) * slot_bytes;
-            sizes[i] = c_size + first + i;
+            ic.batch_pixels[i] = chroma_plane_of(e, ycc, cg, j);
+            outs[i] = c.bscans + (size_t)j * slot_bytes;
+            sizes[i] = c_size + j;
         }
         ic.pixels = ic.batch_pixels[0];
         ic.batch = n;
         ic.tile_end = n * ic.num_tiles;
         ic.seg_end = n * ic.num_segs;
-        if (!ycc_aligned) ic.fast_ok = 0;
-        TileSource csrc = {kSrcPlane, true};
-        if (ycc) {
-            const SourceChoice cs = ycbcr_chroma_source(ycc->layout, ycc->format, ycc->range, first);
-            csrc = cs.src; ic.select = cs.select;
-        }
+        ic.fast_ok = dword_loader_ok(chroma_bits, pimg.row_stride);
+        const TileSource csrc = chroma_source_of(ycc, first, &ic);
         const ScanTarget tc = {c.hdr, 0, 0, &lstats[1 + l], true};
         PictureStatsArgs ps = {e->tile_head, c.huff, ic.num_tiles, n, 1, first, pic};
         if (code_tiles(e, ic, csrc, nullptr, &ps, outs, slot_bytes, sizes, 1, &tc, plan.stitch, stream, nullptr, nullptr)) return JPEGAMD_ERR_HIP;
@@ -1264,7 +1310,7 @@ static int32_t color_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, const Plan
     std::memset(&aa, 0, sizeof(aa));
     for (int i = 0; i < count; ++i) { aa.out[i] = (uint8_t *)outs_dev[i]; aa.out_size[i] = out_sizes_dev[i]; }
     aa.out_capacity = out_capacity;
-    aa.batch = count; aa.hdr_len = c.hdr_len;
+    aa.batch = count; aa.hdr_len = c.hdr_for.len;
     aa.y_size = y_size; aa.c_size = c_size;
     aa.scans = c.bscans; aa.slot_bytes = slot_bytes;
     aa.sos = c.hdr + kColorPrefixMax;
@@ -1285,15 +1331,8 @@ extern "C" int32_t jpegamd_encode_color_batch_async(JpegAmdEncoder *e, const Jpe
     const JpegAmdImage &g0 = imgs[0];
     if (g0.channel_order != JPEGAMD_ORDER_BGR && g0.channel_order != JPEGAMD_ORDER_RGB && !is_px4(g0.channel_order)) return JPEGAMD_ERR_ARG;
     if (g0.width <= 0 || g0.row_stride < bytes_per_pixel(g0.channel_order) * (int64_t)g0.width) return JPEGAMD_ERR_ARG;
-    PlaneSet ps = {};
-    for (int i = 0; i < count; ++i) {
-        const JpegAmdImage &g = imgs[i];
-        if (!outs_dev[i] || !out_sizes_dev[i] || !g.pixels) return JPEGAMD_ERR_ARG;
-        if (g.width != g0.width || g.height != g0.height || g.row_stride != g0.row_stride || (g.bottom_up != 0) != (g0.bottom_up != 0) ||
-            g.channel_order != g0.channel_order || g.quality != g0.quality)
-            return JPEGAMD_ERR_ARG;
-        ps.p[0][i] = (const uint8_t *)g.pixels;
-    }
+    PlaneSet ps;
+    if (int32_t rc = uniform_batch_args(imgs, count, outs_dev, out_sizes_dev, &ps)) return rc;
     return color_batch(e, g0, ps, count, subsampling, outs_dev, out_capacity, out_sizes_dev, stream_);
 }
 
@@ -1340,8 +1379,7 @@ static int32_t ycbcr_args(const JpegAmdEncoder *e, const JpegAmdYCbCrImage *imgs
     if (packed && subsampling != JPEGAMD_SUBSAMPLE_422) return JPEGAMD_ERR_ARG;
     if (p0.width <= 0 || p0.height <= 0 || p0.width > 65535 || p0.height > 65535) return JPEGAMD_ERR_ARG;
     const bool pair = p0.chroma_layout != JPEGAMD_CHROMA_PLANES && !packed;
-    int cw, ch;
-    chroma_dims(p0.width, p0.height, subsampling, &cw, &ch);
+    const int cw = chroma_geom(p0.width, p0.height, subsampling).cw;
     if (packed ? p0.y_stride < 4 * cw : (p0.y_stride < bps * p0.width || p0.c_stride < bps * (pair ? 2 * cw : cw))) return JPEGAMD_ERR_ARG;
     *ps = PlaneSet{};
     *ycc = YccSource{};
@@ -1404,21 +1442,18 @@ extern "C" int32_t jpegamd_debug_ycbcr_matrix_planes(JpegAmdEncoder *e, const Jp
     if (int32_t rc = ycbcr_args(e, imgs, count, subsampling, sample_range, sample_format, matrix, nullptr, nullptr, false, &g0, &ps, &ycc, nullptr))
         return rc;
     if (matrix != JPEGAMD_MATRIX_BT709) return JPEGAMD_ERR_ARG;
-    int cw, ch;
-    chroma_dims(g0.width, g0.height, subsampling, &cw, &ch);
-    const int pitch = (cw + 3) / 4 * 4;
-    const size_t plane_bytes = round_up((size_t)pitch * (size_t)ch, 256);
-    const MatrixScratch ms = matrix_scratch(g0.width, g0.height, count, plane_bytes);
+    const ChromaGeom cg = chroma_geom(g0.width, g0.height, subsampling);
+    const MatrixScratch ms = matrix_scratch(g0.width, g0.height, count, cg.plane_bytes);
     if (int32_t rc = color_batch_alloc(e, ms.total, 0)) return rc;
     hipStream_t stream = (hipStream_t)stream_;
-    if (launch_matrix_pass(e, g0, ps, ycc, count, subsampling, cw, ch, pitch, plane_bytes, ms, stream, nullptr)) return JPEGAMD_ERR_HIP;
+    if (launch_matrix_pass(e, g0, ps, ycc, count, subsampling, cg, ms, stream, nullptr)) return JPEGAMD_ERR_HIP;
     const uint8_t *base = e->color.bplanes;
     for (int i = 0; i < count; ++i) {
         HIP_TRY(hipMemcpy2DAsync((uint8_t *)y_out + (size_t)i * g0.width * g0.height, (size_t)g0.width, base + ms.y_off + (size_t)i * ms.yplane_bytes,
                                  (size_t)ms.ypitch, (size_t)g0.width, (size_t)g0.height, hipMemcpyDeviceToDevice, stream));
         for (int k = 0; k < 2; ++k)
-            HIP_TRY(hipMemcpy2DAsync((uint8_t *)(k ? cr_out : cb_out) + (size_t)i * cw * ch, (size_t)cw, base + (size_t)(2 * i + k) * plane_bytes,
-                                     (size_t)pitch, (size_t)cw, (size_t)ch, hipMemcpyDeviceToDevice, stream));
+            HIP_TRY(hipMemcpy2DAsync((uint8_t *)(k ? cr_out : cb_out) + (size_t)i * cg.cw * cg.ch, (size_t)cg.cw, base + (size_t)(2 * i + k) * cg.plane_bytes,
+                                     (size_t)cg.pitch, (size_t)cg.cw, (size_t)cg.ch, hipMemcpyDeviceToDevice, stream));
     }
     HIP_TRY(hipStreamSynchronize(stream));
     return JPEGAMD_OK;
@@ -1456,7 +1491,8 @@ extern "C" int32_t jpegamd_encode_ycbcr_batch_async(JpegAmdEncoder *e, const Jpe
 // scratch.  jpegamd_encoder_set_pipeline has no effect here: k_stitch reads tile records.
 // ---------------------------------------------------------------------------------------------------------
 struct McuGeometry {
-    int hs, vs, bw, bh, mx, my, cw, ch, seg_mcus, num_segs, num_segs_pad;
+    int hs, vs, bw, bh, mx, my, seg_mcus, num_segs, num_segs_pad;
+    ChromaGeom chroma;
     size_t coef_per_pic;                // int16 elements
 };
 static McuGeometry mcu_geometry(int w, int h, int sub) {
@@ -1465,7 +1501,7 @@ static McuGeometry mcu_geometry(int w, int h, int sub) {
     g.vs = sub == JPEGAMD_SUBSAMPLE_420 ? 2 : 1;
     g.bw = (w + 7) / 8; g.bh = (h + 7) / 8;
     g.mx = (g.bw + g.hs - 1) / g.hs; g.my = (g.bh + g.vs - 1) / g.vs;
-    chroma_dims(w, h, sub, &g.cw, &g.ch);
+    g.chroma = chroma_geom(w, h, sub);
     g.seg_mcus = mcu_seg_mcus(g.hs, g.vs);
     g.num_segs = (int)(((int64_t)g.mx * g.my + g.seg_mcus - 1) / g.seg_mcus);
     g.num_segs_pad = (g.num_segs + kSegGroup - 1) / kSegGroup * kSegGroup;
@@ -1477,7 +1513,7 @@ extern "C" uint64_t jpegamd_max_jfif_bytes_interleaved(int32_t width, int32_t he
     if (width <= 0 || height <= 0 || width > 65535 || height > 65535 || !sub_valid(subsampling)) return 0;
     const McuGeometry g = mcu_geometry(width, height, subsampling);
     // the prefix, every block of every MCU (pad blocks too) at the worst case with every byte stuffed, the flush byte, EOI
-    return kColorPrefixMax + scan_bound((uint64_t)g.mx * (uint64_t)g.my * (uint64_t)(g.hs * g.vs + 2)) + 2 + 16;
+    return kColorPrefixMax + scan_bound((uint64_t)g.mx * (uint64_t)g.my * (uint64_t)(g.hs * g.vs + 2), kMaxBlockBitsColor) + 2 + 16;
 }
 
 constexpr int kMcuSosBytes = 14;
@@ -1491,26 +1527,13 @@ static int32_t mcu_alloc(JpegAmdEncoder *e, const McuGeometry &g, int group) {
         HIP_TRY(hipMalloc((void **)&m.scan_stats, sizeof(ScanStats)));
     }
     const size_t coef = (size_t)group * g.coef_per_pic, segs = (size_t)group * (size_t)g.num_segs_pad;
-    if (coef > m.coef_cap || segs > m.segs_cap) {
-        if (e->pending) HIP_TRY(hipStreamSynchronize(e->last_stream));
-        if (coef > m.coef_cap) {
-            hipFree(m.coef); m.coef = nullptr; m.coef_cap = 0;
-            HIP_TRY(hipMalloc((void **)&m.coef, coef * sizeof(int16_t)));
-            m.coef_cap = coef;
-        }
-        if (segs > m.segs_cap) {
-            hipFree(m.seg.words); hipFree(m.seg.bits); hipFree(m.seg.syms); hipFree(m.seg.exact); hipFree(m.seg.edge); hipFree(m.seg.ffin);
-            m.seg = SegArrays{}; m.segs_cap = 0;
-            const size_t n = segs + 16;                               // k_finalize reads the per-segment arrays four at a time
-            HIP_TRY(hipMalloc((void **)&m.seg.words, (segs + 1) * (size_t)kSegCapWords * sizeof(uint32_t)));
-            HIP_TRY(hipMalloc((void **)&m.seg.bits, n * sizeof(uint32_t)));
-            HIP_TRY(hipMalloc((void **)&m.seg.syms, n * sizeof(uint32_t)));
-            HIP_TRY(hipMalloc((void **)&m.seg.exact, n * sizeof(uint32_t)));
-            HIP_TRY(hipMalloc((void **)&m.seg.edge, n * sizeof(uint32_t)));
-            HIP_TRY(hipMalloc((void **)&m.seg.ffin, n * 8 * sizeof(uint16_t)));
-            m.seg.words_stride = kSegCapWords;
-            m.segs_cap = segs;
-        }
+    if (int32_t rc = grow_scratch(e, &m.coef, &m.coef_cap, coef)) return rc;
+    if (segs > m.segs_cap) {                                          // (grow_scratch's steps over a set of arrays)
+        if (int32_t rc = wait_pending(e)) return rc;
+        free_seg_arrays(&m.seg);
+        m.segs_cap = 0;
+        if (int32_t rc = alloc_seg_arrays(&m.seg, segs, (segs + 1) * (size_t)kSegCapWords, false)) return rc;
+        m.segs_cap = segs;
     }
     return JPEGAMD_OK;
 }
@@ -1519,17 +1542,16 @@ static int32_t mcu_alloc(JpegAmdEncoder *e, const McuGeometry &g, int group) {
 static int32_t prepare_mcu_prefix(JpegAmdEncoder *e, const JpegAmdImage *img, int sub) {
     auto &m = e->mcu;
     const int q = clamp_quality(img->quality);
-    if (m.hdr_w == img->width && m.hdr_h == img->height && m.hdr_q == q && m.hdr_sub == sub) return JPEGAMD_OK;
+    if (m.hdr_for.matches(img->width, img->height, q, sub)) return JPEGAMD_OK;
     uint8_t luma[64], chroma[64], hdr[kColorPrefixMax + kMcuSosBytes];
     quant_table_for_quality(q, luma);
     chroma_quant_table_for_quality(q, chroma);
     const size_t n = build_jfif_prefix_color(img->width, img->height, luma, chroma, chroma_mode(sub), hdr) - kSosBytes;
     const uint8_t sos[kMcuSosBytes] = {0xFF, 0xDA, 0x00, 0x0C, 0x03, 0x01, 0x00, 0x02, 0x11, 0x03, 0x11, 0x00, 0x3F, 0x00};
     std::memcpy(hdr + n, sos, sizeof(sos));
-    if (e->pending) HIP_TRY(hipStreamSynchronize(e->last_stream));
+    if (int32_t rc = wait_pending(e)) return rc;
     HIP_TRY(hipMemcpy(m.hdr, hdr, n + sizeof(sos), hipMemcpyHostToDevice));
-    m.hdr_len = (int)(n + sizeof(sos));
-    m.hdr_w = img->width; m.hdr_h = img->height; m.hdr_q = q; m.hdr_sub = sub;
+    m.hdr_for.set(img->width, img->height, q, sub, (int)(n + sizeof(sos)));
     return JPEGAMD_OK;
 }
 
@@ -1543,9 +1565,9 @@ static int32_t interleaved_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, cons
     ImageDesc iy;
     int32_t rc = describe(e, &g0, &iy);
     if (rc) return rc;
-    const int pitch = (g.cw + 3) / 4 * 4;
+    const ChromaGeom &cg = g.chroma;
     JpegAmdImage pimg = g0;
-    pimg.width = g.cw; pimg.height = g.ch; pimg.row_stride = ycc ? ycc->c_stride : pitch; pimg.bottom_up = 0; pimg.channel_order = JPEGAMD_ORDER_GRAY;
+    pimg.width = cg.cw; pimg.height = cg.ch; pimg.row_stride = ycc ? ycc->c_stride : cg.pitch; pimg.bottom_up = 0; pimg.channel_order = JPEGAMD_ORDER_GRAY;
     pimg.pixels = ycc ? ycc->cb[0] : g0.pixels;                      // (a non-null placeholder: every launch sets its own plane)
     ImageDesc ic;
     rc = describe(e, &pimg, &ic);
@@ -1554,10 +1576,9 @@ static int32_t interleaved_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, cons
 
     const size_t per_pic = g.coef_per_pic * sizeof(int16_t) + (size_t)g.num_segs_pad * kSegCapWords * sizeof(uint32_t);
     const int group = (int)std::max<size_t>(1, std::min<size_t>((size_t)count, kMcuScratchBudget / per_pic));
-    const size_t plane_bytes = round_up((size_t)pitch * (size_t)g.ch, 256);
     rc = color_alloc_consts(e);
     if (rc) return rc;
-    rc = color_batch_alloc(e, ycc ? 0 : 2 * (size_t)count * plane_bytes + 256, 0);
+    rc = color_batch_alloc(e, ycc ? 0 : 2 * (size_t)count * cg.plane_bytes + 256, 0);
     if (rc) return rc;
     rc = mcu_alloc(e, g, group);
     if (rc) return rc;
@@ -1580,19 +1601,7 @@ static int32_t interleaved_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, cons
     HIP_TRY(hipMemsetAsync(m.scan_stats, 0, sizeof(ScanStats), stream));
     HIP_TRY(hipMemsetAsync(e->stats_dev, 0, offsetof(ScanStats, status), stream));      // the sums and the size; the status stays sticky
 
-    if (!ycc) {
-        ChromaPlanesBatchArgs pa;
-        std::memset(&pa, 0, sizeof(pa));
-        for (int i = 0; i < count; ++i) pa.pixels[i] = px.p[0][i];
-        pa.layout = kChromaSrcPx3;
-        pa.batch = count;
-        pa.width = g0.width; pa.height = g0.height; pa.row_stride = g0.row_stride; pa.bottom_up = g0.bottom_up ? 1 : 0;
-        pa.rgb = g0.channel_order == JPEGAMD_ORDER_BGR ? 0 : 1;
-        pa.mode = chroma_mode(subsampling);
-        pa.cw = g.cw; pa.ch = g.ch; pa.pitch = pitch;
-        pa.plane_bytes = plane_bytes; pa.planes = c.bplanes;
-        if (launch_chroma_planes_batch(pa, stream, nullptr)) return JPEGAMD_ERR_HIP;
-    }
+    if (!ycc && launch_plane_pass(e, g0, px, count, subsampling, cg, stream, nullptr)) return JPEGAMD_ERR_HIP;
     const size_t cb_off = (size_t)g.bw * g.bh * 64, cr_off = cb_off + (size_t)g.mx * g.my * 64;
     for (int first = 0; first < count; first += group) {
         const int n = std::min(group, count - first);
@@ -1601,30 +1610,16 @@ static int32_t interleaved_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, cons
             int16_t *coef = m.coef + (size_t)i * g.coef_per_pic;
             {   // Y
                 ImageDesc im = iy;
-                im.pixels = px.p[0][p];
-                for (int k = 0; k < kMaxBatch; ++k) im.batch_pixels[k] = im.pixels;
-                im.fast_ok = ((((uintptr_t)im.pixels) & 3u) == 0 && (g0.row_stride & 3) == 0 && g0.row_stride < (1 << 24)) ? 1 : 0;
-                TileSource src = src_of(&g0);
-                if (ycc) {
-                    const SourceChoice y = ycbcr_y_source(ycc->layout, ycc->format, ycc->range);
-                    src = y.src; im.select = y.select;
-                }
+                set_single_picture(&im, px.p[0][p]);
+                const TileSource src = y_source_of(g0, ycc, &im);
                 if (launch_transform(e, im, true, nullptr, coef, nullptr, stream, nullptr, src)) return JPEGAMD_ERR_HIP;
                 const PictureStatsArgs ps = {e->tile_head, e->huff, im.num_tiles, 1, 0, 0, pic + (size_t)p * kPicStatWords};
                 if (launch_picture_stats(ps, stream)) return JPEGAMD_ERR_HIP;
             }
-            const bool one_plane = ycc && ycc->layout != JPEGAMD_CHROMA_PLANES;
-            for (int k = 0; k < 2; ++k) {   // Cb, Cr
+            for (int k = 0; k < 2; ++k) {   // Cb, Cr: planes 2 p and 2 p + 1 of the call
                 ImageDesc im = ic;
-                if (!ycc) im.pixels = c.bplanes + (size_t)(2 * p + k) * plane_bytes;
-                else im.pixels = (one_plane || k == 0) ? ycc->cb[p] : ycc->cr[p];
-                for (int j = 0; j < kMaxBatch; ++j) im.batch_pixels[j] = im.pixels;
-                im.fast_ok = ((((uintptr_t)im.pixels) & 3u) == 0 && (pimg.row_stride & 3) == 0 && pimg.row_stride < (1 << 24)) ? 1 : 0;
-                TileSource src = {kSrcPlane, true};
-                if (ycc) {
-                    const SourceChoice cs = ycbcr_chroma_source(ycc->layout, ycc->format, ycc->range, k);
-                    src = cs.src; im.select = cs.select;
-                }
+                set_single_picture(&im, chroma_plane_of(e, ycc, cg, 2 * p + k));
+                const TileSource src = chroma_source_of(ycc, 2 * p + k, &im);
                 if (launch_transform(e, im, true, nullptr, coef + (k ? cr_off : cb_off), nullptr, stream, nullptr, src)) return JPEGAMD_ERR_HIP;
                 const PictureStatsArgs ps = {e->tile_head, c.huff, im.num_tiles, 1, 1, 2 * p + k, pic};
                 if (launch_picture_stats(ps, stream)) return JPEGAMD_ERR_HIP;
@@ -1642,13 +1637,13 @@ static int32_t interleaved_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, cons
 
         ImageDesc is = iy;                                           // what run_finalize reads of it: the segments per picture and their length
         is.num_segs = g.num_segs_pad; is.seg_tiles = kSegTiles;
-        const ScanTarget tgt = {m.hdr, m.hdr_len, 1, m.scan_stats, false, &m.seg};
+        const ScanTarget tgt = {m.hdr, m.hdr_for.len, 1, m.scan_stats, false, &m.seg};
         if (run_finalize(e, is, outs_dev + first, out_capacity, out_sizes_dev + first, 1, stream, nullptr, n, false, &tgt)) return JPEGAMD_ERR_HIP;
 
         McuTotalsArgs ta;
         std::memset(&ta, 0, sizeof(ta));
         ta.seg = m.seg;
-        ta.num_segs_pad = g.num_segs_pad; ta.prefix_len = m.hdr_len;
+        ta.num_segs_pad = g.num_segs_pad; ta.prefix_len = m.hdr_for.len;
         ta.last_of_call = first + n == count ? 1 : 0;
         for (int i = 0; i < n; ++i) ta.out_size[i] = out_sizes_dev[first + i];
         ta.out_capacity = out_capacity;
@@ -1669,15 +1664,8 @@ extern "C" int32_t jpegamd_encode_color_interleaved_batch_async(JpegAmdEncoder *
     const JpegAmdImage &g0 = imgs[0];
     if (g0.channel_order != JPEGAMD_ORDER_BGR && g0.channel_order != JPEGAMD_ORDER_RGB) return JPEGAMD_ERR_ARG;
     if (g0.width <= 0 || g0.height <= 0 || g0.width > 65535 || g0.height > 65535 || g0.row_stride < 3 * (int64_t)g0.width) return JPEGAMD_ERR_ARG;
-    PlaneSet ps = {};
-    for (int i = 0; i < count; ++i) {
-        const JpegAmdImage &g = imgs[i];
-        if (!outs_dev[i] || !out_sizes_dev[i] || !g.pixels) return JPEGAMD_ERR_ARG;
-        if (g.width != g0.width || g.height != g0.height || g.row_stride != g0.row_stride || (g.bottom_up != 0) != (g0.bottom_up != 0) ||
-            g.channel_order != g0.channel_order || g.quality != g0.quality)
-            return JPEGAMD_ERR_ARG;
-        ps.p[0][i] = (const uint8_t *)g.pixels;
-    }
+    PlaneSet ps;
+    if (int32_t rc = uniform_batch_args(imgs, count, outs_dev, out_sizes_dev, &ps)) return rc;
     return interleaved_batch(e, g0, ps, count, subsampling, outs_dev, out_capacity, out_sizes_dev, stream_);
 }
 
@@ -1745,7 +1733,7 @@ extern "C" int32_t jpegamd_debug_stages(JpegAmdEncoder *e, const JpegAmdImage *i
 // Fault injection (tests): the next encode on this context finds `value` in word 0 (the string's bit count) of tile `tile`'s
 // record when k_segment_merge reads it.  Not part of the public header.
 extern "C" int32_t jpegamd_debug_poison_tile_record(JpegAmdEncoder *e, int32_t tile, uint32_t value) {
-    if (!e || tile < 0 || tile >= e->max_tiles) return JPEGAMD_ERR_ARG;
+    if (!e || tile < 0 || tile >= e->lim.max_tiles) return JPEGAMD_ERR_ARG;
     e->poison_tile = tile;
     e->poison_value = value;
     return JPEGAMD_OK;
@@ -1754,7 +1742,7 @@ extern "C" int32_t jpegamd_debug_poison_tile_record(JpegAmdEncoder *e, int32_t t
 // Diagnostic: copy the per-wave phase cycle sums of the last launch (null unless JPEGAMD_STAMPS is set
 // in the environment AND the library was built with -DJPEGAMD_STAMPS).  Not part of the public header.
 extern "C" int32_t jpegamd_debug_read_stamps(JpegAmdEncoder *e, unsigned long long *host, int64_t nwaves) {
-    if (!e || !e->stamps_dev || !host || nwaves > (int64_t)(stamp_words(e->max_segs) / 16)) return JPEGAMD_ERR_ARG;
+    if (!e || !e->stamps_dev || !host || nwaves > (int64_t)(stamp_words(e->lim.max_segs) / 16)) return JPEGAMD_ERR_ARG;
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(host, e->stamps_dev, (size_t)nwaves * 16 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     return JPEGAMD_OK;
@@ -1868,7 +1856,7 @@ extern "C" int32_t convertToJpeg(JPEG_COMPRESSION_DTO *dto) {
     }
     // the six stage counters (jpeg_compression.c:188-210) come from the STAMPED variant of the fused kernel: the same code with its
     // phases bracketed by cycle-counter reads (~10 % slower; the asynchronous entry points never run it)
-    const size_t stamp_bytes = stamp_words(e->max_segs) * sizeof(unsigned long long);
+    const size_t stamp_bytes = stamp_words(e->lim.max_segs) * sizeof(unsigned long long);
     if (!e->stamps_dev) HIP_TRY(hipMalloc((void **)&e->stamps_dev, stamp_bytes));
     HIP_TRY(hipMemsetAsync(e->stamps_dev, 0, stamp_bytes, nullptr));
     e->stamp_next = true;

@@ -213,6 +213,39 @@ def test_batch_of_thirty_two(jpegamd, oracle, dev, enc):
     assert st.entropy_bits == sum(m.scan_bits for m in ms) and st.stuffed_bytes == sum(m.stuffed for m in ms)
 
 
+def scratch_need(count, w, h, sub):
+    """(coefficients, segments) the path's scratch must hold for one call, as the host sizes it: per picture every Y block and every
+    chroma block of every MCU at 64 coefficients, and the segments of a picture padded to a multiple of 4 (one group of k_finalize's
+    aggregates); a call this small goes through as one group of `count` pictures."""
+    _, _, bw, bh, mx, my = im.geometry(w, h, sub)
+    return count * (bw * bh + 2 * mx * my) * 64, count * -(-im.segment_count(w, h, sub) // 4) * 4
+
+
+def test_scratch_grown_behind_queued_work(jpegamd, oracle, dev):
+    """Four calls queued on a fresh context with one finish at the end.  The first sizes the scratch.  The second (the 200 x 120
+    picture, five segments where the first had one per picture) needs larger coefficient planes but, padded, no more segments; the
+    third (twelve small pictures) needs more segments but no more coefficients, so the segment arrays are replaced on their own; the
+    fourth is the first again, on the scratch the others left.  Every file is compared byte for byte.  The needs are asserted from
+    the model so that each replacement does happen; whether a replacement waits for the queued work is not something a passing run
+    can show."""
+    small = gs.pictures(jpegamd, 16, 16, 2, seed=61)
+    large = gs.synth_rgb(jpegamd, 200, 120, 62, 0)
+    many = gs.pictures(jpegamd, 16, 16, 12, seed=63)
+    assert im.segment_count(16, 16, S420) == 1 and im.segment_count(200, 120, S444) == 5
+    needs = [scratch_need(2, 16, 16, S420), scratch_need(1, 200, 120, S444), scratch_need(12, 16, 16, S420)]
+    assert needs == [(768, 8), (72000, 8), (4608, 48)]              # coefficients grow in the second call, segments in the third
+    want_small = [model(oracle, r, 50, S420).file for r in small]
+    e = jpegamd.Encoder(512, gs.rows_for(32, 16))
+    try:
+        calls = [RgbCall(jpegamd, e, small, dev, S420, 50), RgbCall(jpegamd, e, [large], dev, S444, 50),
+                 RgbCall(jpegamd, e, many, dev, S420, 50), RgbCall(jpegamd, e, small, dev, S420, 50)]
+        e.finish()
+        got = [gs.intact_files(c) for c in calls]
+    finally:
+        e.close()
+    assert got == [want_small, [model(oracle, large, 50, S444).file], [model(oracle, r, 50, S420).file for r in many], want_small]
+
+
 # ---- the YCbCr entry ------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("sub", SUBS)
 def test_ycbcr_layouts_give_one_file(jpegamd, oracle, dev, enc, sub):
