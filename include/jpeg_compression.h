@@ -347,6 +347,41 @@ int32_t jpegamd_encode_ycbcr_interleaved_batch_async(JpegAmdEncoder *enc, const 
  * nb = mx * my * (hs * vs + 2) blocks, pad blocks included (jpegamd_max_jfif_bytes_color does not count those); 0 for bad args. */
 uint64_t jpegamd_max_jfif_bytes_interleaved(int32_t width, int32_t height, int32_t subsampling);
 
+/* The one-scan files with RESTART INTERVALS (DRI / RSTn, T.81 B.2.4.4, E.1.4) -- what an RTP/JPEG sender puts into
+ * its restart header (RFC 2435) so that a lost packet costs one interval, what a decoder uses to decode a scan in parallel, and what
+ * libjpeg's -restart writes.  restart_interval = Ri is in MCUs, 1 .. 65535; with M = mx * my MCUs the scan has n = ceil(M / Ri)
+ * intervals.  The file:
+ *   1. the prefix of the one-scan file with one DRI segment FF DD 00 04 hi(Ri) lo(Ri) directly in front of the SOS, behind the last
+ *      DHT: 6 bytes longer, nothing else changed;
+ *   2. interval i codes the MCUs [i Ri, min((i + 1) Ri, M)) of the raster MCU order -- block order, tables, ZRL / EOB and the pad-block
+ *      rule (no AC, the DC VALUE of the nearest real block) as above.  At the start of every interval the DC predictors of all three
+ *      components are 0; a pad block's difference is taken against the predictor like any other block's;
+ *   3. every interval but the last: its bit string is padded with 1-bits to a whole byte (nothing when it ends on one), every 0xFF
+ *      byte of it, the padded one included, is followed by a stuffed 0x00, then comes the marker FF D0+(i mod 8), unstuffed;
+ *   4. the last interval ends with the zero-bit flush of the other scans, then EOI; it has no RST marker;
+ *   5. Ri >= M (one interval): the one-scan file of the same picture with the DRI segment inserted, byte for byte.
+ * restart_interval 0: the entry IS the entry without _restart -- same launches, same file, no DRI.  Any other value outside
+ * 1 .. 65535: JPEGAMD_ERR_ARG, refused like every other bad argument before the context is read.  Sources, layouts, subsamplings,
+ * context sizing, refusals, capacity behaviour (size 0, nothing past out_capacity, the other pictures unaffected,
+ * JPEGAMD_ERR_HUFF_CAPACITY from finish, the context usable afterwards), profiling (ns_total only) and set_pipeline are those of the
+ * entries above.  entropy_bits is the sum of the coded bits (pad and flush bits are not counted), stuffed_bytes counts the 0x00
+ * stuffing bytes, those behind padded bytes included, markers not; exact_fallbacks is the three-scan figure.
+ * A segment of the coder never crosses an interval's boundary, so a short interval means many short segments: the path's scratch per
+ * picture is the coefficient planes plus, per segment, a string reserved for min(Ri, S) MCUs (S = 256 / (hs vs + 2)) and 56 bytes of
+ * numbers.  When that exceeds the path's 4 GiB group budget for ONE picture (Ri = 1: from about 15000 x 15000 at 4:4:4, 21500 x 21500 at 4:2:0) the call
+ * answers JPEGAMD_ERR_TOO_LARGE before anything is allocated or launched. */
+int32_t jpegamd_encode_color_interleaved_restart_batch_async(JpegAmdEncoder *enc, const JpegAmdImage *imgs, int32_t count, int32_t subsampling,
+                                                             int32_t restart_interval, void *const *outs_dev, uint64_t out_capacity,
+                                                             uint64_t *const *out_sizes_dev, void *stream);
+int32_t jpegamd_encode_ycbcr_interleaved_restart_batch_async(JpegAmdEncoder *enc, const JpegAmdYCbCrImage *imgs, int32_t count, int32_t subsampling,
+                                                             int32_t restart_interval, void *const *outs_dev, uint64_t out_capacity,
+                                                             void *const *out_sizes_dev, void *stream);
+/* Upper bound on the bytes of the file with restart intervals: jpegamd_max_jfif_bytes_interleaved + 6 + 4 * (n - 1).  That bound holds
+ * the scan's bits rounded up to a byte once with every byte stuffed; the DRI segment adds 6 bytes, and every interval but the last
+ * rounds up on its own -- at most one more byte --, may have that byte stuffed, and ends with two marker bytes.  With
+ * restart_interval 0 it equals jpegamd_max_jfif_bytes_interleaved; 0 for bad arguments (restart_interval outside 0 .. 65535 too). */
+uint64_t jpegamd_max_jfif_bytes_interleaved_restart(int32_t width, int32_t height, int32_t subsampling, int32_t restart_interval);
+
 /* Which kernels follow k_tile_encode for whole pictures (no reference counterpart: a tuning knob, results are byte-identical).
  *   PAIR    k_segment_merge + k_finalize: the tiles' bit strings joined per segment, then stitched behind a kernel boundary;
  *   STITCH  k_stitch: one pass, the offsets handed from workgroup to workgroup inside the launch (decoupled look-back);

@@ -39,8 +39,9 @@ struct CtxLimits {
 // What a header kept on the device was built for, and its length.  Plain data: all zero means "nothing cached" (no picture is 0 wide).
 struct HeaderCache {
     int w, h, q, sub, len;
-    bool matches(int w_, int h_, int q_, int sub_) const { return w == w_ && h == h_ && q == q_ && sub == sub_; }
-    void set(int w_, int h_, int q_, int sub_, int len_) { w = w_; h = h_; q = q_; sub = sub_; len = len_; }
+    int restart;                        // the interval of the DRI segment (files with one: the interleaved path's); 0: none
+    bool matches(int w_, int h_, int q_, int sub_, int restart_ = 0) const { return w == w_ && h == h_ && q == q_ && sub == sub_ && restart == restart_; }
+    void set(int w_, int h_, int q_, int sub_, int len_, int restart_ = 0) { w = w_; h = h_; q = q_; sub = sub_; len = len_; restart = restart_; }
 };
 
 struct JpegAmdEncoder {
@@ -108,7 +109,12 @@ struct JpegAmdEncoder {
         int16_t *coef = nullptr;            // the coefficient planes of one group of pictures
         size_t coef_cap = 0;                // int16 elements
         SegArrays seg = {};                 // the path's own segments (an MCU scan has 1.5 x to 3 x the blocks of the Y scan)
-        size_t segs_cap = 0;
+        size_t segs_cap = 0, words_cap = 0; // entries of the per-segment arrays, words of the strings
+        // restart intervals (jpegamd_encode_*_interleaved_restart_batch_async): what k_mcu_restart_offsets leaves per segment and picture
+        uint32_t *rst_words = nullptr;      // pre, b0, ff: 3 x rst_cap
+        uint64_t *rst_pos = nullptr;
+        unsigned long long *rst_pic_sums = nullptr;   // [kMaxBatch][kMcuPicSums]
+        size_t rst_cap = 0;
         uint8_t *hdr = nullptr;             // the prefix with the three-component SOS
         ScanStats *scan_stats = nullptr;    // k_finalize's record of the call
         HeaderCache hdr_for = {};           // what `hdr` holds
@@ -344,6 +350,7 @@ extern "C" int32_t jpegamd_encoder_destroy(JpegAmdEncoder *e) {
     hipFree(e->color.scan_stats); hipFree(e->color.planes); hipFree(e->color.scans);
     hipFree(e->color.bmeta); hipFree(e->color.bplanes); hipFree(e->color.bscans);
     hipFree(e->mcu.coef); hipFree(e->mcu.hdr); hipFree(e->mcu.scan_stats);
+    hipFree(e->mcu.rst_words); hipFree(e->mcu.rst_pos); hipFree(e->mcu.rst_pic_sums);
     free_seg_arrays(&e->mcu.seg);
     destroy_ring_events(e);
     delete e->tables_host;
@@ -1494,8 +1501,13 @@ struct McuGeometry {
     int hs, vs, bw, bh, mx, my, seg_mcus, num_segs, num_segs_pad;
     ChromaGeom chroma;
     size_t coef_per_pic;                // int16 elements
+    // restart intervals (restart > 0: 4.6.8): the scan's intervals, the segments of each, the picture's last segment that holds MCUs
+    int restart, intervals, segs_per_interval, last_seg;
+    int64_t segs64;                     // num_segs before it is narrowed (restart = 1 on the largest pictures: beyond an int's reach once padded and batched)
+    size_t cap_words;                   // words reserved per segment string
 };
-static McuGeometry mcu_geometry(int w, int h, int sub) {
+// restart: the interval in MCUs, 0 for none.
+static McuGeometry mcu_geometry(int w, int h, int sub, int restart = 0) {
     McuGeometry g;
     g.hs = sub == JPEGAMD_SUBSAMPLE_444 ? 1 : 2;
     g.vs = sub == JPEGAMD_SUBSAMPLE_420 ? 2 : 1;
@@ -1503,10 +1515,24 @@ static McuGeometry mcu_geometry(int w, int h, int sub) {
     g.mx = (g.bw + g.hs - 1) / g.hs; g.my = (g.bh + g.vs - 1) / g.vs;
     g.chroma = chroma_geom(w, h, sub);
     g.seg_mcus = mcu_seg_mcus(g.hs, g.vs);
-    g.num_segs = (int)(((int64_t)g.mx * g.my + g.seg_mcus - 1) / g.seg_mcus);
+    const int64_t mcus = (int64_t)g.mx * g.my;
+    g.restart = restart;
+    g.intervals = restart ? (int)((mcus + restart - 1) / restart) : 1;
+    g.segs_per_interval = (int)((std::min<int64_t>(restart ? restart : mcus, mcus) + g.seg_mcus - 1) / g.seg_mcus);
+    g.segs64 = (int64_t)g.intervals * g.segs_per_interval;          // (no restart: ceil(mcus / seg_mcus), as ever)
+    g.num_segs = (int)std::min<int64_t>(g.segs64, INT32_MAX / 2);
     g.num_segs_pad = (g.num_segs + kSegGroup - 1) / kSegGroup * kSegGroup;
+    const int64_t in_last = mcus - (int64_t)(g.intervals - 1) * (restart ? restart : 0);     // MCUs of the last interval
+    g.last_seg = (int)std::min<int64_t>((int64_t)(g.intervals - 1) * g.segs_per_interval + (in_last + g.seg_mcus - 1) / g.seg_mcus - 1, INT32_MAX / 2);
+    g.cap_words = restart ? (size_t)mcu_restart_cap_words(std::min(restart, g.seg_mcus) * (g.hs * g.vs + 2)) : (size_t)kSegCapWords;
     g.coef_per_pic = ((size_t)g.bw * g.bh + 2 * (size_t)g.mx * g.my) * 64;
     return g;
+}
+// Bytes of the path's scratch one picture takes in the group budget: its coefficient planes and its segment strings; with restart
+// intervals -- segments may be as short as one MCU -- the per-segment numbers as well, the coder's and the writer's (56 bytes).
+static uint64_t mcu_scratch_per_pic(const McuGeometry &g) {
+    const uint64_t segs = (uint64_t)(g.segs64 + kSegGroup - 1) / kSegGroup * kSegGroup;
+    return (uint64_t)g.coef_per_pic * sizeof(int16_t) + segs * (uint64_t)g.cap_words * sizeof(uint32_t) + (g.restart ? segs * 56u : 0u);
 }
 
 extern "C" uint64_t jpegamd_max_jfif_bytes_interleaved(int32_t width, int32_t height, int32_t subsampling) {
@@ -1514,6 +1540,19 @@ extern "C" uint64_t jpegamd_max_jfif_bytes_interleaved(int32_t width, int32_t he
     const McuGeometry g = mcu_geometry(width, height, subsampling);
     // the prefix, every block of every MCU (pad blocks too) at the worst case with every byte stuffed, the flush byte, EOI
     return kColorPrefixMax + scan_bound((uint64_t)g.mx * (uint64_t)g.my * (uint64_t)(g.hs * g.vs + 2), kMaxBlockBitsColor) + 2 + 16;
+}
+
+constexpr int kMcuDriBytes = 6;          // FF DD 00 04 hi lo
+
+extern "C" uint64_t jpegamd_max_jfif_bytes_interleaved_restart(int32_t width, int32_t height, int32_t subsampling, int32_t restart_interval) {
+    const uint64_t plain = jpegamd_max_jfif_bytes_interleaved(width, height, subsampling);
+    if (!plain || restart_interval < 0 || restart_interval > 65535) return 0;
+    if (!restart_interval) return plain;
+    // The plain bound holds the scan's bits rounded up to a byte ONCE, every byte stuffed.  With n intervals the DRI segment is 6
+    // bytes, and every interval but the last rounds up by itself -- at most one more byte --, may have that byte stuffed, and ends
+    // with a two-byte marker: 4 (n - 1).
+    const McuGeometry g = mcu_geometry(width, height, subsampling, restart_interval);
+    return plain + kMcuDriBytes + 4 * (uint64_t)(g.intervals - 1);
 }
 
 constexpr int kMcuSosBytes = 14;
@@ -1527,40 +1566,60 @@ static int32_t mcu_alloc(JpegAmdEncoder *e, const McuGeometry &g, int group) {
         HIP_TRY(hipMalloc((void **)&m.scan_stats, sizeof(ScanStats)));
     }
     const size_t coef = (size_t)group * g.coef_per_pic, segs = (size_t)group * (size_t)g.num_segs_pad;
+    const size_t words = (segs + 1) * g.cap_words;                    // (strings of either length share the array: a call sets its own stride)
     if (int32_t rc = grow_scratch(e, &m.coef, &m.coef_cap, coef)) return rc;
-    if (segs > m.segs_cap) {                                          // (grow_scratch's steps over a set of arrays)
+    if (segs > m.segs_cap || words > m.words_cap) {                   // (grow_scratch's steps over a set of arrays)
         if (int32_t rc = wait_pending(e)) return rc;
+        const size_t new_segs = std::max(segs, m.segs_cap), new_words = std::max(words, m.words_cap);
         free_seg_arrays(&m.seg);
-        m.segs_cap = 0;
-        if (int32_t rc = alloc_seg_arrays(&m.seg, segs, (segs + 1) * (size_t)kSegCapWords, false)) return rc;
-        m.segs_cap = segs;
+        m.segs_cap = m.words_cap = 0;
+        if (int32_t rc = alloc_seg_arrays(&m.seg, new_segs, new_words, false)) return rc;
+        m.segs_cap = new_segs; m.words_cap = new_words;
+    }
+    if (g.restart && segs > m.rst_cap) {
+        if (int32_t rc = wait_pending(e)) return rc;
+        hipFree(m.rst_words); hipFree(m.rst_pos); m.rst_words = nullptr; m.rst_pos = nullptr; m.rst_cap = 0;
+        if (!m.rst_pic_sums) HIP_TRY(hipMalloc((void **)&m.rst_pic_sums, kMaxBatch * kMcuPicSums * sizeof(unsigned long long)));
+        HIP_TRY(hipMalloc((void **)&m.rst_words, 3 * segs * sizeof(uint32_t)));
+        HIP_TRY(hipMalloc((void **)&m.rst_pos, segs * sizeof(uint64_t)));
+        m.rst_cap = segs;
     }
     return JPEGAMD_OK;
 }
 
-// The colour prefix up to its DHTs, then the SOS of all three components (Y: tables 0 / 0, Cb and Cr: 1 / 1).
-static int32_t prepare_mcu_prefix(JpegAmdEncoder *e, const JpegAmdImage *img, int sub) {
+// The colour prefix up to its DHTs, [DRI with the restart interval,] then the SOS of all three components (Y: tables 0 / 0, Cb and
+// Cr: 1 / 1).
+static int32_t prepare_mcu_prefix(JpegAmdEncoder *e, const JpegAmdImage *img, int sub, int restart) {
     auto &m = e->mcu;
     const int q = clamp_quality(img->quality);
-    if (m.hdr_for.matches(img->width, img->height, q, sub)) return JPEGAMD_OK;
-    uint8_t luma[64], chroma[64], hdr[kColorPrefixMax + kMcuSosBytes];
+    if (m.hdr_for.matches(img->width, img->height, q, sub, restart)) return JPEGAMD_OK;
+    uint8_t luma[64], chroma[64], hdr[kColorPrefixMax + kMcuDriBytes + kMcuSosBytes];
     quant_table_for_quality(q, luma);
     chroma_quant_table_for_quality(q, chroma);
-    const size_t n = build_jfif_prefix_color(img->width, img->height, luma, chroma, chroma_mode(sub), hdr) - kSosBytes;
+    size_t n = build_jfif_prefix_color(img->width, img->height, luma, chroma, chroma_mode(sub), hdr) - kSosBytes;
+    if (restart) {
+        const uint8_t dri[kMcuDriBytes] = {0xFF, 0xDD, 0x00, 0x04, (uint8_t)(restart >> 8), (uint8_t)restart};
+        std::memcpy(hdr + n, dri, sizeof(dri));
+        n += sizeof(dri);
+    }
     const uint8_t sos[kMcuSosBytes] = {0xFF, 0xDA, 0x00, 0x0C, 0x03, 0x01, 0x00, 0x02, 0x11, 0x03, 0x11, 0x00, 0x3F, 0x00};
     std::memcpy(hdr + n, sos, sizeof(sos));
     if (int32_t rc = wait_pending(e)) return rc;
     HIP_TRY(hipMemcpy(m.hdr, hdr, n + sizeof(sos), hipMemcpyHostToDevice));
-    m.hdr_for.set(img->width, img->height, q, sub, (int)(n + sizeof(sos)));
+    m.hdr_for.set(img->width, img->height, q, sub, (int)(n + sizeof(sos)), restart);
     return JPEGAMD_OK;
 }
 
 // The interleaved files of a batch whose arguments are known to be good: g0 describes every picture, px holds their pixels.
 // `ycc` (a YCbCr batch, 8-bit full-range BT.601): g0 / px are the Y planes as a GRAY picture, the chroma comes from the caller.
-static int32_t interleaved_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, const PlaneSet &px, int32_t count, int32_t subsampling,
+// `restart`: the restart interval in MCUs (1 .. 65535), or 0 for the file without -- the launches below are then what they were
+// before there were restart intervals: k_mcu_segments<false>, k_finalize, k_mcu_totals.
+static int32_t interleaved_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, const PlaneSet &px, int32_t count, int32_t subsampling, int32_t restart,
                                  void *const *outs_dev, uint64_t out_capacity, uint64_t *const *out_sizes_dev, void *stream_,
                                  const YccSource *ycc = nullptr) {
-    const McuGeometry g = mcu_geometry(g0.width, g0.height, subsampling);
+    const McuGeometry g = mcu_geometry(g0.width, g0.height, subsampling, restart);
+    // segments as short as one MCU: a picture whose scratch alone is beyond the group budget is refused, nothing allocated or launched
+    if (restart && mcu_scratch_per_pic(g) > kMcuScratchBudget) return JPEGAMD_ERR_TOO_LARGE;
     // every launch codes ONE picture's component: the Y plane and a chroma plane must fit the context
     ImageDesc iy;
     int32_t rc = describe(e, &g0, &iy);
@@ -1574,7 +1633,7 @@ static int32_t interleaved_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, cons
     if (rc) return rc;
     if (iy.blocks_w != g.bw || iy.blocks_h != g.bh || ic.blocks_w != g.mx || ic.blocks_h != g.my) return JPEGAMD_ERR_ARG;
 
-    const size_t per_pic = g.coef_per_pic * sizeof(int16_t) + (size_t)g.num_segs_pad * kSegCapWords * sizeof(uint32_t);
+    const size_t per_pic = (size_t)mcu_scratch_per_pic(g);
     const int group = (int)std::max<size_t>(1, std::min<size_t>((size_t)count, kMcuScratchBudget / per_pic));
     rc = color_alloc_consts(e);
     if (rc) return rc;
@@ -1586,7 +1645,7 @@ static int32_t interleaved_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, cons
     if (rc) return rc;
     rc = prepare_color_constants(e, &g0, subsampling);
     if (rc) return rc;
-    rc = prepare_mcu_prefix(e, &g0, subsampling);
+    rc = prepare_mcu_prefix(e, &g0, subsampling, restart);
     if (rc) return rc;
     auto &c = e->color;
     auto &m = e->mcu;
@@ -1632,18 +1691,35 @@ static int32_t interleaved_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, cons
         sa.seg_mcus = g.seg_mcus; sa.num_segs = g.num_segs; sa.num_segs_pad = g.num_segs_pad; sa.batch = n;
         sa.huff_y = e->huff; sa.huff_c = c.huff;
         sa.seg = m.seg;
+        sa.seg.words_stride = (uint32_t)g.cap_words;
         sa.status = &m.scan_stats->status;
+        sa.restart = restart; sa.segs_per_interval = restart ? g.segs_per_interval : 0;
         if (launch_mcu_segments(sa, stream)) return JPEGAMD_ERR_HIP;
 
-        ImageDesc is = iy;                                           // what run_finalize reads of it: the segments per picture and their length
-        is.num_segs = g.num_segs_pad; is.seg_tiles = kSegTiles;
-        const ScanTarget tgt = {m.hdr, m.hdr_for.len, 1, m.scan_stats, false, &m.seg};
-        if (run_finalize(e, is, outs_dev + first, out_capacity, out_sizes_dev + first, 1, stream, nullptr, n, false, &tgt)) return JPEGAMD_ERR_HIP;
+        if (restart) {                                               // k_mcu_restart_offsets + k_mcu_restart_write in k_finalize's place
+            McuRestartArgs ra;
+            std::memset(&ra, 0, sizeof(ra));
+            ra.seg = sa.seg;
+            ra.num_segs_pad = g.num_segs_pad; ra.batch = n;
+            ra.segs_per_interval = g.segs_per_interval; ra.intervals = g.intervals; ra.last_seg = g.last_seg;
+            ra.pre = m.rst_words; ra.b0 = m.rst_words + m.rst_cap; ra.ff = m.rst_words + 2 * m.rst_cap;
+            ra.pos = m.rst_pos; ra.pic_sums = m.rst_pic_sums;
+            for (int i = 0; i < n; ++i) { ra.out[i] = (uint8_t *)outs_dev[first + i]; ra.out_size[i] = out_sizes_dev[first + i]; }
+            ra.out_capacity = out_capacity;
+            ra.prefix = m.hdr; ra.prefix_len = m.hdr_for.len;
+            if (launch_mcu_restart_writer(ra, stream)) return JPEGAMD_ERR_HIP;
+        } else {
+            ImageDesc is = iy;                                       // what run_finalize reads of it: the segments per picture and their length
+            is.num_segs = g.num_segs_pad; is.seg_tiles = kSegTiles;
+            const ScanTarget tgt = {m.hdr, m.hdr_for.len, 1, m.scan_stats, false, &m.seg};
+            if (run_finalize(e, is, outs_dev + first, out_capacity, out_sizes_dev + first, 1, stream, nullptr, n, false, &tgt)) return JPEGAMD_ERR_HIP;
+        }
 
         McuTotalsArgs ta;
         std::memset(&ta, 0, sizeof(ta));
         ta.seg = m.seg;
         ta.num_segs_pad = g.num_segs_pad; ta.prefix_len = m.hdr_for.len;
+        ta.pic_sums = restart ? m.rst_pic_sums : nullptr;
         ta.last_of_call = first + n == count ? 1 : 0;
         for (int i = 0; i < n; ++i) ta.out_size[i] = out_sizes_dev[first + i];
         ta.out_capacity = out_capacity;
@@ -1655,10 +1731,13 @@ static int32_t interleaved_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, cons
     return enqueued(e, stream, count * g.num_segs_pad, cev != nullptr, true);
 }
 
-extern "C" int32_t jpegamd_encode_color_interleaved_batch_async(JpegAmdEncoder *e, const JpegAmdImage *imgs, int32_t count, int32_t subsampling,
-                                                                void *const *outs_dev, uint64_t out_capacity, uint64_t *const *out_sizes_dev,
-                                                                void *stream_) {
+static bool restart_valid(int32_t restart) { return restart >= 0 && restart <= 65535; }
+
+extern "C" int32_t jpegamd_encode_color_interleaved_restart_batch_async(JpegAmdEncoder *e, const JpegAmdImage *imgs, int32_t count, int32_t subsampling,
+                                                                        int32_t restart_interval, void *const *outs_dev, uint64_t out_capacity,
+                                                                        uint64_t *const *out_sizes_dev, void *stream_) {
     // the arguments first: nothing of the context is read before they are known to be good
+    if (!restart_valid(restart_interval)) return JPEGAMD_ERR_ARG;
     if (!e || !imgs || !outs_dev || !out_sizes_dev || count < 1 || count > kMaxBatch) return JPEGAMD_ERR_ARG;
     if (!sub_valid(subsampling)) return JPEGAMD_ERR_ARG;
     const JpegAmdImage &g0 = imgs[0];
@@ -1666,13 +1745,20 @@ extern "C" int32_t jpegamd_encode_color_interleaved_batch_async(JpegAmdEncoder *
     if (g0.width <= 0 || g0.height <= 0 || g0.width > 65535 || g0.height > 65535 || g0.row_stride < 3 * (int64_t)g0.width) return JPEGAMD_ERR_ARG;
     PlaneSet ps;
     if (int32_t rc = uniform_batch_args(imgs, count, outs_dev, out_sizes_dev, &ps)) return rc;
-    return interleaved_batch(e, g0, ps, count, subsampling, outs_dev, out_capacity, out_sizes_dev, stream_);
+    return interleaved_batch(e, g0, ps, count, subsampling, restart_interval, outs_dev, out_capacity, out_sizes_dev, stream_);
 }
 
-extern "C" int32_t jpegamd_encode_ycbcr_interleaved_batch_async(JpegAmdEncoder *e, const JpegAmdYCbCrImage *imgs, int32_t count, int32_t subsampling,
-                                                                void *const *outs_dev, uint64_t out_capacity, void *const *out_sizes_dev,
+extern "C" int32_t jpegamd_encode_color_interleaved_batch_async(JpegAmdEncoder *e, const JpegAmdImage *imgs, int32_t count, int32_t subsampling,
+                                                                void *const *outs_dev, uint64_t out_capacity, uint64_t *const *out_sizes_dev,
                                                                 void *stream_) {
+    return jpegamd_encode_color_interleaved_restart_batch_async(e, imgs, count, subsampling, 0, outs_dev, out_capacity, out_sizes_dev, stream_);
+}
+
+extern "C" int32_t jpegamd_encode_ycbcr_interleaved_restart_batch_async(JpegAmdEncoder *e, const JpegAmdYCbCrImage *imgs, int32_t count, int32_t subsampling,
+                                                                        int32_t restart_interval, void *const *outs_dev, uint64_t out_capacity,
+                                                                        void *const *out_sizes_dev, void *stream_) {
     // the arguments first: nothing of the context is read before they are known to be good
+    if (!restart_valid(restart_interval)) return JPEGAMD_ERR_ARG;
     if (imgs && count >= 1 && count <= kMaxBatch)
         for (int i = 0; i < count; ++i) if (is_packed422(imgs[i].chroma_layout)) return JPEGAMD_ERR_ARG;      // packed 4:2:2 in one scan: a follow-up
     JpegAmdImage g0;
@@ -1682,7 +1768,13 @@ extern "C" int32_t jpegamd_encode_ycbcr_interleaved_batch_async(JpegAmdEncoder *
     if (int32_t rc = ycbcr_args(e, imgs, count, subsampling, JPEGAMD_RANGE_FULL, JPEGAMD_SAMPLES_8, JPEGAMD_MATRIX_BT601, outs_dev, out_sizes_dev,
                                 true, &g0, &ps, &ycc, sizes))
         return rc;
-    return interleaved_batch(e, g0, ps, count, subsampling, outs_dev, out_capacity, sizes, stream_, &ycc);
+    return interleaved_batch(e, g0, ps, count, subsampling, restart_interval, outs_dev, out_capacity, sizes, stream_, &ycc);
+}
+
+extern "C" int32_t jpegamd_encode_ycbcr_interleaved_batch_async(JpegAmdEncoder *e, const JpegAmdYCbCrImage *imgs, int32_t count, int32_t subsampling,
+                                                                void *const *outs_dev, uint64_t out_capacity, void *const *out_sizes_dev,
+                                                                void *stream_) {
+    return jpegamd_encode_ycbcr_interleaved_restart_batch_async(e, imgs, count, subsampling, 0, outs_dev, out_capacity, out_sizes_dev, stream_);
 }
 
 // The capacity status is STICKY on the device: every kernel only ORs into it, and it is cleared here, after it was read.

@@ -117,6 +117,25 @@ __device__ __forceinline__ uint32_t other_half(uint32_t v, int lane) {
 __device__ __forceinline__ int uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
 
 // ------------------------------------------------------------------------------------
+// Stuffing census (k_finalize, k_mcu_restart_offsets)
+// ------------------------------------------------------------------------------------
+// Owned 0xFF bytes of segment t given its byte phase p (= bit offset & 7): those wholly inside it (counted by k_segment_merge)
+// plus the byte that straddles its start -- 0xFF iff the last p bits in front of it and its first 8 - p bits are all ones.
+// edge = (first 8 bits << 8) | last 7 bits of a segment's own string.  A segment shorter than 8 bits is "00 1010" (one
+// flat block): it has no leading one, and its tail ends in 0, so neither side can complete an 0xFF across it.
+__device__ __forceinline__ uint32_t fin_owned_ff(uint4 ffin /*the segment's 8 counts, 16 bits each*/, int t, uint32_t p, uint32_t edge_t, uint32_t edge_prev) {
+    const uint32_t lo = (p & 4u) ? ffin.z : ffin.x, hi = (p & 4u) ? ffin.w : ffin.y;
+    const uint32_t w = (p & 2u) ? hi : lo;
+    uint32_t c = (p & 1u) ? w >> 16 : w & 0xFFFFu;
+    if (p && t > 0) {
+        const uint32_t tail_ones = (uint32_t)__builtin_ctz(~(edge_prev & 0x7Fu));             // 0..7
+        const uint32_t lead_ones = (uint32_t)__clz(~((edge_t >> 8) << 24));                    // 0..8
+        c += (tail_ones >= p && lead_ones >= 8u - p) ? 1u : 0u;
+    }
+    return c;
+}
+
+// ------------------------------------------------------------------------------------
 // Exact-order coefficient (dct.c:72-93 + quantization.c:34-36), cooperative: lane j owns
 // term j = x*8+y of block (bx, by); the ordered float32 sum s_j = fl(s_{j-1} + t_j) is a
 // 63-step DPP wave_shr chain.  Must be called with all 64 lanes active; (bx, by, u, v)

@@ -390,16 +390,47 @@ int launch_append_scans_batch(const AppendBatchArgs &a, void *stream, void *cons
 constexpr int mcu_seg_mcus(int hs, int vs) { return kSegBlocks / (hs * vs + 2); }     // 85 / 42 / 64: at most 256 blocks per segment
 static_assert(mcu_seg_mcus(1, 1) * 3 <= kSegBlocks && mcu_seg_mcus(2, 2) * 6 <= kSegBlocks && mcu_seg_mcus(2, 1) * 4 <= kSegBlocks &&
               kSegBlocks == kTileBlocks * kSegTiles, "a segment of MCUs fits seg_cap_words(kSegTiles)");
+//
+// Restart intervals: with restart = Ri > 0 the scan is n = ceil(M / Ri) intervals of Ri MCUs (M = mx my), and a
+// segment never crosses an interval's boundary: every interval has segs_per_interval = ceil(min(Ri, M) / seg_mcus) segments, segment
+// (i, k) -- entry i segs_per_interval + k of the picture -- holds the MCUs [i Ri + k seg_mcus, min(i Ri + (k + 1) seg_mcus, (i + 1) Ri, M)),
+// EMPTY where that range is (only behind the last interval's last MCU).  The DC predictors are 0 at MCU i Ri.  A segment holds at
+// most min(Ri, seg_mcus) MCUs, and its string is reserved for that many blocks: mcu_restart_cap_words.
+constexpr int mcu_restart_cap_words(int blocks) { return ((blocks * kMaxBlockBitsColor + 31) / 32 + 1 + 63) / 64 * 64; }   // seg_cap_words_at's rounding
+static_assert(mcu_restart_cap_words(kSegBlocks) == seg_cap_words_at(kSegTiles, kMaxBlockBitsColor), "a full segment takes the reservation of the plain scan");
 struct McuSegArgs {
     const int16_t *coef;
     uint64_t pic_stride, cb_off, cr_off;
     int32_t bw, bh, mx, my, hs, vs;
     int32_t seg_mcus, num_segs, num_segs_pad, batch;
     const uint32_t *huff_y, *huff_c;    // [272] (len << 16) | code: AC by run/size symbol, then 16 DC sizes
-    SegArrays seg;                      // the interleaved path's own (words_stride = seg_cap_words(kSegTiles)); no group aggregates
+    SegArrays seg;                      // the interleaved path's own (words_stride = seg_cap_words(kSegTiles), or mcu_restart_cap_words); no group aggregates
     uint32_t *status;                   // ScanStats::status: bit 1 = a count that did not fit its 16 bits
+    int32_t restart, segs_per_interval; // 0, 0: no restart intervals
 };
 int launch_mcu_segments(const McuSegArgs &a, void *stream);
+// The writer of a file with restart intervals: two launches in place of k_finalize (which knows neither the 1-bit padding of an
+// interval nor markers).  k_mcu_restart_offsets, one workgroup per picture: every segment's bit offset inside its interval (pre is its
+// scratch: the bit counts' running sum over the picture), the 0xFF bytes it owns at that phase, and -- an exclusive sum over the
+// picture of what every segment writes -- its place in the file; the picture's sums (bits, symbols, stuffed bytes) and its would-be size word.
+// k_mcu_restart_write, one wave per segment: the bytes whose last bit the segment holds, stuffed; an interval's last segment adds
+// the padded byte, its stuffing byte and RSTn, the picture's last one the zero-bit flush and EOI; the first workgroup the prefix.
+constexpr int kMcuPicSums = 4;
+struct McuRestartArgs {
+    SegArrays seg;
+    int32_t num_segs_pad, batch;
+    int32_t segs_per_interval, intervals;
+    int32_t last_seg;                   // the picture's last segment that is not EMPTY
+    uint32_t *pre, *b0, *ff;            // [batch][num_segs_pad]
+    uint64_t *pos;                      // [batch][num_segs_pad] bytes of the scan in front of the segment's own
+    unsigned long long *pic_sums;       // [batch][kMcuPicSums] the picture's coded bits, symbols and stuffed 0x00 bytes
+    uint8_t *out[kMaxBatch];
+    uint64_t out_capacity;
+    uint64_t *out_size[kMaxBatch];
+    const uint8_t *prefix;
+    int32_t prefix_len;
+};
+int launch_mcu_restart_writer(const McuRestartArgs &a, void *stream);
 // k_mcu_totals, behind k_finalize: per picture of the launch the sums of its segments, its stuffed bytes (from its size) and its
 // exact-order fallbacks (pic: k_picture_stats' words of THESE pictures) ADDED to the context's record, whose sums the caller zeroed;
 // the picture's size word set to 0 when the file did not fit; scan_stats->status (k_finalize's) ORed into the context's.
@@ -407,6 +438,8 @@ struct McuTotalsArgs {
     SegArrays seg;
     int32_t num_segs_pad, prefix_len;
     int32_t last_of_call;               // the launch's last picture is the call's last: its size is what finish reports
+    const unsigned long long *pic_sums; // k_mcu_restart_offsets' sums of THESE pictures (McuRestartArgs), taken instead of the sums over the segments
+                                        // and the stuffed bytes from the size (which holds markers and a padded byte per interval); null without restart intervals
     uint64_t *out_size[kMaxBatch];
     uint64_t out_capacity;
     const unsigned long long *pic;

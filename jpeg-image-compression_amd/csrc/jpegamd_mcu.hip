@@ -14,7 +14,11 @@
 //   census   bits, edge, ffin[8], syms as k_segment_merge defines them (jpegamd_entropy.hip).
 // A pad Y block (beyond the picture's last block column / row when the MCU grid overhangs it) is DC-only, its DC that of the
 // nearest real block: a zero difference wherever that neighbour precedes it in the scan.
+// With restart intervals a segment is a run of MCUs of ONE interval, the predictors are 0 at the interval's first
+// MCU, and k_mcu_restart_offsets + k_mcu_restart_write stand in for k_finalize: per-interval padding with 1-bits, stuffing, RSTn.
 // k_mcu_totals: the per-call record (sums over the batch) and each picture's size word (0 when the file did not fit).
+#include <algorithm>
+
 #include <hip/hip_ext.h>
 #include "jpegamd_device.h"
 
@@ -69,8 +73,9 @@ __device__ __forceinline__ void mcu_walk_block(const uint4 *__restrict__ p, bool
 
 struct McuBlock { const uint4 *p; int pred; bool pad, chroma; };
 
-// Block j of MCU m of a picture whose planes start at `base`: where its coefficients lie, and its DC predictor.
-__device__ __forceinline__ McuBlock mcu_block(const McuSegArgs &a, const int16_t *base, int m, int j) {
+// Block j of MCU m of a picture whose planes start at `base`: where its coefficients lie, and its DC predictor -- 0 where the
+// component's previous block lies in front of MCU `mstart` (the scan's first MCU, or the first of m's restart interval).
+__device__ __forceinline__ McuBlock mcu_block(const McuSegArgs &a, const int16_t *base, int m, int j, int mstart) {
     const int ny = a.hs * a.vs;
     McuBlock b;
     const auto y_at = [&](int mm, int jj, bool *pad) {           // Y block jj of MCU mm, clamped to the picture's blocks
@@ -83,16 +88,19 @@ __device__ __forceinline__ McuBlock mcu_block(const McuSegArgs &a, const int16_t
     if (j < ny) {
         b.chroma = false;
         b.p = reinterpret_cast<const uint4 *>(y_at(m, j, &b.pad));
-        b.pred = j > 0 ? (int)*y_at(m, j - 1, nullptr) : (m > 0 ? (int)*y_at(m - 1, ny - 1, nullptr) : 0);
+        b.pred = j > 0 ? (int)*y_at(m, j - 1, nullptr) : (m > mstart ? (int)*y_at(m - 1, ny - 1, nullptr) : 0);
     } else {
         const int16_t *plane = base + (j == ny ? a.cb_off : a.cr_off);
         b.chroma = true; b.pad = false;
         b.p = reinterpret_cast<const uint4 *>(plane + (size_t)m * 64);
-        b.pred = m > 0 ? (int)plane[(size_t)(m - 1) * 64] : 0;
+        b.pred = m > mstart ? (int)plane[(size_t)(m - 1) * 64] : 0;
     }
     return b;
 }
 
+// kRestart: the segments are cut per restart interval (McuSegArgs::restart > 0) and the predictors restart with it; the plain
+// scan is the instantiation it always was.
+template <bool kRestart>
 __global__ __launch_bounds__(64 * kWavesM) void k_mcu_segments(const McuSegArgs a) {
     __shared__ uint32_t s_tab[2][272];
     __shared__ uint32_t s_win[kWavesM][kMcuWin + 2];
@@ -103,15 +111,21 @@ __global__ __launch_bounds__(64 * kWavesM) void k_mcu_segments(const McuSegArgs 
     if (seg >= a.batch * a.num_segs_pad) return;
     const int image = seg / a.num_segs_pad, sl = seg - image * a.num_segs_pad;
     uint16_t *const ffin = a.seg.ffin + (size_t)seg * 8;
-    if (sl >= a.num_segs) {                                        // an empty segment that rounds the picture's count up: no bits, no ones at either end
+    int m0 = sl * a.seg_mcus, mstart = 0, nmcu = min(a.seg_mcus, a.mx * a.my - m0);
+    if (kRestart) {                                                // segment (iv, k): the k-th run of seg_mcus MCUs of interval iv
+        const int iv = sl / a.segs_per_interval, k = sl - iv * a.segs_per_interval;
+        mstart = iv * a.restart;
+        m0 = mstart + k * a.seg_mcus;
+        nmcu = min(min(a.seg_mcus, a.restart - k * a.seg_mcus), a.mx * a.my - m0);
+    }
+    if (sl >= a.num_segs || (kRestart && nmcu <= 0)) {             // an empty segment that rounds the picture's count up (or lies behind the last MCU of the last interval): no bits, no ones at either end
         if (lane < 8) ffin[lane] = 0;
         if (lane == 0) { a.seg.bits[seg] = 0u; a.seg.edge[seg] = 0u; a.seg.syms[seg] = 0u; a.seg.exact[seg] = 0u; }
         return;
     }
     const int16_t *base = a.coef + (size_t)image * a.pic_stride;
     const int bpm = a.hs * a.vs + 2;
-    const int m0 = sl * a.seg_mcus;
-    const int nblk = min(a.seg_mcus, a.mx * a.my - m0) * bpm;       // 3 .. 256
+    const int nblk = nmcu * bpm;                                    // 3 .. 256
     uint32_t *win = s_win[wave];
 
     // ---- pass 1: bit lengths, then the blocks' places ----
@@ -123,7 +137,7 @@ __global__ __launch_bounds__(64 * kWavesM) void k_mcu_segments(const McuSegArgs 
         len[r] = 0u; pred[r] = 0;
         if (k < nblk) {
             const int mi = k / bpm;
-            const McuBlock b = mcu_block(a, base, m0 + mi, k - mi * bpm);
+            const McuBlock b = mcu_block(a, base, m0 + mi, k - mi * bpm, mstart);
             pred[r] = b.pred;
             uint32_t n = 0;
             mcu_walk_block(b.p, b.pad, b.pred, s_tab[b.chroma ? 1 : 0], [&](uint32_t, uint32_t c) { n += c; ++nsym; });
@@ -154,7 +168,7 @@ __global__ __launch_bounds__(64 * kWavesM) void k_mcu_segments(const McuSegArgs 
             const int k = r * 64 + lane;
             if (k < nblk && off[r] < hi_bit && off[r] + len[r] > lo_bit) {
                 const int mi = k / bpm;
-                const McuBlock b = mcu_block(a, base, m0 + mi, k - mi * bpm);
+                const McuBlock b = mcu_block(a, base, m0 + mi, k - mi * bpm, mstart);
                 uint32_t pos = off[r];
                 mcu_walk_block(b.p, b.pad, pred[r], s_tab[b.chroma ? 1 : 0], [&](uint32_t sym, uint32_t n) {
                     if (n == 0u) return;
@@ -212,20 +226,258 @@ __global__ __launch_bounds__(64 * kWavesM) void k_mcu_segments(const McuSegArgs 
 int launch_mcu_segments(const McuSegArgs &a, void *stream) {
     const int n = a.batch * a.num_segs_pad;
     if (n <= 0) return 0;
-    if (a.seg_mcus < 1 || a.seg_mcus * (a.hs * a.vs + 2) > kSegBlocks || a.num_segs_pad % kSegGroup != 0 ||
-        (int64_t)a.num_segs * a.seg_mcus < (int64_t)a.mx * a.my || a.num_segs > a.num_segs_pad)
+    if (a.seg_mcus < 1 || a.seg_mcus * (a.hs * a.vs + 2) > kSegBlocks || a.num_segs_pad % kSegGroup != 0 || a.num_segs > a.num_segs_pad)
         return (int)hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_mcu_segments, dim3((unsigned)((n + kWavesM - 1) / kWavesM)), dim3(64 * kWavesM), 0, (hipStream_t)stream, a);
+    const int64_t mcus = (int64_t)a.mx * a.my;
+    const dim3 grid((unsigned)((n + kWavesM - 1) / kWavesM)), block(64 * kWavesM);
+    if (a.restart == 0) {
+        if ((int64_t)a.num_segs * a.seg_mcus < mcus) return (int)hipErrorInvalidValue;
+        hipLaunchKernelGGL(k_mcu_segments<false>, grid, block, 0, (hipStream_t)stream, a);
+    } else {
+        // every MCU lies in a segment, and the widest segment fits its reservation
+        const int64_t spi = a.segs_per_interval, in_interval = std::min<int64_t>(a.restart, mcus);
+        if (a.restart < 0 || spi < 1 || spi * a.seg_mcus < in_interval || (int64_t)a.num_segs < (mcus + a.restart - 1) / a.restart * spi ||
+            (int64_t)mcu_restart_cap_words((int)std::min<int64_t>(a.restart, a.seg_mcus) * (a.hs * a.vs + 2)) > (int64_t)a.seg.words_stride)
+            return (int)hipErrorInvalidValue;
+        hipLaunchKernelGGL(k_mcu_segments<true>, grid, block, 0, (hipStream_t)stream, a);
+    }
+    return (int)hipGetLastError();
+}
+
+// ---- the writer of a scan with restart intervals ------------------------------------------------------------
+// Every interval starts on a byte with its bit offset at 0, so a segment's byte phase is the bits of the segments in front of it
+// in ITS interval, and an interval's length in the file follows from its own segments' numbers: where everything goes is one
+// exclusive sum per picture over what each segment writes.  Two launches: the sums must be complete before a byte is placed,
+// and no workgroup waits for another.
+constexpr int kRstThreads = 1024, kRstPer = 8;  // k_mcu_restart_offsets: threads of the workgroup, segments a thread takes per round
+constexpr int kRstStripWords = 132;             // k_mcu_restart_write: a wave's staging strip -- 3 bytes kept + 256 bytes of a pass, every one stuffed, + the word read behind them
+
+// What an interval's last segment writes behind its own bytes: the byte that holds the interval's last r = bits & 7 bits (the
+// last 7 bits of the segment are in `edge`) -- filled up with ones, and stuffed when that makes it 0xFF, in front of RSTn; filled
+// up with zeros in front of EOI -- and the two marker bytes.
+struct RstTail { uint32_t r, byte, bytes, pad_ff; };
+__device__ __forceinline__ RstTail rst_tail(uint32_t interval_bits, uint32_t edge, bool last_interval) {
+    RstTail t;
+    t.r = interval_bits & 7u;
+    const uint32_t fill = last_interval ? 0u : (0xFFu >> t.r);
+    t.byte = t.r ? (((edge & ((1u << t.r) - 1u)) << (8u - t.r)) | fill) : 0u;
+    t.pad_ff = (t.r && t.byte == 0xFFu) ? 1u : 0u;
+    t.bytes = (t.r ? 1u : 0u) + t.pad_ff + 2u;
+    return t;
+}
+
+// Exclusive prefix sums over a round's kRstThreads x kRstPer values, v[j] of a lane being the value of element
+// 64 kRstPer wave + 64 j + lane of the round; *total: their sum.  s_w: 16 words, free again on return.
+__device__ __forceinline__ void rst_round_scan(const uint32_t (&v)[kRstPer], uint32_t (&ex)[kRstPer], uint32_t *s_w, int lane, int wave, uint32_t *total) {
+    static_assert(kRstThreads == 16 * 64, "the waves' totals are scanned in one DPP row");
+    uint32_t carry = 0;
+#pragma unroll
+    for (int j = 0; j < kRstPer; ++j) {
+        const uint32_t incl = wave_incl_scan_u32(v[j]);
+        ex[j] = carry + incl - v[j];
+        carry += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+    }
+    if (lane == 0) s_w[wave] = carry;
+    __syncthreads();
+    const uint32_t wt = lane < 16 ? s_w[lane] : 0u;
+    const uint32_t wincl = half_incl_scan_dpp(wt);
+    *total = (uint32_t)__builtin_amdgcn_readlane((int)wincl, 15);
+    const uint32_t woff = (uint32_t)__builtin_amdgcn_readlane((int)(wincl - wt), wave);
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < kRstPer; ++j) ex[j] += woff;
+}
+
+// Workgroup q: picture q of the launch, its segments in rounds of kRstThreads x kRstPer with the sums carried from round to round.
+// A wave takes 64 kRstPer consecutive segments of the round, lane l the segments l, l + 64, ...: every load is contiguous over the
+// lanes, and a lane's loads of a round are all issued before any is used -- a round costs one trip to memory.
+__global__ __launch_bounds__(kRstThreads) void k_mcu_restart_offsets(const McuRestartArgs a) {
+    __shared__ uint32_t s_w[16];
+    __shared__ unsigned long long s_sum[3][16];
+    const int tid = (int)threadIdx.x, lane = lane_id(), wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int q = (int)blockIdx.x, n = a.num_segs_pad, spi = a.segs_per_interval;
+    const size_t base = (size_t)q * (size_t)n;
+    const int first = wave * 64 * kRstPer + lane;                    // the lane's first element of a round
+    const int last_first = (a.intervals - 1) * spi;                 // the first segment of the last interval
+    // 1. Intervals of several segments: the bit counts' running sum over the picture (mod 2^32: only differences inside an interval
+    //    are read).  An interval of one segment has its bit offset, 0, without it.
+    const bool chained = spi > 1;
+    if (chained) {
+        uint32_t run = 0;
+        for (int c0 = 0; c0 < n; c0 += kRstThreads * kRstPer) {
+            uint32_t v[kRstPer], ex[kRstPer], round;
+#pragma unroll
+            for (int j = 0; j < kRstPer; ++j) { const int i = c0 + first + 64 * j; v[j] = i < n ? a.seg.bits[base + i] : 0u; }
+            rst_round_scan(v, ex, s_w, lane, wave, &round);
+#pragma unroll
+            for (int j = 0; j < kRstPer; ++j) { const int i = c0 + first + 64 * j; if (i < n) a.pre[base + i] = run + ex[j]; }
+            run += round;
+        }
+        __syncthreads();                                            // (the sums are read back by other threads of this workgroup)
+    }
+    // 2. per segment: bit offset in its interval, owned 0xFF bytes at that phase, bytes written; their sums
+    unsigned long long pos = 0, sum_bits = 0, sum_syms = 0, sum_ff = 0;
+    for (int c0 = 0; c0 < n; c0 += kRstThreads * kRstPer) {
+        uint32_t bits[kRstPer], edge[kRstPer], edge_prev[kRstPer], syms[kRstPer], pre_i[kRstPer], pre_0[kRstPer];
+        int k[kRstPer];
+        uint4 ffin[kRstPer];
+#pragma unroll
+        for (int j = 0; j < kRstPer; ++j) {                         // every load of the round (an element behind the last segment reads the last)
+            const int i = min(c0 + first + 64 * j, a.last_seg);
+            k[j] = i % spi;
+            bits[j] = a.seg.bits[base + i]; edge[j] = a.seg.edge[base + i]; syms[j] = a.seg.syms[base + i];
+            edge_prev[j] = a.seg.edge[base + (i > 0 ? i - 1 : 0)];
+            ffin[j] = *reinterpret_cast<const uint4 *>(a.seg.ffin + (base + i) * 8);
+            pre_i[j] = chained ? a.pre[base + i] : 0u;
+            pre_0[j] = chained ? a.pre[base + i - k[j]] : 0u;
+        }
+        uint32_t b0[kRstPer], ff[kRstPer], bytes[kRstPer], ex[kRstPer], round;
+#pragma unroll
+        for (int j = 0; j < kRstPer; ++j) {
+            const int i = c0 + first + 64 * j;
+            b0[j] = ff[j] = bytes[j] = 0u;
+            if (i <= a.last_seg) {                                  // (behind it: EMPTY segments, which write nothing)
+                uint32_t pad_ff = 0;
+                b0[j] = pre_i[j] - pre_0[j];
+                ff[j] = fin_owned_ff(ffin[j], k[j], b0[j] & 7u, edge[j], edge_prev[j]);
+                bytes[j] = ((b0[j] + bits[j]) >> 3) - (b0[j] >> 3) + ff[j];
+                const bool last = i == a.last_seg;
+                if (last || (k[j] == spi - 1 && i < last_first)) {
+                    const RstTail t = rst_tail(b0[j] + bits[j], edge[j], last);
+                    bytes[j] += t.bytes; pad_ff = t.pad_ff;
+                }
+                sum_ff += ff[j] + pad_ff; sum_bits += bits[j]; sum_syms += syms[j];
+            }
+        }
+        rst_round_scan(bytes, ex, s_w, lane, wave, &round);
+#pragma unroll
+        for (int j = 0; j < kRstPer; ++j) {
+            const int i = c0 + first + 64 * j;
+            if (i < n) { a.pos[base + i] = pos + ex[j]; a.b0[base + i] = b0[j]; a.ff[base + i] = ff[j]; }
+        }
+        pos += round;
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        sum_bits += __shfl_xor(sum_bits, off, 64); sum_syms += __shfl_xor(sum_syms, off, 64); sum_ff += __shfl_xor(sum_ff, off, 64);
+    }
+    if (lane == 0) { s_sum[0][wave] = sum_bits; s_sum[1][wave] = sum_syms; s_sum[2][wave] = sum_ff; }
+    __syncthreads();
+    if (tid == 0) {
+        sum_bits = sum_syms = sum_ff = 0;
+        for (int w = 0; w < 16; ++w) { sum_bits += s_sum[0][w]; sum_syms += s_sum[1][w]; sum_ff += s_sum[2][w]; }
+        *a.out_size[q] = (uint64_t)a.prefix_len + pos;              // the would-be size: k_mcu_totals makes it 0 when the file did not fit
+        unsigned long long *rec = a.pic_sums + (size_t)q * kMcuPicSums;
+        rec[0] = sum_bits; rec[1] = sum_syms; rec[2] = sum_ff;
+    }
+}
+
+// Wave w of workgroup g of a picture: its segment 4 g + w.  An output byte is owned by the segment that holds its last bit
+// (k_finalize's rule, inside an interval) and written once: 256 owned bytes a pass, four per lane, go with their stuffing bytes
+// into a zeroed strip in LDS whose offset is the output address mod 4, and whole words of the strip leave as aligned stores.
+__global__ __launch_bounds__(64 * kWavesM) void k_mcu_restart_write(const McuRestartArgs a) {
+    __shared__ uint32_t s_strip[kWavesM][kRstStripWords];
+    const int lane = lane_id(), wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int wgs = (a.num_segs_pad + kWavesM - 1) / kWavesM;
+    const int image = (int)blockIdx.x / wgs, g = (int)blockIdx.x - image * wgs;
+    uint8_t *const out = a.out[image];
+    if (g == 0)
+        for (int i = (int)threadIdx.x; i < a.prefix_len; i += 64 * kWavesM)
+            if ((uint64_t)i < a.out_capacity) out[i] = a.prefix[i];
+    const int sl = g * kWavesM + wave;
+    if (sl > a.last_seg) return;                                    // (no workgroup-wide meeting below)
+    const size_t seg = (size_t)image * (size_t)a.num_segs_pad + (size_t)sl;
+    const int iv = sl / a.segs_per_interval, k = sl - iv * a.segs_per_interval;
+    const uint32_t bits = a.seg.bits[seg], edge = a.seg.edge[seg], b0 = a.b0[seg], my_ff = a.ff[seg];
+    const uint32_t lead = b0 & 7u;                                  // bits of the segment in front that its first byte begins with (0 for k = 0)
+    const uint32_t leadbits = lead ? (a.seg.edge[seg - 1] & ((1u << lead) - 1u)) : 0u;
+    const uint32_t nown = ((b0 + bits) >> 3) - (b0 >> 3);
+    const bool last = sl == a.last_seg, tail = last || (k == a.segs_per_interval - 1 && iv < a.intervals - 1);
+    const RstTail t = rst_tail(b0 + bits, edge, last);
+    const uint64_t base = (uint64_t)a.prefix_len + a.pos[seg];
+    if (base + nown + my_ff + (tail ? t.bytes : 0u) > a.out_capacity) return;    // the file does not fit: k_mcu_totals reports it from the size
+
+    const uint32_t *words = a.seg.words + seg * a.seg.words_stride;
+    uint32_t *const strip32 = s_strip[wave];
+    uint8_t *const strip = reinterpret_cast<uint8_t *>(strip32);
+    for (int p = lane; p < kRstStripWords; p += 64) strip32[p] = 0u;
+    uint8_t *const dst = out + base;
+    const uint32_t fill0 = (uint32_t)((uintptr_t)dst & 3u);          // the bytes in front of it in the first word belong to the segment in front
+    uint8_t *gdst = dst - fill0;                                    // where strip byte 0 goes: 4-byte aligned
+    uint32_t fill = fill0;
+    bool first = true;
+    __builtin_amdgcn_wave_barrier();
+    for (uint32_t done = 0; done < nown; done += 256u) {
+        const uint32_t j = (done >> 2) + (uint32_t)lane;            // owned bytes 4 j .. 4 j + 3: 32 bits from `lead` bits in front of word j
+        uint32_t v = 0;
+        const bool have = 4u * j < nown;
+        if (have) {
+            if (lead) {
+                const uint32_t hi = j ? words[j - 1u] : leadbits;
+                v = __builtin_amdgcn_alignbit(hi, words[j], lead);
+            } else {
+                v = words[j];
+            }
+            const uint32_t nv = nown - 4u * j;
+            if (nv < 4u) v &= 0xFFFFFFFFu << (8u * (4u - nv));
+        }
+        const uint32_t m = ((v & 0x7F7F7F7Fu) + 0x01010101u) & v & 0x80808080u;   // bit 7 of a byte: the byte is 0xFF
+        const uint32_t c = (uint32_t)__popc(m);
+        const uint32_t incl = wave_incl_scan_u32(c);
+        const uint32_t nfill = fill + min(nown - done, 256u) + (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);   // <= 3 + 512
+        if (have) {                                                 // a byte goes behind the lane's place + the 0xFF bytes in front of it; the 0x00 is the strip's
+            uint32_t at = fill + 4u * (uint32_t)lane + incl - c;
+            strip[at] = (uint8_t)(v >> 24); at += 1u + (m >> 31);
+            strip[at] = (uint8_t)(v >> 16); at += 1u + ((m >> 23) & 1u);
+            strip[at] = (uint8_t)(v >> 8);  at += 1u + ((m >> 15) & 1u);
+            strip[at] = (uint8_t)v;
+        }
+        __builtin_amdgcn_wave_barrier();
+        const uint32_t npieces = nfill >> 2;                        // whole words: <= 128
+        const uint32_t rest = strip32[npieces];
+        for (uint32_t p = (uint32_t)lane; p < npieces; p += 64u) {
+            const uint32_t piece = strip32[p];
+            if (first && fill0 && p == 0u) {                        // the segment's first word: its own bytes one by one
+                for (uint32_t b = fill0; b < 4u; ++b) gdst[b] = (uint8_t)(piece >> (8u * b));
+            } else {
+                *reinterpret_cast<uint32_t *>(gdst + 4u * p) = piece;
+            }
+            strip32[p] = 0u;
+        }
+        __builtin_amdgcn_wave_barrier();
+        if (lane == 0) { strip32[npieces] = 0u; strip32[0] = rest; }
+        __builtin_amdgcn_wave_barrier();
+        gdst += 4u * npieces;
+        fill = nfill & 3u;
+        first = first && npieces == 0u;
+    }
+    if ((uint32_t)lane < fill && !(first && (uint32_t)lane < fill0)) gdst[lane] = strip[lane];   // what is left of the last word
+    if (tail && lane == 0) {
+        uint8_t *e = dst + nown + my_ff;
+        if (t.r) { *e++ = (uint8_t)t.byte; if (t.pad_ff) *e++ = 0x00; }
+        e[0] = 0xFF; e[1] = last ? 0xD9 : (uint8_t)(0xD0 + (iv & 7));
+    }
+}
+
+int launch_mcu_restart_writer(const McuRestartArgs &a, void *stream) {
+    if (a.batch < 1 || a.batch > kMaxBatch || a.num_segs_pad < 1 || a.segs_per_interval < 1 || a.intervals < 1 || a.last_seg < 0 ||
+        a.last_seg >= a.num_segs_pad || (int64_t)a.intervals * a.segs_per_interval > (int64_t)a.num_segs_pad ||
+        a.last_seg / a.segs_per_interval != a.intervals - 1)
+        return (int)hipErrorInvalidValue;
+    const int wgs = (a.num_segs_pad + kWavesM - 1) / kWavesM;
+    hipLaunchKernelGGL(k_mcu_restart_offsets, dim3((unsigned)a.batch), dim3(kRstThreads), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(k_mcu_restart_write, dim3((unsigned)(a.batch * wgs)), dim3(64 * kWavesM), 0, (hipStream_t)stream, a);
     return (int)hipGetLastError();
 }
 
 // Workgroup q: picture q of the launch.  Sums of its segments' bits and symbols; its stuffed bytes follow from its size (a file is
-// its prefix, the scan's bits, the flush byte, a 0x00 per 0xFF, and EOI); the size word becomes 0 when the file did not fit.
+// its prefix, the scan's bits, the flush byte, a 0x00 per 0xFF, and EOI) unless the writer counted them (restart intervals: markers
+// and a padded byte per interval); the size word becomes 0 when the file did not fit.
 __global__ __launch_bounds__(256) void k_mcu_totals(const McuTotalsArgs a) {
     __shared__ unsigned long long s_part[2][4];
     const int q = (int)blockIdx.x;
     unsigned long long bits = 0, syms = 0;
-    for (int i = (int)threadIdx.x; i < a.num_segs_pad; i += 256) {
+    const unsigned long long *sums = a.pic_sums ? a.pic_sums + (size_t)q * kMcuPicSums : nullptr;   // (the writer summed them: segments may be as many as MCUs)
+    for (int i = (int)threadIdx.x; i < (sums ? 0 : a.num_segs_pad); i += 256) {
         bits += a.seg.bits[(size_t)q * a.num_segs_pad + i];
         syms += a.seg.syms[(size_t)q * a.num_segs_pad + i];
     }
@@ -236,6 +488,7 @@ __global__ __launch_bounds__(256) void k_mcu_totals(const McuTotalsArgs a) {
     if (threadIdx.x != 0) return;
     bits = s_part[0][0] + s_part[0][1] + s_part[0][2] + s_part[0][3];
     syms = s_part[1][0] + s_part[1][1] + s_part[1][2] + s_part[1][3];
+    if (sums) { bits = sums[0]; syms = sums[1]; }
     const uint32_t st = a.scan_stats->status;
     const uint64_t size = *a.out_size[q];                           // k_finalize's: the would-be size when it did not fit
     const bool fit = (st & ~1u) == 0u && size <= a.out_capacity;
@@ -244,7 +497,8 @@ __global__ __launch_bounds__(256) void k_mcu_totals(const McuTotalsArgs a) {
     atomicAdd((unsigned long long *)&t->total_bits, bits);
     atomicAdd((unsigned long long *)&t->total_syms, syms);
     atomicAdd((unsigned long long *)&t->total_exact, pic[2] + pic[5] + pic[8]);
-    atomicAdd((unsigned long long *)&t->total_ff, (unsigned long long)(size - (uint64_t)a.prefix_len - 2u - (bits + 7u) / 8u));
+    atomicAdd((unsigned long long *)&t->total_ff,
+              sums ? sums[2] : (unsigned long long)(size - (uint64_t)a.prefix_len - 2u - (bits + 7u) / 8u));
     if (!fit) *a.out_size[q] = 0ull;
     if (a.last_of_call && q == (int)gridDim.x - 1) t->out_size = fit ? size : 0ull;
     const uint32_t add = st | (fit ? 0u : 1u);

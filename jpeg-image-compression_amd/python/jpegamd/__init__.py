@@ -124,6 +124,9 @@ def _load() -> C.CDLL:
         "jpegamd_encode_color_interleaved_batch_async": (i32, [vp, C.POINTER(Image), i32, i32, C.POINTER(C.c_void_p), u64, C.POINTER(C.c_void_p), vp]),
         "jpegamd_encode_ycbcr_interleaved_batch_async": (i32, [vp, C.POINTER(YCbCrImage), i32, i32, C.POINTER(C.c_void_p), u64, C.POINTER(C.c_void_p), vp]),
         "jpegamd_max_jfif_bytes_interleaved": (u64, [i32, i32, i32]),
+        "jpegamd_encode_color_interleaved_restart_batch_async": (i32, [vp, C.POINTER(Image), i32, i32, i32, C.POINTER(C.c_void_p), u64, C.POINTER(C.c_void_p), vp]),
+        "jpegamd_encode_ycbcr_interleaved_restart_batch_async": (i32, [vp, C.POINTER(YCbCrImage), i32, i32, i32, C.POINTER(C.c_void_p), u64, C.POINTER(C.c_void_p), vp]),
+        "jpegamd_max_jfif_bytes_interleaved_restart": (u64, [i32, i32, i32, i32]),
         "jpegamd_debug_matrix_coeffs": (i32, [i32, vp]),
         "jpegamd_debug_ycbcr_matrix_planes": (i32, [vp, C.POINTER(YCbCrImage), i32, i32, i32, i32, i32, vp, vp, vp, vp]),
         "jpegamd_debug_chroma_groups": (i32, [i32, i32, i32, i32, i32, i32, i32, vp]),
@@ -144,7 +147,9 @@ def _load() -> C.CDLL:
                     "jpegamd_debug_chroma_groups", "jpegamd_debug_ycbcr_sources", "jpegamd_encode_planar_batch_async", "jpegamd_encode_ycbcr_batch_async",
                     "jpegamd_encode_ycbcr_range_batch_async", "jpegamd_encode_ycbcr_samples_batch_async", "jpegamd_encode_ycbcr_matrix_batch_async",
                     "jpegamd_debug_matrix_coeffs", "jpegamd_debug_ycbcr_matrix_planes", "jpegamd_encode_color_interleaved_batch_async",
-                    "jpegamd_encode_ycbcr_interleaved_batch_async", "jpegamd_max_jfif_bytes_interleaved") and os.environ.get("JPEGAMD_LIB") and not hasattr(lib, name):
+                    "jpegamd_encode_ycbcr_interleaved_batch_async", "jpegamd_max_jfif_bytes_interleaved",
+                    "jpegamd_encode_color_interleaved_restart_batch_async", "jpegamd_encode_ycbcr_interleaved_restart_batch_async",
+                    "jpegamd_max_jfif_bytes_interleaved_restart") and os.environ.get("JPEGAMD_LIB") and not hasattr(lib, name):
             continue                                              # (A/B tooling: a variant build of an older round)
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = res, args
@@ -162,7 +167,9 @@ EXPORTED = ("jpegamd_encoder_create jpegamd_encoder_destroy jpegamd_max_jfif_byt
             "jpegamd_debug_chroma_mfma_consts jpegamd_debug_chroma_group_thresholds jpegamd_debug_color_profile jpegamd_encode_color_batch_async "
             "jpegamd_encode_planar_batch_async jpegamd_encode_ycbcr_batch_async jpegamd_encode_ycbcr_range_batch_async "
             "jpegamd_encode_ycbcr_samples_batch_async jpegamd_encode_ycbcr_matrix_batch_async "
-            "jpegamd_encode_color_interleaved_batch_async jpegamd_encode_ycbcr_interleaved_batch_async jpegamd_max_jfif_bytes_interleaved").split()
+            "jpegamd_encode_color_interleaved_batch_async jpegamd_encode_ycbcr_interleaved_batch_async jpegamd_max_jfif_bytes_interleaved "
+            "jpegamd_encode_color_interleaved_restart_batch_async jpegamd_encode_ycbcr_interleaved_restart_batch_async "
+            "jpegamd_max_jfif_bytes_interleaved_restart").split()
 
 
 def quant_table(quality: int = 50):
@@ -286,7 +293,28 @@ def max_jfif_bytes_interleaved(width: int, height: int, subsampling: int = SUBSA
     return int(lib.jpegamd_max_jfif_bytes_interleaved(width, height, subsampling))
 
 
+def max_jfif_bytes_interleaved_restart(width: int, height: int, subsampling: int = SUBSAMPLE_420, restart_interval: int = 0) -> int:
+    """Upper bound on the bytes of the one-scan file with restart intervals of `restart_interval` MCUs (0: none); 0 for bad arguments."""
+    return int(lib.jpegamd_max_jfif_bytes_interleaved_restart(width, height, subsampling, restart_interval))
+
+
 SCANS = ("separate", "interleaved")
+
+
+def _restart(restart_interval, interleaved: bool, w: int, subsampling: int) -> int:
+    """restart_interval= of the tensor functions -> the interval in MCUs: None / 0 none, an int 1 .. 65535, or "row" for one MCU row
+    (ceil(W / 8) MCUs at SUBSAMPLE_444, ceil(W / 16) otherwise).  Restart intervals exist in scan="interleaved" files alone."""
+    if restart_interval is None or (isinstance(restart_interval, int) and not isinstance(restart_interval, bool) and restart_interval == 0):
+        return 0
+    if restart_interval == "row":
+        ri = -(-w // (8 if subsampling == SUBSAMPLE_444 else 16))
+    elif isinstance(restart_interval, int) and not isinstance(restart_interval, bool) and 1 <= restart_interval <= 65535:
+        ri = restart_interval
+    else:
+        raise ValueError(f'restart_interval must be 0 / None, an int in 1..65535 (MCUs) or "row", not {restart_interval!r}')
+    if not interleaved:
+        raise ValueError('restart_interval needs scan="interleaved"')
+    return ri
 
 
 def _scan(scan) -> bool:
@@ -310,15 +338,18 @@ def encode_bmp_bytes_color(bmp: bytes, quality: int = 0, subsampling: int = SUBS
 _tensor_encoders = {}
 
 
-def encode_tensor(t, quality: int = 0, subsampling: int = SUBSAMPLE_420, layout=None, scan: str = "separate") -> bytes:
+def encode_tensor(t, quality: int = 0, subsampling: int = SUBSAMPLE_420, layout=None, scan: str = "separate", restart_interval=None) -> bytes:
     """A uint8 DEVICE tensor -> JFIF file bytes: [H, W] a grayscale file (the tensor is the luma), [H, W, 3] (R, G, B) a colour file.
     Rows may be strided (t.stride(0) bytes apart); pixels within a row must be packed.  Runs on the tensor's device and the
     current stream; one encoder context per device is kept and grown as needed.
     `layout` names how the picture is stored, as for encode_tensor_batch: "chw" [3, H, W], "rgba" / "bgra" [H, W, 4], "hwc" [H, W, 3].
-    scan="interleaved": the colour file with ONE scan of interleaved MCUs, as for encode_tensor_batch ([H, W, 3] alone)."""
+    scan="interleaved": the colour file with ONE scan of interleaved MCUs, as for encode_tensor_batch ([H, W, 3] alone), and with
+    restart_interval= its restart intervals."""
     import torch
     if _scan(scan):
-        return encode_tensor_batch(t, quality, subsampling, "hwc" if layout is None else layout, _single=True, scan=scan)[0]
+        return encode_tensor_batch(t, quality, subsampling, "hwc" if layout is None else layout, _single=True, scan=scan,
+                                   restart_interval=restart_interval)[0]
+    _restart(restart_interval, False, 1, subsampling)
     if layout is not None:
         return encode_tensor_batch(t, quality, subsampling, layout, _single=True)[0]
     if t.dtype != torch.uint8 or not t.is_cuda:
@@ -450,7 +481,7 @@ def _named_layout(t, layout, single: bool):
 
 
 def encode_tensor_batch(t, quality: int = 0, subsampling: int = SUBSAMPLE_420, layout=None, _single: bool = False,
-                        scan: str = "separate") -> list:
+                        scan: str = "separate", restart_interval=None) -> list:
     """A uint8 DEVICE tensor of N pictures -> N JFIF files: [N, H, W, 3] (R, G, B) colour files through
     jpegamd_encode_color_batch_async, [N, H, W] grayscale files through jpegamd_encode_batch_async.  Pictures may be strided
     (t[::2]), pixels within a row must be packed.  Batches of more than MAX_BATCH pictures go as several calls of at most
@@ -462,9 +493,13 @@ def encode_tensor_batch(t, quality: int = 0, subsampling: int = SUBSAMPLE_420, l
     ignored; "hwc" the explicit name of [N, H, W, 3].  The files are those of the same R, G, B values as [N, H, W, 3].
     scan="interleaved": colour files with ONE scan of interleaved MCUs (jpegamd_encode_color_interleaved_batch_async) -- what
     Motion-JPEG containers and hardware decoders take -- for [N, H, W, 3] (layout None or "hwc") and the three colour subsamplings;
-    every other combination is a ValueError.  They decode to the same pixels as the scan="separate" files."""
+    every other combination is a ValueError.  They decode to the same pixels as the scan="separate" files.
+    restart_interval= (scan="interleaved" alone): restart intervals of that many MCUs, 1 .. 65535, or "row" for one MCU row (DRI /
+    RSTn, jpegamd_encode_color_interleaved_restart_batch_async); 0 / None: none."""
     import torch
     interleaved = _scan(scan)
+    if not interleaved:
+        _restart(restart_interval, False, 1, subsampling)
     if interleaved and layout not in (None, "hwc"):
         raise ValueError(f'scan="interleaved" takes layout="hwc" (or None) alone, not {layout!r}')
     if interleaved and subsampling not in (SUBSAMPLE_444, SUBSAMPLE_420, SUBSAMPLE_422):
@@ -476,6 +511,7 @@ def encode_tensor_batch(t, quality: int = 0, subsampling: int = SUBSAMPLE_420, l
         n, h, w, stride, order, ptr, tensors = _named_layout(t, layout, _single)
     if interleaved and order != ORDER_RGB:
         raise ValueError('scan="interleaved" takes colour pictures [N, H, W, 3] alone')
+    ri = _restart(restart_interval, interleaved, w, subsampling)
     if any(not x.is_cuda or x.device != tensors[0].device for x in tensors):
         raise ValueError("encode_tensor_batch needs a device tensor")
     device = tensors[0].device
@@ -494,7 +530,7 @@ def encode_tensor_batch(t, quality: int = 0, subsampling: int = SUBSAMPLE_420, l
             _tensor_encoders[dev] = (enc, mw, mh)
         cap = max_jfif_bytes(w, h) if gray else max_jfif_bytes_color(w, h, subsampling)
         if interleaved:
-            cap = max_jfif_bytes_interleaved(w, h, subsampling)
+            cap = max_jfif_bytes_interleaved_restart(w, h, subsampling, ri) if ri else max_jfif_bytes_interleaved(w, h, subsampling)
         out = torch.empty((per, cap), dtype=torch.uint8, device=device)
         sizes = torch.zeros(per, dtype=torch.int64, device=device)
         stream = torch.cuda.current_stream(device).cuda_stream
@@ -504,7 +540,10 @@ def encode_tensor_batch(t, quality: int = 0, subsampling: int = SUBSAMPLE_420, l
             size_ptrs = [sizes.data_ptr() + 8 * i for i in range(k)]
             if interleaved:
                 imgs = [Encoder.image(ptr(b0 + i), w, h, stride, bottom_up=False, channel_order=order, quality=quality) for i in range(k)]
-                enc.encode_color_interleaved_batch_async(imgs, subsampling, outs, cap, size_ptrs, stream)
+                if ri:
+                    enc.encode_color_interleaved_restart_batch_async(imgs, subsampling, ri, outs, cap, size_ptrs, stream)
+                else:
+                    enc.encode_color_interleaved_batch_async(imgs, subsampling, outs, cap, size_ptrs, stream)
             elif order is None:
                 imgs = [Encoder.planar_image(ptr(b0 + i), w, h, stride, bottom_up=False, quality=quality) for i in range(k)]
                 enc.encode_planar_batch_async(imgs, subsampling, outs, cap, size_ptrs, stream)
@@ -593,7 +632,7 @@ def _matrix(matrix) -> int:
 
 
 def encode_ycbcr_batch(y, cb, cr=None, quality: int = 0, subsampling: int = SUBSAMPLE_420, order: str = "cbcr",
-                       sample_range: str = "full", matrix: str = "bt601", scan: str = "separate") -> list:
+                       sample_range: str = "full", matrix: str = "bt601", scan: str = "separate", restart_interval=None) -> list:
     """N pictures whose samples already ARE Y, Cb and Cr (JFIF full range; no range or matrix conversion is done) -> N colour JFIF
     files through jpegamd_encode_ycbcr_batch_async, read where they lie: no RGB detour, no chroma-plane pass.
     sample_range="limited": the samples are video range (Y 16..235, Cb / Cr 16..240, as decoders deliver them) and are expanded to
@@ -613,21 +652,24 @@ def encode_ycbcr_batch(y, cb, cr=None, quality: int = 0, subsampling: int = SUBS
 
     and a stack of frames [N, 3 * H // 2, W] slices the same way: f[:, :H] and f[:, H:].unflatten(2, (W // 2, 2)).
     scan="interleaved": the files with ONE scan of interleaved MCUs (jpegamd_encode_ycbcr_interleaved_batch_async), for
-    sample_range="full" and matrix="bt601" alone; anything else is a ValueError."""
+    sample_range="full" and matrix="bt601" alone; anything else is a ValueError.  restart_interval= (scan="interleaved" alone): restart
+    intervals of that many MCUs, or "row", as for encode_tensor_batch (jpegamd_encode_ycbcr_interleaved_restart_batch_async)."""
     rng, mat = _sample_range(sample_range), _matrix(matrix)
     interleaved = _scan(scan)
     if interleaved and (rng != RANGE_FULL or mat != MATRIX_BT601):
         raise ValueError('scan="interleaved" takes sample_range="full" and matrix="bt601" alone')
     n, h, w, y_stride, c_stride, layout = _ycbcr_layout(y, cb, cr, subsampling, order)
+    ri = _restart(restart_interval, interleaved, w, subsampling)
     tensors = [y, cb] + ([cr] if cr is not None else [])
     if any(not x.is_cuda or x.device != y.device for x in tensors):
         raise ValueError("encode_ycbcr_batch needs device tensors on one device")
     return _encode_ycbcr_images(y.device, n, h, w, subsampling, lambda i: Encoder.ycbcr_image(
-        y[i].data_ptr(), cb[i].data_ptr(), cr[i].data_ptr() if cr is not None else 0, w, h, y_stride, c_stride, layout, quality), rng, matrix=mat, interleaved=interleaved)
+        y[i].data_ptr(), cb[i].data_ptr(), cr[i].data_ptr() if cr is not None else 0, w, h, y_stride, c_stride, layout, quality), rng, matrix=mat, interleaved=interleaved,
+        restart=ri)
 
 
 def _encode_ycbcr_images(device, n, h, w, subsampling, image, sample_range: int = RANGE_FULL, sample_format: int = SAMPLES_8,
-                         matrix: int = MATRIX_BT601, interleaved: bool = False):
+                         matrix: int = MATRIX_BT601, interleaved: bool = False, restart: int = 0):
     """`n` YCbCr pictures of one geometry, picture i described by image(i), through the per-device context in calls of at most
     MAX_BATCH -> their files."""
     import torch
@@ -644,6 +686,8 @@ def _encode_ycbcr_images(device, n, h, w, subsampling, image, sample_range: int 
             enc = Encoder(mw, mh)
             _tensor_encoders[dev] = (enc, mw, mh)
         cap = max_jfif_bytes_interleaved(w, h, subsampling) if interleaved else max_jfif_bytes_color(w, h, subsampling)
+        if restart:
+            cap = max_jfif_bytes_interleaved_restart(w, h, subsampling, restart)
         out = torch.empty((per, cap), dtype=torch.uint8, device=device)
         sizes = torch.zeros(per, dtype=torch.int64, device=device)
         stream = torch.cuda.current_stream(device).cuda_stream
@@ -652,7 +696,9 @@ def _encode_ycbcr_images(device, n, h, w, subsampling, image, sample_range: int 
             outs = [out[i].data_ptr() for i in range(k)]
             size_ptrs = [sizes.data_ptr() + 8 * i for i in range(k)]
             imgs = [image(b0 + i) for i in range(k)]
-            if interleaved:
+            if restart:
+                enc.encode_ycbcr_interleaved_restart_batch_async(imgs, subsampling, restart, outs, cap, size_ptrs, stream)
+            elif interleaved:
                 enc.encode_ycbcr_interleaved_batch_async(imgs, subsampling, outs, cap, size_ptrs, stream)
             else:
                 enc.encode_ycbcr_batch_async(imgs, subsampling, outs, cap, size_ptrs, stream, sample_range, sample_format=sample_format,
@@ -895,6 +941,31 @@ class Encoder:
         rc = lib.jpegamd_encode_ycbcr_interleaved_batch_async(self._h, arr, n, int(subsampling), outs, out_cap, sizes, C.c_void_p(stream))
         if rc:
             raise JpegAmdError(rc, "jpegamd_encode_ycbcr_interleaved_batch_async")
+
+    def encode_color_interleaved_restart_batch_async(self, imgs, subsampling: int, restart_interval: int, out_ptrs, out_cap: int, size_ptrs,
+                                                     stream: int = 0):
+        """encode_color_interleaved_batch_async with restart intervals of `restart_interval` MCUs (DRI / RSTn; 0: the file without)
+        (jpegamd_encode_color_interleaved_restart_batch_async)."""
+        n = len(imgs)
+        arr = (Image * n)(*imgs)
+        outs = (C.c_void_p * n)(*[C.c_void_p(p) for p in out_ptrs])
+        sizes = (C.c_void_p * n)(*[C.c_void_p(p) for p in size_ptrs])
+        rc = lib.jpegamd_encode_color_interleaved_restart_batch_async(self._h, arr, n, int(subsampling), int(restart_interval), outs, out_cap, sizes,
+                                                                      C.c_void_p(stream))
+        if rc:
+            raise JpegAmdError(rc, "jpegamd_encode_color_interleaved_restart_batch_async")
+
+    def encode_ycbcr_interleaved_restart_batch_async(self, imgs, subsampling: int, restart_interval: int, out_ptrs, out_cap: int, size_ptrs,
+                                                     stream: int = 0):
+        """encode_ycbcr_interleaved_batch_async with restart intervals (jpegamd_encode_ycbcr_interleaved_restart_batch_async)."""
+        n = len(imgs)
+        arr = (YCbCrImage * n)(*imgs)
+        outs = (C.c_void_p * n)(*[C.c_void_p(p) for p in out_ptrs])
+        sizes = (C.c_void_p * n)(*[C.c_void_p(p) for p in size_ptrs])
+        rc = lib.jpegamd_encode_ycbcr_interleaved_restart_batch_async(self._h, arr, n, int(subsampling), int(restart_interval), outs, out_cap, sizes,
+                                                                      C.c_void_p(stream))
+        if rc:
+            raise JpegAmdError(rc, "jpegamd_encode_ycbcr_interleaved_restart_batch_async")
 
     def color_profile(self, slot: int):
         """Per-kernel ns of a profiled colour encode: planes, (tile, merge, finalize) x Y / Cb / Cr, append."""

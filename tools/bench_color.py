@@ -40,6 +40,9 @@ preallocated [N, H, W, 3] tensor, then the packed batch entry.
 --scan interleaved (with --batch N, default 8; sources rgb, i420, nv12, i422 at full range, BT.601) sends the batch loop through the
 one-scan entries (jpegamd_encode_color_interleaved_batch_async / jpegamd_encode_ycbcr_interleaved_batch_async); the line then carries
 "scan".  The whole call is timed (ns_total); the per-kernel split comes from a kernel trace of the same command.
+--restart N|row (with --scan interleaved alone): restart intervals of N MCUs, or of one MCU row, through the _restart entries
+(jpegamd_encode_color_interleaved_restart_batch_async / jpegamd_encode_ycbcr_interleaved_restart_batch_async); the line then carries
+"restart_interval" in MCUs.  --restart 0 goes through those entries with interval 0 (the file without restart intervals).
 """
 from __future__ import annotations
 
@@ -78,6 +81,8 @@ def main() -> None:
     ap.add_argument("--repack", action="store_true", help="--layout chw: also time permute + packed encode")
     ap.add_argument("--scan", choices=("separate", "interleaved"), default="separate",
                     help="interleaved: the batch loop goes through the one-scan entries (rgb, i420, nv12, i422; full range, bt601)")
+    ap.add_argument("--restart", default=None, metavar="N|row",
+                    help="--scan interleaved: restart intervals of N MCUs (0 .. 65535), or `row` for one MCU row")
     a = ap.parse_args()
     import torch                          # (the device runtime comes up through torch first, as in bench.py)
     if not torch.cuda.is_available():
@@ -108,6 +113,11 @@ def main() -> None:
     if a.scan == "interleaved" and (a.layout is not None or a.sample_range != "full" or a.matrix != "bt601" or
                                     any(s in ("yuyv", "p010", "i010") for s in sources)):
         sys.exit("--scan interleaved takes --source rgb, i420, nv12, i422 at --range full --matrix bt601")
+    if a.restart is not None:
+        if a.scan != "interleaved":
+            sys.exit("--restart needs --scan interleaved")
+        if a.restart != "row" and not (a.restart.isdigit() and int(a.restart) <= 65535):
+            sys.exit("--restart takes a number of MCUs, 0 .. 65535, or `row`")
     if a.batch is not None or sources != ["rgb"] or a.scan == "interleaved":
         run_batch(a, jpegamd, torch, dev, sources)
         return
@@ -245,11 +255,19 @@ def run_batch(a, jpegamd, torch, dev, sources=("rgb",)) -> None:
         ycc = describe(tensors) if describe else None
         one_scan = a.scan == "interleaved"
         cap = jpegamd.max_jfif_bytes_interleaved(w, h, sub) if one_scan else jpegamd.max_jfif_bytes_color(w, h, sub)
+        restart = None
+        if a.restart is not None:                                # `row`: ceil(W / 8) MCUs at 4:4:4, ceil(W / 16) otherwise
+            restart = -(-w // (8 if sub == jpegamd.SUBSAMPLE_444 else 16)) if a.restart == "row" else int(a.restart)
+            cap = jpegamd.max_jfif_bytes_interleaved_restart(w, h, sub, restart)
         outs = [torch.empty(cap, dtype=torch.uint8, device=dev) for _ in range(n)]
         sizes = torch.zeros(n, dtype=torch.int64, device=dev)
         out_ptrs = [o.data_ptr() for o in outs]
         size_ptrs = [sizes.data_ptr() + 8 * i for i in range(n)]
-        if one_scan and ycc is None:
+        if restart is not None and ycc is None:
+            call = lambda: enc.encode_color_interleaved_restart_batch_async(descs, sub, restart, out_ptrs, cap, size_ptrs, stream)
+        elif restart is not None:
+            call = lambda: enc.encode_ycbcr_interleaved_restart_batch_async(ycc, sub, restart, out_ptrs, cap, size_ptrs, stream)
+        elif one_scan and ycc is None:
             call = lambda: enc.encode_color_interleaved_batch_async(descs, sub, out_ptrs, cap, size_ptrs, stream)
         elif one_scan:
             call = lambda: enc.encode_ycbcr_interleaved_batch_async(ycc, sub, out_ptrs, cap, size_ptrs, stream)
@@ -278,6 +296,8 @@ def run_batch(a, jpegamd, torch, dev, sources=("rgb",)) -> None:
                 "gpixels_per_s": round(n * w * h / t, 2)}
         if one_scan:
             line["scan"] = "interleaved"
+        if restart is not None:
+            line["restart_interval"] = restart
         if limited:
             line["range"] = "limited"
         if bt709 and ycc is not None:
