@@ -337,7 +337,8 @@ int32_t jpegamd_encode_ycbcr_matrix_batch_async(JpegAmdEncoder *enc, const JpegA
  * it is slower per picture than the three-scan entries.  Its scratch -- the coefficient planes and the path's own segment arrays
  * -- is allocated on the context's first interleaved call, sized for that call and grown when a later one needs more; a large batch
  * goes through in groups of pictures that bound it.  Limited range, 16-bit samples, BT.709, packed 4:2:2, planar RGB and 4-byte
- * pixels in one scan are follow-ups. */
+ * pixels in one scan: the three entries further down (jpegamd_encode_ycbcr_interleaved_matrix_batch_async and its neighbours).
+ * Y210 and a single-picture or row-sharded one-scan entry are follow-ups. */
 int32_t jpegamd_encode_color_interleaved_batch_async(JpegAmdEncoder *enc, const JpegAmdImage *imgs, int32_t count, int32_t subsampling,
                                                      void *const *outs_dev, uint64_t out_capacity, uint64_t *const *out_sizes_dev,
                                                      void *stream);
@@ -381,6 +382,34 @@ int32_t jpegamd_encode_ycbcr_interleaved_restart_batch_async(JpegAmdEncoder *enc
  * rounds up on its own -- at most one more byte --, may have that byte stuffed, and ends with two marker bytes.  With
  * restart_interval 0 it equals jpegamd_max_jfif_bytes_interleaved; 0 for bad arguments (restart_interval outside 0 .. 65535 too). */
 uint64_t jpegamd_max_jfif_bytes_interleaved_restart(int32_t width, int32_t height, int32_t subsampling, int32_t restart_interval);
+
+/* The one-scan files from EVERY source the three-scan entries read.  No new file: the one-scan file above -- with
+ * restart_interval 1 .. 65535 the file with restart intervals, with 0 the file without; anything else JPEGAMD_ERR_ARG -- built from
+ * the 8-bit full-range BT.601 Y, Cb and Cr samples that the three-scan entry of the same input codes.  Prefix, DRI, SOS, MCU order,
+ * pad rule, DC predictors, stuffing, RSTn, flush, the two bounds above, capacity behaviour, statistics (exact_fallbacks: the
+ * three-scan entry's figure for the same input), profiling and context sizing are those of the entries above; arguments are checked
+ * before the context is read.
+ *   jpegamd_encode_ycbcr_interleaved_matrix_batch_async takes exactly what jpegamd_encode_ycbcr_matrix_batch_async takes and refuses
+ *     what it refuses: any chroma layout (packed _YUYV / _UYVY at JPEGAMD_SUBSAMPLE_422 alone), sample_range FULL / LIMITED,
+ *     sample_format 8 / 10_MSB / 10_LSB (packed with 16-bit samples, Y210: JPEGAMD_ERR_ARG), matrix BT601 / BT709.  The samples are
+ *     the caller's after the depth map, the range map and -- BT.709 -- the matrix map, in that order, sample for sample.  Every kind
+ *     but BT.709 is read where it lies by the tile kernel; a BT.709 batch runs the one pass of the three-scan entry first.  With
+ *     8-bit full-range BT.601 samples in planes or pairs the file is jpegamd_encode_ycbcr_interleaved_restart_batch_async's, byte for
+ *     byte.
+ *   jpegamd_encode_color_interleaved_pixels_batch_async takes JPEGAMD_ORDER_BGR, _RGB, _RGBA and _BGRA (GRAY and unknown orders:
+ *     JPEGAMD_ERR_ARG); the file is that of the same R, G, B values stored as packed RGB.
+ *   jpegamd_encode_planar_interleaved_batch_async takes three planes per picture, as jpegamd_encode_planar_batch_async; subsampling 0
+ *     (no grayscale one-scan file) is JPEGAMD_ERR_ARG. */
+int32_t jpegamd_encode_ycbcr_interleaved_matrix_batch_async(JpegAmdEncoder *enc, const JpegAmdYCbCrImage *imgs, int32_t count,
+                                                            int32_t subsampling, int32_t sample_range, int32_t sample_format, int32_t matrix,
+                                                            int32_t restart_interval, void *const *outs_dev, uint64_t out_capacity,
+                                                            void *const *out_sizes_dev, void *stream);
+int32_t jpegamd_encode_color_interleaved_pixels_batch_async(JpegAmdEncoder *enc, const JpegAmdImage *imgs, int32_t count, int32_t subsampling,
+                                                            int32_t restart_interval, void *const *outs_dev, uint64_t out_capacity,
+                                                            uint64_t *const *out_sizes_dev, void *stream);
+int32_t jpegamd_encode_planar_interleaved_batch_async(JpegAmdEncoder *enc, const JpegAmdPlanarImage *imgs, int32_t count, int32_t subsampling,
+                                                      int32_t restart_interval, void *const *outs_dev, uint64_t out_capacity,
+                                                      void *const *out_sizes_dev, void *stream);
 
 /* Which kernels follow k_tile_encode for whole pictures (no reference counterpart: a tuning knob, results are byte-identical).
  *   PAIR    k_segment_merge + k_finalize: the tiles' bit strings joined per segment, then stitched behind a kernel boundary;

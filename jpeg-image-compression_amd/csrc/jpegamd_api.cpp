@@ -1343,30 +1343,39 @@ extern "C" int32_t jpegamd_encode_color_batch_async(JpegAmdEncoder *e, const Jpe
     return color_batch(e, g0, ps, count, subsampling, outs_dev, out_capacity, out_sizes_dev, stream_);
 }
 
-// `count` planar pictures: the argument checks, then the grayscale or the colour batch with the planes as the pixel source.
-extern "C" int32_t jpegamd_encode_planar_batch_async(JpegAmdEncoder *e, const JpegAmdPlanarImage *imgs, int32_t count, int32_t subsampling,
-                                                     void *const *outs_dev, uint64_t out_capacity, void *const *out_sizes_dev,
-                                                     void *stream_) {
-    // the arguments first: nothing of the context is read before they are known to be good
+// The arguments of a planar batch, checked before anything of the context is read (`gray_ok`: subsampling 0 is taken) -> the R planes
+// as a picture of the internal planar order, all three planes in ps.
+static int32_t planar_args(const JpegAmdEncoder *e, const JpegAmdPlanarImage *imgs, int32_t count, int32_t subsampling, bool gray_ok,
+                           void *const *outs_dev, void *const *out_sizes_dev, JpegAmdImage *g0, PlaneSet *ps, uint64_t **sizes) {
     if (!e || !imgs || !outs_dev || !out_sizes_dev || count < 1 || count > kMaxBatch) return JPEGAMD_ERR_ARG;
-    if (subsampling != 0 && !sub_valid(subsampling)) return JPEGAMD_ERR_ARG;
+    if (!(gray_ok && subsampling == 0) && !sub_valid(subsampling)) return JPEGAMD_ERR_ARG;
     const JpegAmdPlanarImage &p0 = imgs[0];
     if (p0.width <= 0 || p0.height <= 0 || p0.width > 65535 || p0.height > 65535 || p0.row_stride < p0.width) return JPEGAMD_ERR_ARG;
-    PlaneSet ps = {};
-    uint64_t *sizes[kMaxBatch];
+    *ps = PlaneSet{};
     for (int i = 0; i < count; ++i) {
         const JpegAmdPlanarImage &g = imgs[i];
         if (!outs_dev[i] || !out_sizes_dev[i] || !g.plane[0] || !g.plane[1] || !g.plane[2]) return JPEGAMD_ERR_ARG;
         if (g.width != p0.width || g.height != p0.height || g.row_stride != p0.row_stride || (g.bottom_up != 0) != (p0.bottom_up != 0) ||
             g.quality != p0.quality)
             return JPEGAMD_ERR_ARG;
-        for (int k = 0; k < 3; ++k) ps.p[k][i] = (const uint8_t *)g.plane[k];
+        for (int k = 0; k < 3; ++k) ps->p[k][i] = (const uint8_t *)g.plane[k];
         sizes[i] = (uint64_t *)out_sizes_dev[i];
     }
+    g0->pixels = p0.plane[0];
+    g0->width = p0.width; g0->height = p0.height; g0->row_stride = p0.row_stride; g0->bottom_up = p0.bottom_up;
+    g0->channel_order = kOrderPlanar; g0->quality = p0.quality;
+    return JPEGAMD_OK;
+}
+
+// `count` planar pictures: the argument checks, then the grayscale or the colour batch with the planes as the pixel source.
+extern "C" int32_t jpegamd_encode_planar_batch_async(JpegAmdEncoder *e, const JpegAmdPlanarImage *imgs, int32_t count, int32_t subsampling,
+                                                     void *const *outs_dev, uint64_t out_capacity, void *const *out_sizes_dev,
+                                                     void *stream_) {
+    // the arguments first: nothing of the context is read before they are known to be good
     JpegAmdImage g0;
-    g0.pixels = p0.plane[0];
-    g0.width = p0.width; g0.height = p0.height; g0.row_stride = p0.row_stride; g0.bottom_up = p0.bottom_up;
-    g0.channel_order = kOrderPlanar; g0.quality = p0.quality;
+    PlaneSet ps;
+    uint64_t *sizes[kMaxBatch];
+    if (int32_t rc = planar_args(e, imgs, count, subsampling, true, outs_dev, out_sizes_dev, &g0, &ps, sizes)) return rc;
     if (subsampling == 0) return gray_batch(e, g0, ps, count, outs_dev, out_capacity, sizes, 1, stream_);
     return color_batch(e, g0, ps, count, subsampling, outs_dev, out_capacity, sizes, stream_);
 }
@@ -1610,19 +1619,27 @@ static int32_t prepare_mcu_prefix(JpegAmdEncoder *e, const JpegAmdImage *img, in
     return JPEGAMD_OK;
 }
 
-// The interleaved files of a batch whose arguments are known to be good: g0 describes every picture, px holds their pixels.
-// `ycc` (a YCbCr batch, 8-bit full-range BT.601): g0 / px are the Y planes as a GRAY picture, the chroma comes from the caller.
+// The interleaved files of a batch whose arguments are known to be good: g0 describes every picture, px holds their pixels (any
+// layout color_batch takes).  `ycc_in` (a YCbCr batch of any kind): g0 / px are the Y planes as a GRAY picture, the chroma comes
+// from the caller and every launch reads it where it lies; a BT.709 batch (ycc_in->matrix) is the RGB route with
+// k_ycbcr_matrix_batch in front, as in color_batch: every launch then reads the full-range BT.601 planes that pass leaves in scratch.
 // `restart`: the restart interval in MCUs (1 .. 65535), or 0 for the file without -- the launches below are then what they were
 // before there were restart intervals: k_mcu_segments<false>, k_finalize, k_mcu_totals.
 static int32_t interleaved_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, const PlaneSet &px, int32_t count, int32_t subsampling, int32_t restart,
                                  void *const *outs_dev, uint64_t out_capacity, uint64_t *const *out_sizes_dev, void *stream_,
-                                 const YccSource *ycc = nullptr) {
+                                 const YccSource *ycc_in = nullptr) {
+    const bool mx = ycc_in && ycc_in->matrix == JPEGAMD_MATRIX_BT709;
+    const YccSource *const ycc = mx ? nullptr : ycc_in;               // what the launches read: the caller's planes, or the scratch
+    const bool planar = g0.channel_order == kOrderPlanar;
     const McuGeometry g = mcu_geometry(g0.width, g0.height, subsampling, restart);
     // segments as short as one MCU: a picture whose scratch alone is beyond the group budget is refused, nothing allocated or launched
     if (restart && mcu_scratch_per_pic(g) > kMcuScratchBudget) return JPEGAMD_ERR_TOO_LARGE;
     // every launch codes ONE picture's component: the Y plane and a chroma plane must fit the context
+    const MatrixScratch ms = matrix_scratch(g0.width, g0.height, count, g.chroma.plane_bytes);
+    JpegAmdImage gy = g0;                                            // the Y launches' picture: a BT.709 batch reads the scratch Y planes
+    if (mx) gy.row_stride = ms.ypitch;
     ImageDesc iy;
-    int32_t rc = describe(e, &g0, &iy);
+    int32_t rc = describe(e, &gy, &iy, kSegTiles, planar ? kAcceptPlanar : kAcceptPx4);
     if (rc) return rc;
     const ChromaGeom &cg = g.chroma;
     JpegAmdImage pimg = g0;
@@ -1637,7 +1654,7 @@ static int32_t interleaved_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, cons
     const int group = (int)std::max<size_t>(1, std::min<size_t>((size_t)count, kMcuScratchBudget / per_pic));
     rc = color_alloc_consts(e);
     if (rc) return rc;
-    rc = color_batch_alloc(e, ycc ? 0 : 2 * (size_t)count * cg.plane_bytes + 256, 0);
+    rc = color_batch_alloc(e, mx ? ms.total : (ycc ? 0 : 2 * (size_t)count * cg.plane_bytes + 256), 0);
     if (rc) return rc;
     rc = mcu_alloc(e, g, group);
     if (rc) return rc;
@@ -1660,7 +1677,11 @@ static int32_t interleaved_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, cons
     HIP_TRY(hipMemsetAsync(m.scan_stats, 0, sizeof(ScanStats), stream));
     HIP_TRY(hipMemsetAsync(e->stats_dev, 0, offsetof(ScanStats, status), stream));      // the sums and the size; the status stays sticky
 
-    if (!ycc && launch_plane_pass(e, g0, px, count, subsampling, cg, stream, nullptr)) return JPEGAMD_ERR_HIP;
+    if (mx) {                                                        // once for the whole call, in front of the groups
+        if (launch_matrix_pass(e, g0, px, *ycc_in, count, subsampling, cg, ms, stream, nullptr)) return JPEGAMD_ERR_HIP;
+    } else if (!ycc) {
+        if (launch_plane_pass(e, g0, px, count, subsampling, cg, stream, nullptr)) return JPEGAMD_ERR_HIP;
+    }
     const size_t cb_off = (size_t)g.bw * g.bh * 64, cr_off = cb_off + (size_t)g.mx * g.my * 64;
     for (int first = 0; first < count; first += group) {
         const int n = std::min(group, count - first);
@@ -1669,9 +1690,14 @@ static int32_t interleaved_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, cons
             int16_t *coef = m.coef + (size_t)i * g.coef_per_pic;
             {   // Y
                 ImageDesc im = iy;
-                set_single_picture(&im, px.p[0][p]);
-                const TileSource src = y_source_of(g0, ycc, &im);
-                if (launch_transform(e, im, true, nullptr, coef, nullptr, stream, nullptr, src)) return JPEGAMD_ERR_HIP;
+                set_single_picture(&im, mx ? c.bplanes + ms.y_off + (size_t)p * ms.yplane_bytes : px.p[0][p]);
+                PlaneSet one = {};                                   // a planar picture: ITS G and B planes are image 0 of the launch
+                if (planar) {
+                    for (int k = 0; k < 3; ++k) one.p[k][0] = px.p[k][p];
+                    im.fast_ok = dword_loader_ok((uintptr_t)px.p[0][p] | (uintptr_t)px.p[1][p] | (uintptr_t)px.p[2][p], im.row_stride);
+                }
+                const TileSource src = y_source_of(gy, ycc, &im);
+                if (launch_transform(e, im, true, nullptr, coef, nullptr, stream, nullptr, src, planar ? &one : nullptr)) return JPEGAMD_ERR_HIP;
                 const PictureStatsArgs ps = {e->tile_head, e->huff, im.num_tiles, 1, 0, 0, pic + (size_t)p * kPicStatWords};
                 if (launch_picture_stats(ps, stream)) return JPEGAMD_ERR_HIP;
             }
@@ -1733,19 +1759,47 @@ static int32_t interleaved_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, cons
 
 static bool restart_valid(int32_t restart) { return restart >= 0 && restart <= 65535; }
 
-extern "C" int32_t jpegamd_encode_color_interleaved_restart_batch_async(JpegAmdEncoder *e, const JpegAmdImage *imgs, int32_t count, int32_t subsampling,
-                                                                        int32_t restart_interval, void *const *outs_dev, uint64_t out_capacity,
-                                                                        uint64_t *const *out_sizes_dev, void *stream_) {
+// `count` packed pictures in one scan: the argument checks (`px4`: the entry takes RGBA / BGRA as well), then the interleaved batch.
+static int32_t interleaved_pixels(JpegAmdEncoder *e, const JpegAmdImage *imgs, int32_t count, int32_t subsampling, int32_t restart_interval, bool px4,
+                                  void *const *outs_dev, uint64_t out_capacity, uint64_t *const *out_sizes_dev, void *stream_) {
     // the arguments first: nothing of the context is read before they are known to be good
     if (!restart_valid(restart_interval)) return JPEGAMD_ERR_ARG;
     if (!e || !imgs || !outs_dev || !out_sizes_dev || count < 1 || count > kMaxBatch) return JPEGAMD_ERR_ARG;
     if (!sub_valid(subsampling)) return JPEGAMD_ERR_ARG;
     const JpegAmdImage &g0 = imgs[0];
-    if (g0.channel_order != JPEGAMD_ORDER_BGR && g0.channel_order != JPEGAMD_ORDER_RGB) return JPEGAMD_ERR_ARG;
-    if (g0.width <= 0 || g0.height <= 0 || g0.width > 65535 || g0.height > 65535 || g0.row_stride < 3 * (int64_t)g0.width) return JPEGAMD_ERR_ARG;
+    if (g0.channel_order != JPEGAMD_ORDER_BGR && g0.channel_order != JPEGAMD_ORDER_RGB && !(px4 && is_px4(g0.channel_order))) return JPEGAMD_ERR_ARG;
+    if (g0.width <= 0 || g0.height <= 0 || g0.width > 65535 || g0.height > 65535 ||
+        g0.row_stride < bytes_per_pixel(g0.channel_order) * (int64_t)g0.width)
+        return JPEGAMD_ERR_ARG;
     PlaneSet ps;
     if (int32_t rc = uniform_batch_args(imgs, count, outs_dev, out_sizes_dev, &ps)) return rc;
     return interleaved_batch(e, g0, ps, count, subsampling, restart_interval, outs_dev, out_capacity, out_sizes_dev, stream_);
+}
+
+extern "C" int32_t jpegamd_encode_color_interleaved_restart_batch_async(JpegAmdEncoder *e, const JpegAmdImage *imgs, int32_t count, int32_t subsampling,
+                                                                        int32_t restart_interval, void *const *outs_dev, uint64_t out_capacity,
+                                                                        uint64_t *const *out_sizes_dev, void *stream_) {
+    return interleaved_pixels(e, imgs, count, subsampling, restart_interval, false, outs_dev, out_capacity, out_sizes_dev, stream_);
+}
+
+// ... in any of the four pixel orders: RGBA / BGRA are read where they lie.
+extern "C" int32_t jpegamd_encode_color_interleaved_pixels_batch_async(JpegAmdEncoder *e, const JpegAmdImage *imgs, int32_t count, int32_t subsampling,
+                                                                       int32_t restart_interval, void *const *outs_dev, uint64_t out_capacity,
+                                                                       uint64_t *const *out_sizes_dev, void *stream_) {
+    return interleaved_pixels(e, imgs, count, subsampling, restart_interval, true, outs_dev, out_capacity, out_sizes_dev, stream_);
+}
+
+// `count` planar pictures in one scan.  No grayscale file here: subsampling 0 is refused.
+extern "C" int32_t jpegamd_encode_planar_interleaved_batch_async(JpegAmdEncoder *e, const JpegAmdPlanarImage *imgs, int32_t count, int32_t subsampling,
+                                                                 int32_t restart_interval, void *const *outs_dev, uint64_t out_capacity,
+                                                                 void *const *out_sizes_dev, void *stream_) {
+    // the arguments first: nothing of the context is read before they are known to be good
+    if (!restart_valid(restart_interval)) return JPEGAMD_ERR_ARG;
+    JpegAmdImage g0;
+    PlaneSet ps;
+    uint64_t *sizes[kMaxBatch];
+    if (int32_t rc = planar_args(e, imgs, count, subsampling, false, outs_dev, out_sizes_dev, &g0, &ps, sizes)) return rc;
+    return interleaved_batch(e, g0, ps, count, subsampling, restart_interval, outs_dev, out_capacity, sizes, stream_);
 }
 
 extern "C" int32_t jpegamd_encode_color_interleaved_batch_async(JpegAmdEncoder *e, const JpegAmdImage *imgs, int32_t count, int32_t subsampling,
@@ -1769,6 +1823,29 @@ extern "C" int32_t jpegamd_encode_ycbcr_interleaved_restart_batch_async(JpegAmdE
                                 true, &g0, &ps, &ycc, sizes))
         return rc;
     return interleaved_batch(e, g0, ps, count, subsampling, restart_interval, outs_dev, out_capacity, sizes, stream_, &ycc);
+}
+
+// `count` YCbCr pictures of any kind jpegamd_encode_ycbcr_matrix_batch_async takes, in one scan: the same argument checks, then the
+// interleaved batch, whose launches read the samples where they lie (BT.709: behind k_ycbcr_matrix_batch).
+extern "C" int32_t jpegamd_encode_ycbcr_interleaved_matrix_batch_async(JpegAmdEncoder *e, const JpegAmdYCbCrImage *imgs, int32_t count, int32_t subsampling,
+                                                                       int32_t sample_range, int32_t sample_format, int32_t matrix,
+                                                                       int32_t restart_interval, void *const *outs_dev, uint64_t out_capacity,
+                                                                       void *const *out_sizes_dev, void *stream_) {
+    // the arguments first: nothing of the context is read before they are known to be good
+    if (!restart_valid(restart_interval)) return JPEGAMD_ERR_ARG;
+    JpegAmdImage g0;
+    PlaneSet ps;
+    YccSource ycc;
+    uint64_t *sizes[kMaxBatch];
+    if (int32_t rc = ycbcr_args(e, imgs, count, subsampling, sample_range, sample_format, matrix, outs_dev, out_sizes_dev, true, &g0, &ps, &ycc, sizes))
+        return rc;
+    return interleaved_batch(e, g0, ps, count, subsampling, restart_interval, outs_dev, out_capacity, sizes, stream_, &ycc);
+}
+
+// Host-only (tests): whether the plain build has the k_tile_encode instantiation (taps, layout, chroma tables, expand): 1 or 0.  No
+// device is needed.  Not part of the public header.
+extern "C" int32_t jpegamd_debug_tile_variant(int32_t taps, int32_t layout, int32_t chroma, int32_t expand) {
+    return tile_variant_exists(taps != 0, TileSource{layout, chroma != 0, expand != 0}) ? 1 : 0;
 }
 
 extern "C" int32_t jpegamd_encode_ycbcr_interleaved_batch_async(JpegAmdEncoder *e, const JpegAmdYCbCrImage *imgs, int32_t count, int32_t subsampling,

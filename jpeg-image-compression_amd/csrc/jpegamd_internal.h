@@ -127,7 +127,7 @@ constexpr int kMaxBatch = 32;           // images of one geometry coded by ONE l
 // `expand`: the samples are limited range (JPEGAMD_RANGE_LIMITED) and are mapped to full range behind the loader, Y by the luma map
 // and Cb / Cr by the chroma map; with a 16-bit layout it selects the limited-range narrowing.  launch_tile_transform has the list of
 // combinations that exist as kernels (the stamped build: luma kSrcRgb / kSrcPlane and chroma kSrcPlane alone; stage taps: luma
-// kSrcRgb / kSrcPlane, and -- the coefficient planes of an interleaved-MCU file -- chroma kSrcPlane / kSrcPair); any other is
+// kSrcRgb / kSrcPlane, and -- the coefficient planes of an interleaved-MCU file -- every source a colour batch reads); any other is
 // hipErrorInvalidValue.
 constexpr int kSrcRgb = 0, kSrcPlane = 1, kSrcPx4 = 2, kSrcPlanar = 3, kSrcPair = 4, kSrcQuad = 5, kSrcPlane16 = 6, kSrcPair16 = 7;
 struct TileSource {
@@ -205,6 +205,8 @@ struct TilePlanes {                     // the second and third plane of every p
 };
 int launch_tile_transform(const ImageDesc &im, const TransformOutM &out, bool taps, void *stream, void *const *ev = nullptr, TileSource src = {},
                           const TilePlanes *planes = nullptr);
+// whether launch_tile_transform has a kernel for (taps, src): a lookup in its list, no device needed
+bool tile_variant_exists(bool taps, TileSource src);
 // the same kernel with its phases stamped (out.stamps must point at 16 words per wave): jpegamd_tile_pipeline.hip, -DJPEGAMD_STAMPED_TU
 int launch_tile_transform_stamped(const ImageDesc &im, const TransformOutM &out, bool taps, void *stream, void *const *ev = nullptr, TileSource src = {},
                                   const TilePlanes *planes = nullptr);

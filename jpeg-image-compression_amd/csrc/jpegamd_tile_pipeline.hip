@@ -736,7 +736,7 @@ void k_tile_encode(const ImageDesc im, const TransformOutM out, const TileSched 
             }
         }
         if constexpr (kSrc == kSrcPlane16 || kSrc == kSrcPair16) {   // 16-bit words -> the 8-bit samples, either range (kExpand: limited): ONE place behind both
-            static_assert(!kTaps, "the 16-bit sources have no stage taps");   // loaders, so replicated edges copy mapped samples and the stash holds them
+            static_assert(kSrc == kSrcPlane16 || kZBits != kZrlBits, "a pair of 16-bit words is chroma: it has no luma map");   // loaders, so replicated edges copy mapped samples and the stash holds them
             typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
             const uint32_t sh2 = select_shift(im) * 0x00010001u;
 #pragma unroll
@@ -747,7 +747,7 @@ void k_tile_encode(const ImageDesc im, const TransformOutM out, const TileSched 
                 bfrag[s] = __builtin_bit_cast(f16x8, pk);
             }
         } else if constexpr (kExpand) {        // limited range -> full range: ONE place behind both loaders, so the stash below holds the mapped samples
-            static_assert(!kTaps && (kSrc == kSrcPlane || kSrc == kSrcPair || kSrc == kSrcQuad), "range expansion is for the sources of a YCbCr batch");
+            static_assert(kSrc == kSrcPlane || kSrc == kSrcPair || kSrc == kSrcQuad, "range expansion is for the sources of a YCbCr batch");
             typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
 #pragma unroll
             for (int s = 0; s < 4; ++s) {
@@ -1345,9 +1345,22 @@ constexpr Variant kVariants[] = {
     kVariant<false, kSrcPlane16>, kVariant<false, kSrcPlane16, true>, kVariant<false, kSrcPair16, true>,           // 10-bit samples in 16-bit words, either depth map
     kVariant<false, kSrcPlane16, false, true>, kVariant<false, kSrcPlane16, true, true>, kVariant<false, kSrcPair16, true, true>,
     kVariant<true, kSrcPlane, true>, kVariant<true, kSrcPair, true>,                                               // chroma coefficient planes of an interleaved-MCU file (tap_zz)
+    // ... and the coefficient planes of every other source such a file is built from: the tap store lies behind the
+    // quantiser, whatever the loader
+    kVariant<true, kSrcPx4>, kVariant<true, kSrcPlanar>,                                                           // Y of RGBA / BGRA pixels and of three planes
+    kVariant<true, kSrcPair>, kVariant<true, kSrcQuad, true>,                                                      // a packed 4:2:2 plane
+    kVariant<true, kSrcPlane, false, true>, kVariant<true, kSrcPlane, true, true>, kVariant<true, kSrcPair, true, true>,      // limited range
+    kVariant<true, kSrcPair, false, true>, kVariant<true, kSrcQuad, true, true>,
+    kVariant<true, kSrcPlane16>, kVariant<true, kSrcPlane16, true>, kVariant<true, kSrcPair16, true>,              // 16-bit words, either depth map
+    kVariant<true, kSrcPlane16, false, true>, kVariant<true, kSrcPlane16, true, true>, kVariant<true, kSrcPair16, true, true>,
 #endif
     kVariant<false, kSrcPlane>, kVariant<false, kSrcPlane, true>, kVariant<true, kSrcPlane>, kVariant<true, kSrcRgb>, kVariant<false, kSrcRgb>,
 };
+const Variant *find_variant(bool taps, TileSource src) {
+    for (const Variant &k : kVariants)
+        if (k.taps == taps && k.src.layout == src.layout && k.src.chroma == src.chroma && k.src.expand == src.expand) return &k;
+    return nullptr;
+}
 }  // namespace
 
 int launch_tile_transform(const ImageDesc &im, const TransformOutM &out, bool taps, void *stream, void *const *ev, TileSource src, const TilePlanes *planes) {
@@ -1363,12 +1376,14 @@ int launch_tile_transform(const ImageDesc &im, const TransformOutM &out, bool ta
     sch.tiles_per_group = (ntiles + groups - 1) / groups;
     const uint64_t magic = 0x100000000ull / (uint64_t)im.tiles_per_row + 1ull;
     sch.tpr_magic = magic > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)magic;   // tiles_per_row == 1: the correction step makes up for it
-    const Variant *v = nullptr;
-    for (const Variant &k : kVariants)
-        if (k.taps == taps && k.src.layout == src.layout && k.src.chroma == src.chroma && k.src.expand == src.expand) v = &k;
+    const Variant *v = find_variant(taps, src);
     if (!v || (src.layout == kSrcPlanar && !planes)) return (int)hipErrorInvalidValue;
     v->launch(TileLaunch{dim3(wgs), (hipStream_t)stream, ev, im, out, sch, planes});
     return (int)hipGetLastError();
 }
+
+#ifndef JPEGAMD_STAMPED_TU
+bool tile_variant_exists(bool taps, TileSource src) { return find_variant(taps, src) != nullptr; }
+#endif
 
 }  // namespace jpegamd

@@ -127,6 +127,10 @@ def _load() -> C.CDLL:
         "jpegamd_encode_color_interleaved_restart_batch_async": (i32, [vp, C.POINTER(Image), i32, i32, i32, C.POINTER(C.c_void_p), u64, C.POINTER(C.c_void_p), vp]),
         "jpegamd_encode_ycbcr_interleaved_restart_batch_async": (i32, [vp, C.POINTER(YCbCrImage), i32, i32, i32, C.POINTER(C.c_void_p), u64, C.POINTER(C.c_void_p), vp]),
         "jpegamd_max_jfif_bytes_interleaved_restart": (u64, [i32, i32, i32, i32]),
+        "jpegamd_encode_ycbcr_interleaved_matrix_batch_async": (i32, [vp, C.POINTER(YCbCrImage), i32, i32, i32, i32, i32, i32, C.POINTER(C.c_void_p), u64, C.POINTER(C.c_void_p), vp]),
+        "jpegamd_encode_color_interleaved_pixels_batch_async": (i32, [vp, C.POINTER(Image), i32, i32, i32, C.POINTER(C.c_void_p), u64, C.POINTER(C.c_void_p), vp]),
+        "jpegamd_encode_planar_interleaved_batch_async": (i32, [vp, C.POINTER(PlanarImage), i32, i32, i32, C.POINTER(C.c_void_p), u64, C.POINTER(C.c_void_p), vp]),
+        "jpegamd_debug_tile_variant": (i32, [i32, i32, i32, i32]),
         "jpegamd_debug_matrix_coeffs": (i32, [i32, vp]),
         "jpegamd_debug_ycbcr_matrix_planes": (i32, [vp, C.POINTER(YCbCrImage), i32, i32, i32, i32, i32, vp, vp, vp, vp]),
         "jpegamd_debug_chroma_groups": (i32, [i32, i32, i32, i32, i32, i32, i32, vp]),
@@ -149,7 +153,9 @@ def _load() -> C.CDLL:
                     "jpegamd_debug_matrix_coeffs", "jpegamd_debug_ycbcr_matrix_planes", "jpegamd_encode_color_interleaved_batch_async",
                     "jpegamd_encode_ycbcr_interleaved_batch_async", "jpegamd_max_jfif_bytes_interleaved",
                     "jpegamd_encode_color_interleaved_restart_batch_async", "jpegamd_encode_ycbcr_interleaved_restart_batch_async",
-                    "jpegamd_max_jfif_bytes_interleaved_restart") and os.environ.get("JPEGAMD_LIB") and not hasattr(lib, name):
+                    "jpegamd_max_jfif_bytes_interleaved_restart", "jpegamd_encode_ycbcr_interleaved_matrix_batch_async",
+                    "jpegamd_encode_color_interleaved_pixels_batch_async", "jpegamd_encode_planar_interleaved_batch_async",
+                    "jpegamd_debug_tile_variant") and os.environ.get("JPEGAMD_LIB") and not hasattr(lib, name):
             continue                                              # (A/B tooling: a variant build of an older round)
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = res, args
@@ -169,7 +175,8 @@ EXPORTED = ("jpegamd_encoder_create jpegamd_encoder_destroy jpegamd_max_jfif_byt
             "jpegamd_encode_ycbcr_samples_batch_async jpegamd_encode_ycbcr_matrix_batch_async "
             "jpegamd_encode_color_interleaved_batch_async jpegamd_encode_ycbcr_interleaved_batch_async jpegamd_max_jfif_bytes_interleaved "
             "jpegamd_encode_color_interleaved_restart_batch_async jpegamd_encode_ycbcr_interleaved_restart_batch_async "
-            "jpegamd_max_jfif_bytes_interleaved_restart").split()
+            "jpegamd_max_jfif_bytes_interleaved_restart jpegamd_encode_ycbcr_interleaved_matrix_batch_async "
+            "jpegamd_encode_color_interleaved_pixels_batch_async jpegamd_encode_planar_interleaved_batch_async").split()
 
 
 def quant_table(quality: int = 50):
@@ -344,7 +351,7 @@ def encode_tensor(t, quality: int = 0, subsampling: int = SUBSAMPLE_420, layout=
     current stream; one encoder context per device is kept and grown as needed.
     `layout` names how the picture is stored, as for encode_tensor_batch: "chw" [3, H, W], "rgba" / "bgra" [H, W, 4], "hwc" [H, W, 3].
     scan="interleaved": the colour file with ONE scan of interleaved MCUs, as for encode_tensor_batch ([H, W, 3] alone), and with
-    restart_interval= its restart intervals."""
+    restart_interval= its restart intervals (jpegamd.mjpeg.encode_tensor: the one-scan file of every colour layout)."""
     import torch
     if _scan(scan):
         return encode_tensor_batch(t, quality, subsampling, "hwc" if layout is None else layout, _single=True, scan=scan,
@@ -481,7 +488,7 @@ def _named_layout(t, layout, single: bool):
 
 
 def encode_tensor_batch(t, quality: int = 0, subsampling: int = SUBSAMPLE_420, layout=None, _single: bool = False,
-                        scan: str = "separate", restart_interval=None) -> list:
+                        scan: str = "separate", restart_interval=None, _any_layout: bool = False) -> list:
     """A uint8 DEVICE tensor of N pictures -> N JFIF files: [N, H, W, 3] (R, G, B) colour files through
     jpegamd_encode_color_batch_async, [N, H, W] grayscale files through jpegamd_encode_batch_async.  Pictures may be strided
     (t[::2]), pixels within a row must be packed.  Batches of more than MAX_BATCH pictures go as several calls of at most
@@ -493,14 +500,16 @@ def encode_tensor_batch(t, quality: int = 0, subsampling: int = SUBSAMPLE_420, l
     ignored; "hwc" the explicit name of [N, H, W, 3].  The files are those of the same R, G, B values as [N, H, W, 3].
     scan="interleaved": colour files with ONE scan of interleaved MCUs (jpegamd_encode_color_interleaved_batch_async) -- what
     Motion-JPEG containers and hardware decoders take -- for [N, H, W, 3] (layout None or "hwc") and the three colour subsamplings;
-    every other combination is a ValueError.  They decode to the same pixels as the scan="separate" files.
+    every other combination is a ValueError here: jpegamd.mjpeg.encode_tensor_batch gives the one-scan files of every layout.  They
+    decode to the same pixels as the scan="separate" files.
     restart_interval= (scan="interleaved" alone): restart intervals of that many MCUs, 1 .. 65535, or "row" for one MCU row (DRI /
-    RSTn, jpegamd_encode_color_interleaved_restart_batch_async); 0 / None: none."""
+    RSTn, jpegamd_encode_color_interleaved_restart_batch_async); 0 / None: none.
+    (`_any_layout`: jpegamd.mjpeg's call -- scan="interleaved" with every colour layout, through the entries that read them.)"""
     import torch
     interleaved = _scan(scan)
     if not interleaved:
         _restart(restart_interval, False, 1, subsampling)
-    if interleaved and layout not in (None, "hwc"):
+    if interleaved and not _any_layout and layout not in (None, "hwc"):
         raise ValueError(f'scan="interleaved" takes layout="hwc" (or None) alone, not {layout!r}')
     if interleaved and subsampling not in (SUBSAMPLE_444, SUBSAMPLE_420, SUBSAMPLE_422):
         raise ValueError('scan="interleaved" needs SUBSAMPLE_444, SUBSAMPLE_420 or SUBSAMPLE_422')
@@ -509,7 +518,9 @@ def encode_tensor_batch(t, quality: int = 0, subsampling: int = SUBSAMPLE_420, l
         ptr, tensors = (lambda i: t[i].data_ptr()), [t]
     else:
         n, h, w, stride, order, ptr, tensors = _named_layout(t, layout, _single)
-    if interleaved and order != ORDER_RGB:
+    if interleaved and _any_layout and order == ORDER_GRAY:
+        raise ValueError("a one-scan file is a colour file: [N, H, W] grayscale pictures are not taken")
+    if interleaved and not _any_layout and order != ORDER_RGB:
         raise ValueError('scan="interleaved" takes colour pictures [N, H, W, 3] alone')
     ri = _restart(restart_interval, interleaved, w, subsampling)
     if any(not x.is_cuda or x.device != tensors[0].device for x in tensors):
@@ -538,9 +549,14 @@ def encode_tensor_batch(t, quality: int = 0, subsampling: int = SUBSAMPLE_420, l
             k = min(MAX_BATCH, n - b0)
             outs = [out[i].data_ptr() for i in range(k)]
             size_ptrs = [sizes.data_ptr() + 8 * i for i in range(k)]
-            if interleaved:
+            if interleaved and order is None:
+                imgs = [Encoder.planar_image(ptr(b0 + i), w, h, stride, bottom_up=False, quality=quality) for i in range(k)]
+                enc.encode_planar_interleaved_batch_async(imgs, subsampling, ri, outs, cap, size_ptrs, stream)
+            elif interleaved:
                 imgs = [Encoder.image(ptr(b0 + i), w, h, stride, bottom_up=False, channel_order=order, quality=quality) for i in range(k)]
-                if ri:
+                if _any_layout:
+                    enc.encode_color_interleaved_pixels_batch_async(imgs, subsampling, ri, outs, cap, size_ptrs, stream)
+                elif ri:
                     enc.encode_color_interleaved_restart_batch_async(imgs, subsampling, ri, outs, cap, size_ptrs, stream)
                 else:
                     enc.encode_color_interleaved_batch_async(imgs, subsampling, outs, cap, size_ptrs, stream)
@@ -652,7 +668,8 @@ def encode_ycbcr_batch(y, cb, cr=None, quality: int = 0, subsampling: int = SUBS
 
     and a stack of frames [N, 3 * H // 2, W] slices the same way: f[:, :H] and f[:, H:].unflatten(2, (W // 2, 2)).
     scan="interleaved": the files with ONE scan of interleaved MCUs (jpegamd_encode_ycbcr_interleaved_batch_async), for
-    sample_range="full" and matrix="bt601" alone; anything else is a ValueError.  restart_interval= (scan="interleaved" alone): restart
+    sample_range="full" and matrix="bt601" alone; anything else is a ValueError here (jpegamd.mjpeg.encode_ycbcr_batch, _ycbcr16_batch
+    and _yuyv_batch give the one-scan files of every kind).  restart_interval= (scan="interleaved" alone): restart
     intervals of that many MCUs, or "row", as for encode_tensor_batch (jpegamd_encode_ycbcr_interleaved_restart_batch_async)."""
     rng, mat = _sample_range(sample_range), _matrix(matrix)
     interleaved = _scan(scan)
@@ -669,9 +686,10 @@ def encode_ycbcr_batch(y, cb, cr=None, quality: int = 0, subsampling: int = SUBS
 
 
 def _encode_ycbcr_images(device, n, h, w, subsampling, image, sample_range: int = RANGE_FULL, sample_format: int = SAMPLES_8,
-                         matrix: int = MATRIX_BT601, interleaved: bool = False, restart: int = 0):
+                         matrix: int = MATRIX_BT601, interleaved: bool = False, restart: int = 0, any_kind: bool = False):
     """`n` YCbCr pictures of one geometry, picture i described by image(i), through the per-device context in calls of at most
-    MAX_BATCH -> their files."""
+    MAX_BATCH -> their files.  `any_kind` (jpegamd.mjpeg): the interleaved files of whatever range, format, matrix and layout, through
+    jpegamd_encode_ycbcr_interleaved_matrix_batch_async."""
     import torch
     dev = device.index if device.index is not None else torch.cuda.current_device()
     files = []
@@ -696,7 +714,10 @@ def _encode_ycbcr_images(device, n, h, w, subsampling, image, sample_range: int 
             outs = [out[i].data_ptr() for i in range(k)]
             size_ptrs = [sizes.data_ptr() + 8 * i for i in range(k)]
             imgs = [image(b0 + i) for i in range(k)]
-            if restart:
+            if any_kind:
+                enc.encode_ycbcr_interleaved_matrix_batch_async(imgs, subsampling, sample_range, sample_format, matrix, restart, outs, cap,
+                                                                size_ptrs, stream)
+            elif restart:
                 enc.encode_ycbcr_interleaved_restart_batch_async(imgs, subsampling, restart, outs, cap, size_ptrs, stream)
             elif interleaved:
                 enc.encode_ycbcr_interleaved_batch_async(imgs, subsampling, outs, cap, size_ptrs, stream)
@@ -966,6 +987,46 @@ class Encoder:
                                                                       C.c_void_p(stream))
         if rc:
             raise JpegAmdError(rc, "jpegamd_encode_ycbcr_interleaved_restart_batch_async")
+
+    def encode_ycbcr_interleaved_matrix_batch_async(self, imgs, subsampling: int, sample_range: int, sample_format: int, matrix: int,
+                                                    restart_interval: int, out_ptrs, out_cap: int, size_ptrs, stream: int = 0):
+        """The one-scan files of YCbCr pictures of ANY kind encode_ycbcr_batch_async takes -- limited range, 10-bit words, BT.709, a
+        packed 4:2:2 plane -- with restart intervals of `restart_interval` MCUs (0: none)
+        (jpegamd_encode_ycbcr_interleaved_matrix_batch_async)."""
+        n = len(imgs)
+        arr = (YCbCrImage * n)(*imgs)
+        outs = (C.c_void_p * n)(*[C.c_void_p(p) for p in out_ptrs])
+        sizes = (C.c_void_p * n)(*[C.c_void_p(p) for p in size_ptrs])
+        rc = lib.jpegamd_encode_ycbcr_interleaved_matrix_batch_async(self._h, arr, n, int(subsampling), int(sample_range), int(sample_format),
+                                                                     int(matrix), int(restart_interval), outs, out_cap, sizes, C.c_void_p(stream))
+        if rc:
+            raise JpegAmdError(rc, "jpegamd_encode_ycbcr_interleaved_matrix_batch_async")
+
+    def encode_color_interleaved_pixels_batch_async(self, imgs, subsampling: int, restart_interval: int, out_ptrs, out_cap: int, size_ptrs,
+                                                    stream: int = 0):
+        """The one-scan files of RGB / BGR / RGBA / BGRA pictures, with restart intervals of `restart_interval` MCUs (0: none)
+        (jpegamd_encode_color_interleaved_pixels_batch_async)."""
+        n = len(imgs)
+        arr = (Image * n)(*imgs)
+        outs = (C.c_void_p * n)(*[C.c_void_p(p) for p in out_ptrs])
+        sizes = (C.c_void_p * n)(*[C.c_void_p(p) for p in size_ptrs])
+        rc = lib.jpegamd_encode_color_interleaved_pixels_batch_async(self._h, arr, n, int(subsampling), int(restart_interval), outs, out_cap, sizes,
+                                                                     C.c_void_p(stream))
+        if rc:
+            raise JpegAmdError(rc, "jpegamd_encode_color_interleaved_pixels_batch_async")
+
+    def encode_planar_interleaved_batch_async(self, imgs, subsampling: int, restart_interval: int, out_ptrs, out_cap: int, size_ptrs,
+                                              stream: int = 0):
+        """The one-scan files of planar pictures (planar_image), with restart intervals of `restart_interval` MCUs (0: none)
+        (jpegamd_encode_planar_interleaved_batch_async); no grayscale files: subsampling 0 is refused."""
+        n = len(imgs)
+        arr = (PlanarImage * n)(*imgs)
+        outs = (C.c_void_p * n)(*[C.c_void_p(p) for p in out_ptrs])
+        sizes = (C.c_void_p * n)(*[C.c_void_p(p) for p in size_ptrs])
+        rc = lib.jpegamd_encode_planar_interleaved_batch_async(self._h, arr, n, int(subsampling), int(restart_interval), outs, out_cap, sizes,
+                                                               C.c_void_p(stream))
+        if rc:
+            raise JpegAmdError(rc, "jpegamd_encode_planar_interleaved_batch_async")
 
     def color_profile(self, slot: int):
         """Per-kernel ns of a profiled colour encode: planes, (tile, merge, finalize) x Y / Cb / Cr, append."""

@@ -37,9 +37,13 @@ events on the stream; --rounds R medians of --steps calls each are reported, wit
 also times the route without the planar entry, in the same run and alternating with the direct one: permute(0, 2, 3, 1) into a
 preallocated [N, H, W, 3] tensor, then the packed batch entry.
 
---scan interleaved (with --batch N, default 8; sources rgb, i420, nv12, i422 at full range, BT.601) sends the batch loop through the
-one-scan entries (jpegamd_encode_color_interleaved_batch_async / jpegamd_encode_ycbcr_interleaved_batch_async); the line then carries
-"scan".  The whole call is timed (ns_total); the per-kernel split comes from a kernel trace of the same command.
+--scan interleaved (with --batch N, default 8) sends the batch loop through the one-scan entries; the line then carries "scan".  The
+whole call is timed (ns_total); the per-kernel split comes from a kernel trace of the same command.  Sources rgb, i420, nv12, i422 at
+--range full --matrix bt601 keep to jpegamd_encode_color_interleaved_batch_async / jpegamd_encode_ycbcr_interleaved_batch_async (a
+library from before the entries below still serves them); yuyv, p010, i010, --range limited and --matrix bt709 go through
+jpegamd_encode_ycbcr_interleaved_matrix_batch_async, and --layout chw / rgba through jpegamd_encode_planar_interleaved_batch_async /
+jpegamd_encode_color_interleaved_pixels_batch_async.  --mapped (with --range limited; i420, nv12, i422) applies the range map to the
+frames once, outside the timed loop, and codes the mapped frames at full range: what the older entries code for the same input.
 --restart N|row (with --scan interleaved alone): restart intervals of N MCUs, or of one MCU row, through the _restart entries
 (jpegamd_encode_color_interleaved_restart_batch_async / jpegamd_encode_ycbcr_interleaved_restart_batch_async); the line then carries
 "restart_interval" in MCUs.  --restart 0 goes through those entries with interval 0 (the file without restart intervals).
@@ -80,7 +84,9 @@ def main() -> None:
     ap.add_argument("--rounds", type=int, default=5, help="--layout: medians taken (each of --steps calls)")
     ap.add_argument("--repack", action="store_true", help="--layout chw: also time permute + packed encode")
     ap.add_argument("--scan", choices=("separate", "interleaved"), default="separate",
-                    help="interleaved: the batch loop goes through the one-scan entries (rgb, i420, nv12, i422; full range, bt601)")
+                    help="interleaved: the batch loop goes through the one-scan entries (every --source, --range, --matrix; --layout chw / rgba)")
+    ap.add_argument("--mapped", action="store_true",
+                    help="--range limited (i420, nv12, i422): map the frames once outside the timed loop and code them at full range")
     ap.add_argument("--restart", default=None, metavar="N|row",
                     help="--scan interleaved: restart intervals of N MCUs (0 .. 65535), or `row` for one MCU row")
     a = ap.parse_args()
@@ -92,9 +98,6 @@ def main() -> None:
 
     dev = torch.device("cuda:0")
     w = h = a.size
-    if a.layout is not None:
-        run_layout(a, jpegamd, torch, dev)
-        return
     sources = a.source.split(",")
     if any(s not in ("rgb", "i420", "nv12", "i422", "yuyv", "p010", "i010") for s in sources):
         sys.exit("--source takes rgb, i420, nv12, i422, yuyv, p010, i010 or a comma-separated list of them")
@@ -110,14 +113,18 @@ def main() -> None:
         sys.exit("--matrix bt709 --convert with p010 / i010 is written for --range full (the torch route narrows by a shift)")
     if a.narrow and not any(s in ("p010", "i010") for s in sources):
         sys.exit("--narrow needs --source p010 or i010")
-    if a.scan == "interleaved" and (a.layout is not None or a.sample_range != "full" or a.matrix != "bt601" or
-                                    any(s in ("yuyv", "p010", "i010") for s in sources)):
-        sys.exit("--scan interleaved takes --source rgb, i420, nv12, i422 at --range full --matrix bt601")
+    if a.scan == "interleaved" and (a.convert or a.narrow):
+        sys.exit("--convert and --narrow time routes of the three-scan path: not with --scan interleaved")
+    if a.mapped and (a.sample_range != "limited" or any(s not in ("i420", "nv12", "i422") for s in sources)):
+        sys.exit("--mapped needs --range limited and takes --source i420, nv12, i422")
     if a.restart is not None:
         if a.scan != "interleaved":
             sys.exit("--restart needs --scan interleaved")
         if a.restart != "row" and not (a.restart.isdigit() and int(a.restart) <= 65535):
             sys.exit("--restart takes a number of MCUs, 0 .. 65535, or `row`")
+    if a.layout is not None:
+        run_layout(a, jpegamd, torch, dev)
+        return
     if a.batch is not None or sources != ["rgb"] or a.scan == "interleaved":
         run_batch(a, jpegamd, torch, dev, sources)
         return
@@ -248,9 +255,19 @@ def run_batch(a, jpegamd, torch, dev, sources=("rgb",)) -> None:
     limited = a.sample_range == "limited"
     bt709 = a.matrix == "bt709"
     lut_y = lut_c = None
-    if a.convert and limited:
+    if (a.convert or a.mapped) and limited:
         lut_y = torch.tensor([(255 * (min(max(v, 16), 235) - 16) + 109) // 219 for v in range(256)], dtype=torch.uint8, device=dev)
         lut_c = torch.tensor([(255 * (min(max(v, 16), 240) - 16) + 112) // 224 for v in range(256)], dtype=torch.uint8, device=dev)
+    if a.mapped:                                                 # the frames as the range map leaves them, coded at full range from here on
+        if frames is not None:
+            for i in range(n):                                   # (picture by picture: the index tensors of a lookup are eight times the plane)
+                frames[i, :h] = lut_y[frames[i, :h].long()]
+                frames[i, h:] = lut_c[frames[i, h:].long()]
+                cbs[i], crs[i] = lut_c[cbs[i].long()], lut_c[crs[i].long()]
+        if packed is not None:
+            for i in range(n):
+                ys2[i], cbs2[i], crs2[i] = lut_y[ys2[i].long()], lut_c[cbs2[i].long()], lut_c[crs2[i].long()]
+        limited = False
     for source, sub, name, tensors, describe in runs:
         ycc = describe(tensors) if describe else None
         one_scan = a.scan == "interleaved"
@@ -263,7 +280,12 @@ def run_batch(a, jpegamd, torch, dev, sources=("rgb",)) -> None:
         sizes = torch.zeros(n, dtype=torch.int64, device=dev)
         out_ptrs = [o.data_ptr() for o in outs]
         size_ptrs = [sizes.data_ptr() + 8 * i for i in range(n)]
-        if restart is not None and ycc is None:
+        if one_scan and ycc is not None and (limited or bt709 or source in ("yuyv", "p010", "i010")):     # a kind the older one-scan entries refuse
+            fmt = {"p010": jpegamd.SAMPLES_10_MSB, "i010": jpegamd.SAMPLES_10_LSB}.get(source, jpegamd.SAMPLES_8)
+            call = lambda: enc.encode_ycbcr_interleaved_matrix_batch_async(
+                ycc, sub, jpegamd.RANGE_LIMITED if limited else jpegamd.RANGE_FULL, fmt, jpegamd.MATRIX_BT709 if bt709 else jpegamd.MATRIX_BT601,
+                restart or 0, out_ptrs, cap, size_ptrs, stream)
+        elif restart is not None and ycc is None:
             call = lambda: enc.encode_color_interleaved_restart_batch_async(descs, sub, restart, out_ptrs, cap, size_ptrs, stream)
         elif restart is not None:
             call = lambda: enc.encode_ycbcr_interleaved_restart_batch_async(ycc, sub, restart, out_ptrs, cap, size_ptrs, stream)
@@ -300,6 +322,8 @@ def run_batch(a, jpegamd, torch, dev, sources=("rgb",)) -> None:
             line["restart_interval"] = restart
         if limited:
             line["range"] = "limited"
+        if a.mapped:
+            line["range"] = "limited, mapped outside the timed loop"
         if bt709 and ycc is not None:
             line["matrix"] = "bt709"
             line["pass_bytes_per_picture"] = pass_bytes(w, h, sub, jpegamd, 2 if source in ("p010", "i010") else 1)
@@ -499,7 +523,11 @@ def run_layout(a, jpegamd, torch, dev) -> None:
         del hwc
     enc = jpegamd.Encoder(w, n * h)
     stream = torch.cuda.current_stream().cuda_stream
-    cap = jpegamd.max_jfif_bytes_color(w, h, sub)
+    one_scan = a.scan == "interleaved"
+    restart = 0
+    if a.restart is not None:
+        restart = -(-w // 16) if a.restart == "row" else int(a.restart)
+    cap = jpegamd.max_jfif_bytes_interleaved_restart(w, h, sub, restart) if one_scan else jpegamd.max_jfif_bytes_color(w, h, sub)
     outs = [torch.empty(cap, dtype=torch.uint8, device=dev) for _ in range(n)]
     sizes = torch.zeros(n, dtype=torch.int64, device=dev)
     out_ptrs = [o.data_ptr() for o in outs]
@@ -510,11 +538,19 @@ def run_layout(a, jpegamd, torch, dev) -> None:
 
     if a.layout == "chw":
         planar = [jpegamd.Encoder.planar_image(tuple(src[i, k].data_ptr() for k in range(3)), w, h, w, False, a.quality) for i in range(n)]
-        direct = lambda: enc.encode_planar_batch_async(planar, sub, out_ptrs, cap, size_ptrs, stream)
+        if one_scan:
+            direct = lambda: enc.encode_planar_interleaved_batch_async(planar, sub, restart, out_ptrs, cap, size_ptrs, stream)
+        else:
+            direct = lambda: enc.encode_planar_batch_async(planar, sub, out_ptrs, cap, size_ptrs, stream)
     else:
         descs = packed_descs(src, jpegamd.ORDER_RGBA if a.layout == "rgba" else jpegamd.ORDER_RGB, 4 if a.layout == "rgba" else 3)
-        direct = lambda: enc.encode_color_batch_async(descs, sub, out_ptrs, cap, size_ptrs, stream)
+        if one_scan:
+            direct = lambda: enc.encode_color_interleaved_pixels_batch_async(descs, sub, restart, out_ptrs, cap, size_ptrs, stream)
+        else:
+            direct = lambda: enc.encode_color_batch_async(descs, sub, out_ptrs, cap, size_ptrs, stream)
     routes = {"direct": direct}
+    if a.repack and one_scan:
+        sys.exit("--repack times a route of the three-scan path: not with --scan interleaved")
     if a.repack:
         if a.layout != "chw":
             sys.exit("--repack needs --layout chw")
@@ -547,7 +583,8 @@ def run_layout(a, jpegamd, torch, dev) -> None:
         print(json.dumps({"layout": a.layout, "route": k, "width": w, "height": h, "batch": n, "quality": a.quality, "kind": a.kind,
                           "steps": a.steps, "rounds": a.rounds, "bytes": got[k], "us_per_picture_medians": [round(v, 1) for v in m],
                           "us_per_picture": round(statistics.median(m), 1), "spread_us": round(max(m) - min(m), 1),
-                          "gpixels_per_s": round(w * h / statistics.median(m) / 1000, 2)}))
+                          "gpixels_per_s": round(w * h / statistics.median(m) / 1000, 2),
+                          **({"scan": "interleaved", "restart_interval": restart} if one_scan else {})}))
 
 
 if __name__ == "__main__":
