@@ -422,6 +422,49 @@ int32_t jpegamd_encode_planar_interleaved_batch_async(JpegAmdEncoder *enc, const
 #define JPEGAMD_PIPELINE_STITCH 2
 int32_t jpegamd_encoder_set_pipeline(JpegAmdEncoder *enc, int32_t pipeline);
 
+/* The Huffman tables of the ONE-SCAN colour files: the entries named *_interleaved_* above and below.
+ *   STANDARD   (default) the Annex K tables: every entry launches what it launched and writes the bytes it wrote;
+ *   OPTIMIZED  four tables made for each picture from its own symbol counts, as libjpeg -optimize / PIL optimize=True make them.
+ * Takes effect with the next encode on the context; any other value, or a null context: JPEGAMD_ERR_ARG.
+ * The OPTIMIZED file equals the STANDARD one-scan file of the same input and restart interval except for the four DHT segments and
+ * the code words of the scan: coefficients, MCU order, pad blocks, DC predictors and their reset per interval, 1-bit padding,
+ * stuffing, RSTn, flush, EOI, every byte in front of the first DHT, the DRI segment and the SOS are unchanged.
+ *   Counts.  Four tables per picture: luma DC (Tc/Th 0/0) from the DC size symbols of the Y blocks, luma AC (1/0) from their AC
+ *     run/size symbols, chroma DC (0/1) and chroma AC (1/1) from those of the Cb and Cr blocks together.  Every symbol the scan codes
+ *     with the call's restart interval counts: a pad block's DC symbol and its EOB, every ZRL, every EOB, and the DC differences
+ *     taken against a predictor of 0 at each interval's start -- the counts depend on the interval.
+ *   Tables.  T.81 K.2 as libjpeg carries it out, for counts f[0..255]:
+ *     1. f[256] = 1 (a reserved point: no code word is all ones); every index with f > 0 is a tree of one symbol, size[s] = 0;
+ *     2. repeat: c1 = the tree root with the least f > 0, the highest index among equals; c2 = the same among the other roots; stop
+ *        when there is none; f[c1] += f[c2], f[c2] = 0, size[s] += 1 for every symbol of both trees, whose root becomes c1;
+ *     3. n[l] = the symbols with size == l, the reserved one included (l may reach 256);
+ *     4. for l from the largest used length down to 17, while n[l] > 0: j = l - 2; while n[j] == 0, j -= 1;
+ *        n[l] -= 2, n[l-1] += 1, n[j+1] += 2, n[j] -= 1;
+ *     5. l = the largest length with n[l] > 0: n[l] -= 1 (the reserved point leaves);
+ *     6. BITS[l] = n[l], l = 1 .. 16; HUFFVAL = the real symbols with f > 0 ordered by (size of step 2, symbol value); the code words
+ *        are the canonical ones of T.81 Annex C -- a symbol's final length follows from its place in HUFFVAL against BITS.
+ *     A table with one used symbol gives it the 1-bit code 0.
+ *   DHT.  Four segments where the standard four stand, in their order (Tc/Th 00, 10, 01, 11): FF C4, length 19 + nvals, the Tc/Th
+ *     byte, 16 BITS bytes, HUFFVAL.  The prefix's length differs from picture to picture of a batch and never exceeds the standard one's.
+ * Capacity behaviour, status, profiling (ns_total only) and context sizing are those of the STANDARD call; entropy_bits is the sum of
+ * the bits actually coded, stuffed_bytes and exact_fallbacks keep their meaning.  jpegamd_max_jfif_bytes_interleaved and
+ * jpegamd_max_jfif_bytes_interleaved_restart remain upper bounds: an optimised DC symbol is at most 16 + 11 bits and an AC symbol
+ * 16 + 10 (an AC coefficient of 8-bit samples is below 1024 in magnitude for this quantiser as for T.81), 27 + 63 x 26 bits a block --
+ * below the 22 + 63 x 27 the bounds and the path's reservations are made of.  The scratch of the mode -- per picture 4.3 KB of
+ * counters, 2.2 KB of coder tables, one prefix slot -- is allocated with the path's scratch on the context's first OPTIMIZED call.
+ * No effect on the grayscale, three-scan, row-sharded, DTO and file entries, whose coder is inside the tile kernel: optimised tables
+ * for those are a follow-up. */
+#define JPEGAMD_HUFFMAN_STANDARD  0
+#define JPEGAMD_HUFFMAN_OPTIMIZED 1
+int32_t jpegamd_encoder_set_huffman(JpegAmdEncoder *enc, int32_t huffman);
+/* Tests.  Both synchronous, host pointers; bad arguments are refused with JPEGAMD_ERR_ARG before the device is touched.
+ * jpegamd_debug_optimal_huffman: the device's table builder on `n` (1 .. 4096) arbitrary tables of 256 counts, each table's counts
+ * summing to less than 2^54 -> BITS [n][16], HUFFVAL [n][256] (zeros behind the used ones), the number of HUFFVAL bytes [n].
+ * jpegamd_debug_huffman_counts: the symbol counts of the context's last OPTIMIZED call, [pictures of that call][4][256] in the table
+ * order above (a DC table's at 0 .. 15); JPEGAMD_ERR_ARG when the context made no such call. */
+int32_t jpegamd_debug_optimal_huffman(JpegAmdEncoder *enc, const uint64_t *freq, int32_t n, uint8_t *bits, uint8_t *vals, int32_t *nvals);
+int32_t jpegamd_debug_huffman_counts(JpegAmdEncoder *enc, uint64_t *counts);
+
 /* Block until the last enqueued encode on this context finished; optionally fetch stats
  * (stats may be NULL).  Returns JPEGAMD_ERR_HUFF_CAPACITY if the output did not fit. */
 int32_t jpegamd_encoder_finish(JpegAmdEncoder *enc, JpegAmdStats *stats);

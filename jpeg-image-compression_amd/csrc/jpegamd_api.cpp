@@ -61,6 +61,7 @@ struct JpegAmdEncoder {
     uint32_t *desc = nullptr;           // k_stitch's hand-off granules: max_wgs x 16 bytes, then max_wgs x 8 counts in full
     uint32_t epoch = 0;                 // 1 .. 16383: tag of the last k_stitch launch's granules
     int pipeline = JPEGAMD_PIPELINE_AUTO;
+    int huffman = JPEGAMD_HUFFMAN_STANDARD;     // jpegamd_encoder_set_huffman: the tables of the one-scan entries
     int poison_tile = -1;               // jpegamd_debug_poison_tile_record: the next encode overwrites this tile's record word 0 ...
     uint32_t poison_value = 0;          // ... with this value, between k_tile_encode and k_segment_merge
     unsigned long long *stamps_dev = nullptr;   // per-wave phase cycle sums of the stamped kernel (allocated by the first convertToJpeg, or with JPEGAMD_STAMPS=1)
@@ -118,6 +119,14 @@ struct JpegAmdEncoder {
         uint8_t *hdr = nullptr;             // the prefix with the three-component SOS
         ScanStats *scan_stats = nullptr;    // k_finalize's record of the call
         HeaderCache hdr_for = {};           // what `hdr` holds
+        // per-picture optimised Huffman tables (jpegamd_encoder_set_huffman): nothing of this is allocated before the first such call
+        unsigned long long *hcounts = nullptr;   // [hcap][2][272] the symbol counts (k_mcu_histogram)
+        uint32_t *htabs = nullptr;          // [hcap][2][272] the coder's tables (k_huff_optimal)
+        uint8_t *hprefix = nullptr;         // [hcap][kMcuPrefixSlot] the pictures' prefixes
+        uint32_t *hprefix_len = nullptr;    // [hcap]
+        uint8_t *hres = nullptr;            // [4 hcap][kHuffResBytes] BITS / HUFFVAL as k_huff_optimal leaves them
+        int hcap = 0;                       // pictures
+        int hlast = 0;                      // pictures of the last optimised call: hcounts[0, hlast) are theirs
     } mcu;
 };
 
@@ -351,6 +360,7 @@ extern "C" int32_t jpegamd_encoder_destroy(JpegAmdEncoder *e) {
     hipFree(e->color.bmeta); hipFree(e->color.bplanes); hipFree(e->color.bscans);
     hipFree(e->mcu.coef); hipFree(e->mcu.hdr); hipFree(e->mcu.scan_stats);
     hipFree(e->mcu.rst_words); hipFree(e->mcu.rst_pos); hipFree(e->mcu.rst_pic_sums);
+    hipFree(e->mcu.hcounts); hipFree(e->mcu.htabs); hipFree(e->mcu.hprefix); hipFree(e->mcu.hprefix_len); hipFree(e->mcu.hres);
     free_seg_arrays(&e->mcu.seg);
     destroy_ring_events(e);
     delete e->tables_host;
@@ -361,6 +371,12 @@ extern "C" int32_t jpegamd_encoder_destroy(JpegAmdEncoder *e) {
 extern "C" int32_t jpegamd_encoder_set_pipeline(JpegAmdEncoder *e, int32_t pipeline) {
     if (!e || pipeline < JPEGAMD_PIPELINE_AUTO || pipeline > JPEGAMD_PIPELINE_STITCH) return JPEGAMD_ERR_ARG;
     e->pipeline = pipeline;
+    return JPEGAMD_OK;
+}
+
+extern "C" int32_t jpegamd_encoder_set_huffman(JpegAmdEncoder *e, int32_t huffman) {
+    if (!e || (huffman != JPEGAMD_HUFFMAN_STANDARD && huffman != JPEGAMD_HUFFMAN_OPTIMIZED)) return JPEGAMD_ERR_ARG;
+    e->huffman = huffman;
     return JPEGAMD_OK;
 }
 
@@ -1505,6 +1521,9 @@ extern "C" int32_t jpegamd_encode_ycbcr_batch_async(JpegAmdEncoder *e, const Jpe
 // codes the planes in MCU order into the path's OWN segment arrays, the unchanged k_finalize writes prefix, scan and EOI straight
 // into the caller's buffers, k_mcu_totals sums the call's record.  A large batch goes through in groups of pictures that bound the
 // scratch.  jpegamd_encoder_set_pipeline has no effect here: k_stitch reads tile records.
+// With JPEGAMD_HUFFMAN_OPTIMIZED on the context k_mcu_histogram and k_huff_optimal run in front of k_mcu_segments,
+// which then codes every picture with its own tables, and the restart writer stands in for k_finalize at every interval: it reads a
+// prefix and its length per picture.
 // ---------------------------------------------------------------------------------------------------------
 struct McuGeometry {
     int hs, vs, bw, bh, mx, my, seg_mcus, num_segs, num_segs_pad;
@@ -1539,9 +1558,10 @@ static McuGeometry mcu_geometry(int w, int h, int sub, int restart = 0) {
 }
 // Bytes of the path's scratch one picture takes in the group budget: its coefficient planes and its segment strings; with restart
 // intervals -- segments may be as short as one MCU -- the per-segment numbers as well, the coder's and the writer's (56 bytes).
-static uint64_t mcu_scratch_per_pic(const McuGeometry &g) {
+// `writer`: the call goes through k_mcu_restart_offsets / k_mcu_restart_write (restart intervals, or a picture's own tables).
+static uint64_t mcu_scratch_per_pic(const McuGeometry &g, bool writer) {
     const uint64_t segs = (uint64_t)(g.segs64 + kSegGroup - 1) / kSegGroup * kSegGroup;
-    return (uint64_t)g.coef_per_pic * sizeof(int16_t) + segs * (uint64_t)g.cap_words * sizeof(uint32_t) + (g.restart ? segs * 56u : 0u);
+    return (uint64_t)g.coef_per_pic * sizeof(int16_t) + segs * (uint64_t)g.cap_words * sizeof(uint32_t) + (writer ? segs * 56u : 0u);
 }
 
 extern "C" uint64_t jpegamd_max_jfif_bytes_interleaved(int32_t width, int32_t height, int32_t subsampling) {
@@ -1568,7 +1588,8 @@ constexpr int kMcuSosBytes = 14;
 constexpr size_t kMcuScratchBudget = (size_t)4 << 30;       // coefficient planes + segment strings of one group of pictures
 
 // The path's scratch for `group` pictures of geometry g: allocated on the first call, grown when a call needs more.
-static int32_t mcu_alloc(JpegAmdEncoder *e, const McuGeometry &g, int group) {
+// `writer`: the restart writer's arrays as well.  `own_tables`: the scratch of `own_tables` pictures with tables of their own.
+static int32_t mcu_alloc(JpegAmdEncoder *e, const McuGeometry &g, int group, bool writer, int own_tables) {
     auto &m = e->mcu;
     if (!m.hdr) {
         HIP_TRY(hipMalloc((void **)&m.hdr, 1024));
@@ -1585,7 +1606,19 @@ static int32_t mcu_alloc(JpegAmdEncoder *e, const McuGeometry &g, int group) {
         if (int32_t rc = alloc_seg_arrays(&m.seg, new_segs, new_words, false)) return rc;
         m.segs_cap = new_segs; m.words_cap = new_words;
     }
-    if (g.restart && segs > m.rst_cap) {
+    if (own_tables > m.hcap) {
+        if (int32_t rc = wait_pending(e)) return rc;
+        hipFree(m.hcounts); hipFree(m.htabs); hipFree(m.hprefix); hipFree(m.hprefix_len); hipFree(m.hres);
+        m.hcounts = nullptr; m.htabs = nullptr; m.hprefix = nullptr; m.hprefix_len = nullptr; m.hres = nullptr; m.hcap = 0; m.hlast = 0;
+        const size_t n = (size_t)own_tables;
+        HIP_TRY(hipMalloc((void **)&m.hcounts, n * kMcuTabWords * sizeof(unsigned long long)));
+        HIP_TRY(hipMalloc((void **)&m.htabs, n * kMcuTabWords * sizeof(uint32_t)));
+        HIP_TRY(hipMalloc((void **)&m.hprefix, n * kMcuPrefixSlot));
+        HIP_TRY(hipMalloc((void **)&m.hprefix_len, n * sizeof(uint32_t)));
+        HIP_TRY(hipMalloc((void **)&m.hres, 4 * n * kHuffResBytes));
+        m.hcap = own_tables;
+    }
+    if (writer && segs > m.rst_cap) {
         if (int32_t rc = wait_pending(e)) return rc;
         hipFree(m.rst_words); hipFree(m.rst_pos); m.rst_words = nullptr; m.rst_pos = nullptr; m.rst_cap = 0;
         if (!m.rst_pic_sums) HIP_TRY(hipMalloc((void **)&m.rst_pic_sums, kMaxBatch * kMcuPicSums * sizeof(unsigned long long)));
@@ -1632,8 +1665,11 @@ static int32_t interleaved_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, cons
     const YccSource *const ycc = mx ? nullptr : ycc_in;               // what the launches read: the caller's planes, or the scratch
     const bool planar = g0.channel_order == kOrderPlanar;
     const McuGeometry g = mcu_geometry(g0.width, g0.height, subsampling, restart);
+    // A picture's own tables: k_mcu_histogram and k_huff_optimal in front of the coder, and the restart writer for
+    // every interval -- it reads a prefix and its length per picture; without restart intervals the scan is its one interval.
+    const bool optimized = e->huffman == JPEGAMD_HUFFMAN_OPTIMIZED, writer = restart || optimized;
     // segments as short as one MCU: a picture whose scratch alone is beyond the group budget is refused, nothing allocated or launched
-    if (restart && mcu_scratch_per_pic(g) > kMcuScratchBudget) return JPEGAMD_ERR_TOO_LARGE;
+    if (restart && mcu_scratch_per_pic(g, true) > kMcuScratchBudget) return JPEGAMD_ERR_TOO_LARGE;
     // every launch codes ONE picture's component: the Y plane and a chroma plane must fit the context
     const MatrixScratch ms = matrix_scratch(g0.width, g0.height, count, g.chroma.plane_bytes);
     JpegAmdImage gy = g0;                                            // the Y launches' picture: a BT.709 batch reads the scratch Y planes
@@ -1650,13 +1686,13 @@ static int32_t interleaved_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, cons
     if (rc) return rc;
     if (iy.blocks_w != g.bw || iy.blocks_h != g.bh || ic.blocks_w != g.mx || ic.blocks_h != g.my) return JPEGAMD_ERR_ARG;
 
-    const size_t per_pic = (size_t)mcu_scratch_per_pic(g);
+    const size_t per_pic = (size_t)mcu_scratch_per_pic(g, writer);
     const int group = (int)std::max<size_t>(1, std::min<size_t>((size_t)count, kMcuScratchBudget / per_pic));
     rc = color_alloc_consts(e);
     if (rc) return rc;
     rc = color_batch_alloc(e, mx ? ms.total : (ycc ? 0 : 2 * (size_t)count * cg.plane_bytes + 256), 0);
     if (rc) return rc;
-    rc = mcu_alloc(e, g, group);
+    rc = mcu_alloc(e, g, group, writer, optimized ? count : 0);
     if (rc) return rc;
     rc = prepare_constants(e, &g0, false);
     if (rc) return rc;
@@ -1720,9 +1756,25 @@ static int32_t interleaved_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, cons
         sa.seg.words_stride = (uint32_t)g.cap_words;
         sa.status = &m.scan_stats->status;
         sa.restart = restart; sa.segs_per_interval = restart ? g.segs_per_interval : 0;
+        if (optimized) {                                             // the group's pictures are [first, first + n) of the call's table scratch
+            unsigned long long *counts = m.hcounts + (size_t)first * kMcuTabWords;
+            HIP_TRY(hipMemsetAsync(counts, 0, (size_t)n * kMcuTabWords * sizeof(unsigned long long), stream));
+            if (launch_mcu_histogram(sa, counts, stream)) return JPEGAMD_ERR_HIP;
+            HuffOptimalArgs ha;
+            std::memset(&ha, 0, sizeof(ha));
+            ha.counts = counts; ha.jobs = 4 * n;
+            ha.res = m.hres + (size_t)first * 4 * kHuffResBytes;
+            ha.tabs = m.htabs + (size_t)first * kMcuTabWords;
+            ha.prefix = m.hprefix + (size_t)first * kMcuPrefixSlot; ha.prefix_len = m.hprefix_len + first;
+            ha.hdr = m.hdr;                                          // the standard prefix: head, four Annex K DHTs, [DRI,] SOS
+            ha.tail_len = kMcuSosBytes + (restart ? kMcuDriBytes : 0);
+            ha.tail_off = m.hdr_for.len - ha.tail_len; ha.head_len = ha.tail_off - kStdDhtBytes;
+            if (launch_huff_optimal(ha, stream)) return JPEGAMD_ERR_HIP;
+            sa.huff_y = ha.tabs; sa.huff_c = ha.tabs + 272; sa.huff_stride = kMcuTabWords;
+        }
         if (launch_mcu_segments(sa, stream)) return JPEGAMD_ERR_HIP;
 
-        if (restart) {                                               // k_mcu_restart_offsets + k_mcu_restart_write in k_finalize's place
+        if (writer) {                                               // k_mcu_restart_offsets + k_mcu_restart_write in k_finalize's place
             McuRestartArgs ra;
             std::memset(&ra, 0, sizeof(ra));
             ra.seg = sa.seg;
@@ -1733,6 +1785,10 @@ static int32_t interleaved_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, cons
             for (int i = 0; i < n; ++i) { ra.out[i] = (uint8_t *)outs_dev[first + i]; ra.out_size[i] = out_sizes_dev[first + i]; }
             ra.out_capacity = out_capacity;
             ra.prefix = m.hdr; ra.prefix_len = m.hdr_for.len;
+            if (optimized) {
+                ra.pic_prefix = m.hprefix + (size_t)first * kMcuPrefixSlot; ra.pic_prefix_len = m.hprefix_len + first;
+                ra.pic_prefix_stride = kMcuPrefixSlot;
+            }
             if (launch_mcu_restart_writer(ra, stream)) return JPEGAMD_ERR_HIP;
         } else {
             ImageDesc is = iy;                                       // what run_finalize reads of it: the segments per picture and their length
@@ -1745,7 +1801,7 @@ static int32_t interleaved_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, cons
         std::memset(&ta, 0, sizeof(ta));
         ta.seg = m.seg;
         ta.num_segs_pad = g.num_segs_pad; ta.prefix_len = m.hdr_for.len;
-        ta.pic_sums = restart ? m.rst_pic_sums : nullptr;
+        ta.pic_sums = writer ? m.rst_pic_sums : nullptr;          // (the writer's sums: prefix_len is not read then)
         ta.last_of_call = first + n == count ? 1 : 0;
         for (int i = 0; i < n; ++i) ta.out_size[i] = out_sizes_dev[first + i];
         ta.out_capacity = out_capacity;
@@ -1753,8 +1809,66 @@ static int32_t interleaved_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, cons
         ta.scan_stats = m.scan_stats; ta.stats = e->stats_dev;
         if (launch_mcu_totals(ta, n, stream)) return JPEGAMD_ERR_HIP;
     }
+    if (optimized) m.hlast = count;
     if (cev) HIP_TRY(hipEventRecord(cev[21], stream));
     return enqueued(e, stream, count * g.num_segs_pad, cev != nullptr, true);
+}
+
+// Tests: k_huff_optimal on arbitrary counts -- `n` tables of 256 counts each (a table's sum below 2^54) -> BITS, HUFFVAL (zeros behind
+// the used ones) and the number of HUFFVAL bytes of each.  Synchronous, host pointers.
+extern "C" int32_t jpegamd_debug_optimal_huffman(JpegAmdEncoder *e, const uint64_t *freq, int32_t n, uint8_t *bits, uint8_t *vals, int32_t *nvals) {
+    if (!e || !freq || !bits || !vals || !nvals || n < 1 || n > 4096) return JPEGAMD_ERR_ARG;
+    for (int t = 0; t < n; ++t) {
+        uint64_t sum = 0;
+        for (int i = 0; i < 256; ++i) {
+            if (freq[(size_t)t * 256 + i] >> 54) return JPEGAMD_ERR_ARG;
+            sum += freq[(size_t)t * 256 + i];
+        }
+        if (sum >> 54) return JPEGAMD_ERR_ARG;
+    }
+    if (int32_t rc = wait_pending(e)) return rc;
+    unsigned long long *f_dev = nullptr;
+    uint8_t *r_dev = nullptr;
+    const size_t fbytes = (size_t)n * 256 * sizeof(uint64_t), rbytes = (size_t)n * kHuffResBytes;
+    std::vector<uint8_t> res(rbytes);
+    int32_t rc = JPEGAMD_OK;
+    HuffOptimalArgs ha;
+    std::memset(&ha, 0, sizeof(ha));
+    if (hipMalloc((void **)&f_dev, fbytes) != hipSuccess || hipMalloc((void **)&r_dev, rbytes) != hipSuccess) rc = JPEGAMD_ERR_HIP;
+    if (!rc && hipMemcpy(f_dev, freq, fbytes, hipMemcpyHostToDevice) != hipSuccess) rc = JPEGAMD_ERR_HIP;
+    ha.freq = f_dev; ha.jobs = n; ha.res = r_dev;
+    if (!rc && launch_huff_optimal(ha, nullptr)) rc = JPEGAMD_ERR_HIP;
+    if (!rc && hipMemcpy(res.data(), r_dev, rbytes, hipMemcpyDeviceToHost) != hipSuccess) rc = JPEGAMD_ERR_HIP;
+    hipFree(f_dev); hipFree(r_dev);
+    if (rc) return rc;
+    for (int t = 0; t < n; ++t) {
+        const uint8_t *r = res.data() + (size_t)t * kHuffResBytes;
+        std::memcpy(bits + (size_t)t * 16, r, 16);
+        uint32_t nv;
+        std::memcpy(&nv, r + 16, sizeof(nv));
+        nvals[t] = (int32_t)nv;
+        std::memcpy(vals + (size_t)t * 256, r + 32, 256);
+    }
+    return JPEGAMD_OK;
+}
+
+// Tests: the symbol counts of the context's last call with optimised tables, [pictures][4][256] in the order luma DC, luma AC,
+// chroma DC, chroma AC (a DC table's counts at 0 .. 15).  JPEGAMD_ERR_ARG when the context made no such call.  Synchronous.
+extern "C" int32_t jpegamd_debug_huffman_counts(JpegAmdEncoder *e, uint64_t *counts) {
+    if (!e || !counts || e->mcu.hlast < 1) return JPEGAMD_ERR_ARG;
+    if (int32_t rc = wait_pending(e)) return rc;
+    const int n = e->mcu.hlast;
+    std::vector<unsigned long long> dev((size_t)n * kMcuTabWords);
+    HIP_TRY(hipMemcpy(dev.data(), e->mcu.hcounts, dev.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    std::memset(counts, 0, (size_t)n * 4 * 256 * sizeof(uint64_t));
+    for (int q = 0; q < n; ++q)
+        for (int cls = 0; cls < 2; ++cls) {
+            const unsigned long long *src = dev.data() + (size_t)q * kMcuTabWords + (size_t)cls * 272;
+            uint64_t *dst = counts + ((size_t)q * 4 + 2 * cls) * 256;
+            for (int i = 0; i < 16; ++i) dst[i] = src[256 + i];
+            for (int i = 0; i < 256; ++i) dst[256 + i] = src[i];
+        }
+    return JPEGAMD_OK;
 }
 
 static bool restart_valid(int32_t restart) { return restart >= 0 && restart <= 65535; }

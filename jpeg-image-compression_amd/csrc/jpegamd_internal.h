@@ -406,6 +406,7 @@ struct McuSegArgs {
     int32_t bw, bh, mx, my, hs, vs;
     int32_t seg_mcus, num_segs, num_segs_pad, batch;
     const uint32_t *huff_y, *huff_c;    // [272] (len << 16) | code: AC by run/size symbol, then 16 DC sizes
+    uint32_t huff_stride;               // words from a picture's tables to the next picture's (k_huff_optimal's); 0: every picture codes with the same (Annex K)
     SegArrays seg;                      // the interleaved path's own (words_stride = seg_cap_words(kSegTiles), or mcu_restart_cap_words); no group aggregates
     uint32_t *status;                   // ScanStats::status: bit 1 = a count that did not fit its 16 bits
     int32_t restart, segs_per_interval; // 0, 0: no restart intervals
@@ -431,6 +432,11 @@ struct McuRestartArgs {
     uint64_t *out_size[kMaxBatch];
     const uint8_t *prefix;
     int32_t prefix_len;
+    // per-picture prefixes (optimised Huffman tables: k_huff_optimal wrote them): picture q's is pic_prefix + q pic_prefix_stride,
+    // pic_prefix_len[q] bytes, read from device memory; null: `prefix` / `prefix_len` for every picture
+    const uint8_t *pic_prefix;
+    const uint32_t *pic_prefix_len;
+    uint32_t pic_prefix_stride;
 };
 int launch_mcu_restart_writer(const McuRestartArgs &a, void *stream);
 // k_mcu_totals, behind k_finalize: per picture of the launch the sums of its segments, its stuffed bytes (from its size) and its
@@ -449,6 +455,34 @@ struct McuTotalsArgs {
     ScanStats *stats;
 };
 int launch_mcu_totals(const McuTotalsArgs &a, int batch, void *stream, void *const *ev = nullptr);
+
+// Per-picture optimised Huffman tables of the one-scan files.  k_mcu_histogram: the coder's grid and block walk
+// (McuSegArgs, no tables read) with every symbol counted instead of coded, into counts [batch][2][272] u64 -- a component class's AC
+// symbols by run/size at 0, its DC sizes at 256, luma first: the layout of the coder's tables -- which the caller zeroed on the stream.
+int launch_mcu_histogram(const McuSegArgs &a, unsigned long long *counts, void *stream);
+// k_huff_optimal, one wave per table and four tables (luma DC, luma AC, chroma DC, chroma AC) per workgroup: T.81 K.2 as libjpeg
+// carries it out.  A table's counts must sum to less than 2^54 (the merge key holds a count and a slot index in 64 bits).
+// Always: res [jobs][kHuffResBytes] -- BITS[16], the number of HUFFVAL bytes (u32 at 16), HUFFVAL at 32.
+// With `freq` (jpegamd_debug_optimal_huffman): job j reads freq + 256 j, 256 symbols, and nothing else is written.
+// Without: job 4 q + t reads picture q's counts, and the workgroup writes the picture's coder tables (tabs + q kMcuTabWords: [2][272],
+// unused symbols 0), its prefix (prefix + q kMcuPrefixSlot: hdr[0, head_len), the four DHT segments, hdr[tail_off, tail_off + tail_len))
+// and the prefix's length (prefix_len[q]).
+constexpr int kMcuTabWords = 2 * 272;
+constexpr int kMcuPrefixSlot = 704;     // >= kColorPrefixMax + DRI + SOS: an optimised prefix is never longer than the standard one
+constexpr int kHuffResBytes = 288;
+constexpr int kStdDhtBytes = 432;       // the four Annex K DHT segments: 2 x (33 + 183)
+struct HuffOptimalArgs {
+    const unsigned long long *counts;   // [pictures][2][272], or null
+    const unsigned long long *freq;     // [jobs][256], or null
+    int32_t jobs;
+    uint8_t *res;
+    uint32_t *tabs;
+    uint8_t *prefix;
+    uint32_t *prefix_len;
+    const uint8_t *hdr;
+    int32_t head_len, tail_off, tail_len;
+};
+int launch_huff_optimal(const HuffOptimalArgs &a, void *stream);
 
 // ---- host-side constant derivation (quant_consts.cpp) ----------------------------------
 void quant_table_for_quality(int quality, uint8_t table[64]);

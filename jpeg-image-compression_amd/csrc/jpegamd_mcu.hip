@@ -17,6 +17,9 @@
 // With restart intervals a segment is a run of MCUs of ONE interval, the predictors are 0 at the interval's first
 // MCU, and k_mcu_restart_offsets + k_mcu_restart_write stand in for k_finalize: per-interval padding with 1-bits, stuffing, RSTn.
 // k_mcu_totals: the per-call record (sums over the batch) and each picture's size word (0 when the file did not fit).
+// Per-picture optimised Huffman tables: k_mcu_histogram walks the coder's segments and counts every symbol,
+// k_huff_optimal makes each picture's four tables (T.81 K.2 as libjpeg carries it out), its coder tables and its prefix with its own
+// DHT segments; k_mcu_segments then codes with the picture's tables and the restart writer places the picture's prefix.
 #include <algorithm>
 
 #include <hip/hip_ext.h>
@@ -100,25 +103,40 @@ __device__ __forceinline__ McuBlock mcu_block(const McuSegArgs &a, const int16_t
 
 // kRestart: the segments are cut per restart interval (McuSegArgs::restart > 0) and the predictors restart with it; the plain
 // scan is the instantiation it always was.
+// Segment sl of a picture: its first MCU, the first MCU of its interval (of the scan), its MCUs -- none: an EMPTY segment that rounds
+// the picture's count up, or lies behind the last MCU of the last interval.
+struct McuRange { int m0, mstart, nmcu; };
+template <bool kRestart>
+__device__ __forceinline__ McuRange mcu_range(const McuSegArgs &a, int sl) {
+    McuRange r = {sl * a.seg_mcus, 0, 0};
+    r.nmcu = min(a.seg_mcus, a.mx * a.my - r.m0);
+    if (kRestart) {                                                // segment (iv, k): the k-th run of seg_mcus MCUs of interval iv
+        const int iv = sl / a.segs_per_interval, k = sl - iv * a.segs_per_interval;
+        r.mstart = iv * a.restart;
+        r.m0 = r.mstart + k * a.seg_mcus;
+        r.nmcu = min(min(a.seg_mcus, a.restart - k * a.seg_mcus), a.mx * a.my - r.m0);
+    }
+    if (sl >= a.num_segs || r.nmcu < 0) r.nmcu = 0;
+    return r;
+}
+
 template <bool kRestart>
 __global__ __launch_bounds__(64 * kWavesM) void k_mcu_segments(const McuSegArgs a) {
     __shared__ uint32_t s_tab[2][272];
     __shared__ uint32_t s_win[kWavesM][kMcuWin + 2];
     const int lane = lane_id(), wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    for (int i = (int)threadIdx.x; i < 2 * 272; i += 64 * kWavesM) s_tab[i / 272][i % 272] = (i < 272 ? a.huff_y : a.huff_c)[i % 272];
+    {   // the tables of the workgroup's picture (its four segments are one picture's: num_segs_pad is a multiple of kWavesM)
+        const size_t toff = a.huff_stride ? (size_t)(((int)blockIdx.x * kWavesM) / a.num_segs_pad) * a.huff_stride : 0;
+        for (int i = (int)threadIdx.x; i < 2 * 272; i += 64 * kWavesM) s_tab[i / 272][i % 272] = ((i < 272 ? a.huff_y : a.huff_c) + toff)[i % 272];
+    }
     __syncthreads();                                               // (the only workgroup-wide meeting: every wave is on its own below)
     const int seg = (int)blockIdx.x * kWavesM + wave;
     if (seg >= a.batch * a.num_segs_pad) return;
     const int image = seg / a.num_segs_pad, sl = seg - image * a.num_segs_pad;
     uint16_t *const ffin = a.seg.ffin + (size_t)seg * 8;
-    int m0 = sl * a.seg_mcus, mstart = 0, nmcu = min(a.seg_mcus, a.mx * a.my - m0);
-    if (kRestart) {                                                // segment (iv, k): the k-th run of seg_mcus MCUs of interval iv
-        const int iv = sl / a.segs_per_interval, k = sl - iv * a.segs_per_interval;
-        mstart = iv * a.restart;
-        m0 = mstart + k * a.seg_mcus;
-        nmcu = min(min(a.seg_mcus, a.restart - k * a.seg_mcus), a.mx * a.my - m0);
-    }
-    if (sl >= a.num_segs || (kRestart && nmcu <= 0)) {             // an empty segment that rounds the picture's count up (or lies behind the last MCU of the last interval): no bits, no ones at either end
+    const McuRange rg = mcu_range<kRestart>(a, sl);
+    const int m0 = rg.m0, mstart = rg.mstart, nmcu = rg.nmcu;
+    if (nmcu == 0) {                                               // an EMPTY segment: no bits, no ones at either end
         if (lane < 8) ffin[lane] = 0;
         if (lane == 0) { a.seg.bits[seg] = 0u; a.seg.edge[seg] = 0u; a.seg.syms[seg] = 0u; a.seg.exact[seg] = 0u; }
         return;
@@ -205,7 +223,10 @@ __global__ __launch_bounds__(64 * kWavesM) void k_mcu_segments(const McuSegArgs 
         const uint32_t p = seg_bits & 31u;
         const uint32_t tail = p ? ((tail_last << p) | (tail_part >> (32u - p))) : tail_last;
         if (lane == 0) {
-            a.seg.edge[seg] = ((first_word >> 24) << 8) | (tail & 0x7Fu);   // first 8 bits | last 7 bits (a segment is never shorter than 14 bits)
+            // first 8 bits | last 7 bits.  With the Annex K tables a segment is never shorter than 14 bits; with a picture's own
+            // tables an interval's (the scan's) last segment may be as short as 6: its bits then stand at the left of the 8 and at the
+            // right of the 7, zeros elsewhere (the window's).  The readers that take that into account: mcu_tail7, fin_owned_ff.
+            a.seg.edge[seg] = ((first_word >> 24) << 8) | (tail & 0x7Fu);
             a.seg.bits[seg] = seg_bits;
             a.seg.syms[seg] = seg_syms;
             a.seg.exact[seg] = 0u;                                  // (the exact-order fallbacks are counted from the tile records: k_picture_stats)
@@ -223,24 +244,283 @@ __global__ __launch_bounds__(64 * kWavesM) void k_mcu_segments(const McuSegArgs 
     }
 }
 
+// What both walks of the coefficients need of their arguments: every MCU lies in a segment, and the widest segment fits its reservation.
+static bool mcu_seg_args_ok(const McuSegArgs &a) {
+    if (a.seg_mcus < 1 || a.seg_mcus * (a.hs * a.vs + 2) > kSegBlocks || a.num_segs_pad % kSegGroup != 0 || a.num_segs > a.num_segs_pad)
+        return false;
+    static_assert(kSegGroup % kWavesM == 0, "a workgroup's segments belong to one picture");
+    const int64_t mcus = (int64_t)a.mx * a.my;
+    if (a.restart == 0) return (int64_t)a.num_segs * a.seg_mcus >= mcus;
+    const int64_t spi = a.segs_per_interval, in_interval = std::min<int64_t>(a.restart, mcus);
+    return !(a.restart < 0 || spi < 1 || spi * a.seg_mcus < in_interval || (int64_t)a.num_segs < (mcus + a.restart - 1) / a.restart * spi ||
+             (int64_t)mcu_restart_cap_words((int)std::min<int64_t>(a.restart, a.seg_mcus) * (a.hs * a.vs + 2)) > (int64_t)a.seg.words_stride);
+}
+
 int launch_mcu_segments(const McuSegArgs &a, void *stream) {
     const int n = a.batch * a.num_segs_pad;
     if (n <= 0) return 0;
-    if (a.seg_mcus < 1 || a.seg_mcus * (a.hs * a.vs + 2) > kSegBlocks || a.num_segs_pad % kSegGroup != 0 || a.num_segs > a.num_segs_pad)
-        return (int)hipErrorInvalidValue;
-    const int64_t mcus = (int64_t)a.mx * a.my;
+    if (!mcu_seg_args_ok(a)) return (int)hipErrorInvalidValue;
     const dim3 grid((unsigned)((n + kWavesM - 1) / kWavesM)), block(64 * kWavesM);
-    if (a.restart == 0) {
-        if ((int64_t)a.num_segs * a.seg_mcus < mcus) return (int)hipErrorInvalidValue;
-        hipLaunchKernelGGL(k_mcu_segments<false>, grid, block, 0, (hipStream_t)stream, a);
-    } else {
-        // every MCU lies in a segment, and the widest segment fits its reservation
-        const int64_t spi = a.segs_per_interval, in_interval = std::min<int64_t>(a.restart, mcus);
-        if (a.restart < 0 || spi < 1 || spi * a.seg_mcus < in_interval || (int64_t)a.num_segs < (mcus + a.restart - 1) / a.restart * spi ||
-            (int64_t)mcu_restart_cap_words((int)std::min<int64_t>(a.restart, a.seg_mcus) * (a.hs * a.vs + 2)) > (int64_t)a.seg.words_stride)
-            return (int)hipErrorInvalidValue;
-        hipLaunchKernelGGL(k_mcu_segments<true>, grid, block, 0, (hipStream_t)stream, a);
+    if (a.restart == 0) hipLaunchKernelGGL(k_mcu_segments<false>, grid, block, 0, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL(k_mcu_segments<true>, grid, block, 0, (hipStream_t)stream, a);
+    return (int)hipGetLastError();
+}
+
+// ---- per-picture optimised Huffman tables ---------------------------------------------------------------------
+// The symbols of one block counted, not coded: mcu_walk_block's walk without a table.  count(i): symbol i of the class's [272] layout
+// (AC run/size at 0, DC size at 256); the two hot symbols -- DC size 0 and EOB -- go to the caller's registers instead.
+template <class Count>
+__device__ __forceinline__ void mcu_count_block(const uint4 *__restrict__ p, bool pad, int pred, uint32_t &dc0, uint32_t &eobs, Count &&count) {
+    uint4 v = p[0];
+    const uint32_t dc = mcu_size((int)(short)(v.x & 0xFFFFu) - pred) & 15u;
+    if (dc) count(256u + dc); else ++dc0;
+    if (pad) { ++eobs; return; }
+    v.x &= 0xFFFF0000u;
+    uint32_t run = 0xFFFFFFFFu;
+#pragma unroll 1
+    for (int q = 0; q < 8; ++q) {
+        if (q) v = p[q];
+        if ((v.x | v.y | v.z | v.w) == 0u) { run += 8u; continue; }
+        const uint32_t w4[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const int c = (int)(short)((w4[i >> 1] >> (16 * (i & 1))) & 0xFFFFu);
+            if (c == 0) { ++run; continue; }
+            while (run >= 16u) { count(0xF0u); run -= 16u; }
+            count(((run << 4) | mcu_size(c)) & 0xFFu);
+            run = 0u;
+        }
     }
+    if (run) ++eobs;
+}
+
+// k_mcu_segments' grid and segments, one wave per segment: the workgroup's counts in LDS, then added to its picture's.
+// Photo-like content codes a handful of symbols nearly all the time, and 64 lanes adding to one LDS address take turns.  So the
+// symbols that are hot go to counters of the lane's own: EOB and DC size 0 to registers, the AC symbols of run 0 .. 3 and size
+// 1 .. 4 and the other DC sizes to a 16-bit column per lane in LDS (a lane walks at most 4 blocks: no count passes 252) -- plain
+// adds, nobody else writes there -- and only the rest to the shared table with atomics.  The columns are summed over the wave at the end.
+constexpr int kHotRows = 28;                    // 16 AC symbols (run << 2 | size - 1), then DC sizes 0 .. 11 at 16 + size
+__device__ __forceinline__ uint32_t mcu_hot_symbol(int row) { return row < 16 ? (uint32_t)(((row >> 2) << 4) | ((row & 3) + 1)) : 256u + (uint32_t)(row - 16); }
+template <bool kRestart>
+__global__ __launch_bounds__(64 * kWavesM) void k_mcu_histogram(const McuSegArgs a, unsigned long long *__restrict__ counts) {
+    __shared__ uint32_t s_cnt[2][272];                             // (a workgroup walks at most 4 x 256 blocks of 64 symbols: 32 bits hold it)
+    __shared__ uint16_t s_hot[kWavesM][2][kHotRows][64];
+    const int lane = lane_id(), wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    for (int i = (int)threadIdx.x; i < 2 * 272; i += 64 * kWavesM) (&s_cnt[0][0])[i] = 0u;
+    for (int i = 0; i < 2 * kHotRows; ++i) (&s_hot[wave][0][0][0])[i * 64 + lane] = 0;
+    __syncthreads();
+    const int seg = (int)blockIdx.x * kWavesM + wave;
+    const int image = ((int)blockIdx.x * kWavesM) / a.num_segs_pad; // the workgroup's picture
+    if (seg < a.batch * a.num_segs_pad) {
+        const McuRange rg = mcu_range<kRestart>(a, seg - image * a.num_segs_pad);
+        const int16_t *base = a.coef + (size_t)image * a.pic_stride;
+        const int bpm = a.hs * a.vs + 2, nblk = rg.nmcu * bpm;      // 0 (EMPTY: nothing counted), 3 .. 256
+        uint32_t dc0_y = 0, dc0_c = 0, eob_y = 0, eob_c = 0;
+#pragma unroll 1
+        for (int r = 0; r < 4; ++r) {
+            const int k = r * 64 + lane;
+            if (k < nblk) {
+                const int mi = k / bpm;
+                const McuBlock b = mcu_block(a, base, rg.m0 + mi, k - mi * bpm, rg.mstart);
+                uint32_t *const cnt = s_cnt[b.chroma ? 1 : 0];
+                uint16_t *const hot = &s_hot[wave][b.chroma ? 1 : 0][0][lane];
+                uint32_t d = 0, e = 0;
+                mcu_count_block(b.p, b.pad, b.pred, d, e, [&](uint32_t i) {
+                    const uint32_t run = (i >> 4) & 15u, size = i & 15u;
+                    if (i >= 256u && size < 12u) hot[(16u + size) * 64u] += 1;                 // a DC size 1 .. 11
+                    else if (i < 256u && run < 4u && size - 1u < 4u) hot[((run << 2) | (size - 1u)) * 64u] += 1;
+                    else atomicAdd(&cnt[i], 1u);
+                });
+                if (b.chroma) { dc0_c += d; eob_c += e; } else { dc0_y += d; eob_y += e; }
+            }
+        }
+        if (nblk) {
+            const uint32_t t0 = (uint32_t)wave_sum_i32((int)dc0_y), t1 = (uint32_t)wave_sum_i32((int)eob_y);
+            const uint32_t t2 = (uint32_t)wave_sum_i32((int)dc0_c), t3 = (uint32_t)wave_sum_i32((int)eob_c);
+            if (lane == 0) {
+                if (t0) atomicAdd(&s_cnt[0][256], t0);
+                if (t1) atomicAdd(&s_cnt[0][0], t1);
+                if (t2) atomicAdd(&s_cnt[1][256], t2);
+                if (t3) atomicAdd(&s_cnt[1][0], t3);
+            }
+#pragma unroll 1
+            for (int i = 0; i < 2 * kHotRows; ++i) {
+                const uint32_t t = (uint32_t)wave_sum_i32((int)(&s_hot[wave][0][0][0])[i * 64 + lane]);
+                if (lane == 0 && t) atomicAdd(&s_cnt[i / kHotRows][mcu_hot_symbol(i % kHotRows)], t);
+            }
+        }
+    }
+    __syncthreads();
+    if (image < a.batch)
+        for (int i = (int)threadIdx.x; i < 2 * 272; i += 64 * kWavesM) {
+            const uint32_t v = (&s_cnt[0][0])[i];
+            if (v) atomicAdd(&counts[(size_t)image * kMcuTabWords + i], (unsigned long long)v);
+        }
+}
+
+int launch_mcu_histogram(const McuSegArgs &a, unsigned long long *counts, void *stream) {
+    const int n = a.batch * a.num_segs_pad;
+    if (n <= 0) return 0;
+    if (!counts || !mcu_seg_args_ok(a)) return (int)hipErrorInvalidValue;
+    const dim3 grid((unsigned)((n + kWavesM - 1) / kWavesM)), block(64 * kWavesM);
+    if (a.restart == 0) hipLaunchKernelGGL(k_mcu_histogram<false>, grid, block, 0, (hipStream_t)stream, a, counts);
+    else hipLaunchKernelGGL(k_mcu_histogram<true>, grid, block, 0, (hipStream_t)stream, a, counts);
+    return (int)hipGetLastError();
+}
+
+// Minimum of a 64-bit value across the wave, in every lane: the DPP steps of wave_max_u32, a lane without a source keeping its own.
+template <int kCtrl, int kRowMask>
+__device__ __forceinline__ unsigned long long min_dpp_u64(unsigned long long v) {
+    const int lo = (int)(uint32_t)v, hi = (int)(uint32_t)(v >> 32);
+    const uint32_t olo = (uint32_t)__builtin_amdgcn_update_dpp(lo, lo, kCtrl, kRowMask, 0xF, false);
+    const uint32_t ohi = (uint32_t)__builtin_amdgcn_update_dpp(hi, hi, kCtrl, kRowMask, 0xF, false);
+    const unsigned long long o = ((unsigned long long)ohi << 32) | olo;
+    return o < v ? o : v;
+}
+__device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v) {
+    v = min_dpp_u64<0x111, 0xF>(v);
+    v = min_dpp_u64<0x112, 0xF>(v);
+    v = min_dpp_u64<0x114, 0xF>(v);
+    v = min_dpp_u64<0x118, 0xF>(v);
+    v = min_dpp_u64<0x142, 0xA>(v);
+    v = min_dpp_u64<0x143, 0xC>(v);
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, 63), hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), 63);
+    return ((unsigned long long)hi << 32) | lo;
+}
+
+// Wave w of a workgroup: table w of its picture (0 luma DC, 1 luma AC, 2 chroma DC, 3 chroma AC), or job 4 g + w of a debug call.
+// The 257 slots of K.2 -- 256 symbols and the reserved point -- lie over the lanes, slot s in lane s & 63: count, tree id (its root's
+// slot) and depth.  Only a tree's root has a non-zero count (every other member was a c2 once), so "the root with the least count,
+// the highest index among equals" is the minimum of (count << 9 | 511 - slot) over the non-zero counts: one merge is two such
+// minima, then every slot of either tree goes one level down and takes c1's id -- what libjpeg's two chain walks do to codesize[].
+__global__ __launch_bounds__(256) void k_huff_optimal(const HuffOptimalArgs a) {
+    __shared__ uint32_t s_n[4][260];                               // n[l], l = 0 .. 256
+    __shared__ __attribute__((aligned(16))) uint32_t s_key[4][256]; // (depth << 8) | symbol of the used symbols, all ones for the rest
+    __shared__ uint32_t s_first[4][18], s_cum[4][18];              // by final length: the first code word, the HUFFVAL places in front of and at it
+    __shared__ uint8_t s_vals[4][256];
+    const int tid = (int)threadIdx.x, lane = lane_id(), w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int g = (int)blockIdx.x, job = 4 * g + w;
+    const bool active = job < a.jobs;
+    const int nsym = a.freq ? 256 : ((w & 1) ? 256 : 16);
+    const unsigned long long *src = a.freq ? a.freq + (size_t)job * 256 : a.counts + (size_t)g * kMcuTabWords + (size_t)(w >> 1) * 272 + ((w & 1) ? 0 : 256);
+    constexpr unsigned long long kNone = ~0ull;
+    unsigned long long f[5];
+    int tree[5];
+    uint32_t depth[5];
+    bool used[5];
+#pragma unroll
+    for (int r = 0; r < 5; ++r) {
+        const int s = lane + 64 * r;
+        f[r] = r == 4 ? (lane == 0 ? 1ull : 0ull) : ((active && s < nsym) ? src[s] : 0ull);
+        tree[r] = s; depth[r] = 0u; used[r] = f[r] != 0ull;
+    }
+    for (;;) {                                                     // (every value that steers the loop is the same in all lanes)
+        unsigned long long m = kNone;
+#pragma unroll
+        for (int r = 0; r < 5; ++r) if (f[r]) m = min(m, (f[r] << 9) | (unsigned long long)(511 - (lane + 64 * r)));
+        const unsigned long long k1 = wave_min_u64(m);
+        const int c1 = 511 - (int)(k1 & 511ull);
+        m = kNone;
+#pragma unroll
+        for (int r = 0; r < 5; ++r) if (f[r] && lane + 64 * r != c1) m = min(m, (f[r] << 9) | (unsigned long long)(511 - (lane + 64 * r)));
+        const unsigned long long k2 = wave_min_u64(m);
+        if (k2 == kNone) break;
+        const int c2 = 511 - (int)(k2 & 511ull);
+        const unsigned long long sum = (k1 >> 9) + (k2 >> 9);
+#pragma unroll
+        for (int r = 0; r < 5; ++r) {
+            const int s = lane + 64 * r;
+            if (s == c1) f[r] = sum;
+            if (s == c2) f[r] = 0ull;
+            if (tree[r] == c1 || tree[r] == c2) { ++depth[r]; tree[r] = c1; }
+        }
+    }
+    // n[l], then the symbols of lengths beyond 16 moved up (K.2's Adjust_BITS) and the reserved point taken out: one lane, a few steps
+    uint32_t *const n = s_n[w];
+    for (int i = lane; i < 260; i += 64) n[i] = 0u;
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int r = 0; r < 5; ++r) if (used[r]) atomicAdd(&n[min(depth[r], 256u)], 1u);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) s_key[w][lane + 64 * r] = used[r] ? (depth[r] << 8) | (uint32_t)(lane + 64 * r) : 0xFFFFFFFFu;
+    __builtin_amdgcn_wave_barrier();
+    if (lane == 0) {
+        int top = 256;
+        while (top > 0 && n[top] == 0u) --top;
+        for (int l = top; l > 16; --l)
+            while (n[l] > 0u) {
+                int j = l - 2;
+                while (j > 0 && n[j] == 0u) --j;
+                if (j <= 0 || n[l] < 2u) { n[l] = 0u; break; }     // (cannot happen for the lengths of a code tree: no index leaves the array)
+                n[l] -= 2u; n[l - 1] += 1u; n[j + 1] += 2u; n[j] -= 1u;
+            }
+        int l = 16;
+        while (l > 0 && n[l] == 0u) --l;
+        if (l > 0) n[l] -= 1u;
+        uint32_t code = 0, cum = 0;
+        s_cum[w][0] = 0u; s_first[w][0] = 0u;
+        for (l = 1; l <= 16; ++l) {
+            s_first[w][l] = code; cum += n[l]; s_cum[w][l] = cum;
+            code = (code + n[l]) << 1;
+        }
+    }
+    __builtin_amdgcn_wave_barrier();
+    const uint32_t nvals = min(s_cum[w][16], 256u);
+    // a used symbol's place in HUFFVAL: the used symbols in front of it by (depth, symbol); its code follows from the place
+    uint32_t word[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        word[r] = 0u;
+        if (!used[r]) continue;
+        const uint32_t mine = (depth[r] << 8) | (uint32_t)(lane + 64 * r);
+        uint32_t rank = 0;
+        for (int i = 0; i < 64; ++i) {
+            const uint4 k = *reinterpret_cast<const uint4 *>(&s_key[w][4 * i]);
+            rank += (k.x < mine) + (k.y < mine) + (k.z < mine) + (k.w < mine);
+        }
+        if (rank >= nvals) continue;
+        s_vals[w][rank] = (uint8_t)(lane + 64 * r);
+        uint32_t l = 1;
+        while (l < 16u && s_cum[w][l] <= rank) ++l;
+        word[r] = (l << 16) | (s_first[w][l] + rank - s_cum[w][l - 1]);
+    }
+    __builtin_amdgcn_wave_barrier();
+    if (active && a.res) {
+        uint8_t *res = a.res + (size_t)job * kHuffResBytes;
+        if (lane < 16) res[lane] = (uint8_t)n[lane + 1];
+        if (lane == 16) *reinterpret_cast<uint32_t *>(res + 16) = nvals;
+        for (int i = lane; i < 256; i += 64) res[32 + i] = (uint32_t)i < nvals ? s_vals[w][i] : (uint8_t)0;
+    }
+    if (a.freq) return;                                            // (the same for the whole launch)
+    uint32_t *const tab = a.tabs + (size_t)g * kMcuTabWords + (size_t)(w >> 1) * 272 + ((w & 1) ? 0 : 256);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) if (lane + 64 * r < nsym) tab[lane + 64 * r] = word[r];
+    __syncthreads();                                               // the four tables' sizes place the four DHT segments
+    uint8_t *const out = a.prefix + (size_t)g * kMcuPrefixSlot;
+    uint32_t at = (uint32_t)a.head_len, end = (uint32_t)a.head_len;
+    for (int t = 0; t < 4; ++t) {
+        const uint32_t len = 21u + min(s_cum[t][16], 256u);
+        if (t < w) at += len;
+        end += len;
+    }
+    const auto put = [&](uint32_t pos, uint8_t v) { if (pos < (uint32_t)kMcuPrefixSlot) out[pos] = v; };   // (a picture of this coder's coefficients never comes near the slot's end)
+    if (lane == 0) {
+        put(at, 0xFF); put(at + 1, 0xC4); put(at + 2, (uint8_t)((19u + nvals) >> 8)); put(at + 3, (uint8_t)(19u + nvals));
+        put(at + 4, (uint8_t)(((w & 1) << 4) | (w >> 1)));
+    }
+    if (lane < 16) put(at + 5 + lane, (uint8_t)n[lane + 1]);
+    for (uint32_t i = (uint32_t)lane; i < nvals; i += 64u) put(at + 21 + i, s_vals[w][i]);
+    for (int i = tid; i < a.head_len; i += 256) put((uint32_t)i, a.hdr[i]);
+    for (int i = tid; i < a.tail_len; i += 256) put(end + (uint32_t)i, a.hdr[a.tail_off + i]);
+    if (tid == 0) a.prefix_len[g] = min(end + (uint32_t)a.tail_len, (uint32_t)kMcuPrefixSlot);
+}
+
+int launch_huff_optimal(const HuffOptimalArgs &a, void *stream) {
+    if (a.jobs < 1 || (!a.freq) == (!a.counts) || (a.freq && !a.res)) return (int)hipErrorInvalidValue;
+    if (a.counts && (a.jobs % 4 != 0 || !a.tabs || !a.prefix || !a.prefix_len || !a.hdr || a.head_len < 0 || a.tail_len < 0 || a.tail_off < a.head_len ||
+                     a.head_len + a.tail_len > kMcuPrefixSlot))
+        return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_huff_optimal, dim3((unsigned)((a.jobs + 3) / 4)), dim3(256), 0, (hipStream_t)stream, a);
     return (int)hipGetLastError();
 }
 
@@ -256,7 +536,13 @@ constexpr int kRstStripWords = 132;             // k_mcu_restart_write: a wave's
 // last 7 bits of the segment are in `edge`) -- filled up with ones, and stuffed when that makes it 0xFF, in front of RSTn; filled
 // up with zeros in front of EOI -- and the two marker bytes.
 struct RstTail { uint32_t r, byte, bytes, pad_ff; };
-__device__ __forceinline__ RstTail rst_tail(uint32_t interval_bits, uint32_t edge, bool last_interval) {
+// The last 7 bits of an interval whose last segment has `bits` bits: that segment's, or -- it is shorter (a picture's own tables: one
+// MCU may be 6 bits) -- the bits in front of them from the segment in front, which is a full run of MCUs and never that short.  (An
+// interval's first segment has nothing in front: r <= bits there, and the bits taken from edge_prev are never looked at.)
+__device__ __forceinline__ uint32_t mcu_tail7(uint32_t edge, uint32_t bits, uint32_t edge_prev) {
+    return bits >= 7u ? edge & 0x7Fu : (((edge_prev & 0x7Fu) << bits) | (edge & ((1u << bits) - 1u))) & 0x7Fu;
+}
+__device__ __forceinline__ RstTail rst_tail(uint32_t interval_bits, uint32_t edge /*mcu_tail7*/, bool last_interval) {
     RstTail t;
     t.r = interval_bits & 7u;
     const uint32_t fill = last_interval ? 0u : (0xFFu >> t.r);
@@ -343,7 +629,7 @@ __global__ __launch_bounds__(kRstThreads) void k_mcu_restart_offsets(const McuRe
                 bytes[j] = ((b0[j] + bits[j]) >> 3) - (b0[j] >> 3) + ff[j];
                 const bool last = i == a.last_seg;
                 if (last || (k[j] == spi - 1 && i < last_first)) {
-                    const RstTail t = rst_tail(b0[j] + bits[j], edge[j], last);
+                    const RstTail t = rst_tail(b0[j] + bits[j], mcu_tail7(edge[j], bits[j], edge_prev[j]), last);
                     bytes[j] += t.bytes; pad_ff = t.pad_ff;
                 }
                 sum_ff += ff[j] + pad_ff; sum_bits += bits[j]; sum_syms += syms[j];
@@ -365,7 +651,7 @@ __global__ __launch_bounds__(kRstThreads) void k_mcu_restart_offsets(const McuRe
     if (tid == 0) {
         sum_bits = sum_syms = sum_ff = 0;
         for (int w = 0; w < 16; ++w) { sum_bits += s_sum[0][w]; sum_syms += s_sum[1][w]; sum_ff += s_sum[2][w]; }
-        *a.out_size[q] = (uint64_t)a.prefix_len + pos;              // the would-be size: k_mcu_totals makes it 0 when the file did not fit
+        *a.out_size[q] = (uint64_t)(a.pic_prefix_len ? a.pic_prefix_len[q] : (uint32_t)a.prefix_len) + pos;              // the would-be size: k_mcu_totals makes it 0 when the file did not fit
         unsigned long long *rec = a.pic_sums + (size_t)q * kMcuPicSums;
         rec[0] = sum_bits; rec[1] = sum_syms; rec[2] = sum_ff;
     }
@@ -380,20 +666,23 @@ __global__ __launch_bounds__(64 * kWavesM) void k_mcu_restart_write(const McuRes
     const int wgs = (a.num_segs_pad + kWavesM - 1) / kWavesM;
     const int image = (int)blockIdx.x / wgs, g = (int)blockIdx.x - image * wgs;
     uint8_t *const out = a.out[image];
+    const int prefix_len = a.pic_prefix_len ? (int)a.pic_prefix_len[image] : a.prefix_len;   // (a picture with its own tables has its own prefix)
+    const uint8_t *const prefix = a.pic_prefix ? a.pic_prefix + (size_t)image * a.pic_prefix_stride : a.prefix;
     if (g == 0)
-        for (int i = (int)threadIdx.x; i < a.prefix_len; i += 64 * kWavesM)
-            if ((uint64_t)i < a.out_capacity) out[i] = a.prefix[i];
+        for (int i = (int)threadIdx.x; i < prefix_len; i += 64 * kWavesM)
+            if ((uint64_t)i < a.out_capacity) out[i] = prefix[i];
     const int sl = g * kWavesM + wave;
     if (sl > a.last_seg) return;                                    // (no workgroup-wide meeting below)
     const size_t seg = (size_t)image * (size_t)a.num_segs_pad + (size_t)sl;
     const int iv = sl / a.segs_per_interval, k = sl - iv * a.segs_per_interval;
     const uint32_t bits = a.seg.bits[seg], edge = a.seg.edge[seg], b0 = a.b0[seg], my_ff = a.ff[seg];
     const uint32_t lead = b0 & 7u;                                  // bits of the segment in front that its first byte begins with (0 for k = 0)
-    const uint32_t leadbits = lead ? (a.seg.edge[seg - 1] & ((1u << lead) - 1u)) : 0u;
+    const uint32_t edge_prev = sl > 0 ? a.seg.edge[seg - 1] : 0u;
+    const uint32_t leadbits = lead ? (edge_prev & ((1u << lead) - 1u)) : 0u;   // (lead > 0: the segment in front is a full run of MCUs -- never shorter than 7 bits)
     const uint32_t nown = ((b0 + bits) >> 3) - (b0 >> 3);
     const bool last = sl == a.last_seg, tail = last || (k == a.segs_per_interval - 1 && iv < a.intervals - 1);
-    const RstTail t = rst_tail(b0 + bits, edge, last);
-    const uint64_t base = (uint64_t)a.prefix_len + a.pos[seg];
+    const RstTail t = rst_tail(b0 + bits, mcu_tail7(edge, bits, edge_prev), last);
+    const uint64_t base = (uint64_t)prefix_len + a.pos[seg];
     if (base + nown + my_ff + (tail ? t.bytes : 0u) > a.out_capacity) return;    // the file does not fit: k_mcu_totals reports it from the size
 
     const uint32_t *words = a.seg.words + seg * a.seg.words_stride;
@@ -461,7 +750,7 @@ __global__ __launch_bounds__(64 * kWavesM) void k_mcu_restart_write(const McuRes
 int launch_mcu_restart_writer(const McuRestartArgs &a, void *stream) {
     if (a.batch < 1 || a.batch > kMaxBatch || a.num_segs_pad < 1 || a.segs_per_interval < 1 || a.intervals < 1 || a.last_seg < 0 ||
         a.last_seg >= a.num_segs_pad || (int64_t)a.intervals * a.segs_per_interval > (int64_t)a.num_segs_pad ||
-        a.last_seg / a.segs_per_interval != a.intervals - 1)
+        a.last_seg / a.segs_per_interval != a.intervals - 1 || (!a.pic_prefix) != (!a.pic_prefix_len))
         return (int)hipErrorInvalidValue;
     const int wgs = (a.num_segs_pad + kWavesM - 1) / kWavesM;
     hipLaunchKernelGGL(k_mcu_restart_offsets, dim3((unsigned)a.batch), dim3(kRstThreads), 0, (hipStream_t)stream, a);

@@ -131,6 +131,9 @@ def _load() -> C.CDLL:
         "jpegamd_encode_color_interleaved_pixels_batch_async": (i32, [vp, C.POINTER(Image), i32, i32, i32, C.POINTER(C.c_void_p), u64, C.POINTER(C.c_void_p), vp]),
         "jpegamd_encode_planar_interleaved_batch_async": (i32, [vp, C.POINTER(PlanarImage), i32, i32, i32, C.POINTER(C.c_void_p), u64, C.POINTER(C.c_void_p), vp]),
         "jpegamd_debug_tile_variant": (i32, [i32, i32, i32, i32]),
+        "jpegamd_encoder_set_huffman": (i32, [vp, i32]),
+        "jpegamd_debug_optimal_huffman": (i32, [vp, vp, i32, vp, vp, vp]),
+        "jpegamd_debug_huffman_counts": (i32, [vp, vp]),
         "jpegamd_debug_matrix_coeffs": (i32, [i32, vp]),
         "jpegamd_debug_ycbcr_matrix_planes": (i32, [vp, C.POINTER(YCbCrImage), i32, i32, i32, i32, i32, vp, vp, vp, vp]),
         "jpegamd_debug_chroma_groups": (i32, [i32, i32, i32, i32, i32, i32, i32, vp]),
@@ -155,7 +158,8 @@ def _load() -> C.CDLL:
                     "jpegamd_encode_color_interleaved_restart_batch_async", "jpegamd_encode_ycbcr_interleaved_restart_batch_async",
                     "jpegamd_max_jfif_bytes_interleaved_restart", "jpegamd_encode_ycbcr_interleaved_matrix_batch_async",
                     "jpegamd_encode_color_interleaved_pixels_batch_async", "jpegamd_encode_planar_interleaved_batch_async",
-                    "jpegamd_debug_tile_variant") and os.environ.get("JPEGAMD_LIB") and not hasattr(lib, name):
+                    "jpegamd_debug_tile_variant", "jpegamd_encoder_set_huffman", "jpegamd_debug_optimal_huffman",
+                    "jpegamd_debug_huffman_counts") and os.environ.get("JPEGAMD_LIB") and not hasattr(lib, name):
             continue                                              # (A/B tooling: a variant build of an older round)
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = res, args
@@ -176,7 +180,8 @@ EXPORTED = ("jpegamd_encoder_create jpegamd_encoder_destroy jpegamd_max_jfif_byt
             "jpegamd_encode_color_interleaved_batch_async jpegamd_encode_ycbcr_interleaved_batch_async jpegamd_max_jfif_bytes_interleaved "
             "jpegamd_encode_color_interleaved_restart_batch_async jpegamd_encode_ycbcr_interleaved_restart_batch_async "
             "jpegamd_max_jfif_bytes_interleaved_restart jpegamd_encode_ycbcr_interleaved_matrix_batch_async "
-            "jpegamd_encode_color_interleaved_pixels_batch_async jpegamd_encode_planar_interleaved_batch_async").split()
+            "jpegamd_encode_color_interleaved_pixels_batch_async jpegamd_encode_planar_interleaved_batch_async "
+            "jpegamd_encoder_set_huffman jpegamd_debug_optimal_huffman jpegamd_debug_huffman_counts").split()
 
 
 def quant_table(quality: int = 50):
@@ -306,6 +311,15 @@ def max_jfif_bytes_interleaved_restart(width: int, height: int, subsampling: int
 
 
 SCANS = ("separate", "interleaved")
+HUFFMAN_STANDARD, HUFFMAN_OPTIMIZED = 0, 1       # jpegamd_encoder_set_huffman
+HUFFMANS = ("standard", "optimized")
+
+
+def _huffman(huffman) -> int:
+    """huffman= of jpegamd.mjpeg's functions -> HUFFMAN_STANDARD / HUFFMAN_OPTIMIZED; anything else is a ValueError."""
+    if not isinstance(huffman, str) or huffman not in HUFFMANS:
+        raise ValueError(f'huffman must be "standard" or "optimized", not {huffman!r}')
+    return HUFFMANS.index(huffman)
 
 
 def _restart(restart_interval, interleaved: bool, w: int, subsampling: int) -> int:
@@ -488,7 +502,7 @@ def _named_layout(t, layout, single: bool):
 
 
 def encode_tensor_batch(t, quality: int = 0, subsampling: int = SUBSAMPLE_420, layout=None, _single: bool = False,
-                        scan: str = "separate", restart_interval=None, _any_layout: bool = False) -> list:
+                        scan: str = "separate", restart_interval=None, _any_layout: bool = False, _huffman: int = 0) -> list:
     """A uint8 DEVICE tensor of N pictures -> N JFIF files: [N, H, W, 3] (R, G, B) colour files through
     jpegamd_encode_color_batch_async, [N, H, W] grayscale files through jpegamd_encode_batch_async.  Pictures may be strided
     (t[::2]), pixels within a row must be packed.  Batches of more than MAX_BATCH pictures go as several calls of at most
@@ -504,9 +518,12 @@ def encode_tensor_batch(t, quality: int = 0, subsampling: int = SUBSAMPLE_420, l
     decode to the same pixels as the scan="separate" files.
     restart_interval= (scan="interleaved" alone): restart intervals of that many MCUs, 1 .. 65535, or "row" for one MCU row (DRI /
     RSTn, jpegamd_encode_color_interleaved_restart_batch_async); 0 / None: none.
-    (`_any_layout`: jpegamd.mjpeg's call -- scan="interleaved" with every colour layout, through the entries that read them.)"""
+    (`_any_layout`: jpegamd.mjpeg's call -- scan="interleaved" with every colour layout, through the entries that read them;
+    `_huffman`: its tables, set on the per-device context for this call and put back to HUFFMAN_STANDARD behind it.)"""
     import torch
     interleaved = _scan(scan)
+    if _huffman and not interleaved:
+        raise ValueError('optimised Huffman tables need scan="interleaved"')
     if not interleaved:
         _restart(restart_interval, False, 1, subsampling)
     if interleaved and not _any_layout and layout not in (None, "hwc"):
@@ -549,6 +566,10 @@ def encode_tensor_batch(t, quality: int = 0, subsampling: int = SUBSAMPLE_420, l
             k = min(MAX_BATCH, n - b0)
             outs = [out[i].data_ptr() for i in range(k)]
             size_ptrs = [sizes.data_ptr() + 8 * i for i in range(k)]
+            if _huffman:
+                files += _with_huffman(enc, _huffman, lambda: _interleaved_call(enc, order, _any_layout, ptr, b0, k, w, h, stride, quality,
+                                                                                  subsampling, ri, outs, cap, size_ptrs, stream), out, sizes, k)
+                continue
             if interleaved and order is None:
                 imgs = [Encoder.planar_image(ptr(b0 + i), w, h, stride, bottom_up=False, quality=quality) for i in range(k)]
                 enc.encode_planar_interleaved_batch_async(imgs, subsampling, ri, outs, cap, size_ptrs, stream)
@@ -574,6 +595,29 @@ def encode_tensor_batch(t, quality: int = 0, subsampling: int = SUBSAMPLE_420, l
             got = sizes[:k].cpu().tolist()
             files += [bytes(out[i, :got[i]].cpu().numpy().tobytes()) for i in range(k)]
     return files
+
+
+def _interleaved_call(enc, order, any_layout, ptr, b0, k, w, h, stride, quality, subsampling, ri, outs, cap, size_ptrs, stream):
+    """One interleaved batch of encode_tensor_batch queued on `enc`: pictures b0 .. b0 + k - 1."""
+    if order is None:
+        imgs = [Encoder.planar_image(ptr(b0 + i), w, h, stride, bottom_up=False, quality=quality) for i in range(k)]
+        return enc.encode_planar_interleaved_batch_async(imgs, subsampling, ri, outs, cap, size_ptrs, stream)
+    imgs = [Encoder.image(ptr(b0 + i), w, h, stride, bottom_up=False, channel_order=order, quality=quality) for i in range(k)]
+    if any_layout:
+        return enc.encode_color_interleaved_pixels_batch_async(imgs, subsampling, ri, outs, cap, size_ptrs, stream)
+    return enc.encode_color_interleaved_restart_batch_async(imgs, subsampling, ri, outs, cap, size_ptrs, stream)
+
+
+def _with_huffman(enc, huffman: int, queue, out, sizes, k: int) -> list:
+    """queue() with `huffman` set on the shared context, finished, the context back in HUFFMAN_STANDARD whatever happens -> the k files."""
+    enc.set_huffman(huffman)
+    try:
+        queue()
+        enc.finish()
+    finally:
+        enc.set_huffman(HUFFMAN_STANDARD)
+    got = sizes[:k].cpu().tolist()
+    return [bytes(out[i, :got[i]].cpu().numpy().tobytes()) for i in range(k)]
 
 
 def _ycbcr_layout_of(y, cb, cr, subsampling, order, dtypes, sample_bytes, pairs):
@@ -686,11 +730,13 @@ def encode_ycbcr_batch(y, cb, cr=None, quality: int = 0, subsampling: int = SUBS
 
 
 def _encode_ycbcr_images(device, n, h, w, subsampling, image, sample_range: int = RANGE_FULL, sample_format: int = SAMPLES_8,
-                         matrix: int = MATRIX_BT601, interleaved: bool = False, restart: int = 0, any_kind: bool = False):
+                         matrix: int = MATRIX_BT601, interleaved: bool = False, restart: int = 0, any_kind: bool = False, huffman: int = 0):
     """`n` YCbCr pictures of one geometry, picture i described by image(i), through the per-device context in calls of at most
     MAX_BATCH -> their files.  `any_kind` (jpegamd.mjpeg): the interleaved files of whatever range, format, matrix and layout, through
-    jpegamd_encode_ycbcr_interleaved_matrix_batch_async."""
+    jpegamd_encode_ycbcr_interleaved_matrix_batch_async, with the tables `huffman` (set on the context for the call, STANDARD put back)."""
     import torch
+    if huffman and not any_kind:
+        raise ValueError("optimised Huffman tables go through jpegamd.mjpeg")
     dev = device.index if device.index is not None else torch.cuda.current_device()
     files = []
     with torch.cuda.device(dev):
@@ -714,6 +760,10 @@ def _encode_ycbcr_images(device, n, h, w, subsampling, image, sample_range: int 
             outs = [out[i].data_ptr() for i in range(k)]
             size_ptrs = [sizes.data_ptr() + 8 * i for i in range(k)]
             imgs = [image(b0 + i) for i in range(k)]
+            if huffman:
+                files += _with_huffman(enc, huffman, lambda: enc.encode_ycbcr_interleaved_matrix_batch_async(
+                    imgs, subsampling, sample_range, sample_format, matrix, restart, outs, cap, size_ptrs, stream), out, sizes, k)
+                continue
             if any_kind:
                 enc.encode_ycbcr_interleaved_matrix_batch_async(imgs, subsampling, sample_range, sample_format, matrix, restart, outs, cap,
                                                                 size_ptrs, stream)
@@ -839,6 +889,13 @@ class Encoder:
         rc = lib.jpegamd_encoder_set_pipeline(self._h, int(pipeline))
         if rc:
             raise JpegAmdError(rc, "jpegamd_encoder_set_pipeline")
+
+    def set_huffman(self, huffman: int):
+        """HUFFMAN_STANDARD (the Annex K tables, default) or HUFFMAN_OPTIMIZED (per-picture tables) for the one-scan entries
+        (jpegamd_encoder_set_huffman); takes effect with the next encode."""
+        rc = lib.jpegamd_encoder_set_huffman(self._h, int(huffman))
+        if rc:
+            raise JpegAmdError(rc, "jpegamd_encoder_set_huffman")
 
     def set_profiling(self, slots: int):
         rc = lib.jpegamd_encoder_set_profiling(self._h, int(slots))

@@ -5,16 +5,21 @@ Each function is its twin in `jpegamd` without `scan=` and with `restart_interva
 row): the same tensors, the same layout=, order=, sample_range=, matrix= and align=.  The file holds the samples the twin's three-scan
 file holds -- after the depth, range and matrix maps of include/jpeg_compression.h, in that order -- and decodes to the same pixels.
 Nothing is repacked or converted by a pass of its own: the tile kernel reads every source where it lies (BT.709: behind the one
-matrix pass of the three-scan path)."""
+matrix pass of the three-scan path).
+
+huffman= "standard" (the Annex K tables, default) or "optimized": four tables made for each picture from its own symbol counts, as
+libjpeg -optimize makes them -- the same pixels in a smaller file.  The mode is set on the per-device context for the
+call and STANDARD is put back behind it."""
 from __future__ import annotations
 
 import jpegamd as _j
 
 
 def encode_ycbcr_batch(y, cb, cr=None, quality: int = 0, subsampling: int = _j.SUBSAMPLE_420, order: str = "cbcr",
-                       sample_range: str = "full", matrix: str = "bt601", restart_interval=None) -> list:
+                       sample_range: str = "full", matrix: str = "bt601", restart_interval=None, huffman: str = "standard") -> list:
     """jpegamd.encode_ycbcr_batch's pictures (planes, or pairs with cr=None) -> N one-scan files, for either sample_range and matrix,
     through jpegamd_encode_ycbcr_interleaved_matrix_batch_async."""
+    huff = _j._huffman(huffman)
     rng, mat = _j._sample_range(sample_range), _j._matrix(matrix)
     n, h, w, y_stride, c_stride, layout = _j._ycbcr_layout(y, cb, cr, subsampling, order)
     ri = _j._restart(restart_interval, True, w, subsampling)
@@ -23,12 +28,14 @@ def encode_ycbcr_batch(y, cb, cr=None, quality: int = 0, subsampling: int = _j.S
         raise ValueError("encode_ycbcr_batch needs device tensors on one device")
     return _j._encode_ycbcr_images(y.device, n, h, w, subsampling, lambda i: _j.Encoder.ycbcr_image(
         y[i].data_ptr(), cb[i].data_ptr(), cr[i].data_ptr() if cr is not None else 0, w, h, y_stride, c_stride, layout, quality), rng,
-        matrix=mat, interleaved=True, restart=ri, any_kind=True)
+        matrix=mat, interleaved=True, restart=ri, any_kind=True, huffman=huff)
 
 
 def encode_ycbcr16_batch(y, cb, cr=None, quality: int = 0, subsampling: int = _j.SUBSAMPLE_420, order: str = "cbcr",
-                         sample_range: str = "full", align: str = "msb", matrix: str = "bt601", restart_interval=None) -> list:
+                         sample_range: str = "full", align: str = "msb", matrix: str = "bt601", restart_interval=None,
+                         huffman: str = "standard") -> list:
     """jpegamd.encode_ycbcr16_batch's pictures (10-bit samples in 16-bit words: P010 / I010 families) -> N one-scan files."""
+    huff = _j._huffman(huffman)
     rng, mat = _j._sample_range(sample_range), _j._matrix(matrix)
     if not isinstance(align, str) or align not in ("msb", "lsb"):
         raise ValueError(f'align must be "msb" or "lsb", not {align!r}')
@@ -39,29 +46,34 @@ def encode_ycbcr16_batch(y, cb, cr=None, quality: int = 0, subsampling: int = _j
         raise ValueError("encode_ycbcr16_batch needs device tensors on one device")
     return _j._encode_ycbcr_images(y.device, n, h, w, subsampling, lambda i: _j.Encoder.ycbcr_image(
         y[i].data_ptr(), cb[i].data_ptr(), cr[i].data_ptr() if cr is not None else 0, w, h, y_stride, c_stride, layout, quality), rng,
-        _j.SAMPLES_10_MSB if align == "msb" else _j.SAMPLES_10_LSB, mat, interleaved=True, restart=ri, any_kind=True)
+        _j.SAMPLES_10_MSB if align == "msb" else _j.SAMPLES_10_LSB, mat, interleaved=True, restart=ri, any_kind=True, huffman=huff)
 
 
 def encode_yuyv_batch(frames, quality: int = 0, order: str = "yuyv", sample_range: str = "full", matrix: str = "bt601",
-                      restart_interval=None) -> list:
+                      restart_interval=None, huffman: str = "standard") -> list:
     """jpegamd.encode_yuyv_batch's packed 4:2:2 frames (YUY2 / UYVY) -> N one-scan files at SUBSAMPLE_422."""
+    huff = _j._huffman(huffman)
     rng, mat = _j._sample_range(sample_range), _j._matrix(matrix)
     n, h, w, stride, layout = _j._yuyv_layout(frames, order)
     ri = _j._restart(restart_interval, True, w, _j.SUBSAMPLE_422)
     if not frames.is_cuda:
         raise ValueError("encode_yuyv_batch needs a device tensor")
     return _j._encode_ycbcr_images(frames.device, n, h, w, _j.SUBSAMPLE_422, lambda i: _j.Encoder.ycbcr_image(
-        frames[i].data_ptr(), 0, 0, w, h, stride, 0, layout, quality), rng, matrix=mat, interleaved=True, restart=ri, any_kind=True)
+        frames[i].data_ptr(), 0, 0, w, h, stride, 0, layout, quality), rng, matrix=mat, interleaved=True, restart=ri, any_kind=True,
+        huffman=huff)
 
 
-def encode_tensor_batch(t, quality: int = 0, subsampling: int = _j.SUBSAMPLE_420, layout=None, restart_interval=None) -> list:
+def encode_tensor_batch(t, quality: int = 0, subsampling: int = _j.SUBSAMPLE_420, layout=None, restart_interval=None,
+                        huffman: str = "standard") -> list:
     """jpegamd.encode_tensor_batch's colour pictures -> N one-scan files: [N, H, W, 3], or layout= "chw" ([N, 3, H, W] or three plane
     tensors), "rgba" / "bgra" [N, H, W, 4], "hwc".  The files are those of the same R, G, B values as [N, H, W, 3].  A one-scan file is
     a colour file: [N, H, W] grayscale pictures and subsampling 0 are ValueErrors."""
-    return _j.encode_tensor_batch(t, quality, subsampling, layout, scan="interleaved", restart_interval=restart_interval, _any_layout=True)
+    return _j.encode_tensor_batch(t, quality, subsampling, layout, scan="interleaved", restart_interval=restart_interval, _any_layout=True,
+                                  _huffman=_j._huffman(huffman))
 
 
-def encode_tensor(t, quality: int = 0, subsampling: int = _j.SUBSAMPLE_420, layout=None, restart_interval=None) -> bytes:
+def encode_tensor(t, quality: int = 0, subsampling: int = _j.SUBSAMPLE_420, layout=None, restart_interval=None,
+                  huffman: str = "standard") -> bytes:
     """One colour picture -> its one-scan file: [H, W, 3], or layout= "chw" [3, H, W], "rgba" / "bgra" [H, W, 4], "hwc"."""
     return _j.encode_tensor_batch(t, quality, subsampling, "hwc" if layout is None else layout, _single=True, scan="interleaved",
-                                  restart_interval=restart_interval, _any_layout=True)[0]
+                                  restart_interval=restart_interval, _any_layout=True, _huffman=_j._huffman(huffman))[0]

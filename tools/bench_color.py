@@ -47,6 +47,9 @@ frames once, outside the timed loop, and codes the mapped frames at full range: 
 --restart N|row (with --scan interleaved alone): restart intervals of N MCUs, or of one MCU row, through the _restart entries
 (jpegamd_encode_color_interleaved_restart_batch_async / jpegamd_encode_ycbcr_interleaved_restart_batch_async); the line then carries
 "restart_interval" in MCUs.  --restart 0 goes through those entries with interval 0 (the file without restart intervals).
+--huffman standard|optimized (with --scan interleaved alone): the Annex K tables, or per-picture optimised tables
+(jpegamd_encoder_set_huffman on the context); the line then carries "huffman".  `standard` sets nothing on the
+context, so a library from before the mode serves it.
 """
 from __future__ import annotations
 
@@ -87,6 +90,8 @@ def main() -> None:
                     help="interleaved: the batch loop goes through the one-scan entries (every --source, --range, --matrix; --layout chw / rgba)")
     ap.add_argument("--mapped", action="store_true",
                     help="--range limited (i420, nv12, i422): map the frames once outside the timed loop and code them at full range")
+    ap.add_argument("--huffman", choices=("standard", "optimized"), default=None,
+                    help="--scan interleaved: the Annex K tables, or per-picture optimised tables")
     ap.add_argument("--restart", default=None, metavar="N|row",
                     help="--scan interleaved: restart intervals of N MCUs (0 .. 65535), or `row` for one MCU row")
     a = ap.parse_args()
@@ -117,6 +122,8 @@ def main() -> None:
         sys.exit("--convert and --narrow time routes of the three-scan path: not with --scan interleaved")
     if a.mapped and (a.sample_range != "limited" or any(s not in ("i420", "nv12", "i422") for s in sources)):
         sys.exit("--mapped needs --range limited and takes --source i420, nv12, i422")
+    if a.huffman is not None and a.scan != "interleaved":
+        sys.exit("--huffman needs --scan interleaved")
     if a.restart is not None:
         if a.scan != "interleaved":
             sys.exit("--restart needs --scan interleaved")
@@ -198,6 +205,8 @@ def run_batch(a, jpegamd, torch, dev, sources=("rgb",)) -> None:
         descs.append(jpegamd.Encoder.image(pxs[-1].data_ptr(), w, h, img.row_stride, True, jpegamd.ORDER_BGR, a.quality))
         del bmp
     enc = jpegamd.Encoder(w, n * h)
+    if a.huffman == "optimized":
+        enc.set_huffman(jpegamd.HUFFMAN_OPTIMIZED)
     stream = torch.cuda.current_stream().cuda_stream
     frames = None
     if any(s in ("i420", "nv12", "p010", "i010") for s in sources):   # NV12 frames [N, 3 H / 2, W], and the chroma as two planes
@@ -318,6 +327,8 @@ def run_batch(a, jpegamd, torch, dev, sources=("rgb",)) -> None:
                 "gpixels_per_s": round(n * w * h / t, 2)}
         if one_scan:
             line["scan"] = "interleaved"
+        if a.huffman is not None:
+            line["huffman"] = a.huffman
         if restart is not None:
             line["restart_interval"] = restart
         if limited:
@@ -522,6 +533,8 @@ def run_layout(a, jpegamd, torch, dev) -> None:
     if a.layout != "hwc" and not a.repack:
         del hwc
     enc = jpegamd.Encoder(w, n * h)
+    if a.huffman == "optimized":
+        enc.set_huffman(jpegamd.HUFFMAN_OPTIMIZED)
     stream = torch.cuda.current_stream().cuda_stream
     one_scan = a.scan == "interleaved"
     restart = 0
@@ -584,7 +597,8 @@ def run_layout(a, jpegamd, torch, dev) -> None:
                           "steps": a.steps, "rounds": a.rounds, "bytes": got[k], "us_per_picture_medians": [round(v, 1) for v in m],
                           "us_per_picture": round(statistics.median(m), 1), "spread_us": round(max(m) - min(m), 1),
                           "gpixels_per_s": round(w * h / statistics.median(m) / 1000, 2),
-                          **({"scan": "interleaved", "restart_interval": restart} if one_scan else {})}))
+                          **({"scan": "interleaved", "restart_interval": restart} if one_scan else {}),
+                          **({"huffman": a.huffman} if a.huffman is not None else {})}))
 
 
 if __name__ == "__main__":
