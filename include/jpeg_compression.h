@@ -452,7 +452,8 @@ int32_t jpegamd_encoder_set_pipeline(JpegAmdEncoder *enc, int32_t pipeline);
  * 16 + 10 (an AC coefficient of 8-bit samples is below 1024 in magnitude for this quantiser as for T.81), 27 + 63 x 26 bits a block --
  * below the 22 + 63 x 27 the bounds and the path's reservations are made of.  The scratch of the mode -- per picture 4.3 KB of
  * counters, 2.2 KB of coder tables, one prefix slot -- is allocated with the path's scratch on the context's first OPTIMIZED call.
- * No effect on the grayscale, three-scan, row-sharded, DTO and file entries, whose coder is inside the tile kernel: optimised tables
+ * It governs jpegamd_encode_gray_scan_batch_async (further down) as well, with two tables per picture.  No effect on the other
+ * grayscale entries and the three-scan, row-sharded, DTO and file entries, whose coder is inside the tile kernel: optimised tables
  * for those are a follow-up. */
 #define JPEGAMD_HUFFMAN_STANDARD  0
 #define JPEGAMD_HUFFMAN_OPTIMIZED 1
@@ -464,6 +465,46 @@ int32_t jpegamd_encoder_set_huffman(JpegAmdEncoder *enc, int32_t huffman);
  * order above (a DC table's at 0 .. 15); JPEGAMD_ERR_ARG when the context made no such call. */
 int32_t jpegamd_debug_optimal_huffman(JpegAmdEncoder *enc, const uint64_t *freq, int32_t n, uint8_t *bits, uint8_t *vals, int32_t *nvals);
 int32_t jpegamd_debug_huffman_counts(JpegAmdEncoder *enc, uint64_t *counts);
+
+/* GRAYSCALE files with restart intervals and per-picture optimised Huffman tables: the grayscale file written as
+ * a scan of ONE component from coefficient planes, the way the one-scan colour files are.  For a picture of W x H at quality q,
+ * restart_interval = Ri (0 .. 65535, in MCUs) and the context's Huffman mode (jpegamd_encoder_set_huffman governs this entry too):
+ *   Prefix.  The 328-byte prefix of jpegamd_encode_batch_async(..., with_container = 1): SOI, APP0, DQT, SOF0 with one component,
+ *     DHT 0/0 (K.3), DHT 1/0 (K.5), SOS FF DA 00 08 01 01 00 00 3F 00.  Ri > 0: one DRI segment FF DD 00 04 hi lo directly in front
+ *     of the SOS, behind the last DHT.  JPEGAMD_HUFFMAN_OPTIMIZED: the picture's own two DHT segments stand where the standard two
+ *     stand, in the same order (Tc/Th 00, then 10), each FF C4, length 19 + nvals, the Tc/Th byte, 16 BITS bytes, HUFFVAL.
+ *   Scan.  A non-interleaved scan of one component: the MCU is one block.  The bw x bh = ceil(W / 8) x ceil(H / 8) blocks are coded
+ *     in raster order, M = bw bh; there are no pad blocks.  A block's 64 coefficients are exactly those the grayscale entries code
+ *     for the same picture.  Coding is T.81 F.1.2.
+ *   Intervals.  With Ri > 0 interval i codes the blocks [i Ri, min((i + 1) Ri, M)); the DC predictor is 0 at its first block.  Rules
+ *     3 - 5 of the colour files' restart section above apply unchanged: every interval but the last is padded with 1-bits, every
+ *     0xFF is stuffed (the padded byte too), then FF D0+(i mod 8); the last interval ends with the zero-bit flush, then EOI; Ri >= M
+ *     gives the file without intervals with the DRI segment inserted, byte for byte.
+ *   Tables in OPTIMIZED mode.  The DC table is built from the DC size symbols of all blocks, differences taken against 0 at every
+ *     interval start -- the counts depend on Ri; the AC table from the run/size symbols, every ZRL and EOB included.  The construction
+ *     is the one written down for JPEGAMD_HUFFMAN_OPTIMIZED above; a table with one used symbol gets the 1-bit code 0.
+ * Pictures, count (1 .. JPEGAMD_MAX_BATCH, one geometry) and context sizing are those of jpegamd_encode_batch_async; all five channel
+ * orders are taken (GRAY, and the luma of BGR, RGB, RGBA and BGRA pictures), either row order, any valid stride.  restart_interval
+ * outside 0 .. 65535 and every other bad argument: JPEGAMD_ERR_ARG before the context is read.  A picture whose scratch alone exceeds
+ * the path's 4 GiB group budget (small Ri on huge pictures): JPEGAMD_ERR_TOO_LARGE before anything is allocated or launched.
+ * restart_interval 0 with JPEGAMD_HUFFMAN_STANDARD IS jpegamd_encode_batch_async with with_container = 1: same launches, file,
+ * statistics and profiling.  Every other combination takes the coefficient route of the one-scan colour entries -- per picture one
+ * stage-tap launch of the tile kernel; per group of pictures the symbol counts and table builder when OPTIMIZED, the coder, the
+ * restart writer -- and shares their behaviour: a picture that does not fit out_capacity gets size 0, nothing is written past
+ * out_capacity, the other pictures are unaffected, jpegamd_encoder_finish returns JPEGAMD_ERR_HUFF_CAPACITY and the context stays
+ * usable; entropy_bits and stuffed_bytes as defined there, exact_fallbacks the grayscale entry's figure; with profiling on a call
+ * records ns_total only; jpegamd_encoder_set_pipeline has no effect.  After an OPTIMIZED call jpegamd_debug_huffman_counts keeps its
+ * [pictures][4][256] shape with tables 2 and 3 all zero.
+ * The bound.  jpegamd_max_jfif_bytes is NOT an upper bound for the OPTIMIZED file: an optimised DC symbol may take 16 + 11 bits where
+ * Annex K's takes at most 9 + 11.  jpegamd_max_jfif_bytes_gray_scan = 328 + 2 * (ceil(M * 1723 / 8) + 1) + 2 + 16, and with
+ * restart_interval > 0 and n = ceil(M / Ri) intervals + 6 + 4 * (n - 1): a block of either mode is below 22 + 63 x 27 = 1723 bits
+ * (optimised: at most 27 + 63 x 26 = 1665; the coder's string of a segment is reserved for 256 blocks of 1723), the scan rounds up
+ * to a byte once and every byte may be stuffed, then EOI; the DRI segment adds 6 bytes, and every interval but the last rounds up on
+ * its own -- at most one more byte --, may have that byte stuffed, and ends with two marker bytes.  0 for bad arguments (a dimension
+ * outside 1 .. 65535, restart_interval outside 0 .. 65535). */
+int32_t jpegamd_encode_gray_scan_batch_async(JpegAmdEncoder *enc, const JpegAmdImage *imgs, int32_t count, int32_t restart_interval,
+                                             void *const *outs_dev, uint64_t out_capacity, uint64_t *const *out_sizes_dev, void *stream);
+uint64_t jpegamd_max_jfif_bytes_gray_scan(int32_t width, int32_t height, int32_t restart_interval);
 
 /* Block until the last enqueued encode on this context finished; optionally fetch stats
  * (stats may be NULL).  Returns JPEGAMD_ERR_HUFF_CAPACITY if the output did not fit. */

@@ -1525,7 +1525,9 @@ extern "C" int32_t jpegamd_encode_ycbcr_batch_async(JpegAmdEncoder *e, const Jpe
 // which then codes every picture with its own tables, and the restart writer stands in for k_finalize at every interval: it reads a
 // prefix and its length per picture.
 // ---------------------------------------------------------------------------------------------------------
+constexpr int kSubNone = 0;              // `subsampling` of a scan of ONE component (the grayscale file of DESIGN.md 4.6.11): no entry takes it from a caller
 struct McuGeometry {
+    int comps;                          // components of the scan: 3, or 1 -- the MCU is then one block, the MCU grid the block grid
     int hs, vs, bw, bh, mx, my, seg_mcus, num_segs, num_segs_pad;
     ChromaGeom chroma;
     size_t coef_per_pic;                // int16 elements
@@ -1537,12 +1539,14 @@ struct McuGeometry {
 // restart: the interval in MCUs, 0 for none.
 static McuGeometry mcu_geometry(int w, int h, int sub, int restart = 0) {
     McuGeometry g;
-    g.hs = sub == JPEGAMD_SUBSAMPLE_444 ? 1 : 2;
+    g.comps = sub == kSubNone ? 1 : 3;
+    g.hs = sub == JPEGAMD_SUBSAMPLE_444 || sub == kSubNone ? 1 : 2;
     g.vs = sub == JPEGAMD_SUBSAMPLE_420 ? 2 : 1;
     g.bw = (w + 7) / 8; g.bh = (h + 7) / 8;
     g.mx = (g.bw + g.hs - 1) / g.hs; g.my = (g.bh + g.vs - 1) / g.vs;
     g.chroma = chroma_geom(w, h, sub);
-    g.seg_mcus = mcu_seg_mcus(g.hs, g.vs);
+    g.seg_mcus = mcu_seg_mcus(g.hs, g.vs, g.comps);
+    const int bpm = mcu_blocks_per_mcu(g.hs, g.vs, g.comps);
     const int64_t mcus = (int64_t)g.mx * g.my;
     g.restart = restart;
     g.intervals = restart ? (int)((mcus + restart - 1) / restart) : 1;
@@ -1552,8 +1556,8 @@ static McuGeometry mcu_geometry(int w, int h, int sub, int restart = 0) {
     g.num_segs_pad = (g.num_segs + kSegGroup - 1) / kSegGroup * kSegGroup;
     const int64_t in_last = mcus - (int64_t)(g.intervals - 1) * (restart ? restart : 0);     // MCUs of the last interval
     g.last_seg = (int)std::min<int64_t>((int64_t)(g.intervals - 1) * g.segs_per_interval + (in_last + g.seg_mcus - 1) / g.seg_mcus - 1, INT32_MAX / 2);
-    g.cap_words = restart ? (size_t)mcu_restart_cap_words(std::min(restart, g.seg_mcus) * (g.hs * g.vs + 2)) : (size_t)kSegCapWords;
-    g.coef_per_pic = ((size_t)g.bw * g.bh + 2 * (size_t)g.mx * g.my) * 64;
+    g.cap_words = restart ? (size_t)mcu_restart_cap_words(std::min(restart, g.seg_mcus) * bpm) : (size_t)kSegCapWords;
+    g.coef_per_pic = ((size_t)g.bw * g.bh + (g.comps == 1 ? 0 : 2 * (size_t)g.mx * g.my)) * 64;
     return g;
 }
 // Bytes of the path's scratch one picture takes in the group budget: its coefficient planes and its segment strings; with restart
@@ -1630,25 +1634,34 @@ static int32_t mcu_alloc(JpegAmdEncoder *e, const McuGeometry &g, int group, boo
 }
 
 // The colour prefix up to its DHTs, [DRI with the restart interval,] then the SOS of all three components (Y: tables 0 / 0, Cb and
-// Cr: 1 / 1).
+// Cr: 1 / 1).  One component (kSubNone): the grayscale prefix up to its two DHTs, [DRI,] its SOS.
 static int32_t prepare_mcu_prefix(JpegAmdEncoder *e, const JpegAmdImage *img, int sub, int restart) {
     auto &m = e->mcu;
     const int q = clamp_quality(img->quality);
     if (m.hdr_for.matches(img->width, img->height, q, sub, restart)) return JPEGAMD_OK;
     uint8_t luma[64], chroma[64], hdr[kColorPrefixMax + kMcuDriBytes + kMcuSosBytes];
     quant_table_for_quality(q, luma);
-    chroma_quant_table_for_quality(q, chroma);
-    size_t n = build_jfif_prefix_color(img->width, img->height, luma, chroma, chroma_mode(sub), hdr) - kSosBytes;
+    size_t n, nsos;
+    uint8_t sos[kMcuSosBytes] = {0xFF, 0xDA, 0x00, 0x0C, 0x03, 0x01, 0x00, 0x02, 0x11, 0x03, 0x11, 0x00, 0x3F, 0x00};
+    if (sub == kSubNone) {
+        static_assert(JPEGAMD_JFIF_PREFIX_BYTES <= kColorPrefixMax, "the grayscale prefix fits the staging buffer");
+        n = build_jfif_prefix(img->width, img->height, luma, hdr) - kSosBytes;
+        nsos = kSosBytes;
+        std::memcpy(sos, hdr + n, nsos);                                // (behind the DRI segment again)
+    } else {
+        chroma_quant_table_for_quality(q, chroma);
+        n = build_jfif_prefix_color(img->width, img->height, luma, chroma, chroma_mode(sub), hdr) - kSosBytes;
+        nsos = kMcuSosBytes;
+    }
     if (restart) {
         const uint8_t dri[kMcuDriBytes] = {0xFF, 0xDD, 0x00, 0x04, (uint8_t)(restart >> 8), (uint8_t)restart};
         std::memcpy(hdr + n, dri, sizeof(dri));
         n += sizeof(dri);
     }
-    const uint8_t sos[kMcuSosBytes] = {0xFF, 0xDA, 0x00, 0x0C, 0x03, 0x01, 0x00, 0x02, 0x11, 0x03, 0x11, 0x00, 0x3F, 0x00};
-    std::memcpy(hdr + n, sos, sizeof(sos));
+    std::memcpy(hdr + n, sos, nsos);
     if (int32_t rc = wait_pending(e)) return rc;
-    HIP_TRY(hipMemcpy(m.hdr, hdr, n + sizeof(sos), hipMemcpyHostToDevice));
-    m.hdr_for.set(img->width, img->height, q, sub, (int)(n + sizeof(sos)), restart);
+    HIP_TRY(hipMemcpy(m.hdr, hdr, n + nsos, hipMemcpyHostToDevice));
+    m.hdr_for.set(img->width, img->height, q, sub, (int)(n + nsos), restart);
     return JPEGAMD_OK;
 }
 
@@ -1658,6 +1671,8 @@ static int32_t prepare_mcu_prefix(JpegAmdEncoder *e, const JpegAmdImage *img, in
 // k_ycbcr_matrix_batch in front, as in color_batch: every launch then reads the full-range BT.601 planes that pass leaves in scratch.
 // `restart`: the restart interval in MCUs (1 .. 65535), or 0 for the file without -- the launches below are then what they were
 // before there were restart intervals: k_mcu_segments<false>, k_finalize, k_mcu_totals.
+// subsampling kSubNone (jpegamd_encode_gray_scan_batch_async alone): the grayscale file as a scan of ONE component, DESIGN.md 4.6.11 -- the luma of g0 / px
+// tapped and coded, no chroma launch, two tables; always through the restart writer (the caller sends the plain Annex K file elsewhere).
 static int32_t interleaved_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, const PlaneSet &px, int32_t count, int32_t subsampling, int32_t restart,
                                  void *const *outs_dev, uint64_t out_capacity, uint64_t *const *out_sizes_dev, void *stream_,
                                  const YccSource *ycc_in = nullptr) {
@@ -1667,9 +1682,11 @@ static int32_t interleaved_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, cons
     const McuGeometry g = mcu_geometry(g0.width, g0.height, subsampling, restart);
     // A picture's own tables: k_mcu_histogram and k_huff_optimal in front of the coder, and the restart writer for
     // every interval -- it reads a prefix and its length per picture; without restart intervals the scan is its one interval.
+    const bool gray = g.comps == 1;
     const bool optimized = e->huffman == JPEGAMD_HUFFMAN_OPTIMIZED, writer = restart || optimized;
+    if (gray && !writer) return JPEGAMD_ERR_ARG;                    // (that file is gray_batch's: the entry sends it there)
     // segments as short as one MCU: a picture whose scratch alone is beyond the group budget is refused, nothing allocated or launched
-    if (restart && mcu_scratch_per_pic(g, true) > kMcuScratchBudget) return JPEGAMD_ERR_TOO_LARGE;
+    if ((restart || gray) && mcu_scratch_per_pic(g, true) > kMcuScratchBudget) return JPEGAMD_ERR_TOO_LARGE;
     // every launch codes ONE picture's component: the Y plane and a chroma plane must fit the context
     const MatrixScratch ms = matrix_scratch(g0.width, g0.height, count, g.chroma.plane_bytes);
     JpegAmdImage gy = g0;                                            // the Y launches' picture: a BT.709 batch reads the scratch Y planes
@@ -1681,22 +1698,22 @@ static int32_t interleaved_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, cons
     JpegAmdImage pimg = g0;
     pimg.width = cg.cw; pimg.height = cg.ch; pimg.row_stride = ycc ? ycc->c_stride : cg.pitch; pimg.bottom_up = 0; pimg.channel_order = JPEGAMD_ORDER_GRAY;
     pimg.pixels = ycc ? ycc->cb[0] : g0.pixels;                      // (a non-null placeholder: every launch sets its own plane)
-    ImageDesc ic;
-    rc = describe(e, &pimg, &ic);
+    ImageDesc ic = {};
+    rc = gray ? JPEGAMD_OK : describe(e, &pimg, &ic);
     if (rc) return rc;
-    if (iy.blocks_w != g.bw || iy.blocks_h != g.bh || ic.blocks_w != g.mx || ic.blocks_h != g.my) return JPEGAMD_ERR_ARG;
+    if (iy.blocks_w != g.bw || iy.blocks_h != g.bh || (!gray && (ic.blocks_w != g.mx || ic.blocks_h != g.my))) return JPEGAMD_ERR_ARG;
 
     const size_t per_pic = (size_t)mcu_scratch_per_pic(g, writer);
     const int group = (int)std::max<size_t>(1, std::min<size_t>((size_t)count, kMcuScratchBudget / per_pic));
     rc = color_alloc_consts(e);
     if (rc) return rc;
-    rc = color_batch_alloc(e, mx ? ms.total : (ycc ? 0 : 2 * (size_t)count * cg.plane_bytes + 256), 0);
+    rc = color_batch_alloc(e, mx ? ms.total : (ycc || gray ? 0 : 2 * (size_t)count * cg.plane_bytes + 256), 0);
     if (rc) return rc;
     rc = mcu_alloc(e, g, group, writer, optimized ? count : 0);
     if (rc) return rc;
     rc = prepare_constants(e, &g0, false);
     if (rc) return rc;
-    rc = prepare_color_constants(e, &g0, subsampling);
+    rc = gray ? JPEGAMD_OK : prepare_color_constants(e, &g0, subsampling);
     if (rc) return rc;
     rc = prepare_mcu_prefix(e, &g0, subsampling, restart);
     if (rc) return rc;
@@ -1715,7 +1732,7 @@ static int32_t interleaved_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, cons
 
     if (mx) {                                                        // once for the whole call, in front of the groups
         if (launch_matrix_pass(e, g0, px, *ycc_in, count, subsampling, cg, ms, stream, nullptr)) return JPEGAMD_ERR_HIP;
-    } else if (!ycc) {
+    } else if (!ycc && !gray) {
         if (launch_plane_pass(e, g0, px, count, subsampling, cg, stream, nullptr)) return JPEGAMD_ERR_HIP;
     }
     const size_t cb_off = (size_t)g.bw * g.bh * 64, cr_off = cb_off + (size_t)g.mx * g.my * 64;
@@ -1737,7 +1754,7 @@ static int32_t interleaved_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, cons
                 const PictureStatsArgs ps = {e->tile_head, e->huff, im.num_tiles, 1, 0, 0, pic + (size_t)p * kPicStatWords};
                 if (launch_picture_stats(ps, stream)) return JPEGAMD_ERR_HIP;
             }
-            for (int k = 0; k < 2; ++k) {   // Cb, Cr: planes 2 p and 2 p + 1 of the call
+            for (int k = 0; k < (gray ? 0 : 2); ++k) {   // Cb, Cr: planes 2 p and 2 p + 1 of the call
                 ImageDesc im = ic;
                 set_single_picture(&im, chroma_plane_of(e, ycc, cg, 2 * p + k));
                 const TileSource src = chroma_source_of(ycc, 2 * p + k, &im);
@@ -1756,19 +1773,21 @@ static int32_t interleaved_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, cons
         sa.seg.words_stride = (uint32_t)g.cap_words;
         sa.status = &m.scan_stats->status;
         sa.restart = restart; sa.segs_per_interval = restart ? g.segs_per_interval : 0;
+        sa.comps = g.comps;
         if (optimized) {                                             // the group's pictures are [first, first + n) of the call's table scratch
             unsigned long long *counts = m.hcounts + (size_t)first * kMcuTabWords;
             HIP_TRY(hipMemsetAsync(counts, 0, (size_t)n * kMcuTabWords * sizeof(unsigned long long), stream));
             if (launch_mcu_histogram(sa, counts, stream)) return JPEGAMD_ERR_HIP;
             HuffOptimalArgs ha;
             std::memset(&ha, 0, sizeof(ha));
-            ha.counts = counts; ha.jobs = 4 * n;
-            ha.res = m.hres + (size_t)first * 4 * kHuffResBytes;
+            ha.tables = gray ? 2 : 4;
+            ha.counts = counts; ha.jobs = ha.tables * n;
+            ha.res = m.hres + (size_t)first * ha.tables * kHuffResBytes;
             ha.tabs = m.htabs + (size_t)first * kMcuTabWords;
             ha.prefix = m.hprefix + (size_t)first * kMcuPrefixSlot; ha.prefix_len = m.hprefix_len + first;
-            ha.hdr = m.hdr;                                          // the standard prefix: head, four Annex K DHTs, [DRI,] SOS
-            ha.tail_len = kMcuSosBytes + (restart ? kMcuDriBytes : 0);
-            ha.tail_off = m.hdr_for.len - ha.tail_len; ha.head_len = ha.tail_off - kStdDhtBytes;
+            ha.hdr = m.hdr;                                          // the standard prefix: head, the Annex K DHTs (four, or two), [DRI,] SOS
+            ha.tail_len = (gray ? kSosBytes : kMcuSosBytes) + (restart ? kMcuDriBytes : 0);
+            ha.tail_off = m.hdr_for.len - ha.tail_len; ha.head_len = ha.tail_off - (gray ? kStdDhtBytesGray : kStdDhtBytes);
             if (launch_huff_optimal(ha, stream)) return JPEGAMD_ERR_HIP;
             sa.huff_y = ha.tabs; sa.huff_c = ha.tabs + 272; sa.huff_stride = kMcuTabWords;
         }
@@ -1901,6 +1920,32 @@ extern "C" int32_t jpegamd_encode_color_interleaved_pixels_batch_async(JpegAmdEn
                                                                        int32_t restart_interval, void *const *outs_dev, uint64_t out_capacity,
                                                                        uint64_t *const *out_sizes_dev, void *stream_) {
     return interleaved_pixels(e, imgs, count, subsampling, restart_interval, true, outs_dev, out_capacity, out_sizes_dev, stream_);
+}
+
+// The grayscale file as a scan of one component, with restart intervals and the context's Huffman mode.
+// A block in either mode is below kMaxBlockBitsColor bits (optimised: 27 + 63 x 26), every byte may be stuffed; the scan rounds up
+// to a byte once and ends with EOI; n intervals add the DRI segment and 4 (n - 1) bytes (jpegamd_max_jfif_bytes_interleaved_restart).
+extern "C" uint64_t jpegamd_max_jfif_bytes_gray_scan(int32_t width, int32_t height, int32_t restart_interval) {
+    if (width <= 0 || height <= 0 || width > 65535 || height > 65535 || !restart_valid(restart_interval)) return 0;
+    const uint64_t nb = blocks_of(width, height);
+    const uint64_t plain = JPEGAMD_JFIF_PREFIX_BYTES + scan_bound(nb, kMaxBlockBitsColor) + 2 + 16;
+    if (!restart_interval) return plain;
+    const uint64_t n = (nb + (uint64_t)restart_interval - 1) / (uint64_t)restart_interval;
+    return plain + kMcuDriBytes + 4 * (n - 1);
+}
+
+extern "C" int32_t jpegamd_encode_gray_scan_batch_async(JpegAmdEncoder *e, const JpegAmdImage *imgs, int32_t count, int32_t restart_interval,
+                                                        void *const *outs_dev, uint64_t out_capacity, uint64_t *const *out_sizes_dev, void *stream_) {
+    // the arguments first: nothing of the context is read before they are known to be good
+    if (!restart_valid(restart_interval)) return JPEGAMD_ERR_ARG;
+    if (!e || !imgs || !outs_dev || !out_sizes_dev || count < 1 || count > kMaxBatch) return JPEGAMD_ERR_ARG;
+    ImageDesc im;
+    if (int32_t rc = describe(nullptr, &imgs[0], &im, kSegTiles, kAcceptPx4)) return rc;
+    PlaneSet ps;
+    if (int32_t rc = uniform_batch_args(imgs, count, outs_dev, out_sizes_dev, &ps)) return rc;
+    // no intervals, the Annex K tables: the grayscale entry's file, and that entry writes it
+    if (restart_interval == 0 && e->huffman == JPEGAMD_HUFFMAN_STANDARD) return gray_batch(e, imgs[0], ps, count, outs_dev, out_capacity, out_sizes_dev, 1, stream_);
+    return interleaved_batch(e, imgs[0], ps, count, kSubNone, restart_interval, outs_dev, out_capacity, out_sizes_dev, stream_);
 }
 
 // `count` planar pictures in one scan.  No grayscale file here: subsampling 0 is refused.

@@ -121,8 +121,10 @@ __device__ __forceinline__ int uniform(int v) { return __builtin_amdgcn_readfirs
 // ------------------------------------------------------------------------------------
 // Owned 0xFF bytes of segment t given its byte phase p (= bit offset & 7): those wholly inside it (counted by k_segment_merge)
 // plus the byte that straddles its start -- 0xFF iff the last p bits in front of it and its first 8 - p bits are all ones.
-// edge = (first 8 bits << 8) | last 7 bits of a segment's own string.  A segment shorter than 8 bits is "00 1010" (one
-// flat block): it has no leading one, and its tail ends in 0, so neither side can complete an 0xFF across it.
+// edge = (first 8 bits << 8) | last 7 bits of a segment's own string.  A segment shorter than 8 bits -- "00 1010", one flat block
+// with the Annex K tables; 2 .. 7 bits of any value with a picture's own tables (jpegamd_mcu.hip) -- stands at the left of the 8 with
+// zeros behind it: it completes the straddling byte only when it holds all of that byte's last 8 - p bits, and then owns it.  Such a
+// segment is the last of its interval, so its own tail is never the front of a byte that a next segment completes.
 __device__ __forceinline__ uint32_t fin_owned_ff(uint4 ffin /*the segment's 8 counts, 16 bits each*/, int t, uint32_t p, uint32_t edge_t, uint32_t edge_prev) {
     const uint32_t lo = (p & 4u) ? ffin.z : ffin.x, hi = (p & 4u) ? ffin.w : ffin.y;
     const uint32_t w = (p & 2u) ? hi : lo;

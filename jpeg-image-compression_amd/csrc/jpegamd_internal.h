@@ -389,7 +389,11 @@ int launch_append_scans_batch(const AppendBatchArgs &a, void *stream, void *cons
 // picture is the MCUs [s seg_mcus, (s + 1) seg_mcus) of the raster MCU order; every picture has num_segs_pad entries in the segment
 // arrays -- num_segs rounded up to kSegGroup with EMPTY segments (no bits), so that k_finalize's four-at-a-time reads of the
 // per-segment arrays stay aligned for every picture of a batch.
-constexpr int mcu_seg_mcus(int hs, int vs) { return kSegBlocks / (hs * vs + 2); }     // 85 / 42 / 64: at most 256 blocks per segment
+// A scan of ONE component (comps = 1: the grayscale file of DESIGN.md 4.6.11) is the same with an MCU of one block: the plane at 0
+// alone, mx x my = bw x bh, no pad blocks, a segment of kSegBlocks consecutive blocks.
+constexpr int mcu_blocks_per_mcu(int hs, int vs, int comps = 3) { return comps == 1 ? 1 : hs * vs + 2; }
+constexpr int mcu_seg_mcus(int hs, int vs, int comps = 3) { return kSegBlocks / mcu_blocks_per_mcu(hs, vs, comps); }     // 85 / 42 / 64, one component: 256 -- at most 256 blocks per segment
+static_assert(mcu_seg_mcus(1, 1, 1) == kSegBlocks, "a segment of a one-component scan is kSegBlocks blocks");
 static_assert(mcu_seg_mcus(1, 1) * 3 <= kSegBlocks && mcu_seg_mcus(2, 2) * 6 <= kSegBlocks && mcu_seg_mcus(2, 1) * 4 <= kSegBlocks &&
               kSegBlocks == kTileBlocks * kSegTiles, "a segment of MCUs fits seg_cap_words(kSegTiles)");
 //
@@ -410,6 +414,7 @@ struct McuSegArgs {
     SegArrays seg;                      // the interleaved path's own (words_stride = seg_cap_words(kSegTiles), or mcu_restart_cap_words); no group aggregates
     uint32_t *status;                   // ScanStats::status: bit 1 = a count that did not fit its 16 bits
     int32_t restart, segs_per_interval; // 0, 0: no restart intervals
+    int32_t comps;                      // components of the scan: 3, or 1 (hs = vs = 1, mx = bw, my = bh; cb_off, cr_off and huff_c are not read)
 };
 int launch_mcu_segments(const McuSegArgs &a, void *stream);
 // The writer of a file with restart intervals: two launches in place of k_finalize (which knows neither the 1-bit padding of an
@@ -464,17 +469,24 @@ int launch_mcu_histogram(const McuSegArgs &a, unsigned long long *counts, void *
 // carries it out.  A table's counts must sum to less than 2^54 (the merge key holds a count and a slot index in 64 bits).
 // Always: res [jobs][kHuffResBytes] -- BITS[16], the number of HUFFVAL bytes (u32 at 16), HUFFVAL at 32.
 // With `freq` (jpegamd_debug_optimal_huffman): job j reads freq + 256 j, 256 symbols, and nothing else is written.
-// Without: job 4 q + t reads picture q's counts, and the workgroup writes the picture's coder tables (tabs + q kMcuTabWords: [2][272],
-// unused symbols 0), its prefix (prefix + q kMcuPrefixSlot: hdr[0, head_len), the four DHT segments, hdr[tail_off, tail_off + tail_len))
-// and the prefix's length (prefix_len[q]).
+// Without: job tables q + t reads picture q's counts, and the workgroup writes the picture's coder tables (tabs + q kMcuTabWords: [2][272],
+// unused symbols 0), its prefix (prefix + q kMcuPrefixSlot: hdr[0, head_len), the `tables` DHT segments, hdr[tail_off, tail_off + tail_len))
+// and the prefix's length (prefix_len[q]).  The caller cuts the standard DHT segments out of hdr: head_len = tail_off - kStdDhtBytes[Gray].
 constexpr int kMcuTabWords = 2 * 272;
 constexpr int kMcuPrefixSlot = 704;     // >= kColorPrefixMax + DRI + SOS: an optimised prefix is never longer than the standard one
 constexpr int kHuffResBytes = 288;
 constexpr int kStdDhtBytes = 432;       // the four Annex K DHT segments: 2 x (33 + 183)
+constexpr int kStdDhtBytesGray = 216;   // the two of a one-component file: K.3 and K.5
+// A block coded with a picture's own tables is at most 27 + 63 x 26 bits (DC: 16 + 11, AC: 16 + 10): the strings reserved with
+// kMaxBlockBitsColor hold 256 of them.
+constexpr int kMaxBlockBitsOptimized = 27 + 63 * 26;                 // 1665
+static_assert(kMaxBlockBitsOptimized <= kMaxBlockBitsColor && (kSegBlocks * kMaxBlockBitsOptimized + 31) / 32 + 1 <= mcu_restart_cap_words(kSegBlocks),
+              "a segment of 256 blocks in either Huffman mode fits its string");
 struct HuffOptimalArgs {
     const unsigned long long *counts;   // [pictures][2][272], or null
     const unsigned long long *freq;     // [jobs][256], or null
     int32_t jobs;
+    int32_t tables;                     // with `counts`: tables per picture -- 4, or 2 (one component: luma DC and AC alone); jobs = tables x pictures
     uint8_t *res;
     uint32_t *tabs;
     uint8_t *prefix;

@@ -20,6 +20,9 @@
 // Per-picture optimised Huffman tables: k_mcu_histogram walks the coder's segments and counts every symbol,
 // k_huff_optimal makes each picture's four tables (T.81 K.2 as libjpeg carries it out), its coder tables and its prefix with its own
 // DHT segments; k_mcu_segments then codes with the picture's tables and the restart writer places the picture's prefix.
+// A scan of ONE component (the grayscale file with restart intervals and its own tables) is the kComps = 1
+// instantiation of both walks: the MCU is one block, a segment 256 consecutive blocks of one interval, the predictor the block in
+// front; no pad blocks, no chroma tables.  The three-component instantiations are what they were.
 #include <algorithm>
 
 #include <hip/hip_ext.h>
@@ -78,9 +81,18 @@ struct McuBlock { const uint4 *p; int pred; bool pad, chroma; };
 
 // Block j of MCU m of a picture whose planes start at `base`: where its coefficients lie, and its DC predictor -- 0 where the
 // component's previous block lies in front of MCU `mstart` (the scan's first MCU, or the first of m's restart interval).
+// kComps = 1 (a scan of ONE component): the MCU is one block, block m of the plane in raster order -- no pad
+// blocks, no chroma.
+template <int kComps>
 __device__ __forceinline__ McuBlock mcu_block(const McuSegArgs &a, const int16_t *base, int m, int j, int mstart) {
-    const int ny = a.hs * a.vs;
     McuBlock b;
+    if (kComps == 1) {
+        b.chroma = false; b.pad = false;
+        b.p = reinterpret_cast<const uint4 *>(base + (size_t)m * 64);
+        b.pred = m > mstart ? (int)base[(size_t)(m - 1) * 64] : 0;
+        return b;
+    }
+    const int ny = a.hs * a.vs;
     const auto y_at = [&](int mm, int jj, bool *pad) {           // Y block jj of MCU mm, clamped to the picture's blocks
         const int my_ = mm / a.mx, mx_ = mm - my_ * a.mx;
         const int v = jj / a.hs, u = jj - v * a.hs;
@@ -120,14 +132,15 @@ __device__ __forceinline__ McuRange mcu_range(const McuSegArgs &a, int sl) {
     return r;
 }
 
-template <bool kRestart>
+template <bool kRestart, int kComps>
 __global__ __launch_bounds__(64 * kWavesM) void k_mcu_segments(const McuSegArgs a) {
-    __shared__ uint32_t s_tab[2][272];
+    constexpr int kTabs = kComps == 1 ? 1 : 2;                     // one component: its two tables alone
+    __shared__ uint32_t s_tab[kTabs][272];
     __shared__ uint32_t s_win[kWavesM][kMcuWin + 2];
     const int lane = lane_id(), wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     {   // the tables of the workgroup's picture (its four segments are one picture's: num_segs_pad is a multiple of kWavesM)
         const size_t toff = a.huff_stride ? (size_t)(((int)blockIdx.x * kWavesM) / a.num_segs_pad) * a.huff_stride : 0;
-        for (int i = (int)threadIdx.x; i < 2 * 272; i += 64 * kWavesM) s_tab[i / 272][i % 272] = ((i < 272 ? a.huff_y : a.huff_c) + toff)[i % 272];
+        for (int i = (int)threadIdx.x; i < kTabs * 272; i += 64 * kWavesM) s_tab[i / 272][i % 272] = ((i < 272 ? a.huff_y : a.huff_c) + toff)[i % 272];
     }
     __syncthreads();                                               // (the only workgroup-wide meeting: every wave is on its own below)
     const int seg = (int)blockIdx.x * kWavesM + wave;
@@ -142,8 +155,8 @@ __global__ __launch_bounds__(64 * kWavesM) void k_mcu_segments(const McuSegArgs 
         return;
     }
     const int16_t *base = a.coef + (size_t)image * a.pic_stride;
-    const int bpm = a.hs * a.vs + 2;
-    const int nblk = nmcu * bpm;                                    // 3 .. 256
+    const int bpm = kComps == 1 ? 1 : a.hs * a.vs + 2;
+    const int nblk = nmcu * bpm;                                    // 3 .. 256 (one component: 1 .. 256)
     uint32_t *win = s_win[wave];
 
     // ---- pass 1: bit lengths, then the blocks' places ----
@@ -155,10 +168,10 @@ __global__ __launch_bounds__(64 * kWavesM) void k_mcu_segments(const McuSegArgs 
         len[r] = 0u; pred[r] = 0;
         if (k < nblk) {
             const int mi = k / bpm;
-            const McuBlock b = mcu_block(a, base, m0 + mi, k - mi * bpm, mstart);
+            const McuBlock b = mcu_block<kComps>(a, base, m0 + mi, k - mi * bpm, mstart);
             pred[r] = b.pred;
             uint32_t n = 0;
-            mcu_walk_block(b.p, b.pad, b.pred, s_tab[b.chroma ? 1 : 0], [&](uint32_t, uint32_t c) { n += c; ++nsym; });
+            mcu_walk_block(b.p, b.pad, b.pred, s_tab[kTabs > 1 && b.chroma ? 1 : 0], [&](uint32_t, uint32_t c) { n += c; ++nsym; });
             len[r] = n;
         }
     }
@@ -186,9 +199,9 @@ __global__ __launch_bounds__(64 * kWavesM) void k_mcu_segments(const McuSegArgs 
             const int k = r * 64 + lane;
             if (k < nblk && off[r] < hi_bit && off[r] + len[r] > lo_bit) {
                 const int mi = k / bpm;
-                const McuBlock b = mcu_block(a, base, m0 + mi, k - mi * bpm, mstart);
+                const McuBlock b = mcu_block<kComps>(a, base, m0 + mi, k - mi * bpm, mstart);
                 uint32_t pos = off[r];
-                mcu_walk_block(b.p, b.pad, pred[r], s_tab[b.chroma ? 1 : 0], [&](uint32_t sym, uint32_t n) {
+                mcu_walk_block(b.p, b.pad, pred[r], s_tab[kTabs > 1 && b.chroma ? 1 : 0], [&](uint32_t sym, uint32_t n) {
                     if (n == 0u) return;
                     const unsigned long long s64 = ((unsigned long long)sym << (64u - n)) >> (pos & 31u);   // left-aligned at the bit's place in a word pair
                     const uint32_t j = (pos >> 5) - wbase;          // (wraps for a word in front of the window)
@@ -223,9 +236,11 @@ __global__ __launch_bounds__(64 * kWavesM) void k_mcu_segments(const McuSegArgs 
         const uint32_t p = seg_bits & 31u;
         const uint32_t tail = p ? ((tail_last << p) | (tail_part >> (32u - p))) : tail_last;
         if (lane == 0) {
-            // first 8 bits | last 7 bits.  With the Annex K tables a segment is never shorter than 14 bits; with a picture's own
-            // tables an interval's (the scan's) last segment may be as short as 6: its bits then stand at the left of the 8 and at the
-            // right of the 7, zeros elsewhere (the window's).  The readers that take that into account: mcu_tail7, fin_owned_ff.
+            // first 8 bits | last 7 bits.  With the Annex K tables a three-component segment is never shorter than 14 bits; with a
+            // picture's own tables, or one component, an interval's (the scan's) last segment may be shorter than 8 -- one block of one
+            // component is 6 bits with the Annex K tables and as little as 2 with its own: its bits then stand at the left of the 8 and
+            // at the right of the 7, zeros elsewhere (the window's; p = seg_bits, tail_last = 0 above).  The readers that take that into
+            // account: mcu_tail7, fin_owned_ff; rst_tail and the writer's `lead` bits read what mcu_tail7 and a FULL segment in front give.
             a.seg.edge[seg] = ((first_word >> 24) << 8) | (tail & 0x7Fu);
             a.seg.bits[seg] = seg_bits;
             a.seg.syms[seg] = seg_syms;
@@ -245,15 +260,19 @@ __global__ __launch_bounds__(64 * kWavesM) void k_mcu_segments(const McuSegArgs 
 }
 
 // What both walks of the coefficients need of their arguments: every MCU lies in a segment, and the widest segment fits its reservation.
+// A scan of one component (comps = 1): the MCU grid is the block grid, and a segment is kSegBlocks blocks.
 static bool mcu_seg_args_ok(const McuSegArgs &a) {
-    if (a.seg_mcus < 1 || a.seg_mcus * (a.hs * a.vs + 2) > kSegBlocks || a.num_segs_pad % kSegGroup != 0 || a.num_segs > a.num_segs_pad)
+    if (a.comps != 1 && a.comps != 3) return false;
+    if (a.comps == 1 && (a.hs != 1 || a.vs != 1 || a.mx != a.bw || a.my != a.bh || a.seg_mcus != kSegBlocks)) return false;
+    const int bpm = mcu_blocks_per_mcu(a.hs, a.vs, a.comps);
+    if (a.seg_mcus < 1 || a.seg_mcus * bpm > kSegBlocks || a.num_segs_pad % kSegGroup != 0 || a.num_segs > a.num_segs_pad)
         return false;
     static_assert(kSegGroup % kWavesM == 0, "a workgroup's segments belong to one picture");
     const int64_t mcus = (int64_t)a.mx * a.my;
     if (a.restart == 0) return (int64_t)a.num_segs * a.seg_mcus >= mcus;
     const int64_t spi = a.segs_per_interval, in_interval = std::min<int64_t>(a.restart, mcus);
     return !(a.restart < 0 || spi < 1 || spi * a.seg_mcus < in_interval || (int64_t)a.num_segs < (mcus + a.restart - 1) / a.restart * spi ||
-             (int64_t)mcu_restart_cap_words((int)std::min<int64_t>(a.restart, a.seg_mcus) * (a.hs * a.vs + 2)) > (int64_t)a.seg.words_stride);
+             (int64_t)mcu_restart_cap_words((int)std::min<int64_t>(a.restart, a.seg_mcus) * bpm) > (int64_t)a.seg.words_stride);
 }
 
 int launch_mcu_segments(const McuSegArgs &a, void *stream) {
@@ -261,8 +280,9 @@ int launch_mcu_segments(const McuSegArgs &a, void *stream) {
     if (n <= 0) return 0;
     if (!mcu_seg_args_ok(a)) return (int)hipErrorInvalidValue;
     const dim3 grid((unsigned)((n + kWavesM - 1) / kWavesM)), block(64 * kWavesM);
-    if (a.restart == 0) hipLaunchKernelGGL(k_mcu_segments<false>, grid, block, 0, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL(k_mcu_segments<true>, grid, block, 0, (hipStream_t)stream, a);
+    const auto kernel = a.comps == 1 ? (a.restart == 0 ? k_mcu_segments<false, 1> : k_mcu_segments<true, 1>)
+                                     : (a.restart == 0 ? k_mcu_segments<false, 3> : k_mcu_segments<true, 3>);
+    hipLaunchKernelGGL(kernel, grid, block, 0, (hipStream_t)stream, a);
     return (int)hipGetLastError();
 }
 
@@ -301,7 +321,7 @@ __device__ __forceinline__ void mcu_count_block(const uint4 *__restrict__ p, boo
 // adds, nobody else writes there -- and only the rest to the shared table with atomics.  The columns are summed over the wave at the end.
 constexpr int kHotRows = 28;                    // 16 AC symbols (run << 2 | size - 1), then DC sizes 0 .. 11 at 16 + size
 __device__ __forceinline__ uint32_t mcu_hot_symbol(int row) { return row < 16 ? (uint32_t)(((row >> 2) << 4) | ((row & 3) + 1)) : 256u + (uint32_t)(row - 16); }
-template <bool kRestart>
+template <bool kRestart, int kComps>
 __global__ __launch_bounds__(64 * kWavesM) void k_mcu_histogram(const McuSegArgs a, unsigned long long *__restrict__ counts) {
     __shared__ uint32_t s_cnt[2][272];                             // (a workgroup walks at most 4 x 256 blocks of 64 symbols: 32 bits hold it)
     __shared__ uint16_t s_hot[kWavesM][2][kHotRows][64];
@@ -314,14 +334,14 @@ __global__ __launch_bounds__(64 * kWavesM) void k_mcu_histogram(const McuSegArgs
     if (seg < a.batch * a.num_segs_pad) {
         const McuRange rg = mcu_range<kRestart>(a, seg - image * a.num_segs_pad);
         const int16_t *base = a.coef + (size_t)image * a.pic_stride;
-        const int bpm = a.hs * a.vs + 2, nblk = rg.nmcu * bpm;      // 0 (EMPTY: nothing counted), 3 .. 256
+        const int bpm = kComps == 1 ? 1 : a.hs * a.vs + 2, nblk = rg.nmcu * bpm;      // 0 (EMPTY: nothing counted), 3 .. 256 (one component: 1 .. 256)
         uint32_t dc0_y = 0, dc0_c = 0, eob_y = 0, eob_c = 0;
 #pragma unroll 1
         for (int r = 0; r < 4; ++r) {
             const int k = r * 64 + lane;
             if (k < nblk) {
                 const int mi = k / bpm;
-                const McuBlock b = mcu_block(a, base, rg.m0 + mi, k - mi * bpm, rg.mstart);
+                const McuBlock b = mcu_block<kComps>(a, base, rg.m0 + mi, k - mi * bpm, rg.mstart);
                 uint32_t *const cnt = s_cnt[b.chroma ? 1 : 0];
                 uint16_t *const hot = &s_hot[wave][b.chroma ? 1 : 0][0][lane];
                 uint32_t d = 0, e = 0;
@@ -363,8 +383,9 @@ int launch_mcu_histogram(const McuSegArgs &a, unsigned long long *counts, void *
     if (n <= 0) return 0;
     if (!counts || !mcu_seg_args_ok(a)) return (int)hipErrorInvalidValue;
     const dim3 grid((unsigned)((n + kWavesM - 1) / kWavesM)), block(64 * kWavesM);
-    if (a.restart == 0) hipLaunchKernelGGL(k_mcu_histogram<false>, grid, block, 0, (hipStream_t)stream, a, counts);
-    else hipLaunchKernelGGL(k_mcu_histogram<true>, grid, block, 0, (hipStream_t)stream, a, counts);
+    const auto kernel = a.comps == 1 ? (a.restart == 0 ? k_mcu_histogram<false, 1> : k_mcu_histogram<true, 1>)
+                                     : (a.restart == 0 ? k_mcu_histogram<false, 3> : k_mcu_histogram<true, 3>);
+    hipLaunchKernelGGL(kernel, grid, block, 0, (hipStream_t)stream, a, counts);
     return (int)hipGetLastError();
 }
 
@@ -389,6 +410,7 @@ __device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v)
 }
 
 // Wave w of a workgroup: table w of its picture (0 luma DC, 1 luma AC, 2 chroma DC, 3 chroma AC), or job 4 g + w of a debug call.
+// A picture of one component has the first two tables alone (HuffOptimalArgs::tables = 2): waves 2 and 3 then have no job.
 // The 257 slots of K.2 -- 256 symbols and the reserved point -- lie over the lanes, slot s in lane s & 63: count, tree id (its root's
 // slot) and depth.  Only a tree's root has a non-zero count (every other member was a c2 once), so "the root with the least count,
 // the highest index among equals" is the minimum of (count << 9 | 511 - slot) over the non-zero counts: one merge is two such
@@ -399,8 +421,9 @@ __global__ __launch_bounds__(256) void k_huff_optimal(const HuffOptimalArgs a) {
     __shared__ uint32_t s_first[4][18], s_cum[4][18];              // by final length: the first code word, the HUFFVAL places in front of and at it
     __shared__ uint8_t s_vals[4][256];
     const int tid = (int)threadIdx.x, lane = lane_id(), w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int g = (int)blockIdx.x, job = 4 * g + w;
-    const bool active = job < a.jobs;
+    const int ntab = a.freq ? 4 : a.tables;                        // jobs of a workgroup
+    const int g = (int)blockIdx.x, job = ntab * g + w;
+    const bool active = w < ntab && job < a.jobs;
     const int nsym = a.freq ? 256 : ((w & 1) ? 256 : 16);
     const unsigned long long *src = a.freq ? a.freq + (size_t)job * 256 : a.counts + (size_t)g * kMcuTabWords + (size_t)(w >> 1) * 272 + ((w & 1) ? 0 : 256);
     constexpr unsigned long long kNone = ~0ull;
@@ -494,22 +517,22 @@ __global__ __launch_bounds__(256) void k_huff_optimal(const HuffOptimalArgs a) {
     if (a.freq) return;                                            // (the same for the whole launch)
     uint32_t *const tab = a.tabs + (size_t)g * kMcuTabWords + (size_t)(w >> 1) * 272 + ((w & 1) ? 0 : 256);
 #pragma unroll
-    for (int r = 0; r < 4; ++r) if (lane + 64 * r < nsym) tab[lane + 64 * r] = word[r];
-    __syncthreads();                                               // the four tables' sizes place the four DHT segments
+    for (int r = 0; r < 4; ++r) if (active && lane + 64 * r < nsym) tab[lane + 64 * r] = word[r];
+    __syncthreads();                                               // the tables' sizes place the DHT segments
     uint8_t *const out = a.prefix + (size_t)g * kMcuPrefixSlot;
     uint32_t at = (uint32_t)a.head_len, end = (uint32_t)a.head_len;
-    for (int t = 0; t < 4; ++t) {
+    for (int t = 0; t < ntab; ++t) {
         const uint32_t len = 21u + min(s_cum[t][16], 256u);
         if (t < w) at += len;
         end += len;
     }
     const auto put = [&](uint32_t pos, uint8_t v) { if (pos < (uint32_t)kMcuPrefixSlot) out[pos] = v; };   // (a picture of this coder's coefficients never comes near the slot's end)
-    if (lane == 0) {
+    if (active && lane == 0) {
         put(at, 0xFF); put(at + 1, 0xC4); put(at + 2, (uint8_t)((19u + nvals) >> 8)); put(at + 3, (uint8_t)(19u + nvals));
         put(at + 4, (uint8_t)(((w & 1) << 4) | (w >> 1)));
     }
-    if (lane < 16) put(at + 5 + lane, (uint8_t)n[lane + 1]);
-    for (uint32_t i = (uint32_t)lane; i < nvals; i += 64u) put(at + 21 + i, s_vals[w][i]);
+    if (active && lane < 16) put(at + 5 + lane, (uint8_t)n[lane + 1]);
+    for (uint32_t i = (uint32_t)lane; active && i < nvals; i += 64u) put(at + 21 + i, s_vals[w][i]);
     for (int i = tid; i < a.head_len; i += 256) put((uint32_t)i, a.hdr[i]);
     for (int i = tid; i < a.tail_len; i += 256) put(end + (uint32_t)i, a.hdr[a.tail_off + i]);
     if (tid == 0) a.prefix_len[g] = min(end + (uint32_t)a.tail_len, (uint32_t)kMcuPrefixSlot);
@@ -517,10 +540,11 @@ __global__ __launch_bounds__(256) void k_huff_optimal(const HuffOptimalArgs a) {
 
 int launch_huff_optimal(const HuffOptimalArgs &a, void *stream) {
     if (a.jobs < 1 || (!a.freq) == (!a.counts) || (a.freq && !a.res)) return (int)hipErrorInvalidValue;
-    if (a.counts && (a.jobs % 4 != 0 || !a.tabs || !a.prefix || !a.prefix_len || !a.hdr || a.head_len < 0 || a.tail_len < 0 || a.tail_off < a.head_len ||
+    if (a.counts && ((a.tables != 2 && a.tables != 4) || a.jobs % a.tables != 0 || !a.tabs || !a.prefix || !a.prefix_len || !a.hdr || a.head_len < 0 || a.tail_len < 0 || a.tail_off < a.head_len ||
                      a.head_len + a.tail_len > kMcuPrefixSlot))
         return (int)hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_huff_optimal, dim3((unsigned)((a.jobs + 3) / 4)), dim3(256), 0, (hipStream_t)stream, a);
+    const int per_wg = a.freq ? 4 : a.tables;
+    hipLaunchKernelGGL(k_huff_optimal, dim3((unsigned)((a.jobs + per_wg - 1) / per_wg)), dim3(256), 0, (hipStream_t)stream, a);
     return (int)hipGetLastError();
 }
 
@@ -536,9 +560,10 @@ constexpr int kRstStripWords = 132;             // k_mcu_restart_write: a wave's
 // last 7 bits of the segment are in `edge`) -- filled up with ones, and stuffed when that makes it 0xFF, in front of RSTn; filled
 // up with zeros in front of EOI -- and the two marker bytes.
 struct RstTail { uint32_t r, byte, bytes, pad_ff; };
-// The last 7 bits of an interval whose last segment has `bits` bits: that segment's, or -- it is shorter (a picture's own tables: one
-// MCU may be 6 bits) -- the bits in front of them from the segment in front, which is a full run of MCUs and never that short.  (An
-// interval's first segment has nothing in front: r <= bits there, and the bits taken from edge_prev are never looked at.)
+// The last 7 bits of an interval whose last segment has `bits` bits: that segment's, or -- it is shorter, 1 .. 6 bits (a picture's own
+// tables, or one component: one MCU may be 2 bits) -- the bits in front of them from the segment in front, which is a full run of MCUs
+// (at least 512 bits) and never that short.  (An interval's first segment has nothing in front: r <= bits there, and the bits taken
+// from edge_prev are never looked at.)
 __device__ __forceinline__ uint32_t mcu_tail7(uint32_t edge, uint32_t bits, uint32_t edge_prev) {
     return bits >= 7u ? edge & 0x7Fu : (((edge_prev & 0x7Fu) << bits) | (edge & ((1u << bits) - 1u))) & 0x7Fu;
 }
@@ -678,7 +703,7 @@ __global__ __launch_bounds__(64 * kWavesM) void k_mcu_restart_write(const McuRes
     const uint32_t bits = a.seg.bits[seg], edge = a.seg.edge[seg], b0 = a.b0[seg], my_ff = a.ff[seg];
     const uint32_t lead = b0 & 7u;                                  // bits of the segment in front that its first byte begins with (0 for k = 0)
     const uint32_t edge_prev = sl > 0 ? a.seg.edge[seg - 1] : 0u;
-    const uint32_t leadbits = lead ? (edge_prev & ((1u << lead) - 1u)) : 0u;   // (lead > 0: the segment in front is a full run of MCUs -- never shorter than 7 bits)
+    const uint32_t leadbits = lead ? (edge_prev & ((1u << lead) - 1u)) : 0u;   // (lead > 0: the segment in front is a full run of MCUs -- never shorter than 7 bits; this one may be 2)
     const uint32_t nown = ((b0 + bits) >> 3) - (b0 >> 3);
     const bool last = sl == a.last_seg, tail = last || (k == a.segs_per_interval - 1 && iv < a.intervals - 1);
     const RstTail t = rst_tail(b0 + bits, mcu_tail7(edge, bits, edge_prev), last);

@@ -134,6 +134,8 @@ def _load() -> C.CDLL:
         "jpegamd_encoder_set_huffman": (i32, [vp, i32]),
         "jpegamd_debug_optimal_huffman": (i32, [vp, vp, i32, vp, vp, vp]),
         "jpegamd_debug_huffman_counts": (i32, [vp, vp]),
+        "jpegamd_encode_gray_scan_batch_async": (i32, [vp, C.POINTER(Image), i32, i32, C.POINTER(C.c_void_p), u64, C.POINTER(C.c_void_p), vp]),
+        "jpegamd_max_jfif_bytes_gray_scan": (u64, [i32, i32, i32]),
         "jpegamd_debug_matrix_coeffs": (i32, [i32, vp]),
         "jpegamd_debug_ycbcr_matrix_planes": (i32, [vp, C.POINTER(YCbCrImage), i32, i32, i32, i32, i32, vp, vp, vp, vp]),
         "jpegamd_debug_chroma_groups": (i32, [i32, i32, i32, i32, i32, i32, i32, vp]),
@@ -159,7 +161,8 @@ def _load() -> C.CDLL:
                     "jpegamd_max_jfif_bytes_interleaved_restart", "jpegamd_encode_ycbcr_interleaved_matrix_batch_async",
                     "jpegamd_encode_color_interleaved_pixels_batch_async", "jpegamd_encode_planar_interleaved_batch_async",
                     "jpegamd_debug_tile_variant", "jpegamd_encoder_set_huffman", "jpegamd_debug_optimal_huffman",
-                    "jpegamd_debug_huffman_counts") and os.environ.get("JPEGAMD_LIB") and not hasattr(lib, name):
+                    "jpegamd_debug_huffman_counts", "jpegamd_encode_gray_scan_batch_async",
+                    "jpegamd_max_jfif_bytes_gray_scan") and os.environ.get("JPEGAMD_LIB") and not hasattr(lib, name):
             continue                                              # (A/B tooling: a variant build of an older round)
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = res, args
@@ -181,7 +184,8 @@ EXPORTED = ("jpegamd_encoder_create jpegamd_encoder_destroy jpegamd_max_jfif_byt
             "jpegamd_encode_color_interleaved_restart_batch_async jpegamd_encode_ycbcr_interleaved_restart_batch_async "
             "jpegamd_max_jfif_bytes_interleaved_restart jpegamd_encode_ycbcr_interleaved_matrix_batch_async "
             "jpegamd_encode_color_interleaved_pixels_batch_async jpegamd_encode_planar_interleaved_batch_async "
-            "jpegamd_encoder_set_huffman jpegamd_debug_optimal_huffman jpegamd_debug_huffman_counts").split()
+            "jpegamd_encoder_set_huffman jpegamd_debug_optimal_huffman jpegamd_debug_huffman_counts "
+            "jpegamd_encode_gray_scan_batch_async jpegamd_max_jfif_bytes_gray_scan").split()
 
 
 def quant_table(quality: int = 50):
@@ -310,6 +314,11 @@ def max_jfif_bytes_interleaved_restart(width: int, height: int, subsampling: int
     return int(lib.jpegamd_max_jfif_bytes_interleaved_restart(width, height, subsampling, restart_interval))
 
 
+def max_jfif_bytes_gray_scan(width: int, height: int, restart_interval: int = 0) -> int:
+    """Upper bound on the bytes of a grayscale file of jpegamd_encode_gray_scan_batch_async, in either Huffman mode; 0 for bad arguments."""
+    return int(lib.jpegamd_max_jfif_bytes_gray_scan(width, height, restart_interval))
+
+
 SCANS = ("separate", "interleaved")
 HUFFMAN_STANDARD, HUFFMAN_OPTIMIZED = 0, 1       # jpegamd_encoder_set_huffman
 HUFFMANS = ("standard", "optimized")
@@ -357,6 +366,18 @@ def encode_bmp_bytes_color(bmp: bytes, quality: int = 0, subsampling: int = SUBS
 
 
 _tensor_encoders = {}
+
+
+def _tensor_encoder(dev: int, w: int, rows: int):
+    """The per-device context of the tensor functions, grown (a new one made) when a call needs more than w x rows."""
+    enc, mw, mh = _tensor_encoders.get(dev, (None, 0, 0))
+    if enc is None or w > mw or rows > mh:
+        mw, mh = max(w, mw), max(rows, mh)
+        if enc is not None:
+            enc.close()
+        enc = Encoder(mw, mh)
+        _tensor_encoders[dev] = (enc, mw, mh)
+    return enc
 
 
 def encode_tensor(t, quality: int = 0, subsampling: int = SUBSAMPLE_420, layout=None, scan: str = "separate", restart_interval=None) -> bytes:
@@ -549,13 +570,7 @@ def encode_tensor_batch(t, quality: int = 0, subsampling: int = SUBSAMPLE_420, l
     with torch.cuda.device(dev):
         per = min(n, MAX_BATCH)
         rows = per * ((h + 7) // 8 * 8)              # a batch needs `per` x the block rows of one picture
-        enc, mw, mh = _tensor_encoders.get(dev, (None, 0, 0))
-        if enc is None or w > mw or rows > mh:
-            mw, mh = max(w, mw), max(rows, mh)
-            if enc is not None:
-                enc.close()
-            enc = Encoder(mw, mh)
-            _tensor_encoders[dev] = (enc, mw, mh)
+        enc = _tensor_encoder(dev, w, rows)
         cap = max_jfif_bytes(w, h) if gray else max_jfif_bytes_color(w, h, subsampling)
         if interleaved:
             cap = max_jfif_bytes_interleaved_restart(w, h, subsampling, ri) if ri else max_jfif_bytes_interleaved(w, h, subsampling)
@@ -606,6 +621,42 @@ def _interleaved_call(enc, order, any_layout, ptr, b0, k, w, h, stride, quality,
     if any_layout:
         return enc.encode_color_interleaved_pixels_batch_async(imgs, subsampling, ri, outs, cap, size_ptrs, stream)
     return enc.encode_color_interleaved_restart_batch_async(imgs, subsampling, ri, outs, cap, size_ptrs, stream)
+
+
+def _encode_gray_scan_batch(t, quality, restart_interval, huffman, name: str) -> list:
+    """jpegamd.mjpeg.encode_gray_batch: [N, H, W] uint8 on a device -> N grayscale files through jpegamd_encode_gray_scan_batch_async.
+    Every argument is checked on the CPU before any device work."""
+    import torch
+    huff = _huffman(huffman)
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != 3 or min(t.shape) < 1:
+        raise ValueError(f"{name} needs a uint8 tensor [N, H, W]")
+    n, h, w = (int(x) for x in t.shape)
+    if w > 65535 or h > 65535:
+        raise ValueError(f"{name}: a picture is at most 65535 x 65535")
+    if t.stride(2) != 1 or t.stride(1) < w:
+        raise ValueError(f"{name} needs pictures packed within a row (a row stride is fine)")
+    ri = _restart(restart_interval, True, w, SUBSAMPLE_444)            # ("row": ceil(W / 8) -- the MCU is one block)
+    if not t.is_cuda:
+        raise ValueError(f"{name} needs a device tensor")
+    device = t.device
+    dev = device.index if device.index is not None else torch.cuda.current_device()
+    files = []
+    with torch.cuda.device(dev):
+        per = min(n, MAX_BATCH)
+        rows = per * ((h + 7) // 8 * 8)
+        enc = _tensor_encoder(dev, w, rows)
+        cap = max_jfif_bytes_gray_scan(w, h, ri)
+        out = torch.empty((per, cap), dtype=torch.uint8, device=device)
+        sizes = torch.zeros(per, dtype=torch.int64, device=device)
+        stream = torch.cuda.current_stream(device).cuda_stream
+        for b0 in range(0, n, MAX_BATCH):
+            k = min(MAX_BATCH, n - b0)
+            outs = [out[i].data_ptr() for i in range(k)]
+            size_ptrs = [sizes.data_ptr() + 8 * i for i in range(k)]
+            imgs = [Encoder.image(t[b0 + i].data_ptr(), w, h, t.stride(1), bottom_up=False, channel_order=ORDER_GRAY, quality=quality)
+                    for i in range(k)]
+            files += _with_huffman(enc, huff, lambda: enc.encode_gray_scan_batch_async(imgs, ri, outs, cap, size_ptrs, stream), out, sizes, k)
+    return files
 
 
 def _with_huffman(enc, huffman: int, queue, out, sizes, k: int) -> list:
@@ -742,13 +793,7 @@ def _encode_ycbcr_images(device, n, h, w, subsampling, image, sample_range: int 
     with torch.cuda.device(dev):
         per = min(n, MAX_BATCH)
         rows = per * ((h + 7) // 8 * 8)              # a batch needs `per` x the block rows of one picture
-        enc, mw, mh = _tensor_encoders.get(dev, (None, 0, 0))
-        if enc is None or w > mw or rows > mh:
-            mw, mh = max(w, mw), max(rows, mh)
-            if enc is not None:
-                enc.close()
-            enc = Encoder(mw, mh)
-            _tensor_encoders[dev] = (enc, mw, mh)
+        enc = _tensor_encoder(dev, w, rows)
         cap = max_jfif_bytes_interleaved(w, h, subsampling) if interleaved else max_jfif_bytes_color(w, h, subsampling)
         if restart:
             cap = max_jfif_bytes_interleaved_restart(w, h, subsampling, restart)
@@ -1103,6 +1148,18 @@ class Encoder:
         rc = lib.jpegamd_encode_batch_async(self._h, arr, n, outs, out_cap, sizes, 1 if with_container else 0, C.c_void_p(stream))
         if rc:
             raise JpegAmdError(rc, "jpegamd_encode_batch_async")
+
+    def encode_gray_scan_batch_async(self, imgs, restart_interval: int, out_ptrs, out_cap: int, size_ptrs, stream: int = 0):
+        """The grayscale files of `len(imgs)` pictures of one geometry (<= MAX_BATCH; any channel order: the luma) with restart
+        intervals of `restart_interval` blocks (0: none) and the context's Huffman tables (set_huffman)
+        (jpegamd_encode_gray_scan_batch_async); out_cap from max_jfif_bytes_gray_scan."""
+        n = len(imgs)
+        arr = (Image * n)(*imgs)
+        outs = (C.c_void_p * n)(*[C.c_void_p(p) for p in out_ptrs])
+        sizes = (C.c_void_p * n)(*[C.c_void_p(p) for p in size_ptrs])
+        rc = lib.jpegamd_encode_gray_scan_batch_async(self._h, arr, n, int(restart_interval), outs, out_cap, sizes, C.c_void_p(stream))
+        if rc:
+            raise JpegAmdError(rc, "jpegamd_encode_gray_scan_batch_async")
 
     # ---- one image sharded over GPUs by block rows (include/jpeg_compression.h) ----
     def encode_rows_async(self, img: Image, row_begin: int, row_end: int, stream: int = 0):

@@ -9,7 +9,10 @@ matrix pass of the three-scan path).
 
 huffman= "standard" (the Annex K tables, default) or "optimized": four tables made for each picture from its own symbol counts, as
 libjpeg -optimize makes them -- the same pixels in a smaller file.  The mode is set on the per-device context for the
-call and STANDARD is put back behind it."""
+call and STANDARD is put back behind it.
+
+encode_gray_batch / encode_gray: GRAYSCALE pictures with the same two options -- the grayscale file written as a scan of one component
+(DESIGN.md 4.6.11), two tables per picture in "optimized"."""
 from __future__ import annotations
 
 import jpegamd as _j
@@ -77,3 +80,19 @@ def encode_tensor(t, quality: int = 0, subsampling: int = _j.SUBSAMPLE_420, layo
     """One colour picture -> its one-scan file: [H, W, 3], or layout= "chw" [3, H, W], "rgba" / "bgra" [H, W, 4], "hwc"."""
     return _j.encode_tensor_batch(t, quality, subsampling, "hwc" if layout is None else layout, _single=True, scan="interleaved",
                                   restart_interval=restart_interval, _any_layout=True, _huffman=_j._huffman(huffman))[0]
+
+
+def encode_gray_batch(t, quality: int = 0, restart_interval=None, huffman: str = "standard") -> list:
+    """Grayscale pictures, a uint8 device tensor [N, H, W] (row-strided, packed within a row) -> N grayscale files with restart
+    intervals and the chosen tables (jpegamd_encode_gray_scan_batch_async).  restart_interval: None / 0, an int
+    1 .. 65535 (blocks: the MCU of a grayscale scan is one block), or "row" = ceil(W / 8).  Without intervals and with the standard
+    tables the files are jpegamd.encode_tensor_batch's.  Bad values are ValueErrors, raised before any device work."""
+    return _j._encode_gray_scan_batch(t, quality, restart_interval, huffman, "encode_gray_batch")
+
+
+def encode_gray(t, quality: int = 0, restart_interval=None, huffman: str = "standard") -> bytes:
+    """One grayscale picture [H, W] -> its file, as encode_gray_batch."""
+    import torch
+    if not isinstance(t, torch.Tensor) or t.dim() != 2:
+        raise ValueError("encode_gray needs a uint8 tensor [H, W]")
+    return _j._encode_gray_scan_batch(t.unsqueeze(0), quality, restart_interval, huffman, "encode_gray")[0]

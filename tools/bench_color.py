@@ -50,6 +50,11 @@ frames once, outside the timed loop, and codes the mapped frames at full range: 
 --huffman standard|optimized (with --scan interleaved alone): the Annex K tables, or per-picture optimised tables
 (jpegamd_encoder_set_huffman on the context); the line then carries "huffman".  `standard` sets nothing on the
 context, so a library from before the mode serves it.
+
+--scan gray (with --batch N, default 8) times GRAYSCALE files through jpegamd_encode_gray_scan_batch_async: the luma
+of the same --size pictures, --restart N|row in blocks (`row`: ceil(W / 8)), --huffman standard|optimized; the whole call is timed
+(ns_total).  Without --restart (or with 0) and with the standard tables the entry is jpegamd_encode_batch_async, so that line is the
+fused grayscale path's time; "plain_us_per_picture" is jpegamd_encode_batch_async itself, timed in the same run.
 """
 from __future__ import annotations
 
@@ -86,8 +91,9 @@ def main() -> None:
     ap.add_argument("--layout", choices=("hwc", "chw", "rgba"), default=None, help="device tensors stored this way, read where they lie")
     ap.add_argument("--rounds", type=int, default=5, help="--layout: medians taken (each of --steps calls)")
     ap.add_argument("--repack", action="store_true", help="--layout chw: also time permute + packed encode")
-    ap.add_argument("--scan", choices=("separate", "interleaved"), default="separate",
-                    help="interleaved: the batch loop goes through the one-scan entries (every --source, --range, --matrix; --layout chw / rgba)")
+    ap.add_argument("--scan", choices=("separate", "interleaved", "gray"), default="separate",
+                    help="interleaved: the batch loop goes through the one-scan entries (every --source, --range, --matrix; --layout chw / rgba); "
+                    "gray: grayscale files through jpegamd_encode_gray_scan_batch_async (--batch, --restart, --huffman)")
     ap.add_argument("--mapped", action="store_true",
                     help="--range limited (i420, nv12, i422): map the frames once outside the timed loop and code them at full range")
     ap.add_argument("--huffman", choices=("standard", "optimized"), default=None,
@@ -122,13 +128,18 @@ def main() -> None:
         sys.exit("--convert and --narrow time routes of the three-scan path: not with --scan interleaved")
     if a.mapped and (a.sample_range != "limited" or any(s not in ("i420", "nv12", "i422") for s in sources)):
         sys.exit("--mapped needs --range limited and takes --source i420, nv12, i422")
-    if a.huffman is not None and a.scan != "interleaved":
-        sys.exit("--huffman needs --scan interleaved")
+    if a.huffman is not None and a.scan == "separate":
+        sys.exit("--huffman needs --scan interleaved or gray")
     if a.restart is not None:
-        if a.scan != "interleaved":
-            sys.exit("--restart needs --scan interleaved")
+        if a.scan == "separate":
+            sys.exit("--restart needs --scan interleaved or gray")
         if a.restart != "row" and not (a.restart.isdigit() and int(a.restart) <= 65535):
             sys.exit("--restart takes a number of MCUs, 0 .. 65535, or `row`")
+    if a.scan == "gray":
+        if sources != ["rgb"] or a.layout is not None or a.convert or a.narrow or a.mapped or a.subsampling:
+            sys.exit("--scan gray takes --size, --batch, --restart, --huffman, --quality, --kind alone")
+        run_gray(a, jpegamd, torch, dev)
+        return
     if a.layout is not None:
         run_layout(a, jpegamd, torch, dev)
         return
@@ -190,6 +201,48 @@ def ycbcr_420(torch, px, w, h, stride):
     cb = box((32768 - 43 * r - 85 * g + 128 * b) >> 8)
     cr = box((32768 + 128 * r - 107 * g - 21 * b) >> 8)
     return y, cb, cr
+
+
+def run_gray(a, jpegamd, torch, dev) -> None:
+    """--scan gray: N pictures per call through jpegamd_encode_gray_scan_batch_async, and through jpegamd_encode_batch_async."""
+    w = h = a.size
+    n = a.batch or 8
+    pxs, descs = [], []
+    for i in range(n):
+        bmp = jpegamd.synth_bmp(w, h, 1 + i, a.kind, 0)
+        img, off = jpegamd.parse_bmp(bmp)
+        pxs.append(torch.frombuffer(bytearray(bmp[off:off + img.row_stride * h]), dtype=torch.uint8).to(dev))
+        descs.append(jpegamd.Encoder.image(pxs[-1].data_ptr(), w, h, img.row_stride, True, jpegamd.ORDER_BGR, a.quality))
+        del bmp
+    enc = jpegamd.Encoder(w, n * h)
+    restart = 0 if a.restart is None else (-(-w // 8) if a.restart == "row" else int(a.restart))
+    cap = max(jpegamd.max_jfif_bytes_gray_scan(w, h, restart), jpegamd.max_jfif_bytes(w, h))
+    outs = [torch.empty(cap, dtype=torch.uint8, device=dev) for _ in range(n)]
+    sizes = torch.zeros(n, dtype=torch.int64, device=dev)
+    out_ptrs = [o.data_ptr() for o in outs]
+    size_ptrs = [sizes.data_ptr() + 8 * i for i in range(n)]
+    stream = torch.cuda.current_stream().cuda_stream
+
+    def timed(call):
+        for _ in range(a.warmup):
+            call()
+        enc.finish()
+        enc.set_profiling(a.steps)
+        for _ in range(a.steps):
+            call()
+        st = enc.finish()
+        totals = [enc.profile(i).ns_total for i in range(a.steps)]
+        enc.set_profiling(0)
+        return statistics.median(totals), st, sizes.cpu().tolist()
+
+    plain, _, plain_bytes = timed(lambda: enc.encode_batch_async(descs, out_ptrs, cap, size_ptrs, True, stream))
+    if a.huffman == "optimized":
+        enc.set_huffman(jpegamd.HUFFMAN_OPTIMIZED)
+    t, st, got = timed(lambda: enc.encode_gray_scan_batch_async(descs, restart, out_ptrs, cap, size_ptrs, stream))
+    print(json.dumps({"scan": "gray", "width": w, "height": h, "batch": n, "quality": a.quality, "kind": a.kind, "steps": a.steps,
+                      "restart_interval": restart, "huffman": a.huffman or "standard", "bytes": got, "entropy_bits": st.entropy_bits,
+                      "ns_total_median": int(t), "us_per_picture": round(t / n / 1000, 1), "gpixels_per_s": round(n * w * h / t, 2),
+                      "plain_bytes": plain_bytes, "plain_us_per_picture": round(plain / n / 1000, 1), "ratio_to_plain": round(t / plain, 2)}))
 
 
 def run_batch(a, jpegamd, torch, dev, sources=("rgb",)) -> None:
