@@ -77,23 +77,33 @@ class BMPImage(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("data", C.POINTER(C.c_uint8))]
 
 
-def _load() -> C.CDLL:
-    if not LIB_PATH.exists():
-        raise ImportError(f"{LIB_PATH} is missing: build it with `make -C {_PKG_ROOT}` "
-                          "(or __graft_entry__.build()); there is no fallback implementation")
-    lib = C.CDLL(str(LIB_PATH), mode=getattr(os, "RTLD_NOW", 2))
+class BatchStats(C.Structure):
+    _fields_ = [("files_ok", C.c_int32), ("files_failed", C.c_int32), ("bytes_in", C.c_uint64), ("bytes_out", C.c_uint64),
+                ("seconds_total", C.c_double), ("seconds_read", C.c_double), ("seconds_write", C.c_double)]
+
+
+def _prototypes():
+    """Every entry of libjpegamd.so that the binding calls, written ONCE: name -> (result type, argument types), in three groups.
+    `base`: declared in include/jpeg_compression.h, in every build.  `later`: declared there as well, but a variant build of an
+    older round (JPEGAMD_LIB) may lack them.  `hidden`: debug entries that the header deliberately leaves out; a variant build may
+    lack them too."""
     u64, i32, i64, vp = C.c_uint64, C.c_int32, C.c_int64, C.c_void_p
-    sig = {
-        "jpegamd_encoder_create": (i32, [C.POINTER(vp), i32, i32]),
+    vpp, image = C.POINTER(vp), C.POINTER(Image)
+
+    def batch(struct, before: int, after: int = 0):
+        """(context, pictures[], count, `before` ints, outs[], capacity, sizes[], `after` ints, stream)"""
+        return i32, [vp, C.POINTER(struct), i32] + [i32] * before + [vpp, u64, vpp] + [i32] * after + [vp]
+
+    base = {
+        "jpegamd_encoder_create": (i32, [vpp, i32, i32]),
         "jpegamd_encoder_destroy": (i32, [vp]),
         "jpegamd_max_jfif_bytes": (u64, [i32, i32]),
-        "jpegamd_encode_async": (i32, [vp, C.POINTER(Image), vp, u64, vp, i32, vp]),
-        "jpegamd_encode_batch_async": (i32, [vp, C.POINTER(Image), i32, C.POINTER(C.c_void_p), u64, C.POINTER(C.c_void_p), i32, vp]),
+        "jpegamd_encode_async": (i32, [vp, image, vp, u64, vp, i32, vp]),
+        "jpegamd_encode_batch_async": batch(Image, 0, 1),
         "jpegamd_encoder_finish": (i32, [vp, C.POINTER(Stats)]),
-        "jpegamd_encoder_set_pipeline": (i32, [vp, i32]),
         "jpegamd_encoder_set_profiling": (i32, [vp, i32]),
         "jpegamd_encoder_profile": (i32, [vp, i32, C.POINTER(Stats)]),
-        "jpegamd_debug_stages": (i32, [vp, C.POINTER(Image), vp, vp, vp]),
+        "jpegamd_debug_stages": (i32, [vp, image, vp, vp, vp]),
         "jpegamd_debug_dct_exact": (i32, [vp, vp, vp, i64]),
         "jpegamd_synth_bmp": (u64, [i32, i32, C.c_uint32, i32, C.c_uint32, vp, u64]),
         "jpegamd_version": (C.c_char_p, []),
@@ -101,7 +111,6 @@ def _load() -> C.CDLL:
         "jpegamd_segment_meta_words": (i32, []),
         "jpegamd_debug_mfma_consts": (i32, [i32, vp, vp, vp, vp]),
         "jpegamd_debug_group_thresholds": (i32, [i32, vp, vp]),
-        "jpegamd_debug_mfma_offsets": (i32, [i32, vp, vp, vp, vp]),
         "jpegamd_debug_cos_lut": (i32, [vp]),
         "JpegCompression_Init": (i32, []),
         "JpegCompression_DeInit": (i32, []),
@@ -113,79 +122,78 @@ def _load() -> C.CDLL:
         "saveJPEGGrayscale": (C.c_bool, [C.c_char_p, C.POINTER(BMPImage)]),
         "jpegamd_encode_bmp_memory": (i64, [vp, u64, i32, vp, u64]),
         "jpegamd_encode_bmp_memory_color": (i64, [vp, u64, i32, i32, vp, u64]),
+        "jpegamd_parse_bmp": (i32, [vp, u64, image, C.POINTER(u64)]),
+        "jpegamd_encode_files": (i32, [C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), i32, i32, C.POINTER(i32), C.POINTER(BatchStats)]),
         "jpegamd_max_jfif_bytes_color": (u64, [i32, i32, i32]),
-        "jpegamd_encode_color_async": (i32, [vp, C.POINTER(Image), i32, vp, u64, vp, vp]),
-        "jpegamd_encode_color_batch_async": (i32, [vp, C.POINTER(Image), i32, i32, C.POINTER(C.c_void_p), u64, C.POINTER(C.c_void_p), vp]),
-        "jpegamd_encode_planar_batch_async": (i32, [vp, C.POINTER(PlanarImage), i32, i32, C.POINTER(C.c_void_p), u64, C.POINTER(C.c_void_p), vp]),
-        "jpegamd_encode_ycbcr_batch_async": (i32, [vp, C.POINTER(YCbCrImage), i32, i32, C.POINTER(C.c_void_p), u64, C.POINTER(C.c_void_p), vp]),
-        "jpegamd_encode_ycbcr_range_batch_async": (i32, [vp, C.POINTER(YCbCrImage), i32, i32, i32, C.POINTER(C.c_void_p), u64, C.POINTER(C.c_void_p), vp]),
-        "jpegamd_encode_ycbcr_samples_batch_async": (i32, [vp, C.POINTER(YCbCrImage), i32, i32, i32, i32, C.POINTER(C.c_void_p), u64, C.POINTER(C.c_void_p), vp]),
-        "jpegamd_encode_ycbcr_matrix_batch_async": (i32, [vp, C.POINTER(YCbCrImage), i32, i32, i32, i32, i32, C.POINTER(C.c_void_p), u64, C.POINTER(C.c_void_p), vp]),
-        "jpegamd_encode_color_interleaved_batch_async": (i32, [vp, C.POINTER(Image), i32, i32, C.POINTER(C.c_void_p), u64, C.POINTER(C.c_void_p), vp]),
-        "jpegamd_encode_ycbcr_interleaved_batch_async": (i32, [vp, C.POINTER(YCbCrImage), i32, i32, C.POINTER(C.c_void_p), u64, C.POINTER(C.c_void_p), vp]),
-        "jpegamd_max_jfif_bytes_interleaved": (u64, [i32, i32, i32]),
-        "jpegamd_encode_color_interleaved_restart_batch_async": (i32, [vp, C.POINTER(Image), i32, i32, i32, C.POINTER(C.c_void_p), u64, C.POINTER(C.c_void_p), vp]),
-        "jpegamd_encode_ycbcr_interleaved_restart_batch_async": (i32, [vp, C.POINTER(YCbCrImage), i32, i32, i32, C.POINTER(C.c_void_p), u64, C.POINTER(C.c_void_p), vp]),
-        "jpegamd_max_jfif_bytes_interleaved_restart": (u64, [i32, i32, i32, i32]),
-        "jpegamd_encode_ycbcr_interleaved_matrix_batch_async": (i32, [vp, C.POINTER(YCbCrImage), i32, i32, i32, i32, i32, i32, C.POINTER(C.c_void_p), u64, C.POINTER(C.c_void_p), vp]),
-        "jpegamd_encode_color_interleaved_pixels_batch_async": (i32, [vp, C.POINTER(Image), i32, i32, i32, C.POINTER(C.c_void_p), u64, C.POINTER(C.c_void_p), vp]),
-        "jpegamd_encode_planar_interleaved_batch_async": (i32, [vp, C.POINTER(PlanarImage), i32, i32, i32, C.POINTER(C.c_void_p), u64, C.POINTER(C.c_void_p), vp]),
-        "jpegamd_debug_tile_variant": (i32, [i32, i32, i32, i32]),
-        "jpegamd_encoder_set_huffman": (i32, [vp, i32]),
-        "jpegamd_debug_optimal_huffman": (i32, [vp, vp, i32, vp, vp, vp]),
-        "jpegamd_debug_huffman_counts": (i32, [vp, vp]),
-        "jpegamd_encode_gray_scan_batch_async": (i32, [vp, C.POINTER(Image), i32, i32, C.POINTER(C.c_void_p), u64, C.POINTER(C.c_void_p), vp]),
-        "jpegamd_max_jfif_bytes_gray_scan": (u64, [i32, i32, i32]),
-        "jpegamd_debug_matrix_coeffs": (i32, [i32, vp]),
-        "jpegamd_debug_ycbcr_matrix_planes": (i32, [vp, C.POINTER(YCbCrImage), i32, i32, i32, i32, i32, vp, vp, vp, vp]),
-        "jpegamd_debug_chroma_groups": (i32, [i32, i32, i32, i32, i32, i32, i32, vp]),
-        "jpegamd_debug_ycbcr_sources": (i32, [i32, i32, i32, i32, vp]),
+        "jpegamd_encode_color_async": (i32, [vp, image, i32, vp, u64, vp, vp]),
         "jpegamd_debug_chroma_quant_table": (i32, [i32, vp]),
         "jpegamd_debug_chroma_mfma_consts": (i32, [i32, vp, vp, vp, vp, vp, vp]),
         "jpegamd_debug_chroma_group_thresholds": (i32, [i32, vp, vp]),
         "jpegamd_debug_color_profile": (i32, [vp, i32, vp]),
-        "jpegamd_parse_bmp": (i32, [vp, u64, C.POINTER(Image), C.POINTER(u64)]),
-        "jpegamd_gather_streams": (i32, [vp, i32, i32, i32, vp, u64, i32, vp, vp, u64, vp]),
-        "jpegamd_encode_rows_async": (i32, [vp, C.POINTER(Image), i32, i32, vp]),
-        "jpegamd_export_segments": (i32, [vp, C.POINTER(Image), i32, i32, vp, u64, vp, vp, vp]),
-        "jpegamd_import_segments": (i32, [vp, C.POINTER(Image), i32, i32, vp, vp, vp]),
-        "jpegamd_finalize_async": (i32, [vp, C.POINTER(Image), vp, u64, vp, i32, vp]),
+        "jpegamd_encode_rows_async": (i32, [vp, image, i32, i32, vp]),
+        "jpegamd_export_segments": (i32, [vp, image, i32, i32, vp, u64, vp, vp, vp]),
+        "jpegamd_import_segments": (i32, [vp, image, i32, i32, vp, vp, vp]),
+        "jpegamd_finalize_async": (i32, [vp, image, vp, u64, vp, i32, vp]),
     }
-    for name, (res, args) in sig.items():
-        if name in ("jpegamd_encoder_set_pipeline", "jpegamd_gather_streams", "jpegamd_debug_mfma_offsets", "jpegamd_encode_color_batch_async",
-                    "jpegamd_debug_chroma_groups", "jpegamd_debug_ycbcr_sources", "jpegamd_encode_planar_batch_async", "jpegamd_encode_ycbcr_batch_async",
-                    "jpegamd_encode_ycbcr_range_batch_async", "jpegamd_encode_ycbcr_samples_batch_async", "jpegamd_encode_ycbcr_matrix_batch_async",
-                    "jpegamd_debug_matrix_coeffs", "jpegamd_debug_ycbcr_matrix_planes", "jpegamd_encode_color_interleaved_batch_async",
-                    "jpegamd_encode_ycbcr_interleaved_batch_async", "jpegamd_max_jfif_bytes_interleaved",
-                    "jpegamd_encode_color_interleaved_restart_batch_async", "jpegamd_encode_ycbcr_interleaved_restart_batch_async",
-                    "jpegamd_max_jfif_bytes_interleaved_restart", "jpegamd_encode_ycbcr_interleaved_matrix_batch_async",
-                    "jpegamd_encode_color_interleaved_pixels_batch_async", "jpegamd_encode_planar_interleaved_batch_async",
-                    "jpegamd_debug_tile_variant", "jpegamd_encoder_set_huffman", "jpegamd_debug_optimal_huffman",
-                    "jpegamd_debug_huffman_counts", "jpegamd_encode_gray_scan_batch_async",
-                    "jpegamd_max_jfif_bytes_gray_scan") and os.environ.get("JPEGAMD_LIB") and not hasattr(lib, name):
+    later = {
+        "jpegamd_encoder_set_pipeline": (i32, [vp, i32]),
+        "jpegamd_gather_streams": (i32, [vp, i32, i32, i32, vp, u64, i32, vp, vp, u64, vp]),
+        "jpegamd_debug_mfma_offsets": (i32, [i32, vp, vp, vp, vp]),
+        "jpegamd_encode_color_batch_async": batch(Image, 1),                                # (subsampling)
+        "jpegamd_encode_planar_batch_async": batch(PlanarImage, 1),
+        "jpegamd_encode_ycbcr_batch_async": batch(YCbCrImage, 1),
+        "jpegamd_encode_ycbcr_range_batch_async": batch(YCbCrImage, 2),                     # (subsampling, range)
+        "jpegamd_encode_ycbcr_samples_batch_async": batch(YCbCrImage, 3),                   # (subsampling, range, format)
+        "jpegamd_encode_ycbcr_matrix_batch_async": batch(YCbCrImage, 4),                    # (subsampling, range, format, matrix)
+        "jpegamd_encode_color_interleaved_batch_async": batch(Image, 1),
+        "jpegamd_encode_ycbcr_interleaved_batch_async": batch(YCbCrImage, 1),
+        "jpegamd_max_jfif_bytes_interleaved": (u64, [i32, i32, i32]),
+        "jpegamd_encode_color_interleaved_restart_batch_async": batch(Image, 2),            # (subsampling, restart interval)
+        "jpegamd_encode_ycbcr_interleaved_restart_batch_async": batch(YCbCrImage, 2),
+        "jpegamd_max_jfif_bytes_interleaved_restart": (u64, [i32, i32, i32, i32]),
+        "jpegamd_encode_ycbcr_interleaved_matrix_batch_async": batch(YCbCrImage, 5),        # (subsampling, range, format, matrix, restart interval)
+        "jpegamd_encode_color_interleaved_pixels_batch_async": batch(Image, 2),
+        "jpegamd_encode_planar_interleaved_batch_async": batch(PlanarImage, 2),
+        "jpegamd_encoder_set_huffman": (i32, [vp, i32]),
+        "jpegamd_debug_optimal_huffman": (i32, [vp, vp, i32, vp, vp, vp]),
+        "jpegamd_debug_huffman_counts": (i32, [vp, vp]),
+        "jpegamd_encode_gray_scan_batch_async": batch(Image, 1),                            # (restart interval)
+        "jpegamd_max_jfif_bytes_gray_scan": (u64, [i32, i32, i32]),
+    }
+    hidden = {
+        "jpegamd_debug_tile_variant": (i32, [i32, i32, i32, i32]),
+        "jpegamd_debug_matrix_coeffs": (i32, [i32, vp]),
+        "jpegamd_debug_ycbcr_matrix_planes": (i32, [vp, C.POINTER(YCbCrImage), i32, i32, i32, i32, i32, vp, vp, vp, vp]),
+        "jpegamd_debug_chroma_groups": (i32, [i32, i32, i32, i32, i32, i32, i32, vp]),
+        "jpegamd_debug_ycbcr_sources": (i32, [i32, i32, i32, i32, vp]),
+    }
+    return base, later, hidden
+
+
+def _load() -> C.CDLL:
+    if not LIB_PATH.exists():
+        raise ImportError(f"{LIB_PATH} is missing: build it with `make -C {_PKG_ROOT}` "
+                          "(or __graft_entry__.build()); there is no fallback implementation")
+    lib = C.CDLL(str(LIB_PATH), mode=getattr(os, "RTLD_NOW", 2))
+    for name, (res, args) in {**_BASE, **_LATER, **_HIDDEN}.items():
+        if name not in _BASE and os.environ.get("JPEGAMD_LIB") and not hasattr(lib, name):
             continue                                              # (A/B tooling: a variant build of an older round)
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = res, args
     return lib
 
 
+_BASE, _LATER, _HIDDEN = _prototypes()
+EXPORTED = [*_BASE, *_LATER]                                     # what include/jpeg_compression.h declares
 lib = _load()
-EXPORTED = ("jpegamd_encoder_create jpegamd_encoder_destroy jpegamd_max_jfif_bytes jpegamd_encode_async jpegamd_encode_batch_async "
-            "jpegamd_encoder_finish jpegamd_encoder_set_pipeline jpegamd_encoder_set_profiling jpegamd_encoder_profile jpegamd_debug_stages jpegamd_debug_dct_exact "
-            "jpegamd_synth_bmp jpegamd_version jpegamd_debug_quant_table jpegamd_segment_meta_words jpegamd_debug_mfma_consts jpegamd_debug_group_thresholds jpegamd_debug_mfma_offsets jpegamd_debug_cos_lut JpegCompression_Init JpegCompression_DeInit JpegCompression_Reserve "
-            "convertToJpeg JpegCompression_RemoteServiceHandler loadBMPImage freeBMPImage saveJPEGGrayscale "
-            "jpegamd_encode_bmp_memory jpegamd_parse_bmp jpegamd_encode_files jpegamd_gather_streams "
-            "jpegamd_encode_rows_async jpegamd_export_segments jpegamd_import_segments jpegamd_finalize_async "
-            "jpegamd_max_jfif_bytes_color jpegamd_encode_color_async jpegamd_encode_bmp_memory_color jpegamd_debug_chroma_quant_table "
-            "jpegamd_debug_chroma_mfma_consts jpegamd_debug_chroma_group_thresholds jpegamd_debug_color_profile jpegamd_encode_color_batch_async "
-            "jpegamd_encode_planar_batch_async jpegamd_encode_ycbcr_batch_async jpegamd_encode_ycbcr_range_batch_async "
-            "jpegamd_encode_ycbcr_samples_batch_async jpegamd_encode_ycbcr_matrix_batch_async "
-            "jpegamd_encode_color_interleaved_batch_async jpegamd_encode_ycbcr_interleaved_batch_async jpegamd_max_jfif_bytes_interleaved "
-            "jpegamd_encode_color_interleaved_restart_batch_async jpegamd_encode_ycbcr_interleaved_restart_batch_async "
-            "jpegamd_max_jfif_bytes_interleaved_restart jpegamd_encode_ycbcr_interleaved_matrix_batch_async "
-            "jpegamd_encode_color_interleaved_pixels_batch_async jpegamd_encode_planar_interleaved_batch_async "
-            "jpegamd_encoder_set_huffman jpegamd_debug_optimal_huffman jpegamd_debug_huffman_counts "
-            "jpegamd_encode_gray_scan_batch_async jpegamd_max_jfif_bytes_gray_scan").split()
+
+
+def _checked(name: str, *args):
+    """lib.<name>(*args); a non-zero result is a JpegAmdError that names the entry.  `lib` is looked up at call time: tests and
+    tools put their own in its place."""
+    rc = getattr(lib, name)(*args)
+    if rc:
+        raise JpegAmdError(rc, name)
 
 
 def quant_table(quality: int = 50):
@@ -274,9 +282,7 @@ def synth_bmp_into(ptr: int, cap: int, width: int, height: int, seed: int = 1, k
 def parse_bmp(data: bytes):
     """-> (Image view with pixels=offset, pixel_offset) using loadBMPImage's header rules."""
     img, off = Image(), C.c_uint64(0)
-    rc = lib.jpegamd_parse_bmp(data, len(data), C.byref(img), C.byref(off))
-    if rc:
-        raise JpegAmdError(rc, "jpegamd_parse_bmp")
+    _checked("jpegamd_parse_bmp", data, len(data), C.byref(img), C.byref(off))
     return img, off.value
 
 
@@ -380,6 +386,42 @@ def _tensor_encoder(dev: int, w: int, rows: int):
     return enc
 
 
+def _files(out, sizes, k: int) -> list:
+    """The first k files of a finished call: row i of `out`, sizes[i] bytes of it."""
+    got = sizes[:k].cpu().tolist()
+    return [bytes(out[i, :got[i]].cpu().numpy().tobytes()) for i in range(k)]
+
+
+def _encode_pictures(device, n: int, h: int, w: int, cap: int, queue, huffman=None) -> list:
+    """`n` pictures of one geometry through the per-device context, in calls of at most MAX_BATCH -> their files of at most `cap`
+    bytes.  queue(enc, b0, k, outs, cap, size_ptrs, stream) queues pictures b0 .. b0 + k - 1 on `enc`.  `huffman`: None leaves the
+    context's tables alone; a mode is set on the shared context around every call, which is finished inside, and HUFFMAN_STANDARD
+    is put back whatever happens."""
+    import torch
+    dev = device.index if device.index is not None else torch.cuda.current_device()
+    files = []
+    with torch.cuda.device(dev):
+        per = min(n, MAX_BATCH)
+        enc = _tensor_encoder(dev, w, per * ((h + 7) // 8 * 8))      # a batch needs `per` x the block rows of one picture
+        out = torch.empty((per, cap), dtype=torch.uint8, device=device)
+        sizes = torch.zeros(per, dtype=torch.int64, device=device)
+        stream = torch.cuda.current_stream(device).cuda_stream
+        for b0 in range(0, n, MAX_BATCH):
+            k = min(MAX_BATCH, n - b0)
+            outs = [out[i].data_ptr() for i in range(k)]
+            size_ptrs = [sizes.data_ptr() + 8 * i for i in range(k)]
+            if huffman is not None:
+                enc.set_huffman(huffman)
+            try:
+                queue(enc, b0, k, outs, cap, size_ptrs, stream)
+                enc.finish()
+            finally:
+                if huffman is not None:
+                    enc.set_huffman(HUFFMAN_STANDARD)
+            files += _files(out, sizes, k)
+    return files
+
+
 def encode_tensor(t, quality: int = 0, subsampling: int = SUBSAMPLE_420, layout=None, scan: str = "separate", restart_interval=None) -> bytes:
     """A uint8 DEVICE tensor -> JFIF file bytes: [H, W] a grayscale file (the tensor is the luma), [H, W, 3] (R, G, B) a colour file.
     Rows may be strided (t.stride(0) bytes apart); pixels within a row must be packed.  Runs on the tensor's device and the
@@ -410,15 +452,9 @@ def encode_tensor(t, quality: int = 0, subsampling: int = SUBSAMPLE_420, layout=
         raise ValueError("encode_tensor takes [H, W] or [H, W, 3]")
     dev = t.device.index if t.device.index is not None else torch.cuda.current_device()
     with torch.cuda.device(dev):
-        enc, mw, mh = _tensor_encoders.get(dev, (None, 0, 0))
-        if enc is None or w > mw or h > mh:
-            mw, mh = max(w, mw), max(h, mh)
-            if enc is not None:
-                enc.close()
-            enc = Encoder(mw, mh)
-            _tensor_encoders[dev] = (enc, mw, mh)
+        enc = _tensor_encoder(dev, w, h)
         cap = max_jfif_bytes(w, h) if order == ORDER_GRAY else max_jfif_bytes_color(w, h, subsampling)
-        out = torch.empty(cap, dtype=torch.uint8, device=t.device)
+        out = torch.empty((1, cap), dtype=torch.uint8, device=t.device)
         size = torch.zeros(1, dtype=torch.int64, device=t.device)
         stream = torch.cuda.current_stream(t.device).cuda_stream
         img = Encoder.image(t.data_ptr(), w, h, t.stride(0), bottom_up=False, channel_order=order, quality=quality)
@@ -427,8 +463,7 @@ def encode_tensor(t, quality: int = 0, subsampling: int = SUBSAMPLE_420, layout=
         else:
             enc.encode_color_async(img, subsampling, out.data_ptr(), cap, size.data_ptr(), stream)
         enc.finish()
-        n = int(size.item())
-        return bytes(out[:n].cpu().numpy().tobytes())
+        return _files(out, size, 1)[0]
 
 
 def _chroma_groups(max_width: int, max_height: int, width: int, height: int, count: int, subsampling: int = SUBSAMPLE_420,
@@ -436,9 +471,7 @@ def _chroma_groups(max_width: int, max_height: int, width: int, height: int, cou
     """Test hook, not part of the API (jpegamd_debug_chroma_groups is not in the public header).  Host-only: how a colour batch of `count` width x height pictures on a context created for max_width x max_height groups its
     2 x count chroma planes into launches -> (planes per launch, launches, tiles per segment, k_stitch)."""
     out = (C.c_int32 * 4)()
-    rc = lib.jpegamd_debug_chroma_groups(max_width, max_height, pipeline, width, height, count, subsampling, out)
-    if rc:
-        raise JpegAmdError(rc, "jpegamd_debug_chroma_groups")
+    _checked("jpegamd_debug_chroma_groups", max_width, max_height, pipeline, width, height, count, subsampling, out)
     return out[0], out[1], out[2], bool(out[3])
 
 
@@ -541,7 +574,6 @@ def encode_tensor_batch(t, quality: int = 0, subsampling: int = SUBSAMPLE_420, l
     RSTn, jpegamd_encode_color_interleaved_restart_batch_async); 0 / None: none.
     (`_any_layout`: jpegamd.mjpeg's call -- scan="interleaved" with every colour layout, through the entries that read them;
     `_huffman`: its tables, set on the per-device context for this call and put back to HUFFMAN_STANDARD behind it.)"""
-    import torch
     interleaved = _scan(scan)
     if _huffman and not interleaved:
         raise ValueError('optimised Huffman tables need scan="interleaved"')
@@ -563,64 +595,45 @@ def encode_tensor_batch(t, quality: int = 0, subsampling: int = SUBSAMPLE_420, l
     ri = _restart(restart_interval, interleaved, w, subsampling)
     if any(not x.is_cuda or x.device != tensors[0].device for x in tensors):
         raise ValueError("encode_tensor_batch needs a device tensor")
-    device = tensors[0].device
-    dev = device.index if device.index is not None else torch.cuda.current_device()
-    gray = order == ORDER_GRAY or (order is None and subsampling == 0)
-    files = []
-    with torch.cuda.device(dev):
-        per = min(n, MAX_BATCH)
-        rows = per * ((h + 7) // 8 * 8)              # a batch needs `per` x the block rows of one picture
-        enc = _tensor_encoder(dev, w, rows)
-        cap = max_jfif_bytes(w, h) if gray else max_jfif_bytes_color(w, h, subsampling)
-        if interleaved:
-            cap = max_jfif_bytes_interleaved_restart(w, h, subsampling, ri) if ri else max_jfif_bytes_interleaved(w, h, subsampling)
-        out = torch.empty((per, cap), dtype=torch.uint8, device=device)
-        sizes = torch.zeros(per, dtype=torch.int64, device=device)
-        stream = torch.cuda.current_stream(device).cuda_stream
-        for b0 in range(0, n, MAX_BATCH):
-            k = min(MAX_BATCH, n - b0)
-            outs = [out[i].data_ptr() for i in range(k)]
-            size_ptrs = [sizes.data_ptr() + 8 * i for i in range(k)]
-            if _huffman:
-                files += _with_huffman(enc, _huffman, lambda: _interleaved_call(enc, order, _any_layout, ptr, b0, k, w, h, stride, quality,
-                                                                                  subsampling, ri, outs, cap, size_ptrs, stream), out, sizes, k)
-                continue
-            if interleaved and order is None:
-                imgs = [Encoder.planar_image(ptr(b0 + i), w, h, stride, bottom_up=False, quality=quality) for i in range(k)]
-                enc.encode_planar_interleaved_batch_async(imgs, subsampling, ri, outs, cap, size_ptrs, stream)
-            elif interleaved:
-                imgs = [Encoder.image(ptr(b0 + i), w, h, stride, bottom_up=False, channel_order=order, quality=quality) for i in range(k)]
-                if _any_layout:
-                    enc.encode_color_interleaved_pixels_batch_async(imgs, subsampling, ri, outs, cap, size_ptrs, stream)
-                elif ri:
-                    enc.encode_color_interleaved_restart_batch_async(imgs, subsampling, ri, outs, cap, size_ptrs, stream)
-                else:
-                    enc.encode_color_interleaved_batch_async(imgs, subsampling, outs, cap, size_ptrs, stream)
-            elif order is None:
-                imgs = [Encoder.planar_image(ptr(b0 + i), w, h, stride, bottom_up=False, quality=quality) for i in range(k)]
-                enc.encode_planar_batch_async(imgs, subsampling, outs, cap, size_ptrs, stream)
-            else:
-                imgs = [Encoder.image(ptr(b0 + i), w, h, stride, bottom_up=False, channel_order=order, quality=quality)
-                        for i in range(k)]
-                if order == ORDER_GRAY:
-                    enc.encode_batch_async(imgs, outs, cap, size_ptrs, True, stream)
-                else:
-                    enc.encode_color_batch_async(imgs, subsampling, outs, cap, size_ptrs, stream)
-            enc.finish()
-            got = sizes[:k].cpu().tolist()
-            files += [bytes(out[i, :got[i]].cpu().numpy().tobytes()) for i in range(k)]
-    return files
+    if interleaved:
+        cap = max_jfif_bytes_interleaved_restart(w, h, subsampling, ri) if ri else max_jfif_bytes_interleaved(w, h, subsampling)
+    elif order == ORDER_GRAY or (order is None and subsampling == 0):
+        cap = max_jfif_bytes(w, h)
+    else:
+        cap = max_jfif_bytes_color(w, h, subsampling)
+
+    def queue(enc, b0, k, outs, cap, size_ptrs, stream):
+        if order is None:
+            imgs = [Encoder.planar_image(ptr(b0 + i), w, h, stride, bottom_up=False, quality=quality) for i in range(k)]
+        else:
+            imgs = [Encoder.image(ptr(b0 + i), w, h, stride, bottom_up=False, channel_order=order, quality=quality) for i in range(k)]
+        _queue_pixels(enc, imgs, subsampling, outs, cap, size_ptrs, stream, interleaved, ri, _any_layout, _huffman)
+
+    return _encode_pictures(tensors[0].device, n, h, w, cap, queue, _huffman or None)
 
 
-def _interleaved_call(enc, order, any_layout, ptr, b0, k, w, h, stride, quality, subsampling, ri, outs, cap, size_ptrs, stream):
-    """One interleaved batch of encode_tensor_batch queued on `enc`: pictures b0 .. b0 + k - 1."""
-    if order is None:
-        imgs = [Encoder.planar_image(ptr(b0 + i), w, h, stride, bottom_up=False, quality=quality) for i in range(k)]
-        return enc.encode_planar_interleaved_batch_async(imgs, subsampling, ri, outs, cap, size_ptrs, stream)
-    imgs = [Encoder.image(ptr(b0 + i), w, h, stride, bottom_up=False, channel_order=order, quality=quality) for i in range(k)]
-    if any_layout:
-        return enc.encode_color_interleaved_pixels_batch_async(imgs, subsampling, ri, outs, cap, size_ptrs, stream)
-    return enc.encode_color_interleaved_restart_batch_async(imgs, subsampling, ri, outs, cap, size_ptrs, stream)
+def _queue_pixels(enc, imgs, subsampling, outs, cap, size_ptrs, stream, interleaved: bool = False, restart: int = 0,
+                  any_layout: bool = False, huffman: int = 0):
+    """One call of encode_tensor_batch queued on `enc`: which entry takes `imgs` (Image or PlanarImage structs of one geometry).
+    Three scans: the planar, the grayscale (ORDER_GRAY) or the colour batch entry.  One scan: the planar entry; for packed pixels
+    the entry of every pixel order with `any_layout` (jpegamd.mjpeg), otherwise the RGB entries of encode_tensor_batch's own
+    scan="interleaved" -- the restart entry when there are intervals, and for `huffman` (whatever the interval)."""
+    planar = isinstance(imgs[0], PlanarImage)
+    if not interleaved:
+        if planar:
+            enc.encode_planar_batch_async(imgs, subsampling, outs, cap, size_ptrs, stream)
+        elif imgs[0].channel_order == ORDER_GRAY:
+            enc.encode_batch_async(imgs, outs, cap, size_ptrs, True, stream)
+        else:
+            enc.encode_color_batch_async(imgs, subsampling, outs, cap, size_ptrs, stream)
+    elif planar:
+        enc.encode_planar_interleaved_batch_async(imgs, subsampling, restart, outs, cap, size_ptrs, stream)
+    elif any_layout:
+        enc.encode_color_interleaved_pixels_batch_async(imgs, subsampling, restart, outs, cap, size_ptrs, stream)
+    elif restart or huffman:
+        enc.encode_color_interleaved_restart_batch_async(imgs, subsampling, restart, outs, cap, size_ptrs, stream)
+    else:
+        enc.encode_color_interleaved_batch_async(imgs, subsampling, outs, cap, size_ptrs, stream)
 
 
 def _encode_gray_scan_batch(t, quality, restart_interval, huffman, name: str) -> list:
@@ -638,37 +651,13 @@ def _encode_gray_scan_batch(t, quality, restart_interval, huffman, name: str) ->
     ri = _restart(restart_interval, True, w, SUBSAMPLE_444)            # ("row": ceil(W / 8) -- the MCU is one block)
     if not t.is_cuda:
         raise ValueError(f"{name} needs a device tensor")
-    device = t.device
-    dev = device.index if device.index is not None else torch.cuda.current_device()
-    files = []
-    with torch.cuda.device(dev):
-        per = min(n, MAX_BATCH)
-        rows = per * ((h + 7) // 8 * 8)
-        enc = _tensor_encoder(dev, w, rows)
-        cap = max_jfif_bytes_gray_scan(w, h, ri)
-        out = torch.empty((per, cap), dtype=torch.uint8, device=device)
-        sizes = torch.zeros(per, dtype=torch.int64, device=device)
-        stream = torch.cuda.current_stream(device).cuda_stream
-        for b0 in range(0, n, MAX_BATCH):
-            k = min(MAX_BATCH, n - b0)
-            outs = [out[i].data_ptr() for i in range(k)]
-            size_ptrs = [sizes.data_ptr() + 8 * i for i in range(k)]
-            imgs = [Encoder.image(t[b0 + i].data_ptr(), w, h, t.stride(1), bottom_up=False, channel_order=ORDER_GRAY, quality=quality)
-                    for i in range(k)]
-            files += _with_huffman(enc, huff, lambda: enc.encode_gray_scan_batch_async(imgs, ri, outs, cap, size_ptrs, stream), out, sizes, k)
-    return files
 
+    def queue(enc, b0, k, outs, cap, size_ptrs, stream):
+        imgs = [Encoder.image(t[b0 + i].data_ptr(), w, h, t.stride(1), bottom_up=False, channel_order=ORDER_GRAY, quality=quality)
+                for i in range(k)]
+        enc.encode_gray_scan_batch_async(imgs, ri, outs, cap, size_ptrs, stream)
 
-def _with_huffman(enc, huffman: int, queue, out, sizes, k: int) -> list:
-    """queue() with `huffman` set on the shared context, finished, the context back in HUFFMAN_STANDARD whatever happens -> the k files."""
-    enc.set_huffman(huffman)
-    try:
-        queue()
-        enc.finish()
-    finally:
-        enc.set_huffman(HUFFMAN_STANDARD)
-    got = sizes[:k].cpu().tolist()
-    return [bytes(out[i, :got[i]].cpu().numpy().tobytes()) for i in range(k)]
+    return _encode_pictures(t.device, n, h, w, max_jfif_bytes_gray_scan(w, h, ri), queue, huff)   # (the mode is set even for "standard")
 
 
 def _ycbcr_layout_of(y, cb, cr, subsampling, order, dtypes, sample_bytes, pairs):
@@ -770,14 +759,22 @@ def encode_ycbcr_batch(y, cb, cr=None, quality: int = 0, subsampling: int = SUBS
     interleaved = _scan(scan)
     if interleaved and (rng != RANGE_FULL or mat != MATRIX_BT601):
         raise ValueError('scan="interleaved" takes sample_range="full" and matrix="bt601" alone')
-    n, h, w, y_stride, c_stride, layout = _ycbcr_layout(y, cb, cr, subsampling, order)
+    return _encode_ycbcr_planes("encode_ycbcr_batch", _ycbcr_layout, y, cb, cr, quality, subsampling, order, restart_interval,
+                                rng, matrix=mat, interleaved=interleaved)
+
+
+def _encode_ycbcr_planes(name: str, layout_of, y, cb, cr, quality, subsampling, order, restart_interval, sample_range: int,
+                         sample_format: int = SAMPLES_8, matrix: int = MATRIX_BT601, interleaved: bool = False, **one_scan):
+    """What the four planes-or-pairs functions (encode_ycbcr_batch, encode_ycbcr16_batch and their jpegamd.mjpeg twins) share behind
+    their own checks: the layout (layout_of: _ycbcr_layout or _ycbcr16_layout), the restart interval, the device, the encode."""
+    n, h, w, y_stride, c_stride, layout = layout_of(y, cb, cr, subsampling, order)
     ri = _restart(restart_interval, interleaved, w, subsampling)
     tensors = [y, cb] + ([cr] if cr is not None else [])
     if any(not x.is_cuda or x.device != y.device for x in tensors):
-        raise ValueError("encode_ycbcr_batch needs device tensors on one device")
+        raise ValueError(f"{name} needs device tensors on one device")
     return _encode_ycbcr_images(y.device, n, h, w, subsampling, lambda i: Encoder.ycbcr_image(
-        y[i].data_ptr(), cb[i].data_ptr(), cr[i].data_ptr() if cr is not None else 0, w, h, y_stride, c_stride, layout, quality), rng, matrix=mat, interleaved=interleaved,
-        restart=ri)
+        y[i].data_ptr(), cb[i].data_ptr(), cr[i].data_ptr() if cr is not None else 0, w, h, y_stride, c_stride, layout, quality),
+        sample_range, sample_format, matrix, interleaved, ri, **one_scan)
 
 
 def _encode_ycbcr_images(device, n, h, w, subsampling, image, sample_range: int = RANGE_FULL, sample_format: int = SAMPLES_8,
@@ -785,44 +782,35 @@ def _encode_ycbcr_images(device, n, h, w, subsampling, image, sample_range: int 
     """`n` YCbCr pictures of one geometry, picture i described by image(i), through the per-device context in calls of at most
     MAX_BATCH -> their files.  `any_kind` (jpegamd.mjpeg): the interleaved files of whatever range, format, matrix and layout, through
     jpegamd_encode_ycbcr_interleaved_matrix_batch_async, with the tables `huffman` (set on the context for the call, STANDARD put back)."""
-    import torch
     if huffman and not any_kind:
         raise ValueError("optimised Huffman tables go through jpegamd.mjpeg")
-    dev = device.index if device.index is not None else torch.cuda.current_device()
-    files = []
-    with torch.cuda.device(dev):
-        per = min(n, MAX_BATCH)
-        rows = per * ((h + 7) // 8 * 8)              # a batch needs `per` x the block rows of one picture
-        enc = _tensor_encoder(dev, w, rows)
+    if restart:
+        cap = max_jfif_bytes_interleaved_restart(w, h, subsampling, restart)
+    else:
         cap = max_jfif_bytes_interleaved(w, h, subsampling) if interleaved else max_jfif_bytes_color(w, h, subsampling)
-        if restart:
-            cap = max_jfif_bytes_interleaved_restart(w, h, subsampling, restart)
-        out = torch.empty((per, cap), dtype=torch.uint8, device=device)
-        sizes = torch.zeros(per, dtype=torch.int64, device=device)
-        stream = torch.cuda.current_stream(device).cuda_stream
-        for b0 in range(0, n, MAX_BATCH):
-            k = min(MAX_BATCH, n - b0)
-            outs = [out[i].data_ptr() for i in range(k)]
-            size_ptrs = [sizes.data_ptr() + 8 * i for i in range(k)]
-            imgs = [image(b0 + i) for i in range(k)]
-            if huffman:
-                files += _with_huffman(enc, huffman, lambda: enc.encode_ycbcr_interleaved_matrix_batch_async(
-                    imgs, subsampling, sample_range, sample_format, matrix, restart, outs, cap, size_ptrs, stream), out, sizes, k)
-                continue
-            if any_kind:
-                enc.encode_ycbcr_interleaved_matrix_batch_async(imgs, subsampling, sample_range, sample_format, matrix, restart, outs, cap,
-                                                                size_ptrs, stream)
-            elif restart:
-                enc.encode_ycbcr_interleaved_restart_batch_async(imgs, subsampling, restart, outs, cap, size_ptrs, stream)
-            elif interleaved:
-                enc.encode_ycbcr_interleaved_batch_async(imgs, subsampling, outs, cap, size_ptrs, stream)
-            else:
-                enc.encode_ycbcr_batch_async(imgs, subsampling, outs, cap, size_ptrs, stream, sample_range, sample_format=sample_format,
-                                             matrix=matrix)
-            enc.finish()
-            got = sizes[:k].cpu().tolist()
-            files += [bytes(out[i, :got[i]].cpu().numpy().tobytes()) for i in range(k)]
-    return files
+
+    def queue(enc, b0, k, outs, cap, size_ptrs, stream):
+        _queue_ycbcr(enc, [image(b0 + i) for i in range(k)], subsampling, outs, cap, size_ptrs, stream, sample_range, sample_format,
+                     matrix, interleaved, restart, any_kind)
+
+    return _encode_pictures(device, n, h, w, cap, queue, huffman or None)
+
+
+def _queue_ycbcr(enc, imgs, subsampling, outs, cap, size_ptrs, stream, sample_range: int = RANGE_FULL, sample_format: int = SAMPLES_8,
+                 matrix: int = MATRIX_BT601, interleaved: bool = False, restart: int = 0, any_kind: bool = False):
+    """One call of _encode_ycbcr_images queued on `enc`: which entry takes `imgs` (YCbCrImage structs of one geometry).  `any_kind`:
+    the one-scan entry of every range, format and matrix; otherwise the one-scan entries of full-range 8-bit BT.601 samples, with
+    or without restart intervals; otherwise the three-scan entries (encode_ycbcr_batch_async picks among them)."""
+    if any_kind:
+        enc.encode_ycbcr_interleaved_matrix_batch_async(imgs, subsampling, sample_range, sample_format, matrix, restart, outs, cap,
+                                                        size_ptrs, stream)
+    elif restart:
+        enc.encode_ycbcr_interleaved_restart_batch_async(imgs, subsampling, restart, outs, cap, size_ptrs, stream)
+    elif interleaved:
+        enc.encode_ycbcr_interleaved_batch_async(imgs, subsampling, outs, cap, size_ptrs, stream)
+    else:
+        enc.encode_ycbcr_batch_async(imgs, subsampling, outs, cap, size_ptrs, stream, sample_range, sample_format=sample_format,
+                                     matrix=matrix)
 
 
 def encode_ycbcr16_batch(y, cb, cr=None, quality: int = 0, subsampling: int = SUBSAMPLE_420, order: str = "cbcr",
@@ -840,13 +828,8 @@ def encode_ycbcr16_batch(y, cb, cr=None, quality: int = 0, subsampling: int = SU
     rng, mat = _sample_range(sample_range), _matrix(matrix)
     if not isinstance(align, str) or align not in ("msb", "lsb"):
         raise ValueError(f'align must be "msb" or "lsb", not {align!r}')
-    n, h, w, y_stride, c_stride, layout = _ycbcr16_layout(y, cb, cr, subsampling, order)
-    tensors = [y, cb] + ([cr] if cr is not None else [])
-    if any(not x.is_cuda or x.device != y.device for x in tensors):
-        raise ValueError("encode_ycbcr16_batch needs device tensors on one device")
-    return _encode_ycbcr_images(y.device, n, h, w, subsampling, lambda i: Encoder.ycbcr_image(
-        y[i].data_ptr(), cb[i].data_ptr(), cr[i].data_ptr() if cr is not None else 0, w, h, y_stride, c_stride, layout, quality), rng,
-        SAMPLES_10_MSB if align == "msb" else SAMPLES_10_LSB, mat)
+    return _encode_ycbcr_planes("encode_ycbcr16_batch", _ycbcr16_layout, y, cb, cr, quality, subsampling, order, None, rng,
+                                SAMPLES_10_MSB if align == "msb" else SAMPLES_10_LSB, mat)
 
 
 def _yuyv_layout(frames, order):
@@ -881,16 +864,18 @@ def encode_yuyv_batch(frames, quality: int = 0, order: str = "yuyv", sample_rang
     samples, expanded to full range on read as in encode_ycbcr_batch.  matrix="bt709": BT.709 samples, converted to BT.601 by one pass as
     in encode_ycbcr_batch."""
     rng, mat = _sample_range(sample_range), _matrix(matrix)
+    return _encode_yuyv_frames(frames, quality, order, None, rng, mat)
+
+
+def _encode_yuyv_frames(frames, quality, order, restart_interval, sample_range: int, matrix: int, interleaved: bool = False, **one_scan):
+    """What encode_yuyv_batch and its jpegamd.mjpeg twin share behind their own checks, as _encode_ycbcr_planes."""
     n, h, w, stride, layout = _yuyv_layout(frames, order)
+    ri = _restart(restart_interval, interleaved, w, SUBSAMPLE_422)
     if not frames.is_cuda:
         raise ValueError("encode_yuyv_batch needs a device tensor")
     return _encode_ycbcr_images(frames.device, n, h, w, SUBSAMPLE_422, lambda i: Encoder.ycbcr_image(
-        frames[i].data_ptr(), 0, 0, w, h, stride, 0, layout, quality), rng, matrix=mat)
-
-
-class BatchStats(C.Structure):
-    _fields_ = [("files_ok", C.c_int32), ("files_failed", C.c_int32), ("bytes_in", C.c_uint64), ("bytes_out", C.c_uint64),
-                ("seconds_total", C.c_double), ("seconds_read", C.c_double), ("seconds_write", C.c_double)]
+        frames[i].data_ptr(), 0, 0, w, h, stride, 0, layout, quality), sample_range, matrix=matrix, interleaved=interleaved, restart=ri,
+        **one_scan)
 
 
 def encode_files(in_paths, out_paths, quality: int = 0):
@@ -902,10 +887,7 @@ def encode_files(in_paths, out_paths, quality: int = 0):
     outs = (C.c_char_p * n)(*[str(p).encode() for p in out_paths])
     status = (C.c_int32 * n)()
     st = BatchStats()
-    fn = lib.jpegamd_encode_files
-    fn.restype = C.c_int32
-    fn.argtypes = [C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(BatchStats)]
-    rc = fn(ins, outs, n, quality, status, C.byref(st))
+    rc = lib.jpegamd_encode_files(ins, outs, n, quality, status, C.byref(st))
     return int(rc), list(status), st
 
 
@@ -914,9 +896,7 @@ class Encoder:
 
     def __init__(self, max_width: int, max_height: int):
         self._h = C.c_void_p()
-        rc = lib.jpegamd_encoder_create(C.byref(self._h), max_width, max_height)
-        if rc:
-            raise JpegAmdError(rc, "jpegamd_encoder_create")
+        _checked("jpegamd_encoder_create", C.byref(self._h), max_width, max_height)
 
     def close(self):
         if self._h:
@@ -931,27 +911,19 @@ class Encoder:
 
     def set_pipeline(self, pipeline: int):
         """PIPELINE_AUTO / PIPELINE_PAIR (k_segment_merge + k_finalize) / PIPELINE_STITCH (k_stitch): which kernels follow k_tile_encode."""
-        rc = lib.jpegamd_encoder_set_pipeline(self._h, int(pipeline))
-        if rc:
-            raise JpegAmdError(rc, "jpegamd_encoder_set_pipeline")
+        _checked("jpegamd_encoder_set_pipeline", self._h, int(pipeline))
 
     def set_huffman(self, huffman: int):
         """HUFFMAN_STANDARD (the Annex K tables, default) or HUFFMAN_OPTIMIZED (per-picture tables) for the one-scan entries
         (jpegamd_encoder_set_huffman); takes effect with the next encode."""
-        rc = lib.jpegamd_encoder_set_huffman(self._h, int(huffman))
-        if rc:
-            raise JpegAmdError(rc, "jpegamd_encoder_set_huffman")
+        _checked("jpegamd_encoder_set_huffman", self._h, int(huffman))
 
     def set_profiling(self, slots: int):
-        rc = lib.jpegamd_encoder_set_profiling(self._h, int(slots))
-        if rc:
-            raise JpegAmdError(rc, "jpegamd_encoder_set_profiling")
+        _checked("jpegamd_encoder_set_profiling", self._h, int(slots))
 
     def profile(self, slot: int) -> Stats:
         st = Stats()
-        rc = lib.jpegamd_encoder_profile(self._h, slot, C.byref(st))
-        if rc:
-            raise JpegAmdError(rc, "jpegamd_encoder_profile")
+        _checked("jpegamd_encoder_profile", self._h, slot, C.byref(st))
         return st
 
     @staticmethod
@@ -965,17 +937,6 @@ class Encoder:
         r, g, b = planes
         return PlanarImage((C.c_void_p * 3)(r, g, b), width, height, row_stride, 1 if bottom_up else 0, quality)
 
-    def encode_planar_batch_async(self, imgs, subsampling: int, out_ptrs, out_cap: int, size_ptrs, stream: int = 0):
-        """The files of `len(imgs)` planar pictures of one geometry (jpegamd_encode_planar_batch_async): subsampling 0 grayscale
-        files, SUBSAMPLE_444 / SUBSAMPLE_420 / SUBSAMPLE_422 colour files; the context as for the packed batch entries."""
-        n = len(imgs)
-        arr = (PlanarImage * n)(*imgs)
-        outs = (C.c_void_p * n)(*[C.c_void_p(p) for p in out_ptrs])
-        sizes = (C.c_void_p * n)(*[C.c_void_p(p) for p in size_ptrs])
-        rc = lib.jpegamd_encode_planar_batch_async(self._h, arr, n, int(subsampling), outs, out_cap, sizes, C.c_void_p(stream))
-        if rc:
-            raise JpegAmdError(rc, "jpegamd_encode_planar_batch_async")
-
     @staticmethod
     def ycbcr_image(y_ptr: int, cb_ptr: int, cr_ptr: int, width: int, height: int, y_stride: int, c_stride: int,
                     chroma_layout: int = CHROMA_PLANES, quality: int = 0) -> YCbCrImage:
@@ -983,6 +944,23 @@ class Encoder:
         (CHROMA_CBCR / CHROMA_CRCB; `cr_ptr` is then ignored and may be 0), or one packed 4:2:2 plane in `y_ptr` (CHROMA_YUYV /
         CHROMA_UYVY: `y_stride` is its row stride, the chroma arguments are ignored)."""
         return YCbCrImage(y_ptr or None, cb_ptr or None, cr_ptr or None, width, height, y_stride, c_stride, chroma_layout, quality)
+
+    def _batch(self, name: str, struct, imgs, ints, out_ptrs, out_cap: int, size_ptrs, stream: int, tail=()):
+        """A batch entry: name(context, pictures[], count, ints..., outs[], out_cap, sizes[], tail..., stream) with the pictures as
+        one array of `struct` and the two lists of device pointers as arrays.  encode_batch_async is on bench.py's timed path: this
+        raises like _checked, itself, so that the path is one call deeper than it was and no more, and the pointer arrays are made
+        from the integers as they are (no c_void_p object each), which pays that call back."""
+        n = len(imgs)
+        arr, pointers = (struct * n)(*imgs), C.c_void_p * n
+        rc = getattr(lib, name)(self._h, arr, n, *[int(v) for v in ints], pointers(*out_ptrs), out_cap, pointers(*size_ptrs), *tail,
+                                C.c_void_p(stream))
+        if rc:
+            raise JpegAmdError(rc, name)
+
+    def encode_planar_batch_async(self, imgs, subsampling: int, out_ptrs, out_cap: int, size_ptrs, stream: int = 0):
+        """The files of `len(imgs)` planar pictures of one geometry (jpegamd_encode_planar_batch_async): subsampling 0 grayscale
+        files, SUBSAMPLE_444 / SUBSAMPLE_420 / SUBSAMPLE_422 colour files; the context as for the packed batch entries."""
+        self._batch("jpegamd_encode_planar_batch_async", PlanarImage, imgs, (subsampling,), out_ptrs, out_cap, size_ptrs, stream)
 
     def encode_ycbcr_batch_async(self, imgs, subsampling: int, out_ptrs, out_cap: int, size_ptrs, stream: int = 0,
                                  sample_range: int = RANGE_FULL, sample_format: int = SAMPLES_8, matrix: int = MATRIX_BT601):
@@ -992,214 +970,119 @@ class Encoder:
         for 10-bit samples in 16-bit words (strides in bytes), which go through jpegamd_encode_ycbcr_samples_batch_async and are
         narrowed on read.  matrix: MATRIX_BT601, or MATRIX_BT709 for BT.709 samples, which go through
         jpegamd_encode_ycbcr_matrix_batch_async: one pass converts them to BT.601 planes in context scratch."""
-        n = len(imgs)
-        arr = (YCbCrImage * n)(*imgs)
-        outs = (C.c_void_p * n)(*[C.c_void_p(p) for p in out_ptrs])
-        sizes = (C.c_void_p * n)(*[C.c_void_p(p) for p in size_ptrs])
-        if int(matrix) != MATRIX_BT601:              # (the BT.601 call keeps to the older entries, as below)
-            rc = lib.jpegamd_encode_ycbcr_matrix_batch_async(self._h, arr, n, int(subsampling), int(sample_range), int(sample_format),
-                                                             int(matrix), outs, out_cap, sizes, C.c_void_p(stream))
-            if rc:
-                raise JpegAmdError(rc, "jpegamd_encode_ycbcr_matrix_batch_async")
-            return
-        if int(sample_format) != SAMPLES_8:          # (one byte per sample keeps to the older entries, as below)
-            rc = lib.jpegamd_encode_ycbcr_samples_batch_async(self._h, arr, n, int(subsampling), int(sample_range), int(sample_format), outs,
-                                                              out_cap, sizes, C.c_void_p(stream))
-            if rc:
-                raise JpegAmdError(rc, "jpegamd_encode_ycbcr_samples_batch_async")
-            return
-        if int(sample_range) != RANGE_FULL:          # (the full-range call keeps to the older entry: a variant library without the new one still serves it)
-            rc = lib.jpegamd_encode_ycbcr_range_batch_async(self._h, arr, n, int(subsampling), int(sample_range), outs, out_cap, sizes,
-                                                            C.c_void_p(stream))
-            if rc:
-                raise JpegAmdError(rc, "jpegamd_encode_ycbcr_range_batch_async")
-            return
-        rc = lib.jpegamd_encode_ycbcr_batch_async(self._h, arr, n, int(subsampling), outs, out_cap, sizes, C.c_void_p(stream))
-        if rc:
-            raise JpegAmdError(rc, "jpegamd_encode_ycbcr_batch_async")
+        # The newest entry that the call needs: a call that an older entry can serve keeps to it, so that a variant library
+        # without the newer ones still serves it.
+        if int(matrix) != MATRIX_BT601:
+            name, ints = "jpegamd_encode_ycbcr_matrix_batch_async", (subsampling, sample_range, sample_format, matrix)
+        elif int(sample_format) != SAMPLES_8:
+            name, ints = "jpegamd_encode_ycbcr_samples_batch_async", (subsampling, sample_range, sample_format)
+        elif int(sample_range) != RANGE_FULL:
+            name, ints = "jpegamd_encode_ycbcr_range_batch_async", (subsampling, sample_range)
+        else:
+            name, ints = "jpegamd_encode_ycbcr_batch_async", (subsampling,)
+        self._batch(name, YCbCrImage, imgs, ints, out_ptrs, out_cap, size_ptrs, stream)
 
     def encode_async(self, img: Image, out_ptr: int, out_cap: int, size_ptr: int, with_container: bool = True,
                      stream: int = 0):
-        rc = lib.jpegamd_encode_async(self._h, C.byref(img), C.c_void_p(out_ptr), out_cap, C.c_void_p(size_ptr),
-                                      1 if with_container else 0, C.c_void_p(stream))
-        if rc:
-            raise JpegAmdError(rc, "jpegamd_encode_async")
+        _checked("jpegamd_encode_async", self._h, C.byref(img), C.c_void_p(out_ptr), out_cap, C.c_void_p(size_ptr),
+                 1 if with_container else 0, C.c_void_p(stream))
 
     def encode_color_async(self, img: Image, subsampling: int, out_ptr: int, out_cap: int, size_ptr: int, stream: int = 0):
         """The colour file of an RGB / BGR image (jpegamd_encode_color_async): SUBSAMPLE_444, SUBSAMPLE_420 or SUBSAMPLE_422."""
-        rc = lib.jpegamd_encode_color_async(self._h, C.byref(img), int(subsampling), C.c_void_p(out_ptr), out_cap, C.c_void_p(size_ptr),
-                                            C.c_void_p(stream))
-        if rc:
-            raise JpegAmdError(rc, "jpegamd_encode_color_async")
+        _checked("jpegamd_encode_color_async", self._h, C.byref(img), int(subsampling), C.c_void_p(out_ptr), out_cap, C.c_void_p(size_ptr),
+                 C.c_void_p(stream))
 
     def encode_color_batch_async(self, imgs, subsampling: int, out_ptrs, out_cap: int, size_ptrs, stream: int = 0):
         """The colour files of `len(imgs)` RGB / BGR pictures of one geometry (<= MAX_BATCH) with one launch of each kernel
         (jpegamd_encode_color_batch_async); the context must hold len(imgs) x the tiles and segments of one picture."""
-        n = len(imgs)
-        arr = (Image * n)(*imgs)
-        outs = (C.c_void_p * n)(*[C.c_void_p(p) for p in out_ptrs])
-        sizes = (C.c_void_p * n)(*[C.c_void_p(p) for p in size_ptrs])
-        rc = lib.jpegamd_encode_color_batch_async(self._h, arr, n, int(subsampling), outs, out_cap, sizes, C.c_void_p(stream))
-        if rc:
-            raise JpegAmdError(rc, "jpegamd_encode_color_batch_async")
+        self._batch("jpegamd_encode_color_batch_async", Image, imgs, (subsampling,), out_ptrs, out_cap, size_ptrs, stream)
 
     def encode_color_interleaved_batch_async(self, imgs, subsampling: int, out_ptrs, out_cap: int, size_ptrs, stream: int = 0):
         """The colour files of `len(imgs)` RGB / BGR pictures of one geometry (<= MAX_BATCH) with ONE scan of interleaved MCUs each
         (jpegamd_encode_color_interleaved_batch_async); the context as for encode_color_batch_async."""
-        n = len(imgs)
-        arr = (Image * n)(*imgs)
-        outs = (C.c_void_p * n)(*[C.c_void_p(p) for p in out_ptrs])
-        sizes = (C.c_void_p * n)(*[C.c_void_p(p) for p in size_ptrs])
-        rc = lib.jpegamd_encode_color_interleaved_batch_async(self._h, arr, n, int(subsampling), outs, out_cap, sizes, C.c_void_p(stream))
-        if rc:
-            raise JpegAmdError(rc, "jpegamd_encode_color_interleaved_batch_async")
+        self._batch("jpegamd_encode_color_interleaved_batch_async", Image, imgs, (subsampling,), out_ptrs, out_cap, size_ptrs, stream)
 
     def encode_ycbcr_interleaved_batch_async(self, imgs, subsampling: int, out_ptrs, out_cap: int, size_ptrs, stream: int = 0):
         """The same files from 8-bit full-range BT.601 YCbCr pictures in planes or byte pairs
         (jpegamd_encode_ycbcr_interleaved_batch_async)."""
-        n = len(imgs)
-        arr = (YCbCrImage * n)(*imgs)
-        outs = (C.c_void_p * n)(*[C.c_void_p(p) for p in out_ptrs])
-        sizes = (C.c_void_p * n)(*[C.c_void_p(p) for p in size_ptrs])
-        rc = lib.jpegamd_encode_ycbcr_interleaved_batch_async(self._h, arr, n, int(subsampling), outs, out_cap, sizes, C.c_void_p(stream))
-        if rc:
-            raise JpegAmdError(rc, "jpegamd_encode_ycbcr_interleaved_batch_async")
+        self._batch("jpegamd_encode_ycbcr_interleaved_batch_async", YCbCrImage, imgs, (subsampling,), out_ptrs, out_cap, size_ptrs, stream)
 
     def encode_color_interleaved_restart_batch_async(self, imgs, subsampling: int, restart_interval: int, out_ptrs, out_cap: int, size_ptrs,
                                                      stream: int = 0):
         """encode_color_interleaved_batch_async with restart intervals of `restart_interval` MCUs (DRI / RSTn; 0: the file without)
         (jpegamd_encode_color_interleaved_restart_batch_async)."""
-        n = len(imgs)
-        arr = (Image * n)(*imgs)
-        outs = (C.c_void_p * n)(*[C.c_void_p(p) for p in out_ptrs])
-        sizes = (C.c_void_p * n)(*[C.c_void_p(p) for p in size_ptrs])
-        rc = lib.jpegamd_encode_color_interleaved_restart_batch_async(self._h, arr, n, int(subsampling), int(restart_interval), outs, out_cap, sizes,
-                                                                      C.c_void_p(stream))
-        if rc:
-            raise JpegAmdError(rc, "jpegamd_encode_color_interleaved_restart_batch_async")
+        self._batch("jpegamd_encode_color_interleaved_restart_batch_async", Image, imgs, (subsampling, restart_interval), out_ptrs, out_cap,
+                    size_ptrs, stream)
 
     def encode_ycbcr_interleaved_restart_batch_async(self, imgs, subsampling: int, restart_interval: int, out_ptrs, out_cap: int, size_ptrs,
                                                      stream: int = 0):
         """encode_ycbcr_interleaved_batch_async with restart intervals (jpegamd_encode_ycbcr_interleaved_restart_batch_async)."""
-        n = len(imgs)
-        arr = (YCbCrImage * n)(*imgs)
-        outs = (C.c_void_p * n)(*[C.c_void_p(p) for p in out_ptrs])
-        sizes = (C.c_void_p * n)(*[C.c_void_p(p) for p in size_ptrs])
-        rc = lib.jpegamd_encode_ycbcr_interleaved_restart_batch_async(self._h, arr, n, int(subsampling), int(restart_interval), outs, out_cap, sizes,
-                                                                      C.c_void_p(stream))
-        if rc:
-            raise JpegAmdError(rc, "jpegamd_encode_ycbcr_interleaved_restart_batch_async")
+        self._batch("jpegamd_encode_ycbcr_interleaved_restart_batch_async", YCbCrImage, imgs, (subsampling, restart_interval), out_ptrs,
+                    out_cap, size_ptrs, stream)
 
     def encode_ycbcr_interleaved_matrix_batch_async(self, imgs, subsampling: int, sample_range: int, sample_format: int, matrix: int,
                                                     restart_interval: int, out_ptrs, out_cap: int, size_ptrs, stream: int = 0):
         """The one-scan files of YCbCr pictures of ANY kind encode_ycbcr_batch_async takes -- limited range, 10-bit words, BT.709, a
         packed 4:2:2 plane -- with restart intervals of `restart_interval` MCUs (0: none)
         (jpegamd_encode_ycbcr_interleaved_matrix_batch_async)."""
-        n = len(imgs)
-        arr = (YCbCrImage * n)(*imgs)
-        outs = (C.c_void_p * n)(*[C.c_void_p(p) for p in out_ptrs])
-        sizes = (C.c_void_p * n)(*[C.c_void_p(p) for p in size_ptrs])
-        rc = lib.jpegamd_encode_ycbcr_interleaved_matrix_batch_async(self._h, arr, n, int(subsampling), int(sample_range), int(sample_format),
-                                                                     int(matrix), int(restart_interval), outs, out_cap, sizes, C.c_void_p(stream))
-        if rc:
-            raise JpegAmdError(rc, "jpegamd_encode_ycbcr_interleaved_matrix_batch_async")
+        self._batch("jpegamd_encode_ycbcr_interleaved_matrix_batch_async", YCbCrImage, imgs,
+                    (subsampling, sample_range, sample_format, matrix, restart_interval), out_ptrs, out_cap, size_ptrs, stream)
 
     def encode_color_interleaved_pixels_batch_async(self, imgs, subsampling: int, restart_interval: int, out_ptrs, out_cap: int, size_ptrs,
                                                     stream: int = 0):
         """The one-scan files of RGB / BGR / RGBA / BGRA pictures, with restart intervals of `restart_interval` MCUs (0: none)
         (jpegamd_encode_color_interleaved_pixels_batch_async)."""
-        n = len(imgs)
-        arr = (Image * n)(*imgs)
-        outs = (C.c_void_p * n)(*[C.c_void_p(p) for p in out_ptrs])
-        sizes = (C.c_void_p * n)(*[C.c_void_p(p) for p in size_ptrs])
-        rc = lib.jpegamd_encode_color_interleaved_pixels_batch_async(self._h, arr, n, int(subsampling), int(restart_interval), outs, out_cap, sizes,
-                                                                     C.c_void_p(stream))
-        if rc:
-            raise JpegAmdError(rc, "jpegamd_encode_color_interleaved_pixels_batch_async")
+        self._batch("jpegamd_encode_color_interleaved_pixels_batch_async", Image, imgs, (subsampling, restart_interval), out_ptrs, out_cap,
+                    size_ptrs, stream)
 
     def encode_planar_interleaved_batch_async(self, imgs, subsampling: int, restart_interval: int, out_ptrs, out_cap: int, size_ptrs,
                                               stream: int = 0):
         """The one-scan files of planar pictures (planar_image), with restart intervals of `restart_interval` MCUs (0: none)
         (jpegamd_encode_planar_interleaved_batch_async); no grayscale files: subsampling 0 is refused."""
-        n = len(imgs)
-        arr = (PlanarImage * n)(*imgs)
-        outs = (C.c_void_p * n)(*[C.c_void_p(p) for p in out_ptrs])
-        sizes = (C.c_void_p * n)(*[C.c_void_p(p) for p in size_ptrs])
-        rc = lib.jpegamd_encode_planar_interleaved_batch_async(self._h, arr, n, int(subsampling), int(restart_interval), outs, out_cap, sizes,
-                                                               C.c_void_p(stream))
-        if rc:
-            raise JpegAmdError(rc, "jpegamd_encode_planar_interleaved_batch_async")
+        self._batch("jpegamd_encode_planar_interleaved_batch_async", PlanarImage, imgs, (subsampling, restart_interval), out_ptrs, out_cap,
+                    size_ptrs, stream)
 
     def color_profile(self, slot: int):
         """Per-kernel ns of a profiled colour encode: planes, (tile, merge, finalize) x Y / Cb / Cr, append."""
         ns = (C.c_uint64 * 11)()
-        rc = lib.jpegamd_debug_color_profile(self._h, slot, ns)
-        if rc:
-            raise JpegAmdError(rc, "jpegamd_debug_color_profile")
+        _checked("jpegamd_debug_color_profile", self._h, slot, ns)
         return list(ns)
 
     def encode_batch_async(self, imgs, out_ptrs, out_cap: int, size_ptrs, with_container: bool = True, stream: int = 0):
         """`len(imgs)` images of one geometry (<= MAX_BATCH) through ONE launch of each kernel; the context must hold
         len(imgs) x the tiles and segments of one image (e.g. Encoder(W, len(imgs) * H))."""
-        n = len(imgs)
-        arr = (Image * n)(*imgs)
-        outs = (C.c_void_p * n)(*[C.c_void_p(p) for p in out_ptrs])
-        sizes = (C.c_void_p * n)(*[C.c_void_p(p) for p in size_ptrs])
-        rc = lib.jpegamd_encode_batch_async(self._h, arr, n, outs, out_cap, sizes, 1 if with_container else 0, C.c_void_p(stream))
-        if rc:
-            raise JpegAmdError(rc, "jpegamd_encode_batch_async")
+        self._batch("jpegamd_encode_batch_async", Image, imgs, (), out_ptrs, out_cap, size_ptrs, stream, (1 if with_container else 0,))
 
     def encode_gray_scan_batch_async(self, imgs, restart_interval: int, out_ptrs, out_cap: int, size_ptrs, stream: int = 0):
         """The grayscale files of `len(imgs)` pictures of one geometry (<= MAX_BATCH; any channel order: the luma) with restart
         intervals of `restart_interval` blocks (0: none) and the context's Huffman tables (set_huffman)
         (jpegamd_encode_gray_scan_batch_async); out_cap from max_jfif_bytes_gray_scan."""
-        n = len(imgs)
-        arr = (Image * n)(*imgs)
-        outs = (C.c_void_p * n)(*[C.c_void_p(p) for p in out_ptrs])
-        sizes = (C.c_void_p * n)(*[C.c_void_p(p) for p in size_ptrs])
-        rc = lib.jpegamd_encode_gray_scan_batch_async(self._h, arr, n, int(restart_interval), outs, out_cap, sizes, C.c_void_p(stream))
-        if rc:
-            raise JpegAmdError(rc, "jpegamd_encode_gray_scan_batch_async")
+        self._batch("jpegamd_encode_gray_scan_batch_async", Image, imgs, (restart_interval,), out_ptrs, out_cap, size_ptrs, stream)
 
     # ---- one image sharded over GPUs by block rows (include/jpeg_compression.h) ----
     def encode_rows_async(self, img: Image, row_begin: int, row_end: int, stream: int = 0):
-        rc = lib.jpegamd_encode_rows_async(self._h, C.byref(img), C.c_int32(row_begin), C.c_int32(row_end), C.c_void_p(stream))
-        if rc:
-            raise JpegAmdError(rc, "jpegamd_encode_rows_async")
+        _checked("jpegamd_encode_rows_async", self._h, C.byref(img), C.c_int32(row_begin), C.c_int32(row_end), C.c_void_p(stream))
 
     def export_segments(self, img: Image, row_begin: int, row_end: int, dense_ptr: int, dense_cap_words: int, meta_ptr: int,
                         total_ptr: int, stream: int = 0):
-        rc = lib.jpegamd_export_segments(self._h, C.byref(img), C.c_int32(row_begin), C.c_int32(row_end), C.c_void_p(dense_ptr),
-                                         C.c_uint64(dense_cap_words), C.c_void_p(meta_ptr), C.c_void_p(total_ptr), C.c_void_p(stream))
-        if rc:
-            raise JpegAmdError(rc, "jpegamd_export_segments")
+        _checked("jpegamd_export_segments", self._h, C.byref(img), C.c_int32(row_begin), C.c_int32(row_end), C.c_void_p(dense_ptr),
+                 C.c_uint64(dense_cap_words), C.c_void_p(meta_ptr), C.c_void_p(total_ptr), C.c_void_p(stream))
 
     def import_segments(self, img: Image, row_begin: int, row_end: int, dense_ptr: int, meta_ptr: int, stream: int = 0):
-        rc = lib.jpegamd_import_segments(self._h, C.byref(img), C.c_int32(row_begin), C.c_int32(row_end), C.c_void_p(dense_ptr),
-                                         C.c_void_p(meta_ptr), C.c_void_p(stream))
-        if rc:
-            raise JpegAmdError(rc, "jpegamd_import_segments")
+        _checked("jpegamd_import_segments", self._h, C.byref(img), C.c_int32(row_begin), C.c_int32(row_end), C.c_void_p(dense_ptr),
+                 C.c_void_p(meta_ptr), C.c_void_p(stream))
 
     def finalize_async(self, img: Image, out_ptr: int, out_cap: int, size_ptr: int, with_container: bool = True, stream: int = 0):
-        rc = lib.jpegamd_finalize_async(self._h, C.byref(img), C.c_void_p(out_ptr), C.c_uint64(out_cap), C.c_void_p(size_ptr),
-                                        1 if with_container else 0, C.c_void_p(stream))
-        if rc:
-            raise JpegAmdError(rc, "jpegamd_finalize_async")
+        _checked("jpegamd_finalize_async", self._h, C.byref(img), C.c_void_p(out_ptr), C.c_uint64(out_cap), C.c_void_p(size_ptr),
+                 1 if with_container else 0, C.c_void_p(stream))
 
     def finish(self) -> Stats:
         st = Stats()
-        rc = lib.jpegamd_encoder_finish(self._h, C.byref(st))
-        if rc:
-            raise JpegAmdError(rc, "jpegamd_encoder_finish")
+        _checked("jpegamd_encoder_finish", self._h, C.byref(st))
         return st
 
     def debug_stages(self, img: Image, y_ptr: int = 0, zz_ptr: int = 0, mask_ptr: int = 0):
-        rc = lib.jpegamd_debug_stages(self._h, C.byref(img), C.c_void_p(y_ptr), C.c_void_p(zz_ptr),
-                                      C.c_void_p(mask_ptr))
-        if rc:
-            raise JpegAmdError(rc, "jpegamd_debug_stages")
+        _checked("jpegamd_debug_stages", self._h, C.byref(img), C.c_void_p(y_ptr), C.c_void_p(zz_ptr), C.c_void_p(mask_ptr))
 
     def debug_dct_exact(self, blocks_ptr: int, coeffs_ptr: int, nblocks: int):
-        rc = lib.jpegamd_debug_dct_exact(self._h, C.c_void_p(blocks_ptr), C.c_void_p(coeffs_ptr), nblocks)
-        if rc:
-            raise JpegAmdError(rc, "jpegamd_debug_dct_exact")
+        _checked("jpegamd_debug_dct_exact", self._h, C.c_void_p(blocks_ptr), C.c_void_p(coeffs_ptr), nblocks)

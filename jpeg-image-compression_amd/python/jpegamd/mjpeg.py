@@ -24,14 +24,8 @@ def encode_ycbcr_batch(y, cb, cr=None, quality: int = 0, subsampling: int = _j.S
     through jpegamd_encode_ycbcr_interleaved_matrix_batch_async."""
     huff = _j._huffman(huffman)
     rng, mat = _j._sample_range(sample_range), _j._matrix(matrix)
-    n, h, w, y_stride, c_stride, layout = _j._ycbcr_layout(y, cb, cr, subsampling, order)
-    ri = _j._restart(restart_interval, True, w, subsampling)
-    tensors = [y, cb] + ([cr] if cr is not None else [])
-    if any(not x.is_cuda or x.device != y.device for x in tensors):
-        raise ValueError("encode_ycbcr_batch needs device tensors on one device")
-    return _j._encode_ycbcr_images(y.device, n, h, w, subsampling, lambda i: _j.Encoder.ycbcr_image(
-        y[i].data_ptr(), cb[i].data_ptr(), cr[i].data_ptr() if cr is not None else 0, w, h, y_stride, c_stride, layout, quality), rng,
-        matrix=mat, interleaved=True, restart=ri, any_kind=True, huffman=huff)
+    return _j._encode_ycbcr_planes("encode_ycbcr_batch", _j._ycbcr_layout, y, cb, cr, quality, subsampling, order, restart_interval,
+                                   rng, matrix=mat, interleaved=True, any_kind=True, huffman=huff)
 
 
 def encode_ycbcr16_batch(y, cb, cr=None, quality: int = 0, subsampling: int = _j.SUBSAMPLE_420, order: str = "cbcr",
@@ -42,14 +36,9 @@ def encode_ycbcr16_batch(y, cb, cr=None, quality: int = 0, subsampling: int = _j
     rng, mat = _j._sample_range(sample_range), _j._matrix(matrix)
     if not isinstance(align, str) or align not in ("msb", "lsb"):
         raise ValueError(f'align must be "msb" or "lsb", not {align!r}')
-    n, h, w, y_stride, c_stride, layout = _j._ycbcr16_layout(y, cb, cr, subsampling, order)
-    ri = _j._restart(restart_interval, True, w, subsampling)
-    tensors = [y, cb] + ([cr] if cr is not None else [])
-    if any(not x.is_cuda or x.device != y.device for x in tensors):
-        raise ValueError("encode_ycbcr16_batch needs device tensors on one device")
-    return _j._encode_ycbcr_images(y.device, n, h, w, subsampling, lambda i: _j.Encoder.ycbcr_image(
-        y[i].data_ptr(), cb[i].data_ptr(), cr[i].data_ptr() if cr is not None else 0, w, h, y_stride, c_stride, layout, quality), rng,
-        _j.SAMPLES_10_MSB if align == "msb" else _j.SAMPLES_10_LSB, mat, interleaved=True, restart=ri, any_kind=True, huffman=huff)
+    return _j._encode_ycbcr_planes("encode_ycbcr16_batch", _j._ycbcr16_layout, y, cb, cr, quality, subsampling, order, restart_interval,
+                                   rng, _j.SAMPLES_10_MSB if align == "msb" else _j.SAMPLES_10_LSB, mat, interleaved=True, any_kind=True,
+                                   huffman=huff)
 
 
 def encode_yuyv_batch(frames, quality: int = 0, order: str = "yuyv", sample_range: str = "full", matrix: str = "bt601",
@@ -57,13 +46,7 @@ def encode_yuyv_batch(frames, quality: int = 0, order: str = "yuyv", sample_rang
     """jpegamd.encode_yuyv_batch's packed 4:2:2 frames (YUY2 / UYVY) -> N one-scan files at SUBSAMPLE_422."""
     huff = _j._huffman(huffman)
     rng, mat = _j._sample_range(sample_range), _j._matrix(matrix)
-    n, h, w, stride, layout = _j._yuyv_layout(frames, order)
-    ri = _j._restart(restart_interval, True, w, _j.SUBSAMPLE_422)
-    if not frames.is_cuda:
-        raise ValueError("encode_yuyv_batch needs a device tensor")
-    return _j._encode_ycbcr_images(frames.device, n, h, w, _j.SUBSAMPLE_422, lambda i: _j.Encoder.ycbcr_image(
-        frames[i].data_ptr(), 0, 0, w, h, stride, 0, layout, quality), rng, matrix=mat, interleaved=True, restart=ri, any_kind=True,
-        huffman=huff)
+    return _j._encode_yuyv_frames(frames, quality, order, restart_interval, rng, mat, interleaved=True, any_kind=True, huffman=huff)
 
 
 def encode_tensor_batch(t, quality: int = 0, subsampling: int = _j.SUBSAMPLE_420, layout=None, restart_interval=None,
