@@ -506,6 +506,52 @@ int32_t jpegamd_encode_gray_scan_batch_async(JpegAmdEncoder *enc, const JpegAmdI
                                              void *const *outs_dev, uint64_t out_capacity, uint64_t *const *out_sizes_dev, void *stream);
 uint64_t jpegamd_max_jfif_bytes_gray_scan(int32_t width, int32_t height, int32_t restart_interval);
 
+/* Progressive colour files (SOF2): seven scans by spectral selection, no successive approximation (Ah = Al = 0 in every scan).  The
+ * file holds the coefficients of the one-scan file of the same input (jpegamd_encode_color_interleaved_pixels_batch_async,
+ * jpegamd_encode_ycbcr_interleaved_matrix_batch_async), so a decoder reconstructs the same pixels.  What this version gives is the
+ * progressive rendering; the file is a little LARGER than the one-scan file (six more SOS headers, an end-of-band symbol per block
+ * and band, seven flushes), because no end-of-band runs are coded.
+ *   Layout.  The one-scan file's prefix up to and including its four Annex K DHT segments, with ONE change: the frame header's
+ *     marker is FF C2 where that file has FF C0 (length, contents and the sampling factors 0x11 / 0x22 / 0x21 stay).  Then seven
+ *     scans, each an SOS segment and a byte-aligned entropy-coded segment, then EOI:
+ *       scan 1      Y, Cb, Cr interleaved, Ss..Se = 0..0     FF DA 00 0C 03 01 00 02 11 03 11 00 00 00
+ *       scan 2 3 4  Y, Cb, Cr (one each),  Ss..Se = 1..5     FF DA 00 08 01 cc tt 01 05 00   (tt = 00 for Y, 11 for Cb and Cr)
+ *       scan 5 6 7  Y, Cb, Cr (one each),  Ss..Se = 6..63    FF DA 00 08 01 cc tt 06 3F 00
+ *   Scan 1, the DC scan.  The MCU order, the pad blocks and the per-component predictors of the one-scan file; a pad block's DC is
+ *     the DC of the nearest real block.  Every block codes its DC difference alone, with its component's DC table: no AC symbol, no EOB.
+ *   Scans 2 - 7.  The blocks of the component's OWN block grid in raster order: bw x bh for Y -- no pad blocks --, mx x my for Cb
+ *     and Cr.  A block codes its coefficients Ss .. Se as T.81 G.1.2.2 defines them, with the component's Annex K AC table: the zero
+ *     run is 0 at Ss; sixteen zeros are ZRL (0xF0); the block ends with symbol 0x00 -- EOB0, an end-of-band run of exactly one block --
+ *     when coefficient Se is zero, and with no end symbol when it is not.  NO end-of-band run longer than one block is coded: the
+ *     Annex K tables hold no EOBn symbol for n >= 1.
+ *   Every scan.  A 0x00 behind every 0xFF; the last byte padded with zero bits; no restart intervals.
+ * jpegamd_encode_color_progressive_batch_async takes the pictures of jpegamd_encode_color_interleaved_pixels_batch_async (BGR, RGB,
+ * RGBA, BGRA), jpegamd_encode_ycbcr_progressive_batch_async everything jpegamd_encode_ycbcr_interleaved_matrix_batch_async reads,
+ * with the same sample_range, sample_format and matrix.  Each refuses what its one-scan twin refuses, and JPEGAMD_ORDER_GRAY, and a
+ * context set to JPEGAMD_HUFFMAN_OPTIMIZED (per-scan optimised tables are not written yet): JPEGAMD_ERR_ARG with nothing allocated
+ * or launched.  Batching, context sizing, capacity handling and profiling are the one-scan entries': a picture that does not fit
+ * out_capacity gets size 0, nothing is written past out_capacity (what was written of its first scan stays in the buffer), the other
+ * pictures are unaffected, jpegamd_encoder_finish returns JPEGAMD_ERR_HUFF_CAPACITY and the context stays usable.  finish reports
+ * the coded bits and stuffed bytes summed over the seven scans of every picture of the call, exact_fallbacks of the three tap
+ * launches counted once, and the last picture's file size.  The scans 2 - 7 are staged in context scratch at their worst-case
+ * sizes (about 425 bytes per block of every component: 1.3 GiB for an 8192 x 8192 picture at 4:4:4), which counts into the 4 GiB budget that groups the pictures of a call.
+ * The bound.  jpegamd_max_jfif_bytes_progressive = jpegamd_max_jfif_bytes_interleaved + 6 * (10 + 2).  That bound takes every block
+ * of every MCU, pad blocks too, at 22 + 63 x 27 = 1723 bits, every byte stuffed, one rounding up to a byte, and EOI.  Here a block's
+ * DC difference is at most 11 + 11 bits, and a band costs at most 27 bits per coefficient -- every non-zero coefficient is one
+ * symbol of at most 16 + 11 bits, a ZRL of at most 11 bits pays for sixteen zero coefficients, the EOB for the zero coefficient
+ * Se --, so the bands 1..5 and 6..63 are at most 135 and 1566 bits and the three together 1723: what the seven scans code of a
+ * block (pad blocks: the DC alone) costs no more than that bound allows it.  Six more SOS segments add 6 * 10 bytes; seven scans
+ * round up to a byte seven times where the one scan rounds once -- at most six more bytes, each of which may be stuffed: 6 * 2.
+ * 0 for bad arguments (a dimension outside 1 .. 65535, an invalid subsampling). */
+int32_t jpegamd_encode_color_progressive_batch_async(JpegAmdEncoder *enc, const JpegAmdImage *imgs, int32_t count, int32_t subsampling,
+                                                     void *const *outs_dev, uint64_t out_capacity, uint64_t *const *out_sizes_dev,
+                                                     void *stream);
+int32_t jpegamd_encode_ycbcr_progressive_batch_async(JpegAmdEncoder *enc, const JpegAmdYCbCrImage *imgs, int32_t count, int32_t subsampling,
+                                                     int32_t sample_range, int32_t sample_format, int32_t matrix,
+                                                     void *const *outs_dev, uint64_t out_capacity, void *const *out_sizes_dev,
+                                                     void *stream);
+uint64_t jpegamd_max_jfif_bytes_progressive(int32_t width, int32_t height, int32_t subsampling);
+
 /* Block until the last enqueued encode on this context finished; optionally fetch stats
  * (stats may be NULL).  Returns JPEGAMD_ERR_HUFF_CAPACITY if the output did not fit. */
 int32_t jpegamd_encoder_finish(JpegAmdEncoder *enc, JpegAmdStats *stats);

@@ -40,8 +40,13 @@ struct CtxLimits {
 struct HeaderCache {
     int w, h, q, sub, len;
     int restart;                        // the interval of the DRI segment (files with one: the interleaved path's); 0: none
-    bool matches(int w_, int h_, int q_, int sub_, int restart_ = 0) const { return w == w_ && h == h_ && q == q_ && sub == sub_ && restart == restart_; }
-    void set(int w_, int h_, int q_, int sub_, int len_, int restart_ = 0) { w = w_; h = h_; q = q_; sub = sub_; len = len_; restart = restart_; }
+    int progressive;                    // 1: the prefix of a progressive file (SOF2, the DC scan's SOS: the interleaved path's); 0: baseline
+    bool matches(int w_, int h_, int q_, int sub_, int restart_ = 0, int progressive_ = 0) const {
+        return w == w_ && h == h_ && q == q_ && sub == sub_ && restart == restart_ && progressive == progressive_;
+    }
+    void set(int w_, int h_, int q_, int sub_, int len_, int restart_ = 0, int progressive_ = 0) {
+        w = w_; h = h_; q = q_; sub = sub_; len = len_; restart = restart_; progressive = progressive_;
+    }
 };
 
 struct JpegAmdEncoder {
@@ -127,6 +132,10 @@ struct JpegAmdEncoder {
         uint8_t *hres = nullptr;            // [4 hcap][kHuffResBytes] BITS / HUFFVAL as k_huff_optimal leaves them
         int hcap = 0;                       // pictures
         int hlast = 0;                      // pictures of the last optimised call: hcounts[0, hlast) are theirs
+        // progressive files (jpegamd_encode_*_progressive_batch_async): nothing of this is allocated before the first such call
+        uint8_t *pmeta = nullptr;           // ProgMeta: k_finalize's records, the scans' sizes and sums, the six SOS segments
+        uint8_t *pslots = nullptr;          // the scans 2 .. 7 of one group of pictures
+        size_t pslots_cap = 0;
     } mcu;
 };
 
@@ -360,6 +369,7 @@ extern "C" int32_t jpegamd_encoder_destroy(JpegAmdEncoder *e) {
     hipFree(e->color.bmeta); hipFree(e->color.bplanes); hipFree(e->color.bscans);
     hipFree(e->mcu.coef); hipFree(e->mcu.hdr); hipFree(e->mcu.scan_stats);
     hipFree(e->mcu.rst_words); hipFree(e->mcu.rst_pos); hipFree(e->mcu.rst_pic_sums);
+    hipFree(e->mcu.pmeta); hipFree(e->mcu.pslots);
     hipFree(e->mcu.hcounts); hipFree(e->mcu.htabs); hipFree(e->mcu.hprefix); hipFree(e->mcu.hprefix_len); hipFree(e->mcu.hres);
     free_seg_arrays(&e->mcu.seg);
     destroy_ring_events(e);
@@ -1591,6 +1601,38 @@ extern "C" uint64_t jpegamd_max_jfif_bytes_interleaved_restart(int32_t width, in
 constexpr int kMcuSosBytes = 14;
 constexpr size_t kMcuScratchBudget = (size_t)4 << 30;       // coefficient planes + segment strings of one group of pictures
 
+// ---- progressive files ----
+// What a progressive call keeps on the device besides the slots: k_finalize's two records (scan 1's; the scans into slots share the
+// other), every scan's size and sums per picture of the group, and the SOS segments of the scans 2 .. 7, 16 bytes apart.
+struct ProgMeta {
+    ScanStats scan_stats[2];
+    uint64_t size[kProgScans][kMaxBatch];
+    unsigned long long sums[kProgScans][kMaxBatch][2];
+    uint8_t sos[kProgScans][16];
+};
+// Scan k (from 0) of a progressive file: k = 0 the DC scan, then component (k - 1) % 3 of band (k - 1) / 3.
+// The slots of the scans 2 .. 7 of one picture: each holds SOS, the scan at its bound (every block of the component's plane at the
+// band's worst case, every byte stuffed, the flush byte), EOI, and what k_scans_concat reads behind them in 16-byte steps.
+struct ProgSlots { uint64_t off[kProgScans], cap[kProgScans], pic_bytes; };
+static ProgSlots prog_slots(const McuGeometry &g) {
+    ProgSlots s = {};
+    for (int k = 1; k < kProgScans; ++k) {
+        const uint64_t nb = (k - 1) % 3 == 0 ? (uint64_t)g.bw * g.bh : (uint64_t)g.mx * g.my;
+        s.cap[k] = kSosBytes + scan_bound(nb, prog_band_bits((k - 1) / 3)) + 2;
+        s.off[k] = s.pic_bytes;
+        s.pic_bytes += round_up((size_t)s.cap[k] + 64, 256);
+    }
+    return s;
+}
+
+extern "C" uint64_t jpegamd_max_jfif_bytes_progressive(int32_t width, int32_t height, int32_t subsampling) {
+    // The one-scan bound holds every block of every MCU (pad blocks too) at kMaxBlockBitsColor bits -- no less than its DC
+    // difference and its two bands cost together (prog_band_bits) --, every byte stuffed, ONE rounding up to a byte, and EOI.
+    // Seven scans add six SOS segments of kSosBytes, and six more roundings of at most one byte each, which may be stuffed.
+    const uint64_t plain = jpegamd_max_jfif_bytes_interleaved(width, height, subsampling);
+    return plain ? plain + (uint64_t)(kProgScans - 1) * (kSosBytes + 2) : 0;
+}
+
 // The path's scratch for `group` pictures of geometry g: allocated on the first call, grown when a call needs more.
 // `writer`: the restart writer's arrays as well.  `own_tables`: the scratch of `own_tables` pictures with tables of their own.
 static int32_t mcu_alloc(JpegAmdEncoder *e, const McuGeometry &g, int group, bool writer, int own_tables) {
@@ -1635,10 +1677,12 @@ static int32_t mcu_alloc(JpegAmdEncoder *e, const McuGeometry &g, int group, boo
 
 // The colour prefix up to its DHTs, [DRI with the restart interval,] then the SOS of all three components (Y: tables 0 / 0, Cb and
 // Cr: 1 / 1).  One component (kSubNone): the grayscale prefix up to its two DHTs, [DRI,] its SOS.
-static int32_t prepare_mcu_prefix(JpegAmdEncoder *e, const JpegAmdImage *img, int sub, int restart) {
+// progressive (colour, no restart intervals): the frame header's marker is SOF2, and the SOS is the DC scan's (Ss = Se = 0).
+constexpr int kColorSofOffset = 2 + 18 + 134;       // SOI, APP0, DQT with two tables
+static int32_t prepare_mcu_prefix(JpegAmdEncoder *e, const JpegAmdImage *img, int sub, int restart, bool progressive = false) {
     auto &m = e->mcu;
     const int q = clamp_quality(img->quality);
-    if (m.hdr_for.matches(img->width, img->height, q, sub, restart)) return JPEGAMD_OK;
+    if (m.hdr_for.matches(img->width, img->height, q, sub, restart, progressive ? 1 : 0)) return JPEGAMD_OK;
     uint8_t luma[64], chroma[64], hdr[kColorPrefixMax + kMcuDriBytes + kMcuSosBytes];
     quant_table_for_quality(q, luma);
     size_t n, nsos;
@@ -1658,11 +1702,84 @@ static int32_t prepare_mcu_prefix(JpegAmdEncoder *e, const JpegAmdImage *img, in
         std::memcpy(hdr + n, dri, sizeof(dri));
         n += sizeof(dri);
     }
+    if (progressive) {
+        if (sub == kSubNone || restart || hdr[kColorSofOffset] != 0xFF || hdr[kColorSofOffset + 1] != 0xC0) return JPEGAMD_ERR_ARG;
+        hdr[kColorSofOffset + 1] = 0xC2;
+        sos[kMcuSosBytes - 2] = 0x00;                                   // Se
+    }
     std::memcpy(hdr + n, sos, nsos);
     if (int32_t rc = wait_pending(e)) return rc;
     HIP_TRY(hipMemcpy(m.hdr, hdr, n + nsos, hipMemcpyHostToDevice));
-    m.hdr_for.set(img->width, img->height, q, sub, (int)(n + nsos), restart);
+    m.hdr_for.set(img->width, img->height, q, sub, (int)(n + nsos), restart, progressive ? 1 : 0);
     return JPEGAMD_OK;
+}
+
+// The scratch of a progressive call: the records (made once, with the SOS segments of the scans 2 .. 7) and `slot_bytes` of slots.
+static int32_t prog_alloc(JpegAmdEncoder *e, size_t slot_bytes) {
+    auto &m = e->mcu;
+    if (!m.pmeta) {
+        HIP_TRY(hipMalloc((void **)&m.pmeta, sizeof(ProgMeta)));
+        uint8_t sos[kProgScans][16] = {};
+        for (int k = 1; k < kProgScans; ++k) {
+            color_sos(1 + (k - 1) % 3, sos[k]);
+            sos[k][7] = (uint8_t)kProgBandSs[(k - 1) / 3]; sos[k][8] = (uint8_t)kProgBandSe[(k - 1) / 3];
+        }
+        HIP_TRY(hipMemcpy(m.pmeta + offsetof(ProgMeta, sos), sos, sizeof(sos), hipMemcpyHostToDevice));
+    }
+    return grow_scratch(e, &m.pslots, &m.pslots_cap, slot_bytes);
+}
+
+// The seven scans of the progressive files of one group of pictures, [first, first + n) of the call, whose coefficient planes the taps
+// left in m.coef: one after the other on the stream over the path's one set of segment arrays.  `sa`: the group's arguments of the
+// three-component coder (the DC scan's as they are).  Scan 1 goes through k_finalize behind the file's prefix into the caller's
+// buffers, the others behind their SOS into the pictures' slots; k_scans_concat joins them.
+static int progressive_scans(JpegAmdEncoder *e, const McuGeometry &g, const ProgSlots &slots, const McuSegArgs &sa3, const ImageDesc &iy, int first,
+                             int n, bool last_of_call, void *const *outs_dev, uint64_t out_capacity, uint64_t *const *out_sizes_dev,
+                             const unsigned long long *pic, hipStream_t stream) {
+    auto &m = e->mcu;
+    ProgMeta *meta = reinterpret_cast<ProgMeta *>(m.pmeta);
+    if (hipMemsetAsync(m.pmeta, 0, offsetof(ProgMeta, sos), stream) != hipSuccess) return (int)hipErrorUnknown;
+    for (int k = 0; k < kProgScans; ++k) {
+        const int comp = k ? (k - 1) % 3 : 0, band = k ? (k - 1) / 3 : 0;
+        McuSegArgs sa = sa3;
+        if (k) {                                                         // ONE component: its plane, its block grid, its table class
+            sa.coef = sa3.coef + (comp == 0 ? 0 : (comp == 1 ? sa3.cb_off : sa3.cr_off));
+            sa.bw = sa.mx = comp ? g.mx : g.bw; sa.bh = sa.my = comp ? g.my : g.bh;
+            sa.hs = sa.vs = 1; sa.comps = 1;
+            sa.seg_mcus = mcu_seg_mcus(1, 1, 1);
+            sa.num_segs = (int)(((int64_t)sa.bw * sa.bh + sa.seg_mcus - 1) / sa.seg_mcus);
+            sa.num_segs_pad = (sa.num_segs + kSegGroup - 1) / kSegGroup * kSegGroup;
+            if (sa.num_segs_pad > g.num_segs_pad) return (int)hipErrorInvalidValue;     // (a plane has fewer segments than the MCU scan: the arrays hold them)
+            if (comp) sa.huff_y = sa3.huff_c;
+            sa.ss = kProgBandSs[band]; sa.se = kProgBandSe[band];
+        }
+        sa.sums = &meta->sums[k][0][0];
+        sa.status = &meta->scan_stats[k ? 1 : 0].status;
+        if (int err = launch_mcu_band_segments(sa, stream)) return err;
+
+        ImageDesc is = iy;                                               // what run_finalize reads of it: the segments per picture and their length
+        is.num_segs = sa.num_segs_pad; is.seg_tiles = kSegTiles;
+        void *outs[kMaxBatch];
+        uint64_t *sizes[kMaxBatch];
+        for (int i = 0; i < n; ++i) {
+            outs[i] = k ? (void *)(m.pslots + (size_t)i * slots.pic_bytes + slots.off[k]) : outs_dev[first + i];
+            sizes[i] = &meta->size[k][i];
+        }
+        const ScanTarget tgt = {k ? meta->sos[k] : m.hdr, k ? kSosBytes : m.hdr_for.len, k == kProgScans - 1 ? 1 : 0, &meta->scan_stats[k ? 1 : 0], false, &m.seg};
+        if (int err = run_finalize(e, is, outs, k ? slots.cap[k] : out_capacity, sizes, 1, stream, nullptr, n, false, &tgt)) return err;
+    }
+    ScansConcatArgs ca;
+    std::memset(&ca, 0, sizeof(ca));
+    for (int i = 0; i < n; ++i) { ca.out[i] = (uint8_t *)outs_dev[first + i]; ca.out_size[i] = out_sizes_dev[first + i]; }
+    ca.out_capacity = out_capacity;
+    ca.batch = n; ca.prefix_len = m.hdr_for.len; ca.last_of_call = last_of_call ? 1 : 0;
+    ca.size = &meta->size[0][0];
+    ca.slots = m.pslots; ca.pic_bytes = slots.pic_bytes;
+    for (int k = 0; k < kProgScans; ++k) ca.slot_off[k] = slots.off[k];
+    ca.sums = &meta->sums[0][0][0];
+    ca.pic = pic;
+    ca.scan_stats = meta->scan_stats; ca.stats = e->stats_dev;
+    return launch_scans_concat(ca, stream);
 }
 
 // The interleaved files of a batch whose arguments are known to be good: g0 describes every picture, px holds their pixels (any
@@ -1675,7 +1792,10 @@ static int32_t prepare_mcu_prefix(JpegAmdEncoder *e, const JpegAmdImage *img, in
 // tapped and coded, no chroma launch, two tables; always through the restart writer (the caller sends the plain Annex K file elsewhere).
 static int32_t interleaved_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, const PlaneSet &px, int32_t count, int32_t subsampling, int32_t restart,
                                  void *const *outs_dev, uint64_t out_capacity, uint64_t *const *out_sizes_dev, void *stream_,
-                                 const YccSource *ycc_in = nullptr) {
+                                 const YccSource *ycc_in = nullptr, bool progressive = false) {
+    // `progressive`: the same taps, plane pass, matrix pass and grouping; behind a group's taps its seven scans
+    // (progressive_scans) in place of k_mcu_segments, k_finalize and k_mcu_totals.  Colour, the Annex K tables, no restart intervals.
+    if (progressive && (restart || subsampling == kSubNone || e->huffman != JPEGAMD_HUFFMAN_STANDARD)) return JPEGAMD_ERR_ARG;
     const bool mx = ycc_in && ycc_in->matrix == JPEGAMD_MATRIX_BT709;
     const YccSource *const ycc = mx ? nullptr : ycc_in;               // what the launches read: the caller's planes, or the scratch
     const bool planar = g0.channel_order == kOrderPlanar;
@@ -1703,7 +1823,8 @@ static int32_t interleaved_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, cons
     if (rc) return rc;
     if (iy.blocks_w != g.bw || iy.blocks_h != g.bh || (!gray && (ic.blocks_w != g.mx || ic.blocks_h != g.my))) return JPEGAMD_ERR_ARG;
 
-    const size_t per_pic = (size_t)mcu_scratch_per_pic(g, writer);
+    const ProgSlots slots = progressive ? prog_slots(g) : ProgSlots{};
+    const size_t per_pic = (size_t)mcu_scratch_per_pic(g, writer) + (size_t)slots.pic_bytes;
     const int group = (int)std::max<size_t>(1, std::min<size_t>((size_t)count, kMcuScratchBudget / per_pic));
     rc = color_alloc_consts(e);
     if (rc) return rc;
@@ -1715,10 +1836,14 @@ static int32_t interleaved_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, cons
     if (rc) return rc;
     rc = gray ? JPEGAMD_OK : prepare_color_constants(e, &g0, subsampling);
     if (rc) return rc;
-    rc = prepare_mcu_prefix(e, &g0, subsampling, restart);
+    rc = prepare_mcu_prefix(e, &g0, subsampling, restart, progressive);
     if (rc) return rc;
     auto &c = e->color;
     auto &m = e->mcu;
+    if (progressive) {
+        rc = prog_alloc(e, (size_t)group * (size_t)slots.pic_bytes);
+        if (rc) return rc;
+    }
     unsigned long long *pic = reinterpret_cast<unsigned long long *>(c.bmeta + kBatchMetaStats);
     hipStream_t stream = (hipStream_t)stream_;
 
@@ -1774,6 +1899,12 @@ static int32_t interleaved_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, cons
         sa.status = &m.scan_stats->status;
         sa.restart = restart; sa.segs_per_interval = restart ? g.segs_per_interval : 0;
         sa.comps = g.comps;
+        if (progressive) {
+            if (progressive_scans(e, g, slots, sa, iy, first, n, first + n == count, outs_dev, out_capacity, out_sizes_dev,
+                                  pic + (size_t)first * kPicStatWords, stream))
+                return JPEGAMD_ERR_HIP;
+            continue;
+        }
         if (optimized) {                                             // the group's pictures are [first, first + n) of the call's table scratch
             unsigned long long *counts = m.hcounts + (size_t)first * kMcuTabWords;
             HIP_TRY(hipMemsetAsync(counts, 0, (size_t)n * kMcuTabWords * sizeof(unsigned long long), stream));
@@ -1894,7 +2025,8 @@ static bool restart_valid(int32_t restart) { return restart >= 0 && restart <= 6
 
 // `count` packed pictures in one scan: the argument checks (`px4`: the entry takes RGBA / BGRA as well), then the interleaved batch.
 static int32_t interleaved_pixels(JpegAmdEncoder *e, const JpegAmdImage *imgs, int32_t count, int32_t subsampling, int32_t restart_interval, bool px4,
-                                  void *const *outs_dev, uint64_t out_capacity, uint64_t *const *out_sizes_dev, void *stream_) {
+                                  void *const *outs_dev, uint64_t out_capacity, uint64_t *const *out_sizes_dev, void *stream_,
+                                  bool progressive = false) {
     // the arguments first: nothing of the context is read before they are known to be good
     if (!restart_valid(restart_interval)) return JPEGAMD_ERR_ARG;
     if (!e || !imgs || !outs_dev || !out_sizes_dev || count < 1 || count > kMaxBatch) return JPEGAMD_ERR_ARG;
@@ -1906,7 +2038,16 @@ static int32_t interleaved_pixels(JpegAmdEncoder *e, const JpegAmdImage *imgs, i
         return JPEGAMD_ERR_ARG;
     PlaneSet ps;
     if (int32_t rc = uniform_batch_args(imgs, count, outs_dev, out_sizes_dev, &ps)) return rc;
-    return interleaved_batch(e, g0, ps, count, subsampling, restart_interval, outs_dev, out_capacity, out_sizes_dev, stream_);
+    return interleaved_batch(e, g0, ps, count, subsampling, restart_interval, outs_dev, out_capacity, out_sizes_dev, stream_, nullptr, progressive);
+}
+
+// Progressive colour files of `count` RGB / BGR / RGBA / BGRA pictures: the argument checks of
+// jpegamd_encode_color_interleaved_pixels_batch_async, then the interleaved batch with its seven scans.  A context set to
+// JPEGAMD_HUFFMAN_OPTIMIZED is refused (interleaved_batch: before anything is allocated or launched).
+extern "C" int32_t jpegamd_encode_color_progressive_batch_async(JpegAmdEncoder *e, const JpegAmdImage *imgs, int32_t count, int32_t subsampling,
+                                                                void *const *outs_dev, uint64_t out_capacity, uint64_t *const *out_sizes_dev,
+                                                                void *stream_) {
+    return interleaved_pixels(e, imgs, count, subsampling, 0, true, outs_dev, out_capacity, out_sizes_dev, stream_, true);
 }
 
 extern "C" int32_t jpegamd_encode_color_interleaved_restart_batch_async(JpegAmdEncoder *e, const JpegAmdImage *imgs, int32_t count, int32_t subsampling,
@@ -1999,6 +2140,20 @@ extern "C" int32_t jpegamd_encode_ycbcr_interleaved_matrix_batch_async(JpegAmdEn
     if (int32_t rc = ycbcr_args(e, imgs, count, subsampling, sample_range, sample_format, matrix, outs_dev, out_sizes_dev, true, &g0, &ps, &ycc, sizes))
         return rc;
     return interleaved_batch(e, g0, ps, count, subsampling, restart_interval, outs_dev, out_capacity, sizes, stream_, &ycc);
+}
+
+// ... and their progressive files: the same argument checks, then the interleaved batch with its seven scans.
+extern "C" int32_t jpegamd_encode_ycbcr_progressive_batch_async(JpegAmdEncoder *e, const JpegAmdYCbCrImage *imgs, int32_t count, int32_t subsampling,
+                                                                int32_t sample_range, int32_t sample_format, int32_t matrix,
+                                                                void *const *outs_dev, uint64_t out_capacity, void *const *out_sizes_dev,
+                                                                void *stream_) {
+    JpegAmdImage g0;
+    PlaneSet ps;
+    YccSource ycc;
+    uint64_t *sizes[kMaxBatch];
+    if (int32_t rc = ycbcr_args(e, imgs, count, subsampling, sample_range, sample_format, matrix, outs_dev, out_sizes_dev, true, &g0, &ps, &ycc, sizes))
+        return rc;
+    return interleaved_batch(e, g0, ps, count, subsampling, 0, outs_dev, out_capacity, sizes, stream_, &ycc, true);
 }
 
 // Host-only (tests): whether the plain build has the k_tile_encode instantiation (taps, layout, chroma tables, expand): 1 or 0.  No

@@ -415,8 +415,41 @@ struct McuSegArgs {
     uint32_t *status;                   // ScanStats::status: bit 1 = a count that did not fit its 16 bits
     int32_t restart, segs_per_interval; // 0, 0: no restart intervals
     int32_t comps;                      // components of the scan: 3, or 1 (hs = vs = 1, mx = bw, my = bh; cb_off, cr_off and huff_c are not read)
+    // launch_mcu_band_segments alone (a scan of a progressive file; k_mcu_segments reads none of these):
+    int32_t ss, se;                     // the band, uniform over the launch: 0, 0 the DC scan (comps = 3), 1 <= ss <= se <= 63 an AC scan (comps = 1)
+    unsigned long long *sums;           // [batch][2]: every segment's bits and symbols are ADDED to its picture's pair (the caller zeroed them)
 };
 int launch_mcu_segments(const McuSegArgs &a, void *stream);
+
+// Progressive colour files: kProgScans scans by spectral selection, Ah = Al = 0 -- the DC scan of the three
+// components in MCU order (the segments, pad blocks and predictors of the one-scan file), then the bands 1 .. 5 and 6 .. 63 of Y, Cb
+// and Cr, each a scan of ONE component over its plane's blocks in raster order (comps = 1: coef points at the plane, bw x bh is ITS
+// block grid, huff_y ITS table class).  launch_mcu_band_segments codes one scan into the segment arrays; the unchanged k_finalize
+// writes it -- scan 1 behind the file's prefix into the caller's buffer, the others behind their SOS into slots of context scratch --
+// and k_scans_concat puts the slots behind scan 1 when the whole file fits, writes the size word and adds up the call's record.
+// A block of a band is at most 27 bits per coefficient of the band (a ZRL pays for sixteen zeros, EOB for a zero coefficient se),
+// a DC difference at most 11 + 11 bits: together no more than kMaxBlockBitsColor, the bound of a whole block.
+constexpr int kProgScans = 7;
+constexpr int kProgBandSs[2] = {1, 6}, kProgBandSe[2] = {5, 63};
+constexpr int prog_band_bits(int band) { return (kProgBandSe[band] - kProgBandSs[band] + 1) * 27; }
+static_assert(22 + prog_band_bits(0) + prog_band_bits(1) == kMaxBlockBitsColor, "the three bands of a block cost no more than the block's bound");
+int launch_mcu_band_segments(const McuSegArgs &a, void *stream);
+struct ScansConcatArgs {
+    uint8_t *out[kMaxBatch];
+    uint64_t *out_size[kMaxBatch];
+    uint64_t out_capacity;
+    int32_t batch;
+    int32_t prefix_len;                 // bytes in front of scan 1's entropy-coded segment: the file's prefix with SOS 1
+    int32_t last_of_call;               // the launch's last picture is the call's last: its size is what finish reports
+    const uint64_t *size;               // [kProgScans][kMaxBatch] k_finalize's: scan 1 with the prefix, the others with their SOS, the last with EOI
+    const uint8_t *slots;               // scan k >= 1 (from 0) of picture q at slots + q pic_bytes + slot_off[k]; multiples of 16
+    uint64_t pic_bytes, slot_off[kProgScans];
+    const unsigned long long *sums;     // [kProgScans][kMaxBatch][2] coded bits and symbols (launch_mcu_band_segments)
+    const unsigned long long *pic;      // k_picture_stats' words of THESE pictures
+    const ScanStats *scan_stats;        // [2] k_finalize's records: scan 1's, and the one the scans into slots share
+    ScanStats *stats;                   // the context's record, whose sums the caller zeroed
+};
+int launch_scans_concat(const ScansConcatArgs &a, void *stream);
 // The writer of a file with restart intervals: two launches in place of k_finalize (which knows neither the 1-bit padding of an
 // interval nor markers).  k_mcu_restart_offsets, one workgroup per picture: every segment's bit offset inside its interval (pre is its
 // scratch: the bit counts' running sum over the picture), the 0xFF bytes it owns at that phase, and -- an exclusive sum over the

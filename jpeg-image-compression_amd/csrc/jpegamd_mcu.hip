@@ -23,6 +23,9 @@
 // A scan of ONE component (the grayscale file with restart intervals and its own tables) is the kComps = 1
 // instantiation of both walks: the MCU is one block, a segment 256 consecutive blocks of one interval, the predictor the block in
 // front; no pad blocks, no chroma tables.  The three-component instantiations are what they were.
+// Progressive files: the segment coder is mcu_code_segments, which k_mcu_segments instantiates with the walk of a
+// whole block and k_mcu_band_segments with the DC-only walk (the three-component DC scan) or the walk of a band ss .. se (an AC scan of
+// one component); k_scans_concat joins the seven scans k_finalize wrote.
 #include <algorithm>
 
 #include <hip/hip_ext.h>
@@ -76,6 +79,59 @@ __device__ __forceinline__ void mcu_walk_block(const uint4 *__restrict__ p, bool
     }
     if (run) emit(eob & 0xFFFFu, eob >> 16);       // zigzag 63 is zero
 }
+
+// ---- the walks of a progressive file's scans (spectral selection, Ah = Al = 0) --------------------------------
+// The DC scan: a block is its DC difference alone -- a pad block's too: its DC is the nearest real block's.
+template <class Emit>
+__device__ __forceinline__ void mcu_walk_dc(const uint4 *__restrict__ p, int pred, const uint32_t *tab, Emit &&emit) {
+    const int diff = (int)*reinterpret_cast<const int16_t *>(p) - pred;
+    const uint32_t nb = mcu_size(diff), t = tab[256u + (nb & 15u)];
+    emit(((t & 0xFFFFu) << nb) | mcu_amp(diff, nb), (t >> 16) + nb);
+}
+
+// Bits 16 i .. 16 i + 15 of a word that holds coefficients j0 and j0 + 1 of a group of eight: all ones where lo <= j <= hi.
+__device__ __forceinline__ uint32_t mcu_band_mask(int j0, int lo, int hi) {
+    return ((j0 >= lo && j0 <= hi) ? 0x0000FFFFu : 0u) | ((j0 + 1 >= lo && j0 + 1 <= hi) ? 0xFFFF0000u : 0u);
+}
+
+// An AC scan of the band ss .. se (1 <= ss <= se <= 63, the same for the whole launch): T.81 G.1.2.2 without EOB runs -- the zero
+// run is 0 at ss, sixteen zeros are a ZRL, and the block ends with EOB0 (symbol 0x00) when coefficient se is zero, with nothing when
+// it is not.  Only the 16-byte groups that hold ss .. se are read (1 .. 5: p[0] alone); what a group holds outside the band is
+// masked to zero, and the run starts at minus the coefficients masked in front of ss.  A band's string is never longer than the
+// whole block's (the same symbols at most, one per coefficient, a ZRL per sixteen zeros, an EOB for a zero coefficient se).
+template <class Emit>
+__device__ __forceinline__ void mcu_walk_band(const uint4 *__restrict__ p, int ss, int se, const uint32_t *tab, Emit &&emit) {
+    const uint32_t eob = tab[0x00], zrl = tab[0xF0];
+    const int q1 = se >> 3;
+    uint32_t run = 0u - (uint32_t)(ss & 7);
+    uint4 v = make_uint4(0u, 0u, 0u, 0u);
+#pragma unroll 1
+    for (int q = ss >> 3; q <= q1; ++q) {
+        v = p[q];
+        const int lo = ss - 8 * q, hi = se - 8 * q;                // the band in this group: coefficients max(lo, 0) .. min(hi, 7)
+        if (lo > 0 || hi < 7) {
+            v.x &= mcu_band_mask(0, lo, hi); v.y &= mcu_band_mask(2, lo, hi);
+            v.z &= mcu_band_mask(4, lo, hi); v.w &= mcu_band_mask(6, lo, hi);
+        }
+        if ((v.x | v.y | v.z | v.w) == 0u) { run += 8u; continue; }
+        const uint32_t w4[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const int c = (int)(short)((w4[i >> 1] >> (16 * (i & 1))) & 0xFFFFu);
+            if (c == 0) { ++run; continue; }
+            while (run >= 16u) { emit(zrl & 0xFFFFu, zrl >> 16); run -= 16u; }
+            const uint32_t nb = mcu_size(c), t = tab[((run << 4) | nb) & 0xFFu];
+            emit(((t & 0xFFFFu) << nb) | mcu_amp(c, nb), (t >> 16) + nb);
+            run = 0u;
+        }
+    }
+    // coefficient se itself, of the last group's words (`run` also counts the zeros masked behind se)
+    const int i = se & 7;
+    const uint32_t w = (i & 4) ? ((i & 2) ? v.w : v.z) : ((i & 2) ? v.y : v.x);
+    if ((((i & 1) ? w >> 16 : w) & 0xFFFFu) == 0u) emit(eob & 0xFFFFu, eob >> 16);
+}
+
+constexpr int kWalkBlock = 0, kWalkDc = 1, kWalkBand = 2;   // what a coder launch codes of a block: all of it, its DC, a band of its AC
 
 struct McuBlock { const uint4 *p; int pred; bool pad, chroma; };
 
@@ -132,11 +188,19 @@ __device__ __forceinline__ McuRange mcu_range(const McuSegArgs &a, int sl) {
     return r;
 }
 
-template <bool kRestart, int kComps>
-__global__ __launch_bounds__(64 * kWavesM) void k_mcu_segments(const McuSegArgs a) {
+template <int kWalk, class Emit>
+__device__ __forceinline__ void mcu_walk(const McuSegArgs &a, const McuBlock &b, int pred, const uint32_t *tab, Emit &&emit) {
+    if constexpr (kWalk == kWalkDc) mcu_walk_dc(b.p, pred, tab, emit);
+    else if constexpr (kWalk == kWalkBand) mcu_walk_band(b.p, a.ss, a.se, tab, emit);
+    else mcu_walk_block(b.p, b.pad, pred, tab, emit);
+}
+
+// The segment coder, shared by k_mcu_segments (kWalkBlock) and k_mcu_band_segments (a progressive file's scans): s_tab and s_win are
+// the kernel's LDS.  A band launch also adds every segment's bits and symbols to its picture's pair in a.sums (the scans of a
+// file share one set of segment arrays, so the sums are taken as the segments are made).
+template <bool kRestart, int kComps, int kWalk>
+__device__ __forceinline__ void mcu_code_segments(const McuSegArgs &a, uint32_t (*s_tab)[272], uint32_t (*s_win)[kMcuWin + 2]) {
     constexpr int kTabs = kComps == 1 ? 1 : 2;                     // one component: its two tables alone
-    __shared__ uint32_t s_tab[kTabs][272];
-    __shared__ uint32_t s_win[kWavesM][kMcuWin + 2];
     const int lane = lane_id(), wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     {   // the tables of the workgroup's picture (its four segments are one picture's: num_segs_pad is a multiple of kWavesM)
         const size_t toff = a.huff_stride ? (size_t)(((int)blockIdx.x * kWavesM) / a.num_segs_pad) * a.huff_stride : 0;
@@ -171,7 +235,7 @@ __global__ __launch_bounds__(64 * kWavesM) void k_mcu_segments(const McuSegArgs 
             const McuBlock b = mcu_block<kComps>(a, base, m0 + mi, k - mi * bpm, mstart);
             pred[r] = b.pred;
             uint32_t n = 0;
-            mcu_walk_block(b.p, b.pad, b.pred, s_tab[kTabs > 1 && b.chroma ? 1 : 0], [&](uint32_t, uint32_t c) { n += c; ++nsym; });
+            mcu_walk<kWalk>(a, b, b.pred, s_tab[kTabs > 1 && b.chroma ? 1 : 0], [&](uint32_t, uint32_t c) { n += c; ++nsym; });
             len[r] = n;
         }
     }
@@ -201,7 +265,7 @@ __global__ __launch_bounds__(64 * kWavesM) void k_mcu_segments(const McuSegArgs 
                 const int mi = k / bpm;
                 const McuBlock b = mcu_block<kComps>(a, base, m0 + mi, k - mi * bpm, mstart);
                 uint32_t pos = off[r];
-                mcu_walk_block(b.p, b.pad, pred[r], s_tab[kTabs > 1 && b.chroma ? 1 : 0], [&](uint32_t sym, uint32_t n) {
+                mcu_walk<kWalk>(a, b, pred[r], s_tab[kTabs > 1 && b.chroma ? 1 : 0], [&](uint32_t sym, uint32_t n) {
                     if (n == 0u) return;
                     const unsigned long long s64 = ((unsigned long long)sym << (64u - n)) >> (pos & 31u);   // left-aligned at the bit's place in a word pair
                     const uint32_t j = (pos >> 5) - wbase;          // (wraps for a word in front of the window)
@@ -245,6 +309,10 @@ __global__ __launch_bounds__(64 * kWavesM) void k_mcu_segments(const McuSegArgs 
             a.seg.bits[seg] = seg_bits;
             a.seg.syms[seg] = seg_syms;
             a.seg.exact[seg] = 0u;                                  // (the exact-order fallbacks are counted from the tile records: k_picture_stats)
+            if constexpr (kWalk != kWalkBlock) {
+                atomicAdd(a.sums + 2 * (size_t)image, (unsigned long long)seg_bits);
+                atomicAdd(a.sums + 2 * (size_t)image + 1, (unsigned long long)seg_syms);
+            }
         }
     }
     uint32_t mine = 0;
@@ -257,6 +325,26 @@ __global__ __launch_bounds__(64 * kWavesM) void k_mcu_segments(const McuSegArgs 
         ffin[lane] = (uint16_t)min(mine, 65535u);
         if (mine > 65535u) atomicOr(a.status, 2u);
     }
+}
+
+template <bool kRestart, int kComps>
+__global__ __launch_bounds__(64 * kWavesM) void k_mcu_segments(const McuSegArgs a) {
+    __shared__ uint32_t s_tab[kComps == 1 ? 1 : 2][272];
+    __shared__ uint32_t s_win[kWavesM][kMcuWin + 2];
+    mcu_code_segments<kRestart, kComps, kWalkBlock>(a, s_tab, s_win);
+}
+
+// A scan of a progressive file: k_mcu_segments' segments, window and census over another walk of a block --
+// <3, kWalkDc> the DC scan of the three components in MCU order, <1, kWalkBand> the band ss .. se of ONE component's plane.
+// No restart intervals.  A band's string is never longer than the whole block's (mcu_walk_band), a DC difference is at most
+// 11 + 11 bits: seg_cap_words(kSegTiles) holds every segment, as it holds k_mcu_segments'.
+template <int kComps, int kWalk>
+__global__ __launch_bounds__(64 * kWavesM) void k_mcu_band_segments(const McuSegArgs a) {
+    static_assert((kComps == 3 && kWalk == kWalkDc) || (kComps == 1 && kWalk == kWalkBand), "the scans of DESIGN.md 4.6.12");
+    static_assert(22 <= kMaxBlockBitsColor && 63 * 27 <= kMaxBlockBitsColor, "a block of either walk fits the reservation of a whole block");
+    __shared__ uint32_t s_tab[kComps == 1 ? 1 : 2][272];
+    __shared__ uint32_t s_win[kWavesM][kMcuWin + 2];
+    mcu_code_segments<false, kComps, kWalk>(a, s_tab, s_win);
 }
 
 // What both walks of the coefficients need of their arguments: every MCU lies in a segment, and the widest segment fits its reservation.
@@ -283,6 +371,78 @@ int launch_mcu_segments(const McuSegArgs &a, void *stream) {
     const auto kernel = a.comps == 1 ? (a.restart == 0 ? k_mcu_segments<false, 1> : k_mcu_segments<true, 1>)
                                      : (a.restart == 0 ? k_mcu_segments<false, 3> : k_mcu_segments<true, 3>);
     hipLaunchKernelGGL(kernel, grid, block, 0, (hipStream_t)stream, a);
+    return (int)hipGetLastError();
+}
+
+// A scan of a progressive file: three components and ss = se = 0 the DC scan, one component and 1 <= ss <= se <= 63 an AC band.
+int launch_mcu_band_segments(const McuSegArgs &a, void *stream) {
+    const int n = a.batch * a.num_segs_pad;
+    if (n <= 0) return 0;
+    const bool dc = a.comps == 3 && a.ss == 0 && a.se == 0, band = a.comps == 1 && a.ss >= 1 && a.ss <= a.se && a.se <= 63;
+    if (!a.sums || a.restart != 0 || a.huff_stride != 0 || !(dc || band) || !mcu_seg_args_ok(a)) return (int)hipErrorInvalidValue;
+    const dim3 grid((unsigned)((n + kWavesM - 1) / kWavesM)), block(64 * kWavesM);
+    const auto kernel = dc ? k_mcu_band_segments<3, kWalkDc> : k_mcu_band_segments<1, kWalkBand>;
+    hipLaunchKernelGGL(kernel, grid, block, 0, (hipStream_t)stream, a);
+    return (int)hipGetLastError();
+}
+
+// Workgroup (bx, p): picture p of the launch.  Every workgroup of a picture derives the same sizes and the same verdict
+// (k_append_scans_batch's plan); (0, p) writes the picture's size word and adds its numbers to the context's record.
+// A file is scan 1 as k_finalize left it in the caller's buffer -- the prefix in front --, then the scans 2 .. kProgScans out of their
+// slots, each with its SOS in front and the last with EOI behind it.  Its stuffed bytes follow from its size: every scan is its
+// header, its bits rounded up to a byte, and a 0x00 per 0xFF.
+constexpr int kConcatWgs = 64;
+__global__ __launch_bounds__(256) void k_scans_concat(const ScansConcatArgs a) {
+    const int p = (int)blockIdx.y;
+    // bit 0 of scan 1's record only says that SOME picture's first scan outgrew out_capacity, which the sizes tell picture by
+    // picture; anything else there, and any bit of the slots' record (a slot holds its scan's bound: it cannot overflow), fails
+    // every picture, and nothing is copied out of a slot.
+    const uint32_t st = a.scan_stats[0].status | a.scan_stats[1].status, hard = (a.scan_stats[0].status & ~1u) | a.scan_stats[1].status;
+    uint64_t size[kProgScans], total = 0;
+#pragma unroll
+    for (int k = 0; k < kProgScans; ++k) { size[k] = a.size[k * kMaxBatch + p]; total += size[k]; }
+    const bool fit = hard == 0u && total <= a.out_capacity;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        unsigned long long bits = 0, syms = 0, bytes = 0;
+#pragma unroll
+        for (int k = 0; k < kProgScans; ++k) {
+            const unsigned long long b = a.sums[2 * (k * kMaxBatch + p)];
+            bits += b; syms += a.sums[2 * (k * kMaxBatch + p) + 1]; bytes += (b + 7u) / 8u;
+        }
+        const unsigned long long *pic = a.pic + (size_t)p * kPicStatWords;
+        ScanStats *t = a.stats;
+        atomicAdd((unsigned long long *)&t->total_bits, bits);
+        atomicAdd((unsigned long long *)&t->total_syms, syms);
+        atomicAdd((unsigned long long *)&t->total_exact, pic[2] + pic[5] + pic[8]);
+        atomicAdd((unsigned long long *)&t->total_ff, (unsigned long long)(total - (uint64_t)a.prefix_len - (uint64_t)(kProgScans - 1) * kSosBytes - 2u) - bytes);
+        *a.out_size[p] = fit ? total : 0ull;
+        if (a.last_of_call && p == (int)gridDim.y - 1) t->out_size = fit ? total : 0ull;
+        const uint32_t add = st | (fit ? 0u : 1u);
+        if (add) atomicOr(&t->status, add);
+    }
+    if (!fit) return;
+    uint8_t *d = a.out[p] + size[0];
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x * 16u;
+#pragma unroll
+    for (int k = 1; k < kProgScans; ++k) {
+        const uint64_t n = size[k];
+        const uint8_t *src = a.slots + (size_t)p * a.pic_bytes + a.slot_off[k];
+        for (uint64_t i = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) * 16u; i < n; i += stride) {
+            const uint4 v = *reinterpret_cast<const uint4 *>(src + i);              // (a slot is padded to 16 bytes)
+            const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+            const uint64_t m = n - i < 16u ? n - i : 16u;
+#pragma unroll
+            for (int j = 0; j < 16; ++j)
+                if ((uint64_t)j < m) d[i + j] = (uint8_t)(w[j >> 2] >> (8 * (j & 3)));
+        }
+        d += n;
+    }
+}
+
+int launch_scans_concat(const ScansConcatArgs &a, void *stream) {
+    if (a.batch < 1 || a.batch > kMaxBatch || a.pic_bytes % 16 != 0) return (int)hipErrorInvalidValue;
+    for (int k = 1; k < kProgScans; ++k) if (a.slot_off[k] % 16 != 0) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_scans_concat, dim3(kConcatWgs, (unsigned)a.batch), dim3(256), 0, (hipStream_t)stream, a);
     return (int)hipGetLastError();
 }
 

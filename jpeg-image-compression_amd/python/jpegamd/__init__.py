@@ -134,6 +134,10 @@ def _prototypes():
         "jpegamd_export_segments": (i32, [vp, image, i32, i32, vp, u64, vp, vp, vp]),
         "jpegamd_import_segments": (i32, [vp, image, i32, i32, vp, vp, vp]),
         "jpegamd_finalize_async": (i32, [vp, image, vp, u64, vp, i32, vp]),
+        # progressive files: no variant build is kept from before them
+        "jpegamd_encode_color_progressive_batch_async": batch(Image, 1),
+        "jpegamd_encode_ycbcr_progressive_batch_async": batch(YCbCrImage, 4),               # (subsampling, range, format, matrix)
+        "jpegamd_max_jfif_bytes_progressive": (u64, [i32, i32, i32]),
     }
     later = {
         "jpegamd_encoder_set_pipeline": (i32, [vp, i32]),
@@ -323,6 +327,11 @@ def max_jfif_bytes_interleaved_restart(width: int, height: int, subsampling: int
 def max_jfif_bytes_gray_scan(width: int, height: int, restart_interval: int = 0) -> int:
     """Upper bound on the bytes of a grayscale file of jpegamd_encode_gray_scan_batch_async, in either Huffman mode; 0 for bad arguments."""
     return int(lib.jpegamd_max_jfif_bytes_gray_scan(width, height, restart_interval))
+
+
+def max_jfif_bytes_progressive(width: int, height: int, subsampling: int = SUBSAMPLE_420) -> int:
+    """Upper bound on the bytes of a progressive colour file (seven scans); 0 for bad arguments."""
+    return int(lib.jpegamd_max_jfif_bytes_progressive(width, height, subsampling))
 
 
 SCANS = ("separate", "interleaved")
@@ -556,7 +565,8 @@ def _named_layout(t, layout, single: bool):
 
 
 def encode_tensor_batch(t, quality: int = 0, subsampling: int = SUBSAMPLE_420, layout=None, _single: bool = False,
-                        scan: str = "separate", restart_interval=None, _any_layout: bool = False, _huffman: int = 0) -> list:
+                        scan: str = "separate", restart_interval=None, _any_layout: bool = False, _huffman: int = 0,
+                        _progressive: bool = False) -> list:
     """A uint8 DEVICE tensor of N pictures -> N JFIF files: [N, H, W, 3] (R, G, B) colour files through
     jpegamd_encode_color_batch_async, [N, H, W] grayscale files through jpegamd_encode_batch_async.  Pictures may be strided
     (t[::2]), pixels within a row must be packed.  Batches of more than MAX_BATCH pictures go as several calls of at most
@@ -573,8 +583,11 @@ def encode_tensor_batch(t, quality: int = 0, subsampling: int = SUBSAMPLE_420, l
     restart_interval= (scan="interleaved" alone): restart intervals of that many MCUs, 1 .. 65535, or "row" for one MCU row (DRI /
     RSTn, jpegamd_encode_color_interleaved_restart_batch_async); 0 / None: none.
     (`_any_layout`: jpegamd.mjpeg's call -- scan="interleaved" with every colour layout, through the entries that read them;
-    `_huffman`: its tables, set on the per-device context for this call and put back to HUFFMAN_STANDARD behind it.)"""
+    `_huffman`: its tables, set on the per-device context for this call and put back to HUFFMAN_STANDARD behind it;
+    `_progressive`: jpegamd.progressive's call -- jpegamd.mjpeg's, with the progressive file of every packed layout written instead.)"""
     interleaved = _scan(scan)
+    if _progressive and layout == "chw":
+        raise ValueError('progressive files take packed pixels: layout "hwc", "rgba" or "bgra", not "chw"')
     if _huffman and not interleaved:
         raise ValueError('optimised Huffman tables need scan="interleaved"')
     if not interleaved:
@@ -595,7 +608,9 @@ def encode_tensor_batch(t, quality: int = 0, subsampling: int = SUBSAMPLE_420, l
     ri = _restart(restart_interval, interleaved, w, subsampling)
     if any(not x.is_cuda or x.device != tensors[0].device for x in tensors):
         raise ValueError("encode_tensor_batch needs a device tensor")
-    if interleaved:
+    if _progressive:
+        cap = max_jfif_bytes_progressive(w, h, subsampling)
+    elif interleaved:
         cap = max_jfif_bytes_interleaved_restart(w, h, subsampling, ri) if ri else max_jfif_bytes_interleaved(w, h, subsampling)
     elif order == ORDER_GRAY or (order is None and subsampling == 0):
         cap = max_jfif_bytes(w, h)
@@ -607,19 +622,22 @@ def encode_tensor_batch(t, quality: int = 0, subsampling: int = SUBSAMPLE_420, l
             imgs = [Encoder.planar_image(ptr(b0 + i), w, h, stride, bottom_up=False, quality=quality) for i in range(k)]
         else:
             imgs = [Encoder.image(ptr(b0 + i), w, h, stride, bottom_up=False, channel_order=order, quality=quality) for i in range(k)]
-        _queue_pixels(enc, imgs, subsampling, outs, cap, size_ptrs, stream, interleaved, ri, _any_layout, _huffman)
+        _queue_pixels(enc, imgs, subsampling, outs, cap, size_ptrs, stream, interleaved, ri, _any_layout, _huffman, _progressive)
 
-    return _encode_pictures(tensors[0].device, n, h, w, cap, queue, _huffman or None)
+    # (a progressive call sets the standard tables on the shared context: the entry refuses any other mode)
+    return _encode_pictures(tensors[0].device, n, h, w, cap, queue, HUFFMAN_STANDARD if _progressive else (_huffman or None))
 
 
 def _queue_pixels(enc, imgs, subsampling, outs, cap, size_ptrs, stream, interleaved: bool = False, restart: int = 0,
-                  any_layout: bool = False, huffman: int = 0):
+                  any_layout: bool = False, huffman: int = 0, progressive: bool = False):
     """One call of encode_tensor_batch queued on `enc`: which entry takes `imgs` (Image or PlanarImage structs of one geometry).
     Three scans: the planar, the grayscale (ORDER_GRAY) or the colour batch entry.  One scan: the planar entry; for packed pixels
     the entry of every pixel order with `any_layout` (jpegamd.mjpeg), otherwise the RGB entries of encode_tensor_batch's own
     scan="interleaved" -- the restart entry when there are intervals, and for `huffman` (whatever the interval)."""
     planar = isinstance(imgs[0], PlanarImage)
-    if not interleaved:
+    if progressive:                                               # (jpegamd.progressive: packed pixels, no intervals, the standard tables)
+        enc.encode_color_progressive_batch_async(imgs, subsampling, outs, cap, size_ptrs, stream)
+    elif not interleaved:
         if planar:
             enc.encode_planar_batch_async(imgs, subsampling, outs, cap, size_ptrs, stream)
         elif imgs[0].channel_order == ORDER_GRAY:
@@ -778,12 +796,21 @@ def _encode_ycbcr_planes(name: str, layout_of, y, cb, cr, quality, subsampling, 
 
 
 def _encode_ycbcr_images(device, n, h, w, subsampling, image, sample_range: int = RANGE_FULL, sample_format: int = SAMPLES_8,
-                         matrix: int = MATRIX_BT601, interleaved: bool = False, restart: int = 0, any_kind: bool = False, huffman: int = 0):
+                         matrix: int = MATRIX_BT601, interleaved: bool = False, restart: int = 0, any_kind: bool = False, huffman: int = 0,
+                         progressive: bool = False):
     """`n` YCbCr pictures of one geometry, picture i described by image(i), through the per-device context in calls of at most
     MAX_BATCH -> their files.  `any_kind` (jpegamd.mjpeg): the interleaved files of whatever range, format, matrix and layout, through
     jpegamd_encode_ycbcr_interleaved_matrix_batch_async, with the tables `huffman` (set on the context for the call, STANDARD put back)."""
     if huffman and not any_kind:
         raise ValueError("optimised Huffman tables go through jpegamd.mjpeg")
+    if progressive:                                               # (jpegamd.progressive: any kind, no intervals, the standard tables set for the call)
+        cap = max_jfif_bytes_progressive(w, h, subsampling)
+
+        def queue_progressive(enc, b0, k, outs, cap, size_ptrs, stream):
+            enc.encode_ycbcr_progressive_batch_async([image(b0 + i) for i in range(k)], subsampling, sample_range, sample_format, matrix,
+                                                     outs, cap, size_ptrs, stream)
+
+        return _encode_pictures(device, n, h, w, cap, queue_progressive, HUFFMAN_STANDARD)
     if restart:
         cap = max_jfif_bytes_interleaved_restart(w, h, subsampling, restart)
     else:
@@ -891,7 +918,25 @@ def encode_files(in_paths, out_paths, quality: int = 0):
     return int(rc), list(status), st
 
 
-class Encoder:
+class _ProgressiveEntries:
+    """The progressive entries of a context, a base of Encoder: they take the context's handle and its batch
+    marshaller as every other batch method does."""
+
+    def encode_color_progressive_batch_async(self, imgs, subsampling: int, out_ptrs, out_cap: int, size_ptrs, stream: int = 0):
+        """The progressive files (SOF2, seven scans by spectral selection) of RGB / BGR / RGBA / BGRA pictures
+        (jpegamd_encode_color_progressive_batch_async); out_cap from max_jfif_bytes_progressive.  The context's Huffman mode must be
+        HUFFMAN_STANDARD."""
+        self._batch("jpegamd_encode_color_progressive_batch_async", Image, imgs, (subsampling,), out_ptrs, out_cap, size_ptrs, stream)
+
+    def encode_ycbcr_progressive_batch_async(self, imgs, subsampling: int, sample_range: int, sample_format: int, matrix: int,
+                                             out_ptrs, out_cap: int, size_ptrs, stream: int = 0):
+        """The progressive files of YCbCr pictures of any kind encode_ycbcr_interleaved_matrix_batch_async takes
+        (jpegamd_encode_ycbcr_progressive_batch_async)."""
+        self._batch("jpegamd_encode_ycbcr_progressive_batch_async", YCbCrImage, imgs, (subsampling, sample_range, sample_format, matrix),
+                    out_ptrs, out_cap, size_ptrs, stream)
+
+
+class Encoder(_ProgressiveEntries):
     """Level-1 context: device pointers in, device pointers out, stream-ordered."""
 
     def __init__(self, max_width: int, max_height: int):

@@ -51,6 +51,10 @@ frames once, outside the timed loop, and codes the mapped frames at full range: 
 (jpegamd_encoder_set_huffman on the context); the line then carries "huffman".  `standard` sets nothing on the
 context, so a library from before the mode serves it.
 
+--scan progressive (with --batch N, default 8) sends the batch loop through the progressive entries:
+jpegamd_encode_color_progressive_batch_async for rgb, jpegamd_encode_ycbcr_progressive_batch_async for every YCbCr source, --range and
+--matrix; the whole call is timed (ns_total), the line carries "scan": "progressive".  No --restart, --huffman, --layout, --convert, --narrow.
+
 --scan gray (with --batch N, default 8) times GRAYSCALE files through jpegamd_encode_gray_scan_batch_async: the luma
 of the same --size pictures, --restart N|row in blocks (`row`: ceil(W / 8)), --huffman standard|optimized; the whole call is timed
 (ns_total).  Without --restart (or with 0) and with the standard tables the entry is jpegamd_encode_batch_async, so that line is the
@@ -91,9 +95,10 @@ def main() -> None:
     ap.add_argument("--layout", choices=("hwc", "chw", "rgba"), default=None, help="device tensors stored this way, read where they lie")
     ap.add_argument("--rounds", type=int, default=5, help="--layout: medians taken (each of --steps calls)")
     ap.add_argument("--repack", action="store_true", help="--layout chw: also time permute + packed encode")
-    ap.add_argument("--scan", choices=("separate", "interleaved", "gray"), default="separate",
+    ap.add_argument("--scan", choices=("separate", "interleaved", "gray", "progressive"), default="separate",
                     help="interleaved: the batch loop goes through the one-scan entries (every --source, --range, --matrix; --layout chw / rgba); "
-                    "gray: grayscale files through jpegamd_encode_gray_scan_batch_async (--batch, --restart, --huffman)")
+                    "gray: grayscale files through jpegamd_encode_gray_scan_batch_async (--batch, --restart, --huffman); "
+                    "progressive: the batch loop goes through the progressive entries (every --source, --range, --matrix)")
     ap.add_argument("--mapped", action="store_true",
                     help="--range limited (i420, nv12, i422): map the frames once outside the timed loop and code them at full range")
     ap.add_argument("--huffman", choices=("standard", "optimized"), default=None,
@@ -126,6 +131,8 @@ def main() -> None:
         sys.exit("--narrow needs --source p010 or i010")
     if a.scan == "interleaved" and (a.convert or a.narrow):
         sys.exit("--convert and --narrow time routes of the three-scan path: not with --scan interleaved")
+    if a.scan == "progressive" and (a.convert or a.narrow or a.layout is not None or a.huffman is not None or a.restart is not None):
+        sys.exit("--scan progressive takes --size, --batch, --source, --subsampling, --range, --matrix, --mapped, --quality, --kind alone")
     if a.mapped and (a.sample_range != "limited" or any(s not in ("i420", "nv12", "i422") for s in sources)):
         sys.exit("--mapped needs --range limited and takes --source i420, nv12, i422")
     if a.huffman is not None and a.scan == "separate":
@@ -143,7 +150,7 @@ def main() -> None:
     if a.layout is not None:
         run_layout(a, jpegamd, torch, dev)
         return
-    if a.batch is not None or sources != ["rgb"] or a.scan == "interleaved":
+    if a.batch is not None or sources != ["rgb"] or a.scan in ("interleaved", "progressive"):
         run_batch(a, jpegamd, torch, dev, sources)
         return
     bmp = jpegamd.synth_bmp(w, h, 1, a.kind, 0)
@@ -332,8 +339,10 @@ def run_batch(a, jpegamd, torch, dev, sources=("rgb",)) -> None:
         limited = False
     for source, sub, name, tensors, describe in runs:
         ycc = describe(tensors) if describe else None
-        one_scan = a.scan == "interleaved"
+        one_scan, progressive = a.scan == "interleaved", a.scan == "progressive"
         cap = jpegamd.max_jfif_bytes_interleaved(w, h, sub) if one_scan else jpegamd.max_jfif_bytes_color(w, h, sub)
+        if progressive:
+            cap = jpegamd.max_jfif_bytes_progressive(w, h, sub)
         restart = None
         if a.restart is not None:                                # `row`: ceil(W / 8) MCUs at 4:4:4, ceil(W / 16) otherwise
             restart = -(-w // (8 if sub == jpegamd.SUBSAMPLE_444 else 16)) if a.restart == "row" else int(a.restart)
@@ -342,7 +351,14 @@ def run_batch(a, jpegamd, torch, dev, sources=("rgb",)) -> None:
         sizes = torch.zeros(n, dtype=torch.int64, device=dev)
         out_ptrs = [o.data_ptr() for o in outs]
         size_ptrs = [sizes.data_ptr() + 8 * i for i in range(n)]
-        if one_scan and ycc is not None and (limited or bt709 or source in ("yuyv", "p010", "i010")):     # a kind the older one-scan entries refuse
+        if progressive and ycc is None:
+            call = lambda: enc.encode_color_progressive_batch_async(descs, sub, out_ptrs, cap, size_ptrs, stream)
+        elif progressive:
+            fmt = {"p010": jpegamd.SAMPLES_10_MSB, "i010": jpegamd.SAMPLES_10_LSB}.get(source, jpegamd.SAMPLES_8)
+            call = lambda: enc.encode_ycbcr_progressive_batch_async(
+                ycc, sub, jpegamd.RANGE_LIMITED if limited else jpegamd.RANGE_FULL, fmt, jpegamd.MATRIX_BT709 if bt709 else jpegamd.MATRIX_BT601,
+                out_ptrs, cap, size_ptrs, stream)
+        elif one_scan and ycc is not None and (limited or bt709 or source in ("yuyv", "p010", "i010")):     # a kind the older one-scan entries refuse
             fmt = {"p010": jpegamd.SAMPLES_10_MSB, "i010": jpegamd.SAMPLES_10_LSB}.get(source, jpegamd.SAMPLES_8)
             call = lambda: enc.encode_ycbcr_interleaved_matrix_batch_async(
                 ycc, sub, jpegamd.RANGE_LIMITED if limited else jpegamd.RANGE_FULL, fmt, jpegamd.MATRIX_BT709 if bt709 else jpegamd.MATRIX_BT601,
@@ -378,8 +394,8 @@ def run_batch(a, jpegamd, torch, dev, sources=("rgb",)) -> None:
                 "steps": a.steps, "bytes": sizes.cpu().tolist(), "entropy_bits": st.entropy_bits,
                 "ns_total_median": int(t), "us_per_picture": round(t / n / 1000, 1),
                 "gpixels_per_s": round(n * w * h / t, 2)}
-        if one_scan:
-            line["scan"] = "interleaved"
+        if one_scan or progressive:
+            line["scan"] = a.scan
         if a.huffman is not None:
             line["huffman"] = a.huffman
         if restart is not None:
