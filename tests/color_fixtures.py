@@ -12,6 +12,7 @@ from __future__ import annotations
 import numpy as np
 
 import color_model as cm
+import scan_model as sm
 
 SYMBOL_QUALITY = 96          # chroma steps: 1 at DC, zigzag 1 and 2 (DC size 11, AC size 10), >= 2 elsewhere (rounding noise stays 0)
 TIE_QUALITY = 100            # chroma steps 1: the widest guard band
@@ -74,7 +75,7 @@ def extreme_plane(lut: np.ndarray) -> np.ndarray:
 
 
 # ---- chroma symbol coverage ---------------------------------------------------------------------------------------------
-def _basis() -> np.ndarray:
+def basis() -> np.ndarray:
     """[64 raster k = 8 v + u, 8 y, 8 x]: the orthonormal 2-D DCT basis."""
     c = np.array([np.sqrt(0.5)] + [1.0] * 7)
     x = np.arange(8)
@@ -117,7 +118,7 @@ def symbol_plane(oracle, seed: int = 7) -> np.ndarray:
     run 0..15, the ZRL, EOBs and a block whose zigzag 63 is non-zero.  Blocks are single / paired basis functions with chosen
     quantised amplitudes; each candidate is checked with the oracle's stage functions and kept when it adds a (run, size) code."""
     table = cm.scaled_table(cm.CHROMA_Q, SYMBOL_QUALITY)
-    basis = _basis()
+    bank = basis()
     rng = np.random.default_rng(seed)
     specs = []                                                            # [(zigzag position, quantised value), ...] per candidate
     for s in range(1, 11):
@@ -135,7 +136,7 @@ def symbol_plane(oracle, seed: int = 7) -> np.ndarray:
         f = np.zeros(64)
         for p, a in sp:
             f[cm.ZIGZAG[p]] = a * int(table[cm.ZIGZAG[p]])
-        px = 128.0 + np.tensordot(f, basis, axes=1)
+        px = 128.0 + np.tensordot(f, bank, axes=1)
         if px.min() < 0 or px.max() > 255:
             continue
         cands.append(np.rint(px).astype(np.uint8))
@@ -153,9 +154,9 @@ def symbol_plane(oracle, seed: int = 7) -> np.ndarray:
 
 def chroma_symbol_coverage(oracle, plane: np.ndarray, quality: int = SYMBOL_QUALITY):
     """-> dict: DC sizes, AC (run, size) codes, runs, AC sizes, ZRL / EOB counts and blocks without EOB of the plane's chroma scan,
-    from the model's own symbol list (color_model._symbols)."""
+    from the model's own symbol list (scan_model.symbols)."""
     zz = cm.plane_zigzag(oracle, plane, cm.scaled_table(cm.CHROMA_Q, quality))
-    sym, _, _, is_dc = cm._symbols(oracle, zz)
+    sym, _, _, is_dc, _ = sm.symbols(oracle, zz)
     ac = sym[~is_dc]
     codes = {int(v) for v in ac if v not in (0x00, 0xF0)}
     return dict(dc_sizes={int(v) for v in sym[is_dc]}, codes=codes, runs={c >> 4 for c in codes}, sizes={c & 15 for c in codes},

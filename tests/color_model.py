@@ -4,38 +4,20 @@ The file is three non-interleaved baseline scans.  The model builds each of them
   * Y:  the oracle's grayscale file of the same BMP, minus its 328-byte prefix and its EOI (the colour path's Y scan is defined to
         be that entropy-coded segment byte for byte);
   * Cb, Cr: the integer planes of the spec, then the oracle's stage functions (exact-order DCT, quantisation with the chroma
-        table, zigzag, run/size symbols) and a Huffman packer for the T.81 Annex K chroma tables (K.4 DC, K.6 AC) below.
-"""
+        table, zigzag, run/size symbols) and a Huffman packer for the T.81 Annex K chroma tables (K.4 DC, K.6 AC): scan_model's.
+The Annex K constants and the steps every model shares live in scan_model.py and are imported here by name."""
 from __future__ import annotations
 
-import ctypes as C
 import hashlib
 import struct
 
 import numpy as np
 
-# T.81 Annex K: K.1 / K.2 (quantisation, raster order), K.3-K.6 as BITS / HUFFVAL
-LUMA_Q = [16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87, 80, 62,
-          18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100,
-          103, 99]
-CHROMA_Q = [17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99,
-            99, 99] + [99] * 32
-DC_LUMA_BITS = [0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0]
-DC_CHROMA_BITS = [0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0]
-DC_VALS = list(range(12))
-AC_LUMA_BITS = [0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 0x7D]
-AC_LUMA_VALS = bytes.fromhex(
-    "01020300041105122131410613516107227114328191a1082342b1c11552d1f02433627282090a161718191a25262728292a3435363738393a434445464748"
-    "494a535455565758595a636465666768696a737475767778797a838485868788898a92939495969798999aa2a3a4a5a6a7a8a9aab2b3b4b5b6b7b8b9bac2c3"
-    "c4c5c6c7c8c9cad2d3d4d5d6d7d8d9dae1e2e3e4e5e6e7e8e9eaf1f2f3f4f5f6f7f8f9fa")
-AC_CHROMA_BITS = [0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 0x77]
-AC_CHROMA_VALS = bytes.fromhex(
-    "000102031104052131061241510761711322328108144291a1b1c109233352f0156272d10a162434e125f11718191a262728292a35363738393a4344454647"
-    "48494a535455565758595a636465666768696a737475767778797a82838485868788898a92939495969798999aa2a3a4a5a6a7a8a9aab2b3b4b5b6b7b8b9bac2"
-    "c3c4c5c6c7c8c9cad2d3d4d5d6d7d8d9dae2e3e4e5e6e7e8e9eaf2f3f4f5f6f7f8f9fa")
+from scan_model import (AC_CHROMA_BITS, AC_CHROMA_VALS, AC_LUMA_BITS, AC_LUMA_VALS, CHROMA_Q, DC_CHROMA_BITS, DC_LUMA_BITS,    # noqa: F401
+                        DC_VALS, LUMA_Q, SUB_420, SUB_444, canonical, chroma_planes, plane_zigzag, scaled_table, sos, three_scans)
+
 ZIGZAG = [0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
           35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63]
-SUB_444, SUB_420 = 1, 2
 PLANES, CBCR, CRCB = 0, 1, 2                                    # JPEGAMD_CHROMA_PLANES / _CBCR / _CRCB
 
 _memo = {}
@@ -48,25 +30,6 @@ def memo(fn, oracle, *args):
     if key not in _memo:
         _memo[key] = fn(oracle, *args)
     return _memo[key]
-
-
-def scaled_table(base, quality: int) -> np.ndarray:
-    """quant_table_for_quality's rule (0 -> 50; libjpeg scaling; clamp 1..255) applied to `base`."""
-    q = 50 if quality <= 0 else min(quality, 100)
-    s = 5000 // q if q < 50 else 200 - 2 * q
-    return np.array([min(max((b * s + 50) // 100, 1), 255) for b in base], np.uint8)
-
-
-def canonical(bits, vals):
-    """symbol -> (code, length); symbols the table does not list are absent (length 0: no code bits, as the reference)."""
-    out, code, k = {}, 0, 0
-    for ln in range(1, 17):
-        for _ in range(bits[ln - 1]):
-            out[vals[k]] = (code, ln)
-            code += 1
-            k += 1
-        code <<= 1
-    return out
 
 
 def read_bmp_rgb(bmp: bytes) -> np.ndarray:
@@ -94,89 +57,10 @@ def write_bmp(rgb: np.ndarray) -> bytes:
     return hdr + info + data
 
 
-def chroma_planes(rgb: np.ndarray, sub: int):
-    """The spec's integer Cb / Cr planes: uint8 [ch, cw] each."""
-    r, g, b = (rgb[:, :, i].astype(np.int64) for i in range(3))
-    cb = (32768 - 43 * r - 85 * g + 128 * b) >> 8
-    cr = (32768 + 128 * r - 107 * g - 21 * b) >> 8
-    if sub == SUB_420:
-        h, w = cb.shape
-        ys, xs = np.arange(0, h, 2), np.arange(0, w, 2)
-        y1, x1 = np.minimum(ys + 1, h - 1), np.minimum(xs + 1, w - 1)
-
-        def avg(p):
-            return (p[ys][:, xs] + p[ys][:, x1] + p[y1][:, xs] + p[y1][:, x1] + 2) >> 2
-        cb, cr = avg(cb), avg(cr)
-    return cb.astype(np.uint8), cr.astype(np.uint8)
-
-
-def plane_zigzag(oracle, plane: np.ndarray, qt: np.ndarray) -> np.ndarray:
-    """The oracle's stage functions over an 8-bit plane (edge-replicated to multiples of 8): int16 [NB, 64] zigzag, raster block order."""
-    h, w = plane.shape
-    ph, pw = (h + 7) & ~7, (w + 7) & ~7
-    padded = np.pad(plane, ((0, ph - h), (0, pw - w)), mode="edge")
-    y = np.ascontiguousarray((padded.astype(np.int16) - 128).astype(np.int8))
-    lib = oracle._lib
-    d = np.zeros((ph, pw), np.float32)
-    lib.oracle_dct_image(y.ctypes.data, pw, ph, d.ctypes.data)
-    q = np.zeros((ph, pw), np.int16)
-    qt = np.ascontiguousarray(qt, np.uint8)
-    lib.oracle_quant_image(d.ctypes.data, pw, ph, qt.ctypes.data, q.ctypes.data)
-    zz = np.zeros(((pw // 8) * (ph // 8), 64), np.int16)
-    lib.oracle_zigzag_image(q.ctypes.data, pw, ph, zz.ctypes.data)
-    return zz
-
-
-def _symbols(oracle, zz: np.ndarray):
-    """oracle_rle -> (symbol, amplitude bits, amplitude length) arrays and a DC flag per symbol."""
-    zz = np.ascontiguousarray(zz, np.int16)
-    nb = zz.shape[0]
-    cap = nb * 70 + 16
-    buf = np.zeros(cap * 4, np.uint8)
-    n = oracle._lib.oracle_rle(zz.ctypes.data, nb, C.c_void_p(buf.ctypes.data), cap)
-    assert n >= 0, n
-    rec = buf[:4 * n].reshape(n, 4)
-    sym, alen, amp = rec[:, 0].astype(np.int64), rec[:, 1].astype(np.int64), rec[:, 2].astype(np.int64) | (rec[:, 3].astype(np.int64) << 8)
-    # symbols per block: DC, (ZRLs + symbol) per non-zero AC, EOB unless zigzag 63 is non-zero (rle.c)
-    rows, cols = np.nonzero(zz[:, 1:])
-    pos = cols + 1
-    same = np.r_[False, rows[1:] == rows[:-1]]
-    prev = np.where(same, np.r_[0, pos[:-1]], 0)
-    per_ac = 1 + (pos - prev - 1) // 16
-    counts = 1 + np.bincount(rows, weights=per_ac, minlength=nb).astype(np.int64) + (zz[:, 63] == 0)
-    assert counts.sum() == n, (counts.sum(), n)
-    is_dc = np.zeros(n, bool)
-    is_dc[np.r_[0, np.cumsum(counts)[:-1]]] = True
-    return sym, amp, alen, is_dc
-
-
-def pack_scan(oracle, zz: np.ndarray, chroma: bool) -> bytes:
-    """Entropy-coded segment of zigzag blocks with the luma or chroma tables: DC predictor 0 at the start, 0xFF stuffing,
-    zero-bit flush."""
-    sym, amp, alen, is_dc = _symbols(oracle, zz)
-    dc = canonical(DC_CHROMA_BITS if chroma else DC_LUMA_BITS, DC_VALS)
-    ac = canonical(AC_CHROMA_BITS if chroma else AC_LUMA_BITS, AC_CHROMA_VALS if chroma else AC_LUMA_VALS)
-    dc_code, dc_len, ac_code, ac_len = (np.zeros(256, np.int64) for _ in range(4))
-    for s, (c, ln) in dc.items():
-        dc_code[s], dc_len[s] = c, ln
-    for s, (c, ln) in ac.items():
-        ac_code[s], ac_len[s] = c, ln
-    code = np.where(is_dc, dc_code[sym], ac_code[sym])
-    clen = np.where(is_dc, dc_len[sym], ac_len[sym])
-    val = (code << alen) | (amp & ((1 << alen) - 1))
-    length = clen + alen
-    total = int(length.sum())
-    starts = np.cumsum(length) - length
-    idx = np.repeat(np.arange(len(val)), length)
-    off = np.arange(total) - starts[idx]
-    bits = ((val[idx] >> (length[idx] - 1 - off)) & 1).astype(np.uint8)
-    by = np.packbits(bits)                                    # zero-padded to whole bytes
-    ff = np.nonzero(by == 0xFF)[0]
-    return np.insert(by, ff + 1, 0).tobytes()
-
-
-def sos(component: int) -> bytes:
-    return bytes([0xFF, 0xDA, 0x00, 0x08, 0x01, component, 0x00 if component == 1 else 0x11, 0, 63, 0])
+def synth_rgb(w, h, seed, kind=0, flags=0):
+    """A picture of the project's generator (0 photo-like, 1 noise, 2 flat, 3 gradient) as uint8 [H, W, 3]."""
+    import jpegamd
+    return read_bmp_rgb(jpegamd.synth_bmp(w, h, seed, kind, flags))
 
 
 def color_prefix(width: int, height: int, quality: int, sub: int) -> bytes:
@@ -205,12 +89,7 @@ def color_file(oracle, bmp: bytes, quality: int = 0, sub: int = SUB_420) -> byte
     """The whole colour file the library must write for this BMP."""
     rgb = read_bmp_rgb(bmp)
     h, w, _ = rgb.shape
-    cq = scaled_table(CHROMA_Q, quality)
-    cb, cr = chroma_planes(rgb, sub)
-    parts = [color_prefix(w, h, quality, sub), gray_scan(oracle, bmp, quality)]
-    for comp, plane in ((2, cb), (3, cr)):
-        parts += [sos(comp), pack_scan(oracle, plane_zigzag(oracle, plane, cq), True)]
-    return b"".join(parts) + b"\xff\xd9"
+    return three_scans(oracle, color_prefix(w, h, quality, sub), gray_scan(oracle, bmp, quality), *chroma_planes(rgb, sub), quality)
 
 
 def rgb_file(oracle, rgb: np.ndarray, quality: int, sub: int) -> bytes:
@@ -226,14 +105,6 @@ def gray_file(oracle, plane: np.ndarray, quality: int) -> bytes:
     return oracle.encode_bmp(write_bmp(np.repeat(plane[:, :, None], 3, axis=2)), quality)
 
 
-def model_planes(rgb: np.ndarray, sub: int):
-    """What the colour path derives from an RGB picture: the luma formula and chroma_planes."""
-    r, g, b = (rgb[:, :, i].astype(np.int64) for i in range(3))
-    y = ((77 * r + 150 * g + 29 * b) >> 8).astype(np.uint8)
-    cb, cr = chroma_planes(rgb, sub)
-    return y, cb, cr
-
-
 def chroma_rows(cb: np.ndarray, cr: np.ndarray, layout: int):
     """The stored chroma of one picture: [cb rows, cr rows] for PLANES, [pair rows] otherwise."""
     if layout == PLANES:
@@ -246,8 +117,4 @@ def ycbcr_file(oracle, y: np.ndarray, cb: np.ndarray, cr: np.ndarray, quality: i
     """The file of samples that already are Y, Cb and Cr: the colour prefix, the oracle's grayscale scan of the Y plane, and the chroma
     pipeline over the Cb and Cr planes exactly as given."""
     h, w = y.shape
-    cq = scaled_table(CHROMA_Q, quality)
-    parts = [color_prefix(w, h, quality, sub), gray_scan(oracle, write_bmp(np.stack([y, y, y], axis=2)), quality)]
-    for comp, plane in ((2, cb), (3, cr)):
-        parts += [sos(comp), pack_scan(oracle, plane_zigzag(oracle, plane, cq), True)]
-    return b"".join(parts) + b"\xff\xd9"
+    return three_scans(oracle, color_prefix(w, h, quality, sub), gray_scan(oracle, write_bmp(np.stack([y, y, y], axis=2)), quality), cb, cr, quality)

@@ -10,6 +10,7 @@ import pytest
 
 import color_model as cm
 import color_model_422 as m422
+import scan_model as sm
 from color_model import CBCR, CRCB, PLANES
 from threshold_fixtures import gray_bmp                         # noqa: F401  (the bare-header BMP with R = G = B, either row order)
 
@@ -42,7 +43,7 @@ def gray_bmp_sized(p: np.ndarray) -> bytes:
 
 
 def synth_rgb(jpegamd, w, h, seed, kind, flags=0):
-    return cm.read_bmp_rgb(jpegamd.synth_bmp(w, h, seed, kind, flags))
+    return cm.synth_rgb(w, h, seed, kind, flags)
 
 
 def pictures(jpegamd, w, h, n, seed=0, base=100, step=37):
@@ -70,7 +71,7 @@ def random_planes(w, h, sub, seed):
 def smooth_planes(w, h, sub, seed):
     """(y, cb, cr) of photo-like content: the model's planes of a synthetic picture (small files)."""
     import jpegamd
-    return cm.model_planes(synth_rgb(jpegamd, w, h, seed, 0), sub)
+    return sm.planes_of(synth_rgb(jpegamd, w, h, seed, 0), sub)
 
 
 def block_rows_reversed(plane):

@@ -7,6 +7,7 @@ import numpy as np
 
 import color_model as cm
 import gray_scan_model as gm
+import scan_model as sm
 
 INTERVALS = (0, 1, "row", 255, 256, 257, 65535)
 MODES = (False, True)                                          # optimised tables?
@@ -29,8 +30,7 @@ def ramp(w, h):
 
 
 def synth_luma(w, h, seed, kind=0):
-    import jpegamd
-    return gm.luma(cm.read_bmp_rgb(jpegamd.synth_bmp(w, h, seed, kind, 0)))
+    return sm.luma_plane(cm.synth_rgb(w, h, seed, kind))
 
 
 # ---- 1. geometry: (name, plane, quality) ------------------------------------------------------------------------------------------------

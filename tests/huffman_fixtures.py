@@ -9,18 +9,11 @@ import color_model_422 as m422
 import huffman_model as hm
 import interleaved_model as im
 import restart_model as rm
+from color_model import synth_rgb
+from interleaved_model import row_interval
 
 S444, S420, S422 = cm.SUB_444, cm.SUB_420, m422.SUB_422
 SUBS = (S444, S420, S422)
-
-
-def synth_rgb(w, h, seed, kind=0):
-    import jpegamd
-    return cm.read_bmp_rgb(jpegamd.synth_bmp(w, h, seed, kind, 0))
-
-
-def row_interval(w, sub):
-    return -(-w // (8 if sub == S444 else 16))
 
 
 def interval(ri, w, sub):

@@ -2,7 +2,7 @@
 TEST INFRASTRUCTURE ONLY.
 
 optimal_table is T.81 K.2 as libjpeg carries it out, with code sizes up to 256 (no error path for long codes).  The file is built from
-interleaved_model's and restart_model's parts -- geometry, prefix, DRI, MCU order with pad blocks, symbols -- in two passes: every
+interleaved_model's and restart_model's parts -- geometry, prefix, DRI, coefficients -- and scan_model's coder in two passes: every
 symbol the scan codes with the call's restart interval is counted into four tables (luma DC, luma AC, chroma DC, chroma AC), then coded
 with the tables made of the counts.  Besides the file the model keeps what the device's coder and writer have to get right: the counts,
 the tables, the bit count of every coder segment, and the short tails of DESIGN.md 4.6.10."""
@@ -15,6 +15,7 @@ import numpy as np
 import color_model as cm
 import interleaved_model as im
 import restart_model as rm
+import scan_model as sm
 
 STD_DHT_BYTES = 2 * (33 + 183)                                  # the four Annex K DHT segments
 TABLE_IDS = (0x00, 0x10, 0x01, 0x11)                            # luma DC, luma AC, chroma DC, chroma AC
@@ -69,14 +70,6 @@ def optimal_table(freq):
     return n[1:17], vals, top
 
 
-def code_arrays(bits, vals):
-    """-> (code[256], length[256]) of the canonical code, 0 / 0 for symbols without one."""
-    code, length = np.zeros(256, np.int64), np.zeros(256, np.int64)
-    for s, (c, ln) in cm.canonical(bits, vals).items():
-        code[s], length[s] = c, ln
-    return code, length
-
-
 def dht(bits, vals, tc_th: int) -> bytes:
     n = 19 + len(vals)
     return bytes([0xFF, 0xC4, n >> 8, n & 0xFF, tc_th]) + bytes(bits) + bytes(vals)
@@ -112,76 +105,29 @@ class Optimized:
 def planes_file(oracle, y: np.ndarray, cb: np.ndarray, cr: np.ndarray, quality: int, sub: int, ri: int = 0) -> Optimized:
     assert 0 <= ri <= 65535
     h, w = y.shape
-    hs, vs, bw, bh, mx, my = im.geometry(w, h, sub)
-    ny, m, s = hs * vs, mx * my, rm.seg_mcus(sub)
-    bpm = ny + 2
-    lq, cq = cm.scaled_table(cm.LUMA_Q, quality), cm.scaled_table(cm.CHROMA_Q, quality)
-    zy, pad = im._mcu_order_luma(cm.plane_zigzag(oracle, y, lq), bw, bh, hs, vs, mx, my)
-    zcb, zcr = cm.plane_zigzag(oracle, cb, cq), cm.plane_zigzag(oracle, cr, cq)
-    step = ri if ri else m
-    spans = [(a, min(a + step, m)) for a in range(0, m, step)]
+    zy, zcb, zcr, pads, ny, m = im.scan_blocks(oracle, y, cb, cr, quality, sub)
     # pass 1: the symbols of every interval (predictors 0 at its start), counted
+    intervals = sm.scan_symbols(oracle, zy, zcb, zcr, ny, ri if ri else m)
     counts = np.zeros((4, 256), np.int64)
-    coded = []
-    for a, b in spans:
-        per = []
-        for comp, zz in enumerate((zy[a * ny:b * ny], zcb[a:b], zcr[a:b])):
-            sym, amp, alen, is_dc, nsym = im._symbols_by_block(oracle, zz)
-            cls = 2 * (comp > 0)
-            counts[cls] += np.bincount(sym[is_dc], minlength=256)
-            counts[cls + 1] += np.bincount(sym[~is_dc], minlength=256)
-            blk = np.arange(zz.shape[0])
-            key = (blk // ny) * bpm + blk % ny if comp == 0 else blk * bpm + ny + comp - 1
-            per.append((sym, amp, alen, is_dc, np.repeat(key, nsym)))
-        coded.append(per)
+    for per in intervals:
+        for comp, (sym, _, _, is_dc, _) in enumerate(per):
+            counts[2 * (comp > 0)] += np.bincount(sym[is_dc], minlength=256)
+            counts[2 * (comp > 0) + 1] += np.bincount(sym[~is_dc], minlength=256)
     tables = tuple(optimal_table(c) for c in counts)
-    arrays = [code_arrays(b, v) for b, v, _ in tables]
+    arrays = [sm.code_arrays(b, v) for b, v, _ in tables]
+    assert all(length[c > 0].all() for (_, length), c in zip(arrays, counts))      # every symbol of the scan has a code
     # pass 2: coded with the picture's tables
-    body = bytearray()
-    stuffed = scan_bits = borrowed = borrowed_ff = against = 0
-    seg_all = []
-    for i, ((a, b), per) in enumerate(zip(spans, coded)):
-        vals, lens, keys = [], [], []
-        for comp, (sym, amp, alen, is_dc, key) in enumerate(per):
-            (dcc, dcl), (acc, acl) = arrays[2 * (comp > 0)], arrays[2 * (comp > 0) + 1]
-            clen = np.where(is_dc, dcl[sym], acl[sym])
-            assert clen.min() >= 1
-            vals.append((np.where(is_dc, dcc[sym], acc[sym]) << alen) | (amp & ((1 << alen) - 1)))
-            lens.append(clen + alen)
-            keys.append(key)
-        val, length, key = np.concatenate(vals), np.concatenate(lens), np.concatenate(keys)
-        order = np.argsort(key, kind="stable")
-        val, length, key = val[order], length[order], key[order]
-        total = int(length.sum())
-        starts = np.cumsum(length) - length
-        idx = np.repeat(np.arange(len(val)), length)
-        off = np.arange(total) - starts[idx]
-        bits = ((val[idx] >> (length[idx] - 1 - off)) & 1).astype(np.uint8)
-        mcu_bits = np.bincount(key // bpm, weights=length, minlength=b - a).astype(np.int64)
-        scan_bits += total
-        last = i == len(spans) - 1
-        r = total % 8
-        padded = np.r_[bits, np.full(8 - r, 0 if last else 1, np.uint8)] if r else bits
-        by = np.packbits(padded)
-        ends = np.cumsum(mcu_bits)                               # the coder's segments: runs of s MCUs from the interval's first
-        seg_bits = np.diff(np.r_[0, ends[s - 1::s], ends[-1]]) if (b - a) % s else np.diff(np.r_[0, ends[s - 1::s]])
-        assert seg_bits.sum() == total and len(seg_bits) == -(-(b - a) // s)
-        assert all(int(x) >= 14 for x in seg_bits[:-1])          # only an interval's last segment may be short: what the device's readers of `edge` rely on
-        seg_all.append(tuple(int(x) for x in seg_bits))
-        if int(seg_bits[-1]) < r:
-            borrowed += 1
-            borrowed_ff += bool(not last and by[-1] == 0xFF)
-        b0 = total - int(seg_bits[-1])
-        if len(seg_bits) > 1 and seg_bits[-1] < 14 and b0 % 8 and by[b0 // 8] == 0xFF:
-            against += 1
-        ff = np.nonzero(by == 0xFF)[0]
-        stuffed += len(ff)
-        body += np.insert(by, ff + 1, 0).tobytes()
-        if not last:
-            body += bytes([0xFF, 0xD0 + i % 8])
+    body, ivs = sm.frame_intervals(*sm.scan_bits(intervals, arrays[:2], arrays[2:], ny), ri if ri else m, rm.seg_mcus(sub))
+    assert all(x >= 14 for v in ivs for x in v.seg_bits[:-1])   # only an interval's last segment may be short: what the device's readers of `edge` rely on
+    borrowed = [v for v in ivs if v.seg_bits[-1] < v.r]
+    against = 0
+    for v in ivs:
+        b0 = v.bits - v.seg_bits[-1]                            # where the interval's last coder segment begins
+        against += bool(len(v.seg_bits) > 1 and v.seg_bits[-1] < 14 and b0 % 8 and v.padded[b0 // 8] == 0xFF)
     pre = prefix(w, h, quality, sub, ri, tables)
-    return Optimized(pre + bytes(body) + b"\xff\xd9", counts, tables, len(pre), scan_bits, stuffed, len(spans), int(pad.sum()),
-                     tuple(seg_all), borrowed, borrowed_ff, against, min(min(x) for x in seg_all))
+    return Optimized(pre + body + b"\xff\xd9", counts, tables, len(pre), sum(v.bits for v in ivs), sum(v.ff for v in ivs), len(ivs), pads,
+                     tuple(v.seg_bits for v in ivs), len(borrowed), sum(v.pad_ff for v in borrowed), against,
+                     min(min(v.seg_bits) for v in ivs))
 
 
 def ycbcr_file(oracle, y, cb, cr, quality: int = 0, sub: int = cm.SUB_420, ri: int = 0) -> Optimized:
@@ -191,9 +137,7 @@ def ycbcr_file(oracle, y, cb, cr, quality: int = 0, sub: int = cm.SUB_420, ri: i
 
 def rgb_file(oracle, rgb: np.ndarray, quality: int = 0, sub: int = cm.SUB_420, ri: int = 0) -> Optimized:
     """The optimised file the library must write for these R, G, B pixels: the planes of interleaved_model.interleaved_file."""
-    y = im.m422.luma_plane(rgb)
-    cb, cr = im.m422.chroma_planes_422(rgb) if sub == im.m422.SUB_422 else cm.chroma_planes(rgb, sub)
-    return planes_file(oracle, y, cb, cr, quality, sub, ri)
+    return planes_file(oracle, *sm.planes_of(rgb, sub), quality, sub, ri)
 
 
 def standard_file(oracle, rgb: np.ndarray, quality: int, sub: int, ri: int = 0) -> bytes:

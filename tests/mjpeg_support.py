@@ -16,9 +16,12 @@ import color_model_422 as m422
 import depth_model as dm
 import gpu_support as gs
 import interleaved_model as im
+from interleaved_model import row_interval                      # noqa: F401  (the suites take it from here)
 import matrix_model as mm
 import range_model as rgm
 import restart_model as rsm
+import scan_model as sm
+from color_model import synth_rgb
 from gpu_support import CBCR, CRCB, PLANES, S420, S422, S444, UYVY, YUYV  # noqa: F401
 
 SUBS = (S444, S420, S422)
@@ -63,16 +66,9 @@ LIMITED8_709 = Kind("limited8-709", limited=True, bt709=True)
 LIMITED10_709 = Kind("limited10-709", "msb", True, True)
 
 
-def synth_rgb(w, h, seed, kind=0):
-    import jpegamd
-    return cm.read_bmp_rgb(jpegamd.synth_bmp(w, h, seed, kind, 0))
-
-
 def derived_planes(rgb, sub):
     """(y, cb, cr) as the RGB entries derive them at `sub`."""
-    y = m422.luma_plane(rgb)
-    cb, cr = m422.chroma_planes_422(rgb) if sub == S422 else cm.chroma_planes(rgb, sub)
-    return tuple(np.ascontiguousarray(p) for p in (y, cb, cr))
+    return tuple(np.ascontiguousarray(p) for p in sm.planes_of(rgb, sub))
 
 
 def stored_planes(kind: Kind, w, h, sub, seed, smooth=None):
@@ -132,10 +128,6 @@ def decode(data: bytes) -> np.ndarray:
     image = pytest.importorskip("PIL.Image")
     with image.open(io.BytesIO(data)) as f:
         return np.asarray(f.convert("RGB"))
-
-
-def row_interval(w, sub):
-    return -(-w // (8 if sub == S444 else 16))
 
 
 # ---- calls queued on a context --------------------------------------------------------------------------------------------------------
@@ -242,26 +234,26 @@ def fake_context():
     return fake, C.cast(fake, C.c_void_p)
 
 
-def _arrays(n=4):
+def out_arrays(n=4):
     return (C.c_void_p * n)(*([C.c_void_p(0x1000)] * n)), (C.c_void_p * n)(*([C.c_void_p(0x2000)] * n))
 
 
 def call_ycc(jpegamd, ctx, imgs, sub, rng=0, fmt=0, matrix=0, ri=0, count=None, outs=True):
     arr = (jpegamd.YCbCrImage * max(len(imgs), 1))(*imgs) if imgs is not None else None
-    out_arr, size_arr = _arrays() if outs else (None, None)
+    out_arr, size_arr = out_arrays() if outs else (None, None)
     return jpegamd.lib.jpegamd_encode_ycbcr_interleaved_matrix_batch_async(ctx, arr, len(imgs) if count is None else count, sub, rng, fmt, matrix,
                                                                            ri, out_arr, 1 << 20, size_arr, None)
 
 
 def call_pixels(jpegamd, ctx, imgs, sub, ri=0, count=None, outs=True):
     arr = (jpegamd.Image * max(len(imgs), 1))(*imgs) if imgs is not None else None
-    out_arr, size_arr = _arrays() if outs else (None, None)
+    out_arr, size_arr = out_arrays() if outs else (None, None)
     return jpegamd.lib.jpegamd_encode_color_interleaved_pixels_batch_async(ctx, arr, len(imgs) if count is None else count, sub, ri, out_arr,
                                                                            1 << 20, size_arr, None)
 
 
 def call_planar(jpegamd, ctx, imgs, sub, ri=0, count=None, outs=True):
     arr = (jpegamd.PlanarImage * max(len(imgs), 1))(*imgs) if imgs is not None else None
-    out_arr, size_arr = _arrays() if outs else (None, None)
+    out_arr, size_arr = out_arrays() if outs else (None, None)
     return jpegamd.lib.jpegamd_encode_planar_interleaved_batch_async(ctx, arr, len(imgs) if count is None else count, sub, ri, out_arr, 1 << 20,
                                                                      size_arr, None)

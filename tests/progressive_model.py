@@ -2,7 +2,7 @@
 
 Seven scans by spectral selection, Ah = Al = 0: the DC scan of the three components in the MCU order of interleaved_model (pad blocks
 made, per-component predictors), then the bands 1..5 and 6..63 of Y, Cb and Cr, each over the component's own block grid in raster
-order.  The coefficients are color_model.plane_zigzag's, the tables Annex K's; a band is coded as T.81 G.1.2.2 with end-of-band runs
+order.  The coefficients are scan_model.plane_zigzag's, the tables Annex K's, the packer scan_model's; a band is coded as T.81 G.1.2.2 with end-of-band runs
 of exactly one block (symbol 0x00).  Besides the file the model returns the counters the GPU tests claim to exercise."""
 from __future__ import annotations
 
@@ -11,8 +11,8 @@ from dataclasses import dataclass
 import numpy as np
 
 import color_model as cm
-import color_model_422 as m422
 import interleaved_model as im
+import scan_model as sm
 
 BANDS = ((1, 5), (6, 63))
 SCANS = 7
@@ -55,30 +55,8 @@ def prefix(w: int, h: int, quality: int, sub: int) -> bytes:
     return bytes(p[:-len(im.SOS3)]) + SOS_DC
 
 
-def _tables(chroma: bool):
-    dc = cm.canonical(cm.DC_CHROMA_BITS if chroma else cm.DC_LUMA_BITS, cm.DC_VALS)
-    ac = cm.canonical(cm.AC_CHROMA_BITS if chroma else cm.AC_LUMA_BITS, cm.AC_CHROMA_VALS if chroma else cm.AC_LUMA_VALS)
-    return dc, ac
-
-
 def _amp(v: int, size: int) -> int:
     return (v if v >= 0 else v - 1) & ((1 << size) - 1)
-
-
-def _pack(symbols):
-    """[(value, bits)] -> (the byte-aligned, stuffed entropy-coded segment, coded bits, stuffed bytes)."""
-    if not symbols:
-        return b"", 0, 0
-    val = np.array([s[0] for s in symbols], np.int64)
-    length = np.array([s[1] for s in symbols], np.int64)
-    total = int(length.sum())
-    starts = np.cumsum(length) - length
-    idx = np.repeat(np.arange(len(val)), length)
-    off = np.arange(total) - starts[idx]
-    bits = ((val[idx] >> (length[idx] - 1 - off)) & 1).astype(np.uint8)
-    by = np.packbits(bits)                                       # zero-padded to whole bytes
-    ff = np.nonzero(by == 0xFF)[0]
-    return np.insert(by, ff + 1, 0).tobytes(), total, len(ff)
 
 
 def _segments(block_bits, per_segment: int):
@@ -89,30 +67,21 @@ def planes_file(oracle, y: np.ndarray, cb: np.ndarray, cr: np.ndarray, quality: 
     h, w = y.shape
     hs, vs, bw, bh, mx, my = im.geometry(w, h, sub)
     ny, bpm = hs * vs, hs * vs + 2
-    lq, cq = cm.scaled_table(cm.LUMA_Q, quality), cm.scaled_table(cm.CHROMA_Q, quality)
-    planes = [cm.plane_zigzag(oracle, y, lq), cm.plane_zigzag(oracle, cb, cq), cm.plane_zigzag(oracle, cr, cq)]
+    lq, cq = sm.scaled_table(sm.LUMA_Q, quality), sm.scaled_table(sm.CHROMA_Q, quality)
+    planes = [sm.plane_zigzag(oracle, y, lq), sm.plane_zigzag(oracle, cb, cq), sm.plane_zigzag(oracle, cr, cq)]
     assert planes[0].shape[0] == bw * bh and planes[1].shape[0] == planes[2].shape[0] == mx * my
-    zy, pad = im._mcu_order_luma(planes[0], bw, bh, hs, vs, mx, my)
+    zy, pad = sm.mcu_order_luma(planes[0], bw, bh, hs, vs, mx, my)
 
     scans, scan_bits, seg_bits, stuffed = [], [], [], []
     # ---- scan 1: the DC differences in MCU order, each component against its own predictor ----
     dc_size, per_comp = 0, []
     for comp, zz in enumerate((zy, planes[1], planes[2])):
-        dc, _ = _tables(comp > 0)
-        diffs = np.diff(np.r_[0, zz[:, 0].astype(np.int64)])
-        out = []
-        for d in diffs.tolist():
-            size = abs(d).bit_length()
-            dc_size = max(dc_size, size)
-            code, ln = dc.get(size, (0, 0))
-            out.append(((code << size) | _amp(d, size), ln + size))
-        per_comp.append(out)
-    symbols, mcu_bits = [], []
-    for m in range(mx * my):
-        blocks = per_comp[0][m * ny:(m + 1) * ny] + [per_comp[1][m], per_comp[2][m]]
-        symbols += blocks
-        mcu_bits.append(sum(b[1] for b in blocks))
-    data, total, ff = _pack(symbols)
+        (code, ln), _ = sm.std_tables(comp > 0)
+        size, amp = sm.dc_symbols(zz[:, 0], len(zz))
+        dc_size = max(dc_size, int(size.max()))
+        per_comp.append(((code[size] << size) | amp, ln[size] + size, np.ones(len(zz), np.int64)))
+    val, length, mcu_bits = sm.mcu_merge(per_comp, ny)
+    data, total, ff = sm.pack(val, length)
     scans.append(data); scan_bits.append(total); stuffed.append(ff)
     seg_bits.append(_segments(mcu_bits, SEG_BLOCKS // bpm))
 
@@ -121,7 +90,7 @@ def planes_file(oracle, y: np.ndarray, cb: np.ndarray, cr: np.ndarray, quality: 
     no_end, eob_only = [0, 0], [0, 0]
     for band, (ss, se) in enumerate(BANDS):
         for comp in range(3):
-            _, ac = _tables(comp > 0)
+            code, ln = (t.tolist() for t in sm.std_tables(comp > 0)[1])
             zz = planes[comp].astype(np.int64)
             symbols, block_bits = [], []
             for blk in zz.tolist():
@@ -132,21 +101,21 @@ def planes_file(oracle, y: np.ndarray, cb: np.ndarray, cr: np.ndarray, quality: 
                         run += 1
                         continue
                     while run >= 16:
-                        symbols.append(ac[0xF0])
+                        symbols.append((code[0xF0], ln[0xF0]))
                         zrl[(band, comp > 0)] += 1
                         run -= 16
                     size = abs(c).bit_length()
-                    code, ln = ac.get((run << 4) | size, (0, 0))
-                    symbols.append(((code << size) | _amp(c, size), ln + size))
+                    rs = (run << 4) | size
+                    symbols.append(((code[rs] << size) | _amp(c, size), ln[rs] + size))
                     run = 0
                 if blk[se] == 0:
-                    symbols.append(ac[0x00])                     # EOB0: an end-of-band run of exactly one block
+                    symbols.append((code[0x00], ln[0x00]))       # EOB0: an end-of-band run of exactly one block
                 else:
                     no_end[band] += 1
                 if not any(blk[ss:se + 1]):
                     eob_only[band] += 1
                 block_bits.append(sum(s[1] for s in symbols[n0:]))
-            data, total, ff = _pack(symbols)
+            data, total, ff = sm.pack(*np.array(symbols, np.int64).T)
             scans.append(data); scan_bits.append(total); stuffed.append(ff)
             seg_bits.append(_segments(block_bits, SEG_BLOCKS))
     every = np.concatenate(planes)
@@ -163,6 +132,4 @@ def progressive_ycbcr_file(oracle, y, cb, cr, quality: int = 0, sub: int = cm.SU
 
 def progressive_file(oracle, rgb: np.ndarray, quality: int = 0, sub: int = cm.SUB_420) -> Progressive:
     """The progressive file the library must write for these R, G, B pixels: the planes the other colour paths derive."""
-    y = m422.luma_plane(rgb)
-    cb, cr = m422.chroma_planes_422(rgb) if sub == m422.SUB_422 else cm.chroma_planes(rgb, sub)
-    return planes_file(oracle, y, cb, cr, quality, sub)
+    return planes_file(oracle, *sm.planes_of(rgb, sub), quality, sub)

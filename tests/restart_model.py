@@ -1,11 +1,11 @@
 """CPU model of the one-scan colour file WITH RESTART INTERVALS (include/jpeg_compression.h) -- TEST INFRASTRUCTURE
 ONLY.
 
-Built from interleaved_model's parts: its geometry, prefix, MCU order with pad blocks, symbols and tables.  The oracle's RLE runs per
-interval and per component, so every interval starts with all three DC predictors at 0.  An interval's bit string is padded with
-1-bits to a byte, stuffed, and followed by RSTn; the last one is flushed with 0-bits and followed by EOI.  Besides the file the model
-counts what the device's writer has to get right: padded bytes that came out 0xFF, intervals that needed no padding, 0xFF bytes that
-straddle two of the coder's segments inside an interval."""
+Built from interleaved_model's geometry, prefix and coefficients and scan_model's coder.  The oracle's RLE runs per interval and per
+component, so every interval starts with all three DC predictors at 0.  An interval's bit string is padded with 1-bits to a byte,
+stuffed, and followed by RSTn; the last one is flushed with 0-bits and followed by EOI (scan_model.frame_intervals).  Besides the file
+the model counts what the device's writer has to get right: padded bytes that came out 0xFF, intervals that needed no padding, 0xFF
+bytes that straddle two of the coder's segments inside an interval."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -14,6 +14,7 @@ import numpy as np
 
 import color_model as cm
 import interleaved_model as im
+import scan_model as sm
 
 
 @dataclass(frozen=True)
@@ -60,80 +61,17 @@ def segment_entries(w: int, h: int, sub: int, ri: int) -> int:
     return -(-m // ri) * -(-min(ri, m) // seg_mcus(sub))
 
 
-def _coded(oracle, zz: np.ndarray, chroma: bool):
-    """The blocks' symbols coded with the component's tables, DC predictor 0 in front of the first block: value and length per
-    symbol, symbols per block."""
-    sym, amp, alen, is_dc, counts = im._symbols_by_block(oracle, zz)
-    dcc, dcl, acc, acl = im._tables(chroma)
-    code = np.where(is_dc, dcc[sym], acc[sym])
-    clen = np.where(is_dc, dcl[sym], acl[sym])
-    return (code << alen) | (amp & ((1 << alen) - 1)), clen + alen, counts
-
-
-def _interval_bits(oracle, zy, zcb, zcr, a: int, b: int, ny: int):
-    """MCUs [a, b) as one interval: its bits (uint8 0 / 1) and the bit count of each of its MCUs."""
-    bpm = ny + 2
-    vals, lens, keys = [], [], []
-    for comp, zz in enumerate((zy[a * ny:b * ny], zcb[a:b], zcr[a:b])):
-        val, length, counts = _coded(oracle, zz, comp > 0)
-        blk = np.arange(zz.shape[0])
-        key = (blk // ny) * bpm + blk % ny if comp == 0 else blk * bpm + ny + comp - 1
-        vals.append(val)
-        lens.append(length)
-        keys.append(np.repeat(key, counts))
-    val, length, key = np.concatenate(vals), np.concatenate(lens), np.concatenate(keys)
-    order = np.argsort(key, kind="stable")
-    val, length, key = val[order], length[order], key[order]
-    total = int(length.sum())
-    starts = np.cumsum(length) - length
-    idx = np.repeat(np.arange(len(val)), length)
-    off = np.arange(total) - starts[idx]
-    bits = ((val[idx] >> (length[idx] - 1 - off)) & 1).astype(np.uint8)
-    mcu_bits = np.bincount(key // bpm, weights=length, minlength=b - a).astype(np.int64)
-    return bits, mcu_bits
-
-
 def planes_file(oracle, y: np.ndarray, cb: np.ndarray, cr: np.ndarray, quality: int, sub: int, ri: int) -> Restart:
     assert 1 <= ri <= 65535
     h, w = y.shape
-    hs, vs, bw, bh, mx, my = im.geometry(w, h, sub)
-    ny, m, s = hs * vs, mx * my, seg_mcus(sub)
-    lq, cq = cm.scaled_table(cm.LUMA_Q, quality), cm.scaled_table(cm.CHROMA_Q, quality)
-    zy, _ = im._mcu_order_luma(cm.plane_zigzag(oracle, y, lq), bw, bh, hs, vs, mx, my)
-    zcb, zcr = cm.plane_zigzag(oracle, cb, cq), cm.plane_zigzag(oracle, cr, cq)
-    n = -(-m // ri)
-    body = bytearray()
-    markers = pad_ff = aligned = stuffed = scan_bits = two = longest = 0
-    phases = []
-    for i in range(n):
-        a, b = i * ri, min((i + 1) * ri, m)
-        bits, mcu_bits = _interval_bits(oracle, zy, zcb, zcr, a, b, ny)
-        scan_bits += len(bits)
-        last = i == n - 1
-        r = len(bits) % 8
-        if r:
-            bits = np.r_[bits, np.full(8 - r, 0 if last else 1, np.uint8)]
-        elif not last:
-            aligned += 1
-        by = np.packbits(bits)
-        if r and not last and by[-1] == 0xFF:
-            pad_ff += 1
-        ends = np.cumsum(mcu_bits)                               # the coder's segments: runs of s MCUs from the interval's first
-        seg_bits = np.diff(np.r_[0, ends[s - 1::s], ends[-1]]) if (b - a) % s else np.diff(np.r_[0, ends[s - 1::s]])
-        assert seg_bits.sum() == ends[-1] and len(seg_bits) == -(-(b - a) // s) and seg_bits.min() >= 14
-        two += len(seg_bits) >= 2
-        longest = max(longest, int(seg_bits.max()))
-        for p in np.cumsum(seg_bits)[:-1]:
-            if p % 8 and by[p // 8] == 0xFF:
-                phases.append(int(p % 8))
-        ff = np.nonzero(by == 0xFF)[0]
-        stuffed += len(ff)
-        body += np.insert(by, ff + 1, 0).tobytes()
-        if not last:
-            body += bytes([0xFF, 0xD0 + i % 8])
-            markers += 1
-    return Restart(prefix(w, h, quality, sub, ri) + bytes(body) + b"\xff\xd9", n, markers, pad_ff, aligned, len(phases), tuple(phases),
-                   stuffed, scan_bits, segment_entries(w, h, sub, ri), int(two), longest)
+    zy, zcb, zcr, _, ny, _ = im.scan_blocks(oracle, y, cb, cr, quality, sub)
+    bits, mcu_bits = sm.scan_bits(sm.scan_symbols(oracle, zy, zcb, zcr, ny, ri), sm.std_tables(False), sm.std_tables(True), ny)
+    body, ivs = sm.frame_intervals(bits, mcu_bits, ri, seg_mcus(sub))
+    assert min(min(v.seg_bits) for v in ivs) >= 14
+    phases = tuple(p for v in ivs for p in v.straddle_phases)
+    return Restart(prefix(w, h, quality, sub, ri) + body + b"\xff\xd9", len(ivs), len(ivs) - 1, sum(v.pad_ff for v in ivs),
+                   sum(v.aligned for v in ivs), len(phases), phases, sum(v.ff for v in ivs), sum(v.bits for v in ivs),
+                   segment_entries(w, h, sub, ri), sum(len(v.seg_bits) >= 2 for v in ivs), max(max(v.seg_bits) for v in ivs))
 
 
 def restart_ycbcr_file(oracle, y, cb, cr, quality: int = 0, sub: int = cm.SUB_420, ri: int = 1) -> Restart:
@@ -143,31 +81,10 @@ def restart_ycbcr_file(oracle, y, cb, cr, quality: int = 0, sub: int = cm.SUB_42
 
 def restart_file(oracle, rgb: np.ndarray, quality: int = 0, sub: int = cm.SUB_420, ri: int = 1) -> Restart:
     """The file the library must write for these R, G, B pixels: the planes of interleaved_model.interleaved_file."""
-    y = im.m422.luma_plane(rgb)
-    cb, cr = im.m422.chroma_planes_422(rgb) if sub == im.m422.SUB_422 else cm.chroma_planes(rgb, sub)
-    return planes_file(oracle, y, cb, cr, quality, sub, ri)
+    return planes_file(oracle, *sm.planes_of(rgb, sub), quality, sub, ri)
 
 
 def with_dri(plain: bytes, ri: int) -> bytes:
     """Rule 5: the one-scan file `plain` with the DRI segment inserted in front of its SOS."""
     at = plain.index(im.SOS3)
     return plain[:at] + dri(ri) + plain[at:]
-
-
-def walk_scan(data: bytes):
-    """A structural walk of a file's scan that knows nothing of how it was written: -> (markers in order, stuffed 0x00 bytes).  Every
-    0xFF of the scan must be followed by 0x00, by an RSTn marker or -- as the file's last two bytes -- by EOI."""
-    at = data.index(im.SOS3) + len(im.SOS3)
-    markers, stuffed = [], 0
-    while True:
-        j = data.find(b"\xff", at)
-        assert j >= 0 and j + 1 < len(data), "the scan ends without EOI"
-        nxt = data[j + 1]
-        if nxt == 0x00:
-            stuffed += 1
-        elif 0xD0 <= nxt <= 0xD7:
-            markers.append(nxt - 0xD0)
-        else:
-            assert nxt == 0xD9 and j + 2 == len(data), (hex(nxt), j, len(data))
-            return markers, stuffed
-        at = j + 2

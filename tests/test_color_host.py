@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import color_model as cm
+import scan_model as sm
 
 QUALITIES = (1, 10, 50, 75, 90, 100)
 
@@ -84,7 +85,7 @@ def test_model_packer_matches_the_oracle_on_luma(oracle, jpegamd):
     """The model's Huffman packer, run with the luma tables, is the oracle's own entropy coder."""
     for (w, h, seed, kind) in ((53, 37, 3, 0), (40, 17, 4, 1), (64, 64, 2, 3)):
         st = oracle.stages(jpegamd.synth_bmp(w, h, seed, kind, 0))
-        assert cm.pack_scan(oracle, st["zigzag"], False) == oracle.entropy(st["zigzag"])
+        assert sm.pack_scan(oracle, st["zigzag"], False) == oracle.entropy(st["zigzag"])
 
 
 def test_model_prefix_shares_the_grayscale_headers(oracle):

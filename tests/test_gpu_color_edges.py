@@ -12,6 +12,7 @@ import pytest
 
 import color_fixtures as cf
 import color_model as cm
+import scan_model as sm
 from gpu_support import WIDE_STRIDE, ColorCall, dev, encode_gray, model, rows_for, stored_rows, stream, synth_rgb, upload     # noqa: F401
 from gpu_support import gray_bmp_sized as gray_bmp
 
@@ -170,7 +171,7 @@ def _chroma_scan_model(oracle, rgb, quality, sub, rows=2048):
             parts[k].append(plane)
     out = []
     for comp, k in ((2, 0), (3, 1)):
-        out += [cm.sos(comp), cm.pack_scan(oracle, cm.plane_zigzag(oracle, np.concatenate(parts[k]), cq), True)]
+        out += [cm.sos(comp), sm.pack_scan(oracle, cm.plane_zigzag(oracle, np.concatenate(parts[k]), cq), True)]
     return b"".join(out)
 
 

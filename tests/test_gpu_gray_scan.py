@@ -14,6 +14,7 @@ import gray_scan_model as gm
 import huffman_fixtures as hf
 import huffman_model as hm
 import mjpeg_support as ms
+import scan_model as sm
 from gpu_support import dev  # noqa: F401
 
 torch = gs.torch
@@ -112,7 +113,7 @@ def test_one_interval_is_the_grayscale_entrys_file_with_dri(jpegamd, oracle, dev
 def test_every_order_row_order_and_a_padded_stride(jpegamd, oracle, dev, enc, optimized):
     w, h, q, ri = 72, 40, 75, 5
     rgb = hf.synth_rgb(w, h, 21)
-    y = gm.luma(rgb)
+    y = sm.luma_plane(rgb)
     want = gf.model(oracle, y, q, ri, optimized).file
     enc.set_huffman(jpegamd.HUFFMAN_OPTIMIZED if optimized else jpegamd.HUFFMAN_STANDARD)
     try:

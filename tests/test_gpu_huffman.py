@@ -10,6 +10,7 @@ import color_model as cm
 import gpu_support as gs
 import huffman_fixtures as hf
 import huffman_model as hm
+import interleaved_model as im
 import mjpeg_support as ms
 from gpu_support import dev  # noqa: F401
 from huffman_fixtures import S420, S422, S444, SUBS
@@ -207,4 +208,4 @@ def test_mjpeg_functions_leave_the_shared_context_in_standard(jpegamd, oracle, d
     planes = ms.derived_planes(rgb, S420)
     y, cb, cr = (torch.from_numpy(p).to(dev)[None] for p in planes)
     assert mj.encode_ycbcr_batch(y, cb, cr, 50, S420, huffman="optimized") == [hf.planes_model(oracle, planes, 50, S420, 0).file]
-    assert mj.encode_ycbcr_batch(y, cb, cr, 50, S420) == [cm.memo(hm.im.interleaved_ycbcr_file, oracle, *planes, 50, S420).file]
+    assert mj.encode_ycbcr_batch(y, cb, cr, 50, S420) == [cm.memo(im.interleaved_ycbcr_file, oracle, *planes, 50, S420).file]

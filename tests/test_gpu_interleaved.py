@@ -11,6 +11,7 @@ import pytest
 import color_model as cm
 import gpu_support as gs
 import interleaved_model as im
+import scan_model as sm
 from gpu_support import CBCR, CRCB, PLANES, S420, S422, S444, dev  # noqa: F401
 
 torch = gs.torch
@@ -56,9 +57,7 @@ class YccCall(gs.Outputs):
 
 def derived_planes(rgb, sub):
     """(y, cb, cr) as the RGB entries derive them at `sub`."""
-    y = cm.model_planes(rgb, S444)[0]
-    cb, cr = gs.m422.chroma_planes_422(rgb) if sub == S422 else cm.chroma_planes(rgb, sub)
-    return tuple(np.ascontiguousarray(p) for p in (y, cb, cr))
+    return tuple(np.ascontiguousarray(p) for p in sm.planes_of(rgb, sub))
 
 
 def rgb_files(jpegamd, enc, rgbs, dev, sub, q=0, **kw):
@@ -306,7 +305,7 @@ def test_independent_decoder_sees_the_three_scan_pixels(jpegamd, oracle, dev, en
 
 def test_neighbours_on_the_same_context_are_unchanged(jpegamd, oracle, dev, enc):
     rgbs = gs.pictures(jpegamd, 72, 40, 4, seed=9)
-    grays = [cm.model_planes(r, S444)[0] for r in rgbs]
+    grays = [sm.luma_plane(r) for r in rgbs]
     want_color = [gs.model(oracle, r, 50, S420) for r in rgbs]
     want_gray = [cm.memo(cm.gray_file, oracle, p, 50) for p in grays]
     want_one = [model(oracle, r, 50, S420).file for r in rgbs]

@@ -14,6 +14,7 @@ import color_model as cm
 import gpu_support as gs
 import interleaved_model as im
 import restart_model as rm
+import scan_model as sm
 from gpu_support import CBCR, CRCB, PLANES, S420, S422, S444, dev  # noqa: F401
 
 torch = gs.torch
@@ -65,9 +66,7 @@ def rgb_files(jpegamd, enc, rgbs, dev, sub, ri, q=0, **kw):
 
 def derived_planes(rgb, sub):
     """(y, cb, cr) as the RGB entries derive them at `sub`."""
-    y = cm.model_planes(rgb, S444)[0]
-    cb, cr = gs.m422.chroma_planes_422(rgb) if sub == S422 else cm.chroma_planes(rgb, sub)
-    return tuple(np.ascontiguousarray(p) for p in (y, cb, cr))
+    return tuple(np.ascontiguousarray(p) for p in sm.planes_of(rgb, sub))
 
 
 def decode(data: bytes) -> np.ndarray:
@@ -113,7 +112,7 @@ def test_geometry_and_interval(jpegamd, oracle, dev, enc, w, h, sub):
         assert st.entropy_bits == m.scan_bits and st.stuffed_bytes == m.stuffed, ri
     if (w, h) == (200, 120):
         assert seen_two > 0                                         # Ri = S + 1 and Ri = M: intervals of several coder segments
-        assert rm.walk_scan(model(oracle, rgb, 75, sub, 1).file)[0][8] == 0         # the marker counter wrapped
+        assert sm.walk_scan(model(oracle, rgb, 75, sub, 1).file, im.SOS3)[0][8] == 0         # the marker counter wrapped
 
 
 def test_one_interval_is_the_plain_file_with_dri(jpegamd, oracle, dev, enc):
@@ -195,7 +194,7 @@ def test_more_segments_than_one_round_of_the_offsets_kernel(jpegamd, dev, size, 
         e.close()
     at = f.index(im.SOS3)
     assert f[at - 6:at] == rm.dri(ri) and f[:at - 6] == plain[:at - 6]
-    markers, stuffed = rm.walk_scan(f)
+    markers, stuffed = sm.walk_scan(f, im.SOS3)
     assert len(markers) == n - 1 and markers == [i % 8 for i in range(n - 1)]
     assert stuffed == st.stuffed_bytes
     assert np.array_equal(decode(f), decode(plain))
@@ -289,7 +288,7 @@ def test_ycbcr_odd_address_and_stride(jpegamd, oracle, dev, enc, sub, layout):
 # ---- neighbours, decoder, binding -------------------------------------------------------------------------------------------------------
 def test_neighbours_on_the_same_context_are_unchanged(jpegamd, oracle, dev, enc):
     rgbs = gs.pictures(jpegamd, 72, 40, 4, seed=9)
-    grays = [cm.model_planes(r, S444)[0] for r in rgbs]
+    grays = [sm.luma_plane(r) for r in rgbs]
     want_color = [gs.model(oracle, r, 50, S420) for r in rgbs]
     want_gray = [cm.memo(cm.gray_file, oracle, p, 50) for p in grays]
     want_one = [plain_model(oracle, r, 50, S420).file for r in rgbs]

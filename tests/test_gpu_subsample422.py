@@ -7,6 +7,7 @@ import pytest
 
 import color_model as cm
 import color_model_422 as m422
+import scan_model as sm
 from gpu_support import (PLANES, CBCR, CRCB, S422, UYVY, YUYV, ColorBatch, ColorCall, YccBatch, dev, finish_files, random_planes,     # noqa: F401
                          rows_for, run_ycc, stream, synth_rgb, upload, ycc_file)
 from gpu_support import LAYOUTS_422 as YCC_LAYOUTS
@@ -146,7 +147,7 @@ def test_the_rgb_paths_own_planes_give_the_rgb_paths_file_at_422(jpegamd, oracle
     want = [want_rgb(oracle, r, 0) for r in rgbs]
     enc = jpegamd.Encoder(w, rows_for(3, h))
     assert finish_batch(enc, ColorBatch(jpegamd, enc, rgbs, dev, S422)) == want      # what the colour path writes
-    planes = [(m422.luma_plane(r),) + m422.chroma_planes_422(r) for r in rgbs]
+    planes = [sm.planes_of(r, S422) for r in rgbs]
     for layout in YCC_LAYOUTS:
         assert run_ycc(jpegamd, enc, planes, dev, S422, layout) == want, layout
 
@@ -265,7 +266,7 @@ def test_one_picture_of_a_422_batch_one_byte_short(jpegamd, oracle, dev):
     cap = len(exp[1]) - 1
     assert cap > max(len(exp[0]), len(exp[2]))
     enc = jpegamd.Encoder(w, rows_for(3, h))
-    planes = [(m422.luma_plane(r),) + m422.chroma_planes_422(r) for r in rgbs]
+    planes = [sm.planes_of(r, S422) for r in rgbs]
     jobs = [lambda c: ColorBatch(jpegamd, enc, rgbs, dev, S422, cap=c), lambda c: YccBatch(jpegamd, enc, planes, dev, S422, YUYV, cap=c),
             lambda c: YccBatch(jpegamd, enc, planes, dev, S422, PLANES, cap=c)]
     for k, job in enumerate(jobs):

@@ -16,6 +16,7 @@ import pytest
 import color_fixtures as cf
 import color_model as cm
 import path_model as pm
+import scan_model as sm
 import threshold_fixtures as tf
 from gpu_support import dev     # noqa: F401
 
@@ -122,7 +123,7 @@ def test_statistics_of_the_zrl_and_write_out_fixtures(jpegamd, oracle, dev, luma
             enc.set_pipeline(getattr(jpegamd, "PIPELINE_" + pipeline))
             got, st, _ = _run(jpegamd, enc, dev, [y], w, h, q, True)
             zz = oracle.stages(tf.gray_bmp(y), q)["zigzag"]
-            sym, _, alen, is_dc = cm._symbols(oracle, zz)
+            sym, _, alen, is_dc, _ = sm.symbols(oracle, zz)
             bits = int((alen + np.where(is_dc, pm.LUMA.dc_len[sym & 15], pm.LUMA.ac_len[sym])).sum())
             assert got[0] == want
             assert st.entropy_bits == bits and (bits + 7) // 8 == len(pm.unstuff(want[328:-2])), s["name"]

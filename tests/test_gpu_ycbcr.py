@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import color_model as cm
+import scan_model as sm
 from gpu_support import (CBCR, CRCB, LAYOUTS, PLANES, S420, S444, WIDE_STRIDE, ColorBatch, YccBatch, chroma_dims, dev, model, pictures,     # noqa: F401
                          random_planes, rows_for, run_ycc, smooth_planes, stream, upload)
 from gpu_support import ycc_file as expected
@@ -46,7 +47,7 @@ def test_the_rgb_paths_own_planes_give_the_rgb_paths_file(jpegamd, dev, sub):
     enc.finish()
     want = [f for f, _ in b.results()]
     assert all(len(f) > 700 for f in want)
-    planes = [cm.model_planes(rgb, sub) for rgb in rgbs]
+    planes = [sm.planes_of(rgb, sub) for rgb in rgbs]
     for layout in LAYOUTS:
         assert run_ycc(jpegamd, enc, planes, dev, sub, layout) == want, (sub, layout)
 

@@ -13,6 +13,7 @@ import color_model as cm
 import gray_scan_fixtures as gf
 import gray_scan_model as gm
 import mjpeg_support as ms
+import scan_model as sm
 
 ERR_ARG, ERR_TOO_LARGE = -1, -5
 NAMES = ("jpegamd_encode_gray_scan_batch_async", "jpegamd_max_jfif_bytes_gray_scan")
@@ -61,7 +62,7 @@ def test_every_variant_decodes_to_the_reference_pixels(oracle, shapes):
             for opt in gf.MODES:
                 m = gf.model(oracle, p, q, ri, opt)
                 assert np.array_equal(_decode(m.file), want), (name, ri, opt)
-                markers, stuffed = gm.walk_scan(m.file)
+                markers, stuffed = sm.walk_scan(m.file, gm.SOS1)
                 n = -(-blocks // ri) if ri else 1
                 assert markers == [i % 8 for i in range(n - 1)] and stuffed == m.stuffed, (name, ri, opt)
                 assert m.intervals == n and m.markers == n - 1
@@ -163,7 +164,7 @@ def test_symbols_are_exported_and_documented(jpegamd):
 
 def _call(jpegamd, ctx, imgs, ri=0, count=None, outs=True, sizes=True):
     arr = (jpegamd.Image * max(len(imgs), 1))(*imgs) if imgs is not None else None
-    out_arr, size_arr = ms._arrays()
+    out_arr, size_arr = ms.out_arrays()
     return jpegamd.lib.jpegamd_encode_gray_scan_batch_async(ctx, arr, len(imgs) if count is None else count, ri, out_arr if outs else None,
                                                            1 << 20, size_arr if sizes else None, None)
 

@@ -16,6 +16,7 @@ import huffman_model as hm
 import interleaved_model as im
 import mjpeg_support as ms
 import restart_model as rm
+import scan_model as sm
 from huffman_fixtures import S420, S422, S444, SUBS
 
 ERR_ARG = -1
@@ -127,7 +128,7 @@ def test_optimised_file_differs_from_the_standard_one_in_dht_and_scan_alone(jpeg
             assert m.file[:head] == std[:head]
             s_at = std.index(im.SOS3) + len(im.SOS3)
             assert m.file[m.prefix_len - tail:m.prefix_len] == std[s_at - tail:s_at]
-            assert rm.walk_scan(m.file)[0] == rm.walk_scan(std)[0] and rm.walk_scan(m.file)[1] == m.stuffed
+            assert sm.walk_scan(m.file, im.SOS3)[0] == sm.walk_scan(std, im.SOS3)[0] and sm.walk_scan(m.file, im.SOS3)[1] == m.stuffed
             assert len(m.file) <= (jpegamd.max_jfif_bytes_interleaved_restart(200, 120, sub, ri))
     # the counts depend on the interval: a DC difference against 0 at every interval's start
     a, b = hf.model(oracle, rgb, 75, S420, 0), hf.model(oracle, rgb, 75, S420, 1)

@@ -12,6 +12,7 @@ import pytest
 import color_model as cm
 import color_model_422 as m422
 import interleaved_model as im
+import scan_model as sm
 
 ERR_ARG = -1
 CAP = 1 << 20
@@ -74,8 +75,8 @@ def test_model_luma_scan_is_the_oracles(jpegamd, oracle):
     """The model's Y coefficients and symbols are the ones the three-scan file's Y scan is made of."""
     for w, h, kind in ((33, 17, 1), (72, 24, 0)):
         rgb = cm.read_bmp_rgb(jpegamd.synth_bmp(w, h, 3, kind, 0))
-        zz = cm.plane_zigzag(oracle, m422.luma_plane(rgb), cm.scaled_table(cm.LUMA_Q, 90))
-        assert cm.pack_scan(oracle, zz, False) == cm.gray_scan(oracle, cm.write_bmp(rgb), 90)
+        zz = cm.plane_zigzag(oracle, sm.luma_plane(rgb), cm.scaled_table(cm.LUMA_Q, 90))
+        assert sm.pack_scan(oracle, zz, False) == cm.gray_scan(oracle, cm.write_bmp(rgb), 90)
 
 
 def test_symbols_are_exported_and_documented(jpegamd):

@@ -14,6 +14,7 @@ import color_model as cm
 import color_model_422 as m422
 import interleaved_model as im
 import restart_model as rm
+import scan_model as sm
 
 ERR_ARG = -1
 CAP = 1 << 20
@@ -79,7 +80,7 @@ def test_scan_structure(jpegamd, oracle, w, h, sub):
     for ri in intervals_for(w, h, sub):
         m = _model(oracle, rgb, sub, ri)
         n = -(-(mx * my) // ri)
-        markers, stuffed = rm.walk_scan(m.file)
+        markers, stuffed = sm.walk_scan(m.file, im.SOS3)
         assert markers == [i % 8 for i in range(n - 1)], ri
         assert len(markers) == m.markers == n - 1 == m.intervals - 1
         assert stuffed == m.stuffed
@@ -95,7 +96,7 @@ def test_scan_structure(jpegamd, oracle, w, h, sub):
 def test_marker_counter_wraps(jpegamd, oracle):
     rgb = _picture(jpegamd, 200, 120)
     m = _model(oracle, rgb, cm.SUB_420, 1)
-    markers, _ = rm.walk_scan(m.file)
+    markers, _ = sm.walk_scan(m.file, im.SOS3)
     assert len(markers) == 103 >= 9 and markers[:10] == [0, 1, 2, 3, 4, 5, 6, 7, 0, 1] and markers[-1] == 102 % 8
 
 

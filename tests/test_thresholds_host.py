@@ -9,8 +9,8 @@ from __future__ import annotations
 import numpy as np
 import pytest
 
-import color_model as cm
 import path_model as pm
+import scan_model as sm
 import threshold_fixtures as tf
 
 MAX_UNREACHABLE = 3
@@ -29,7 +29,7 @@ def reports(doc):
 def _totals_match(oracle, rep, zz, scan, chroma):
     """bits -- to the bit: the oracle's run/size symbols with the code lengths of T.81's tables, and the scan's zero-bit flush --,
     symbols, 0xFF bytes"""
-    sym, _, alen, is_dc = cm._symbols(oracle, zz)
+    sym, _, alen, is_dc, _ = sm.symbols(oracle, zz)
     tab = pm.CHROMA if chroma else pm.LUMA
     assert rep["total_bits"] == int((alen + np.where(is_dc, tab.dc_len[sym & 15], tab.ac_len[sym])).sum())
     stream = pm.unstuff(scan)

@@ -24,11 +24,12 @@ for _p in (str(HERE), str(HERE.parent)):
 import color_fixtures as cf   # noqa: E402
 import color_model as cm      # noqa: E402
 import path_model as pm       # noqa: E402
+import scan_model as sm       # noqa: E402
 
 JSON_PATH = HERE / "golden" / "thresholds.json"
 NPAT, BANK_SEED = 64, 20240917
 _BANK = np.random.default_rng(BANK_SEED).integers(-128, 128, (NPAT, 8, 8))
-_BASIS = cf._basis()
+_BASIS = cf.basis()
 K = pm.K
 
 
@@ -111,7 +112,7 @@ def zigzag_of(spec: dict) -> np.ndarray:
 
 
 def scan_of(spec: dict, zz: np.ndarray) -> bytes:
-    return cm.pack_scan(_oracle(), zz, True) if spec["plane"] == "cb" else _oracle().entropy(zz)
+    return sm.pack_scan(_oracle(), zz, True) if spec["plane"] == "cb" else _oracle().entropy(zz)
 
 
 def report_of(spec: dict, with_scan: bool = True):
