@@ -510,7 +510,7 @@ uint64_t jpegamd_max_jfif_bytes_gray_scan(int32_t width, int32_t height, int32_t
  * file holds the coefficients of the one-scan file of the same input (jpegamd_encode_color_interleaved_pixels_batch_async,
  * jpegamd_encode_ycbcr_interleaved_matrix_batch_async), so a decoder reconstructs the same pixels.  What this version gives is the
  * progressive rendering; the file is a little LARGER than the one-scan file (six more SOS headers, an end-of-band symbol per block
- * and band, seven flushes), because no end-of-band runs are coded.
+ * and band, seven flushes), because no end-of-band runs are coded: the entries with per-scan optimised tables further down code them.
  *   Layout.  The one-scan file's prefix up to and including its four Annex K DHT segments, with ONE change: the frame header's
  *     marker is FF C2 where that file has FF C0 (length, contents and the sampling factors 0x11 / 0x22 / 0x21 stay).  Then seven
  *     scans, each an SOS segment and a byte-aligned entropy-coded segment, then EOI:
@@ -528,7 +528,7 @@ uint64_t jpegamd_max_jfif_bytes_gray_scan(int32_t width, int32_t height, int32_t
  * jpegamd_encode_color_progressive_batch_async takes the pictures of jpegamd_encode_color_interleaved_pixels_batch_async (BGR, RGB,
  * RGBA, BGRA), jpegamd_encode_ycbcr_progressive_batch_async everything jpegamd_encode_ycbcr_interleaved_matrix_batch_async reads,
  * with the same sample_range, sample_format and matrix.  Each refuses what its one-scan twin refuses, and JPEGAMD_ORDER_GRAY, and a
- * context set to JPEGAMD_HUFFMAN_OPTIMIZED (per-scan optimised tables are not written yet): JPEGAMD_ERR_ARG with nothing allocated
+ * context set to JPEGAMD_HUFFMAN_OPTIMIZED (per-scan optimised tables are the entries below): JPEGAMD_ERR_ARG with nothing allocated
  * or launched.  Batching, context sizing, capacity handling and profiling are the one-scan entries': a picture that does not fit
  * out_capacity gets size 0, nothing is written past out_capacity (what was written of its first scan stays in the buffer), the other
  * pictures are unaffected, jpegamd_encoder_finish returns JPEGAMD_ERR_HUFF_CAPACITY and the context stays usable.  finish reports
@@ -551,6 +551,48 @@ int32_t jpegamd_encode_ycbcr_progressive_batch_async(JpegAmdEncoder *enc, const 
                                                      void *const *outs_dev, uint64_t out_capacity, void *const *out_sizes_dev,
                                                      void *stream);
 uint64_t jpegamd_max_jfif_bytes_progressive(int32_t width, int32_t height, int32_t subsampling);
+
+/* Progressive colour files with END-OF-BAND RUNS and PER-SCAN OPTIMISED TABLES: the file above with three changes.  Unchanged: the
+ * coefficients, the scan script, the SOS bytes, the MCU order, pad blocks and predictors of scan 1, stuffing, the zero-bit flush of
+ * every scan, EOI.  The file is about the size of the one-scan file with per-picture optimised tables.
+ *   1. No Annex K DHT segments.  The head is SOI, APP0, DQT, SOF2.  Scan 1 is preceded by its own DHT 0/0 (Y DC) and DHT 0/1 (Cb and
+ *      Cr DC, counted together), in that order, then the DC scan's SOS.  Each of the scans 2 .. 7 is preceded by ONE DHT segment with
+ *      Tc/Th 0x10 (Y) or 0x11 (Cb, Cr), then its 10-byte SOS: the table ids 1/0 and 1/1 are redefined from scan to scan.  Every DHT
+ *      is FF C4, length 19 + nvals, the Tc/Th byte, 16 BITS bytes, HUFFVAL.  Every table is built from the counts of the symbols ITS
+ *      scan codes by the construction of JPEGAMD_HUFFMAN_OPTIMIZED above: steps 1 - 6 with the reserved point, the highest index
+ *      winning ties, the 16-bit limit; a table with one used symbol gives it the 1-bit code 0.
+ *   2. End-of-band runs in the scans 2 .. 7 (T.81 G.1.2.2).  Blocks are indexed in the component's own raster block order.  Let E[i]
+ *      mean "coefficient Se of block i is zero" and Z[i] "the coefficients Ss .. Se of block i are all zero".  A block first codes its
+ *      non-zero coefficients as above -- run/size and amplitude, a ZRL per sixteen zeros, nothing for the trailing zeros.  Block i
+ *      then STARTS A RUN iff E[i] and not (Z[i] and i mod 256 != 0 and E[i - 1]).  The run's length r is 1 plus the number of
+ *      consecutive blocks j = i + 1, i + 2, ... with Z[j] and j mod 256 != 0.  It is coded as symbol n << 4, n = floor(log2 r),
+ *      followed by the n low bits of r - 2^n.  A block that neither starts a run nor has non-zero coefficients codes nothing.
+ *   3. A run never crosses a multiple of 256 blocks: r <= 256, the symbols are EOB0 .. EOB8 (0x00 .. 0x80).  (256 blocks are what
+ *      one wave codes; decoders accept any partition into runs.  The cost is at most one symbol per 256 blocks.)
+ *   Scan 1 is the DC scan above coded with the two optimised DC tables; pad blocks count.
+ * jpegamd_encode_color_progressive_optimized_batch_async and jpegamd_encode_ycbcr_progressive_optimized_batch_async take the
+ * arguments of their twins above: the same pictures, batching, context sizing, capacity behaviour (size 0,
+ * JPEGAMD_ERR_HUFF_CAPACITY, nothing written past out_capacity, the other pictures unaffected), refusals and statistics -- bits and
+ * stuffed bytes summed over the seven scans, exact_fallbacks counted once.  They do not read the context's Huffman mode and leave it
+ * as it was (the twins keep refusing JPEGAMD_HUFFMAN_OPTIMIZED).  The scans also take the scratch of the restart writer.
+ * The bound.  jpegamd_max_jfif_bytes_progressive_optimized = jpegamd_max_jfif_bytes_progressive + 780.  The scans: a DC difference
+ * is at most 16 + 11 bits; a non-zero AC coefficient 16 + 10; a ZRL 16 bits for sixteen zeros; a run's symbol 16 + 8 bits, paid for
+ * by the zero coefficient Se of the block that starts it.  So a block costs at most 27 + 63 x 26 = 1665 bits over all scans, below
+ * the 1723 the bound above allows it, with the same roundings, stuffing and SOS segments.  The headers: an AC table has at most
+ * 160 run/size symbols, ZRL and EOB0 .. EOB8 = 170 symbols, a DC table 12: the DHT segments are at most 2 x 33 + 6 x 191 = 1212
+ * bytes where the four Annex K segments, which the bound above holds, are 432.  0 for bad arguments.
+ * jpegamd_debug_progressive_counts (tests; synchronous, `counts` a HOST pointer): the symbol counts of the context's last such call,
+ * [pictures of that call][8][256] in the file's table order -- Y DC, chroma DC, then the scans 2 .. 7.  JPEGAMD_ERR_ARG when the
+ * context made no such call. */
+int32_t jpegamd_encode_color_progressive_optimized_batch_async(JpegAmdEncoder *enc, const JpegAmdImage *imgs, int32_t count, int32_t subsampling,
+                                                               void *const *outs_dev, uint64_t out_capacity, uint64_t *const *out_sizes_dev,
+                                                               void *stream);
+int32_t jpegamd_encode_ycbcr_progressive_optimized_batch_async(JpegAmdEncoder *enc, const JpegAmdYCbCrImage *imgs, int32_t count,
+                                                               int32_t subsampling, int32_t sample_range, int32_t sample_format, int32_t matrix,
+                                                               void *const *outs_dev, uint64_t out_capacity, void *const *out_sizes_dev,
+                                                               void *stream);
+uint64_t jpegamd_max_jfif_bytes_progressive_optimized(int32_t width, int32_t height, int32_t subsampling);
+int32_t jpegamd_debug_progressive_counts(JpegAmdEncoder *enc, uint64_t *counts);
 
 /* Block until the last enqueued encode on this context finished; optionally fetch stats
  * (stats may be NULL).  Returns JPEGAMD_ERR_HUFF_CAPACITY if the output did not fit. */

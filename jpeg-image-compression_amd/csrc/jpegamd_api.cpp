@@ -136,6 +136,14 @@ struct JpegAmdEncoder {
         uint8_t *pmeta = nullptr;           // ProgMeta: k_finalize's records, the scans' sizes and sums, the six SOS segments
         uint8_t *pslots = nullptr;          // the scans 2 .. 7 of one group of pictures
         size_t pslots_cap = 0;
+        // ... with end-of-band runs and per-scan optimised tables (jpegamd_encode_*_progressive_optimized_batch_async): allocated by the first such call
+        unsigned long long *pcounts = nullptr;   // [pcap][kProgTables][256] the symbol counts (k_mcu_band_histogram)
+        uint8_t *pres = nullptr;            // [pcap][kProgTables][kHuffResBytes] BITS / HUFFVAL (k_huff_optimal)
+        uint32_t *ptabs = nullptr;          // [pcap][kProgTables][272] the coder's tables (k_prog_tables)
+        uint8_t *phdr = nullptr;            // [kProgScans][pictures of the call][kMcuPrefixSlot] every scan's DHT segment(s) and SOS
+        uint32_t *phdr_len = nullptr;       // [kProgScans][pictures of the call]
+        int pcap = 0;                       // pictures
+        int plast = 0;                      // pictures of the last such call: pcounts[0, plast) are theirs
     } mcu;
 };
 
@@ -370,6 +378,7 @@ extern "C" int32_t jpegamd_encoder_destroy(JpegAmdEncoder *e) {
     hipFree(e->mcu.coef); hipFree(e->mcu.hdr); hipFree(e->mcu.scan_stats);
     hipFree(e->mcu.rst_words); hipFree(e->mcu.rst_pos); hipFree(e->mcu.rst_pic_sums);
     hipFree(e->mcu.pmeta); hipFree(e->mcu.pslots);
+    hipFree(e->mcu.pcounts); hipFree(e->mcu.pres); hipFree(e->mcu.ptabs); hipFree(e->mcu.phdr); hipFree(e->mcu.phdr_len);
     hipFree(e->mcu.hcounts); hipFree(e->mcu.htabs); hipFree(e->mcu.hprefix); hipFree(e->mcu.hprefix_len); hipFree(e->mcu.hres);
     free_seg_arrays(&e->mcu.seg);
     destroy_ring_events(e);
@@ -1601,24 +1610,30 @@ extern "C" uint64_t jpegamd_max_jfif_bytes_interleaved_restart(int32_t width, in
 constexpr int kMcuSosBytes = 14;
 constexpr size_t kMcuScratchBudget = (size_t)4 << 30;       // coefficient planes + segment strings of one group of pictures
 
-// ---- progressive files (DESIGN.md 4.6.12) ----
+// ---- progressive files (DESIGN.md 4.6.12, 4.6.13) ----
+constexpr int kProgNone = 0, kProgStandard = 1, kProgRuns = 2;      // interleaved_batch's `progressive`: one scan / seven scans, Annex K / seven scans with runs and own tables
 // What a progressive call keeps on the device besides the slots: k_finalize's two records (scan 1's; the scans into slots share the
 // other), every scan's size and sums per picture of the group, and the SOS segments of the scans 2 .. 7, 16 bytes apart.
 struct ProgMeta {
     ScanStats scan_stats[2];
     uint64_t size[kProgScans][kMaxBatch];
     unsigned long long sums[kProgScans][kMaxBatch][2];
+    unsigned long long writer_sums[kProgScans][kMaxBatch][kMcuPicSums];     // k_mcu_restart_offsets' (4.6.13 alone)
     uint8_t sos[kProgScans][16];
 };
 // Scan k (from 0) of a progressive file: k = 0 the DC scan, then component (k - 1) % 3 of band (k - 1) / 3.
 // The slots of the scans 2 .. 7 of one picture: each holds SOS, the scan at its bound (every block of the component's plane at the
 // band's worst case, every byte stuffed, the flush byte), EOI, and what k_scans_concat reads behind them in 16-byte steps.
+// own_tables (4.6.13): the scan's DHT segment in front of its SOS; a coefficient of a band then costs at most 16 + 10 bits, a run's
+// symbol 16 + 8, paid for by the zero coefficient se of the block that starts it -- below the 27 of prog_band_bits either way.
+constexpr int kProgDhtMax = 21 + 170;       // an AC table of a scan: 160 run/size symbols, ZRL, EOB0 .. EOB8
+static_assert(kProgDhtMax + kSosBytes <= kMcuPrefixSlot, "a scan's header fits its slot");
 struct ProgSlots { uint64_t off[kProgScans], cap[kProgScans], pic_bytes; };
-static ProgSlots prog_slots(const McuGeometry &g) {
+static ProgSlots prog_slots(const McuGeometry &g, bool own_tables = false) {
     ProgSlots s = {};
     for (int k = 1; k < kProgScans; ++k) {
         const uint64_t nb = (k - 1) % 3 == 0 ? (uint64_t)g.bw * g.bh : (uint64_t)g.mx * g.my;
-        s.cap[k] = kSosBytes + scan_bound(nb, prog_band_bits((k - 1) / 3)) + 2;
+        s.cap[k] = (own_tables ? kProgDhtMax : 0) + kSosBytes + scan_bound(nb, prog_band_bits((k - 1) / 3)) + 2;
         s.off[k] = s.pic_bytes;
         s.pic_bytes += round_up((size_t)s.cap[k] + 64, 256);
     }
@@ -1631,6 +1646,21 @@ extern "C" uint64_t jpegamd_max_jfif_bytes_progressive(int32_t width, int32_t he
     // Seven scans add six SOS segments of kSosBytes, and six more roundings of at most one byte each, which may be stuffed.
     const uint64_t plain = jpegamd_max_jfif_bytes_interleaved(width, height, subsampling);
     return plain ? plain + (uint64_t)(kProgScans - 1) * (kSosBytes + 2) : 0;
+}
+
+extern "C" uint64_t jpegamd_max_jfif_bytes_progressive_optimized(int32_t width, int32_t height, int32_t subsampling) {
+    // The scans: a DC difference is at most 16 + 11 bits with a table of the picture's own; a non-zero AC coefficient 16 + 10 (sizes
+    // 1 .. 10: the reasoning of jpegamd_max_jfif_bytes_gray_scan's optimised mode); a ZRL at most 16 bits for sixteen zero
+    // coefficients; a run's symbol at most 16 + 8 bits (EOB8 and eight more), and only a block whose coefficient se is zero starts one
+    // -- so every coefficient of a band pays for at most 26 bits, and a block for 27 + 63 x 26 = kMaxBlockBitsOptimized over all
+    // scans, below the kMaxBlockBitsColor per block that jpegamd_max_jfif_bytes_progressive holds -- with its seven roundings, its
+    // stuffing, six SOS segments and EOI.
+    // The headers: that bound holds kColorPrefixMax for a prefix with the four Annex K DHT segments (kStdDhtBytes).  Here a DC table
+    // has at most 12 symbols, DHT 21 + 12 = 33 bytes, and an AC table at most 160 run/size symbols, ZRL and EOB0 .. EOB8 = 170, DHT
+    // 21 + 170 = kProgDhtMax: 2 x 33 + 6 x 191 = 1212 bytes against 432 -- 780 more.
+    static_assert(2 * 33 + 6 * kProgDhtMax - kStdDhtBytes == 780 && kMaxBlockBitsOptimized <= kMaxBlockBitsColor, "the bound's derivation");
+    const uint64_t std_tables = jpegamd_max_jfif_bytes_progressive(width, height, subsampling);
+    return std_tables ? std_tables + 780 : 0;
 }
 
 // The path's scratch for `group` pictures of geometry g: allocated on the first call, grown when a call needs more.
@@ -1729,6 +1759,111 @@ static int32_t prog_alloc(JpegAmdEncoder *e, size_t slot_bytes) {
     return grow_scratch(e, &m.pslots, &m.pslots_cap, slot_bytes);
 }
 
+// ... and of a call that makes its own tables (4.6.13), for `pictures` pictures.
+static int32_t prog_tables_alloc(JpegAmdEncoder *e, int pictures) {
+    auto &m = e->mcu;
+    if (pictures <= m.pcap) return JPEGAMD_OK;
+    if (int32_t rc = wait_pending(e)) return rc;
+    hipFree(m.pcounts); hipFree(m.pres); hipFree(m.ptabs); hipFree(m.phdr); hipFree(m.phdr_len);
+    m.pcounts = nullptr; m.pres = nullptr; m.ptabs = nullptr; m.phdr = nullptr; m.phdr_len = nullptr; m.pcap = 0; m.plast = 0;
+    const size_t n = (size_t)pictures;
+    HIP_TRY(hipMalloc((void **)&m.pcounts, n * kProgTables * 256 * sizeof(unsigned long long)));
+    HIP_TRY(hipMalloc((void **)&m.pres, n * kProgTables * kHuffResBytes));
+    HIP_TRY(hipMalloc((void **)&m.ptabs, n * kProgTables * 272 * sizeof(uint32_t)));
+    HIP_TRY(hipMalloc((void **)&m.phdr, n * kProgScans * kMcuPrefixSlot));
+    HIP_TRY(hipMalloc((void **)&m.phdr_len, n * kProgScans * sizeof(uint32_t)));
+    m.pcap = pictures;
+    return JPEGAMD_OK;
+}
+
+// Scan k (from 0) of a progressive file as the one-component (k >= 1) form of the group's three-component arguments.
+static bool prog_scan_args(const McuGeometry &g, const McuSegArgs &sa3, int k, McuSegArgs *out) {
+    const int comp = k ? (k - 1) % 3 : 0, band = k ? (k - 1) / 3 : 0;
+    McuSegArgs sa = sa3;
+    if (k) {                                                         // ONE component: its plane, its block grid, its table class
+        sa.coef = sa3.coef + (comp == 0 ? 0 : (comp == 1 ? sa3.cb_off : sa3.cr_off));
+        sa.bw = sa.mx = comp ? g.mx : g.bw; sa.bh = sa.my = comp ? g.my : g.bh;
+        sa.hs = sa.vs = 1; sa.comps = 1;
+        sa.seg_mcus = mcu_seg_mcus(1, 1, 1);
+        sa.num_segs = (int)(((int64_t)sa.bw * sa.bh + sa.seg_mcus - 1) / sa.seg_mcus);
+        sa.num_segs_pad = (sa.num_segs + kSegGroup - 1) / kSegGroup * kSegGroup;
+        if (sa.num_segs_pad > g.num_segs_pad) return false;         // (a plane has fewer segments than the MCU scan: the arrays hold them)
+        if (comp) sa.huff_y = sa3.huff_c;
+        sa.ss = kProgBandSs[band]; sa.se = kProgBandSe[band];
+    }
+    *out = sa;
+    return true;
+}
+
+// The seven scans of one group's files with end-of-band runs and tables of their own: count every scan's symbols,
+// make all the tables and headers at once (the counts of a scan with runs do not depend on a table, so nothing of a later scan waits
+// for an earlier one), then code scan by scan over the path's one set of segment arrays and let the restart writer -- one interval, a
+// header per picture, no EOI but behind the last scan -- place each: scan 1 in the caller's buffers, the others in the slots.
+static int progressive_runs_scans(JpegAmdEncoder *e, const McuGeometry &g, const ProgSlots &slots, const McuSegArgs &sa3, int first, int n, int count,
+                                  bool last_of_call, void *const *outs_dev, uint64_t out_capacity, uint64_t *const *out_sizes_dev,
+                                  const unsigned long long *pic, hipStream_t stream) {
+    auto &m = e->mcu;
+    ProgMeta *meta = reinterpret_cast<ProgMeta *>(m.pmeta);
+    if (hipMemsetAsync(m.pmeta, 0, offsetof(ProgMeta, sos), stream) != hipSuccess) return (int)hipErrorUnknown;
+    unsigned long long *counts = m.pcounts + (size_t)first * kProgTables * 256;
+    if (hipMemsetAsync(counts, 0, (size_t)n * kProgTables * 256 * sizeof(unsigned long long), stream) != hipSuccess) return (int)hipErrorUnknown;
+    McuSegArgs sa[kProgScans];
+    for (int k = 0; k < kProgScans; ++k) {
+        if (!prog_scan_args(g, sa3, k, &sa[k])) return (int)hipErrorInvalidValue;
+        if (int err = launch_mcu_band_histogram(sa[k], counts, k ? k + 1 : 0, stream)) return err;
+    }
+    HuffOptimalArgs ha;
+    std::memset(&ha, 0, sizeof(ha));
+    ha.freq = counts; ha.jobs = kProgTables * n;
+    ha.res = m.pres + (size_t)first * kProgTables * kHuffResBytes;
+    if (int err = launch_huff_optimal(ha, stream)) return err;
+    ProgTablesArgs pa;
+    std::memset(&pa, 0, sizeof(pa));
+    pa.res = ha.res; pa.tabs = m.ptabs + (size_t)first * kProgTables * 272;
+    pa.hdr_out = m.phdr; pa.hdr_len = m.phdr_len; pa.pictures = count; pa.first = first;
+    pa.hdr = m.hdr; pa.sos_off = m.hdr_for.len - kMcuSosBytes; pa.head_len = pa.sos_off - kStdDhtBytes;
+    pa.sos = &meta->sos[0][0];
+    if (int err = launch_prog_tables(pa, n, stream)) return err;
+
+    for (int k = 0; k < kProgScans; ++k) {
+        McuSegArgs &s = sa[k];
+        s.huff_y = pa.tabs + (k ? (size_t)(k + 1) * 272 : 0); s.huff_c = pa.tabs + 272; s.huff_stride = kProgTables * 272;
+        s.runs = 1;
+        s.sums = &meta->sums[k][0][0];
+        s.status = &meta->scan_stats[k ? 1 : 0].status;
+        if (int err = launch_mcu_band_segments(s, stream)) return err;
+        McuRestartArgs ra;
+        std::memset(&ra, 0, sizeof(ra));
+        ra.seg = s.seg;
+        ra.num_segs_pad = s.num_segs_pad; ra.batch = n;
+        ra.segs_per_interval = s.num_segs; ra.intervals = 1; ra.last_seg = s.num_segs - 1;       // the scan is its one interval
+        ra.pre = m.rst_words; ra.b0 = m.rst_words + m.rst_cap; ra.ff = m.rst_words + 2 * m.rst_cap;
+        ra.pos = m.rst_pos; ra.pic_sums = &meta->writer_sums[k][0][0];
+        for (int i = 0; i < n; ++i) {
+            ra.out[i] = k ? m.pslots + (size_t)i * slots.pic_bytes + slots.off[k] : (uint8_t *)outs_dev[first + i];
+            ra.out_size[i] = &meta->size[k][i];
+        }
+        ra.out_capacity = k ? slots.cap[k] : out_capacity;
+        ra.pic_prefix = m.phdr + ((size_t)k * count + (size_t)first) * kMcuPrefixSlot; ra.pic_prefix_len = m.phdr_len + (size_t)k * count + first;
+        ra.pic_prefix_stride = kMcuPrefixSlot;
+        ra.no_eoi = k == kProgScans - 1 ? 0 : 1;
+        if (int err = launch_mcu_restart_writer(ra, stream)) return err;
+    }
+    ScansConcatArgs ca;
+    std::memset(&ca, 0, sizeof(ca));
+    for (int i = 0; i < n; ++i) { ca.out[i] = (uint8_t *)outs_dev[first + i]; ca.out_size[i] = out_sizes_dev[first + i]; }
+    ca.out_capacity = out_capacity;
+    ca.batch = n; ca.prefix_len = 0; ca.last_of_call = last_of_call ? 1 : 0;
+    ca.size = &meta->size[0][0];
+    ca.slots = m.pslots; ca.pic_bytes = slots.pic_bytes;
+    for (int k = 0; k < kProgScans; ++k) ca.slot_off[k] = slots.off[k];
+    ca.sums = &meta->sums[0][0][0];
+    ca.writer_sums = &meta->writer_sums[0][0][0];
+    ca.pic = pic;
+    ca.scan_stats = meta->scan_stats; ca.stats = e->stats_dev;
+    return launch_scans_concat(ca, stream);
+}
+
 // The seven scans of the progressive files of one group of pictures, [first, first + n) of the call, whose coefficient planes the taps
 // left in m.coef: one after the other on the stream over the path's one set of segment arrays.  `sa`: the group's arguments of the
 // three-component coder (the DC scan's as they are).  Scan 1 goes through k_finalize behind the file's prefix into the caller's
@@ -1740,19 +1875,8 @@ static int progressive_scans(JpegAmdEncoder *e, const McuGeometry &g, const Prog
     ProgMeta *meta = reinterpret_cast<ProgMeta *>(m.pmeta);
     if (hipMemsetAsync(m.pmeta, 0, offsetof(ProgMeta, sos), stream) != hipSuccess) return (int)hipErrorUnknown;
     for (int k = 0; k < kProgScans; ++k) {
-        const int comp = k ? (k - 1) % 3 : 0, band = k ? (k - 1) / 3 : 0;
-        McuSegArgs sa = sa3;
-        if (k) {                                                         // ONE component: its plane, its block grid, its table class
-            sa.coef = sa3.coef + (comp == 0 ? 0 : (comp == 1 ? sa3.cb_off : sa3.cr_off));
-            sa.bw = sa.mx = comp ? g.mx : g.bw; sa.bh = sa.my = comp ? g.my : g.bh;
-            sa.hs = sa.vs = 1; sa.comps = 1;
-            sa.seg_mcus = mcu_seg_mcus(1, 1, 1);
-            sa.num_segs = (int)(((int64_t)sa.bw * sa.bh + sa.seg_mcus - 1) / sa.seg_mcus);
-            sa.num_segs_pad = (sa.num_segs + kSegGroup - 1) / kSegGroup * kSegGroup;
-            if (sa.num_segs_pad > g.num_segs_pad) return (int)hipErrorInvalidValue;     // (a plane has fewer segments than the MCU scan: the arrays hold them)
-            if (comp) sa.huff_y = sa3.huff_c;
-            sa.ss = kProgBandSs[band]; sa.se = kProgBandSe[band];
-        }
+        McuSegArgs sa;
+        if (!prog_scan_args(g, sa3, k, &sa)) return (int)hipErrorInvalidValue;
         sa.sums = &meta->sums[k][0][0];
         sa.status = &meta->scan_stats[k ? 1 : 0].status;
         if (int err = launch_mcu_band_segments(sa, stream)) return err;
@@ -1792,10 +1916,13 @@ static int progressive_scans(JpegAmdEncoder *e, const McuGeometry &g, const Prog
 // tapped and coded, no chroma launch, two tables; always through the restart writer (the caller sends the plain Annex K file elsewhere).
 static int32_t interleaved_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, const PlaneSet &px, int32_t count, int32_t subsampling, int32_t restart,
                                  void *const *outs_dev, uint64_t out_capacity, uint64_t *const *out_sizes_dev, void *stream_,
-                                 const YccSource *ycc_in = nullptr, bool progressive = false) {
+                                 const YccSource *ycc_in = nullptr, int progressive = kProgNone) {
     // `progressive`: the same taps, plane pass, matrix pass and grouping; behind a group's taps its seven scans
     // (progressive_scans) in place of k_mcu_segments, k_finalize and k_mcu_totals.  Colour, the Annex K tables, no restart intervals.
-    if (progressive && (restart || subsampling == kSubNone || e->huffman != JPEGAMD_HUFFMAN_STANDARD)) return JPEGAMD_ERR_ARG;
+    // kProgRuns: histograms, tables and the restart writer as well (progressive_runs_scans); the context's Huffman
+    // mode is neither read nor changed.
+    const bool runs = progressive == kProgRuns;
+    if (progressive && (restart || subsampling == kSubNone || (!runs && e->huffman != JPEGAMD_HUFFMAN_STANDARD))) return JPEGAMD_ERR_ARG;
     const bool mx = ycc_in && ycc_in->matrix == JPEGAMD_MATRIX_BT709;
     const YccSource *const ycc = mx ? nullptr : ycc_in;               // what the launches read: the caller's planes, or the scratch
     const bool planar = g0.channel_order == kOrderPlanar;
@@ -1803,7 +1930,7 @@ static int32_t interleaved_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, cons
     // A picture's own tables: k_mcu_histogram and k_huff_optimal in front of the coder, and the restart writer for
     // every interval -- it reads a prefix and its length per picture; without restart intervals the scan is its one interval.
     const bool gray = g.comps == 1;
-    const bool optimized = e->huffman == JPEGAMD_HUFFMAN_OPTIMIZED, writer = restart || optimized;
+    const bool optimized = !runs && e->huffman == JPEGAMD_HUFFMAN_OPTIMIZED, writer = restart || optimized || runs;
     if (gray && !writer) return JPEGAMD_ERR_ARG;                    // (that file is gray_batch's: the entry sends it there)
     // segments as short as one MCU: a picture whose scratch alone is beyond the group budget is refused, nothing allocated or launched
     if ((restart || gray) && mcu_scratch_per_pic(g, true) > kMcuScratchBudget) return JPEGAMD_ERR_TOO_LARGE;
@@ -1823,7 +1950,7 @@ static int32_t interleaved_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, cons
     if (rc) return rc;
     if (iy.blocks_w != g.bw || iy.blocks_h != g.bh || (!gray && (ic.blocks_w != g.mx || ic.blocks_h != g.my))) return JPEGAMD_ERR_ARG;
 
-    const ProgSlots slots = progressive ? prog_slots(g) : ProgSlots{};
+    const ProgSlots slots = progressive ? prog_slots(g, runs) : ProgSlots{};
     const size_t per_pic = (size_t)mcu_scratch_per_pic(g, writer) + (size_t)slots.pic_bytes;
     const int group = (int)std::max<size_t>(1, std::min<size_t>((size_t)count, kMcuScratchBudget / per_pic));
     rc = color_alloc_consts(e);
@@ -1836,12 +1963,14 @@ static int32_t interleaved_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, cons
     if (rc) return rc;
     rc = gray ? JPEGAMD_OK : prepare_color_constants(e, &g0, subsampling);
     if (rc) return rc;
-    rc = prepare_mcu_prefix(e, &g0, subsampling, restart, progressive);
+    rc = prepare_mcu_prefix(e, &g0, subsampling, restart, progressive != kProgNone);
     if (rc) return rc;
     auto &c = e->color;
     auto &m = e->mcu;
     if (progressive) {
         rc = prog_alloc(e, (size_t)group * (size_t)slots.pic_bytes);
+        if (rc) return rc;
+        rc = runs ? prog_tables_alloc(e, count) : JPEGAMD_OK;
         if (rc) return rc;
     }
     unsigned long long *pic = reinterpret_cast<unsigned long long *>(c.bmeta + kBatchMetaStats);
@@ -1900,8 +2029,10 @@ static int32_t interleaved_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, cons
         sa.restart = restart; sa.segs_per_interval = restart ? g.segs_per_interval : 0;
         sa.comps = g.comps;
         if (progressive) {
-            if (progressive_scans(e, g, slots, sa, iy, first, n, first + n == count, outs_dev, out_capacity, out_sizes_dev,
-                                  pic + (size_t)first * kPicStatWords, stream))
+            if (runs ? progressive_runs_scans(e, g, slots, sa, first, n, count, first + n == count, outs_dev, out_capacity, out_sizes_dev,
+                                              pic + (size_t)first * kPicStatWords, stream)
+                     : progressive_scans(e, g, slots, sa, iy, first, n, first + n == count, outs_dev, out_capacity, out_sizes_dev,
+                                         pic + (size_t)first * kPicStatWords, stream))
                 return JPEGAMD_ERR_HIP;
             continue;
         }
@@ -1960,6 +2091,7 @@ static int32_t interleaved_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, cons
         if (launch_mcu_totals(ta, n, stream)) return JPEGAMD_ERR_HIP;
     }
     if (optimized) m.hlast = count;
+    if (runs) m.plast = count;
     if (cev) HIP_TRY(hipEventRecord(cev[21], stream));
     return enqueued(e, stream, count * g.num_segs_pad, cev != nullptr, true);
 }
@@ -2026,7 +2158,7 @@ static bool restart_valid(int32_t restart) { return restart >= 0 && restart <= 6
 // `count` packed pictures in one scan: the argument checks (`px4`: the entry takes RGBA / BGRA as well), then the interleaved batch.
 static int32_t interleaved_pixels(JpegAmdEncoder *e, const JpegAmdImage *imgs, int32_t count, int32_t subsampling, int32_t restart_interval, bool px4,
                                   void *const *outs_dev, uint64_t out_capacity, uint64_t *const *out_sizes_dev, void *stream_,
-                                  bool progressive = false) {
+                                  int progressive = kProgNone) {
     // the arguments first: nothing of the context is read before they are known to be good
     if (!restart_valid(restart_interval)) return JPEGAMD_ERR_ARG;
     if (!e || !imgs || !outs_dev || !out_sizes_dev || count < 1 || count > kMaxBatch) return JPEGAMD_ERR_ARG;
@@ -2047,7 +2179,25 @@ static int32_t interleaved_pixels(JpegAmdEncoder *e, const JpegAmdImage *imgs, i
 extern "C" int32_t jpegamd_encode_color_progressive_batch_async(JpegAmdEncoder *e, const JpegAmdImage *imgs, int32_t count, int32_t subsampling,
                                                                 void *const *outs_dev, uint64_t out_capacity, uint64_t *const *out_sizes_dev,
                                                                 void *stream_) {
-    return interleaved_pixels(e, imgs, count, subsampling, 0, true, outs_dev, out_capacity, out_sizes_dev, stream_, true);
+    return interleaved_pixels(e, imgs, count, subsampling, 0, true, outs_dev, out_capacity, out_sizes_dev, stream_, kProgStandard);
+}
+
+// ... with end-of-band runs and per-scan optimised tables: the same checks, pictures and batching.  The context's
+// Huffman mode is not read.
+extern "C" int32_t jpegamd_encode_color_progressive_optimized_batch_async(JpegAmdEncoder *e, const JpegAmdImage *imgs, int32_t count, int32_t subsampling,
+                                                                          void *const *outs_dev, uint64_t out_capacity, uint64_t *const *out_sizes_dev,
+                                                                          void *stream_) {
+    return interleaved_pixels(e, imgs, count, subsampling, 0, true, outs_dev, out_capacity, out_sizes_dev, stream_, kProgRuns);
+}
+
+// Tests: the symbol counts of the context's last call with per-scan tables, [pictures][8][256] in the file's table order: Y DC,
+// chroma DC, then the AC tables of the scans 2 .. 7.  JPEGAMD_ERR_ARG when the context made no such call.  Synchronous.
+extern "C" int32_t jpegamd_debug_progressive_counts(JpegAmdEncoder *e, uint64_t *counts) {
+    if (!e || !counts || e->mcu.plast < 1) return JPEGAMD_ERR_ARG;
+    if (int32_t rc = wait_pending(e)) return rc;
+    static_assert(sizeof(uint64_t) == sizeof(unsigned long long), "the counts are copied as they lie");
+    HIP_TRY(hipMemcpy(counts, e->mcu.pcounts, (size_t)e->mcu.plast * kProgTables * 256 * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    return JPEGAMD_OK;
 }
 
 extern "C" int32_t jpegamd_encode_color_interleaved_restart_batch_async(JpegAmdEncoder *e, const JpegAmdImage *imgs, int32_t count, int32_t subsampling,
@@ -2153,7 +2303,20 @@ extern "C" int32_t jpegamd_encode_ycbcr_progressive_batch_async(JpegAmdEncoder *
     uint64_t *sizes[kMaxBatch];
     if (int32_t rc = ycbcr_args(e, imgs, count, subsampling, sample_range, sample_format, matrix, outs_dev, out_sizes_dev, true, &g0, &ps, &ycc, sizes))
         return rc;
-    return interleaved_batch(e, g0, ps, count, subsampling, 0, outs_dev, out_capacity, sizes, stream_, &ycc, true);
+    return interleaved_batch(e, g0, ps, count, subsampling, 0, outs_dev, out_capacity, sizes, stream_, &ycc, kProgStandard);
+}
+
+extern "C" int32_t jpegamd_encode_ycbcr_progressive_optimized_batch_async(JpegAmdEncoder *e, const JpegAmdYCbCrImage *imgs, int32_t count, int32_t subsampling,
+                                                                          int32_t sample_range, int32_t sample_format, int32_t matrix,
+                                                                          void *const *outs_dev, uint64_t out_capacity, void *const *out_sizes_dev,
+                                                                          void *stream_) {
+    JpegAmdImage g0;
+    PlaneSet ps;
+    YccSource ycc;
+    uint64_t *sizes[kMaxBatch];
+    if (int32_t rc = ycbcr_args(e, imgs, count, subsampling, sample_range, sample_format, matrix, outs_dev, out_sizes_dev, true, &g0, &ps, &ycc, sizes))
+        return rc;
+    return interleaved_batch(e, g0, ps, count, subsampling, 0, outs_dev, out_capacity, sizes, stream_, &ycc, kProgRuns);
 }
 
 // Host-only (tests): whether the plain build has the k_tile_encode instantiation (taps, layout, chroma tables, expand): 1 or 0.  No

@@ -418,6 +418,7 @@ struct McuSegArgs {
     // launch_mcu_band_segments alone (a scan of a progressive file; k_mcu_segments reads none of these):
     int32_t ss, se;                     // the band, uniform over the launch: 0, 0 the DC scan (comps = 3), 1 <= ss <= se <= 63 an AC scan (comps = 1)
     unsigned long long *sums;           // [batch][2]: every segment's bits and symbols are ADDED to its picture's pair (the caller zeroed them)
+    int32_t runs;                       // an AC scan with end-of-band runs and the pictures' own tables (huff_stride > 0); the DC scan: its own tables
 };
 int launch_mcu_segments(const McuSegArgs &a, void *stream);
 
@@ -448,8 +449,29 @@ struct ScansConcatArgs {
     const unsigned long long *pic;      // k_picture_stats' words of THESE pictures
     const ScanStats *scan_stats;        // [2] k_finalize's records: scan 1's, and the one the scans into slots share
     ScanStats *stats;                   // the context's record, whose sums the caller zeroed
+    // the scans went through the restart writer: `size` is k_mcu_restart_offsets' -- every scan with ITS header, the
+    // last with EOI --, and the stuffed bytes are word 2 of its sums, [kProgScans][kMaxBatch][kMcuPicSums]; null: k_finalize's scans
+    const unsigned long long *writer_sums;
 };
 int launch_scans_concat(const ScansConcatArgs &a, void *stream);
+// Progressive files with end-of-band runs and per-scan optimised tables: kProgTables tables per picture in the
+// file's order -- Y DC, chroma DC (scan 1), then the AC tables of the scans 2 .. 7.  launch_mcu_band_histogram counts the symbols of
+// one scan (the coder's walks, no table read) into counts [pictures][kProgTables][256], which the caller zeroed; k_huff_optimal makes
+// BITS / HUFFVAL of all of them in one launch (its `freq` form: the counts ARE kProgTables x pictures jobs of 256 symbols);
+// k_prog_tables makes the coder's tables and every scan's header -- DHT segment(s) + SOS, scan 1's behind the file's head -- of them.
+constexpr int kProgTables = 8;
+int launch_mcu_band_histogram(const McuSegArgs &a, unsigned long long *counts, int table, void *stream);
+struct ProgTablesArgs {
+    const uint8_t *res;                 // [launch pictures][kProgTables][kHuffResBytes] k_huff_optimal's
+    uint32_t *tabs;                     // [launch pictures][kProgTables][272]
+    uint8_t *hdr_out;                   // scan k (from 0) of picture p of the CALL at hdr_out + (k pictures + p) kMcuPrefixSlot
+    uint32_t *hdr_len;                  // [kProgScans][pictures]
+    int32_t pictures, first;            // pictures of the call; the launch's first
+    const uint8_t *hdr;                 // the standard progressive prefix: head, the Annex K DHTs, the DC scan's SOS
+    int32_t head_len, sos_off;
+    const uint8_t *sos;                 // the SOS of scan k >= 1 (from 0) at sos + 16 k
+};
+int launch_prog_tables(const ProgTablesArgs &a, int batch, void *stream);
 // The writer of a file with restart intervals: two launches in place of k_finalize (which knows neither the 1-bit padding of an
 // interval nor markers).  k_mcu_restart_offsets, one workgroup per picture: every segment's bit offset inside its interval (pre is its
 // scratch: the bit counts' running sum over the picture), the 0xFF bytes it owns at that phase, and -- an exclusive sum over the
@@ -475,6 +497,7 @@ struct McuRestartArgs {
     const uint8_t *pic_prefix;
     const uint32_t *pic_prefix_len;
     uint32_t pic_prefix_stride;
+    int32_t no_eoi;                     // the scan's last segment flushes its byte with 0-bits and writes no EOI: another scan follows
 };
 int launch_mcu_restart_writer(const McuRestartArgs &a, void *stream);
 // k_mcu_totals, behind k_finalize: per picture of the launch the sums of its segments, its stuffed bytes (from its size) and its

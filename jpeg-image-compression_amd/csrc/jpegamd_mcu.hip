@@ -26,6 +26,9 @@
 // Progressive files: the segment coder is mcu_code_segments, which k_mcu_segments instantiates with the walk of a
 // whole block and k_mcu_band_segments with the DC-only walk (the three-component DC scan) or the walk of a band ss .. se (an AC scan of
 // one component); k_scans_concat joins the seven scans k_finalize wrote.
+// ... with end-of-band runs and a table per scan: the band walk without end symbols plus mcu_band_runs
+// (kWalkBandRuns), k_mcu_band_histogram counting what that walk codes, k_huff_optimal over all eight tables of a picture at once,
+// k_prog_tables making the coder's tables and every scan's DHT + SOS, and the restart writer placing each scan behind its header.
 #include <algorithm>
 
 #include <hip/hip_ext.h>
@@ -82,8 +85,8 @@ __device__ __forceinline__ void mcu_walk_block(const uint4 *__restrict__ p, bool
 
 // ---- the walks of a progressive file's scans (spectral selection, Ah = Al = 0) --------------------------------
 // The DC scan: a block is its DC difference alone -- a pad block's too: its DC is the nearest real block's.
-template <class Emit>
-__device__ __forceinline__ void mcu_walk_dc(const uint4 *__restrict__ p, int pred, const uint32_t *tab, Emit &&emit) {
+template <class Tab, class Emit>
+__device__ __forceinline__ void mcu_walk_dc(const uint4 *__restrict__ p, int pred, const Tab &tab, Emit &&emit) {
     const int diff = (int)*reinterpret_cast<const int16_t *>(p) - pred;
     const uint32_t nb = mcu_size(diff), t = tab[256u + (nb & 15u)];
     emit(((t & 0xFFFFu) << nb) | mcu_amp(diff, nb), (t >> 16) + nb);
@@ -99,9 +102,11 @@ __device__ __forceinline__ uint32_t mcu_band_mask(int j0, int lo, int hi) {
 // it is not.  Only the 16-byte groups that hold ss .. se are read (1 .. 5: p[0] alone); what a group holds outside the band is
 // masked to zero, and the run starts at minus the coefficients masked in front of ss.  A band's string is never longer than the
 // whole block's (the same symbols at most, one per coefficient, a ZRL per sixteen zeros, an EOB for a zero coefficient se).
-template <class Emit>
-__device__ __forceinline__ void mcu_walk_band(const uint4 *__restrict__ p, int ss, int se, const uint32_t *tab, Emit &&emit) {
-    const uint32_t eob = tab[0x00], zrl = tab[0xF0];
+// kRuns: nothing is emitted for the trailing zeros -- the caller codes end-of-band runs over the blocks of a
+// segment (mcu_band_runs).  Returns whether coefficient se is zero.  Tab: a coder table, or McuSymbolTab to count symbols.
+template <bool kRuns = false, class Tab, class Emit>
+__device__ __forceinline__ bool mcu_walk_band(const uint4 *__restrict__ p, int ss, int se, const Tab &tab, Emit &&emit) {
+    const uint32_t eob = kRuns ? 0u : tab[0x00], zrl = tab[0xF0];
     const int q1 = se >> 3;
     uint32_t run = 0u - (uint32_t)(ss & 7);
     uint4 v = make_uint4(0u, 0u, 0u, 0u);
@@ -128,10 +133,45 @@ __device__ __forceinline__ void mcu_walk_band(const uint4 *__restrict__ p, int s
     // coefficient se itself, of the last group's words (`run` also counts the zeros masked behind se)
     const int i = se & 7;
     const uint32_t w = (i & 4) ? ((i & 2) ? v.w : v.z) : ((i & 2) ? v.y : v.x);
-    if ((((i & 1) ? w >> 16 : w) & 0xFFFFu) == 0u) emit(eob & 0xFFFFu, eob >> 16);
+    const bool end_zero = (((i & 1) ? w >> 16 : w) & 0xFFFFu) == 0u;
+    if (!kRuns && end_zero) emit(eob & 0xFFFFu, eob >> 16);
+    return end_zero;
 }
 
-constexpr int kWalkBlock = 0, kWalkDc = 1, kWalkBand = 2;   // what a coder launch codes of a block: all of it, its DC, a band of its AC
+// what a coder launch codes of a block: all of it, its DC, a band of its AC, a band of its AC with end-of-band runs
+constexpr int kWalkBlock = 0, kWalkDc = 1, kWalkBand = 2, kWalkBandRuns = 3;
+
+// A table that gives symbol i the 1-bit code word i: a walk over it emits (symbol << size | amplitude, 1 + size) -- the symbol
+// itself is what the counting kernel takes from it, so the walks that count are the walks that code.
+struct McuSymbolTab { __device__ __forceinline__ uint32_t operator[](uint32_t i) const { return (1u << 16) | i; } };
+
+// End-of-band runs of one segment.  The lane holds the segment's blocks lane + 64 r; z[r]: the
+// band of that block is all zero, e[r]: its coefficient se is zero (both false behind the segment's last block).  Block k starts a
+// run iff e[k] and not (z[k] and k > 0 and e[k - 1]); the run is 1 + the blocks behind it with z, up to the segment's end: a run
+// never leaves its segment, so nothing is read from a neighbour and nothing is pending at the end.  run[r]: 1 .. 256, 0 for none.
+__device__ __forceinline__ void mcu_band_runs(int lane, const bool (&z)[4], const bool (&e)[4], uint32_t (&run)[4]) {
+    unsigned long long zm[4], em[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) { zm[r] = __ballot(z[r]); em[r] = __ballot(e[r]); }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const bool e_prev = lane > 0 ? ((em[r] >> (lane - 1)) & 1ull) != 0ull : (r > 0 && (em[r > 0 ? r - 1 : 0] >> 63) != 0ull);
+        run[r] = 0u;
+        if (!e[r] || (z[r] && e_prev)) continue;                   // (block 0 of the segment has no e_prev: it starts a run whenever e)
+        uint32_t n = 1u;
+        bool go = true;
+#pragma unroll
+        for (int w = r; w < 4; ++w) {                              // the set bits of z from block 64 r + lane + 1 on
+            const int bit = w == r ? lane + 1 : 0;
+            if (!go || bit > 63) continue;
+            const unsigned long long inv = ~(zm[w] >> bit);
+            const uint32_t avail = 64u - (uint32_t)bit, c = min(inv ? (uint32_t)__builtin_ctzll(inv) : 64u, avail);
+            n += c;
+            go = c == avail;
+        }
+        run[r] = n;
+    }
+}
 
 struct McuBlock { const uint4 *p; int pred; bool pad, chroma; };
 
@@ -188,12 +228,18 @@ __device__ __forceinline__ McuRange mcu_range(const McuSegArgs &a, int sl) {
     return r;
 }
 
-template <int kWalk, class Emit>
-__device__ __forceinline__ void mcu_walk(const McuSegArgs &a, const McuBlock &b, int pred, const uint32_t *tab, Emit &&emit) {
+// Returns whether coefficient se is zero (kWalkBandRuns alone: false for the others).
+template <int kWalk, class Tab, class Emit>
+__device__ __forceinline__ bool mcu_walk(const McuSegArgs &a, const McuBlock &b, int pred, const Tab &tab, Emit &&emit) {
     if constexpr (kWalk == kWalkDc) mcu_walk_dc(b.p, pred, tab, emit);
     else if constexpr (kWalk == kWalkBand) mcu_walk_band(b.p, a.ss, a.se, tab, emit);
+    else if constexpr (kWalk == kWalkBandRuns) return mcu_walk_band<true>(b.p, a.ss, a.se, tab, emit);
     else mcu_walk_block(b.p, b.pad, pred, tab, emit);
+    return false;
 }
+
+// The symbol of a run of `run` blocks: EOBn, n = floor(log2 run), followed by the n low bits of run - 2^n.
+__device__ __forceinline__ uint32_t mcu_run_log2(uint32_t run) { return 31u - (uint32_t)__clz((int)run); }
 
 // The segment coder, shared by k_mcu_segments (kWalkBlock) and k_mcu_band_segments (a progressive file's scans): s_tab and s_win are
 // the kernel's LDS.  A band launch also adds every segment's bits and symbols to its picture's pair in a.sums (the scans of a
@@ -226,18 +272,28 @@ __device__ __forceinline__ void mcu_code_segments(const McuSegArgs &a, uint32_t 
     // ---- pass 1: bit lengths, then the blocks' places ----
     uint32_t len[4], off[4], nsym = 0, carry = 0;
     int pred[4];
+    [[maybe_unused]] bool z[4], e[4];
+    [[maybe_unused]] uint32_t run[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         const int k = r * 64 + lane;
         len[r] = 0u; pred[r] = 0;
+        if constexpr (kWalk == kWalkBandRuns) z[r] = e[r] = false;
         if (k < nblk) {
             const int mi = k / bpm;
             const McuBlock b = mcu_block<kComps>(a, base, m0 + mi, k - mi * bpm, mstart);
             pred[r] = b.pred;
             uint32_t n = 0;
-            mcu_walk<kWalk>(a, b, b.pred, s_tab[kTabs > 1 && b.chroma ? 1 : 0], [&](uint32_t, uint32_t c) { n += c; ++nsym; });
+            const bool end_zero = mcu_walk<kWalk>(a, b, b.pred, (const uint32_t *)s_tab[kTabs > 1 && b.chroma ? 1 : 0], [&](uint32_t, uint32_t c) { n += c; ++nsym; });
             len[r] = n;
+            if constexpr (kWalk == kWalkBandRuns) { z[r] = n == 0u; e[r] = end_zero; }     // (every code word has a bit: no symbols, no bits)
         }
+    }
+    if constexpr (kWalk == kWalkBandRuns) {                        // the runs the lane's blocks start: their symbols behind the blocks' own
+        mcu_band_runs(lane, z, e, run);
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+            if (run[r]) { const uint32_t n = mcu_run_log2(run[r]); len[r] += (s_tab[0][n << 4] >> 16) + n; ++nsym; }
     }
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -265,7 +321,7 @@ __device__ __forceinline__ void mcu_code_segments(const McuSegArgs &a, uint32_t 
                 const int mi = k / bpm;
                 const McuBlock b = mcu_block<kComps>(a, base, m0 + mi, k - mi * bpm, mstart);
                 uint32_t pos = off[r];
-                mcu_walk<kWalk>(a, b, pred[r], s_tab[kTabs > 1 && b.chroma ? 1 : 0], [&](uint32_t sym, uint32_t n) {
+                const auto put = [&](uint32_t sym, uint32_t n) {
                     if (n == 0u) return;
                     const unsigned long long s64 = ((unsigned long long)sym << (64u - n)) >> (pos & 31u);   // left-aligned at the bit's place in a word pair
                     const uint32_t j = (pos >> 5) - wbase;          // (wraps for a word in front of the window)
@@ -273,7 +329,13 @@ __device__ __forceinline__ void mcu_code_segments(const McuSegArgs &a, uint32_t 
                     if (j <= (uint32_t)kMcuWin && hi) atomicOr(&win[j], hi);
                     if (j + 1u <= (uint32_t)kMcuWin && lo) atomicOr(&win[j + 1u], lo);
                     pos += n;
-                });
+                };
+                mcu_walk<kWalk>(a, b, pred[r], (const uint32_t *)s_tab[kTabs > 1 && b.chroma ? 1 : 0], put);
+                if constexpr (kWalk == kWalkBandRuns)
+                    if (run[r]) {
+                        const uint32_t n = mcu_run_log2(run[r]), t = s_tab[0][n << 4];
+                        put(((t & 0xFFFFu) << n) | (run[r] - (1u << n)), (t >> 16) + n);
+                    }
             }
         }
         __builtin_amdgcn_wave_barrier();
@@ -336,11 +398,13 @@ __global__ __launch_bounds__(64 * kWavesM) void k_mcu_segments(const McuSegArgs 
 
 // A scan of a progressive file: k_mcu_segments' segments, window and census over another walk of a block --
 // <3, kWalkDc> the DC scan of the three components in MCU order, <1, kWalkBand> the band ss .. se of ONE component's plane.
+// <1, kWalkBandRuns> the same band with end-of-band runs inside the segment and the picture's own table.
 // No restart intervals.  A band's string is never longer than the whole block's (mcu_walk_band), a DC difference is at most
-// 11 + 11 bits: seg_cap_words(kSegTiles) holds every segment, as it holds k_mcu_segments'.
+// 11 + 11 bits (16 + 11 with a table of the picture's own, a band's coefficient then 16 + 10 and a run's symbol 16 + 8 for a zero
+// coefficient se: kMaxBlockBitsOptimized): seg_cap_words(kSegTiles) holds every segment, as it holds k_mcu_segments'.
 template <int kComps, int kWalk>
 __global__ __launch_bounds__(64 * kWavesM) void k_mcu_band_segments(const McuSegArgs a) {
-    static_assert((kComps == 3 && kWalk == kWalkDc) || (kComps == 1 && kWalk == kWalkBand), "the scans of DESIGN.md 4.6.12");
+    static_assert((kComps == 3 && kWalk == kWalkDc) || (kComps == 1 && (kWalk == kWalkBand || kWalk == kWalkBandRuns)), "the scans of DESIGN.md 4.6.12 and 4.6.13");
     static_assert(22 <= kMaxBlockBitsColor && 63 * 27 <= kMaxBlockBitsColor, "a block of either walk fits the reservation of a whole block");
     __shared__ uint32_t s_tab[kComps == 1 ? 1 : 2][272];
     __shared__ uint32_t s_win[kWavesM][kMcuWin + 2];
@@ -379,10 +443,129 @@ int launch_mcu_band_segments(const McuSegArgs &a, void *stream) {
     const int n = a.batch * a.num_segs_pad;
     if (n <= 0) return 0;
     const bool dc = a.comps == 3 && a.ss == 0 && a.se == 0, band = a.comps == 1 && a.ss >= 1 && a.ss <= a.se && a.se <= 63;
-    if (!a.sums || a.restart != 0 || a.huff_stride != 0 || !(dc || band) || !mcu_seg_args_ok(a)) return (int)hipErrorInvalidValue;
+    // (runs: the scans of DESIGN.md 4.6.13 -- every picture codes with its own tables, huff_stride words apart)
+    if (!a.sums || a.restart != 0 || (a.huff_stride != 0) != (a.runs != 0) || !(dc || band) || !mcu_seg_args_ok(a)) return (int)hipErrorInvalidValue;
     const dim3 grid((unsigned)((n + kWavesM - 1) / kWavesM)), block(64 * kWavesM);
-    const auto kernel = dc ? k_mcu_band_segments<3, kWalkDc> : k_mcu_band_segments<1, kWalkBand>;
+    const auto kernel = dc ? k_mcu_band_segments<3, kWalkDc> : (a.runs ? k_mcu_band_segments<1, kWalkBandRuns> : k_mcu_band_segments<1, kWalkBand>);
     hipLaunchKernelGGL(kernel, grid, block, 0, (hipStream_t)stream, a);
+    return (int)hipGetLastError();
+}
+
+// The symbols of one scan of a file of DESIGN.md 4.6.13 counted, not coded: the coder's grid, segments and walks over McuSymbolTab,
+// one wave per segment, the workgroup's counts in LDS, then added to its picture's tables in counts [pictures][kProgTables][256]:
+// <3, kWalkDc> the DC sizes of Y into table 0 and of Cb and Cr into table 1, <1, kWalkBandRuns> the band's symbols into `table`.
+template <int kComps, int kWalk>
+__global__ __launch_bounds__(64 * kWavesM) void k_mcu_band_histogram(const McuSegArgs a, unsigned long long *__restrict__ counts, int table) {
+    static_assert((kComps == 3 && kWalk == kWalkDc) || (kComps == 1 && kWalk == kWalkBandRuns), "the scans of DESIGN.md 4.6.13");
+    constexpr int kTabs = kComps == 1 ? 1 : 2;
+    __shared__ uint32_t s_cnt[kTabs][256];                         // (a workgroup walks at most 4 x 256 blocks of 64 symbols: 32 bits hold it)
+    const int lane = lane_id(), wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    for (int i = (int)threadIdx.x; i < kTabs * 256; i += 64 * kWavesM) (&s_cnt[0][0])[i] = 0u;
+    __syncthreads();
+    const int seg = (int)blockIdx.x * kWavesM + wave;
+    const int image = ((int)blockIdx.x * kWavesM) / a.num_segs_pad; // the workgroup's picture
+    if (seg < a.batch * a.num_segs_pad) {
+        const McuRange rg = mcu_range<false>(a, seg - image * a.num_segs_pad);
+        const int16_t *base = a.coef + (size_t)image * a.pic_stride;
+        const int bpm = kComps == 1 ? 1 : a.hs * a.vs + 2, nblk = rg.nmcu * bpm;      // 0 (EMPTY: nothing counted) .. 256
+        [[maybe_unused]] bool z[4], e[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int k = r * 64 + lane;
+            if constexpr (kWalk == kWalkBandRuns) z[r] = e[r] = false;
+            if (k < nblk) {
+                const int mi = k / bpm;
+                const McuBlock b = mcu_block<kComps>(a, base, rg.m0 + mi, k - mi * bpm, rg.mstart);
+                uint32_t *const cnt = s_cnt[kTabs > 1 && b.chroma ? 1 : 0];
+                uint32_t n = 0;
+                const bool end_zero = mcu_walk<kWalk>(a, b, b.pred, McuSymbolTab(), [&](uint32_t v, uint32_t c) {
+                    atomicAdd(&cnt[(v >> (c - 1u)) & 0xFFu], 1u);  // (a DC size s arrives as 256 + s)
+                    ++n;
+                });
+                if constexpr (kWalk == kWalkBandRuns) { z[r] = n == 0u; e[r] = end_zero; }
+            }
+        }
+        if constexpr (kWalk == kWalkBandRuns) {
+            uint32_t run[4];
+            mcu_band_runs(lane, z, e, run);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) if (run[r]) atomicAdd(&s_cnt[0][mcu_run_log2(run[r]) << 4], 1u);
+        }
+    }
+    __syncthreads();
+    if (image < a.batch)
+        for (int i = (int)threadIdx.x; i < kTabs * 256; i += 64 * kWavesM) {
+            const uint32_t v = (&s_cnt[0][0])[i];
+            if (v) atomicAdd(&counts[((size_t)image * kProgTables + (size_t)(table + (i >> 8))) * 256 + (size_t)(i & 255)], (unsigned long long)v);
+        }
+}
+
+int launch_mcu_band_histogram(const McuSegArgs &a, unsigned long long *counts, int table, void *stream) {
+    const int n = a.batch * a.num_segs_pad;
+    if (n <= 0) return 0;
+    const bool dc = a.comps == 3 && a.ss == 0 && a.se == 0 && table == 0, band = a.comps == 1 && a.ss >= 1 && a.ss <= a.se && a.se <= 63 && table >= 2 && table < kProgTables;
+    if (!counts || a.restart != 0 || !(dc || band) || !mcu_seg_args_ok(a)) return (int)hipErrorInvalidValue;
+    const dim3 grid((unsigned)((n + kWavesM - 1) / kWavesM)), block(64 * kWavesM);
+    const auto kernel = dc ? k_mcu_band_histogram<3, kWalkDc> : k_mcu_band_histogram<1, kWalkBandRuns>;
+    hipLaunchKernelGGL(kernel, grid, block, 0, (hipStream_t)stream, a, counts, table);
+    return (int)hipGetLastError();
+}
+
+// Workgroup q: picture q of the launch; wave t: its table t in the file's order (Y DC, chroma DC, then the AC tables of the scans
+// 2 .. 7), as k_huff_optimal left it in res (BITS, the number of HUFFVAL bytes, HUFFVAL).  The wave writes the coder's table --
+// [272] words at tabs + (q kProgTables + t) 272: an AC table's code words by run/size at 0, a DC table's by size at 256, unused
+// symbols 0 -- and the table's DHT segment into its scan's header slot: scan 1's is the file's head (hdr[0, head_len)), the two DC
+// tables and the DC scan's SOS (hdr[sos_off, sos_off + kMcuSosLen)); scan k's (from 0) its table and sos + 16 k.
+constexpr int kMcuSosLen = 14;
+__global__ __launch_bounds__(64 * kProgTables) void k_prog_tables(const ProgTablesArgs a) {
+    __shared__ uint32_t s_nvals[kProgTables];
+    const int lane = lane_id(), t = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), q = (int)blockIdx.x;
+    const uint8_t *res = a.res + ((size_t)q * kProgTables + (size_t)t) * kHuffResBytes;
+    const uint32_t nvals = min(*reinterpret_cast<const uint32_t *>(res + 16), 256u);
+    if (lane == 0) s_nvals[t] = nvals;
+    uint32_t first[17], cum[17];                                   // by length: the first code word, the HUFFVAL places up to and with it
+    first[0] = cum[0] = 0u;
+    uint32_t code = 0;
+#pragma unroll
+    for (int l = 1; l <= 16; ++l) { const uint32_t n = res[l - 1]; first[l] = code; cum[l] = cum[l - 1] + n; code = (code + n) << 1; }
+    uint32_t *const tab = a.tabs + ((size_t)q * kProgTables + (size_t)t) * 272;
+    for (int i = lane; i < 272; i += 64) tab[i] = 0u;
+    __syncthreads();                                               // (the zeros are in place before a code word; s_nvals is complete)
+    for (uint32_t i = (uint32_t)lane; i < nvals; i += 64u) {
+        uint32_t l = 1, f = 0, c0 = 0;
+#pragma unroll
+        for (int k = 1; k <= 16; ++k) if (cum[k] <= i) l = (uint32_t)k + 1u;
+#pragma unroll
+        for (int k = 1; k <= 16; ++k) if ((uint32_t)k == l) { f = first[k]; c0 = cum[k - 1]; }
+        const uint32_t sym = res[32 + i];
+        if (l <= 16u && (t >= 2 || sym < 16u)) tab[(t < 2 ? 256u : 0u) + sym] = (l << 16) | (f + i - c0);
+    }
+    const int scan = t < 2 ? 0 : t - 1;
+    uint8_t *const out = a.hdr_out + ((size_t)scan * a.pictures + (size_t)(a.first + q)) * kMcuPrefixSlot;
+    uint32_t at = t < 2 ? (uint32_t)a.head_len + (t == 1 ? 21u + s_nvals[0] : 0u) : 0u;
+    const auto put = [&](uint32_t pos, uint8_t v) { if (pos < (uint32_t)kMcuPrefixSlot) out[pos] = v; };
+    if (lane == 0) {
+        put(at, 0xFF); put(at + 1, 0xC4); put(at + 2, (uint8_t)((19u + nvals) >> 8)); put(at + 3, (uint8_t)(19u + nvals));
+        put(at + 4, (uint8_t)(t < 2 ? t : ((t - 2) % 3 == 0 ? 0x10 : 0x11)));
+    }
+    if (lane < 16) put(at + 5 + lane, res[lane]);
+    for (uint32_t i = (uint32_t)lane; i < nvals; i += 64u) put(at + 21 + i, res[32 + i]);
+    at += 21u + nvals;
+    if (t == 0) {
+        for (int i = lane; i < a.head_len; i += 64) put((uint32_t)i, a.hdr[i]);
+    } else {                                                       // the SOS behind the scan's last table, and the slot's length
+        const uint8_t *sos = t == 1 ? a.hdr + a.sos_off : a.sos + 16 * scan;
+        const uint32_t nsos = t == 1 ? (uint32_t)kMcuSosLen : (uint32_t)kSosBytes;
+        if ((uint32_t)lane < nsos) put(at + (uint32_t)lane, sos[lane]);
+        if (lane == 0) a.hdr_len[(size_t)scan * a.pictures + (size_t)(a.first + q)] = min(at + nsos, (uint32_t)kMcuPrefixSlot);
+    }
+}
+
+int launch_prog_tables(const ProgTablesArgs &a, int batch, void *stream) {
+    if (batch < 1 || batch > kMaxBatch || !a.res || !a.tabs || !a.hdr_out || !a.hdr_len || !a.hdr || !a.sos || a.head_len < 0 ||
+        a.head_len + 2 * 33 + kMcuSosLen > kMcuPrefixSlot || a.first < 0 || a.first + batch > a.pictures)
+        return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_prog_tables, dim3((unsigned)batch), dim3(64 * kProgTables), 0, (hipStream_t)stream, a);
     return (int)hipGetLastError();
 }
 
@@ -403,18 +586,21 @@ __global__ __launch_bounds__(256) void k_scans_concat(const ScansConcatArgs a) {
     for (int k = 0; k < kProgScans; ++k) { size[k] = a.size[k * kMaxBatch + p]; total += size[k]; }
     const bool fit = hard == 0u && total <= a.out_capacity;
     if (blockIdx.x == 0 && threadIdx.x == 0) {
-        unsigned long long bits = 0, syms = 0, bytes = 0;
+        unsigned long long bits = 0, syms = 0, bytes = 0, ff = 0;
 #pragma unroll
         for (int k = 0; k < kProgScans; ++k) {
             const unsigned long long b = a.sums[2 * (k * kMaxBatch + p)];
             bits += b; syms += a.sums[2 * (k * kMaxBatch + p) + 1]; bytes += (b + 7u) / 8u;
+            if (a.writer_sums) ff += a.writer_sums[(k * kMaxBatch + p) * kMcuPicSums + 2];
         }
         const unsigned long long *pic = a.pic + (size_t)p * kPicStatWords;
         ScanStats *t = a.stats;
         atomicAdd((unsigned long long *)&t->total_bits, bits);
         atomicAdd((unsigned long long *)&t->total_syms, syms);
         atomicAdd((unsigned long long *)&t->total_exact, pic[2] + pic[5] + pic[8]);
-        atomicAdd((unsigned long long *)&t->total_ff, (unsigned long long)(total - (uint64_t)a.prefix_len - (uint64_t)(kProgScans - 1) * kSosBytes - 2u) - bytes);
+        // the stuffed bytes follow from the size -- or the restart writer counted them (4.6.13: the headers differ from picture to picture)
+        atomicAdd((unsigned long long *)&t->total_ff,
+                  a.writer_sums ? ff : (unsigned long long)(total - (uint64_t)a.prefix_len - (uint64_t)(kProgScans - 1) * kSosBytes - 2u) - bytes);
         *a.out_size[p] = fit ? total : 0ull;
         if (a.last_of_call && p == (int)gridDim.y - 1) t->out_size = fit ? total : 0ull;
         const uint32_t add = st | (fit ? 0u : 1u);
@@ -815,7 +1001,7 @@ __global__ __launch_bounds__(kRstThreads) void k_mcu_restart_offsets(const McuRe
                 const bool last = i == a.last_seg;
                 if (last || (k[j] == spi - 1 && i < last_first)) {
                     const RstTail t = rst_tail(b0[j] + bits[j], mcu_tail7(edge[j], bits[j], edge_prev[j]), last);
-                    bytes[j] += t.bytes; pad_ff = t.pad_ff;
+                    bytes[j] += t.bytes - (last && a.no_eoi ? 2u : 0u); pad_ff = t.pad_ff;
                 }
                 sum_ff += ff[j] + pad_ff; sum_bits += bits[j]; sum_syms += syms[j];
             }
@@ -867,8 +1053,9 @@ __global__ __launch_bounds__(64 * kWavesM) void k_mcu_restart_write(const McuRes
     const uint32_t nown = ((b0 + bits) >> 3) - (b0 >> 3);
     const bool last = sl == a.last_seg, tail = last || (k == a.segs_per_interval - 1 && iv < a.intervals - 1);
     const RstTail t = rst_tail(b0 + bits, mcu_tail7(edge, bits, edge_prev), last);
+    const bool marker = !(last && a.no_eoi);                        // (a scan that another follows is flushed and ends there: no EOI)
     const uint64_t base = (uint64_t)prefix_len + a.pos[seg];
-    if (base + nown + my_ff + (tail ? t.bytes : 0u) > a.out_capacity) return;    // the file does not fit: k_mcu_totals reports it from the size
+    if (base + nown + my_ff + (tail ? t.bytes - (marker ? 0u : 2u) : 0u) > a.out_capacity) return;    // the file does not fit: k_mcu_totals reports it from the size
 
     const uint32_t *words = a.seg.words + seg * a.seg.words_stride;
     uint32_t *const strip32 = s_strip[wave];
@@ -928,7 +1115,7 @@ __global__ __launch_bounds__(64 * kWavesM) void k_mcu_restart_write(const McuRes
     if (tail && lane == 0) {
         uint8_t *e = dst + nown + my_ff;
         if (t.r) { *e++ = (uint8_t)t.byte; if (t.pad_ff) *e++ = 0x00; }
-        e[0] = 0xFF; e[1] = last ? 0xD9 : (uint8_t)(0xD0 + (iv & 7));
+        if (marker) { e[0] = 0xFF; e[1] = last ? 0xD9 : (uint8_t)(0xD0 + (iv & 7)); }
     }
 }
 

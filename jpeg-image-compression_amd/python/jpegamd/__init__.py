@@ -138,6 +138,11 @@ def _prototypes():
         "jpegamd_encode_color_progressive_batch_async": batch(Image, 1),
         "jpegamd_encode_ycbcr_progressive_batch_async": batch(YCbCrImage, 4),               # (subsampling, range, format, matrix)
         "jpegamd_max_jfif_bytes_progressive": (u64, [i32, i32, i32]),
+        # ... with end-of-band runs and per-scan optimised tables
+        "jpegamd_encode_color_progressive_optimized_batch_async": batch(Image, 1),
+        "jpegamd_encode_ycbcr_progressive_optimized_batch_async": batch(YCbCrImage, 4),
+        "jpegamd_max_jfif_bytes_progressive_optimized": (u64, [i32, i32, i32]),
+        "jpegamd_debug_progressive_counts": (i32, [vp, vp]),
     }
     later = {
         "jpegamd_encoder_set_pipeline": (i32, [vp, i32]),
@@ -334,8 +339,15 @@ def max_jfif_bytes_progressive(width: int, height: int, subsampling: int = SUBSA
     return int(lib.jpegamd_max_jfif_bytes_progressive(width, height, subsampling))
 
 
+def max_jfif_bytes_progressive_optimized(width: int, height: int, subsampling: int = SUBSAMPLE_420) -> int:
+    """Upper bound on the bytes of a progressive colour file with end-of-band runs and per-scan optimised tables (DESIGN.md
+    4.6.13): max_jfif_bytes_progressive + 780; 0 for bad arguments."""
+    return int(lib.jpegamd_max_jfif_bytes_progressive_optimized(width, height, subsampling))
+
+
 SCANS = ("separate", "interleaved")
 HUFFMAN_STANDARD, HUFFMAN_OPTIMIZED = 0, 1       # jpegamd_encoder_set_huffman
+PROGRESSIVE_OPTIMIZED = "optimized"              # a `progressive` argument inside this package: the entries of DESIGN.md 4.6.13 (True: 4.6.12's)
 HUFFMANS = ("standard", "optimized")
 
 
@@ -609,7 +621,7 @@ def encode_tensor_batch(t, quality: int = 0, subsampling: int = SUBSAMPLE_420, l
     if any(not x.is_cuda or x.device != tensors[0].device for x in tensors):
         raise ValueError("encode_tensor_batch needs a device tensor")
     if _progressive:
-        cap = max_jfif_bytes_progressive(w, h, subsampling)
+        cap = (max_jfif_bytes_progressive_optimized if _progressive == PROGRESSIVE_OPTIMIZED else max_jfif_bytes_progressive)(w, h, subsampling)
     elif interleaved:
         cap = max_jfif_bytes_interleaved_restart(w, h, subsampling, ri) if ri else max_jfif_bytes_interleaved(w, h, subsampling)
     elif order == ORDER_GRAY or (order is None and subsampling == 0):
@@ -624,8 +636,10 @@ def encode_tensor_batch(t, quality: int = 0, subsampling: int = SUBSAMPLE_420, l
             imgs = [Encoder.image(ptr(b0 + i), w, h, stride, bottom_up=False, channel_order=order, quality=quality) for i in range(k)]
         _queue_pixels(enc, imgs, subsampling, outs, cap, size_ptrs, stream, interleaved, ri, _any_layout, _huffman, _progressive)
 
-    # (a progressive call sets the standard tables on the shared context: the entry refuses any other mode)
-    return _encode_pictures(tensors[0].device, n, h, w, cap, queue, HUFFMAN_STANDARD if _progressive else (_huffman or None))
+    # (a progressive call sets the standard tables on the shared context: the entry refuses any other mode; the optimised
+    # progressive entries do not read the mode)
+    return _encode_pictures(tensors[0].device, n, h, w, cap, queue,
+                            HUFFMAN_STANDARD if _progressive and _progressive != PROGRESSIVE_OPTIMIZED else (_huffman or None))
 
 
 def _queue_pixels(enc, imgs, subsampling, outs, cap, size_ptrs, stream, interleaved: bool = False, restart: int = 0,
@@ -635,7 +649,9 @@ def _queue_pixels(enc, imgs, subsampling, outs, cap, size_ptrs, stream, interlea
     the entry of every pixel order with `any_layout` (jpegamd.mjpeg), otherwise the RGB entries of encode_tensor_batch's own
     scan="interleaved" -- the restart entry when there are intervals, and for `huffman` (whatever the interval)."""
     planar = isinstance(imgs[0], PlanarImage)
-    if progressive:                                               # (jpegamd.progressive: packed pixels, no intervals, the standard tables)
+    if progressive == PROGRESSIVE_OPTIMIZED:                      # (jpegamd.progressive_optimized: the tables of every scan its own)
+        enc.encode_color_progressive_optimized_batch_async(imgs, subsampling, outs, cap, size_ptrs, stream)
+    elif progressive:                                             # (jpegamd.progressive: packed pixels, no intervals, the standard tables)
         enc.encode_color_progressive_batch_async(imgs, subsampling, outs, cap, size_ptrs, stream)
     elif not interleaved:
         if planar:
@@ -803,14 +819,15 @@ def _encode_ycbcr_images(device, n, h, w, subsampling, image, sample_range: int 
     jpegamd_encode_ycbcr_interleaved_matrix_batch_async, with the tables `huffman` (set on the context for the call, STANDARD put back)."""
     if huffman and not any_kind:
         raise ValueError("optimised Huffman tables go through jpegamd.mjpeg")
-    if progressive:                                               # (jpegamd.progressive: any kind, no intervals, the standard tables set for the call)
-        cap = max_jfif_bytes_progressive(w, h, subsampling)
+    if progressive:                                               # (jpegamd.progressive: any kind, no intervals, the standard tables set for the call;
+        own = progressive == PROGRESSIVE_OPTIMIZED                # jpegamd.progressive_optimized: the context's mode is left alone)
+        cap = (max_jfif_bytes_progressive_optimized if own else max_jfif_bytes_progressive)(w, h, subsampling)
 
         def queue_progressive(enc, b0, k, outs, cap, size_ptrs, stream):
-            enc.encode_ycbcr_progressive_batch_async([image(b0 + i) for i in range(k)], subsampling, sample_range, sample_format, matrix,
-                                                     outs, cap, size_ptrs, stream)
+            entry = enc.encode_ycbcr_progressive_optimized_batch_async if own else enc.encode_ycbcr_progressive_batch_async
+            entry([image(b0 + i) for i in range(k)], subsampling, sample_range, sample_format, matrix, outs, cap, size_ptrs, stream)
 
-        return _encode_pictures(device, n, h, w, cap, queue_progressive, HUFFMAN_STANDARD)
+        return _encode_pictures(device, n, h, w, cap, queue_progressive, None if own else HUFFMAN_STANDARD)
     if restart:
         cap = max_jfif_bytes_interleaved_restart(w, h, subsampling, restart)
     else:
@@ -934,6 +951,18 @@ class _ProgressiveEntries:
         (jpegamd_encode_ycbcr_progressive_batch_async)."""
         self._batch("jpegamd_encode_ycbcr_progressive_batch_async", YCbCrImage, imgs, (subsampling, sample_range, sample_format, matrix),
                     out_ptrs, out_cap, size_ptrs, stream)
+
+    def encode_color_progressive_optimized_batch_async(self, imgs, subsampling: int, out_ptrs, out_cap: int, size_ptrs, stream: int = 0):
+        """The progressive files with end-of-band runs and per-scan optimised tables of the same pictures
+        (jpegamd_encode_color_progressive_optimized_batch_async); out_cap from max_jfif_bytes_progressive_optimized.  The context's
+        Huffman mode is neither read nor changed."""
+        self._batch("jpegamd_encode_color_progressive_optimized_batch_async", Image, imgs, (subsampling,), out_ptrs, out_cap, size_ptrs, stream)
+
+    def encode_ycbcr_progressive_optimized_batch_async(self, imgs, subsampling: int, sample_range: int, sample_format: int, matrix: int,
+                                                       out_ptrs, out_cap: int, size_ptrs, stream: int = 0):
+        """... of YCbCr pictures of any kind (jpegamd_encode_ycbcr_progressive_optimized_batch_async)."""
+        self._batch("jpegamd_encode_ycbcr_progressive_optimized_batch_async", YCbCrImage, imgs,
+                    (subsampling, sample_range, sample_format, matrix), out_ptrs, out_cap, size_ptrs, stream)
 
 
 class Encoder(_ProgressiveEntries):

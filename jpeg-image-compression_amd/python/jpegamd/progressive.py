@@ -4,7 +4,8 @@ YCbCr source the one-scan functions of `jpegamd.mjpeg` read.
 Each function is its twin in `jpegamd.mjpeg` without `restart_interval=` and `huffman=`: the same tensors, the same layout=, order=,
 sample_range=, matrix= and align=.  The file holds the coefficients of the twin's one-scan file in seven scans by spectral selection
 (the DC of all three components, then the bands 1..5 and 6..63 of Y, Cb and Cr) and decodes to the same pixels.  It is a little larger
-than the one-scan file: this version codes no end-of-band runs, its value is the progressive rendering.
+than the one-scan file: it codes no end-of-band runs with the Annex K tables (`jpegamd.progressive_optimized` does, with tables of its
+own, and is about the size of the optimised one-scan file).
 
 Planar R, G, B pictures (layout="chw") are not taken.  The Annex K tables are set on the per-device context for the call."""
 from __future__ import annotations

@@ -53,7 +53,9 @@ context, so a library from before the mode serves it.
 
 --scan progressive (with --batch N, default 8) sends the batch loop through the progressive entries:
 jpegamd_encode_color_progressive_batch_async for rgb, jpegamd_encode_ycbcr_progressive_batch_async for every YCbCr source, --range and
---matrix; the whole call is timed (ns_total), the line carries "scan": "progressive".  No --restart, --huffman, --layout, --convert, --narrow.
+--matrix; the whole call is timed (ns_total), the line carries "scan": "progressive".  No --restart, --layout, --convert, --narrow.
+With --huffman optimized the loop goes through jpegamd_encode_*_progressive_optimized_batch_async (end-of-band runs and
+per-scan optimised tables; nothing is set on the context); --huffman standard is the plain progressive loop.
 
 --scan gray (with --batch N, default 8) times GRAYSCALE files through jpegamd_encode_gray_scan_batch_async: the luma
 of the same --size pictures, --restart N|row in blocks (`row`: ceil(W / 8)), --huffman standard|optimized; the whole call is timed
@@ -131,8 +133,8 @@ def main() -> None:
         sys.exit("--narrow needs --source p010 or i010")
     if a.scan == "interleaved" and (a.convert or a.narrow):
         sys.exit("--convert and --narrow time routes of the three-scan path: not with --scan interleaved")
-    if a.scan == "progressive" and (a.convert or a.narrow or a.layout is not None or a.huffman is not None or a.restart is not None):
-        sys.exit("--scan progressive takes --size, --batch, --source, --subsampling, --range, --matrix, --mapped, --quality, --kind alone")
+    if a.scan == "progressive" and (a.convert or a.narrow or a.layout is not None or a.restart is not None):
+        sys.exit("--scan progressive takes --size, --batch, --source, --subsampling, --range, --matrix, --mapped, --quality, --kind, --huffman alone")
     if a.mapped and (a.sample_range != "limited" or any(s not in ("i420", "nv12", "i422") for s in sources)):
         sys.exit("--mapped needs --range limited and takes --source i420, nv12, i422")
     if a.huffman is not None and a.scan == "separate":
@@ -265,7 +267,7 @@ def run_batch(a, jpegamd, torch, dev, sources=("rgb",)) -> None:
         descs.append(jpegamd.Encoder.image(pxs[-1].data_ptr(), w, h, img.row_stride, True, jpegamd.ORDER_BGR, a.quality))
         del bmp
     enc = jpegamd.Encoder(w, n * h)
-    if a.huffman == "optimized":
+    if a.huffman == "optimized" and a.scan != "progressive":      # (the optimised progressive entries do not read the context's mode)
         enc.set_huffman(jpegamd.HUFFMAN_OPTIMIZED)
     stream = torch.cuda.current_stream().cuda_stream
     frames = None
@@ -341,8 +343,9 @@ def run_batch(a, jpegamd, torch, dev, sources=("rgb",)) -> None:
         ycc = describe(tensors) if describe else None
         one_scan, progressive = a.scan == "interleaved", a.scan == "progressive"
         cap = jpegamd.max_jfif_bytes_interleaved(w, h, sub) if one_scan else jpegamd.max_jfif_bytes_color(w, h, sub)
+        own = progressive and a.huffman == "optimized"
         if progressive:
-            cap = jpegamd.max_jfif_bytes_progressive(w, h, sub)
+            cap = (jpegamd.max_jfif_bytes_progressive_optimized if own else jpegamd.max_jfif_bytes_progressive)(w, h, sub)
         restart = None
         if a.restart is not None:                                # `row`: ceil(W / 8) MCUs at 4:4:4, ceil(W / 16) otherwise
             restart = -(-w // (8 if sub == jpegamd.SUBSAMPLE_444 else 16)) if a.restart == "row" else int(a.restart)
@@ -352,10 +355,12 @@ def run_batch(a, jpegamd, torch, dev, sources=("rgb",)) -> None:
         out_ptrs = [o.data_ptr() for o in outs]
         size_ptrs = [sizes.data_ptr() + 8 * i for i in range(n)]
         if progressive and ycc is None:
-            call = lambda: enc.encode_color_progressive_batch_async(descs, sub, out_ptrs, cap, size_ptrs, stream)
+            entry = enc.encode_color_progressive_optimized_batch_async if own else enc.encode_color_progressive_batch_async
+            call = lambda: entry(descs, sub, out_ptrs, cap, size_ptrs, stream)
         elif progressive:
             fmt = {"p010": jpegamd.SAMPLES_10_MSB, "i010": jpegamd.SAMPLES_10_LSB}.get(source, jpegamd.SAMPLES_8)
-            call = lambda: enc.encode_ycbcr_progressive_batch_async(
+            entry = enc.encode_ycbcr_progressive_optimized_batch_async if own else enc.encode_ycbcr_progressive_batch_async
+            call = lambda: entry(
                 ycc, sub, jpegamd.RANGE_LIMITED if limited else jpegamd.RANGE_FULL, fmt, jpegamd.MATRIX_BT709 if bt709 else jpegamd.MATRIX_BT601,
                 out_ptrs, cap, size_ptrs, stream)
         elif one_scan and ycc is not None and (limited or bt709 or source in ("yuyv", "p010", "i010")):     # a kind the older one-scan entries refuse
