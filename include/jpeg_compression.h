@@ -594,6 +594,68 @@ int32_t jpegamd_encode_ycbcr_progressive_optimized_batch_async(JpegAmdEncoder *e
 uint64_t jpegamd_max_jfif_bytes_progressive_optimized(int32_t width, int32_t height, int32_t subsampling);
 int32_t jpegamd_debug_progressive_counts(JpegAmdEncoder *enc, uint64_t *counts);
 
+/* Progressive colour files with SUCCESSIVE APPROXIMATION: SOF2, and the coefficients of the one-scan file of the same input -- the
+ * quantiser, the pad blocks and the MCU order of the progressive file above.  The ten scans are those of libjpeg's
+ * jpeg_simple_progression for YCbCr (what `cjpeg -progressive` writes), in this order:
+ *     scan  components            Ss..Se  Ah Al  tables (the file's order)
+ *      1    Y Cb Cr interleaved   0..0    0  1   0: Y DC, 1: Cb + Cr DC
+ *      2    Y                     1..5    0  2   2
+ *      3    Cr                    1..63   0  1   3
+ *      4    Cb                    1..63   0  1   4
+ *      5    Y                     6..63   0  2   5
+ *      6    Y                     1..63   2  1   6
+ *      7    Y Cb Cr interleaved   0..0    1  0   none: raw bits, its SOS alone
+ *      8    Cr                    1..63   1  0   7
+ *      9    Cb                    1..63   1  0   8
+ *     10    Y                     1..63   1  0   9
+ * The head is SOI, APP0, DQT, SOF2; there are no Annex K segments.  Every table is made of its own scan's symbol counts by the
+ * construction above and written as the scan's own DHT in front of its SOS: Tc/Th 0x00 / 0x01 for the DC tables, 0x10 for Y AC scans
+ * and 0x11 for chroma AC scans.  SOS: the segments above with Ss, Se and the byte Ah << 4 | Al.  Every scan is stuffed and flushed
+ * with 0-bits; EOI follows the last.
+ *   First DC scan (Ah = 0).  The value is DC >> Al, an arithmetic shift; the difference to the previous block's shifted value (0 in
+ *     front of a component's first block) is coded as a DC difference always is.  Pad blocks count.
+ *   DC refinement scan.  One raw bit per block in MCU order, (DC >> Al) & 1.  Pad blocks count.  No Huffman table.
+ *   First AC scans.  The walk of the file above (points 2 and 3) over v = sign(c) (|c| >> Al); E and Z of the run rule are taken on v.
+ *   AC refinement scans (T.81 G.1.2.3, what libjpeg's encode_mcu_AC_refine writes).  a[k] = |c[k]| >> Al.  A coefficient of the band
+ *     is NEW if a = 1, OLD if a > 1, zero otherwise.  K is the last new k of the band; Z: the band has no new coefficient; E: a[Se] != 1.
+ *     The block's string is HEAD, RUN SYMBOL (if the block starts a run), TAIL.
+ *       Head: for k = Ss .. K, r counts zeros and B collects the bits a & 1 of old coefficients.  At every non-zero coefficient, while
+ *         r > 15: code ZRL, then B; empty B; r -= 16.  An old coefficient then appends its bit to B.  A new coefficient codes symbol
+ *         (r << 4) | 1, one sign bit (1 for positive), then B; it empties B and sets r = 0.
+ *       Tail: the correction bits a & 1 of the old coefficients behind K -- of a Z block: of all its old coefficients.  No ZRL behind K.
+ *       Runs: the rule above, unchanged, with this E and Z.  Block i starts a run iff E[i] and not (Z[i] and i mod 256 != 0 and
+ *         E[i - 1]); the run covers the following Z blocks up to the next multiple of 256; the symbol is EOBn and n bits.
+ *     Because the symbol stands between its starter's head and tail and a covered block's string is its tail alone, the scan is the
+ *     concatenation of the blocks' strings in block order.
+ * jpegamd_encode_color_progressive_successive_batch_async and jpegamd_encode_ycbcr_progressive_successive_batch_async take the
+ * arguments, refusals, batching, context sizing, capacity behaviour (size 0, JPEGAMD_ERR_HUFF_CAPACITY, nothing written past
+ * out_capacity, the other pictures unaffected) and statistics of the _progressive_optimized_ entries: bits and stuffed bytes summed
+ * over the ten scans, exact_fallbacks counted once.  They neither read nor change the context's Huffman mode.
+ * The bound, jpegamd_max_jfif_bytes_progressive_successive.  Bits per block, summed over the scans that touch it.  A Y block: its DC
+ * difference at most 16 + 11 (scan 1); its refinement bit, 1 (scan 7); its 63 coefficients in the first scans 2 and 5 at most
+ * 26 each (a non-zero one 16 + 10 -- the point transform only shortens amplitudes --, a ZRL 16 for sixteen zeros, either scan's run
+ * symbol 16 + 8 paid by its own zero coefficient Se); in each of the refinement scans 6 and 10 a new coefficient 16 + 1, an old one 1,
+ * sixteen zeros a ZRL of at most 16, and the run symbol 16 + 8 only where coefficient Se is not new and costs at most 1:
+ * 62 x 17 + 25 = 1079.  Together 27 + 1 + 1638 + 2 x 1079 = 3824 bits; a chroma block has one refinement scan and costs less.  The
+ * bound is the one-scan bound's form with 3824 for 1723 -- every block of every MCU, pad blocks too, every byte stuffed, one
+ * rounding up to a byte, EOI, 640 bytes for the head with 432 bytes of DHT and a 14-byte SOS -- plus nine more roundings of at most
+ * one byte each that may be stuffed (18), eight more SOS of 10 bytes and one of 14, and the DHT segments of ten tables, at most
+ * 2 x 33 + 8 x 191 = 1594 bytes against the 432 held: 1162 more.  0 for bad arguments.
+ * One block's string in any single scan is at most 1665 bits (a first scan: 27 or 63 x 26; a refinement scan: 1079; the DC
+ * refinement scan: 1): the reservation of a coder segment (256 blocks of 1665 bits) holds every scan's segments.
+ * jpegamd_debug_progressive_successive_counts (tests; synchronous, `counts` a HOST pointer): the symbol counts of the context's last
+ * such call, [pictures of that call][10][256] in the file's table order.  JPEGAMD_ERR_ARG when the context's last call with per-scan
+ * tables was not one of these (jpegamd_debug_progressive_counts answers the same way after one of these). */
+int32_t jpegamd_encode_color_progressive_successive_batch_async(JpegAmdEncoder *enc, const JpegAmdImage *imgs, int32_t count, int32_t subsampling,
+                                                                void *const *outs_dev, uint64_t out_capacity, uint64_t *const *out_sizes_dev,
+                                                                void *stream);
+int32_t jpegamd_encode_ycbcr_progressive_successive_batch_async(JpegAmdEncoder *enc, const JpegAmdYCbCrImage *imgs, int32_t count,
+                                                                int32_t subsampling, int32_t sample_range, int32_t sample_format, int32_t matrix,
+                                                                void *const *outs_dev, uint64_t out_capacity, void *const *out_sizes_dev,
+                                                                void *stream);
+uint64_t jpegamd_max_jfif_bytes_progressive_successive(int32_t width, int32_t height, int32_t subsampling);
+int32_t jpegamd_debug_progressive_successive_counts(JpegAmdEncoder *enc, uint64_t *counts);
+
 /* Block until the last enqueued encode on this context finished; optionally fetch stats
  * (stats may be NULL).  Returns JPEGAMD_ERR_HUFF_CAPACITY if the output did not fit. */
 int32_t jpegamd_encoder_finish(JpegAmdEncoder *enc, JpegAmdStats *stats);

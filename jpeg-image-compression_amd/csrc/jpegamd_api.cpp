@@ -144,6 +144,7 @@ struct JpegAmdEncoder {
         uint32_t *phdr_len = nullptr;       // [kProgScans][pictures of the call]
         int pcap = 0;                       // pictures
         int plast = 0;                      // pictures of the last such call: pcounts[0, plast) are theirs
+        int plast_tables = 0;               // ... and the tables of its script: pcounts is [plast][plast_tables][256]
     } mcu;
 };
 
@@ -1611,34 +1612,85 @@ constexpr int kMcuSosBytes = 14;
 constexpr size_t kMcuScratchBudget = (size_t)4 << 30;       // coefficient planes + segment strings of one group of pictures
 
 // ---- progressive files ----
-constexpr int kProgNone = 0, kProgStandard = 1, kProgRuns = 2;      // interleaved_batch's `progressive`: one scan / seven scans, Annex K / seven scans with runs and own tables
+// interleaved_batch's `progressive`: one scan / seven scans, Annex K / seven scans with runs and own tables / the ten scans of successive approximation
+constexpr int kProgNone = 0, kProgStandard = 1, kProgRuns = 2, kProgSuccessive = 3;
+
+// The scan script: what every scan of a progressive file codes, in the file's order.  comp: the component of a
+// one-component scan (0 Y, 1 Cb, 2 Cr), -1 the three interleaved; table: the scan's first table in the file's table order (a DC
+// scan has two: Y, then Cb + Cr), -1 for a scan of raw bits.  The files of 4.6.12 and 4.6.13 are the first script (4.6.12 reads no
+// table numbers), the file of 4.6.14 -- libjpeg's jpeg_simple_progression for YCbCr -- the second.
+struct ProgScan { int8_t comp; uint8_t ss, se, ah, al; int8_t table; };
+struct ProgScript { int id, scans, tables; ProgScan scan[kProgScansMax]; };
+static const ProgScript kScriptSpectral = {0, kProgScans, kProgTables,
+    {{-1, 0, 0, 0, 0, 0}, {0, 1, 5, 0, 0, 2}, {1, 1, 5, 0, 0, 3}, {2, 1, 5, 0, 0, 4}, {0, 6, 63, 0, 0, 5}, {1, 6, 63, 0, 0, 6}, {2, 6, 63, 0, 0, 7}}};
+static const ProgScript kScriptSuccessive = {1, 10, 10,
+    {{-1, 0, 0, 0, 1, 0}, {0, 1, 5, 0, 2, 2}, {2, 1, 63, 0, 1, 3}, {1, 1, 63, 0, 1, 4}, {0, 6, 63, 0, 2, 5},
+     {0, 1, 63, 2, 1, 6}, {-1, 0, 0, 1, 0, -1}, {2, 1, 63, 1, 0, 7}, {1, 1, 63, 1, 0, 8}, {0, 1, 63, 1, 0, 9}}};
+static_assert(kProgScans <= kProgScansMax && kProgTables <= kProgTablesMax, "the scripts fit the kernels' maxima");
+static const ProgScript &prog_script(int progressive) { return progressive == kProgSuccessive ? kScriptSuccessive : kScriptSpectral; }
+// The SOS segment of a script's scan: 14 bytes for the three components (Y: tables 0 / 0, Cb and Cr: 1 / 1), kSosBytes for one.
+static int prog_sos(const ProgScan &s, uint8_t out[16]) {
+    int n = kSosBytes;
+    if (s.comp < 0) {
+        const uint8_t sos3[14] = {0xFF, 0xDA, 0x00, 0x0C, 0x03, 0x01, 0x00, 0x02, 0x11, 0x03, 0x11, 0x00, 0x00, 0x00};
+        std::memcpy(out, sos3, sizeof(sos3));
+        n = (int)sizeof(sos3);
+    } else {
+        color_sos(1 + s.comp, out);
+    }
+    out[n - 3] = s.ss; out[n - 2] = s.se; out[n - 1] = (uint8_t)((s.ah << 4) | s.al);
+    return n;
+}
+
 // What a progressive call keeps on the device besides the slots: k_finalize's two records (scan 1's; the scans into slots share the
-// other), every scan's size and sums per picture of the group, and the SOS segments of the scans 2 .. 7, 16 bytes apart.
+// other), every scan's size and sums per picture of the group -- [scans][kMaxBatch] arrays one behind the other, so a call clears as
+// many bytes as its script has scans for --, and behind the records of the longest script the SOS segments of every script's
+// scans, 16 bytes apart.
 struct ProgMeta {
-    ScanStats scan_stats[2];
-    uint64_t size[kProgScans][kMaxBatch];
-    unsigned long long sums[kProgScans][kMaxBatch][2];
-    unsigned long long writer_sums[kProgScans][kMaxBatch][kMcuPicSums];     // k_mcu_restart_offsets' (4.6.13 alone)
-    uint8_t sos[kProgScans][16];
+    ScanStats *scan_stats;              // [2]
+    uint64_t *size;                     // [scans][kMaxBatch]
+    unsigned long long *sums;           // [scans][kMaxBatch][2]
+    unsigned long long *writer_sums;    // [scans][kMaxBatch][kMcuPicSums] k_mcu_restart_offsets' (4.6.13, 4.6.14)
+    size_t record_bytes;                // all of the above
 };
-// Scan k (from 0) of a progressive file: k = 0 the DC scan, then component (k - 1) % 3 of band (k - 1) / 3.
-// The slots of the scans 2 .. 7 of one picture: each holds SOS, the scan at its bound (every block of the component's plane at the
-// band's worst case, every byte stuffed, the flush byte), EOI, and what k_scans_concat reads behind them in 16-byte steps.
+static_assert(sizeof(ScanStats) % 8 == 0, "the arrays behind the two records are aligned");
+constexpr size_t prog_meta_bytes(int scans) { return 2 * sizeof(ScanStats) + (size_t)scans * kMaxBatch * (8 + 16 + 8 * kMcuPicSums); }
+constexpr size_t kProgMetaSos = prog_meta_bytes(kProgScansMax), kProgMetaAlloc = kProgMetaSos + 2 * kProgScansMax * 16;
+static ProgMeta prog_meta(uint8_t *base, int scans) {
+    ProgMeta m;
+    m.scan_stats = reinterpret_cast<ScanStats *>(base);
+    m.size = reinterpret_cast<uint64_t *>(base + 2 * sizeof(ScanStats));
+    m.sums = reinterpret_cast<unsigned long long *>(m.size + (size_t)scans * kMaxBatch);
+    m.writer_sums = m.sums + (size_t)scans * kMaxBatch * 2;
+    m.record_bytes = prog_meta_bytes(scans);
+    return m;
+}
+static const uint8_t *prog_meta_sos(const uint8_t *base, const ProgScript &sc) { return base + kProgMetaSos + (size_t)sc.id * kProgScansMax * 16; }
+
+// The slots of the scans 2 .. of one picture: each holds the scan's header, the scan at its bound (every block of the component's
+// plane at the band's worst case, every byte stuffed, the flush byte), EOI, and what k_scans_concat reads behind them in 16-byte steps.
 // own_tables (4.6.13): the scan's DHT segment in front of its SOS; a coefficient of a band then costs at most 16 + 10 bits, a run's
 // symbol 16 + 8, paid for by the zero coefficient se of the block that starts it -- below the 27 of prog_band_bits either way.
+// Successive approximation: a first scan's coefficient costs no more (shorter amplitudes); a refinement scan's at most 17, its run's
+// symbol at a coefficient se that costs 1 (kMaxBlockBitsRefine): below 27 a coefficient again; the DC refinement scan, the one
+// three-component scan in a slot, is 1 bit a block of an MCU, pad blocks included.
 constexpr int kProgDhtMax = 21 + 170;       // an AC table of a scan: 160 run/size symbols, ZRL, EOB0 .. EOB8
 static_assert(kProgDhtMax + kSosBytes <= kMcuPrefixSlot, "a scan's header fits its slot");
-struct ProgSlots { uint64_t off[kProgScans], cap[kProgScans], pic_bytes; };
-static ProgSlots prog_slots(const McuGeometry &g, bool own_tables = false) {
+static_assert(kMaxBlockBitsRefine <= 63 * 27, "a refinement scan's block is within the slot's 27 bits a coefficient");
+struct ProgSlots { uint64_t off[kProgScansMax], cap[kProgScansMax], pic_bytes; };
+static ProgSlots prog_slots(const McuGeometry &g, const ProgScript &sc, bool own_tables = false) {
     ProgSlots s = {};
-    for (int k = 1; k < kProgScans; ++k) {
-        const uint64_t nb = (k - 1) % 3 == 0 ? (uint64_t)g.bw * g.bh : (uint64_t)g.mx * g.my;
-        s.cap[k] = (own_tables ? kProgDhtMax : 0) + kSosBytes + scan_bound(nb, prog_band_bits((k - 1) / 3)) + 2;
+    for (int k = 1; k < sc.scans; ++k) {
+        const ProgScan &c = sc.scan[k];
+        const uint64_t nb = c.comp < 0 ? (uint64_t)g.mx * g.my * (uint64_t)(g.hs * g.vs + 2) : (c.comp == 0 ? (uint64_t)g.bw * g.bh : (uint64_t)g.mx * g.my);
+        const uint64_t bits = c.comp < 0 ? 1u : (uint64_t)(c.se - c.ss + 1) * 27u;      // (prog_band_bits for the bands of 4.6.12)
+        s.cap[k] = (own_tables && c.table >= 0 ? kProgDhtMax : 0) + (c.comp < 0 ? 14 : kSosBytes) + scan_bound(nb, bits) + 2;
         s.off[k] = s.pic_bytes;
         s.pic_bytes += round_up((size_t)s.cap[k] + 64, 256);
     }
     return s;
 }
+static_assert(prog_band_bits(0) == 5 * 27 && prog_band_bits(1) == 58 * 27, "the slots of the seven-scan files are what they were");
 
 extern "C" uint64_t jpegamd_max_jfif_bytes_progressive(int32_t width, int32_t height, int32_t subsampling) {
     // The one-scan bound holds every block of every MCU (pad blocks too) at kMaxBlockBitsColor bits -- no less than its DC
@@ -1661,6 +1713,23 @@ extern "C" uint64_t jpegamd_max_jfif_bytes_progressive_optimized(int32_t width, 
     static_assert(2 * 33 + 6 * kProgDhtMax - kStdDhtBytes == 780 && kMaxBlockBitsOptimized <= kMaxBlockBitsColor, "the bound's derivation");
     const uint64_t std_tables = jpegamd_max_jfif_bytes_progressive(width, height, subsampling);
     return std_tables ? std_tables + 780 : 0;
+}
+
+// The ten scans of successive approximation.  A Y block over the scans that touch it: its DC difference at most
+// 16 + 11 bits (scan 1), its DC refinement bit (scan 7), its 63 coefficients in the first scans 2 and 5 at 26 bits each (the
+// reasoning above: a point transform only shortens amplitudes, and either scan's run symbol is paid by its own zero coefficient se),
+// and kMaxBlockBitsRefine in each of the refinement scans 6 and 10: 27 + 1 + 63 x 26 + 2 x 1079 = kMaxBlockBitsSuccessive.  A chroma
+// block has one refinement scan and costs less.  So: the one-scan bound's form -- every block of every MCU, pad blocks too, at
+// that many bits, every byte stuffed, one rounding, EOI, kColorPrefixMax for the head with 432 bytes of DHT and a 14-byte SOS --,
+// nine more roundings that may be stuffed, eight SOS of kSosBytes and one of 14, and the DHT segments of ten tables, 2 x 33 + 8 x
+// kProgDhtMax = 1594 bytes against 432.
+constexpr int kMaxBlockBitsSuccessive = 27 + 1 + 63 * 26 + 2 * kMaxBlockBitsRefine;      // 3824
+extern "C" uint64_t jpegamd_max_jfif_bytes_progressive_successive(int32_t width, int32_t height, int32_t subsampling) {
+    static_assert(kMaxBlockBitsSuccessive == 3824 && 2 * 33 + 8 * kProgDhtMax - kStdDhtBytes == 1162, "the bound's derivation");
+    if (width <= 0 || height <= 0 || width > 65535 || height > 65535 || !sub_valid(subsampling)) return 0;
+    const McuGeometry g = mcu_geometry(width, height, subsampling);
+    const uint64_t blocks = (uint64_t)g.mx * (uint64_t)g.my * (uint64_t)(g.hs * g.vs + 2);
+    return kColorPrefixMax + scan_bound(blocks, kMaxBlockBitsSuccessive) + 2 + 16 + 9 * 2 + 8 * kSosBytes + 14 + 1162;
 }
 
 // The path's scratch for `group` pictures of geometry g: allocated on the first call, grown when a call needs more.
@@ -1748,13 +1817,11 @@ static int32_t prepare_mcu_prefix(JpegAmdEncoder *e, const JpegAmdImage *img, in
 static int32_t prog_alloc(JpegAmdEncoder *e, size_t slot_bytes) {
     auto &m = e->mcu;
     if (!m.pmeta) {
-        HIP_TRY(hipMalloc((void **)&m.pmeta, sizeof(ProgMeta)));
-        uint8_t sos[kProgScans][16] = {};
-        for (int k = 1; k < kProgScans; ++k) {
-            color_sos(1 + (k - 1) % 3, sos[k]);
-            sos[k][7] = (uint8_t)kProgBandSs[(k - 1) / 3]; sos[k][8] = (uint8_t)kProgBandSe[(k - 1) / 3];
-        }
-        HIP_TRY(hipMemcpy(m.pmeta + offsetof(ProgMeta, sos), sos, sizeof(sos), hipMemcpyHostToDevice));
+        HIP_TRY(hipMalloc((void **)&m.pmeta, kProgMetaAlloc));
+        uint8_t sos[2][kProgScansMax][16] = {};
+        for (const ProgScript *sc : {&kScriptSpectral, &kScriptSuccessive})
+            for (int k = 0; k < sc->scans; ++k) prog_sos(sc->scan[k], sos[sc->id][k]);
+        HIP_TRY(hipMemcpy(m.pmeta + kProgMetaSos, sos, sizeof(sos), hipMemcpyHostToDevice));
     }
     return grow_scratch(e, &m.pslots, &m.pslots_cap, slot_bytes);
 }
@@ -1767,20 +1834,22 @@ static int32_t prog_tables_alloc(JpegAmdEncoder *e, int pictures) {
     hipFree(m.pcounts); hipFree(m.pres); hipFree(m.ptabs); hipFree(m.phdr); hipFree(m.phdr_len);
     m.pcounts = nullptr; m.pres = nullptr; m.ptabs = nullptr; m.phdr = nullptr; m.phdr_len = nullptr; m.pcap = 0; m.plast = 0;
     const size_t n = (size_t)pictures;
-    HIP_TRY(hipMalloc((void **)&m.pcounts, n * kProgTables * 256 * sizeof(unsigned long long)));
-    HIP_TRY(hipMalloc((void **)&m.pres, n * kProgTables * kHuffResBytes));
-    HIP_TRY(hipMalloc((void **)&m.ptabs, n * kProgTables * 272 * sizeof(uint32_t)));
-    HIP_TRY(hipMalloc((void **)&m.phdr, n * kProgScans * kMcuPrefixSlot));
-    HIP_TRY(hipMalloc((void **)&m.phdr_len, n * kProgScans * sizeof(uint32_t)));
+    // (room for the longest script: a call lays its pictures out with its own script's numbers)
+    HIP_TRY(hipMalloc((void **)&m.pcounts, n * kProgTablesMax * 256 * sizeof(unsigned long long)));
+    HIP_TRY(hipMalloc((void **)&m.pres, n * kProgTablesMax * kHuffResBytes));
+    HIP_TRY(hipMalloc((void **)&m.ptabs, n * kProgTablesMax * 272 * sizeof(uint32_t)));
+    HIP_TRY(hipMalloc((void **)&m.phdr, n * kProgScansMax * kMcuPrefixSlot));
+    HIP_TRY(hipMalloc((void **)&m.phdr_len, n * kProgScansMax * sizeof(uint32_t)));
     m.pcap = pictures;
     return JPEGAMD_OK;
 }
 
-// Scan k (from 0) of a progressive file as the one-component (k >= 1) form of the group's three-component arguments.
-static bool prog_scan_args(const McuGeometry &g, const McuSegArgs &sa3, int k, McuSegArgs *out) {
-    const int comp = k ? (k - 1) % 3 : 0, band = k ? (k - 1) / 3 : 0;
+// A script's scan as the one-component (comp >= 0) form of the group's three-component arguments.
+static bool prog_scan_args(const McuGeometry &g, const McuSegArgs &sa3, const ProgScan &c, McuSegArgs *out) {
+    const int comp = c.comp;
     McuSegArgs sa = sa3;
-    if (k) {                                                         // ONE component: its plane, its block grid, its table class
+    sa.ah = c.ah; sa.al = c.al;
+    if (comp >= 0) {                                                 // ONE component: its plane, its block grid, its table class
         sa.coef = sa3.coef + (comp == 0 ? 0 : (comp == 1 ? sa3.cb_off : sa3.cr_off));
         sa.bw = sa.mx = comp ? g.mx : g.bw; sa.bh = sa.my = comp ? g.my : g.bh;
         sa.hs = sa.vs = 1; sa.comps = 1;
@@ -1789,7 +1858,7 @@ static bool prog_scan_args(const McuGeometry &g, const McuSegArgs &sa3, int k, M
         sa.num_segs_pad = (sa.num_segs + kSegGroup - 1) / kSegGroup * kSegGroup;
         if (sa.num_segs_pad > g.num_segs_pad) return false;         // (a plane has fewer segments than the MCU scan: the arrays hold them)
         if (comp) sa.huff_y = sa3.huff_c;
-        sa.ss = kProgBandSs[band]; sa.se = kProgBandSe[band];
+        sa.ss = c.ss; sa.se = c.se;
     }
     *out = sa;
     return true;
@@ -1799,38 +1868,53 @@ static bool prog_scan_args(const McuGeometry &g, const McuSegArgs &sa3, int k, M
 // make all the tables and headers at once (the counts of a scan with runs do not depend on a table, so nothing of a later scan waits
 // for an earlier one), then code scan by scan over the path's one set of segment arrays and let the restart writer -- one interval, a
 // header per picture, no EOI but behind the last scan -- place each: scan 1 in the caller's buffers, the others in the slots.
-static int progressive_runs_scans(JpegAmdEncoder *e, const McuGeometry &g, const ProgSlots &slots, const McuSegArgs &sa3, int first, int n, int count,
-                                  bool last_of_call, void *const *outs_dev, uint64_t out_capacity, uint64_t *const *out_sizes_dev,
+// `sc`: the file's scan script -- the seven scans of 4.6.13, or the ten of successive approximation (4.6.14), whose scan of raw bits
+// is not counted and gets a header of its SOS alone.
+static int progressive_runs_scans(JpegAmdEncoder *e, const McuGeometry &g, const ProgScript &sc, const ProgSlots &slots, const McuSegArgs &sa3, int first, int n,
+                                  int count, bool last_of_call, void *const *outs_dev, uint64_t out_capacity, uint64_t *const *out_sizes_dev,
                                   const unsigned long long *pic, hipStream_t stream) {
     auto &m = e->mcu;
-    ProgMeta *meta = reinterpret_cast<ProgMeta *>(m.pmeta);
-    if (hipMemsetAsync(m.pmeta, 0, offsetof(ProgMeta, sos), stream) != hipSuccess) return (int)hipErrorUnknown;
-    unsigned long long *counts = m.pcounts + (size_t)first * kProgTables * 256;
-    if (hipMemsetAsync(counts, 0, (size_t)n * kProgTables * 256 * sizeof(unsigned long long), stream) != hipSuccess) return (int)hipErrorUnknown;
-    McuSegArgs sa[kProgScans];
-    for (int k = 0; k < kProgScans; ++k) {
-        if (!prog_scan_args(g, sa3, k, &sa[k])) return (int)hipErrorInvalidValue;
-        if (int err = launch_mcu_band_histogram(sa[k], counts, k ? k + 1 : 0, stream)) return err;
+    const ProgMeta meta = prog_meta(m.pmeta, sc.scans);
+    const size_t tables = (size_t)sc.tables;
+    if (hipMemsetAsync(m.pmeta, 0, meta.record_bytes, stream) != hipSuccess) return (int)hipErrorUnknown;
+    unsigned long long *counts = m.pcounts + (size_t)first * tables * 256;
+    if (hipMemsetAsync(counts, 0, (size_t)n * tables * 256 * sizeof(unsigned long long), stream) != hipSuccess) return (int)hipErrorUnknown;
+    McuSegArgs sa[kProgScansMax];
+    for (int k = 0; k < sc.scans; ++k) {
+        if (!prog_scan_args(g, sa3, sc.scan[k], &sa[k])) return (int)hipErrorInvalidValue;
+        if (sc.scan[k].table < 0) continue;
+        if (int err = launch_mcu_band_histogram(sa[k], counts, sc.scan[k].table, sc.tables, stream)) return err;
     }
     HuffOptimalArgs ha;
     std::memset(&ha, 0, sizeof(ha));
-    ha.freq = counts; ha.jobs = kProgTables * n;
-    ha.res = m.pres + (size_t)first * kProgTables * kHuffResBytes;
+    ha.freq = counts; ha.jobs = sc.tables * n;
+    ha.res = m.pres + (size_t)first * tables * kHuffResBytes;
     if (int err = launch_huff_optimal(ha, stream)) return err;
     ProgTablesArgs pa;
     std::memset(&pa, 0, sizeof(pa));
-    pa.res = ha.res; pa.tabs = m.ptabs + (size_t)first * kProgTables * 272;
+    pa.res = ha.res; pa.tabs = m.ptabs + (size_t)first * tables * 272;
     pa.hdr_out = m.phdr; pa.hdr_len = m.phdr_len; pa.pictures = count; pa.first = first;
-    pa.hdr = m.hdr; pa.sos_off = m.hdr_for.len - kMcuSosBytes; pa.head_len = pa.sos_off - kStdDhtBytes;
-    pa.sos = &meta->sos[0][0];
+    pa.hdr = m.hdr; pa.head_len = m.hdr_for.len - kMcuSosBytes - kStdDhtBytes;
+    pa.sos = prog_meta_sos(m.pmeta, sc);
+    pa.scans = sc.scans; pa.tables = sc.tables;
+    for (int k = 0; k < sc.scans; ++k) {
+        const ProgScan &c = sc.scan[k];
+        pa.sos_len[k] = (uint8_t)(c.comp < 0 ? kMcuSosBytes : kSosBytes);
+        if (c.table < 0) { pa.bare |= 1u << k; continue; }
+        for (int t = c.table; t < c.table + (c.comp < 0 ? 2 : 1); ++t) {
+            pa.table_scan[t] = (uint8_t)k;
+            pa.table_id[t] = (uint8_t)(c.comp < 0 ? t - c.table : (c.comp == 0 ? 0x10 : 0x11));
+        }
+    }
     if (int err = launch_prog_tables(pa, n, stream)) return err;
 
-    for (int k = 0; k < kProgScans; ++k) {
+    for (int k = 0; k < sc.scans; ++k) {
         McuSegArgs &s = sa[k];
-        s.huff_y = pa.tabs + (k ? (size_t)(k + 1) * 272 : 0); s.huff_c = pa.tabs + 272; s.huff_stride = kProgTables * 272;
+        const int table = sc.scan[k].table < 0 ? 0 : sc.scan[k].table;   // (a scan of raw bits reads no table: any that exists)
+        s.huff_y = pa.tabs + (size_t)table * 272; s.huff_c = pa.tabs + (size_t)(table + (sc.scan[k].comp < 0 ? 1 : 0)) * 272; s.huff_stride = (uint32_t)(tables * 272);
         s.runs = 1;
-        s.sums = &meta->sums[k][0][0];
-        s.status = &meta->scan_stats[k ? 1 : 0].status;
+        s.sums = meta.sums + (size_t)k * kMaxBatch * 2;
+        s.status = &meta.scan_stats[k ? 1 : 0].status;
         if (int err = launch_mcu_band_segments(s, stream)) return err;
         McuRestartArgs ra;
         std::memset(&ra, 0, sizeof(ra));
@@ -1838,15 +1922,15 @@ static int progressive_runs_scans(JpegAmdEncoder *e, const McuGeometry &g, const
         ra.num_segs_pad = s.num_segs_pad; ra.batch = n;
         ra.segs_per_interval = s.num_segs; ra.intervals = 1; ra.last_seg = s.num_segs - 1;       // the scan is its one interval
         ra.pre = m.rst_words; ra.b0 = m.rst_words + m.rst_cap; ra.ff = m.rst_words + 2 * m.rst_cap;
-        ra.pos = m.rst_pos; ra.pic_sums = &meta->writer_sums[k][0][0];
+        ra.pos = m.rst_pos; ra.pic_sums = meta.writer_sums + (size_t)k * kMaxBatch * kMcuPicSums;
         for (int i = 0; i < n; ++i) {
             ra.out[i] = k ? m.pslots + (size_t)i * slots.pic_bytes + slots.off[k] : (uint8_t *)outs_dev[first + i];
-            ra.out_size[i] = &meta->size[k][i];
+            ra.out_size[i] = meta.size + (size_t)k * kMaxBatch + i;
         }
         ra.out_capacity = k ? slots.cap[k] : out_capacity;
         ra.pic_prefix = m.phdr + ((size_t)k * count + (size_t)first) * kMcuPrefixSlot; ra.pic_prefix_len = m.phdr_len + (size_t)k * count + first;
         ra.pic_prefix_stride = kMcuPrefixSlot;
-        ra.no_eoi = k == kProgScans - 1 ? 0 : 1;
+        ra.no_eoi = k == sc.scans - 1 ? 0 : 1;
         if (int err = launch_mcu_restart_writer(ra, stream)) return err;
     }
     ScansConcatArgs ca;
@@ -1854,13 +1938,14 @@ static int progressive_runs_scans(JpegAmdEncoder *e, const McuGeometry &g, const
     for (int i = 0; i < n; ++i) { ca.out[i] = (uint8_t *)outs_dev[first + i]; ca.out_size[i] = out_sizes_dev[first + i]; }
     ca.out_capacity = out_capacity;
     ca.batch = n; ca.prefix_len = 0; ca.last_of_call = last_of_call ? 1 : 0;
-    ca.size = &meta->size[0][0];
+    ca.scans = sc.scans;
+    ca.size = meta.size;
     ca.slots = m.pslots; ca.pic_bytes = slots.pic_bytes;
-    for (int k = 0; k < kProgScans; ++k) ca.slot_off[k] = slots.off[k];
-    ca.sums = &meta->sums[0][0][0];
-    ca.writer_sums = &meta->writer_sums[0][0][0];
+    for (int k = 0; k < sc.scans; ++k) ca.slot_off[k] = slots.off[k];
+    ca.sums = meta.sums;
+    ca.writer_sums = meta.writer_sums;
     ca.pic = pic;
-    ca.scan_stats = meta->scan_stats; ca.stats = e->stats_dev;
+    ca.scan_stats = meta.scan_stats; ca.stats = e->stats_dev;
     return launch_scans_concat(ca, stream);
 }
 
@@ -1872,13 +1957,15 @@ static int progressive_scans(JpegAmdEncoder *e, const McuGeometry &g, const Prog
                              int n, bool last_of_call, void *const *outs_dev, uint64_t out_capacity, uint64_t *const *out_sizes_dev,
                              const unsigned long long *pic, hipStream_t stream) {
     auto &m = e->mcu;
-    ProgMeta *meta = reinterpret_cast<ProgMeta *>(m.pmeta);
-    if (hipMemsetAsync(m.pmeta, 0, offsetof(ProgMeta, sos), stream) != hipSuccess) return (int)hipErrorUnknown;
-    for (int k = 0; k < kProgScans; ++k) {
+    const ProgScript &sc = kScriptSpectral;                          // (k_finalize knows no per-picture header: the script with the Annex K tables alone)
+    const ProgMeta meta = prog_meta(m.pmeta, sc.scans);
+    const uint8_t *sos = prog_meta_sos(m.pmeta, sc);
+    if (hipMemsetAsync(m.pmeta, 0, meta.record_bytes, stream) != hipSuccess) return (int)hipErrorUnknown;
+    for (int k = 0; k < sc.scans; ++k) {
         McuSegArgs sa;
-        if (!prog_scan_args(g, sa3, k, &sa)) return (int)hipErrorInvalidValue;
-        sa.sums = &meta->sums[k][0][0];
-        sa.status = &meta->scan_stats[k ? 1 : 0].status;
+        if (!prog_scan_args(g, sa3, sc.scan[k], &sa)) return (int)hipErrorInvalidValue;
+        sa.sums = meta.sums + (size_t)k * kMaxBatch * 2;
+        sa.status = &meta.scan_stats[k ? 1 : 0].status;
         if (int err = launch_mcu_band_segments(sa, stream)) return err;
 
         ImageDesc is = iy;                                               // what run_finalize reads of it: the segments per picture and their length
@@ -1887,9 +1974,9 @@ static int progressive_scans(JpegAmdEncoder *e, const McuGeometry &g, const Prog
         uint64_t *sizes[kMaxBatch];
         for (int i = 0; i < n; ++i) {
             outs[i] = k ? (void *)(m.pslots + (size_t)i * slots.pic_bytes + slots.off[k]) : outs_dev[first + i];
-            sizes[i] = &meta->size[k][i];
+            sizes[i] = meta.size + (size_t)k * kMaxBatch + i;
         }
-        const ScanTarget tgt = {k ? meta->sos[k] : m.hdr, k ? kSosBytes : m.hdr_for.len, k == kProgScans - 1 ? 1 : 0, &meta->scan_stats[k ? 1 : 0], false, &m.seg};
+        const ScanTarget tgt = {k ? sos + 16 * k : m.hdr, k ? kSosBytes : m.hdr_for.len, k == sc.scans - 1 ? 1 : 0, &meta.scan_stats[k ? 1 : 0], false, &m.seg};
         if (int err = run_finalize(e, is, outs, k ? slots.cap[k] : out_capacity, sizes, 1, stream, nullptr, n, false, &tgt)) return err;
     }
     ScansConcatArgs ca;
@@ -1897,12 +1984,13 @@ static int progressive_scans(JpegAmdEncoder *e, const McuGeometry &g, const Prog
     for (int i = 0; i < n; ++i) { ca.out[i] = (uint8_t *)outs_dev[first + i]; ca.out_size[i] = out_sizes_dev[first + i]; }
     ca.out_capacity = out_capacity;
     ca.batch = n; ca.prefix_len = m.hdr_for.len; ca.last_of_call = last_of_call ? 1 : 0;
-    ca.size = &meta->size[0][0];
+    ca.scans = sc.scans;
+    ca.size = meta.size;
     ca.slots = m.pslots; ca.pic_bytes = slots.pic_bytes;
-    for (int k = 0; k < kProgScans; ++k) ca.slot_off[k] = slots.off[k];
-    ca.sums = &meta->sums[0][0][0];
+    for (int k = 0; k < sc.scans; ++k) ca.slot_off[k] = slots.off[k];
+    ca.sums = meta.sums;
     ca.pic = pic;
-    ca.scan_stats = meta->scan_stats; ca.stats = e->stats_dev;
+    ca.scan_stats = meta.scan_stats; ca.stats = e->stats_dev;
     return launch_scans_concat(ca, stream);
 }
 
@@ -1921,7 +2009,9 @@ static int32_t interleaved_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, cons
     // (progressive_scans) in place of k_mcu_segments, k_finalize and k_mcu_totals.  Colour, the Annex K tables, no restart intervals.
     // kProgRuns: histograms, tables and the restart writer as well (progressive_runs_scans); the context's Huffman
     // mode is neither read nor changed.
-    const bool runs = progressive == kProgRuns;
+    // kProgSuccessive: kProgRuns' steps over the script of ten scans.
+    const bool runs = progressive >= kProgRuns;
+    const ProgScript &script = prog_script(progressive);
     if (progressive && (restart || subsampling == kSubNone || (!runs && e->huffman != JPEGAMD_HUFFMAN_STANDARD))) return JPEGAMD_ERR_ARG;
     const bool mx = ycc_in && ycc_in->matrix == JPEGAMD_MATRIX_BT709;
     const YccSource *const ycc = mx ? nullptr : ycc_in;               // what the launches read: the caller's planes, or the scratch
@@ -1950,7 +2040,7 @@ static int32_t interleaved_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, cons
     if (rc) return rc;
     if (iy.blocks_w != g.bw || iy.blocks_h != g.bh || (!gray && (ic.blocks_w != g.mx || ic.blocks_h != g.my))) return JPEGAMD_ERR_ARG;
 
-    const ProgSlots slots = progressive ? prog_slots(g, runs) : ProgSlots{};
+    const ProgSlots slots = progressive ? prog_slots(g, script, runs) : ProgSlots{};
     const size_t per_pic = (size_t)mcu_scratch_per_pic(g, writer) + (size_t)slots.pic_bytes;
     const int group = (int)std::max<size_t>(1, std::min<size_t>((size_t)count, kMcuScratchBudget / per_pic));
     rc = color_alloc_consts(e);
@@ -2029,7 +2119,7 @@ static int32_t interleaved_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, cons
         sa.restart = restart; sa.segs_per_interval = restart ? g.segs_per_interval : 0;
         sa.comps = g.comps;
         if (progressive) {
-            if (runs ? progressive_runs_scans(e, g, slots, sa, first, n, count, first + n == count, outs_dev, out_capacity, out_sizes_dev,
+            if (runs ? progressive_runs_scans(e, g, script, slots, sa, first, n, count, first + n == count, outs_dev, out_capacity, out_sizes_dev,
                                               pic + (size_t)first * kPicStatWords, stream)
                      : progressive_scans(e, g, slots, sa, iy, first, n, first + n == count, outs_dev, out_capacity, out_sizes_dev,
                                          pic + (size_t)first * kPicStatWords, stream))
@@ -2091,7 +2181,7 @@ static int32_t interleaved_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, cons
         if (launch_mcu_totals(ta, n, stream)) return JPEGAMD_ERR_HIP;
     }
     if (optimized) m.hlast = count;
-    if (runs) m.plast = count;
+    if (runs) { m.plast = count; m.plast_tables = script.tables; }
     if (cev) HIP_TRY(hipEventRecord(cev[21], stream));
     return enqueued(e, stream, count * g.num_segs_pad, cev != nullptr, true);
 }
@@ -2192,12 +2282,28 @@ extern "C" int32_t jpegamd_encode_color_progressive_optimized_batch_async(JpegAm
 
 // Tests: the symbol counts of the context's last call with per-scan tables, [pictures][8][256] in the file's table order: Y DC,
 // chroma DC, then the AC tables of the scans 2 .. 7.  JPEGAMD_ERR_ARG when the context made no such call.  Synchronous.
-extern "C" int32_t jpegamd_debug_progressive_counts(JpegAmdEncoder *e, uint64_t *counts) {
-    if (!e || !counts || e->mcu.plast < 1) return JPEGAMD_ERR_ARG;
+static int32_t debug_prog_counts(JpegAmdEncoder *e, uint64_t *counts, int tables) {
+    if (!e || !counts || e->mcu.plast < 1 || e->mcu.plast_tables != tables) return JPEGAMD_ERR_ARG;
     if (int32_t rc = wait_pending(e)) return rc;
     static_assert(sizeof(uint64_t) == sizeof(unsigned long long), "the counts are copied as they lie");
-    HIP_TRY(hipMemcpy(counts, e->mcu.pcounts, (size_t)e->mcu.plast * kProgTables * 256 * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(counts, e->mcu.pcounts, (size_t)e->mcu.plast * (size_t)tables * 256 * sizeof(uint64_t), hipMemcpyDeviceToHost));
     return JPEGAMD_OK;
+}
+extern "C" int32_t jpegamd_debug_progressive_counts(JpegAmdEncoder *e, uint64_t *counts) { return debug_prog_counts(e, counts, kScriptSpectral.tables); }
+
+// Progressive files with successive approximation: the ten scans of libjpeg's jpeg_simple_progression, a table per
+// scan, end-of-band runs.  The arguments, refusals, batching, capacity behaviour and statistics of the entry above; the context's
+// Huffman mode is not read.
+extern "C" int32_t jpegamd_encode_color_progressive_successive_batch_async(JpegAmdEncoder *e, const JpegAmdImage *imgs, int32_t count, int32_t subsampling,
+                                                                           void *const *outs_dev, uint64_t out_capacity, uint64_t *const *out_sizes_dev,
+                                                                           void *stream_) {
+    return interleaved_pixels(e, imgs, count, subsampling, 0, true, outs_dev, out_capacity, out_sizes_dev, stream_, kProgSuccessive);
+}
+
+// Tests: the symbol counts of the context's last call of the successive entries, [pictures][10][256] in the file's table order.
+// JPEGAMD_ERR_ARG when the context's last call with per-scan tables was not one of them.  Synchronous.
+extern "C" int32_t jpegamd_debug_progressive_successive_counts(JpegAmdEncoder *e, uint64_t *counts) {
+    return debug_prog_counts(e, counts, kScriptSuccessive.tables);
 }
 
 extern "C" int32_t jpegamd_encode_color_interleaved_restart_batch_async(JpegAmdEncoder *e, const JpegAmdImage *imgs, int32_t count, int32_t subsampling,
@@ -2317,6 +2423,19 @@ extern "C" int32_t jpegamd_encode_ycbcr_progressive_optimized_batch_async(JpegAm
     if (int32_t rc = ycbcr_args(e, imgs, count, subsampling, sample_range, sample_format, matrix, outs_dev, out_sizes_dev, true, &g0, &ps, &ycc, sizes))
         return rc;
     return interleaved_batch(e, g0, ps, count, subsampling, 0, outs_dev, out_capacity, sizes, stream_, &ycc, kProgRuns);
+}
+
+extern "C" int32_t jpegamd_encode_ycbcr_progressive_successive_batch_async(JpegAmdEncoder *e, const JpegAmdYCbCrImage *imgs, int32_t count, int32_t subsampling,
+                                                                           int32_t sample_range, int32_t sample_format, int32_t matrix,
+                                                                           void *const *outs_dev, uint64_t out_capacity, void *const *out_sizes_dev,
+                                                                           void *stream_) {
+    JpegAmdImage g0;
+    PlaneSet ps;
+    YccSource ycc;
+    uint64_t *sizes[kMaxBatch];
+    if (int32_t rc = ycbcr_args(e, imgs, count, subsampling, sample_range, sample_format, matrix, outs_dev, out_sizes_dev, true, &g0, &ps, &ycc, sizes))
+        return rc;
+    return interleaved_batch(e, g0, ps, count, subsampling, 0, outs_dev, out_capacity, sizes, stream_, &ycc, kProgSuccessive);
 }
 
 // Host-only (tests): whether the plain build has the k_tile_encode instantiation (taps, layout, chroma tables, expand): 1 or 0.  No

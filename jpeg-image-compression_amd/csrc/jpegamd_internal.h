@@ -419,8 +419,10 @@ struct McuSegArgs {
     int32_t ss, se;                     // the band, uniform over the launch: 0, 0 the DC scan (comps = 3), 1 <= ss <= se <= 63 an AC scan (comps = 1)
     unsigned long long *sums;           // [batch][2]: every segment's bits and symbols are ADDED to its picture's pair (the caller zeroed them)
     int32_t runs;                       // an AC scan with end-of-band runs and the pictures' own tables (huff_stride > 0); the DC scan: its own tables
-};
-int launch_mcu_segments(const McuSegArgs &a, void *stream);
+    // successive approximation (`runs` alone): ah = 0, al > 0 a first scan over the point transform by al; ah = al + 1
+    // a refinement scan that codes bit al.  0, 0: the scans of 4.6.12 / 4.6.13.  (They lie in what was the struct's padding.)
+    uint8_t ah, al;
+};int launch_mcu_segments(const McuSegArgs &a, void *stream);
 
 // Progressive colour files: kProgScans scans by spectral selection, Ah = Al = 0 -- the DC scan of the three
 // components in MCU order (the segments, pad blocks and predictors of the one-scan file), then the bands 1 .. 5 and 6 .. 63 of Y, Cb
@@ -431,6 +433,7 @@ int launch_mcu_segments(const McuSegArgs &a, void *stream);
 // A block of a band is at most 27 bits per coefficient of the band (a ZRL pays for sixteen zeros, EOB for a zero coefficient se),
 // a DC difference at most 11 + 11 bits: together no more than kMaxBlockBitsColor, the bound of a whole block.
 constexpr int kProgScans = 7;
+constexpr int kProgScansMax = 10, kProgTablesMax = 10;          // the most scans and tables a scan script has; the kernels take the counts at run time
 constexpr int kProgBandSs[2] = {1, 6}, kProgBandSe[2] = {5, 63};
 constexpr int prog_band_bits(int band) { return (kProgBandSe[band] - kProgBandSs[band] + 1) * 27; }
 static_assert(22 + prog_band_bits(0) + prog_band_bits(1) == kMaxBlockBitsColor, "the three bands of a block cost no more than the block's bound");
@@ -442,15 +445,16 @@ struct ScansConcatArgs {
     int32_t batch;
     int32_t prefix_len;                 // bytes in front of scan 1's entropy-coded segment: the file's prefix with SOS 1
     int32_t last_of_call;               // the launch's last picture is the call's last: its size is what finish reports
-    const uint64_t *size;               // [kProgScans][kMaxBatch] k_finalize's: scan 1 with the prefix, the others with their SOS, the last with EOI
+    int32_t scans;                      // the file's scans: 2 .. kProgScansMax
+    const uint64_t *size;               // [scans][kMaxBatch] k_finalize's: scan 1 with the prefix, the others with their SOS, the last with EOI
     const uint8_t *slots;               // scan k >= 1 (from 0) of picture q at slots + q pic_bytes + slot_off[k]; multiples of 16
-    uint64_t pic_bytes, slot_off[kProgScans];
-    const unsigned long long *sums;     // [kProgScans][kMaxBatch][2] coded bits and symbols (launch_mcu_band_segments)
+    uint64_t pic_bytes, slot_off[kProgScansMax];
+    const unsigned long long *sums;     // [scans][kMaxBatch][2] coded bits and symbols (launch_mcu_band_segments)
     const unsigned long long *pic;      // k_picture_stats' words of THESE pictures
     const ScanStats *scan_stats;        // [2] k_finalize's records: scan 1's, and the one the scans into slots share
     ScanStats *stats;                   // the context's record, whose sums the caller zeroed
     // the scans went through the restart writer: `size` is k_mcu_restart_offsets' -- every scan with ITS header, the
-    // last with EOI --, and the stuffed bytes are word 2 of its sums, [kProgScans][kMaxBatch][kMcuPicSums]; null: k_finalize's scans
+    // last with EOI --, and the stuffed bytes are word 2 of its sums, [scans][kMaxBatch][kMcuPicSums]; null: k_finalize's scans
     const unsigned long long *writer_sums;
 };
 int launch_scans_concat(const ScansConcatArgs &a, void *stream);
@@ -459,17 +463,24 @@ int launch_scans_concat(const ScansConcatArgs &a, void *stream);
 // one scan (the coder's walks, no table read) into counts [pictures][kProgTables][256], which the caller zeroed; k_huff_optimal makes
 // BITS / HUFFVAL of all of them in one launch (its `freq` form: the counts ARE kProgTables x pictures jobs of 256 symbols);
 // k_prog_tables makes the coder's tables and every scan's header -- DHT segment(s) + SOS, scan 1's behind the file's head -- of them.
+// With successive approximation the scans and tables are a script's: `tables` tables per picture in `counts`,
+// and the launches below take the script's numbers -- the seven-scan file's are kProgScans and kProgTables.
 constexpr int kProgTables = 8;
-int launch_mcu_band_histogram(const McuSegArgs &a, unsigned long long *counts, int table, void *stream);
+int launch_mcu_band_histogram(const McuSegArgs &a, unsigned long long *counts, int table, int tables, void *stream);
 struct ProgTablesArgs {
-    const uint8_t *res;                 // [launch pictures][kProgTables][kHuffResBytes] k_huff_optimal's
-    uint32_t *tabs;                     // [launch pictures][kProgTables][272]
+    const uint8_t *res;                 // [launch pictures][tables][kHuffResBytes] k_huff_optimal's
+    uint32_t *tabs;                     // [launch pictures][tables][272]
     uint8_t *hdr_out;                   // scan k (from 0) of picture p of the CALL at hdr_out + (k pictures + p) kMcuPrefixSlot
-    uint32_t *hdr_len;                  // [kProgScans][pictures]
+    uint32_t *hdr_len;                  // [scans][pictures]
     int32_t pictures, first;            // pictures of the call; the launch's first
-    const uint8_t *hdr;                 // the standard progressive prefix: head, the Annex K DHTs, the DC scan's SOS
-    int32_t head_len, sos_off;
-    const uint8_t *sos;                 // the SOS of scan k >= 1 (from 0) at sos + 16 k
+    const uint8_t *hdr;                 // the standard progressive prefix: its head (SOI .. SOF2) is the file's
+    int32_t head_len;
+    const uint8_t *sos;                 // the SOS of scan k (from 0) at sos + 16 k, sos_len[k] bytes
+    int32_t scans, tables;              // the script's: <= kProgScansMax, 2 .. kProgTablesMax
+    uint32_t bare;                      // bit k: scan k has no table -- its header is its SOS alone
+    uint8_t table_scan[kProgTablesMax]; // the scan (from 0) of table t: non-decreasing, tables 0 and 1 the DC tables of scan 0
+    uint8_t table_id[kProgTablesMax];   // its Tc/Th byte
+    uint8_t sos_len[kProgScansMax];
 };
 int launch_prog_tables(const ProgTablesArgs &a, int batch, void *stream);
 // The writer of a file with restart intervals: two launches in place of k_finalize (which knows neither the 1-bit padding of an
@@ -538,6 +549,12 @@ constexpr int kStdDhtBytesGray = 216;   // the two of a one-component file: K.3 
 constexpr int kMaxBlockBitsOptimized = 27 + 63 * 26;                 // 1665
 static_assert(kMaxBlockBitsOptimized <= kMaxBlockBitsColor && (kSegBlocks * kMaxBlockBitsOptimized + 31) / 32 + 1 <= mcu_restart_cap_words(kSegBlocks),
               "a segment of 256 blocks in either Huffman mode fits its string");
+// Successive approximation.  A first scan codes shifted values: the sizes only shrink, so its block is within
+// kMaxBlockBitsOptimized.  A block of an AC refinement scan: a new coefficient costs a symbol and its sign, 16 + 1 bits; an old one its
+// correction bit; sixteen zeros a ZRL of at most 16 bits -- a bit each; the run's symbol 16 + 8 bits, and only a block whose
+// coefficient se is not new (it costs at most 1 bit) starts one: 62 x 17 + max(17, 1 + 24).  A block of the DC refinement scan: 1 bit.
+constexpr int kMaxBlockBitsRefine = 62 * 17 + 25;                    // 1079
+static_assert(kMaxBlockBitsRefine <= kMaxBlockBitsOptimized, "one block's string in any single scan fits the reservation of a segment");
 struct HuffOptimalArgs {
     const unsigned long long *counts;   // [pictures][2][272], or null
     const unsigned long long *freq;     // [jobs][256], or null

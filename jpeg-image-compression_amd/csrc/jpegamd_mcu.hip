@@ -29,6 +29,9 @@
 // ... with end-of-band runs and a table per scan: the band walk without end symbols plus mcu_band_runs
 // (kWalkBandRuns), k_mcu_band_histogram counting what that walk codes, k_huff_optimal over all eight tables of a picture at once,
 // k_prog_tables making the coder's tables and every scan's DHT + SOS, and the restart writer placing each scan behind its header.
+// ... with successive approximation: four more walks -- the DC and a band by a point transform, one bit of the DC,
+// one bit of a band (T.81 G.1.2.3) --, raw bits through an outlet of their own that the counting kernel does not see, and a scan and
+// table count that k_prog_tables and k_scans_concat take at run time.
 #include <algorithm>
 
 #include <hip/hip_ext.h>
@@ -104,8 +107,9 @@ __device__ __forceinline__ uint32_t mcu_band_mask(int j0, int lo, int hi) {
 // whole block's (the same symbols at most, one per coefficient, a ZRL per sixteen zeros, an EOB for a zero coefficient se).
 // kRuns: nothing is emitted for the trailing zeros -- the caller codes end-of-band runs over the blocks of a
 // segment (mcu_band_runs).  Returns whether coefficient se is zero.  Tab: a coder table, or McuSymbolTab to count symbols.
-template <bool kRuns = false, class Tab, class Emit>
-__device__ __forceinline__ bool mcu_walk_band(const uint4 *__restrict__ p, int ss, int se, const Tab &tab, Emit &&emit) {
+// kPoint: the walk is over v = sign(c) (|c| >> al), the first scan of a band cut by successive approximation.
+template <bool kRuns = false, bool kPoint = false, class Tab, class Emit>
+__device__ __forceinline__ bool mcu_walk_band(const uint4 *__restrict__ p, int ss, int se, const Tab &tab, Emit &&emit, [[maybe_unused]] int al = 0) {
     const uint32_t eob = kRuns ? 0u : tab[0x00], zrl = tab[0xF0];
     const int q1 = se >> 3;
     uint32_t run = 0u - (uint32_t)(ss & 7);
@@ -122,7 +126,8 @@ __device__ __forceinline__ bool mcu_walk_band(const uint4 *__restrict__ p, int s
         const uint32_t w4[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
-            const int c = (int)(short)((w4[i >> 1] >> (16 * (i & 1))) & 0xFFFFu);
+            int c = (int)(short)((w4[i >> 1] >> (16 * (i & 1))) & 0xFFFFu);
+            if constexpr (kPoint) c = c < 0 ? -((-c) >> al) : c >> al;
             if (c == 0) { ++run; continue; }
             while (run >= 16u) { emit(zrl & 0xFFFFu, zrl >> 16); run -= 16u; }
             const uint32_t nb = mcu_size(c), t = tab[((run << 4) | nb) & 0xFFu];
@@ -133,13 +138,98 @@ __device__ __forceinline__ bool mcu_walk_band(const uint4 *__restrict__ p, int s
     // coefficient se itself, of the last group's words (`run` also counts the zeros masked behind se)
     const int i = se & 7;
     const uint32_t w = (i & 4) ? ((i & 2) ? v.w : v.z) : ((i & 2) ? v.y : v.x);
-    const bool end_zero = (((i & 1) ? w >> 16 : w) & 0xFFFFu) == 0u;
+    bool end_zero = (((i & 1) ? w >> 16 : w) & 0xFFFFu) == 0u;
+    if constexpr (kPoint) { const int c = (int)(short)(((i & 1) ? w >> 16 : w) & 0xFFFFu); end_zero = ((c < 0 ? -c : c) >> al) == 0; }
     if (!kRuns && end_zero) emit(eob & 0xFFFFu, eob >> 16);
     return end_zero;
 }
 
-// what a coder launch codes of a block: all of it, its DC, a band of its AC, a band of its AC with end-of-band runs
-constexpr int kWalkBlock = 0, kWalkDc = 1, kWalkBand = 2, kWalkBandRuns = 3;
+// ---- the walks of successive approximation (T.81 G.1.2.1 and G.1.2.3 as libjpeg carries them out) ------------------
+// A walk has two outlets: emit(code word with the bits that belong to it, count) for what a Huffman table codes -- the counting
+// kernel sees these alone, through McuSymbolTab -- and raw(bits, count <= 32) for correction bits and the DC refinement bit.
+// The first DC scan: the difference of DC >> al (an arithmetic shift) to the shifted DC in front.
+template <class Tab, class Emit>
+__device__ __forceinline__ void mcu_walk_dc_point(const uint4 *__restrict__ p, int pred, int al, const Tab &tab, Emit &&emit) {
+    const int diff = ((int)*reinterpret_cast<const int16_t *>(p) >> al) - (pred >> al);
+    const uint32_t nb = mcu_size(diff), t = tab[256u + (nb & 15u)];
+    emit(((t & 0xFFFFu) << nb) | mcu_amp(diff, nb), (t >> 16) + nb);
+}
+// The DC refinement scan: bit al of the DC, no table.
+template <class Raw>
+__device__ __forceinline__ void mcu_walk_dc_refine(const uint4 *__restrict__ p, int al, Raw &&raw) {
+    raw(((uint32_t)(int)*reinterpret_cast<const int16_t *>(p) >> al) & 1u, 1u);
+}
+
+// `n` <= 64 bits, right-aligned in `bits`, through an outlet that takes at most 32 a call.
+template <class Raw>
+__device__ __forceinline__ void mcu_raw64(unsigned long long bits, uint32_t n, Raw &&raw) {
+    if (n > 32u) { raw((uint32_t)(bits >> 32) & (0xFFFFFFFFu >> (64u - n)), n - 32u); raw((uint32_t)bits, 32u); }
+    else if (n) raw((uint32_t)bits & (0xFFFFFFFFu >> (32u - n)), n);
+}
+
+// An AC refinement scan of the band ss .. se that codes bit al: a[k] = |c[k]| >> al, a coefficient is NEW if a = 1, OLD if a > 1.
+// The block's string is head, the symbol of the run it starts (`run` blocks: the caller knows it in its second pass, 0 for none and
+// in a pass that only measures -- the symbol's place does not change a length), tail.  Head, k = ss .. K (the last new k): r counts
+// zeros, B collects the bits a & 1 of old coefficients; at every non-zero coefficient, while r > 15: ZRL, B; an old coefficient adds
+// its bit to B; a new one codes (r << 4) | 1, its sign bit (1: positive) and B.  Tail: the bits of the old coefficients behind K.
+// The data: 64-bit masks of new, old and value bits (sign of a new, a & 1 of an old coefficient) built from the band's 16-byte groups,
+// walked with ctz; B and the tail are a 64-bit register each (at most 63 bits), no scratch.
+// Returns bit 0: E, a[se] != 1 -- bit 1: Z, the band has no new coefficient.
+template <class Tab, class Emit, class Raw>
+__device__ __forceinline__ uint32_t mcu_walk_band_refine(const uint4 *__restrict__ p, int ss, int se, int al, uint32_t run, const Tab &tab, Emit &&emit, Raw &&raw) {
+    unsigned long long newm = 0ull, oldm = 0ull, valm = 0ull;
+    const int q1 = se >> 3;
+#pragma unroll 1
+    for (int q = ss >> 3; q <= q1; ++q) {
+        const uint4 v = p[q];
+        if ((v.x | v.y | v.z | v.w) == 0u) continue;
+        const uint32_t w4[4] = {v.x, v.y, v.z, v.w};
+        uint32_t n8 = 0, o8 = 0, v8 = 0;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const int c = (int)(short)((w4[i >> 1] >> (16 * (i & 1))) & 0xFFFFu);
+            const uint32_t a = (uint32_t)(c < 0 ? -c : c) >> al;
+            n8 |= (a == 1u ? 1u : 0u) << i;
+            o8 |= (a > 1u ? 1u : 0u) << i;
+            v8 |= (a == 1u ? (c > 0 ? 1u : 0u) : (a & 1u)) << i;
+        }
+        newm |= (unsigned long long)n8 << (8 * q); oldm |= (unsigned long long)o8 << (8 * q); valm |= (unsigned long long)v8 << (8 * q);
+    }
+    const unsigned long long band = (~0ull << ss) & (~0ull >> (63 - se));
+    newm &= band; oldm &= band;
+    const uint32_t flags = (((newm >> se) & 1ull) ? 0u : 1u) | (newm ? 0u : 2u);
+    const unsigned long long head = newm ? ~0ull >> __builtin_clzll(newm) : 0ull;     // bits 0 .. K
+    const uint32_t zrl = tab[0xF0];
+    unsigned long long m = (newm | oldm) & head, b = 0ull;
+    uint32_t r = 0u, nb = 0u;
+    int prev = ss - 1;
+    while (m) {
+        const int k = __builtin_ctzll(m);
+        m &= m - 1ull;
+        r += (uint32_t)(k - prev - 1); prev = k;                     // (everything between two non-zero coefficients is zero)
+        while (r > 15u) { emit(zrl & 0xFFFFu, zrl >> 16); mcu_raw64(b, nb, raw); b = 0ull; nb = 0u; r -= 16u; }
+        const uint32_t bit = (uint32_t)(valm >> k) & 1u;
+        if ((oldm >> k) & 1ull) { b = (b << 1) | bit; ++nb; continue; }
+        const uint32_t t = tab[((r << 4) | 1u) & 0xFFu];
+        emit(((t & 0xFFFFu) << 1) | bit, (t >> 16) + 1u);
+        mcu_raw64(b, nb, raw); b = 0ull; nb = 0u; r = 0u;
+    }
+    if (run) {
+        const uint32_t n = 31u - (uint32_t)__clz((int)run), t = tab[n << 4];
+        emit(((t & 0xFFFFu) << n) | (run - (1u << n)), (t >> 16) + n);
+    }
+    m = oldm & ~head;
+    nb = (uint32_t)__popcll(m);
+    b = 0ull;
+    while (m) { const int k = __builtin_ctzll(m); m &= m - 1ull; b = (b << 1) | ((valm >> k) & 1ull); }
+    mcu_raw64(b, nb, raw);
+    return flags;
+}
+
+// what a coder launch codes of a block: all of it, its DC, a band of its AC, a band of its AC with end-of-band runs; with successive
+// approximation: its DC by a point transform, one bit of its DC, a band by a point transform (with runs), one bit of a band (with runs)
+constexpr int kWalkBlock = 0, kWalkDc = 1, kWalkBand = 2, kWalkBandRuns = 3, kWalkDcPoint = 4, kWalkDcRefine = 5, kWalkBandPoint = 6, kWalkBandRefine = 7;
+constexpr bool mcu_walk_has_runs(int walk) { return walk == kWalkBandRuns || walk == kWalkBandPoint || walk == kWalkBandRefine; }
 
 // A table that gives symbol i the 1-bit code word i: a walk over it emits (symbol << size | amplitude, 1 + size) -- the symbol
 // itself is what the counting kernel takes from it, so the walks that count are the walks that code.
@@ -228,14 +318,19 @@ __device__ __forceinline__ McuRange mcu_range(const McuSegArgs &a, int sl) {
     return r;
 }
 
-// Returns whether coefficient se is zero (kWalkBandRuns alone: false for the others).
-template <int kWalk, class Tab, class Emit>
-__device__ __forceinline__ bool mcu_walk(const McuSegArgs &a, const McuBlock &b, int pred, const Tab &tab, Emit &&emit) {
+// Returns bit 0: E, the block may start or join a run (a walk with runs alone: coefficient se is zero -- of a refinement scan: not
+// new); bit 1: Z, of a refinement scan alone (the others' Z is "nothing emitted").  raw, run: mcu_walk_band_refine's.
+template <int kWalk, class Tab, class Emit, class Raw>
+__device__ __forceinline__ uint32_t mcu_walk(const McuSegArgs &a, const McuBlock &b, int pred, const Tab &tab, Emit &&emit, Raw &&raw, [[maybe_unused]] uint32_t run = 0u) {
     if constexpr (kWalk == kWalkDc) mcu_walk_dc(b.p, pred, tab, emit);
     else if constexpr (kWalk == kWalkBand) mcu_walk_band(b.p, a.ss, a.se, tab, emit);
-    else if constexpr (kWalk == kWalkBandRuns) return mcu_walk_band<true>(b.p, a.ss, a.se, tab, emit);
+    else if constexpr (kWalk == kWalkBandRuns) return mcu_walk_band<true>(b.p, a.ss, a.se, tab, emit) ? 1u : 0u;
+    else if constexpr (kWalk == kWalkDcPoint) mcu_walk_dc_point(b.p, pred, (int)a.al, tab, emit);
+    else if constexpr (kWalk == kWalkDcRefine) mcu_walk_dc_refine(b.p, (int)a.al, raw);
+    else if constexpr (kWalk == kWalkBandPoint) return mcu_walk_band<true, true>(b.p, a.ss, a.se, tab, emit, (int)a.al) ? 1u : 0u;
+    else if constexpr (kWalk == kWalkBandRefine) return mcu_walk_band_refine(b.p, a.ss, a.se, (int)a.al, run, tab, emit, raw);
     else mcu_walk_block(b.p, b.pad, pred, tab, emit);
-    return false;
+    return 0u;
 }
 
 // The symbol of a run of `run` blocks: EOBn, n = floor(log2 run), followed by the n low bits of run - 2^n.
@@ -247,6 +342,7 @@ __device__ __forceinline__ uint32_t mcu_run_log2(uint32_t run) { return 31u - (u
 template <bool kRestart, int kComps, int kWalk>
 __device__ __forceinline__ void mcu_code_segments(const McuSegArgs &a, uint32_t (*s_tab)[272], uint32_t (*s_win)[kMcuWin + 2]) {
     constexpr int kTabs = kComps == 1 ? 1 : 2;                     // one component: its two tables alone
+    constexpr bool kRuns = mcu_walk_has_runs(kWalk);
     const int lane = lane_id(), wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     {   // the tables of the workgroup's picture (its four segments are one picture's: num_segs_pad is a multiple of kWavesM)
         const size_t toff = a.huff_stride ? (size_t)(((int)blockIdx.x * kWavesM) / a.num_segs_pad) * a.huff_stride : 0;
@@ -278,18 +374,20 @@ __device__ __forceinline__ void mcu_code_segments(const McuSegArgs &a, uint32_t 
     for (int r = 0; r < 4; ++r) {
         const int k = r * 64 + lane;
         len[r] = 0u; pred[r] = 0;
-        if constexpr (kWalk == kWalkBandRuns) z[r] = e[r] = false;
+        if constexpr (kRuns) z[r] = e[r] = false;
         if (k < nblk) {
             const int mi = k / bpm;
             const McuBlock b = mcu_block<kComps>(a, base, m0 + mi, k - mi * bpm, mstart);
             pred[r] = b.pred;
             uint32_t n = 0;
-            const bool end_zero = mcu_walk<kWalk>(a, b, b.pred, (const uint32_t *)s_tab[kTabs > 1 && b.chroma ? 1 : 0], [&](uint32_t, uint32_t c) { n += c; ++nsym; });
+            const uint32_t flags = mcu_walk<kWalk>(a, b, b.pred, (const uint32_t *)s_tab[kTabs > 1 && b.chroma ? 1 : 0], [&](uint32_t, uint32_t c) { n += c; ++nsym; },
+                                                   [&](uint32_t, uint32_t c) { n += c; });
             len[r] = n;
-            if constexpr (kWalk == kWalkBandRuns) { z[r] = n == 0u; e[r] = end_zero; }     // (every code word has a bit: no symbols, no bits)
+            // (every code word has a bit: no symbols, no bits -- but a Z block of a refinement scan has its correction bits: the walk says)
+            if constexpr (kRuns) { z[r] = kWalk == kWalkBandRefine ? (flags & 2u) != 0u : n == 0u; e[r] = (flags & 1u) != 0u; }
         }
     }
-    if constexpr (kWalk == kWalkBandRuns) {                        // the runs the lane's blocks start: their symbols behind the blocks' own
+    if constexpr (kRuns) {                                         // the runs the lane's blocks start: their symbols behind the blocks' own (a refinement scan: behind their heads)
         mcu_band_runs(lane, z, e, run);
 #pragma unroll
         for (int r = 0; r < 4; ++r)
@@ -330,8 +428,9 @@ __device__ __forceinline__ void mcu_code_segments(const McuSegArgs &a, uint32_t 
                     if (j + 1u <= (uint32_t)kMcuWin && lo) atomicOr(&win[j + 1u], lo);
                     pos += n;
                 };
-                mcu_walk<kWalk>(a, b, pred[r], (const uint32_t *)s_tab[kTabs > 1 && b.chroma ? 1 : 0], put);
-                if constexpr (kWalk == kWalkBandRuns)
+                if constexpr (kWalk == kWalkBandRefine) mcu_walk<kWalk>(a, b, pred[r], (const uint32_t *)s_tab[0], put, put, run[r]);     // (the run's symbol between head and tail)
+                else mcu_walk<kWalk>(a, b, pred[r], (const uint32_t *)s_tab[kTabs > 1 && b.chroma ? 1 : 0], put, put);
+                if constexpr (kRuns && kWalk != kWalkBandRefine)
                     if (run[r]) {
                         const uint32_t n = mcu_run_log2(run[r]), t = s_tab[0][n << 4];
                         put(((t & 0xFFFFu) << n) | (run[r] - (1u << n)), (t >> 16) + n);
@@ -404,8 +503,12 @@ __global__ __launch_bounds__(64 * kWavesM) void k_mcu_segments(const McuSegArgs 
 // coefficient se: kMaxBlockBitsOptimized): seg_cap_words(kSegTiles) holds every segment, as it holds k_mcu_segments'.
 template <int kComps, int kWalk>
 __global__ __launch_bounds__(64 * kWavesM) void k_mcu_band_segments(const McuSegArgs a) {
-    static_assert((kComps == 3 && kWalk == kWalkDc) || (kComps == 1 && (kWalk == kWalkBand || kWalk == kWalkBandRuns)), "the scans of DESIGN.md 4.6.12 and 4.6.13");
+    static_assert((kComps == 3 && (kWalk == kWalkDc || kWalk == kWalkDcPoint || kWalk == kWalkDcRefine)) ||
+                  (kComps == 1 && (kWalk == kWalkBand || kWalk == kWalkBandRuns || kWalk == kWalkBandPoint || kWalk == kWalkBandRefine)),
+                  "the scans of DESIGN.md 4.6.12, 4.6.13 and 4.6.14");
     static_assert(22 <= kMaxBlockBitsColor && 63 * 27 <= kMaxBlockBitsColor, "a block of either walk fits the reservation of a whole block");
+    // successive approximation: a point transform only shortens amplitudes; a refinement block is kMaxBlockBitsRefine, the DC bit 1
+    static_assert(kMaxBlockBitsRefine <= kMaxBlockBitsOptimized && kMaxBlockBitsOptimized <= kMaxBlockBitsColor, "one block's string in any single scan fits the segment's reservation");
     __shared__ uint32_t s_tab[kComps == 1 ? 1 : 2][272];
     __shared__ uint32_t s_win[kWavesM][kMcuWin + 2];
     mcu_code_segments<false, kComps, kWalk>(a, s_tab, s_win);
@@ -445,19 +548,26 @@ int launch_mcu_band_segments(const McuSegArgs &a, void *stream) {
     const bool dc = a.comps == 3 && a.ss == 0 && a.se == 0, band = a.comps == 1 && a.ss >= 1 && a.ss <= a.se && a.se <= 63;
     // (runs: the scans of DESIGN.md 4.6.13 -- every picture codes with its own tables, huff_stride words apart)
     if (!a.sums || a.restart != 0 || (a.huff_stride != 0) != (a.runs != 0) || !(dc || band) || !mcu_seg_args_ok(a)) return (int)hipErrorInvalidValue;
+    // successive approximation: own tables alone; a first scan with al > 0, or the refinement of bit al = ah - 1
+    const bool point = a.ah == 0 && a.al > 0, refine = a.ah > 0;
+    if ((point || refine) && (!a.runs || a.al > 13 || (refine && a.ah != a.al + 1))) return (int)hipErrorInvalidValue;
     const dim3 grid((unsigned)((n + kWavesM - 1) / kWavesM)), block(64 * kWavesM);
-    const auto kernel = dc ? k_mcu_band_segments<3, kWalkDc> : (a.runs ? k_mcu_band_segments<1, kWalkBandRuns> : k_mcu_band_segments<1, kWalkBand>);
+    const auto kernel = dc ? (refine ? k_mcu_band_segments<3, kWalkDcRefine> : (point ? k_mcu_band_segments<3, kWalkDcPoint> : k_mcu_band_segments<3, kWalkDc>))
+                           : (refine ? k_mcu_band_segments<1, kWalkBandRefine>
+                                     : (point ? k_mcu_band_segments<1, kWalkBandPoint> : (a.runs ? k_mcu_band_segments<1, kWalkBandRuns> : k_mcu_band_segments<1, kWalkBand>)));
     hipLaunchKernelGGL(kernel, grid, block, 0, (hipStream_t)stream, a);
     return (int)hipGetLastError();
 }
 
-// The symbols of one scan of a file of DESIGN.md 4.6.13 counted, not coded: the coder's grid, segments and walks over McuSymbolTab,
-// one wave per segment, the workgroup's counts in LDS, then added to its picture's tables in counts [pictures][kProgTables][256]:
-// <3, kWalkDc> the DC sizes of Y into table 0 and of Cb and Cr into table 1, <1, kWalkBandRuns> the band's symbols into `table`.
+// The symbols of one scan of a file of DESIGN.md 4.6.13 or 4.6.14 counted, not coded: the coder's grid, segments and walks over
+// McuSymbolTab, one wave per segment, the workgroup's counts in LDS, then added to its picture's tables in counts [pictures][tables][256]:
+// <3, kWalkDc | kWalkDcPoint> the DC sizes of Y into table 0 and of Cb and Cr into table 1, <1, a walk with runs> the band's symbols
+// into `table`.  Raw bits (a refinement scan's correction bits) leave the walk through its other outlet and are not seen here.
 template <int kComps, int kWalk>
-__global__ __launch_bounds__(64 * kWavesM) void k_mcu_band_histogram(const McuSegArgs a, unsigned long long *__restrict__ counts, int table) {
-    static_assert((kComps == 3 && kWalk == kWalkDc) || (kComps == 1 && kWalk == kWalkBandRuns), "the scans of DESIGN.md 4.6.13");
+__global__ __launch_bounds__(64 * kWavesM) void k_mcu_band_histogram(const McuSegArgs a, unsigned long long *__restrict__ counts, int table, int tables) {
+    static_assert((kComps == 3 && (kWalk == kWalkDc || kWalk == kWalkDcPoint)) || (kComps == 1 && mcu_walk_has_runs(kWalk)), "the scans of DESIGN.md 4.6.13 and 4.6.14 that have a table");
     constexpr int kTabs = kComps == 1 ? 1 : 2;
+    constexpr bool kRuns = mcu_walk_has_runs(kWalk);
     __shared__ uint32_t s_cnt[kTabs][256];                         // (a workgroup walks at most 4 x 256 blocks of 64 symbols: 32 bits hold it)
     const int lane = lane_id(), wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     for (int i = (int)threadIdx.x; i < kTabs * 256; i += 64 * kWavesM) (&s_cnt[0][0])[i] = 0u;
@@ -472,20 +582,20 @@ __global__ __launch_bounds__(64 * kWavesM) void k_mcu_band_histogram(const McuSe
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int k = r * 64 + lane;
-            if constexpr (kWalk == kWalkBandRuns) z[r] = e[r] = false;
+            if constexpr (kRuns) z[r] = e[r] = false;
             if (k < nblk) {
                 const int mi = k / bpm;
                 const McuBlock b = mcu_block<kComps>(a, base, rg.m0 + mi, k - mi * bpm, rg.mstart);
                 uint32_t *const cnt = s_cnt[kTabs > 1 && b.chroma ? 1 : 0];
                 uint32_t n = 0;
-                const bool end_zero = mcu_walk<kWalk>(a, b, b.pred, McuSymbolTab(), [&](uint32_t v, uint32_t c) {
+                const uint32_t flags = mcu_walk<kWalk>(a, b, b.pred, McuSymbolTab(), [&](uint32_t v, uint32_t c) {
                     atomicAdd(&cnt[(v >> (c - 1u)) & 0xFFu], 1u);  // (a DC size s arrives as 256 + s)
                     ++n;
-                });
-                if constexpr (kWalk == kWalkBandRuns) { z[r] = n == 0u; e[r] = end_zero; }
+                }, [](uint32_t, uint32_t) {});
+                if constexpr (kRuns) { z[r] = kWalk == kWalkBandRefine ? (flags & 2u) != 0u : n == 0u; e[r] = (flags & 1u) != 0u; }
             }
         }
-        if constexpr (kWalk == kWalkBandRuns) {
+        if constexpr (kRuns) {
             uint32_t run[4];
             mcu_band_runs(lane, z, e, run);
 #pragma unroll
@@ -496,18 +606,22 @@ __global__ __launch_bounds__(64 * kWavesM) void k_mcu_band_histogram(const McuSe
     if (image < a.batch)
         for (int i = (int)threadIdx.x; i < kTabs * 256; i += 64 * kWavesM) {
             const uint32_t v = (&s_cnt[0][0])[i];
-            if (v) atomicAdd(&counts[((size_t)image * kProgTables + (size_t)(table + (i >> 8))) * 256 + (size_t)(i & 255)], (unsigned long long)v);
+            if (v) atomicAdd(&counts[((size_t)image * (size_t)tables + (size_t)(table + (i >> 8))) * 256 + (size_t)(i & 255)], (unsigned long long)v);
         }
 }
 
-int launch_mcu_band_histogram(const McuSegArgs &a, unsigned long long *counts, int table, void *stream) {
+// `tables`: the tables of a picture in `counts` (kProgTables, or kProgTablesMax); a DC scan counts into `table` and `table` + 1.
+int launch_mcu_band_histogram(const McuSegArgs &a, unsigned long long *counts, int table, int tables, void *stream) {
     const int n = a.batch * a.num_segs_pad;
     if (n <= 0) return 0;
-    const bool dc = a.comps == 3 && a.ss == 0 && a.se == 0 && table == 0, band = a.comps == 1 && a.ss >= 1 && a.ss <= a.se && a.se <= 63 && table >= 2 && table < kProgTables;
-    if (!counts || a.restart != 0 || !(dc || band) || !mcu_seg_args_ok(a)) return (int)hipErrorInvalidValue;
+    const bool dc = a.comps == 3 && a.ss == 0 && a.se == 0 && table == 0 && tables >= 2 && a.ah == 0;
+    const bool band = a.comps == 1 && a.ss >= 1 && a.ss <= a.se && a.se <= 63 && table >= 2 && table < tables;
+    const bool point = a.ah == 0 && a.al > 0, refine = a.ah > 0;
+    if (!counts || a.restart != 0 || !(dc || band) || tables > kProgTablesMax || a.al > 13 || (refine && a.ah != a.al + 1) || !mcu_seg_args_ok(a)) return (int)hipErrorInvalidValue;
     const dim3 grid((unsigned)((n + kWavesM - 1) / kWavesM)), block(64 * kWavesM);
-    const auto kernel = dc ? k_mcu_band_histogram<3, kWalkDc> : k_mcu_band_histogram<1, kWalkBandRuns>;
-    hipLaunchKernelGGL(kernel, grid, block, 0, (hipStream_t)stream, a, counts, table);
+    const auto kernel = dc ? (point ? k_mcu_band_histogram<3, kWalkDcPoint> : k_mcu_band_histogram<3, kWalkDc>)
+                           : (refine ? k_mcu_band_histogram<1, kWalkBandRefine> : (point ? k_mcu_band_histogram<1, kWalkBandPoint> : k_mcu_band_histogram<1, kWalkBandRuns>));
+    hipLaunchKernelGGL(kernel, grid, block, 0, (hipStream_t)stream, a, counts, table, tables);
     return (int)hipGetLastError();
 }
 
@@ -516,11 +630,17 @@ int launch_mcu_band_histogram(const McuSegArgs &a, unsigned long long *counts, i
 // [272] words at tabs + (q kProgTables + t) 272: an AC table's code words by run/size at 0, a DC table's by size at 256, unused
 // symbols 0 -- and the table's DHT segment into its scan's header slot: scan 1's is the file's head (hdr[0, head_len)), the two DC
 // tables and the DC scan's SOS (hdr[sos_off, sos_off + kMcuSosLen)); scan k's (from 0) its table and sos + 16 k.
+// The script is the launch's: a.tables waves, table t belongs to scan a.table_scan[t] and is written with the
+// Tc/Th byte a.table_id[t]; the tables of a scan are consecutive, its header is [the head,] their DHT segments in that order and
+// its SOS (a.sos + 16 k, a.sos_len[k] bytes), written by the scan's last table.  A scan without a table (bit k of a.bare) gets a
+// header of its SOS alone, from wave 0.
 constexpr int kMcuSosLen = 14;
-__global__ __launch_bounds__(64 * kProgTables) void k_prog_tables(const ProgTablesArgs a) {
-    __shared__ uint32_t s_nvals[kProgTables];
-    const int lane = lane_id(), t = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), q = (int)blockIdx.x;
-    const uint8_t *res = a.res + ((size_t)q * kProgTables + (size_t)t) * kHuffResBytes;
+__global__ __launch_bounds__(64 * kProgTablesMax) void k_prog_tables(const ProgTablesArgs a) {
+    __shared__ uint32_t s_nvals[kProgTablesMax];
+    const int lane = lane_id(), t = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), q = (int)blockIdx.x;   // (64 a.tables threads: every wave has a table)
+    const int ntab = a.tables;
+    const bool dc_table = (a.table_id[t] & 0x10) == 0;
+    const uint8_t *res = a.res + ((size_t)q * ntab + (size_t)t) * kHuffResBytes;
     const uint32_t nvals = min(*reinterpret_cast<const uint32_t *>(res + 16), 256u);
     if (lane == 0) s_nvals[t] = nvals;
     uint32_t first[17], cum[17];                                   // by length: the first code word, the HUFFVAL places up to and with it
@@ -528,7 +648,7 @@ __global__ __launch_bounds__(64 * kProgTables) void k_prog_tables(const ProgTabl
     uint32_t code = 0;
 #pragma unroll
     for (int l = 1; l <= 16; ++l) { const uint32_t n = res[l - 1]; first[l] = code; cum[l] = cum[l - 1] + n; code = (code + n) << 1; }
-    uint32_t *const tab = a.tabs + ((size_t)q * kProgTables + (size_t)t) * 272;
+    uint32_t *const tab = a.tabs + ((size_t)q * ntab + (size_t)t) * 272;
     for (int i = lane; i < 272; i += 64) tab[i] = 0u;
     __syncthreads();                                               // (the zeros are in place before a code word; s_nvals is complete)
     for (uint32_t i = (uint32_t)lane; i < nvals; i += 64u) {
@@ -538,40 +658,56 @@ __global__ __launch_bounds__(64 * kProgTables) void k_prog_tables(const ProgTabl
 #pragma unroll
         for (int k = 1; k <= 16; ++k) if ((uint32_t)k == l) { f = first[k]; c0 = cum[k - 1]; }
         const uint32_t sym = res[32 + i];
-        if (l <= 16u && (t >= 2 || sym < 16u)) tab[(t < 2 ? 256u : 0u) + sym] = (l << 16) | (f + i - c0);
+        if (l <= 16u && (!dc_table || sym < 16u)) tab[(dc_table ? 256u : 0u) + sym] = (l << 16) | (f + i - c0);
     }
-    const int scan = t < 2 ? 0 : t - 1;
-    uint8_t *const out = a.hdr_out + ((size_t)scan * a.pictures + (size_t)(a.first + q)) * kMcuPrefixSlot;
-    uint32_t at = t < 2 ? (uint32_t)a.head_len + (t == 1 ? 21u + s_nvals[0] : 0u) : 0u;
-    const auto put = [&](uint32_t pos, uint8_t v) { if (pos < (uint32_t)kMcuPrefixSlot) out[pos] = v; };
-    if (lane == 0) {
-        put(at, 0xFF); put(at + 1, 0xC4); put(at + 2, (uint8_t)((19u + nvals) >> 8)); put(at + 3, (uint8_t)(19u + nvals));
-        put(at + 4, (uint8_t)(t < 2 ? t : ((t - 2) % 3 == 0 ? 0x10 : 0x11)));
+    const int scan = a.table_scan[t];
+    uint32_t at = scan == 0 ? (uint32_t)a.head_len : 0u;
+    bool last_of_scan = true;
+    for (int u = 0; u < ntab; ++u)
+        if ((int)a.table_scan[u] == scan) { if (u < t) at += 21u + s_nvals[u]; if (u > t) last_of_scan = false; }
+    {
+        uint8_t *const out = a.hdr_out + ((size_t)scan * a.pictures + (size_t)(a.first + q)) * kMcuPrefixSlot;
+        const auto put = [&](uint32_t pos, uint8_t v) { if (pos < (uint32_t)kMcuPrefixSlot) out[pos] = v; };
+        if (lane == 0) {
+            put(at, 0xFF); put(at + 1, 0xC4); put(at + 2, (uint8_t)((19u + nvals) >> 8)); put(at + 3, (uint8_t)(19u + nvals));
+            put(at + 4, a.table_id[t]);
+        }
+        if (lane < 16) put(at + 5 + lane, res[lane]);
+        for (uint32_t i = (uint32_t)lane; i < nvals; i += 64u) put(at + 21 + i, res[32 + i]);
+        at += 21u + nvals;
+        if (t == 0)
+            for (int i = lane; i < a.head_len; i += 64) put((uint32_t)i, a.hdr[i]);
+        if (last_of_scan) {                                        // the SOS behind the scan's last table, and the slot's length
+            const uint8_t *sos = a.sos + 16 * scan;
+            const uint32_t nsos = a.sos_len[scan];
+            if ((uint32_t)lane < nsos) put(at + (uint32_t)lane, sos[lane]);
+            if (lane == 0) a.hdr_len[(size_t)scan * a.pictures + (size_t)(a.first + q)] = min(at + nsos, (uint32_t)kMcuPrefixSlot);
+        }
     }
-    if (lane < 16) put(at + 5 + lane, res[lane]);
-    for (uint32_t i = (uint32_t)lane; i < nvals; i += 64u) put(at + 21 + i, res[32 + i]);
-    at += 21u + nvals;
-    if (t == 0) {
-        for (int i = lane; i < a.head_len; i += 64) put((uint32_t)i, a.hdr[i]);
-    } else {                                                       // the SOS behind the scan's last table, and the slot's length
-        const uint8_t *sos = t == 1 ? a.hdr + a.sos_off : a.sos + 16 * scan;
-        const uint32_t nsos = t == 1 ? (uint32_t)kMcuSosLen : (uint32_t)kSosBytes;
-        if ((uint32_t)lane < nsos) put(at + (uint32_t)lane, sos[lane]);
-        if (lane == 0) a.hdr_len[(size_t)scan * a.pictures + (size_t)(a.first + q)] = min(at + nsos, (uint32_t)kMcuPrefixSlot);
-    }
+    if (t == 0)
+        for (int k = 1; k < a.scans; ++k)
+            if ((a.bare >> k) & 1u) {                              // a scan of raw bits: its SOS alone
+                const uint32_t nsos = a.sos_len[k];
+                if ((uint32_t)lane < nsos) a.hdr_out[((size_t)k * a.pictures + (size_t)(a.first + q)) * kMcuPrefixSlot + (size_t)lane] = a.sos[16 * k + lane];
+                if (lane == 0) a.hdr_len[(size_t)k * a.pictures + (size_t)(a.first + q)] = nsos;
+            }
 }
 
 int launch_prog_tables(const ProgTablesArgs &a, int batch, void *stream) {
     if (batch < 1 || batch > kMaxBatch || !a.res || !a.tabs || !a.hdr_out || !a.hdr_len || !a.hdr || !a.sos || a.head_len < 0 ||
-        a.head_len + 2 * 33 + kMcuSosLen > kMcuPrefixSlot || a.first < 0 || a.first + batch > a.pictures)
+        a.head_len + 2 * 33 + kMcuSosLen > kMcuPrefixSlot || a.first < 0 || a.first + batch > a.pictures || a.tables < 2 ||
+        a.tables > kProgTablesMax || a.scans < 1 || a.scans > kProgScansMax || a.table_scan[0] != 0 || (a.bare & 1u))
         return (int)hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_prog_tables, dim3((unsigned)batch), dim3(64 * kProgTables), 0, (hipStream_t)stream, a);
+    for (int t = 0; t < a.tables; ++t)                             // (a scan's tables are consecutive; scan 0 has the DC tables in front of the head's end)
+        if (a.table_scan[t] >= a.scans || ((a.bare >> a.table_scan[t]) & 1u) || (t && a.table_scan[t] < a.table_scan[t - 1])) return (int)hipErrorInvalidValue;
+    for (int k = 0; k < a.scans; ++k) if (a.sos_len[k] < 1 || a.sos_len[k] > 16) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_prog_tables, dim3((unsigned)batch), dim3(64 * (unsigned)a.tables), 0, (hipStream_t)stream, a);
     return (int)hipGetLastError();
 }
 
 // Workgroup (bx, p): picture p of the launch.  Every workgroup of a picture derives the same sizes and the same verdict
 // (k_append_scans_batch's plan); (0, p) writes the picture's size word and adds its numbers to the context's record.
-// A file is scan 1 as k_finalize left it in the caller's buffer -- the prefix in front --, then the scans 2 .. kProgScans out of their
+// A file is scan 1 as k_finalize left it in the caller's buffer -- the prefix in front --, then the scans 2 .. a.scans out of their
 // slots, each with its SOS in front and the last with EOI behind it.  Its stuffed bytes follow from its size: every scan is its
 // header, its bits rounded up to a byte, and a 0x00 per 0xFF.
 constexpr int kConcatWgs = 64;
@@ -581,14 +717,15 @@ __global__ __launch_bounds__(256) void k_scans_concat(const ScansConcatArgs a) {
     // picture; anything else there, and any bit of the slots' record (a slot holds its scan's bound: it cannot overflow), fails
     // every picture, and nothing is copied out of a slot.
     const uint32_t st = a.scan_stats[0].status | a.scan_stats[1].status, hard = (a.scan_stats[0].status & ~1u) | a.scan_stats[1].status;
-    uint64_t size[kProgScans], total = 0;
+    uint64_t size[kProgScansMax], total = 0;                       // (a.scans of them: the loops below are unrolled to the maximum, so nothing is indexed at run time)
 #pragma unroll
-    for (int k = 0; k < kProgScans; ++k) { size[k] = a.size[k * kMaxBatch + p]; total += size[k]; }
+    for (int k = 0; k < kProgScansMax; ++k) { size[k] = k < a.scans ? a.size[k * kMaxBatch + p] : 0ull; total += size[k]; }
     const bool fit = hard == 0u && total <= a.out_capacity;
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         unsigned long long bits = 0, syms = 0, bytes = 0, ff = 0;
 #pragma unroll
-        for (int k = 0; k < kProgScans; ++k) {
+        for (int k = 0; k < kProgScansMax; ++k) {
+            if (k >= a.scans) continue;
             const unsigned long long b = a.sums[2 * (k * kMaxBatch + p)];
             bits += b; syms += a.sums[2 * (k * kMaxBatch + p) + 1]; bytes += (b + 7u) / 8u;
             if (a.writer_sums) ff += a.writer_sums[(k * kMaxBatch + p) * kMcuPicSums + 2];
@@ -600,7 +737,7 @@ __global__ __launch_bounds__(256) void k_scans_concat(const ScansConcatArgs a) {
         atomicAdd((unsigned long long *)&t->total_exact, pic[2] + pic[5] + pic[8]);
         // the stuffed bytes follow from the size -- or the restart writer counted them (4.6.13: the headers differ from picture to picture)
         atomicAdd((unsigned long long *)&t->total_ff,
-                  a.writer_sums ? ff : (unsigned long long)(total - (uint64_t)a.prefix_len - (uint64_t)(kProgScans - 1) * kSosBytes - 2u) - bytes);
+                  a.writer_sums ? ff : (unsigned long long)(total - (uint64_t)a.prefix_len - (uint64_t)(a.scans - 1) * kSosBytes - 2u) - bytes);
         *a.out_size[p] = fit ? total : 0ull;
         if (a.last_of_call && p == (int)gridDim.y - 1) t->out_size = fit ? total : 0ull;
         const uint32_t add = st | (fit ? 0u : 1u);
@@ -610,7 +747,8 @@ __global__ __launch_bounds__(256) void k_scans_concat(const ScansConcatArgs a) {
     uint8_t *d = a.out[p] + size[0];
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x * 16u;
 #pragma unroll
-    for (int k = 1; k < kProgScans; ++k) {
+    for (int k = 1; k < kProgScansMax; ++k) {
+        if (k >= a.scans) continue;
         const uint64_t n = size[k];
         const uint8_t *src = a.slots + (size_t)p * a.pic_bytes + a.slot_off[k];
         for (uint64_t i = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) * 16u; i < n; i += stride) {
@@ -626,8 +764,8 @@ __global__ __launch_bounds__(256) void k_scans_concat(const ScansConcatArgs a) {
 }
 
 int launch_scans_concat(const ScansConcatArgs &a, void *stream) {
-    if (a.batch < 1 || a.batch > kMaxBatch || a.pic_bytes % 16 != 0) return (int)hipErrorInvalidValue;
-    for (int k = 1; k < kProgScans; ++k) if (a.slot_off[k] % 16 != 0) return (int)hipErrorInvalidValue;
+    if (a.batch < 1 || a.batch > kMaxBatch || a.pic_bytes % 16 != 0 || a.scans < 2 || a.scans > kProgScansMax) return (int)hipErrorInvalidValue;
+    for (int k = 1; k < a.scans; ++k) if (a.slot_off[k] % 16 != 0) return (int)hipErrorInvalidValue;
     hipLaunchKernelGGL(k_scans_concat, dim3(kConcatWgs, (unsigned)a.batch), dim3(256), 0, (hipStream_t)stream, a);
     return (int)hipGetLastError();
 }

@@ -143,6 +143,11 @@ def _prototypes():
         "jpegamd_encode_ycbcr_progressive_optimized_batch_async": batch(YCbCrImage, 4),
         "jpegamd_max_jfif_bytes_progressive_optimized": (u64, [i32, i32, i32]),
         "jpegamd_debug_progressive_counts": (i32, [vp, vp]),
+        # ... with successive approximation: ten scans
+        "jpegamd_encode_color_progressive_successive_batch_async": batch(Image, 1),
+        "jpegamd_encode_ycbcr_progressive_successive_batch_async": batch(YCbCrImage, 4),
+        "jpegamd_max_jfif_bytes_progressive_successive": (u64, [i32, i32, i32]),
+        "jpegamd_debug_progressive_successive_counts": (i32, [vp, vp]),
     }
     later = {
         "jpegamd_encoder_set_pipeline": (i32, [vp, i32]),
@@ -345,9 +350,31 @@ def max_jfif_bytes_progressive_optimized(width: int, height: int, subsampling: i
     return int(lib.jpegamd_max_jfif_bytes_progressive_optimized(width, height, subsampling))
 
 
+def max_jfif_bytes_progressive_successive(width: int, height: int, subsampling: int = SUBSAMPLE_420) -> int:
+    """Upper bound on the bytes of a progressive colour file with successive approximation (ten scans); 0 for bad
+    arguments."""
+    return int(lib.jpegamd_max_jfif_bytes_progressive_successive(width, height, subsampling))
+
+
 SCANS = ("separate", "interleaved")
 HUFFMAN_STANDARD, HUFFMAN_OPTIMIZED = 0, 1       # jpegamd_encoder_set_huffman
 PROGRESSIVE_OPTIMIZED = "optimized"              # a `progressive` argument inside this package: the entries of DESIGN.md 4.6.13 (True: 4.6.12's)
+PROGRESSIVE_SUCCESSIVE = "successive"            # ... of DESIGN.md 4.6.14
+
+
+def _progressive_mode(progressive):
+    """A `progressive` argument -> (the bound, the Encoder method of packed pixels, the one of YCbCr pictures, whether the entries
+    make their own tables and leave the context's Huffman mode alone)."""
+    if progressive == PROGRESSIVE_SUCCESSIVE:
+        return (max_jfif_bytes_progressive_successive, "encode_color_progressive_successive_batch_async",
+                "encode_ycbcr_progressive_successive_batch_async", True)
+    if progressive == PROGRESSIVE_OPTIMIZED:
+        return (max_jfif_bytes_progressive_optimized, "encode_color_progressive_optimized_batch_async",
+                "encode_ycbcr_progressive_optimized_batch_async", True)
+    return max_jfif_bytes_progressive, "encode_color_progressive_batch_async", "encode_ycbcr_progressive_batch_async", False
+
+
+
 HUFFMANS = ("standard", "optimized")
 
 
@@ -621,7 +648,7 @@ def encode_tensor_batch(t, quality: int = 0, subsampling: int = SUBSAMPLE_420, l
     if any(not x.is_cuda or x.device != tensors[0].device for x in tensors):
         raise ValueError("encode_tensor_batch needs a device tensor")
     if _progressive:
-        cap = (max_jfif_bytes_progressive_optimized if _progressive == PROGRESSIVE_OPTIMIZED else max_jfif_bytes_progressive)(w, h, subsampling)
+        cap = _progressive_mode(_progressive)[0](w, h, subsampling)
     elif interleaved:
         cap = max_jfif_bytes_interleaved_restart(w, h, subsampling, ri) if ri else max_jfif_bytes_interleaved(w, h, subsampling)
     elif order == ORDER_GRAY or (order is None and subsampling == 0):
@@ -636,10 +663,10 @@ def encode_tensor_batch(t, quality: int = 0, subsampling: int = SUBSAMPLE_420, l
             imgs = [Encoder.image(ptr(b0 + i), w, h, stride, bottom_up=False, channel_order=order, quality=quality) for i in range(k)]
         _queue_pixels(enc, imgs, subsampling, outs, cap, size_ptrs, stream, interleaved, ri, _any_layout, _huffman, _progressive)
 
-    # (a progressive call sets the standard tables on the shared context: the entry refuses any other mode; the optimised
-    # progressive entries do not read the mode)
+    # (a progressive call sets the standard tables on the shared context: the entry refuses any other mode; the progressive
+    # entries that make their own tables do not read the mode)
     return _encode_pictures(tensors[0].device, n, h, w, cap, queue,
-                            HUFFMAN_STANDARD if _progressive and _progressive != PROGRESSIVE_OPTIMIZED else (_huffman or None))
+                            HUFFMAN_STANDARD if _progressive and not _progressive_mode(_progressive)[3] else (_huffman or None))
 
 
 def _queue_pixels(enc, imgs, subsampling, outs, cap, size_ptrs, stream, interleaved: bool = False, restart: int = 0,
@@ -649,10 +676,9 @@ def _queue_pixels(enc, imgs, subsampling, outs, cap, size_ptrs, stream, interlea
     the entry of every pixel order with `any_layout` (jpegamd.mjpeg), otherwise the RGB entries of encode_tensor_batch's own
     scan="interleaved" -- the restart entry when there are intervals, and for `huffman` (whatever the interval)."""
     planar = isinstance(imgs[0], PlanarImage)
-    if progressive == PROGRESSIVE_OPTIMIZED:                      # (jpegamd.progressive_optimized: the tables of every scan its own)
-        enc.encode_color_progressive_optimized_batch_async(imgs, subsampling, outs, cap, size_ptrs, stream)
-    elif progressive:                                             # (jpegamd.progressive: packed pixels, no intervals, the standard tables)
-        enc.encode_color_progressive_batch_async(imgs, subsampling, outs, cap, size_ptrs, stream)
+    if progressive:                                               # (jpegamd.progressive: packed pixels, no intervals, the standard tables;
+        # jpegamd.progressive_optimized, jpegamd.progressive_successive: the tables of every scan its own)
+        getattr(enc, _progressive_mode(progressive)[1])(imgs, subsampling, outs, cap, size_ptrs, stream)
     elif not interleaved:
         if planar:
             enc.encode_planar_batch_async(imgs, subsampling, outs, cap, size_ptrs, stream)
@@ -820,12 +846,11 @@ def _encode_ycbcr_images(device, n, h, w, subsampling, image, sample_range: int 
     if huffman and not any_kind:
         raise ValueError("optimised Huffman tables go through jpegamd.mjpeg")
     if progressive:                                               # (jpegamd.progressive: any kind, no intervals, the standard tables set for the call;
-        own = progressive == PROGRESSIVE_OPTIMIZED                # jpegamd.progressive_optimized: the context's mode is left alone)
-        cap = (max_jfif_bytes_progressive_optimized if own else max_jfif_bytes_progressive)(w, h, subsampling)
+        bound, _, method, own = _progressive_mode(progressive)    # jpegamd.progressive_optimized, _successive: the context's mode is left alone)
+        cap = bound(w, h, subsampling)
 
         def queue_progressive(enc, b0, k, outs, cap, size_ptrs, stream):
-            entry = enc.encode_ycbcr_progressive_optimized_batch_async if own else enc.encode_ycbcr_progressive_batch_async
-            entry([image(b0 + i) for i in range(k)], subsampling, sample_range, sample_format, matrix, outs, cap, size_ptrs, stream)
+            getattr(enc, method)([image(b0 + i) for i in range(k)], subsampling, sample_range, sample_format, matrix, outs, cap, size_ptrs, stream)
 
         return _encode_pictures(device, n, h, w, cap, queue_progressive, None if own else HUFFMAN_STANDARD)
     if restart:
@@ -962,6 +987,18 @@ class _ProgressiveEntries:
                                                        out_ptrs, out_cap: int, size_ptrs, stream: int = 0):
         """... of YCbCr pictures of any kind (jpegamd_encode_ycbcr_progressive_optimized_batch_async)."""
         self._batch("jpegamd_encode_ycbcr_progressive_optimized_batch_async", YCbCrImage, imgs,
+                    (subsampling, sample_range, sample_format, matrix), out_ptrs, out_cap, size_ptrs, stream)
+
+    def encode_color_progressive_successive_batch_async(self, imgs, subsampling: int, out_ptrs, out_cap: int, size_ptrs, stream: int = 0):
+        """The progressive files with successive approximation -- the ten scans of libjpeg's default script, a table per scan
+         -- of the same pictures (jpegamd_encode_color_progressive_successive_batch_async); out_cap from
+        max_jfif_bytes_progressive_successive.  The context's Huffman mode is neither read nor changed."""
+        self._batch("jpegamd_encode_color_progressive_successive_batch_async", Image, imgs, (subsampling,), out_ptrs, out_cap, size_ptrs, stream)
+
+    def encode_ycbcr_progressive_successive_batch_async(self, imgs, subsampling: int, sample_range: int, sample_format: int, matrix: int,
+                                                        out_ptrs, out_cap: int, size_ptrs, stream: int = 0):
+        """... of YCbCr pictures of any kind (jpegamd_encode_ycbcr_progressive_successive_batch_async)."""
+        self._batch("jpegamd_encode_ycbcr_progressive_successive_batch_async", YCbCrImage, imgs,
                     (subsampling, sample_range, sample_format, matrix), out_ptrs, out_cap, size_ptrs, stream)
 
 

@@ -55,7 +55,9 @@ context, so a library from before the mode serves it.
 jpegamd_encode_color_progressive_batch_async for rgb, jpegamd_encode_ycbcr_progressive_batch_async for every YCbCr source, --range and
 --matrix; the whole call is timed (ns_total), the line carries "scan": "progressive".  No --restart, --layout, --convert, --narrow.
 With --huffman optimized the loop goes through jpegamd_encode_*_progressive_optimized_batch_async (end-of-band runs and
-per-scan optimised tables; nothing is set on the context); --huffman standard is the plain progressive loop.
+per-scan optimised tables; nothing is set on the context); --huffman standard is the plain progressive loop.  With --successive as
+well it goes through jpegamd_encode_*_progressive_successive_batch_async (DESIGN.md 4.6.14: the ten scans of successive approximation);
+the line then carries "successive": true.
 
 --scan gray (with --batch N, default 8) times GRAYSCALE files through jpegamd_encode_gray_scan_batch_async: the luma
 of the same --size pictures, --restart N|row in blocks (`row`: ceil(W / 8)), --huffman standard|optimized; the whole call is timed
@@ -107,7 +109,11 @@ def main() -> None:
                     help="--scan interleaved: the Annex K tables, or per-picture optimised tables")
     ap.add_argument("--restart", default=None, metavar="N|row",
                     help="--scan interleaved: restart intervals of N MCUs (0 .. 65535), or `row` for one MCU row")
+    ap.add_argument("--successive", action="store_true",
+                    help="--scan progressive --huffman optimized: the ten scans of successive approximation (DESIGN.md 4.6.14)")
     a = ap.parse_args()
+    if a.successive and (a.scan != "progressive" or a.huffman != "optimized"):
+        sys.exit("--successive needs --scan progressive --huffman optimized")
     import torch                          # (the device runtime comes up through torch first, as in bench.py)
     if not torch.cuda.is_available():
         sys.exit("bench_color.py: no GPU")
@@ -344,8 +350,17 @@ def run_batch(a, jpegamd, torch, dev, sources=("rgb",)) -> None:
         one_scan, progressive = a.scan == "interleaved", a.scan == "progressive"
         cap = jpegamd.max_jfif_bytes_interleaved(w, h, sub) if one_scan else jpegamd.max_jfif_bytes_color(w, h, sub)
         own = progressive and a.huffman == "optimized"
+        # the three progressive files: (bound, entry of packed pixels, entry of YCbCr pictures)
+        bound, color_entry, ycbcr_entry = (jpegamd.max_jfif_bytes_progressive, enc.encode_color_progressive_batch_async,
+                                           enc.encode_ycbcr_progressive_batch_async)
+        if own and a.successive:
+            bound, color_entry, ycbcr_entry = (jpegamd.max_jfif_bytes_progressive_successive, enc.encode_color_progressive_successive_batch_async,
+                                               enc.encode_ycbcr_progressive_successive_batch_async)
+        elif own:
+            bound, color_entry, ycbcr_entry = (jpegamd.max_jfif_bytes_progressive_optimized, enc.encode_color_progressive_optimized_batch_async,
+                                               enc.encode_ycbcr_progressive_optimized_batch_async)
         if progressive:
-            cap = (jpegamd.max_jfif_bytes_progressive_optimized if own else jpegamd.max_jfif_bytes_progressive)(w, h, sub)
+            cap = bound(w, h, sub)
         restart = None
         if a.restart is not None:                                # `row`: ceil(W / 8) MCUs at 4:4:4, ceil(W / 16) otherwise
             restart = -(-w // (8 if sub == jpegamd.SUBSAMPLE_444 else 16)) if a.restart == "row" else int(a.restart)
@@ -355,11 +370,11 @@ def run_batch(a, jpegamd, torch, dev, sources=("rgb",)) -> None:
         out_ptrs = [o.data_ptr() for o in outs]
         size_ptrs = [sizes.data_ptr() + 8 * i for i in range(n)]
         if progressive and ycc is None:
-            entry = enc.encode_color_progressive_optimized_batch_async if own else enc.encode_color_progressive_batch_async
+            entry = color_entry
             call = lambda: entry(descs, sub, out_ptrs, cap, size_ptrs, stream)
         elif progressive:
             fmt = {"p010": jpegamd.SAMPLES_10_MSB, "i010": jpegamd.SAMPLES_10_LSB}.get(source, jpegamd.SAMPLES_8)
-            entry = enc.encode_ycbcr_progressive_optimized_batch_async if own else enc.encode_ycbcr_progressive_batch_async
+            entry = ycbcr_entry
             call = lambda: entry(
                 ycc, sub, jpegamd.RANGE_LIMITED if limited else jpegamd.RANGE_FULL, fmt, jpegamd.MATRIX_BT709 if bt709 else jpegamd.MATRIX_BT601,
                 out_ptrs, cap, size_ptrs, stream)
@@ -403,6 +418,8 @@ def run_batch(a, jpegamd, torch, dev, sources=("rgb",)) -> None:
             line["scan"] = a.scan
         if a.huffman is not None:
             line["huffman"] = a.huffman
+        if a.successive:
+            line["successive"] = True
         if restart is not None:
             line["restart_interval"] = restart
         if limited:
