@@ -656,6 +656,71 @@ int32_t jpegamd_encode_ycbcr_progressive_successive_batch_async(JpegAmdEncoder *
 uint64_t jpegamd_max_jfif_bytes_progressive_successive(int32_t width, int32_t height, int32_t subsampling);
 int32_t jpegamd_debug_progressive_successive_counts(JpegAmdEncoder *enc, uint64_t *counts);
 
+/* ---- Progressive files with a scan script of the caller's, and grayscale progressive files ----------------------------------------
+ * NORMATIVE.  A script is 1 .. JPEGAMD_MAX_SCANS scans in the file's order; a scan is a set of components (bit 0 Y, bit 1 Cb, bit 2
+ * Cr; a grayscale file: bit 0 alone) and Ss, Se, Ah, Al.  jpegamd_validate_scan_script (host only, no device) accepts a script that
+ * keeps every rule below (T.81 G.1.1.1, libjpeg's validate_script) and answers JPEGAMD_ERR_ARG otherwise; *bad_scan (may be NULL) is
+ * then the index of the first scan that breaks a rule, -1 for a rule about the whole script (and -1 on success):
+ *   - count is 1 .. JPEGAMD_MAX_SCANS, file_components 1 or 3 (whole script);
+ *   - components is a non-empty subset of the file's components;
+ *   - Ss = 0 implies Se = 0: a DC scan, of one, two or three components; Ss > 0: exactly one component and Ss <= Se <= 63;
+ *   - Al <= 13; Ah = 0 or Ah = Al + 1;
+ *   - for every (component, coefficient) the scan covers: Ah = 0 if no earlier scan coded it, otherwise Ah = the Al of the last that did
+ *     and Ah = Al + 1 (so a first scan cannot be repeated, and a coefficient coded down to bit 0 is done);
+ *   - an AC scan of a component comes after the component's first DC scan;
+ *   - the script needs at most 16 Huffman tables (whole script): a first DC scan one per table class among its components (Y is a
+ *     class, Cb and Cr share one), an AC scan one, a DC refinement scan none;
+ *   - every component of the file has a first DC scan (whole script).  Nothing else has to be complete: a DC-only script is valid.
+ * The file.  Head: SOI, APP0, DQT, SOF2 (a grayscale file: the one-component head, one quantisation table).  Every scan with symbols
+ * has tables of its own, made of the scan's symbol counts as in the files above, numbered in the file's order and written as DHT
+ * segments in front of the scan's SOS -- a first DC scan with Y and chroma: Y's, then the chroma table.  Tc/Th: 0x00 / 0x01 the DC
+ * tables of Y / chroma, 0x10 / 0x11 the AC tables; a grayscale file uses 0x00 and 0x10.  SOS: Ns, the scan's components with
+ * ascending selectors 1, 2, 3 -- Y with the tables 0 / 0, Cb and Cr 1 / 1 --, Ss, Se, Ah << 4 | Al: 8 + 2 Ns bytes.  The scans are
+ * coded as in the file above (first and refinement scans, runs inside segments of 256 blocks); the scan shapes:
+ *   three components, DC   the interleaved MCU of the one-scan file, pad blocks included;
+ *   two components, DC     {Y, Cb}, {Y, Cr}, {Cb, Cr}: the MCU of T.81 A.2.3 -- Y's hs x vs blocks with the pad blocks of the
+ *                          three-component scan, one block of each chroma component --, a component's predictor its previous block
+ *                          in this scan's order, over the three-component MCU grid;
+ *   one component, DC/AC   the component's own ceil(X / 8) x ceil(Y / 8) blocks in raster order (chroma: of its subsampled plane),
+ *                          no pad blocks, the predictor the block in front.
+ * scans == NULL with scan_count == 0 is libjpeg's jpeg_simple_progression for the file's component count: the ten scans above for a
+ * colour file -- the file is the _successive_ entry's byte for byte --, and for a grayscale file the six scans
+ *   DC 0,1; AC 1-5 0,2; AC 6-63 0,2; AC 1-63 2,1; DC 1,0; AC 1-63 1,0   (Ss-Se Ah,Al).
+ * The entries take batches of up to 32 pictures with the arguments, grouping, capacity behaviour and statistics of the _successive_
+ * entries; the gray entry any of the five channel orders, as jpegamd_encode_gray_scan_batch_async.  The script is validated before
+ * anything is allocated or launched: a refused call (JPEGAMD_ERR_ARG) leaves the context as it was.  The context's Huffman mode is
+ * neither read nor changed.  Not built: restart intervals, the planar (three-pointer) source, the Annex K tables with a script.
+ * The bound, jpegamd_max_jfif_bytes_progressive_script (subsampling 0: grayscale), scan by scan: the scan's DHT segments at most (a
+ * DC table 21 + 12 = 33 bytes, an AC table 21 + 170 = 191), its SOS, and its blocks -- every block of every MCU of an interleaved scan,
+ * pad blocks too; a component's own blocks otherwise -- at the scan's worst bits per block, every byte stuffed, plus one rounding up
+ * to a byte that may be stuffed.  Bits per block: a first DC scan 16 + 11 = 27; a DC refinement scan 1; a first AC scan of n
+ * coefficients 26 n + 1 (a coefficient 16 + 10, a ZRL at most a bit per zero, the run symbol 16 + 8 paid by a zero coefficient Se
+ * that costs nothing else -- 27 when n = 1); an AC refinement scan 17 (n - 1) + 25 (the derivation of 1079 above for n = 63).  The file
+ * adds its head (bounded by the standard prefix: 640 bytes, grayscale 328) and EOI.  0 for an invalid script or bad dimensions.  One
+ * block's string in any scan is at most 1665 bits: the reservation of a coder segment holds every scan's segments.
+ * jpegamd_debug_progressive_script_counts (tests; synchronous, HOST pointer): the counts of the context's last script call,
+ * [pictures][tables][256] with `tables` that script's table count; JPEGAMD_ERR_ARG after any other call (and the two entries above
+ * answer JPEGAMD_ERR_ARG after a script call). */
+#define JPEGAMD_MAX_SCANS 16
+typedef struct JpegAmdScan {
+    uint8_t components;                 /* bit 0 Y, bit 1 Cb, bit 2 Cr; a grayscale file: bit 0 alone */
+    uint8_t ss, se, ah, al;
+} JpegAmdScan;
+int32_t jpegamd_validate_scan_script(const JpegAmdScan *scans, int32_t count, int32_t file_components, int32_t *bad_scan);
+int32_t jpegamd_encode_color_progressive_script_batch_async(JpegAmdEncoder *enc, const JpegAmdImage *imgs, int32_t count, int32_t subsampling,
+                                                            const JpegAmdScan *scans, int32_t scan_count, void *const *outs_dev,
+                                                            uint64_t out_capacity, uint64_t *const *out_sizes_dev, void *stream);
+int32_t jpegamd_encode_ycbcr_progressive_script_batch_async(JpegAmdEncoder *enc, const JpegAmdYCbCrImage *imgs, int32_t count,
+                                                            int32_t subsampling, int32_t sample_range, int32_t sample_format, int32_t matrix,
+                                                            const JpegAmdScan *scans, int32_t scan_count, void *const *outs_dev,
+                                                            uint64_t out_capacity, void *const *out_sizes_dev, void *stream);
+int32_t jpegamd_encode_gray_progressive_script_batch_async(JpegAmdEncoder *enc, const JpegAmdImage *imgs, int32_t count,
+                                                           const JpegAmdScan *scans, int32_t scan_count, void *const *outs_dev,
+                                                           uint64_t out_capacity, uint64_t *const *out_sizes_dev, void *stream);
+uint64_t jpegamd_max_jfif_bytes_progressive_script(int32_t width, int32_t height, int32_t subsampling, const JpegAmdScan *scans,
+                                                   int32_t scan_count);
+int32_t jpegamd_debug_progressive_script_counts(JpegAmdEncoder *enc, uint64_t *counts, int32_t tables);
+
 /* Block until the last enqueued encode on this context finished; optionally fetch stats
  * (stats may be NULL).  Returns JPEGAMD_ERR_HUFF_CAPACITY if the output did not fit. */
 int32_t jpegamd_encoder_finish(JpegAmdEncoder *enc, JpegAmdStats *stats);

@@ -145,6 +145,9 @@ struct JpegAmdEncoder {
         int pcap = 0;                       // pictures
         int plast = 0;                      // pictures of the last such call: pcounts[0, plast) are theirs
         int plast_tables = 0;               // ... and the tables of its script: pcounts is [plast][plast_tables][256]
+        int plast_script = 0;               // ... and which script it was: ProgScript::id
+        uint8_t psos[16][16] = {};          // a caller's script: the SOS segments that lie in pmeta, the key of that upload
+        bool psos_valid = false;
     } mcu;
 };
 
@@ -1613,33 +1616,91 @@ constexpr size_t kMcuScratchBudget = (size_t)4 << 30;       // coefficient plane
 
 // ---- progressive files ----
 // interleaved_batch's `progressive`: one scan / seven scans, Annex K / seven scans with runs and own tables / the ten scans of successive approximation
-constexpr int kProgNone = 0, kProgStandard = 1, kProgRuns = 2, kProgSuccessive = 3;
+constexpr int kProgNone = 0, kProgStandard = 1, kProgRuns = 2, kProgSuccessive = 3, kProgScript = 4;      // kProgScript: a caller's scan script (4.6.15)
 
-// The scan script: what every scan of a progressive file codes, in the file's order.  comp: the component of a
-// one-component scan (0 Y, 1 Cb, 2 Cr), -1 the three interleaved; table: the scan's first table in the file's table order (a DC
-// scan has two: Y, then Cb + Cr), -1 for a scan of raw bits.  The files of 4.6.12 and 4.6.13 are the first script (4.6.12 reads no
-// table numbers), the file of 4.6.14 -- libjpeg's jpeg_simple_progression for YCbCr -- the second.
-struct ProgScan { int8_t comp; uint8_t ss, se, ah, al; int8_t table; };
-struct ProgScript { int id, scans, tables; ProgScan scan[kProgScansMax]; };
-static const ProgScript kScriptSpectral = {0, kProgScans, kProgTables,
-    {{-1, 0, 0, 0, 0, 0}, {0, 1, 5, 0, 0, 2}, {1, 1, 5, 0, 0, 3}, {2, 1, 5, 0, 0, 4}, {0, 6, 63, 0, 0, 5}, {1, 6, 63, 0, 0, 6}, {2, 6, 63, 0, 0, 7}}};
-static const ProgScript kScriptSuccessive = {1, 10, 10,
-    {{-1, 0, 0, 0, 1, 0}, {0, 1, 5, 0, 2, 2}, {2, 1, 63, 0, 1, 3}, {1, 1, 63, 0, 1, 4}, {0, 6, 63, 0, 2, 5},
-     {0, 1, 63, 2, 1, 6}, {-1, 0, 0, 1, 0, -1}, {2, 1, 63, 1, 0, 7}, {1, 1, 63, 1, 0, 8}, {0, 1, 63, 1, 0, 9}}};
+// The scan script: what every scan of a progressive file codes, in the file's order.  mask: the scan's
+// components (bit 0 Y, bit 1 Cb, bit 2 Cr; 7: the three interleaved); table: the scan's first table in the file's table order (a DC
+// scan has one per table class of its components: Y, then Cb + Cr), -1 for a scan of raw bits.  The files of 4.6.12 and 4.6.13 are
+// the first script (4.6.12 reads no table numbers), the file of 4.6.14 -- libjpeg's jpeg_simple_progression for YCbCr -- the second;
+// id 2 is a caller's (4.6.15: prog_script_from), whose SOS segments are uploaded per call.  comps: the file's components, 3 or 1.
+struct ProgScan { uint8_t mask; uint8_t ss, se, ah, al; int8_t table; };
+struct ProgScript { int id, scans, tables, comps; ProgScan scan[kProgScansMax]; };
+static const ProgScript kScriptSpectral = {0, kProgScans, kProgTables, 3,
+    {{7, 0, 0, 0, 0, 0}, {1, 1, 5, 0, 0, 2}, {2, 1, 5, 0, 0, 3}, {4, 1, 5, 0, 0, 4}, {1, 6, 63, 0, 0, 5}, {2, 6, 63, 0, 0, 6}, {4, 6, 63, 0, 0, 7}}};
+static const ProgScript kScriptSuccessive = {1, 10, 10, 3,
+    {{7, 0, 0, 0, 1, 0}, {1, 1, 5, 0, 2, 2}, {4, 1, 63, 0, 1, 3}, {2, 1, 63, 0, 1, 4}, {1, 6, 63, 0, 2, 5},
+     {1, 1, 63, 2, 1, 6}, {7, 0, 0, 1, 0, -1}, {4, 1, 63, 1, 0, 7}, {2, 1, 63, 1, 0, 8}, {1, 1, 63, 1, 0, 9}}};
 static_assert(kProgScans <= kProgScansMax && kProgTables <= kProgTablesMax, "the scripts fit the kernels' maxima");
+static_assert(JPEGAMD_MAX_SCANS == kProgScansMax && JPEGAMD_MAX_SCANS == kProgTablesMax, "the public limit is the kernels'");
 static const ProgScript &prog_script(int progressive) { return progressive == kProgSuccessive ? kScriptSuccessive : kScriptSpectral; }
-// The SOS segment of a script's scan: 14 bytes for the three components (Y: tables 0 / 0, Cb and Cr: 1 / 1), kSosBytes for one.
+static int popcount3(int mask) { return (mask & 1) + ((mask >> 1) & 1) + ((mask >> 2) & 1); }
+// the tables a scan owns: a first DC scan one per table class among its components, an AC scan one, a DC refinement scan none
+static int prog_scan_tables(const ProgScan &s) { return s.ss ? 1 : (s.ah ? 0 : ((s.mask & 1) ? 1 : 0) + ((s.mask & 6) ? 1 : 0)); }
+// The SOS segment of a script's scan, 8 + 2 n bytes for n components: the selectors ascending, Y with the tables 0 / 0, Cb and Cr 1 / 1.
 static int prog_sos(const ProgScan &s, uint8_t out[16]) {
-    int n = kSosBytes;
-    if (s.comp < 0) {
-        const uint8_t sos3[14] = {0xFF, 0xDA, 0x00, 0x0C, 0x03, 0x01, 0x00, 0x02, 0x11, 0x03, 0x11, 0x00, 0x00, 0x00};
-        std::memcpy(out, sos3, sizeof(sos3));
-        n = (int)sizeof(sos3);
-    } else {
-        color_sos(1 + s.comp, out);
-    }
-    out[n - 3] = s.ss; out[n - 2] = s.se; out[n - 1] = (uint8_t)((s.ah << 4) | s.al);
+    const int nc = popcount3(s.mask);
+    int n = 0;
+    out[n++] = 0xFF; out[n++] = 0xDA; out[n++] = 0x00; out[n++] = (uint8_t)(6 + 2 * nc); out[n++] = (uint8_t)nc;
+    for (int c = 0; c < 3; ++c)
+        if ((s.mask >> c) & 1) { out[n++] = (uint8_t)(c + 1); out[n++] = c ? 0x11 : 0x00; }
+    out[n++] = s.ss; out[n++] = s.se; out[n++] = (uint8_t)((s.ah << 4) | s.al);
     return n;
+}
+
+// T.81 G.1.1.1 and libjpeg's validate_script (include/jpeg_compression.h has the rules).
+extern "C" int32_t jpegamd_validate_scan_script(const JpegAmdScan *scans, int32_t count, int32_t file_components, int32_t *bad_scan) {
+    int32_t bad_local;
+    int32_t &bad = bad_scan ? *bad_scan : bad_local;
+    bad = -1;
+    if (!scans || count < 1 || count > JPEGAMD_MAX_SCANS || (file_components != 1 && file_components != 3)) return JPEGAMD_ERR_ARG;
+    int8_t last_al[3][64];                                           // the al of the last scan that coded (component, coefficient); -1: none did
+    std::memset(last_al, -1, sizeof(last_al));
+    const int full = file_components == 3 ? 7 : 1;
+    int tables = 0;
+    for (int k = 0; k < count; ++k) {
+        const JpegAmdScan &c = scans[k];
+        bad = k;
+        if (c.components == 0 || (c.components & ~full)) return JPEGAMD_ERR_ARG;
+        if (c.ss == 0 ? c.se != 0 : (popcount3(c.components) != 1 || c.se < c.ss || c.se > 63)) return JPEGAMD_ERR_ARG;
+        if (c.al > 13 || (c.ah != 0 && c.ah != c.al + 1)) return JPEGAMD_ERR_ARG;
+        for (int j = 0; j < 3; ++j) {
+            if (!((c.components >> j) & 1)) continue;
+            if (c.ss > 0 && last_al[j][0] < 0) return JPEGAMD_ERR_ARG;           // an AC scan in front of the component's first DC scan
+            for (int i = c.ss; i <= c.se; ++i) {
+                // a first scan of it: Ah = 0; a refinement: of the bit below the last one coded (a coefficient coded down to bit 0 is done)
+                if (last_al[j][i] < 0 ? c.ah != 0 : (c.ah != (uint8_t)last_al[j][i] || c.ah != c.al + 1)) return JPEGAMD_ERR_ARG;
+                last_al[j][i] = (int8_t)c.al;
+            }
+        }
+        const ProgScan ps = {c.components, c.ss, c.se, c.ah, c.al, 0};
+        tables += prog_scan_tables(ps);
+    }
+    bad = -1;
+    if (tables > JPEGAMD_MAX_SCANS) return JPEGAMD_ERR_ARG;
+    for (int j = 0; j < file_components; ++j) if (last_al[j][0] < 0) return JPEGAMD_ERR_ARG;
+    return JPEGAMD_OK;
+}
+
+// libjpeg's jpeg_simple_progression: the ten scans of a YCbCr file (kScriptSuccessive), the six of a grayscale file.
+static const JpegAmdScan kDefaultScansColor[10] = {{7, 0, 0, 0, 1}, {1, 1, 5, 0, 2}, {4, 1, 63, 0, 1}, {2, 1, 63, 0, 1}, {1, 6, 63, 0, 2},
+                                                   {1, 1, 63, 2, 1}, {7, 0, 0, 1, 0}, {4, 1, 63, 1, 0}, {2, 1, 63, 1, 0}, {1, 1, 63, 1, 0}};
+static const JpegAmdScan kDefaultScansGray[6] = {{1, 0, 0, 0, 1}, {1, 1, 5, 0, 2}, {1, 6, 63, 0, 2}, {1, 1, 63, 2, 1}, {1, 0, 0, 1, 0}, {1, 1, 63, 1, 0}};
+// A caller's script as the internal one, tables numbered in file order; scans == NULL with count 0: the default script of the
+// file's component count.  false: the script breaks a rule.
+static bool prog_script_from(const JpegAmdScan *scans, int32_t count, int comps, ProgScript *out) {
+    if (!scans && count == 0) { scans = comps == 3 ? kDefaultScansColor : kDefaultScansGray; count = comps == 3 ? 10 : 6; }
+    if (jpegamd_validate_scan_script(scans, count, comps, nullptr) != JPEGAMD_OK) return false;
+    ProgScript sc = {};
+    sc.id = 2; sc.scans = count; sc.comps = comps;
+    for (int k = 0; k < count; ++k) {
+        ProgScan &c = sc.scan[k];
+        c.mask = scans[k].components; c.ss = scans[k].ss; c.se = scans[k].se; c.ah = scans[k].ah; c.al = scans[k].al;
+        const int nt = prog_scan_tables(c);
+        c.table = nt ? (int8_t)sc.tables : (int8_t)-1;
+        sc.tables += nt;
+    }
+    *out = sc;
+    return true;
 }
 
 // What a progressive call keeps on the device besides the slots: k_finalize's two records (scan 1's; the scans into slots share the
@@ -1655,7 +1716,7 @@ struct ProgMeta {
 };
 static_assert(sizeof(ScanStats) % 8 == 0, "the arrays behind the two records are aligned");
 constexpr size_t prog_meta_bytes(int scans) { return 2 * sizeof(ScanStats) + (size_t)scans * kMaxBatch * (8 + 16 + 8 * kMcuPicSums); }
-constexpr size_t kProgMetaSos = prog_meta_bytes(kProgScansMax), kProgMetaAlloc = kProgMetaSos + 2 * kProgScansMax * 16;
+constexpr size_t kProgMetaSos = prog_meta_bytes(kProgScansMax), kProgMetaAlloc = kProgMetaSos + 3 * kProgScansMax * 16;      // (the two built-in scripts', a caller's)
 static ProgMeta prog_meta(uint8_t *base, int scans) {
     ProgMeta m;
     m.scan_stats = reinterpret_cast<ScanStats *>(base);
@@ -1678,13 +1739,22 @@ constexpr int kProgDhtMax = 21 + 170;       // an AC table of a scan: 160 run/si
 static_assert(kProgDhtMax + kSosBytes <= kMcuPrefixSlot, "a scan's header fits its slot");
 static_assert(kMaxBlockBitsRefine <= 63 * 27, "a refinement scan's block is within the slot's 27 bits a coefficient");
 struct ProgSlots { uint64_t off[kProgScansMax], cap[kProgScansMax], pic_bytes; };
+// the blocks a scan codes: every block of every MCU of an interleaved scan, pad blocks included; a component's own blocks of a scan of one
+static uint64_t prog_scan_blocks(const McuGeometry &g, const ProgScan &c) {
+    const uint64_t mcus = (uint64_t)g.mx * g.my;
+    if (popcount3(c.mask) == 1) return c.mask == 1 ? (uint64_t)g.bw * g.bh : mcus;
+    return mcus * (uint64_t)((c.mask & 1 ? g.hs * g.vs : 0) + popcount3(c.mask & 6));
+}
+// the DHT segments in front of a scan's SOS at most: a DC table 33 bytes, an AC table kProgDhtMax
+static uint64_t prog_scan_dht_max(const ProgScan &c) { return c.ss ? kProgDhtMax : 33u * (uint64_t)prog_scan_tables(c); }
 static ProgSlots prog_slots(const McuGeometry &g, const ProgScript &sc, bool own_tables = false) {
     ProgSlots s = {};
     for (int k = 1; k < sc.scans; ++k) {
         const ProgScan &c = sc.scan[k];
-        const uint64_t nb = c.comp < 0 ? (uint64_t)g.mx * g.my * (uint64_t)(g.hs * g.vs + 2) : (c.comp == 0 ? (uint64_t)g.bw * g.bh : (uint64_t)g.mx * g.my);
-        const uint64_t bits = c.comp < 0 ? 1u : (uint64_t)(c.se - c.ss + 1) * 27u;      // (prog_band_bits for the bands of 4.6.12)
-        s.cap[k] = (own_tables && c.table >= 0 ? kProgDhtMax : 0) + (c.comp < 0 ? 14 : kSosBytes) + scan_bound(nb, bits) + 2;
+        const uint64_t nb = prog_scan_blocks(g, c);
+        // a DC scan (4.6.15: a first one may live in a slot): 27 bits a block, a refinement 1; (prog_band_bits for the bands of 4.6.12)
+        const uint64_t bits = c.ss == 0 ? (c.ah ? 1u : 27u) : (uint64_t)(c.se - c.ss + 1) * 27u;
+        s.cap[k] = (own_tables ? prog_scan_dht_max(c) : 0) + (8 + 2 * popcount3(c.mask)) + scan_bound(nb, bits) + 2;
         s.off[k] = s.pic_bytes;
         s.pic_bytes += round_up((size_t)s.cap[k] + 64, 256);
     }
@@ -1778,6 +1848,7 @@ static int32_t mcu_alloc(JpegAmdEncoder *e, const McuGeometry &g, int group, boo
 // Cr: 1 / 1).  One component (kSubNone): the grayscale prefix up to its two DHTs, [DRI,] its SOS.
 // progressive (colour, no restart intervals): the frame header's marker is SOF2, and the SOS is the DC scan's (Ss = Se = 0).
 constexpr int kColorSofOffset = 2 + 18 + 134;       // SOI, APP0, DQT with two tables
+constexpr int kGraySofOffset = 2 + 18 + 69;         // ... with one: the one-component head (a grayscale progressive file)
 static int32_t prepare_mcu_prefix(JpegAmdEncoder *e, const JpegAmdImage *img, int sub, int restart, bool progressive = false) {
     auto &m = e->mcu;
     const int q = clamp_quality(img->quality);
@@ -1802,9 +1873,10 @@ static int32_t prepare_mcu_prefix(JpegAmdEncoder *e, const JpegAmdImage *img, in
         n += sizeof(dri);
     }
     if (progressive) {
-        if (sub == kSubNone || restart || hdr[kColorSofOffset] != 0xFF || hdr[kColorSofOffset + 1] != 0xC0) return JPEGAMD_ERR_ARG;
-        hdr[kColorSofOffset + 1] = 0xC2;
-        sos[kMcuSosBytes - 2] = 0x00;                                   // Se
+        const int sof = sub == kSubNone ? kGraySofOffset : kColorSofOffset;
+        if (restart || hdr[sof] != 0xFF || hdr[sof + 1] != 0xC0) return JPEGAMD_ERR_ARG;
+        hdr[sof + 1] = 0xC2;
+        sos[nsos - 2] = 0x00;                                           // Se
     }
     std::memcpy(hdr + n, sos, nsos);
     if (int32_t rc = wait_pending(e)) return rc;
@@ -1826,6 +1898,21 @@ static int32_t prog_alloc(JpegAmdEncoder *e, size_t slot_bytes) {
     return grow_scratch(e, &m.pslots, &m.pslots_cap, slot_bytes);
 }
 
+// The SOS segments of a caller's script behind the built-in scripts': uploaded when they differ from what lies there.
+static int32_t prog_upload_sos(JpegAmdEncoder *e, const ProgScript &sc) {
+    auto &m = e->mcu;
+    uint8_t sos[kProgScansMax][16] = {};
+    for (int k = 0; k < sc.scans; ++k) prog_sos(sc.scan[k], sos[k]);
+    static_assert(sizeof(sos) == sizeof(m.psos), "the key is the upload");
+    if (m.psos_valid && std::memcmp(sos, m.psos, sizeof(sos)) == 0) return JPEGAMD_OK;
+    if (int32_t rc = wait_pending(e)) return rc;                    // (a call in flight may still read the segments)
+    m.psos_valid = false;
+    HIP_TRY(hipMemcpy(m.pmeta + kProgMetaSos + (size_t)sc.id * kProgScansMax * 16, sos, sizeof(sos), hipMemcpyHostToDevice));
+    std::memcpy(m.psos, sos, sizeof(sos));
+    m.psos_valid = true;
+    return JPEGAMD_OK;
+}
+
 // ... and of a call that makes its own tables (4.6.13), for `pictures` pictures.
 static int32_t prog_tables_alloc(JpegAmdEncoder *e, int pictures) {
     auto &m = e->mcu;
@@ -1845,10 +1932,20 @@ static int32_t prog_tables_alloc(JpegAmdEncoder *e, int pictures) {
 }
 
 // A script's scan as the one-component (comp >= 0) form of the group's three-component arguments.
+// A scan of two components (4.6.15): the group's grid with the scan's own MCU; a grayscale file's scans: the group's arguments are the
+// one-component form already.
 static bool prog_scan_args(const McuGeometry &g, const McuSegArgs &sa3, const ProgScan &c, McuSegArgs *out) {
-    const int comp = c.comp;
+    const int comp = g.comps == 3 && popcount3(c.mask) == 1 ? (c.mask == 1 ? 0 : (c.mask == 2 ? 1 : 2)) : -1;
     McuSegArgs sa = sa3;
     sa.ah = c.ah; sa.al = c.al;
+    if (g.comps == 1) { sa.ss = c.ss; sa.se = c.se; }
+    if (g.comps == 3 && popcount3(c.mask) == 2) {
+        sa.comps = 2; sa.mask = c.mask;
+        sa.seg_mcus = kSegBlocks / mcu_blocks_per_mcu2(g.hs, g.vs, c.mask);
+        sa.num_segs = (int)(((int64_t)g.mx * g.my + sa.seg_mcus - 1) / sa.seg_mcus);
+        sa.num_segs_pad = (sa.num_segs + kSegGroup - 1) / kSegGroup * kSegGroup;
+        if (sa.num_segs_pad > g.num_segs_pad) return false;         // (a shorter MCU: no more segments than the three-component scan has)
+    }
     if (comp >= 0) {                                                 // ONE component: its plane, its block grid, its table class
         sa.coef = sa3.coef + (comp == 0 ? 0 : (comp == 1 ? sa3.cb_off : sa3.cr_off));
         sa.bw = sa.mx = comp ? g.mx : g.bw; sa.bh = sa.my = comp ? g.my : g.bh;
@@ -1894,16 +1991,17 @@ static int progressive_runs_scans(JpegAmdEncoder *e, const McuGeometry &g, const
     std::memset(&pa, 0, sizeof(pa));
     pa.res = ha.res; pa.tabs = m.ptabs + (size_t)first * tables * 272;
     pa.hdr_out = m.phdr; pa.hdr_len = m.phdr_len; pa.pictures = count; pa.first = first;
-    pa.hdr = m.hdr; pa.head_len = m.hdr_for.len - kMcuSosBytes - kStdDhtBytes;
+    pa.hdr = m.hdr; pa.head_len = g.comps == 1 ? m.hdr_for.len - kSosBytes - kStdDhtBytesGray : m.hdr_for.len - kMcuSosBytes - kStdDhtBytes;
     pa.sos = prog_meta_sos(m.pmeta, sc);
     pa.scans = sc.scans; pa.tables = sc.tables;
     for (int k = 0; k < sc.scans; ++k) {
         const ProgScan &c = sc.scan[k];
-        pa.sos_len[k] = (uint8_t)(c.comp < 0 ? kMcuSosBytes : kSosBytes);
+        pa.sos_len[k] = (uint8_t)(8 + 2 * popcount3(c.mask));
         if (c.table < 0) { pa.bare |= 1u << k; continue; }
-        for (int t = c.table; t < c.table + (c.comp < 0 ? 2 : 1); ++t) {
+        const int nt = prog_scan_tables(c);
+        for (int t = c.table; t < c.table + nt; ++t) {              // Tc/Th: 0x00 / 0x01 the DC tables of Y / chroma, 0x10 / 0x11 the AC tables
             pa.table_scan[t] = (uint8_t)k;
-            pa.table_id[t] = (uint8_t)(c.comp < 0 ? t - c.table : (c.comp == 0 ? 0x10 : 0x11));
+            pa.table_id[t] = (uint8_t)((c.ss ? 0x10 : 0x00) | ((nt == 2 ? t > c.table : !(c.mask & 1)) ? 1 : 0));
         }
     }
     if (int err = launch_prog_tables(pa, n, stream)) return err;
@@ -1911,7 +2009,7 @@ static int progressive_runs_scans(JpegAmdEncoder *e, const McuGeometry &g, const
     for (int k = 0; k < sc.scans; ++k) {
         McuSegArgs &s = sa[k];
         const int table = sc.scan[k].table < 0 ? 0 : sc.scan[k].table;   // (a scan of raw bits reads no table: any that exists)
-        s.huff_y = pa.tabs + (size_t)table * 272; s.huff_c = pa.tabs + (size_t)(table + (sc.scan[k].comp < 0 ? 1 : 0)) * 272; s.huff_stride = (uint32_t)(tables * 272);
+        s.huff_y = pa.tabs + (size_t)table * 272; s.huff_c = pa.tabs + (size_t)(table + (prog_scan_tables(sc.scan[k]) == 2 ? 1 : 0)) * 272; s.huff_stride = (uint32_t)(tables * 272);
         s.runs = 1;
         s.sums = meta.sums + (size_t)k * kMaxBatch * 2;
         s.status = &meta.scan_stats[k ? 1 : 0].status;
@@ -2004,15 +2102,17 @@ static int progressive_scans(JpegAmdEncoder *e, const McuGeometry &g, const Prog
 // tapped and coded, no chroma launch, two tables; always through the restart writer (the caller sends the plain Annex K file elsewhere).
 static int32_t interleaved_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, const PlaneSet &px, int32_t count, int32_t subsampling, int32_t restart,
                                  void *const *outs_dev, uint64_t out_capacity, uint64_t *const *out_sizes_dev, void *stream_,
-                                 const YccSource *ycc_in = nullptr, int progressive = kProgNone) {
+                                 const YccSource *ycc_in = nullptr, int progressive = kProgNone, const ProgScript *user_script = nullptr) {
     // `progressive`: the same taps, plane pass, matrix pass and grouping; behind a group's taps its seven scans
     // (progressive_scans) in place of k_mcu_segments, k_finalize and k_mcu_totals.  Colour, the Annex K tables, no restart intervals.
     // kProgRuns: histograms, tables and the restart writer as well (progressive_runs_scans); the context's Huffman
     // mode is neither read nor changed.
     // kProgSuccessive: kProgRuns' steps over the script of ten scans.
     const bool runs = progressive >= kProgRuns;
-    const ProgScript &script = prog_script(progressive);
-    if (progressive && (restart || subsampling == kSubNone || (!runs && e->huffman != JPEGAMD_HUFFMAN_STANDARD))) return JPEGAMD_ERR_ARG;
+    // kProgScript: kProgRuns' steps over the caller's script, which the entry validated; colour or grayscale.
+    if ((progressive == kProgScript) != (user_script != nullptr)) return JPEGAMD_ERR_ARG;
+    const ProgScript &script = user_script ? *user_script : prog_script(progressive);
+    if (progressive && (restart || script.comps != (subsampling == kSubNone ? 1 : 3) || (!runs && e->huffman != JPEGAMD_HUFFMAN_STANDARD))) return JPEGAMD_ERR_ARG;
     const bool mx = ycc_in && ycc_in->matrix == JPEGAMD_MATRIX_BT709;
     const YccSource *const ycc = mx ? nullptr : ycc_in;               // what the launches read: the caller's planes, or the scratch
     const bool planar = g0.channel_order == kOrderPlanar;
@@ -2061,6 +2161,8 @@ static int32_t interleaved_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, cons
         rc = prog_alloc(e, (size_t)group * (size_t)slots.pic_bytes);
         if (rc) return rc;
         rc = runs ? prog_tables_alloc(e, count) : JPEGAMD_OK;
+        if (rc) return rc;
+        rc = user_script ? prog_upload_sos(e, script) : JPEGAMD_OK;
         if (rc) return rc;
     }
     unsigned long long *pic = reinterpret_cast<unsigned long long *>(c.bmeta + kBatchMetaStats);
@@ -2181,7 +2283,7 @@ static int32_t interleaved_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, cons
         if (launch_mcu_totals(ta, n, stream)) return JPEGAMD_ERR_HIP;
     }
     if (optimized) m.hlast = count;
-    if (runs) { m.plast = count; m.plast_tables = script.tables; }
+    if (runs) { m.plast = count; m.plast_tables = script.tables; m.plast_script = script.id; }
     if (cev) HIP_TRY(hipEventRecord(cev[21], stream));
     return enqueued(e, stream, count * g.num_segs_pad, cev != nullptr, true);
 }
@@ -2248,7 +2350,7 @@ static bool restart_valid(int32_t restart) { return restart >= 0 && restart <= 6
 // `count` packed pictures in one scan: the argument checks (`px4`: the entry takes RGBA / BGRA as well), then the interleaved batch.
 static int32_t interleaved_pixels(JpegAmdEncoder *e, const JpegAmdImage *imgs, int32_t count, int32_t subsampling, int32_t restart_interval, bool px4,
                                   void *const *outs_dev, uint64_t out_capacity, uint64_t *const *out_sizes_dev, void *stream_,
-                                  int progressive = kProgNone) {
+                                  int progressive = kProgNone, const ProgScript *user_script = nullptr) {
     // the arguments first: nothing of the context is read before they are known to be good
     if (!restart_valid(restart_interval)) return JPEGAMD_ERR_ARG;
     if (!e || !imgs || !outs_dev || !out_sizes_dev || count < 1 || count > kMaxBatch) return JPEGAMD_ERR_ARG;
@@ -2260,7 +2362,7 @@ static int32_t interleaved_pixels(JpegAmdEncoder *e, const JpegAmdImage *imgs, i
         return JPEGAMD_ERR_ARG;
     PlaneSet ps;
     if (int32_t rc = uniform_batch_args(imgs, count, outs_dev, out_sizes_dev, &ps)) return rc;
-    return interleaved_batch(e, g0, ps, count, subsampling, restart_interval, outs_dev, out_capacity, out_sizes_dev, stream_, nullptr, progressive);
+    return interleaved_batch(e, g0, ps, count, subsampling, restart_interval, outs_dev, out_capacity, out_sizes_dev, stream_, nullptr, progressive, user_script);
 }
 
 // Progressive colour files of `count` RGB / BGR / RGBA / BGRA pictures: the argument checks of
@@ -2282,14 +2384,14 @@ extern "C" int32_t jpegamd_encode_color_progressive_optimized_batch_async(JpegAm
 
 // Tests: the symbol counts of the context's last call with per-scan tables, [pictures][8][256] in the file's table order: Y DC,
 // chroma DC, then the AC tables of the scans 2 .. 7.  JPEGAMD_ERR_ARG when the context made no such call.  Synchronous.
-static int32_t debug_prog_counts(JpegAmdEncoder *e, uint64_t *counts, int tables) {
-    if (!e || !counts || e->mcu.plast < 1 || e->mcu.plast_tables != tables) return JPEGAMD_ERR_ARG;
+static int32_t debug_prog_counts(JpegAmdEncoder *e, uint64_t *counts, int tables, int script) {
+    if (!e || !counts || e->mcu.plast < 1 || e->mcu.plast_tables != tables || e->mcu.plast_script != script) return JPEGAMD_ERR_ARG;
     if (int32_t rc = wait_pending(e)) return rc;
     static_assert(sizeof(uint64_t) == sizeof(unsigned long long), "the counts are copied as they lie");
     HIP_TRY(hipMemcpy(counts, e->mcu.pcounts, (size_t)e->mcu.plast * (size_t)tables * 256 * sizeof(uint64_t), hipMemcpyDeviceToHost));
     return JPEGAMD_OK;
 }
-extern "C" int32_t jpegamd_debug_progressive_counts(JpegAmdEncoder *e, uint64_t *counts) { return debug_prog_counts(e, counts, kScriptSpectral.tables); }
+extern "C" int32_t jpegamd_debug_progressive_counts(JpegAmdEncoder *e, uint64_t *counts) { return debug_prog_counts(e, counts, kScriptSpectral.tables, kScriptSpectral.id); }
 
 // Progressive files with successive approximation: the ten scans of libjpeg's jpeg_simple_progression, a table per
 // scan, end-of-band runs.  The arguments, refusals, batching, capacity behaviour and statistics of the entry above; the context's
@@ -2303,7 +2405,7 @@ extern "C" int32_t jpegamd_encode_color_progressive_successive_batch_async(JpegA
 // Tests: the symbol counts of the context's last call of the successive entries, [pictures][10][256] in the file's table order.
 // JPEGAMD_ERR_ARG when the context's last call with per-scan tables was not one of them.  Synchronous.
 extern "C" int32_t jpegamd_debug_progressive_successive_counts(JpegAmdEncoder *e, uint64_t *counts) {
-    return debug_prog_counts(e, counts, kScriptSuccessive.tables);
+    return debug_prog_counts(e, counts, kScriptSuccessive.tables, kScriptSuccessive.id);
 }
 
 extern "C" int32_t jpegamd_encode_color_interleaved_restart_batch_async(JpegAmdEncoder *e, const JpegAmdImage *imgs, int32_t count, int32_t subsampling,
@@ -2436,6 +2538,80 @@ extern "C" int32_t jpegamd_encode_ycbcr_progressive_successive_batch_async(JpegA
     if (int32_t rc = ycbcr_args(e, imgs, count, subsampling, sample_range, sample_format, matrix, outs_dev, out_sizes_dev, true, &g0, &ps, &ycc, sizes))
         return rc;
     return interleaved_batch(e, g0, ps, count, subsampling, 0, outs_dev, out_capacity, sizes, stream_, &ycc, kProgSuccessive);
+}
+
+// ---- a caller's scan script, and grayscale progressive files ----
+// The script is validated first: a refused call allocates and launches nothing and leaves the context as it was.
+extern "C" int32_t jpegamd_encode_color_progressive_script_batch_async(JpegAmdEncoder *e, const JpegAmdImage *imgs, int32_t count, int32_t subsampling,
+                                                                       const JpegAmdScan *scans, int32_t scan_count, void *const *outs_dev,
+                                                                       uint64_t out_capacity, uint64_t *const *out_sizes_dev, void *stream_) {
+    ProgScript sc;
+    if (!prog_script_from(scans, scan_count, 3, &sc)) return JPEGAMD_ERR_ARG;
+    return interleaved_pixels(e, imgs, count, subsampling, 0, true, outs_dev, out_capacity, out_sizes_dev, stream_, kProgScript, &sc);
+}
+
+extern "C" int32_t jpegamd_encode_ycbcr_progressive_script_batch_async(JpegAmdEncoder *e, const JpegAmdYCbCrImage *imgs, int32_t count, int32_t subsampling,
+                                                                       int32_t sample_range, int32_t sample_format, int32_t matrix,
+                                                                       const JpegAmdScan *scans, int32_t scan_count, void *const *outs_dev,
+                                                                       uint64_t out_capacity, void *const *out_sizes_dev, void *stream_) {
+    ProgScript sc;
+    if (!prog_script_from(scans, scan_count, 3, &sc)) return JPEGAMD_ERR_ARG;
+    JpegAmdImage g0;
+    PlaneSet ps;
+    YccSource ycc;
+    uint64_t *sizes[kMaxBatch];
+    if (int32_t rc = ycbcr_args(e, imgs, count, subsampling, sample_range, sample_format, matrix, outs_dev, out_sizes_dev, true, &g0, &ps, &ycc, sizes))
+        return rc;
+    return interleaved_batch(e, g0, ps, count, subsampling, 0, outs_dev, out_capacity, sizes, stream_, &ycc, kProgScript, &sc);
+}
+
+// The grayscale file (SOF2, one component) of pictures in any of the five channel orders: the luma of the gray-scan entry, no chroma
+// launch, no pad blocks; the DC tables are 0x00, the AC tables 0x10.
+extern "C" int32_t jpegamd_encode_gray_progressive_script_batch_async(JpegAmdEncoder *e, const JpegAmdImage *imgs, int32_t count, const JpegAmdScan *scans,
+                                                                      int32_t scan_count, void *const *outs_dev, uint64_t out_capacity,
+                                                                      uint64_t *const *out_sizes_dev, void *stream_) {
+    ProgScript sc;
+    if (!prog_script_from(scans, scan_count, 1, &sc)) return JPEGAMD_ERR_ARG;
+    if (!e || !imgs || !outs_dev || !out_sizes_dev || count < 1 || count > kMaxBatch) return JPEGAMD_ERR_ARG;
+    ImageDesc im;
+    if (int32_t rc = describe(nullptr, &imgs[0], &im, kSegTiles, kAcceptPx4)) return rc;
+    PlaneSet ps;
+    if (int32_t rc = uniform_batch_args(imgs, count, outs_dev, out_sizes_dev, &ps)) return rc;
+    return interleaved_batch(e, imgs[0], ps, count, kSubNone, 0, outs_dev, out_capacity, out_sizes_dev, stream_, nullptr, kProgScript, &sc);
+}
+
+// The bound of a file with a caller's script, scan by scan.  A scan is its DHT segments at most (a DC table 33 bytes: 21 + 12
+// symbols; an AC table kProgDhtMax), its SOS (8 + 2 n bytes for n components), and its blocks (prog_scan_blocks: pad blocks
+// included where the scan is interleaved) at the scan's worst bits per block, every byte stuffed, with ONE rounding up to a byte that
+// may be stuffed (scan_bound).  The bits per block: a first DC scan 16 + 11 = 27; a DC refinement scan 1; a first AC scan 26 per
+// coefficient of the band (16 + 10; a ZRL is at most a bit per zero) and 1 more -- the run's symbol, 16 + 8, is paid by a zero
+// coefficient se that costs nothing else, which is 27 when the band is that one coefficient; an AC refinement scan 17 per
+// coefficient, the run's symbol at a coefficient se that costs 1: 17 (n - 1) + 25 (kMaxBlockBitsRefine's derivation for n
+// coefficients).  The file adds its head (no more than the whole standard prefix) and EOI.
+static uint64_t prog_scan_block_bits(const ProgScan &c) {
+    const uint64_t n = (uint64_t)(c.se - c.ss + 1);
+    return c.ss == 0 ? (c.ah ? 1u : 27u) : (c.ah ? 17u * (n - 1) + 25u : 26u * n + 1u);
+}
+static_assert(27 <= kMaxBlockBitsColor && 63 * 26 + 1 <= kMaxBlockBitsColor && 62 * 17 + 25 == kMaxBlockBitsRefine && kMaxBlockBitsRefine <= kMaxBlockBitsColor,
+              "one block's string of any scan of a script fits the reservation of a coder segment");
+static_assert(26 * 63 + 1 <= 27 * 63 && 17 * 0 + 25 <= 27 && 26 + 1 <= 27, "a scan at its bound fits its slot (prog_slots: 27 bits a coefficient)");
+extern "C" uint64_t jpegamd_max_jfif_bytes_progressive_script(int32_t width, int32_t height, int32_t subsampling, const JpegAmdScan *scans, int32_t scan_count) {
+    if (width <= 0 || height <= 0 || width > 65535 || height > 65535 || (subsampling != kSubNone && !sub_valid(subsampling))) return 0;
+    ProgScript sc;
+    if (!prog_script_from(scans, scan_count, subsampling == kSubNone ? 1 : 3, &sc)) return 0;
+    const McuGeometry g = mcu_geometry(width, height, subsampling);
+    uint64_t total = (subsampling == kSubNone ? (uint64_t)JPEGAMD_JFIF_PREFIX_BYTES : (uint64_t)kColorPrefixMax) + 2 + 16;
+    for (int k = 0; k < sc.scans; ++k) {
+        const ProgScan &c = sc.scan[k];
+        total += prog_scan_dht_max(c) + (uint64_t)(8 + 2 * popcount3(c.mask)) + scan_bound(prog_scan_blocks(g, c), prog_scan_block_bits(c));
+    }
+    return total;
+}
+
+// Tests: the symbol counts of the context's last call of the script entries, [pictures][tables][256] in the file's table order;
+// `tables`: the tables of that call's script.  JPEGAMD_ERR_ARG when the last call with per-scan tables was not one of them.
+extern "C" int32_t jpegamd_debug_progressive_script_counts(JpegAmdEncoder *e, uint64_t *counts, int32_t tables) {
+    return debug_prog_counts(e, counts, tables, 2);
 }
 
 // Host-only (tests): whether the plain build has the k_tile_encode instantiation (taps, layout, chroma tables, expand): 1 or 0.  No

@@ -422,7 +422,15 @@ struct McuSegArgs {
     // successive approximation (`runs` alone): ah = 0, al > 0 a first scan over the point transform by al; ah = al + 1
     // a refinement scan that codes bit al.  0, 0: the scans of 4.6.12 / 4.6.13.  (They lie in what was the struct's padding.)
     uint8_t ah, al;
-};int launch_mcu_segments(const McuSegArgs &a, void *stream);
+    // a caller's scan script: comps = 2, the DC scan of TWO interleaved components -- bit 0 Y, bit 1 Cb, bit 2 Cr,
+    // two of them: Y as hs x vs blocks with pad blocks, a chroma component one block; the MCU grid, planes and strides are the
+    // three-component scan's.  huff_y: the table of the scan's first component class, huff_c: of its second ({Cb, Cr}: not read).
+    // comps = 1 with ss = se = 0: the DC scan of one component over its own block grid.  Not read by the other scans.
+    uint8_t mask;
+};
+// blocks per MCU and MCUs per segment of a two-component DC scan
+constexpr int mcu_blocks_per_mcu2(int hs, int vs, int mask) { return (mask & 1 ? hs * vs : 0) + ((mask >> 1) & 1) + ((mask >> 2) & 1); }
+int launch_mcu_segments(const McuSegArgs &a, void *stream);
 
 // Progressive colour files: kProgScans scans by spectral selection, Ah = Al = 0 -- the DC scan of the three
 // components in MCU order (the segments, pad blocks and predictors of the one-scan file), then the bands 1 .. 5 and 6 .. 63 of Y, Cb
@@ -433,7 +441,7 @@ struct McuSegArgs {
 // A block of a band is at most 27 bits per coefficient of the band (a ZRL pays for sixteen zeros, EOB for a zero coefficient se),
 // a DC difference at most 11 + 11 bits: together no more than kMaxBlockBitsColor, the bound of a whole block.
 constexpr int kProgScans = 7;
-constexpr int kProgScansMax = 10, kProgTablesMax = 10;          // the most scans and tables a scan script has; the kernels take the counts at run time
+constexpr int kProgScansMax = 16, kProgTablesMax = 16;          // the most scans and tables a scan script has (JPEGAMD_MAX_SCANS); the kernels take the counts at run time
 constexpr int kProgBandSs[2] = {1, 6}, kProgBandSe[2] = {5, 63};
 constexpr int prog_band_bits(int band) { return (kProgBandSe[band] - kProgBandSs[band] + 1) * 27; }
 static_assert(22 + prog_band_bits(0) + prog_band_bits(1) == kMaxBlockBitsColor, "the three bands of a block cost no more than the block's bound");
@@ -445,7 +453,7 @@ struct ScansConcatArgs {
     int32_t batch;
     int32_t prefix_len;                 // bytes in front of scan 1's entropy-coded segment: the file's prefix with SOS 1
     int32_t last_of_call;               // the launch's last picture is the call's last: its size is what finish reports
-    int32_t scans;                      // the file's scans: 2 .. kProgScansMax
+    int32_t scans;                      // the file's scans: 1 .. kProgScansMax (one scan: nothing is appended)
     const uint64_t *size;               // [scans][kMaxBatch] k_finalize's: scan 1 with the prefix, the others with their SOS, the last with EOI
     const uint8_t *slots;               // scan k >= 1 (from 0) of picture q at slots + q pic_bytes + slot_off[k]; multiples of 16
     uint64_t pic_bytes, slot_off[kProgScansMax];
@@ -476,9 +484,9 @@ struct ProgTablesArgs {
     const uint8_t *hdr;                 // the standard progressive prefix: its head (SOI .. SOF2) is the file's
     int32_t head_len;
     const uint8_t *sos;                 // the SOS of scan k (from 0) at sos + 16 k, sos_len[k] bytes
-    int32_t scans, tables;              // the script's: <= kProgScansMax, 2 .. kProgTablesMax
+    int32_t scans, tables;              // the script's: 1 .. kProgScansMax, 1 .. kProgTablesMax
     uint32_t bare;                      // bit k: scan k has no table -- its header is its SOS alone
-    uint8_t table_scan[kProgTablesMax]; // the scan (from 0) of table t: non-decreasing, tables 0 and 1 the DC tables of scan 0
+    uint8_t table_scan[kProgTablesMax]; // the scan (from 0) of table t: non-decreasing, table 0 (and 1, when it has two) the DC tables of scan 0; any scan may own two
     uint8_t table_id[kProgTablesMax];   // its Tc/Th byte
     uint8_t sos_len[kProgScansMax];
 };

@@ -32,6 +32,8 @@
 // ... with successive approximation: four more walks -- the DC and a band by a point transform, one bit of the DC,
 // one bit of a band (T.81 G.1.2.3) --, raw bits through an outlet of their own that the counting kernel does not see, and a scan and
 // table count that k_prog_tables and k_scans_concat take at run time.
+// ... with a scan script of the caller's, and grayscale files: the DC scan of ONE component (kComps = 1 with the DC
+// walks) and of TWO interleaved components (kComps = 2, McuSegArgs::mask) as instantiations of their own, up to 16 scans and tables.
 #include <algorithm>
 
 #include <hip/hip_ext.h>
@@ -278,7 +280,9 @@ __device__ __forceinline__ McuBlock mcu_block(const McuSegArgs &a, const int16_t
         b.pred = m > mstart ? (int)base[(size_t)(m - 1) * 64] : 0;
         return b;
     }
-    const int ny = a.hs * a.vs;
+    // kComps = 2 (the DC scan of two interleaved components, a.mask): the three-component MCU without the
+    // component that is not in the scan -- Y's blocks, pad blocks and predictors as they are, a chroma component its one block.
+    const int ny = kComps == 2 && !(a.mask & 1) ? 0 : a.hs * a.vs;
     const auto y_at = [&](int mm, int jj, bool *pad) {           // Y block jj of MCU mm, clamped to the picture's blocks
         const int my_ = mm / a.mx, mx_ = mm - my_ * a.mx;
         const int v = jj / a.hs, u = jj - v * a.hs;
@@ -291,8 +295,9 @@ __device__ __forceinline__ McuBlock mcu_block(const McuSegArgs &a, const int16_t
         b.p = reinterpret_cast<const uint4 *>(y_at(m, j, &b.pad));
         b.pred = j > 0 ? (int)*y_at(m, j - 1, nullptr) : (m > mstart ? (int)*y_at(m - 1, ny - 1, nullptr) : 0);
     } else {
-        const int16_t *plane = base + (j == ny ? a.cb_off : a.cr_off);
-        b.chroma = true; b.pad = false;
+        const bool cb = kComps == 2 ? (a.mask == 6 ? j == 0 : (a.mask & 2) != 0) : j == ny;
+        const int16_t *plane = base + (cb ? a.cb_off : a.cr_off);
+        b.chroma = kComps == 2 ? ny != 0 : true; b.pad = false;       // (the table class: {Cb, Cr} code with the scan's one table)
         b.p = reinterpret_cast<const uint4 *>(plane + (size_t)m * 64);
         b.pred = m > mstart ? (int)plane[(size_t)(m - 1) * 64] : 0;
     }
@@ -361,8 +366,8 @@ __device__ __forceinline__ void mcu_code_segments(const McuSegArgs &a, uint32_t 
         return;
     }
     const int16_t *base = a.coef + (size_t)image * a.pic_stride;
-    const int bpm = kComps == 1 ? 1 : a.hs * a.vs + 2;
-    const int nblk = nmcu * bpm;                                    // 3 .. 256 (one component: 1 .. 256)
+    const int bpm = kComps == 1 ? 1 : (kComps == 2 ? mcu_blocks_per_mcu2(a.hs, a.vs, a.mask) : a.hs * a.vs + 2);
+    const int nblk = nmcu * bpm;                                    // 3 .. 256 (two components: 2 .. 256, one: 1 .. 256)
     uint32_t *win = s_win[wave];
 
     // ---- pass 1: bit lengths, then the blocks' places ----
@@ -503,9 +508,9 @@ __global__ __launch_bounds__(64 * kWavesM) void k_mcu_segments(const McuSegArgs 
 // coefficient se: kMaxBlockBitsOptimized): seg_cap_words(kSegTiles) holds every segment, as it holds k_mcu_segments'.
 template <int kComps, int kWalk>
 __global__ __launch_bounds__(64 * kWavesM) void k_mcu_band_segments(const McuSegArgs a) {
-    static_assert((kComps == 3 && (kWalk == kWalkDc || kWalk == kWalkDcPoint || kWalk == kWalkDcRefine)) ||
+    static_assert(((kComps == 3 || kComps == 2 || kComps == 1) && (kWalk == kWalkDc || kWalk == kWalkDcPoint || kWalk == kWalkDcRefine)) ||
                   (kComps == 1 && (kWalk == kWalkBand || kWalk == kWalkBandRuns || kWalk == kWalkBandPoint || kWalk == kWalkBandRefine)),
-                  "the scans of DESIGN.md 4.6.12, 4.6.13 and 4.6.14");
+                  "the scans of DESIGN.md 4.6.12 .. 4.6.15");
     static_assert(22 <= kMaxBlockBitsColor && 63 * 27 <= kMaxBlockBitsColor, "a block of either walk fits the reservation of a whole block");
     // successive approximation: a point transform only shortens amplitudes; a refinement block is kMaxBlockBitsRefine, the DC bit 1
     static_assert(kMaxBlockBitsRefine <= kMaxBlockBitsOptimized && kMaxBlockBitsOptimized <= kMaxBlockBitsColor, "one block's string in any single scan fits the segment's reservation");
@@ -517,9 +522,11 @@ __global__ __launch_bounds__(64 * kWavesM) void k_mcu_band_segments(const McuSeg
 // What both walks of the coefficients need of their arguments: every MCU lies in a segment, and the widest segment fits its reservation.
 // A scan of one component (comps = 1): the MCU grid is the block grid, and a segment is kSegBlocks blocks.
 static bool mcu_seg_args_ok(const McuSegArgs &a) {
-    if (a.comps != 1 && a.comps != 3) return false;
+    if (a.comps != 1 && a.comps != 2 && a.comps != 3) return false;
     if (a.comps == 1 && (a.hs != 1 || a.vs != 1 || a.mx != a.bw || a.my != a.bh || a.seg_mcus != kSegBlocks)) return false;
-    const int bpm = mcu_blocks_per_mcu(a.hs, a.vs, a.comps);
+    // two components (a DC scan of a caller's script): two of Y, Cb, Cr; the three-component grid, no restart intervals
+    if (a.comps == 2 && ((a.mask != 3 && a.mask != 5 && a.mask != 6) || a.restart != 0 || a.hs < 1 || a.hs > 2 || a.vs < 1 || a.vs > 2)) return false;
+    const int bpm = a.comps == 2 ? mcu_blocks_per_mcu2(a.hs, a.vs, a.mask) : mcu_blocks_per_mcu(a.hs, a.vs, a.comps);
     if (a.seg_mcus < 1 || a.seg_mcus * bpm > kSegBlocks || a.num_segs_pad % kSegGroup != 0 || a.num_segs > a.num_segs_pad)
         return false;
     static_assert(kSegGroup % kWavesM == 0, "a workgroup's segments belong to one picture");
@@ -533,7 +540,7 @@ static bool mcu_seg_args_ok(const McuSegArgs &a) {
 int launch_mcu_segments(const McuSegArgs &a, void *stream) {
     const int n = a.batch * a.num_segs_pad;
     if (n <= 0) return 0;
-    if (!mcu_seg_args_ok(a)) return (int)hipErrorInvalidValue;
+    if (a.comps == 2 || !mcu_seg_args_ok(a)) return (int)hipErrorInvalidValue;    // (two components: a progressive DC scan alone)
     const dim3 grid((unsigned)((n + kWavesM - 1) / kWavesM)), block(64 * kWavesM);
     const auto kernel = a.comps == 1 ? (a.restart == 0 ? k_mcu_segments<false, 1> : k_mcu_segments<true, 1>)
                                      : (a.restart == 0 ? k_mcu_segments<false, 3> : k_mcu_segments<true, 3>);
@@ -542,17 +549,22 @@ int launch_mcu_segments(const McuSegArgs &a, void *stream) {
 }
 
 // A scan of a progressive file: three components and ss = se = 0 the DC scan, one component and 1 <= ss <= se <= 63 an AC band.
+// A caller's script also has DC scans of one component and of two (McuSegArgs::mask): instantiations of their
+// own -- the ones above are launched for what they always were --, with the pictures' own tables alone.
 int launch_mcu_band_segments(const McuSegArgs &a, void *stream) {
     const int n = a.batch * a.num_segs_pad;
     if (n <= 0) return 0;
-    const bool dc = a.comps == 3 && a.ss == 0 && a.se == 0, band = a.comps == 1 && a.ss >= 1 && a.ss <= a.se && a.se <= 63;
+    const bool dc12 = (a.comps == 1 || a.comps == 2) && a.ss == 0 && a.se == 0 && a.runs;
+    const bool dc = (a.comps == 3 && a.ss == 0 && a.se == 0) || dc12, band = a.comps == 1 && a.ss >= 1 && a.ss <= a.se && a.se <= 63;
     // (runs: the scans of DESIGN.md 4.6.13 -- every picture codes with its own tables, huff_stride words apart)
     if (!a.sums || a.restart != 0 || (a.huff_stride != 0) != (a.runs != 0) || !(dc || band) || !mcu_seg_args_ok(a)) return (int)hipErrorInvalidValue;
     // successive approximation: own tables alone; a first scan with al > 0, or the refinement of bit al = ah - 1
     const bool point = a.ah == 0 && a.al > 0, refine = a.ah > 0;
     if ((point || refine) && (!a.runs || a.al > 13 || (refine && a.ah != a.al + 1))) return (int)hipErrorInvalidValue;
     const dim3 grid((unsigned)((n + kWavesM - 1) / kWavesM)), block(64 * kWavesM);
-    const auto kernel = dc ? (refine ? k_mcu_band_segments<3, kWalkDcRefine> : (point ? k_mcu_band_segments<3, kWalkDcPoint> : k_mcu_band_segments<3, kWalkDc>))
+    const auto kernel = a.comps == 2 ? (refine ? k_mcu_band_segments<2, kWalkDcRefine> : (point ? k_mcu_band_segments<2, kWalkDcPoint> : k_mcu_band_segments<2, kWalkDc>))
+                        : dc12 ? (refine ? k_mcu_band_segments<1, kWalkDcRefine> : (point ? k_mcu_band_segments<1, kWalkDcPoint> : k_mcu_band_segments<1, kWalkDc>))
+                        : dc ? (refine ? k_mcu_band_segments<3, kWalkDcRefine> : (point ? k_mcu_band_segments<3, kWalkDcPoint> : k_mcu_band_segments<3, kWalkDc>))
                            : (refine ? k_mcu_band_segments<1, kWalkBandRefine>
                                      : (point ? k_mcu_band_segments<1, kWalkBandPoint> : (a.runs ? k_mcu_band_segments<1, kWalkBandRuns> : k_mcu_band_segments<1, kWalkBand>)));
     hipLaunchKernelGGL(kernel, grid, block, 0, (hipStream_t)stream, a);
@@ -565,7 +577,7 @@ int launch_mcu_band_segments(const McuSegArgs &a, void *stream) {
 // into `table`.  Raw bits (a refinement scan's correction bits) leave the walk through its other outlet and are not seen here.
 template <int kComps, int kWalk>
 __global__ __launch_bounds__(64 * kWavesM) void k_mcu_band_histogram(const McuSegArgs a, unsigned long long *__restrict__ counts, int table, int tables) {
-    static_assert((kComps == 3 && (kWalk == kWalkDc || kWalk == kWalkDcPoint)) || (kComps == 1 && mcu_walk_has_runs(kWalk)), "the scans of DESIGN.md 4.6.13 and 4.6.14 that have a table");
+    static_assert(kComps >= 1 && kComps <= 3 && (kWalk == kWalkDc || kWalk == kWalkDcPoint || (kComps == 1 && mcu_walk_has_runs(kWalk))), "the scans of DESIGN.md 4.6.13 .. 4.6.15 that have a table");
     constexpr int kTabs = kComps == 1 ? 1 : 2;
     constexpr bool kRuns = mcu_walk_has_runs(kWalk);
     __shared__ uint32_t s_cnt[kTabs][256];                         // (a workgroup walks at most 4 x 256 blocks of 64 symbols: 32 bits hold it)
@@ -577,7 +589,7 @@ __global__ __launch_bounds__(64 * kWavesM) void k_mcu_band_histogram(const McuSe
     if (seg < a.batch * a.num_segs_pad) {
         const McuRange rg = mcu_range<false>(a, seg - image * a.num_segs_pad);
         const int16_t *base = a.coef + (size_t)image * a.pic_stride;
-        const int bpm = kComps == 1 ? 1 : a.hs * a.vs + 2, nblk = rg.nmcu * bpm;      // 0 (EMPTY: nothing counted) .. 256
+        const int bpm = kComps == 1 ? 1 : (kComps == 2 ? mcu_blocks_per_mcu2(a.hs, a.vs, a.mask) : a.hs * a.vs + 2), nblk = rg.nmcu * bpm;      // 0 (EMPTY: nothing counted) .. 256
         [[maybe_unused]] bool z[4], e[4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
@@ -610,16 +622,20 @@ __global__ __launch_bounds__(64 * kWavesM) void k_mcu_band_histogram(const McuSe
         }
 }
 
-// `tables`: the tables of a picture in `counts` (kProgTables, or kProgTablesMax); a DC scan counts into `table` and `table` + 1.
+// `tables`: the tables of a picture in `counts` (the script's); a DC scan with Y and chroma counts into `table` and `table` + 1.
 int launch_mcu_band_histogram(const McuSegArgs &a, unsigned long long *counts, int table, int tables, void *stream) {
     const int n = a.batch * a.num_segs_pad;
     if (n <= 0) return 0;
-    const bool dc = a.comps == 3 && a.ss == 0 && a.se == 0 && table == 0 && tables >= 2 && a.ah == 0;
-    const bool band = a.comps == 1 && a.ss >= 1 && a.ss <= a.se && a.se <= 63 && table >= 2 && table < tables;
+    // a DC scan counts into as many tables as its components have classes: Y one, Cb and Cr one together
+    const int dc_tables = a.comps == 3 || (a.comps == 2 && (a.mask & 1)) ? 2 : 1;
+    const bool dc = a.comps >= 1 && a.comps <= 3 && a.ss == 0 && a.se == 0 && table >= 0 && table + dc_tables <= tables && a.ah == 0;
+    const bool band = a.comps == 1 && a.ss >= 1 && a.ss <= a.se && a.se <= 63 && table >= 1 && table < tables;
     const bool point = a.ah == 0 && a.al > 0, refine = a.ah > 0;
     if (!counts || a.restart != 0 || !(dc || band) || tables > kProgTablesMax || a.al > 13 || (refine && a.ah != a.al + 1) || !mcu_seg_args_ok(a)) return (int)hipErrorInvalidValue;
     const dim3 grid((unsigned)((n + kWavesM - 1) / kWavesM)), block(64 * kWavesM);
-    const auto kernel = dc ? (point ? k_mcu_band_histogram<3, kWalkDcPoint> : k_mcu_band_histogram<3, kWalkDc>)
+    const auto kernel = dc && a.comps == 2 ? (point ? k_mcu_band_histogram<2, kWalkDcPoint> : k_mcu_band_histogram<2, kWalkDc>)
+                        : dc && a.comps == 1 ? (point ? k_mcu_band_histogram<1, kWalkDcPoint> : k_mcu_band_histogram<1, kWalkDc>)
+                        : dc ? (point ? k_mcu_band_histogram<3, kWalkDcPoint> : k_mcu_band_histogram<3, kWalkDc>)
                            : (refine ? k_mcu_band_histogram<1, kWalkBandRefine> : (point ? k_mcu_band_histogram<1, kWalkBandPoint> : k_mcu_band_histogram<1, kWalkBandRuns>));
     hipLaunchKernelGGL(kernel, grid, block, 0, (hipStream_t)stream, a, counts, table, tables);
     return (int)hipGetLastError();
@@ -632,7 +648,8 @@ int launch_mcu_band_histogram(const McuSegArgs &a, unsigned long long *counts, i
 // tables and the DC scan's SOS (hdr[sos_off, sos_off + kMcuSosLen)); scan k's (from 0) its table and sos + 16 k.
 // The script is the launch's: a.tables waves, table t belongs to scan a.table_scan[t] and is written with the
 // Tc/Th byte a.table_id[t]; the tables of a scan are consecutive, its header is [the head,] their DHT segments in that order and
-// its SOS (a.sos + 16 k, a.sos_len[k] bytes), written by the scan's last table.  A scan without a table (bit k of a.bare) gets a
+// its SOS (a.sos + 16 k, a.sos_len[k] bytes), written by the scan's last table.  A caller's script (4.6.15): 1 .. 16 tables and
+// scans; scan 0 owns table 0 and, when it has two, table 1; any other scan may own two tables as well.  A scan without a table (bit k of a.bare) gets a
 // header of its SOS alone, from wave 0.
 constexpr int kMcuSosLen = 14;
 __global__ __launch_bounds__(64 * kProgTablesMax) void k_prog_tables(const ProgTablesArgs a) {
@@ -695,7 +712,7 @@ __global__ __launch_bounds__(64 * kProgTablesMax) void k_prog_tables(const ProgT
 
 int launch_prog_tables(const ProgTablesArgs &a, int batch, void *stream) {
     if (batch < 1 || batch > kMaxBatch || !a.res || !a.tabs || !a.hdr_out || !a.hdr_len || !a.hdr || !a.sos || a.head_len < 0 ||
-        a.head_len + 2 * 33 + kMcuSosLen > kMcuPrefixSlot || a.first < 0 || a.first + batch > a.pictures || a.tables < 2 ||
+        a.head_len + 2 * 33 + kMcuSosLen > kMcuPrefixSlot || a.first < 0 || a.first + batch > a.pictures || a.tables < 1 ||
         a.tables > kProgTablesMax || a.scans < 1 || a.scans > kProgScansMax || a.table_scan[0] != 0 || (a.bare & 1u))
         return (int)hipErrorInvalidValue;
     for (int t = 0; t < a.tables; ++t)                             // (a scan's tables are consecutive; scan 0 has the DC tables in front of the head's end)
@@ -764,7 +781,7 @@ __global__ __launch_bounds__(256) void k_scans_concat(const ScansConcatArgs a) {
 }
 
 int launch_scans_concat(const ScansConcatArgs &a, void *stream) {
-    if (a.batch < 1 || a.batch > kMaxBatch || a.pic_bytes % 16 != 0 || a.scans < 2 || a.scans > kProgScansMax) return (int)hipErrorInvalidValue;
+    if (a.batch < 1 || a.batch > kMaxBatch || a.pic_bytes % 16 != 0 || a.scans < 1 || a.scans > kProgScansMax) return (int)hipErrorInvalidValue;
     for (int k = 1; k < a.scans; ++k) if (a.slot_off[k] % 16 != 0) return (int)hipErrorInvalidValue;
     hipLaunchKernelGGL(k_scans_concat, dim3(kConcatWgs, (unsigned)a.batch), dim3(256), 0, (hipStream_t)stream, a);
     return (int)hipGetLastError();

@@ -148,6 +148,13 @@ def _prototypes():
         "jpegamd_encode_ycbcr_progressive_successive_batch_async": batch(YCbCrImage, 4),
         "jpegamd_max_jfif_bytes_progressive_successive": (u64, [i32, i32, i32]),
         "jpegamd_debug_progressive_successive_counts": (i32, [vp, vp]),
+        # ... with a scan script of the caller's, and grayscale progressive files: (.., scans[], scan count, outs[], ..)
+        "jpegamd_validate_scan_script": (i32, [vp, i32, i32, C.POINTER(i32)]),
+        "jpegamd_encode_color_progressive_script_batch_async": (i32, [vp, C.POINTER(Image), i32, i32, vp, i32, vpp, u64, vpp, vp]),
+        "jpegamd_encode_ycbcr_progressive_script_batch_async": (i32, [vp, C.POINTER(YCbCrImage), i32, i32, i32, i32, i32, vp, i32, vpp, u64, vpp, vp]),
+        "jpegamd_encode_gray_progressive_script_batch_async": (i32, [vp, C.POINTER(Image), i32, vp, i32, vpp, u64, vpp, vp]),
+        "jpegamd_max_jfif_bytes_progressive_script": (u64, [i32, i32, i32, vp, i32]),
+        "jpegamd_debug_progressive_script_counts": (i32, [vp, vp, i32]),
     }
     later = {
         "jpegamd_encoder_set_pipeline": (i32, [vp, i32]),
@@ -356,15 +363,79 @@ def max_jfif_bytes_progressive_successive(width: int, height: int, subsampling: 
     return int(lib.jpegamd_max_jfif_bytes_progressive_successive(width, height, subsampling))
 
 
+MAX_SCANS = 16                                                   # JPEGAMD_MAX_SCANS
+
+
+class Scan(C.Structure):
+    """JpegAmdScan: the component set as a bit mask (bit 0 Y, bit 1 Cb, bit 2 Cr), Ss, Se, Ah, Al."""
+    _fields_ = [("components", C.c_uint8), ("ss", C.c_uint8), ("se", C.c_uint8), ("ah", C.c_uint8), ("al", C.c_uint8)]
+
+
+def _scan_array(scans):
+    """scans: None (the default script) or a sequence of (components, Ss, Se, Ah, Al), components a tuple of component indices 0 .. 2
+    -> (the JpegAmdScan array or None, its length).  Values that no JpegAmdScan holds are a ValueError; the rules of a script are
+    the library's to check."""
+    if scans is None:
+        return None, 0
+    out = []
+    for k, scan in enumerate(scans):
+        try:
+            comps, ss, se, ah, al = scan
+            comps = tuple(int(c) for c in comps)
+            rest = tuple(int(v) for v in (ss, se, ah, al))
+        except (TypeError, ValueError):
+            raise ValueError(f"scan {k}: expected (components, ss, se, ah, al) with components a tuple of indices, not {scan!r}") from None
+        if any(c < 0 or c > 2 for c in comps) or len(set(comps)) != len(comps) or any(v < 0 or v > 255 for v in rest):
+            raise ValueError(f"scan {k}: component indices are distinct and 0 .. 2, the other values 0 .. 255, not {scan!r}")
+        out.append(Scan(sum(1 << c for c in comps), *rest))
+    return (Scan * len(out))(*out), len(out)
+
+
+def validate_scan_script(scans, components: int = 3) -> None:
+    """Check a scan script -- a sequence of (components, Ss, Se, Ah, Al) -- for a file of `components` components (3, or 1 for a
+    grayscale file) with jpegamd_validate_scan_script; a script that breaks a rule is a ValueError that names the offending scan."""
+    arr, n = _scan_array(scans if scans is not None else ())
+    bad = C.c_int32(-1)
+    if lib.jpegamd_validate_scan_script(arr, n, int(components), C.byref(bad)):
+        where = f"scan {bad.value}" if bad.value >= 0 else "the script as a whole"
+        raise ValueError(f"invalid scan script for {components} component(s): {where} breaks a rule of T.81 G.1.1.1")
+
+
+def max_jfif_bytes_progressive_script(width: int, height: int, subsampling: int = SUBSAMPLE_420, scans=None) -> int:
+    """Upper bound on the bytes of a progressive file with the scan script `scans` (None: the default script; DESIGN.md 4.6.15);
+    subsampling 0: a grayscale file.  0 for bad arguments or an invalid script."""
+    arr, n = _scan_array(scans)
+    return int(lib.jpegamd_max_jfif_bytes_progressive_script(width, height, subsampling, arr, n))
+
+
+class ProgressiveScript:
+    """A `progressive` argument inside this package: the entries of DESIGN.md 4.6.15 with this script (None: the default one)."""
+
+    def __init__(self, scans):
+        self.scans = None if scans is None else [(tuple(c), ss, se, ah, al) for c, ss, se, ah, al in scans]
+
+
 SCANS = ("separate", "interleaved")
 HUFFMAN_STANDARD, HUFFMAN_OPTIMIZED = 0, 1       # jpegamd_encoder_set_huffman
 PROGRESSIVE_OPTIMIZED = "optimized"              # a `progressive` argument inside this package: the entries of DESIGN.md 4.6.13 (True: 4.6.12's)
 PROGRESSIVE_SUCCESSIVE = "successive"            # ... of DESIGN.md 4.6.14
 
 
+def _progressive_entry(enc, progressive, ycbcr: bool):
+    """The Encoder method a `progressive` argument names, as a callable with the arguments of the entries without a script: a
+    ProgressiveScript's scans go in front of the output pointers."""
+    fn = getattr(enc, _progressive_mode(progressive)[2 if ycbcr else 1])
+    if isinstance(progressive, ProgressiveScript):
+        return lambda *a: fn(*a[:-4], progressive.scans, *a[-4:])
+    return fn
+
+
 def _progressive_mode(progressive):
     """A `progressive` argument -> (the bound, the Encoder method of packed pixels, the one of YCbCr pictures, whether the entries
     make their own tables and leave the context's Huffman mode alone)."""
+    if isinstance(progressive, ProgressiveScript):
+        return (lambda w, h, sub: max_jfif_bytes_progressive_script(w, h, sub, progressive.scans), "encode_color_progressive_script_batch_async",
+                "encode_ycbcr_progressive_script_batch_async", True)
     if progressive == PROGRESSIVE_SUCCESSIVE:
         return (max_jfif_bytes_progressive_successive, "encode_color_progressive_successive_batch_async",
                 "encode_ycbcr_progressive_successive_batch_async", True)
@@ -678,7 +749,7 @@ def _queue_pixels(enc, imgs, subsampling, outs, cap, size_ptrs, stream, interlea
     planar = isinstance(imgs[0], PlanarImage)
     if progressive:                                               # (jpegamd.progressive: packed pixels, no intervals, the standard tables;
         # jpegamd.progressive_optimized, jpegamd.progressive_successive: the tables of every scan its own)
-        getattr(enc, _progressive_mode(progressive)[1])(imgs, subsampling, outs, cap, size_ptrs, stream)
+        _progressive_entry(enc, progressive, False)(imgs, subsampling, outs, cap, size_ptrs, stream)
     elif not interleaved:
         if planar:
             enc.encode_planar_batch_async(imgs, subsampling, outs, cap, size_ptrs, stream)
@@ -846,11 +917,12 @@ def _encode_ycbcr_images(device, n, h, w, subsampling, image, sample_range: int 
     if huffman and not any_kind:
         raise ValueError("optimised Huffman tables go through jpegamd.mjpeg")
     if progressive:                                               # (jpegamd.progressive: any kind, no intervals, the standard tables set for the call;
-        bound, _, method, own = _progressive_mode(progressive)    # jpegamd.progressive_optimized, _successive: the context's mode is left alone)
+        bound, _, _, own = _progressive_mode(progressive)    # jpegamd.progressive_optimized, _successive: the context's mode is left alone)
         cap = bound(w, h, subsampling)
 
         def queue_progressive(enc, b0, k, outs, cap, size_ptrs, stream):
-            getattr(enc, method)([image(b0 + i) for i in range(k)], subsampling, sample_range, sample_format, matrix, outs, cap, size_ptrs, stream)
+            _progressive_entry(enc, progressive, True)([image(b0 + i) for i in range(k)], subsampling, sample_range, sample_format, matrix, outs,
+                                                       cap, size_ptrs, stream)
 
         return _encode_pictures(device, n, h, w, cap, queue_progressive, None if own else HUFFMAN_STANDARD)
     if restart:
@@ -1002,7 +1074,37 @@ class _ProgressiveEntries:
                     (subsampling, sample_range, sample_format, matrix), out_ptrs, out_cap, size_ptrs, stream)
 
 
-class Encoder(_ProgressiveEntries):
+class _ProgressiveScriptEntries(_ProgressiveEntries):
+    """... and those that take a scan script.  `scans`: None for the default script, or a sequence of (components,
+    Ss, Se, Ah, Al) with components a tuple of component indices; out_cap from max_jfif_bytes_progressive_script."""
+
+    def _script_batch(self, name: str, struct, imgs, ints, scans, out_ptrs, out_cap: int, size_ptrs, stream: int):
+        n = len(imgs)
+        arr, pointers = (struct * n)(*imgs), C.c_void_p * n
+        sc, ns = _scan_array(scans)
+        rc = getattr(lib, name)(self._h, arr, n, *[int(v) for v in ints], sc, ns, pointers(*out_ptrs), out_cap, pointers(*size_ptrs),
+                                C.c_void_p(stream))
+        if rc:
+            raise JpegAmdError(rc, name)
+
+    def encode_color_progressive_script_batch_async(self, imgs, subsampling: int, scans, out_ptrs, out_cap: int, size_ptrs, stream: int = 0):
+        """The progressive files of RGB / BGR / RGBA / BGRA pictures with the caller's scan script
+        (jpegamd_encode_color_progressive_script_batch_async).  The context's Huffman mode is neither read nor changed."""
+        self._script_batch("jpegamd_encode_color_progressive_script_batch_async", Image, imgs, (subsampling,), scans, out_ptrs, out_cap, size_ptrs, stream)
+
+    def encode_ycbcr_progressive_script_batch_async(self, imgs, subsampling: int, sample_range: int, sample_format: int, matrix: int, scans,
+                                                    out_ptrs, out_cap: int, size_ptrs, stream: int = 0):
+        """... of YCbCr pictures of any kind (jpegamd_encode_ycbcr_progressive_script_batch_async)."""
+        self._script_batch("jpegamd_encode_ycbcr_progressive_script_batch_async", YCbCrImage, imgs,
+                           (subsampling, sample_range, sample_format, matrix), scans, out_ptrs, out_cap, size_ptrs, stream)
+
+    def encode_gray_progressive_script_batch_async(self, imgs, scans, out_ptrs, out_cap: int, size_ptrs, stream: int = 0):
+        """The grayscale progressive files (SOF2, one component) of pictures in any of the five channel orders: their luma
+        (jpegamd_encode_gray_progressive_script_batch_async); out_cap from max_jfif_bytes_progressive_script with subsampling 0."""
+        self._script_batch("jpegamd_encode_gray_progressive_script_batch_async", Image, imgs, (), scans, out_ptrs, out_cap, size_ptrs, stream)
+
+
+class Encoder(_ProgressiveScriptEntries):
     """Level-1 context: device pointers in, device pointers out, stream-ordered."""
 
     def __init__(self, max_width: int, max_height: int):

@@ -58,6 +58,10 @@ With --huffman optimized the loop goes through jpegamd_encode_*_progressive_opti
 per-scan optimised tables; nothing is set on the context); --huffman standard is the plain progressive loop.  With --successive as
 well it goes through jpegamd_encode_*_progressive_successive_batch_async (DESIGN.md 4.6.14: the ten scans of successive approximation);
 the line then carries "successive": true.
+--scans NAME|FILE (with --scan progressive; rgb pictures) goes through the entries that take a scan script: NAME is
+spectral, successive (the built-in scripts, passed explicitly) or gray (the default script of a grayscale file); FILE holds a script in
+the text form of libjpeg's -scans files (jpegamd.progressive_script.parse_scan_script).  A script in which component 0 alone appears
+writes grayscale files (the luma of the pictures) through jpegamd_encode_gray_progressive_script_batch_async.  The line carries "scans".
 
 --scan gray (with --batch N, default 8) times GRAYSCALE files through jpegamd_encode_gray_scan_batch_async: the luma
 of the same --size pictures, --restart N|row in blocks (`row`: ceil(W / 8)), --huffman standard|optimized; the whole call is timed
@@ -111,7 +115,11 @@ def main() -> None:
                     help="--scan interleaved: restart intervals of N MCUs (0 .. 65535), or `row` for one MCU row")
     ap.add_argument("--successive", action="store_true",
                     help="--scan progressive --huffman optimized: the ten scans of successive approximation (DESIGN.md 4.6.14)")
+    ap.add_argument("--scans", default=None, metavar="NAME|FILE",
+                    help="--scan progressive: a scan script -- spectral, successive, gray, or a file in libjpeg's -scans text form (DESIGN.md 4.6.15)")
     a = ap.parse_args()
+    if a.scans is not None and (a.scan != "progressive" or a.successive or a.huffman is not None or a.source != "rgb"):
+        sys.exit("--scans needs --scan progressive and takes --size, --batch, --subsampling, --quality, --kind alone")
     if a.successive and (a.scan != "progressive" or a.huffman != "optimized"):
         sys.exit("--successive needs --scan progressive --huffman optimized")
     import torch                          # (the device runtime comes up through torch first, as in bench.py)
@@ -150,6 +158,11 @@ def main() -> None:
             sys.exit("--restart needs --scan interleaved or gray")
         if a.restart != "row" and not (a.restart.isdigit() and int(a.restart) <= 65535):
             sys.exit("--restart takes a number of MCUs, 0 .. 65535, or `row`")
+    if a.scans is not None:
+        if a.convert or a.narrow or a.mapped or a.layout is not None or a.restart is not None:
+            sys.exit("--scans takes --size, --batch, --subsampling, --quality, --kind alone")
+        run_scans(a, jpegamd, torch, dev)
+        return
     if a.scan == "gray":
         if sources != ["rgb"] or a.layout is not None or a.convert or a.narrow or a.mapped or a.subsampling:
             sys.exit("--scan gray takes --size, --batch, --restart, --huffman, --quality, --kind alone")
@@ -258,6 +271,55 @@ def run_gray(a, jpegamd, torch, dev) -> None:
                       "restart_interval": restart, "huffman": a.huffman or "standard", "bytes": got, "entropy_bits": st.entropy_bits,
                       "ns_total_median": int(t), "us_per_picture": round(t / n / 1000, 1), "gpixels_per_s": round(n * w * h / t, 2),
                       "plain_bytes": plain_bytes, "plain_us_per_picture": round(plain / n / 1000, 1), "ratio_to_plain": round(t / plain, 2)}))
+
+
+def run_scans(a, jpegamd, torch, dev) -> None:
+    """--scan progressive --scans: N pictures per call through the entries that take a scan script."""
+    import jpegamd.progressive_script as ps
+    named = {"spectral": ps.SPECTRAL, "successive": ps.SUCCESSIVE, "gray": ps.GRAY_SUCCESSIVE}
+    if a.scans in named:
+        script = named[a.scans]
+    else:
+        with open(a.scans, encoding="utf-8") as f:
+            script = ps.parse_scan_script(f.read())
+    gray = all(comps == (0,) for comps, *_ in script)
+    jpegamd.validate_scan_script(script, 1 if gray else 3)
+    w = h = a.size
+    n = a.batch or 8
+    pxs, descs = [], []
+    for i in range(n):
+        bmp = jpegamd.synth_bmp(w, h, 1 + i, a.kind, 0)
+        img, off = jpegamd.parse_bmp(bmp)
+        pxs.append(torch.frombuffer(bytearray(bmp[off:off + img.row_stride * h]), dtype=torch.uint8).to(dev))
+        descs.append(jpegamd.Encoder.image(pxs[-1].data_ptr(), w, h, img.row_stride, True, jpegamd.ORDER_BGR, a.quality))
+        del bmp
+    enc = jpegamd.Encoder(w, n * h)
+    stream = torch.cuda.current_stream().cuda_stream
+    for sub, name in ([(0, "gray")] if gray else rgb_subsamplings(a, jpegamd)):
+        cap = jpegamd.max_jfif_bytes_progressive_script(w, h, sub, script)
+        outs = [torch.empty(cap, dtype=torch.uint8, device=dev) for _ in range(n)]
+        sizes = torch.zeros(n, dtype=torch.int64, device=dev)
+        out_ptrs = [o.data_ptr() for o in outs]
+        size_ptrs = [sizes.data_ptr() + 8 * i for i in range(n)]
+        if gray:
+            call = lambda: enc.encode_gray_progressive_script_batch_async(descs, script, out_ptrs, cap, size_ptrs, stream)
+        else:
+            call = lambda: enc.encode_color_progressive_script_batch_async(descs, sub, script, out_ptrs, cap, size_ptrs, stream)
+        for _ in range(a.warmup):
+            call()
+        enc.finish()
+        enc.set_profiling(a.steps)
+        for _ in range(a.steps):
+            call()
+        st = enc.finish()
+        totals = [enc.profile(i).ns_total for i in range(a.steps)]
+        enc.set_profiling(0)
+        t = statistics.median(totals)
+        print(json.dumps({"source": "rgb", "subsampling": name, "width": w, "height": h, "batch": n, "quality": a.quality, "kind": a.kind,
+                          "steps": a.steps, "bytes": sizes.cpu().tolist(), "entropy_bits": st.entropy_bits, "ns_total_median": int(t),
+                          "us_per_picture": round(t / n / 1000, 1), "gpixels_per_s": round(n * w * h / t, 2), "scan": "progressive",
+                          "scans": a.scans, "scan_count": len(script)}))
+        del outs
 
 
 def run_batch(a, jpegamd, torch, dev, sources=("rgb",)) -> None:
