@@ -466,6 +466,33 @@ int32_t jpegamd_encoder_set_huffman(JpegAmdEncoder *enc, int32_t huffman);
 int32_t jpegamd_debug_optimal_huffman(JpegAmdEncoder *enc, const uint64_t *freq, int32_t n, uint8_t *bits, uint8_t *vals, int32_t *nvals);
 int32_t jpegamd_debug_huffman_counts(JpegAmdEncoder *enc, uint64_t *counts);
 
+/* CALLER-SUPPLIED QUANTISATION TABLES.
+ * Annex K scaled for `quality` (0 -> 50), raster order, as the encoder derives them; either pointer may be NULL. */
+int32_t jpegamd_quant_tables_for_quality(int32_t quality, uint8_t *luma, uint8_t *chroma);
+/* Tables of the caller's for every later encode on this context.  uint8[64], RASTER order (the order of
+ * jpegamd_debug_quant_table and of cjpeg -qtables), entries 1..255.
+ *   luma, chroma   : component 1 uses luma, components 2 and 3 use chroma
+ *   luma, NULL     : one table for all components (a colour file still carries DQT ids 0 and 1, identical: no prefix changes length)
+ *   NULL, NULL     : back to the tables of each picture's `quality`
+ *   NULL, chroma   : JPEGAMD_ERR_ARG
+ * An entry of 0: JPEGAMD_ERR_ARG, and the context keeps what it had.  The tables are copied.
+ * The setting is sticky on the context, like jpegamd_encoder_set_huffman.  While tables are set a picture's `quality` selects
+ * nothing (the batch entries still want it uniform).  The file is the one the same entry writes for a quality, with these two
+ * tables in its DQT segment (zigzag order there) and in its quantiser and nothing else changed; for the tables of
+ * jpegamd_quant_tables_for_quality(q) it is byte for byte the file of quality q.
+ * The call itself touches no device memory and does not disturb queued work.  The NEXT encode uploads the quantiser's constants
+ * and the file headers by the route a change of `quality` takes -- which waits for the work queued on this context before it
+ * rewrites them, so a table switch costs a stream wait exactly as a quality switch does.
+ * Every jpegamd_max_jfif_bytes* bound holds unchanged: each is made of per-block worst cases that already cover the all-ones
+ * table (quality 100), the finest an 8-bit table can be.
+ * The tables govern every encode entry that takes a context: jpegamd_encode_async / _batch_async, the three-scan, one-scan,
+ * gray-scan and progressive entries from every source, jpegamd_encode_rows_async / export / import / jpegamd_finalize_async (every
+ * rank sets the same tables) and jpegamd_debug_stages.  convertToJpeg, the stage functions and the BMP and file entries own their
+ * contexts and stay quality-only. */
+int32_t jpegamd_encoder_set_quant_tables(JpegAmdEncoder *enc, const uint8_t *luma, const uint8_t *chroma);
+/* What the context holds: *custom = 1 and the two tables, or *custom = 0 (tables untouched). */
+int32_t jpegamd_encoder_get_quant_tables(JpegAmdEncoder *enc, uint8_t *luma, uint8_t *chroma, int32_t *custom);
+
 /* GRAYSCALE files with restart intervals and per-picture optimised Huffman tables: the grayscale file written as
  * a scan of ONE component from coefficient planes, the way the one-scan colour files are.  For a picture of W x H at quality q,
  * restart_interval = Ri (0 .. 65535, in MCUs) and the context's Huffman mode (jpegamd_encoder_set_huffman governs this entry too):
@@ -775,6 +802,10 @@ int32_t jpegamd_debug_color_profile(JpegAmdEncoder *enc, int32_t slot, uint64_t 
 int32_t jpegamd_debug_group_thresholds(int32_t quality, float *grp_thr, float *lo_bound);
 /* The same for the colour files' chroma table (as jpegamd_debug_chroma_mfma_consts is to jpegamd_debug_mfma_consts). */
 int32_t jpegamd_debug_chroma_group_thresholds(int32_t quality, float *grp_thr, float *lo_bound);
+/* Host-only, for tests: the fast quantiser's constants for an arbitrary table (raster order, entries 1..255; what
+ * jpegamd_debug_mfma_consts, _mfma_offsets and _group_thresholds give for a quality).  Any output pointer may be NULL. */
+int32_t jpegamd_debug_table_consts(const uint8_t *table, float *qmul, float *qthr, float *bias, double *delta,
+                                   float *zoff, float *qadd, float *grp_thr, float *lo_bound);
 /* ... and what the uncentred matrix operand (luma 0 .. 255 as binary16 subnormals) adds: zoff[64] / qadd[64] = bias + zoff by zigzag
  * position, the DC row's surplus in accumulator units, the accumulator scale.  Any pointer may be NULL. */
 int32_t jpegamd_debug_mfma_offsets(int32_t quality, float *zoff, float *qadd, float *dc_off, float *scale);

@@ -49,6 +49,8 @@ struct HeaderCache {
     }
 };
 
+constexpr int kFirstTableKey = 101;     // (the qualities end at 100)
+
 struct JpegAmdEncoder {
     int device = -1;
     int max_w = 0, max_h = 0;
@@ -71,7 +73,12 @@ struct JpegAmdEncoder {
     uint32_t poison_value = 0;          // ... with this value, between k_tile_encode and k_segment_merge
     unsigned long long *stamps_dev = nullptr;   // per-wave phase cycle sums of the stamped kernel (allocated by the first convertToJpeg, or with JPEGAMD_STAMPS=1)
     bool stamp_next = false;                    // the next k_tile_encode launch is the stamped variant (convertToJpeg)
-    // cached constants
+    // The caller's quantisation tables (jpegamd_encoder_set_quant_tables; raster order) and the key the caches below hold them under:
+    // outside 0 .. 100, where the keys of the quality-driven pictures lie, and new with every successful set.
+    bool custom_tables = false;
+    int table_key = kFirstTableKey - 1;
+    uint8_t custom_luma[64], custom_chroma[64];
+    // cached constants (cur_quality, color.cur_quality and the q of the three HeaderCaches are table keys: quant_choice)
     int cur_quality = -1;
     uint8_t qtable[64];
     HeaderCache prefix_for = {};        // what `prefix` holds (no subsampling: 0)
@@ -190,16 +197,20 @@ extern "C" int32_t jpegamd_debug_cos_lut(float *lut /*[8][8]: COS_LUT[x][u]*/) {
 // Behind the constant getters below (host-only, reentrant; tests pin the values against the oracle's arithmetic): the constants of
 // the fast path for `quality` with the luma or the chroma table, and the guard bands by raster index, handed to `take`.
 template <class Take>
-static int32_t with_mfma_consts(int32_t quality, bool chroma, Take take) {
-    uint8_t t[64];
+static int32_t with_table_consts(const uint8_t t[64], Take take) {
     double delta[64];
     MfmaTables *mt = new (std::nothrow) MfmaTables;
     if (!mt) return JPEGAMD_ERR_HIP;
-    (chroma ? chroma_quant_table_for_quality : quant_table_for_quality)(quality, t);
     derive_mfma_tables(t, mt, delta);
     take(*mt, delta);
     delete mt;
     return JPEGAMD_OK;
+}
+template <class Take>
+static int32_t with_mfma_consts(int32_t quality, bool chroma, Take take) {
+    uint8_t t[64];
+    (chroma ? chroma_quant_table_for_quality : quant_table_for_quality)(quality, t);
+    return with_table_consts(t, take);
 }
 template <class T, size_t N>
 static void copy_out(void *dst /*may be null*/, const T (&src)[N]) { if (dst) std::memcpy(dst, src, sizeof(src)); }
@@ -235,6 +246,23 @@ static int32_t group_thresholds(int32_t quality, bool chroma, float *grp_thr /*[
 }
 extern "C" int32_t jpegamd_debug_group_thresholds(int32_t quality, float *grp_thr, float *lo_bound) { return group_thresholds(quality, false, grp_thr, lo_bound); }
 extern "C" int32_t jpegamd_debug_chroma_group_thresholds(int32_t quality, float *grp_thr, float *lo_bound) { return group_thresholds(quality, true, grp_thr, lo_bound); }
+
+// The same constants for a table of the caller's (raster order, entries 1 .. 255).
+static bool table_valid(const uint8_t *t) { return std::find(t, t + 64, (uint8_t)0) == t + 64; }
+extern "C" int32_t jpegamd_debug_table_consts(const uint8_t *table, float *qmul, float *qthr, float *bias, double *delta, float *zoff, float *qadd,
+                                              float *grp_thr, float *lo_bound) {
+    if (!table || !table_valid(table)) return JPEGAMD_ERR_ARG;
+    return with_table_consts(table, [&](const MfmaTables &mt, const double (&d)[64]) {
+        copy_out(qmul, mt.qmul); copy_out(qthr, mt.qthr); copy_out(bias, mt.bias); copy_out(delta, d);
+        copy_out(zoff, mt.zoff); copy_out(qadd, mt.qadd); copy_out(grp_thr, mt.grp_thr); copy_out(lo_bound, mt.lo_bound);
+    });
+}
+
+extern "C" int32_t jpegamd_quant_tables_for_quality(int32_t quality, uint8_t *luma, uint8_t *chroma) {
+    if (luma) quant_table_for_quality(quality, luma);
+    if (chroma) chroma_quant_table_for_quality(quality, chroma);
+    return JPEGAMD_OK;
+}
 
 // The colour subsamplings: 4:4:4, 4:2:0 (chroma halved both ways) and 4:2:2 (halved along the row alone).
 static bool sub_valid(int sub) { return sub == JPEGAMD_SUBSAMPLE_444 || sub == JPEGAMD_SUBSAMPLE_420 || sub == JPEGAMD_SUBSAMPLE_422; }
@@ -403,6 +431,28 @@ extern "C" int32_t jpegamd_encoder_set_huffman(JpegAmdEncoder *e, int32_t huffma
     return JPEGAMD_OK;
 }
 
+// Host state only: the next encode finds a key its caches do not hold and uploads constants and headers behind the queued work.
+extern "C" int32_t jpegamd_encoder_set_quant_tables(JpegAmdEncoder *e, const uint8_t *luma, const uint8_t *chroma) {
+    if (!e || (!luma && chroma)) return JPEGAMD_ERR_ARG;
+    if (!luma) { e->custom_tables = false; return JPEGAMD_OK; }
+    if (!chroma) chroma = luma;
+    if (!table_valid(luma) || !table_valid(chroma)) return JPEGAMD_ERR_ARG;
+    std::memmove(e->custom_luma, luma, 64);
+    std::memmove(e->custom_chroma, chroma, 64);
+    e->custom_tables = true;
+    e->table_key = e->table_key == INT32_MAX ? kFirstTableKey : e->table_key + 1;
+    return JPEGAMD_OK;
+}
+
+extern "C" int32_t jpegamd_encoder_get_quant_tables(JpegAmdEncoder *e, uint8_t *luma, uint8_t *chroma, int32_t *custom) {
+    if (!e || !custom) return JPEGAMD_ERR_ARG;
+    *custom = e->custom_tables ? 1 : 0;
+    if (!e->custom_tables) return JPEGAMD_OK;
+    if (luma) std::memcpy(luma, e->custom_luma, 64);
+    if (chroma) std::memcpy(chroma, e->custom_chroma, 64);
+    return JPEGAMD_OK;
+}
+
 extern "C" int32_t jpegamd_encoder_set_profiling(JpegAmdEncoder *e, int32_t slots) {
     if (!e || slots < 0 || slots > 65536) return JPEGAMD_ERR_ARG;
     if (e->pending) HIP_TRY(hipStreamSynchronize(e->last_stream));
@@ -488,10 +538,24 @@ static int32_t upload_tables(JpegAmdEncoder *e, const uint8_t t[64], MfmaTables 
     return JPEGAMD_OK;
 }
 
-static int32_t prepare_constants(JpegAmdEncoder *e, const JpegAmdImage *img, bool need_prefix) {
+// The quantisation tables of a picture on this context (raster order; either pointer may be null) and the key the caches of
+// constants and headers hold them under: the caller's tables while some are set, else those of the picture's quality.
+static int quant_choice(const JpegAmdEncoder *e, const JpegAmdImage *img, uint8_t *luma, uint8_t *chroma) {
+    if (e->custom_tables) {
+        if (luma) std::memcpy(luma, e->custom_luma, 64);
+        if (chroma) std::memcpy(chroma, e->custom_chroma, 64);
+        return e->table_key;
+    }
     const int q = clamp_quality(img->quality);
+    if (luma) quant_table_for_quality(q, luma);
+    if (chroma) chroma_quant_table_for_quality(q, chroma);
+    return q;
+}
+
+static int32_t prepare_constants(JpegAmdEncoder *e, const JpegAmdImage *img, bool need_prefix) {
+    const int q = quant_choice(e, img, nullptr, nullptr);
     if (q != e->cur_quality) {
-        quant_table_for_quality(q, e->qtable);
+        quant_choice(e, img, e->qtable, nullptr);
         if (int32_t rc = upload_tables(e, e->qtable, e->tables_dev)) return rc;
         e->cur_quality = q;
     }
@@ -964,17 +1028,16 @@ static int32_t color_alloc(JpegAmdEncoder *e, int w, int h) {
 
 static int32_t prepare_color_constants(JpegAmdEncoder *e, const JpegAmdImage *img, int sub) {
     auto &c = e->color;
-    const int q = clamp_quality(img->quality);
+    const int q = quant_choice(e, img, nullptr, nullptr);
     if (q != c.cur_quality) {
         uint8_t t[64];
-        chroma_quant_table_for_quality(q, t);
+        quant_choice(e, img, nullptr, t);
         if (int32_t rc = upload_tables(e, t, c.tables_dev)) return rc;
         c.cur_quality = q;
     }
     if (!c.hdr_for.matches(img->width, img->height, q, sub)) {
         uint8_t luma[64], chroma[64], hdr[kColorPrefixMax];
-        quant_table_for_quality(q, luma);
-        chroma_quant_table_for_quality(q, chroma);
+        quant_choice(e, img, luma, chroma);
         const int len = (int)build_jfif_prefix_color(img->width, img->height, luma, chroma, chroma_mode(sub), hdr);
         if (int32_t rc = wait_pending(e)) return rc;
         HIP_TRY(hipMemcpy(c.hdr, hdr, (size_t)len, hipMemcpyHostToDevice));
@@ -1851,10 +1914,10 @@ constexpr int kColorSofOffset = 2 + 18 + 134;       // SOI, APP0, DQT with two t
 constexpr int kGraySofOffset = 2 + 18 + 69;         // ... with one: the one-component head (a grayscale progressive file)
 static int32_t prepare_mcu_prefix(JpegAmdEncoder *e, const JpegAmdImage *img, int sub, int restart, bool progressive = false) {
     auto &m = e->mcu;
-    const int q = clamp_quality(img->quality);
+    const int q = quant_choice(e, img, nullptr, nullptr);
     if (m.hdr_for.matches(img->width, img->height, q, sub, restart, progressive ? 1 : 0)) return JPEGAMD_OK;
     uint8_t luma[64], chroma[64], hdr[kColorPrefixMax + kMcuDriBytes + kMcuSosBytes];
-    quant_table_for_quality(q, luma);
+    quant_choice(e, img, luma, chroma);
     size_t n, nsos;
     uint8_t sos[kMcuSosBytes] = {0xFF, 0xDA, 0x00, 0x0C, 0x03, 0x01, 0x00, 0x02, 0x11, 0x03, 0x11, 0x00, 0x3F, 0x00};
     if (sub == kSubNone) {
@@ -1863,7 +1926,6 @@ static int32_t prepare_mcu_prefix(JpegAmdEncoder *e, const JpegAmdImage *img, in
         nsos = kSosBytes;
         std::memcpy(sos, hdr + n, nsos);                                // (behind the DRI segment again)
     } else {
-        chroma_quant_table_for_quality(q, chroma);
         n = build_jfif_prefix_color(img->width, img->height, luma, chroma, chroma_mode(sub), hdr) - kSosBytes;
         nsos = kMcuSosBytes;
     }

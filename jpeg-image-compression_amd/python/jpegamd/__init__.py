@@ -6,8 +6,10 @@ here; if the shared library is missing the import fails loudly.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
+import threading
 from pathlib import Path
 
 _PKG_ROOT = Path(__file__).resolve().parents[2]          # .../jpeg-image-compression_amd
@@ -155,6 +157,11 @@ def _prototypes():
         "jpegamd_encode_gray_progressive_script_batch_async": (i32, [vp, C.POINTER(Image), i32, vp, i32, vpp, u64, vpp, vp]),
         "jpegamd_max_jfif_bytes_progressive_script": (u64, [i32, i32, i32, vp, i32]),
         "jpegamd_debug_progressive_script_counts": (i32, [vp, vp, i32]),
+        # caller-supplied quantisation tables
+        "jpegamd_quant_tables_for_quality": (i32, [i32, vp, vp]),
+        "jpegamd_encoder_set_quant_tables": (i32, [vp, vp, vp]),
+        "jpegamd_encoder_get_quant_tables": (i32, [vp, vp, vp, C.POINTER(i32)]),
+        "jpegamd_debug_table_consts": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     }
     later = {
         "jpegamd_encoder_set_pipeline": (i32, [vp, i32]),
@@ -270,6 +277,61 @@ def group_thresholds(quality: int = 50, with_lo_bound: bool = False, chroma: boo
     t, lo = np.zeros(8, np.float32), np.zeros(8, np.float32)
     (lib.jpegamd_debug_chroma_group_thresholds if chroma else lib.jpegamd_debug_group_thresholds)(quality, t.ctypes.data, lo.ctypes.data)
     return (t.reshape(4, 2), lo.reshape(4, 2)) if with_lo_bound else t.reshape(4, 2)
+
+
+def quant_tables_for_quality(quality: int = 50):
+    """(luma, chroma), uint8[64] each in raster order: Annex K scaled for `quality` (0 -> 50) as the encoder derives them
+    (jpegamd_quant_tables_for_quality)."""
+    import numpy as np
+    luma, chroma = np.zeros(64, np.uint8), np.zeros(64, np.uint8)
+    _checked("jpegamd_quant_tables_for_quality", int(quality), luma.ctypes.data, chroma.ctypes.data)
+    return luma, chroma
+
+
+def as_quant_table(t):
+    """A quantisation table given as 64 values or as 8 x 8 values (a list or an array; raster order) -> uint8[64] in raster order.
+    A wrong shape, a value that is no integer or one outside 1 .. 255 is a ValueError."""
+    import numpy as np
+    try:
+        a = np.asarray(t)
+    except Exception:
+        raise ValueError("a quantisation table is 64 values or 8 x 8 values") from None
+    if a.shape not in ((64,), (8, 8)):
+        raise ValueError(f"a quantisation table is 64 values or 8 x 8 values, not an array of shape {a.shape}")
+    if a.dtype.kind not in "iu":
+        if a.dtype.kind != "f" or not np.all(a == np.floor(a)):
+            raise ValueError("the entries of a quantisation table are integers 1 .. 255")
+    a = a.reshape(64)
+    if np.any(a < 1) or np.any(a > 255):
+        raise ValueError(f"the entries of a quantisation table are 1 .. 255, not {int(a.min())} .. {int(a.max())}")
+    return np.ascontiguousarray(a.astype(np.uint8))
+
+
+def table_consts(table):
+    """Constants of the matrix-pipe quantiser for an arbitrary table (jpegamd_debug_table_consts): what mfma_consts and
+    group_thresholds give for a quality -- qmul/qthr/bias/zoff/qadd float32[64] by zigzag position, delta float64[64] by raster k,
+    grp_thr and lo_bound float32 [4][2]."""
+    import numpy as np
+    t = as_quant_table(table)
+    out = {k: np.zeros(64, np.float32) for k in ("qmul", "qthr", "bias", "zoff", "qadd")}
+    delta, grp, lo = np.zeros(64, np.float64), np.zeros(8, np.float32), np.zeros(8, np.float32)
+    _checked("jpegamd_debug_table_consts", t.ctypes.data, out["qmul"].ctypes.data, out["qthr"].ctypes.data, out["bias"].ctypes.data,
+             delta.ctypes.data, out["zoff"].ctypes.data, out["qadd"].ctypes.data, grp.ctypes.data, lo.ctypes.data)
+    return dict(out, delta=delta, grp_thr=grp.reshape(4, 2), lo_bound=lo.reshape(4, 2))
+
+
+def parse_qtables(text: str):
+    """The text format of cjpeg -qtables -> (luma, chroma), uint8[64] each in raster order; chroma is None for a text of one table.
+    Decimal integers separated by whitespace, `#` starts a comment that runs to the end of the line, 64 values a table in raster
+    order, one or two tables; anything else is a ValueError that names the count found."""
+    words = " ".join(line.split("#", 1)[0] for line in text.splitlines()).split()
+    bad = [w for w in words if not (w.isascii() and w.isdigit())]
+    if bad:
+        raise ValueError(f"quantisation tables are written as decimal integers, not {bad[0]!r}")
+    if len(words) not in (64, 128):
+        raise ValueError(f"expected 64 or 128 values (one or two tables of 64), found {len(words)}")
+    values = [int(w) for w in words]
+    return as_quant_table(values[:64]), (as_quant_table(values[64:]) if len(values) == 128 else None)
 
 
 def cos_lut():
@@ -505,6 +567,41 @@ def _tensor_encoder(dev: int, w: int, rows: int):
     return enc
 
 
+_block_tables = threading.local()            # .tables: the (luma, chroma) of the innermost quant_tables block of this thread
+
+
+@contextlib.contextmanager
+def quant_tables(luma, chroma=None):
+    """with jpegamd.quant_tables(luma, chroma): every module-level encode of this thread -- jpegamd's, jpegamd.mjpeg's and the
+    progressive modules' -- writes its files with these quantisation tables (as_quant_table takes each; chroma None: the luma table
+    for every component) and ignores `quality`.  The tables are set on the shared per-device context for each call and taken off
+    behind it, so that outside the block, also when an exception leaves it, the cached contexts encode by quality.  Blocks nest:
+    the inner tables hold until the inner block ends."""
+    tables = (as_quant_table(luma), None if chroma is None else as_quant_table(chroma))
+    before = getattr(_block_tables, "tables", None)
+    _block_tables.tables = tables
+    try:
+        yield
+    finally:
+        _block_tables.tables = before
+
+
+@contextlib.contextmanager
+def _borrowed_encoder(dev: int, w: int, rows: int):
+    """The per-device context for the calls of one tensor function: with the tables of the thread's quant_tables block set on it, and
+    back on quality when the function is done with it, whatever happens."""
+    enc = _tensor_encoder(dev, w, rows)
+    tables = getattr(_block_tables, "tables", None)
+    if tables is None:
+        yield enc
+        return
+    enc.set_quant_tables(*tables)
+    try:
+        yield enc
+    finally:
+        enc.set_quant_tables(None)
+
+
 def _files(out, sizes, k: int) -> list:
     """The first k files of a finished call: row i of `out`, sizes[i] bytes of it."""
     got = sizes[:k].cpu().tolist()
@@ -519,9 +616,9 @@ def _encode_pictures(device, n: int, h: int, w: int, cap: int, queue, huffman=No
     import torch
     dev = device.index if device.index is not None else torch.cuda.current_device()
     files = []
-    with torch.cuda.device(dev):
-        per = min(n, MAX_BATCH)
-        enc = _tensor_encoder(dev, w, per * ((h + 7) // 8 * 8))      # a batch needs `per` x the block rows of one picture
+    per = min(n, MAX_BATCH)
+    # (a batch needs `per` x the block rows of one picture; inside a quant_tables block the context carries its tables meanwhile)
+    with torch.cuda.device(dev), _borrowed_encoder(dev, w, per * ((h + 7) // 8 * 8)) as enc:
         out = torch.empty((per, cap), dtype=torch.uint8, device=device)
         sizes = torch.zeros(per, dtype=torch.int64, device=device)
         stream = torch.cuda.current_stream(device).cuda_stream
@@ -570,8 +667,7 @@ def encode_tensor(t, quality: int = 0, subsampling: int = SUBSAMPLE_420, layout=
     else:
         raise ValueError("encode_tensor takes [H, W] or [H, W, 3]")
     dev = t.device.index if t.device.index is not None else torch.cuda.current_device()
-    with torch.cuda.device(dev):
-        enc = _tensor_encoder(dev, w, h)
+    with torch.cuda.device(dev), _borrowed_encoder(dev, w, h) as enc:
         cap = max_jfif_bytes(w, h) if order == ORDER_GRAY else max_jfif_bytes_color(w, h, subsampling)
         out = torch.empty((1, cap), dtype=torch.uint8, device=t.device)
         size = torch.zeros(1, dtype=torch.int64, device=t.device)
@@ -1130,6 +1226,26 @@ class Encoder(_ProgressiveScriptEntries):
         """HUFFMAN_STANDARD (the Annex K tables, default) or HUFFMAN_OPTIMIZED (per-picture tables) for the one-scan entries
         (jpegamd_encoder_set_huffman); takes effect with the next encode."""
         _checked("jpegamd_encoder_set_huffman", self._h, int(huffman))
+
+    def set_quant_tables(self, luma, chroma=None):
+        """Quantisation tables of the caller's for every later encode on this context (jpegamd_encoder_set_quant_tables): each as
+        as_quant_table takes it; chroma None: the luma table for every component.  set_quant_tables(None): back to the tables of each
+        picture's quality.  Takes effect with the next encode; a refused table leaves the context as it was."""
+        if luma is None:
+            if chroma is not None:
+                raise ValueError("a chroma table needs a luma table")
+            _checked("jpegamd_encoder_set_quant_tables", self._h, None, None)
+            return
+        lt = as_quant_table(luma)
+        ct = None if chroma is None else as_quant_table(chroma)
+        _checked("jpegamd_encoder_set_quant_tables", self._h, lt.ctypes.data, None if ct is None else ct.ctypes.data)
+
+    def quant_tables(self):
+        """None while the context encodes by quality, else the (luma, chroma) it holds: uint8[64] each, raster order."""
+        import numpy as np
+        luma, chroma, custom = np.zeros(64, np.uint8), np.zeros(64, np.uint8), C.c_int32(0)
+        _checked("jpegamd_encoder_get_quant_tables", self._h, luma.ctypes.data, chroma.ctypes.data, C.byref(custom))
+        return (luma, chroma) if custom.value else None
 
     def set_profiling(self, slots: int):
         _checked("jpegamd_encoder_set_profiling", self._h, int(slots))

@@ -63,6 +63,10 @@ spectral, successive (the built-in scripts, passed explicitly) or gray (the defa
 the text form of libjpeg's -scans files (jpegamd.progressive_script.parse_scan_script).  A script in which component 0 alone appears
 writes grayscale files (the luma of the pictures) through jpegamd_encode_gray_progressive_script_batch_async.  The line carries "scans".
 
+--qtables FILE (every mode): the context encodes with the one or two quantisation tables of FILE -- the text form of cjpeg -qtables,
+64 decimal values a table in raster order, `#` comments (jpegamd.parse_qtables; examples in tools/qtables/) -- set through
+jpegamd_encoder_set_quant_tables; --quality then selects nothing, and every line carries "qtables".
+
 --scan gray (with --batch N, default 8) times GRAYSCALE files through jpegamd_encode_gray_scan_batch_async: the luma
 of the same --size pictures, --restart N|row in blocks (`row`: ceil(W / 8)), --huffman standard|optimized; the whole call is timed
 (ns_total).  Without --restart (or with 0) and with the standard tables the entry is jpegamd_encode_batch_async, so that line is the
@@ -117,6 +121,8 @@ def main() -> None:
                     help="--scan progressive --huffman optimized: the ten scans of successive approximation (DESIGN.md 4.6.14)")
     ap.add_argument("--scans", default=None, metavar="NAME|FILE",
                     help="--scan progressive: a scan script -- spectral, successive, gray, or a file in libjpeg's -scans text form (DESIGN.md 4.6.15)")
+    ap.add_argument("--qtables", default=None, metavar="FILE",
+                    help="every --scan mode: quantisation tables of the caller's, one or two in the text form of cjpeg -qtables (tools/qtables/)")
     a = ap.parse_args()
     if a.scans is not None and (a.scan != "progressive" or a.successive or a.huffman is not None or a.source != "rgb"):
         sys.exit("--scans needs --scan progressive and takes --size, --batch, --subsampling, --quality, --kind alone")
@@ -178,7 +184,7 @@ def main() -> None:
     img, off = jpegamd.parse_bmp(bmp)
     px = torch.frombuffer(bytearray(bmp[off:off + img.row_stride * h]), dtype=torch.uint8).to(dev)
     desc = jpegamd.Encoder.image(px.data_ptr(), w, h, img.row_stride, True, jpegamd.ORDER_BGR, a.quality)
-    enc = jpegamd.Encoder(w, h)
+    enc = new_encoder(a, jpegamd, w, h)
     stream = torch.cuda.current_stream().cuda_stream
     for sub, name in rgb_subsamplings(a, jpegamd):
         cap = jpegamd.max_jfif_bytes_color(w, h, sub)
@@ -196,10 +202,24 @@ def main() -> None:
         enc.set_profiling(0)
         med = {k: int(statistics.median(p[i] for p in per)) for i, k in enumerate(KERNELS)}
         t = statistics.median(totals)
-        print(json.dumps({"subsampling": name, "width": w, "height": h, "quality": a.quality, "kind": a.kind, "steps": a.steps,
-                          "bytes": int(size.item()), "entropy_bits": st.entropy_bits, "ns_total_median": int(t),
-                          "gpixels_per_s": round(w * h / t, 2), "kernel_ns_median": med,
-                          "kernel_ns_sum": sum(med.values())}))
+        report(a, {"subsampling": name, "width": w, "height": h, "quality": a.quality, "kind": a.kind, "steps": a.steps,
+                    "bytes": int(size.item()), "entropy_bits": st.entropy_bits, "ns_total_median": int(t),
+                    "gpixels_per_s": round(w * h / t, 2), "kernel_ns_median": med,
+                    "kernel_ns_sum": sum(med.values())})
+
+
+def new_encoder(a, jpegamd, w, rows):
+    """The context of a run, with the tables of --qtables set on it."""
+    enc = jpegamd.Encoder(w, rows)
+    if a.qtables is not None:
+        with open(a.qtables, encoding="utf-8") as f:
+            enc.set_quant_tables(*jpegamd.parse_qtables(f.read()))
+    return enc
+
+
+def report(a, line) -> None:
+    """One JSON result line; with --qtables it names the file whose tables wrote the files ("quality" then selected nothing)."""
+    print(json.dumps(dict(line, qtables=a.qtables) if a.qtables is not None else line))
 
 
 def rgb_subsamplings(a, jpegamd):
@@ -242,7 +262,7 @@ def run_gray(a, jpegamd, torch, dev) -> None:
         pxs.append(torch.frombuffer(bytearray(bmp[off:off + img.row_stride * h]), dtype=torch.uint8).to(dev))
         descs.append(jpegamd.Encoder.image(pxs[-1].data_ptr(), w, h, img.row_stride, True, jpegamd.ORDER_BGR, a.quality))
         del bmp
-    enc = jpegamd.Encoder(w, n * h)
+    enc = new_encoder(a, jpegamd, w, n * h)
     restart = 0 if a.restart is None else (-(-w // 8) if a.restart == "row" else int(a.restart))
     cap = max(jpegamd.max_jfif_bytes_gray_scan(w, h, restart), jpegamd.max_jfif_bytes(w, h))
     outs = [torch.empty(cap, dtype=torch.uint8, device=dev) for _ in range(n)]
@@ -267,10 +287,10 @@ def run_gray(a, jpegamd, torch, dev) -> None:
     if a.huffman == "optimized":
         enc.set_huffman(jpegamd.HUFFMAN_OPTIMIZED)
     t, st, got = timed(lambda: enc.encode_gray_scan_batch_async(descs, restart, out_ptrs, cap, size_ptrs, stream))
-    print(json.dumps({"scan": "gray", "width": w, "height": h, "batch": n, "quality": a.quality, "kind": a.kind, "steps": a.steps,
-                      "restart_interval": restart, "huffman": a.huffman or "standard", "bytes": got, "entropy_bits": st.entropy_bits,
-                      "ns_total_median": int(t), "us_per_picture": round(t / n / 1000, 1), "gpixels_per_s": round(n * w * h / t, 2),
-                      "plain_bytes": plain_bytes, "plain_us_per_picture": round(plain / n / 1000, 1), "ratio_to_plain": round(t / plain, 2)}))
+    report(a, {"scan": "gray", "width": w, "height": h, "batch": n, "quality": a.quality, "kind": a.kind, "steps": a.steps,
+                "restart_interval": restart, "huffman": a.huffman or "standard", "bytes": got, "entropy_bits": st.entropy_bits,
+                "ns_total_median": int(t), "us_per_picture": round(t / n / 1000, 1), "gpixels_per_s": round(n * w * h / t, 2),
+                "plain_bytes": plain_bytes, "plain_us_per_picture": round(plain / n / 1000, 1), "ratio_to_plain": round(t / plain, 2)})
 
 
 def run_scans(a, jpegamd, torch, dev) -> None:
@@ -293,7 +313,7 @@ def run_scans(a, jpegamd, torch, dev) -> None:
         pxs.append(torch.frombuffer(bytearray(bmp[off:off + img.row_stride * h]), dtype=torch.uint8).to(dev))
         descs.append(jpegamd.Encoder.image(pxs[-1].data_ptr(), w, h, img.row_stride, True, jpegamd.ORDER_BGR, a.quality))
         del bmp
-    enc = jpegamd.Encoder(w, n * h)
+    enc = new_encoder(a, jpegamd, w, n * h)
     stream = torch.cuda.current_stream().cuda_stream
     for sub, name in ([(0, "gray")] if gray else rgb_subsamplings(a, jpegamd)):
         cap = jpegamd.max_jfif_bytes_progressive_script(w, h, sub, script)
@@ -315,10 +335,10 @@ def run_scans(a, jpegamd, torch, dev) -> None:
         totals = [enc.profile(i).ns_total for i in range(a.steps)]
         enc.set_profiling(0)
         t = statistics.median(totals)
-        print(json.dumps({"source": "rgb", "subsampling": name, "width": w, "height": h, "batch": n, "quality": a.quality, "kind": a.kind,
-                          "steps": a.steps, "bytes": sizes.cpu().tolist(), "entropy_bits": st.entropy_bits, "ns_total_median": int(t),
-                          "us_per_picture": round(t / n / 1000, 1), "gpixels_per_s": round(n * w * h / t, 2), "scan": "progressive",
-                          "scans": a.scans, "scan_count": len(script)}))
+        report(a, {"source": "rgb", "subsampling": name, "width": w, "height": h, "batch": n, "quality": a.quality, "kind": a.kind,
+                    "steps": a.steps, "bytes": sizes.cpu().tolist(), "entropy_bits": st.entropy_bits, "ns_total_median": int(t),
+                    "us_per_picture": round(t / n / 1000, 1), "gpixels_per_s": round(n * w * h / t, 2), "scan": "progressive",
+                    "scans": a.scans, "scan_count": len(script)})
         del outs
 
 
@@ -334,7 +354,7 @@ def run_batch(a, jpegamd, torch, dev, sources=("rgb",)) -> None:
         pxs.append(torch.frombuffer(bytearray(bmp[off:off + img.row_stride * h]), dtype=torch.uint8).to(dev))
         descs.append(jpegamd.Encoder.image(pxs[-1].data_ptr(), w, h, img.row_stride, True, jpegamd.ORDER_BGR, a.quality))
         del bmp
-    enc = jpegamd.Encoder(w, n * h)
+    enc = new_encoder(a, jpegamd, w, n * h)
     if a.huffman == "optimized" and a.scan != "progressive":      # (the optimised progressive entries do not read the context's mode)
         enc.set_huffman(jpegamd.HUFFMAN_OPTIMIZED)
     stream = torch.cuda.current_stream().cuda_stream
@@ -494,7 +514,7 @@ def run_batch(a, jpegamd, torch, dev, sources=("rgb",)) -> None:
             if a.convert:
                 line.update(time_matrix_convert(a, jpegamd, torch, enc, source, tensors, (lut_y, lut_c), h, sub, out_ptrs, cap, size_ptrs,
                                                 sizes, stream, n))
-            print(json.dumps(line))
+            report(a, line)
             del outs
             continue
         if a.narrow and source in ("p010", "i010"):
@@ -502,7 +522,7 @@ def run_batch(a, jpegamd, torch, dev, sources=("rgb",)) -> None:
         if a.convert and source not in ("p010", "i010"):
             line.update(time_convert(a, jpegamd, torch, enc, source, tensors, describe, (lut_y, lut_c), h, sub, out_ptrs, cap, size_ptrs,
                                      sizes, stream, n))
-        print(json.dumps(line))
+        report(a, line)
         del outs
 
 
@@ -685,7 +705,7 @@ def run_layout(a, jpegamd, torch, dev) -> None:
         src = hwc
     if a.layout != "hwc" and not a.repack:
         del hwc
-    enc = jpegamd.Encoder(w, n * h)
+    enc = new_encoder(a, jpegamd, w, n * h)
     if a.huffman == "optimized":
         enc.set_huffman(jpegamd.HUFFMAN_OPTIMIZED)
     stream = torch.cuda.current_stream().cuda_stream
@@ -746,12 +766,12 @@ def run_layout(a, jpegamd, torch, dev) -> None:
             medians[k].append(statistics.median(e0.elapsed_time(e1) for e0, e1 in evs) * 1000.0 / n)
     for k in routes:
         m = medians[k]
-        print(json.dumps({"layout": a.layout, "route": k, "width": w, "height": h, "batch": n, "quality": a.quality, "kind": a.kind,
-                          "steps": a.steps, "rounds": a.rounds, "bytes": got[k], "us_per_picture_medians": [round(v, 1) for v in m],
-                          "us_per_picture": round(statistics.median(m), 1), "spread_us": round(max(m) - min(m), 1),
-                          "gpixels_per_s": round(w * h / statistics.median(m) / 1000, 2),
-                          **({"scan": "interleaved", "restart_interval": restart} if one_scan else {}),
-                          **({"huffman": a.huffman} if a.huffman is not None else {})}))
+        report(a, {"layout": a.layout, "route": k, "width": w, "height": h, "batch": n, "quality": a.quality, "kind": a.kind,
+                    "steps": a.steps, "rounds": a.rounds, "bytes": got[k], "us_per_picture_medians": [round(v, 1) for v in m],
+                    "us_per_picture": round(statistics.median(m), 1), "spread_us": round(max(m) - min(m), 1),
+                    "gpixels_per_s": round(w * h / statistics.median(m) / 1000, 2),
+                    **({"scan": "interleaved", "restart_interval": restart} if one_scan else {}),
+                    **({"huffman": a.huffman} if a.huffman is not None else {})})
 
 
 if __name__ == "__main__":
