@@ -112,6 +112,7 @@ int32_t jpegamd_encoder_destroy(JpegAmdEncoder *enc);
 
 /* Upper bound on the JFIF bytes an image of this size can produce (every block at the
  * 1658-bit worst case and every byte stuffed): size `out` with this. */
+/* (With metadata set on the context -- jpegamd_encoder_set_metadata -- a buffer needs jpegamd_encoder_metadata_bytes() more than this bound.) */
 uint64_t jpegamd_max_jfif_bytes(int32_t width, int32_t height);
 
 /* Enqueue one encode on `stream` (a hipStream_t, or NULL for the default stream).
@@ -164,6 +165,7 @@ int32_t jpegamd_encode_batch_async(JpegAmdEncoder *enc, const JpegAmdImage *imgs
  *  test suite rely on it as a known-bad value, and a new meaning for it would change what existing code gets.) */
 #define JPEGAMD_SUBSAMPLE_422 4
 /* Upper bound on the colour file's bytes (every block at the 1723-bit chroma worst case, every byte stuffed); 0 for bad args. */
+/* (With metadata set on the context -- jpegamd_encoder_set_metadata -- a buffer needs jpegamd_encoder_metadata_bytes() more than this bound.) */
 uint64_t jpegamd_max_jfif_bytes_color(int32_t width, int32_t height, int32_t subsampling);
 int32_t jpegamd_encode_color_async(JpegAmdEncoder *enc, const JpegAmdImage *img, int32_t subsampling, void *out_dev,
                                    uint64_t out_capacity, uint64_t *out_size_dev, void *stream);
@@ -346,6 +348,7 @@ int32_t jpegamd_encode_ycbcr_interleaved_batch_async(JpegAmdEncoder *enc, const 
                                                      void *const *outs_dev, uint64_t out_capacity, void *const *out_sizes_dev, void *stream);
 /* Upper bound on the interleaved file's bytes: 640 (the prefix) + 2 * (ceil(nb * 1723 / 8) + 1) + 2 + 16 with
  * nb = mx * my * (hs * vs + 2) blocks, pad blocks included (jpegamd_max_jfif_bytes_color does not count those); 0 for bad args. */
+/* (With metadata set on the context -- jpegamd_encoder_set_metadata -- a buffer needs jpegamd_encoder_metadata_bytes() more than this bound.) */
 uint64_t jpegamd_max_jfif_bytes_interleaved(int32_t width, int32_t height, int32_t subsampling);
 
 /* The one-scan files with RESTART INTERVALS (DRI / RSTn, T.81 B.2.4.4, E.1.4) -- what an RTP/JPEG sender puts into
@@ -381,6 +384,7 @@ int32_t jpegamd_encode_ycbcr_interleaved_restart_batch_async(JpegAmdEncoder *enc
  * the scan's bits rounded up to a byte once with every byte stuffed; the DRI segment adds 6 bytes, and every interval but the last
  * rounds up on its own -- at most one more byte --, may have that byte stuffed, and ends with two marker bytes.  With
  * restart_interval 0 it equals jpegamd_max_jfif_bytes_interleaved; 0 for bad arguments (restart_interval outside 0 .. 65535 too). */
+/* (With metadata set on the context -- jpegamd_encoder_set_metadata -- a buffer needs jpegamd_encoder_metadata_bytes() more than this bound.) */
 uint64_t jpegamd_max_jfif_bytes_interleaved_restart(int32_t width, int32_t height, int32_t subsampling, int32_t restart_interval);
 
 /* The one-scan files from EVERY source the three-scan entries read.  No new file: the one-scan file above -- with
@@ -493,6 +497,71 @@ int32_t jpegamd_encoder_set_quant_tables(JpegAmdEncoder *enc, const uint8_t *lum
 /* What the context holds: *custom = 1 and the two tables, or *custom = 0 (tables untouched). */
 int32_t jpegamd_encoder_get_quant_tables(JpegAmdEncoder *enc, uint8_t *luma, uint8_t *chroma, int32_t *custom);
 
+/* METADATA: ICC profile, Exif, comment, pixel density, segments of the caller's.
+ * Let F be the file an entry writes for some call.  For a context that holds metadata the file is
+ *     F[0, 20) with its density fields replaced  |  B  |  F[20, ..)
+ * F[0, 20) is SOI and the JFIF APP0 segment: byte 13 the density units (0 aspect ratio, 1 dots per inch, 2 dots per cm), bytes
+ * 14 .. 17 the X and Y density (big-endian, 1 .. 65535 each); with density_units -1 they stay 01 0060 0060 (96 dpi).
+ * B, the "blob" of M bytes, is a sequence of complete marker segments -- FF mm, a big-endian length of payload + 2, the payload -- in
+ * this order:
+ *   1. Exif      FFE1, "Exif\0\0" + the caller's TIFF block (exif / exif_len; at most 65527 bytes)
+ *   2. segments  the caller's own, in the caller's order: at most 16, markers 0xE1 .. 0xEF and 0xFE only, 0 .. 65533 bytes of payload
+ *                each, not interpreted (XMP, MPF, a second comment)
+ *   3. ICC       the profile cut into chunks of at most 65519 bytes; each FFE2, "ICC_PROFILE\0" + the chunk's number (from 1) + the
+ *                number of chunks + the chunk, as libjpeg's jpeg_write_icc_profile writes it.  More than 255 chunks (a profile above
+ *                16707345 bytes): refused
+ *   4. comment   FFFE, 0 .. 65533 bytes; a non-NULL pointer with length 0 writes an empty COM segment, NULL writes none
+ * A NULL exif / icc pointer writes no such segment; an exif or icc pointer with length 0 writes none either.  The bytes are copied
+ * verbatim: an FF inside a payload is not stuffed.  Nothing behind offset 20 of F changes, for any entry, source, subsampling,
+ * scan kind, restart interval, Huffman mode, scan script or quantisation tables. */
+typedef struct {
+    int32_t marker;             /* 0xE1 .. 0xEF, 0xFE */
+    const uint8_t *data;        /* the payload; NULL only with len 0 */
+    uint32_t len;               /* 0 .. 65533 */
+} JpegAmdSegment;
+typedef struct {
+    int32_t density_units;      /* -1: leave 96 dpi (x_density, y_density are not looked at); 0, 1, 2 */
+    int32_t x_density, y_density;   /* 1 .. 65535 */
+    const uint8_t *exif;        /* the TIFF block, WITHOUT the "Exif\0\0" identifier */
+    uint32_t exif_len;
+    const uint8_t *icc;
+    uint64_t icc_len;
+    const uint8_t *comment;
+    uint32_t comment_len;
+    const JpegAmdSegment *segments;
+    int32_t segment_count;      /* 0 .. 16 */
+} JpegAmdMetadata;
+#define JPEGAMD_METADATA_HEAD_BYTES 20
+#define JPEGAMD_METADATA_MAX_SEGMENTS 16
+/* THE definition of B and of the 20 leading bytes; everything else goes through it.  Host only: no context, no device.  Validates
+ * `m`, returns M (>= 0), fills `blob` when M <= capacity (a NULL blob with capacity 0 asks for the length alone; a capacity that is
+ * too small still returns M and writes nothing), and fills `head` (may be NULL) with the 20 leading bytes.  JPEGAMD_ERR_ARG: m NULL,
+ * any refusal above, a NULL pointer with a non-zero length, a NULL blob with a capacity. */
+int64_t jpegamd_build_metadata(const JpegAmdMetadata *m, uint8_t *blob, uint64_t capacity, uint8_t *head /*[20]*/);
+/* Metadata for every later encode on this context; `m` NULL (or a description that sets nothing) clears it.  Everything is copied:
+ * the caller may free its buffers at once.  Sticky on the context, like jpegamd_encoder_set_quant_tables.  An invalid description:
+ * JPEGAMD_ERR_ARG, and the context keeps what it had.
+ * The call itself touches no device memory and does not disturb queued work.  The NEXT encode uploads the 20 + M bytes into context
+ * scratch that only grows -- behind the work queued on this context, so a switch costs a stream wait as a switch of quantisation
+ * tables does.
+ * CAPACITY.  No jpegamd_max_jfif_bytes* changes: a caller sizes its buffers as bound + jpegamd_encoder_metadata_bytes().  With M
+ * bytes set an entry behaves towards out_capacity as it does without metadata towards out_capacity - M (a capacity <= M counts
+ * as 0): a file that fits has its size + M in the size word; a size word the entry leaves non-zero for a file that did NOT fit (the
+ * would-be size) has + M too, a zero stays zero; JPEGAMD_ERR_HUFF_CAPACITY is raised exactly when it would be for out_capacity - M;
+ * nothing is written at or beyond out + out_capacity, nor in front of out.  JpegAmdStats.jfif_bytes includes M; every other field is
+ * what the call reports without metadata.
+ * With nothing set every entry writes the bytes it wrote before, with the launches it made before.  With metadata set each call
+ * makes ONE more launch (k_metadata_place) behind its own.
+ * The metadata governs every encode entry that takes a context and writes whole files: jpegamd_encode_async / _batch_async (with
+ * with_container 0 -- a bare scan, no file -- they return JPEGAMD_ERR_ARG while metadata is set), the three-scan and one-scan colour,
+ * planar and YCbCr entries with and without restart intervals, the gray-scan entry and every progressive entry.  One description
+ * serves every picture of a batch.  jpegamd_encode_rows_async / export / import / jpegamd_finalize_async and jpegamd_debug_stages
+ * return JPEGAMD_ERR_ARG while metadata is set rather than drop it silently.  convertToJpeg, the stage functions and the BMP and
+ * file entries own their contexts and write no metadata. */
+int32_t jpegamd_encoder_set_metadata(JpegAmdEncoder *enc, const JpegAmdMetadata *m);
+/* M of the metadata the context holds (0: none, or a density alone). */
+int64_t jpegamd_encoder_metadata_bytes(JpegAmdEncoder *enc);
+
 /* GRAYSCALE files with restart intervals and per-picture optimised Huffman tables: the grayscale file written as
  * a scan of ONE component from coefficient planes, the way the one-scan colour files are.  For a picture of W x H at quality q,
  * restart_interval = Ri (0 .. 65535, in MCUs) and the context's Huffman mode (jpegamd_encoder_set_huffman governs this entry too):
@@ -531,6 +600,7 @@ int32_t jpegamd_encoder_get_quant_tables(JpegAmdEncoder *enc, uint8_t *luma, uin
  * outside 1 .. 65535, restart_interval outside 0 .. 65535). */
 int32_t jpegamd_encode_gray_scan_batch_async(JpegAmdEncoder *enc, const JpegAmdImage *imgs, int32_t count, int32_t restart_interval,
                                              void *const *outs_dev, uint64_t out_capacity, uint64_t *const *out_sizes_dev, void *stream);
+/* (With metadata set on the context -- jpegamd_encoder_set_metadata -- a buffer needs jpegamd_encoder_metadata_bytes() more than this bound.) */
 uint64_t jpegamd_max_jfif_bytes_gray_scan(int32_t width, int32_t height, int32_t restart_interval);
 
 /* Progressive colour files (SOF2): seven scans by spectral selection, no successive approximation (Ah = Al = 0 in every scan).  The
@@ -577,6 +647,7 @@ int32_t jpegamd_encode_ycbcr_progressive_batch_async(JpegAmdEncoder *enc, const 
                                                      int32_t sample_range, int32_t sample_format, int32_t matrix,
                                                      void *const *outs_dev, uint64_t out_capacity, void *const *out_sizes_dev,
                                                      void *stream);
+/* (With metadata set on the context -- jpegamd_encoder_set_metadata -- a buffer needs jpegamd_encoder_metadata_bytes() more than this bound.) */
 uint64_t jpegamd_max_jfif_bytes_progressive(int32_t width, int32_t height, int32_t subsampling);
 
 /* Progressive colour files with END-OF-BAND RUNS and PER-SCAN OPTIMISED TABLES: the file above with three changes.  Unchanged: the
@@ -618,6 +689,7 @@ int32_t jpegamd_encode_ycbcr_progressive_optimized_batch_async(JpegAmdEncoder *e
                                                                int32_t subsampling, int32_t sample_range, int32_t sample_format, int32_t matrix,
                                                                void *const *outs_dev, uint64_t out_capacity, void *const *out_sizes_dev,
                                                                void *stream);
+/* (With metadata set on the context -- jpegamd_encoder_set_metadata -- a buffer needs jpegamd_encoder_metadata_bytes() more than this bound.) */
 uint64_t jpegamd_max_jfif_bytes_progressive_optimized(int32_t width, int32_t height, int32_t subsampling);
 int32_t jpegamd_debug_progressive_counts(JpegAmdEncoder *enc, uint64_t *counts);
 
@@ -680,6 +752,7 @@ int32_t jpegamd_encode_ycbcr_progressive_successive_batch_async(JpegAmdEncoder *
                                                                 int32_t subsampling, int32_t sample_range, int32_t sample_format, int32_t matrix,
                                                                 void *const *outs_dev, uint64_t out_capacity, void *const *out_sizes_dev,
                                                                 void *stream);
+/* (With metadata set on the context -- jpegamd_encoder_set_metadata -- a buffer needs jpegamd_encoder_metadata_bytes() more than this bound.) */
 uint64_t jpegamd_max_jfif_bytes_progressive_successive(int32_t width, int32_t height, int32_t subsampling);
 int32_t jpegamd_debug_progressive_successive_counts(JpegAmdEncoder *enc, uint64_t *counts);
 
@@ -744,6 +817,7 @@ int32_t jpegamd_encode_ycbcr_progressive_script_batch_async(JpegAmdEncoder *enc,
 int32_t jpegamd_encode_gray_progressive_script_batch_async(JpegAmdEncoder *enc, const JpegAmdImage *imgs, int32_t count,
                                                            const JpegAmdScan *scans, int32_t scan_count, void *const *outs_dev,
                                                            uint64_t out_capacity, uint64_t *const *out_sizes_dev, void *stream);
+/* (With metadata set on the context -- jpegamd_encoder_set_metadata -- a buffer needs jpegamd_encoder_metadata_bytes() more than this bound.) */
 uint64_t jpegamd_max_jfif_bytes_progressive_script(int32_t width, int32_t height, int32_t subsampling, const JpegAmdScan *scans,
                                                    int32_t scan_count);
 int32_t jpegamd_debug_progressive_script_counts(JpegAmdEncoder *enc, uint64_t *counts, int32_t tables);

@@ -78,6 +78,12 @@ struct JpegAmdEncoder {
     bool custom_tables = false;
     int table_key = kFirstTableKey - 1;
     uint8_t custom_luma[64], custom_chroma[64];
+    // Metadata (jpegamd_encoder_set_metadata): the 20 leading bytes of every file, the blob and kMetaSrcPad zero bytes
+    // as ONE host string, empty while nothing is set; its copy in device scratch that only grows, made by the next encode.
+    std::vector<uint8_t> meta;
+    bool meta_dirty = false;
+    uint8_t *meta_dev = nullptr;
+    size_t meta_cap = 0;
     // cached constants (cur_quality, color.cur_quality and the q of the three HeaderCaches are table keys: quant_choice)
     int cur_quality = -1;
     uint8_t qtable[64];
@@ -404,6 +410,7 @@ extern "C" int32_t jpegamd_encoder_destroy(JpegAmdEncoder *e) {
     free_seg_arrays(&e->seg);
     hipFree(e->huff); hipFree(e->prefix); hipFree(e->stats_dev); hipFree(e->tables_dev);
     hipFree(e->tile_head); hipFree(e->tile_over); hipFree(e->code_tab); hipFree(e->tile_ctr); hipFree(e->desc); hipFree(e->stamps_dev);
+    hipFree(e->meta_dev);
     hipFree(e->color.tables_dev); hipFree(e->color.code_tab); hipFree(e->color.huff); hipFree(e->color.hdr); hipFree(e->color.scan_size);
     hipFree(e->color.scan_stats); hipFree(e->color.planes); hipFree(e->color.scans);
     hipFree(e->color.bmeta); hipFree(e->color.bplanes); hipFree(e->color.bscans);
@@ -452,6 +459,24 @@ extern "C" int32_t jpegamd_encoder_get_quant_tables(JpegAmdEncoder *e, uint8_t *
     if (chroma) std::memcpy(chroma, e->custom_chroma, 64);
     return JPEGAMD_OK;
 }
+
+// Host state only, as the tables above: the next encode uploads.  The description is turned into its bytes here, which is the copy.
+static uint64_t metadata_bytes(const JpegAmdEncoder *e) { return e->meta.empty() ? 0 : e->meta.size() - kJfifHeadBytes - kMetaSrcPad; }
+extern "C" int32_t jpegamd_encoder_set_metadata(JpegAmdEncoder *e, const JpegAmdMetadata *m) {
+    if (!e) return JPEGAMD_ERR_ARG;
+    if (!m) { e->meta.clear(); return JPEGAMD_OK; }
+    const int64_t n = jpegamd_build_metadata(m, nullptr, 0, nullptr);
+    if (n < 0) return (int32_t)n;
+    std::vector<uint8_t> bytes;
+    try { bytes.assign((size_t)kJfifHeadBytes + (size_t)n + kMetaSrcPad, 0); } catch (const std::bad_alloc &) { return JPEGAMD_ERR_HIP; }
+    jpegamd_build_metadata(m, bytes.data() + kJfifHeadBytes, (uint64_t)n, bytes.data());
+    if (n == 0 && m->density_units < 0) bytes.clear();              // a description that sets nothing: today's files, today's launches
+    e->meta.swap(bytes);
+    e->meta_dirty = true;
+    return JPEGAMD_OK;
+}
+
+extern "C" int64_t jpegamd_encoder_metadata_bytes(JpegAmdEncoder *e) { return e ? (int64_t)metadata_bytes(e) : JPEGAMD_ERR_ARG; }
 
 extern "C" int32_t jpegamd_encoder_set_profiling(JpegAmdEncoder *e, int32_t slots) {
     if (!e || slots < 0 || slots > 65536) return JPEGAMD_ERR_ARG;
@@ -803,6 +828,54 @@ static int32_t enqueued(JpegAmdEncoder *e, hipStream_t stream, int segs, bool ti
     return JPEGAMD_OK;
 }
 
+// Grow-only scratch: *p holds *cap units of `unit` bytes; a call that needs more gets a new buffer of exactly `need` units, behind
+// whatever queued work may still use the old one.  The contents are not kept.
+template <class T>
+static int32_t grow_scratch(JpegAmdEncoder *e, T **p, size_t *cap, size_t need, size_t unit = sizeof(T)) {
+    if (need <= *cap) return JPEGAMD_OK;
+    if (int32_t rc = wait_pending(e)) return rc;
+    hipFree(*p); *p = nullptr; *cap = 0;
+    HIP_TRY(hipMalloc((void **)p, need * unit));
+    *cap = need;
+    return JPEGAMD_OK;
+}
+
+// Metadata around the launches of one call: `run(outs, capacity)` is an entry's whole launch sequence.  Nothing
+// set: exactly that.  Otherwise the sequence runs M bytes further into every buffer with M bytes less capacity -- a capacity of at
+// most M counts as 0, and the pointers then stay where they are: nothing is written either way -- and k_metadata_place, once per call
+// behind the last launch, puts the 20 leading bytes and the blob in front and adds M to the sizes.  A profiled call's time runs to the end
+// of that kernel: the slot's last event takes its end stamp, or -- `end_recorded`: the entry records that event on the stream -- is
+// recorded again behind it.
+template <class Run>
+static int32_t with_metadata(JpegAmdEncoder *e, int32_t count, void *const *outs_dev, uint64_t out_capacity, uint64_t *const *out_sizes_dev,
+                             void *stream, bool end_recorded, Run run) {
+    if (e->meta.empty()) return run(outs_dev, out_capacity);
+    const uint64_t m = metadata_bytes(e);
+    if (e->meta_dirty) {                                               // the context's copy, behind whatever queued work still reads the old one
+        if (int32_t rc = grow_scratch(e, &e->meta_dev, &e->meta_cap, e->meta.size())) return rc;
+        if (int32_t rc = wait_pending(e)) return rc;
+        HIP_TRY(hipMemcpy(e->meta_dev, e->meta.data(), e->meta.size(), hipMemcpyHostToDevice));
+        e->meta_dirty = false;
+    }
+    const uint64_t cap = out_capacity > m ? out_capacity - m : 0;
+    void *outs[kMaxBatch];
+    for (int i = 0; i < count; ++i) outs[i] = cap ? (uint8_t *)outs_dev[i] + m : outs_dev[i];
+    if (int32_t rc = run(outs, cap)) return rc;
+    MetadataPlaceArgs pa;
+    std::memset(&pa, 0, sizeof(pa));
+    for (int i = 0; i < count; ++i) { pa.out[i] = (uint8_t *)outs_dev[i]; pa.out_size[i] = out_sizes_dev[i]; }
+    pa.out_capacity = out_capacity;
+    pa.src = e->meta_dev; pa.bytes = kJfifHeadBytes + m; pa.batch = count; pa.stats = e->stats_dev;
+    hipEvent_t end = nullptr;
+    if (e->timed && e->last_slot >= 0) {
+        const auto &set = e->ring[(size_t)e->last_slot];
+        end = set.color ? set.cev[21] : set.ev[5];
+    }
+    if (launch_metadata_place(pa, stream, end_recorded ? nullptr : end)) return JPEGAMD_ERR_HIP;
+    if (end && end_recorded) HIP_TRY(hipEventRecord(end, (hipStream_t)stream));
+    return JPEGAMD_OK;
+}
+
 // ---------------------------------------------------------------------------------------------------------
 // One image sharded over several GPUs by block rows.  Each rank transforms and entropy-codes its rows
 // (jpegamd_encode_rows_async: the unstuffed per-segment bit strings stay in its scratch), exports them densely
@@ -811,7 +884,7 @@ static int32_t enqueued(JpegAmdEncoder *e, hipStream_t stream, int segs, bool ti
 // 0xFF stuffing and the zero-padded flush depend on the global byte phase and so happen once, at the root.
 // ---------------------------------------------------------------------------------------------------------
 static int32_t shard_desc(JpegAmdEncoder *e, const JpegAmdImage *img, int32_t by0, int32_t by1, ImageDesc *im) {
-    if (!e) return JPEGAMD_ERR_ARG;
+    if (!e || !e->meta.empty()) return JPEGAMD_ERR_ARG;            // (the sharded entries write no metadata: refused, not dropped)
     int32_t rc = describe(e, img, im);
     if (rc) return rc;
     if (by0 < 0 || by1 < by0 || by1 > im->blocks_h) return JPEGAMD_ERR_ARG;
@@ -931,8 +1004,8 @@ static int32_t plan_batch(const JpegAmdEncoder *e, const JpegAmdImage &g0, const
 }
 
 // The grayscale files of a batch whose arguments are known to be good: g0 describes every picture, ps holds their pixels.
-static int32_t gray_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, const PlaneSet &ps, int32_t count, void *const *outs_dev,
-                          uint64_t out_capacity, uint64_t *const *out_sizes_dev, int32_t with_container, void *stream_) {
+static int32_t gray_batch_run(JpegAmdEncoder *e, const JpegAmdImage &g0, const PlaneSet &ps, int32_t count, void *const *outs_dev,
+                              uint64_t out_capacity, uint64_t *const *out_sizes_dev, int32_t with_container, void *stream_) {
     ImageDesc im;
     bool stitch;
     int32_t rc = plan_batch(e, g0, ps, count, &im, &stitch);
@@ -946,6 +1019,15 @@ static int32_t gray_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, const Plane
     if (code_tiles(e, im, src_of(&g0), &ps, nullptr, outs_dev, out_capacity, out_sizes_dev, with_container, nullptr, stitch, stream, ev,
                    ev ? ev + 4 : nullptr)) return JPEGAMD_ERR_HIP;
     return enqueued(e, stream, count * im.num_segs, ev != nullptr);
+}
+
+// ... with the context's metadata in front (a bare scan is no file: refused while metadata is set).
+static int32_t gray_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, const PlaneSet &ps, int32_t count, void *const *outs_dev,
+                          uint64_t out_capacity, uint64_t *const *out_sizes_dev, int32_t with_container, void *stream_) {
+    if (!e->meta.empty() && !with_container) return JPEGAMD_ERR_ARG;
+    return with_metadata(e, count, outs_dev, out_capacity, out_sizes_dev, stream_, false, [&](void *const *outs, uint64_t cap) {
+        return gray_batch_run(e, g0, ps, count, outs, cap, out_sizes_dev, with_container, stream_);
+    });
 }
 
 // One picture: the argument checks, then a batch of one.
@@ -1004,18 +1086,6 @@ static int32_t color_alloc_consts(JpegAmdEncoder *e) {
     return JPEGAMD_OK;
 }
 
-// Grow-only scratch: *p holds *cap units of `unit` bytes; a call that needs more gets a new buffer of exactly `need` units, behind
-// whatever queued work may still use the old one.  The contents are not kept.
-template <class T>
-static int32_t grow_scratch(JpegAmdEncoder *e, T **p, size_t *cap, size_t need, size_t unit = sizeof(T)) {
-    if (need <= *cap) return JPEGAMD_OK;
-    if (int32_t rc = wait_pending(e)) return rc;
-    hipFree(*p); *p = nullptr; *cap = 0;
-    HIP_TRY(hipMalloc((void **)p, need * unit));
-    *cap = need;
-    return JPEGAMD_OK;
-}
-
 static int32_t color_alloc(JpegAmdEncoder *e, int w, int h) {
     auto &c = e->color;
     if (int32_t rc = color_alloc_consts(e)) return rc;
@@ -1054,6 +1124,8 @@ static int run_scan(JpegAmdEncoder *e, const ImageDesc &im, TileSource src, void
     return launch_sum_stats(e->seg.syms, e->seg.exact, im.num_segs, tgt.stats, stream);
 }
 
+static int32_t color_single_run(JpegAmdEncoder *e, const JpegAmdImage *img, int32_t subsampling, void *out_dev, uint64_t out_capacity,
+                                uint64_t *out_size_dev, void *stream_);
 extern "C" int32_t jpegamd_encode_color_async(JpegAmdEncoder *e, const JpegAmdImage *img, int32_t subsampling, void *out_dev,
                                               uint64_t out_capacity, uint64_t *out_size_dev, void *stream_) {
     if (!e || !img || !out_dev || !out_size_dev) return JPEGAMD_ERR_ARG;
@@ -1063,6 +1135,14 @@ extern "C" int32_t jpegamd_encode_color_async(JpegAmdEncoder *e, const JpegAmdIm
         return jpegamd_encode_color_batch_async(e, img, 1, subsampling, one.outs, out_capacity, one.sizes, stream_);
     }
     if (img->channel_order != JPEGAMD_ORDER_BGR && img->channel_order != JPEGAMD_ORDER_RGB) return JPEGAMD_ERR_ARG;
+    const SingleOut one = {{out_dev}, {out_size_dev}};
+    return with_metadata(e, 1, one.outs, out_capacity, one.sizes, stream_, false, [&](void *const *outs, uint64_t cap) {
+        return color_single_run(e, img, subsampling, outs[0], cap, out_size_dev, stream_);
+    });
+}
+
+static int32_t color_single_run(JpegAmdEncoder *e, const JpegAmdImage *img, int32_t subsampling, void *out_dev, uint64_t out_capacity,
+                                uint64_t *out_size_dev, void *stream_) {
     ImageDesc iy;
     const bool stitch_y = use_stitch(e, img->width, img->height);
     int32_t rc = describe(e, img, &iy, stitch_y ? kSegTilesBatch : kSegTiles);
@@ -1322,9 +1402,9 @@ static const uint8_t *chroma_plane_of(const JpegAmdEncoder *e, const YccSource *
 // `ycc` (a YCbCr batch): g0 / px are the Y planes as a GRAY picture, the chroma scans read the caller's planes -- no
 // k_chroma_planes_batch launch, no plane scratch.  A BT.709 YCbCr batch (ycc->matrix) is the RGB route with another kernel in front:
 // k_ycbcr_matrix_batch writes BT.601 Y, Cb and Cr planes into the plane scratch, and every launch reads those as full-range planes.
-static int32_t color_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, const PlaneSet &px, int32_t count, int32_t subsampling,
-                           void *const *outs_dev, uint64_t out_capacity, uint64_t *const *out_sizes_dev, void *stream_,
-                           const YccSource *ycc_in = nullptr) {
+static int32_t color_batch_run(JpegAmdEncoder *e, const JpegAmdImage &g0, const PlaneSet &px, int32_t count, int32_t subsampling,
+                               void *const *outs_dev, uint64_t out_capacity, uint64_t *const *out_sizes_dev, void *stream_,
+                               const YccSource *ycc_in) {
     const bool mx = ycc_in && ycc_in->matrix == JPEGAMD_MATRIX_BT709;
     const YccSource *const ycc = mx ? nullptr : ycc_in;               // what the launches read: the caller's planes, or the scratch
     // Y: the grayscale batch's launch plan
@@ -1429,6 +1509,15 @@ static int32_t color_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, const Plan
     hipEvent_t ev_append[2] = {nullptr, cev ? cev[21] : nullptr};
     if (launch_append_scans_batch(aa, stream, cev ? (void *const *)ev_append : nullptr)) return JPEGAMD_ERR_HIP;
     return enqueued(e, stream, count * iy.num_segs, cev != nullptr, true);
+}
+
+// ... with the context's metadata in front.
+static int32_t color_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, const PlaneSet &px, int32_t count, int32_t subsampling,
+                           void *const *outs_dev, uint64_t out_capacity, uint64_t *const *out_sizes_dev, void *stream_,
+                           const YccSource *ycc_in = nullptr) {
+    return with_metadata(e, count, outs_dev, out_capacity, out_sizes_dev, stream_, false, [&](void *const *outs, uint64_t cap) {
+        return color_batch_run(e, g0, px, count, subsampling, outs, cap, out_sizes_dev, stream_, ycc_in);
+    });
 }
 
 extern "C" int32_t jpegamd_encode_color_batch_async(JpegAmdEncoder *e, const JpegAmdImage *imgs, int32_t count, int32_t subsampling,
@@ -2162,9 +2251,9 @@ static int progressive_scans(JpegAmdEncoder *e, const McuGeometry &g, const Prog
 // before there were restart intervals: k_mcu_segments<false>, k_finalize, k_mcu_totals.
 // subsampling kSubNone (jpegamd_encode_gray_scan_batch_async alone): the grayscale file as a scan of ONE component, DESIGN.md 4.6.11 -- the luma of g0 / px
 // tapped and coded, no chroma launch, two tables; always through the restart writer (the caller sends the plain Annex K file elsewhere).
-static int32_t interleaved_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, const PlaneSet &px, int32_t count, int32_t subsampling, int32_t restart,
-                                 void *const *outs_dev, uint64_t out_capacity, uint64_t *const *out_sizes_dev, void *stream_,
-                                 const YccSource *ycc_in = nullptr, int progressive = kProgNone, const ProgScript *user_script = nullptr) {
+static int32_t interleaved_batch_run(JpegAmdEncoder *e, const JpegAmdImage &g0, const PlaneSet &px, int32_t count, int32_t subsampling, int32_t restart,
+                                     void *const *outs_dev, uint64_t out_capacity, uint64_t *const *out_sizes_dev, void *stream_,
+                                     const YccSource *ycc_in, int progressive, const ProgScript *user_script) {
     // `progressive`: the same taps, plane pass, matrix pass and grouping; behind a group's taps its seven scans
     // (progressive_scans) in place of k_mcu_segments, k_finalize and k_mcu_totals.  Colour, the Annex K tables, no restart intervals.
     // kProgRuns: histograms, tables and the restart writer as well (progressive_runs_scans); the context's Huffman
@@ -2348,6 +2437,15 @@ static int32_t interleaved_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, cons
     if (runs) { m.plast = count; m.plast_tables = script.tables; m.plast_script = script.id; }
     if (cev) HIP_TRY(hipEventRecord(cev[21], stream));
     return enqueued(e, stream, count * g.num_segs_pad, cev != nullptr, true);
+}
+
+// ... with the context's metadata in front: placed once, behind the last group's launches.
+static int32_t interleaved_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, const PlaneSet &px, int32_t count, int32_t subsampling, int32_t restart,
+                                 void *const *outs_dev, uint64_t out_capacity, uint64_t *const *out_sizes_dev, void *stream_,
+                                 const YccSource *ycc_in = nullptr, int progressive = kProgNone, const ProgScript *user_script = nullptr) {
+    return with_metadata(e, count, outs_dev, out_capacity, out_sizes_dev, stream_, true, [&](void *const *outs, uint64_t cap) {
+        return interleaved_batch_run(e, g0, px, count, subsampling, restart, outs, cap, out_sizes_dev, stream_, ycc_in, progressive, user_script);
+    });
 }
 
 // Tests: k_huff_optimal on arbitrary counts -- `n` tables of 256 counts each (a table's sum below 2^54) -> BITS, HUFFVAL (zeros behind
@@ -2722,7 +2820,7 @@ static uint64_t last_symbol_count(const JpegAmdEncoder *e) { return e->mirror.to
 
 extern "C" int32_t jpegamd_debug_stages(JpegAmdEncoder *e, const JpegAmdImage *img, int8_t *y_centered,
                                         int16_t *quant_zigzag, uint64_t *exact_mask) {
-    if (!e) return JPEGAMD_ERR_ARG;
+    if (!e || !e->meta.empty()) return JPEGAMD_ERR_ARG;            // (no file, so no metadata: refused while some is set)
     ImageDesc im;
     int32_t rc = describe(e, img, &im);
     if (rc) return rc;

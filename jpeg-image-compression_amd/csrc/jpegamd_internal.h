@@ -382,6 +382,24 @@ struct AppendBatchArgs {
 };
 int launch_append_scans_batch(const AppendBatchArgs &a, void *stream, void *const *ev = nullptr);
 
+// Metadata in front of the tables (jpegamd_metadata.hip).  The entries of a context that holds metadata of M bytes
+// write each file at out + M; k_metadata_place then copies `bytes` = 20 + M bytes -- the file's 20 leading bytes with the caller's
+// density, then the marker segments -- to out[0, bytes), over the shifted copy of those 20 bytes, and adds M to every size word that
+// is not zero (a file that did not fit keeps its zero) and to the record's out_size.  A picture with out_capacity < bytes is left alone.
+constexpr int kJfifHeadBytes = 20;      // SOI and the APP0 segment: what every file begins with
+constexpr int kMetaSrcPad = 32;         // zero bytes behind src[bytes): the kernel reads whole 16-byte pieces, one beyond the last
+struct MetadataPlaceArgs {
+    uint8_t *out[kMaxBatch];
+    uint64_t *out_size[kMaxBatch];
+    uint64_t out_capacity;
+    const uint8_t *src;                 // 16-byte aligned; bytes + kMetaSrcPad readable
+    uint64_t bytes;                     // 20 + M
+    int32_t batch;
+    ScanStats *stats;                   // the context's record
+};
+// end_event (may be null): takes the kernel's end stamp, as the events of launch_append_scans_batch do.
+int launch_metadata_place(const MetadataPlaceArgs &a, void *stream, void *end_event = nullptr);
+
 // Interleaved-MCU colour files (jpegamd_encode_color_interleaved_batch_async, jpegamd_mcu.hip): ONE scan coded from coefficient
 // planes.  A picture's planes lie at coef + picture * pic_stride (int16 elements): Y [bh][bw][64] at 0, Cb and Cr [my][mx][64] at
 // cb_off / cr_off -- what the stage-tap build of k_tile_encode stores through tap_zz, zigzag order inside a block.  The MCU grid

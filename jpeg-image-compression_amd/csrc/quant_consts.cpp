@@ -15,10 +15,12 @@
 //   last     rounding of K/q, of the fma, and of the reference's final scale and division
 //
 // tests/test_host.py::test_mfma_constants_are_on_the_safe_side pins the stored constants against the oracle's arithmetic.
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <vector>
 
+#include "jpeg_compression.h"
 #include "jpegamd_internal.h"
 
 namespace jpegamd {
@@ -377,3 +379,89 @@ void cos_lut_copy(float out[64]) {
 }
 
 }  // namespace jpegamd
+
+// ---- metadata in front of the tables ------------------------------------------------------------------------
+// Host only and reentrant: the one definition of the blob B and of the 20 leading bytes (see the header).  One pass over the
+// description checks it and counts M; a second one writes, when the caller's buffer holds M bytes.
+namespace jpegamd {
+namespace {
+constexpr uint64_t kSegPayloadMax = 65533;                           // the 16-bit length counts itself
+constexpr char kExifId[] = "Exif\0";                                  // 6 bytes with the terminator
+constexpr char kIccId[] = "ICC_PROFILE";                             // 12 bytes with the terminator
+constexpr uint64_t kExifMax = kSegPayloadMax - 6, kIccChunkMax = kSegPayloadMax - 14, kIccMaxChunks = 255;
+
+struct BlobWriter {
+    uint8_t *p;                                                      // null: count only
+    uint64_t n = 0;
+    void bytes(const void *src, uint64_t len) {
+        if (p && len) std::memcpy(p + n, src, (size_t)len);
+        n += len;
+    }
+    void byte(unsigned v) { if (p) p[n] = (uint8_t)v; ++n; }
+    void segment_head(int marker, uint64_t payload) { byte(0xFF); byte((unsigned)marker); byte((unsigned)((payload + 2) >> 8)); byte((unsigned)(payload + 2)); }
+};
+
+bool metadata_valid(const JpegAmdMetadata &m) {
+    if (m.density_units != -1) {
+        if (m.density_units < 0 || m.density_units > 2) return false;
+        if (m.x_density < 1 || m.x_density > 65535 || m.y_density < 1 || m.y_density > 65535) return false;
+    }
+    if ((!m.exif && m.exif_len) || m.exif_len > kExifMax) return false;
+    if ((!m.icc && m.icc_len) || m.icc_len > kIccChunkMax * kIccMaxChunks) return false;
+    if ((!m.comment && m.comment_len) || m.comment_len > kSegPayloadMax) return false;
+    if (m.segment_count < 0 || m.segment_count > JPEGAMD_METADATA_MAX_SEGMENTS || (!m.segments && m.segment_count)) return false;
+    for (int i = 0; i < m.segment_count; ++i) {
+        const JpegAmdSegment &s = m.segments[i];
+        if (!((s.marker >= 0xE1 && s.marker <= 0xEF) || s.marker == 0xFE)) return false;
+        if ((!s.data && s.len) || s.len > kSegPayloadMax) return false;
+    }
+    return true;
+}
+
+uint64_t write_blob(const JpegAmdMetadata &m, uint8_t *out) {
+    BlobWriter w{out};
+    if (m.exif && m.exif_len) {
+        w.segment_head(0xE1, 6 + (uint64_t)m.exif_len);
+        w.bytes(kExifId, 6);
+        w.bytes(m.exif, m.exif_len);
+    }
+    for (int i = 0; i < m.segment_count; ++i) {
+        w.segment_head(m.segments[i].marker, m.segments[i].len);
+        w.bytes(m.segments[i].data, m.segments[i].len);
+    }
+    if (m.icc && m.icc_len) {
+        const uint64_t chunks = (m.icc_len + kIccChunkMax - 1) / kIccChunkMax;
+        for (uint64_t c = 0; c < chunks; ++c) {
+            const uint64_t off = c * kIccChunkMax, len = std::min(kIccChunkMax, m.icc_len - off);
+            w.segment_head(0xE2, 14 + len);
+            w.bytes(kIccId, 12);
+            w.byte((unsigned)(c + 1));
+            w.byte((unsigned)chunks);
+            w.bytes(m.icc + off, len);
+        }
+    }
+    if (m.comment) {
+        w.segment_head(0xFE, m.comment_len);
+        w.bytes(m.comment, m.comment_len);
+    }
+    return w.n;
+}
+}  // namespace
+
+void metadata_head(int units, int x_density, int y_density, uint8_t head[kJfifHeadBytes]) {
+    static const uint8_t plain[kJfifHeadBytes] = {0xFF, 0xD8, 0xFF, 0xE0, 0x00, 0x10, 'J', 'F', 'I', 'F', 0x00, 0x01, 0x01, 0x01, 0x00, 0x60, 0x00, 0x60, 0x00, 0x00};
+    std::memcpy(head, plain, sizeof(plain));
+    if (units < 0) return;
+    head[13] = (uint8_t)units;
+    head[14] = (uint8_t)(x_density >> 8); head[15] = (uint8_t)x_density;
+    head[16] = (uint8_t)(y_density >> 8); head[17] = (uint8_t)y_density;
+}
+}  // namespace jpegamd
+
+extern "C" int64_t jpegamd_build_metadata(const JpegAmdMetadata *m, uint8_t *blob, uint64_t capacity, uint8_t *head) {
+    if (!m || (!blob && capacity) || !jpegamd::metadata_valid(*m)) return JPEGAMD_ERR_ARG;
+    const uint64_t need = jpegamd::write_blob(*m, nullptr);
+    if (blob && need <= capacity) jpegamd::write_blob(*m, blob);
+    if (head) jpegamd::metadata_head(m->density_units, m->x_density, m->y_density, head);
+    return (int64_t)need;
+}

@@ -84,6 +84,18 @@ class BatchStats(C.Structure):
                 ("seconds_total", C.c_double), ("seconds_read", C.c_double), ("seconds_write", C.c_double)]
 
 
+class Segment(C.Structure):
+    """JpegAmdSegment: a marker segment of the caller's (0xE1 .. 0xEF, 0xFE) and its payload."""
+    _fields_ = [("marker", C.c_int32), ("data", C.c_void_p), ("len", C.c_uint32)]
+
+
+class Metadata(C.Structure):
+    """JpegAmdMetadata: pixel density, Exif, ICC profile, comment, segments."""
+    _fields_ = [("density_units", C.c_int32), ("x_density", C.c_int32), ("y_density", C.c_int32),
+                ("exif", C.c_void_p), ("exif_len", C.c_uint32), ("icc", C.c_void_p), ("icc_len", C.c_uint64),
+                ("comment", C.c_void_p), ("comment_len", C.c_uint32), ("segments", C.POINTER(Segment)), ("segment_count", C.c_int32)]
+
+
 def _prototypes():
     """Every entry of libjpegamd.so that the binding calls, written ONCE: name -> (result type, argument types), in three groups.
     `base`: declared in include/jpeg_compression.h, in every build.  `later`: declared there as well, but a variant build of an
@@ -162,6 +174,10 @@ def _prototypes():
         "jpegamd_encoder_set_quant_tables": (i32, [vp, vp, vp]),
         "jpegamd_encoder_get_quant_tables": (i32, [vp, vp, vp, C.POINTER(i32)]),
         "jpegamd_debug_table_consts": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        # metadata in front of the tables
+        "jpegamd_build_metadata": (i64, [C.POINTER(Metadata), vp, u64, vp]),
+        "jpegamd_encoder_set_metadata": (i32, [vp, C.POINTER(Metadata)]),
+        "jpegamd_encoder_metadata_bytes": (i64, [vp]),
     }
     later = {
         "jpegamd_encoder_set_pipeline": (i32, [vp, i32]),
@@ -332,6 +348,86 @@ def parse_qtables(text: str):
         raise ValueError(f"expected 64 or 128 values (one or two tables of 64), found {len(words)}")
     values = [int(w) for w in words]
     return as_quant_table(values[:64]), (as_quant_table(values[64:]) if len(values) == 128 else None)
+
+
+_EXIF_ID = b"Exif\0\0"
+
+
+def _bytes_of(value, what: str) -> bytes:
+    if isinstance(value, (bytes, bytearray, memoryview)):
+        return bytes(value)
+    raise ValueError(f"{what} is given as bytes, not as {type(value).__name__}")
+
+
+def _metadata_struct(icc_profile=None, exif=None, comment=None, dpi=None, density=None, segments=()):
+    """The keywords of build_metadata -> (Metadata, the objects its pointers refer to: keep them while the struct is in use)."""
+    m, keep = Metadata(), []
+    m.density_units = -1
+
+    def buffer(data: bytes):
+        buf = C.create_string_buffer(data, len(data)) if data else C.create_string_buffer(1)
+        keep.append(buf)
+        return C.cast(buf, C.c_void_p)
+
+    if dpi is not None and density is not None:
+        raise ValueError("give dpi or density, not both")
+    if dpi is not None:
+        x, y = dpi if isinstance(dpi, (tuple, list)) else (dpi, dpi)
+        density = (1, x, y)
+    if density is not None:
+        units, x, y = density
+        if any(v != int(v) for v in (units, x, y)):
+            raise ValueError("a pixel density is made of whole numbers: units 0 .. 2, X and Y 1 .. 65535")
+        m.density_units, m.x_density, m.y_density = int(units), int(x), int(y)
+        if m.density_units < 0:
+            raise ValueError("density units are 0 (aspect ratio), 1 (dots per inch) or 2 (dots per cm)")
+    if exif is not None:
+        data = exif.tobytes() if hasattr(exif, "tobytes") and not isinstance(exif, memoryview) else _bytes_of(exif, "exif")
+        if data.startswith(_EXIF_ID):
+            data = data[len(_EXIF_ID):]
+        m.exif, m.exif_len = buffer(data), len(data)
+    if icc_profile is not None:
+        data = _bytes_of(icc_profile, "icc_profile")
+        m.icc, m.icc_len = buffer(data), len(data)
+    if comment is not None:
+        data = comment.encode("utf-8") if isinstance(comment, str) else _bytes_of(comment, "comment")
+        m.comment, m.comment_len = buffer(data), len(data)
+    segments = list(segments)
+    if segments:
+        arr = (Segment * len(segments))()
+        for seg, (marker, payload) in zip(arr, segments):
+            data = _bytes_of(payload, "a segment's payload")
+            seg.marker, seg.data, seg.len = int(marker), buffer(data), len(data)
+        keep.append(arr)
+        m.segments, m.segment_count = arr, len(segments)
+    return m, keep
+
+
+def build_metadata(icc_profile=None, exif=None, comment=None, dpi=None, density=None, segments=()):
+    """(head, blob), both bytes: the 20 leading bytes of every file and the marker segments that follow them, as a context with this
+    metadata writes them (jpegamd_build_metadata; host only).  dpi=(x, y) or a number: dots per inch; density=(units, x, y) with
+    units 0 / 1 / 2.  exif: the TIFF block as bytes, with or without the "Exif\\0\\0" identifier, or an object with .tobytes()
+    (PIL's Image.Exif).  comment: str (written as UTF-8) or bytes; "" writes an empty comment.  segments: (marker, payload) pairs of
+    the caller's own, 0xE1 .. 0xEF and 0xFE, written between Exif and the ICC profile.  What the library refuses is a ValueError."""
+    m, keep = _metadata_struct(icc_profile, exif, comment, dpi, density, segments)
+    head = C.create_string_buffer(20)
+    n = lib.jpegamd_build_metadata(C.byref(m), None, 0, head)
+    if n < 0:
+        raise ValueError("metadata refused: a density outside units 0 .. 2 / 1 .. 65535, Exif above 65527 bytes, a comment or segment "
+                         "above 65533, a marker other than 0xE1 .. 0xEF / 0xFE, more than 16 segments or an ICC profile above 16707345 bytes")
+    blob = C.create_string_buffer(max(int(n), 1))
+    if lib.jpegamd_build_metadata(C.byref(m), blob, int(n), head) != n:
+        raise JpegAmdError(-1, "jpegamd_build_metadata")
+    del keep
+    return head.raw, blob.raw[:int(n)]
+
+
+def exif_orientation(n: int) -> bytes:
+    """The TIFF block that holds the orientation tag (0x0112) alone, value n = 1 .. 8: 26 bytes, little-endian.  For exif=."""
+    import struct
+    if not 1 <= int(n) <= 8:
+        raise ValueError("an Exif orientation is 1 .. 8")
+    return b"II*\0" + struct.pack("<IHHHIHHI", 8, 1, 0x0112, 3, 1, int(n), 0, 0)
 
 
 def cos_lut():
@@ -586,20 +682,48 @@ def quant_tables(luma, chroma=None):
         _block_tables.tables = before
 
 
+_block_metadata = threading.local()          # .keywords: those of the innermost metadata block of this thread
+
+
+@contextlib.contextmanager
+def metadata(icc_profile=None, exif=None, comment=None, dpi=None, density=None, segments=()):
+    """with jpegamd.metadata(icc_profile=, exif=, comment=, dpi=, density=, segments=): every module-level encode of this thread --
+    jpegamd's, jpegamd.mjpeg's and the progressive modules' -- writes this metadata into its files (build_metadata names the
+    keywords).  It is set on the shared per-device context for each call and taken off behind it, so that outside the block, also
+    when an exception leaves it, the cached contexts write plain files.  Blocks nest: the inner metadata holds until the inner block
+    ends (it replaces the outer one, it is not merged with it)."""
+    keywords = dict(icc_profile=icc_profile, exif=exif, comment=comment, dpi=dpi, density=density, segments=tuple(segments))
+    build_metadata(**keywords)                   # (refused here, not at the first encode)
+    before = getattr(_block_metadata, "keywords", None)
+    _block_metadata.keywords = keywords
+    try:
+        yield
+    finally:
+        _block_metadata.keywords = before
+
+
 @contextlib.contextmanager
 def _borrowed_encoder(dev: int, w: int, rows: int):
-    """The per-device context for the calls of one tensor function: with the tables of the thread's quant_tables block set on it, and
-    back on quality when the function is done with it, whatever happens."""
+    """The per-device context for the calls of one tensor function: with the tables of the thread's quant_tables block and the
+    metadata of its metadata block set on it, and back on quality and plain files when the function is done with it, whatever
+    happens."""
     enc = _tensor_encoder(dev, w, rows)
     tables = getattr(_block_tables, "tables", None)
-    if tables is None:
+    keywords = getattr(_block_metadata, "keywords", None)
+    if tables is None and keywords is None:
         yield enc
         return
-    enc.set_quant_tables(*tables)
     try:
+        if tables is not None:
+            enc.set_quant_tables(*tables)
+        if keywords is not None:
+            enc.set_metadata(**keywords)
         yield enc
     finally:
-        enc.set_quant_tables(None)
+        if tables is not None:
+            enc.set_quant_tables(None)
+        if keywords is not None:
+            enc.set_metadata(None)
 
 
 def _files(out, sizes, k: int) -> list:
@@ -619,6 +743,7 @@ def _encode_pictures(device, n: int, h: int, w: int, cap: int, queue, huffman=No
     per = min(n, MAX_BATCH)
     # (a batch needs `per` x the block rows of one picture; inside a quant_tables block the context carries its tables meanwhile)
     with torch.cuda.device(dev), _borrowed_encoder(dev, w, per * ((h + 7) // 8 * 8)) as enc:
+        cap += enc.metadata_bytes()                                  # (no bound counts the metadata of a metadata block)
         out = torch.empty((per, cap), dtype=torch.uint8, device=device)
         sizes = torch.zeros(per, dtype=torch.int64, device=device)
         stream = torch.cuda.current_stream(device).cuda_stream
@@ -668,7 +793,7 @@ def encode_tensor(t, quality: int = 0, subsampling: int = SUBSAMPLE_420, layout=
         raise ValueError("encode_tensor takes [H, W] or [H, W, 3]")
     dev = t.device.index if t.device.index is not None else torch.cuda.current_device()
     with torch.cuda.device(dev), _borrowed_encoder(dev, w, h) as enc:
-        cap = max_jfif_bytes(w, h) if order == ORDER_GRAY else max_jfif_bytes_color(w, h, subsampling)
+        cap = (max_jfif_bytes(w, h) if order == ORDER_GRAY else max_jfif_bytes_color(w, h, subsampling)) + enc.metadata_bytes()
         out = torch.empty((1, cap), dtype=torch.uint8, device=t.device)
         size = torch.zeros(1, dtype=torch.int64, device=t.device)
         stream = torch.cuda.current_stream(t.device).cuda_stream
@@ -1246,6 +1371,24 @@ class Encoder(_ProgressiveScriptEntries):
         luma, chroma, custom = np.zeros(64, np.uint8), np.zeros(64, np.uint8), C.c_int32(0)
         _checked("jpegamd_encoder_get_quant_tables", self._h, luma.ctypes.data, chroma.ctypes.data, C.byref(custom))
         return (luma, chroma) if custom.value else None
+
+    def set_metadata(self, *none, icc_profile=None, exif=None, comment=None, dpi=None, density=None, segments=()):
+        """Metadata for every later encode on this context (jpegamd_encoder_set_metadata): the keywords of build_metadata.
+        set_metadata(None), or no keyword at all: plain files again.  Everything is copied; takes effect with the next encode, whose
+        buffers need metadata_bytes() more than the bound; a refused description is a ValueError and leaves the context as it was."""
+        if none not in ((), (None,)):
+            raise TypeError("set_metadata takes keywords, or None alone to clear")
+        m, keep = _metadata_struct(icc_profile, exif, comment, dpi, density, segments)
+        rc = lib.jpegamd_encoder_set_metadata(self._h, C.byref(m))
+        del keep
+        if rc == -1:
+            raise ValueError("metadata refused (see build_metadata)")
+        if rc:
+            raise JpegAmdError(rc, "jpegamd_encoder_set_metadata")
+
+    def metadata_bytes(self) -> int:
+        """M: the bytes the context's metadata adds to every file (jpegamd_encoder_metadata_bytes)."""
+        return int(lib.jpegamd_encoder_metadata_bytes(self._h))
 
     def set_profiling(self, slots: int):
         _checked("jpegamd_encoder_set_profiling", self._h, int(slots))

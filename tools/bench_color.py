@@ -67,6 +67,12 @@ writes grayscale files (the luma of the pictures) through jpegamd_encode_gray_pr
 64 decimal values a table in raster order, `#` comments (jpegamd.parse_qtables; examples in tools/qtables/) -- set through
 jpegamd_encoder_set_quant_tables; --quality then selects nothing, and every line carries "qtables".
 
+--icc BYTES, --comment TEXT, --dpi N (every mode, any of them): the context writes metadata into every file -- a synthetic ICC profile of
+BYTES bytes, a comment, a pixel density -- set through jpegamd_encoder_set_metadata; every buffer is sized as the
+bound + Encoder.metadata_bytes(), and every line carries "metadata_bytes".  The batch loop and --scan gray also time the same call with
+the metadata taken off, in the same run: "no_metadata_ns_total_median" and "metadata_ratio".  The time of a call includes
+k_metadata_place.
+
 --scan gray (with --batch N, default 8) times GRAYSCALE files through jpegamd_encode_gray_scan_batch_async: the luma
 of the same --size pictures, --restart N|row in blocks (`row`: ceil(W / 8)), --huffman standard|optimized; the whole call is timed
 (ns_total).  Without --restart (or with 0) and with the standard tables the entry is jpegamd_encode_batch_async, so that line is the
@@ -123,6 +129,9 @@ def main() -> None:
                     help="--scan progressive: a scan script -- spectral, successive, gray, or a file in libjpeg's -scans text form (DESIGN.md 4.6.15)")
     ap.add_argument("--qtables", default=None, metavar="FILE",
                     help="every --scan mode: quantisation tables of the caller's, one or two in the text form of cjpeg -qtables (tools/qtables/)")
+    ap.add_argument("--icc", type=int, default=None, metavar="BYTES", help="every --scan mode: a synthetic ICC profile of this length in every file")
+    ap.add_argument("--comment", default=None, metavar="TEXT", help="every --scan mode: a comment in every file")
+    ap.add_argument("--dpi", type=int, default=None, metavar="N", help="every --scan mode: this pixel density in every file")
     a = ap.parse_args()
     if a.scans is not None and (a.scan != "progressive" or a.successive or a.huffman is not None or a.source != "rgb"):
         sys.exit("--scans needs --scan progressive and takes --size, --batch, --subsampling, --quality, --kind alone")
@@ -187,7 +196,7 @@ def main() -> None:
     enc = new_encoder(a, jpegamd, w, h)
     stream = torch.cuda.current_stream().cuda_stream
     for sub, name in rgb_subsamplings(a, jpegamd):
-        cap = jpegamd.max_jfif_bytes_color(w, h, sub)
+        cap = jpegamd.max_jfif_bytes_color(w, h, sub) + a.metadata_bytes
         out = torch.empty(cap, dtype=torch.uint8, device=dev)
         size = torch.zeros(1, dtype=torch.int64, device=dev)
         for _ in range(a.warmup):
@@ -214,11 +223,35 @@ def new_encoder(a, jpegamd, w, rows):
     if a.qtables is not None:
         with open(a.qtables, encoding="utf-8") as f:
             enc.set_quant_tables(*jpegamd.parse_qtables(f.read()))
+    a.metadata = {}
+    if a.icc is not None:
+        a.metadata["icc_profile"] = bytes((i * 197 + 31) & 0xFF for i in range(a.icc))
+    if a.comment is not None:
+        a.metadata["comment"] = a.comment
+    if a.dpi is not None:
+        a.metadata["dpi"] = a.dpi
+    if a.metadata:
+        enc.set_metadata(**a.metadata)
+    a.metadata_bytes = enc.metadata_bytes()
     return enc
+
+
+def without_metadata(a, enc, timed):
+    """{}, or -- with metadata on the context -- the same timed call with the metadata taken off: its median and the ratio to `t`."""
+    if not a.metadata:
+        return lambda t: {}
+    enc.set_metadata(None)
+    try:
+        plain = timed()
+    finally:
+        enc.set_metadata(**a.metadata)
+    return lambda t: {"no_metadata_ns_total_median": int(plain), "metadata_ratio": round(t / plain, 4)}
 
 
 def report(a, line) -> None:
     """One JSON result line; with --qtables it names the file whose tables wrote the files ("quality" then selected nothing)."""
+    if getattr(a, "metadata", None):
+        line = dict(line, metadata_bytes=a.metadata_bytes)
     print(json.dumps(dict(line, qtables=a.qtables) if a.qtables is not None else line))
 
 
@@ -264,7 +297,7 @@ def run_gray(a, jpegamd, torch, dev) -> None:
         del bmp
     enc = new_encoder(a, jpegamd, w, n * h)
     restart = 0 if a.restart is None else (-(-w // 8) if a.restart == "row" else int(a.restart))
-    cap = max(jpegamd.max_jfif_bytes_gray_scan(w, h, restart), jpegamd.max_jfif_bytes(w, h))
+    cap = max(jpegamd.max_jfif_bytes_gray_scan(w, h, restart), jpegamd.max_jfif_bytes(w, h)) + a.metadata_bytes
     outs = [torch.empty(cap, dtype=torch.uint8, device=dev) for _ in range(n)]
     sizes = torch.zeros(n, dtype=torch.int64, device=dev)
     out_ptrs = [o.data_ptr() for o in outs]
@@ -290,7 +323,8 @@ def run_gray(a, jpegamd, torch, dev) -> None:
     report(a, {"scan": "gray", "width": w, "height": h, "batch": n, "quality": a.quality, "kind": a.kind, "steps": a.steps,
                 "restart_interval": restart, "huffman": a.huffman or "standard", "bytes": got, "entropy_bits": st.entropy_bits,
                 "ns_total_median": int(t), "us_per_picture": round(t / n / 1000, 1), "gpixels_per_s": round(n * w * h / t, 2),
-                "plain_bytes": plain_bytes, "plain_us_per_picture": round(plain / n / 1000, 1), "ratio_to_plain": round(t / plain, 2)})
+                "plain_bytes": plain_bytes, "plain_us_per_picture": round(plain / n / 1000, 1), "ratio_to_plain": round(t / plain, 2),
+                **without_metadata(a, enc, lambda: timed(lambda: enc.encode_gray_scan_batch_async(descs, restart, out_ptrs, cap, size_ptrs, stream))[0])(t)})
 
 
 def run_scans(a, jpegamd, torch, dev) -> None:
@@ -316,7 +350,7 @@ def run_scans(a, jpegamd, torch, dev) -> None:
     enc = new_encoder(a, jpegamd, w, n * h)
     stream = torch.cuda.current_stream().cuda_stream
     for sub, name in ([(0, "gray")] if gray else rgb_subsamplings(a, jpegamd)):
-        cap = jpegamd.max_jfif_bytes_progressive_script(w, h, sub, script)
+        cap = jpegamd.max_jfif_bytes_progressive_script(w, h, sub, script) + a.metadata_bytes
         outs = [torch.empty(cap, dtype=torch.uint8, device=dev) for _ in range(n)]
         sizes = torch.zeros(n, dtype=torch.int64, device=dev)
         out_ptrs = [o.data_ptr() for o in outs]
@@ -447,6 +481,7 @@ def run_batch(a, jpegamd, torch, dev, sources=("rgb",)) -> None:
         if a.restart is not None:                                # `row`: ceil(W / 8) MCUs at 4:4:4, ceil(W / 16) otherwise
             restart = -(-w // (8 if sub == jpegamd.SUBSAMPLE_444 else 16)) if a.restart == "row" else int(a.restart)
             cap = jpegamd.max_jfif_bytes_interleaved_restart(w, h, sub, restart)
+        cap += a.metadata_bytes
         outs = [torch.empty(cap, dtype=torch.uint8, device=dev) for _ in range(n)]
         sizes = torch.zeros(n, dtype=torch.int64, device=dev)
         out_ptrs = [o.data_ptr() for o in outs]
@@ -482,20 +517,24 @@ def run_batch(a, jpegamd, torch, dev, sources=("rgb",)) -> None:
             if bt709:
                 kw["matrix"] = jpegamd.MATRIX_BT709
             call = lambda: enc.encode_ycbcr_batch_async(ycc, sub, out_ptrs, cap, size_ptrs, stream, **kw)
-        for _ in range(a.warmup):
-            call()
-        enc.finish()
-        enc.set_profiling(a.steps)
-        for _ in range(a.steps):
-            call()
-        st = enc.finish()
-        totals = [enc.profile(i).ns_total for i in range(a.steps)]
-        enc.set_profiling(0)
-        t = statistics.median(totals)
+        def timed():
+            for _ in range(a.warmup):
+                call()
+            enc.finish()
+            enc.set_profiling(a.steps)
+            for _ in range(a.steps):
+                call()
+            st = enc.finish()
+            totals = [enc.profile(i).ns_total for i in range(a.steps)]
+            enc.set_profiling(0)
+            return statistics.median(totals), st
+
+        t, st = timed()
         line = {"source": source, "subsampling": name, "width": w, "height": h, "batch": n, "quality": a.quality, "kind": a.kind,
                 "steps": a.steps, "bytes": sizes.cpu().tolist(), "entropy_bits": st.entropy_bits,
                 "ns_total_median": int(t), "us_per_picture": round(t / n / 1000, 1),
                 "gpixels_per_s": round(n * w * h / t, 2)}
+        line.update(without_metadata(a, enc, lambda: timed()[0])(t))
         if one_scan or progressive:
             line["scan"] = a.scan
         if a.huffman is not None:
@@ -713,7 +752,7 @@ def run_layout(a, jpegamd, torch, dev) -> None:
     restart = 0
     if a.restart is not None:
         restart = -(-w // 16) if a.restart == "row" else int(a.restart)
-    cap = jpegamd.max_jfif_bytes_interleaved_restart(w, h, sub, restart) if one_scan else jpegamd.max_jfif_bytes_color(w, h, sub)
+    cap = (jpegamd.max_jfif_bytes_interleaved_restart(w, h, sub, restart) if one_scan else jpegamd.max_jfif_bytes_color(w, h, sub)) + a.metadata_bytes
     outs = [torch.empty(cap, dtype=torch.uint8, device=dev) for _ in range(n)]
     sizes = torch.zeros(n, dtype=torch.int64, device=dev)
     out_ptrs = [o.data_ptr() for o in outs]
