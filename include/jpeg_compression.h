@@ -822,6 +822,66 @@ uint64_t jpegamd_max_jfif_bytes_progressive_script(int32_t width, int32_t height
                                                    int32_t scan_count);
 int32_t jpegamd_debug_progressive_script_counts(JpegAmdEncoder *enc, uint64_t *counts, int32_t tables);
 
+/* Float pictures: float32, float16 or bfloat16 samples -- what a renderer, a generative model or an augmentation
+ * pipeline leaves on the device -- encoded directly.  One kernel (k_float_planes_batch) in front of the tile encoder reads every sample
+ * once, where it lies, makes its byte, applies the RGB -> YCbCr map and the chroma subsampling of this header to those bytes and
+ * leaves 8-bit Y, Cb and Cr planes in context scratch, which are then coded as a BT.709 batch's planes are.  Every file is BYTE FOR
+ * BYTE the file the uint8 entries write for the bytes of the samples.
+ *
+ * The byte of a stored sample x, for the call's `scale` and `offset`:
+ *     x32 = x converted to float32            (exact for float16 and bfloat16, subnormals included)
+ *     p   = x32 * scale                       rounded once to float32
+ *     t   = p + offset                        rounded once to float32 (NOT fused with the multiply)
+ *     v   = 0                                 if t is NaN
+ *           min(max(rint(t), 0), 255)         otherwise; rint = round half to even; +inf -> 255, -inf -> 0
+ * v is the byte: torch's x.float().mul(scale).add(offset).round().clamp(0, 255).to(uint8) with NaN -> 0.  Behind it, everything is
+ * this header's definition for those bytes: Y = (77 R + 150 G + 29 B) >> 8; Cb and Cr per pixel by the two formulas above; 4:2:0 and
+ * 4:2:2 samples by (a + b + c + d + 2) >> 2 and (a + b + 1) >> 1 with the last column / row replicated; the byte of a single-channel
+ * picture is its Y sample.  scale and offset must be finite and |scale| <= 16777216: no float32 or bfloat16 subnormal can then
+ * reach 0.5, so the result does not depend on the device's float32 denormal mode (float16 subnormals do count: at scale 65536 the
+ * largest one maps to 4).  Samples in [0, 1]: (255, 0); in [-1, 1]: (127.5, 127.5), where 0 is a tie and gives 128; in [0, 255]: (1, 0).
+ *
+ * One description covers every tensor layout.  [3, H, W]: pixel_stride = the sample size.  [H, W, 3], and a channels-last
+ * [N, 3, H, W]: the three pointers one sample apart, pixel_stride = 3 samples.  RGBA floats: 4 samples.  BGR: swap the pointers.
+ * Crops and strided rows as they come.  plane[1] == plane[2] == NULL: ONE channel, the luma itself, for subsampling 0 alone.
+ * Refused with JPEGAMD_ERR_ARG before the context is read: null arrays, elements or plane[0]; exactly one of plane[1] / plane[2]
+ * null; a single channel with a colour subsampling; count outside 1 .. JPEGAMD_MAX_BATCH; an unknown sample_type or subsampling; a
+ * non-finite scale or offset, |scale| above the bound; a pointer, row_stride or pixel_stride that is no multiple of the sample size;
+ * pixel_stride below the sample size; row_stride < pixel_stride * width; pictures of different geometry.  Nothing outside a row's own
+ * samples is read.
+ *
+ *   jpegamd_encode_float_batch_async                     three scans for JPEGAMD_SUBSAMPLE_444 / _420 / _422; subsampling 0: the fused
+ *                                                        grayscale file (the luma of three planes, or the single channel)
+ *   jpegamd_encode_float_interleaved_batch_async         one scan, restart_interval 0 .. 65535, the context's Huffman mode; subsampling
+ *                                                        0 goes where jpegamd_encode_gray_scan_batch_async goes (the plain file is
+ *                                                        the fused entry's)
+ *   jpegamd_encode_float_progressive_script_batch_async  progressive files; scans NULL (scan_count 0): libjpeg's default script;
+ *                                                        subsampling 0: the grayscale progressive file
+ * Context sizing, capacity, status, statistics and every jpegamd_max_jfif_bytes* bound are those of the uint8 entry each call stands
+ * for (jpegamd_encode_planar_batch_async, jpegamd_encode_planar_interleaved_batch_async / jpegamd_encode_gray_scan_batch_async,
+ * jpegamd_encode_color_progressive_script_batch_async / jpegamd_encode_gray_progressive_script_batch_async); quantisation tables and
+ * metadata set on the context apply.  With profiling on, ns_total opens at the front pass. */
+#define JPEGAMD_FLOAT_F32  0
+#define JPEGAMD_FLOAT_F16  1
+#define JPEGAMD_FLOAT_BF16 2
+typedef struct JpegAmdFloatImage {
+    const void *plane[3];   /* DEVICE pointers to the first sample of R, G, B; plane[1] == plane[2] == NULL: one channel (luma) */
+    int32_t width, height;  /* 1..65535 */
+    int32_t row_stride;     /* bytes between rows, the same for the three planes */
+    int32_t pixel_stride;   /* bytes between horizontally adjacent samples of a plane */
+    int32_t quality;
+} JpegAmdFloatImage;
+int32_t jpegamd_encode_float_batch_async(JpegAmdEncoder *enc, const JpegAmdFloatImage *imgs, int32_t count, int32_t subsampling,
+                                         int32_t sample_type, float scale, float offset, void *const *outs_dev, uint64_t out_capacity,
+                                         void *const *out_sizes_dev, void *stream);
+int32_t jpegamd_encode_float_interleaved_batch_async(JpegAmdEncoder *enc, const JpegAmdFloatImage *imgs, int32_t count, int32_t subsampling,
+                                                     int32_t sample_type, float scale, float offset, int32_t restart_interval,
+                                                     void *const *outs_dev, uint64_t out_capacity, void *const *out_sizes_dev, void *stream);
+int32_t jpegamd_encode_float_progressive_script_batch_async(JpegAmdEncoder *enc, const JpegAmdFloatImage *imgs, int32_t count,
+                                                            int32_t subsampling, int32_t sample_type, float scale, float offset,
+                                                            const JpegAmdScan *scans, int32_t scan_count, void *const *outs_dev,
+                                                            uint64_t out_capacity, void *const *out_sizes_dev, void *stream);
+
 /* Block until the last enqueued encode on this context finished; optionally fetch stats
  * (stats may be NULL).  Returns JPEGAMD_ERR_HUFF_CAPACITY if the output did not fit. */
 int32_t jpegamd_encoder_finish(JpegAmdEncoder *enc, JpegAmdStats *stats);

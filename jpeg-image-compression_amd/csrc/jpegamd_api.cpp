@@ -10,6 +10,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <mutex>
 #include <new>
@@ -1003,9 +1004,21 @@ static int32_t plan_batch(const JpegAmdEncoder *e, const JpegAmdImage &g0, const
     return JPEGAMD_OK;
 }
 
+// A batch of float pictures (jpegamd_encode_float_batch_async and its twins): what k_float_planes_batch reads.  The launches behind
+// that pass read the planes it leaves in color.bplanes.
+struct FloatSource {
+    const uint8_t *plane[3][kMaxBatch]; // R, G, B; one channel: plane[0] alone
+    int32_t channels, type, row_stride, pixel_stride;      // 1 or 3; JPEGAMD_FLOAT_*; bytes
+    float scale, offset;
+};
+static int launch_float_luma_pass(JpegAmdEncoder *e, const FloatSource &fl, const JpegAmdImage &gy, int32_t count, hipStream_t stream,
+                                  void *const *ev);
+
 // The grayscale files of a batch whose arguments are known to be good: g0 describes every picture, ps holds their pixels.
+// `fl` (a float batch): g0 / ps are the Y planes in color.bplanes, which the caller has sized and k_float_planes_batch fills first.
 static int32_t gray_batch_run(JpegAmdEncoder *e, const JpegAmdImage &g0, const PlaneSet &ps, int32_t count, void *const *outs_dev,
-                              uint64_t out_capacity, uint64_t *const *out_sizes_dev, int32_t with_container, void *stream_) {
+                              uint64_t out_capacity, uint64_t *const *out_sizes_dev, int32_t with_container, void *stream_,
+                              const FloatSource *fl = nullptr) {
     ImageDesc im;
     bool stitch;
     int32_t rc = plan_batch(e, g0, ps, count, &im, &stitch);
@@ -1016,17 +1029,24 @@ static int32_t gray_batch_run(JpegAmdEncoder *e, const JpegAmdImage &g0, const P
     hipEvent_t *ev;
     rc = claim_slot(e, false, !stitch, &ev);
     if (rc) return rc;
-    if (code_tiles(e, im, src_of(&g0), &ps, nullptr, outs_dev, out_capacity, out_sizes_dev, with_container, nullptr, stitch, stream, ev,
-                   ev ? ev + 4 : nullptr)) return JPEGAMD_ERR_HIP;
+    hipEvent_t ev_tiles[4] = {ev ? ev[0] : nullptr, ev ? ev[1] : nullptr, ev ? ev[2] : nullptr, ev ? ev[3] : nullptr};
+    if (fl) {                                                          // the front pass: ITS begin stamp opens ns_transform and ns_total
+        hipEvent_t ev_front[2] = {ev_tiles[0], nullptr};
+        if (launch_float_luma_pass(e, *fl, g0, count, stream, ev ? (void *const *)ev_front : nullptr)) return JPEGAMD_ERR_HIP;
+        ev_tiles[0] = nullptr;
+    }
+    if (code_tiles(e, im, src_of(&g0), &ps, nullptr, outs_dev, out_capacity, out_sizes_dev, with_container, nullptr, stitch, stream,
+                   ev ? ev_tiles : nullptr, ev ? ev + 4 : nullptr)) return JPEGAMD_ERR_HIP;
     return enqueued(e, stream, count * im.num_segs, ev != nullptr);
 }
 
 // ... with the context's metadata in front (a bare scan is no file: refused while metadata is set).
 static int32_t gray_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, const PlaneSet &ps, int32_t count, void *const *outs_dev,
-                          uint64_t out_capacity, uint64_t *const *out_sizes_dev, int32_t with_container, void *stream_) {
+                          uint64_t out_capacity, uint64_t *const *out_sizes_dev, int32_t with_container, void *stream_,
+                          const FloatSource *fl = nullptr) {
     if (!e->meta.empty() && !with_container) return JPEGAMD_ERR_ARG;
     return with_metadata(e, count, outs_dev, out_capacity, out_sizes_dev, stream_, false, [&](void *const *outs, uint64_t cap) {
-        return gray_batch_run(e, g0, ps, count, outs, cap, out_sizes_dev, with_container, stream_);
+        return gray_batch_run(e, g0, ps, count, outs, cap, out_sizes_dev, with_container, stream_, fl);
     });
 }
 
@@ -1358,6 +1378,47 @@ static int launch_matrix_pass(JpegAmdEncoder *e, const JpegAmdImage &g0, const P
     return launch_ycbcr_matrix_batch(ma, stream, ev);
 }
 
+// k_float_planes_batch over the caller's float samples into color.bplanes, laid out as `m` says: `out` kFloatOutColor -- Y, Cb and Cr
+// planes of geometry cg, where a BT.709 batch has them -- or the Y planes alone (m.y_off = 0: kFloatOutLuma of three channels, or
+// kFloatOutSingle).  The host picks the walk from the pointers and strides: three planes of packed samples; the three channels of a
+// pixel side by side in either order; anything else by samples.
+static int launch_float_pass(JpegAmdEncoder *e, const FloatSource &fl, int w, int h, int32_t count, int out, int32_t subsampling,
+                             const ChromaGeom &cg, const MatrixScratch &m, hipStream_t stream, void *const *ev) {
+    FloatPlanesBatchArgs fa;
+    std::memset(&fa, 0, sizeof(fa));
+    const int kb = fl.type == JPEGAMD_FLOAT_F32 ? 4 : 2;
+    // the three samples of a pixel side by side: 0 as R G B, 1 as B G R, -1 otherwise -- one answer for every picture of the call
+    const auto side_by_side = [&](int i) {
+        const uint8_t *r = fl.plane[0][i], *g = fl.plane[1][i], *b = fl.plane[2][i];
+        return (g == r + kb && b == g + kb) ? 0 : ((g == b + kb && r == g + kb) ? 1 : -1);
+    };
+    int order = fl.channels == 3 && fl.pixel_stride == 3 * kb ? side_by_side(0) : -1;
+    for (int i = 1; i < count && order >= 0; ++i) if (side_by_side(i) != order) order = -1;
+    fa.walk = order >= 0 ? kFloatWalkPacked3 : (fl.pixel_stride == kb ? kFloatWalkPlanar : kFloatWalkGeneric);
+    fa.reversed = order == 1 ? 1 : 0;
+    for (int i = 0; i < count; ++i)
+        for (int k = 0; k < fl.channels; ++k) fa.plane[k][i] = fl.plane[k][i];
+    if (order == 1) for (int i = 0; i < count; ++i) fa.plane[0][i] = fl.plane[2][i];                   // the lowest of the three
+    fa.batch = count;
+    fa.width = w; fa.height = h; fa.row_stride = fl.row_stride; fa.pixel_stride = fl.pixel_stride;
+    fa.type = fl.type; fa.out = out; fa.scale = fl.scale; fa.offset = fl.offset;
+    fa.ypitch = m.ypitch; fa.yplane_bytes = m.yplane_bytes; fa.yplanes = e->color.bplanes + m.y_off;
+    if (out == kFloatOutColor) {
+        fa.mode = chroma_mode(subsampling);
+        fa.cw = cg.cw; fa.ch = cg.ch; fa.pitch = cg.pitch; fa.plane_bytes = cg.plane_bytes; fa.planes = e->color.bplanes;
+    } else {
+        fa.cw = w; fa.ch = h;
+    }
+    return launch_float_planes_batch(fa, stream, ev);
+}
+// ... the Y planes alone, for the grayscale routes: gy describes the scratch planes (matrix_scratch with no chroma in front).
+static int launch_float_luma_pass(JpegAmdEncoder *e, const FloatSource &fl, const JpegAmdImage &gy, int32_t count, hipStream_t stream,
+                                  void *const *ev) {
+    const MatrixScratch m = matrix_scratch(gy.width, gy.height, count, 0);
+    return launch_float_pass(e, fl, gy.width, gy.height, count, fl.channels == 1 ? kFloatOutSingle : kFloatOutLuma, 0, ChromaGeom{}, m,
+                             stream, ev);
+}
+
 // k_chroma_planes_batch over the pixels of an RGB batch (g0 / px, any layout the colour entries take): the 2 x count chroma planes of
 // geometry cg into color.bplanes, plane j (picture j / 2, Cb even, Cr odd) at j x cg.plane_bytes.
 static int launch_plane_pass(JpegAmdEncoder *e, const JpegAmdImage &g0, const PlaneSet &px, int32_t count, int32_t subsampling,
@@ -1404,9 +1465,11 @@ static const uint8_t *chroma_plane_of(const JpegAmdEncoder *e, const YccSource *
 // k_ycbcr_matrix_batch writes BT.601 Y, Cb and Cr planes into the plane scratch, and every launch reads those as full-range planes.
 static int32_t color_batch_run(JpegAmdEncoder *e, const JpegAmdImage &g0, const PlaneSet &px, int32_t count, int32_t subsampling,
                                void *const *outs_dev, uint64_t out_capacity, uint64_t *const *out_sizes_dev, void *stream_,
-                               const YccSource *ycc_in) {
-    const bool mx = ycc_in && ycc_in->matrix == JPEGAMD_MATRIX_BT709;
-    const YccSource *const ycc = mx ? nullptr : ycc_in;               // what the launches read: the caller's planes, or the scratch
+                               const YccSource *ycc_in, const FloatSource *fl) {
+    // a front pass fills the scratch planes: k_ycbcr_matrix_batch (a BT.709 batch), or k_float_planes_batch (`fl`, a float batch: g0 is a
+    // GRAY picture of the batch's geometry, px is not read)
+    const bool front = fl || (ycc_in && ycc_in->matrix == JPEGAMD_MATRIX_BT709);
+    const YccSource *const ycc = front ? nullptr : ycc_in;            // what the launches read: the caller's planes, or the scratch
     // Y: the grayscale batch's launch plan
     ImageDesc iy;
     bool stitch_y;
@@ -1421,12 +1484,12 @@ static int32_t color_batch_run(JpegAmdEncoder *e, const JpegAmdImage &g0, const 
     const MatrixScratch ms = matrix_scratch(g0.width, g0.height, count, cg.plane_bytes);
     rc = color_alloc_consts(e);
     if (rc) return rc;
-    rc = color_batch_alloc(e, mx ? ms.total : (ycc ? 0 : planes * cg.plane_bytes + 256), planes * slot_bytes);
+    rc = color_batch_alloc(e, front ? ms.total : (ycc ? 0 : planes * cg.plane_bytes + 256), planes * slot_bytes);
     if (rc) return rc;
-    // a BT.709 batch: the Y launch is a GRAY batch over the scratch Y planes
+    // behind a front pass the Y launch is a GRAY batch over the scratch Y planes
     JpegAmdImage gy = g0;
     PlaneSet py = px;
-    if (mx) {
+    if (front) {
         gy.pixels = e->color.bplanes + ms.y_off; gy.row_stride = ms.ypitch;
         for (int i = 0; i < count; ++i) py.p[0][i] = e->color.bplanes + ms.y_off + (size_t)i * ms.yplane_bytes;
         rc = plan_batch(e, gy, py, count, &iy, &stitch_y);
@@ -1450,7 +1513,10 @@ static int32_t color_batch_run(JpegAmdEncoder *e, const JpegAmdImage &g0, const 
 
     hipEvent_t *const ev_y = ycc ? cev : nullptr;     // a YCbCr batch begins with its Y launch: that kernel's begin stamp opens ns_total
     hipEvent_t ev_planes[2] = {cev ? cev[0] : nullptr, nullptr};      // (a plane pass comes first: ITS begin stamp opens ns_total)
-    if (mx) {
+    if (fl) {
+        if (launch_float_pass(e, *fl, g0.width, g0.height, count, kFloatOutColor, subsampling, cg, ms, stream, cev ? (void *const *)ev_planes : nullptr))
+            return JPEGAMD_ERR_HIP;
+    } else if (front) {
         if (launch_matrix_pass(e, g0, px, *ycc_in, count, subsampling, cg, ms, stream, cev ? (void *const *)ev_planes : nullptr))
             return JPEGAMD_ERR_HIP;
     } else if (!ycc) {
@@ -1514,9 +1580,9 @@ static int32_t color_batch_run(JpegAmdEncoder *e, const JpegAmdImage &g0, const 
 // ... with the context's metadata in front.
 static int32_t color_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, const PlaneSet &px, int32_t count, int32_t subsampling,
                            void *const *outs_dev, uint64_t out_capacity, uint64_t *const *out_sizes_dev, void *stream_,
-                           const YccSource *ycc_in = nullptr) {
+                           const YccSource *ycc_in = nullptr, const FloatSource *fl = nullptr) {
     return with_metadata(e, count, outs_dev, out_capacity, out_sizes_dev, stream_, false, [&](void *const *outs, uint64_t cap) {
-        return color_batch_run(e, g0, px, count, subsampling, outs, cap, out_sizes_dev, stream_, ycc_in);
+        return color_batch_run(e, g0, px, count, subsampling, outs, cap, out_sizes_dev, stream_, ycc_in, fl);
     });
 }
 
@@ -2253,7 +2319,7 @@ static int progressive_scans(JpegAmdEncoder *e, const McuGeometry &g, const Prog
 // tapped and coded, no chroma launch, two tables; always through the restart writer (the caller sends the plain Annex K file elsewhere).
 static int32_t interleaved_batch_run(JpegAmdEncoder *e, const JpegAmdImage &g0, const PlaneSet &px, int32_t count, int32_t subsampling, int32_t restart,
                                      void *const *outs_dev, uint64_t out_capacity, uint64_t *const *out_sizes_dev, void *stream_,
-                                     const YccSource *ycc_in, int progressive, const ProgScript *user_script) {
+                                     const YccSource *ycc_in, int progressive, const ProgScript *user_script, const FloatSource *fl) {
     // `progressive`: the same taps, plane pass, matrix pass and grouping; behind a group's taps its seven scans
     // (progressive_scans) in place of k_mcu_segments, k_finalize and k_mcu_totals.  Colour, the Annex K tables, no restart intervals.
     // kProgRuns: histograms, tables and the restart writer as well (progressive_runs_scans); the context's Huffman
@@ -2264,8 +2330,10 @@ static int32_t interleaved_batch_run(JpegAmdEncoder *e, const JpegAmdImage &g0, 
     if ((progressive == kProgScript) != (user_script != nullptr)) return JPEGAMD_ERR_ARG;
     const ProgScript &script = user_script ? *user_script : prog_script(progressive);
     if (progressive && (restart || script.comps != (subsampling == kSubNone ? 1 : 3) || (!runs && e->huffman != JPEGAMD_HUFFMAN_STANDARD))) return JPEGAMD_ERR_ARG;
-    const bool mx = ycc_in && ycc_in->matrix == JPEGAMD_MATRIX_BT709;
-    const YccSource *const ycc = mx ? nullptr : ycc_in;               // what the launches read: the caller's planes, or the scratch
+    // a front pass fills the scratch planes, as in color_batch_run: `fl` (a float batch; g0 a GRAY picture of its geometry, px not read)
+    // has k_float_planes_batch there, which for a scan of one component writes the Y planes alone
+    const bool front = fl || (ycc_in && ycc_in->matrix == JPEGAMD_MATRIX_BT709);
+    const YccSource *const ycc = front ? nullptr : ycc_in;            // what the launches read: the caller's planes, or the scratch
     const bool planar = g0.channel_order == kOrderPlanar;
     const McuGeometry g = mcu_geometry(g0.width, g0.height, subsampling, restart);
     // A picture's own tables: k_mcu_histogram and k_huff_optimal in front of the coder, and the restart writer for
@@ -2276,9 +2344,9 @@ static int32_t interleaved_batch_run(JpegAmdEncoder *e, const JpegAmdImage &g0, 
     // segments as short as one MCU: a picture whose scratch alone is beyond the group budget is refused, nothing allocated or launched
     if ((restart || gray) && mcu_scratch_per_pic(g, true) > kMcuScratchBudget) return JPEGAMD_ERR_TOO_LARGE;
     // every launch codes ONE picture's component: the Y plane and a chroma plane must fit the context
-    const MatrixScratch ms = matrix_scratch(g0.width, g0.height, count, g.chroma.plane_bytes);
-    JpegAmdImage gy = g0;                                            // the Y launches' picture: a BT.709 batch reads the scratch Y planes
-    if (mx) gy.row_stride = ms.ypitch;
+    const MatrixScratch ms = matrix_scratch(g0.width, g0.height, count, gray ? 0 : g.chroma.plane_bytes);
+    JpegAmdImage gy = g0;                                            // the Y launches' picture: behind a front pass they read the scratch Y planes
+    if (front) gy.row_stride = ms.ypitch;
     ImageDesc iy;
     int32_t rc = describe(e, &gy, &iy, kSegTiles, planar ? kAcceptPlanar : kAcceptPx4);
     if (rc) return rc;
@@ -2296,7 +2364,7 @@ static int32_t interleaved_batch_run(JpegAmdEncoder *e, const JpegAmdImage &g0, 
     const int group = (int)std::max<size_t>(1, std::min<size_t>((size_t)count, kMcuScratchBudget / per_pic));
     rc = color_alloc_consts(e);
     if (rc) return rc;
-    rc = color_batch_alloc(e, mx ? ms.total : (ycc || gray ? 0 : 2 * (size_t)count * cg.plane_bytes + 256), 0);
+    rc = color_batch_alloc(e, front ? ms.total : (ycc || gray ? 0 : 2 * (size_t)count * cg.plane_bytes + 256), 0);
     if (rc) return rc;
     rc = mcu_alloc(e, g, group, writer, optimized ? count : 0);
     if (rc) return rc;
@@ -2327,7 +2395,11 @@ static int32_t interleaved_batch_run(JpegAmdEncoder *e, const JpegAmdImage &g0, 
     HIP_TRY(hipMemsetAsync(m.scan_stats, 0, sizeof(ScanStats), stream));
     HIP_TRY(hipMemsetAsync(e->stats_dev, 0, offsetof(ScanStats, status), stream));      // the sums and the size; the status stays sticky
 
-    if (mx) {                                                        // once for the whole call, in front of the groups
+    if (fl) {                                                        // once for the whole call, in front of the groups
+        if (gray ? launch_float_luma_pass(e, *fl, gy, count, stream, nullptr)
+                 : launch_float_pass(e, *fl, g0.width, g0.height, count, kFloatOutColor, subsampling, cg, ms, stream, nullptr))
+            return JPEGAMD_ERR_HIP;
+    } else if (front) {
         if (launch_matrix_pass(e, g0, px, *ycc_in, count, subsampling, cg, ms, stream, nullptr)) return JPEGAMD_ERR_HIP;
     } else if (!ycc && !gray) {
         if (launch_plane_pass(e, g0, px, count, subsampling, cg, stream, nullptr)) return JPEGAMD_ERR_HIP;
@@ -2340,7 +2412,7 @@ static int32_t interleaved_batch_run(JpegAmdEncoder *e, const JpegAmdImage &g0, 
             int16_t *coef = m.coef + (size_t)i * g.coef_per_pic;
             {   // Y
                 ImageDesc im = iy;
-                set_single_picture(&im, mx ? c.bplanes + ms.y_off + (size_t)p * ms.yplane_bytes : px.p[0][p]);
+                set_single_picture(&im, front ? c.bplanes + ms.y_off + (size_t)p * ms.yplane_bytes : px.p[0][p]);
                 PlaneSet one = {};                                   // a planar picture: ITS G and B planes are image 0 of the launch
                 if (planar) {
                     for (int k = 0; k < 3; ++k) one.p[k][0] = px.p[k][p];
@@ -2442,9 +2514,10 @@ static int32_t interleaved_batch_run(JpegAmdEncoder *e, const JpegAmdImage &g0, 
 // ... with the context's metadata in front: placed once, behind the last group's launches.
 static int32_t interleaved_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, const PlaneSet &px, int32_t count, int32_t subsampling, int32_t restart,
                                  void *const *outs_dev, uint64_t out_capacity, uint64_t *const *out_sizes_dev, void *stream_,
-                                 const YccSource *ycc_in = nullptr, int progressive = kProgNone, const ProgScript *user_script = nullptr) {
+                                 const YccSource *ycc_in = nullptr, int progressive = kProgNone, const ProgScript *user_script = nullptr,
+                                 const FloatSource *fl = nullptr) {
     return with_metadata(e, count, outs_dev, out_capacity, out_sizes_dev, stream_, true, [&](void *const *outs, uint64_t cap) {
-        return interleaved_batch_run(e, g0, px, count, subsampling, restart, outs, cap, out_sizes_dev, stream_, ycc_in, progressive, user_script);
+        return interleaved_batch_run(e, g0, px, count, subsampling, restart, outs, cap, out_sizes_dev, stream_, ycc_in, progressive, user_script, fl);
     });
 }
 
@@ -2738,6 +2811,151 @@ extern "C" int32_t jpegamd_encode_gray_progressive_script_batch_async(JpegAmdEnc
     PlaneSet ps;
     if (int32_t rc = uniform_batch_args(imgs, count, outs_dev, out_sizes_dev, &ps)) return rc;
     return interleaved_batch(e, imgs[0], ps, count, kSubNone, 0, outs_dev, out_capacity, out_sizes_dev, stream_, nullptr, kProgScript, &sc);
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Float pictures: f32 / f16 / bf16 samples, read once where they lie by k_float_planes_batch, which leaves the
+// planes of their bytes in context scratch; behind it every route is the one a BT.709 batch takes.
+// ---------------------------------------------------------------------------------------------------------
+constexpr float kFloatScaleMax = 16777216.0f;
+
+// The arguments of a float batch, checked before anything of the context is read (outs_dev / out_sizes_dev: null for an entry that
+// writes no files; subsampling 0: the grayscale file) -> the batch's geometry as a GRAY picture and what the pass reads.  ps holds
+// placeholders: no launch behind the pass reads the caller's samples.
+static int32_t float_args(const JpegAmdEncoder *e, const JpegAmdFloatImage *imgs, int32_t count, int32_t subsampling, int32_t sample_type,
+                          float scale, float offset, void *const *outs_dev, void *const *out_sizes_dev, bool files, JpegAmdImage *g0,
+                          PlaneSet *ps, FloatSource *fl, uint64_t **sizes) {
+    if (!e || !imgs || (files && (!outs_dev || !out_sizes_dev)) || count < 1 || count > kMaxBatch) return JPEGAMD_ERR_ARG;
+    if (subsampling != 0 && !sub_valid(subsampling)) return JPEGAMD_ERR_ARG;
+    if (sample_type != JPEGAMD_FLOAT_F32 && sample_type != JPEGAMD_FLOAT_F16 && sample_type != JPEGAMD_FLOAT_BF16) return JPEGAMD_ERR_ARG;
+    if (!std::isfinite(scale) || !std::isfinite(offset) || std::fabs(scale) > kFloatScaleMax) return JPEGAMD_ERR_ARG;
+    const int64_t kb = sample_type == JPEGAMD_FLOAT_F32 ? 4 : 2;
+    const JpegAmdFloatImage &p0 = imgs[0];
+    if (p0.width <= 0 || p0.height <= 0 || p0.width > 65535 || p0.height > 65535) return JPEGAMD_ERR_ARG;
+    if (p0.pixel_stride < kb || p0.pixel_stride % kb != 0 || p0.row_stride % kb != 0 || (int64_t)p0.row_stride < (int64_t)p0.pixel_stride * p0.width)
+        return JPEGAMD_ERR_ARG;
+    if (!p0.plane[0] || (p0.plane[1] == nullptr) != (p0.plane[2] == nullptr)) return JPEGAMD_ERR_ARG;
+    const int channels = p0.plane[1] ? 3 : 1;
+    if (channels == 1 && subsampling != 0) return JPEGAMD_ERR_ARG;
+    *ps = PlaneSet{};
+    *fl = FloatSource{};
+    fl->channels = channels; fl->type = sample_type; fl->row_stride = p0.row_stride; fl->pixel_stride = p0.pixel_stride;
+    fl->scale = scale; fl->offset = offset;
+    for (int i = 0; i < count; ++i) {
+        const JpegAmdFloatImage &g = imgs[i];
+        if (files && (!outs_dev[i] || !out_sizes_dev[i])) return JPEGAMD_ERR_ARG;
+        if (g.width != p0.width || g.height != p0.height || g.row_stride != p0.row_stride || g.pixel_stride != p0.pixel_stride ||
+            g.quality != p0.quality)
+            return JPEGAMD_ERR_ARG;
+        for (int k = 0; k < 3; ++k) {
+            if ((g.plane[k] != nullptr) != (k < channels) || (uintptr_t)g.plane[k] % (uintptr_t)kb != 0) return JPEGAMD_ERR_ARG;
+            fl->plane[k][i] = (const uint8_t *)g.plane[k];
+        }
+        ps->p[0][i] = (const uint8_t *)g.plane[0];
+        if (files) sizes[i] = (uint64_t *)out_sizes_dev[i];
+    }
+    g0->pixels = p0.plane[0];
+    g0->width = p0.width; g0->height = p0.height; g0->row_stride = (p0.width + 3) / 4 * 4; g0->bottom_up = 0;
+    g0->channel_order = JPEGAMD_ORDER_GRAY; g0->quality = p0.quality;
+    return JPEGAMD_OK;
+}
+
+// The Y planes of a float batch's grayscale routes: sized here, filled by the route's front pass -> the pictures its launches code.
+static int32_t float_luma_planes(JpegAmdEncoder *e, const JpegAmdImage &g0, int32_t count, JpegAmdImage *gy, PlaneSet *py) {
+    const MatrixScratch ms = matrix_scratch(g0.width, g0.height, count, 0);
+    if (int32_t rc = color_batch_alloc(e, ms.total, 0)) return rc;
+    *gy = g0;
+    *py = PlaneSet{};
+    gy->pixels = e->color.bplanes; gy->row_stride = ms.ypitch;
+    for (int i = 0; i < count; ++i) py->p[0][i] = e->color.bplanes + (size_t)i * ms.yplane_bytes;
+    return JPEGAMD_OK;
+}
+
+// `count` float pictures in three scans (SUBSAMPLE_444 / _420 / _422), or -- subsampling 0 -- as the fused grayscale file of their
+// luma or of their single channel: the files jpegamd_encode_planar_batch_async writes for the bytes of the samples.
+extern "C" int32_t jpegamd_encode_float_batch_async(JpegAmdEncoder *e, const JpegAmdFloatImage *imgs, int32_t count, int32_t subsampling,
+                                                    int32_t sample_type, float scale, float offset, void *const *outs_dev,
+                                                    uint64_t out_capacity, void *const *out_sizes_dev, void *stream_) {
+    // the arguments first: nothing of the context is read before they are known to be good
+    JpegAmdImage g0, gy;
+    PlaneSet ps, py;
+    FloatSource fl;
+    uint64_t *sizes[kMaxBatch];
+    if (int32_t rc = float_args(e, imgs, count, subsampling, sample_type, scale, offset, outs_dev, out_sizes_dev, true, &g0, &ps, &fl, sizes))
+        return rc;
+    if (subsampling != 0) return color_batch(e, g0, ps, count, subsampling, outs_dev, out_capacity, sizes, stream_, nullptr, &fl);
+    if (int32_t rc = float_luma_planes(e, g0, count, &gy, &py)) return rc;
+    return gray_batch(e, gy, py, count, outs_dev, out_capacity, sizes, 1, stream_, &fl);
+}
+
+// ... in one scan, with restart intervals and the context's Huffman mode; subsampling 0 goes where jpegamd_encode_gray_scan_batch_async
+// goes: the plain file is the fused entry's.
+extern "C" int32_t jpegamd_encode_float_interleaved_batch_async(JpegAmdEncoder *e, const JpegAmdFloatImage *imgs, int32_t count,
+                                                                int32_t subsampling, int32_t sample_type, float scale, float offset,
+                                                                int32_t restart_interval, void *const *outs_dev, uint64_t out_capacity,
+                                                                void *const *out_sizes_dev, void *stream_) {
+    // the arguments first: nothing of the context is read before they are known to be good
+    if (!restart_valid(restart_interval)) return JPEGAMD_ERR_ARG;
+    JpegAmdImage g0, gy;
+    PlaneSet ps, py;
+    FloatSource fl;
+    uint64_t *sizes[kMaxBatch];
+    if (int32_t rc = float_args(e, imgs, count, subsampling, sample_type, scale, offset, outs_dev, out_sizes_dev, true, &g0, &ps, &fl, sizes))
+        return rc;
+    if (subsampling == 0 && restart_interval == 0 && e->huffman == JPEGAMD_HUFFMAN_STANDARD) {
+        if (int32_t rc = float_luma_planes(e, g0, count, &gy, &py)) return rc;
+        return gray_batch(e, gy, py, count, outs_dev, out_capacity, sizes, 1, stream_, &fl);
+    }
+    return interleaved_batch(e, g0, ps, count, subsampling == 0 ? kSubNone : subsampling, restart_interval, outs_dev, out_capacity, sizes, stream_,
+                             nullptr, kProgNone, nullptr, &fl);
+}
+
+// ... as progressive files with a scan script (null: the default one); subsampling 0: the grayscale progressive file.
+extern "C" int32_t jpegamd_encode_float_progressive_script_batch_async(JpegAmdEncoder *e, const JpegAmdFloatImage *imgs, int32_t count,
+                                                                       int32_t subsampling, int32_t sample_type, float scale, float offset,
+                                                                       const JpegAmdScan *scans, int32_t scan_count, void *const *outs_dev,
+                                                                       uint64_t out_capacity, void *const *out_sizes_dev, void *stream_) {
+    ProgScript sc;
+    if (!prog_script_from(scans, scan_count, subsampling == 0 ? 1 : 3, &sc)) return JPEGAMD_ERR_ARG;
+    JpegAmdImage g0;
+    PlaneSet ps;
+    FloatSource fl;
+    uint64_t *sizes[kMaxBatch];
+    if (int32_t rc = float_args(e, imgs, count, subsampling, sample_type, scale, offset, outs_dev, out_sizes_dev, true, &g0, &ps, &fl, sizes))
+        return rc;
+    return interleaved_batch(e, g0, ps, count, subsampling == 0 ? kSubNone : subsampling, 0, outs_dev, out_capacity, sizes, stream_, nullptr,
+                             kProgScript, &sc, &fl);
+}
+
+// Tests: the pass of a float batch alone, into the same scratch, and its planes copied tightly packed into the caller's DEVICE buffers
+// (y_out: count x height x width bytes; cb_out, cr_out: count x ch x cw, not written for subsampling 0 and then free to be null).
+// Returns when the copies are done.  Not part of the public header.
+extern "C" int32_t jpegamd_debug_float_planes(JpegAmdEncoder *e, const JpegAmdFloatImage *imgs, int32_t count, int32_t subsampling,
+                                              int32_t sample_type, float scale, float offset, void *y_out, void *cb_out, void *cr_out,
+                                              void *stream_) {
+    JpegAmdImage g0;
+    PlaneSet ps;
+    FloatSource fl;
+    if (!y_out || (subsampling != 0 && (!cb_out || !cr_out))) return JPEGAMD_ERR_ARG;
+    if (int32_t rc = float_args(e, imgs, count, subsampling, sample_type, scale, offset, nullptr, nullptr, false, &g0, &ps, &fl, nullptr))
+        return rc;
+    const bool gray = subsampling == 0;
+    const ChromaGeom cg = gray ? ChromaGeom{} : chroma_geom(g0.width, g0.height, subsampling);
+    const MatrixScratch ms = matrix_scratch(g0.width, g0.height, count, cg.plane_bytes);
+    if (int32_t rc = color_batch_alloc(e, ms.total, 0)) return rc;
+    hipStream_t stream = (hipStream_t)stream_;
+    const int out = gray ? (fl.channels == 1 ? kFloatOutSingle : kFloatOutLuma) : kFloatOutColor;
+    if (launch_float_pass(e, fl, g0.width, g0.height, count, out, subsampling, cg, ms, stream, nullptr)) return JPEGAMD_ERR_HIP;
+    const uint8_t *base = e->color.bplanes;
+    for (int i = 0; i < count; ++i) {
+        HIP_TRY(hipMemcpy2DAsync((uint8_t *)y_out + (size_t)i * g0.width * g0.height, (size_t)g0.width, base + ms.y_off + (size_t)i * ms.yplane_bytes,
+                                 (size_t)ms.ypitch, (size_t)g0.width, (size_t)g0.height, hipMemcpyDeviceToDevice, stream));
+        for (int k = 0; k < (gray ? 0 : 2); ++k)
+            HIP_TRY(hipMemcpy2DAsync((uint8_t *)(k ? cr_out : cb_out) + (size_t)i * cg.cw * cg.ch, (size_t)cg.cw, base + (size_t)(2 * i + k) * cg.plane_bytes,
+                                     (size_t)cg.pitch, (size_t)cg.cw, (size_t)cg.ch, hipMemcpyDeviceToDevice, stream));
+    }
+    HIP_TRY(hipStreamSynchronize(stream));
+    return JPEGAMD_OK;
 }
 
 // The bound of a file with a caller's script, scan by scan.  A scan is its DHT segments at most (a DC table 33 bytes: 21 + 12

@@ -351,6 +351,29 @@ struct YccMatrixBatchArgs {
     uint8_t *planes, *yplanes;
 };
 int launch_ycbcr_matrix_batch(const YccMatrixBatchArgs &a, void *stream, void *const *ev = nullptr);
+
+// Float pictures (jpegamd_encode_float_batch_async and its twins, jpegamd_float.hip).  k_float_planes_batch reads every f32 / f16 /
+// bf16 sample of the batch once, where it lies, makes the byte of each (jpeg_compression.h: x * scale + offset in two float32
+// roundings, round half to even, clamp, NaN -> 0), applies the header's RGB -> YCbCr map and chroma subsampling to those bytes, and
+// writes the planes exactly where k_ycbcr_matrix_batch writes its own: what codes a BT.709 batch's planes codes these unchanged.
+constexpr int kFloatF32 = 0, kFloatF16 = 1, kFloatBF16 = 2;                 // JPEGAMD_FLOAT_*
+// three planes of packed samples / the three channels of a pixel side by side, read from plane[0] / samples pixel_stride apart
+constexpr int kFloatWalkPlanar = 0, kFloatWalkPacked3 = 1, kFloatWalkGeneric = 2;
+// Y, Cb and Cr planes / the Y plane alone of three channels / the bytes of the single channel as the Y plane
+constexpr int kFloatOutColor = 0, kFloatOutLuma = 1, kFloatOutSingle = 2;
+struct FloatPlanesBatchArgs {
+    const uint8_t *plane[3][kMaxBatch]; // R, G, B of every picture (kFloatOutSingle: plane[0] alone; kFloatWalkPacked3: plane[0] is the
+                                        // lowest of the three pointers)
+    int32_t batch;
+    int32_t width, height, row_stride, pixel_stride;       // strides in bytes, multiples of the sample size
+    int32_t mode, walk, type, out;      // kChromaMode* (kFloatOutColor alone), kFloatWalk*, kFloatF32 / F16 / BF16, kFloatOut*
+    int32_t reversed;                   // kFloatWalkPacked3: the pixel's samples lie B, G, R
+    float scale, offset;
+    int32_t cw, ch, pitch, ypitch;      // (kFloatOutLuma, kFloatOutSingle: cw = width, ch = height; pitch, plane_bytes, planes unused)
+    uint64_t plane_bytes, yplane_bytes; // multiples of 16
+    uint8_t *planes, *yplanes;
+};
+int launch_float_planes_batch(const FloatPlanesBatchArgs &a, void *stream, void *const *ev = nullptr);
 // k_picture_stats: what the tile records of one k_tile_encode launch add up to per picture and scan -- bits (with the first DC
 // symbol of every tile, which the record leaves out), run/size symbols, exact-order fallbacks -- summed into
 // pic[picture][scan][3].  Launch image i is picture i, scan 0 (luma), or plane first_plane + i (chroma).

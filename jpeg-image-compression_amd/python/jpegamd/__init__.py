@@ -56,6 +56,16 @@ class YCbCrImage(C.Structure):
                 ("y_stride", C.c_int32), ("c_stride", C.c_int32), ("chroma_layout", C.c_int32), ("quality", C.c_int32)]
 
 
+FLOAT_F32, FLOAT_F16, FLOAT_BF16 = 0, 1, 2                   # JPEGAMD_FLOAT_*: the sample type of a float picture
+
+
+class FloatImage(C.Structure):
+    """JpegAmdFloatImage: the R, G and B samples of one float picture (device pointers to the first sample of each; plane[1] and
+    plane[2] null: one channel, the luma), strides in bytes."""
+    _fields_ = [("plane", C.c_void_p * 3), ("width", C.c_int32), ("height", C.c_int32), ("row_stride", C.c_int32),
+                ("pixel_stride", C.c_int32), ("quality", C.c_int32)]
+
+
 class Stats(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("jfif_bytes", "entropy_bits", "stuffed_bytes", "exact_fallbacks",
                                           "ns_transform", "ns_entropy", "ns_pack", "ns_total")]
@@ -97,11 +107,11 @@ class Metadata(C.Structure):
 
 
 def _prototypes():
-    """Every entry of libjpegamd.so that the binding calls, written ONCE: name -> (result type, argument types), in three groups.
+    """Every entry of libjpegamd.so that the binding calls, written ONCE: name -> (result type, argument types), in four groups.
     `base`: declared in include/jpeg_compression.h, in every build.  `later`: declared there as well, but a variant build of an
     older round (JPEGAMD_LIB) may lack them.  `hidden`: debug entries that the header deliberately leaves out; a variant build may
-    lack them too."""
-    u64, i32, i64, vp = C.c_uint64, C.c_int32, C.c_int64, C.c_void_p
+    lack them too.  `tests`: debug entries the header leaves out that every build has."""
+    u64, i32, i64, vp, f32 = C.c_uint64, C.c_int32, C.c_int64, C.c_void_p, C.c_float
     vpp, image = C.POINTER(vp), C.POINTER(Image)
 
     def batch(struct, before: int, after: int = 0):
@@ -178,6 +188,11 @@ def _prototypes():
         "jpegamd_build_metadata": (i64, [C.POINTER(Metadata), vp, u64, vp]),
         "jpegamd_encoder_set_metadata": (i32, [vp, C.POINTER(Metadata)]),
         "jpegamd_encoder_metadata_bytes": (i64, [vp]),
+        # float pictures: (context, pictures[], count, subsampling, sample type, scale, offset, ..., outs[], ..)
+        "jpegamd_encode_float_batch_async": (i32, [vp, C.POINTER(FloatImage), i32, i32, i32, f32, f32, vpp, u64, vpp, vp]),
+        "jpegamd_encode_float_interleaved_batch_async": (i32, [vp, C.POINTER(FloatImage), i32, i32, i32, f32, f32, i32, vpp, u64, vpp, vp]),
+        "jpegamd_encode_float_progressive_script_batch_async": (i32, [vp, C.POINTER(FloatImage), i32, i32, i32, f32, f32, vp, i32, vpp, u64,
+                                                                      vpp, vp]),
     }
     later = {
         "jpegamd_encoder_set_pipeline": (i32, [vp, i32]),
@@ -211,7 +226,10 @@ def _prototypes():
         "jpegamd_debug_chroma_groups": (i32, [i32, i32, i32, i32, i32, i32, i32, vp]),
         "jpegamd_debug_ycbcr_sources": (i32, [i32, i32, i32, i32, vp]),
     }
-    return base, later, hidden
+    tests = {
+        "jpegamd_debug_float_planes": (i32, [vp, C.POINTER(FloatImage), i32, i32, i32, f32, f32, vp, vp, vp, vp]),
+    }
+    return base, later, hidden, tests
 
 
 def _load() -> C.CDLL:
@@ -219,15 +237,15 @@ def _load() -> C.CDLL:
         raise ImportError(f"{LIB_PATH} is missing: build it with `make -C {_PKG_ROOT}` "
                           "(or __graft_entry__.build()); there is no fallback implementation")
     lib = C.CDLL(str(LIB_PATH), mode=getattr(os, "RTLD_NOW", 2))
-    for name, (res, args) in {**_BASE, **_LATER, **_HIDDEN}.items():
-        if name not in _BASE and os.environ.get("JPEGAMD_LIB") and not hasattr(lib, name):
+    for name, (res, args) in {**_BASE, **_LATER, **_HIDDEN, **_TESTS}.items():
+        if name not in _BASE and name not in _TESTS and os.environ.get("JPEGAMD_LIB") and not hasattr(lib, name):
             continue                                              # (A/B tooling: a variant build of an older round)
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = res, args
     return lib
 
 
-_BASE, _LATER, _HIDDEN = _prototypes()
+_BASE, _LATER, _HIDDEN, _TESTS = _prototypes()
 EXPORTED = [*_BASE, *_LATER]                                     # what include/jpeg_compression.h declares
 lib = _load()
 
@@ -917,6 +935,9 @@ def encode_tensor_batch(t, quality: int = 0, subsampling: int = SUBSAMPLE_420, l
     `_huffman`: its tables, set on the per-device context for this call and put back to HUFFMAN_STANDARD behind it;
     `_progressive`: jpegamd.progressive's call -- jpegamd.mjpeg's, with the progressive file of every packed layout written instead.)"""
     interleaved = _scan(scan)
+    if _progressive and getattr(getattr(t, "dtype", None), "is_floating_point", False):
+        raise ValueError("the progressive encoder needs a uint8 tensor: float pictures go through "
+                         "jpegamd.progressive_script.encode_float_batch")
     if _progressive and layout == "chw":
         raise ValueError('progressive files take packed pixels: layout "hwc", "rgba" or "bgra", not "chw"')
     if _huffman and not interleaved:
@@ -1240,6 +1261,143 @@ def _encode_yuyv_frames(frames, quality, order, restart_interval, sample_range: 
         **one_scan)
 
 
+FLOAT_LAYOUTS = ("chw", "hwc", "rgba", "bgra", "gray")
+FLOAT_SCALE_MAX = 16777216.0                                     # |scale| of a float call is at most this (include/jpeg_compression.h)
+
+
+def _value_range(value_range):
+    """value_range=(lo, hi) of the float functions -> (scale, offset) of the C entries: float32(255 / (hi - lo)) and
+    float32(-lo * 255 / (hi - lo)), computed in double and rounded once.  (0, 1) -> (255, 0); (-1, 1) -> (127.5, 127.5);
+    (0, 255) -> (1, 0).  hi < lo inverts the picture.  Anything that is no pair of distinct finite numbers, or a range so narrow that
+    |scale| passes FLOAT_SCALE_MAX, is a ValueError."""
+    import math
+    try:
+        lo, hi = value_range
+        lo, hi = float(lo), float(hi)
+    except (TypeError, ValueError):
+        raise ValueError(f"value_range must be a pair of numbers (lo, hi), not {value_range!r}") from None
+    if not (math.isfinite(lo) and math.isfinite(hi)) or lo == hi:
+        raise ValueError(f"value_range must be two distinct finite numbers, not {value_range!r}")
+    scale = 255.0 / (hi - lo)
+    scale32, offset32 = C.c_float(scale).value, C.c_float(-lo * scale + 0.0).value
+    if not (math.isfinite(scale32) and math.isfinite(offset32)) or abs(scale32) > FLOAT_SCALE_MAX:
+        raise ValueError(f"value_range {value_range!r} gives a scale or offset outside what the encoder takes (|scale| <= {FLOAT_SCALE_MAX:.0f})")
+    return scale32, offset32
+
+
+def _float_layout(t, layout, single: bool):
+    """The float pictures of `t` stored as `layout` says -> (count, height, width, row stride, pixel stride -- both in BYTES --,
+    FLOAT_* sample type, channels, picture index -> the (R, G, B) pointers of JpegAmdFloatImage, the channel views).
+    layout: "chw" [N, 3, H, W], "hwc" [N, H, W, 3], "rgba" / "bgra" [N, H, W, 4] (the fourth sample ignored), "gray" [N, H, W] (one
+    channel: the luma itself), or `t` a sequence of three [N, H, W] tensors, the R, G and B planes; `single`: without the N.  Every
+    stride that one row stride and one pixel stride describe is taken as it is -- channels_last, crops, t[::2], strided rows -- and
+    nothing is copied.  Shapes, dtypes and strides only: host tensors pass."""
+    import torch
+    types = {torch.float32: FLOAT_F32, torch.float16: FLOAT_F16, torch.bfloat16: FLOAT_BF16}
+    planes = list(t) if isinstance(t, (tuple, list)) else None
+    if planes is None and (not isinstance(layout, str) or layout not in FLOAT_LAYOUTS):
+        raise ValueError(f"layout must be one of {FLOAT_LAYOUTS}, or the pictures a sequence of three plane tensors, not {layout!r}")
+    if planes is not None and len(planes) != 3:
+        raise ValueError("a sequence of tensors is the R, G and B planes: three of them")
+    tensors = planes if planes is not None else [t]
+    if any(not isinstance(x, torch.Tensor) or x.dtype not in types for x in tensors) or len({x.dtype for x in tensors}) != 1:
+        raise ValueError("the float encoder needs float32, float16 or bfloat16 tensors of one dtype")
+    lead = 0 if single else 1                                  # dimensions in front of a picture
+    if planes is not None:
+        if any(p.dim() != lead + 2 or p.shape != planes[0].shape for p in planes):
+            raise ValueError("the three planes must be [H, W] or [N, H, W] tensors of one shape")
+    elif layout == "gray":
+        if t.dim() != lead + 2:
+            raise ValueError('layout="gray" takes [H, W] or [N, H, W]')
+        planes = [t]
+    elif layout == "chw":
+        if t.dim() != lead + 3 or t.shape[lead] != 3:
+            raise ValueError('layout="chw" takes [3, H, W] or [N, 3, H, W]')
+        planes = [t.select(lead, k) for k in range(3)]
+    else:
+        c = 3 if layout == "hwc" else 4
+        if t.dim() != lead + 3 or t.shape[-1] != c:
+            raise ValueError(f'layout="{layout}" takes [H, W, {c}] or [N, H, W, {c}]')
+        planes = [t.select(lead + 2, k) for k in ((2, 1, 0) if layout == "bgra" else (0, 1, 2))]
+    if single:
+        planes = [p.unsqueeze(0) for p in planes]
+    n, h, w = (int(v) for v in planes[0].shape)
+    if n < 1 or h < 1 or w < 1 or h > 65535 or w > 65535:
+        raise ValueError("the encoder needs at least one picture of 1..65535 pixels each way")
+    size = planes[0].element_size()
+    pixel = {p.stride(2) if w > 1 else 1 for p in planes}
+    if len(pixel) != 1:
+        raise ValueError("the planes of a picture must share one pixel stride")
+    pixel = pixel.pop()
+    if pixel < 1:
+        raise ValueError(f"the samples of a row must lie at a positive stride, not {pixel} (expanded or flipped views are not taken)")
+    rows = {p.stride(1) if h > 1 else pixel * w for p in planes}
+    if len(rows) != 1:
+        raise ValueError("the planes of a picture must share one row stride")
+    row = rows.pop()
+    if row < pixel * w:
+        raise ValueError(f"rows overlap or run backwards (the row stride {row} is less than a row of {pixel * w} samples)")
+    if row * size >= 1 << 31:
+        raise ValueError("a row stride must stay below 2^31 bytes")
+    return n, h, w, row * size, pixel * size, types[planes[0].dtype], len(planes), (lambda i: tuple(p[i].data_ptr() for p in planes)), planes
+
+
+def _encode_float(name: str, t, quality, subsampling, layout, value_range, single: bool, interleaved: bool = False, restart_interval=None,
+                  huffman=None, progressive: bool = False, scans=None) -> list:
+    """What the float functions of jpegamd, jpegamd.mjpeg and jpegamd.progressive_script share: every argument checked on the CPU,
+    then the pictures through the per-device context in calls of at most MAX_BATCH.  One channel (layout="gray") is a grayscale file
+    whatever `subsampling` says."""
+    scale, offset = _value_range(value_range)
+    huff = None if huffman is None else _huffman(huffman)
+    n, h, w, row, pixel, sample_type, channels, ptr, planes = _float_layout(t, layout, single)
+    sub = 0 if channels == 1 else subsampling
+    if sub not in (0, SUBSAMPLE_444, SUBSAMPLE_420, SUBSAMPLE_422):
+        raise ValueError("subsampling must be SUBSAMPLE_444, SUBSAMPLE_420, SUBSAMPLE_422 or 0 (a grayscale file)")
+    ri = _restart(restart_interval, interleaved, w, sub or SUBSAMPLE_444)      # (a grayscale scan: "row" is ceil(W / 8))
+    if progressive:
+        cap = max_jfif_bytes_progressive_script(w, h, sub, scans)
+        if not cap:
+            if scans is not None:
+                validate_scan_script(scans, 1 if sub == 0 else 3)
+            raise ValueError("bad dimensions")
+    elif interleaved:
+        cap = max_jfif_bytes_gray_scan(w, h, ri) if sub == 0 else max_jfif_bytes_interleaved_restart(w, h, sub, ri)
+    else:
+        cap = max_jfif_bytes(w, h) if sub == 0 else max_jfif_bytes_color(w, h, sub)
+    if any(not p.is_cuda or p.device != planes[0].device for p in planes):
+        raise ValueError(f"{name} needs device tensors on one device")
+
+    def queue(enc, b0, k, outs, cap, size_ptrs, stream):
+        imgs = [Encoder.float_image(ptr(b0 + i), w, h, row, pixel, quality) for i in range(k)]
+        if progressive:
+            enc.encode_float_progressive_script_batch_async(imgs, sub, sample_type, scale, offset, scans, outs, cap, size_ptrs, stream)
+        elif interleaved:
+            enc.encode_float_interleaved_batch_async(imgs, sub, sample_type, scale, offset, ri, outs, cap, size_ptrs, stream)
+        else:
+            enc.encode_float_batch_async(imgs, sub, sample_type, scale, offset, outs, cap, size_ptrs, stream)
+
+    return _encode_pictures(planes[0].device, n, h, w, cap, queue, huff)
+
+
+def encode_float_batch(t, quality: int = 0, subsampling: int = SUBSAMPLE_420, layout="chw", value_range=(0.0, 1.0)) -> list:
+    """A float32, float16 or bfloat16 DEVICE tensor of N pictures -> N JFIF files through jpegamd_encode_float_batch_async: one kernel
+    reads every sample once, where it lies, and makes the byte x.float().mul(scale).add(offset).round().clamp(0, 255) of it (NaN -> 0;
+    include/jpeg_compression.h has the definition), with (scale, offset) = (255 / (hi - lo), -lo * scale) of value_range=(lo, hi):
+    (0, 1), (-1, 1), (0, 255).  The files are byte for byte those of encode_tensor_batch for the uint8 tensor of these bytes: no
+    conversion pass of the caller's, no byte tensor.
+    layout: "chw" [N, 3, H, W] (also in torch.channels_last memory), "hwc" [N, H, W, 3], "rgba" / "bgra" [N, H, W, 4], "gray"
+    [N, H, W] -- one channel, the luma itself: a grayscale file --, or `t` a sequence of three [N, H, W] plane tensors.  subsampling 0:
+    the grayscale file of the pictures' luma.  Crops, strided rows and t[::2] are read as they are; what one row stride and one pixel
+    stride cannot describe is a ValueError.  Batches of more than MAX_BATCH pictures go as several calls; the per-device context of
+    encode_tensor is used, with the tables and metadata of a quant_tables / metadata block."""
+    return _encode_float("encode_float_batch", t, quality, subsampling, layout, value_range, False)
+
+
+def encode_float(t, quality: int = 0, subsampling: int = SUBSAMPLE_420, layout="chw", value_range=(0.0, 1.0)) -> bytes:
+    """One float picture -> its file, as encode_float_batch: [3, H, W], [H, W, 3], [H, W, 4], [H, W] or three [H, W] planes."""
+    return _encode_float("encode_float", t, quality, subsampling, layout, value_range, True)[0]
+
+
 def encode_files(in_paths, out_paths, quality: int = 0):
     """File-to-file batch with overlapped I/O and transfers (jpegamd_encode_files) -> (return code, [status per file], BatchStats)."""
     n = len(in_paths)
@@ -1325,7 +1483,52 @@ class _ProgressiveScriptEntries(_ProgressiveEntries):
         self._script_batch("jpegamd_encode_gray_progressive_script_batch_async", Image, imgs, (), scans, out_ptrs, out_cap, size_ptrs, stream)
 
 
-class Encoder(_ProgressiveScriptEntries):
+class _FloatEntries(_ProgressiveScriptEntries):
+    """... and the entries of float pictures: float32 / float16 / bfloat16 samples, each made a byte by
+    x * scale + offset, rounded half to even and clamped, by one kernel in front of the tile encoder."""
+
+    @staticmethod
+    def float_image(planes, width: int, height: int, row_stride: int, pixel_stride: int, quality: int = 0) -> FloatImage:
+        """`planes`: the device pointers of the first R, G and B sample -- (p, 0, 0) or (p,): one channel, the luma -- with rows
+        `row_stride` and the samples of a row `pixel_stride` BYTES apart."""
+        r, g, b = (tuple(planes) + (0, 0))[:3]
+        return FloatImage((C.c_void_p * 3)(r or None, g or None, b or None), width, height, row_stride, pixel_stride, quality)
+
+    def _float_batch(self, name: str, imgs, subsampling: int, sample_type: int, scale: float, offset: float, middle, out_ptrs, out_cap: int,
+                     size_ptrs, stream: int):
+        """A float entry: name(context, pictures[], count, subsampling, sample type, scale, offset, middle..., outs[], out_cap,
+        sizes[], stream)."""
+        n = len(imgs)
+        arr, pointers = (FloatImage * n)(*imgs), C.c_void_p * n
+        rc = getattr(lib, name)(self._h, arr, n, int(subsampling), int(sample_type), C.c_float(scale), C.c_float(offset), *middle,
+                                pointers(*out_ptrs), out_cap, pointers(*size_ptrs), C.c_void_p(stream))
+        if rc:
+            raise JpegAmdError(rc, name)
+
+    def encode_float_batch_async(self, imgs, subsampling: int, sample_type: int, scale: float, offset: float, out_ptrs, out_cap: int,
+                                 size_ptrs, stream: int = 0):
+        """The files of `len(imgs)` float pictures of one geometry (float_image; FLOAT_F32 / FLOAT_F16 / FLOAT_BF16 samples, each made a
+        byte by x * scale + offset, rounded half to even and clamped) in three scans, or for subsampling 0 the grayscale file
+        (jpegamd_encode_float_batch_async); the context, out_cap and the files as for encode_planar_batch_async on those bytes."""
+        self._float_batch("jpegamd_encode_float_batch_async", imgs, subsampling, sample_type, scale, offset, (), out_ptrs, out_cap, size_ptrs, stream)
+
+    def encode_float_interleaved_batch_async(self, imgs, subsampling: int, sample_type: int, scale: float, offset: float, restart_interval: int,
+                                             out_ptrs, out_cap: int, size_ptrs, stream: int = 0):
+        """... in ONE scan, with restart intervals of `restart_interval` MCUs (0: none) and the context's Huffman tables; subsampling
+        0: the grayscale file of encode_gray_scan_batch_async (jpegamd_encode_float_interleaved_batch_async)."""
+        self._float_batch("jpegamd_encode_float_interleaved_batch_async", imgs, subsampling, sample_type, scale, offset, (int(restart_interval),),
+                          out_ptrs, out_cap, size_ptrs, stream)
+
+    def encode_float_progressive_script_batch_async(self, imgs, subsampling: int, sample_type: int, scale: float, offset: float, scans,
+                                                    out_ptrs, out_cap: int, size_ptrs, stream: int = 0):
+        """... as progressive files with the scan script `scans` (None: the default one); subsampling 0: the grayscale progressive
+        file (jpegamd_encode_float_progressive_script_batch_async)."""
+        sc, ns = _scan_array(scans)
+        self._float_batch("jpegamd_encode_float_progressive_script_batch_async", imgs, subsampling, sample_type, scale, offset, (sc, ns),
+                          out_ptrs, out_cap, size_ptrs, stream)
+
+
+class Encoder(_FloatEntries):
     """Level-1 context: device pointers in, device pointers out, stream-ordered."""
 
     def __init__(self, max_width: int, max_height: int):

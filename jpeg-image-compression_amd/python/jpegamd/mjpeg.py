@@ -79,3 +79,19 @@ def encode_gray(t, quality: int = 0, restart_interval=None, huffman: str = "stan
     if not isinstance(t, torch.Tensor) or t.dim() != 2:
         raise ValueError("encode_gray needs a uint8 tensor [H, W]")
     return _j._encode_gray_scan_batch(t.unsqueeze(0), quality, restart_interval, huffman, "encode_gray")[0]
+
+
+def encode_float_batch(t, quality: int = 0, subsampling: int = _j.SUBSAMPLE_420, layout="chw", value_range=(0.0, 1.0),
+                       restart_interval=None, huffman: str = "standard") -> list:
+    """jpegamd.encode_float_batch's float32 / float16 / bfloat16 pictures -> N one-scan files through
+    jpegamd_encode_float_interleaved_batch_async: byte for byte encode_tensor_batch's files of the bytes of the samples.  One channel
+    (layout="gray") or subsampling 0: the grayscale file of encode_gray_batch."""
+    return _j._encode_float("encode_float_batch", t, quality, subsampling, layout, value_range, False, interleaved=True,
+                            restart_interval=restart_interval, huffman=huffman)
+
+
+def encode_float(t, quality: int = 0, subsampling: int = _j.SUBSAMPLE_420, layout="chw", value_range=(0.0, 1.0), restart_interval=None,
+                 huffman: str = "standard") -> bytes:
+    """One float picture -> its one-scan file, as encode_float_batch."""
+    return _j._encode_float("encode_float", t, quality, subsampling, layout, value_range, True, interleaved=True,
+                            restart_interval=restart_interval, huffman=huffman)[0]

@@ -116,3 +116,15 @@ def encode_gray(t, quality: int = 0, scans=None) -> bytes:
     if t.dim() != 2:
         raise ValueError("encode_gray takes [H, W]")
     return encode_gray_batch(t[None], quality, scans)[0]
+
+
+def encode_float_batch(t, quality: int = 0, subsampling: int = _j.SUBSAMPLE_420, layout="chw", value_range=(0.0, 1.0), scans=None) -> list:
+    """jpegamd.encode_float_batch's float32 / float16 / bfloat16 pictures -> N progressive files through
+    jpegamd_encode_float_progressive_script_batch_async: byte for byte encode_tensor_batch's files of the bytes of the samples.  One
+    channel (layout="gray") or subsampling 0: the grayscale progressive file of encode_gray_batch."""
+    return _j._encode_float("encode_float_batch", t, quality, subsampling, layout, value_range, False, progressive=True, scans=scans)
+
+
+def encode_float(t, quality: int = 0, subsampling: int = _j.SUBSAMPLE_420, layout="chw", value_range=(0.0, 1.0), scans=None) -> bytes:
+    """One float picture -> its progressive file, as encode_float_batch."""
+    return _j._encode_float("encode_float", t, quality, subsampling, layout, value_range, True, progressive=True, scans=scans)[0]

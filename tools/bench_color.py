@@ -73,6 +73,12 @@ bound + Encoder.metadata_bytes(), and every line carries "metadata_bytes".  The 
 the metadata taken off, in the same run: "no_metadata_ns_total_median" and "metadata_ratio".  The time of a call includes
 k_metadata_place.
 
+--source float32|float16|bfloat16 (with --batch N, default 8; --layout chw, the default, or hwc; every --scan mode) times FLOAT pictures
+in [0, 1] through the float entries (jpegamd_encode_float_batch_async, _interleaved_, _progressive_script_; --scan gray:
+the luma through the one-scan entry with subsampling 0).  Routes `float`, `convert` (the four torch ops of a caller without the entry,
+then the uint8 entry of the same layout), `uint8` (that entry alone on the bytes) and `copy` (a device copy of as many bytes as the front
+pass moves) alternate in one run, --rounds medians of --steps calls each, timed between events on the stream; one line per route.
+
 --scan gray (with --batch N, default 8) times GRAYSCALE files through jpegamd_encode_gray_scan_batch_async: the luma
 of the same --size pictures, --restart N|row in blocks (`row`: ceil(W / 8)), --huffman standard|optimized; the whole call is timed
 (ns_total).  Without --restart (or with 0) and with the standard tables the entry is jpegamd_encode_batch_async, so that line is the
@@ -146,6 +152,19 @@ def main() -> None:
     dev = torch.device("cuda:0")
     w = h = a.size
     sources = a.source.split(",")
+    if any(s in FLOAT_SOURCES for s in sources):
+        if any(s not in FLOAT_SOURCES for s in sources):
+            sys.exit("--source float32, float16 and bfloat16 do not mix with the byte sources")
+        if a.sample_range != "full" or a.matrix != "bt601" or a.convert or a.narrow or a.mapped or a.repack or a.scans or a.successive:
+            sys.exit("--source float32|float16|bfloat16 takes --size, --batch, --layout chw|hwc, --scan, --subsampling, --restart, --huffman, "
+                     "--rounds, --quality, --kind, --qtables and the metadata options alone")
+        if a.scan in ("separate", "progressive") and (a.restart is not None or a.huffman is not None):
+            sys.exit("--restart and --huffman need --scan interleaved or gray")
+        if a.scan == "gray" and a.subsampling:
+            sys.exit("--scan gray has no --subsampling")
+        for s in sources:
+            run_float(a, jpegamd, torch, dev, s)
+        return
     if any(s not in ("rgb", "i420", "nv12", "i422", "yuyv", "p010", "i010") for s in sources):
         sys.exit("--source takes rgb, i420, nv12, i422, yuyv, p010, i010 or a comma-separated list of them")
     if a.sample_range != "full" and "rgb" in sources:
@@ -811,6 +830,149 @@ def run_layout(a, jpegamd, torch, dev) -> None:
                     "gpixels_per_s": round(w * h / statistics.median(m) / 1000, 2),
                     **({"scan": "interleaved", "restart_interval": restart} if one_scan else {}),
                     **({"huffman": a.huffman} if a.huffman is not None else {})})
+
+
+FLOAT_SOURCES = ("float32", "float16", "bfloat16")
+
+
+def run_float(a, jpegamd, torch, dev, source) -> None:
+    """--source float32|float16|bfloat16: N float pictures in [0, 1] per call, stored as --layout chw (default) or hwc, through the float
+    entries.  Three routes alternate in one run, each call timed as a whole between two events on the stream:
+    `float` the float entry; `convert` what a caller does without it -- x.mul(255).round().clamp(0, 255).to(uint8), then the uint8 entry
+    of the same layout, as one unit --; `uint8` that entry alone on bytes quantised beforehand, the floor the float call approaches
+    from above; and `copy`, a device-to-device copy that moves as many bytes as k_float_planes_batch reads and writes, the yardstick
+    for that kernel's own time in a kernel trace of the same command."""
+    w = h = a.size
+    n = a.batch or 8
+    layout = a.layout or "chw"
+    if layout not in ("chw", "hwc"):
+        sys.exit("--source float32|float16|bfloat16 takes --layout chw or hwc")
+    dtype = getattr(torch, source)
+    sample_type = {"float32": jpegamd.FLOAT_F32, "float16": jpegamd.FLOAT_F16, "bfloat16": jpegamd.FLOAT_BF16}[source]
+    size = 4 if source == "float32" else 2
+    gray = a.scan == "gray"
+    subs = [(0, "gray")] if gray else [s for s in rgb_subsamplings(a, jpegamd)]
+    pics = []
+    for i in range(n):
+        bmp = jpegamd.synth_bmp(w, h, 1 + i, a.kind, 0)
+        img, off = jpegamd.parse_bmp(bmp)
+        rows = torch.frombuffer(bytearray(bmp[off:off + img.row_stride * h]), dtype=torch.uint8).to(dev).view(h, img.row_stride)
+        pics.append(rows[:, :3 * w].reshape(h, w, 3).flip(0).flip(2))       # bottom-up B, G, R -> top-down R, G, B
+        del bmp, rows
+    hwc8 = torch.stack(pics)
+    del pics
+    src8 = hwc8.permute(0, 3, 1, 2).contiguous() if layout == "chw" else hwc8
+    del hwc8
+    src = src8.to(torch.float32).div(255.0).to(dtype)                       # the float pictures
+    q8 = src.mul(255).round().clamp(0, 255).to(torch.uint8)                 # their bytes (bfloat16 does not hold every k / 255)
+    del src8
+    enc = new_encoder(a, jpegamd, w, n * h)
+    if a.huffman == "optimized":
+        enc.set_huffman(jpegamd.HUFFMAN_OPTIMIZED)
+    stream = torch.cuda.current_stream().cuda_stream
+    restart = 0
+    if a.restart is not None:
+        restart = -(-w // (8 if gray else 16)) if a.restart == "row" else int(a.restart)
+    if layout == "chw":
+        images = lambda t, sz: [jpegamd.Encoder.float_image(tuple(t[i, k].data_ptr() for k in range(3)), w, h, sz * w, sz, a.quality) for i in range(n)]
+    else:
+        images = lambda t, sz: [jpegamd.Encoder.float_image(tuple(t[i].data_ptr() + sz * k for k in range(3)), w, h, 3 * sz * w, 3 * sz, a.quality)
+                                for i in range(n)]
+    fimgs = images(src, size)
+    for sub, name in subs:
+        if a.scan == "progressive":
+            cap = jpegamd.max_jfif_bytes_progressive_script(w, h, sub, None)
+        elif gray:
+            cap = max(jpegamd.max_jfif_bytes_gray_scan(w, h, restart), jpegamd.max_jfif_bytes(w, h))
+        elif a.scan == "interleaved":
+            cap = jpegamd.max_jfif_bytes_interleaved_restart(w, h, sub, restart)
+        else:
+            cap = jpegamd.max_jfif_bytes_color(w, h, sub)
+        cap += a.metadata_bytes
+        outs = [torch.empty(cap, dtype=torch.uint8, device=dev) for _ in range(n)]
+        sizes = torch.zeros(n, dtype=torch.int64, device=dev)
+        tail = ([o.data_ptr() for o in outs], cap, [sizes.data_ptr() + 8 * i for i in range(n)], stream)
+
+        def float_call():
+            if a.scan == "progressive":
+                enc.encode_float_progressive_script_batch_async(fimgs, sub, sample_type, 255.0, 0.0, None, *tail)
+            elif a.scan in ("interleaved", "gray"):
+                enc.encode_float_interleaved_batch_async(fimgs, sub, sample_type, 255.0, 0.0, restart, *tail)
+            else:
+                enc.encode_float_batch_async(fimgs, sub, sample_type, 255.0, 0.0, *tail)
+
+        def uint8_entry(t):
+            """The uint8 entry of the same layout and file on the bytes `t`, or None where no entry reads that layout."""
+            if layout == "chw":
+                planar = [jpegamd.Encoder.planar_image(tuple(t[i, k].data_ptr() for k in range(3)), w, h, w, False, a.quality) for i in range(n)]
+                if a.scan == "separate":
+                    return lambda: enc.encode_planar_batch_async(planar, sub, *tail)
+                if a.scan == "interleaved":
+                    return lambda: enc.encode_planar_interleaved_batch_async(planar, sub, restart, *tail)
+                if gray and restart == 0 and a.huffman != "optimized":
+                    return lambda: enc.encode_planar_batch_async(planar, 0, *tail)
+                return None
+            descs = [jpegamd.Encoder.image(t[i].data_ptr(), w, h, 3 * w, False, jpegamd.ORDER_RGB, a.quality) for i in range(n)]
+            if a.scan == "separate":
+                return lambda: enc.encode_color_batch_async(descs, sub, *tail)
+            if a.scan == "interleaved":
+                return lambda: enc.encode_color_interleaved_pixels_batch_async(descs, sub, restart, *tail)
+            if gray:
+                return lambda: enc.encode_gray_scan_batch_async(descs, restart, *tail)
+            return lambda: enc.encode_color_progressive_script_batch_async(descs, sub, None, *tail)
+
+        routes = {"float": float_call}
+        plain = uint8_entry(q8)
+        if plain is not None:
+            routes["uint8"] = plain
+
+            def convert():
+                t = src.mul(255).round().clamp(0, 255).to(torch.uint8)
+                uint8_entry(t)()
+                return t                                                    # (alive until the next call has been queued)
+            routes["convert"] = convert
+        # what the front pass moves: every sample in, the planes out
+        cw, ch = (w if sub == jpegamd.SUBSAMPLE_444 else (w + 1) // 2), ((h + 1) // 2 if sub == jpegamd.SUBSAMPLE_420 else h)
+        pass_bytes = n * (3 * w * h * size + w * h + (2 * cw * ch if sub else 0))
+        half = torch.empty(pass_bytes // 2, dtype=torch.uint8, device=dev)
+        other = torch.empty_like(half)
+        routes["copy"] = lambda: other.copy_(half)
+        medians = {k: [] for k in routes}
+        got = {}
+        for k, call in routes.items():
+            for _ in range(a.warmup):
+                call()
+            wait = torch.cuda.synchronize if k == "copy" else enc.finish    # (a context with nothing queued has nothing to finish)
+            wait()
+            got[k] = sizes.cpu().tolist()
+        for _ in range(a.rounds):
+            for k, call in routes.items():                                  # the routes alternate: one thermal history
+                evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(a.steps)]
+                keep = None
+                for e0, e1 in evs:
+                    e0.record()
+                    keep = call()
+                    e1.record()
+                if k != "copy":
+                    enc.finish()
+                torch.cuda.synchronize()
+                del keep
+                medians[k].append(statistics.median(e0.elapsed_time(e1) for e0, e1 in evs) * 1000.0 / n)
+        for k in routes:
+            m = medians[k]
+            line = {"source": source, "layout": layout, "scan": a.scan, "subsampling": name, "route": k, "width": w, "height": h, "batch": n,
+                    "quality": a.quality, "kind": a.kind, "steps": a.steps, "rounds": a.rounds,
+                    "us_per_picture_medians": [round(v, 1) for v in m], "us_per_picture": round(statistics.median(m), 1),
+                    "spread_us": round(max(m) - min(m), 1)}
+            if k == "copy":
+                line.update(pass_bytes_per_picture=pass_bytes // n, copy_gb_per_s=round(pass_bytes / n / statistics.median(m) / 1000, 1))
+            else:
+                line.update(bytes=got[k], gpixels_per_s=round(w * h / statistics.median(m) / 1000, 2),
+                            ratio_to_float=round(statistics.median(m) / statistics.median(medians["float"]), 3))
+            if a.scan in ("interleaved", "gray"):
+                line.update(restart_interval=restart, huffman=a.huffman or "standard")
+            report(a, line)
+        del outs, half, other
 
 
 if __name__ == "__main__":
