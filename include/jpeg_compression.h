@@ -882,6 +882,65 @@ int32_t jpegamd_encode_float_progressive_script_batch_async(JpegAmdEncoder *enc,
                                                             const JpegAmdScan *scans, int32_t scan_count, void *const *outs_dev,
                                                             uint64_t out_capacity, void *const *out_sizes_dev, void *stream);
 
+/* Reduced pictures: a file SMALLER than the picture it is made from -- a preview beside the full file, the 1/2, 1/4
+ * and 1/8 steps of a pyramid, a contact sheet, a low-bandwidth stream -- with the box filter fused in front of the encoder.  One kernel
+ * (k_reduce_planes_batch) reads every byte of the source once, where it lies, forms the box means, applies the RGB -> YCbCr map and the
+ * chroma subsampling of this header to them and leaves 8-bit Y, Cb and Cr planes of the reduced picture in context scratch, which are
+ * then coded as a float batch's planes are.
+ *
+ * The map, for a factor f in 1 .. JPEGAMD_MAX_REDUCE (the same both ways) and a source of W x H samples per channel:
+ *     ow = ceil(W / f), oh = ceil(H / f)
+ *     box(X, Y) = the source samples x in [f X, min(f X + f, W)), y in [f Y, min(f Y + f, H))
+ *     n = the number of samples in the box   (1 .. f * f: only what lies inside the picture, nothing is replicated)
+ *     S = their sum
+ *     v(X, Y) = (S + (n >> 1)) / n            integer division rounding down; 0 .. 255
+ * applied to R, G and B separately, or to the single channel.  v is a byte.  Behind it, everything is this header's definition for
+ * those bytes: Y = (77 R + 150 G + 29 B) >> 8; Cb and Cr per REDUCED pixel by the two formulas above; 4:2:0 and 4:2:2 samples by
+ * (a + b + c + d + 2) >> 2 and (a + b + 1) >> 1 with the last reduced column / row replicated; the byte of a single-channel picture
+ * is its Y sample.  Every file is BYTE FOR BYTE the file the uint8 entries write for the ow x oh picture of those bytes stored as
+ * packed RGB (or as JPEGAMD_ORDER_GRAY).  f = 1 is the identity map: a uint8 source at any row and pixel stride.  The mean is taken of
+ * the STORED (gamma-encoded) bytes; averaging in linear light is out of scope.
+ *
+ * One description covers every tensor layout, as JpegAmdFloatImage does with one byte per sample.  [3, H, W]: pixel_stride = 1.
+ * [H, W, 3], and a channels-last [N, 3, H, W]: the three pointers one byte apart, pixel_stride = 3.  RGBA: 4.  BGR: swap the pointers.
+ * Crops and strided rows as they come; top-down only.  plane[1] == plane[2] == NULL: ONE channel, the luma itself, for subsampling 0
+ * alone.  width and height are the SOURCE's (1 .. 65535 each, whatever the context was made for).  Refused with JPEGAMD_ERR_ARG before
+ * the context is read: null arrays, elements or plane[0]; exactly one of plane[1] / plane[2] null; a single channel with a colour
+ * subsampling; count outside 1 .. JPEGAMD_MAX_BATCH; factor outside 1 .. JPEGAMD_MAX_REDUCE; an unknown subsampling; pixel_stride
+ * below 1; row_stride < pixel_stride * width (in 64 bits); pictures of different geometry; a bad restart interval or script.  Nothing
+ * outside a row's own pixel_stride * width bytes is read.
+ *
+ *   jpegamd_reduced_size                                   (ow, oh) of a source and a factor; host only; JPEGAMD_ERR_ARG for a width or
+ *                                                          height outside 1 .. 65535, a factor outside the range, a null result
+ *   jpegamd_encode_reduced_batch_async                     three scans for JPEGAMD_SUBSAMPLE_444 / _420 / _422; subsampling 0: the fused
+ *                                                          grayscale file (the luma of three planes, or the single channel)
+ *   jpegamd_encode_reduced_interleaved_batch_async         one scan, restart_interval 0 .. 65535 in MCUs of the REDUCED picture, the
+ *                                                          context's Huffman mode; subsampling 0: the gray scan
+ *   jpegamd_encode_reduced_progressive_script_batch_async  progressive files; scans NULL (scan_count 0): libjpeg's default script;
+ *                                                          subsampling 0: the grayscale progressive file
+ * Context sizing, capacity, status, statistics and profiling are the float entries' rules at the REDUCED geometry: the context holds
+ * count x the reduced picture's block rows, and buffers are sized with the jpegamd_max_jfif_bytes* functions at (ow, oh).  Quantisation
+ * tables and metadata set on the context apply. */
+#define JPEGAMD_MAX_REDUCE 8
+typedef struct JpegAmdStridedImage {
+    const void *plane[3];   /* DEVICE pointers to the first byte of R, G, B; plane[1] == plane[2] == NULL: one channel (luma) */
+    int32_t width, height;  /* of the SOURCE, 1..65535 */
+    int32_t row_stride;     /* bytes between rows, the same for the three planes */
+    int32_t pixel_stride;   /* bytes between horizontally adjacent samples of a plane */
+    int32_t quality;
+} JpegAmdStridedImage;
+int32_t jpegamd_reduced_size(int32_t width, int32_t height, int32_t factor, int32_t *out_width, int32_t *out_height);
+int32_t jpegamd_encode_reduced_batch_async(JpegAmdEncoder *enc, const JpegAmdStridedImage *imgs, int32_t count, int32_t subsampling,
+                                           int32_t factor, void *const *outs_dev, uint64_t out_capacity, void *const *out_sizes_dev,
+                                           void *stream);
+int32_t jpegamd_encode_reduced_interleaved_batch_async(JpegAmdEncoder *enc, const JpegAmdStridedImage *imgs, int32_t count,
+                                                       int32_t subsampling, int32_t factor, int32_t restart_interval, void *const *outs_dev,
+                                                       uint64_t out_capacity, void *const *out_sizes_dev, void *stream);
+int32_t jpegamd_encode_reduced_progressive_script_batch_async(JpegAmdEncoder *enc, const JpegAmdStridedImage *imgs, int32_t count,
+                                                              int32_t subsampling, int32_t factor, const JpegAmdScan *scans,
+                                                              int32_t scan_count, void *const *outs_dev, uint64_t out_capacity,
+                                                              void *const *out_sizes_dev, void *stream);
+
 /* Block until the last enqueued encode on this context finished; optionally fetch stats
  * (stats may be NULL).  Returns JPEGAMD_ERR_HUFF_CAPACITY if the output did not fit. */
 int32_t jpegamd_encoder_finish(JpegAmdEncoder *enc, JpegAmdStats *stats);

@@ -1006,10 +1006,13 @@ static int32_t plan_batch(const JpegAmdEncoder *e, const JpegAmdImage &g0, const
 
 // A batch of float pictures (jpegamd_encode_float_batch_async and its twins): what k_float_planes_batch reads.  The launches behind
 // that pass read the planes it leaves in color.bplanes.
+// `reduce` (jpegamd_encode_reduced_batch_async and its twins): BYTES instead, src_width x src_height of them per channel, which
+// k_reduce_planes_batch averages in reduce x reduce boxes; the geometry of every launch behind the pass is the reduced picture's.
 struct FloatSource {
     const uint8_t *plane[3][kMaxBatch]; // R, G, B; one channel: plane[0] alone
     int32_t channels, type, row_stride, pixel_stride;      // 1 or 3; JPEGAMD_FLOAT_*; bytes
     float scale, offset;
+    int32_t reduce, src_width, src_height;                 // 0: float samples
 };
 static int launch_float_luma_pass(JpegAmdEncoder *e, const FloatSource &fl, const JpegAmdImage &gy, int32_t count, hipStream_t stream,
                                   void *const *ev);
@@ -1382,8 +1385,11 @@ static int launch_matrix_pass(JpegAmdEncoder *e, const JpegAmdImage &g0, const P
 // planes of geometry cg, where a BT.709 batch has them -- or the Y planes alone (m.y_off = 0: kFloatOutLuma of three channels, or
 // kFloatOutSingle).  The host picks the walk from the pointers and strides: three planes of packed samples; the three channels of a
 // pixel side by side in either order; anything else by samples.
+static int launch_reduce_pass(JpegAmdEncoder *e, const FloatSource &fl, int w, int h, int32_t count, int out, int32_t subsampling,
+                              const ChromaGeom &cg, const MatrixScratch &m, hipStream_t stream, void *const *ev);
 static int launch_float_pass(JpegAmdEncoder *e, const FloatSource &fl, int w, int h, int32_t count, int out, int32_t subsampling,
                              const ChromaGeom &cg, const MatrixScratch &m, hipStream_t stream, void *const *ev) {
+    if (fl.reduce) return launch_reduce_pass(e, fl, w, h, count, out, subsampling, cg, m, stream, ev);
     FloatPlanesBatchArgs fa;
     std::memset(&fa, 0, sizeof(fa));
     const int kb = fl.type == JPEGAMD_FLOAT_F32 ? 4 : 2;
@@ -1410,6 +1416,38 @@ static int launch_float_pass(JpegAmdEncoder *e, const FloatSource &fl, int w, in
         fa.cw = w; fa.ch = h;
     }
     return launch_float_planes_batch(fa, stream, ev);
+}
+// k_reduce_planes_batch in its place for a batch of bytes to be reduced (fl.reduce): w x h is the REDUCED picture, `out` and the
+// scratch layout are the float pass's, and the walk is chosen the same way -- with every factor that is not 1, 2, 4 or 8 on the walk
+// that takes bytes one by one.
+static int launch_reduce_pass(JpegAmdEncoder *e, const FloatSource &fl, int w, int h, int32_t count, int out, int32_t subsampling,
+                              const ChromaGeom &cg, const MatrixScratch &m, hipStream_t stream, void *const *ev) {
+    static_assert(kReduceOutColor == kFloatOutColor && kReduceOutLuma == kFloatOutLuma && kReduceOutSingle == kFloatOutSingle, "one `out`");
+    ReducePlanesBatchArgs ra;
+    std::memset(&ra, 0, sizeof(ra));
+    const auto side_by_side = [&](int i) {
+        const uint8_t *r = fl.plane[0][i], *g = fl.plane[1][i], *b = fl.plane[2][i];
+        return (g == r + 1 && b == g + 1) ? 0 : ((g == b + 1 && r == g + 1) ? 1 : -1);
+    };
+    const bool pow2 = fl.reduce == 1 || fl.reduce == 2 || fl.reduce == 4 || fl.reduce == 8;
+    int order = pow2 && fl.channels == 3 && fl.pixel_stride == 3 ? side_by_side(0) : -1;
+    for (int i = 1; i < count && order >= 0; ++i) if (side_by_side(i) != order) order = -1;
+    ra.walk = order >= 0 ? kReduceWalkPacked3 : (pow2 && fl.pixel_stride == 1 ? kReduceWalkPlanar : kReduceWalkGeneric);
+    ra.reversed = order == 1 ? 1 : 0;
+    for (int i = 0; i < count; ++i)
+        for (int k = 0; k < fl.channels; ++k) ra.plane[k][i] = fl.plane[k][i];
+    if (order == 1) for (int i = 0; i < count; ++i) ra.plane[0][i] = fl.plane[2][i];                   // the lowest of the three
+    ra.batch = count;
+    ra.src_width = fl.src_width; ra.src_height = fl.src_height; ra.row_stride = fl.row_stride; ra.pixel_stride = fl.pixel_stride;
+    ra.factor = fl.reduce; ra.width = w; ra.height = h; ra.out = out;
+    ra.ypitch = m.ypitch; ra.yplane_bytes = m.yplane_bytes; ra.yplanes = e->color.bplanes + m.y_off;
+    if (out == kReduceOutColor) {
+        ra.mode = chroma_mode(subsampling);
+        ra.cw = cg.cw; ra.ch = cg.ch; ra.pitch = cg.pitch; ra.plane_bytes = cg.plane_bytes; ra.planes = e->color.bplanes;
+    } else {
+        ra.cw = w; ra.ch = h;
+    }
+    return launch_reduce_planes_batch(ra, stream, ev);
 }
 // ... the Y planes alone, for the grayscale routes: gy describes the scratch planes (matrix_scratch with no chroma in front).
 static int launch_float_luma_pass(JpegAmdEncoder *e, const FloatSource &fl, const JpegAmdImage &gy, int32_t count, hipStream_t stream,
@@ -2871,43 +2909,79 @@ static int32_t float_luma_planes(JpegAmdEncoder *e, const JpegAmdImage &g0, int3
     return JPEGAMD_OK;
 }
 
-// `count` float pictures in three scans (SUBSAMPLE_444 / _420 / _422), or -- subsampling 0 -- as the fused grayscale file of their
-// luma or of their single channel: the files jpegamd_encode_planar_batch_async writes for the bytes of the samples.
-extern "C" int32_t jpegamd_encode_float_batch_async(JpegAmdEncoder *e, const JpegAmdFloatImage *imgs, int32_t count, int32_t subsampling,
-                                                    int32_t sample_type, float scale, float offset, void *const *outs_dev,
-                                                    uint64_t out_capacity, void *const *out_sizes_dev, void *stream_) {
-    // the arguments first: nothing of the context is read before they are known to be good
-    JpegAmdImage g0, gy;
-    PlaneSet ps, py;
-    FloatSource fl;
-    uint64_t *sizes[kMaxBatch];
-    if (int32_t rc = float_args(e, imgs, count, subsampling, sample_type, scale, offset, outs_dev, out_sizes_dev, true, &g0, &ps, &fl, sizes))
-        return rc;
+// What the entries of a front-pass source share once its arguments are good (g0: the geometry of the files as a GRAY picture, fl: what
+// the pass reads).  Three scans (SUBSAMPLE_444 / _420 / _422), or -- subsampling 0 -- the fused grayscale file of the luma or of the
+// single channel: the files jpegamd_encode_planar_batch_async writes for the bytes the pass makes.
+static int32_t front_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, const PlaneSet &ps, const FloatSource &fl, int32_t count,
+                           int32_t subsampling, void *const *outs_dev, uint64_t out_capacity, uint64_t *const *sizes, void *stream_) {
+    JpegAmdImage gy;
+    PlaneSet py;
     if (subsampling != 0) return color_batch(e, g0, ps, count, subsampling, outs_dev, out_capacity, sizes, stream_, nullptr, &fl);
     if (int32_t rc = float_luma_planes(e, g0, count, &gy, &py)) return rc;
     return gray_batch(e, gy, py, count, outs_dev, out_capacity, sizes, 1, stream_, &fl);
 }
-
 // ... in one scan, with restart intervals and the context's Huffman mode; subsampling 0 goes where jpegamd_encode_gray_scan_batch_async
 // goes: the plain file is the fused entry's.
+static int32_t front_interleaved_batch(JpegAmdEncoder *e, const JpegAmdImage &g0, const PlaneSet &ps, const FloatSource &fl, int32_t count,
+                                       int32_t subsampling, int32_t restart_interval, void *const *outs_dev, uint64_t out_capacity,
+                                       uint64_t *const *sizes, void *stream_) {
+    if (subsampling == 0 && restart_interval == 0 && e->huffman == JPEGAMD_HUFFMAN_STANDARD)
+        return front_batch(e, g0, ps, fl, count, 0, outs_dev, out_capacity, sizes, stream_);
+    return interleaved_batch(e, g0, ps, count, subsampling == 0 ? kSubNone : subsampling, restart_interval, outs_dev, out_capacity, sizes, stream_,
+                             nullptr, kProgNone, nullptr, &fl);
+}
+// Tests: the pass alone, into the same scratch, and its planes copied tightly packed into the caller's DEVICE buffers (y_out: count x
+// height x width bytes; cb_out, cr_out: count x ch x cw, not written for subsampling 0 and then free to be null).  Returns when the
+// copies are done.
+static int32_t front_debug_planes(JpegAmdEncoder *e, const JpegAmdImage &g0, const FloatSource &fl, int32_t count, int32_t subsampling,
+                                  void *y_out, void *cb_out, void *cr_out, void *stream_) {
+    const bool gray = subsampling == 0;
+    const ChromaGeom cg = gray ? ChromaGeom{} : chroma_geom(g0.width, g0.height, subsampling);
+    const MatrixScratch ms = matrix_scratch(g0.width, g0.height, count, cg.plane_bytes);
+    if (int32_t rc = color_batch_alloc(e, ms.total, 0)) return rc;
+    hipStream_t stream = (hipStream_t)stream_;
+    const int out = gray ? (fl.channels == 1 ? kFloatOutSingle : kFloatOutLuma) : kFloatOutColor;
+    if (launch_float_pass(e, fl, g0.width, g0.height, count, out, subsampling, cg, ms, stream, nullptr)) return JPEGAMD_ERR_HIP;
+    const uint8_t *base = e->color.bplanes;
+    for (int i = 0; i < count; ++i) {
+        HIP_TRY(hipMemcpy2DAsync((uint8_t *)y_out + (size_t)i * g0.width * g0.height, (size_t)g0.width, base + ms.y_off + (size_t)i * ms.yplane_bytes,
+                                 (size_t)ms.ypitch, (size_t)g0.width, (size_t)g0.height, hipMemcpyDeviceToDevice, stream));
+        for (int k = 0; k < (gray ? 0 : 2); ++k)
+            HIP_TRY(hipMemcpy2DAsync((uint8_t *)(k ? cr_out : cb_out) + (size_t)i * cg.cw * cg.ch, (size_t)cg.cw, base + (size_t)(2 * i + k) * cg.plane_bytes,
+                                     (size_t)cg.pitch, (size_t)cg.cw, (size_t)cg.ch, hipMemcpyDeviceToDevice, stream));
+    }
+    HIP_TRY(hipStreamSynchronize(stream));
+    return JPEGAMD_OK;
+}
+
+// `count` float pictures in three scans, or -- subsampling 0 -- as the fused grayscale file (front_batch).
+extern "C" int32_t jpegamd_encode_float_batch_async(JpegAmdEncoder *e, const JpegAmdFloatImage *imgs, int32_t count, int32_t subsampling,
+                                                    int32_t sample_type, float scale, float offset, void *const *outs_dev,
+                                                    uint64_t out_capacity, void *const *out_sizes_dev, void *stream_) {
+    // the arguments first: nothing of the context is read before they are known to be good
+    JpegAmdImage g0;
+    PlaneSet ps;
+    FloatSource fl;
+    uint64_t *sizes[kMaxBatch];
+    if (int32_t rc = float_args(e, imgs, count, subsampling, sample_type, scale, offset, outs_dev, out_sizes_dev, true, &g0, &ps, &fl, sizes))
+        return rc;
+    return front_batch(e, g0, ps, fl, count, subsampling, outs_dev, out_capacity, sizes, stream_);
+}
+
+// ... in one scan (front_interleaved_batch).
 extern "C" int32_t jpegamd_encode_float_interleaved_batch_async(JpegAmdEncoder *e, const JpegAmdFloatImage *imgs, int32_t count,
                                                                 int32_t subsampling, int32_t sample_type, float scale, float offset,
                                                                 int32_t restart_interval, void *const *outs_dev, uint64_t out_capacity,
                                                                 void *const *out_sizes_dev, void *stream_) {
     // the arguments first: nothing of the context is read before they are known to be good
     if (!restart_valid(restart_interval)) return JPEGAMD_ERR_ARG;
-    JpegAmdImage g0, gy;
-    PlaneSet ps, py;
+    JpegAmdImage g0;
+    PlaneSet ps;
     FloatSource fl;
     uint64_t *sizes[kMaxBatch];
     if (int32_t rc = float_args(e, imgs, count, subsampling, sample_type, scale, offset, outs_dev, out_sizes_dev, true, &g0, &ps, &fl, sizes))
         return rc;
-    if (subsampling == 0 && restart_interval == 0 && e->huffman == JPEGAMD_HUFFMAN_STANDARD) {
-        if (int32_t rc = float_luma_planes(e, g0, count, &gy, &py)) return rc;
-        return gray_batch(e, gy, py, count, outs_dev, out_capacity, sizes, 1, stream_, &fl);
-    }
-    return interleaved_batch(e, g0, ps, count, subsampling == 0 ? kSubNone : subsampling, restart_interval, outs_dev, out_capacity, sizes, stream_,
-                             nullptr, kProgNone, nullptr, &fl);
+    return front_interleaved_batch(e, g0, ps, fl, count, subsampling, restart_interval, outs_dev, out_capacity, sizes, stream_);
 }
 
 // ... as progressive files with a scan script (null: the default one); subsampling 0: the grayscale progressive file.
@@ -2927,9 +3001,7 @@ extern "C" int32_t jpegamd_encode_float_progressive_script_batch_async(JpegAmdEn
                              kProgScript, &sc, &fl);
 }
 
-// Tests: the pass of a float batch alone, into the same scratch, and its planes copied tightly packed into the caller's DEVICE buffers
-// (y_out: count x height x width bytes; cb_out, cr_out: count x ch x cw, not written for subsampling 0 and then free to be null).
-// Returns when the copies are done.  Not part of the public header.
+// Tests: the pass of a float batch alone (front_debug_planes).  Not part of the public header.
 extern "C" int32_t jpegamd_debug_float_planes(JpegAmdEncoder *e, const JpegAmdFloatImage *imgs, int32_t count, int32_t subsampling,
                                               int32_t sample_type, float scale, float offset, void *y_out, void *cb_out, void *cr_out,
                                               void *stream_) {
@@ -2939,22 +3011,119 @@ extern "C" int32_t jpegamd_debug_float_planes(JpegAmdEncoder *e, const JpegAmdFl
     if (!y_out || (subsampling != 0 && (!cb_out || !cr_out))) return JPEGAMD_ERR_ARG;
     if (int32_t rc = float_args(e, imgs, count, subsampling, sample_type, scale, offset, nullptr, nullptr, false, &g0, &ps, &fl, nullptr))
         return rc;
-    const bool gray = subsampling == 0;
-    const ChromaGeom cg = gray ? ChromaGeom{} : chroma_geom(g0.width, g0.height, subsampling);
-    const MatrixScratch ms = matrix_scratch(g0.width, g0.height, count, cg.plane_bytes);
-    if (int32_t rc = color_batch_alloc(e, ms.total, 0)) return rc;
-    hipStream_t stream = (hipStream_t)stream_;
-    const int out = gray ? (fl.channels == 1 ? kFloatOutSingle : kFloatOutLuma) : kFloatOutColor;
-    if (launch_float_pass(e, fl, g0.width, g0.height, count, out, subsampling, cg, ms, stream, nullptr)) return JPEGAMD_ERR_HIP;
-    const uint8_t *base = e->color.bplanes;
+    return front_debug_planes(e, g0, fl, count, subsampling, y_out, cb_out, cr_out, stream_);
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Reduced pictures: uint8 samples at any row and pixel stride, averaged in factor x factor boxes by
+// k_reduce_planes_batch, which leaves the planes of the REDUCED picture in context scratch; behind it every route is a float batch's.
+// ---------------------------------------------------------------------------------------------------------
+extern "C" int32_t jpegamd_reduced_size(int32_t width, int32_t height, int32_t factor, int32_t *out_width, int32_t *out_height) {
+    if (width <= 0 || height <= 0 || width > 65535 || height > 65535 || factor < 1 || factor > JPEGAMD_MAX_REDUCE || !out_width || !out_height)
+        return JPEGAMD_ERR_ARG;
+    *out_width = (width + factor - 1) / factor;
+    *out_height = (height + factor - 1) / factor;
+    return JPEGAMD_OK;
+}
+
+// The arguments of a reduced batch, checked before anything of the context is read, as float_args checks a float batch's -> the
+// REDUCED geometry as a GRAY picture and what the pass reads.
+static int32_t reduced_args(const JpegAmdEncoder *e, const JpegAmdStridedImage *imgs, int32_t count, int32_t subsampling, int32_t factor,
+                            void *const *outs_dev, void *const *out_sizes_dev, bool files, JpegAmdImage *g0, PlaneSet *ps, FloatSource *fl,
+                            uint64_t **sizes) {
+    static_assert(JPEGAMD_MAX_REDUCE == kMaxReduce, "one bound");
+    if (!e || !imgs || (files && (!outs_dev || !out_sizes_dev)) || count < 1 || count > kMaxBatch) return JPEGAMD_ERR_ARG;
+    if (subsampling != 0 && !sub_valid(subsampling)) return JPEGAMD_ERR_ARG;
+    const JpegAmdStridedImage &p0 = imgs[0];
+    int32_t ow, oh;
+    if (jpegamd_reduced_size(p0.width, p0.height, factor, &ow, &oh)) return JPEGAMD_ERR_ARG;
+    if (p0.pixel_stride < 1 || (int64_t)p0.row_stride < (int64_t)p0.pixel_stride * p0.width) return JPEGAMD_ERR_ARG;
+    if (!p0.plane[0] || (p0.plane[1] == nullptr) != (p0.plane[2] == nullptr)) return JPEGAMD_ERR_ARG;
+    const int channels = p0.plane[1] ? 3 : 1;
+    if (channels == 1 && subsampling != 0) return JPEGAMD_ERR_ARG;
+    *ps = PlaneSet{};
+    *fl = FloatSource{};
+    fl->channels = channels; fl->row_stride = p0.row_stride; fl->pixel_stride = p0.pixel_stride;
+    fl->reduce = factor; fl->src_width = p0.width; fl->src_height = p0.height;
     for (int i = 0; i < count; ++i) {
-        HIP_TRY(hipMemcpy2DAsync((uint8_t *)y_out + (size_t)i * g0.width * g0.height, (size_t)g0.width, base + ms.y_off + (size_t)i * ms.yplane_bytes,
-                                 (size_t)ms.ypitch, (size_t)g0.width, (size_t)g0.height, hipMemcpyDeviceToDevice, stream));
-        for (int k = 0; k < (gray ? 0 : 2); ++k)
-            HIP_TRY(hipMemcpy2DAsync((uint8_t *)(k ? cr_out : cb_out) + (size_t)i * cg.cw * cg.ch, (size_t)cg.cw, base + (size_t)(2 * i + k) * cg.plane_bytes,
-                                     (size_t)cg.pitch, (size_t)cg.cw, (size_t)cg.ch, hipMemcpyDeviceToDevice, stream));
+        const JpegAmdStridedImage &g = imgs[i];
+        if (files && (!outs_dev[i] || !out_sizes_dev[i])) return JPEGAMD_ERR_ARG;
+        if (g.width != p0.width || g.height != p0.height || g.row_stride != p0.row_stride || g.pixel_stride != p0.pixel_stride ||
+            g.quality != p0.quality)
+            return JPEGAMD_ERR_ARG;
+        for (int k = 0; k < 3; ++k) {
+            if ((g.plane[k] != nullptr) != (k < channels)) return JPEGAMD_ERR_ARG;
+            fl->plane[k][i] = (const uint8_t *)g.plane[k];
+        }
+        ps->p[0][i] = (const uint8_t *)g.plane[0];
+        if (files) sizes[i] = (uint64_t *)out_sizes_dev[i];
     }
-    HIP_TRY(hipStreamSynchronize(stream));
+    g0->pixels = p0.plane[0];
+    g0->width = ow; g0->height = oh; g0->row_stride = (ow + 3) / 4 * 4; g0->bottom_up = 0;
+    g0->channel_order = JPEGAMD_ORDER_GRAY; g0->quality = p0.quality;
+    return JPEGAMD_OK;
+}
+
+// `count` pictures of bytes, each reduced by `factor` both ways, in three scans, or -- subsampling 0 -- as the fused grayscale file
+// (front_batch): the files the uint8 entries write for the reduced bytes.
+extern "C" int32_t jpegamd_encode_reduced_batch_async(JpegAmdEncoder *e, const JpegAmdStridedImage *imgs, int32_t count, int32_t subsampling,
+                                                      int32_t factor, void *const *outs_dev, uint64_t out_capacity,
+                                                      void *const *out_sizes_dev, void *stream_) {
+    // the arguments first: nothing of the context is read before they are known to be good
+    JpegAmdImage g0;
+    PlaneSet ps;
+    FloatSource fl;
+    uint64_t *sizes[kMaxBatch];
+    if (int32_t rc = reduced_args(e, imgs, count, subsampling, factor, outs_dev, out_sizes_dev, true, &g0, &ps, &fl, sizes)) return rc;
+    return front_batch(e, g0, ps, fl, count, subsampling, outs_dev, out_capacity, sizes, stream_);
+}
+
+// ... in one scan (front_interleaved_batch); restart_interval counts MCUs of the reduced picture.
+extern "C" int32_t jpegamd_encode_reduced_interleaved_batch_async(JpegAmdEncoder *e, const JpegAmdStridedImage *imgs, int32_t count,
+                                                                  int32_t subsampling, int32_t factor, int32_t restart_interval,
+                                                                  void *const *outs_dev, uint64_t out_capacity, void *const *out_sizes_dev,
+                                                                  void *stream_) {
+    // the arguments first: nothing of the context is read before they are known to be good
+    if (!restart_valid(restart_interval)) return JPEGAMD_ERR_ARG;
+    JpegAmdImage g0;
+    PlaneSet ps;
+    FloatSource fl;
+    uint64_t *sizes[kMaxBatch];
+    if (int32_t rc = reduced_args(e, imgs, count, subsampling, factor, outs_dev, out_sizes_dev, true, &g0, &ps, &fl, sizes)) return rc;
+    return front_interleaved_batch(e, g0, ps, fl, count, subsampling, restart_interval, outs_dev, out_capacity, sizes, stream_);
+}
+
+// ... as progressive files with a scan script (null: the default one); subsampling 0: the grayscale progressive file.
+extern "C" int32_t jpegamd_encode_reduced_progressive_script_batch_async(JpegAmdEncoder *e, const JpegAmdStridedImage *imgs, int32_t count,
+                                                                         int32_t subsampling, int32_t factor, const JpegAmdScan *scans,
+                                                                         int32_t scan_count, void *const *outs_dev, uint64_t out_capacity,
+                                                                         void *const *out_sizes_dev, void *stream_) {
+    ProgScript sc;
+    if (!prog_script_from(scans, scan_count, subsampling == 0 ? 1 : 3, &sc)) return JPEGAMD_ERR_ARG;
+    JpegAmdImage g0;
+    PlaneSet ps;
+    FloatSource fl;
+    uint64_t *sizes[kMaxBatch];
+    if (int32_t rc = reduced_args(e, imgs, count, subsampling, factor, outs_dev, out_sizes_dev, true, &g0, &ps, &fl, sizes)) return rc;
+    return interleaved_batch(e, g0, ps, count, subsampling == 0 ? kSubNone : subsampling, 0, outs_dev, out_capacity, sizes, stream_, nullptr,
+                             kProgScript, &sc, &fl);
+}
+
+// Tests: the pass of a reduced batch alone (front_debug_planes; the buffers hold planes of the REDUCED geometry) and the reciprocal the
+// kernel divides by n with.  Not part of the public header.
+extern "C" int32_t jpegamd_debug_reduced_planes(JpegAmdEncoder *e, const JpegAmdStridedImage *imgs, int32_t count, int32_t subsampling,
+                                                int32_t factor, void *y_out, void *cb_out, void *cr_out, void *stream_) {
+    JpegAmdImage g0;
+    PlaneSet ps;
+    FloatSource fl;
+    if (!y_out || (subsampling != 0 && (!cb_out || !cr_out))) return JPEGAMD_ERR_ARG;
+    if (int32_t rc = reduced_args(e, imgs, count, subsampling, factor, nullptr, nullptr, false, &g0, &ps, &fl, nullptr)) return rc;
+    return front_debug_planes(e, g0, fl, count, subsampling, y_out, cb_out, cr_out, stream_);
+}
+extern "C" int32_t jpegamd_debug_reduce_reciprocal(int32_t n, uint32_t *multiplier, int32_t *shift) {
+    if (n < 1 || n > kMaxReduce * kMaxReduce || !multiplier || !shift) return JPEGAMD_ERR_ARG;
+    *multiplier = reduce_recip(n);
+    *shift = kReduceShift;
     return JPEGAMD_OK;
 }
 

@@ -374,6 +374,34 @@ struct FloatPlanesBatchArgs {
     uint8_t *planes, *yplanes;
 };
 int launch_float_planes_batch(const FloatPlanesBatchArgs &a, void *stream, void *const *ev = nullptr);
+
+// Reduced pictures (jpegamd_encode_reduced_batch_async and its twins, jpegamd_reduce.hip).  k_reduce_planes_batch reads every byte of
+// the batch's sources once, where it lies, forms the mean of every factor x factor box (jpeg_compression.h: (S + (n >> 1)) / n over
+// the n samples inside the picture), applies the header's RGB -> YCbCr map and chroma subsampling to those bytes, and writes the planes
+// of the REDUCED picture exactly where k_float_planes_batch writes its own.
+constexpr int kMaxReduce = 8;                                               // JPEGAMD_MAX_REDUCE
+// The division by n = 1 .. kMaxReduce^2 is a multiply by ceil(2^22 / n) and a shift: exact for every numerator up to 255 n + n / 2
+// (the error term x e / (n 2^22), e < n, stays below 1 / n; the product below 2^31).  tests/test_reduce_host.py walks all of them.
+constexpr int kReduceShift = 22;
+constexpr uint32_t reduce_recip(int n) { return (uint32_t)(((1u << kReduceShift) + (uint32_t)n - 1u) / (uint32_t)n); }
+// the walks and outputs of the float pass: three planes of bytes / R G B (or B G R) bytes side by side, read from plane[0] / bytes
+// pixel_stride apart (and every factor that is not 1, 2, 4 or 8)
+constexpr int kReduceWalkPlanar = 0, kReduceWalkPacked3 = 1, kReduceWalkGeneric = 2;
+constexpr int kReduceOutColor = 0, kReduceOutLuma = 1, kReduceOutSingle = 2;
+struct ReducePlanesBatchArgs {
+    const uint8_t *plane[3][kMaxBatch]; // R, G, B of every picture (kReduceOutSingle: plane[0] alone; kReduceWalkPacked3: plane[0] is the
+                                        // lowest of the three pointers)
+    int32_t batch;
+    int32_t src_width, src_height, row_stride, pixel_stride;   // the source: samples, bytes
+    int32_t factor;                     // 1 .. kMaxReduce
+    int32_t width, height;              // the reduced picture: ceil(src_width / factor), ceil(src_height / factor)
+    int32_t mode, walk, out;            // kChromaMode* (kReduceOutColor alone), kReduceWalk*, kReduceOut*
+    int32_t reversed;                   // kReduceWalkPacked3: the pixel's bytes lie B, G, R
+    int32_t cw, ch, pitch, ypitch;      // (kReduceOutLuma, kReduceOutSingle: cw = width, ch = height; pitch, plane_bytes, planes unused)
+    uint64_t plane_bytes, yplane_bytes; // multiples of 16
+    uint8_t *planes, *yplanes;
+};
+int launch_reduce_planes_batch(const ReducePlanesBatchArgs &a, void *stream, void *const *ev = nullptr);
 // k_picture_stats: what the tile records of one k_tile_encode launch add up to per picture and scan -- bits (with the first DC
 // symbol of every tile, which the record leaves out), run/size symbols, exact-order fallbacks -- summed into
 // pic[picture][scan][3].  Launch image i is picture i, scan 0 (luma), or plane first_plane + i (chroma).

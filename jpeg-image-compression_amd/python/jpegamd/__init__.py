@@ -66,6 +66,15 @@ class FloatImage(C.Structure):
                 ("pixel_stride", C.c_int32), ("quality", C.c_int32)]
 
 
+MAX_REDUCE = 8                                               # JPEGAMD_MAX_REDUCE: the largest factor of a reduced picture
+
+
+class StridedImage(C.Structure):
+    """JpegAmdStridedImage: the R, G and B BYTES of one picture to be reduced (device pointers to the first byte of each; plane[1] and
+    plane[2] null: one channel, the luma), width and height of the SOURCE, strides in bytes."""
+    _fields_ = FloatImage._fields_
+
+
 class Stats(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("jfif_bytes", "entropy_bits", "stuffed_bytes", "exact_fallbacks",
                                           "ns_transform", "ns_entropy", "ns_pack", "ns_total")]
@@ -193,6 +202,11 @@ def _prototypes():
         "jpegamd_encode_float_interleaved_batch_async": (i32, [vp, C.POINTER(FloatImage), i32, i32, i32, f32, f32, i32, vpp, u64, vpp, vp]),
         "jpegamd_encode_float_progressive_script_batch_async": (i32, [vp, C.POINTER(FloatImage), i32, i32, i32, f32, f32, vp, i32, vpp, u64,
                                                                       vpp, vp]),
+        # reduced pictures: (context, pictures[], count, subsampling, factor, ..., outs[], out_cap, sizes[], stream)
+        "jpegamd_reduced_size": (i32, [i32, i32, i32, C.POINTER(i32), C.POINTER(i32)]),
+        "jpegamd_encode_reduced_batch_async": (i32, [vp, C.POINTER(StridedImage), i32, i32, i32, vpp, u64, vpp, vp]),
+        "jpegamd_encode_reduced_interleaved_batch_async": (i32, [vp, C.POINTER(StridedImage), i32, i32, i32, i32, vpp, u64, vpp, vp]),
+        "jpegamd_encode_reduced_progressive_script_batch_async": (i32, [vp, C.POINTER(StridedImage), i32, i32, i32, vp, i32, vpp, u64, vpp, vp]),
     }
     later = {
         "jpegamd_encoder_set_pipeline": (i32, [vp, i32]),
@@ -228,6 +242,8 @@ def _prototypes():
     }
     tests = {
         "jpegamd_debug_float_planes": (i32, [vp, C.POINTER(FloatImage), i32, i32, i32, f32, f32, vp, vp, vp, vp]),
+        "jpegamd_debug_reduced_planes": (i32, [vp, C.POINTER(StridedImage), i32, i32, i32, vp, vp, vp, vp]),
+        "jpegamd_debug_reduce_reciprocal": (i32, [i32, C.POINTER(C.c_uint32), C.POINTER(i32)]),
     }
     return base, later, hidden, tests
 
@@ -1285,15 +1301,15 @@ def _value_range(value_range):
     return scale32, offset32
 
 
-def _float_layout(t, layout, single: bool):
-    """The float pictures of `t` stored as `layout` says -> (count, height, width, row stride, pixel stride -- both in BYTES --,
+def _float_layout(t, layout, single: bool, byte: bool = False):
+    """The float pictures (`byte`: the uint8 pictures, sample type 0, of the reduced functions) of `t` stored as `layout` says -> (count, height, width, row stride, pixel stride -- both in BYTES --,
     FLOAT_* sample type, channels, picture index -> the (R, G, B) pointers of JpegAmdFloatImage, the channel views).
     layout: "chw" [N, 3, H, W], "hwc" [N, H, W, 3], "rgba" / "bgra" [N, H, W, 4] (the fourth sample ignored), "gray" [N, H, W] (one
     channel: the luma itself), or `t` a sequence of three [N, H, W] tensors, the R, G and B planes; `single`: without the N.  Every
     stride that one row stride and one pixel stride describe is taken as it is -- channels_last, crops, t[::2], strided rows -- and
     nothing is copied.  Shapes, dtypes and strides only: host tensors pass."""
     import torch
-    types = {torch.float32: FLOAT_F32, torch.float16: FLOAT_F16, torch.bfloat16: FLOAT_BF16}
+    types = {torch.uint8: 0} if byte else {torch.float32: FLOAT_F32, torch.float16: FLOAT_F16, torch.bfloat16: FLOAT_BF16}
     planes = list(t) if isinstance(t, (tuple, list)) else None
     if planes is None and (not isinstance(layout, str) or layout not in FLOAT_LAYOUTS):
         raise ValueError(f"layout must be one of {FLOAT_LAYOUTS}, or the pictures a sequence of three plane tensors, not {layout!r}")
@@ -1301,7 +1317,8 @@ def _float_layout(t, layout, single: bool):
         raise ValueError("a sequence of tensors is the R, G and B planes: three of them")
     tensors = planes if planes is not None else [t]
     if any(not isinstance(x, torch.Tensor) or x.dtype not in types for x in tensors) or len({x.dtype for x in tensors}) != 1:
-        raise ValueError("the float encoder needs float32, float16 or bfloat16 tensors of one dtype")
+        raise ValueError("the reduced encoder needs uint8 tensors" if byte else
+                         "the float encoder needs float32, float16 or bfloat16 tensors of one dtype")
     lead = 0 if single else 1                                  # dimensions in front of a picture
     if planes is not None:
         if any(p.dim() != lead + 2 or p.shape != planes[0].shape for p in planes):
@@ -1396,6 +1413,75 @@ def encode_float_batch(t, quality: int = 0, subsampling: int = SUBSAMPLE_420, la
 def encode_float(t, quality: int = 0, subsampling: int = SUBSAMPLE_420, layout="chw", value_range=(0.0, 1.0)) -> bytes:
     """One float picture -> its file, as encode_float_batch: [3, H, W], [H, W, 3], [H, W, 4], [H, W] or three [H, W] planes."""
     return _encode_float("encode_float", t, quality, subsampling, layout, value_range, True)[0]
+
+
+def reduced_size(width: int, height: int, factor: int) -> tuple:
+    """(ow, oh) = (ceil(width / factor), ceil(height / factor)) of a reduced picture (jpegamd_reduced_size): what the files of the
+    reduced functions measure and what their buffers are sized for.  A ValueError outside 1..65535 and 1..MAX_REDUCE."""
+    ow, oh = C.c_int32(0), C.c_int32(0)
+    try:
+        rc = lib.jpegamd_reduced_size(width, height, factor, C.byref(ow), C.byref(oh))
+    except (C.ArgumentError, TypeError):
+        rc = -1
+    if rc:
+        raise ValueError(f"reduced_size takes a width and height of 1..65535 and a factor of 1..{MAX_REDUCE}, not {(width, height, factor)!r}")
+    return ow.value, oh.value
+
+
+def _encode_reduced(name: str, t, quality, subsampling, factor, layout, single: bool, interleaved: bool = False, restart_interval=None,
+                    huffman=None, progressive: bool = False, scans=None) -> list:
+    """What the reduced functions of jpegamd, jpegamd.mjpeg and jpegamd.progressive_script share, as _encode_float: every argument
+    checked on the CPU, then the pictures through the per-device context -- sized for the REDUCED pictures -- in calls of at most
+    MAX_BATCH.  One channel (layout="gray") is a grayscale file whatever `subsampling` says."""
+    huff = None if huffman is None else _huffman(huffman)
+    if isinstance(factor, bool) or not isinstance(factor, int) or not 1 <= factor <= MAX_REDUCE:
+        raise ValueError(f"factor must be an integer of 1..{MAX_REDUCE}, not {factor!r}")
+    n, h, w, row, pixel, _, channels, ptr, planes = _float_layout(t, layout, single, byte=True)
+    ow, oh = reduced_size(w, h, factor)
+    sub = 0 if channels == 1 else subsampling
+    if sub not in (0, SUBSAMPLE_444, SUBSAMPLE_420, SUBSAMPLE_422):
+        raise ValueError("subsampling must be SUBSAMPLE_444, SUBSAMPLE_420, SUBSAMPLE_422 or 0 (a grayscale file)")
+    ri = _restart(restart_interval, interleaved, ow, sub or SUBSAMPLE_444)     # ("row": an MCU row of the REDUCED picture)
+    if progressive:
+        cap = max_jfif_bytes_progressive_script(ow, oh, sub, scans)
+        if not cap:
+            if scans is not None:
+                validate_scan_script(scans, 1 if sub == 0 else 3)
+            raise ValueError("bad dimensions")
+    elif interleaved:
+        cap = max_jfif_bytes_gray_scan(ow, oh, ri) if sub == 0 else max_jfif_bytes_interleaved_restart(ow, oh, sub, ri)
+    else:
+        cap = max_jfif_bytes(ow, oh) if sub == 0 else max_jfif_bytes_color(ow, oh, sub)
+    if any(not p.is_cuda or p.device != planes[0].device for p in planes):
+        raise ValueError(f"{name} needs device tensors on one device")
+
+    def queue(enc, b0, k, outs, cap, size_ptrs, stream):
+        imgs = [Encoder.strided_image(ptr(b0 + i), w, h, row, pixel, quality) for i in range(k)]
+        if progressive:
+            enc.encode_reduced_progressive_script_batch_async(imgs, sub, factor, scans, outs, cap, size_ptrs, stream)
+        elif interleaved:
+            enc.encode_reduced_interleaved_batch_async(imgs, sub, factor, ri, outs, cap, size_ptrs, stream)
+        else:
+            enc.encode_reduced_batch_async(imgs, sub, factor, outs, cap, size_ptrs, stream)
+
+    return _encode_pictures(planes[0].device, n, oh, ow, cap, queue, huff)
+
+
+def encode_reduced_batch(t, quality: int = 0, subsampling: int = SUBSAMPLE_420, factor: int = 2, layout="chw") -> list:
+    """A uint8 DEVICE tensor of N pictures -> N JFIF files of ceil(W / factor) x ceil(H / factor) pixels through
+    jpegamd_encode_reduced_batch_async: one kernel reads every byte once, where it lies, and makes every reduced sample the rounded mean
+    (S + (n >> 1)) // n of its factor x factor box -- of what of the box lies inside the picture; include/jpeg_compression.h has the
+    definition.  The files are byte for byte those of encode_tensor_batch for the uint8 tensor of those means: no resize of the
+    caller's, no float copy, no reduced tensor.  The mean is of the stored (gamma-encoded) bytes.
+    factor: 1..MAX_REDUCE; 1 reduces nothing and encodes a uint8 tensor at any row and pixel stride.  layout, the three-plane form,
+    subsampling 0, crops, strided rows, t[::2] and channels_last memory as for encode_float_batch; the per-device context of
+    encode_tensor is used, with the tables and metadata of a quant_tables / metadata block."""
+    return _encode_reduced("encode_reduced_batch", t, quality, subsampling, factor, layout, False)
+
+
+def encode_reduced(t, quality: int = 0, subsampling: int = SUBSAMPLE_420, factor: int = 2, layout="chw") -> bytes:
+    """One picture of bytes -> its reduced file, as encode_reduced_batch: [3, H, W], [H, W, 3], [H, W, 4], [H, W] or three [H, W] planes."""
+    return _encode_reduced("encode_reduced", t, quality, subsampling, factor, layout, True)[0]
 
 
 def encode_files(in_paths, out_paths, quality: int = 0):
@@ -1528,7 +1614,49 @@ class _FloatEntries(_ProgressiveScriptEntries):
                           out_ptrs, out_cap, size_ptrs, stream)
 
 
-class Encoder(_FloatEntries):
+class _ReducedEntries(_FloatEntries):
+    """... and the entries of reduced pictures: bytes at any row and pixel stride, averaged in factor x factor
+    boxes by one kernel in front of the tile encoder; the files measure reduced_size(width, height, factor)."""
+
+    @staticmethod
+    def strided_image(planes, width: int, height: int, row_stride: int, pixel_stride: int, quality: int = 0) -> StridedImage:
+        """`planes`: the device pointers of the first R, G and B byte -- (p, 0, 0) or (p,): one channel, the luma -- of a SOURCE of
+        width x height pixels with rows `row_stride` and the bytes of a row `pixel_stride` bytes apart."""
+        r, g, b = (tuple(planes) + (0, 0))[:3]
+        return StridedImage((C.c_void_p * 3)(r or None, g or None, b or None), width, height, row_stride, pixel_stride, quality)
+
+    def _reduced_batch(self, name: str, imgs, subsampling: int, factor: int, middle, out_ptrs, out_cap: int, size_ptrs, stream: int):
+        """A reduced entry: name(context, pictures[], count, subsampling, factor, middle..., outs[], out_cap, sizes[], stream)."""
+        n = len(imgs)
+        arr, pointers = (StridedImage * n)(*imgs), C.c_void_p * n
+        rc = getattr(lib, name)(self._h, arr, n, int(subsampling), int(factor), *middle, pointers(*out_ptrs), out_cap, pointers(*size_ptrs),
+                                C.c_void_p(stream))
+        if rc:
+            raise JpegAmdError(rc, name)
+
+    def encode_reduced_batch_async(self, imgs, subsampling: int, factor: int, out_ptrs, out_cap: int, size_ptrs, stream: int = 0):
+        """The files of `len(imgs)` pictures of bytes of one geometry (strided_image), each reduced by `factor` both ways, in three
+        scans, or for subsampling 0 the grayscale file (jpegamd_encode_reduced_batch_async); the context, out_cap and the files as for
+        encode_planar_batch_async on the reduced bytes."""
+        self._reduced_batch("jpegamd_encode_reduced_batch_async", imgs, subsampling, factor, (), out_ptrs, out_cap, size_ptrs, stream)
+
+    def encode_reduced_interleaved_batch_async(self, imgs, subsampling: int, factor: int, restart_interval: int, out_ptrs, out_cap: int,
+                                               size_ptrs, stream: int = 0):
+        """... in ONE scan, with restart intervals of `restart_interval` MCUs of the reduced picture (0: none) and the context's Huffman
+        tables; subsampling 0: the grayscale file of encode_gray_scan_batch_async (jpegamd_encode_reduced_interleaved_batch_async)."""
+        self._reduced_batch("jpegamd_encode_reduced_interleaved_batch_async", imgs, subsampling, factor, (int(restart_interval),), out_ptrs,
+                            out_cap, size_ptrs, stream)
+
+    def encode_reduced_progressive_script_batch_async(self, imgs, subsampling: int, factor: int, scans, out_ptrs, out_cap: int, size_ptrs,
+                                                      stream: int = 0):
+        """... as progressive files with the scan script `scans` (None: the default one); subsampling 0: the grayscale progressive
+        file (jpegamd_encode_reduced_progressive_script_batch_async)."""
+        sc, ns = _scan_array(scans)
+        self._reduced_batch("jpegamd_encode_reduced_progressive_script_batch_async", imgs, subsampling, factor, (sc, ns), out_ptrs, out_cap,
+                            size_ptrs, stream)
+
+
+class Encoder(_ReducedEntries):
     """Level-1 context: device pointers in, device pointers out, stream-ordered."""
 
     def __init__(self, max_width: int, max_height: int):

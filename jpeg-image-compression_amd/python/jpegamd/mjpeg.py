@@ -95,3 +95,20 @@ def encode_float(t, quality: int = 0, subsampling: int = _j.SUBSAMPLE_420, layou
     """One float picture -> its one-scan file, as encode_float_batch."""
     return _j._encode_float("encode_float", t, quality, subsampling, layout, value_range, True, interleaved=True,
                             restart_interval=restart_interval, huffman=huffman)[0]
+
+
+def encode_reduced_batch(t, quality: int = 0, subsampling: int = _j.SUBSAMPLE_420, factor: int = 2, layout="chw", restart_interval=None,
+                         huffman: str = "standard") -> list:
+    """jpegamd.encode_reduced_batch's uint8 pictures, each reduced by `factor` both ways -> N one-scan files through
+    jpegamd_encode_reduced_interleaved_batch_async: byte for byte encode_tensor_batch's files of the reduced bytes.  restart_interval
+    counts MCUs of the REDUCED picture ("row": one of its MCU rows).  One channel (layout="gray") or subsampling 0: the grayscale file
+    of encode_gray_batch."""
+    return _j._encode_reduced("encode_reduced_batch", t, quality, subsampling, factor, layout, False, interleaved=True,
+                              restart_interval=restart_interval, huffman=huffman)
+
+
+def encode_reduced(t, quality: int = 0, subsampling: int = _j.SUBSAMPLE_420, factor: int = 2, layout="chw", restart_interval=None,
+                   huffman: str = "standard") -> bytes:
+    """One picture of bytes -> its reduced one-scan file, as encode_reduced_batch."""
+    return _j._encode_reduced("encode_reduced", t, quality, subsampling, factor, layout, True, interleaved=True,
+                              restart_interval=restart_interval, huffman=huffman)[0]

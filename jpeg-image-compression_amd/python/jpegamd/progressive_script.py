@@ -128,3 +128,15 @@ def encode_float_batch(t, quality: int = 0, subsampling: int = _j.SUBSAMPLE_420,
 def encode_float(t, quality: int = 0, subsampling: int = _j.SUBSAMPLE_420, layout="chw", value_range=(0.0, 1.0), scans=None) -> bytes:
     """One float picture -> its progressive file, as encode_float_batch."""
     return _j._encode_float("encode_float", t, quality, subsampling, layout, value_range, True, progressive=True, scans=scans)[0]
+
+
+def encode_reduced_batch(t, quality: int = 0, subsampling: int = _j.SUBSAMPLE_420, factor: int = 2, layout="chw", scans=None) -> list:
+    """jpegamd.encode_reduced_batch's uint8 pictures, each reduced by `factor` both ways -> N progressive files through
+    jpegamd_encode_reduced_progressive_script_batch_async: byte for byte encode_tensor_batch's files of the reduced bytes.  One channel
+    (layout="gray") or subsampling 0: the grayscale progressive file of encode_gray_batch."""
+    return _j._encode_reduced("encode_reduced_batch", t, quality, subsampling, factor, layout, False, progressive=True, scans=scans)
+
+
+def encode_reduced(t, quality: int = 0, subsampling: int = _j.SUBSAMPLE_420, factor: int = 2, layout="chw", scans=None) -> bytes:
+    """One picture of bytes -> its reduced progressive file, as encode_reduced_batch."""
+    return _j._encode_reduced("encode_reduced", t, quality, subsampling, factor, layout, True, progressive=True, scans=scans)[0]

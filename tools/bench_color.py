@@ -79,6 +79,14 @@ the luma through the one-scan entry with subsampling 0).  Routes `float`, `conve
 then the uint8 entry of the same layout), `uint8` (that entry alone on the bytes) and `copy` (a device copy of as many bytes as the front
 pass moves) alternate in one run, --rounds medians of --steps calls each, timed between events on the stream; one line per route.
 
+--reduce F (1 .. 8; with --batch N, default 8; --layout chw, the default, or hwc; every --scan mode) times uint8 pictures of --size pixels
+each way encoded REDUCED by F both ways through the reduced entries (jpegamd_encode_reduced_batch_async, _interleaved_,
+_progressive_script_; --scan gray: the luma through the one-scan entry with subsampling 0).  Routes `reduced`, `resize` (what a caller
+does without the entry: a float copy, avg_pool2d with ceil_mode and divisor_override=1, the division by the box counts, +0.5, floor,
+clamp, the cast and the planar uint8 entry, as one unit), `uint8` (the uint8 entry of the same layout alone on bytes reduced beforehand:
+the floor) and `copy` (a device copy of as many bytes as the source holds) alternate in one run, --rounds medians of --steps calls
+each, timed between events on the stream; one line per route.
+
 --scan gray (with --batch N, default 8) times GRAYSCALE files through jpegamd_encode_gray_scan_batch_async: the luma
 of the same --size pictures, --restart N|row in blocks (`row`: ceil(W / 8)), --huffman standard|optimized; the whole call is timed
 (ns_total).  Without --restart (or with 0) and with the standard tables the entry is jpegamd_encode_batch_async, so that line is the
@@ -138,6 +146,8 @@ def main() -> None:
     ap.add_argument("--icc", type=int, default=None, metavar="BYTES", help="every --scan mode: a synthetic ICC profile of this length in every file")
     ap.add_argument("--comment", default=None, metavar="TEXT", help="every --scan mode: a comment in every file")
     ap.add_argument("--dpi", type=int, default=None, metavar="N", help="every --scan mode: this pixel density in every file")
+    ap.add_argument("--reduce", type=int, default=None, metavar="F",
+                    help="every --scan mode: uint8 pictures encoded reduced by F (1 .. 8) both ways through the reduced entries (DESIGN.md 4.6.19)")
     a = ap.parse_args()
     if a.scans is not None and (a.scan != "progressive" or a.successive or a.huffman is not None or a.source != "rgb"):
         sys.exit("--scans needs --scan progressive and takes --size, --batch, --subsampling, --quality, --kind alone")
@@ -152,6 +162,18 @@ def main() -> None:
     dev = torch.device("cuda:0")
     w = h = a.size
     sources = a.source.split(",")
+    if a.reduce is not None:
+        if not 1 <= a.reduce <= jpegamd.MAX_REDUCE:
+            sys.exit(f"--reduce takes 1 .. {jpegamd.MAX_REDUCE}")
+        if a.source != "rgb" or a.sample_range != "full" or a.matrix != "bt601" or a.convert or a.narrow or a.mapped or a.repack or a.scans or a.successive:
+            sys.exit("--reduce takes --size, --batch, --layout chw|hwc, --scan, --subsampling, --restart, --huffman, --rounds, --quality, --kind, "
+                     "--qtables and the metadata options alone")
+        if a.scan in ("separate", "progressive") and (a.restart is not None or a.huffman is not None):
+            sys.exit("--restart and --huffman need --scan interleaved or gray")
+        if a.scan == "gray" and a.subsampling:
+            sys.exit("--scan gray has no --subsampling")
+        run_reduce(a, jpegamd, torch, dev)
+        return
     if any(s in FLOAT_SOURCES for s in sources):
         if any(s not in FLOAT_SOURCES for s in sources):
             sys.exit("--source float32, float16 and bfloat16 do not mix with the byte sources")
@@ -973,6 +995,149 @@ def run_float(a, jpegamd, torch, dev, source) -> None:
                 line.update(restart_interval=restart, huffman=a.huffman or "standard")
             report(a, line)
         del outs, half, other
+
+
+def run_reduce(a, jpegamd, torch, dev) -> None:
+    """--reduce F: N uint8 pictures per call, stored as --layout chw (default) or hwc, each encoded reduced by F both ways through the
+    reduced entries.  Four routes alternate in one run, each call timed as a whole between two events on the stream:
+    `reduced` the reduced entry; `resize` what a caller does without it -- a float copy, avg_pool2d(ceil_mode=True, divisor_override=1),
+    the division by the box counts, + 0.5, floor, clamp and the cast, then the planar uint8 entry, as one unit --; `uint8` the uint8 entry
+    of the same layout alone on bytes reduced beforehand, the floor the reduced call approaches from above; and `copy`, a device-to-device
+    copy of as many bytes as the source holds, the yardstick for k_reduce_planes_batch's own time in a kernel trace of the same command."""
+    import torch.nn.functional as F
+    w = h = a.size
+    f = a.reduce
+    ow, oh = jpegamd.reduced_size(w, h, f)
+    n = a.batch or 8
+    layout = a.layout or "chw"
+    if layout not in ("chw", "hwc"):
+        sys.exit("--reduce takes --layout chw or hwc")
+    gray = a.scan == "gray"
+    subs = [(0, "gray")] if gray else [s for s in rgb_subsamplings(a, jpegamd)]
+    pics = []
+    for i in range(n):
+        bmp = jpegamd.synth_bmp(w, h, 1 + i, a.kind, 0)
+        img, off = jpegamd.parse_bmp(bmp)
+        rows = torch.frombuffer(bytearray(bmp[off:off + img.row_stride * h]), dtype=torch.uint8).to(dev).view(h, img.row_stride)
+        pics.append(rows[:, :3 * w].reshape(h, w, 3).flip(0).flip(2))       # bottom-up B, G, R -> top-down R, G, B
+        del bmp, rows
+    hwc8 = torch.stack(pics)
+    del pics
+    src = hwc8.permute(0, 3, 1, 2).contiguous() if layout == "chw" else hwc8
+    del hwc8
+    # the box counts of the map, and the caller's route with them
+    nx = torch.clamp(w - f * torch.arange(ow, device=dev), max=f)
+    ny = torch.clamp(h - f * torch.arange(oh, device=dev), max=f)
+    inv = 1.0 / (ny[:, None] * nx[None, :]).to(torch.float32)
+
+    def resized():
+        x = (src if layout == "chw" else src.permute(0, 3, 1, 2)).to(torch.float32, memory_format=torch.contiguous_format)
+        return F.avg_pool2d(x, f, ceil_mode=True, divisor_override=1).mul(inv).add(0.5).floor().clamp(0, 255).to(torch.uint8)
+
+    small_chw = resized()                                                  # [N, 3, oh, ow]
+    small = small_chw if layout == "chw" else small_chw.permute(0, 2, 3, 1).contiguous()
+    enc = new_encoder(a, jpegamd, ow, n * ((oh + 7) // 8 * 8))
+    if a.huffman == "optimized":
+        enc.set_huffman(jpegamd.HUFFMAN_OPTIMIZED)
+    stream = torch.cuda.current_stream().cuda_stream
+    restart = 0
+    if a.restart is not None:
+        restart = -(-ow // (8 if gray else 16)) if a.restart == "row" else int(a.restart)
+    if layout == "chw":
+        rimgs = [jpegamd.Encoder.strided_image(tuple(src[i, k].data_ptr() for k in range(3)), w, h, w, 1, a.quality) for i in range(n)]
+    else:
+        rimgs = [jpegamd.Encoder.strided_image(tuple(src[i].data_ptr() + k for k in range(3)), w, h, 3 * w, 3, a.quality) for i in range(n)]
+    for sub, name in subs:
+        if a.scan == "progressive":
+            cap = jpegamd.max_jfif_bytes_progressive_script(ow, oh, sub, None)
+        elif gray:
+            cap = max(jpegamd.max_jfif_bytes_gray_scan(ow, oh, restart), jpegamd.max_jfif_bytes(ow, oh))
+        elif a.scan == "interleaved":
+            cap = jpegamd.max_jfif_bytes_interleaved_restart(ow, oh, sub, restart)
+        else:
+            cap = jpegamd.max_jfif_bytes_color(ow, oh, sub)
+        cap += a.metadata_bytes
+        outs = [torch.empty(cap, dtype=torch.uint8, device=dev) for _ in range(n)]
+        sizes = torch.zeros(n, dtype=torch.int64, device=dev)
+        tail = ([o.data_ptr() for o in outs], cap, [sizes.data_ptr() + 8 * i for i in range(n)], stream)
+
+        def reduced_call():
+            if a.scan == "progressive":
+                enc.encode_reduced_progressive_script_batch_async(rimgs, sub, f, None, *tail)
+            elif a.scan in ("interleaved", "gray"):
+                enc.encode_reduced_interleaved_batch_async(rimgs, sub, f, restart, *tail)
+            else:
+                enc.encode_reduced_batch_async(rimgs, sub, f, *tail)
+
+        def uint8_entry(t, lay):
+            """The uint8 entry of the same file on the reduced bytes `t` stored as `lay`, or None where no entry reads that layout."""
+            if lay == "chw":
+                planar = [jpegamd.Encoder.planar_image(tuple(t[i, k].data_ptr() for k in range(3)), ow, oh, ow, False, a.quality) for i in range(n)]
+                if a.scan == "separate":
+                    return lambda: enc.encode_planar_batch_async(planar, sub, *tail)
+                if a.scan == "interleaved":
+                    return lambda: enc.encode_planar_interleaved_batch_async(planar, sub, restart, *tail)
+                if gray and restart == 0 and a.huffman != "optimized":
+                    return lambda: enc.encode_planar_batch_async(planar, 0, *tail)
+                return None
+            descs = [jpegamd.Encoder.image(t[i].data_ptr(), ow, oh, 3 * ow, False, jpegamd.ORDER_RGB, a.quality) for i in range(n)]
+            if a.scan == "separate":
+                return lambda: enc.encode_color_batch_async(descs, sub, *tail)
+            if a.scan == "interleaved":
+                return lambda: enc.encode_color_interleaved_pixels_batch_async(descs, sub, restart, *tail)
+            if gray:
+                return lambda: enc.encode_gray_scan_batch_async(descs, restart, *tail)
+            return lambda: enc.encode_color_progressive_script_batch_async(descs, sub, None, *tail)
+
+        routes = {"reduced": reduced_call}
+        plain = uint8_entry(small, layout)
+        if plain is not None:
+            routes["uint8"] = plain
+        if uint8_entry(small_chw, "chw") is not None:
+            def resize():
+                t = resized()
+                uint8_entry(t, "chw")()
+                return t                                                    # (alive until the next call has been queued)
+            routes["resize"] = resize
+        other = torch.empty_like(src)
+        routes["copy"] = lambda: other.copy_(src)
+        medians = {k: [] for k in routes}
+        got = {}
+        for k, call in routes.items():
+            for _ in range(a.warmup):
+                call()
+            wait = torch.cuda.synchronize if k == "copy" else enc.finish    # (a context with nothing queued has nothing to finish)
+            wait()
+            got[k] = sizes.cpu().tolist()
+        for _ in range(a.rounds):
+            for k, call in routes.items():                                  # the routes alternate: one thermal history
+                evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(a.steps)]
+                keep = None
+                for e0, e1 in evs:
+                    e0.record()
+                    keep = call()
+                    e1.record()
+                if k != "copy":
+                    enc.finish()
+                torch.cuda.synchronize()
+                del keep
+                medians[k].append(statistics.median(e0.elapsed_time(e1) for e0, e1 in evs) * 1000.0 / n)
+        for k in routes:
+            m = medians[k]
+            line = {"source": "uint8", "reduce": f, "layout": layout, "scan": a.scan, "subsampling": name, "route": k, "width": w, "height": h,
+                    "reduced_width": ow, "reduced_height": oh, "batch": n, "quality": a.quality, "kind": a.kind, "steps": a.steps,
+                    "rounds": a.rounds, "us_per_picture_medians": [round(v, 1) for v in m], "us_per_picture": round(statistics.median(m), 1),
+                    "spread_us": round(max(m) - min(m), 1)}
+            if k == "copy":
+                line.update(source_bytes_per_picture=src.numel() // n, copy_gb_per_s=round(2 * src.numel() / n / statistics.median(m) / 1000, 1))
+            else:
+                line.update(bytes=got[k], source_gpixels_per_s=round(w * h / statistics.median(m) / 1000, 2),
+                            ratio_to_reduced=round(statistics.median(m) / statistics.median(medians["reduced"]), 3),
+                            same_sizes_as_reduced=got[k] == got["reduced"])     # (torch divides in float32: exact where n is a power of 2)
+            if a.scan in ("interleaved", "gray"):
+                line.update(restart_interval=restart, huffman=a.huffman or "standard")
+            report(a, line)
+        del outs, other
 
 
 if __name__ == "__main__":
