@@ -941,6 +941,61 @@ int32_t jpegamd_encode_reduced_progressive_script_batch_async(JpegAmdEncoder *en
                                                               int32_t scan_count, void *const *outs_dev, uint64_t out_capacity,
                                                               void *const *out_sizes_dev, void *stream);
 
+/* Resized pictures: a file of ANY smaller size -- "320 wide", "fit inside 1024 x 1024", 1920 x 1080 from a
+ * 4096 x 2304 frame, a contact-sheet cell -- with exact area resampling fused in front of the encoder.  One kernel
+ * (k_resize_planes_batch) reads the source where it lies, weights every source sample by the exact share of it that lies inside a
+ * target sample's footprint, applies the RGB -> YCbCr map and the chroma subsampling of this header to the rounded means and leaves
+ * 8-bit Y, Cb and Cr planes of the target in context scratch, which are then coded as a float batch's planes are.
+ *
+ * The map, for a source of W x H samples per channel and a target of ow x oh:
+ *     1 <= ow <= W <= R ow  and  1 <= oh <= H <= R oh,  R = JPEGAMD_MAX_RESIZE_RATIO     (no enlargement; one target sample's
+ *                                                                                          footprint is at most 65 x 65 samples)
+ *     wx(X, x) = max(0, min((X + 1) W, (x + 1) ow) - max(X W, x ow))        sum over x: W
+ *     wy(Y, y) = max(0, min((Y + 1) H, (y + 1) oh) - max(Y H, y oh))        sum over y: H
+ *     S(X, Y)  = sum over y of wy(Y, y) * sum over x of wx(X, x) * s(x, y)  <= 255 W H < 2^40
+ *     D        = W H                                                        < 2^32
+ *     v(X, Y)  = (S + (D >> 1)) / D            integer division rounding down; 0 .. 255
+ * applied to R, G and B separately, or to the single channel.  This is the area mean: every source sample weighted by the exact share
+ * of it inside the footprint [X W / ow, (X + 1) W / ow) x [Y H / oh, (Y + 1) H / oh), rounded half up: v = floor(mean + 1/2).
+ * ow = W, oh = H is the identity.  Where W = fx ow and H = fy oh the weights are constant and v is the plain box mean; for
+ * fx = fy = f it is sample for sample the reduced map above (whose partial edge boxes, where W is no multiple of f, are its own
+ * definition and not this one).  A target sample touches at most ceil(W / ow) + 1 source columns and ceil(H / oh) + 1 rows.  v is a
+ * byte.  Behind it, everything is this header's definition for those bytes: Y = (77 R + 150 G + 29 B) >> 8; Cb and Cr per RESIZED
+ * pixel by the two formulas above; 4:2:0 and 4:2:2 samples by (a + b + c + d + 2) >> 2 and (a + b + 1) >> 1 with the last resized
+ * column / row replicated; the byte of a single-channel picture is its Y sample.  Every file is BYTE FOR BYTE the file the uint8
+ * entries write for the ow x oh picture of those bytes stored as packed RGB (or as JPEGAMD_ORDER_GRAY).  The mean is taken of the
+ * STORED (gamma-encoded) bytes; averaging in linear light is out of scope.
+ *
+ * JpegAmdStridedImage describes the source as it does for the reduced entries; width and height are the SOURCE's (1 .. 65535 each,
+ * whatever the context was made for).  Refused with JPEGAMD_ERR_ARG before the context is read: everything the reduced entries
+ * refuse, with jpegamd_resize_check on (width, height, out_width, out_height) in place of the factor's range.  Nothing outside a row's
+ * own pixel_stride * width bytes is read.
+ *
+ *   jpegamd_resize_check                                   JPEGAMD_OK where the constraints above hold for a source of 1 .. 65535
+ *                                                          each way, JPEGAMD_ERR_ARG otherwise; host only
+ *   jpegamd_encode_resized_batch_async                     three scans for JPEGAMD_SUBSAMPLE_444 / _420 / _422; subsampling 0: the fused
+ *                                                          grayscale file (the luma of three planes, or the single channel)
+ *   jpegamd_encode_resized_interleaved_batch_async         one scan, restart_interval 0 .. 65535 in MCUs of the RESIZED picture, the
+ *                                                          context's Huffman mode; subsampling 0: the gray scan
+ *   jpegamd_encode_resized_progressive_script_batch_async  progressive files; scans NULL (scan_count 0): libjpeg's default script;
+ *                                                          subsampling 0: the grayscale progressive file
+ * Context sizing, capacity, status, statistics and profiling are the float entries' rules at the TARGET geometry: the context holds
+ * count x the resized picture's block rows, and buffers are sized with the jpegamd_max_jfif_bytes* functions at (ow, oh).  Quantisation
+ * tables and metadata set on the context apply. */
+#define JPEGAMD_MAX_RESIZE_RATIO 64
+int32_t jpegamd_resize_check(int32_t width, int32_t height, int32_t out_width, int32_t out_height);
+int32_t jpegamd_encode_resized_batch_async(JpegAmdEncoder *enc, const JpegAmdStridedImage *imgs, int32_t count, int32_t subsampling,
+                                           int32_t out_width, int32_t out_height, void *const *outs_dev, uint64_t out_capacity,
+                                           void *const *out_sizes_dev, void *stream);
+int32_t jpegamd_encode_resized_interleaved_batch_async(JpegAmdEncoder *enc, const JpegAmdStridedImage *imgs, int32_t count,
+                                                       int32_t subsampling, int32_t out_width, int32_t out_height,
+                                                       int32_t restart_interval, void *const *outs_dev, uint64_t out_capacity,
+                                                       void *const *out_sizes_dev, void *stream);
+int32_t jpegamd_encode_resized_progressive_script_batch_async(JpegAmdEncoder *enc, const JpegAmdStridedImage *imgs, int32_t count,
+                                                              int32_t subsampling, int32_t out_width, int32_t out_height,
+                                                              const JpegAmdScan *scans, int32_t scan_count, void *const *outs_dev,
+                                                              uint64_t out_capacity, void *const *out_sizes_dev, void *stream);
+
 /* Block until the last enqueued encode on this context finished; optionally fetch stats
  * (stats may be NULL).  Returns JPEGAMD_ERR_HUFF_CAPACITY if the output did not fit. */
 int32_t jpegamd_encoder_finish(JpegAmdEncoder *enc, JpegAmdStats *stats);

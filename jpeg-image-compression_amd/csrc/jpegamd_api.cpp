@@ -1013,6 +1013,8 @@ struct FloatSource {
     int32_t channels, type, row_stride, pixel_stride;      // 1 or 3; JPEGAMD_FLOAT_*; bytes
     float scale, offset;
     int32_t reduce, src_width, src_height;                 // 0: float samples
+    int32_t resize, out_width, out_height;                 // resize: BYTES again, which k_resize_planes_batch resamples to out_width x
+                                                           // out_height by exact area means (jpegamd_encode_resized_batch_async)
 };
 static int launch_float_luma_pass(JpegAmdEncoder *e, const FloatSource &fl, const JpegAmdImage &gy, int32_t count, hipStream_t stream,
                                   void *const *ev);
@@ -1387,9 +1389,12 @@ static int launch_matrix_pass(JpegAmdEncoder *e, const JpegAmdImage &g0, const P
 // pixel side by side in either order; anything else by samples.
 static int launch_reduce_pass(JpegAmdEncoder *e, const FloatSource &fl, int w, int h, int32_t count, int out, int32_t subsampling,
                               const ChromaGeom &cg, const MatrixScratch &m, hipStream_t stream, void *const *ev);
+static int launch_resize_pass(JpegAmdEncoder *e, const FloatSource &fl, int w, int h, int32_t count, int out, int32_t subsampling,
+                              const ChromaGeom &cg, const MatrixScratch &m, hipStream_t stream, void *const *ev);
 static int launch_float_pass(JpegAmdEncoder *e, const FloatSource &fl, int w, int h, int32_t count, int out, int32_t subsampling,
                              const ChromaGeom &cg, const MatrixScratch &m, hipStream_t stream, void *const *ev) {
     if (fl.reduce) return launch_reduce_pass(e, fl, w, h, count, out, subsampling, cg, m, stream, ev);
+    if (fl.resize) return launch_resize_pass(e, fl, w, h, count, out, subsampling, cg, m, stream, ev);
     FloatPlanesBatchArgs fa;
     std::memset(&fa, 0, sizeof(fa));
     const int kb = fl.type == JPEGAMD_FLOAT_F32 ? 4 : 2;
@@ -1448,6 +1453,41 @@ static int launch_reduce_pass(JpegAmdEncoder *e, const FloatSource &fl, int w, i
         ra.cw = w; ra.ch = h;
     }
     return launch_reduce_planes_batch(ra, stream, ev);
+}
+// k_resize_planes_batch in its place for a batch of bytes to be resized (fl.resize): w x h is the TARGET (fl.out_width x
+// fl.out_height), `out` and the scratch layout are the float pass's.  The walk: planes of bytes one apart; the three channels of every
+// picture at the same places inside a pixel of at most kResizePackedMax bytes (R G B, B G R, RGBA, BGRA), read as one run from the
+// lowest of the three pointers; anything else by bytes.
+static int launch_resize_pass(JpegAmdEncoder *e, const FloatSource &fl, int w, int h, int32_t count, int out, int32_t subsampling,
+                              const ChromaGeom &cg, const MatrixScratch &m, hipStream_t stream, void *const *ev) {
+    static_assert(kResizeOutColor == kFloatOutColor && kResizeOutLuma == kFloatOutLuma && kResizeOutSingle == kFloatOutSingle, "one `out`");
+    ResizePlanesBatchArgs ra;
+    std::memset(&ra, 0, sizeof(ra));
+    bool packed = fl.channels == 3 && fl.pixel_stride > 1 && fl.pixel_stride <= kResizePackedMax;
+    for (int i = 0; i < count && packed; ++i) {
+        const uint8_t *lowest = std::min(fl.plane[0][i], std::min(fl.plane[1][i], fl.plane[2][i]));
+        for (int k = 0; k < 3; ++k) {
+            const ptrdiff_t off = fl.plane[k][i] - lowest;
+            if (off >= fl.pixel_stride || (i > 0 && off != ra.offset[k])) packed = false;
+            if (i == 0) ra.offset[k] = (int32_t)std::min<ptrdiff_t>(off, kResizePackedMax);
+        }
+    }
+    if (!packed) ra.offset[0] = ra.offset[1] = ra.offset[2] = 0;
+    ra.walk = packed ? kResizeWalkPacked : (fl.pixel_stride == 1 ? kResizeWalkPlanar : kResizeWalkGeneric);
+    for (int i = 0; i < count; ++i)
+        for (int k = 0; k < fl.channels; ++k) ra.plane[k][i] = fl.plane[k][i];
+    if (packed) for (int i = 0; i < count; ++i) ra.plane[0][i] = fl.plane[0][i] - ra.offset[0];        // the lowest of the three
+    ra.batch = count;
+    ra.src_width = fl.src_width; ra.src_height = fl.src_height; ra.row_stride = fl.row_stride; ra.pixel_stride = fl.pixel_stride;
+    ra.width = w; ra.height = h; ra.out = out;
+    ra.ypitch = m.ypitch; ra.yplane_bytes = m.yplane_bytes; ra.yplanes = e->color.bplanes + m.y_off;
+    if (out == kResizeOutColor) {
+        ra.mode = chroma_mode(subsampling);
+        ra.cw = cg.cw; ra.ch = cg.ch; ra.pitch = cg.pitch; ra.plane_bytes = cg.plane_bytes; ra.planes = e->color.bplanes;
+    } else {
+        ra.cw = w; ra.ch = h;
+    }
+    return launch_resize_planes_batch(ra, stream, ev);
 }
 // ... the Y planes alone, for the grayscale routes: gy describes the scratch planes (matrix_scratch with no chroma in front).
 static int launch_float_luma_pass(JpegAmdEncoder *e, const FloatSource &fl, const JpegAmdImage &gy, int32_t count, hipStream_t stream,
@@ -3124,6 +3164,99 @@ extern "C" int32_t jpegamd_debug_reduce_reciprocal(int32_t n, uint32_t *multipli
     if (n < 1 || n > kMaxReduce * kMaxReduce || !multiplier || !shift) return JPEGAMD_ERR_ARG;
     *multiplier = reduce_recip(n);
     *shift = kReduceShift;
+    return JPEGAMD_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Resized pictures: uint8 samples at any row and pixel stride, resampled to out_width x out_height by exact area
+// means by k_resize_planes_batch, which leaves the planes of the TARGET in context scratch; behind it every route is a float batch's.
+// ---------------------------------------------------------------------------------------------------------
+extern "C" int32_t jpegamd_resize_check(int32_t width, int32_t height, int32_t out_width, int32_t out_height) {
+    static_assert(JPEGAMD_MAX_RESIZE_RATIO == kMaxResizeRatio, "one bound");
+    if (width <= 0 || height <= 0 || width > 65535 || height > 65535) return JPEGAMD_ERR_ARG;
+    if (out_width < 1 || out_width > width || (int64_t)width > (int64_t)JPEGAMD_MAX_RESIZE_RATIO * out_width) return JPEGAMD_ERR_ARG;
+    if (out_height < 1 || out_height > height || (int64_t)height > (int64_t)JPEGAMD_MAX_RESIZE_RATIO * out_height) return JPEGAMD_ERR_ARG;
+    return JPEGAMD_OK;
+}
+
+// The arguments of a resized batch: reduced_args' checks with jpegamd_resize_check in place of the factor's (a factor of 1 passes
+// reduced_args whatever the source measures) -> the TARGET geometry as a GRAY picture and what the pass reads.
+static int32_t resized_args(const JpegAmdEncoder *e, const JpegAmdStridedImage *imgs, int32_t count, int32_t subsampling, int32_t out_width,
+                            int32_t out_height, void *const *outs_dev, void *const *out_sizes_dev, bool files, JpegAmdImage *g0, PlaneSet *ps,
+                            FloatSource *fl, uint64_t **sizes) {
+    if (!e || !imgs || count < 1 || count > kMaxBatch) return JPEGAMD_ERR_ARG;
+    if (jpegamd_resize_check(imgs[0].width, imgs[0].height, out_width, out_height)) return JPEGAMD_ERR_ARG;
+    if (int32_t rc = reduced_args(e, imgs, count, subsampling, 1, outs_dev, out_sizes_dev, files, g0, ps, fl, sizes)) return rc;
+    fl->reduce = 0; fl->resize = 1; fl->out_width = out_width; fl->out_height = out_height;
+    g0->width = out_width; g0->height = out_height; g0->row_stride = (out_width + 3) / 4 * 4;
+    return JPEGAMD_OK;
+}
+
+// `count` pictures of bytes, each resized to out_width x out_height, in three scans, or -- subsampling 0 -- as the fused grayscale
+// file (front_batch): the files the uint8 entries write for the resized bytes.
+extern "C" int32_t jpegamd_encode_resized_batch_async(JpegAmdEncoder *e, const JpegAmdStridedImage *imgs, int32_t count, int32_t subsampling,
+                                                      int32_t out_width, int32_t out_height, void *const *outs_dev, uint64_t out_capacity,
+                                                      void *const *out_sizes_dev, void *stream_) {
+    // the arguments first: nothing of the context is read before they are known to be good
+    JpegAmdImage g0;
+    PlaneSet ps;
+    FloatSource fl;
+    uint64_t *sizes[kMaxBatch];
+    if (int32_t rc = resized_args(e, imgs, count, subsampling, out_width, out_height, outs_dev, out_sizes_dev, true, &g0, &ps, &fl, sizes))
+        return rc;
+    return front_batch(e, g0, ps, fl, count, subsampling, outs_dev, out_capacity, sizes, stream_);
+}
+
+// ... in one scan (front_interleaved_batch); restart_interval counts MCUs of the resized picture.
+extern "C" int32_t jpegamd_encode_resized_interleaved_batch_async(JpegAmdEncoder *e, const JpegAmdStridedImage *imgs, int32_t count,
+                                                                  int32_t subsampling, int32_t out_width, int32_t out_height,
+                                                                  int32_t restart_interval, void *const *outs_dev, uint64_t out_capacity,
+                                                                  void *const *out_sizes_dev, void *stream_) {
+    // the arguments first: nothing of the context is read before they are known to be good
+    if (!restart_valid(restart_interval)) return JPEGAMD_ERR_ARG;
+    JpegAmdImage g0;
+    PlaneSet ps;
+    FloatSource fl;
+    uint64_t *sizes[kMaxBatch];
+    if (int32_t rc = resized_args(e, imgs, count, subsampling, out_width, out_height, outs_dev, out_sizes_dev, true, &g0, &ps, &fl, sizes))
+        return rc;
+    return front_interleaved_batch(e, g0, ps, fl, count, subsampling, restart_interval, outs_dev, out_capacity, sizes, stream_);
+}
+
+// ... as progressive files with a scan script (null: the default one); subsampling 0: the grayscale progressive file.
+extern "C" int32_t jpegamd_encode_resized_progressive_script_batch_async(JpegAmdEncoder *e, const JpegAmdStridedImage *imgs, int32_t count,
+                                                                         int32_t subsampling, int32_t out_width, int32_t out_height,
+                                                                         const JpegAmdScan *scans, int32_t scan_count, void *const *outs_dev,
+                                                                         uint64_t out_capacity, void *const *out_sizes_dev, void *stream_) {
+    ProgScript sc;
+    if (!prog_script_from(scans, scan_count, subsampling == 0 ? 1 : 3, &sc)) return JPEGAMD_ERR_ARG;
+    JpegAmdImage g0;
+    PlaneSet ps;
+    FloatSource fl;
+    uint64_t *sizes[kMaxBatch];
+    if (int32_t rc = resized_args(e, imgs, count, subsampling, out_width, out_height, outs_dev, out_sizes_dev, true, &g0, &ps, &fl, sizes))
+        return rc;
+    return interleaved_batch(e, g0, ps, count, subsampling == 0 ? kSubNone : subsampling, 0, outs_dev, out_capacity, sizes, stream_, nullptr,
+                             kProgScript, &sc, &fl);
+}
+
+// Tests: the pass of a resized batch alone (front_debug_planes; the buffers hold planes of the TARGET geometry) and the kernel's
+// division, (s + (d >> 1)) / d for s <= 255 d + (d >> 1), by the text the kernel runs.  Not part of the public header.
+extern "C" int32_t jpegamd_debug_resized_planes(JpegAmdEncoder *e, const JpegAmdStridedImage *imgs, int32_t count, int32_t subsampling,
+                                                int32_t out_width, int32_t out_height, void *y_out, void *cb_out, void *cr_out,
+                                                void *stream_) {
+    JpegAmdImage g0;
+    PlaneSet ps;
+    FloatSource fl;
+    if (!y_out || (subsampling != 0 && (!cb_out || !cr_out))) return JPEGAMD_ERR_ARG;
+    if (int32_t rc = resized_args(e, imgs, count, subsampling, out_width, out_height, nullptr, nullptr, false, &g0, &ps, &fl, nullptr))
+        return rc;
+    return front_debug_planes(e, g0, fl, count, subsampling, y_out, cb_out, cr_out, stream_);
+}
+extern "C" int32_t jpegamd_debug_resize_divide(uint32_t d, uint64_t s, uint32_t *q) {
+    if (d == 0 || !q || s > 255 * (uint64_t)d + (d >> 1)) return JPEGAMD_ERR_ARG;
+    const ResizeDivide dv = resize_divide_for(d);
+    *q = resize_divide(s + (d >> 1), dv.d, dv.mul, dv.shift);
     return JPEGAMD_OK;
 }
 

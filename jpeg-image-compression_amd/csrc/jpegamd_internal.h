@@ -402,6 +402,51 @@ struct ReducePlanesBatchArgs {
     uint8_t *planes, *yplanes;
 };
 int launch_reduce_planes_batch(const ReducePlanesBatchArgs &a, void *stream, void *const *ev = nullptr);
+
+// Resized pictures (jpegamd_encode_resized_batch_async and its twins, jpegamd_resize.hip).  k_resize_planes_batch makes every sample
+// of the width x height target the exact area mean of the src_width x src_height source (jpeg_compression.h, "Resized pictures":
+// (S + (D >> 1)) / D with D = src_width src_height), applies the header's RGB -> YCbCr map and chroma subsampling to those bytes, and
+// writes the planes exactly where k_float_planes_batch writes its own.
+constexpr int kMaxResizeRatio = 64;                                         // JPEGAMD_MAX_RESIZE_RATIO
+// The division of n = S + (D >> 1) <= 256 D by D < 2^32, whose quotient is at most 256: the bits of n above `shift` times
+// mul = floor(2^(31 + shift) / D), >> 31, is the quotient or one less, and one comparison of the remainder corrects it.  With
+// shift = max(0, bits(D) - 12): cutting n costs at most 2^shift / D <= 2^-11 of the quotient and cutting mul at most
+// n / 2^(31 + shift) <= 2^-11, less than 2^-10 together; at shift == 0 (D < 2^12, n < 2^20) n is not cut at all and the one
+// truncation costs n / 2^31 < 2^-11.  The kernel and jpegamd_debug_resize_divide share this text.
+struct ResizeDivide { uint32_t d, mul; int32_t shift; };
+constexpr ResizeDivide resize_divide_for(uint32_t d) {
+    int bits = 0;
+    for (uint32_t t = d; t; t >>= 1) ++bits;
+    const int shift = bits > 12 ? bits - 12 : 0;
+    return ResizeDivide{d, (uint32_t)(((uint64_t)1 << (31 + shift)) / d), shift};
+}
+constexpr uint32_t resize_divide(uint64_t n, uint32_t d, uint32_t mul, int shift) {
+    uint32_t q = (uint32_t)(((uint64_t)(uint32_t)(n >> shift) * mul) >> 31);
+    if (n - (uint64_t)q * d >= d) ++q;
+    return q;
+}
+// the walks: three planes of bytes one apart (16-byte loads) / the three channels of a pixel inside its pixel_stride <= kResizePackedMax
+// bytes, read as one run from plane[0] (R G B, B G R, RGBA, BGRA) / bytes pixel_stride apart, gathered one by one
+constexpr int kResizeWalkPlanar = 0, kResizeWalkPacked = 1, kResizeWalkGeneric = 2;
+constexpr int kResizeOutColor = 0, kResizeOutLuma = 1, kResizeOutSingle = 2;
+constexpr int kResizePackedMax = 4;
+constexpr int kResizeLdsBudget = 32768;                                     // bytes of source rows a workgroup stages at a time
+struct ResizePlanesBatchArgs {
+    const uint8_t *plane[3][kMaxBatch]; // R, G, B of every picture (kResizeOutSingle: plane[0] alone; kResizeWalkPacked: plane[0] is the
+                                        // lowest of the three pointers and offset[] says where each channel lies from it)
+    int32_t batch;
+    int32_t src_width, src_height, row_stride, pixel_stride;   // the source: samples, bytes
+    int32_t width, height;              // the target: width <= src_width <= 64 width, the same for the heights
+    int32_t mode, walk, out;            // kChromaMode* (kResizeOutColor alone), kResizeWalk*, kResizeOut*
+    int32_t offset[3];                  // kResizeWalkPacked: bytes from plane[0] to R, G, B, each below pixel_stride
+    int32_t cw, ch, pitch, ypitch;      // (kResizeOutLuma, kResizeOutSingle: cw = width, ch = height; pitch, plane_bytes, planes unused)
+    uint64_t plane_bytes, yplane_bytes; // multiples of 16
+    uint8_t *planes, *yplanes;
+    // filled by launch_resize_planes_batch
+    ResizeDivide div;                   // by D = src_width src_height
+    int32_t lds_pitch, lds_rows;        // bytes of one staged source row of one run (a multiple of 16); source rows staged at a time
+};
+int launch_resize_planes_batch(const ResizePlanesBatchArgs &a, void *stream, void *const *ev = nullptr);
 // k_picture_stats: what the tile records of one k_tile_encode launch add up to per picture and scan -- bits (with the first DC
 // symbol of every tile, which the record leaves out), run/size symbols, exact-order fallbacks -- summed into
 // pic[picture][scan][3].  Launch image i is picture i, scan 0 (luma), or plane first_plane + i (chroma).

@@ -207,6 +207,13 @@ def _prototypes():
         "jpegamd_encode_reduced_batch_async": (i32, [vp, C.POINTER(StridedImage), i32, i32, i32, vpp, u64, vpp, vp]),
         "jpegamd_encode_reduced_interleaved_batch_async": (i32, [vp, C.POINTER(StridedImage), i32, i32, i32, i32, vpp, u64, vpp, vp]),
         "jpegamd_encode_reduced_progressive_script_batch_async": (i32, [vp, C.POINTER(StridedImage), i32, i32, i32, vp, i32, vpp, u64, vpp, vp]),
+        # resized pictures: (context, pictures[], count, subsampling, out_width, out_height, ..., outs[], out_cap,
+        # sizes[], stream)
+        "jpegamd_resize_check": (i32, [i32, i32, i32, i32]),
+        "jpegamd_encode_resized_batch_async": (i32, [vp, C.POINTER(StridedImage), i32, i32, i32, i32, vpp, u64, vpp, vp]),
+        "jpegamd_encode_resized_interleaved_batch_async": (i32, [vp, C.POINTER(StridedImage), i32, i32, i32, i32, i32, vpp, u64, vpp, vp]),
+        "jpegamd_encode_resized_progressive_script_batch_async": (i32, [vp, C.POINTER(StridedImage), i32, i32, i32, i32, vp, i32, vpp, u64,
+                                                                        vpp, vp]),
     }
     later = {
         "jpegamd_encoder_set_pipeline": (i32, [vp, i32]),
@@ -244,6 +251,8 @@ def _prototypes():
         "jpegamd_debug_float_planes": (i32, [vp, C.POINTER(FloatImage), i32, i32, i32, f32, f32, vp, vp, vp, vp]),
         "jpegamd_debug_reduced_planes": (i32, [vp, C.POINTER(StridedImage), i32, i32, i32, vp, vp, vp, vp]),
         "jpegamd_debug_reduce_reciprocal": (i32, [i32, C.POINTER(C.c_uint32), C.POINTER(i32)]),
+        "jpegamd_debug_resized_planes": (i32, [vp, C.POINTER(StridedImage), i32, i32, i32, i32, vp, vp, vp, vp]),
+        "jpegamd_debug_resize_divide": (i32, [C.c_uint32, u64, C.POINTER(C.c_uint32)]),
     }
     return base, later, hidden, tests
 
@@ -1484,6 +1493,92 @@ def encode_reduced(t, quality: int = 0, subsampling: int = SUBSAMPLE_420, factor
     return _encode_reduced("encode_reduced", t, quality, subsampling, factor, layout, True)[0]
 
 
+MAX_RESIZE_RATIO = 64                                        # JPEGAMD_MAX_RESIZE_RATIO: source over target, each way
+
+
+def resize_check(width: int, height: int, out_width: int, out_height: int) -> None:
+    """What the resized functions take (jpegamd_resize_check): a source of 1..65535 each way and a target that is no larger than it
+    and no smaller than 1/MAX_RESIZE_RATIO of it, each way.  A ValueError otherwise."""
+    try:
+        rc = lib.jpegamd_resize_check(width, height, out_width, out_height)
+    except (C.ArgumentError, TypeError):
+        rc = -1
+    if rc:
+        raise ValueError(f"a resized picture needs a source of 1..65535 each way and a target of 1 <= out_width <= width <= "
+                         f"{MAX_RESIZE_RATIO} * out_width (the same for the heights), not {(width, height)!r} -> {(out_width, out_height)!r}")
+
+
+def fit_size(w: int, h: int, max_w: int, max_h: int) -> tuple:
+    """The largest size of the picture's shape inside max_w x max_h, in integers: (w, h) itself where it fits; else the side that
+    binds becomes the bound and the other is rounded half up, at least 1.  Python only; resize_check still judges the result."""
+    if any(isinstance(v, bool) or not isinstance(v, int) or v < 1 for v in (w, h, max_w, max_h)):
+        raise ValueError(f"fit_size takes four positive integers, not {(w, h, max_w, max_h)!r}")
+    if w <= max_w and h <= max_h:
+        return w, h
+    if w * max_h >= h * max_w:
+        return max_w, max(1, (h * max_w + w // 2) // w)
+    return max(1, (w * max_h + h // 2) // h), max_h
+
+
+def _encode_resized(name: str, t, quality, subsampling, size, layout, single: bool, interleaved: bool = False, restart_interval=None,
+                    huffman=None, progressive: bool = False, scans=None) -> list:
+    """What the resized functions of jpegamd, jpegamd.mjpeg and jpegamd.progressive_script share, as _encode_reduced: every argument
+    checked on the CPU, then the pictures through the per-device context -- sized for the RESIZED pictures -- in calls of at most
+    MAX_BATCH.  One channel (layout="gray") is a grayscale file whatever `subsampling` says."""
+    huff = None if huffman is None else _huffman(huffman)
+    if (not isinstance(size, (tuple, list)) or len(size) != 2 or
+            any(isinstance(v, bool) or not isinstance(v, int) for v in size)):
+        raise ValueError(f"size must be (out_width, out_height), two integers, not {size!r}")
+    ow, oh = size
+    n, h, w, row, pixel, _, channels, ptr, planes = _float_layout(t, layout, single, byte=True)
+    resize_check(w, h, ow, oh)
+    sub = 0 if channels == 1 else subsampling
+    if sub not in (0, SUBSAMPLE_444, SUBSAMPLE_420, SUBSAMPLE_422):
+        raise ValueError("subsampling must be SUBSAMPLE_444, SUBSAMPLE_420, SUBSAMPLE_422 or 0 (a grayscale file)")
+    ri = _restart(restart_interval, interleaved, ow, sub or SUBSAMPLE_444)     # ("row": an MCU row of the RESIZED picture)
+    if progressive:
+        cap = max_jfif_bytes_progressive_script(ow, oh, sub, scans)
+        if not cap:
+            if scans is not None:
+                validate_scan_script(scans, 1 if sub == 0 else 3)
+            raise ValueError("bad dimensions")
+    elif interleaved:
+        cap = max_jfif_bytes_gray_scan(ow, oh, ri) if sub == 0 else max_jfif_bytes_interleaved_restart(ow, oh, sub, ri)
+    else:
+        cap = max_jfif_bytes(ow, oh) if sub == 0 else max_jfif_bytes_color(ow, oh, sub)
+    if any(not p.is_cuda or p.device != planes[0].device for p in planes):
+        raise ValueError(f"{name} needs device tensors on one device")
+
+    def queue(enc, b0, k, outs, cap, size_ptrs, stream):
+        imgs = [Encoder.strided_image(ptr(b0 + i), w, h, row, pixel, quality) for i in range(k)]
+        if progressive:
+            enc.encode_resized_progressive_script_batch_async(imgs, sub, ow, oh, scans, outs, cap, size_ptrs, stream)
+        elif interleaved:
+            enc.encode_resized_interleaved_batch_async(imgs, sub, ow, oh, ri, outs, cap, size_ptrs, stream)
+        else:
+            enc.encode_resized_batch_async(imgs, sub, ow, oh, outs, cap, size_ptrs, stream)
+
+    return _encode_pictures(planes[0].device, n, oh, ow, cap, queue, huff)
+
+
+def encode_resized_batch(t, quality: int = 0, subsampling: int = SUBSAMPLE_420, size=None, layout="chw") -> list:
+    """A uint8 DEVICE tensor of N pictures -> N JFIF files of size = (out_width, out_height) pixels through
+    jpegamd_encode_resized_batch_async: one kernel makes every sample of the target the exact area mean of the source -- every source
+    byte weighted by the share of it inside the target sample's footprint, rounded half up; include/jpeg_compression.h has the
+    definition.  The files are byte for byte those of encode_tensor_batch for the uint8 tensor of those means: no resize of the
+    caller's, no float copy, no resized tensor.  The mean is of the stored (gamma-encoded) bytes.
+    size: no larger than the source and no smaller than 1/MAX_RESIZE_RATIO of it, each way (resize_check); fit_size gives the size
+    that fits a box.  layout, the three-plane form, subsampling 0, crops, strided rows, t[::2] and channels_last memory as for
+    encode_reduced_batch; the per-device context of encode_tensor is used, with the tables and metadata of a quant_tables / metadata
+    block."""
+    return _encode_resized("encode_resized_batch", t, quality, subsampling, size, layout, False)
+
+
+def encode_resized(t, quality: int = 0, subsampling: int = SUBSAMPLE_420, size=None, layout="chw") -> bytes:
+    """One picture of bytes -> its resized file, as encode_resized_batch: [3, H, W], [H, W, 3], [H, W, 4], [H, W] or three [H, W] planes."""
+    return _encode_resized("encode_resized", t, quality, subsampling, size, layout, True)[0]
+
+
 def encode_files(in_paths, out_paths, quality: int = 0):
     """File-to-file batch with overlapped I/O and transfers (jpegamd_encode_files) -> (return code, [status per file], BatchStats)."""
     n = len(in_paths)
@@ -1656,7 +1751,46 @@ class _ReducedEntries(_FloatEntries):
                             size_ptrs, stream)
 
 
-class Encoder(_ReducedEntries):
+class _ResizedEntries(_ReducedEntries):
+    """... and the entries of resized pictures: bytes at any row and pixel stride (strided_image), resampled to
+    out_width x out_height by exact area means by one kernel in front of the tile encoder."""
+
+    def _resized_batch(self, name: str, imgs, subsampling: int, out_width: int, out_height: int, middle, out_ptrs, out_cap: int, size_ptrs,
+                       stream: int):
+        """A resized entry: name(context, pictures[], count, subsampling, out_width, out_height, middle..., outs[], out_cap, sizes[],
+        stream)."""
+        n = len(imgs)
+        arr, pointers = (StridedImage * n)(*imgs), C.c_void_p * n
+        rc = getattr(lib, name)(self._h, arr, n, int(subsampling), int(out_width), int(out_height), *middle, pointers(*out_ptrs), out_cap,
+                                pointers(*size_ptrs), C.c_void_p(stream))
+        if rc:
+            raise JpegAmdError(rc, name)
+
+    def encode_resized_batch_async(self, imgs, subsampling: int, out_width: int, out_height: int, out_ptrs, out_cap: int, size_ptrs,
+                                   stream: int = 0):
+        """The files of `len(imgs)` pictures of bytes of one geometry (strided_image), each resized to out_width x out_height, in three
+        scans, or for subsampling 0 the grayscale file (jpegamd_encode_resized_batch_async); the context, out_cap and the files as for
+        encode_planar_batch_async on the resized bytes."""
+        self._resized_batch("jpegamd_encode_resized_batch_async", imgs, subsampling, out_width, out_height, (), out_ptrs, out_cap, size_ptrs,
+                            stream)
+
+    def encode_resized_interleaved_batch_async(self, imgs, subsampling: int, out_width: int, out_height: int, restart_interval: int,
+                                               out_ptrs, out_cap: int, size_ptrs, stream: int = 0):
+        """... in ONE scan, with restart intervals of `restart_interval` MCUs of the resized picture (0: none) and the context's Huffman
+        tables; subsampling 0: the grayscale file of encode_gray_scan_batch_async (jpegamd_encode_resized_interleaved_batch_async)."""
+        self._resized_batch("jpegamd_encode_resized_interleaved_batch_async", imgs, subsampling, out_width, out_height,
+                            (int(restart_interval),), out_ptrs, out_cap, size_ptrs, stream)
+
+    def encode_resized_progressive_script_batch_async(self, imgs, subsampling: int, out_width: int, out_height: int, scans, out_ptrs,
+                                                      out_cap: int, size_ptrs, stream: int = 0):
+        """... as progressive files with the scan script `scans` (None: the default one); subsampling 0: the grayscale progressive
+        file (jpegamd_encode_resized_progressive_script_batch_async)."""
+        sc, ns = _scan_array(scans)
+        self._resized_batch("jpegamd_encode_resized_progressive_script_batch_async", imgs, subsampling, out_width, out_height, (sc, ns),
+                            out_ptrs, out_cap, size_ptrs, stream)
+
+
+class Encoder(_ResizedEntries):
     """Level-1 context: device pointers in, device pointers out, stream-ordered."""
 
     def __init__(self, max_width: int, max_height: int):

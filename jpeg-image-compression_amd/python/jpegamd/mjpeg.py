@@ -112,3 +112,20 @@ def encode_reduced(t, quality: int = 0, subsampling: int = _j.SUBSAMPLE_420, fac
     """One picture of bytes -> its reduced one-scan file, as encode_reduced_batch."""
     return _j._encode_reduced("encode_reduced", t, quality, subsampling, factor, layout, True, interleaved=True,
                               restart_interval=restart_interval, huffman=huffman)[0]
+
+
+def encode_resized_batch(t, quality: int = 0, subsampling: int = _j.SUBSAMPLE_420, size=None, layout="chw", restart_interval=None,
+                         huffman: str = "standard") -> list:
+    """jpegamd.encode_resized_batch's uint8 pictures, each resized to size = (out_width, out_height) -> N one-scan files through
+    jpegamd_encode_resized_interleaved_batch_async: byte for byte encode_tensor_batch's files of the resized bytes.  restart_interval
+    counts MCUs of the RESIZED picture ("row": one of its MCU rows).  One channel (layout="gray") or subsampling 0: the grayscale file
+    of encode_gray_batch."""
+    return _j._encode_resized("encode_resized_batch", t, quality, subsampling, size, layout, False, interleaved=True,
+                              restart_interval=restart_interval, huffman=huffman)
+
+
+def encode_resized(t, quality: int = 0, subsampling: int = _j.SUBSAMPLE_420, size=None, layout="chw", restart_interval=None,
+                   huffman: str = "standard") -> bytes:
+    """One picture of bytes -> its resized one-scan file, as encode_resized_batch."""
+    return _j._encode_resized("encode_resized", t, quality, subsampling, size, layout, True, interleaved=True,
+                              restart_interval=restart_interval, huffman=huffman)[0]

@@ -140,3 +140,15 @@ def encode_reduced_batch(t, quality: int = 0, subsampling: int = _j.SUBSAMPLE_42
 def encode_reduced(t, quality: int = 0, subsampling: int = _j.SUBSAMPLE_420, factor: int = 2, layout="chw", scans=None) -> bytes:
     """One picture of bytes -> its reduced progressive file, as encode_reduced_batch."""
     return _j._encode_reduced("encode_reduced", t, quality, subsampling, factor, layout, True, progressive=True, scans=scans)[0]
+
+
+def encode_resized_batch(t, quality: int = 0, subsampling: int = _j.SUBSAMPLE_420, size=None, layout="chw", scans=None) -> list:
+    """jpegamd.encode_resized_batch's uint8 pictures, each resized to size = (out_width, out_height) -> N progressive files through
+    jpegamd_encode_resized_progressive_script_batch_async: byte for byte encode_tensor_batch's files of the resized bytes.  One channel
+    (layout="gray") or subsampling 0: the grayscale progressive file of encode_gray_batch."""
+    return _j._encode_resized("encode_resized_batch", t, quality, subsampling, size, layout, False, progressive=True, scans=scans)
+
+
+def encode_resized(t, quality: int = 0, subsampling: int = _j.SUBSAMPLE_420, size=None, layout="chw", scans=None) -> bytes:
+    """One picture of bytes -> its resized progressive file, as encode_resized_batch."""
+    return _j._encode_resized("encode_resized", t, quality, subsampling, size, layout, True, progressive=True, scans=scans)[0]

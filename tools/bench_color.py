@@ -87,6 +87,12 @@ clamp, the cast and the planar uint8 entry, as one unit), `uint8` (the uint8 ent
 the floor) and `copy` (a device copy of as many bytes as the source holds) alternate in one run, --rounds medians of --steps calls
 each, timed between events on the stream; one line per route.
 
+--resize WxH (beside --reduce, with the same options) times uint8 pictures of --size pixels each way encoded RESIZED to W x H through the
+resized entries (jpegamd_encode_resized_batch_async, _interleaved_, _progressive_script_), in every --scan mode.  Routes
+`resized`, `resize` (what a caller does without the entry: a float copy, F.interpolate(mode="area"), +0.5, floor, clamp, the cast and the
+planar uint8 entry, as one unit; torch's area mode gives whole samples to a bin, so its bytes are close to the entry's and not equal),
+`uint8` (the uint8 entry alone on bytes resized beforehand: the floor) and `copy`, as for --reduce.
+
 --scan gray (with --batch N, default 8) times GRAYSCALE files through jpegamd_encode_gray_scan_batch_async: the luma
 of the same --size pictures, --restart N|row in blocks (`row`: ceil(W / 8)), --huffman standard|optimized; the whole call is timed
 (ns_total).  Without --restart (or with 0) and with the standard tables the entry is jpegamd_encode_batch_async, so that line is the
@@ -148,6 +154,8 @@ def main() -> None:
     ap.add_argument("--dpi", type=int, default=None, metavar="N", help="every --scan mode: this pixel density in every file")
     ap.add_argument("--reduce", type=int, default=None, metavar="F",
                     help="every --scan mode: uint8 pictures encoded reduced by F (1 .. 8) both ways through the reduced entries (DESIGN.md 4.6.19)")
+    ap.add_argument("--resize", default=None, metavar="WxH",
+                    help="every --scan mode: uint8 pictures encoded resized to W x H through the resized entries (DESIGN.md 4.6.20)")
     a = ap.parse_args()
     if a.scans is not None and (a.scan != "progressive" or a.successive or a.huffman is not None or a.source != "rgb"):
         sys.exit("--scans needs --scan progressive and takes --size, --batch, --subsampling, --quality, --kind alone")
@@ -162,11 +170,19 @@ def main() -> None:
     dev = torch.device("cuda:0")
     w = h = a.size
     sources = a.source.split(",")
-    if a.reduce is not None:
-        if not 1 <= a.reduce <= jpegamd.MAX_REDUCE:
+    if a.resize is not None:
+        if a.reduce is not None:
+            sys.exit("--resize and --reduce are two runs")
+        try:
+            a.resize = tuple(int(v) for v in a.resize.lower().split("x"))
+            jpegamd.resize_check(w, h, *a.resize)
+        except (ValueError, TypeError) as e:
+            sys.exit(f"--resize takes WxH: {e}")
+    if a.reduce is not None or a.resize is not None:
+        if a.reduce is not None and not 1 <= a.reduce <= jpegamd.MAX_REDUCE:
             sys.exit(f"--reduce takes 1 .. {jpegamd.MAX_REDUCE}")
         if a.source != "rgb" or a.sample_range != "full" or a.matrix != "bt601" or a.convert or a.narrow or a.mapped or a.repack or a.scans or a.successive:
-            sys.exit("--reduce takes --size, --batch, --layout chw|hwc, --scan, --subsampling, --restart, --huffman, --rounds, --quality, --kind, "
+            sys.exit("--reduce and --resize take --size, --batch, --layout chw|hwc, --scan, --subsampling, --restart, --huffman, --rounds, --quality, --kind, "
                      "--qtables and the metadata options alone")
         if a.scan in ("separate", "progressive") and (a.restart is not None or a.huffman is not None):
             sys.exit("--restart and --huffman need --scan interleaved or gray")
@@ -1003,11 +1019,14 @@ def run_reduce(a, jpegamd, torch, dev) -> None:
     `reduced` the reduced entry; `resize` what a caller does without it -- a float copy, avg_pool2d(ceil_mode=True, divisor_override=1),
     the division by the box counts, + 0.5, floor, clamp and the cast, then the planar uint8 entry, as one unit --; `uint8` the uint8 entry
     of the same layout alone on bytes reduced beforehand, the floor the reduced call approaches from above; and `copy`, a device-to-device
-    copy of as many bytes as the source holds, the yardstick for k_reduce_planes_batch's own time in a kernel trace of the same command."""
+    copy of as many bytes as the source holds, the yardstick for k_reduce_planes_batch's own time in a kernel trace of the same command.
+    --resize WxH: the same four routes around the resized entries; the front route is named `resized`, and the
+    caller's route is F.interpolate(mode="area") in place of the pooling."""
     import torch.nn.functional as F
     w = h = a.size
     f = a.reduce
-    ow, oh = jpegamd.reduced_size(w, h, f)
+    ow, oh = a.resize if a.resize else jpegamd.reduced_size(w, h, f)
+    front = "resized" if a.resize else "reduced"
     n = a.batch or 8
     layout = a.layout or "chw"
     if layout not in ("chw", "hwc"):
@@ -1026,12 +1045,15 @@ def run_reduce(a, jpegamd, torch, dev) -> None:
     src = hwc8.permute(0, 3, 1, 2).contiguous() if layout == "chw" else hwc8
     del hwc8
     # the box counts of the map, and the caller's route with them
-    nx = torch.clamp(w - f * torch.arange(ow, device=dev), max=f)
-    ny = torch.clamp(h - f * torch.arange(oh, device=dev), max=f)
-    inv = 1.0 / (ny[:, None] * nx[None, :]).to(torch.float32)
+    if not a.resize:
+        nx = torch.clamp(w - f * torch.arange(ow, device=dev), max=f)
+        ny = torch.clamp(h - f * torch.arange(oh, device=dev), max=f)
+        inv = 1.0 / (ny[:, None] * nx[None, :]).to(torch.float32)
 
     def resized():
         x = (src if layout == "chw" else src.permute(0, 3, 1, 2)).to(torch.float32, memory_format=torch.contiguous_format)
+        if a.resize:
+            return F.interpolate(x, size=(oh, ow), mode="area").add(0.5).floor().clamp(0, 255).to(torch.uint8)
         return F.avg_pool2d(x, f, ceil_mode=True, divisor_override=1).mul(inv).add(0.5).floor().clamp(0, 255).to(torch.uint8)
 
     small_chw = resized()                                                  # [N, 3, oh, ow]
@@ -1062,7 +1084,14 @@ def run_reduce(a, jpegamd, torch, dev) -> None:
         tail = ([o.data_ptr() for o in outs], cap, [sizes.data_ptr() + 8 * i for i in range(n)], stream)
 
         def reduced_call():
-            if a.scan == "progressive":
+            if a.resize:
+                if a.scan == "progressive":
+                    enc.encode_resized_progressive_script_batch_async(rimgs, sub, ow, oh, None, *tail)
+                elif a.scan in ("interleaved", "gray"):
+                    enc.encode_resized_interleaved_batch_async(rimgs, sub, ow, oh, restart, *tail)
+                else:
+                    enc.encode_resized_batch_async(rimgs, sub, ow, oh, *tail)
+            elif a.scan == "progressive":
                 enc.encode_reduced_progressive_script_batch_async(rimgs, sub, f, None, *tail)
             elif a.scan in ("interleaved", "gray"):
                 enc.encode_reduced_interleaved_batch_async(rimgs, sub, f, restart, *tail)
@@ -1089,7 +1118,7 @@ def run_reduce(a, jpegamd, torch, dev) -> None:
                 return lambda: enc.encode_gray_scan_batch_async(descs, restart, *tail)
             return lambda: enc.encode_color_progressive_script_batch_async(descs, sub, None, *tail)
 
-        routes = {"reduced": reduced_call}
+        routes = {front: reduced_call}
         plain = uint8_entry(small, layout)
         if plain is not None:
             routes["uint8"] = plain
@@ -1124,7 +1153,7 @@ def run_reduce(a, jpegamd, torch, dev) -> None:
                 medians[k].append(statistics.median(e0.elapsed_time(e1) for e0, e1 in evs) * 1000.0 / n)
         for k in routes:
             m = medians[k]
-            line = {"source": "uint8", "reduce": f, "layout": layout, "scan": a.scan, "subsampling": name, "route": k, "width": w, "height": h,
+            line = {"source": "uint8", **({"resize": f"{ow}x{oh}"} if a.resize else {"reduce": f}), "layout": layout, "scan": a.scan, "subsampling": name, "route": k, "width": w, "height": h,
                     "reduced_width": ow, "reduced_height": oh, "batch": n, "quality": a.quality, "kind": a.kind, "steps": a.steps,
                     "rounds": a.rounds, "us_per_picture_medians": [round(v, 1) for v in m], "us_per_picture": round(statistics.median(m), 1),
                     "spread_us": round(max(m) - min(m), 1)}
@@ -1132,8 +1161,8 @@ def run_reduce(a, jpegamd, torch, dev) -> None:
                 line.update(source_bytes_per_picture=src.numel() // n, copy_gb_per_s=round(2 * src.numel() / n / statistics.median(m) / 1000, 1))
             else:
                 line.update(bytes=got[k], source_gpixels_per_s=round(w * h / statistics.median(m) / 1000, 2),
-                            ratio_to_reduced=round(statistics.median(m) / statistics.median(medians["reduced"]), 3),
-                            same_sizes_as_reduced=got[k] == got["reduced"])     # (torch divides in float32: exact where n is a power of 2)
+                            **{f"ratio_to_{front}": round(statistics.median(m) / statistics.median(medians[front]), 3),
+                               f"same_sizes_as_{front}": got[k] == got[front]})     # (torch divides in float32: exact where n is a power of 2)
             if a.scan in ("interleaved", "gray"):
                 line.update(restart_interval=restart, huffman=a.huffman or "standard")
             report(a, line)
